@@ -3,7 +3,7 @@
 
 Metric (BASELINE.json): Mtexels/s of BC7 encode, 4096x4096 RGBA8, TEX_COMPRESS_DEFAULT (cfg2).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of DirectX::Compress' hot path (dxtex_compress_device: source resident in HBM, BC7 payload written to
 HBM) over one 4096^2 synthetic image per GPU: SURVEY.md section 8d's cfg2 recipe (directxtex_amd.synth.survey_rgba8, LCG seed
@@ -11,7 +11,12 @@ HBM) over one 4096^2 synthetic image per GPU: SURVEY.md section 8d's cfg2 recipe
 path has no exchange step, so there is no data-path collective: the only collectives are the timing barrier and the MAX over
 ranks). Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, slowest rank). --dump-outputs DIR then also writes what the last
+timed step computed (rank 0's BC7 payload) as DIR/bc7_payload_sample.npy: float32 bytes of a fixed, seeded sample of half of its
+blocks (DUMP_SEED), shape (blocks, 16), 32 MiB. Everything below is measured only with --full.
+
+Extra objects on the line (--full):
   roofline     - dominant kernel: algorithmic bytes per launch / its mean duration (hipEvents on the launch stream, recorded in
                  a separate, untimed profiling pass through dxtex_ctx_profile_*), against 8 TB/s HBM. BC7 at the reference's
                  search depth is VALU-bound, so the HBM fraction is small by design; `valu` gives the kernel's VALU issue
@@ -47,12 +52,22 @@ HBM_PEAK_GBS = 8000.0               # MI355X_MICROARCH.md: 8 TB/s
 PCIE_PEAK_GBS = 63.0                # PCIe 5.0 x16, one direction (MI355X_MICROARCH.md)
 BAND_ROWS = 16                      # block rows per digest band (tests/golden/make_golden_fullsize.py)
 TEX_COMPRESS_PARALLEL = 0x10000000
+DUMP_SEED = 0                       # --dump-outputs: the block sample is the same in every run and build
 
 
 def make_image(rank):
     """4096^2 RGBA8, LCG seed 2 (+ rank: every GPU compresses its own image), opaque."""
     from directxtex_amd import synth
     return synth.survey_rgba8(WIDTH, HEIGHT, 2 + rank, "opaque")
+
+
+def dump_outputs(out_dir, payload):
+    """The BC7 payload of the last timed step as float32 bytes, (blocks, 16), for a seeded half of the 1 048 576 blocks in ascending
+    order: the whole payload as float32 would be 64 MiB, over the 64 MB the dump may take."""
+    blocks = np.ascontiguousarray(payload, np.uint8).reshape(-1, 16)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(blocks.shape[0], blocks.shape[0] // 2, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "bc7_payload_sample.npy"), blocks[pick].astype(np.float32))
 
 
 def hbm_roofline(algo_bytes, ms, kernel=None, traffic=None, time_key="kernel_ms"):
@@ -505,6 +520,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's output under DIR (see the module docstring)")
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else the line can carry: per-kernel times, roofline "
+                    "and PMC counters, parity, CPU baseline, the other workloads (the options below apply to it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-full", action="store_true", help="run the reference on the whole 4096^2 image (about 3.5 min on 128 threads)")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 --pmc child passes for roofline.traffic / roofline.valu (the committed "
@@ -517,6 +535,8 @@ def main():
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo lets several "
                     "ranks share one GPU in the tests)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import directxtex_amd as dx
@@ -563,6 +583,31 @@ def main():
     # whole-job throughput: texels of all ranks / slowest rank's time (no data-path collective anywhere)
     elapsed, texels = sharding.aggregate(elapsed, float(WIDTH) * HEIGHT * args.steps, world, dev)
     value = texels / elapsed / 1e6
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dst.cpu().numpy())
+
+    def finish(line):
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        ctx.close()
+        if distributed:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+
+    headline = {
+        "metric": "Mtexels/s BC7 encode (4096^2 RGBA8, TEX_COMPRESS_DEFAULT)",
+        "value": round(value, 3), "unit": "Mtexels/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "fp32 seed fit + i32 exact error sums (u8 texels in, 128-bit blocks out)", "data": "synthetic",
+        "config": {"workload": "cfg2: 4096x4096 RGBA8 -> BC7_UNORM, TEX_COMPRESS_DEFAULT, one image per GPU, source and "
+                               "payload resident in HBM (dxtex_compress_device)",
+                   "image": "SURVEY.md 8d cfg2 recipe (directxtex_amd.synth.survey_rgba8: LCG gradients + 4-octave noise, flat to noisy blocks), "
+                            "opaque, seed 2+rank",
+                   "sharding": f"image-per-GPU x{n_gpus}, no data-path collective"},
+    }
+    if not args.full:
+        finish(headline)
+        return
 
     # per-kernel durations: a separate, untimed pass with hipEvents around every launch on the launch stream
     ctx.profile_begin()
@@ -830,25 +875,9 @@ def main():
                     cfg5["cpu_baseline_error"] = repr(e)
             extra.setdefault("other_workloads", {})["cfg5_shard"] = cfg5
 
-        line = {
-            "metric": "Mtexels/s BC7 encode (4096^2 RGBA8, TEX_COMPRESS_DEFAULT)",
-            "value": round(value, 3), "unit": "Mtexels/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "fp32 seed fit + i32 exact error sums (u8 texels in, 128-bit blocks out)", "data": "synthetic",
-            "config": {"workload": "cfg2: 4096x4096 RGBA8 -> BC7_UNORM, TEX_COMPRESS_DEFAULT, one image per GPU, source and "
-                                   "payload resident in HBM (dxtex_compress_device)",
-                       "image": "SURVEY.md 8d cfg2 recipe (directxtex_amd.synth.survey_rgba8: LCG gradients + 4-octave noise, flat to noisy blocks), "
-                                "opaque, seed 2+rank",
-                       "sharding": f"image-per-GPU x{n_gpus}, no data-path collective"},
-            "roofline": roof, "cpu_baseline": cpu, "parity": parity,
-        }
-        line.update(extra)
-        print(json.dumps(line), flush=True)
-
-    ctx.close()
-    if distributed:
-        import torch.distributed as dist
-        dist.destroy_process_group()
+        headline.update(roofline=roof, cpu_baseline=cpu, parity=parity)
+        headline.update(extra)
+    finish(headline)
 
 
 if __name__ == "__main__":

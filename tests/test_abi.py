@@ -61,20 +61,16 @@ def test_header_is_plain_c():
 def test_integration_binding_compiles_against_the_reference_headers(tmp_path):
     """The reference-side binding shown in INTEGRATION.md (DirectXTexCompressMI355X.cpp) is real code: the document's snippet is the
     file oracle/binding/DirectXTexCompressMI355X.cpp character for character, and that file compiles against the reference's own
-    headers (in place, with the oracle's stand-ins for its un-vendored dependencies) and include/dxtex_amd.h. oracle/Makefile
-    links it with the reference and the product into oracle/_ref/binding_demo, which tests/test_zz_binding_gpu.py runs on a GPU."""
-    import subprocess
+    headers (in place, with the oracle's stand-ins for its un-vendored dependencies) and include/dxtex_amd.h. build() does that
+    compile: oracle/Makefile builds it and oracle/binding/DirectXTexMI355X.cpp (array Compress, Decompress, mips, Resize, Convert)
+    against those headers and links them with the reference and the product into oracle/_ref/binding_demo, which
+    tests/test_zz_binding_gpu.py runs on a GPU."""
     doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     code = re.search(r"```cpp\n(// DirectXTexCompressMI355X.cpp.*?)```", doc, re.S).group(1)
     path = os.path.join(ROOT, "oracle", "binding", "DirectXTexCompressMI355X.cpp")
     assert open(path).read() == code, "INTEGRATION.md and oracle/binding/DirectXTexCompressMI355X.cpp have drifted apart"
-    ref = "/root/reference/DirectXTex"
-    if not os.path.isdir(ref):
-        pytest.skip("/root/reference absent")
-    for src in (path, os.path.join(ROOT, "oracle", "binding", "DirectXTexMI355X.cpp")):       # the second file: array Compress, Decompress, mips, Resize, Convert
-        r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-w", "-I" + os.path.join(ROOT, "oracle", "shim"), "-I" + ref, "-I" + os.path.join(ROOT, "include"), src],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr[-3000:]
+    demo = os.path.join(ROOT, "oracle", "_ref", "binding_demo")
+    assert os.path.isfile(demo) and os.access(demo, os.X_OK), f"{demo} missing: the binding did not compile and link in __graft_entry__.build()"
 
 
 def test_product_library_reads_no_environment():

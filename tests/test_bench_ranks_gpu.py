@@ -23,7 +23,7 @@ def _free_port():
 def test_two_ranks_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--backend", "gloo", "--no-cpu-baseline", "--cfg5-images", "10"]
+           "--full", "--backend", "gloo", "--no-cpu-baseline", "--cfg5-images", "10"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
