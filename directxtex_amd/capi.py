@@ -83,6 +83,9 @@ _SIGS = {
     "dxtex_compress_many": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float]),
     "dxtex_convert": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_convert_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_convert_slice": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32]),
+    "dxtex_convert_slice_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32]),
+    "dxtex_convert_dither_stats": (ctypes.c_int32, [_ctx_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -429,14 +432,28 @@ class Context:
         arr = (Image * len(levels))(*levels)
         self._check(self._lib.dxtex_generate_mips_device(self._h, arr, len(levels), filter_flags), "generate_mips_device")
 
-    def convert(self, pixels, width, height, src_format, dst_format, filter_flags=0, threshold=0.5):
+    def convert(self, pixels, width, height, src_format, dst_format, filter_flags=0, threshold=0.5, z=0):
+        """DirectX::Convert of one image; filter_flags may carry TEX_FILTER_DITHER (0x10000) / TEX_FILTER_DITHER_DIFFUSION (0x20000).
+        z = the slice of a volume (the phase of ordered dithering; dxtex_convert_slice)."""
         pixels = np.ascontiguousarray(pixels)
         src = _host_image(pixels, width, height, src_format)
         rp, sp = compute_pitch(dst_format, width, height)
         out = np.zeros(sp, np.uint8)
         dst = Image(width, height, dst_format, rp, sp, out.ctypes.data)
-        self._check(self._lib.dxtex_convert(self._h, ctypes.byref(src), ctypes.byref(dst), filter_flags, threshold), "convert")
+        self._check(self._lib.dxtex_convert_slice(self._h, ctypes.byref(src), ctypes.byref(dst), filter_flags, threshold, z), "convert")
         return out
+
+    def convert_device(self, src_ptr, width, height, src_format, dst_ptr, dst_format, filter_flags=0, threshold=0.5, z=0, src_row_pitch=None):
+        """dxtex_convert_slice_device: device pointers (tight destination pitch), asynchronous on the context's stream."""
+        src = device_image(src_ptr, width, height, src_format, src_row_pitch)
+        dst = device_image(dst_ptr, width, height, dst_format)
+        self._check(self._lib.dxtex_convert_slice_device(self._h, ctypes.byref(src), ctypes.byref(dst), filter_flags, threshold, z), "convert_device")
+
+    def convert_dither_stats(self):
+        """(texels the error-diffusion merge re-ran, texels converted with error diffusion), cumulative on this context."""
+        rerun, total = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.dxtex_convert_dither_stats(self._h, ctypes.byref(rerun), ctypes.byref(total)), "convert_dither_stats")
+        return rerun.value, total.value
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

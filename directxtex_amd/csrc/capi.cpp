@@ -55,6 +55,9 @@ struct dxtex_ctx
     void* mseBuf = nullptr; size_t mseBytes = 0;
     // R32G32B32A32_FLOAT rows on their way into a format whose element holds several texels (launch_pack_group)
     void* groupRows = nullptr; size_t groupRowsBytes = 0;
+    // error-diffusion Convert: row buffers (launch_convert_diffuse) and the device counter of texels its merge re-ran
+    void* ditherRows = nullptr; size_t ditherRowsBytes = 0;
+    unsigned long long* ditherRerun = nullptr; uint64_t ditherTexels = 0;
     // dxtex_compress_many (host pointers): double-buffered pinned + device staging, copy streams on either side of ctx->stream
     struct Lane
     {
@@ -301,6 +304,8 @@ void dxtex_ctx_destroy(dxtex_ctx* ctx)
     if (ctx->stageOut) (void)hipFree(ctx->stageOut);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->groupRows) (void)hipFree(ctx->groupRows);
+    if (ctx->ditherRows) (void)hipFree(ctx->ditherRows);
+    if (ctx->ditherRerun) (void)hipFree(ctx->ditherRerun);
     if (ctx->triBuf) (void)hipFree(ctx->triBuf);
     if (ctx->triPinned) (void)hipHostFree(ctx->triPinned);
     if (ctx->triConsumed) (void)hipEventDestroy(ctx->triConsumed);
@@ -890,7 +895,7 @@ dxtex_hresult dxtex_decode_blocks(dxtex_ctx* ctx, int32_t bc_format, const uint8
 // ---- GenerateMipMaps / Resize / Convert ----------------------------------------------------------------------------------
 namespace
 {
-constexpr uint32_t kFilterModeMask = 0xF00000u, kFilterDitherMask = 0xF0000u;
+constexpr uint32_t kFilterModeMask = 0xF00000u, kFilterDitherOrdered = 0x10000u, kFilterDitherDiffusion = 0x20000u;
 inline bool ispow2(size_t x) { return x != 0 && (x & (x - 1)) == 0; }
 
 struct LevelPair { const uint8_t* src; size_t srcPitch, sw, sh; uint8_t* dst; size_t dstPitch, dw, dh; };
@@ -1273,7 +1278,7 @@ dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_i
 
 namespace
 {
-// ConvertEx's checks (DirectXTexConvert.cpp:5107-5125); dithering is not implemented on this path
+// ConvertEx's checks (DirectXTexConvert.cpp:5107-5125)
 dxtex_hresult check_convert(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, ConvertPlan* plan)
 {
     if (!ctx) return DXTEX_E_POINTER;
@@ -1285,15 +1290,45 @@ dxtex_hresult check_convert(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_
     if ((in && (in->cls & FC_BC)) || (out && (out->cls & FC_BC))) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "Convert does not take block-compressed formats");
     if (!in || !out) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "format is not supported by the MI355X path");
     if (src->width != dst->width || src->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
-    if (filter & kFilterDitherMask) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "dithered conversion is not implemented on the MI355X path");
     *plan = resolve_convert_plan(*in, *out, filter);
     return DXTEX_S_OK;
 }
 
-// the conversion kernel, through float rows + the pack kernel when the destination's element holds several texels
+// development knob (libdxtex_amd_dev.so only): texels per speculated segment of the error-diffusion kernel; 0 = its default
+static const uint32_t kDitherSegment = dev_env("DXTEX_DITHER_SEGMENT") ? uint32_t(strtoul(dev_env("DXTEX_DITHER_SEGMENT"), nullptr, 10)) : 0u;
+
+// the conversion kernel, through float rows + the pack kernel when the destination's element holds several texels. ConvertCustom's
+// branches (:4820-4910): TEX_FILTER_DITHER_DIFFUSION first, then TEX_FILTER_DITHER; z is the slice of a volume (ordered dithering's phase).
 dxtex_hresult submit_convert(dxtex_ctx* ctx, const uint8_t* dSrc, size_t srcPitch, int srcFormat, uint8_t* dDst, size_t dstPitch, int dstFormat,
-                             size_t width, size_t height, const ConvertPlan& plan, float threshold)
+                             size_t width, size_t height, const ConvertPlan& basePlan, float threshold, uint32_t filter, uint32_t z)
 {
+    int dither = CONVERT_DITHER_NONE;
+    ConvertPlan plan = basePlan;
+    if ((filter & (kFilterDitherDiffusion | kFilterDitherOrdered)) && dither_spec(dstFormat).valid)
+    {
+        // a dithered store sees ConvertScanline's NaNs as they are (XMVectorClamp keeps them)
+        if (plan.tcv == TCV_CLAMP_SNORM) plan.tcv = TCV_CLAMP_SNORM_NAN;
+        else if (plan.tcv == TCV_X2BIAS_TO_UNORM) plan.tcv = TCV_X2BIAS_TO_UNORM_NAN;
+    }
+    if (filter & kFilterDitherDiffusion)
+    {
+        if (dither_spec(dstFormat).valid)
+        {
+            dxtex_hresult hr = ensure(ctx, &ctx->ditherRows, &ctx->ditherRowsBytes, convert_diffuse_scratch_bytes(uint32_t(width)));
+            if (hr != DXTEX_S_OK) return hr;
+            if (!ctx->ditherRerun)
+            {
+                HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->ditherRerun), sizeof(unsigned long long)));
+                HIP_TRY(ctx, hipMemsetAsync(ctx->ditherRerun, 0, sizeof(unsigned long long), ctx->stream));
+            }
+            ctx->ditherTexels += uint64_t(width) * height;
+            const hipError_t e = launch_convert_diffuse(dSrc, srcPitch, srcFormat, dDst, dstPitch, dstFormat, uint32_t(width), uint32_t(height), plan, threshold,
+                                                        ctx->ditherRows, ctx->ditherRerun, kDitherSegment, ctx->stream);
+            return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        }
+        dither = CONVERT_DITHER_ZERO_ERROR;      // no dithered store: StoreScanline after the zero error row
+    }
+    else if (filter & kFilterDitherOrdered) dither = CONVERT_DITHER_ORDERED;
     uint8_t* out = dDst; size_t outPitch = dstPitch; int outFormat = dstFormat;
     const bool grouped = is_group_format(dstFormat);
     if (grouped)
@@ -1302,25 +1337,51 @@ dxtex_hresult submit_convert(dxtex_ctx* ctx, const uint8_t* dSrc, size_t srcPitc
         if (hr != DXTEX_S_OK) return hr;
         outFormat = FMT_R32G32B32A32_FLOAT;
     }
-    hipError_t e = launch_convert(dSrc, srcPitch, srcFormat, out, outPitch, outFormat, uint32_t(width), uint32_t(height), plan, threshold, ctx->stream);
+    hipError_t e = launch_convert(dSrc, srcPitch, srcFormat, out, outPitch, outFormat, uint32_t(width), uint32_t(height), plan, threshold, ctx->stream,
+                                  dither, z);
     if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dDst, dstPitch, dstFormat, uint32_t(width), uint32_t(height), ctx->stream);
     return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
 }
 } // namespace
 
-dxtex_hresult dxtex_convert_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold)
+dxtex_hresult dxtex_convert_slice_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold, uint32_t z)
 {
     ConvertPlan plan;
     dxtex_hresult hr = check_convert(ctx, src, dst, filter, &plan);
     if (hr != DXTEX_S_OK) return hr;
     ScopedDevice sd(ctx->device);
     time_begin(ctx);
-    hr = submit_convert(ctx, src->pixels, src->rowPitch, src->format, dst->pixels, dst->rowPitch, dst->format, src->width, src->height, plan, threshold);
+    hr = submit_convert(ctx, src->pixels, src->rowPitch, src->format, dst->pixels, dst->rowPitch, dst->format, src->width, src->height, plan, threshold,
+                        filter, z);
     time_end(ctx);
     return hr;
 }
 
+dxtex_hresult dxtex_convert_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold)
+{
+    return dxtex_convert_slice_device(ctx, src, dst, filter, threshold, 0);
+}
+
 dxtex_hresult dxtex_convert(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold)
+{
+    return dxtex_convert_slice(ctx, src, dst, filter, threshold, 0);
+}
+
+dxtex_hresult dxtex_convert_dither_stats(dxtex_ctx* ctx, uint64_t* rerunTexels, uint64_t* texels)
+{
+    if (!ctx || !rerunTexels || !texels) return DXTEX_E_POINTER;
+    ScopedDevice sd(ctx->device);
+    unsigned long long n = 0;
+    if (ctx->ditherRerun)
+    {
+        HIP_TRY(ctx, counted_copy(ctx, &n, ctx->ditherRerun, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *rerunTexels = n; *texels = ctx->ditherTexels;
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_convert_slice(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold, uint32_t z)
 {
     ConvertPlan plan;
     dxtex_hresult hr = check_convert(ctx, src, dst, filter, &plan);
@@ -1333,7 +1394,7 @@ dxtex_hresult dxtex_convert(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_
     HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, src->pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
     time_begin(ctx);
     hr = submit_convert(ctx, static_cast<const uint8_t*>(ctx->stageIn), src->rowPitch, src->format, static_cast<uint8_t*>(ctx->stageOut),
-                        dst->rowPitch, dst->format, src->width, src->height, plan, threshold);
+                        dst->rowPitch, dst->format, src->width, src->height, plan, threshold, filter, z);
     time_end(ctx);
     if (hr != DXTEX_S_OK) return hr;
     HIP_TRY(ctx, counted_copy(ctx, dst->pixels, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));

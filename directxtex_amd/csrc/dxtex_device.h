@@ -76,6 +76,10 @@ enum : int
     TCV_SNORM_TO_UNORM = 4,  // SNORM -> UNORM  v*0.5 + 0.5 (:3457-3463)
     TCV_X2BIAS_TO_UNORM = 5, // FLOAT -> UNORM with TEX_FILTER_FLOAT_X2BIAS: clamp(v,-1,1)*0.5 + 0.5 (:3469-3477)
     TCV_SAT_TO_SNORM = 6,    // positive-only FLOAT (x2 bias) -> SNORM / FLOAT: saturate(v)*2 + -1 (:3506-3515, :3549-3561)
+    // TCV_CLAMP_SNORM / TCV_X2BIAS_TO_UNORM with XMVectorClamp's NaN rule (maxps(-1, v): a NaN survives). The undithered stores map
+    // a NaN like the -1 the two codes above leave; the dithered stores (dxtex_dither.h) need the NaN itself.
+    TCV_CLAMP_SNORM_NAN = 7,
+    TCV_X2BIAS_TO_UNORM_NAN = 8,
 };
 enum : int
 {
@@ -476,6 +480,8 @@ __device__ __forceinline__ float tcv1(float v, int tcv)
     case TCV_SNORM_TO_UNORM: return v * 0.5f + 0.5f;
     case TCV_X2BIAS_TO_UNORM: { float m = (v > -1.0f) ? v : -1.0f; m = (m < 1.0f) ? m : 1.0f; return m * 0.5f + 0.5f; }
     case TCV_SAT_TO_SNORM: { float m = (v > 0.0f) ? v : 0.0f; m = (m < 1.0f) ? m : 1.0f; return m * 2.0f + -1.0f; }
+    case TCV_CLAMP_SNORM_NAN: { float m = (-1.0f > v) ? -1.0f : v; return (1.0f < m) ? 1.0f : m; }
+    case TCV_X2BIAS_TO_UNORM_NAN: { float m = (-1.0f > v) ? -1.0f : v; m = (1.0f < m) ? 1.0f : m; return m * 0.5f + 0.5f; }
     default: return v;
     }
 }

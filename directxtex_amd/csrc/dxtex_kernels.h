@@ -48,9 +48,20 @@ struct ConvertPlan;
 hipError_t launch_bc_decode(const uint8_t* src, uint64_t srcRowPitch, int srcFormat, uint8_t* dst, uint64_t dstRowPitch, int dstFormat,
                             uint32_t width, uint32_t height, const ConvertPlan& plan, hipStream_t stream);
 
-// Convert (ConvertCustom without dithering): same size, different format.
+// Convert (ConvertCustom): same size, different format. dither = CONVERT_DITHER_*: ORDERED applies StoreScanlineDither's ordered branch
+// (rows counted from the top of the given image, slice z); ZERO_ERROR adds the zero error row of the diffusion branch before a store
+// that does not dither (the formats dither_spec() marks invalid).
+enum : int { CONVERT_DITHER_NONE = 0, CONVERT_DITHER_ORDERED = 1, CONVERT_DITHER_ZERO_ERROR = 2 };
 hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream);
+                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream,
+                          int dither = CONVERT_DITHER_NONE, uint32_t z = 0);
+// Error-diffusion Convert of one image (a destination format with a dithered store) in one workgroup; `scratch` holds
+// convert_diffuse_scratch_bytes(width) bytes of device memory; the texels the merge re-ran are added to *rerun (device memory).
+// segLen = texels per speculated segment of a row (0: the default).
+size_t convert_diffuse_scratch_bytes(uint32_t width);
+hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
+                                  uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, void* scratch,
+                                  unsigned long long* rerun, uint32_t segLen, hipStream_t stream);
 
 // Resize / one mip level. filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row

@@ -14,6 +14,7 @@
 //                     to +-65504 (:1695-1699).
 #pragma once
 #include "dxtex_device.h"
+#include "dxtex_dither.h"
 
 namespace dxtex
 {
@@ -465,6 +466,15 @@ __device__ __forceinline__ void store_texel(uint8_t* row, uint32_t x, int format
     default:
         break;
     }
+}
+
+// StoreScanlineDither's ordered branch (DirectXTexConvert.cpp:4096-4101 and the per-format cases) for one texel: element `idx` of `row`,
+// at column x, row y of the image and slice z. Formats without a dithered store take store_texel (:4559-4560).
+__device__ __forceinline__ void store_texel_dither(uint8_t* row, uint32_t idx, int format, const Texel& t, float threshold, uint32_t x, uint32_t y, uint32_t z)
+{
+    const DitherSpec s = dither_spec(format);
+    if (!s.valid) { store_texel(row, idx, format, t, threshold); return; }
+    dither_write(row, idx, s.bytes, dither_ordered(s, t.r, t.g, t.b, t.a, x, y, z, threshold));
 }
 
 // ---- formats whose memory element holds more than one texel (FC_GROUP): one element from its texels ------------------------------

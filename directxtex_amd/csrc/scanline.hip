@@ -1,7 +1,9 @@
 // Scanline-layer kernels for gfx950: Convert, Resize / GenerateMipMaps filters, ComputeMSE.
 //
 //   reference                                                             here
-//   ConvertCustom (DirectXTexConvert.cpp:4804-4913, no-dither branch)      convert_kernel
+//   ConvertCustom (DirectXTexConvert.cpp:4804-4913), no-dither and         convert_kernel / convert_quad_kernel
+//     ordered-dither branches (StoreScanlineDither without an error buffer)
+//   ConvertCustom's error-diffusion branch (:4820-4852)                   convert_diffuse_kernel (one workgroup per image)
 //   Resize{Point,Box,Linear,Cubic,Triangle}Filter (DirectXTexResize.cpp:255-803) and
 //   Generate2DMips{Point,Box,Linear,Cubic,Triangle}Filter (DirectXTexMipmaps.cpp:907-1602)   resize_*_kernel
 //   ComputeMSE_ (DirectXTexMisc.cpp:27-176)                                mse_kernel
@@ -61,14 +63,27 @@ __device__ __forceinline__ void store_linear(const ImgView& v, uint32_t x, uint3
 // Rows are the grid's y dimension, which HIP limits to 65535: taller images wrap (grid_rows() caps the launch, the kernels stride).
 __host__ __device__ inline uint32_t grid_rows(uint32_t height) { return height < 65535u ? height : 65535u; }
 
-__global__ void __launch_bounds__(256) convert_kernel(ImgView src, ImgView dst, ConvertPlan plan, float threshold)
+// The converted texel to the destination: StoreScanline, StoreScanlineDither's ordered branch, or StoreScanline after the zero error
+// row of the diffusion branch (:4073-4092: v + 0.0f, which turns -0.0f into +0.0f) for a format without a dithered store. DITHER is a
+// template argument so that the undithered kernels stay the code they were (a run-time mode word cost them 7-15 %).
+template<bool DITHER>
+__device__ __forceinline__ void store_converted(uint8_t* row, uint32_t idx, int format, Texel t, float threshold, int dither, uint32_t x, uint32_t y, uint32_t z)
+{
+    if constexpr (!DITHER) { store_texel(row, idx, format, t, threshold); return; }
+    if (dither == CONVERT_DITHER_ORDERED) { store_texel_dither(row, idx, format, t, threshold, x, y, z); return; }
+    if (dither == CONVERT_DITHER_ZERO_ERROR) { t.r = t.r + 0.0f; t.g = t.g + 0.0f; t.b = t.b + 0.0f; t.a = t.a + 0.0f; }
+    store_texel(row, idx, format, t, threshold);
+}
+
+template<bool DITHER>
+__global__ void __launch_bounds__(256) convert_kernel(ImgView src, ImgView dst, ConvertPlan plan, float threshold, int dither, uint32_t z)
 {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
     if (x >= src.width) return;
     for (uint32_t y = blockIdx.y; y < src.height; y += gridDim.y)
     {
         const Texel t = load_texel(src.pixels + uint64_t(y) * src.rowPitch, x, src.format);
-        store_texel(dst.pixels + uint64_t(y) * dst.rowPitch, x, dst.format, apply_plan(t, plan), threshold);
+        store_converted<DITHER>(dst.pixels + uint64_t(y) * dst.rowPitch, x, dst.format, apply_plan(t, plan), threshold, dither, x, y, z);
     }
 }
 
@@ -134,8 +149,9 @@ __device__ __forceinline__ void store_quad(uint8_t* p, const uint32_t (&q)[W], u
 // SQ / DQ = bytes of a source / destination quad (16, 32 or 64; 0 = taken from the arguments: the 48-byte R32G32B32 quads).
 // ROWS quads (of consecutive rows, same columns) are loaded before the first is converted, so that a lane keeps 64 bytes of
 // reads in flight: with one 16-byte load per lane the kernel was bound by latency x occupancy (Little's law), not by HBM.
-template<int SQ, int DQ, int ROWS>
-__global__ void __launch_bounds__(256) convert_quad_kernel(ImgView src, ImgView dst, ConvertPlan plan, float threshold, uint32_t srcQuadBytes, uint32_t dstQuadBytes)
+template<int SQ, int DQ, int ROWS, bool DITHER>
+__global__ void __launch_bounds__(256) convert_quad_kernel(ImgView src, ImgView dst, ConvertPlan plan, float threshold, uint32_t srcQuadBytes, uint32_t dstQuadBytes,
+                                                           int dither, uint32_t z)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q * 4u >= src.width) return;
@@ -175,7 +191,8 @@ __global__ void __launch_bounds__(256) convert_quad_kernel(ImgView src, ImgView 
             for (uint32_t k = 0; k < 4u; ++k) tx[k] = apply_plan(tx[k], plan);
             switch (dst.format)
             {
-#define DXTEX_QCASE(F, QB) case F: if constexpr (DQ == QB || (DQ == 0 && QB > 0)) { _Pragma("unroll") for (uint32_t k = 0; k < 4u; ++k) store_texel(reinterpret_cast<uint8_t*>(out), k, F, tx[k], threshold); } break;
+#define DXTEX_QCASE(F, QB) case F: if constexpr (DQ == QB || (DQ == 0 && QB > 0)) { _Pragma("unroll") for (uint32_t k = 0; k < 4u; ++k) \
+                store_converted<DITHER>(reinterpret_cast<uint8_t*>(out), k, F, tx[k], threshold, dither, q * 4u + k, y0 + uint32_t(r), z); } break;
                 DXTEX_QUAD_FORMATS(DXTEX_QCASE)
 #undef DXTEX_QCASE
             default: break;
@@ -184,6 +201,83 @@ __global__ void __launch_bounds__(256) convert_quad_kernel(ImgView src, ImgView 
                 store_quad<DW>(dst.pixels + uint64_t(y0 + uint32_t(r)) * dst.rowPitch + uint64_t(q) * dq, out, dq);
         }
     }
+}
+
+// ---- Convert with error diffusion (ConvertCustom's TEX_FILTER_DITHER_DIFFUSION branch, :4820-4852) ---------------------------------------
+// One workgroup walks the rows of one image. Per row: every lane loads, converts, adds the previous row's error slots and pre-steps texels
+// (stored by processing position: even rows left to right, odd rows right to left); then the vError chain runs as segments of segLen
+// positions, one per lane, first from vError = 0 and then re-run from the exact incoming state until each merges with its stored run
+// (dxtex_dither.h: dither_row_segmented is the same scheme written serially); then every lane builds slots of the next row's error buffer.
+// The chain reads the pre-stepped texels and reads / writes the divided errors once per step: they sit in LDS for rows of up to
+// kDiffuseLdsTexels texels (2 x 64 KiB) and in device memory for wider rows (a 16384-texel row needs 256 KiB per buffer). The error
+// slots and the per-segment states stay in device memory: the parallel phases touch them once per row.
+constexpr uint32_t kDiffuseThreads = 1024;
+constexpr uint32_t kDiffuseMinSeg = 16;         // shorter segments leave the chain's merge distance (~15-30 texels on 8-bit data) to extra rounds
+constexpr uint32_t kDiffuseLdsTexels = 4096;
+
+struct DiffuseArgs
+{
+    ImgView src, dst;
+    ConvertPlan plan;
+    DitherSpec spec;
+    float threshold;
+    uint32_t segLen;
+    F4 *pre, *err, *slot, *in, *pending;
+    unsigned long long* rerun;
+};
+
+template<bool LDS>
+__global__ void __launch_bounds__(kDiffuseThreads) convert_diffuse_kernel(DiffuseArgs a)
+{
+    if constexpr (LDS)
+    {
+        __shared__ F4 rows[2 * kDiffuseLdsTexels];
+        a.pre = rows; a.err = rows + kDiffuseLdsTexels;
+    }
+    const uint32_t n = a.src.width, L = a.segLen, nseg = (n + L - 1) / L;
+    const F4 zero = { { 0.0f, 0.0f, 0.0f, 0.0f } };
+    const DitherSpec& s = a.spec;
+    for (uint32_t x = threadIdx.x; x < n; x += blockDim.x) a.slot[x] = zero;
+    unsigned long long rerun = 0;
+    for (uint32_t y = 0; y < a.src.height; ++y)
+    {
+        const bool odd = (y & 1u) != 0;
+        const uint8_t* srow = a.src.pixels + uint64_t(y) * a.src.rowPitch;
+        uint8_t* drow = a.dst.pixels + uint64_t(y) * a.dst.rowPitch;
+        for (uint32_t x = threadIdx.x; x < n; x += blockDim.x)
+        {
+            Texel t = apply_plan(load_texel(srow, x, a.src.format), a.plan);
+            const F4 e = a.slot[x];
+            t.r = t.r + e.v[0]; t.g = t.g + e.v[1]; t.b = t.b + e.v[2]; t.a = t.a + e.v[3];       // :4073-4086
+            a.pre[odd ? n - 1u - x : x] = dither_pre(s, t.r, t.g, t.b, t.a);
+        }
+        __syncthreads();
+        const auto out = [&](uint32_t p, uint64_t w) { dither_write(drow, odd ? n - 1u - p : p, s.bytes, w); };
+        for (uint32_t k = threadIdx.x; k < nseg; k += blockDim.x)
+        {
+            a.in[k] = zero;
+            dither_segment(s, a.pre, a.err, k * L, min((k + 1u) * L, n), zero, false, a.threshold, out);
+        }
+        for (;;)
+        {
+            __syncthreads();
+            for (uint32_t k = threadIdx.x; k < nseg; k += blockDim.x)
+                if (k) a.pending[k] = dither_seg_input(a.err, k, L);
+            __syncthreads();
+            int changed = 0;
+            for (uint32_t k = threadIdx.x; k < nseg; k += blockDim.x)
+            {
+                if (!k || dither_same(s, a.pending[k], a.in[k])) continue;
+                a.in[k] = a.pending[k];
+                rerun += dither_segment(s, a.pre, a.err, k * L, min((k + 1u) * L, n), a.in[k], true, a.threshold, out);
+                changed = 1;
+            }
+            if (!__syncthreads_or(changed)) break;
+        }
+        for (uint32_t x = threadIdx.x; x < n; x += blockDim.x) a.slot[x] = dither_slot(a.err, odd ? n - 1u - x : x, n);
+        __syncthreads();
+    }
+    if (rerun) atomicAdd(a.rerun, rerun);
 }
 
 // ---- PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205): rgb * a, or rgb / a where a > 0, in linear space ------------
@@ -957,7 +1051,7 @@ hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* d
 }
 
 hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream)
+                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream, int dither, uint32_t z)
 {
     if (!width || !height) return hipSuccess;
     const FmtInfo* in = format_info(srcFormat);
@@ -973,7 +1067,8 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
         // row groups per workgroup column: enough workgroups to fill 256 CUs several times over, few enough that a lane streams several groups
 #define DXTEX_QUAD(SQ, DQ, ROWS) do { const uint32_t groups = (height + (ROWS) - 1u) / (ROWS); \
             const uint32_t gy = std::min<uint32_t>(groups, std::max<uint32_t>(1u, 8192u / gx)); \
-            hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq); } while (0)
+            if (dither) hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS, true>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq, dither, z); \
+            else hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS, false>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq, dither, z); } while (0)
         if (sq == 16u && dq == 16u) DXTEX_QUAD(16, 16, 4);
         else if (sq == 16u && dq == 32u) DXTEX_QUAD(16, 32, 4);
         else if (sq == 16u && dq == 64u) DXTEX_QUAD(16, 64, 4);
@@ -986,8 +1081,35 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
 #undef DXTEX_QUAD
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(convert_kernel, dim3((width + 255) / 256, grid_rows(height)), dim3(256), 0, stream,
-                       make_view(src, srcPitch, width, height, srcFormat), make_view(dst, dstPitch, width, height, dstFormat), plan, threshold);
+    const ImgView sv = make_view(src, srcPitch, width, height, srcFormat), dv = make_view(dst, dstPitch, width, height, dstFormat);
+    const dim3 grid((width + 255) / 256, grid_rows(height));
+    if (dither) hipLaunchKernelGGL(convert_kernel<true>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z);
+    else hipLaunchKernelGGL(convert_kernel<false>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z);
+    return hipGetLastError();
+}
+
+size_t convert_diffuse_scratch_bytes(uint32_t width)
+{
+    return size_t(5) * width * sizeof(F4);      // pre, err, slot by texel; in, pending by segment (at most one per texel)
+}
+
+hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
+                                  uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, void* scratch,
+                                  unsigned long long* rerun, uint32_t segLen, hipStream_t stream)
+{
+    if (!width || !height) return hipSuccess;
+    DiffuseArgs a;
+    a.spec = dither_spec(dstFormat);
+    if (!a.spec.valid) return hipErrorInvalidValue;
+    a.src = make_view(src, srcPitch, width, height, srcFormat);
+    a.dst = make_view(dst, dstPitch, width, height, dstFormat);
+    a.plan = plan; a.threshold = threshold;
+    a.segLen = segLen ? segLen : std::max<uint32_t>(kDiffuseMinSeg, (width + kDiffuseThreads - 1) / kDiffuseThreads);
+    a.rerun = rerun;
+    F4* f = static_cast<F4*>(scratch);
+    a.pre = f; a.err = f + width; a.slot = f + 2 * size_t(width); a.in = f + 3 * size_t(width); a.pending = f + 4 * size_t(width);
+    if (width <= kDiffuseLdsTexels) hipLaunchKernelGGL(convert_diffuse_kernel<true>, dim3(1), dim3(kDiffuseThreads), 0, stream, a);
+    else hipLaunchKernelGGL(convert_diffuse_kernel<false>, dim3(1), dim3(kDiffuseThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -645,6 +645,7 @@ struct HostSpace
     static HRESULT Mips3D(dxtex_ctx* c, const dxtex_volume* l, size_t n, uint32_t f) noexcept { return dxtex_generate_mips3d(c, l, n, f); }
     static HRESULT Resize(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f) noexcept { return dxtex_resize(c, s, d, f); }
     static HRESULT Convert(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t) noexcept { return dxtex_convert(c, s, d, f, t); }
+    static HRESULT ConvertSlice(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t, uint32_t z) noexcept { return dxtex_convert_slice(c, s, d, f, t, z); }
     static HRESULT PMAlpha(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f) noexcept { return dxtex_premultiply_alpha(c, s, d, f); }
     static HRESULT Coverage(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, size_t n, float r) noexcept { return dxtex_scale_mips_alpha_for_coverage(c, s, d, n, r); }
     static HRESULT CopyRows(dxtex_ctx*, uint8_t* dst, size_t dstPitch, const uint8_t* src, size_t srcPitch, size_t rowBytes, size_t rows) noexcept
@@ -663,6 +664,7 @@ struct DeviceSpace
     static HRESULT Mips3D(dxtex_ctx* c, const dxtex_volume* l, size_t n, uint32_t f) noexcept { return dxtex_generate_mips3d_device(c, l, n, f); }
     static HRESULT Resize(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f) noexcept { return dxtex_resize_device(c, s, d, f); }
     static HRESULT Convert(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t) noexcept { return dxtex_convert_device(c, s, d, f, t); }
+    static HRESULT ConvertSlice(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t, uint32_t z) noexcept { return dxtex_convert_slice_device(c, s, d, f, t, z); }
     static HRESULT PMAlpha(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f) noexcept { return dxtex_premultiply_alpha_device(c, s, d, f); }
     static HRESULT Coverage(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, size_t n, float r) noexcept { return dxtex_scale_mips_alpha_for_coverage_device(c, s, d, n, r); }
     static HRESULT CopyRows(dxtex_ctx* c, uint8_t* dst, size_t dstPitch, const uint8_t* src, size_t srcPitch, size_t rowBytes, size_t rows) noexcept
@@ -1114,13 +1116,17 @@ HRESULT Resize(Device& device, const Image* srcImages, size_t nimages, const Tex
 // ---- Convert (ConvertEx, DirectXTexConvert.cpp:5107-5176) ---------------------------------------------------------------------------
 namespace
 {
-// rows are independent in Convert (dither is out of scope), so progress / cancel works on bands of rows (the per-row
-// callbacks of ConvertCustom, DirectXTexConvert.cpp:4834-4896)
+// Progress / cancel works on bands of rows (the per-row callbacks of ConvertCustom, DirectXTexConvert.cpp:4834-4896). Rows are
+// independent without dithering; ordered dithering reads the row index mod 4, so its bands are whole multiples of 4 rows and each band's
+// first row has the phase of the image row it is. Error diffusion carries an error row from each row to the next: the image is submitted
+// whole, and the callback runs only at row 0 and at the end (ConvertEx's own calls).
 constexpr size_t kBandTexels = size_t(1) << 24;
 
 HRESULT ConvertBands(Device& device, const Image& src, const Image& dst, const ConvertOptions& options, const StatusCallback& statusCallback)
 {
-    const size_t bandRows = std::max<size_t>(1, BandSize(device.ProgressBandTexels(), kBandTexels) / std::max<size_t>(1, src.width));
+    size_t bandRows = std::max<size_t>(1, BandSize(device.ProgressBandTexels(), kBandTexels) / std::max<size_t>(1, src.width));
+    if (options.filter & TEX_FILTER_DITHER_DIFFUSION) bandRows = std::max<size_t>(1, src.height);
+    else if (options.filter & TEX_FILTER_DITHER) bandRows = (bandRows + 3) & ~size_t(3);
     for (size_t y = 0; y < src.height; y += bandRows)
     {
         if (y && !statusCallback(y, src.height)) return E_ABORT;
@@ -1186,15 +1192,19 @@ HRESULT ConvertArrayT(Device& device, const Image* srcImages, size_t nimages, co
     const Image* dest = result.GetImages();
     if (!dest) { result.Release(); return E_POINTER; }
     if (statusCallback && !statusCallback(0, nimages)) { result.Release(); return E_ABORT; }
+    // ConvertCustom's z (:5330-5365): the slice within its mip level for a volume, 0 for every other image (the phase of ordered dithering)
+    size_t slice = 0, levelDepth = metadata.IsVolumemap() ? std::max<size_t>(1, metadata.depth) : 0;
     for (size_t i = 0; i < nimages; ++i)
     {
+        const uint32_t z = uint32_t(slice);
+        if (levelDepth && ++slice >= levelDepth) { slice = 0; levelDepth = std::max<size_t>(1, levelDepth >> 1); }
         const Image& src = srcImages[i];
         if (src.format != metadata.format) { result.Release(); return E_FAIL; }
         if (src.width > UINT32_MAX || src.height > UINT32_MAX) { result.Release(); return E_FAIL; }
         if (src.width != dest[i].width || src.height != dest[i].height) { result.Release(); return E_FAIL; }
         if (!src.pixels) { result.Release(); return E_POINTER; }
         const dxtex_image s = View(src), d = View(dest[i]);
-        hr = Space::Convert(device.Get(), &s, &d, uint32_t(options.filter), options.threshold);
+        hr = Space::ConvertSlice(device.Get(), &s, &d, uint32_t(options.filter), options.threshold, z);
         if (FAILED(hr)) { result.Release(); return hr; }
         if (statusCallback && !statusCallback(i, nimages)) { result.Release(); return E_ABORT; }
     }

@@ -187,8 +187,25 @@ typedef struct dxtex_volume
 dxtex_hresult dxtex_generate_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nlevels, uint32_t filter);
 dxtex_hresult dxtex_generate_mips3d_device(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nlevels, uint32_t filter);
 
+/* Convert = ConvertCustom (DirectXTexConvert.cpp:4804-4913), all three of its branches, byte for byte:
+ *   TEX_FILTER_DITHER_DIFFUSION (0x20000, checked first: with both bits set diffusion runs): Floyd-Steinberg error diffusion
+ *     (StoreScanlineDither with an error buffer): serpentine rows (even rows left to right, odd rows right to left), 7/16 of a texel's
+ *     divided error to the next texel of its row, 3/16, 5/16, 1/16 to the next row; vError restarts at zero on every row. One GPU
+ *     workgroup per image, exact for every input (the serial chain is run as speculated segments merged exactly, see dxtex_dither.h).
+ *   TEX_FILTER_DITHER (0x10000): ordered dithering, offset g_Dither[(z & 3) + (y & 3) * 8 + (x & 3)] with y the row within the image.
+ *   Destination formats with a dithered store: R16G16B16A16_{UNORM,UINT,SNORM,SINT}, R10G10B10A2_{UNORM,UINT}, R10G10B10_XR_BIAS_A2_UNORM,
+ *   R8G8B8A8_{UNORM,UNORM_SRGB,UINT,SNORM,SINT}, R16G16_*, D24_UNORM_S8_UINT, R8G8_*, D16_UNORM, R16_*, R8_*, A8_UNORM, B5G6R5_UNORM,
+ *   B5G5R5A1_UNORM, B8G8R8A8_UNORM[_SRGB], B8G8R8X8_UNORM[_SRGB] (X written as 0), B4G4R4A4_UNORM, A4B4G4R4_UNORM. Every other
+ *   format is stored undithered; under diffusion after the zero error row was added (so -0.0 becomes +0.0 in float destinations).
+ * dxtex_convert[_device] are slice 0; dxtex_convert_slice[_device] take the slice z of a volume (0..depth-1 within its mip level),
+ * which only ordered dithering reads. */
 dxtex_hresult dxtex_convert(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold);
 dxtex_hresult dxtex_convert_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold);
+dxtex_hresult dxtex_convert_slice(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold, uint32_t z);
+dxtex_hresult dxtex_convert_slice_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold, uint32_t z);
+/* Diagnostics of error diffusion on this context, cumulative: texels converted with diffusion into a dithered format, and how many of
+ * them the exact merge had to run a second (or further) time. Waits for the context's stream (copies 8 bytes to the host). */
+dxtex_hresult dxtex_convert_dither_stats(dxtex_ctx* ctx, uint64_t* rerunTexels, uint64_t* texels);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
