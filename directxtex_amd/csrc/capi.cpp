@@ -33,6 +33,24 @@ struct Marks final : dxtex::KernelMarks
     void mark(const char* kernelName) override;
     void reset() { names.clear(); used = 0; }
 };
+
+// A grow-only buffer of the context, device (hipMalloc) or pinned host memory (hipHostMalloc). grow() keeps an allocation that is large
+// enough and otherwise replaces it with one of max(need, minBytes) bytes; the destructor frees it (dxtex_ctx_destroy deletes the context
+// once every stream that used it has drained).
+template<bool Pinned>
+struct GrowBuf
+{
+    void* p = nullptr;
+    size_t bytes = 0;
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf&) = delete;
+    GrowBuf& operator=(const GrowBuf&) = delete;
+    ~GrowBuf() { if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p)); }
+    dxtex_hresult grow(dxtex_ctx* ctx, size_t need, size_t minBytes = 1u << 20);
+    uint8_t* u8() const { return static_cast<uint8_t*>(p); }
+};
+using DeviceBuf = GrowBuf<false>;
+using PinnedBuf = GrowBuf<true>;
 }
 
 struct dxtex_ctx
@@ -43,26 +61,24 @@ struct dxtex_ctx
     hipEvent_t evStart = nullptr, evStop = nullptr;
     float lastKernelMs = -1.0f;
     bool timing = false;
-    // grow-only device staging for the host-pointer entry points
-    void* stageIn = nullptr; size_t stageInBytes = 0;
-    void* stageOut = nullptr; size_t stageOutBytes = 0;
-    // grow-only device scratch for the multi-kernel BC6H/BC7 search (per-mode candidates)
-    void* scratch = nullptr; size_t scratchBytes = 0;
+    // staging for the host-pointer entry points
+    DeviceBuf stageIn, stageOut;
+    // the multi-kernel BC6H/BC7 search (per-mode candidates)
+    DeviceBuf scratch;
     // triangle-filter gather tables (host copies stay alive until the next call: the upload is stream-ordered)
-    void* triBuf = nullptr; size_t triBytes = 0;
+    DeviceBuf triBuf;
     std::vector<uint8_t> triHost;
-    void* triPinned = nullptr; size_t triPinnedBytes = 0; hipEvent_t triConsumed = nullptr; bool triPending = false;
-    void* mseBuf = nullptr; size_t mseBytes = 0;
+    PinnedBuf triPinned; hipEvent_t triConsumed = nullptr; bool triPending = false;
+    DeviceBuf mseBuf;
     // R32G32B32A32_FLOAT rows on their way into a format whose element holds several texels (launch_pack_group)
-    void* groupRows = nullptr; size_t groupRowsBytes = 0;
+    DeviceBuf groupRows;
     // error-diffusion Convert: row buffers (launch_convert_diffuse) and the device counter of texels its merge re-ran
-    void* ditherRows = nullptr; size_t ditherRowsBytes = 0;
-    unsigned long long* ditherRerun = nullptr; uint64_t ditherTexels = 0;
+    DeviceBuf ditherRows, ditherRerun; uint64_t ditherTexels = 0;
     // dxtex_compress_many (host pointers): double-buffered pinned + device staging, copy streams on either side of ctx->stream
     struct Lane
     {
-        void* pinIn = nullptr; size_t pinInBytes = 0; void* pinOut = nullptr; size_t pinOutBytes = 0;
-        void* devIn = nullptr; size_t devInBytes = 0; void* devOut = nullptr; size_t devOutBytes = 0;
+        PinnedBuf pinIn, pinOut;
+        DeviceBuf devIn, devOut;
         hipEvent_t uploaded = nullptr, computed = nullptr, downloaded = nullptr;
     } lane[2];
     hipStream_t h2d = nullptr, d2h = nullptr;
@@ -111,15 +127,29 @@ inline hipError_t counted_copy(dxtex_ctx* ctx, void* dst, const void* src, size_
 
 #define HIP_TRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, (e_ == hipErrorOutOfMemory) ? DXTEX_E_OUTOFMEMORY : DXTEX_E_FAIL, #expr, e_); } while (0)
 
-dxtex_hresult ensure(dxtex_ctx* ctx, void** buf, size_t* have, size_t need)
+template<bool Pinned>
+dxtex_hresult GrowBuf<Pinned>::grow(dxtex_ctx* ctx, size_t need, size_t minBytes)
 {
-    if (*have >= need) return DXTEX_S_OK;
-    if (*buf) { HIP_TRY(ctx, hipFree(*buf)); *buf = nullptr; *have = 0; }
-    const size_t bytes = std::max<size_t>(need, 1u << 20);
-    HIP_TRY(ctx, hipMalloc(buf, bytes));
-    *have = bytes;
+    if (bytes >= need) return DXTEX_S_OK;
+    if (p) { HIP_TRY(ctx, Pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; bytes = 0; }
+    const size_t want = std::max(need, minBytes);
+    HIP_TRY(ctx, Pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want));
+    bytes = want;
     return DXTEX_S_OK;
 }
+
+inline size_t align256(size_t bytes) { return (bytes + 255) & ~size_t(255); }
+
+// Consecutive parts of one allocation, each 256-byte aligned: their offsets and the bytes the allocation needs
+struct Arena
+{
+    std::vector<size_t> at;
+    size_t total = 0;
+    Arena(const size_t* bytes, size_t n) { for (size_t i = 0; i < n; ++i) { at.push_back(total); total += align256(bytes[i]); } }
+};
+
+// a copy of an image whose pixels are elsewhere (in the context's staging)
+dxtex_image with_pixels(const dxtex_image& im, uint8_t* pixels) { dxtex_image o = im; o.pixels = pixels; return o; }
 
 struct ScopedDevice
 {
@@ -149,7 +179,7 @@ void time_end(dxtex_ctx* ctx) { if (!kNoTiming) { (void)hipEventRecord(ctx->evSt
 
 // The part of ConvertScanline that Compress reaches (DirectXTexConvert.cpp:3080-3854), resolved once
 // per image on the host into the (tcv, tsw) pair the tile loader applies.
-dxtex_hresult tile_conversion(const FmtInfo& in, const FmtInfo& out, uint32_t compressFlags, int* tcv, int* tsw)
+void tile_conversion(const FmtInfo& in, const FmtInfo& out, uint32_t compressFlags, int* tcv, int* tsw)
 {
     bool srgbIn = (compressFlags & DXTEX_COMPRESS_SRGB_IN) != 0 || (in.cls & FC_SRGB);
     bool srgbOut = (compressFlags & DXTEX_COMPRESS_SRGB_OUT) != 0 || (out.cls & FC_SRGB);
@@ -184,13 +214,13 @@ dxtex_hresult tile_conversion(const FmtInfo& in, const FmtInfo& out, uint32_t co
     }
     if (srgbIn && (in.cls & (FC_FLOAT | FC_UNORM))) *tcv |= TCV_SRGB_TO_LINEAR;      // :3170-3180
     if (srgbOut && (out.cls & (FC_FLOAT | FC_UNORM))) *tcv |= TCV_LINEAR_TO_SRGB;    // :3843-3853
-    return DXTEX_S_OK;
 }
 
 // Compress' argument checks (DirectXTexCompress.cpp:671-676, :741-745) and the source view the tile loaders take
-dxtex_hresult compress_view(dxtex_ctx* ctx, const uint8_t* dSrc, size_t width, size_t height, int srcFormat, size_t srcRowPitch, int dstFormat,
-                            uint32_t flags, SrcView* view)
+dxtex_hresult compress_view(dxtex_ctx* ctx, const dxtex_image& src, int dstFormat, uint32_t flags, SrcView* view)
 {
+    const int srcFormat = src.format;
+    const size_t width = src.width, height = src.height;
     const FmtInfo* in = format_info(srcFormat);
     const FmtInfo* out = format_info(dstFormat);
     // the reference's order (DirectXTexCompress.cpp:671-676): E_INVALIDARG for a compressed source or an uncompressed target first,
@@ -208,49 +238,42 @@ dxtex_hresult compress_view(dxtex_ctx* ctx, const uint8_t* dSrc, size_t width, s
     if (!width || !height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
     if (width > 0xFFFFFFFCull || height > 0xFFFFFFFCull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
     SrcView v;
-    v.pixels = dSrc; v.width = uint32_t(width); v.height = uint32_t(height); v.rowPitch = srcRowPitch; v.format = srcFormat;
-    const dxtex_hresult hr = tile_conversion(*in, *out, flags, &v.tcv, &v.tsw);
-    if (hr != DXTEX_S_OK) return fail(ctx, hr, "unsupported tile conversion");
+    v.pixels = src.pixels; v.width = uint32_t(width); v.height = uint32_t(height); v.rowPitch = src.rowPitch; v.format = srcFormat;
+    tile_conversion(*in, *out, flags, &v.tcv, &v.tsw);
     *view = v;
     return DXTEX_S_OK;
 }
 
-dxtex_hresult submit_compress(dxtex_ctx* ctx, const uint8_t* dSrc, size_t width, size_t height, int srcFormat, size_t srcRowPitch,
-                              uint8_t* dDst, int dstFormat, size_t dstRowPitch, uint32_t flags, float threshold)
+// BC7 / BC6H: the search scratch for `nblocks` blocks of `count` images (BC1-BC5 need none)
+dxtex_hresult grow_scratch(dxtex_ctx* ctx, int format, uint64_t nblocks, uint32_t flags, size_t count = 1)
 {
-    SrcView v;
-    dxtex_hresult hr = compress_view(ctx, dSrc, width, height, srcFormat, srcRowPitch, dstFormat, flags, &v);
-    if (hr != DXTEX_S_OK) return hr;
+    if (is_bc7(format)) return ctx->scratch.grow(ctx, bc7_scratch_bytes(nblocks, flags, count));
+    if (is_bc6h(format)) return ctx->scratch.grow(ctx, bc6h_scratch_bytes(nblocks, count));
+    return DXTEX_S_OK;
+}
 
+// the BC encoders: one image (view) -> blocks of `format` at dst
+dxtex_hresult encode(dxtex_ctx* ctx, const SrcView& v, uint8_t* dst, size_t dstRowPitch, int format, uint32_t flags, float threshold)
+{
+    const uint64_t nblocks = uint64_t((v.width + 3) / 4) * uint64_t((v.height + 3) / 4);
+    const dxtex_hresult hr = grow_scratch(ctx, format, nblocks, flags);
+    if (hr != DXTEX_S_OK) return hr;
+    KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
     hipError_t e;
-    switch (dstFormat)
-    {
-    case FMT_BC1_UNORM: case FMT_BC1_UNORM_SRGB: case FMT_BC2_UNORM: case FMT_BC2_UNORM_SRGB:
-    case FMT_BC3_UNORM: case FMT_BC3_UNORM_SRGB: case FMT_BC4_UNORM: case FMT_BC4_SNORM:
-    case FMT_BC5_UNORM: case FMT_BC5_SNORM:
-        e = launch_bc15_encode(v, dDst, dstRowPitch, dstFormat, flags, threshold, ctx->stream);
-        break;
-    case FMT_BC7_UNORM: case FMT_BC7_UNORM_SRGB:
-    {
-        const uint64_t nblocks = uint64_t((width + 3) / 4) * uint64_t((height + 3) / 4);
-        hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, bc7_scratch_bytes(nblocks, flags));
-        if (hr != DXTEX_S_OK) return hr;
-        e = launch_bc7_encode(v, dDst, dstRowPitch, flags, ctx->scratch, ctx->stream, ctx->profiling ? &ctx->marks : nullptr, side_streams(ctx));
-        break;
-    }
-    case FMT_BC6H_UF16: case FMT_BC6H_SF16:
-    {
-        const uint64_t nblocks = uint64_t((width + 3) / 4) * uint64_t((height + 3) / 4);
-        hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, bc6h_scratch_bytes(nblocks));
-        if (hr != DXTEX_S_OK) return hr;
-        e = launch_bc6h_encode(v, dDst, dstRowPitch, dstFormat == FMT_BC6H_SF16, ctx->scratch, ctx->stream, ctx->profiling ? &ctx->marks : nullptr, side_streams(ctx));
-        break;
-    }
-    default:
-        return fail(ctx, DXTEX_E_NOT_SUPPORTED, "BC format not implemented yet");
-    }
+    if (is_bc7(format)) e = launch_bc7_encode(v, dst, dstRowPitch, flags, ctx->scratch.p, ctx->stream, marks, side_streams(ctx));
+    else if (is_bc6h(format)) e = launch_bc6h_encode(v, dst, dstRowPitch, format == FMT_BC6H_SF16, ctx->scratch.p, ctx->stream, marks, side_streams(ctx));
+    else if (is_bc15(format)) e = launch_bc15_encode(v, dst, dstRowPitch, format, flags, threshold, ctx->stream);
+    else return fail(ctx, DXTEX_E_NOT_SUPPORTED, "BC format not implemented yet");
     if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     return DXTEX_S_OK;
+}
+
+dxtex_hresult submit_compress(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags, float threshold)
+{
+    SrcView v;
+    const dxtex_hresult hr = compress_view(ctx, src, dst.format, flags, &v);
+    if (hr != DXTEX_S_OK) return hr;
+    return encode(ctx, v, dst.pixels, dst.rowPitch, dst.format, flags, threshold);
 }
 
 dxtex_hresult check_pair(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
@@ -260,6 +283,68 @@ dxtex_hresult check_pair(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_ima
     if (!src->pixels || !dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
     if (src->width != dst->width || src->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
     return DXTEX_S_OK;
+}
+
+// tight size checks for host-pointer images: a pitch below the format's minimum would make the kernels read or write past the staging
+dxtex_hresult check_host_pitches(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, size_t* srcBytes, size_t* dstBytes)
+{
+    size_t minSrcRow = 0, minSrcSlice = 0, minDstRow = 0, minDstSlice = 0;
+    if (dxtex_compute_pitch(src->format, src->width, src->height, &minSrcRow, &minSrcSlice) != DXTEX_S_OK ||
+        dxtex_compute_pitch(dst->format, dst->width, dst->height, &minDstRow, &minDstSlice) != DXTEX_S_OK)
+        return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    if (src->rowPitch < minSrcRow || dst->rowPitch < minDstRow) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the format's minimum (ComputePitch)");
+    const size_t srcRows = (minSrcRow && minSrcSlice) ? minSrcSlice / minSrcRow : src->height;
+    const size_t dstRows = (minDstRow && minDstSlice) ? minDstSlice / minDstRow : dst->height;
+    if (src->rowPitch > SIZE_MAX / std::max<size_t>(1, srcRows) || dst->rowPitch > SIZE_MAX / std::max<size_t>(1, dstRows))
+        return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    *srcBytes = src->rowPitch * srcRows;
+    *dstBytes = dst->rowPitch * dstRows;
+    return DXTEX_S_OK;
+}
+
+// submit() between the timing events, on the context's device: what a timed entry point does after its checks
+template<class Submit>
+dxtex_hresult run_timed(dxtex_ctx* ctx, Submit&& submit)
+{
+    ScopedDevice sd(ctx->device);
+    time_begin(ctx);
+    const dxtex_hresult hr = submit();
+    time_end(ctx);
+    return hr;
+}
+
+// The staging of every single-image host-pointer entry point: inBytes from hostIn go up into ctx->stageIn, submit(stageIn, stageOut)
+// queues the kernels between the timing events (so dxtex_ctx_last_kernel_ms covers kernels only), outBytes of ctx->stageOut come back
+// to hostOut, and the call returns once they have landed. A failed submit returns at once: no download, no synchronisation.
+template<class Submit>
+dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, void* hostOut, size_t outBytes, Submit&& submit)
+{
+    ScopedDevice sd(ctx->device);
+    dxtex_hresult hr = ctx->stageIn.grow(ctx, inBytes); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, outBytes); if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, hostIn, inBytes, hipMemcpyHostToDevice, ctx->stream));
+    hr = run_timed(ctx, [&] { return submit(ctx->stageIn.u8(), ctx->stageOut.u8()); });
+    if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, hostOut, ctx->stageOut.p, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+struct LevelPair { const uint8_t* src; size_t srcPitch, sw, sh; uint8_t* dst; size_t dstPitch, dw, dh; };
+LevelPair pair_of(const dxtex_image& s, const dxtex_image& d) { return { s.pixels, s.rowPitch, s.width, s.height, d.pixels, d.rowPitch, d.width, d.height }; }
+// the (level i - 1 -> level i) pairs of a mip chain
+std::vector<LevelPair> mip_pairs(const dxtex_image* levels, size_t nlevels)
+{
+    std::vector<LevelPair> pairs;
+    for (size_t i = 1; i < nlevels; ++i) pairs.push_back(pair_of(levels[i - 1], levels[i]));
+    return pairs;
+}
+// copies of n images whose pixels lie at the arena's offsets from `base` (a host variant's levels in the staging)
+std::vector<dxtex_image> in_arena(const dxtex_image* im, size_t n, uint8_t* base, const Arena& a)
+{
+    std::vector<dxtex_image> o(n);
+    for (size_t i = 0; i < n; ++i) o[i] = with_pixels(im[i], base + a.at[i]);
+    return o;
 }
 } // namespace
 
@@ -300,39 +385,15 @@ void dxtex_ctx_destroy(dxtex_ctx* ctx)
     if (!ctx) return;
     ScopedDevice sd(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stageIn) (void)hipFree(ctx->stageIn);
-    if (ctx->stageOut) (void)hipFree(ctx->stageOut);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->groupRows) (void)hipFree(ctx->groupRows);
-    if (ctx->ditherRows) (void)hipFree(ctx->ditherRows);
-    if (ctx->ditherRerun) (void)hipFree(ctx->ditherRerun);
-    if (ctx->triBuf) (void)hipFree(ctx->triBuf);
-    if (ctx->triPinned) (void)hipHostFree(ctx->triPinned);
-    if (ctx->triConsumed) (void)hipEventDestroy(ctx->triConsumed);
-    if (ctx->mseBuf) (void)hipFree(ctx->mseBuf);
-    if (ctx->h2d) { (void)hipStreamSynchronize(ctx->h2d); (void)hipStreamDestroy(ctx->h2d); }
-    if (ctx->d2h) { (void)hipStreamSynchronize(ctx->d2h); (void)hipStreamDestroy(ctx->d2h); }
-    for (dxtex_ctx::Lane& l : ctx->lane)
-    {
-        if (l.pinIn) (void)hipHostFree(l.pinIn);
-        if (l.pinOut) (void)hipHostFree(l.pinOut);
-        if (l.devIn) (void)hipFree(l.devIn);
-        if (l.devOut) (void)hipFree(l.devOut);
-        if (l.uploaded) (void)hipEventDestroy(l.uploaded);
-        if (l.computed) (void)hipEventDestroy(l.computed);
-        if (l.downloaded) (void)hipEventDestroy(l.downloaded);
-    }
-    for (int k = 0; k < kSideStreams; ++k)
-    {
-        if (ctx->side.side[k]) { (void)hipStreamSynchronize(ctx->side.side[k]); (void)hipStreamDestroy(ctx->side.side[k]); }
-        if (ctx->side.joined[k]) (void)hipEventDestroy(ctx->side.joined[k]);
-    }
-    if (ctx->side.forked) (void)hipEventDestroy(ctx->side.forked);
-    for (hipEvent_t e : ctx->marks.pool) (void)hipEventDestroy(e);
-    if (ctx->evStart) (void)hipEventDestroy(ctx->evStart);
-    if (ctx->evStop) (void)hipEventDestroy(ctx->evStop);
+    std::vector<hipStream_t> streams = { ctx->h2d, ctx->d2h };
+    std::vector<hipEvent_t> events = ctx->marks.pool;
+    events.insert(events.end(), { ctx->evStart, ctx->evStop, ctx->triConsumed, ctx->side.forked });
+    for (int k = 0; k < kSideStreams; ++k) { streams.push_back(ctx->side.side[k]); events.push_back(ctx->side.joined[k]); }
+    for (const dxtex_ctx::Lane& l : ctx->lane) events.insert(events.end(), { l.uploaded, l.computed, l.downloaded });
+    for (hipStream_t s : streams) if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    for (hipEvent_t e : events) if (e) (void)hipEventDestroy(e);
     if (ctx->ownStream) (void)hipStreamDestroy(ctx->ownStream);
-    delete ctx;
+    delete ctx;        // the buffers go with it: every stream that used them has drained, and the device is still the context's
 }
 
 dxtex_hresult dxtex_ctx_set_stream(dxtex_ctx* ctx, void* hip_stream)
@@ -466,12 +527,7 @@ dxtex_hresult dxtex_compress_device(dxtex_ctx* ctx, const dxtex_image* src, cons
 {
     dxtex_hresult hr = check_pair(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    time_begin(ctx);
-    hr = submit_compress(ctx, src->pixels, src->width, src->height, src->format, src->rowPitch,
-                         dst->pixels, dst->format, dst->rowPitch, flags, threshold);
-    time_end(ctx);
-    return hr;
+    return run_timed(ctx, [&] { return submit_compress(ctx, *src, *dst, flags, threshold); });
 }
 
 dxtex_hresult dxtex_compress_many_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count,
@@ -485,8 +541,8 @@ dxtex_hresult dxtex_compress_many_device(dxtex_ctx* ctx, const dxtex_image* srcs
     bool allBc7 = count > 1, allBc6 = count > 1;
     for (size_t i = 0; i < count; ++i)
     {
-        allBc7 = allBc7 && (dsts[i].format == FMT_BC7_UNORM || dsts[i].format == FMT_BC7_UNORM_SRGB);
-        allBc6 = allBc6 && dsts[i].format == dsts[0].format && (dsts[i].format == FMT_BC6H_UF16 || dsts[i].format == FMT_BC6H_SF16);
+        allBc7 = allBc7 && is_bc7(dsts[i].format);
+        allBc6 = allBc6 && dsts[i].format == dsts[0].format && is_bc6h(dsts[i].format);
     }
     if (allBc7 || allBc6)
     {
@@ -496,16 +552,17 @@ dxtex_hresult dxtex_compress_many_device(dxtex_ctx* ctx, const dxtex_image* srcs
         {
             dxtex_hresult hr = check_pair(ctx, &srcs[i], &dsts[i]);
             if (hr == DXTEX_S_OK)
-                hr = compress_view(ctx, srcs[i].pixels, srcs[i].width, srcs[i].height, srcs[i].format, srcs[i].rowPitch, dsts[i].format, flags, &batch[i].src);
+                hr = compress_view(ctx, srcs[i], dsts[i].format, flags, &batch[i].src);
             if (hr != DXTEX_S_OK) return hr;
             batch[i].dst = dsts[i].pixels; batch[i].dstRowPitch = dsts[i].rowPitch;
             nblocks += uint64_t((srcs[i].width + 3) / 4) * uint64_t((srcs[i].height + 3) / 4);
         }
-        dxtex_hresult hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, allBc7 ? bc7_scratch_bytes(nblocks, flags, count) : bc6h_scratch_bytes(nblocks, count));
+        const dxtex_hresult hr = grow_scratch(ctx, dsts[0].format, nblocks, flags, count);
         if (hr != DXTEX_S_OK) return hr;
+        KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
         time_begin(ctx);
-        const hipError_t e = allBc7 ? launch_bc7_encode_many(batch.data(), count, flags, ctx->scratch, ctx->stream, ctx->profiling ? &ctx->marks : nullptr, side_streams(ctx))
-                                    : launch_bc6h_encode_many(batch.data(), count, dsts[0].format == FMT_BC6H_SF16, ctx->scratch, ctx->stream, ctx->profiling ? &ctx->marks : nullptr, side_streams(ctx));
+        const hipError_t e = allBc7 ? launch_bc7_encode_many(batch.data(), count, flags, ctx->scratch.p, ctx->stream, marks, side_streams(ctx))
+                                    : launch_bc6h_encode_many(batch.data(), count, dsts[0].format == FMT_BC6H_SF16, ctx->scratch.p, ctx->stream, marks, side_streams(ctx));
         time_end(ctx);
         if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
         return DXTEX_S_OK;
@@ -524,23 +581,19 @@ dxtex_hresult dxtex_compress_many_device(dxtex_ctx* ctx, const dxtex_image* srcs
     for (size_t i = 0; i < count; ++i)
     {
         dxtex_hresult hr = check_pair(ctx, &srcs[i], &dsts[i]);
-        const FmtInfo* out = (hr == DXTEX_S_OK) ? format_info(dsts[i].format) : nullptr;
-        const bool bc15 = out && (out->cls & FC_BC) && bc_block_bytes(dsts[i].format) && dsts[i].format != FMT_BC7_UNORM && dsts[i].format != FMT_BC7_UNORM_SRGB &&
-                          dsts[i].format != FMT_BC6H_UF16 && dsts[i].format != FMT_BC6H_SF16;
-        if (hr == DXTEX_S_OK && bc15 && bc15_small_image(uint32_t(srcs[i].width), uint32_t(srcs[i].height)) && srcs[i].width <= 0xFFFFFFFFull && srcs[i].height <= 0xFFFFFFFFull)
+        if (hr == DXTEX_S_OK && is_bc15(dsts[i].format) && bc15_small_image(uint32_t(srcs[i].width), uint32_t(srcs[i].height)) && srcs[i].width <= 0xFFFFFFFFull && srcs[i].height <= 0xFFFFFFFFull)
         {
             if (!small.empty() && (smallFormat != dsts[i].format || int(small.size()) == bc15_small_batch_max())) hr = flush_small();
             BcImage im;
             if (hr == DXTEX_S_OK)
-                hr = compress_view(ctx, srcs[i].pixels, srcs[i].width, srcs[i].height, srcs[i].format, srcs[i].rowPitch, dsts[i].format, flags, &im.src);
+                hr = compress_view(ctx, srcs[i], dsts[i].format, flags, &im.src);
             if (hr == DXTEX_S_OK) { im.dst = dsts[i].pixels; im.dstRowPitch = dsts[i].rowPitch; small.push_back(im); smallFormat = dsts[i].format; }
         }
         else if (hr == DXTEX_S_OK)
         {
             hr = flush_small();                        // keeps the images in submission order on the stream
             if (hr == DXTEX_S_OK)
-                hr = submit_compress(ctx, srcs[i].pixels, srcs[i].width, srcs[i].height, srcs[i].format, srcs[i].rowPitch,
-                                     dsts[i].pixels, dsts[i].format, dsts[i].rowPitch, flags, threshold);
+                hr = submit_compress(ctx, srcs[i], dsts[i], flags, threshold);
         }
         if (hr != DXTEX_S_OK) { time_end(ctx); return hr; }
     }
@@ -557,21 +610,18 @@ dxtex_hresult dxtex_ctx_prepare(dxtex_ctx* ctx, size_t width, size_t height, int
     if (!count) return fail(ctx, DXTEX_E_INVALIDARG, "empty batch");
     size_t srcRow = 0, srcSlice = 0, dstRow = 0, dstSlice = 0;
     SrcView v;
-    dxtex_hresult hr = compress_view(ctx, nullptr, width, height, src_format, 0, dst_format, flags, &v);           // the format / size checks of dxtex_compress
+    dxtex_hresult hr = compress_view(ctx, { width, height, src_format, 0, 0, nullptr }, dst_format, flags, &v);      // the format / size checks of dxtex_compress
     if (hr != DXTEX_S_OK) return hr;
     if (dxtex_compute_pitch(src_format, width, height, &srcRow, &srcSlice) != DXTEX_S_OK || dxtex_compute_pitch(dst_format, width, height, &dstRow, &dstSlice) != DXTEX_S_OK)
         return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
     ScopedDevice sd(ctx->device);
     const uint64_t nblocks = uint64_t((width + 3) / 4) * uint64_t((height + 3) / 4) * count;
-    if (dst_format == FMT_BC7_UNORM || dst_format == FMT_BC7_UNORM_SRGB)
-        hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, bc7_scratch_bytes(nblocks, flags, count));
-    else if (dst_format == FMT_BC6H_UF16 || dst_format == FMT_BC6H_SF16)
-        hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, bc6h_scratch_bytes(nblocks, count));
+    hr = grow_scratch(ctx, dst_format, nblocks, flags, count);
     if (hr != DXTEX_S_OK) return hr;
-    // staging as dxtex_compress_many lays it out: every image 256-byte aligned
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, ((srcSlice + 255) & ~size_t(255)) * count); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, ((dstSlice + 255) & ~size_t(255)) * count); if (hr != DXTEX_S_OK) return hr;
-    if (device_bytes) *device_bytes = ctx->scratchBytes + ctx->stageInBytes + ctx->stageOutBytes;
+    // the staging of dxtex_compress (and of the warm-up below), `count` images 256-byte aligned (dxtex_compress_many stages through its lanes)
+    hr = ctx->stageIn.grow(ctx, align256(srcSlice) * count); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, align256(dstSlice) * count); if (hr != DXTEX_S_OK) return hr;
+    if (device_bytes) *device_bytes = ctx->scratch.bytes + ctx->stageIn.bytes + ctx->stageOut.bytes;
     // GPUCompressBC::Prepare also binds the shaders the size needs (BCDirectCompute.cpp:203-369). The counterpart here: the HIP runtime loads a
     // kernel's code object on its first launch, and the BC7 / BC6H pipelines are some forty kernels plus three side streams - 19 ms on the first
     // call of a fresh process against 1.2 ms on the second (tools/cold_probe.py: a 64 x 64 image). One block of zeros goes through the same
@@ -582,10 +632,10 @@ dxtex_hresult dxtex_ctx_prepare(dxtex_ctx* ctx, size_t width, size_t height, int
         const size_t ww = std::min<size_t>(width, 4), wh = std::min<size_t>(height, 4);
         size_t wRow = 0, wSlice = 0, oRow = 0, oSlice = 0;
         if (dxtex_compute_pitch(src_format, ww, wh, &wRow, &wSlice) == DXTEX_S_OK && dxtex_compute_pitch(dst_format, ww, wh, &oRow, &oSlice) == DXTEX_S_OK &&
-            wSlice <= ctx->stageInBytes && oSlice <= ctx->stageOutBytes)
+            wSlice <= ctx->stageIn.bytes && oSlice <= ctx->stageOut.bytes)
         {
-            HIP_TRY(ctx, hipMemsetAsync(ctx->stageIn, 0, wSlice, ctx->stream));
-            hr = submit_compress(ctx, static_cast<const uint8_t*>(ctx->stageIn), ww, wh, src_format, wRow, static_cast<uint8_t*>(ctx->stageOut), dst_format, oRow, flags, 0.5f);
+            HIP_TRY(ctx, hipMemsetAsync(ctx->stageIn.p, 0, wSlice, ctx->stream));
+            hr = submit_compress(ctx, { ww, wh, src_format, wRow, wSlice, ctx->stageIn.u8() }, { ww, wh, dst_format, oRow, oSlice, ctx->stageOut.u8() }, flags, 0.5f);
             if (hr != DXTEX_S_OK) return hr;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             ctx->warmedFormats |= bit;
@@ -603,38 +653,8 @@ dxtex_hresult dxtex_ctx_prepare(dxtex_ctx* ctx, size_t width, size_t height, int
 // 0.1-0.5 ms of kernel time and 1.6 ms of PCIe, it is the copies that overlap each other).
 namespace
 {
-dxtex_hresult ensure_pinned(dxtex_ctx* ctx, void** buf, size_t* have, size_t need)
-{
-    if (*have >= need) return DXTEX_S_OK;
-    if (*buf) { HIP_TRY(ctx, hipHostFree(*buf)); *buf = nullptr; *have = 0; }
-    const size_t bytes = std::max<size_t>(need, 1u << 20);
-    HIP_TRY(ctx, hipHostMalloc(buf, bytes, hipHostMallocDefault));
-    *have = bytes;
-    return DXTEX_S_OK;
-}
+struct ManyChunk { size_t first, count; };
 
-struct ManyChunk { size_t first, count, inBytes, outBytes; };
-
-// tight size checks for host-pointer images: a pitch below the format's minimum would make the kernels read or write past the staging
-dxtex_hresult check_host_pitches(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, size_t* srcBytes, size_t* dstBytes)
-{
-    size_t minSrcRow = 0, minSrcSlice = 0, minDstRow = 0, minDstSlice = 0;
-    if (dxtex_compute_pitch(src->format, src->width, src->height, &minSrcRow, &minSrcSlice) != DXTEX_S_OK ||
-        dxtex_compute_pitch(dst->format, dst->width, dst->height, &minDstRow, &minDstSlice) != DXTEX_S_OK)
-        return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
-    if (src->rowPitch < minSrcRow || dst->rowPitch < minDstRow) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the format's minimum (ComputePitch)");
-    const size_t srcRows = (minSrcRow && minSrcSlice) ? minSrcSlice / minSrcRow : src->height;
-    const size_t dstRows = (minDstRow && minDstSlice) ? minDstSlice / minDstRow : dst->height;
-    if (src->rowPitch > SIZE_MAX / std::max<size_t>(1, srcRows) || dst->rowPitch > SIZE_MAX / std::max<size_t>(1, dstRows))
-        return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
-    *srcBytes = src->rowPitch * srcRows;
-    *dstBytes = dst->rowPitch * dstRows;
-    return DXTEX_S_OK;
-}
-}
-
-namespace
-{
 dxtex_hresult compress_many_pipelined(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t flags, float threshold);
 }
 
@@ -665,19 +685,17 @@ dxtex_hresult compress_many_pipelined(dxtex_ctx* ctx, const dxtex_image* srcs, c
     std::vector<size_t> inBytes(count), outBytes(count);
     std::vector<ManyChunk> chunks;
     {
-        ManyChunk cur = { 0, 0, 0, 0 };
+        ManyChunk cur = { 0, 0 };
         uint64_t texels = 0;
         for (size_t i = 0; i < count; ++i)
         {
             dxtex_hresult hr = check_pair(ctx, &srcs[i], &dsts[i]);
-            if (hr == DXTEX_S_OK) { SrcView v; hr = compress_view(ctx, nullptr, srcs[i].width, srcs[i].height, srcs[i].format, srcs[i].rowPitch, dsts[i].format, flags, &v); }
+            if (hr == DXTEX_S_OK) { SrcView v; hr = compress_view(ctx, srcs[i], dsts[i].format, flags, &v); }
             if (hr == DXTEX_S_OK) hr = check_host_pitches(ctx, &srcs[i], &dsts[i], &inBytes[i], &outBytes[i]);
             if (hr != DXTEX_S_OK) return hr;
             const uint64_t t = uint64_t(srcs[i].width) * srcs[i].height;
-            if (cur.count && texels + t > chunkTexels) { chunks.push_back(cur); cur = { i, 0, 0, 0 }; texels = 0; }
+            if (cur.count && texels + t > chunkTexels) { chunks.push_back(cur); cur = { i, 0 }; texels = 0; }
             ++cur.count; texels += t;
-            cur.inBytes += (inBytes[i] + 255) & ~size_t(255);
-            cur.outBytes += (outBytes[i] + 255) & ~size_t(255);
         }
         chunks.push_back(cur);
     }
@@ -695,12 +713,9 @@ dxtex_hresult compress_many_pipelined(dxtex_ctx* ctx, const dxtex_image* srcs, c
     {
         dxtex_ctx::Lane& l = ctx->lane[c & 1];
         HIP_TRY(ctx, hipEventSynchronize(l.downloaded));
-        size_t at = 0;
-        for (size_t i = chunks[c].first; i < chunks[c].first + chunks[c].count; ++i)
-        {
-            std::memcpy(dsts[i].pixels, static_cast<const uint8_t*>(l.pinOut) + at, outBytes[i]);
-            at += (outBytes[i] + 255) & ~size_t(255);
-        }
+        const Arena out(&outBytes[chunks[c].first], chunks[c].count);
+        for (size_t k = 0; k < chunks[c].count; ++k)
+            std::memcpy(dsts[chunks[c].first + k].pixels, l.pinOut.u8() + out.at[k], outBytes[chunks[c].first + k]);
         return DXTEX_S_OK;
     };
 
@@ -710,32 +725,29 @@ dxtex_hresult compress_many_pipelined(dxtex_ctx* ctx, const dxtex_image* srcs, c
         const ManyChunk& ch = chunks[c];
         dxtex_ctx::Lane& l = ctx->lane[c & 1];
         if (c >= 2) { const dxtex_hresult hr = scatter(c - 2); if (hr != DXTEX_S_OK) return hr; }      // frees this lane's pinOut (and, stream-ordered, devOut)
-        dxtex_hresult hr = ensure_pinned(ctx, &l.pinIn, &l.pinInBytes, ch.inBytes); if (hr != DXTEX_S_OK) return hr;
-        hr = ensure_pinned(ctx, &l.pinOut, &l.pinOutBytes, ch.outBytes); if (hr != DXTEX_S_OK) return hr;
-        hr = ensure(ctx, &l.devIn, &l.devInBytes, ch.inBytes); if (hr != DXTEX_S_OK) return hr;
-        hr = ensure(ctx, &l.devOut, &l.devOutBytes, ch.outBytes); if (hr != DXTEX_S_OK) return hr;
+        const Arena in(&inBytes[ch.first], ch.count), out(&outBytes[ch.first], ch.count);
+        dxtex_hresult hr = l.pinIn.grow(ctx, in.total); if (hr != DXTEX_S_OK) return hr;
+        hr = l.pinOut.grow(ctx, out.total); if (hr != DXTEX_S_OK) return hr;
+        hr = l.devIn.grow(ctx, in.total); if (hr != DXTEX_S_OK) return hr;
+        hr = l.devOut.grow(ctx, out.total); if (hr != DXTEX_S_OK) return hr;
         // gather (pinIn of this lane was last read by the upload of chunk c - 2, which the kernels of c - 2 waited for, which the download
         // of c - 2 waited for, which scatter(c - 2) has just waited for)
         ds.assign(srcs + ch.first, srcs + ch.first + ch.count);
         dd.assign(dsts + ch.first, dsts + ch.first + ch.count);
-        size_t atIn = 0, atOut = 0;
         for (size_t k = 0; k < ch.count; ++k)
         {
-            const size_t i = ch.first + k;
-            std::memcpy(static_cast<uint8_t*>(l.pinIn) + atIn, srcs[i].pixels, inBytes[i]);
-            ds[k].pixels = static_cast<uint8_t*>(l.devIn) + atIn;
-            dd[k].pixels = static_cast<uint8_t*>(l.devOut) + atOut;
-            atIn += (inBytes[i] + 255) & ~size_t(255);
-            atOut += (outBytes[i] + 255) & ~size_t(255);
+            std::memcpy(l.pinIn.u8() + in.at[k], srcs[ch.first + k].pixels, inBytes[ch.first + k]);
+            ds[k].pixels = l.devIn.u8() + in.at[k];
+            dd[k].pixels = l.devOut.u8() + out.at[k];
         }
-        HIP_TRY(ctx, counted_copy(ctx, l.devIn, l.pinIn, atIn, hipMemcpyHostToDevice, ctx->h2d));
+        HIP_TRY(ctx, counted_copy(ctx, l.devIn.p, l.pinIn.p, in.total, hipMemcpyHostToDevice, ctx->h2d));
         HIP_TRY(ctx, hipEventRecord(l.uploaded, ctx->h2d));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, l.uploaded, 0));
         hr = dxtex_compress_many_device(ctx, ds.data(), dd.data(), ch.count, flags, threshold);
         if (hr != DXTEX_S_OK) return hr;
         HIP_TRY(ctx, hipEventRecord(l.computed, ctx->stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->d2h, l.computed, 0));
-        HIP_TRY(ctx, counted_copy(ctx, l.pinOut, l.devOut, atOut, hipMemcpyDeviceToHost, ctx->d2h));
+        HIP_TRY(ctx, counted_copy(ctx, l.pinOut.p, l.devOut.p, out.total, hipMemcpyDeviceToHost, ctx->d2h));
         HIP_TRY(ctx, hipEventRecord(l.downloaded, ctx->d2h));
         // (no wait of h2d on `computed`: the next upload into this lane's devIn belongs to chunk c + 2, and iteration c + 2 begins with
         // scatter(c), a host wait for downloaded(c), which is stream-ordered after computed(c). The upload of chunk c + 1 - the other
@@ -755,21 +767,11 @@ dxtex_hresult dxtex_compress(dxtex_ctx* ctx, const dxtex_image* src, const dxtex
 {
     dxtex_hresult hr = check_pair(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    { SrcView v; hr = compress_view(ctx, nullptr, src->width, src->height, src->format, src->rowPitch, dst->format, flags, &v); if (hr != DXTEX_S_OK) return hr; }
-    ScopedDevice sd(ctx->device);
+    { SrcView v; hr = compress_view(ctx, *src, dst->format, flags, &v); if (hr != DXTEX_S_OK) return hr; }
     size_t srcBytes = 0, dstBytes = 0;
     hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, src->pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-    time_begin(ctx);
-    hr = submit_compress(ctx, static_cast<const uint8_t*>(ctx->stageIn), src->width, src->height, src->format, src->rowPitch,
-                         static_cast<uint8_t*>(ctx->stageOut), dst->format, dst->rowPitch, flags, threshold);
-    time_end(ctx);
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, dst->pixels, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      { return submit_compress(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags, threshold); });
 }
 
 dxtex_hresult dxtex_encode_blocks(dxtex_ctx* ctx, int32_t bc_format, uint32_t bc_flags, float threshold,
@@ -780,59 +782,27 @@ dxtex_hresult dxtex_encode_blocks(dxtex_ctx* ctx, int32_t bc_format, uint32_t bc
     const size_t bb = bc_block_bytes(bc_format);
     if (!bb) return fail(ctx, DXTEX_E_INVALIDARG, "not a BC format");
     if (!nblocks) return DXTEX_S_OK;
-    ScopedDevice sd(ctx->device);
     // nblocks tiles of 16 x float4 == an R32G32B32A32_FLOAT image 4 texels wide and 4*nblocks high.
-    const size_t srcBytes = nblocks * 256, dstBytes = nblocks * bb;
-    dxtex_hresult hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, rgba, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-
-    SrcView v;
-    v.pixels = static_cast<const uint8_t*>(ctx->stageIn); v.width = 4; v.height = uint32_t(nblocks * 4);
-    v.rowPitch = 64; v.format = FMT_R32G32B32A32_FLOAT; v.tcv = TCV_NONE; v.tsw = TSW_NONE;   // raw floats, as BC_ENCODE receives them
-    hipError_t e;
-    if (bc_format == FMT_BC7_UNORM || bc_format == FMT_BC7_UNORM_SRGB)
+    return run_staged(ctx, rgba, nblocks * 256, bc, nblocks * bb, [&](uint8_t* in, uint8_t* out)
     {
-        hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, bc7_scratch_bytes(nblocks, bc_flags));
-        if (hr != DXTEX_S_OK) return hr;
-    }
-    if (bc_format == FMT_BC6H_UF16 || bc_format == FMT_BC6H_SF16)
-    {
-        hr = ensure(ctx, &ctx->scratch, &ctx->scratchBytes, bc6h_scratch_bytes(nblocks));
-        if (hr != DXTEX_S_OK) return hr;
-    }
-    time_begin(ctx);
-    switch (bc_format)
-    {
-    case FMT_BC6H_UF16: case FMT_BC6H_SF16:
-        e = launch_bc6h_encode(v, static_cast<uint8_t*>(ctx->stageOut), bb, bc_format == FMT_BC6H_SF16, ctx->scratch, ctx->stream, ctx->profiling ? &ctx->marks : nullptr, side_streams(ctx));
-        break;
-    case FMT_BC7_UNORM: case FMT_BC7_UNORM_SRGB:
-        e = launch_bc7_encode(v, static_cast<uint8_t*>(ctx->stageOut), bb, bc_flags, ctx->scratch, ctx->stream, ctx->profiling ? &ctx->marks : nullptr, side_streams(ctx));
-        break;
-    default:
-        e = launch_bc15_encode(v, static_cast<uint8_t*>(ctx->stageOut), bb, bc_format, bc_flags, threshold, ctx->stream);
-        break;
-    }
-    time_end(ctx);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-    HIP_TRY(ctx, counted_copy(ctx, bc, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+        SrcView v;
+        v.pixels = in; v.width = 4; v.height = uint32_t(nblocks * 4);
+        v.rowPitch = 64; v.format = FMT_R32G32B32A32_FLOAT; v.tcv = TCV_NONE; v.tsw = TSW_NONE;   // raw floats, as BC_ENCODE receives them
+        return encode(ctx, v, out, bb, bc_format, bc_flags, threshold);
+    });
 }
 
 // DecompressBC (DirectXTexCompress.cpp:425-535): BC image -> uncompressed image of the same size, on device pointers.
-static dxtex_hresult submit_decompress(dxtex_ctx* ctx, const uint8_t* dSrc, int srcFormat, size_t srcRowPitch,
-                                       uint8_t* dDst, int dstFormat, size_t dstRowPitch, size_t width, size_t height)
+static dxtex_hresult submit_decompress(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst)
 {
-    const FmtInfo* in = format_info(srcFormat);
-    const FmtInfo* out = format_info(dstFormat);
+    const FmtInfo* in = format_info(src.format);
+    const FmtInfo* out = format_info(dst.format);
     if (!in || !(in->cls & FC_BC)) return fail(ctx, DXTEX_E_INVALIDARG, "source image is not block compressed");
     if (out && (out->cls & FC_BC)) return fail(ctx, DXTEX_E_INVALIDARG, "destination format is block compressed");
     if (!out || (out->cls & FC_GROUP)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "destination format is not supported by the MI355X path");
-    if (!width || !height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    if (!src.width || !src.height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
     const ConvertPlan plan = resolve_convert_plan(*in, *out, 0);
-    hipError_t e = launch_bc_decode(dSrc, srcRowPitch, srcFormat, dDst, dstRowPitch, dstFormat, uint32_t(width), uint32_t(height), plan, ctx->stream);
+    hipError_t e = launch_bc_decode(src.pixels, src.rowPitch, src.format, dst.pixels, dst.rowPitch, dst.format, uint32_t(src.width), uint32_t(src.height), plan, ctx->stream);
     if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     return DXTEX_S_OK;
 }
@@ -841,32 +811,18 @@ dxtex_hresult dxtex_decompress_device(dxtex_ctx* ctx, const dxtex_image* src, co
 {
     dxtex_hresult hr = check_pair(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    time_begin(ctx);
-    hr = submit_decompress(ctx, src->pixels, src->format, src->rowPitch, dst->pixels, dst->format, dst->rowPitch, src->width, src->height);
-    time_end(ctx);
-    return hr;
+    return run_timed(ctx, [&] { return submit_decompress(ctx, *src, *dst); });
 }
 
 dxtex_hresult dxtex_decompress(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
 {
     dxtex_hresult hr = check_pair(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
     size_t srcBytes = 0, dstBytes = 0;
     if (format_info(src->format) && format_info(dst->format)) { hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr; }
     else { srcBytes = src->rowPitch * std::max<size_t>(1, (src->height + 3) / 4); dstBytes = dst->rowPitch * dst->height; }      // submit_decompress rejects the formats below
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, src->pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-    time_begin(ctx);
-    hr = submit_decompress(ctx, static_cast<const uint8_t*>(ctx->stageIn), src->format, src->rowPitch,
-                           static_cast<uint8_t*>(ctx->stageOut), dst->format, dst->rowPitch, src->width, src->height);
-    time_end(ctx);
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, dst->pixels, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      { return submit_decompress(ctx, with_pixels(*src, in), with_pixels(*dst, out)); });
 }
 
 dxtex_hresult dxtex_decode_blocks(dxtex_ctx* ctx, int32_t bc_format, const uint8_t* bc, size_t nblocks, float* rgba)
@@ -876,21 +832,13 @@ dxtex_hresult dxtex_decode_blocks(dxtex_ctx* ctx, int32_t bc_format, const uint8
     const size_t bb = bc_block_bytes(bc_format);
     if (!bb) return fail(ctx, DXTEX_E_INVALIDARG, "not a BC format");
     if (!nblocks) return DXTEX_S_OK;
-    ScopedDevice sd(ctx->device);
     // nblocks blocks == a BC image 4 texels wide and 4*nblocks high; the raw decoder output is R32G32B32A32_FLOAT
-    const size_t srcBytes = nblocks * bb, dstBytes = nblocks * 256;
-    dxtex_hresult hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, bc, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-    ConvertPlan plan; plan.srgbIn = 0; plan.tcv = TCV_NONE; plan.tsw = TSW_NONE; plan.srgbOut = 0; plan.depth = 0;
-    time_begin(ctx);
-    hipError_t e = launch_bc_decode(static_cast<const uint8_t*>(ctx->stageIn), bb, bc_format, static_cast<uint8_t*>(ctx->stageOut), 64,
-                                    FMT_R32G32B32A32_FLOAT, 4, uint32_t(nblocks * 4), plan, ctx->stream);
-    time_end(ctx);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-    HIP_TRY(ctx, counted_copy(ctx, rgba, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged(ctx, bc, nblocks * bb, rgba, nblocks * 256, [&](uint8_t* in, uint8_t* out)
+    {
+        ConvertPlan plan; plan.srgbIn = 0; plan.tcv = TCV_NONE; plan.tsw = TSW_NONE; plan.srgbOut = 0; plan.depth = 0;
+        const hipError_t e = launch_bc_decode(in, bb, bc_format, out, 64, FMT_R32G32B32A32_FLOAT, 4, uint32_t(nblocks * 4), plan, ctx->stream);
+        return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    });
 }
 // ---- GenerateMipMaps / Resize / Convert ----------------------------------------------------------------------------------
 namespace
@@ -898,25 +846,33 @@ namespace
 constexpr uint32_t kFilterModeMask = 0xF00000u, kFilterDitherOrdered = 0x10000u, kFilterDitherDiffusion = 0x20000u;
 inline bool ispow2(size_t x) { return x != 0 && (x & (x - 1)) == 0; }
 
-struct LevelPair { const uint8_t* src; size_t srcPitch, sw, sh; uint8_t* dst; size_t dstPitch, dw, dh; };
 
-// Builds the triangle tables of every (src -> dst) pair into one device buffer, then launches the filter per pair.
-// The triangle filter's gather lists go to the device through a pinned buffer of the context; an event marks when the last
-// upload has been consumed, so an asynchronous (_device) call never rewrites host memory under a copy in flight.
-dxtex_hresult upload_tables(dxtex_ctx* ctx, const std::vector<uint8_t>& host)
+// The triangle filter's gather lists of every axis of every level go to the device as one table image (ctx->triHost, then upload_tables).
+// pack_triangle_axis appends one axis' lists (source -> dest texels) 16-byte aligned and returns where they start; the offsets become
+// device pointers once the tables are uploaded.
+struct TriAxis { size_t ofs, ent; };
+TriAxis pack_triangle_axis(std::vector<uint8_t>& host, size_t source, size_t dest, bool wrap)
 {
-    dxtex_hresult hr = ensure(ctx, &ctx->triBuf, &ctx->triBytes, host.size()); if (hr != DXTEX_S_OK) return hr;
+    std::vector<uint32_t> ofs; std::vector<TriEntry> ent;
+    build_triangle_axis(source, dest, wrap, ofs, ent);
+    auto append = [&](const void* p, size_t bytes) { const size_t at = (host.size() + 15) & ~size_t(15); host.resize(at + bytes); std::memcpy(host.data() + at, p, bytes); return at; };
+    const size_t o = append(ofs.data(), ofs.size() * 4);
+    return { o, append(ent.data(), std::max<size_t>(1, ent.size()) * 8) };
+}
+const uint32_t* tri_ofs(const uint8_t* tables, TriAxis a) { return reinterpret_cast<const uint32_t*>(tables + a.ofs); }
+
+// The packed tables (ctx->triHost, plus 16 bytes of tail padding) go to the device through a pinned buffer of the context; an event marks
+// when the last upload has been consumed, so an asynchronous (_device) call never rewrites host memory under a copy in flight.
+dxtex_hresult upload_tables(dxtex_ctx* ctx)
+{
+    std::vector<uint8_t>& host = ctx->triHost;
+    host.resize(host.size() + 16);
+    dxtex_hresult hr = ctx->triBuf.grow(ctx, host.size()); if (hr != DXTEX_S_OK) return hr;
     if (ctx->triPending) { HIP_TRY(ctx, hipEventSynchronize(ctx->triConsumed)); ctx->triPending = false; }
-    if (ctx->triPinnedBytes < host.size())
-    {
-        if (ctx->triPinned) { HIP_TRY(ctx, hipHostFree(ctx->triPinned)); ctx->triPinned = nullptr; ctx->triPinnedBytes = 0; }
-        const size_t bytes = std::max<size_t>(host.size(), 1u << 16);
-        HIP_TRY(ctx, hipHostMalloc(&ctx->triPinned, bytes, hipHostMallocDefault));
-        ctx->triPinnedBytes = bytes;
-    }
+    hr = ctx->triPinned.grow(ctx, host.size(), 1u << 16); if (hr != DXTEX_S_OK) return hr;
     if (!ctx->triConsumed) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->triConsumed, hipEventDisableTiming));
-    std::memcpy(ctx->triPinned, host.data(), host.size());
-    HIP_TRY(ctx, counted_copy(ctx, ctx->triBuf, ctx->triPinned, host.size(), hipMemcpyHostToDevice, ctx->stream));
+    std::memcpy(ctx->triPinned.p, host.data(), host.size());
+    HIP_TRY(ctx, counted_copy(ctx, ctx->triBuf.p, ctx->triPinned.p, host.size(), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(ctx->triConsumed, ctx->stream));
     ctx->triPending = true;
     return DXTEX_S_OK;
@@ -929,14 +885,14 @@ bool is_group_format(int format) { const FmtInfo* f = format_info(format); retur
 dxtex_hresult group_rows(dxtex_ctx* ctx, size_t width, size_t height, uint8_t** rows, size_t* pitch)
 {
     *pitch = width * 16;
-    const dxtex_hresult hr = ensure(ctx, &ctx->groupRows, &ctx->groupRowsBytes, *pitch * height);
-    *rows = static_cast<uint8_t*>(ctx->groupRows);
+    const dxtex_hresult hr = ctx->groupRows.grow(ctx, *pitch * height);
+    *rows = ctx->groupRows.u8();
     return hr;
 }
 
+// Builds the triangle tables of every (src -> dst) pair into one device buffer, then launches the filter per pair.
 dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs, int format, uint32_t mode, uint32_t flags, bool mipAlias)
 {
-    std::vector<size_t> base(pairs.size(), 0);
     const bool grouped = is_group_format(format);
     // one resize: straight into the destination, or through float rows and the pack kernel
     auto resize_one = [&](const LevelPair& p, const TriangleTables* t, const uint8_t* staleSrc, uint64_t stalePitch, uint32_t staleW) -> dxtex_hresult
@@ -950,27 +906,18 @@ dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs
     };
     if (mode == DXTEX_FILTER_TRIANGLE)
     {
-        std::vector<uint8_t>& host = ctx->triHost;
-        host.clear();
-        std::vector<uint32_t> ofs; std::vector<TriEntry> ent;
-        struct Slot { size_t ofsX, entX, ofsY, entY; };
-        std::vector<Slot> slots(pairs.size());
-        auto append = [&](const void* p, size_t bytes) { const size_t at = (host.size() + 15) & ~size_t(15); host.resize(at + bytes); std::memcpy(host.data() + at, p, bytes); return at; };
-        for (size_t i = 0; i < pairs.size(); ++i)
+        ctx->triHost.clear();
+        std::vector<TriAxis> x, y;
+        for (const LevelPair& p : pairs)
         {
-            build_triangle_axis(pairs[i].sw, pairs[i].dw, (flags & DXTEX_FILTER_WRAP_U) != 0, ofs, ent);
-            slots[i].ofsX = append(ofs.data(), ofs.size() * 4); slots[i].entX = append(ent.data(), std::max<size_t>(1, ent.size()) * 8);
-            build_triangle_axis(pairs[i].sh, pairs[i].dh, (flags & DXTEX_FILTER_WRAP_V) != 0, ofs, ent);
-            slots[i].ofsY = append(ofs.data(), ofs.size() * 4); slots[i].entY = append(ent.data(), std::max<size_t>(1, ent.size()) * 8);
+            x.push_back(pack_triangle_axis(ctx->triHost, p.sw, p.dw, (flags & DXTEX_FILTER_WRAP_U) != 0));
+            y.push_back(pack_triangle_axis(ctx->triHost, p.sh, p.dh, (flags & DXTEX_FILTER_WRAP_V) != 0));
         }
-        host.resize(host.size() + 16);
-        dxtex_hresult hr = upload_tables(ctx, host); if (hr != DXTEX_S_OK) return hr;
-        const uint8_t* d = static_cast<const uint8_t*>(ctx->triBuf);
+        dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
+        const uint8_t* d = ctx->triBuf.u8();
         for (size_t i = 0; i < pairs.size(); ++i)
         {
-            TriangleTables t;
-            t.ofsX = reinterpret_cast<const uint32_t*>(d + slots[i].ofsX); t.entX = d + slots[i].entX;
-            t.ofsY = reinterpret_cast<const uint32_t*>(d + slots[i].ofsY); t.entY = d + slots[i].entY;
+            const TriangleTables t = { tri_ofs(d, x[i]), d + x[i].ent, tri_ofs(d, y[i]), d + y[i].ent };
             const dxtex_hresult hr1 = resize_one(pairs[i], &t, nullptr, 0, 0);
             if (hr1 != DXTEX_S_OK) return hr1;
         }
@@ -1044,15 +991,7 @@ dxtex_hresult dxtex_generate_mips_device(dxtex_ctx* ctx, const dxtex_image* leve
     uint32_t mode = 0;
     dxtex_hresult hr = check_mips(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    std::vector<LevelPair> pairs;
-    for (size_t i = 1; i < nlevels; ++i)
-        pairs.push_back({ levels[i - 1].pixels, levels[i - 1].rowPitch, levels[i - 1].width, levels[i - 1].height,
-                          levels[i].pixels, levels[i].rowPitch, levels[i].width, levels[i].height });
-    time_begin(ctx);
-    hr = submit_resizes(ctx, pairs, levels[0].format, mode, filter, true);
-    time_end(ctx);
-    return hr;
+    return run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(levels, nlevels), levels[0].format, mode, filter, true); });
 }
 
 dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, size_t nlevels, uint32_t filter)
@@ -1061,23 +1000,17 @@ dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, siz
     dxtex_hresult hr = check_mips(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
     ScopedDevice sd(ctx->device);
-    // one device allocation holding the whole chain, 256-byte aligned levels
-    std::vector<size_t> at(nlevels);
-    size_t total = 0;
-    for (size_t i = 0; i < nlevels; ++i) { at[i] = total; total += (levels[i].rowPitch * levels[i].height + 255) & ~size_t(255); }
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, total); if (hr != DXTEX_S_OK) return hr;
-    uint8_t* d = static_cast<uint8_t*>(ctx->stageIn);
-    HIP_TRY(ctx, counted_copy(ctx, d, levels[0].pixels, levels[0].rowPitch * levels[0].height, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<LevelPair> pairs;
-    for (size_t i = 1; i < nlevels; ++i)
-        pairs.push_back({ d + at[i - 1], levels[i - 1].rowPitch, levels[i - 1].width, levels[i - 1].height,
-                          d + at[i], levels[i].rowPitch, levels[i].width, levels[i].height });
-    time_begin(ctx);
-    hr = submit_resizes(ctx, pairs, levels[0].format, mode, filter, true);
-    time_end(ctx);
+    // one device allocation holding the whole chain
+    std::vector<size_t> bytes(nlevels);
+    for (size_t i = 0; i < nlevels; ++i) bytes[i] = levels[i].rowPitch * levels[i].height;
+    const Arena a(bytes.data(), nlevels);
+    hr = ctx->stageIn.grow(ctx, a.total); if (hr != DXTEX_S_OK) return hr;
+    const std::vector<dxtex_image> d = in_arena(levels, nlevels, ctx->stageIn.u8(), a);
+    HIP_TRY(ctx, counted_copy(ctx, d[0].pixels, levels[0].pixels, bytes[0], hipMemcpyHostToDevice, ctx->stream));
+    hr = run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(d.data(), nlevels), levels[0].format, mode, filter, true); });
     if (hr != DXTEX_S_OK) return hr;
     for (size_t i = 1; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, d + at[i], levels[i].rowPitch * levels[i].height, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, d[i].pixels, bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
@@ -1118,27 +1051,19 @@ dxtex_hresult check_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nl
 dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, uint32_t mode, uint32_t flags)
 {
     const int format = lv[0].format;
-    struct Slot { size_t ofsX, entX, ofsY, entY, ofsZ, entZ; };
-    std::vector<Slot> slots(lv.size());
+    std::vector<TriAxis> x(lv.size()), y(lv.size()), z(lv.size());      // [i]: level i - 1 -> level i
     const uint8_t* tri = nullptr;
     if (mode == DXTEX_FILTER_TRIANGLE)
     {
-        std::vector<uint8_t>& host = ctx->triHost;
-        host.clear();
-        std::vector<uint32_t> ofs; std::vector<TriEntry> ent;
-        auto append = [&](const void* p, size_t bytes) { const size_t at = (host.size() + 15) & ~size_t(15); host.resize(at + bytes); std::memcpy(host.data() + at, p, bytes); return at; };
+        ctx->triHost.clear();
         for (size_t i = 1; i < lv.size(); ++i)
         {
-            build_triangle_axis(lv[i - 1].width, lv[i].width, (flags & DXTEX_FILTER_WRAP_U) != 0, ofs, ent);
-            slots[i].ofsX = append(ofs.data(), ofs.size() * 4); slots[i].entX = append(ent.data(), std::max<size_t>(1, ent.size()) * 8);
-            build_triangle_axis(lv[i - 1].height, lv[i].height, (flags & DXTEX_FILTER_WRAP_V) != 0, ofs, ent);
-            slots[i].ofsY = append(ofs.data(), ofs.size() * 4); slots[i].entY = append(ent.data(), std::max<size_t>(1, ent.size()) * 8);
-            build_triangle_axis(lv[i - 1].depth, lv[i].depth, (flags & 0x4u) != 0, ofs, ent);
-            slots[i].ofsZ = append(ofs.data(), ofs.size() * 4); slots[i].entZ = append(ent.data(), std::max<size_t>(1, ent.size()) * 8);
+            x[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].width, lv[i].width, (flags & DXTEX_FILTER_WRAP_U) != 0);
+            y[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].height, lv[i].height, (flags & DXTEX_FILTER_WRAP_V) != 0);
+            z[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].depth, lv[i].depth, (flags & 0x4u) != 0);
         }
-        host.resize(host.size() + 16);
-        dxtex_hresult hr = upload_tables(ctx, host); if (hr != DXTEX_S_OK) return hr;
-        tri = static_cast<const uint8_t*>(ctx->triBuf);
+        dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
+        tri = ctx->triBuf.u8();
     }
     const VolumeView* twoHigh = nullptr;     // box: the last SOURCE level that was 2 texels high (what urow1 / vrow1's old buffers hold)
     for (size_t i = 1; i < lv.size(); ++i)
@@ -1153,12 +1078,7 @@ dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, u
         if (s.depth > 1 || mode == DXTEX_FILTER_TRIANGLE)
         {
             TriangleTables3 t{};
-            if (tri)
-            {
-                t.ofsX = reinterpret_cast<const uint32_t*>(tri + slots[i].ofsX); t.entX = tri + slots[i].entX;
-                t.ofsY = reinterpret_cast<const uint32_t*>(tri + slots[i].ofsY); t.entY = tri + slots[i].entY;
-                t.ofsZ = reinterpret_cast<const uint32_t*>(tri + slots[i].ofsZ); t.entZ = tri + slots[i].entZ;
-            }
+            if (tri) t = { tri_ofs(tri, x[i]), tri + x[i].ent, tri_ofs(tri, y[i]), tri + y[i].ent, tri_ofs(tri, z[i]), tri + z[i].ent };
             e = launch_resize3d(s, d, mode, flags, tri ? &t : nullptr, ctx->stream, staleU, staleV, stale ? twoHigh->rowPitch : 0, stale ? twoHigh->width : 0u);
         }
         else
@@ -1182,13 +1102,9 @@ dxtex_hresult dxtex_generate_mips3d_device(dxtex_ctx* ctx, const dxtex_volume* l
     uint32_t mode = 0;
     dxtex_hresult hr = check_mips3d(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
     std::vector<VolumeView> lv(nlevels);
     for (size_t i = 0; i < nlevels; ++i) lv[i] = view_of(levels[i], levels[i].pixels);
-    time_begin(ctx);
-    hr = submit_mips3d(ctx, lv, mode, filter);
-    time_end(ctx);
-    return hr;
+    return run_timed(ctx, [&] { return submit_mips3d(ctx, lv, mode, filter); });
 }
 
 dxtex_hresult dxtex_generate_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nlevels, uint32_t filter)
@@ -1197,20 +1113,17 @@ dxtex_hresult dxtex_generate_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, 
     dxtex_hresult hr = check_mips3d(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
     ScopedDevice sd(ctx->device);
-    std::vector<size_t> at(nlevels);
-    size_t total = 0;
-    for (size_t i = 0; i < nlevels; ++i) { at[i] = total; total += (levels[i].slicePitch * levels[i].depth + 255) & ~size_t(255); }
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, total); if (hr != DXTEX_S_OK) return hr;
-    uint8_t* d = static_cast<uint8_t*>(ctx->stageIn);
-    HIP_TRY(ctx, counted_copy(ctx, d, levels[0].pixels, levels[0].slicePitch * levels[0].depth, hipMemcpyHostToDevice, ctx->stream));
+    std::vector<size_t> bytes(nlevels);
+    for (size_t i = 0; i < nlevels; ++i) bytes[i] = levels[i].slicePitch * levels[i].depth;
+    const Arena a(bytes.data(), nlevels);
+    hr = ctx->stageIn.grow(ctx, a.total); if (hr != DXTEX_S_OK) return hr;
     std::vector<VolumeView> lv(nlevels);
-    for (size_t i = 0; i < nlevels; ++i) lv[i] = view_of(levels[i], d + at[i]);
-    time_begin(ctx);
-    hr = submit_mips3d(ctx, lv, mode, filter);
-    time_end(ctx);
+    for (size_t i = 0; i < nlevels; ++i) lv[i] = view_of(levels[i], ctx->stageIn.u8() + a.at[i]);
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, levels[0].pixels, bytes[0], hipMemcpyHostToDevice, ctx->stream));
+    hr = run_timed(ctx, [&] { return submit_mips3d(ctx, lv, mode, filter); });
     if (hr != DXTEX_S_OK) return hr;
     for (size_t i = 1; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, d + at[i], levels[i].slicePitch * levels[i].depth, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, lv[i].pixels, bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
@@ -1239,6 +1152,11 @@ dxtex_hresult check_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_i
     *mode = m;
     return DXTEX_S_OK;
 }
+
+dxtex_hresult submit_resize(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t mode, uint32_t filter)
+{
+    return submit_resizes(ctx, { pair_of(src, dst) }, src.format, mode, filter, false);
+}
 } // namespace
 
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter)
@@ -1246,12 +1164,7 @@ dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const 
     uint32_t mode = 0;
     dxtex_hresult hr = check_resize(ctx, src, dst, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    std::vector<LevelPair> pairs{ { src->pixels, src->rowPitch, src->width, src->height, dst->pixels, dst->rowPitch, dst->width, dst->height } };
-    time_begin(ctx);
-    hr = submit_resizes(ctx, pairs, src->format, mode, filter, false);
-    time_end(ctx);
-    return hr;
+    return run_timed(ctx, [&] { return submit_resize(ctx, *src, *dst, mode, filter); });
 }
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter)
@@ -1259,21 +1172,10 @@ dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_i
     uint32_t mode = 0;
     dxtex_hresult hr = check_resize(ctx, src, dst, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
     size_t srcBytes = 0, dstBytes = 0;
     hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, src->pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<LevelPair> pairs{ { static_cast<const uint8_t*>(ctx->stageIn), src->rowPitch, src->width, src->height,
-                                    static_cast<uint8_t*>(ctx->stageOut), dst->rowPitch, dst->width, dst->height } };
-    time_begin(ctx);
-    hr = submit_resizes(ctx, pairs, src->format, mode, filter, false);
-    time_end(ctx);
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, dst->pixels, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      { return submit_resize(ctx, with_pixels(*src, in), with_pixels(*dst, out), mode, filter); });
 }
 
 namespace
@@ -1299,12 +1201,13 @@ static const uint32_t kDitherSegment = dev_env("DXTEX_DITHER_SEGMENT") ? uint32_
 
 // the conversion kernel, through float rows + the pack kernel when the destination's element holds several texels. ConvertCustom's
 // branches (:4820-4910): TEX_FILTER_DITHER_DIFFUSION first, then TEX_FILTER_DITHER; z is the slice of a volume (ordered dithering's phase).
-dxtex_hresult submit_convert(dxtex_ctx* ctx, const uint8_t* dSrc, size_t srcPitch, int srcFormat, uint8_t* dDst, size_t dstPitch, int dstFormat,
-                             size_t width, size_t height, const ConvertPlan& basePlan, float threshold, uint32_t filter, uint32_t z)
+dxtex_hresult submit_convert(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, const ConvertPlan& basePlan, float threshold,
+                             uint32_t filter, uint32_t z)
 {
+    const size_t width = src.width, height = src.height;
     int dither = CONVERT_DITHER_NONE;
     ConvertPlan plan = basePlan;
-    if ((filter & (kFilterDitherDiffusion | kFilterDitherOrdered)) && dither_spec(dstFormat).valid)
+    if ((filter & (kFilterDitherDiffusion | kFilterDitherOrdered)) && dither_spec(dst.format).valid)
     {
         // a dithered store sees ConvertScanline's NaNs as they are (XMVectorClamp keeps them)
         if (plan.tcv == TCV_CLAMP_SNORM) plan.tcv = TCV_CLAMP_SNORM_NAN;
@@ -1312,34 +1215,34 @@ dxtex_hresult submit_convert(dxtex_ctx* ctx, const uint8_t* dSrc, size_t srcPitc
     }
     if (filter & kFilterDitherDiffusion)
     {
-        if (dither_spec(dstFormat).valid)
+        if (dither_spec(dst.format).valid)
         {
-            dxtex_hresult hr = ensure(ctx, &ctx->ditherRows, &ctx->ditherRowsBytes, convert_diffuse_scratch_bytes(uint32_t(width)));
+            dxtex_hresult hr = ctx->ditherRows.grow(ctx, convert_diffuse_scratch_bytes(uint32_t(width)));
             if (hr != DXTEX_S_OK) return hr;
-            if (!ctx->ditherRerun)
+            if (!ctx->ditherRerun.p)
             {
-                HIP_TRY(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->ditherRerun), sizeof(unsigned long long)));
-                HIP_TRY(ctx, hipMemsetAsync(ctx->ditherRerun, 0, sizeof(unsigned long long), ctx->stream));
+                hr = ctx->ditherRerun.grow(ctx, sizeof(unsigned long long), sizeof(unsigned long long)); if (hr != DXTEX_S_OK) return hr;
+                HIP_TRY(ctx, hipMemsetAsync(ctx->ditherRerun.p, 0, sizeof(unsigned long long), ctx->stream));
             }
             ctx->ditherTexels += uint64_t(width) * height;
-            const hipError_t e = launch_convert_diffuse(dSrc, srcPitch, srcFormat, dDst, dstPitch, dstFormat, uint32_t(width), uint32_t(height), plan, threshold,
-                                                        ctx->ditherRows, ctx->ditherRerun, kDitherSegment, ctx->stream);
+            const hipError_t e = launch_convert_diffuse(src.pixels, src.rowPitch, src.format, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), plan, threshold,
+                                                        ctx->ditherRows.p, static_cast<unsigned long long*>(ctx->ditherRerun.p), kDitherSegment, ctx->stream);
             return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
         }
         dither = CONVERT_DITHER_ZERO_ERROR;      // no dithered store: StoreScanline after the zero error row
     }
     else if (filter & kFilterDitherOrdered) dither = CONVERT_DITHER_ORDERED;
-    uint8_t* out = dDst; size_t outPitch = dstPitch; int outFormat = dstFormat;
-    const bool grouped = is_group_format(dstFormat);
+    uint8_t* out = dst.pixels; size_t outPitch = dst.rowPitch; int outFormat = dst.format;
+    const bool grouped = is_group_format(dst.format);
     if (grouped)
     {
         const dxtex_hresult hr = group_rows(ctx, width, height, &out, &outPitch);
         if (hr != DXTEX_S_OK) return hr;
         outFormat = FMT_R32G32B32A32_FLOAT;
     }
-    hipError_t e = launch_convert(dSrc, srcPitch, srcFormat, out, outPitch, outFormat, uint32_t(width), uint32_t(height), plan, threshold, ctx->stream,
+    hipError_t e = launch_convert(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), plan, threshold, ctx->stream,
                                   dither, z);
-    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dDst, dstPitch, dstFormat, uint32_t(width), uint32_t(height), ctx->stream);
+    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream);
     return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
 }
 } // namespace
@@ -1349,12 +1252,7 @@ dxtex_hresult dxtex_convert_slice_device(dxtex_ctx* ctx, const dxtex_image* src,
     ConvertPlan plan;
     dxtex_hresult hr = check_convert(ctx, src, dst, filter, &plan);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    time_begin(ctx);
-    hr = submit_convert(ctx, src->pixels, src->rowPitch, src->format, dst->pixels, dst->rowPitch, dst->format, src->width, src->height, plan, threshold,
-                        filter, z);
-    time_end(ctx);
-    return hr;
+    return run_timed(ctx, [&] { return submit_convert(ctx, *src, *dst, plan, threshold, filter, z); });
 }
 
 dxtex_hresult dxtex_convert_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter, float threshold)
@@ -1372,9 +1270,9 @@ dxtex_hresult dxtex_convert_dither_stats(dxtex_ctx* ctx, uint64_t* rerunTexels, 
     if (!ctx || !rerunTexels || !texels) return DXTEX_E_POINTER;
     ScopedDevice sd(ctx->device);
     unsigned long long n = 0;
-    if (ctx->ditherRerun)
+    if (ctx->ditherRerun.p)
     {
-        HIP_TRY(ctx, counted_copy(ctx, &n, ctx->ditherRerun, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, counted_copy(ctx, &n, ctx->ditherRerun.p, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     *rerunTexels = n; *texels = ctx->ditherTexels;
@@ -1386,20 +1284,10 @@ dxtex_hresult dxtex_convert_slice(dxtex_ctx* ctx, const dxtex_image* src, const 
     ConvertPlan plan;
     dxtex_hresult hr = check_convert(ctx, src, dst, filter, &plan);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
     size_t srcBytes = 0, dstBytes = 0;
     hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, src->pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-    time_begin(ctx);
-    hr = submit_convert(ctx, static_cast<const uint8_t*>(ctx->stageIn), src->rowPitch, src->format, static_cast<uint8_t*>(ctx->stageOut),
-                        dst->rowPitch, dst->format, src->width, src->height, plan, threshold, filter, z);
-    time_end(ctx);
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, dst->pixels, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      { return submit_convert(ctx, with_pixels(*src, in), with_pixels(*dst, out), plan, threshold, filter, z); });
 }
 
 namespace
@@ -1417,15 +1305,21 @@ dxtex_hresult check_pmalpha(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_
     return DXTEX_S_OK;
 }
 
-// EstimateAlphaScaleForCoverage (DirectXTexMipmaps.cpp:310-352) around the device coverage count
-dxtex_hresult alpha_coverage(dxtex_ctx* ctx, const uint8_t* d, const dxtex_image& im, float scale, float alphaReference, float* coverage)
+dxtex_hresult submit_pmalpha(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags)
 {
-    dxtex_hresult hr = ensure(ctx, &ctx->mseBuf, &ctx->mseBytes, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-    hipError_t e = launch_alpha_coverage(d, im.rowPitch, im.format, uint32_t(im.width), uint32_t(im.height), scale, alphaReference,
-                                         static_cast<unsigned long long*>(ctx->mseBuf), ctx->stream);
+    const hipError_t e = launch_pmalpha(src.pixels, src.rowPitch, dst.pixels, dst.rowPitch, src.format, uint32_t(src.width), uint32_t(src.height), flags, ctx->stream);
+    return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+}
+
+// EstimateAlphaScaleForCoverage (DirectXTexMipmaps.cpp:310-352) around the device coverage count
+dxtex_hresult alpha_coverage(dxtex_ctx* ctx, const dxtex_image& im, float scale, float alphaReference, float* coverage)
+{
+    dxtex_hresult hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    hipError_t e = launch_alpha_coverage(im.pixels, im.rowPitch, im.format, uint32_t(im.width), uint32_t(im.height), scale, alphaReference,
+                                         static_cast<unsigned long long*>(ctx->mseBuf.p), ctx->stream);
     if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     unsigned long long n = 0;
-    HIP_TRY(ctx, counted_copy(ctx, &n, ctx->mseBuf, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, counted_copy(ctx, &n, ctx->mseBuf.p, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const float cscale = static_cast<float>((im.width - 1) * (im.height - 1) * 8 * 8);      // :299-303
     *coverage = (cscale > 0.f) ? static_cast<float>(size_t(n)) / cscale : 0.0f;
@@ -1449,15 +1343,14 @@ dxtex_hresult check_coverage_chain(dxtex_ctx* ctx, const dxtex_image* src, const
 }
 
 // the body of ScaleMipMapsAlphaForCoverage (:3503-3553) on device-resident levels
-dxtex_hresult submit_coverage_chain(dxtex_ctx* ctx, const std::vector<const uint8_t*>& s, const std::vector<uint8_t*>& d, const dxtex_image* src,
-                                    const dxtex_image* dst, size_t nlevels, float alphaReference)
+dxtex_hresult submit_coverage_chain(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, size_t nlevels, float alphaReference)
 {
     float target = 0.0f;
-    dxtex_hresult hr = alpha_coverage(ctx, s[0], src[0], 1.0f, alphaReference, &target);
+    dxtex_hresult hr = alpha_coverage(ctx, src[0], 1.0f, alphaReference, &target);
     if (hr != DXTEX_S_OK) return hr;
     const FmtInfo* f = format_info(src[0].format);
     const size_t rowBytes = (src[0].width * f->bpp + 7) / 8;
-    HIP_TRY(ctx, hipMemcpy2DAsync(d[0], dst[0].rowPitch, s[0], src[0].rowPitch, std::min(rowBytes, std::min(src[0].rowPitch, dst[0].rowPitch)), src[0].height,
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst[0].pixels, dst[0].rowPitch, src[0].pixels, src[0].rowPitch, std::min(rowBytes, std::min(src[0].rowPitch, dst[0].rowPitch)), src[0].height,
                                   hipMemcpyDeviceToDevice, ctx->stream));
     for (size_t level = 1; level < nlevels; ++level)
     {
@@ -1465,14 +1358,14 @@ dxtex_hresult submit_coverage_chain(dxtex_ctx* ctx, const std::vector<const uint
         for (int i = 0; i < 10; ++i)
         {
             float cov = 0.0f;
-            hr = alpha_coverage(ctx, s[level], src[level], scale, alphaReference, &cov);
+            hr = alpha_coverage(ctx, src[level], scale, alphaReference, &cov);
             if (hr != DXTEX_S_OK) return hr;
             if (cov < target) lo = scale;
             else if (cov > target) hi = scale;
             else break;
             scale = (lo + hi) * 0.5f;
         }
-        hipError_t e = launch_scale_alpha(s[level], src[level].rowPitch, d[level], dst[level].rowPitch, src[level].format, uint32_t(src[level].width),
+        hipError_t e = launch_scale_alpha(src[level].pixels, src[level].rowPitch, dst[level].pixels, dst[level].rowPitch, src[level].format, uint32_t(src[level].width),
                                           uint32_t(src[level].height), scale, ctx->stream);
         if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     }
@@ -1484,32 +1377,17 @@ dxtex_hresult dxtex_premultiply_alpha_device(dxtex_ctx* ctx, const dxtex_image* 
 {
     dxtex_hresult hr = check_pmalpha(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    time_begin(ctx);
-    hipError_t e = launch_pmalpha(src->pixels, src->rowPitch, dst->pixels, dst->rowPitch, src->format, uint32_t(src->width), uint32_t(src->height), flags, ctx->stream);
-    time_end(ctx);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-    return DXTEX_S_OK;
+    return run_timed(ctx, [&] { return submit_pmalpha(ctx, *src, *dst, flags); });
 }
 
 dxtex_hresult dxtex_premultiply_alpha(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags)
 {
     dxtex_hresult hr = check_pmalpha(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
     size_t srcBytes = 0, dstBytes = 0;
     hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, srcBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn, src->pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
-    time_begin(ctx);
-    hipError_t e = launch_pmalpha(static_cast<const uint8_t*>(ctx->stageIn), src->rowPitch, static_cast<uint8_t*>(ctx->stageOut), dst->rowPitch, src->format,
-                                  uint32_t(src->width), uint32_t(src->height), flags, ctx->stream);
-    time_end(ctx);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-    HIP_TRY(ctx, counted_copy(ctx, dst->pixels, ctx->stageOut, dstBytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      { return submit_pmalpha(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags); });
 }
 
 dxtex_hresult dxtex_scale_mips_alpha_for_coverage_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, size_t nlevels, float alphaReference)
@@ -1517,9 +1395,7 @@ dxtex_hresult dxtex_scale_mips_alpha_for_coverage_device(dxtex_ctx* ctx, const d
     dxtex_hresult hr = check_coverage_chain(ctx, src, dst, nlevels);
     if (hr != DXTEX_S_OK) return hr;
     ScopedDevice sd(ctx->device);
-    std::vector<const uint8_t*> s(nlevels); std::vector<uint8_t*> d(nlevels);
-    for (size_t i = 0; i < nlevels; ++i) { s[i] = src[i].pixels; d[i] = dst[i].pixels; }
-    return submit_coverage_chain(ctx, s, d, src, dst, nlevels, alphaReference);
+    return submit_coverage_chain(ctx, src, dst, nlevels, alphaReference);
 }
 
 dxtex_hresult dxtex_scale_mips_alpha_for_coverage(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, size_t nlevels, float alphaReference)
@@ -1527,26 +1403,19 @@ dxtex_hresult dxtex_scale_mips_alpha_for_coverage(dxtex_ctx* ctx, const dxtex_im
     dxtex_hresult hr = check_coverage_chain(ctx, src, dst, nlevels);
     if (hr != DXTEX_S_OK) return hr;
     ScopedDevice sd(ctx->device);
-    std::vector<size_t> atS(nlevels), atD(nlevels);
-    size_t totalS = 0, totalD = 0;
+    std::vector<size_t> srcBytes(nlevels), dstBytes(nlevels);
+    for (size_t i = 0; i < nlevels; ++i) { srcBytes[i] = src[i].rowPitch * src[i].height; dstBytes[i] = dst[i].rowPitch * dst[i].height; }
+    const Arena as(srcBytes.data(), nlevels), ad(dstBytes.data(), nlevels);
+    hr = ctx->stageIn.grow(ctx, as.total); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, ad.total); if (hr != DXTEX_S_OK) return hr;
+    const std::vector<dxtex_image> s = in_arena(src, nlevels, ctx->stageIn.u8(), as), d = in_arena(dst, nlevels, ctx->stageOut.u8(), ad);
     for (size_t i = 0; i < nlevels; ++i)
-    {
-        atS[i] = totalS; totalS += (src[i].rowPitch * src[i].height + 255) & ~size_t(255);
-        atD[i] = totalD; totalD += (dst[i].rowPitch * dst[i].height + 255) & ~size_t(255);
-    }
-    hr = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, totalS); if (hr != DXTEX_S_OK) return hr;
-    hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, totalD); if (hr != DXTEX_S_OK) return hr;
-    std::vector<const uint8_t*> s(nlevels); std::vector<uint8_t*> d(nlevels);
-    for (size_t i = 0; i < nlevels; ++i)
-    {
-        s[i] = static_cast<const uint8_t*>(ctx->stageIn) + atS[i]; d[i] = static_cast<uint8_t*>(ctx->stageOut) + atD[i];
-        HIP_TRY(ctx, counted_copy(ctx, static_cast<uint8_t*>(ctx->stageIn) + atS[i], src[i].pixels, src[i].rowPitch * src[i].height, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemsetAsync(ctx->stageOut, 0, totalD, ctx->stream));
-    hr = submit_coverage_chain(ctx, s, d, src, dst, nlevels, alphaReference);
+        HIP_TRY(ctx, counted_copy(ctx, s[i].pixels, src[i].pixels, srcBytes[i], hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->stageOut.p, 0, ad.total, ctx->stream));
+    hr = submit_coverage_chain(ctx, s.data(), d.data(), nlevels, alphaReference);
     if (hr != DXTEX_S_OK) return hr;
     for (size_t i = 0; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, dst[i].pixels, d[i], dst[i].rowPitch * dst[i].height, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, counted_copy(ctx, dst[i].pixels, d[i].pixels, dstBytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
@@ -1560,12 +1429,12 @@ dxtex_hresult dxtex_compute_mse_device(dxtex_ctx* ctx, const dxtex_image* a, con
     const FmtInfo* fb = format_info(b->format);
     if (!fa || !fb || (fa->cls & FC_BC) || (fb->cls & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "ComputeMSE takes uncompressed images (decompress first)");
     ScopedDevice sd(ctx->device);
-    hr = ensure(ctx, &ctx->mseBuf, &ctx->mseBytes, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
     hipError_t e = launch_mse(a->pixels, a->rowPitch, a->format, b->pixels, b->rowPitch, b->format, uint32_t(a->width), uint32_t(a->height),
-                              static_cast<double*>(ctx->mseBuf), ctx->stream);
+                              static_cast<double*>(ctx->mseBuf.p), ctx->stream);
     if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     double sum[4];
-    HIP_TRY(ctx, counted_copy(ctx, sum, ctx->mseBuf, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, counted_copy(ctx, sum, ctx->mseBuf.p, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const double n = double(a->width) * double(a->height);
     for (int c = 0; c < 4; ++c) mse[c] = sum[c] / n;
@@ -1658,14 +1527,13 @@ dxtex_hresult dxtex_alpha_all_opaque_device(dxtex_ctx* ctx, const dxtex_image* i
     if (!images || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
     const FmtInfo* f = format_info(images[0].format);
     if (!f || (f->cls & FC_GROUP)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "format is not supported by the MI355X path");
-    // HasAlpha (DirectXTexUtil.cpp:340-372): of the BC formats BC1 / BC2 / BC3 / BC7 carry alpha; a format without alpha is opaque (:805-806)
+    // HasAlpha (DirectXTexUtil.cpp:340-372): of the BC formats BC1 / BC2 / BC3 / BC7 carry alpha (BC4 / BC5 have no A channel in the format
+    // table, BC6H has one there but carries none); a format without alpha is opaque (:805-806)
     const bool bc = (f->cls & FC_BC) != 0;
-    const bool bcAlpha = bc && bc_block_bytes(f->format) && f->format != FMT_BC4_UNORM && f->format != FMT_BC4_SNORM && f->format != FMT_BC5_UNORM &&
-                         f->format != FMT_BC5_SNORM && f->format != FMT_BC6H_UF16 && f->format != FMT_BC6H_SF16;
-    if ((bc && !bcAlpha) || (!bc && !(f->cls & FC_A))) { *opaque = 1; return DXTEX_S_OK; }
+    if (!(f->cls & FC_A) || is_bc6h(f->format)) { *opaque = 1; return DXTEX_S_OK; }
     ScopedDevice sd(ctx->device);
-    dxtex_hresult hr = ensure(ctx, &ctx->mseBuf, &ctx->mseBytes, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-    unsigned long long* counter = static_cast<unsigned long long*>(ctx->mseBuf);
+    dxtex_hresult hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    unsigned long long* counter = static_cast<unsigned long long*>(ctx->mseBuf.p);
     HIP_TRY(ctx, hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
     for (size_t i = 0; i < count; ++i)
     {
@@ -1678,10 +1546,10 @@ dxtex_hresult dxtex_alpha_all_opaque_device(dxtex_ctx* ctx, const dxtex_image* i
         {
             // IsAlphaAllOpaqueBC decodes every block to floats and tests the texels inside the image against 0.99
             const size_t pitch = im.width * 16;
-            hr = ensure(ctx, &ctx->stageOut, &ctx->stageOutBytes, pitch * im.height); if (hr != DXTEX_S_OK) return hr;
-            hr = submit_decompress(ctx, im.pixels, im.format, im.rowPitch, static_cast<uint8_t*>(ctx->stageOut), FMT_R32G32B32A32_FLOAT, pitch, im.width, im.height);
+            hr = ctx->stageOut.grow(ctx, pitch * im.height); if (hr != DXTEX_S_OK) return hr;
+            hr = submit_decompress(ctx, im, { im.width, im.height, FMT_R32G32B32A32_FLOAT, pitch, pitch * im.height, ctx->stageOut.u8() });
             if (hr != DXTEX_S_OK) return hr;
-            e = launch_alpha_below(static_cast<const uint8_t*>(ctx->stageOut), pitch, FMT_R32G32B32A32_FLOAT, uint32_t(im.width), uint32_t(im.height), 0.99f, counter, ctx->stream);
+            e = launch_alpha_below(ctx->stageOut.u8(), pitch, FMT_R32G32B32A32_FLOAT, uint32_t(im.width), uint32_t(im.height), 0.99f, counter, ctx->stream);
         }
         else
             e = launch_alpha_below(im.pixels, im.rowPitch, im.format, uint32_t(im.width), uint32_t(im.height), 0.997f, counter, ctx->stream);
@@ -1834,12 +1702,12 @@ dxtex_hresult dxtex_generate_mips_multi(dxtex_ctx* const* ctxs, size_t nctx, con
             E[0] = C[0];
             if (C[L].b <= C[L].a) return DXTEX_S_OK;
             // one arena for the context's rows of every level (the staging buffer of the single-image calls, reused across calls)
-            std::vector<size_t> at(L + 1);
-            size_t bytes = 0;
-            for (size_t l = 0; l <= L; ++l) { at[l] = bytes; bytes += ((E[l].b - E[l].a) * levels[l].rowPitch + 255) & ~size_t(255); }
+            std::vector<size_t> bytes(L + 1);
+            for (size_t l = 0; l <= L; ++l) bytes[l] = (E[l].b - E[l].a) * levels[l].rowPitch;
+            const Arena a(bytes.data(), L + 1);
             ScopedDevice sd(ctx->device);
-            dxtex_hresult h = ensure(ctx, &ctx->stageIn, &ctx->stageInBytes, bytes); if (h != DXTEX_S_OK) return h;
-            uint8_t* arena = static_cast<uint8_t*>(ctx->stageIn);
+            dxtex_hresult h = ctx->stageIn.grow(ctx, a.total); if (h != DXTEX_S_OK) return h;
+            uint8_t* arena = ctx->stageIn.u8();
             // rows [a, b) of level l as one copy: whole pitches, the last row only as far as its texels go (a host image may end there)
             auto span = [&](size_t l, const Rows& r) -> size_t
             {
@@ -1847,13 +1715,13 @@ dxtex_hresult dxtex_generate_mips_multi(dxtex_ctx* const* ctxs, size_t nctx, con
                 (void)dxtex_compute_pitch(levels[l].format, levels[l].width, 1, &minRow, &minSlice);
                 return (r.b - r.a - 1) * levels[l].rowPitch + minRow;
             };
-            HIP_TRY(ctx, counted_copy(ctx, arena + at[0], levels[0].pixels + E[0].a * levels[0].rowPitch, span(0, E[0]), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, counted_copy(ctx, arena + a.at[0], levels[0].pixels + E[0].a * levels[0].rowPitch, span(0, E[0]), hipMemcpyHostToDevice, ctx->stream));
             time_begin(ctx);
             for (size_t l = 1; l <= L; ++l)
             {
                 const size_t s0 = 2 * E[l].a;         // first row of the source sub-image, inside [E[l - 1].a, E[l - 1].b)
-                std::vector<LevelPair> pairs{ { arena + at[l - 1] + (s0 - E[l - 1].a) * levels[l - 1].rowPitch, levels[l - 1].rowPitch, levels[l - 1].width, 2 * (E[l].b - E[l].a),
-                                                arena + at[l], levels[l].rowPitch, levels[l].width, E[l].b - E[l].a } };
+                std::vector<LevelPair> pairs{ { arena + a.at[l - 1] + (s0 - E[l - 1].a) * levels[l - 1].rowPitch, levels[l - 1].rowPitch, levels[l - 1].width, 2 * (E[l].b - E[l].a),
+                                                arena + a.at[l], levels[l].rowPitch, levels[l].width, E[l].b - E[l].a } };
                 h = submit_resizes(ctx, pairs, levels[0].format, mode, explicitFilter, false);
                 if (h != DXTEX_S_OK) { time_end(ctx); return h; }
             }
@@ -1862,7 +1730,7 @@ dxtex_hresult dxtex_generate_mips_multi(dxtex_ctx* const* ctxs, size_t nctx, con
             {
                 const Rows o = owned(l);
                 if (o.b <= o.a) continue;
-                HIP_TRY(ctx, counted_copy(ctx, levels[l].pixels + o.a * levels[l].rowPitch, arena + at[l] + (o.a - E[l].a) * levels[l].rowPitch, span(l, o), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, counted_copy(ctx, levels[l].pixels + o.a * levels[l].rowPitch, arena + a.at[l] + (o.a - E[l].a) * levels[l].rowPitch, span(l, o), hipMemcpyDeviceToHost, ctx->stream));
             }
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             return DXTEX_S_OK;

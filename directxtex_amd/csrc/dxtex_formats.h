@@ -99,6 +99,9 @@ inline const FmtInfo* format_info(int format)
 }
 
 inline bool is_bc(int format) { const FmtInfo* f = format_info(format); return f && (f->cls & FC_BC); }
+inline bool is_bc7(int format) { return format == FMT_BC7_UNORM || format == FMT_BC7_UNORM_SRGB; }
+inline bool is_bc6h(int format) { return format == FMT_BC6H_UF16 || format == FMT_BC6H_SF16; }
+inline bool is_bc15(int format) { return is_bc(format) && !is_bc7(format) && !is_bc6h(format); }      // BC1 ... BC5
 inline size_t bc_block_bytes(int format)
 {
     switch (format)

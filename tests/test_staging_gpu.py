@@ -1,0 +1,221 @@
+"""The host-pointer entry points stage through the context's buffers: on one small odd-sized image each moves exactly the bytes its pitches
+give (dxtex_ctx_transfer_bytes), times its kernels (dxtex_ctx_last_kernel_ms), returns what the *_device variant returns on the same
+input, and a call that fails its argument checks moves nothing and returns the HRESULT of those checks."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import directxtex_amd as dx
+from directxtex_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+W, H = 37, 21
+RGBA8, RGBA16F, RGBG = dx.DXGI_FORMAT_R8G8B8A8_UNORM, dx.DXGI_FORMAT_R16G16B16A16_FLOAT, 68
+BC1, BC7 = dx.DXGI_FORMAT_BC1_UNORM, dx.DXGI_FORMAT_BC7_UNORM
+LINEAR = 0x200000
+E_FAIL, E_INVALIDARG = 0x80004005, 0x80070057
+
+
+def pitch(fmt, w=W, h=H):
+    return dx.compute_pitch(fmt, w, h)
+
+
+def moved(ctx, call):
+    """(h2d, d2h) bytes of one call, with the counters reset before it."""
+    ctx.transfer_bytes(reset=True)
+    call()
+    return ctx.transfer_bytes()
+
+
+def refused(ctx, fn, *args):
+    """A raw C ABI call that must fail its checks: -> (HRESULT, bytes moved)."""
+    ctx.transfer_bytes(reset=True)
+    hr = getattr(ctx._lib, fn)(ctx._h, *args)
+    return hr & 0xFFFFFFFF, ctx.transfer_bytes()
+
+
+def host_image(arr, w, h, fmt, row_pitch=None):
+    rp, sp = pitch(fmt, w, h)
+    rp = row_pitch or rp
+    return dx.Image(w, h, fmt, rp, rp * (sp // pitch(fmt, w, h)[0]), arr.ctypes.data)
+
+
+class Device:
+    """Device copies of host buffers, freed on exit."""
+
+    def __init__(self, ctx):
+        self.ctx, self.ptrs = ctx, []
+
+    def put(self, arr):
+        p = self.ctx.device_alloc(max(1, arr.nbytes))
+        self.ctx.upload(p, arr, sync=True)
+        self.ptrs.append(p)
+        return p
+
+    def empty(self, nbytes):
+        p = self.ctx.device_alloc(nbytes, zero=True)
+        self.ptrs.append(p)
+        return p
+
+    def get(self, p, nbytes):
+        out = np.zeros(nbytes, np.uint8)
+        self.ctx.download(out, p, sync=True)
+        return out
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.ctx.synchronize()
+        for p in self.ptrs:
+            self.ctx.device_free(p)
+
+
+@pytest.fixture(scope="module")
+def img():
+    return synth.rgba8(W, H, seed=7, alpha="smooth")
+
+
+def test_compress_staging(ctx, img):
+    src_rp, src_sp = pitch(RGBA8)
+    for fmt in (BC1, BC7):
+        dst_rp, dst_sp = pitch(fmt)
+        out = {}
+        assert moved(ctx, lambda: out.setdefault("tight", ctx.compress(img, W, H, RGBA8, fmt))) == (src_sp, dst_sp)
+        assert ctx.last_kernel_ms() >= 0
+        # a padded source row pitch: the staging carries whole padded rows
+        padded = np.zeros((H, src_rp + 12), np.uint8)
+        padded[:, :src_rp] = img.reshape(H, src_rp)
+        assert moved(ctx, lambda: out.setdefault("padded", ctx.compress(padded, W, H, RGBA8, fmt, src_row_pitch=src_rp + 12))) == ((src_rp + 12) * H, dst_sp)
+        assert np.array_equal(out["padded"], out["tight"])
+        with Device(ctx) as d:
+            s, o = d.put(padded), d.empty(dst_sp)
+            ctx.compress_device(s, W, H, RGBA8, o, fmt, src_row_pitch=src_rp + 12)
+            assert np.array_equal(d.get(o, dst_sp), out["tight"])
+    # size mismatch: check_pair, before anything moves
+    src, dst = np.zeros(src_sp, np.uint8), np.zeros(pitch(BC1)[1], np.uint8)
+    assert refused(ctx, "dxtex_compress", ctypes.byref(host_image(src, W, H, RGBA8)), ctypes.byref(host_image(dst, W - 1, H, BC1)), 0, 0.5) == (E_FAIL, (0, 0))
+    # source row pitch below the format's minimum: check_host_pitches
+    assert refused(ctx, "dxtex_compress", ctypes.byref(host_image(src, W, H, RGBA8, src_rp - 4)), ctypes.byref(host_image(dst, W, H, BC1)), 0, 0.5) == (E_INVALIDARG, (0, 0))
+
+
+def test_decompress_staging(ctx, img):
+    bc = ctx.compress(img, W, H, RGBA8, BC1)
+    bc_sp, out_sp = pitch(BC1)[1], pitch(RGBA8)[1]
+    got = {}
+    assert moved(ctx, lambda: got.setdefault("host", ctx.decompress(bc, W, H, BC1, RGBA8))) == (bc_sp, out_sp)
+    assert ctx.last_kernel_ms() >= 0
+    with Device(ctx) as d:
+        s, o = d.put(bc), d.empty(out_sp)
+        ctx.decompress_device(s, W, H, BC1, o, RGBA8)
+        assert np.array_equal(d.get(o, out_sp), got["host"])
+    dst = np.zeros(out_sp, np.uint8)
+    assert refused(ctx, "dxtex_decompress", ctypes.byref(host_image(bc, W, H, BC1)), ctypes.byref(host_image(dst, W, H - 1, RGBA8))) == (E_FAIL, (0, 0))
+
+
+def test_block_staging(ctx, img):
+    n = 5
+    rgba = (img.reshape(-1, 4)[:n * 16].astype(np.float32) / 255.0).reshape(n, 16, 4)
+    blocks = {}
+    assert moved(ctx, lambda: blocks.setdefault("bc7", ctx.encode_blocks(BC7, rgba))) == (n * 256, n * 16)
+    assert ctx.last_kernel_ms() >= 0
+    assert moved(ctx, lambda: blocks.setdefault("bc1", ctx.encode_blocks(BC1, rgba))) == (n * 256, n * 8)
+    assert moved(ctx, lambda: ctx.decode_blocks(BC1, blocks["bc1"])) == (n * 8, n * 256)
+    assert ctx.last_kernel_ms() >= 0
+    f = np.zeros((n, 16, 4), np.float32)
+    b = np.zeros((n, 16), np.uint8)
+    assert refused(ctx, "dxtex_encode_blocks", RGBA8, 0, ctypes.c_float(0.5), f.ctypes.data, n, b.ctypes.data) == (E_INVALIDARG, (0, 0))
+    assert refused(ctx, "dxtex_decode_blocks", RGBA8, b.ctypes.data, n, f.ctypes.data) == (E_INVALIDARG, (0, 0))
+
+
+def test_resize_staging(ctx, img):
+    nw, nh = 20, 11
+    assert moved(ctx, lambda: ctx.resize(img, W, H, RGBA8, nw, nh, LINEAR)) == (pitch(RGBA8)[1], pitch(RGBA8, nw, nh)[1])
+    assert ctx.last_kernel_ms() >= 0
+    src, dst = np.zeros(pitch(RGBA8)[1], np.uint8), np.zeros(pitch(RGBA8, nw, nh)[1], np.uint8)
+    # source row pitch below the format's minimum: check_host_pitches
+    assert refused(ctx, "dxtex_resize", ctypes.byref(host_image(src, W, H, RGBA8, pitch(RGBA8)[0] - 4)), ctypes.byref(host_image(dst, nw, nh, RGBA8)),
+                   LINEAR) == (E_INVALIDARG, (0, 0))
+
+
+def test_convert_staging(ctx, img):
+    for fmt in (RGBA16F, RGBG):                       # RGBG: a packed two-texel destination (float rows + the pack kernel)
+        out_sp = pitch(fmt)[1]
+        got = {}
+        assert moved(ctx, lambda: got.setdefault("host", ctx.convert(img, W, H, RGBA8, fmt))) == (pitch(RGBA8)[1], out_sp)
+        assert ctx.last_kernel_ms() >= 0
+        with Device(ctx) as d:
+            s, o = d.put(img), d.empty(out_sp)
+            ctx.convert_device(s, W, H, RGBA8, o, fmt)
+            assert np.array_equal(d.get(o, out_sp), got["host"])
+    src, dst = np.zeros(pitch(RGBA8)[1], np.uint8), np.zeros(pitch(RGBA16F)[1], np.uint8)
+    assert refused(ctx, "dxtex_convert", ctypes.byref(host_image(src, W, H, RGBA8)), ctypes.byref(host_image(dst, W - 1, H, RGBA16F)),
+                   0, ctypes.c_float(0.5)) == (E_FAIL, (0, 0))
+
+
+def test_premultiply_staging(ctx, img):
+    sp = pitch(RGBA8)[1]
+    assert moved(ctx, lambda: ctx.premultiply_alpha(img, W, H, RGBA8)) == (sp, sp)
+    assert ctx.last_kernel_ms() >= 0
+    src, dst = np.zeros(sp, np.uint8), np.zeros(sp, np.uint8)
+    assert refused(ctx, "dxtex_premultiply_alpha", ctypes.byref(host_image(src, W, H, RGBA8)), ctypes.byref(host_image(dst, W, H - 1, RGBA8)), 0) == (E_FAIL, (0, 0))
+
+
+def chain(w, h, n):
+    dims = [(w, h)]
+    for _ in range(n - 1):
+        w, h = max(1, w >> 1), max(1, h >> 1)
+        dims.append((w, h))
+    return dims
+
+
+def test_generate_mips_staging(ctx, img):
+    n = 3
+    dims = chain(W, H, n)
+    sizes = [pitch(RGBA8, w, h)[1] for w, h in dims]
+    got = {}
+    assert moved(ctx, lambda: got.setdefault("host", ctx.generate_mips(img, W, H, RGBA8, n, 0))) == (sizes[0], sum(sizes[1:]))
+    assert ctx.last_kernel_ms() >= 0
+    with Device(ctx) as d:
+        ptrs = [d.put(img)] + [d.empty(s) for s in sizes[1:]]
+        ctx.generate_mips_device([dx.device_image(p, w, h, RGBA8) for p, (w, h) in zip(ptrs, dims)], 0)
+        for p, s, level in zip(ptrs[1:], sizes[1:], got["host"][1:]):
+            assert np.array_equal(d.get(p, s), level)
+    bufs = [np.zeros(s, np.uint8) for s in sizes]
+    levels = [host_image(b, w, h, RGBA8) for b, (w, h) in zip(bufs, dims)]
+    levels[1].height += 1                             # not a mip chain
+    assert refused(ctx, "dxtex_generate_mips", (dx.Image * n)(*levels), n, 0) == (E_INVALIDARG, (0, 0))
+
+
+def test_generate_mips3d_staging(ctx, img):
+    n, depth = 3, 3
+    vol = np.concatenate([img.reshape(-1)] * depth)
+    rp, sp = pitch(RGBA8)
+    dims = [(w, h, max(1, depth >> i)) for i, (w, h) in enumerate(chain(W, H, n))]
+    sizes = [pitch(RGBA8, w, h)[1] * d for w, h, d in dims]
+    # (linear: the triangle filter would also upload its gather tables)
+    assert moved(ctx, lambda: ctx.generate_mips3d(vol, W, H, depth, RGBA8, n, LINEAR)) == (sp * depth, sum(sizes[1:]))
+    assert ctx.last_kernel_ms() >= 0
+    bufs = [np.zeros(s, np.uint8) for s in sizes]
+    vols = [dx.capi.Volume(w, h, d, RGBA8, pitch(RGBA8, w, h)[0], pitch(RGBA8, w, h)[1], b.ctypes.data) for b, (w, h, d) in zip(bufs, dims)]
+    vols[1].depth += 1                                # not a volume mip chain
+    assert refused(ctx, "dxtex_generate_mips3d", (dx.capi.Volume * n)(*vols), n, 0) == (E_INVALIDARG, (0, 0))
+
+
+def test_coverage_staging(ctx, img):
+    n = 3
+    dims = chain(W, H, n)
+    levels = ctx.generate_mips(img, W, H, RGBA8, n, 0)
+    sizes = [pitch(RGBA8, w, h)[1] for w, h in dims]
+    # every level goes up and comes back; each coverage probe of the search also reads back its 8-byte count (one for level 0 alone,
+    # up to ten more per further level)
+    assert moved(ctx, lambda: ctx.scale_mips_alpha_for_coverage(levels[:1], W, H, RGBA8, 0.5)) == (sizes[0], sizes[0] + 8)
+    up, down = moved(ctx, lambda: ctx.scale_mips_alpha_for_coverage(levels, W, H, RGBA8, 0.5))
+    assert up == sum(sizes) and (down - sum(sizes)) % 8 == 0 and 8 * 3 <= down - sum(sizes) <= 8 * (1 + 10 * (n - 1))
+    outs = [np.zeros(s, np.uint8) for s in sizes]
+    src = [host_image(b, w, h, RGBA8) for b, (w, h) in zip(levels, dims)]
+    dst = [host_image(b, w, h, RGBA8) for b, (w, h) in zip(outs, dims)]
+    dst[2].width += 1                                 # a destination level of another size
+    assert refused(ctx, "dxtex_scale_mips_alpha_for_coverage", (dx.Image * n)(*src), (dx.Image * n)(*dst), n, ctypes.c_float(0.5)) == (E_FAIL, (0, 0))
