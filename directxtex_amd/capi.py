@@ -86,6 +86,8 @@ _SIGS = {
     "dxtex_convert_slice": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32]),
     "dxtex_convert_slice_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float, ctypes.c_uint32]),
     "dxtex_convert_dither_stats": (ctypes.c_int32, [_ctx_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),
+    "dxtex_compute_normal_map": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_compute_normal_map_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -454,6 +456,24 @@ class Context:
         rerun, total = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.dxtex_convert_dither_stats(self._h, ctypes.byref(rerun), ctypes.byref(total)), "convert_dither_stats")
         return rerun.value, total.value
+
+    # -- ComputeNormalMap ---------------------------------------------------------------------------
+    def compute_normal_map(self, pixels, width, height, src_format, dst_format, flags=0, amplitude=1.0, src_row_pitch=None):
+        """DirectX::ComputeNormalMap of one height map; flags = CNMAP_* (channel in the low 4 bits). Returns the destination
+        (tight pitch) as a numpy uint8 buffer."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, src_format, src_row_pitch)
+        rp, sp = compute_pitch(dst_format, width, height)
+        out = np.zeros(sp, np.uint8)
+        dst = Image(width, height, dst_format, rp, sp, out.ctypes.data)
+        self._check(self._lib.dxtex_compute_normal_map(self._h, ctypes.byref(src), ctypes.byref(dst), flags, amplitude), "compute_normal_map")
+        return out
+
+    def compute_normal_map_device(self, src_ptr, width, height, src_format, dst_ptr, dst_format, flags=0, amplitude=1.0, src_row_pitch=None):
+        """dxtex_compute_normal_map_device: device pointers (tight destination pitch), asynchronous on the context's stream."""
+        src = device_image(src_ptr, width, height, src_format, src_row_pitch)
+        dst = device_image(dst_ptr, width, height, dst_format)
+        self._check(self._lib.dxtex_compute_normal_map_device(self._h, ctypes.byref(src), ctypes.byref(dst), flags, amplitude), "compute_normal_map_device")
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

@@ -4,6 +4,7 @@
 #include "../../include/dxtex_amd.h"
 #include "dxtex_formats.h"
 #include "dxtex_kernels.h"
+#include "dxtex_nmap.h"
 #include "dxtex_plan.h"
 #include "triangle_filter.h"
 
@@ -1288,6 +1289,75 @@ dxtex_hresult dxtex_convert_slice(dxtex_ctx* ctx, const dxtex_image* src, const 
     hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
     return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
                       { return submit_convert(ctx, with_pixels(*src, in), with_pixels(*dst, out), plan, threshold, filter, z); });
+}
+
+namespace
+{
+// ComputeNormalMap's checks (DirectXTexNormalMaps.cpp:257-283, ComputeNMap :83-94), in its order; the destination's class decides the
+// encoding. Formats format_info() does not know (the ones GetConvertFlags has no entry for among them) are not supported here.
+dxtex_hresult check_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, bool* unorm)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    if (!src->pixels || !dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    const auto valid = [](int f) { return f >= 1 && f <= 191; };
+    if (!valid(src->format) || !valid(dst->format)) return fail(ctx, DXTEX_E_INVALIDARG, "invalid format");
+    if ((flags & NMAP_CHANNEL_MASK) > NMAP_CHANNEL_LUMINANCE) return fail(ctx, DXTEX_E_INVALIDARG, "invalid channel selector");
+    const FmtInfo* in = format_info(src->format);
+    const FmtInfo* out = format_info(dst->format);
+    if (!in || !out || ((in->cls | out->cls) & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "format is not supported by ComputeNormalMap");
+    if (!(out->cls & (FC_UNORM | FC_SNORM | FC_FLOAT))) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "destination is not a UNORM, SNORM or FLOAT format");
+    if (src->width != dst->width || src->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
+    if (!src->width || !src->height) return DXTEX_S_OK;
+    // the stencil reads rows above and below the one it writes: it cannot run in place
+    size_t srcRow = 0, srcSlice = 0, dstRow = 0, dstSlice = 0;
+    if (dxtex_compute_pitch(src->format, src->width, src->height, &srcRow, &srcSlice) != DXTEX_S_OK ||
+        dxtex_compute_pitch(dst->format, dst->width, dst->height, &dstRow, &dstSlice) != DXTEX_S_OK)
+        return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src->pixels), d0 = reinterpret_cast<uintptr_t>(dst->pixels);
+    const uintptr_t s1 = s0 + src->rowPitch * (srcSlice / std::max<size_t>(1, srcRow) - 1) + srcRow;
+    const uintptr_t d1 = d0 + dst->rowPitch * (dstSlice / std::max<size_t>(1, dstRow) - 1) + dstRow;
+    if (s0 < d1 && d0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "source and destination pixels overlap");
+    *unorm = (out->cls & FC_UNORM) != 0;
+    return DXTEX_S_OK;
+}
+
+// the normal-map kernel, through float rows + the pack kernel when the destination's element holds several texels
+dxtex_hresult submit_normal_map(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags, float amplitude, bool unorm)
+{
+    const size_t width = src.width, height = src.height;
+    uint8_t* out = dst.pixels; size_t outPitch = dst.rowPitch; int outFormat = dst.format;
+    const bool grouped = is_group_format(dst.format);
+    if (grouped)
+    {
+        const dxtex_hresult hr = group_rows(ctx, width, height, &out, &outPitch);
+        if (hr != DXTEX_S_OK) return hr;
+        outFormat = FMT_R32G32B32A32_FLOAT;
+    }
+    hipError_t e = launch_normal_map(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), flags, amplitude,
+                                     unorm, ctx->stream);
+    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream);
+    return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+}
+} // namespace
+
+dxtex_hresult dxtex_compute_normal_map_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, float amplitude)
+{
+    bool unorm = false;
+    const dxtex_hresult hr = check_normal_map(ctx, src, dst, flags, &unorm);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_normal_map(ctx, *src, *dst, flags, amplitude, unorm); });
+}
+
+dxtex_hresult dxtex_compute_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, float amplitude)
+{
+    bool unorm = false;
+    dxtex_hresult hr = check_normal_map(ctx, src, dst, flags, &unorm);
+    if (hr != DXTEX_S_OK) return hr;
+    size_t srcBytes = 0, dstBytes = 0;
+    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      { return submit_normal_map(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags, amplitude, unorm); });
 }
 
 namespace

@@ -63,6 +63,12 @@ hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int src
                                   uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, void* scratch,
                                   unsigned long long* rerun, uint32_t segLen, hipStream_t stream);
 
+// ComputeNormalMap of one image: dstFormat's rows receive what the reference hands to StoreScanline (R32G32B32A32_FLOAT rows for
+// launch_pack_group when the destination packs several texels per element); unorm = the destination format is UNORM (its encoding).
+// flags = CNMAP_FLAGS. Source and destination must not overlap.
+hipError_t launch_normal_map(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
+                             uint32_t width, uint32_t height, uint32_t flags, float amplitude, bool unorm, hipStream_t stream);
+
 // Resize / one mip level. filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row
 // ofs[i]..ofs[i+1] indexes (source index, fp32 weight bits) pairs, see triangle_filter.h. `staleLevel` (box mips only):

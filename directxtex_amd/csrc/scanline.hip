@@ -7,6 +7,7 @@
 //   Resize{Point,Box,Linear,Cubic,Triangle}Filter (DirectXTexResize.cpp:255-803) and
 //   Generate2DMips{Point,Box,Linear,Cubic,Triangle}Filter (DirectXTexMipmaps.cpp:907-1602)   resize_*_kernel
 //   ComputeMSE_ (DirectXTexMisc.cpp:27-176)                                mse_kernel
+//   ComputeNMap (DirectXTexNormalMaps.cpp:77-240)                          nmap_kernel
 //
 // The reference walks scanlines through a float4 row buffer (LoadScanline -> filter -> StoreScanline). Here every
 // lane owns one destination texel and reads the source texels it needs straight from HBM/L2 with LoadScanline's
@@ -18,6 +19,7 @@
 #include "dxtex_store.h"
 #include "dxtex_formats.h"
 #include "cubic_filter.h"
+#include "dxtex_nmap.h"
 #include <algorithm>
 
 namespace dxtex
@@ -278,6 +280,73 @@ __global__ void __launch_bounds__(kDiffuseThreads) convert_diffuse_kernel(Diffus
         __syncthreads();
     }
     if (rerun) atomicAdd(a.rerun, rerun);
+}
+
+// ---- ComputeNormalMap (DirectXTexNormalMaps.cpp:77-240) ----------------------------------------------------------------------------
+// A workgroup owns kNmapThreads columns and a strip of kNmapRows rows, and walks down it with a ring of four rows of heights in LDS:
+// the reference's val0 / val1 / val2 cycle plus the row being filled. Each lane turns one texel per row into a height (load_texel +
+// nmap_height); lane 0 and the last lane also load the left / right halo column, so every source texel is read once per strip (plus
+// the strip's two halo rows). The next row is loaded into registers before the current one is computed, so its latency overlaps the
+// arithmetic and the store. Columns and rows outside the image wrap, or repeat the edge under CNMAP_MIRROR_U / _V (nmap_edge). Row -1
+// under MIRROR_V is row 0: what the reference means by memcpy(row0, row1, rowPitch) (:128), which copies rowPitch bytes into a row of
+// 16-byte XMVECTORs and so is defined only when the source has 16 bytes per texel and a tight pitch.
+constexpr uint32_t kNmapThreads = 256, kNmapRows = 32;
+struct NmapArgs { ImgView src, dst; uint32_t flags; float amplitude; int unorm; uint32_t strips; };
+
+__device__ __forceinline__ float nmap_load(const ImgView& s, uint32_t x, uint32_t y, uint32_t flags)
+{
+    const Texel t = load_texel(s.pixels + uint64_t(y) * s.rowPitch, x, s.format);
+    return nmap_height(t.r, t.g, t.b, t.a, flags);
+}
+
+__global__ void __launch_bounds__(kNmapThreads) nmap_kernel(NmapArgs a)
+{
+    __shared__ float ring[4][kNmapThreads + 2];      // slot i of a row = column x0 - 1 + i
+    const uint32_t W = a.src.width, H = a.src.height, t = threadIdx.x;
+    const int64_t x0 = int64_t(blockIdx.x) * kNmapThreads, x = x0 + t;
+    const bool clampU = (a.flags & NMAP_MIRROR_U) != 0, clampV = (a.flags & NMAP_MIRROR_V) != 0;
+    // slot t + 1 holds column x (the right halo when x == W); lane 0 adds slot 0, the last lane slot kNmapThreads + 1 if that is needed
+    const bool own = x <= int64_t(W);
+    const uint32_t ownCol = nmap_edge(x, W, clampU);
+    const bool extra = t == 0 || (t == kNmapThreads - 1 && x0 + int64_t(kNmapThreads) <= int64_t(W));
+    const uint32_t extraSlot = t == 0 ? 0u : kNmapThreads + 1u;
+    const uint32_t extraCol = nmap_edge(t == 0 ? x0 - 1 : x0 + int64_t(kNmapThreads), W, clampU);
+    float hv = 0.0f, he = 0.0f;
+    const auto load_row = [&](int64_t r)
+    {
+        const uint32_t sy = nmap_edge(r, H, clampV);
+        if (own) hv = nmap_load(a.src, ownCol, sy, a.flags);
+        if (extra) he = nmap_load(a.src, extraCol, sy, a.flags);
+    };
+    const auto put_row = [&](int64_t r)      // the row loaded last into its ring slot
+    {
+        float* s = ring[uint32_t(r + 1) & 3u];
+        if (own) s[t + 1] = hv;
+        if (extra) s[extraSlot] = he;
+    };
+    for (uint32_t strip = blockIdx.y; strip < a.strips; strip += gridDim.y)
+    {
+        const uint32_t y0 = strip * kNmapRows, y1 = uint32_t(min(uint64_t(y0) + kNmapRows, uint64_t(H)));
+        __syncthreads();        // the previous strip's reads of the ring are done
+        load_row(int64_t(y0) - 1); put_row(int64_t(y0) - 1);
+        load_row(y0); put_row(y0);
+        load_row(int64_t(y0) + 1);
+        for (uint32_t y = y0; y < y1; ++y)
+        {
+            put_row(int64_t(y) + 1);
+            __syncthreads();
+            if (y + 1u < y1) load_row(int64_t(y) + 2);
+            if (x < int64_t(W))
+            {
+                const float* top = ring[y & 3u];
+                const float* mid = ring[(y + 1u) & 3u];
+                const float* bot = ring[(y + 2u) & 3u];
+                const float h[3][3] = { { top[t], top[t + 1], top[t + 2] }, { mid[t], mid[t + 1], mid[t + 2] }, { bot[t], bot[t + 1], bot[t + 2] } };
+                const NmapOut o = nmap_texel(h, a.flags, a.amplitude, a.unorm != 0);
+                store_texel(a.dst.pixels + uint64_t(y) * a.dst.rowPitch, uint32_t(x), a.dst.format, Texel{ o.x, o.y, o.z, o.w });
+            }
+        }
+    }
 }
 
 // ---- PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205): rgb * a, or rgb / a where a > 0, in linear space ------------
@@ -1085,6 +1154,19 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
     const dim3 grid((width + 255) / 256, grid_rows(height));
     if (dither) hipLaunchKernelGGL(convert_kernel<true>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z);
     else hipLaunchKernelGGL(convert_kernel<false>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z);
+    return hipGetLastError();
+}
+
+hipError_t launch_normal_map(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
+                             uint32_t width, uint32_t height, uint32_t flags, float amplitude, bool unorm, hipStream_t stream)
+{
+    if (!width || !height) return hipSuccess;
+    NmapArgs a;
+    a.src = make_view(src, srcPitch, width, height, srcFormat);
+    a.dst = make_view(dst, dstPitch, width, height, dstFormat);
+    a.flags = flags; a.amplitude = amplitude; a.unorm = unorm ? 1 : 0;
+    a.strips = uint32_t((uint64_t(height) + kNmapRows - 1u) / kNmapRows);
+    hipLaunchKernelGGL(nmap_kernel, dim3(uint32_t((uint64_t(width) + kNmapThreads - 1u) / kNmapThreads), grid_rows(a.strips)), dim3(kNmapThreads), 0, stream, a);
     return hipGetLastError();
 }
 

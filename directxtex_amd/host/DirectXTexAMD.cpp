@@ -647,6 +647,7 @@ struct HostSpace
     static HRESULT Convert(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t) noexcept { return dxtex_convert(c, s, d, f, t); }
     static HRESULT ConvertSlice(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t, uint32_t z) noexcept { return dxtex_convert_slice(c, s, d, f, t, z); }
     static HRESULT PMAlpha(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f) noexcept { return dxtex_premultiply_alpha(c, s, d, f); }
+    static HRESULT NormalMap(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float a) noexcept { return dxtex_compute_normal_map(c, s, d, f, a); }
     static HRESULT Coverage(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, size_t n, float r) noexcept { return dxtex_scale_mips_alpha_for_coverage(c, s, d, n, r); }
     static HRESULT CopyRows(dxtex_ctx*, uint8_t* dst, size_t dstPitch, const uint8_t* src, size_t srcPitch, size_t rowBytes, size_t rows) noexcept
     {
@@ -666,6 +667,7 @@ struct DeviceSpace
     static HRESULT Convert(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t) noexcept { return dxtex_convert_device(c, s, d, f, t); }
     static HRESULT ConvertSlice(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float t, uint32_t z) noexcept { return dxtex_convert_slice_device(c, s, d, f, t, z); }
     static HRESULT PMAlpha(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f) noexcept { return dxtex_premultiply_alpha_device(c, s, d, f); }
+    static HRESULT NormalMap(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, uint32_t f, float a) noexcept { return dxtex_compute_normal_map_device(c, s, d, f, a); }
     static HRESULT Coverage(dxtex_ctx* c, const dxtex_image* s, const dxtex_image* d, size_t n, float r) noexcept { return dxtex_scale_mips_alpha_for_coverage_device(c, s, d, n, r); }
     static HRESULT CopyRows(dxtex_ctx* c, uint8_t* dst, size_t dstPitch, const uint8_t* src, size_t srcPitch, size_t rowBytes, size_t rows) noexcept
     {
@@ -1290,6 +1292,68 @@ HRESULT PremultiplyAlpha(Device& device, const Image* srcImages, size_t nimages,
     return PremultiplyAlphaArrayT<HostSpace>(device, srcImages, nimages, metadata, flags, result);
 }
 
+// ---- ComputeNormalMap (DirectXTexNormalMaps.cpp:249-396) ---------------------------------------------------------------------------
+namespace
+{
+bool NmapValid(DXGI_FORMAT f) noexcept { return size_t(f) >= 1 && size_t(f) <= 191; }
+bool NmapChannelValid(CNMAP_FLAGS flags) noexcept { return (flags & 0xf) <= CNMAP_CHANNEL_LUMINANCE; }
+bool NmapUnsupported(DXGI_FORMAT f) noexcept { return IsCompressed(f) || IsTypeless(f) || IsPlanar(f) || IsPalettized(f); }
+
+template <class Space>
+HRESULT ComputeNormalMapArrayT(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, CNMAP_FLAGS flags, float amplitude,
+                               DXGI_FORMAT format, typename Space::Out& result) noexcept
+{
+    if (!device) return E_POINTER;
+    if (!srcImages || !nimages || !NmapValid(metadata.format) || !NmapValid(format)) return E_INVALIDARG;
+    if (NmapUnsupported(format) || NmapUnsupported(metadata.format)) return HRESULT_E_NOT_SUPPORTED;
+    if (!NmapChannelValid(flags)) return E_INVALIDARG;
+    if (metadata.width > UINT32_MAX || metadata.height > UINT32_MAX) return E_INVALIDARG;
+    result.Release();
+    TexMetadata mdata2 = metadata;
+    mdata2.format = format;
+    HRESULT hr = Space::Init(device, result, mdata2);
+    if (FAILED(hr)) return hr;
+    if (nimages != result.GetImageCount()) { result.Release(); return E_FAIL; }
+    const Image* dest = result.GetImages();
+    if (!dest) { result.Release(); return E_POINTER; }
+    for (size_t i = 0; i < nimages; ++i)
+    {
+        const Image& src = srcImages[i];
+        if (IsCompressed(src.format) || IsTypeless(src.format)) { result.Release(); return HRESULT_E_NOT_SUPPORTED; }
+        if (src.width != dest[i].width || src.height != dest[i].height) { result.Release(); return E_FAIL; }
+        const dxtex_image s = View(src), d = View(dest[i]);
+        hr = Space::NormalMap(device.Get(), &s, &d, uint32_t(flags), amplitude);
+        if (FAILED(hr)) { result.Release(); return hr; }
+    }
+    return S_OK;
+}
+}
+
+HRESULT ComputeNormalMap(Device& device, const Image& srcImage, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, ScratchImage& normalMap) noexcept
+{
+    if (!device) return E_POINTER;
+    if (!srcImage.pixels) return E_POINTER;
+    if (!NmapValid(srcImage.format) || !NmapValid(format)) return E_INVALIDARG;
+    if (!NmapChannelValid(flags)) return E_INVALIDARG;
+    if (NmapUnsupported(format) || NmapUnsupported(srcImage.format)) return HRESULT_E_NOT_SUPPORTED;
+    if (srcImage.width > UINT32_MAX || srcImage.height > UINT32_MAX) return E_INVALIDARG;
+    normalMap.Release();
+    HRESULT hr = normalMap.Initialize2D(format, srcImage.width, srcImage.height, 1, 1);
+    if (FAILED(hr)) return hr;
+    const Image* img = normalMap.GetImage(0, 0, 0);
+    if (!img) { normalMap.Release(); return E_POINTER; }
+    const dxtex_image s = View(srcImage), d = View(*img);
+    hr = dxtex_compute_normal_map(device.Get(), &s, &d, uint32_t(flags), amplitude);
+    if (FAILED(hr)) normalMap.Release();
+    return hr;
+}
+
+HRESULT ComputeNormalMap(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, CNMAP_FLAGS flags, float amplitude,
+                         DXGI_FORMAT format, ScratchImage& normalMaps) noexcept
+{
+    return ComputeNormalMapArrayT<HostSpace>(device, srcImages, nimages, metadata, flags, amplitude, format, normalMaps);
+}
+
 // ---- ScaleMipMapsAlphaForCoverage (DirectXTexMipmaps.cpp:3483-3556) ------------------------------------------------------------------
 namespace
 {
@@ -1534,6 +1598,12 @@ HRESULT PremultiplyAlpha(Device& device, const DeviceScratchImage& src, TEX_PMAL
 {
     if (!Resident(device, src)) return E_INVALIDARG;
     return PremultiplyAlphaArrayT<DeviceSpace>(device, src.GetImages(), src.GetImageCount(), src.GetMetadata(), flags, result);
+}
+
+HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, DeviceScratchImage& normalMaps) noexcept
+{
+    if (!Resident(device, src)) return E_INVALIDARG;
+    return ComputeNormalMapArrayT<DeviceSpace>(device, src.GetImages(), src.GetImageCount(), src.GetMetadata(), flags, amplitude, format, normalMaps);
 }
 
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const DeviceScratchImage& src, float alphaReference, DeviceScratchImage& mipChain) noexcept

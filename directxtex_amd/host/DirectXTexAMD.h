@@ -283,6 +283,18 @@ enum TEX_PMALPHA_FLAGS : uint32_t
 };
 HRESULT PremultiplyAlpha(Device& device, const Image& srcImage, TEX_PMALPHA_FLAGS flags, ScratchImage& image) noexcept;
 HRESULT PremultiplyAlpha(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, TEX_PMALPHA_FLAGS flags, ScratchImage& result) noexcept;
+// ComputeNormalMap (DirectXTex.h:973-1002). CNMAP_FLAGS values as in the reference; the channel is flags & 0xf (0 = red). The array form
+// treats every image (mip level, array item, volume slice) as an independent 2-D height map. On failure the output is released.
+enum CNMAP_FLAGS : uint32_t
+{
+    CNMAP_DEFAULT = 0, CNMAP_CHANNEL_RED = 0x1, CNMAP_CHANNEL_GREEN = 0x2, CNMAP_CHANNEL_BLUE = 0x3, CNMAP_CHANNEL_ALPHA = 0x4,
+    CNMAP_CHANNEL_LUMINANCE = 0x5, CNMAP_MIRROR_U = 0x1000, CNMAP_MIRROR_V = 0x2000, CNMAP_MIRROR = 0x3000, CNMAP_INVERT_SIGN = 0x4000,
+    CNMAP_COMPUTE_OCCLUSION = 0x8000,
+};
+inline CNMAP_FLAGS operator|(CNMAP_FLAGS a, CNMAP_FLAGS b) noexcept { return CNMAP_FLAGS(uint32_t(a) | uint32_t(b)); }
+HRESULT ComputeNormalMap(Device& device, const Image& srcImage, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, ScratchImage& normalMap) noexcept;
+HRESULT ComputeNormalMap(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, CNMAP_FLAGS flags, float amplitude,
+                         DXGI_FORMAT format, ScratchImage& normalMaps) noexcept;
 // ScaleMipMapsAlphaForCoverage (DirectXTex.h:848-851): mipChain must already be initialised with the chain's layout
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, size_t item,
                                      float alphaReference, ScratchImage& mipChain) noexcept;
@@ -343,6 +355,7 @@ HRESULT GenerateMipMaps3D(Device& device, const DeviceScratchImage& src, TEX_FIL
 HRESULT Resize(Device& device, const DeviceScratchImage& src, size_t width, size_t height, TEX_FILTER_FLAGS filter, DeviceScratchImage& result) noexcept;
 HRESULT Convert(Device& device, const DeviceScratchImage& src, DXGI_FORMAT format, TEX_FILTER_FLAGS filter, float threshold, DeviceScratchImage& result) noexcept;
 HRESULT PremultiplyAlpha(Device& device, const DeviceScratchImage& src, TEX_PMALPHA_FLAGS flags, DeviceScratchImage& result) noexcept;
+HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, DeviceScratchImage& normalMaps) noexcept;
 // every array item of a mip chain (the per-item loop texconv runs, texconv.cpp:3470-3490); the 10-step bisection per level reads 8 bytes back per step
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const DeviceScratchImage& src, float alphaReference, DeviceScratchImage& mipChain) noexcept;
 // level 0 of every array item / depth slice as a texture with one mip level (what texconv keeps before it regenerates a chain, texconv.cpp:3324-3380)

@@ -1,9 +1,9 @@
 // dxtexconv - a texconv-style batch converter on top of the MI355X host layer (DirectXTexAMD.h): DDS in, DDS out, every
 // image-processing step on the GPU. The pipeline and its order are the reference tool's (Texconv/texconv.cpp): load (:2077-2090)
-// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> convert (:3100-3140) ->
-// mipmaps (:3302-3460) -> alpha-coverage preservation (:3462-3500) -> premultiply alpha (:3502-3545) -> compress (:3547-3735) ->
-// alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips,
-// swizzles, normal maps, tone mapping, WIC codecs, dithered conversion) is refused, not approximated.
+// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> normal map (:3047-3098) or
+// convert (:3100-3140) -> mipmaps (:3302-3460) -> alpha-coverage preservation (:3462-3500) -> premultiply alpha (:3502-3545) ->
+// compress (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation
+// here (flips, swizzles, tone mapping, WIC codecs, dithered conversion) is refused, not approximated.
 //
 //   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga>...        (-ft hdr | tga: Radiance / TGA output of level 0)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
@@ -13,6 +13,8 @@
 //     -pmalpha -alpha      to / from premultiplied alpha        -keepcoverage <ref>   keep alpha-test coverage in the mips
 //     -at <threshold>      alpha threshold (BC1, 1-bit alpha)   -bc <q|x|d|u>...  BC7 quick / 3 subsets, dither, uniform weights
 //     -x2bias              *2 - 1 on conversions to / from SNORM -sepalpha        resize / mip alpha separately (alpha mode custom)
+//     -nmap <l|r|g|b|a>[m|u|v][i][o]   height map -> normal map (channel; mirror both / u / v; invert sign; occlusion in alpha)
+//     -nmapamp <weight>    normal-map amplitude, default 1 (needs -nmap first)
 //     -dword -badtails -permissive -ignoremips -xlum            DDS reader tolerances (DDS_FLAGS)
 //     -dx10 -dx9           force the 'DX10' header (+ alpha mode) / a Direct3D 9 file        -tga20   TGA output with the 2.0 extension area
 //     -px <s> -sx <s> -l   output name prefix / suffix, lower case    -y   overwrite    -info (print what the files hold, no GPU)    -timing -nologo -gpu <n> | -gpus <a,b,...> (files dealt out over the GPUs)
@@ -83,6 +85,9 @@ struct Options
          timing = false, nologo = false, hdrOut = false, tgaOut = false, tga20 = false, info = false;
     uint32_t format = 0, filter = 0, filterOpts = 0, srgb = 0, convert = 0, compress = 0, ddsRead = DDS_FLAGS_ALLOW_LARGE_FILES;
     float alphaThreshold = TEX_THRESHOLD_DEFAULT, keepCoverage = 0.f;
+    bool nmap = false;                  // -nmap: ComputeNormalMap replaces the convert step
+    uint32_t nmapFlags = 0;             // CNMAP_FLAGS
+    float nmapAmplitude = 1.f;
     std::vector<int> gpus;              // one worker (own Device, own host thread) per entry; input i goes to worker i mod n
     size_t overlap = 2;                 // workers per listed GPU: file k + 1 is read, decoded and uploaded while file k's kernels run
     std::string prefix, suffix, out;
@@ -130,7 +135,8 @@ HRESULT TopLevels(const ScratchImage& in, ScratchImage& out)
 int usage()
 {
     std::fprintf(stderr, "usage: dxtexconv [-w W] [-h H] [-pow2] [-fl LEVEL] [-m N] [-f FORMAT] [-if FILTER] [-wrap] [-mirror] [-srgb|-srgbi|-srgbo]\n"
-                         "                 [-pmalpha|-alpha] [-keepcoverage REF] [-at T] [-bc qxdu] [-x2bias] [-sepalpha] [-dword] [-badtails] [-permissive]\n"
+                         "                 [-pmalpha|-alpha] [-keepcoverage REF] [-at T] [-bc qxdu] [-x2bias] [-sepalpha] [-nmap <l|r|g|b|a>[m|u|v][i][o]] [-nmapamp W]\n"
+                         "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N] -o <out.dds | dir> in.dds...\n");
     return 1;
 }
@@ -168,6 +174,34 @@ bool Parse(int argc, char** argv, Options& o)
         else if (a == "-mirror") { if (o.filterOpts & TEX_FILTER_WRAP) { std::fprintf(stderr, "-wrap and -mirror exclude each other\n"); return false; } o.filterOpts |= TEX_FILTER_MIRROR; }
         else if (a == "-sepalpha") { o.sepalpha = true; o.filterOpts |= TEX_FILTER_SEPARATE_ALPHA; }
         else if (a == "-x2bias") o.convert |= TEX_FILTER_FLOAT_X2BIAS;
+        else if (a == "-nmap" || a == "-normal-map")
+        {
+            // texconv.cpp:1638-1693: the first channel letter found in the order l r g b a; m, or u / v; i; o
+            const std::string v = next();
+            const auto has = [&](char c) { return v.find(c) != std::string::npos; };
+            uint32_t f = CNMAP_DEFAULT;
+            if (has('l')) f |= CNMAP_CHANNEL_LUMINANCE;
+            else if (has('r')) f |= CNMAP_CHANNEL_RED;
+            else if (has('g')) f |= CNMAP_CHANNEL_GREEN;
+            else if (has('b')) f |= CNMAP_CHANNEL_BLUE;
+            else if (has('a')) f |= CNMAP_CHANNEL_ALPHA;
+            else if (!missing) { std::fprintf(stderr, "invalid value for -nmap (%s): missing l, r, g, b or a\n", v.c_str()); return false; }
+            if (has('m')) f |= CNMAP_MIRROR;
+            else { if (has('u')) f |= CNMAP_MIRROR_U; if (has('v')) f |= CNMAP_MIRROR_V; }
+            if (has('i')) f |= CNMAP_INVERT_SIGN;
+            if (has('o')) f |= CNMAP_COMPUTE_OCCLUSION;
+            o.nmap = true; o.nmapFlags = f;
+        }
+        else if (a == "-nmapamp" || a == "-normal-map-amplitude")
+        {
+            // texconv.cpp:1695-1713
+            if (!o.nmap) { std::fprintf(stderr, "-nmapamp requires -nmap\n"); return false; }
+            const char* v = next();
+            char* end = nullptr;
+            o.nmapAmplitude = std::strtof(v, &end);
+            if (!missing && end == v) { std::fprintf(stderr, "invalid value for -nmapamp (%s)\n", v); return false; }
+            if (o.nmapAmplitude < 0.f) { std::fprintf(stderr, "normal map amplitude must be positive (%s)\n", v); return false; }
+        }
         else if (a == "-pow2") o.pow2 = true;
         else if (a == "-pmalpha") o.pmalpha = true;
         else if (a == "-alpha") o.demul = true;
@@ -329,8 +363,24 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         }
     }
 
+    // --- normal map (texconv.cpp:3047-3098), in place of the convert step; a compressed target gets texconv's intermediate format
+    if (o.nmap)
+    {
+        DXGI_FORMAT nmfmt = tformat;
+        if (IsCompressed(tformat))
+        {
+            const bool wide = BitsPerColor(info.format) > 8;
+            if (tformat == DXGI_FORMAT_BC4_SNORM || tformat == DXGI_FORMAT_BC5_SNORM) nmfmt = wide ? DXGI_FORMAT_R16G16B16A16_SNORM : DXGI_FORMAT_R8G8B8A8_SNORM;
+            else if (tformat == DXGI_FORMAT_BC6H_SF16 || tformat == DXGI_FORMAT_BC6H_UF16) nmfmt = DXGI_FORMAT_R32G32B32_FLOAT;
+            else nmfmt = wide ? DXGI_FORMAT_R16G16B16A16_UNORM : DXGI_FORMAT_R8G8B8A8_UNORM;
+        }
+        DeviceScratchImage t;
+        check("normalmap", ComputeNormalMap(dev, image, CNMAP_FLAGS(o.nmapFlags), o.nmapAmplitude, nmfmt, t));
+        keep(t);
+        haveOriginal = false;
+    }
     // --- convert to the uncompressed target format
-    if (!IsCompressed(tformat) && tformat != info.format)
+    else if (!IsCompressed(tformat) && tformat != info.format)
     {
         DeviceScratchImage t;
         check("convert", Convert(dev, image, tformat, TEX_FILTER_FLAGS(filter | o.srgb | o.convert), o.alphaThreshold, t));

@@ -19,6 +19,7 @@
  *   Generate2DMips{Point,Box,Linear,Cubic,Triangle}Filter  DirectXTexMipmaps.cpp:907-1602  dxtex_generate_mips
  *   ConvertCustom                              DirectXTexConvert.cpp:4804-4913 dxtex_convert
  *   Resize*Filter                              DirectXTexResize.cpp:255-803    dxtex_resize
+ *   ComputeNMap                                DirectXTexNormalMaps.cpp:77-240 dxtex_compute_normal_map
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -206,6 +207,25 @@ dxtex_hresult dxtex_convert_slice_device(dxtex_ctx* ctx, const dxtex_image* src,
 /* Diagnostics of error diffusion on this context, cumulative: texels converted with diffusion into a dithered format, and how many of
  * them the exact merge had to run a second (or further) time. Waits for the context's stream (copies 8 bytes to the host). */
 dxtex_hresult dxtex_convert_dither_stats(dxtex_ctx* ctx, uint64_t* rerunTexels, uint64_t* texels);
+
+/* ComputeNormalMap (DirectXTexNormalMaps.cpp:77-240) of one height map: src and dst have the same size, dst->format is a UNORM, SNORM or
+ * FLOAT format (it may equal src->format). flags = CNMAP_FLAGS: channel (flags & 0xf: 0 or 1 red, 2 green, 3 blue, 4 alpha, 5 luminance),
+ * DXTEX_CNMAP_MIRROR_U / _V (repeat the edge texel instead of wrapping), DXTEX_CNMAP_INVERT_SIGN, DXTEX_CNMAP_COMPUTE_OCCLUSION (alpha =
+ * occlusion term, else 1). HRESULTs: E_INVALIDARG for a bad channel, a format outside 1..191 or overlapping pixels; NOT_SUPPORTED for
+ * block-compressed or unknown formats and for destinations that are not UNORM / SNORM / FLOAT; E_FAIL for a size mismatch. Under
+ * MIRROR_V the row above row 0 is row 0 (the reference's memcpy there is defined only for 16-byte texels with a tight pitch). */
+#define DXTEX_CNMAP_CHANNEL_RED        0x1u
+#define DXTEX_CNMAP_CHANNEL_GREEN      0x2u
+#define DXTEX_CNMAP_CHANNEL_BLUE       0x3u
+#define DXTEX_CNMAP_CHANNEL_ALPHA      0x4u
+#define DXTEX_CNMAP_CHANNEL_LUMINANCE  0x5u
+#define DXTEX_CNMAP_MIRROR_U           0x1000u
+#define DXTEX_CNMAP_MIRROR_V           0x2000u
+#define DXTEX_CNMAP_MIRROR             0x3000u
+#define DXTEX_CNMAP_INVERT_SIGN        0x4000u
+#define DXTEX_CNMAP_COMPUTE_OCCLUSION  0x8000u
+dxtex_hresult dxtex_compute_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, float amplitude);
+dxtex_hresult dxtex_compute_normal_map_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, float amplitude);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
