@@ -895,14 +895,15 @@ dxtex_hresult group_rows(dxtex_ctx* ctx, size_t width, size_t height, uint8_t** 
 dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs, int format, uint32_t mode, uint32_t flags, bool mipAlias)
 {
     const bool grouped = is_group_format(format);
+    KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
     // one resize: straight into the destination, or through float rows and the pack kernel
     auto resize_one = [&](const LevelPair& p, const TriangleTables* t, const uint8_t* staleSrc, uint64_t stalePitch, uint32_t staleW) -> dxtex_hresult
     {
         uint8_t* out = p.dst; size_t outPitch = p.dstPitch;
         if (grouped) { const dxtex_hresult hr = group_rows(ctx, p.dw, p.dh, &out, &outPitch); if (hr != DXTEX_S_OK) return hr; }
         hipError_t e = launch_resize(p.src, p.srcPitch, uint32_t(p.sw), uint32_t(p.sh), out, outPitch, uint32_t(p.dw), uint32_t(p.dh),
-                                     format, mode, flags, mipAlias, t, ctx->stream, staleSrc, stalePitch, staleW, grouped ? FMT_R32G32B32A32_FLOAT : -1);
-        if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, p.dst, p.dstPitch, format, uint32_t(p.dw), uint32_t(p.dh), ctx->stream);
+                                     format, mode, flags, mipAlias, t, ctx->stream, staleSrc, stalePitch, staleW, grouped ? FMT_R32G32B32A32_FLOAT : -1, marks);
+        if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, p.dst, p.dstPitch, format, uint32_t(p.dw), uint32_t(p.dh), ctx->stream, marks);
         return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     };
     if (mode == DXTEX_FILTER_TRIANGLE)
@@ -945,7 +946,7 @@ dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs
             {
                 MipLevel th = { nullptr, 0, 0, 0 };
                 if (twoHigh) th = { const_cast<uint8_t*>(twoHigh->src), twoHigh->srcPitch, uint32_t(twoHigh->sw), uint32_t(twoHigh->sh) };
-                const hipError_t e = launch_resize_tail(lv.data(), int(lv.size()), format, mode, flags, twoHigh ? &th : nullptr, ctx->stream);
+                const hipError_t e = launch_resize_tail(lv.data(), int(lv.size()), format, mode, flags, twoHigh ? &th : nullptr, ctx->stream, marks);
                 if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
                 return DXTEX_S_OK;
             }
@@ -1241,9 +1242,10 @@ dxtex_hresult submit_convert(dxtex_ctx* ctx, const dxtex_image& src, const dxtex
         if (hr != DXTEX_S_OK) return hr;
         outFormat = FMT_R32G32B32A32_FLOAT;
     }
+    KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
     hipError_t e = launch_convert(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), plan, threshold, ctx->stream,
-                                  dither, z);
-    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream);
+                                  dither, z, marks);
+    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream, marks);
     return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
 }
 } // namespace
@@ -1501,7 +1503,7 @@ dxtex_hresult dxtex_compute_mse_device(dxtex_ctx* ctx, const dxtex_image* a, con
     ScopedDevice sd(ctx->device);
     hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
     hipError_t e = launch_mse(a->pixels, a->rowPitch, a->format, b->pixels, b->rowPitch, b->format, uint32_t(a->width), uint32_t(a->height),
-                              static_cast<double*>(ctx->mseBuf.p), ctx->stream);
+                              static_cast<double*>(ctx->mseBuf.p), ctx->stream, ctx->profiling ? &ctx->marks : nullptr);
     if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
     double sum[4];
     HIP_TRY(ctx, counted_copy(ctx, sum, ctx->mseBuf.p, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));

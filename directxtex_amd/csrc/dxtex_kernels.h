@@ -54,7 +54,7 @@ hipError_t launch_bc_decode(const uint8_t* src, uint64_t srcRowPitch, int srcFor
 enum : int { CONVERT_DITHER_NONE = 0, CONVERT_DITHER_ORDERED = 1, CONVERT_DITHER_ZERO_ERROR = 2 };
 hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
                           uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream,
-                          int dither = CONVERT_DITHER_NONE, uint32_t z = 0);
+                          int dither = CONVERT_DITHER_NONE, uint32_t z = 0, KernelMarks* marks = nullptr);
 // Error-diffusion Convert of one image (a destination format with a dithered store) in one workgroup; `scratch` holds
 // convert_diffuse_scratch_bytes(width) bytes of device memory; the texels the merge re-ran are added to *rerun (device memory).
 // segLen = texels per speculated segment of a row (0: the default).
@@ -77,11 +77,13 @@ struct TriangleTables { const uint32_t* ofsX; const void* entX; const uint32_t* 
 hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, uint32_t srcH, uint8_t* dst, uint64_t dstPitch,
                          uint32_t dstW, uint32_t dstH, int format, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
                          const TriangleTables* tri, hipStream_t stream,
-                         const uint8_t* staleLevel = nullptr, uint64_t stalePitch = 0, uint32_t staleW = 0, int dstFormat = -1);
+                         const uint8_t* staleLevel = nullptr, uint64_t stalePitch = 0, uint32_t staleW = 0, int dstFormat = -1,
+                         KernelMarks* marks = nullptr);
 // dstFormat >= 0: the destination rows are written in that format instead of `format` (R32G32B32A32_FLOAT rows for launch_pack_group).
 
 // Formats whose element holds several texels (FC_GROUP): R32G32B32A32_FLOAT rows -> the format, with StoreScanline's pair / bit packing.
-hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* dst, uint64_t dstPitch, int dstFormat, uint32_t width, uint32_t height, hipStream_t stream);
+hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* dst, uint64_t dstPitch, int dstFormat, uint32_t width, uint32_t height, hipStream_t stream,
+                             KernelMarks* marks = nullptr);
 
 // The tail of a 2-D mip chain (levels[0] = the first source level, at most 64 x 64; levels[1..] = the levels generated from it) in one
 // workgroup: point / linear / cubic / box, the arithmetic of launch_resize with mipAlias. twoHigh = the last level of the chain before
@@ -92,7 +94,7 @@ bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode);
 // levels[] as for launch_resize_tail
 bool resize_cubic_tail_applies(const MipLevel* levels, int nlevels, int format, uint32_t filterFlags);
 hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, uint32_t filterMode, uint32_t filterFlags,
-                              const MipLevel* twoHigh, hipStream_t stream);
+                              const MipLevel* twoHigh, hipStream_t stream, KernelMarks* marks = nullptr);
 
 // Volume mips (Generate3DMips*Filter): one level whose source is more than one slice deep. Slices of a level are `slicePitch` apart.
 struct VolumeView { const uint8_t* pixels; uint64_t rowPitch, slicePitch; uint32_t width, height, depth; int format; };
@@ -102,7 +104,7 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
 
 // ComputeMSE: out4 (device) receives the per-channel SUM of squared differences; divide by width * height on the host.
 hipError_t launch_mse(const uint8_t* a, uint64_t aPitch, int aFormat, const uint8_t* b, uint64_t bPitch, int bFormat,
-                      uint32_t width, uint32_t height, double* out4, hipStream_t stream);
+                      uint32_t width, uint32_t height, double* out4, hipStream_t stream, KernelMarks* marks = nullptr);
 // PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205); pmFlags = TEX_PMALPHA_*
 hipError_t launch_pmalpha(const uint8_t* src, uint64_t srcPitch, uint8_t* dst, uint64_t dstPitch, int format, uint32_t width, uint32_t height,
                           uint32_t pmFlags, hipStream_t stream);

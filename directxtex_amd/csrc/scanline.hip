@@ -1065,8 +1065,9 @@ __global__ void __launch_bounds__(256) mse_kernel(ImgView a, ImgView b, int srgb
         {
             Texel p = load_texel(a.pixels + uint64_t(y) * a.rowPitch, x, a.format);
             Texel q = load_texel(b.pixels + uint64_t(y) * b.rowPitch, x, b.format);
-            if (srgbA) { p.r = powf(p.r, 2.2f); p.g = powf(p.g, 2.2f); p.b = powf(p.b, 2.2f); p.a = powf(p.a, 2.2f); }     // XMVectorPow(v, g_Gamma22)
-            if (srgbB) { q.r = powf(q.r, 2.2f); q.g = powf(q.g, 2.2f); q.b = powf(q.b, 2.2f); q.a = powf(q.a, 2.2f); }
+            // XMVectorPow(v, g_Gamma22) with g_Gamma22 = { 2.2, 2.2, 2.2, 1 } (DirectXTexMisc.cpp:24): alpha keeps its value
+            if (srgbA) { p.r = powf(p.r, 2.2f); p.g = powf(p.g, 2.2f); p.b = powf(p.b, 2.2f); }
+            if (srgbB) { q.r = powf(q.r, 2.2f); q.g = powf(q.g, 2.2f); q.b = powf(q.b, 2.2f); }
             const float d[4] = { p.r - q.r, p.g - q.g, p.b - q.b, ignoreAlpha ? 0.0f : p.a - q.a };
 #pragma unroll
             for (int c = 0; c < 4; ++c) s[c] += double(d[c]) * double(d[c]);
@@ -1110,17 +1111,25 @@ bool can_srgb(int format)
 }
 } // namespace
 
-hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* dst, uint64_t dstPitch, int dstFormat, uint32_t width, uint32_t height, hipStream_t stream)
+// The launchers below name the kernel they enqueue (a string literal: dxtex_ctx_profile_end aggregates by pointer) and close the call
+// with a null mark, as the BC encoders do; with marks == nullptr (not profiling) nothing is recorded.
+#define DXTEX_MARK(NAME) do { if (marks) marks->mark(NAME); } while (0)
+
+hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* dst, uint64_t dstPitch, int dstFormat, uint32_t width, uint32_t height, hipStream_t stream,
+                             KernelMarks* marks)
 {
     if (!width || !height) return hipSuccess;
     const uint32_t per = group_texels(dstFormat), groups = (width + per - 1) / per;
+    DXTEX_MARK("pack_group");
     hipLaunchKernelGGL(pack_group_kernel, dim3((groups + 255) / 256, grid_rows(height)), dim3(256), 0, stream,
                        make_view(rows, rowsPitch, width, height, FMT_R32G32B32A32_FLOAT), make_view(dst, dstPitch, width, height, dstFormat));
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream, int dither, uint32_t z)
+                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream, int dither, uint32_t z,
+                          KernelMarks* marks)
 {
     if (!width || !height) return hipSuccess;
     const FmtInfo* in = format_info(srcFormat);
@@ -1136,8 +1145,10 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
         // row groups per workgroup column: enough workgroups to fill 256 CUs several times over, few enough that a lane streams several groups
 #define DXTEX_QUAD(SQ, DQ, ROWS) do { const uint32_t groups = (height + (ROWS) - 1u) / (ROWS); \
             const uint32_t gy = std::min<uint32_t>(groups, std::max<uint32_t>(1u, 8192u / gx)); \
-            if (dither) hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS, true>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq, dither, z); \
-            else hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS, false>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq, dither, z); } while (0)
+            if (dither) { DXTEX_MARK("convert_quad<" #SQ "," #DQ "," #ROWS ",dither>"); \
+                          hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS, true>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq, dither, z); } \
+            else { DXTEX_MARK("convert_quad<" #SQ "," #DQ "," #ROWS ">"); \
+                   hipLaunchKernelGGL((convert_quad_kernel<SQ, DQ, ROWS, false>), dim3(gx, gy), dim3(256), 0, stream, sv, dv, plan, threshold, sq, dq, dither, z); } } while (0)
         if (sq == 16u && dq == 16u) DXTEX_QUAD(16, 16, 4);
         else if (sq == 16u && dq == 32u) DXTEX_QUAD(16, 32, 4);
         else if (sq == 16u && dq == 64u) DXTEX_QUAD(16, 64, 4);
@@ -1148,12 +1159,14 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
         else if (sq == 64u && dq == 32u) DXTEX_QUAD(64, 32, 1);
         else DXTEX_QUAD(0, 0, 1);
 #undef DXTEX_QUAD
+        DXTEX_MARK(nullptr);
         return hipGetLastError();
     }
     const ImgView sv = make_view(src, srcPitch, width, height, srcFormat), dv = make_view(dst, dstPitch, width, height, dstFormat);
     const dim3 grid((width + 255) / 256, grid_rows(height));
-    if (dither) hipLaunchKernelGGL(convert_kernel<true>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z);
-    else hipLaunchKernelGGL(convert_kernel<false>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z);
+    if (dither) { DXTEX_MARK("convert<dither>"); hipLaunchKernelGGL(convert_kernel<true>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z); }
+    else { DXTEX_MARK("convert"); hipLaunchKernelGGL(convert_kernel<false>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z); }
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
@@ -1197,7 +1210,8 @@ hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int src
 
 hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, uint32_t srcH, uint8_t* dst, uint64_t dstPitch,
                          uint32_t dstW, uint32_t dstH, int format, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
-                         const TriangleTables* tri, hipStream_t stream, const uint8_t* staleLevel, uint64_t stalePitch, uint32_t staleW, int dstFormat)
+                         const TriangleTables* tri, hipStream_t stream, const uint8_t* staleLevel, uint64_t stalePitch, uint32_t staleW, int dstFormat,
+                         KernelMarks* marks)
 {
     if (!dstW || !dstH) return hipSuccess;
     ResizeArgs a;
@@ -1216,8 +1230,8 @@ hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, u
     const dim3 grid((dstW + 255) / 256, grid_rows(dstH)), block(256);
     switch (filterMode)
     {
-    case 0x100000u: hipLaunchKernelGGL(resize_point_kernel, grid, block, 0, stream, a); break;
-    case 0x200000u: hipLaunchKernelGGL(resize_linear_kernel, grid, block, 0, stream, a); break;
+    case 0x100000u: DXTEX_MARK("resize_point"); hipLaunchKernelGGL(resize_point_kernel, grid, block, 0, stream, a); break;
+    case 0x200000u: DXTEX_MARK("resize_linear"); hipLaunchKernelGGL(resize_linear_kernel, grid, block, 0, stream, a); break;
     case 0x300000u:
         // the 2:1 RGBA8 case of a power-of-two mip chain has a separable kernel (a column strip per lane); the small levels take it too (6 us a
         // launch against 10 - 30 us of the general kernel's sixteen dependent taps)
@@ -1236,28 +1250,46 @@ hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, u
                                (reinterpret_cast<uintptr_t>(dst) % 8) == 0;
             const uint32_t lanesX = pairs ? dstW / 2 : dstW;
             while (strip > 4 && uint64_t((lanesX + 63) / 64) * ((dstH + strip - 1) / strip) < 4096) strip >>= 1;
-            if (pairs) hipLaunchKernelGGL(resize_cubic_half_rgba8_x2_kernel, dim3((lanesX + 255) / 256, grid_rows((dstH + strip - 1) / strip)), block, 0, stream, a, strip);
-            else hipLaunchKernelGGL(resize_cubic_half_rgba8_kernel, dim3((dstW + 255) / 256, grid_rows((dstH + strip - 1) / strip)), block, 0, stream, a, strip);
+            if (pairs)
+            {
+                DXTEX_MARK("resize_cubic_half_rgba8_x2");
+                hipLaunchKernelGGL(resize_cubic_half_rgba8_x2_kernel, dim3((lanesX + 255) / 256, grid_rows((dstH + strip - 1) / strip)), block, 0, stream, a, strip);
+            }
+            else
+            {
+                DXTEX_MARK("resize_cubic_half_rgba8");
+                hipLaunchKernelGGL(resize_cubic_half_rgba8_kernel, dim3((dstW + 255) / 256, grid_rows((dstH + strip - 1) / strip)), block, 0, stream, a, strip);
+            }
         }
         else
+        {
+            DXTEX_MARK("resize_cubic");
             hipLaunchKernelGGL(resize_cubic_kernel, grid, block, 0, stream, a);
+        }
         break;
     case 0x400000u:
         if (format == FMT_R8G8B8A8_UNORM && !a.srgbIn && !a.srgbOut && srcW == 2 * dstW && srcH == 2 * dstH && (dstW % 2) == 0 && dstW >= 256 &&
             (srcPitch % 16) == 0 && (dstPitch % 8) == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 && (reinterpret_cast<uintptr_t>(dst) % 8) == 0)
+        {
+            DXTEX_MARK("resize_box_half_rgba8");
             hipLaunchKernelGGL(resize_box_half_rgba8_kernel, dim3((dstW / 2 + 255) / 256, grid_rows(dstH)), block, 0, stream, a);
+        }
         else
+        {
+            DXTEX_MARK("resize_box");
             hipLaunchKernelGGL(resize_box_kernel, grid, block, 0, stream, a);
+        }
         break;
-    case 0x500000u: hipLaunchKernelGGL(resize_triangle_kernel, grid, block, 0, stream, a); break;
+    case 0x500000u: DXTEX_MARK("resize_triangle"); hipLaunchKernelGGL(resize_triangle_kernel, grid, block, 0, stream, a); break;
     default: return hipErrorInvalidValue;
     }
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
 bool resize_half_tail_applies(const MipLevel* levels, int nlevels, int format, uint32_t filterFlags);
 hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, uint32_t filterMode, uint32_t filterFlags,
-                              const MipLevel* twoHigh, hipStream_t stream)
+                              const MipLevel* twoHigh, hipStream_t stream, KernelMarks* marks)
 {
     if (nlevels < 2) return hipSuccess;
     const bool halving = (filterMode == 0x300000u || filterMode == 0x400000u) && resize_half_tail_applies(levels, nlevels, format, filterFlags);
@@ -1267,7 +1299,8 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
         for (int k = 1; k < nlevels; ++k)
         {
             const hipError_t e = launch_resize(levels[k - 1].pixels, levels[k - 1].pitch, levels[k - 1].width, levels[k - 1].height, levels[k].pixels, levels[k].pitch,
-                                               levels[k].width, levels[k].height, format, filterMode, filterFlags, true, nullptr, stream);
+                                               levels[k].width, levels[k].height, format, filterMode, filterFlags, true, nullptr, stream,
+                                               nullptr, 0, 0, -1, marks);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -1285,8 +1318,9 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
             c.dst[k - 1] = levels[k].pixels; c.dstPitch[k - 1] = levels[k].pitch;
         }
         for (int k = nlevels - 1; k < kTailMaxLevels; ++k) { c.dst[k] = c.dst[0]; c.dstPitch[k] = c.dstPitch[0]; }
-        if (filterMode == 0x300000u) hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<true>, dim3(1), dim3(1024), 0, stream, c);
-        else hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<false>, dim3(1), dim3(1024), 0, stream, c);
+        if (filterMode == 0x300000u) { DXTEX_MARK("resize_half_tail_rgba8<cubic>"); hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<true>, dim3(1), dim3(1024), 0, stream, c); }
+        else { DXTEX_MARK("resize_half_tail_rgba8<box>"); hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<false>, dim3(1), dim3(1024), 0, stream, c); }
+        DXTEX_MARK(nullptr);
         return hipGetLastError();
     }
     TailArgs t;
@@ -1308,11 +1342,13 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
         t.nlevels = std::min(kTailMaxLevels, nlevels - at);
         for (int k = 0; k < t.nlevels; ++k) t.level[k] = make_view(levels[at + k].pixels, levels[at + k].pitch, levels[at + k].width, levels[at + k].height, format);
         for (int k = t.nlevels; k < kTailMaxLevels; ++k) t.level[k] = t.level[0];
+        DXTEX_MARK("resize_tail");
         hipLaunchKernelGGL(resize_tail_kernel, dim3(1), dim3(1024), 0, stream, t);
         // a chain with more than kTailMaxLevels tail levels (cannot happen below 64 x 64, kept for safety) continues from the last one written
         a.src = t.level[t.nlevels - 1];
         at += t.nlevels;
     }
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
@@ -1414,16 +1450,19 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
 }
 
 hipError_t launch_mse(const uint8_t* a, uint64_t aPitch, int aFormat, const uint8_t* b, uint64_t bPitch, int bFormat,
-                      uint32_t width, uint32_t height, double* out4, hipStream_t stream)
+                      uint32_t width, uint32_t height, double* out4, hipStream_t stream, KernelMarks* marks)
 {
     hipError_t e = hipMemsetAsync(out4, 0, 4 * sizeof(double), stream);
     if (e != hipSuccess) return e;
     if (!width || !height) return hipSuccess;
     const bool ignoreAlpha = aFormat == FMT_B8G8R8X8_UNORM || aFormat == FMT_B8G8R8X8_UNORM_SRGB || bFormat == FMT_B8G8R8X8_UNORM || bFormat == FMT_B8G8R8X8_UNORM_SRGB;
     const uint32_t gx = std::min<uint32_t>((width + 255) / 256, 64), gy = std::min<uint32_t>(height, 1024);
+    DXTEX_MARK("mse");
     hipLaunchKernelGGL(mse_kernel, dim3(gx, gy), dim3(256), 0, stream, make_view(a, aPitch, width, height, aFormat),
                        make_view(b, bPitch, width, height, bFormat), srgb_linear_format(aFormat) ? 1 : 0, srgb_linear_format(bFormat) ? 1 : 0,
                        ignoreAlpha ? 1 : 0, out4);
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
+#undef DXTEX_MARK
 } // namespace dxtex

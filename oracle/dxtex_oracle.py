@@ -115,6 +115,14 @@ _F = np.float32
 def load_image(pixels, width, height, fmt, row_pitch=None):
     """-> (H, W, 4) float32, exactly what LoadScanline puts in the XMVECTOR row buffer."""
     raw = np.ascontiguousarray(pixels).view(np.uint8).reshape(-1)
+    if fmt == 68:              # R8G8_B8G8_UNORM: one XMLoadUByteN4 per two texels, (r, g0, b, 1) and (r, g1, b, 1), :1192-1205
+        ne = (width + 1) // 2
+        rp = row_pitch or ne * 4
+        v = np.stack([raw[y * rp: y * rp + ne * 4] for y in range(height)]).reshape(height, ne, 4).astype(np.float32) * _F(1.0 / 255.0)
+        out = np.ones((height, ne * 2, 4), np.float32)
+        out[:, 0::2, :3] = v[..., :3]
+        out[:, 1::2, :3] = v[..., [0, 3, 2]]
+        return out[:, :width].copy()
     bpp = {2: 16, 10: 8, 28: 4, 29: 4, 87: 4, 88: 4, 91: 4, 93: 4, 49: 2, 61: 1, 63: 1, 65: 1, 41: 4, 54: 2}[fmt]
     rp = row_pitch or width * bpp
     rows = np.stack([raw[y * rp: y * rp + width * bpp] for y in range(height)])
