@@ -51,6 +51,39 @@ class Image(ctypes.Structure):
                 ("rowPitch", ctypes.c_size_t), ("slicePitch", ctypes.c_size_t), ("pixels", ctypes.c_void_p)]
 
 
+class Transform(ctypes.Structure):
+    """dxtex_transform (include/dxtex_amd.h): one of texconv's per-texel ops for TransformImage."""
+    _fields_ = [("op", ctypes.c_uint32), ("swizzle", ctypes.c_uint32 * 4), ("zero", ctypes.c_uint32 * 4), ("one", ctypes.c_uint32 * 4),
+                ("colorKey", ctypes.c_uint32)]
+
+
+def make_transform(op, swizzle=(0, 1, 2, 3), zero=(0, 0, 0, 0), one=(0, 0, 0, 0), color_key=0):
+    """A Transform; `swizzle` may also be a texconv mask string such as "bgr1" (parse_swizzle_mask)."""
+    if isinstance(swizzle, str):
+        swizzle, zero, one = parse_swizzle_mask(swizzle)
+    return Transform(op, (ctypes.c_uint32 * 4)(*swizzle), (ctypes.c_uint32 * 4)(*zero), (ctypes.c_uint32 * 4)(*one), color_key)
+
+
+def parse_swizzle_mask(mask):
+    """texconv's ParseSwizzleMask (texconv.cpp:1157-1248) -> (swizzle, zero, one), or None for a bad mask: 1 to 4 characters of
+    rgbaxyzw01 (either case for the letters), the last repeated into the remaining channels."""
+    if not 1 <= len(mask) <= 4:
+        return None
+    swz, zero, one = [0, 1, 2, 3], [0] * 4, [0] * 4
+    for j, ch in enumerate(mask):
+        c = ch.lower()
+        for k in range(j, 4):
+            if c in "rgbaxyzw":
+                swz[k], zero[k], one[k] = "rgba".index(c) if c in "rgba" else "xyzw".index(c), 0, 0
+            elif ch == "0":
+                swz[k], zero[k], one[k] = k, 1, 0
+            elif ch == "1":
+                swz[k], zero[k], one[k] = k, 0, 1
+            else:
+                return None
+    return swz, zero, one
+
+
 _lib = None
 _P = ctypes.POINTER
 _ctx_p = ctypes.c_void_p
@@ -88,6 +121,8 @@ _SIGS = {
     "dxtex_convert_dither_stats": (ctypes.c_int32, [_ctx_p, _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),
     "dxtex_compute_normal_map": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_compute_normal_map_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_transform_image": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Transform)]),
+    "dxtex_transform_images_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, _P(Transform)]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -474,6 +509,25 @@ class Context:
         src = device_image(src_ptr, width, height, src_format, src_row_pitch)
         dst = device_image(dst_ptr, width, height, dst_format)
         self._check(self._lib.dxtex_compute_normal_map_device(self._h, ctypes.byref(src), ctypes.byref(dst), flags, amplitude), "compute_normal_map_device")
+
+    # -- TransformImage with texconv's per-texel ops -----------------------------------------------------------------------------
+    def transform_image(self, pixels, width, height, fmt, transform, row_pitch=None):
+        """dxtex_transform_image: one image (host pixels) through a Transform (make_transform). Returns the destination (tight pitch)
+        as a numpy uint8 buffer."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        rp, sp = compute_pitch(fmt, width, height)
+        out = np.zeros(sp, np.uint8)
+        dst = Image(width, height, fmt, rp, sp, out.ctypes.data)
+        self._check(self._lib.dxtex_transform_image(self._h, ctypes.byref(src), ctypes.byref(dst), ctypes.byref(transform)), "transform_image")
+        return out
+
+    def transform_images_device(self, srcs, dsts, transform):
+        """dxtex_transform_images_device: lists of device Images (device_image) of one format, asynchronous on the context's stream;
+        TONEMAP takes its maximum over all of `srcs`."""
+        n = len(srcs)
+        a, b = (Image * max(n, 1))(*srcs), (Image * max(n, 1))(*dsts)
+        self._check(self._lib.dxtex_transform_images_device(self._h, a, b, n, ctypes.byref(transform)), "transform_images_device")
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

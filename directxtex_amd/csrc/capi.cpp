@@ -5,6 +5,7 @@
 #include "dxtex_formats.h"
 #include "dxtex_kernels.h"
 #include "dxtex_nmap.h"
+#include "dxtex_transform.h"
 #include "dxtex_plan.h"
 #include "triangle_filter.h"
 
@@ -1295,6 +1296,20 @@ dxtex_hresult dxtex_convert_slice(dxtex_ctx* ctx, const dxtex_image* src, const 
 
 namespace
 {
+// E_INVALIDARG where the bytes of src's rows and dst's rows intersect (images of a non-zero size)
+dxtex_hresult check_no_overlap(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst)
+{
+    size_t srcRow = 0, srcSlice = 0, dstRow = 0, dstSlice = 0;
+    if (dxtex_compute_pitch(src.format, src.width, src.height, &srcRow, &srcSlice) != DXTEX_S_OK ||
+        dxtex_compute_pitch(dst.format, dst.width, dst.height, &dstRow, &dstSlice) != DXTEX_S_OK)
+        return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src.pixels), d0 = reinterpret_cast<uintptr_t>(dst.pixels);
+    const uintptr_t s1 = s0 + src.rowPitch * (srcSlice / std::max<size_t>(1, srcRow) - 1) + srcRow;
+    const uintptr_t d1 = d0 + dst.rowPitch * (dstSlice / std::max<size_t>(1, dstRow) - 1) + dstRow;
+    if (s0 < d1 && d0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "source and destination pixels overlap");
+    return DXTEX_S_OK;
+}
+
 // ComputeNormalMap's checks (DirectXTexNormalMaps.cpp:257-283, ComputeNMap :83-94), in its order; the destination's class decides the
 // encoding. Formats format_info() does not know (the ones GetConvertFlags has no entry for among them) are not supported here.
 dxtex_hresult check_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, bool* unorm)
@@ -1312,14 +1327,8 @@ dxtex_hresult check_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxt
     if (src->width != dst->width || src->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
     if (!src->width || !src->height) return DXTEX_S_OK;
     // the stencil reads rows above and below the one it writes: it cannot run in place
-    size_t srcRow = 0, srcSlice = 0, dstRow = 0, dstSlice = 0;
-    if (dxtex_compute_pitch(src->format, src->width, src->height, &srcRow, &srcSlice) != DXTEX_S_OK ||
-        dxtex_compute_pitch(dst->format, dst->width, dst->height, &dstRow, &dstSlice) != DXTEX_S_OK)
-        return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src->pixels), d0 = reinterpret_cast<uintptr_t>(dst->pixels);
-    const uintptr_t s1 = s0 + src->rowPitch * (srcSlice / std::max<size_t>(1, srcRow) - 1) + srcRow;
-    const uintptr_t d1 = d0 + dst->rowPitch * (dstSlice / std::max<size_t>(1, dstRow) - 1) + dstRow;
-    if (s0 < d1 && d0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "source and destination pixels overlap");
+    const dxtex_hresult hr = check_no_overlap(ctx, *src, *dst);
+    if (hr != DXTEX_S_OK) return hr;
     *unorm = (out->cls & FC_UNORM) != 0;
     return DXTEX_S_OK;
 }
@@ -1360,6 +1369,107 @@ dxtex_hresult dxtex_compute_normal_map(dxtex_ctx* ctx, const dxtex_image* src, c
     hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
     return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
                       { return submit_normal_map(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags, amplitude, unorm); });
+}
+
+namespace
+{
+// TransformImage's checks (DirectXTexMisc.cpp:606-700), in its order, over `count` source / destination pairs of one format; resolves what
+// the kernel needs of the descriptor. The four Xbox-only formats and everything else format_info() does not know are not supported.
+dxtex_hresult check_transform(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, const dxtex_transform* t, XformArgs* args)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!t) return fail(ctx, DXTEX_E_POINTER, "null transform");
+    if (!srcs || !dsts || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
+    if (t->op > DXTEX_TRANSFORM_RECONSTRUCT_Z) return fail(ctx, DXTEX_E_INVALIDARG, "unknown transform op");
+    const int format = srcs[0].format;
+    const FmtInfo* f = format_info(format);
+    if (!f || (f->cls & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "TransformImage does not take planar, palettised, compressed or typeless formats");
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_image& s = srcs[i];
+        const dxtex_image& d = dsts[i];
+        if (s.width > 0xFFFFFFFFull || s.height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+        if (s.format != format || d.format != format) return fail(ctx, DXTEX_E_FAIL, "format mismatch");
+        if (s.width != d.width || s.height != d.height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
+        if (!s.pixels || !d.pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+        if (s.width && s.height) { const dxtex_hresult hr = check_no_overlap(ctx, s, d); if (hr != DXTEX_S_OK) return hr; }
+    }
+    XformArgs a = {};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (t->op == DXTEX_TRANSFORM_SWIZZLE && t->swizzle[k] > 3) return fail(ctx, DXTEX_E_INVALIDARG, "swizzle index above 3");
+        a.swz[k] = t->swizzle[k] & 3u;
+        if (t->zero[k]) a.zero |= 1u << k;
+        if (t->one[k]) a.one |= 1u << k;
+    }
+    xf_color_key_value(t->colorKey & 0xFFFFFFu, a.key);
+    // FormatDataType (DirectXTexConvert.cpp:5529-5553): the convert-type bits are exactly UNORM
+    a.unorm = (f->cls & (FC_UNORM | FC_SNORM | FC_FLOAT | FC_UINT | FC_SINT)) == FC_UNORM;
+    *args = a;
+    return DXTEX_S_OK;
+}
+
+// the transform of `count` images on the stream; for TONEMAP every source is reduced into the context's result word before the first
+// destination is written, and the apply kernels read it there
+dxtex_hresult submit_transform(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t op, const XformArgs& args)
+{
+    Marks* marks = ctx->profiling ? &ctx->marks : nullptr;
+    uint32_t* maxBits = nullptr;
+    if (op == DXTEX_TRANSFORM_TONEMAP)
+    {
+        const dxtex_hresult hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+        maxBits = static_cast<uint32_t*>(ctx->mseBuf.p);
+        HIP_TRY(ctx, hipMemsetAsync(maxBits, 0, sizeof(uint32_t), ctx->stream));
+        for (size_t i = 0; i < count; ++i)
+        {
+            const dxtex_image& s = srcs[i];
+            const hipError_t e = launch_tonemap_max(s.pixels, s.rowPitch, s.format, uint32_t(s.width), uint32_t(s.height), maxBits, ctx->stream, marks);
+            if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        }
+    }
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_image& src = srcs[i];
+        const dxtex_image& dst = dsts[i];
+        const size_t width = src.width, height = src.height;
+        if (!width || !height) continue;
+        uint8_t* out = dst.pixels; size_t outPitch = dst.rowPitch; int outFormat = dst.format;
+        const bool grouped = is_group_format(dst.format);
+        if (grouped)
+        {
+            const dxtex_hresult hr = group_rows(ctx, width, height, &out, &outPitch);
+            if (hr != DXTEX_S_OK) return hr;
+            outFormat = FMT_R32G32B32A32_FLOAT;
+        }
+        hipError_t e = launch_transform(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), op, args, maxBits,
+                                        ctx->stream, marks);
+        if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream, marks);
+        if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    }
+    return DXTEX_S_OK;
+}
+} // namespace
+
+dxtex_hresult dxtex_transform_images_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, const dxtex_transform* t)
+{
+    XformArgs args;
+    const dxtex_hresult hr = check_transform(ctx, srcs, dsts, count, t, &args);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_transform(ctx, srcs, dsts, count, t->op, args); });
+}
+
+dxtex_hresult dxtex_transform_image(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, const dxtex_transform* t)
+{
+    XformArgs args;
+    dxtex_hresult hr = check_transform(ctx, src, dst, src && dst ? 1 : 0, t, &args);
+    if (hr != DXTEX_S_OK) return hr;
+    size_t srcBytes = 0, dstBytes = 0;
+    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
+                      {
+                          const dxtex_image s = with_pixels(*src, in), d = with_pixels(*dst, out);
+                          return submit_transform(ctx, &s, &d, 1, t->op, args);
+                      });
 }
 
 namespace

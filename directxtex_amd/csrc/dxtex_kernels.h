@@ -69,6 +69,17 @@ hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int src
 hipError_t launch_normal_map(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
                              uint32_t width, uint32_t height, uint32_t flags, float amplitude, bool unorm, hipStream_t stream);
 
+// TransformImage of one image with one of texconv's per-texel ops (op = XFORM_*, args resolved by the caller, see dxtex_transform.h):
+// LoadScanline -> op -> StoreScanline with threshold 0. dstFormat's rows as for launch_normal_map (R32G32B32A32_FLOAT rows for
+// launch_pack_group where the destination packs several texels). XFORM_TONEMAP reads the maximum luminance's bits from maxBits (device
+// memory), which launch_tonemap_max folds each image of the set into (the caller zeroes it first).
+struct XformArgs;
+hipError_t launch_transform(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
+                            uint32_t width, uint32_t height, uint32_t op, const XformArgs& args, const uint32_t* maxBits, hipStream_t stream,
+                            KernelMarks* marks = nullptr);
+hipError_t launch_tonemap_max(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, uint32_t* maxBits, hipStream_t stream,
+                              KernelMarks* marks = nullptr);
+
 // Resize / one mip level. filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row
 // ofs[i]..ofs[i+1] indexes (source index, fp32 weight bits) pairs, see triangle_filter.h. `staleLevel` (box mips only):

@@ -8,6 +8,8 @@
 //   Generate2DMips{Point,Box,Linear,Cubic,Triangle}Filter (DirectXTexMipmaps.cpp:907-1602)   resize_*_kernel
 //   ComputeMSE_ (DirectXTexMisc.cpp:27-176)                                mse_kernel
 //   ComputeNMap (DirectXTexNormalMaps.cpp:77-240)                          nmap_kernel
+//   TransformImage / EvaluateImage (DirectXTexMisc.cpp:179-263) with       transform_kernel<op>, tonemap_max_kernel
+//     texconv's swizzle / tone-map / colour-key / invert-Y / reconstruct-Z lambdas
 //
 // The reference walks scanlines through a float4 row buffer (LoadScanline -> filter -> StoreScanline). Here every
 // lane owns one destination texel and reads the source texels it needs straight from HBM/L2 with LoadScanline's
@@ -20,6 +22,7 @@
 #include "dxtex_formats.h"
 #include "cubic_filter.h"
 #include "dxtex_nmap.h"
+#include "dxtex_transform.h"
 #include <algorithm>
 
 namespace dxtex
@@ -346,6 +349,49 @@ __global__ void __launch_bounds__(kNmapThreads) nmap_kernel(NmapArgs a)
                 store_texel(a.dst.pixels + uint64_t(y) * a.dst.rowPitch, uint32_t(x), a.dst.format, Texel{ o.x, o.y, o.z, o.w });
             }
         }
+    }
+}
+
+// ---- TransformImage with texconv's per-texel lambdas (DirectXTexMisc.cpp:179-263, texconv.cpp:2645-3301) --------------------------------
+// LoadScanline -> op -> StoreScanline (threshold 0), a destination texel per lane, in convert_kernel's shape. The op is a template
+// argument: one kernel per op, no mode word in the loop. TONEMAP reads the running maximum's bits that tonemap_max_kernel left in
+// device memory, so the two passes follow each other on the stream with no host round trip.
+template<uint32_t OP>
+__global__ void __launch_bounds__(256) transform_kernel(ImgView src, ImgView dst, XformArgs a, const uint32_t* maxBits)
+{
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= src.width) return;
+    float M = 0.0f;
+    if constexpr (OP == XFORM_TONEMAP) { const float m = xf_float(*maxBits); M = m * m; }
+    for (uint32_t y = blockIdx.y; y < src.height; y += gridDim.y)
+    {
+        const Texel t = load_texel(src.pixels + uint64_t(y) * src.rowPitch, x, src.format);
+        float c[4] = { t.r, t.g, t.b, t.a };
+        xf_apply<OP>(c, a, M);
+        store_texel(dst.pixels + uint64_t(y) * dst.rowPitch, x, dst.format, Texel{ c[0], c[1], c[2], c[3] });
+    }
+}
+
+// The tone map's maximum luminance of one image, folded into *maxBits: a wave and a workgroup maximum, then one global atomic max per
+// workgroup on the float's bits (every candidate is +0 or above, where unsigned order is float order).
+__global__ void __launch_bounds__(256) tonemap_max_kernel(ImgView src, uint32_t* maxBits)
+{
+    __shared__ uint32_t waveMax[4];
+    uint32_t m = 0;
+    for (uint32_t y = blockIdx.y; y < src.height; y += gridDim.y)
+        for (uint32_t x = blockIdx.x * 256u + threadIdx.x; x < src.width; x += gridDim.x * 256u)
+        {
+            const Texel t = load_texel(src.pixels + uint64_t(y) * src.rowPitch, x, src.format);
+            m = max(m, xf_lum_bits(t.r, t.g, t.b));
+        }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, uint32_t(__shfl_xor(int(m), o)));
+    if ((threadIdx.x & 63u) == 0) waveMax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        m = max(max(waveMax[0], waveMax[1]), max(waveMax[2], waveMax[3]));
+        if (m) atomicMax(maxBits, m);
     }
 }
 
@@ -1180,6 +1226,42 @@ hipError_t launch_normal_map(const uint8_t* src, uint64_t srcPitch, int srcForma
     a.flags = flags; a.amplitude = amplitude; a.unorm = unorm ? 1 : 0;
     a.strips = uint32_t((uint64_t(height) + kNmapRows - 1u) / kNmapRows);
     hipLaunchKernelGGL(nmap_kernel, dim3(uint32_t((uint64_t(width) + kNmapThreads - 1u) / kNmapThreads), grid_rows(a.strips)), dim3(kNmapThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_transform(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
+                            uint32_t width, uint32_t height, uint32_t op, const XformArgs& args, const uint32_t* maxBits, hipStream_t stream,
+                            KernelMarks* marks)
+{
+    if (!width || !height) return hipSuccess;
+    const ImgView sv = make_view(src, srcPitch, width, height, srcFormat), dv = make_view(dst, dstPitch, width, height, dstFormat);
+    // about 8192 workgroups, as convert_quad launches: a workgroup walks several rows rather than one workgroup being dispatched per row
+    const uint32_t gx = (width + 255) / 256;
+    const dim3 grid(gx, std::min<uint32_t>(grid_rows(height), std::max<uint32_t>(1u, 8192u / gx)));
+#define DXTEX_XFORM(OP, NAME) do { DXTEX_MARK(NAME); hipLaunchKernelGGL(transform_kernel<OP>, grid, dim3(256), 0, stream, sv, dv, args, maxBits); } while (0)
+    switch (op)
+    {
+    case XFORM_SWIZZLE: DXTEX_XFORM(XFORM_SWIZZLE, "transform<swizzle>"); break;
+    case XFORM_TONEMAP: DXTEX_XFORM(XFORM_TONEMAP, "transform<tonemap>"); break;
+    case XFORM_COLOR_KEY: DXTEX_XFORM(XFORM_COLOR_KEY, "transform<color_key>"); break;
+    case XFORM_INVERT_Y: DXTEX_XFORM(XFORM_INVERT_Y, "transform<invert_y>"); break;
+    case XFORM_RECONSTRUCT_Z: DXTEX_XFORM(XFORM_RECONSTRUCT_Z, "transform<reconstruct_z>"); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef DXTEX_XFORM
+    DXTEX_MARK(nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_tonemap_max(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, uint32_t* maxBits, hipStream_t stream,
+                              KernelMarks* marks)
+{
+    if (!width || !height) return hipSuccess;
+    // about 2048 workgroups at most, each looping over its rows: one atomic per workgroup stays far below the cost of the read
+    const uint32_t gx = std::min<uint32_t>((width + 255) / 256, 8), gy = std::min<uint32_t>(height, std::max<uint32_t>(1u, 2048u / gx));
+    DXTEX_MARK("tonemap_max");
+    hipLaunchKernelGGL(tonemap_max_kernel, dim3(gx, gy), dim3(256), 0, stream, make_view(src, srcPitch, width, height, format), maxBits);
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 

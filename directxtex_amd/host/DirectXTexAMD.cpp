@@ -4,6 +4,7 @@
 #include "../../include/dxtex_amd.h"
 
 #include <algorithm>
+#include <cctype>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -1354,6 +1355,93 @@ HRESULT ComputeNormalMap(Device& device, const Image* srcImages, size_t nimages,
     return ComputeNormalMapArrayT<HostSpace>(device, srcImages, nimages, metadata, flags, amplitude, format, normalMaps);
 }
 
+// ---- TransformImage (DirectXTexMisc.cpp:606-700) with texconv's per-texel ops -------------------------------------------------------
+namespace
+{
+bool XformUnsupported(DXGI_FORMAT f) noexcept { return IsPlanar(f) || IsPalettized(f) || IsCompressed(f) || IsTypeless(f); }
+
+dxtex_transform XformDesc(const TexTransform& t) noexcept
+{
+    dxtex_transform d;
+    d.op = uint32_t(t.op);
+    for (int k = 0; k < 4; ++k) { d.swizzle[k] = t.swizzle[k]; d.zero[k] = t.zero[k]; d.one[k] = t.one[k]; }
+    d.colorKey = t.colorKey;
+    return d;
+}
+
+// the array form's checks that come before the destination exists (:622-636)
+HRESULT XformSetChecks(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata) noexcept
+{
+    if (!device) return E_POINTER;
+    if (!srcImages || !nimages) return E_INVALIDARG;
+    if (XformUnsupported(metadata.format)) return HRESULT_E_NOT_SUPPORTED;
+    if (metadata.width > UINT32_MAX || metadata.height > UINT32_MAX) return E_INVALIDARG;
+    if (metadata.IsVolumemap() && metadata.depth > UINT16_MAX) return E_INVALIDARG;
+    return S_OK;
+}
+}
+
+bool ParseSwizzleMask(const char* mask, TexTransform& t) noexcept
+{
+    if (!mask || !mask[0] || std::strlen(mask) > 4) return false;
+    TexTransform p;
+    for (uint32_t j = 0; j < 4 && mask[j]; ++j)
+    {
+        const char c = char(std::tolower(static_cast<unsigned char>(mask[j])));
+        const char* letters = "rgbaxyzw";
+        const char* at = std::strchr(letters, c);
+        for (uint32_t k = j; k < 4; ++k)
+        {
+            if (at && c) { p.swizzle[k] = uint32_t(at - letters) & 3u; p.zero[k] = 0; p.one[k] = 0; }
+            else if (c == '0') { p.swizzle[k] = k; p.zero[k] = 1; p.one[k] = 0; }
+            else if (c == '1') { p.swizzle[k] = k; p.zero[k] = 0; p.one[k] = 1; }
+            else return false;
+        }
+    }
+    p.op = TEX_TRANSFORM_SWIZZLE;
+    t = p;
+    return true;
+}
+
+bool IsIdentitySwizzle(const TexTransform& t) noexcept
+{
+    for (uint32_t k = 0; k < 4; ++k)
+        if (t.swizzle[k] != k || t.zero[k] || t.one[k]) return false;
+    return true;
+}
+
+HRESULT TransformImage(Device& device, const Image& srcImage, const TexTransform& transform, ScratchImage& result) noexcept
+{
+    if (!device) return E_POINTER;
+    if (srcImage.width > UINT32_MAX || srcImage.height > UINT32_MAX) return E_INVALIDARG;
+    if (XformUnsupported(srcImage.format)) return HRESULT_E_NOT_SUPPORTED;
+    result.Release();
+    HRESULT hr = result.Initialize2D(srcImage.format, srcImage.width, srcImage.height, 1, 1);
+    if (FAILED(hr)) return hr;
+    const Image* img = result.GetImage(0, 0, 0);
+    if (!img) { result.Release(); return E_POINTER; }
+    const dxtex_image s = View(srcImage), d = View(*img);
+    const dxtex_transform desc = XformDesc(transform);
+    hr = dxtex_transform_image(device.Get(), &s, &d, &desc);
+    if (FAILED(hr)) result.Release();
+    return hr;
+}
+
+HRESULT TransformImage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, const TexTransform& transform,
+                       ScratchImage& result) noexcept
+{
+    HRESULT hr = XformSetChecks(device, srcImages, nimages, metadata);
+    if (FAILED(hr)) return hr;
+    result.Release();
+    // one upload of the set (it checks every image against the layout: E_FAIL for a format or size mismatch), the resident call, one download
+    DeviceScratchImage in, out;
+    hr = in.Upload(device, srcImages, nimages, metadata);
+    if (SUCCEEDED(hr)) hr = TransformImage(device, in, transform, out);
+    if (SUCCEEDED(hr)) hr = out.Download(result);
+    if (FAILED(hr)) result.Release();
+    return hr;
+}
+
 // ---- ScaleMipMapsAlphaForCoverage (DirectXTexMipmaps.cpp:3483-3556) ------------------------------------------------------------------
 namespace
 {
@@ -1604,6 +1692,25 @@ HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FL
 {
     if (!Resident(device, src)) return E_INVALIDARG;
     return ComputeNormalMapArrayT<DeviceSpace>(device, src.GetImages(), src.GetImageCount(), src.GetMetadata(), flags, amplitude, format, normalMaps);
+}
+
+HRESULT TransformImage(Device& device, const DeviceScratchImage& src, const TexTransform& transform, DeviceScratchImage& result) noexcept
+{
+    if (!Resident(device, src)) return E_INVALIDARG;
+    const TexMetadata& metadata = src.GetMetadata();
+    HRESULT hr = XformSetChecks(device, src.GetImages(), src.GetImageCount(), metadata);
+    if (FAILED(hr)) return hr;
+    result.Release();
+    hr = result.Initialize(device, metadata);
+    if (FAILED(hr)) return hr;
+    if (src.GetImageCount() != result.GetImageCount()) { result.Release(); return E_FAIL; }
+    const size_t n = src.GetImageCount();
+    std::vector<dxtex_image> s(n), d(n);
+    for (size_t i = 0; i < n; ++i) { s[i] = View(src.GetImages()[i]); d[i] = View(result.GetImages()[i]); }
+    const dxtex_transform desc = XformDesc(transform);
+    hr = dxtex_transform_images_device(device.Get(), s.data(), d.data(), n, &desc);
+    if (FAILED(hr)) result.Release();
+    return hr;
 }
 
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const DeviceScratchImage& src, float alphaReference, DeviceScratchImage& mipChain) noexcept

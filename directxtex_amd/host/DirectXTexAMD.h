@@ -295,6 +295,28 @@ inline CNMAP_FLAGS operator|(CNMAP_FLAGS a, CNMAP_FLAGS b) noexcept { return CNM
 HRESULT ComputeNormalMap(Device& device, const Image& srcImage, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, ScratchImage& normalMap) noexcept;
 HRESULT ComputeNormalMap(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, CNMAP_FLAGS flags, float amplitude,
                          DXGI_FORMAT format, ScratchImage& normalMaps) noexcept;
+// TransformImage (DirectXTex.h:918-929) with one of texconv's per-texel lambdas as a descriptor, since a std::function cannot run on the
+// GPU: TexTransform mirrors dxtex_transform (include/dxtex_amd.h, which states each op). ParseSwizzleMask is texconv's
+// (texconv.cpp:1157-1248, plus its 1-4 character rule): it fills a SWIZZLE descriptor and returns false for a bad mask. The array form
+// uploads the set once, transforms it on the device (TONEMAP takes its maximum over every image passed) and downloads it once. The result
+// has the source's metadata; on failure it is released.
+enum TEX_TRANSFORM_OP : uint32_t
+{
+    TEX_TRANSFORM_SWIZZLE = 0, TEX_TRANSFORM_TONEMAP = 1, TEX_TRANSFORM_COLOR_KEY = 2, TEX_TRANSFORM_INVERT_Y = 3, TEX_TRANSFORM_RECONSTRUCT_Z = 4,
+};
+struct TexTransform
+{
+    TEX_TRANSFORM_OP op = TEX_TRANSFORM_SWIZZLE;
+    uint32_t swizzle[4] = { 0, 1, 2, 3 };      // SWIZZLE: source channel of each output channel
+    uint32_t zero[4] = {};                     // SWIZZLE: non-zero = the output channel is 0
+    uint32_t one[4] = {};                      // SWIZZLE: non-zero = the output channel is 1
+    uint32_t colorKey = 0;                     // COLOR_KEY: 0x00RRGGBB
+};
+bool ParseSwizzleMask(const char* mask, TexTransform& transform) noexcept;
+bool IsIdentitySwizzle(const TexTransform& transform) noexcept;       // texconv.cpp:2646-2648: the swizzle step does not run
+HRESULT TransformImage(Device& device, const Image& srcImage, const TexTransform& transform, ScratchImage& result) noexcept;
+HRESULT TransformImage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, const TexTransform& transform,
+                       ScratchImage& result) noexcept;
 // ScaleMipMapsAlphaForCoverage (DirectXTex.h:848-851): mipChain must already be initialised with the chain's layout
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, size_t item,
                                      float alphaReference, ScratchImage& mipChain) noexcept;
@@ -356,6 +378,7 @@ HRESULT Resize(Device& device, const DeviceScratchImage& src, size_t width, size
 HRESULT Convert(Device& device, const DeviceScratchImage& src, DXGI_FORMAT format, TEX_FILTER_FLAGS filter, float threshold, DeviceScratchImage& result) noexcept;
 HRESULT PremultiplyAlpha(Device& device, const DeviceScratchImage& src, TEX_PMALPHA_FLAGS flags, DeviceScratchImage& result) noexcept;
 HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, DeviceScratchImage& normalMaps) noexcept;
+HRESULT TransformImage(Device& device, const DeviceScratchImage& src, const TexTransform& transform, DeviceScratchImage& result) noexcept;
 // every array item of a mip chain (the per-item loop texconv runs, texconv.cpp:3470-3490); the 10-step bisection per level reads 8 bytes back per step
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const DeviceScratchImage& src, float alphaReference, DeviceScratchImage& mipChain) noexcept;
 // level 0 of every array item / depth slice as a texture with one mip level (what texconv keeps before it regenerates a chain, texconv.cpp:3324-3380)

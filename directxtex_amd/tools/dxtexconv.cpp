@@ -1,9 +1,10 @@
 // dxtexconv - a texconv-style batch converter on top of the MI355X host layer (DirectXTexAMD.h): DDS in, DDS out, every
 // image-processing step on the GPU. The pipeline and its order are the reference tool's (Texconv/texconv.cpp): load (:2077-2090)
-// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> normal map (:3047-3098) or
-// convert (:3100-3140) -> mipmaps (:3302-3460) -> alpha-coverage preservation (:3462-3500) -> premultiply alpha (:3502-3545) ->
-// compress (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation
-// here (flips, swizzles, tone mapping, WIC codecs, dithered conversion) is refused, not approximated.
+// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> swizzle (:2645-2694) -> tone map
+// (:2966-3044) -> normal map (:3047-3098) or convert (:3100-3140) -> colour key (:3134-3191) -> invert Y (:3193-3240) -> reconstruct Z
+// (:3242-3301) -> mipmaps (:3302-3460) -> alpha-coverage preservation (:3462-3500) -> premultiply alpha (:3502-3545) -> compress
+// (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
+// rotations, HDR colour rotation, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
 //   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga>...        (-ft hdr | tga: Radiance / TGA output of level 0)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
@@ -15,6 +16,9 @@
 //     -x2bias              *2 - 1 on conversions to / from SNORM -sepalpha        resize / mip alpha separately (alpha mode custom)
 //     -nmap <l|r|g|b|a>[m|u|v][i][o]   height map -> normal map (channel; mirror both / u / v; invert sign; occlusion in alpha)
 //     -nmapamp <weight>    normal-map amplitude, default 1 (needs -nmap first)
+//     -swizzle <mask>      1-4 of rgbaxyzw01, the last repeated (e.g. bgr1, rrrg)    -tonemap   Reinhard tone map to LDR (maximum over all images)
+//     -c <hex-RGB>         colour key: texels near it become transparent (formats with alpha)    -inverty   g = 1 - g    -reconstructz   z from x, y
+//                          texconv's long names work too: --swizzle --tonemap --color-key --invert-y --reconstruct-z
 //     -dword -badtails -permissive -ignoremips -xlum            DDS reader tolerances (DDS_FLAGS)
 //     -dx10 -dx9           force the 'DX10' header (+ alpha mode) / a Direct3D 9 file        -tga20   TGA output with the 2.0 extension area
 //     -px <s> -sx <s> -l   output name prefix / suffix, lower case    -y   overwrite    -info (print what the files hold, no GPU)    -timing -nologo -gpu <n> | -gpus <a,b,...> (files dealt out over the GPUs)
@@ -88,6 +92,9 @@ struct Options
     bool nmap = false;                  // -nmap: ComputeNormalMap replaces the convert step
     uint32_t nmapFlags = 0;             // CNMAP_FLAGS
     float nmapAmplitude = 1.f;
+    TexTransform swizzle;               // -swizzle: runs unless it is the identity
+    bool tonemap = false, colorKey = false, invertY = false, reconstructZ = false;
+    uint32_t colorKeyValue = 0;         // -c: 0x00RRGGBB
     std::vector<int> gpus;              // one worker (own Device, own host thread) per entry; input i goes to worker i mod n
     size_t overlap = 2;                 // workers per listed GPU: file k + 1 is read, decoded and uploaded while file k's kernels run
     std::string prefix, suffix, out;
@@ -136,6 +143,7 @@ int usage()
 {
     std::fprintf(stderr, "usage: dxtexconv [-w W] [-h H] [-pow2] [-fl LEVEL] [-m N] [-f FORMAT] [-if FILTER] [-wrap] [-mirror] [-srgb|-srgbi|-srgbo]\n"
                          "                 [-pmalpha|-alpha] [-keepcoverage REF] [-at T] [-bc qxdu] [-x2bias] [-sepalpha] [-nmap <l|r|g|b|a>[m|u|v][i][o]] [-nmapamp W]\n"
+                         "                 [-swizzle MASK] [-tonemap] [-c RRGGBB] [-inverty] [-reconstructz]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N] -o <out.dds | dir> in.dds...\n");
     return 1;
@@ -202,6 +210,25 @@ bool Parse(int argc, char** argv, Options& o)
             if (!missing && end == v) { std::fprintf(stderr, "invalid value for -nmapamp (%s)\n", v); return false; }
             if (o.nmapAmplitude < 0.f) { std::fprintf(stderr, "normal map amplitude must be positive (%s)\n", v); return false; }
         }
+        else if (a == "-swizzle")
+        {
+            // texconv.cpp:1919-1931
+            const char* v = next();
+            if (missing) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return false; }
+            if (!*v || std::strlen(v) > 4) { std::fprintf(stderr, "Invalid value specified with -swizzle (%s)\n", v); return false; }
+            if (!ParseSwizzleMask(v, o.swizzle)) { std::fprintf(stderr, "-swizzle requires a 1 to 4 character mask composed of these letters: r, g, b, a, x, y, w, z, 0, 1\n"); return false; }
+        }
+        else if (a == "-c" || a == "-color-key")
+        {
+            // texconv.cpp:1825-1834: swscanf "%x", then & 0xFFFFFF
+            const char* v = next();
+            unsigned int key = 0;
+            if (missing || std::sscanf(v, "%x", &key) != 1) { std::fprintf(stderr, "Invalid value specified with -c (%s)\n", v); return false; }
+            o.colorKey = true; o.colorKeyValue = key & 0xFFFFFFu;
+        }
+        else if (a == "-tonemap") o.tonemap = true;
+        else if (a == "-inverty" || a == "-invert-y") o.invertY = true;
+        else if (a == "-reconstructz" || a == "-reconstruct-z") o.reconstructZ = true;
         else if (a == "-pow2") o.pow2 = true;
         else if (a == "-pmalpha") o.pmalpha = true;
         else if (a == "-alpha") o.demul = true;
@@ -321,8 +348,21 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     bool haveOriginal = false;
     if (IsCompressed(info.format))
     {
+        // texconv.cpp:2394-2448: BC4 / BC5 decode to four channels where a later step reads or writes the ones they lack
+        const TexTransform& sw = o.swizzle;
+        const bool swz123 = sw.swizzle[1] != 1 || sw.swizzle[2] != 2 || sw.swizzle[3] != 3 || sw.zero[1] || sw.zero[2] || sw.zero[3] || sw.one[1] || sw.one[2] || sw.one[3];
+        const bool swz23 = sw.swizzle[2] != 2 || sw.swizzle[3] != 3 || sw.zero[2] || sw.zero[3] || sw.one[2] || sw.one[3];
+        DXGI_FORMAT formatDecompress = DXGI_FORMAT_UNKNOWN;
+        switch (info.format)
+        {
+        case DXGI_FORMAT_BC4_SNORM: if (o.invertY || o.reconstructZ || swz123) formatDecompress = DXGI_FORMAT_R8G8B8A8_SNORM; break;
+        case DXGI_FORMAT_BC5_SNORM: if (o.reconstructZ || swz23) formatDecompress = DXGI_FORMAT_R8G8B8A8_SNORM; break;
+        case DXGI_FORMAT_BC4_UNORM: if (o.invertY || o.reconstructZ || swz123) formatDecompress = DXGI_FORMAT_R8G8B8A8_UNORM; break;
+        case DXGI_FORMAT_BC5_UNORM: if (o.reconstructZ || swz23) formatDecompress = DXGI_FORMAT_R8G8B8A8_UNORM; break;
+        default: break;
+        }
         DeviceScratchImage t;
-        check("decompress", Decompress(dev, image, DXGI_FORMAT_UNKNOWN, t));
+        check("decompress", Decompress(dev, image, formatDecompress, t));
         cimage = std::move(loaded); dcimage = std::move(image); haveOriginal = true;
         keep(t);
     }
@@ -363,6 +403,18 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         }
     }
 
+    // --- per-texel transforms on the resident image (TransformImage with texconv's lambdas); each one ends any hand-through of the blocks
+    auto transform = [&](const char* what, const TexTransform& t)
+    {
+        DeviceScratchImage r;
+        check(what, TransformImage(dev, image, t, r));
+        keep(r);
+        haveOriginal = false;
+    };
+    auto simple = [](TEX_TRANSFORM_OP op, uint32_t key = 0) { TexTransform t; t.op = op; t.colorKey = key; return t; };
+    if (!IsIdentitySwizzle(o.swizzle)) transform("swizzle", o.swizzle);
+    if (o.tonemap) transform("tonemap", simple(TEX_TRANSFORM_TONEMAP));
+
     // --- normal map (texconv.cpp:3047-3098), in place of the convert step; a compressed target gets texconv's intermediate format
     if (o.nmap)
     {
@@ -387,6 +439,10 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         keep(t);
         haveOriginal = false;
     }
+
+    if (o.colorKey && HasAlpha(info.format)) transform("colorkey", simple(TEX_TRANSFORM_COLOR_KEY, o.colorKeyValue));
+    if (o.invertY) transform("inverty", simple(TEX_TRANSFORM_INVERT_Y));
+    if (o.reconstructZ) transform("reconstructz", simple(TEX_TRANSFORM_RECONSTRUCT_Z));
 
     // --- mipmaps
     const bool keepCoverage = o.keepCoverage > 0.f && HasAlpha(info.format) && !IsAlphaAllOpaque(dev, image);

@@ -20,6 +20,9 @@
  *   ConvertCustom                              DirectXTexConvert.cpp:4804-4913 dxtex_convert
  *   Resize*Filter                              DirectXTexResize.cpp:255-803    dxtex_resize
  *   ComputeNMap                                DirectXTexNormalMaps.cpp:77-240 dxtex_compute_normal_map
+ *   TransformImage / EvaluateImage with        DirectXTexMisc.cpp:179-263      dxtex_transform_image
+ *     texconv's swizzle, tone-map, colour-key,   texconv.cpp:2645-3301
+ *     invert-Y and reconstruct-Z lambdas
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -226,6 +229,36 @@ dxtex_hresult dxtex_convert_dither_stats(dxtex_ctx* ctx, uint64_t* rerunTexels, 
 #define DXTEX_CNMAP_COMPUTE_OCCLUSION  0x8000u
 dxtex_hresult dxtex_compute_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, float amplitude);
 dxtex_hresult dxtex_compute_normal_map_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, float amplitude);
+
+/* TransformImage (DirectXTexMisc.cpp:606-700) with one of texconv's per-texel lambdas, described instead of passed as a function:
+ * LoadScanline -> op -> StoreScanline (threshold 0), no sRGB conversion. Channels an op does not write keep their bits.
+ *   SWIZZLE        out[k] = in[swizzle[k]] (0..3), then 0 where zero[k], then 1 where one[k] (texconv.cpp:2645-2694)
+ *   TONEMAP        Reinhard with the maximum luminance (r * 0.3 + g * 0.59) + b * 0.11 over ALL the sources of the call, taken before any
+ *                  destination is written; alpha kept (:2966-3044)
+ *   COLOR_KEY      colorKey = 0x00RRGGBB: a texel within 0.2 of the key in r, g and b becomes (0, 0, 0, 0), every other one gets alpha 1
+ *                  (:3134-3191; texconv runs it only where HasAlpha(format))
+ *   INVERT_Y       g = 1 - g (:3193-3240)
+ *   RECONSTRUCT_Z  b = sqrt(1 - (x^2 + y^2)), on x * 2 - 1 and with * 0.5 + 0.5 when FormatDataType(format) is UNORM (:3242-3301)
+ * Source and destination share format and size. HRESULTs: NOT_SUPPORTED for planar, palettised, compressed, typeless and unknown formats;
+ * E_INVALIDARG for a width or height above UINT32_MAX, a bad op or swizzle index and overlapping pixels; E_FAIL for a format or size
+ * mismatch between the images; E_POINTER for null pixels. */
+#define DXTEX_TRANSFORM_SWIZZLE        0u
+#define DXTEX_TRANSFORM_TONEMAP        1u
+#define DXTEX_TRANSFORM_COLOR_KEY      2u
+#define DXTEX_TRANSFORM_INVERT_Y       3u
+#define DXTEX_TRANSFORM_RECONSTRUCT_Z  4u
+typedef struct dxtex_transform
+{
+    uint32_t op;            /* DXTEX_TRANSFORM_* */
+    uint32_t swizzle[4];    /* SWIZZLE: source channel of each output channel */
+    uint32_t zero[4];       /* SWIZZLE: non-zero = the output channel is 0 */
+    uint32_t one[4];        /* SWIZZLE: non-zero = the output channel is 1 (after zero) */
+    uint32_t colorKey;      /* COLOR_KEY: 0x00RRGGBB (the high byte is ignored) */
+} dxtex_transform;
+/* host pointers, one image, through the context's staging; returns when the destination has landed */
+dxtex_hresult dxtex_transform_image(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, const dxtex_transform* t);
+/* device pointers, `count` images of one format (a mip chain, an array, volume slices): asynchronous on the context's stream */
+dxtex_hresult dxtex_transform_images_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, const dxtex_transform* t);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
