@@ -763,15 +763,15 @@ __global__ void __launch_bounds__(256) bc_decode_kernel(DecodeArgs a)
 }
 } // namespace
 
-hipError_t launch_bc_decode(const uint8_t* src, uint64_t srcRowPitch, int srcFormat, uint8_t* dst, uint64_t dstRowPitch, int dstFormat,
-                            uint32_t width, uint32_t height, const ConvertPlan& plan, hipStream_t stream)
+hipError_t launch_bc_decode(const ImgView& src, const ImgView& dst, const ConvertPlan& plan, hipStream_t stream)
 {
+    const int srcFormat = src.format, dstFormat = dst.format;
     DecodeArgs a;
-    a.src = src; a.srcRowPitch = srcRowPitch; a.srcFormat = srcFormat;
-    a.dst = dst; a.dstRowPitch = dstRowPitch; a.dstFormat = dstFormat;
-    a.width = width; a.height = height; a.nbw = (width + 3) / 4; a.nbh = (height + 3) / 4;
+    a.src = src.pixels; a.srcRowPitch = src.rowPitch; a.srcFormat = srcFormat;
+    a.dst = dst.pixels; a.dstRowPitch = dst.rowPitch; a.dstFormat = dstFormat;
+    a.width = dst.width; a.height = dst.height; a.nbw = (dst.width + 3) / 4; a.nbh = (dst.height + 3) / 4;
     a.plan = plan;
-    a.vec16 = ((reinterpret_cast<uintptr_t>(dst) | dstRowPitch) & 15u) == 0;
+    a.vec16 = ((reinterpret_cast<uintptr_t>(dst.pixels) | dst.rowPitch) & 15u) == 0;
     const bool emptyPlan = !plan.srgbIn && !plan.srgbOut && plan.tcv == TCV_NONE && plan.tsw == TSW_NONE && !plan.depth;
     const bool rgba8 = dstFormat == FMT_R8G8B8A8_UNORM || dstFormat == FMT_R8G8B8A8_UNORM_SRGB;
     switch (srcFormat)

@@ -71,7 +71,9 @@ struct dxtex_ctx
     DeviceBuf triBuf;
     std::vector<uint8_t> triHost;
     PinnedBuf triPinned; hipEvent_t triConsumed = nullptr; bool triPending = false;
-    DeviceBuf mseBuf;
+    // the result of a reduction on its way to the host or to the next kernel: ComputeMSE's four sums, the alpha-coverage and below-threshold
+    // counts, the tone-map maximum. 4 doubles; the stream orders its users, and each of them (or its launcher) clears what it accumulates into
+    DeviceBuf resultCell;
     // R32G32B32A32_FLOAT rows on their way into a format whose element holds several texels (launch_pack_group)
     DeviceBuf groupRows;
     // error-diffusion Convert: row buffers (launch_convert_diffuse) and the device counter of texels its merge re-ran
@@ -118,6 +120,16 @@ dxtex_hresult fail(dxtex_ctx* ctx, dxtex_hresult hr, const char* what, hipError_
     }
     return hr;
 }
+
+// what an entry point returns for the status of the launches it queued
+dxtex_hresult launched(dxtex_ctx* ctx, hipError_t e) { return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e); }
+
+// where launchers record their kernels' names: the context's marks while it is profiling, nowhere otherwise
+Marks* marks_of(dxtex_ctx* ctx) { return ctx->profiling ? &ctx->marks : nullptr; }
+
+// The surface of an image as the launchers take it. The only place that narrows an image's extents to 32 bits: the check_* of the entry
+// points bound them.
+ImgView view_of(const dxtex_image& im) { return ImgView{ im.pixels, im.rowPitch, uint32_t(im.width), uint32_t(im.height), im.format }; }
 
 // every host <-> device copy of the library goes through here so that dxtex_ctx_transfer_bytes can account for it
 inline hipError_t counted_copy(dxtex_ctx* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t stream)
@@ -260,14 +272,13 @@ dxtex_hresult encode(dxtex_ctx* ctx, const SrcView& v, uint8_t* dst, size_t dstR
     const uint64_t nblocks = uint64_t((v.width + 3) / 4) * uint64_t((v.height + 3) / 4);
     const dxtex_hresult hr = grow_scratch(ctx, format, nblocks, flags);
     if (hr != DXTEX_S_OK) return hr;
-    KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
+    KernelMarks* marks = marks_of(ctx);
     hipError_t e;
     if (is_bc7(format)) e = launch_bc7_encode(v, dst, dstRowPitch, flags, ctx->scratch.p, ctx->stream, marks, side_streams(ctx));
     else if (is_bc6h(format)) e = launch_bc6h_encode(v, dst, dstRowPitch, format == FMT_BC6H_SF16, ctx->scratch.p, ctx->stream, marks, side_streams(ctx));
     else if (is_bc15(format)) e = launch_bc15_encode(v, dst, dstRowPitch, format, flags, threshold, ctx->stream);
     else return fail(ctx, DXTEX_E_NOT_SUPPORTED, "BC format not implemented yet");
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-    return DXTEX_S_OK;
+    return launched(ctx, e);
 }
 
 dxtex_hresult submit_compress(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags, float threshold)
@@ -332,8 +343,45 @@ dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, voi
     return DXTEX_S_OK;
 }
 
-struct LevelPair { const uint8_t* src; size_t srcPitch, sw, sh; uint8_t* dst; size_t dstPitch, dw, dh; };
-LevelPair pair_of(const dxtex_image& s, const dxtex_image& d) { return { s.pixels, s.rowPitch, s.width, s.height, d.pixels, d.rowPitch, d.width, d.height }; }
+// run_staged for a source and a destination image: submit(src, dst) receives the two images with their pixels in the staging
+template<class Submit>
+dxtex_hresult run_staged_images(dxtex_ctx* ctx, const dxtex_image* src, size_t srcBytes, const dxtex_image* dst, size_t dstBytes, Submit&& submit)
+{
+    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes,
+                      [&](uint8_t* in, uint8_t* out) { return submit(with_pixels(*src, in), with_pixels(*dst, out)); });
+}
+
+// The host-pointer twin of a single-image entry point, after its check_*: the pitch checks (so the staging holds every byte the kernels
+// touch), then submit(src, dst) - what the _device twin runs on the caller's images - on the staged ones.
+template<class Submit>
+dxtex_hresult run_host_twin(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, Submit&& submit)
+{
+    size_t srcBytes = 0, dstBytes = 0;
+    const dxtex_hresult hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_staged_images(ctx, src, srcBytes, dst, dstBytes, submit);
+}
+
+// A destination whose element holds several texels (FC_GROUP) is written in two steps: the operation leaves R32G32B32A32_FLOAT rows in
+// ctx->groupRows (what the reference hands to StoreScanline), launch_pack_group stores them. The stream orders the steps, so one
+// buffer serves every level of a chain. launch(out) queues the operation's kernels with `out` as their destination: dst itself, or the
+// float rows; `marks` is what the operation's own launcher records into.
+bool is_group_format(int format) { const FmtInfo* f = format_info(format); return f && (f->cls & FC_GROUP); }
+template<class Launch>
+dxtex_hresult launch_into(dxtex_ctx* ctx, const ImgView& dst, KernelMarks* marks, Launch&& launch)
+{
+    if (!is_group_format(dst.format)) return launched(ctx, launch(dst));
+    ImgView rows = { nullptr, uint64_t(dst.width) * 16, dst.width, dst.height, FMT_R32G32B32A32_FLOAT };
+    const dxtex_hresult hr = ctx->groupRows.grow(ctx, rows.rowPitch * dst.height);
+    if (hr != DXTEX_S_OK) return hr;
+    rows.pixels = ctx->groupRows.u8();
+    hipError_t e = launch(rows);
+    if (e == hipSuccess) e = launch_pack_group(rows, dst, ctx->stream, marks);
+    return launched(ctx, e);
+}
+
+struct LevelPair { ImgView src, dst; };
+LevelPair pair_of(const dxtex_image& s, const dxtex_image& d) { return { view_of(s), view_of(d) }; }
 // the (level i - 1 -> level i) pairs of a mip chain
 std::vector<LevelPair> mip_pairs(const dxtex_image* levels, size_t nlevels)
 {
@@ -561,13 +609,12 @@ dxtex_hresult dxtex_compress_many_device(dxtex_ctx* ctx, const dxtex_image* srcs
         }
         const dxtex_hresult hr = grow_scratch(ctx, dsts[0].format, nblocks, flags, count);
         if (hr != DXTEX_S_OK) return hr;
-        KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
+        KernelMarks* marks = marks_of(ctx);
         time_begin(ctx);
         const hipError_t e = allBc7 ? launch_bc7_encode_many(batch.data(), count, flags, ctx->scratch.p, ctx->stream, marks, side_streams(ctx))
                                     : launch_bc6h_encode_many(batch.data(), count, dsts[0].format == FMT_BC6H_SF16, ctx->scratch.p, ctx->stream, marks, side_streams(ctx));
         time_end(ctx);
-        if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-        return DXTEX_S_OK;
+        return launched(ctx, e);
     }
     time_begin(ctx);
     // BC1-BC5: runs of small images of one target format (the tail of a mip chain) share a launch; everything else goes image by image
@@ -578,7 +625,7 @@ dxtex_hresult dxtex_compress_many_device(dxtex_ctx* ctx, const dxtex_image* srcs
         if (small.empty()) return DXTEX_S_OK;
         const hipError_t e = launch_bc15_encode_small(small.data(), int(small.size()), smallFormat, flags, threshold, ctx->stream);
         small.clear();
-        return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        return launched(ctx, e);
     };
     for (size_t i = 0; i < count; ++i)
     {
@@ -770,10 +817,7 @@ dxtex_hresult dxtex_compress(dxtex_ctx* ctx, const dxtex_image* src, const dxtex
     dxtex_hresult hr = check_pair(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
     { SrcView v; hr = compress_view(ctx, *src, dst->format, flags, &v); if (hr != DXTEX_S_OK) return hr; }
-    size_t srcBytes = 0, dstBytes = 0;
-    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      { return submit_compress(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags, threshold); });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_compress(ctx, s, d, flags, threshold); });
 }
 
 dxtex_hresult dxtex_encode_blocks(dxtex_ctx* ctx, int32_t bc_format, uint32_t bc_flags, float threshold,
@@ -803,10 +847,7 @@ static dxtex_hresult submit_decompress(dxtex_ctx* ctx, const dxtex_image& src, c
     if (out && (out->cls & FC_BC)) return fail(ctx, DXTEX_E_INVALIDARG, "destination format is block compressed");
     if (!out || (out->cls & FC_GROUP)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "destination format is not supported by the MI355X path");
     if (!src.width || !src.height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
-    const ConvertPlan plan = resolve_convert_plan(*in, *out, 0);
-    hipError_t e = launch_bc_decode(src.pixels, src.rowPitch, src.format, dst.pixels, dst.rowPitch, dst.format, uint32_t(src.width), uint32_t(src.height), plan, ctx->stream);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-    return DXTEX_S_OK;
+    return launched(ctx, launch_bc_decode(view_of(src), view_of(dst), resolve_convert_plan(*in, *out, 0), ctx->stream));
 }
 
 dxtex_hresult dxtex_decompress_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
@@ -820,11 +861,10 @@ dxtex_hresult dxtex_decompress(dxtex_ctx* ctx, const dxtex_image* src, const dxt
 {
     dxtex_hresult hr = check_pair(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    size_t srcBytes = 0, dstBytes = 0;
-    if (format_info(src->format) && format_info(dst->format)) { hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr; }
-    else { srcBytes = src->rowPitch * std::max<size_t>(1, (src->height + 3) / 4); dstBytes = dst->rowPitch * dst->height; }      // submit_decompress rejects the formats below
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      { return submit_decompress(ctx, with_pixels(*src, in), with_pixels(*dst, out)); });
+    const auto submit = [&](const dxtex_image& s, const dxtex_image& d) { return submit_decompress(ctx, s, d); };
+    if (format_info(src->format) && format_info(dst->format)) return run_host_twin(ctx, src, dst, submit);
+    // a format without a minimum pitch to check: staged as its pitches say, and submit_decompress rejects it
+    return run_staged_images(ctx, src, src->rowPitch * std::max<size_t>(1, (src->height + 3) / 4), dst, dst->rowPitch * dst->height, submit);
 }
 
 dxtex_hresult dxtex_decode_blocks(dxtex_ctx* ctx, int32_t bc_format, const uint8_t* bc, size_t nblocks, float* rgba)
@@ -838,8 +878,8 @@ dxtex_hresult dxtex_decode_blocks(dxtex_ctx* ctx, int32_t bc_format, const uint8
     return run_staged(ctx, bc, nblocks * bb, rgba, nblocks * 256, [&](uint8_t* in, uint8_t* out)
     {
         ConvertPlan plan; plan.srgbIn = 0; plan.tcv = TCV_NONE; plan.tsw = TSW_NONE; plan.srgbOut = 0; plan.depth = 0;
-        const hipError_t e = launch_bc_decode(in, bb, bc_format, out, 64, FMT_R32G32B32A32_FLOAT, 4, uint32_t(nblocks * 4), plan, ctx->stream);
-        return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        const uint32_t rows = uint32_t(nblocks * 4);
+        return launched(ctx, launch_bc_decode({ in, bb, 4, rows, bc_format }, { out, 64, 4, rows, FMT_R32G32B32A32_FLOAT }, plan, ctx->stream));
     });
 }
 // ---- GenerateMipMaps / Resize / Convert ----------------------------------------------------------------------------------
@@ -880,32 +920,13 @@ dxtex_hresult upload_tables(dxtex_ctx* ctx)
     return DXTEX_S_OK;
 }
 
-// A destination whose element holds several texels (FC_GROUP) is written in two steps: the operation leaves R32G32B32A32_FLOAT rows in
-// ctx->groupRows (what the reference hands to StoreScanline), launch_pack_group stores them. The stream orders the steps, so one
-// buffer serves every level of a chain.
-bool is_group_format(int format) { const FmtInfo* f = format_info(format); return f && (f->cls & FC_GROUP); }
-dxtex_hresult group_rows(dxtex_ctx* ctx, size_t width, size_t height, uint8_t** rows, size_t* pitch)
-{
-    *pitch = width * 16;
-    const dxtex_hresult hr = ctx->groupRows.grow(ctx, *pitch * height);
-    *rows = ctx->groupRows.u8();
-    return hr;
-}
-
 // Builds the triangle tables of every (src -> dst) pair into one device buffer, then launches the filter per pair.
-dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs, int format, uint32_t mode, uint32_t flags, bool mipAlias)
+dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs, uint32_t mode, uint32_t flags, bool mipAlias)
 {
-    const bool grouped = is_group_format(format);
-    KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
-    // one resize: straight into the destination, or through float rows and the pack kernel
-    auto resize_one = [&](const LevelPair& p, const TriangleTables* t, const uint8_t* staleSrc, uint64_t stalePitch, uint32_t staleW) -> dxtex_hresult
+    KernelMarks* marks = marks_of(ctx);
+    auto resize_one = [&](const LevelPair& p, const TriangleTables* t, const ImgView* stale)
     {
-        uint8_t* out = p.dst; size_t outPitch = p.dstPitch;
-        if (grouped) { const dxtex_hresult hr = group_rows(ctx, p.dw, p.dh, &out, &outPitch); if (hr != DXTEX_S_OK) return hr; }
-        hipError_t e = launch_resize(p.src, p.srcPitch, uint32_t(p.sw), uint32_t(p.sh), out, outPitch, uint32_t(p.dw), uint32_t(p.dh),
-                                     format, mode, flags, mipAlias, t, ctx->stream, staleSrc, stalePitch, staleW, grouped ? FMT_R32G32B32A32_FLOAT : -1, marks);
-        if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, p.dst, p.dstPitch, format, uint32_t(p.dw), uint32_t(p.dh), ctx->stream, marks);
-        return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        return launch_into(ctx, p.dst, marks, [&](const ImgView& out) { return launch_resize(p.src, out, mode, flags, mipAlias, t, ctx->stream, stale, marks); });
     };
     if (mode == DXTEX_FILTER_TRIANGLE)
     {
@@ -913,48 +934,41 @@ dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs
         std::vector<TriAxis> x, y;
         for (const LevelPair& p : pairs)
         {
-            x.push_back(pack_triangle_axis(ctx->triHost, p.sw, p.dw, (flags & DXTEX_FILTER_WRAP_U) != 0));
-            y.push_back(pack_triangle_axis(ctx->triHost, p.sh, p.dh, (flags & DXTEX_FILTER_WRAP_V) != 0));
+            x.push_back(pack_triangle_axis(ctx->triHost, p.src.width, p.dst.width, (flags & DXTEX_FILTER_WRAP_U) != 0));
+            y.push_back(pack_triangle_axis(ctx->triHost, p.src.height, p.dst.height, (flags & DXTEX_FILTER_WRAP_V) != 0));
         }
         dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
         const uint8_t* d = ctx->triBuf.u8();
         for (size_t i = 0; i < pairs.size(); ++i)
         {
             const TriangleTables t = { tri_ofs(d, x[i]), d + x[i].ent, tri_ofs(d, y[i]), d + y[i].ent };
-            const dxtex_hresult hr1 = resize_one(pairs[i], &t, nullptr, 0, 0);
+            const dxtex_hresult hr1 = resize_one(pairs[i], &t, nullptr);
             if (hr1 != DXTEX_S_OK) return hr1;
         }
         return DXTEX_S_OK;
     }
-    const LevelPair* twoHigh = nullptr;      // box mips: the last source level that was 2 texels high (resize_box_kernel's stale tap)
+    const ImgView* twoHigh = nullptr;      // box mips: the last source level that was 2 texels high (resize_box_kernel's stale tap)
     for (size_t i = 0; i < pairs.size(); ++i)
     {
         const LevelPair& p = pairs[i];
         // a mip chain's last levels (source at most 64 x 64, each level the next one's source) run in one workgroup
-        const bool cubicTail = mode == DXTEX_FILTER_CUBIC && p.sw <= 64 && p.sh <= 64;
-        if (mipAlias && !grouped && pairs.size() - i >= 2 && (cubicTail || resize_tail_applies(uint32_t(p.sw), uint32_t(p.sh), mode)))
+        const bool cubicTail = mode == DXTEX_FILTER_CUBIC && p.src.width <= 64 && p.src.height <= 64;
+        if (mipAlias && !is_group_format(p.dst.format) && pairs.size() - i >= 2 && (cubicTail || resize_tail_applies(p.src.width, p.src.height, mode)))
         {
             bool chain = true;
-            for (size_t k = i + 1; k < pairs.size(); ++k) chain = chain && pairs[k].src == pairs[k - 1].dst && pairs[k].srcPitch == pairs[k - 1].dstPitch;
-            std::vector<MipLevel> lv;
+            for (size_t k = i + 1; k < pairs.size(); ++k) chain = chain && pairs[k].src.pixels == pairs[k - 1].dst.pixels && pairs[k].src.rowPitch == pairs[k - 1].dst.rowPitch;
+            std::vector<ImgView> lv;
             if (chain)
             {
-                lv.push_back({ const_cast<uint8_t*>(p.src), p.srcPitch, uint32_t(p.sw), uint32_t(p.sh) });
-                for (size_t k = i; k < pairs.size(); ++k) lv.push_back({ pairs[k].dst, pairs[k].dstPitch, uint32_t(pairs[k].dw), uint32_t(pairs[k].dh) });
-                if (cubicTail) chain = resize_cubic_tail_applies(lv.data(), int(lv.size()), format, flags);
+                lv.push_back(p.src);
+                for (size_t k = i; k < pairs.size(); ++k) lv.push_back(pairs[k].dst);
+                if (cubicTail) chain = resize_cubic_tail_applies(lv.data(), int(lv.size()), flags);
             }
-            if (chain)
-            {
-                MipLevel th = { nullptr, 0, 0, 0 };
-                if (twoHigh) th = { const_cast<uint8_t*>(twoHigh->src), twoHigh->srcPitch, uint32_t(twoHigh->sw), uint32_t(twoHigh->sh) };
-                const hipError_t e = launch_resize_tail(lv.data(), int(lv.size()), format, mode, flags, twoHigh ? &th : nullptr, ctx->stream, marks);
-                if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
-                return DXTEX_S_OK;
-            }
+            if (chain) return launched(ctx, launch_resize_tail(lv.data(), int(lv.size()), mode, flags, twoHigh, ctx->stream, marks));
         }
-        if (mipAlias && p.sh >= 2) twoHigh = &p;
-        const bool stale = mipAlias && mode == DXTEX_FILTER_BOX && p.sh == 1 && p.sw > 1 && twoHigh;
-        const dxtex_hresult hr1 = resize_one(p, nullptr, stale ? twoHigh->src : nullptr, stale ? twoHigh->srcPitch : 0, stale ? uint32_t(twoHigh->sw) : 0u);
+        if (mipAlias && p.src.height >= 2) twoHigh = &p.src;
+        const bool stale = mipAlias && mode == DXTEX_FILTER_BOX && p.src.height == 1 && p.src.width > 1 && twoHigh;
+        const dxtex_hresult hr1 = resize_one(p, nullptr, stale ? twoHigh : nullptr);
         if (hr1 != DXTEX_S_OK) return hr1;
     }
     return DXTEX_S_OK;
@@ -994,7 +1008,7 @@ dxtex_hresult dxtex_generate_mips_device(dxtex_ctx* ctx, const dxtex_image* leve
     uint32_t mode = 0;
     dxtex_hresult hr = check_mips(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(levels, nlevels), levels[0].format, mode, filter, true); });
+    return run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(levels, nlevels), mode, filter, true); });
 }
 
 dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, size_t nlevels, uint32_t filter)
@@ -1010,7 +1024,7 @@ dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, siz
     hr = ctx->stageIn.grow(ctx, a.total); if (hr != DXTEX_S_OK) return hr;
     const std::vector<dxtex_image> d = in_arena(levels, nlevels, ctx->stageIn.u8(), a);
     HIP_TRY(ctx, counted_copy(ctx, d[0].pixels, levels[0].pixels, bytes[0], hipMemcpyHostToDevice, ctx->stream));
-    hr = run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(d.data(), nlevels), levels[0].format, mode, filter, true); });
+    hr = run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(d.data(), nlevels), mode, filter, true); });
     if (hr != DXTEX_S_OK) return hr;
     for (size_t i = 1; i < nlevels; ++i)
         HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, d[i].pixels, bytes[i], hipMemcpyDeviceToHost, ctx->stream));
@@ -1049,11 +1063,16 @@ dxtex_hresult check_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nl
     return DXTEX_S_OK;
 }
 
+// slice z of a volume level as a 2-D surface
+ImgView slice_of(const VolumeView& v, uint32_t z)
+{
+    return ImgView{ const_cast<uint8_t*>(v.pixels) + uint64_t(z) * v.slicePitch, v.rowPitch, v.width, v.height, v.format };
+}
+
 // The level loop of Generate3DMips*Filter on device-resident levels: 3-D kernels while the source is more than one slice deep,
 // then the reference's 2-D branches (the kernels GenerateMipMaps uses) - except the triangle filter, which has no 2-D branch.
 dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, uint32_t mode, uint32_t flags)
 {
-    const int format = lv[0].format;
     std::vector<TriAxis> x(lv.size()), y(lv.size()), z(lv.size());      // [i]: level i - 1 -> level i
     const uint8_t* tri = nullptr;
     if (mode == DXTEX_FILTER_TRIANGLE)
@@ -1075,19 +1094,19 @@ dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, u
         if (s.height >= 2) twoHigh = &s;
         // row 1 of the last slice pair loaded into urow1 / vrow1 at that level: slices depth-2 and depth-1 (a one-slice level only has urow1)
         const bool stale = mode == DXTEX_FILTER_BOX && s.height == 1 && s.width > 1 && twoHigh;
-        const uint8_t* staleU = stale ? twoHigh->pixels + uint64_t(twoHigh->depth >= 2 ? twoHigh->depth - 2 : 0) * twoHigh->slicePitch : nullptr;
-        const uint8_t* staleV = stale ? twoHigh->pixels + uint64_t(twoHigh->depth - 1) * twoHigh->slicePitch : nullptr;
+        ImgView staleU{}, staleV{};
+        if (stale) { staleU = slice_of(*twoHigh, twoHigh->depth >= 2 ? twoHigh->depth - 2 : 0); staleV = slice_of(*twoHigh, twoHigh->depth - 1); }
         hipError_t e;
         if (s.depth > 1 || mode == DXTEX_FILTER_TRIANGLE)
         {
             TriangleTables3 t{};
             if (tri) t = { tri_ofs(tri, x[i]), tri + x[i].ent, tri_ofs(tri, y[i]), tri + y[i].ent, tri_ofs(tri, z[i]), tri + z[i].ent };
-            e = launch_resize3d(s, d, mode, flags, tri ? &t : nullptr, ctx->stream, staleU, staleV, stale ? twoHigh->rowPitch : 0, stale ? twoHigh->width : 0u);
+            e = launch_resize3d(s, d, mode, flags, tri ? &t : nullptr, ctx->stream, stale ? &staleU : nullptr, stale ? &staleV : nullptr);
         }
         else
-            e = launch_resize(s.pixels, s.rowPitch, s.width, s.height, const_cast<uint8_t*>(d.pixels), d.rowPitch, d.width, d.height, format, mode, flags, true,
-                              nullptr, ctx->stream, staleU, stale ? twoHigh->rowPitch : 0, stale ? twoHigh->width : 0u);
-        if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+            e = launch_resize(slice_of(s, 0), slice_of(d, 0), mode, flags, true, nullptr, ctx->stream, stale ? &staleU : nullptr);
+        const dxtex_hresult hr = launched(ctx, e);
+        if (hr != DXTEX_S_OK) return hr;
     }
     return DXTEX_S_OK;
 }
@@ -1158,7 +1177,7 @@ dxtex_hresult check_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_i
 
 dxtex_hresult submit_resize(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t mode, uint32_t filter)
 {
-    return submit_resizes(ctx, { pair_of(src, dst) }, src.format, mode, filter, false);
+    return submit_resizes(ctx, { pair_of(src, dst) }, mode, filter, false);
 }
 } // namespace
 
@@ -1175,10 +1194,7 @@ dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_i
     uint32_t mode = 0;
     dxtex_hresult hr = check_resize(ctx, src, dst, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    size_t srcBytes = 0, dstBytes = 0;
-    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      { return submit_resize(ctx, with_pixels(*src, in), with_pixels(*dst, out), mode, filter); });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_resize(ctx, s, d, mode, filter); });
 }
 
 namespace
@@ -1207,7 +1223,7 @@ static const uint32_t kDitherSegment = dev_env("DXTEX_DITHER_SEGMENT") ? uint32_
 dxtex_hresult submit_convert(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, const ConvertPlan& basePlan, float threshold,
                              uint32_t filter, uint32_t z)
 {
-    const size_t width = src.width, height = src.height;
+    const ImgView sv = view_of(src);
     int dither = CONVERT_DITHER_NONE;
     ConvertPlan plan = basePlan;
     if ((filter & (kFilterDitherDiffusion | kFilterDitherOrdered)) && dither_spec(dst.format).valid)
@@ -1220,34 +1236,22 @@ dxtex_hresult submit_convert(dxtex_ctx* ctx, const dxtex_image& src, const dxtex
     {
         if (dither_spec(dst.format).valid)
         {
-            dxtex_hresult hr = ctx->ditherRows.grow(ctx, convert_diffuse_scratch_bytes(uint32_t(width)));
+            dxtex_hresult hr = ctx->ditherRows.grow(ctx, convert_diffuse_scratch_bytes(sv.width));
             if (hr != DXTEX_S_OK) return hr;
             if (!ctx->ditherRerun.p)
             {
                 hr = ctx->ditherRerun.grow(ctx, sizeof(unsigned long long), sizeof(unsigned long long)); if (hr != DXTEX_S_OK) return hr;
                 HIP_TRY(ctx, hipMemsetAsync(ctx->ditherRerun.p, 0, sizeof(unsigned long long), ctx->stream));
             }
-            ctx->ditherTexels += uint64_t(width) * height;
-            const hipError_t e = launch_convert_diffuse(src.pixels, src.rowPitch, src.format, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), plan, threshold,
-                                                        ctx->ditherRows.p, static_cast<unsigned long long*>(ctx->ditherRerun.p), kDitherSegment, ctx->stream);
-            return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+            ctx->ditherTexels += uint64_t(src.width) * src.height;
+            return launched(ctx, launch_convert_diffuse(sv, view_of(dst), plan, threshold, ctx->ditherRows.p, static_cast<unsigned long long*>(ctx->ditherRerun.p),
+                                                        kDitherSegment, ctx->stream));
         }
         dither = CONVERT_DITHER_ZERO_ERROR;      // no dithered store: StoreScanline after the zero error row
     }
     else if (filter & kFilterDitherOrdered) dither = CONVERT_DITHER_ORDERED;
-    uint8_t* out = dst.pixels; size_t outPitch = dst.rowPitch; int outFormat = dst.format;
-    const bool grouped = is_group_format(dst.format);
-    if (grouped)
-    {
-        const dxtex_hresult hr = group_rows(ctx, width, height, &out, &outPitch);
-        if (hr != DXTEX_S_OK) return hr;
-        outFormat = FMT_R32G32B32A32_FLOAT;
-    }
-    KernelMarks* marks = ctx->profiling ? &ctx->marks : nullptr;
-    hipError_t e = launch_convert(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), plan, threshold, ctx->stream,
-                                  dither, z, marks);
-    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream, marks);
-    return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    KernelMarks* marks = marks_of(ctx);
+    return launch_into(ctx, view_of(dst), marks, [&](const ImgView& out) { return launch_convert(sv, out, plan, threshold, ctx->stream, dither, z, marks); });
 }
 } // namespace
 
@@ -1288,10 +1292,7 @@ dxtex_hresult dxtex_convert_slice(dxtex_ctx* ctx, const dxtex_image* src, const 
     ConvertPlan plan;
     dxtex_hresult hr = check_convert(ctx, src, dst, filter, &plan);
     if (hr != DXTEX_S_OK) return hr;
-    size_t srcBytes = 0, dstBytes = 0;
-    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      { return submit_convert(ctx, with_pixels(*src, in), with_pixels(*dst, out), plan, threshold, filter, z); });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_convert(ctx, s, d, plan, threshold, filter, z); });
 }
 
 namespace
@@ -1336,19 +1337,8 @@ dxtex_hresult check_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxt
 // the normal-map kernel, through float rows + the pack kernel when the destination's element holds several texels
 dxtex_hresult submit_normal_map(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags, float amplitude, bool unorm)
 {
-    const size_t width = src.width, height = src.height;
-    uint8_t* out = dst.pixels; size_t outPitch = dst.rowPitch; int outFormat = dst.format;
-    const bool grouped = is_group_format(dst.format);
-    if (grouped)
-    {
-        const dxtex_hresult hr = group_rows(ctx, width, height, &out, &outPitch);
-        if (hr != DXTEX_S_OK) return hr;
-        outFormat = FMT_R32G32B32A32_FLOAT;
-    }
-    hipError_t e = launch_normal_map(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), flags, amplitude,
-                                     unorm, ctx->stream);
-    if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream);
-    return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    // (launch_normal_map records no kernel names, and so neither does the pack that follows it)
+    return launch_into(ctx, view_of(dst), nullptr, [&](const ImgView& out) { return launch_normal_map(view_of(src), out, flags, amplitude, unorm, ctx->stream); });
 }
 } // namespace
 
@@ -1365,10 +1355,7 @@ dxtex_hresult dxtex_compute_normal_map(dxtex_ctx* ctx, const dxtex_image* src, c
     bool unorm = false;
     dxtex_hresult hr = check_normal_map(ctx, src, dst, flags, &unorm);
     if (hr != DXTEX_S_OK) return hr;
-    size_t srcBytes = 0, dstBytes = 0;
-    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      { return submit_normal_map(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags, amplitude, unorm); });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_normal_map(ctx, s, d, flags, amplitude, unorm); });
 }
 
 namespace
@@ -1413,38 +1400,25 @@ dxtex_hresult check_transform(dxtex_ctx* ctx, const dxtex_image* srcs, const dxt
 // destination is written, and the apply kernels read it there
 dxtex_hresult submit_transform(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t op, const XformArgs& args)
 {
-    Marks* marks = ctx->profiling ? &ctx->marks : nullptr;
+    KernelMarks* marks = marks_of(ctx);
     uint32_t* maxBits = nullptr;
     if (op == DXTEX_TRANSFORM_TONEMAP)
     {
-        const dxtex_hresult hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-        maxBits = static_cast<uint32_t*>(ctx->mseBuf.p);
+        const dxtex_hresult hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+        maxBits = static_cast<uint32_t*>(ctx->resultCell.p);
         HIP_TRY(ctx, hipMemsetAsync(maxBits, 0, sizeof(uint32_t), ctx->stream));
         for (size_t i = 0; i < count; ++i)
         {
-            const dxtex_image& s = srcs[i];
-            const hipError_t e = launch_tonemap_max(s.pixels, s.rowPitch, s.format, uint32_t(s.width), uint32_t(s.height), maxBits, ctx->stream, marks);
-            if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+            const dxtex_hresult hr1 = launched(ctx, launch_tonemap_max(view_of(srcs[i]), maxBits, ctx->stream, marks));
+            if (hr1 != DXTEX_S_OK) return hr1;
         }
     }
     for (size_t i = 0; i < count; ++i)
     {
-        const dxtex_image& src = srcs[i];
-        const dxtex_image& dst = dsts[i];
-        const size_t width = src.width, height = src.height;
-        if (!width || !height) continue;
-        uint8_t* out = dst.pixels; size_t outPitch = dst.rowPitch; int outFormat = dst.format;
-        const bool grouped = is_group_format(dst.format);
-        if (grouped)
-        {
-            const dxtex_hresult hr = group_rows(ctx, width, height, &out, &outPitch);
-            if (hr != DXTEX_S_OK) return hr;
-            outFormat = FMT_R32G32B32A32_FLOAT;
-        }
-        hipError_t e = launch_transform(src.pixels, src.rowPitch, src.format, out, outPitch, outFormat, uint32_t(width), uint32_t(height), op, args, maxBits,
-                                        ctx->stream, marks);
-        if (e == hipSuccess && grouped) e = launch_pack_group(out, outPitch, dst.pixels, dst.rowPitch, dst.format, uint32_t(width), uint32_t(height), ctx->stream, marks);
-        if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        if (!srcs[i].width || !srcs[i].height) continue;
+        const ImgView sv = view_of(srcs[i]);
+        const dxtex_hresult hr = launch_into(ctx, view_of(dsts[i]), marks, [&](const ImgView& out) { return launch_transform(sv, out, op, args, maxBits, ctx->stream, marks); });
+        if (hr != DXTEX_S_OK) return hr;
     }
     return DXTEX_S_OK;
 }
@@ -1463,13 +1437,7 @@ dxtex_hresult dxtex_transform_image(dxtex_ctx* ctx, const dxtex_image* src, cons
     XformArgs args;
     dxtex_hresult hr = check_transform(ctx, src, dst, src && dst ? 1 : 0, t, &args);
     if (hr != DXTEX_S_OK) return hr;
-    size_t srcBytes = 0, dstBytes = 0;
-    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      {
-                          const dxtex_image s = with_pixels(*src, in), d = with_pixels(*dst, out);
-                          return submit_transform(ctx, &s, &d, 1, t->op, args);
-                      });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_transform(ctx, &s, &d, 1, t->op, args); });
 }
 
 namespace
@@ -1489,19 +1457,17 @@ dxtex_hresult check_pmalpha(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_
 
 dxtex_hresult submit_pmalpha(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags)
 {
-    const hipError_t e = launch_pmalpha(src.pixels, src.rowPitch, dst.pixels, dst.rowPitch, src.format, uint32_t(src.width), uint32_t(src.height), flags, ctx->stream);
-    return e == hipSuccess ? DXTEX_S_OK : fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    return launched(ctx, launch_pmalpha(view_of(src), view_of(dst), flags, ctx->stream));
 }
 
 // EstimateAlphaScaleForCoverage (DirectXTexMipmaps.cpp:310-352) around the device coverage count
 dxtex_hresult alpha_coverage(dxtex_ctx* ctx, const dxtex_image& im, float scale, float alphaReference, float* coverage)
 {
-    dxtex_hresult hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-    hipError_t e = launch_alpha_coverage(im.pixels, im.rowPitch, im.format, uint32_t(im.width), uint32_t(im.height), scale, alphaReference,
-                                         static_cast<unsigned long long*>(ctx->mseBuf.p), ctx->stream);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    dxtex_hresult hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    hr = launched(ctx, launch_alpha_coverage(view_of(im), scale, alphaReference, static_cast<unsigned long long*>(ctx->resultCell.p), ctx->stream));
+    if (hr != DXTEX_S_OK) return hr;
     unsigned long long n = 0;
-    HIP_TRY(ctx, counted_copy(ctx, &n, ctx->mseBuf.p, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, counted_copy(ctx, &n, ctx->resultCell.p, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const float cscale = static_cast<float>((im.width - 1) * (im.height - 1) * 8 * 8);      // :299-303
     *coverage = (cscale > 0.f) ? static_cast<float>(size_t(n)) / cscale : 0.0f;
@@ -1547,9 +1513,8 @@ dxtex_hresult submit_coverage_chain(dxtex_ctx* ctx, const dxtex_image* src, cons
             else break;
             scale = (lo + hi) * 0.5f;
         }
-        hipError_t e = launch_scale_alpha(src[level].pixels, src[level].rowPitch, dst[level].pixels, dst[level].rowPitch, src[level].format, uint32_t(src[level].width),
-                                          uint32_t(src[level].height), scale, ctx->stream);
-        if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+        hr = launched(ctx, launch_scale_alpha(view_of(src[level]), view_of(dst[level]), scale, ctx->stream));
+        if (hr != DXTEX_S_OK) return hr;
     }
     return DXTEX_S_OK;
 }
@@ -1566,10 +1531,7 @@ dxtex_hresult dxtex_premultiply_alpha(dxtex_ctx* ctx, const dxtex_image* src, co
 {
     dxtex_hresult hr = check_pmalpha(ctx, src, dst);
     if (hr != DXTEX_S_OK) return hr;
-    size_t srcBytes = 0, dstBytes = 0;
-    hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes); if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, srcBytes, dst->pixels, dstBytes, [&](uint8_t* in, uint8_t* out)
-                      { return submit_pmalpha(ctx, with_pixels(*src, in), with_pixels(*dst, out), flags); });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_pmalpha(ctx, s, d, flags); });
 }
 
 dxtex_hresult dxtex_scale_mips_alpha_for_coverage_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, size_t nlevels, float alphaReference)
@@ -1611,12 +1573,11 @@ dxtex_hresult dxtex_compute_mse_device(dxtex_ctx* ctx, const dxtex_image* a, con
     const FmtInfo* fb = format_info(b->format);
     if (!fa || !fb || (fa->cls & FC_BC) || (fb->cls & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "ComputeMSE takes uncompressed images (decompress first)");
     ScopedDevice sd(ctx->device);
-    hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-    hipError_t e = launch_mse(a->pixels, a->rowPitch, a->format, b->pixels, b->rowPitch, b->format, uint32_t(a->width), uint32_t(a->height),
-                              static_cast<double*>(ctx->mseBuf.p), ctx->stream, ctx->profiling ? &ctx->marks : nullptr);
-    if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+    hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    hr = launched(ctx, launch_mse(view_of(*a), view_of(*b), static_cast<double*>(ctx->resultCell.p), ctx->stream, marks_of(ctx)));
+    if (hr != DXTEX_S_OK) return hr;
     double sum[4];
-    HIP_TRY(ctx, counted_copy(ctx, sum, ctx->mseBuf.p, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, counted_copy(ctx, sum, ctx->resultCell.p, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const double n = double(a->width) * double(a->height);
     for (int c = 0; c < 4; ++c) mse[c] = sum[c] / n;
@@ -1714,8 +1675,8 @@ dxtex_hresult dxtex_alpha_all_opaque_device(dxtex_ctx* ctx, const dxtex_image* i
     const bool bc = (f->cls & FC_BC) != 0;
     if (!(f->cls & FC_A) || is_bc6h(f->format)) { *opaque = 1; return DXTEX_S_OK; }
     ScopedDevice sd(ctx->device);
-    dxtex_hresult hr = ctx->mseBuf.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-    unsigned long long* counter = static_cast<unsigned long long*>(ctx->mseBuf.p);
+    dxtex_hresult hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    unsigned long long* counter = static_cast<unsigned long long*>(ctx->resultCell.p);
     HIP_TRY(ctx, hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
     for (size_t i = 0; i < count; ++i)
     {
@@ -1729,13 +1690,15 @@ dxtex_hresult dxtex_alpha_all_opaque_device(dxtex_ctx* ctx, const dxtex_image* i
             // IsAlphaAllOpaqueBC decodes every block to floats and tests the texels inside the image against 0.99
             const size_t pitch = im.width * 16;
             hr = ctx->stageOut.grow(ctx, pitch * im.height); if (hr != DXTEX_S_OK) return hr;
-            hr = submit_decompress(ctx, im, { im.width, im.height, FMT_R32G32B32A32_FLOAT, pitch, pitch * im.height, ctx->stageOut.u8() });
+            const dxtex_image decoded = { im.width, im.height, FMT_R32G32B32A32_FLOAT, pitch, pitch * im.height, ctx->stageOut.u8() };
+            hr = submit_decompress(ctx, im, decoded);
             if (hr != DXTEX_S_OK) return hr;
-            e = launch_alpha_below(ctx->stageOut.u8(), pitch, FMT_R32G32B32A32_FLOAT, uint32_t(im.width), uint32_t(im.height), 0.99f, counter, ctx->stream);
+            e = launch_alpha_below(view_of(decoded), 0.99f, counter, ctx->stream);
         }
         else
-            e = launch_alpha_below(im.pixels, im.rowPitch, im.format, uint32_t(im.width), uint32_t(im.height), 0.997f, counter, ctx->stream);
-        if (e != hipSuccess) return fail(ctx, DXTEX_E_FAIL, "kernel launch failed", e);
+            e = launch_alpha_below(view_of(im), 0.997f, counter, ctx->stream);
+        hr = launched(ctx, e);
+        if (hr != DXTEX_S_OK) return hr;
     }
     unsigned long long n = 0;
     HIP_TRY(ctx, counted_copy(ctx, &n, counter, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
@@ -1902,9 +1865,10 @@ dxtex_hresult dxtex_generate_mips_multi(dxtex_ctx* const* ctxs, size_t nctx, con
             for (size_t l = 1; l <= L; ++l)
             {
                 const size_t s0 = 2 * E[l].a;         // first row of the source sub-image, inside [E[l - 1].a, E[l - 1].b)
-                std::vector<LevelPair> pairs{ { arena + a.at[l - 1] + (s0 - E[l - 1].a) * levels[l - 1].rowPitch, levels[l - 1].rowPitch, levels[l - 1].width, 2 * (E[l].b - E[l].a),
-                                                arena + a.at[l], levels[l].rowPitch, levels[l].width, E[l].b - E[l].a } };
-                h = submit_resizes(ctx, pairs, levels[0].format, mode, explicitFilter, false);
+                dxtex_image s = levels[l - 1], d = levels[l];
+                s.pixels = arena + a.at[l - 1] + (s0 - E[l - 1].a) * levels[l - 1].rowPitch; s.height = 2 * (E[l].b - E[l].a);
+                d.pixels = arena + a.at[l]; d.height = E[l].b - E[l].a;
+                h = submit_resizes(ctx, { pair_of(s, d) }, mode, explicitFilter, false);
                 if (h != DXTEX_S_OK) { time_end(ctx); return h; }
             }
             time_end(ctx);

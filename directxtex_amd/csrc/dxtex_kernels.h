@@ -43,88 +43,86 @@ hipError_t launch_bc6h_encode(const SrcView& src, uint8_t* dst, uint64_t dstRowP
 hipError_t launch_bc6h_encode_many(const BcImage* images, size_t count, bool isSigned, void* scratch, hipStream_t stream, KernelMarks* marks,
                                    const SideStreams* side = nullptr);
 
-// BC -> uncompressed (DecompressBC). `plan` = resolve_convert_plan(bc format, target format, TEX_FILTER_DEFAULT).
-struct ConvertPlan;
-hipError_t launch_bc_decode(const uint8_t* src, uint64_t srcRowPitch, int srcFormat, uint8_t* dst, uint64_t dstRowPitch, int dstFormat,
-                            uint32_t width, uint32_t height, const ConvertPlan& plan, hipStream_t stream);
+// The one host-and-device description of a 2-D surface: `height` rows of `width` texels of `format`, `rowPitch` bytes apart. Every scanline
+// launcher and the BC decoder take their surfaces as views (for a BC surface width and height count texels too), and the scanline kernels
+// receive them as they are. A source is only read through its view.
+struct ImgView
+{
+    uint8_t* pixels;
+    uint64_t rowPitch;
+    uint32_t width, height;
+    int format;
+};
 
-// Convert (ConvertCustom): same size, different format. dither = CONVERT_DITHER_*: ORDERED applies StoreScanlineDither's ordered branch
-// (rows counted from the top of the given image, slice z); ZERO_ERROR adds the zero error row of the diffusion branch before a store
-// that does not dither (the formats dither_spec() marks invalid).
+// BC -> uncompressed (DecompressBC). `plan` = resolve_convert_plan(bc format, target format, TEX_FILTER_DEFAULT). The size is dst's.
+struct ConvertPlan;
+hipError_t launch_bc_decode(const ImgView& src, const ImgView& dst, const ConvertPlan& plan, hipStream_t stream);
+
+// Convert (ConvertCustom): same size (src's; dst matches it), different format. dither = CONVERT_DITHER_*: ORDERED applies
+// StoreScanlineDither's ordered branch (rows counted from the top of the given image, slice z); ZERO_ERROR adds the zero error row of the
+// diffusion branch before a store that does not dither (the formats dither_spec() marks invalid).
 enum : int { CONVERT_DITHER_NONE = 0, CONVERT_DITHER_ORDERED = 1, CONVERT_DITHER_ZERO_ERROR = 2 };
-hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream,
+hipError_t launch_convert(const ImgView& src, const ImgView& dst, const ConvertPlan& plan, float threshold, hipStream_t stream,
                           int dither = CONVERT_DITHER_NONE, uint32_t z = 0, KernelMarks* marks = nullptr);
-// Error-diffusion Convert of one image (a destination format with a dithered store) in one workgroup; `scratch` holds
+// Error-diffusion Convert of one image (a destination format with a dithered store; the size is src's) in one workgroup; `scratch` holds
 // convert_diffuse_scratch_bytes(width) bytes of device memory; the texels the merge re-ran are added to *rerun (device memory).
 // segLen = texels per speculated segment of a row (0: the default).
 size_t convert_diffuse_scratch_bytes(uint32_t width);
-hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                                  uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, void* scratch,
+hipError_t launch_convert_diffuse(const ImgView& src, const ImgView& dst, const ConvertPlan& plan, float threshold, void* scratch,
                                   unsigned long long* rerun, uint32_t segLen, hipStream_t stream);
 
-// ComputeNormalMap of one image: dstFormat's rows receive what the reference hands to StoreScanline (R32G32B32A32_FLOAT rows for
-// launch_pack_group when the destination packs several texels per element); unorm = the destination format is UNORM (its encoding).
-// flags = CNMAP_FLAGS. Source and destination must not overlap.
-hipError_t launch_normal_map(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                             uint32_t width, uint32_t height, uint32_t flags, float amplitude, bool unorm, hipStream_t stream);
+// ComputeNormalMap of one image (the size is src's): dst's rows receive what the reference hands to StoreScanline (R32G32B32A32_FLOAT
+// rows for launch_pack_group when the destination packs several texels per element); unorm = the destination format is UNORM (its
+// encoding). flags = CNMAP_FLAGS. Source and destination must not overlap.
+hipError_t launch_normal_map(const ImgView& src, const ImgView& dst, uint32_t flags, float amplitude, bool unorm, hipStream_t stream);
 
-// TransformImage of one image with one of texconv's per-texel ops (op = XFORM_*, args resolved by the caller, see dxtex_transform.h):
-// LoadScanline -> op -> StoreScanline with threshold 0. dstFormat's rows as for launch_normal_map (R32G32B32A32_FLOAT rows for
-// launch_pack_group where the destination packs several texels). XFORM_TONEMAP reads the maximum luminance's bits from maxBits (device
+// TransformImage of one image (the size is src's) with one of texconv's per-texel ops (op = XFORM_*, args resolved by the caller, see
+// dxtex_transform.h): LoadScanline -> op -> StoreScanline with threshold 0. dst's rows as for launch_normal_map (R32G32B32A32_FLOAT rows
+// for launch_pack_group where the destination packs several texels). XFORM_TONEMAP reads the maximum luminance's bits from maxBits (device
 // memory), which launch_tonemap_max folds each image of the set into (the caller zeroes it first).
 struct XformArgs;
-hipError_t launch_transform(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                            uint32_t width, uint32_t height, uint32_t op, const XformArgs& args, const uint32_t* maxBits, hipStream_t stream,
+hipError_t launch_transform(const ImgView& src, const ImgView& dst, uint32_t op, const XformArgs& args, const uint32_t* maxBits, hipStream_t stream,
                             KernelMarks* marks = nullptr);
-hipError_t launch_tonemap_max(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, uint32_t* maxBits, hipStream_t stream,
-                              KernelMarks* marks = nullptr);
+hipError_t launch_tonemap_max(const ImgView& src, uint32_t* maxBits, hipStream_t stream, KernelMarks* marks = nullptr);
 
-// Resize / one mip level. filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
+// Resize / one mip level: src is filtered (as src.format) into dst, whose rows are written in dst.format (R32G32B32A32_FLOAT rows for
+// launch_pack_group, src.format otherwise). filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row
-// ofs[i]..ofs[i+1] indexes (source index, fp32 weight bits) pairs, see triangle_filter.h. `staleLevel` (box mips only):
-// the last level of the chain that was 2 texels high, see resize_box_kernel.
+// ofs[i]..ofs[i+1] indexes (source index, fp32 weight bits) pairs, see triangle_filter.h. `stale` (box mips only): the last level of the
+// chain that was 2 texels high (its row 1 is what is read), see resize_box_kernel.
 struct TriangleTables { const uint32_t* ofsX; const void* entX; const uint32_t* ofsY; const void* entY; };
-hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, uint32_t srcH, uint8_t* dst, uint64_t dstPitch,
-                         uint32_t dstW, uint32_t dstH, int format, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
-                         const TriangleTables* tri, hipStream_t stream,
-                         const uint8_t* staleLevel = nullptr, uint64_t stalePitch = 0, uint32_t staleW = 0, int dstFormat = -1,
-                         KernelMarks* marks = nullptr);
-// dstFormat >= 0: the destination rows are written in that format instead of `format` (R32G32B32A32_FLOAT rows for launch_pack_group).
+hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
+                         const TriangleTables* tri, hipStream_t stream, const ImgView* stale = nullptr, KernelMarks* marks = nullptr);
 
-// Formats whose element holds several texels (FC_GROUP): R32G32B32A32_FLOAT rows -> the format, with StoreScanline's pair / bit packing.
-hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* dst, uint64_t dstPitch, int dstFormat, uint32_t width, uint32_t height, hipStream_t stream,
-                             KernelMarks* marks = nullptr);
+// Formats whose element holds several texels (FC_GROUP): R32G32B32A32_FLOAT rows -> dst's format, with StoreScanline's pair / bit packing.
+// The size is dst's.
+hipError_t launch_pack_group(const ImgView& rows, const ImgView& dst, hipStream_t stream, KernelMarks* marks = nullptr);
 
-// The tail of a 2-D mip chain (levels[0] = the first source level, at most 64 x 64; levels[1..] = the levels generated from it) in one
-// workgroup: point / linear / cubic / box, the arithmetic of launch_resize with mipAlias. twoHigh = the last level of the chain before
-// levels[0] that was at least 2 texels high (the box filter's stale tap, see resize_box_kernel), or nullptr.
-struct MipLevel { uint8_t* pixels; uint64_t pitch; uint32_t width, height; };
+// The tail of a 2-D mip chain (levels[0] = the first source level, at most 64 x 64; levels[1..] = the levels generated from it, all of
+// levels[0]'s format) in one workgroup: point / linear / cubic / box, the arithmetic of launch_resize with mipAlias. twoHigh = the last
+// level of the chain before levels[0] that was at least 2 texels high (the box filter's stale tap, see resize_box_kernel), or nullptr.
 bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode);
 // cubic: only the tail of a power-of-two RGBA8 chain with clamp addressing (every level an exact halving) has a one-workgroup form;
 // levels[] as for launch_resize_tail
-bool resize_cubic_tail_applies(const MipLevel* levels, int nlevels, int format, uint32_t filterFlags);
-hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, uint32_t filterMode, uint32_t filterFlags,
-                              const MipLevel* twoHigh, hipStream_t stream, KernelMarks* marks = nullptr);
+bool resize_cubic_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags);
+hipError_t launch_resize_tail(const ImgView* levels, int nlevels, uint32_t filterMode, uint32_t filterFlags,
+                              const ImgView* twoHigh, hipStream_t stream, KernelMarks* marks = nullptr);
 
 // Volume mips (Generate3DMips*Filter): one level whose source is more than one slice deep. Slices of a level are `slicePitch` apart.
 struct VolumeView { const uint8_t* pixels; uint64_t rowPitch, slicePitch; uint32_t width, height, depth; int format; };
 struct TriangleTables3 { const uint32_t* ofsX; const void* entX; const uint32_t* ofsY; const void* entY; const uint32_t* ofsZ; const void* entZ; };
+// staleU / staleV (box only, both or neither): the slices whose row 1 the reference's never re-pointed urow3 / vrow3 still see, see resize3d_box_kernel.
 hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_t filterMode, uint32_t filterFlags, const TriangleTables3* tri,
-                           hipStream_t stream, const uint8_t* staleU = nullptr, const uint8_t* staleV = nullptr, uint64_t stalePitch = 0, uint32_t staleW = 0);
+                           hipStream_t stream, const ImgView* staleU = nullptr, const ImgView* staleV = nullptr);
 
-// ComputeMSE: out4 (device) receives the per-channel SUM of squared differences; divide by width * height on the host.
-hipError_t launch_mse(const uint8_t* a, uint64_t aPitch, int aFormat, const uint8_t* b, uint64_t bPitch, int bFormat,
-                      uint32_t width, uint32_t height, double* out4, hipStream_t stream, KernelMarks* marks = nullptr);
-// PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205); pmFlags = TEX_PMALPHA_*
-hipError_t launch_pmalpha(const uint8_t* src, uint64_t srcPitch, uint8_t* dst, uint64_t dstPitch, int format, uint32_t width, uint32_t height,
-                          uint32_t pmFlags, hipStream_t stream);
-// ScaleAlpha and CalculateAlphaCoverage (DirectXTexMipmaps.cpp:143-305); *count receives the number of covered sub-samples
-hipError_t launch_scale_alpha(const uint8_t* src, uint64_t srcPitch, uint8_t* dst, uint64_t dstPitch, int format, uint32_t width, uint32_t height,
-                              float scale, hipStream_t stream);
-hipError_t launch_alpha_coverage(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, float scale, float alphaReference,
-                                 unsigned long long* count, hipStream_t stream);
+// ComputeMSE: out4 (device) receives the per-channel SUM of squared differences; divide by width * height (a's; b matches it) on the host.
+hipError_t launch_mse(const ImgView& a, const ImgView& b, double* out4, hipStream_t stream, KernelMarks* marks = nullptr);
+// PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205); pmFlags = TEX_PMALPHA_*. Size and format are src's; dst matches them.
+hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream);
+// ScaleAlpha and CalculateAlphaCoverage (DirectXTexMipmaps.cpp:143-305); *count receives the number of covered sub-samples.
+// launch_scale_alpha: size and format are src's; dst matches them.
+hipError_t launch_scale_alpha(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream);
+hipError_t launch_alpha_coverage(const ImgView& src, float scale, float alphaReference, unsigned long long* count, hipStream_t stream);
 // IsAlphaAllOpaque's scan: *count (device, NOT cleared here) is incremented by the number of texels with alpha < threshold
-hipError_t launch_alpha_below(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, float threshold,
-                              unsigned long long* count, hipStream_t stream);
+hipError_t launch_alpha_below(const ImgView& src, float threshold, unsigned long long* count, hipStream_t stream);
 } // namespace dxtex

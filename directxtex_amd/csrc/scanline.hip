@@ -29,14 +29,6 @@ namespace dxtex
 {
 namespace
 {
-struct ImgView
-{
-    uint8_t* pixels;
-    uint64_t rowPitch;
-    uint32_t width, height;
-    int format;
-};
-
 struct ResizeArgs
 {
     ImgView src, dst;
@@ -1128,11 +1120,8 @@ __global__ void __launch_bounds__(256) mse_kernel(ImgView a, ImgView b, int srgb
         atomicAdd(&out[threadIdx.x], part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
 
-ImgView make_view(const uint8_t* p, uint64_t pitch, uint32_t w, uint32_t h, int fmt)
-{
-    ImgView v; v.pixels = const_cast<uint8_t*>(p); v.rowPitch = pitch; v.width = w; v.height = h; v.format = fmt;
-    return v;
-}
+// the stale tap of a level that has none (the kernels test .pixels)
+ImgView no_stale(int format) { return ImgView{ nullptr, 0, 0, 2, format }; }
 
 bool srgb_linear_format(int format)
 {
@@ -1161,33 +1150,30 @@ bool can_srgb(int format)
 // with a null mark, as the BC encoders do; with marks == nullptr (not profiling) nothing is recorded.
 #define DXTEX_MARK(NAME) do { if (marks) marks->mark(NAME); } while (0)
 
-hipError_t launch_pack_group(const uint8_t* rows, uint64_t rowsPitch, uint8_t* dst, uint64_t dstPitch, int dstFormat, uint32_t width, uint32_t height, hipStream_t stream,
-                             KernelMarks* marks)
+hipError_t launch_pack_group(const ImgView& rows, const ImgView& dst, hipStream_t stream, KernelMarks* marks)
 {
-    if (!width || !height) return hipSuccess;
-    const uint32_t per = group_texels(dstFormat), groups = (width + per - 1) / per;
+    if (!dst.width || !dst.height) return hipSuccess;
+    const uint32_t per = group_texels(dst.format), groups = (dst.width + per - 1) / per;
     DXTEX_MARK("pack_group");
-    hipLaunchKernelGGL(pack_group_kernel, dim3((groups + 255) / 256, grid_rows(height)), dim3(256), 0, stream,
-                       make_view(rows, rowsPitch, width, height, FMT_R32G32B32A32_FLOAT), make_view(dst, dstPitch, width, height, dstFormat));
+    hipLaunchKernelGGL(pack_group_kernel, dim3((groups + 255) / 256, grid_rows(dst.height)), dim3(256), 0, stream, rows, dst);
     DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                          uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, hipStream_t stream, int dither, uint32_t z,
+hipError_t launch_convert(const ImgView& sv, const ImgView& dv, const ConvertPlan& plan, float threshold, hipStream_t stream, int dither, uint32_t z,
                           KernelMarks* marks)
 {
+    const uint32_t width = sv.width, height = sv.height;
     if (!width || !height) return hipSuccess;
-    const FmtInfo* in = format_info(srcFormat);
-    const FmtInfo* out = format_info(dstFormat);
+    const FmtInfo* in = format_info(sv.format);
+    const FmtInfo* out = format_info(dv.format);
     // four texels per lane through 16-byte loads / stores where a texel is a whole number of dwords on both sides and rows are 16-byte aligned
     if (in && out && !((in->cls | out->cls) & FC_GROUP) && in->bpp >= 32 && out->bpp >= 32 && (in->bpp % 32) == 0 && (out->bpp % 32) == 0 && (width % 4u) == 0 &&
-        ((reinterpret_cast<uintptr_t>(src) | srcPitch | reinterpret_cast<uintptr_t>(dst) | dstPitch) & 15u) == 0)
+        ((reinterpret_cast<uintptr_t>(sv.pixels) | sv.rowPitch | reinterpret_cast<uintptr_t>(dv.pixels) | dv.rowPitch) & 15u) == 0)
     {
         const uint32_t quads = width / 4u;
         const uint32_t gx = (quads + 255u) / 256u;
         const uint32_t sq = uint32_t(in->bpp / 8u) * 4u, dq = uint32_t(out->bpp / 8u) * 4u;
-        const ImgView sv = make_view(src, srcPitch, width, height, srcFormat), dv = make_view(dst, dstPitch, width, height, dstFormat);
         // row groups per workgroup column: enough workgroups to fill 256 CUs several times over, few enough that a lane streams several groups
 #define DXTEX_QUAD(SQ, DQ, ROWS) do { const uint32_t groups = (height + (ROWS) - 1u) / (ROWS); \
             const uint32_t gy = std::min<uint32_t>(groups, std::max<uint32_t>(1u, 8192u / gx)); \
@@ -1208,7 +1194,6 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
         DXTEX_MARK(nullptr);
         return hipGetLastError();
     }
-    const ImgView sv = make_view(src, srcPitch, width, height, srcFormat), dv = make_view(dst, dstPitch, width, height, dstFormat);
     const dim3 grid((width + 255) / 256, grid_rows(height));
     if (dither) { DXTEX_MARK("convert<dither>"); hipLaunchKernelGGL(convert_kernel<true>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z); }
     else { DXTEX_MARK("convert"); hipLaunchKernelGGL(convert_kernel<false>, grid, dim3(256), 0, stream, sv, dv, plan, threshold, dither, z); }
@@ -1216,25 +1201,23 @@ hipError_t launch_convert(const uint8_t* src, uint64_t srcPitch, int srcFormat, 
     return hipGetLastError();
 }
 
-hipError_t launch_normal_map(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                             uint32_t width, uint32_t height, uint32_t flags, float amplitude, bool unorm, hipStream_t stream)
+hipError_t launch_normal_map(const ImgView& src, const ImgView& dst, uint32_t flags, float amplitude, bool unorm, hipStream_t stream)
 {
+    const uint32_t width = src.width, height = src.height;
     if (!width || !height) return hipSuccess;
     NmapArgs a;
-    a.src = make_view(src, srcPitch, width, height, srcFormat);
-    a.dst = make_view(dst, dstPitch, width, height, dstFormat);
+    a.src = src; a.dst = dst;
     a.flags = flags; a.amplitude = amplitude; a.unorm = unorm ? 1 : 0;
     a.strips = uint32_t((uint64_t(height) + kNmapRows - 1u) / kNmapRows);
     hipLaunchKernelGGL(nmap_kernel, dim3(uint32_t((uint64_t(width) + kNmapThreads - 1u) / kNmapThreads), grid_rows(a.strips)), dim3(kNmapThreads), 0, stream, a);
     return hipGetLastError();
 }
 
-hipError_t launch_transform(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                            uint32_t width, uint32_t height, uint32_t op, const XformArgs& args, const uint32_t* maxBits, hipStream_t stream,
+hipError_t launch_transform(const ImgView& sv, const ImgView& dv, uint32_t op, const XformArgs& args, const uint32_t* maxBits, hipStream_t stream,
                             KernelMarks* marks)
 {
+    const uint32_t width = sv.width, height = sv.height;
     if (!width || !height) return hipSuccess;
-    const ImgView sv = make_view(src, srcPitch, width, height, srcFormat), dv = make_view(dst, dstPitch, width, height, dstFormat);
     // about 8192 workgroups, as convert_quad launches: a workgroup walks several rows rather than one workgroup being dispatched per row
     const uint32_t gx = (width + 255) / 256;
     const dim3 grid(gx, std::min<uint32_t>(grid_rows(height), std::max<uint32_t>(1u, 8192u / gx)));
@@ -1253,14 +1236,14 @@ hipError_t launch_transform(const uint8_t* src, uint64_t srcPitch, int srcFormat
     return hipGetLastError();
 }
 
-hipError_t launch_tonemap_max(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, uint32_t* maxBits, hipStream_t stream,
-                              KernelMarks* marks)
+hipError_t launch_tonemap_max(const ImgView& src, uint32_t* maxBits, hipStream_t stream, KernelMarks* marks)
 {
+    const uint32_t width = src.width, height = src.height;
     if (!width || !height) return hipSuccess;
     // about 2048 workgroups at most, each looping over its rows: one atomic per workgroup stays far below the cost of the read
     const uint32_t gx = std::min<uint32_t>((width + 255) / 256, 8), gy = std::min<uint32_t>(height, std::max<uint32_t>(1u, 2048u / gx));
     DXTEX_MARK("tonemap_max");
-    hipLaunchKernelGGL(tonemap_max_kernel, dim3(gx, gy), dim3(256), 0, stream, make_view(src, srcPitch, width, height, format), maxBits);
+    hipLaunchKernelGGL(tonemap_max_kernel, dim3(gx, gy), dim3(256), 0, stream, src, maxBits);
     DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
@@ -1270,16 +1253,15 @@ size_t convert_diffuse_scratch_bytes(uint32_t width)
     return size_t(5) * width * sizeof(F4);      // pre, err, slot by texel; in, pending by segment (at most one per texel)
 }
 
-hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int srcFormat, uint8_t* dst, uint64_t dstPitch, int dstFormat,
-                                  uint32_t width, uint32_t height, const ConvertPlan& plan, float threshold, void* scratch,
+hipError_t launch_convert_diffuse(const ImgView& src, const ImgView& dst, const ConvertPlan& plan, float threshold, void* scratch,
                                   unsigned long long* rerun, uint32_t segLen, hipStream_t stream)
 {
-    if (!width || !height) return hipSuccess;
+    const uint32_t width = src.width;
+    if (!width || !src.height) return hipSuccess;
     DiffuseArgs a;
-    a.spec = dither_spec(dstFormat);
+    a.spec = dither_spec(dst.format);
     if (!a.spec.valid) return hipErrorInvalidValue;
-    a.src = make_view(src, srcPitch, width, height, srcFormat);
-    a.dst = make_view(dst, dstPitch, width, height, dstFormat);
+    a.src = src; a.dst = dst;
     a.plan = plan; a.threshold = threshold;
     a.segLen = segLen ? segLen : std::max<uint32_t>(kDiffuseMinSeg, (width + kDiffuseThreads - 1) / kDiffuseThreads);
     a.rerun = rerun;
@@ -1290,16 +1272,15 @@ hipError_t launch_convert_diffuse(const uint8_t* src, uint64_t srcPitch, int src
     return hipGetLastError();
 }
 
-hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, uint32_t srcH, uint8_t* dst, uint64_t dstPitch,
-                         uint32_t dstW, uint32_t dstH, int format, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
-                         const TriangleTables* tri, hipStream_t stream, const uint8_t* staleLevel, uint64_t stalePitch, uint32_t staleW, int dstFormat,
-                         KernelMarks* marks)
+hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
+                         const TriangleTables* tri, hipStream_t stream, const ImgView* stale, KernelMarks* marks)
 {
+    const uint32_t srcW = src.width, srcH = src.height, dstW = dst.width, dstH = dst.height;
+    const int format = src.format;
     if (!dstW || !dstH) return hipSuccess;
     ResizeArgs a;
-    a.stale = make_view(staleLevel, stalePitch, staleW, 2, format);
-    a.src = make_view(src, srcPitch, srcW, srcH, format);
-    a.dst = make_view(dst, dstPitch, dstW, dstH, dstFormat >= 0 ? dstFormat : format);
+    a.stale = stale ? *stale : no_stale(format);
+    a.src = src; a.dst = dst;
     // sRGB formats filter in linear space; TEX_FILTER_SRGB forces it for the other colour formats (:2803-2945)
     const bool wantIn = srgb_linear_format(format) || (filterFlags & 0x1000000u), wantOut = srgb_linear_format(format) || (filterFlags & 0x2000000u);
     a.srgbIn = (can_srgb(format) && wantIn) ? 1 : 0;
@@ -1318,8 +1299,8 @@ hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, u
         // the 2:1 RGBA8 case of a power-of-two mip chain has a separable kernel (a column strip per lane); the small levels take it too (6 us a
         // launch against 10 - 30 us of the general kernel's sixteen dependent taps)
         if (format == FMT_R8G8B8A8_UNORM && !a.srgbIn && !a.srgbOut && srcW == 2 * dstW && srcH == 2 * dstH &&
-            !a.wrapU && !a.wrapV && !a.mirrorU && !a.mirrorV && (srcPitch % 4) == 0 && (dstPitch % 4) == 0 &&
-            (reinterpret_cast<uintptr_t>(src) % 4) == 0 && (reinterpret_cast<uintptr_t>(dst) % 4) == 0)
+            !a.wrapU && !a.wrapV && !a.mirrorU && !a.mirrorV && (src.rowPitch % 4) == 0 && (dst.rowPitch % 4) == 0 &&
+            (reinterpret_cast<uintptr_t>(src.pixels) % 4) == 0 && (reinterpret_cast<uintptr_t>(dst.pixels) % 4) == 0)
         {
             // rows per lane: long strips amortise the two extra row passes at their top; short ones keep a small level spread over the chip
             // (at least ~4096 wavefronts while that leaves 4 rows or more per strip)
@@ -1328,8 +1309,8 @@ hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, u
 #if !defined(DXTEX_CUBIC_X2)
 #define DXTEX_CUBIC_X2 1               // 0: every level through the one-texel-per-lane kernel (A/B builds)
 #endif
-            const bool pairs = DXTEX_CUBIC_X2 && (dstW % 2) == 0 && (srcPitch % 16) == 0 && (dstPitch % 8) == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 &&
-                               (reinterpret_cast<uintptr_t>(dst) % 8) == 0;
+            const bool pairs = DXTEX_CUBIC_X2 && (dstW % 2) == 0 && (src.rowPitch % 16) == 0 && (dst.rowPitch % 8) == 0 && (reinterpret_cast<uintptr_t>(src.pixels) % 16) == 0 &&
+                               (reinterpret_cast<uintptr_t>(dst.pixels) % 8) == 0;
             const uint32_t lanesX = pairs ? dstW / 2 : dstW;
             while (strip > 4 && uint64_t((lanesX + 63) / 64) * ((dstH + strip - 1) / strip) < 4096) strip >>= 1;
             if (pairs)
@@ -1351,7 +1332,7 @@ hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, u
         break;
     case 0x400000u:
         if (format == FMT_R8G8B8A8_UNORM && !a.srgbIn && !a.srgbOut && srcW == 2 * dstW && srcH == 2 * dstH && (dstW % 2) == 0 && dstW >= 256 &&
-            (srcPitch % 16) == 0 && (dstPitch % 8) == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 && (reinterpret_cast<uintptr_t>(dst) % 8) == 0)
+            (src.rowPitch % 16) == 0 && (dst.rowPitch % 8) == 0 && (reinterpret_cast<uintptr_t>(src.pixels) % 16) == 0 && (reinterpret_cast<uintptr_t>(dst.pixels) % 8) == 0)
         {
             DXTEX_MARK("resize_box_half_rgba8");
             hipLaunchKernelGGL(resize_box_half_rgba8_kernel, dim3((dstW / 2 + 255) / 256, grid_rows(dstH)), block, 0, stream, a);
@@ -1369,20 +1350,19 @@ hipError_t launch_resize(const uint8_t* src, uint64_t srcPitch, uint32_t srcW, u
     return hipGetLastError();
 }
 
-bool resize_half_tail_applies(const MipLevel* levels, int nlevels, int format, uint32_t filterFlags);
-hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, uint32_t filterMode, uint32_t filterFlags,
-                              const MipLevel* twoHigh, hipStream_t stream, KernelMarks* marks)
+bool resize_half_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags);
+hipError_t launch_resize_tail(const ImgView* levels, int nlevels, uint32_t filterMode, uint32_t filterFlags,
+                              const ImgView* twoHigh, hipStream_t stream, KernelMarks* marks)
 {
     if (nlevels < 2) return hipSuccess;
-    const bool halving = (filterMode == 0x300000u || filterMode == 0x400000u) && resize_half_tail_applies(levels, nlevels, format, filterFlags);
+    const int format = levels[0].format;
+    const bool halving = (filterMode == 0x300000u || filterMode == 0x400000u) && resize_half_tail_applies(levels, nlevels, filterFlags);
     if (filterMode == 0x300000u && !halving)
     {
         // a cubic chain the one-workgroup form does not cover (not an exact-halving RGBA8 clamp chain): one launch per level, as GenerateMipMaps does above the tail
         for (int k = 1; k < nlevels; ++k)
         {
-            const hipError_t e = launch_resize(levels[k - 1].pixels, levels[k - 1].pitch, levels[k - 1].width, levels[k - 1].height, levels[k].pixels, levels[k].pitch,
-                                               levels[k].width, levels[k].height, format, filterMode, filterFlags, true, nullptr, stream,
-                                               nullptr, 0, 0, -1, marks);
+            const hipError_t e = launch_resize(levels[k - 1], levels[k], filterMode, filterFlags, true, nullptr, stream, nullptr, marks);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -1391,13 +1371,13 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
     {
         // the LDS tail: RGBA8, no sRGB, every level an exact halving (cubic: clamp addressing; admitted by the caller, checked again here)
         CubicTailArgs c;
-        c.src = levels[0].pixels; c.srcPitch = levels[0].pitch; c.srcW = levels[0].width; c.srcH = levels[0].height; c.nlevels = nlevels - 1;
+        c.src = levels[0].pixels; c.srcPitch = levels[0].rowPitch; c.srcW = levels[0].width; c.srcH = levels[0].height; c.nlevels = nlevels - 1;
         if (format != FMT_R8G8B8A8_UNORM || (filterFlags & 0x3000077u) || c.nlevels > kTailMaxLevels || c.srcW > kTailSide || c.srcH > kTailSide) return hipErrorInvalidValue;
         for (int k = 1; k < nlevels; ++k)
         {
-            if (levels[k].width * 2u != levels[k - 1].width || levels[k].height * 2u != levels[k - 1].height || (levels[k].pitch % 4) != 0 ||
+            if (levels[k].width * 2u != levels[k - 1].width || levels[k].height * 2u != levels[k - 1].height || (levels[k].rowPitch % 4) != 0 ||
                 (reinterpret_cast<uintptr_t>(levels[k].pixels) % 4) != 0) return hipErrorInvalidValue;
-            c.dst[k - 1] = levels[k].pixels; c.dstPitch[k - 1] = levels[k].pitch;
+            c.dst[k - 1] = levels[k].pixels; c.dstPitch[k - 1] = levels[k].rowPitch;
         }
         for (int k = nlevels - 1; k < kTailMaxLevels; ++k) { c.dst[k] = c.dst[0]; c.dstPitch[k] = c.dstPitch[0]; }
         if (filterMode == 0x300000u) { DXTEX_MARK("resize_half_tail_rgba8<cubic>"); hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<true>, dim3(1), dim3(1024), 0, stream, c); }
@@ -1407,8 +1387,8 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
     }
     TailArgs t;
     ResizeArgs& a = t.a;
-    a.stale = make_view(nullptr, 0, 0, 2, format);
-    a.src = make_view(levels[0].pixels, levels[0].pitch, levels[0].width, levels[0].height, format);
+    a.stale = no_stale(format);
+    a.src = levels[0];
     a.dst = a.src;
     const bool wantIn = srgb_linear_format(format) || (filterFlags & 0x1000000u), wantOut = srgb_linear_format(format) || (filterFlags & 0x2000000u);
     a.srgbIn = (can_srgb(format) && wantIn) ? 1 : 0;
@@ -1418,11 +1398,11 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
     a.mipAlias = 1;
     a.triOfsX = nullptr; a.triX = nullptr; a.triOfsY = nullptr; a.triY = nullptr;
     t.mode = filterMode;
-    t.twoHigh = twoHigh ? make_view(twoHigh->pixels, twoHigh->pitch, twoHigh->width, twoHigh->height, format) : make_view(nullptr, 0, 0, 2, format);
+    t.twoHigh = twoHigh ? *twoHigh : no_stale(format);
     for (int at = 1; at < nlevels; )
     {
         t.nlevels = std::min(kTailMaxLevels, nlevels - at);
-        for (int k = 0; k < t.nlevels; ++k) t.level[k] = make_view(levels[at + k].pixels, levels[at + k].pitch, levels[at + k].width, levels[at + k].height, format);
+        for (int k = 0; k < t.nlevels; ++k) t.level[k] = levels[at + k];
         for (int k = t.nlevels; k < kTailMaxLevels; ++k) t.level[k] = t.level[0];
         DXTEX_MARK("resize_tail");
         hipLaunchKernelGGL(resize_tail_kernel, dim3(1), dim3(1024), 0, stream, t);
@@ -1434,20 +1414,20 @@ hipError_t launch_resize_tail(const MipLevel* levels, int nlevels, int format, u
     return hipGetLastError();
 }
 
-bool resize_half_tail_applies(const MipLevel* levels, int nlevels, int format, uint32_t filterFlags)
+bool resize_half_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags)
 {
     // the LDS tail of a power-of-two RGBA8 chain (resize_cubic_tail_rgba8_kernel): every remaining level halves both sides exactly
-    if (nlevels < 2 || nlevels - 1 > kTailMaxLevels || format != FMT_R8G8B8A8_UNORM || (filterFlags & 0x3000077u)) return false;       // sRGB, wrap, mirror bits
-    if (levels[0].width > kTailSide || levels[0].height > kTailSide || (levels[0].pitch % 4) != 0 || (reinterpret_cast<uintptr_t>(levels[0].pixels) % 4) != 0) return false;
+    if (nlevels < 2 || nlevels - 1 > kTailMaxLevels || levels[0].format != FMT_R8G8B8A8_UNORM || (filterFlags & 0x3000077u)) return false;       // sRGB, wrap, mirror bits
+    if (levels[0].width > kTailSide || levels[0].height > kTailSide || (levels[0].rowPitch % 4) != 0 || (reinterpret_cast<uintptr_t>(levels[0].pixels) % 4) != 0) return false;
     for (int k = 1; k < nlevels; ++k)
-        if (levels[k].width * 2u != levels[k - 1].width || levels[k].height * 2u != levels[k - 1].height || (levels[k].pitch % 4) != 0 ||
+        if (levels[k].width * 2u != levels[k - 1].width || levels[k].height * 2u != levels[k - 1].height || (levels[k].rowPitch % 4) != 0 ||
             (reinterpret_cast<uintptr_t>(levels[k].pixels) % 4) != 0) return false;
     return true;
 }
 
-bool resize_cubic_tail_applies(const MipLevel* levels, int nlevels, int format, uint32_t filterFlags)
+bool resize_cubic_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags)
 {
-    return resize_half_tail_applies(levels, nlevels, format, filterFlags);
+    return resize_half_tail_applies(levels, nlevels, filterFlags);
 }
 
 bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode)
@@ -1457,50 +1437,45 @@ bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode)
     return srcW <= kTailSide && srcH <= kTailSide && (filterMode == 0x100000u || filterMode == 0x200000u || filterMode == 0x400000u);
 }
 
-hipError_t launch_pmalpha(const uint8_t* src, uint64_t srcPitch, uint8_t* dst, uint64_t dstPitch, int format, uint32_t width, uint32_t height,
-                          uint32_t pmFlags, hipStream_t stream)
+hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream)
 {
-    if (!width || !height) return hipSuccess;
+    const int format = src.format;
+    if (!src.width || !src.height) return hipSuccess;
     // TEX_PMALPHA_IGNORE_SRGB (0x1): plain Load/StoreScanline; otherwise the *Linear wrappers with the SRGB_IN/OUT bits (:68-112)
     const bool linear = !(pmFlags & 0x1u);
     const bool wantIn = linear && (srgb_linear_format(format) || (pmFlags & 0x1000000u)), wantOut = linear && (srgb_linear_format(format) || (pmFlags & 0x2000000u));
-    hipLaunchKernelGGL(pmalpha_kernel, dim3((width + 255) / 256, grid_rows(height)), dim3(256), 0, stream,
-                       make_view(src, srcPitch, width, height, format), make_view(dst, dstPitch, width, height, format),
+    hipLaunchKernelGGL(pmalpha_kernel, dim3((src.width + 255) / 256, grid_rows(src.height)), dim3(256), 0, stream, src, dst,
                        (can_srgb(format) && wantIn) ? 1 : 0, (can_srgb(format) && wantOut) ? 1 : 0, (pmFlags & 0x2u) ? 1 : 0);
     return hipGetLastError();
 }
 
-hipError_t launch_scale_alpha(const uint8_t* src, uint64_t srcPitch, uint8_t* dst, uint64_t dstPitch, int format, uint32_t width, uint32_t height,
-                              float scale, hipStream_t stream)
+hipError_t launch_scale_alpha(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream)
 {
-    if (!width || !height) return hipSuccess;
-    hipLaunchKernelGGL(scale_alpha_kernel, dim3((width + 255) / 256, grid_rows(height)), dim3(256), 0, stream,
-                       make_view(src, srcPitch, width, height, format), make_view(dst, dstPitch, width, height, format), scale);
+    if (!src.width || !src.height) return hipSuccess;
+    hipLaunchKernelGGL(scale_alpha_kernel, dim3((src.width + 255) / 256, grid_rows(src.height)), dim3(256), 0, stream, src, dst, scale);
     return hipGetLastError();
 }
 
-hipError_t launch_alpha_coverage(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, float scale, float alphaReference,
-                                 unsigned long long* count, hipStream_t stream)
+hipError_t launch_alpha_coverage(const ImgView& src, float scale, float alphaReference, unsigned long long* count, hipStream_t stream)
 {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
-    if (width < 2 || height < 2) return hipSuccess;
-    hipLaunchKernelGGL(alpha_coverage_kernel, dim3((width - 1 + 255) / 256, grid_rows(height - 1)), dim3(256), 0, stream,
-                       make_view(src, srcPitch, width, height, format), scale, alphaReference, count);
+    if (src.width < 2 || src.height < 2) return hipSuccess;
+    hipLaunchKernelGGL(alpha_coverage_kernel, dim3((src.width - 1 + 255) / 256, grid_rows(src.height - 1)), dim3(256), 0, stream,
+                       src, scale, alphaReference, count);
     return hipGetLastError();
 }
 
-hipError_t launch_alpha_below(const uint8_t* src, uint64_t srcPitch, int format, uint32_t width, uint32_t height, float threshold,
-                              unsigned long long* count, hipStream_t stream)
+hipError_t launch_alpha_below(const ImgView& src, float threshold, unsigned long long* count, hipStream_t stream)
 {
-    if (!width || !height) return hipSuccess;
-    const uint32_t gx = std::min<uint32_t>((width + 255) / 256, 64), gy = std::min<uint32_t>(height, 2048);
-    hipLaunchKernelGGL(alpha_below_kernel, dim3(gx, gy), dim3(256), 0, stream, make_view(src, srcPitch, width, height, format), threshold, count);
+    if (!src.width || !src.height) return hipSuccess;
+    const uint32_t gx = std::min<uint32_t>((src.width + 255) / 256, 64), gy = std::min<uint32_t>(src.height, 2048);
+    hipLaunchKernelGGL(alpha_below_kernel, dim3(gx, gy), dim3(256), 0, stream, src, threshold, count);
     return hipGetLastError();
 }
 
 hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_t filterMode, uint32_t filterFlags, const TriangleTables3* tri,
-                           hipStream_t stream, const uint8_t* staleU, const uint8_t* staleV, uint64_t stalePitch, uint32_t staleW)
+                           hipStream_t stream, const ImgView* staleU, const ImgView* staleV)
 {
     if (!dst.width || !dst.height || !dst.depth) return hipSuccess;
     Resize3Args a;
@@ -1513,8 +1488,8 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
     a.srgbOut = (can_srgb(format) && wantOut) ? 1 : 0;
     a.wrapU = (filterFlags & 0x1u) != 0; a.wrapV = (filterFlags & 0x2u) != 0; a.wrapW = (filterFlags & 0x4u) != 0;
     a.mirrorU = (filterFlags & 0x10u) != 0; a.mirrorV = (filterFlags & 0x20u) != 0; a.mirrorW = (filterFlags & 0x40u) != 0;
-    a.staleU = make_view(staleU, stalePitch, staleW, 2, format);
-    a.staleV = make_view(staleV, stalePitch, staleW, 2, format);
+    a.staleU = staleU ? *staleU : no_stale(format);
+    a.staleV = staleV ? *staleV : no_stale(format);
     a.triOfsX = tri ? tri->ofsX : nullptr; a.triX = tri ? reinterpret_cast<const uint2*>(tri->entX) : nullptr;
     a.triOfsY = tri ? tri->ofsY : nullptr; a.triY = tri ? reinterpret_cast<const uint2*>(tri->entY) : nullptr;
     a.triOfsZ = tri ? tri->ofsZ : nullptr; a.triZ = tri ? reinterpret_cast<const uint2*>(tri->entZ) : nullptr;
@@ -1531,17 +1506,17 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
     return hipGetLastError();
 }
 
-hipError_t launch_mse(const uint8_t* a, uint64_t aPitch, int aFormat, const uint8_t* b, uint64_t bPitch, int bFormat,
-                      uint32_t width, uint32_t height, double* out4, hipStream_t stream, KernelMarks* marks)
+hipError_t launch_mse(const ImgView& a, const ImgView& b, double* out4, hipStream_t stream, KernelMarks* marks)
 {
+    const uint32_t width = a.width, height = a.height;
+    const int aFormat = a.format, bFormat = b.format;
     hipError_t e = hipMemsetAsync(out4, 0, 4 * sizeof(double), stream);
     if (e != hipSuccess) return e;
     if (!width || !height) return hipSuccess;
     const bool ignoreAlpha = aFormat == FMT_B8G8R8X8_UNORM || aFormat == FMT_B8G8R8X8_UNORM_SRGB || bFormat == FMT_B8G8R8X8_UNORM || bFormat == FMT_B8G8R8X8_UNORM_SRGB;
     const uint32_t gx = std::min<uint32_t>((width + 255) / 256, 64), gy = std::min<uint32_t>(height, 1024);
     DXTEX_MARK("mse");
-    hipLaunchKernelGGL(mse_kernel, dim3(gx, gy), dim3(256), 0, stream, make_view(a, aPitch, width, height, aFormat),
-                       make_view(b, bPitch, width, height, bFormat), srgb_linear_format(aFormat) ? 1 : 0, srgb_linear_format(bFormat) ? 1 : 0,
+    hipLaunchKernelGGL(mse_kernel, dim3(gx, gy), dim3(256), 0, stream, a, b, srgb_linear_format(aFormat) ? 1 : 0, srgb_linear_format(bFormat) ? 1 : 0,
                        ignoreAlpha ? 1 : 0, out4);
     DXTEX_MARK(nullptr);
     return hipGetLastError();
