@@ -1087,6 +1087,7 @@ dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, u
         dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
         tri = ctx->triBuf.u8();
     }
+    KernelMarks* marks = marks_of(ctx);
     const VolumeView* twoHigh = nullptr;     // box: the last SOURCE level that was 2 texels high (what urow1 / vrow1's old buffers hold)
     for (size_t i = 1; i < lv.size(); ++i)
     {
@@ -1101,10 +1102,10 @@ dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, u
         {
             TriangleTables3 t{};
             if (tri) t = { tri_ofs(tri, x[i]), tri + x[i].ent, tri_ofs(tri, y[i]), tri + y[i].ent, tri_ofs(tri, z[i]), tri + z[i].ent };
-            e = launch_resize3d(s, d, mode, flags, tri ? &t : nullptr, ctx->stream, stale ? &staleU : nullptr, stale ? &staleV : nullptr);
+            e = launch_resize3d(s, d, mode, flags, tri ? &t : nullptr, ctx->stream, stale ? &staleU : nullptr, stale ? &staleV : nullptr, marks);
         }
         else
-            e = launch_resize(slice_of(s, 0), slice_of(d, 0), mode, flags, true, nullptr, ctx->stream, stale ? &staleU : nullptr);
+            e = launch_resize(slice_of(s, 0), slice_of(d, 0), mode, flags, true, nullptr, ctx->stream, stale ? &staleU : nullptr, marks);
         const dxtex_hresult hr = launched(ctx, e);
         if (hr != DXTEX_S_OK) return hr;
     }
@@ -1457,14 +1458,15 @@ dxtex_hresult check_pmalpha(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_
 
 dxtex_hresult submit_pmalpha(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags)
 {
-    return launched(ctx, launch_pmalpha(view_of(src), view_of(dst), flags, ctx->stream));
+    return launched(ctx, launch_pmalpha(view_of(src), view_of(dst), flags, ctx->stream, marks_of(ctx)));
 }
 
 // EstimateAlphaScaleForCoverage (DirectXTexMipmaps.cpp:310-352) around the device coverage count
 dxtex_hresult alpha_coverage(dxtex_ctx* ctx, const dxtex_image& im, float scale, float alphaReference, float* coverage)
 {
     dxtex_hresult hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
-    hr = launched(ctx, launch_alpha_coverage(view_of(im), scale, alphaReference, static_cast<unsigned long long*>(ctx->resultCell.p), ctx->stream));
+    hr = launched(ctx, launch_alpha_coverage(view_of(im), scale, alphaReference, static_cast<unsigned long long*>(ctx->resultCell.p), ctx->stream,
+                                             marks_of(ctx)));
     if (hr != DXTEX_S_OK) return hr;
     unsigned long long n = 0;
     HIP_TRY(ctx, counted_copy(ctx, &n, ctx->resultCell.p, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
@@ -1513,7 +1515,7 @@ dxtex_hresult submit_coverage_chain(dxtex_ctx* ctx, const dxtex_image* src, cons
             else break;
             scale = (lo + hi) * 0.5f;
         }
-        hr = launched(ctx, launch_scale_alpha(view_of(src[level]), view_of(dst[level]), scale, ctx->stream));
+        hr = launched(ctx, launch_scale_alpha(view_of(src[level]), view_of(dst[level]), scale, ctx->stream, marks_of(ctx)));
         if (hr != DXTEX_S_OK) return hr;
     }
     return DXTEX_S_OK;
@@ -1693,10 +1695,10 @@ dxtex_hresult dxtex_alpha_all_opaque_device(dxtex_ctx* ctx, const dxtex_image* i
             const dxtex_image decoded = { im.width, im.height, FMT_R32G32B32A32_FLOAT, pitch, pitch * im.height, ctx->stageOut.u8() };
             hr = submit_decompress(ctx, im, decoded);
             if (hr != DXTEX_S_OK) return hr;
-            e = launch_alpha_below(view_of(decoded), 0.99f, counter, ctx->stream);
+            e = launch_alpha_below(view_of(decoded), 0.99f, counter, ctx->stream, marks_of(ctx));
         }
         else
-            e = launch_alpha_below(view_of(im), 0.997f, counter, ctx->stream);
+            e = launch_alpha_below(view_of(im), 0.997f, counter, ctx->stream, marks_of(ctx));
         hr = launched(ctx, e);
         if (hr != DXTEX_S_OK) return hr;
     }

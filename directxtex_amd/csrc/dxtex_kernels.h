@@ -113,16 +113,17 @@ struct VolumeView { const uint8_t* pixels; uint64_t rowPitch, slicePitch; uint32
 struct TriangleTables3 { const uint32_t* ofsX; const void* entX; const uint32_t* ofsY; const void* entY; const uint32_t* ofsZ; const void* entZ; };
 // staleU / staleV (box only, both or neither): the slices whose row 1 the reference's never re-pointed urow3 / vrow3 still see, see resize3d_box_kernel.
 hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_t filterMode, uint32_t filterFlags, const TriangleTables3* tri,
-                           hipStream_t stream, const ImgView* staleU = nullptr, const ImgView* staleV = nullptr);
+                           hipStream_t stream, const ImgView* staleU = nullptr, const ImgView* staleV = nullptr, KernelMarks* marks = nullptr);
 
 // ComputeMSE: out4 (device) receives the per-channel SUM of squared differences; divide by width * height (a's; b matches it) on the host.
 hipError_t launch_mse(const ImgView& a, const ImgView& b, double* out4, hipStream_t stream, KernelMarks* marks = nullptr);
 // PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205); pmFlags = TEX_PMALPHA_*. Size and format are src's; dst matches them.
-hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream);
+hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream, KernelMarks* marks = nullptr);
 // ScaleAlpha and CalculateAlphaCoverage (DirectXTexMipmaps.cpp:143-305); *count receives the number of covered sub-samples.
 // launch_scale_alpha: size and format are src's; dst matches them.
-hipError_t launch_scale_alpha(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream);
-hipError_t launch_alpha_coverage(const ImgView& src, float scale, float alphaReference, unsigned long long* count, hipStream_t stream);
+hipError_t launch_scale_alpha(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream, KernelMarks* marks = nullptr);
+hipError_t launch_alpha_coverage(const ImgView& src, float scale, float alphaReference, unsigned long long* count, hipStream_t stream,
+                                 KernelMarks* marks = nullptr);
 // IsAlphaAllOpaque's scan: *count (device, NOT cleared here) is incremented by the number of texels with alpha < threshold
-hipError_t launch_alpha_below(const ImgView& src, float threshold, unsigned long long* count, hipStream_t stream);
+hipError_t launch_alpha_below(const ImgView& src, float threshold, unsigned long long* count, hipStream_t stream, KernelMarks* marks = nullptr);
 } // namespace dxtex

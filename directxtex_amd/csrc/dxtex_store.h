@@ -99,7 +99,9 @@ __device__ __forceinline__ int32_t store_bn(float v)
 
 __device__ __forceinline__ uint16_t store_half(float v)
 {
-    float s = (v > -65504.0f) ? v : -65504.0f; s = (s < 65504.0f) ? s : 65504.0f;      // XMVectorClamp(v, g_HalfMin, g_HalfMax)
+    // XMVectorClamp(v, g_HalfMin, g_HalfMax) = _mm_min_ps(max, _mm_max_ps(min, v)): both return their second operand when one is NaN, so a NaN
+    // stays NaN (as it does through std::max(std::min(v, 65504), -65504) of the one-channel stores) instead of landing on a bound
+    float s = (v < -65504.0f) ? -65504.0f : v; s = (s > 65504.0f) ? 65504.0f : s;
     return __half_as_ushort(__float2half_rn(s));
 }
 

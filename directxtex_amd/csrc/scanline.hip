@@ -1437,45 +1437,53 @@ bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode)
     return srcW <= kTailSide && srcH <= kTailSide && (filterMode == 0x100000u || filterMode == 0x200000u || filterMode == 0x400000u);
 }
 
-hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream)
+hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream, KernelMarks* marks)
 {
     const int format = src.format;
     if (!src.width || !src.height) return hipSuccess;
     // TEX_PMALPHA_IGNORE_SRGB (0x1): plain Load/StoreScanline; otherwise the *Linear wrappers with the SRGB_IN/OUT bits (:68-112)
     const bool linear = !(pmFlags & 0x1u);
     const bool wantIn = linear && (srgb_linear_format(format) || (pmFlags & 0x1000000u)), wantOut = linear && (srgb_linear_format(format) || (pmFlags & 0x2000000u));
+    DXTEX_MARK("pmalpha");
     hipLaunchKernelGGL(pmalpha_kernel, dim3((src.width + 255) / 256, grid_rows(src.height)), dim3(256), 0, stream, src, dst,
                        (can_srgb(format) && wantIn) ? 1 : 0, (can_srgb(format) && wantOut) ? 1 : 0, (pmFlags & 0x2u) ? 1 : 0);
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_scale_alpha(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream)
+hipError_t launch_scale_alpha(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream, KernelMarks* marks)
 {
     if (!src.width || !src.height) return hipSuccess;
+    DXTEX_MARK("scale_alpha");
     hipLaunchKernelGGL(scale_alpha_kernel, dim3((src.width + 255) / 256, grid_rows(src.height)), dim3(256), 0, stream, src, dst, scale);
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_alpha_coverage(const ImgView& src, float scale, float alphaReference, unsigned long long* count, hipStream_t stream)
+hipError_t launch_alpha_coverage(const ImgView& src, float scale, float alphaReference, unsigned long long* count, hipStream_t stream, KernelMarks* marks)
 {
     hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
     if (src.width < 2 || src.height < 2) return hipSuccess;
+    DXTEX_MARK("alpha_coverage");
     hipLaunchKernelGGL(alpha_coverage_kernel, dim3((src.width - 1 + 255) / 256, grid_rows(src.height - 1)), dim3(256), 0, stream,
                        src, scale, alphaReference, count);
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
-hipError_t launch_alpha_below(const ImgView& src, float threshold, unsigned long long* count, hipStream_t stream)
+hipError_t launch_alpha_below(const ImgView& src, float threshold, unsigned long long* count, hipStream_t stream, KernelMarks* marks)
 {
     if (!src.width || !src.height) return hipSuccess;
     const uint32_t gx = std::min<uint32_t>((src.width + 255) / 256, 64), gy = std::min<uint32_t>(src.height, 2048);
+    DXTEX_MARK("alpha_below");
     hipLaunchKernelGGL(alpha_below_kernel, dim3(gx, gy), dim3(256), 0, stream, src, threshold, count);
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_t filterMode, uint32_t filterFlags, const TriangleTables3* tri,
-                           hipStream_t stream, const ImgView* staleU, const ImgView* staleV)
+                           hipStream_t stream, const ImgView* staleU, const ImgView* staleV, KernelMarks* marks)
 {
     if (!dst.width || !dst.height || !dst.depth) return hipSuccess;
     Resize3Args a;
@@ -1496,13 +1504,14 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
     const dim3 grid((dst.width + 255) / 256, dst.height, dst.depth), block(256);
     switch (filterMode)
     {
-    case 0x100000u: hipLaunchKernelGGL(resize3d_point_kernel, grid, block, 0, stream, a); break;
-    case 0x200000u: hipLaunchKernelGGL(resize3d_linear_kernel, grid, block, 0, stream, a); break;
-    case 0x300000u: hipLaunchKernelGGL(resize3d_cubic_kernel, grid, block, 0, stream, a); break;
-    case 0x400000u: hipLaunchKernelGGL(resize3d_box_kernel, grid, block, 0, stream, a); break;
-    case 0x500000u: hipLaunchKernelGGL(resize3d_triangle_kernel, grid, block, 0, stream, a); break;
+    case 0x100000u: DXTEX_MARK("resize3d_point"); hipLaunchKernelGGL(resize3d_point_kernel, grid, block, 0, stream, a); break;
+    case 0x200000u: DXTEX_MARK("resize3d_linear"); hipLaunchKernelGGL(resize3d_linear_kernel, grid, block, 0, stream, a); break;
+    case 0x300000u: DXTEX_MARK("resize3d_cubic"); hipLaunchKernelGGL(resize3d_cubic_kernel, grid, block, 0, stream, a); break;
+    case 0x400000u: DXTEX_MARK("resize3d_box"); hipLaunchKernelGGL(resize3d_box_kernel, grid, block, 0, stream, a); break;
+    case 0x500000u: DXTEX_MARK("resize3d_triangle"); hipLaunchKernelGGL(resize3d_triangle_kernel, grid, block, 0, stream, a); break;
     default: return hipErrorInvalidValue;
     }
+    DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 

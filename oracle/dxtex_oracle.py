@@ -19,6 +19,12 @@ BC_BLOCK_BYTES = {71: 8, 72: 8, 80: 8, 81: 8, 74: 16, 75: 16, 77: 16, 78: 16, 83
 _ref = None
 
 
+class _RefImage(ctypes.Structure):
+    """DirectX::Image (DirectXTex.h)."""
+    _fields_ = [("width", ctypes.c_size_t), ("height", ctypes.c_size_t), ("format", ctypes.c_int32), ("rowPitch", ctypes.c_size_t),
+                ("slicePitch", ctypes.c_size_t), ("pixels", ctypes.c_void_p)]
+
+
 def have_ref():
     return os.path.exists(_REF_PATH)
 
@@ -52,6 +58,15 @@ def _load_ref():
             f.restype = ctypes.c_int64
         lib.dxtex_ref_compute_mse.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, sz, sz, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         lib.dxtex_ref_compute_mse.restype = ctypes.c_int
+        # the reference's own ScratchImage members, as the library exports them (ref_image.cpp compiles DirectXTexImage.cpp in place)
+        lib._ZN7DirectX12ScratchImage12Initialize2DE11DXGI_FORMATmmmmNS_8CP_FLAGSE.argtypes = [vp, ctypes.c_int, sz, sz, sz, sz, ctypes.c_uint32]
+        lib._ZN7DirectX12ScratchImage12Initialize2DE11DXGI_FORMATmmmmNS_8CP_FLAGSE.restype = ctypes.c_int32
+        lib._ZNK7DirectX12ScratchImage8GetImageEmmm.argtypes = [vp, sz, sz, sz]
+        lib._ZNK7DirectX12ScratchImage8GetImageEmmm.restype = ctypes.POINTER(_RefImage)
+        lib._ZNK7DirectX12ScratchImage16IsAlphaAllOpaqueEv.argtypes = [vp]
+        lib._ZNK7DirectX12ScratchImage16IsAlphaAllOpaqueEv.restype = ctypes.c_bool
+        lib._ZN7DirectX12ScratchImage7ReleaseEv.argtypes = [vp]
+        lib._ZN7DirectX12ScratchImage7ReleaseEv.restype = None
         lib.dxtex_ref_save_dds.argtypes = [vp, sz, sz, ctypes.c_int, sz, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, i32p]
         lib.dxtex_ref_save_dds.restype = ctypes.c_int64
         lib.dxtex_ref_load_dds.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_uint64), vp, sz, i32p]
@@ -441,6 +456,33 @@ def ref_compute_mse(a, fmt_a, b, fmt_b, width, height):
     if hr != 0:
         raise RefError(hr)
     return np.array(list(v), np.float32)
+
+
+def ref_alpha_all_opaque(images, fmt, width, height):
+    """ScratchImage::IsAlphaAllOpaque (DirectXTexImage.cpp:800-852; IsAlphaAllOpaqueBC, DirectXTexCompress.cpp:539-621) over a list of
+    tight images of one size and format (a texture array; block-compressed formats included) -> bool.
+
+    The function is a member of ScratchImage, so the oracle drives the reference's own exported members: Initialize2D on a zeroed
+    object (the state its constructor leaves, DirectXTex.h: every member 0 / nullptr; 256 bytes hold its 88), GetImage for each item's
+    pixels, IsAlphaAllOpaque, Release. Nothing of the function is restated here, and any build of oracle/_ref answers."""
+    images = [np.ascontiguousarray(i).view(np.uint8).reshape(-1) for i in images]
+    nbytes = image_bytes(fmt, width, height)
+    assert all(i.size == nbytes for i in images), ([i.size for i in images], fmt, width, height)
+    lib = _load_ref()
+    si = ctypes.create_string_buffer(256)
+    hr = lib._ZN7DirectX12ScratchImage12Initialize2DE11DXGI_FORMATmmmmNS_8CP_FLAGSE(si, fmt, width, height, len(images), 1, 0)
+    if hr < 0:
+        raise RefError(hr)
+    try:
+        for item, px in enumerate(images):
+            im = lib._ZNK7DirectX12ScratchImage8GetImageEmmm(si, 0, item, 0).contents
+            rows = im.slicePitch // im.rowPitch
+            assert nbytes % rows == 0 and nbytes // rows <= im.rowPitch, (nbytes, rows, im.rowPitch)
+            for y, row in enumerate(px.reshape(rows, -1)):
+                ctypes.memmove(im.pixels + y * im.rowPitch, row.ctypes.data, row.size)
+        return bool(lib._ZNK7DirectX12ScratchImage16IsAlphaAllOpaqueEv(si))
+    finally:
+        lib._ZN7DirectX12ScratchImage7ReleaseEv(si)
 
 
 def texture_bytes(fmt, width, height, array_size, mip_levels):

@@ -5,8 +5,8 @@ flag x source x destination x size matrix; the device variant, the host layer, t
 Non-finite rule. Where a result lane is NaN, the reference's sign and payload come from x86 SSE rules (the first NaN operand is
 propagated, quieted; XMVector3Normalize writes 0x7FC00000 for an infinite length) and the GPU's from its own (operands may be
 canonicalised, and a product by -1 may be compiled as a negation). So a NaN lane of a 32-bit FLOAT destination must be a NaN in both,
-with any sign and payload. A 16-bit float store first clamps to +-65504 (XMVectorClamp, a min / max selection whose NaN result depends
-on operand order, as test_nonfinite_gpu.py notes): a lane that is NaN before the store is not compared there. Every other lane, and every
+with any sign and payload. A 16-bit float store first clamps to +-65504 (XMVectorClamp, which lets a NaN through, as store_half does): a
+lane that is NaN before the store must be a NaN half in both, with any sign and payload. Every other lane, and every
 UNORM / SNORM destination (whose stores saturate NaN to a defined value), must be equal bit for bit."""
 import hashlib
 import json
@@ -153,9 +153,9 @@ def _nan_equal(got, want, dst, rows):
     if dst in (RGBA32F, 41):                      # a NaN lane matches any NaN, every other lane bit for bit
         g, r = got.view(np.float32), want.view(np.float32)
         return bool(np.all((np.isnan(g) & np.isnan(r)) | (g.view(np.uint32) == r.view(np.uint32))))
-    if dst == 10:                                 # lanes that are NaN before the half store's clamp are not compared
-        keep = ~np.isnan(rows.reshape(-1))
-        return np.array_equal(got.view(np.uint16)[keep], want.view(np.uint16)[keep])
+    if dst == 10:                                 # a lane that is NaN before the half store is a NaN half in both, every other lane bit for bit
+        g, r = got.view(np.float16), want.view(np.float16)
+        return bool(np.all((np.isnan(g) & np.isnan(r)) | (got.view(np.uint16) == want.view(np.uint16))))
     return np.array_equal(got, want)
 
 

@@ -128,3 +128,42 @@ def test_alpha_coverage_running_vector_quirk():
     assert np.array_equal(out[0], mips[0])
     scale = a1[0, 0] / m1[0, 0]
     assert np.allclose(a1, m1 * scale, rtol=1e-6) and 0.0 < scale <= 4.0
+
+
+def _bc3_block(alpha0, alpha1, index):
+    """One BC3 block: alpha endpoints, sixteen 3-bit alpha indices all equal to `index`, then an opaque white BC1 colour block."""
+    bits = sum(index << (3 * i) for i in range(16))
+    return np.frombuffer(bytes([alpha0, alpha1]) + bits.to_bytes(6, "little") + b"\xff\xff\xff\xff\x00\x00\x00\x00", np.uint8)
+
+
+def test_reference_alpha_all_opaque_thresholds():
+    """ScratchImage::IsAlphaAllOpaque as the oracle calls it: uncompressed texels are tested against 0.997 (DirectXTexImage.cpp:822),
+    decoded block-compressed texels against 0.99 (DirectXTexCompress.cpp:574). 254 / 255 = 0.9961 is below the first; 253 / 255 = 0.9922
+    lies between the two, 252 / 255 = 0.9882 below both."""
+    _need_ref()
+    img = np.full((6, 7, 4), 255, np.uint8)
+    assert oracle.ref_alpha_all_opaque([img], RGBA8, 7, 6)
+    img[5, 6, 3] = 254
+    assert not oracle.ref_alpha_all_opaque([img], RGBA8, 7, 6)
+    assert not oracle.ref_alpha_all_opaque([np.full((6, 7, 4), 255, np.uint8), img], RGBA8, 7, 6)      # the second image of an array counts
+    for alpha1, want in ((253, True), (252, False)):
+        block = _bc3_block(255, alpha1, 1)                 # alpha0 > alpha1: eight-alpha mode, index 1 = alpha1
+        dec = oracle.ref_decode_blocks(77, block)[0, :, 3]
+        assert np.all(dec == dec[0]) and abs(float(dec[0]) - alpha1 / 255.0) < 1e-6 and (0.99 <= dec[0] < 0.997) == want
+        assert oracle.ref_alpha_all_opaque([block], 77, 4, 4) == want
+    # a transparent texel in the padding of a partial block does not count (:587-611): the same block declared 4 x 4 and 3 x 4
+    block = _bc3_block(255, 0, 0).copy()
+    block[2:8] = np.frombuffer((1 << 9).to_bytes(6, "little"), np.uint8)       # texel 3 (x = 3, y = 0) takes alpha1 = 0, the rest alpha0
+    assert not oracle.ref_alpha_all_opaque([block], 77, 4, 4)
+    assert oracle.ref_alpha_all_opaque([block], 77, 3, 4)
+    assert oracle.ref_alpha_all_opaque([np.zeros(8, np.uint8)], 80, 4, 4)      # BC4: no alpha in the format
+    # float alphas: NaN is not less than the threshold, -0.0 is; the half on either side of 0.997
+    for dtype, fmt in ((np.float32, 2), (np.float16, 10)):
+        for a, want in ((np.nan, True), (-0.0, False), (1.0, True), (0.9966, False), (0.9971, True)):
+            px = np.ones((3, 5, 4), dtype)
+            px[2, 4, 3] = a
+            assert oracle.ref_alpha_all_opaque([px], fmt, 5, 3) == want, (fmt, a)
+    rng = np.random.default_rng(7)
+    for fmt in (24, 86, 115, 65, 61):                      # random alphas are not all opaque; R8 has no alpha
+        payload = rng.integers(0, 256, oracle.image_bytes(fmt, 9, 6), dtype=np.uint8)
+        assert oracle.ref_alpha_all_opaque([payload], fmt, 9, 6) == (fmt == 61)

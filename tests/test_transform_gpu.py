@@ -57,6 +57,9 @@ def _source(fmt, w, h, seed):
     return pix, rp
 
 
+HALF_FORMATS = (10, 34, 54)             # R16G16B16A16_FLOAT, R16G16_FLOAT, R16_FLOAT
+
+
 def _want(oracle, pix, w, h, fmt, rp, op, mask, m=None, nan_texels=False):
     rows = R.load_rows(oracle, pix, w, h, fmt, rp)
     swz, zero, one = R.parse_swizzle_mask(mask) if mask else ((0, 1, 2, 3), (0,) * 4, (0,) * 4)
@@ -68,10 +71,15 @@ def _want(oracle, pix, w, h, fmt, rp, op, mask, m=None, nan_texels=False):
 
 
 def _assert_same(got, want, nan, fmt, w, h, rp, what):
-    """Byte for byte, except that where the op hands StoreScanline a NaN, formats other than R32G32B32A32_FLOAT only have to store the
-    texel somehow: the shared store path clamps a NaN half to -65504 where XMVectorClamp lets it through (a divergence of the scanline
-    layer that predates the transforms); R32G32B32A32_FLOAT stores the row as it is, so its NaNs are compared bit for bit."""
+    """Byte for byte. Where the op hands StoreScanline a NaN: R32G32B32A32_FLOAT stores the row as it is, so its NaNs are compared bit for
+    bit; a half format stores a NaN half on both sides (store_half lets it through the clamp, as XMVectorClamp does), compared as "NaN in
+    both" since a NaN half's sign and payload are the platform's; the other formats only have to store the texel somehow."""
     g, t = got.reshape(h, rp), want.reshape(h, rp)
+    if fmt in HALF_FORMATS and nan.any():
+        gh, th = g.view(np.float16), t.view(np.float16)
+        same = (g.view(np.uint16) == t.view(np.uint16)) | (np.isnan(gh) & np.isnan(th))
+        assert same.all(), (what, fmt, w, h, np.argwhere(~same)[:8])
+        return
     if fmt != RGBA32F and nan.any() and fmt not in (107, 66):
         bpt = rp // w
         keep = np.ones((h, rp), bool)
