@@ -51,6 +51,12 @@ class Image(ctypes.Structure):
                 ("rowPitch", ctypes.c_size_t), ("slicePitch", ctypes.c_size_t), ("pixels", ctypes.c_void_p)]
 
 
+class ImageStats(ctypes.Structure):
+    """dxtex_image_stats (include/dxtex_amd.h): Analyze's figures for one image, per channel r, g, b, a."""
+    _fields_ = [("min", ctypes.c_float * 4), ("max", ctypes.c_float * 4), ("avg", ctypes.c_double * 4), ("variance", ctypes.c_double * 4),
+                ("luminance", ctypes.c_float), ("specials", ctypes.c_uint64 * 4)]
+
+
 class Transform(ctypes.Structure):
     """dxtex_transform (include/dxtex_amd.h): one of texconv's per-texel ops for TransformImage."""
     _fields_ = [("op", ctypes.c_uint32), ("swizzle", ctypes.c_uint32 * 4), ("zero", ctypes.c_uint32 * 4), ("one", ctypes.c_uint32 * 4),
@@ -132,6 +138,13 @@ _SIGS = {
     "dxtex_resize": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
     "dxtex_resize_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
     "dxtex_compute_mse_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(ctypes.c_double)]),
+    "dxtex_compute_mse_flags_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, _P(ctypes.c_double)]),
+    "dxtex_analyze": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_size_t, _P(ImageStats)]),
+    "dxtex_analyze_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_size_t, _P(ImageStats)]),
+    "dxtex_analyze_bc": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),
+    "dxtex_analyze_bc_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),
+    "dxtex_difference": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_difference_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_device_alloc": (ctypes.c_int32, [_ctx_p, ctypes.c_size_t, _P(ctypes.c_void_p)]),
     "dxtex_device_free": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p]),
     "dxtex_memcpy_h2d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
@@ -445,6 +458,63 @@ class Context:
         out = (ctypes.c_double * 4)()
         self._check(self._lib.dxtex_compute_mse_device(self._h, ctypes.byref(a), ctypes.byref(b), out), "compute_mse_device")
         return np.array(list(out), np.float64)
+
+    # -- texdiag's diagnostics -------------------------------------------------------------------------
+    def compute_mse_flags_device(self, a, b, flags=0):
+        """dxtex_compute_mse_flags_device: per-channel MSE (4 doubles) of two device Images (device_image) under CMSE_FLAGS."""
+        out = (ctypes.c_double * 4)()
+        self._check(self._lib.dxtex_compute_mse_flags_device(self._h, ctypes.byref(a), ctypes.byref(b), flags, out), "compute_mse_flags_device")
+        return np.array(list(out), np.float64)
+
+    @staticmethod
+    def _stats(s):
+        return {"min": np.array(list(s.min), np.float32), "max": np.array(list(s.max), np.float32), "avg": np.array(list(s.avg), np.float64),
+                "variance": np.array(list(s.variance), np.float64), "luminance": np.float32(s.luminance),
+                "specials": np.array(list(s.specials), np.uint64)}
+
+    def analyze_device(self, images):
+        """dxtex_analyze_device: a list of device Images -> one dict per image (min, max, avg, variance, luminance, specials)."""
+        n = len(images)
+        arr, out = (Image * max(n, 1))(*images), (ImageStats * max(n, 1))()
+        self._check(self._lib.dxtex_analyze_device(self._h, arr, n, out), "analyze_device")
+        return [self._stats(out[i]) for i in range(n)]
+
+    def analyze(self, items):
+        """dxtex_analyze: items = [(pixels, width, height, format, row_pitch or None), ...] in host memory -> one dict per image."""
+        keep = [np.ascontiguousarray(it[0]) for it in items]
+        n = len(items)
+        arr = (Image * max(n, 1))(*[_host_image(k, w, h, f, rp) for k, (_, w, h, f, rp) in zip(keep, items)])
+        out = (ImageStats * max(n, 1))()
+        self._check(self._lib.dxtex_analyze(self._h, arr, n, out), "analyze")
+        return [self._stats(out[i]) for i in range(n)]
+
+    def analyze_bc_device(self, image):
+        """dxtex_analyze_bc_device: a device Image of a BC format -> (the 15 bins as uint64, the number of blocks)."""
+        hist, blocks = (ctypes.c_uint64 * 15)(), ctypes.c_uint64(0)
+        self._check(self._lib.dxtex_analyze_bc_device(self._h, ctypes.byref(image), hist, ctypes.byref(blocks)), "analyze_bc_device")
+        return np.array(list(hist), np.uint64), int(blocks.value)
+
+    def analyze_bc(self, payload, width, height, bc_format, row_pitch=None):
+        """dxtex_analyze_bc of a BC payload in host memory -> (the 15 bins as uint64, the number of blocks)."""
+        payload = np.ascontiguousarray(payload)
+        im = _host_image(payload, width, height, bc_format, row_pitch)
+        hist, blocks = (ctypes.c_uint64 * 15)(), ctypes.c_uint64(0)
+        self._check(self._lib.dxtex_analyze_bc(self._h, ctypes.byref(im), hist, ctypes.byref(blocks)), "analyze_bc")
+        return np.array(list(hist), np.uint64), int(blocks.value)
+
+    def difference_device(self, a, b, dst, diff_color=0, threshold=0.25):
+        """dxtex_difference_device on device Images: b is R32G32B32A32_FLOAT, dst has a's format; asynchronous on the context's stream."""
+        self._check(self._lib.dxtex_difference_device(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(dst), diff_color, threshold), "difference_device")
+
+    def difference(self, a_pixels, b_float, width, height, fmt, diff_color=0, threshold=0.25):
+        """dxtex_difference: host image `a_pixels` of `fmt` against `b_float` (R32G32B32A32_FLOAT) -> the map in `fmt` (tight pitch)."""
+        a_pixels, b_float = np.ascontiguousarray(a_pixels), np.ascontiguousarray(b_float, np.float32)
+        a, b = _host_image(a_pixels, width, height, fmt), _host_image(b_float, width, height, F.DXGI_FORMAT_R32G32B32A32_FLOAT)
+        rp, sp = compute_pitch(fmt, width, height)
+        out = np.zeros(sp, np.uint8)
+        dst = Image(width, height, fmt, rp, sp, out.ctypes.data)
+        self._check(self._lib.dxtex_difference(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(dst), diff_color, threshold), "difference")
+        return out
 
     # -- GenerateMipMaps / Convert / Resize ---------------------------------------------------------
     def generate_mips(self, level0, width, height, fmt, nlevels, filter_flags):

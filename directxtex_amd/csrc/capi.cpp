@@ -6,6 +6,7 @@
 #include "dxtex_kernels.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
+#include "dxtex_diag.h"
 #include "dxtex_plan.h"
 #include "triangle_filter.h"
 
@@ -1583,6 +1584,234 @@ dxtex_hresult dxtex_compute_mse_device(dxtex_ctx* ctx, const dxtex_image* a, con
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const double n = double(a->width) * double(a->height);
     for (int c = 0; c < 4; ++c) mse[c] = sum[c] / n;
+    return DXTEX_S_OK;
+}
+
+// ---- texdiag's diagnostics: Analyze, AnalyzeBC, ComputeMSE with flags, Difference ------------------------------------------------------
+namespace
+{
+// an uncompressed image the scanline layer loads, of a size the kernels index: what all but AnalyzeBC take
+dxtex_hresult check_diag_image(dxtex_ctx* ctx, const dxtex_image& im)
+{
+    if (!im.pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    const FmtInfo* f = format_info(im.format);
+    if (!f || (f->cls & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the diagnostics take uncompressed images of a loadable format (decompress first)");
+    if (im.width > 0xFFFFFFFFull || im.height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    return DXTEX_S_OK;
+}
+
+// the bytes of a host image that the kernels touch (check_host_pitches for one image)
+dxtex_hresult host_image_bytes(dxtex_ctx* ctx, const dxtex_image& im, size_t* bytes)
+{
+    size_t other = 0;
+    return check_host_pitches(ctx, &im, &im, bytes, &other);
+}
+
+// `n` host images into consecutive 256-byte aligned parts of ctx->stageIn: their device twins
+dxtex_hresult stage_inputs(dxtex_ctx* ctx, const dxtex_image* images, size_t n, std::vector<dxtex_image>* staged)
+{
+    std::vector<size_t> bytes(n);
+    for (size_t i = 0; i < n; ++i) { const dxtex_hresult hr = host_image_bytes(ctx, images[i], &bytes[i]); if (hr != DXTEX_S_OK) return hr; }
+    const Arena arena(bytes.data(), n);
+    const dxtex_hresult hr = ctx->stageIn.grow(ctx, arena.total); if (hr != DXTEX_S_OK) return hr;
+    *staged = in_arena(images, n, ctx->stageIn.u8(), arena);
+    for (size_t i = 0; i < n; ++i)
+        HIP_TRY(ctx, counted_copy(ctx, (*staged)[i].pixels, images[i].pixels, bytes[i], hipMemcpyHostToDevice, ctx->stream));
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult check_analyze(dxtex_ctx* ctx, const dxtex_image* images, size_t count, dxtex_image_stats* stats)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!stats) return fail(ctx, DXTEX_E_POINTER, "null result");
+    if (!images || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_hresult hr = check_diag_image(ctx, images[i]); if (hr != DXTEX_S_OK) return hr;
+        if (!images[i].width || !images[i].height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    }
+    return DXTEX_S_OK;
+}
+
+// both passes of every image into one accumulator each, one copy back, then the reference's figures
+dxtex_hresult submit_analyze(dxtex_ctx* ctx, const dxtex_image* images, size_t count, dxtex_image_stats* stats)
+{
+    dxtex_hresult hr = ctx->resultCell.grow(ctx, count * sizeof(AnalyzeAcc)); if (hr != DXTEX_S_OK) return hr;
+    AnalyzeAcc* acc = static_cast<AnalyzeAcc*>(ctx->resultCell.p);
+    hr = run_timed(ctx, [&]
+    {
+        HIP_TRY(ctx, hipMemsetAsync(acc, 0, count * sizeof(AnalyzeAcc), ctx->stream));
+        for (size_t i = 0; i < count; ++i)
+        {
+            const dxtex_hresult hr1 = launched(ctx, launch_analyze(view_of(images[i]), acc + i, ctx->stream, marks_of(ctx)));
+            if (hr1 != DXTEX_S_OK) return hr1;
+        }
+        return DXTEX_S_OK;
+    });
+    if (hr != DXTEX_S_OK) return hr;
+    std::vector<AnalyzeAcc> host(count);
+    HIP_TRY(ctx, counted_copy(ctx, host.data(), acc, count * sizeof(AnalyzeAcc), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < count; ++i)
+    {
+        const double n = double(images[i].width) * double(images[i].height);
+        dxtex_image_stats& s = stats[i];
+        for (int c = 0; c < 4; ++c)
+        {
+            s.min[c] = dg_min_of(host[i].minKeyInv[c]);
+            s.max[c] = dg_max_of(host[i].maxKey[c]);
+            s.avg[c] = host[i].sum[c] / n;
+            s.variance[c] = host[i].variance[c];
+            s.specials[c] = host[i].specials[c];
+        }
+        s.luminance = dg_float(host[i].lumBits);
+    }
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult check_analyze_bc(dxtex_ctx* ctx, const dxtex_image* image, const uint64_t* hist, const uint64_t* blocks)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!hist || !blocks) return fail(ctx, DXTEX_E_POINTER, "null result");
+    if (!image) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    if (!image->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!is_bc(image->format) || !dg_bc_block_bytes(image->format)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "AnalyzeBC takes a block-compressed image");
+    if (image->width > 0xFFFFFFFFull || image->height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    return DXTEX_S_OK;
+}
+
+// the histogram of `image` into hist (device memory, kBcHistBins counters)
+dxtex_hresult submit_bc_hist(dxtex_ctx* ctx, const dxtex_image& image, unsigned long long* hist)
+{
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, kBcHistBins * sizeof(unsigned long long), ctx->stream));
+    return launched(ctx, launch_bc_hist(view_of(image), hist, ctx->stream, marks_of(ctx)));
+}
+uint64_t bc_block_count(const dxtex_image& image) { return uint64_t((image.width + 3) / 4) * uint64_t((image.height + 3) / 4); }
+
+dxtex_hresult check_difference(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!a || !b || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    if (!a->pixels || !b->pixels || !dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (a->width != b->width || a->height != b->height || a->width != dst->width || a->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
+    const dxtex_hresult hr = check_diag_image(ctx, *a); if (hr != DXTEX_S_OK) return hr;
+    if (b->format != FMT_R32G32B32A32_FLOAT) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the second image of Difference must be R32G32B32A32_FLOAT (convert it first)");
+    if (dst->format != a->format) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the difference map has the first image's format");
+    if (b->rowPitch % 16) return fail(ctx, DXTEX_E_INVALIDARG, "the second image's rowPitch must be a multiple of 16 (its rows are read as float4)");
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult submit_difference(dxtex_ctx* ctx, const dxtex_image& a, const dxtex_image& b, const dxtex_image& dst, uint32_t diffColor, float threshold)
+{
+    if (!a.width || !a.height) return DXTEX_S_OK;
+    KernelMarks* marks = marks_of(ctx);
+    const ImgView av = view_of(a), bv = view_of(b);
+    return launch_into(ctx, view_of(dst), marks, [&](const ImgView& out) { return launch_difference(av, bv, out, diffColor & 0xFFFFFFu, threshold, ctx->stream, marks); });
+}
+} // namespace
+
+dxtex_hresult dxtex_compute_mse_flags_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, uint32_t cmse_flags, double mse[4])
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!a || !b) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    if (!a->pixels || !b->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!mse) return fail(ctx, DXTEX_E_POINTER, "null result");
+    if (a->width != b->width || a->height != b->height) return fail(ctx, DXTEX_E_INVALIDARG, "size mismatch");     // DirectXTexMisc.cpp:398
+    dxtex_hresult hr = check_diag_image(ctx, *a); if (hr != DXTEX_S_OK) return hr;
+    hr = check_diag_image(ctx, *b); if (hr != DXTEX_S_OK) return hr;
+    if (!a->width || !a->height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    ScopedDevice sd(ctx->device);
+    hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_mse_flags(view_of(*a), view_of(*b), cmse_flags, static_cast<double*>(ctx->resultCell.p), ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    double sum[4];
+    HIP_TRY(ctx, counted_copy(ctx, sum, ctx->resultCell.p, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const double n = double(a->width) * double(a->height);
+    for (int c = 0; c < 4; ++c) mse[c] = sum[c] / n;
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_analyze_device(dxtex_ctx* ctx, const dxtex_image* images, size_t count, dxtex_image_stats* stats_out)
+{
+    const dxtex_hresult hr = check_analyze(ctx, images, count, stats_out);
+    if (hr != DXTEX_S_OK) return hr;
+    ScopedDevice sd(ctx->device);
+    return submit_analyze(ctx, images, count, stats_out);
+}
+
+dxtex_hresult dxtex_analyze(dxtex_ctx* ctx, const dxtex_image* images, size_t count, dxtex_image_stats* stats_out)
+{
+    dxtex_hresult hr = check_analyze(ctx, images, count, stats_out);
+    if (hr != DXTEX_S_OK) return hr;
+    ScopedDevice sd(ctx->device);
+    std::vector<dxtex_image> staged;
+    hr = stage_inputs(ctx, images, count, &staged);
+    if (hr != DXTEX_S_OK) return hr;
+    return submit_analyze(ctx, staged.data(), count, stats_out);
+}
+
+dxtex_hresult dxtex_analyze_bc_device(dxtex_ctx* ctx, const dxtex_image* image, uint64_t hist[15], uint64_t* blocks)
+{
+    dxtex_hresult hr = check_analyze_bc(ctx, image, hist, blocks);
+    if (hr != DXTEX_S_OK) return hr;
+    ScopedDevice sd(ctx->device);
+    hr = ctx->resultCell.grow(ctx, kBcHistBins * sizeof(unsigned long long)); if (hr != DXTEX_S_OK) return hr;
+    hr = run_timed(ctx, [&] { return submit_bc_hist(ctx, *image, static_cast<unsigned long long*>(ctx->resultCell.p)); });
+    if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, hist, ctx->resultCell.p, kBcHistBins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *blocks = bc_block_count(*image);
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_analyze_bc(dxtex_ctx* ctx, const dxtex_image* image, uint64_t hist[15], uint64_t* blocks)
+{
+    dxtex_hresult hr = check_analyze_bc(ctx, image, hist, blocks);
+    if (hr != DXTEX_S_OK) return hr;
+    size_t bytes = 0;
+    hr = host_image_bytes(ctx, *image, &bytes);
+    if (hr != DXTEX_S_OK) return hr;
+    hr = run_staged(ctx, image->pixels, bytes, hist, kBcHistBins * sizeof(uint64_t),
+                    [&](uint8_t* in, uint8_t* out) { return submit_bc_hist(ctx, with_pixels(*image, in), reinterpret_cast<unsigned long long*>(out)); });
+    if (hr != DXTEX_S_OK) return hr;
+    *blocks = bc_block_count(*image);
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_difference_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, uint32_t diffColor, float threshold)
+{
+    const dxtex_hresult hr = check_difference(ctx, a, b, dst);
+    if (hr != DXTEX_S_OK) return hr;
+    if (reinterpret_cast<uintptr_t>(b->pixels) % 16) return fail(ctx, DXTEX_E_INVALIDARG, "the second image's pixels must be 16-byte aligned");
+    return run_timed(ctx, [&] { return submit_difference(ctx, *a, *b, *dst, diffColor, threshold); });
+}
+
+dxtex_hresult dxtex_difference(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, uint32_t diffColor, float threshold)
+{
+    dxtex_hresult hr = check_difference(ctx, a, b, dst);
+    if (hr != DXTEX_S_OK) return hr;
+    size_t dstBytes = 0;
+    hr = host_image_bytes(ctx, *dst, &dstBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    ScopedDevice sd(ctx->device);
+    const dxtex_image in[2] = { *a, *b };
+    std::vector<dxtex_image> staged;
+    hr = stage_inputs(ctx, in, 2, &staged);
+    if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, dstBytes); if (hr != DXTEX_S_OK) return hr;
+    hr = run_timed(ctx, [&] { return submit_difference(ctx, staged[0], staged[1], with_pixels(*dst, ctx->stageOut.u8()), diffColor, threshold); });
+    if (hr != DXTEX_S_OK) return hr;
+    // only the texels come back: the caller's row padding stays as it was, as with the device form
+    size_t rowBytes = 0, sliceBytes = 0;
+    if (dxtex_compute_pitch(dst->format, dst->width, dst->height, &rowBytes, &sliceBytes) != DXTEX_S_OK) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    if (rowBytes && sliceBytes)
+    {
+        const size_t rows = sliceBytes / rowBytes;
+        ctx->d2hBytes += rowBytes * rows;
+        HIP_TRY(ctx, hipMemcpy2DAsync(dst->pixels, dst->rowPitch, ctx->stageOut.p, dst->rowPitch, rowBytes, rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
 

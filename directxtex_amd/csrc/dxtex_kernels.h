@@ -117,6 +117,28 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
 
 // ComputeMSE: out4 (device) receives the per-channel SUM of squared differences; divide by width * height (a's; b matches it) on the host.
 hipError_t launch_mse(const ImgView& a, const ImgView& b, double* out4, hipStream_t stream, KernelMarks* marks = nullptr);
+// ---- texdiag's diagnostics (diag.hip; the per-texel rules are in dxtex_diag.h) ----
+// Analyze of one image, both passes: *acc (device, zeroed by the caller) receives the raw accumulators; dg_min_of / dg_max_of and a
+// division by width * height turn them into the reference's figures on the host.
+struct AnalyzeAcc
+{
+    uint32_t maxKey[4];                 // max of dg_key(v) over the values that are not NaN; 0 = none
+    uint32_t minKeyInv[4];              // max of ~dg_key(v): the complement of the minimum's key; 0 = none
+    uint32_t lumBits, pad;              // bits of the maximum luminance (+0 or above)
+    double sum[4];                      // pass 1: sum of v
+    double variance[4];                 // pass 2: sum of (v - float(sum / N))^2
+    unsigned long long specials[4];     // values that are not finite
+};
+hipError_t launch_analyze(const ImgView& src, AnalyzeAcc* acc, hipStream_t stream, KernelMarks* marks = nullptr);
+// ComputeMSE with CMSE_FLAGS (the bits the two formats imply are added here): out4 as for launch_mse.
+hipError_t launch_mse_flags(const ImgView& a, const ImgView& b, uint32_t flags, double* out4, hipStream_t stream, KernelMarks* marks = nullptr);
+// AnalyzeBC: hist[kBcHistBins] (device, zeroed by the caller) receives the block-mode histogram of the ceil(w / 4) x ceil(h / 4) blocks.
+constexpr uint32_t kBcHistBins = 15;
+hipError_t launch_bc_hist(const ImgView& src, unsigned long long* hist, hipStream_t stream, KernelMarks* marks = nullptr);
+// Difference's map: a in any loadable format, b in R32G32B32A32_FLOAT (16-byte aligned rows), dst's rows as for launch_normal_map.
+hipError_t launch_difference(const ImgView& a, const ImgView& b, const ImgView& dst, uint32_t diffColor, float threshold, hipStream_t stream,
+                             KernelMarks* marks = nullptr);
+
 // PremultiplyAlpha / DemultiplyAlpha (DirectXTexPMAlpha.cpp:30-205); pmFlags = TEX_PMALPHA_*. Size and format are src's; dst matches them.
 hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream, KernelMarks* marks = nullptr);
 // ScaleAlpha and CalculateAlphaCoverage (DirectXTexMipmaps.cpp:143-305); *count receives the number of covered sub-samples.

@@ -323,6 +323,36 @@ HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const Image* srcImages, siz
 
 HRESULT ComputeMSE(Device& device, const Image& image1, const Image& image2, float& mse, float* mseV) noexcept;
 
+// ---- texdiag's diagnostics (Texdiag/texdiag.cpp: analyze, compare, diff) on the device (DirectXTexAMD_Diag.cpp) ------------------------
+// Every input goes up once; compressed inputs are decompressed there to R32G32B32A32_FLOAT, as the reference's wrappers do
+// (DirectXTexMisc.cpp:409-470, :489-501); only the figures - or Difference's map - come back.
+enum CMSE_FLAGS : uint32_t
+{
+    CMSE_DEFAULT = 0, CMSE_IMAGE1_SRGB = 0x1, CMSE_IMAGE2_SRGB = 0x2, CMSE_IGNORE_RED = 0x10, CMSE_IGNORE_GREEN = 0x20, CMSE_IGNORE_BLUE = 0x40,
+    CMSE_IGNORE_ALPHA = 0x80, CMSE_IMAGE1_X2_BIAS = 0x100, CMSE_IMAGE2_X2_BIAS = 0x200,
+};
+inline CMSE_FLAGS operator|(CMSE_FLAGS a, CMSE_FLAGS b) noexcept { return CMSE_FLAGS(uint32_t(a) | uint32_t(b)); }
+// ComputeMSE with CMSE_FLAGS (DirectXTex.h:1041), accumulated in fp64; the five-argument form above keeps its behaviour
+HRESULT ComputeMSE(Device& device, const Image& image1, const Image& image2, float& mse, float* mseV, CMSE_FLAGS flags) noexcept;
+// texdiag's AnalyzeData (texdiag.cpp:668-696), per channel r, g, b, a; what each figure is: dxtex_image_stats in include/dxtex_amd.h
+struct AnalyzeData
+{
+    float imageMin[4], imageMax[4];
+    double imageAvg[4], imageVariance[4], imageStdDev[4];
+    float luminance;
+    uint64_t specials[4];
+};
+HRESULT Analyze(Device& device, const Image& image, AnalyzeData& result) noexcept;
+// every image of a set (mips, items, slices) in one upload and one read-back: results[nimages]
+HRESULT Analyze(Device& device, const Image* images, size_t nimages, const TexMetadata& metadata, AnalyzeData* results) noexcept;
+// texdiag's AnalyzeBCData (:790-857): blockHist as dxtex_analyze_bc states it
+struct AnalyzeBCData { uint64_t blocks; uint64_t blockHist[15]; };
+HRESULT AnalyzeBC(Device& device, const Image& image, AnalyzeBCData& result) noexcept;
+// Difference (texdiag.cpp:1229-1320): image 2 is converted to R32G32B32A32_FLOAT under dwFilter (so an _SRGB image 2 is linearised and
+// image 1 is not, as there), the map is made in image 1's format (R32G32B32A32_FLOAT if it was compressed) and converted to `format`.
+HRESULT Difference(Device& device, const Image& image1, const Image& image2, TEX_FILTER_FLAGS dwFilter, DXGI_FORMAT format, uint32_t diffColor,
+                   float threshold, ScratchImage& result) noexcept;
+
 // ---- the device-resident pipeline ---------------------------------------------------------------------------------------------------
 // texconv runs resize -> convert -> mipmaps -> compress (Texconv/texconv.cpp:2609, 3109, 3434, 3711) as four ScratchImage -> ScratchImage calls;
 // on a GPU that is four uploads and four downloads around a millisecond of kernels. The reference's own GPU path keeps its intermediate on
@@ -379,6 +409,12 @@ HRESULT Convert(Device& device, const DeviceScratchImage& src, DXGI_FORMAT forma
 HRESULT PremultiplyAlpha(Device& device, const DeviceScratchImage& src, TEX_PMALPHA_FLAGS flags, DeviceScratchImage& result) noexcept;
 HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, DeviceScratchImage& normalMaps) noexcept;
 HRESULT TransformImage(Device& device, const DeviceScratchImage& src, const TexTransform& transform, DeviceScratchImage& result) noexcept;
+// the diagnostics on resident images: image 0 of each side for ComputeMSE and Difference, every image (results[GetImageCount()]) for Analyze / AnalyzeBC
+HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, float& mse, float* mseV, CMSE_FLAGS flags) noexcept;
+HRESULT Analyze(Device& device, const DeviceScratchImage& images, AnalyzeData* results) noexcept;
+HRESULT AnalyzeBC(Device& device, const DeviceScratchImage& images, AnalyzeBCData* results) noexcept;
+HRESULT Difference(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, TEX_FILTER_FLAGS dwFilter, DXGI_FORMAT format,
+                   uint32_t diffColor, float threshold, DeviceScratchImage& result) noexcept;
 // every array item of a mip chain (the per-item loop texconv runs, texconv.cpp:3470-3490); the 10-step bisection per level reads 8 bytes back per step
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const DeviceScratchImage& src, float alphaReference, DeviceScratchImage& mipChain) noexcept;
 // level 0 of every array item / depth slice as a texture with one mip level (what texconv keeps before it regenerates a chain, texconv.cpp:3324-3380)

@@ -23,6 +23,8 @@
  *   TransformImage / EvaluateImage with        DirectXTexMisc.cpp:179-263      dxtex_transform_image
  *     texconv's swizzle, tone-map, colour-key,   texconv.cpp:2645-3301
  *     invert-Y and reconstruct-Z lambdas
+ *   ComputeMSE_ with CMSE_FLAGS                DirectXTexMisc.cpp:27-176       dxtex_compute_mse_flags_device
+ *   texdiag's Analyze / AnalyzeBC / Difference Texdiag/texdiag.cpp:698-1320    dxtex_analyze / dxtex_analyze_bc / dxtex_difference
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -277,6 +279,58 @@ dxtex_hresult dxtex_generate_mips_multi(dxtex_ctx* const* ctxs, size_t nctx, con
 /* ComputeMSE (DirectXTexMisc.cpp:27-176) for two same-size images on the device: per-channel MSE in
  * mse[4] over [0,1] floats. Used for PSNR reporting without a D2H round trip. */
 dxtex_hresult dxtex_compute_mse_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, double mse[4]);
+
+/* ---- texdiag's diagnostics (Texdiag/texdiag.cpp: analyze, compare, diff) ------------------------------------------------------------
+ * All four take uncompressed images of a format the scanline layer loads (decompress first: the host layer does); DXTEX_E_NOT_SUPPORTED
+ * otherwise. Results are read back in one device-to-host copy per call, which synchronises the stream. */
+
+/* CMSE_FLAGS, bit-for-bit (DirectXTex.h:1022-1038). */
+#define DXTEX_CMSE_DEFAULT          0x0u
+#define DXTEX_CMSE_IMAGE1_SRGB      0x1u
+#define DXTEX_CMSE_IMAGE2_SRGB      0x2u
+#define DXTEX_CMSE_IGNORE_RED       0x10u
+#define DXTEX_CMSE_IGNORE_GREEN     0x20u
+#define DXTEX_CMSE_IGNORE_BLUE      0x40u
+#define DXTEX_CMSE_IGNORE_ALPHA     0x80u
+#define DXTEX_CMSE_IMAGE1_X2_BIAS   0x100u
+#define DXTEX_CMSE_IMAGE2_X2_BIAS   0x200u
+/* ComputeMSE_ (DirectXTexMisc.cpp:27-176) with every CMSE_FLAGS bit: v^2.2 on r, g, b of an sRGB image, then v * 2 - 1 under X2_BIAS, the
+ * ignored channels zero; the flags the two formats imply (:47-91) are added. Accumulated in fp64. E_INVALIDARG for a size mismatch. */
+dxtex_hresult dxtex_compute_mse_flags_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, uint32_t cmse_flags, double mse[4]);
+
+/* Analyze (texdiag.cpp:698-787) over LoadScanline's floats, per channel (r, g, b, a). The reference's quirks stay: `variance` is the raw
+ * sum of (v - float(avg))^2, not divided by the texel count (its square root is texdiag's "Std Dev"); luminance is the maximum of
+ * (r * 0.3 + g * 0.59) + b * 0.11, never below 0; min / max start from +FLT_MAX / -FLT_MAX. Stated deviation: a NaN takes no part in min,
+ * max or luminance (the reference's minps / maxps make that depend on texel order) and is only counted in `specials` with the
+ * infinities; -0 orders below +0. min, max, luminance and specials are exact and deterministic; avg and variance are fp64 sums whose
+ * last bits depend on the order workgroups finish in. */
+typedef struct dxtex_image_stats
+{
+    float    min[4], max[4];
+    double   avg[4], variance[4];
+    float    luminance;
+    uint64_t specials[4];
+} dxtex_image_stats;
+/* `count` images (a mip chain, an array, volume slices; formats and sizes may differ), one result each, all read back in one copy.
+ * E_POINTER for null pixels or a null result; E_INVALIDARG for no images, an empty image or one above UINT32_MAX texels a side. */
+dxtex_hresult dxtex_analyze_device(dxtex_ctx* ctx, const dxtex_image* images, size_t count, dxtex_image_stats* stats_out);
+dxtex_hresult dxtex_analyze(dxtex_ctx* ctx, const dxtex_image* images, size_t count, dxtex_image_stats* stats_out);
+
+/* AnalyzeBC (texdiag.cpp:906-1226): the block-mode histogram of one BC image. BC1: hist[0] four-colour, hist[1] three-colour blocks; BC2:
+ * none; BC3 alpha / BC4 red: hist[0] eight-value, hist[1] six-value blocks; BC5: the same for red, hist[2] / hist[3] for green; BC6H:
+ * hist[1..14] by mode, hist[0] reserved prefixes; BC7: hist[0..7] by mode, hist[8] a zero mode byte. *blocks = ceil(w / 4) * ceil(h / 4)
+ * (the reference walks rowPitch / block bytes per row and so counts padding; with tight pitches the two agree).
+ * DXTEX_E_NOT_SUPPORTED for a format that is not block-compressed. */
+dxtex_hresult dxtex_analyze_bc_device(dxtex_ctx* ctx, const dxtex_image* image, uint64_t hist[15], uint64_t* blocks);
+dxtex_hresult dxtex_analyze_bc(dxtex_ctx* ctx, const dxtex_image* image, uint64_t hist[15], uint64_t* blocks);
+
+/* Difference's per-texel map (texdiag.cpp:1285-1309): d = |a - b| on r, g, b with alpha 1; where diffColor (0x00RRGGBB) is not 0 and all
+ * three of d are >= threshold the texel becomes that colour (bytes * 1/255, alpha 1). `b` is R32G32B32A32_FLOAT (texdiag converts image
+ * 2 first; its rowPitch - and, for the device form, its pointer - a multiple of 16, else E_INVALIDARG), `dst` has a's format and size;
+ * stored with StoreScanline's default threshold; row padding of `dst` is not written by either form. E_FAIL for a size mismatch;
+ * DXTEX_E_NOT_SUPPORTED for compressed or unknown formats, b not R32G32B32A32_FLOAT, or dst->format != a->format. */
+dxtex_hresult dxtex_difference_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, uint32_t diffColor, float threshold);
+dxtex_hresult dxtex_difference(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, uint32_t diffColor, float threshold);
 
 /* PremultiplyAlpha / its REVERSE (DirectXTex.h:864-884, DirectXTexPMAlpha.cpp:214-262): same size and format on both sides,
  * the format must carry alpha (else DXTEX_E_NOT_SUPPORTED). `flags` = TEX_PMALPHA_FLAGS. */
