@@ -51,6 +51,11 @@ class Image(ctypes.Structure):
                 ("rowPitch", ctypes.c_size_t), ("slicePitch", ctypes.c_size_t), ("pixels", ctypes.c_void_p)]
 
 
+class Rect(ctypes.Structure):
+    """dxtex_rect / DirectX::Rect: a rectangle of texels."""
+    _fields_ = [("x", ctypes.c_size_t), ("y", ctypes.c_size_t), ("w", ctypes.c_size_t), ("h", ctypes.c_size_t)]
+
+
 class ImageStats(ctypes.Structure):
     """dxtex_image_stats (include/dxtex_amd.h): Analyze's figures for one image, per channel r, g, b, a."""
     _fields_ = [("min", ctypes.c_float * 4), ("max", ctypes.c_float * 4), ("avg", ctypes.c_double * 4), ("variance", ctypes.c_double * 4),
@@ -145,6 +150,10 @@ _SIGS = {
     "dxtex_analyze_bc_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_uint64), _P(ctypes.c_uint64)]),
     "dxtex_difference": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_difference_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_copy_rectangle": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Rect), _P(Image), ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t]),
+    "dxtex_copy_rectangles_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Rect), _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_uint32]),
+    "dxtex_merge_image": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
+    "dxtex_merge_image_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
     "dxtex_device_alloc": (ctypes.c_int32, [_ctx_p, ctypes.c_size_t, _P(ctypes.c_void_p)]),
     "dxtex_device_free": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p]),
     "dxtex_memcpy_h2d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
@@ -514,6 +523,45 @@ class Context:
         out = np.zeros(sp, np.uint8)
         dst = Image(width, height, fmt, rp, sp, out.ctypes.data)
         self._check(self._lib.dxtex_difference(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(dst), diff_color, threshold), "difference")
+        return out
+
+    # -- CopyRectangle and texassemble's merge ---------------------------------------------------------
+    def copy_rectangle(self, src, rect, dst, filter_flags=0, x_offset=0, y_offset=0):
+        """dxtex_copy_rectangle on host Images (their `pixels` point into numpy buffers the caller keeps alive): the w x h texels at
+        rect = (x, y, w, h) of `src` into `dst` at (x_offset, y_offset); returns when the destination's rows have landed."""
+        r = Rect(*rect)
+        self._check(self._lib.dxtex_copy_rectangle(self._h, ctypes.byref(src), ctypes.byref(r), ctypes.byref(dst), filter_flags, x_offset, y_offset), "copy_rectangle")
+
+    def copy_rectangles_device(self, srcs, rects, dsts, x_offsets, y_offsets, filter_flags=0):
+        """dxtex_copy_rectangles_device: lists of device Images, (x, y, w, h) rectangles and offsets, one kernel launch per 32 of them;
+        asynchronous on the context's stream. Each rectangle is checked against its own destination only: the rectangles of one call must
+        not write bytes that another rectangle of the same call reads or writes (they run in one launch, in no order)."""
+        n = len(srcs)
+        m = max(n, 1)
+        a, b = (Image * m)(*srcs), (Image * m)(*dsts)
+        r = (Rect * m)(*[Rect(*q) for q in rects])
+        xs, ys = (ctypes.c_size_t * m)(*x_offsets), (ctypes.c_size_t * m)(*y_offsets)
+        self._check(self._lib.dxtex_copy_rectangles_device(self._h, a, r, b, xs, ys, n, filter_flags), "copy_rectangles_device")
+
+    @staticmethod
+    def _merge_args(permute, zero, one):
+        return (ctypes.c_uint32 * 4)(*permute), (ctypes.c_uint32 * 4)(*zero), (ctypes.c_uint32 * 4)(*one)
+
+    def merge_image_device(self, a, b, dst, permute, zero=(0, 0, 0, 0), one=(0, 0, 0, 0)):
+        """dxtex_merge_image_device on device Images: b is R32G32B32A32_FLOAT, dst has a's format; asynchronous on the context's stream."""
+        p, z, o = self._merge_args(permute, zero, one)
+        self._check(self._lib.dxtex_merge_image_device(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(dst), p, z, o), "merge_image_device")
+
+    def merge_image(self, a_pixels, b_float, width, height, fmt, permute, zero=(0, 0, 0, 0), one=(0, 0, 0, 0)):
+        """dxtex_merge_image: texassemble's merge of host image `a_pixels` of `fmt` with `b_float` (R32G32B32A32_FLOAT): channel k of the
+        result is channel permute[k] of a (0..3) or of b (4..7), then 0 / 1 by the masks -> the merged image in `fmt` (tight pitch)."""
+        a_pixels, b_float = np.ascontiguousarray(a_pixels), np.ascontiguousarray(b_float, np.float32)
+        a, b = _host_image(a_pixels, width, height, fmt), _host_image(b_float, width, height, F.DXGI_FORMAT_R32G32B32A32_FLOAT)
+        rp, sp = compute_pitch(fmt, width, height)
+        out = np.zeros(sp, np.uint8)
+        dst = Image(width, height, fmt, rp, sp, out.ctypes.data)
+        p, z, o = self._merge_args(permute, zero, one)
+        self._check(self._lib.dxtex_merge_image(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(dst), p, z, o), "merge_image")
         return out
 
     # -- GenerateMipMaps / Convert / Resize ---------------------------------------------------------

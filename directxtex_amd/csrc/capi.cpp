@@ -8,6 +8,7 @@
 #include "dxtex_transform.h"
 #include "dxtex_diag.h"
 #include "dxtex_plan.h"
+#include "dxtex_copyrect.h"
 #include "triangle_filter.h"
 
 #include <hip/hip_runtime.h>
@@ -1803,6 +1804,236 @@ dxtex_hresult dxtex_difference(dxtex_ctx* ctx, const dxtex_image* a, const dxtex
     hr = run_timed(ctx, [&] { return submit_difference(ctx, staged[0], staged[1], with_pixels(*dst, ctx->stageOut.u8()), diffColor, threshold); });
     if (hr != DXTEX_S_OK) return hr;
     // only the texels come back: the caller's row padding stays as it was, as with the device form
+    size_t rowBytes = 0, sliceBytes = 0;
+    if (dxtex_compute_pitch(dst->format, dst->width, dst->height, &rowBytes, &sliceBytes) != DXTEX_S_OK) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    if (rowBytes && sliceBytes)
+    {
+        const size_t rows = sliceBytes / rowBytes;
+        ctx->d2hBytes += rowBytes * rows;
+        HIP_TRY(ctx, hipMemcpy2DAsync(dst->pixels, dst->rowPitch, ctx->stageOut.p, dst->rowPitch, rowBytes, rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+// ---- CopyRectangle and texassemble's merge ----------------------------------------------------------------------------------------------
+namespace
+{
+// IsPlanar / IsPalettized (DirectXTexUtil.cpp): with IsCompressed, what CopyRectangle refuses first (:286-289)
+bool copy_refused_format(int f)
+{
+    const bool bc = (f >= 70 && f <= 84) || (f >= 94 && f <= 99);
+    const bool planar = f == 103 || f == 104 || f == 105 || f == 106 || f == 110 || f == 118 || f == 119 || f == 120 || f == 130;     // NV12 P010 P016 420_OPAQUE NV11, Xbox depth planes, P208
+    const bool palettised = f >= 111 && f <= 114;       // AI44 IA44 P8 A8P8
+    return bc || planar || palettised;
+}
+
+// CopyRectangle's checks in its order (DirectXTexMisc.cpp:283-311, :328, :365), then this project's additions; appends the rectangle's job
+// (two where its destination rows overlap each other) to `jobs`.
+dxtex_hresult check_copy_rect(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_rect& r, const dxtex_image& dst, uint32_t filter, size_t xOffset, size_t yOffset,
+                              std::vector<CopyJob>* jobs)
+{
+    if (!src.pixels || !dst.pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (copy_refused_format(src.format) || copy_refused_format(dst.format))
+        return fail(ctx, DXTEX_E_NOT_SUPPORTED, "CopyRectangle does not take compressed, planar or palettised formats");
+    // (written so that no sum wraps: x + w > width  <=>  w > width || x > width - w)
+    if (!r.w || !r.h || r.w > src.width || r.x > src.width - r.w || r.h > src.height || r.y > src.height - r.h)
+        return fail(ctx, DXTEX_E_INVALIDARG, "the rectangle is empty or outside the source");
+    if (r.w > dst.width || xOffset > dst.width - r.w || r.h > dst.height || yOffset > dst.height - r.h)
+        return fail(ctx, DXTEX_E_INVALIDARG, "the rectangle at its offset is outside the destination");
+    const FmtInfo* in = format_info(src.format);
+    const FmtInfo* out = format_info(dst.format);
+    // BitsPerPixel() == 0 (:303-305, :341-343): a value that names no format; below 8 bits: R1_UNORM (:307-311, :345-349)
+    const auto known = [](int f) { return (f >= 1 && f <= 120) || (f >= 130 && f <= 132) || (f >= 189 && f <= 191); };
+    for (const int f : { src.format, dst.format })
+    {
+        if (!known(f)) return fail(ctx, DXTEX_E_INVALIDARG, "unknown format");
+        if (f == FMT_R1_UNORM) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "CopyRectangle does not take R1_UNORM");
+    }
+    if (!in || !out) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "format is not supported by the MI355X path");
+    if (src.width > 0xFFFFFFFFull || src.height > 0xFFFFFFFFull || dst.width > 0xFFFFFFFFull || dst.height > 0xFFFFFFFFull)
+        return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    const bool same = src.format == dst.format;
+    if (!same && ((in->cls | out->cls) & FC_GROUP))
+        return fail(ctx, DXTEX_E_NOT_SUPPORTED, "CopyRectangle between different formats does not take the packed two-texel formats");
+    const uint64_t sbpp = copy_texel_bytes(*in), dbpp = copy_texel_bytes(*out);
+    const uint64_t rowsS = uint64_t(src.height), rowsD = uint64_t(dst.height);
+    if (src.rowPitch > UINT64_MAX / std::max<uint64_t>(1, rowsS) || dst.rowPitch > UINT64_MAX / std::max<uint64_t>(1, rowsD))
+        return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    // the bytes of the last row touched must end inside rowPitch * height on both sides: the reference's E_FAIL (:328, :365), made a
+    // check of the destination's end too (the reference's same-format test, pDest > pEndDest, lets a write run past the image)
+    const uint64_t srcFirst = uint64_t(r.y) * src.rowPitch + uint64_t(r.x) * sbpp, srcLast = srcFirst + uint64_t(r.h - 1) * src.rowPitch + uint64_t(r.w) * sbpp;
+    const uint64_t dstFirst = uint64_t(yOffset) * dst.rowPitch + uint64_t(xOffset) * dbpp, dstLast = dstFirst + uint64_t(r.h - 1) * dst.rowPitch + uint64_t(r.w) * dbpp;
+    if (srcLast > src.rowPitch * rowsS || dstLast > dst.rowPitch * rowsD) return fail(ctx, DXTEX_E_FAIL, "the rectangle's bytes run past the end of an image");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(src.pixels) + srcFirst, s1 = reinterpret_cast<uintptr_t>(src.pixels) + srcLast;
+    const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst.pixels) + dstFirst, d1 = reinterpret_cast<uintptr_t>(dst.pixels) + dstLast;
+    if (s0 < d1 && d0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "source and destination pixels overlap");
+
+    CopyJob j = {};
+    j.srcPitch = src.rowPitch; j.dstPitch = dst.rowPitch;
+    j.height = uint32_t(r.h);
+    j.srcFormat = src.format; j.dstFormat = dst.format;
+    if (same)
+    {
+        j.src = src.pixels + srcFirst; j.dst = dst.pixels + dstFirst;
+        const uint64_t rowBytes = uint64_t(r.w) * sbpp;
+        j.vec = copy_access_bytes(s0, d0, src.rowPitch, dst.rowPitch, j.height);
+        if (rowBytes / j.vec + 16u > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "rectangle too large");      // width + tail (below 16) stays a uint32_t
+        j.width = uint32_t(rowBytes / j.vec); j.tail = uint32_t(rowBytes % j.vec);
+        if (j.height > 1 && rowBytes > dst.rowPitch)
+        {
+            // A row of the packed formats can be longer than the destination's pitch: consecutive rows then write the same bytes, and in the
+            // reference's row-by-row memcpy the later row wins. Row y + 1 covers everything of row y from its pitch on, so every row but the
+            // last moves its first dstPitch bytes only and the last row moves all of its bytes: the same result, with no byte written twice.
+            CopyJob last = j;
+            last.src += uint64_t(j.height - 1) * j.srcPitch; last.dst += uint64_t(j.height - 1) * j.dstPitch;
+            last.height = 1;
+            last.vec = copy_access_bytes(reinterpret_cast<uintptr_t>(last.src), reinterpret_cast<uintptr_t>(last.dst), 0, 0, 1);
+            last.width = uint32_t(rowBytes / last.vec); last.tail = uint32_t(rowBytes % last.vec);
+            j.height -= 1;
+            j.width = uint32_t(dst.rowPitch / j.vec); j.tail = uint32_t(dst.rowPitch % j.vec);
+            jobs->push_back(j);
+            jobs->push_back(last);
+            return DXTEX_S_OK;
+        }
+    }
+    else
+    {
+        j.src = src.pixels + uint64_t(r.y) * src.rowPitch; j.dst = dst.pixels + uint64_t(yOffset) * dst.rowPitch;
+        j.width = uint32_t(r.w); j.sx = uint32_t(r.x); j.dx = uint32_t(xOffset);
+        j.plan = resolve_convert_plan(*in, *out, filter & ~(kFilterDitherOrdered | kFilterDitherDiffusion));      // CopyRectangle never dithers
+    }
+    jobs->push_back(j);
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult check_merge(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t* permute, const uint32_t* zero,
+                          const uint32_t* one, MergeArgs* args)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!a || !b || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    if (!permute || !zero || !one) return fail(ctx, DXTEX_E_POINTER, "null permute / zero / one");
+    if (!a->pixels || !b->pixels || !dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    const dxtex_hresult hr = check_diag_image(ctx, *a); if (hr != DXTEX_S_OK) return hr;
+    if (b->format != FMT_R32G32B32A32_FLOAT) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the second image of a merge must be R32G32B32A32_FLOAT (convert it first)");
+    if (dst->format != a->format) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the merged image has the first image's format");
+    if (a->width != b->width || a->height != b->height || a->width != dst->width || a->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
+    if (b->rowPitch % 16) return fail(ctx, DXTEX_E_INVALIDARG, "the second image's rowPitch must be a multiple of 16 (its rows are read as float4)");
+    MergeArgs m = {};
+    for (int k = 0; k < 4; ++k)
+    {
+        if (permute[k] > 7) return fail(ctx, DXTEX_E_INVALIDARG, "permute index above 7");
+        m.sel[k] = permute[k];
+        if (zero[k]) m.zero |= 1u << k;
+        if (one[k]) m.one |= 1u << k;
+    }
+    if (a->width && a->height)
+    {
+        dxtex_hresult ov = check_no_overlap(ctx, *a, *dst); if (ov != DXTEX_S_OK) return ov;
+        ov = check_no_overlap(ctx, *b, *dst); if (ov != DXTEX_S_OK) return ov;
+    }
+    *args = m;
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult submit_merge(dxtex_ctx* ctx, const dxtex_image& a, const dxtex_image& b, const dxtex_image& dst, const MergeArgs& args)
+{
+    if (!a.width || !a.height) return DXTEX_S_OK;
+    KernelMarks* marks = marks_of(ctx);
+    const ImgView av = view_of(a), bv = view_of(b);
+    return launch_into(ctx, view_of(dst), marks, [&](const ImgView& out) { return launch_merge(av, bv, out, args, ctx->stream, marks); });
+}
+} // namespace
+
+dxtex_hresult dxtex_copy_rectangles_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_rect* rects, const dxtex_image* dsts, const size_t* xOffsets,
+                                           const size_t* yOffsets, size_t count, uint32_t filter)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!srcs || !rects || !dsts || !xOffsets || !yOffsets || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no rectangles");
+    std::vector<CopyJob> jobs;
+    jobs.reserve(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_hresult hr = check_copy_rect(ctx, srcs[i], rects[i], dsts[i], filter, xOffsets[i], yOffsets[i], &jobs);
+        if (hr != DXTEX_S_OK) return hr;
+    }
+    return run_timed(ctx, [&] { return launched(ctx, launch_copy_rects(jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_copy_rectangle(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_rect* rect, const dxtex_image* dst, uint32_t filter, size_t xOffset, size_t yOffset)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src || !rect || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image or rectangle");
+    std::vector<CopyJob> host, jobs;
+    dxtex_hresult hr = check_copy_rect(ctx, *src, *rect, *dst, filter, xOffset, yOffset, &host);
+    if (hr != DXTEX_S_OK) return hr;
+    // Only the rectangle travels: its rows go up into a tight image in the staging, the same rectangle of a tight destination comes back
+    // into the caller's rows. (Nothing else of the caller's destination is read or written, so its other bytes stay as they were.)
+    const FmtInfo* in = format_info(src->format);
+    const FmtInfo* out = format_info(dst->format);
+    const size_t sbpp = copy_texel_bytes(*in), dbpp = copy_texel_bytes(*out);
+    const size_t upRow = rect->w * sbpp, downRow = rect->w * dbpp;
+    dxtex_image s = *src, d = *dst;
+    s.width = d.width = rect->w; s.height = d.height = rect->h;
+    s.rowPitch = upRow; d.rowPitch = downRow;
+    s.slicePitch = upRow * rect->h; d.slicePitch = downRow * rect->h;
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, s.slicePitch); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, d.slicePitch); if (hr != DXTEX_S_OK) return hr;
+    s.pixels = ctx->stageIn.u8(); d.pixels = ctx->stageOut.u8();
+    const dxtex_rect whole = { 0, 0, rect->w, rect->h };
+    hr = check_copy_rect(ctx, s, whole, d, filter, 0, 0, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    // rows of `width` bytes between a host image and its tight copy in the staging. A row of the packed formats can be longer than the
+    // host image's pitch (see check_copy_rect): those rows travel one by one, in order, so that the later row wins as in the reference.
+    const auto rows_copy = [&](uint8_t* to, size_t toPitch, const uint8_t* from, size_t fromPitch, size_t width, hipMemcpyKind kind) -> hipError_t
+    {
+        if (width <= toPitch && width <= fromPitch) return hipMemcpy2DAsync(to, toPitch, from, fromPitch, width, rect->h, kind, ctx->stream);
+        for (size_t y = 0; y < rect->h; ++y)
+        {
+            const hipError_t e = hipMemcpyAsync(to + y * toPitch, from + y * fromPitch, width, kind, ctx->stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    ctx->h2dBytes += upRow * rect->h;
+    HIP_TRY(ctx, rows_copy(s.pixels, upRow, src->pixels + rect->y * src->rowPitch + rect->x * sbpp, src->rowPitch, upRow, hipMemcpyHostToDevice));
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_copy_rects(jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    ctx->d2hBytes += downRow * rect->h;
+    HIP_TRY(ctx, rows_copy(dst->pixels + yOffset * dst->rowPitch + xOffset * dbpp, dst->rowPitch, d.pixels, downRow, downRow, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_merge_image_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4],
+                                       const uint32_t zero[4], const uint32_t one[4])
+{
+    MergeArgs args;
+    const dxtex_hresult hr = check_merge(ctx, a, b, dst, permute, zero, one, &args);
+    if (hr != DXTEX_S_OK) return hr;
+    if (reinterpret_cast<uintptr_t>(b->pixels) % 16) return fail(ctx, DXTEX_E_INVALIDARG, "the second image's pixels must be 16-byte aligned");
+    return run_timed(ctx, [&] { return submit_merge(ctx, *a, *b, *dst, args); });
+}
+
+dxtex_hresult dxtex_merge_image(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4], const uint32_t zero[4],
+                                const uint32_t one[4])
+{
+    MergeArgs args;
+    dxtex_hresult hr = check_merge(ctx, a, b, dst, permute, zero, one, &args);
+    if (hr != DXTEX_S_OK) return hr;
+    size_t dstBytes = 0;
+    hr = host_image_bytes(ctx, *dst, &dstBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    ScopedDevice sd(ctx->device);
+    const dxtex_image in[2] = { *a, *b };
+    std::vector<dxtex_image> staged;
+    hr = stage_inputs(ctx, in, 2, &staged);
+    if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, dstBytes); if (hr != DXTEX_S_OK) return hr;
+    hr = run_timed(ctx, [&] { return submit_merge(ctx, staged[0], staged[1], with_pixels(*dst, ctx->stageOut.u8()), args); });
+    if (hr != DXTEX_S_OK) return hr;
+    // only the texels come back, as with dxtex_difference: the caller's row padding stays as it was
     size_t rowBytes = 0, sliceBytes = 0;
     if (dxtex_compute_pitch(dst->format, dst->width, dst->height, &rowBytes, &sliceBytes) != DXTEX_S_OK) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
     if (rowBytes && sliceBytes)

@@ -85,6 +85,14 @@ hipError_t launch_transform(const ImgView& src, const ImgView& dst, uint32_t op,
                             KernelMarks* marks = nullptr);
 hipError_t launch_tonemap_max(const ImgView& src, uint32_t* maxBits, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
+// texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
+// launch_normal_map; the size is a's.
+struct CopyJob;
+struct MergeArgs;
+hipError_t launch_copy_rects(const CopyJob* jobs, size_t count, hipStream_t stream, KernelMarks* marks = nullptr);
+hipError_t launch_merge(const ImgView& a, const ImgView& b, const ImgView& dst, const MergeArgs& args, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // Resize / one mip level: src is filtered (as src.format) into dst, whose rows are written in dst.format (R32G32B32A32_FLOAT rows for
 // launch_pack_group, src.format otherwise). filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row

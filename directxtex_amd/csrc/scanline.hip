@@ -10,6 +10,8 @@
 //   ComputeNMap (DirectXTexNormalMaps.cpp:77-240)                          nmap_kernel
 //   TransformImage / EvaluateImage (DirectXTexMisc.cpp:179-263) with       transform_kernel<op>, tonemap_max_kernel
 //     texconv's swizzle / tone-map / colour-key / invert-Y / reconstruct-Z lambdas
+//   CopyRectangle (DirectXTexMisc.cpp:275-381)                             copy_rect_kernel (a batch of rectangles per launch)
+//   texassemble's merge lambda (Texassemble/texassemble.cpp:2236-2268)     merge_kernel
 //
 // The reference walks scanlines through a float4 row buffer (LoadScanline -> filter -> StoreScanline). Here every
 // lane owns one destination texel and reads the source texels it needs straight from HBM/L2 with LoadScanline's
@@ -24,6 +26,7 @@
 #include "cubic_filter.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
+#include "dxtex_copyrect.h"
 #include <algorithm>
 
 namespace dxtex
@@ -355,6 +358,84 @@ __global__ void __launch_bounds__(256) tonemap_max_kernel(ImgView src, uint32_t*
     {
         m = max(max(waveMax[0], waveMax[1]), max(waveMax[2], waveMax[3]));
         if (m) atomicMax(maxBits, m);
+    }
+}
+
+// ---- CopyRectangle (DirectXTexMisc.cpp:275-381) ------------------------------------------------------------------------------------
+// A batch of rectangles in one launch: blockIdx.z picks the job from the argument block, blockIdx.x the 256 columns (accesses of the
+// mover, texels of the converting route), blockIdx.y the first group of rows; the grid is sized for the largest job and a workgroup
+// outside its own job's extent leaves at once. Both routes are pure streaming. Nothing outside the rectangle is written.
+//
+// The mover keeps ROWS accesses of consecutive rows in flight per lane before the first store (as convert_quad_kernel does, and for the
+// same reason: one 16-byte load per lane is bound by latency, not by HBM). T is the access type of the job's `vec`.
+template<typename T, int ROWS>
+__device__ __forceinline__ void copy_rect_move(const CopyJob& j, uint32_t u)
+{
+    const uint64_t at = uint64_t(u) * sizeof(T);
+    for (uint32_t y0 = blockIdx.y * uint32_t(ROWS); y0 < j.height; y0 += gridDim.y * uint32_t(ROWS))
+    {
+        T v[ROWS];
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+        {
+            const uint32_t y = min(y0 + uint32_t(r), j.height - 1u);      // a short last group re-reads the last row (and does not store it)
+            v[r] = *reinterpret_cast<const T*>(j.src + uint64_t(y) * j.srcPitch + at);
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r)
+            if (y0 + uint32_t(r) < j.height) *reinterpret_cast<T*>(j.dst + uint64_t(y0 + uint32_t(r)) * j.dstPitch + at) = v[r];
+    }
+}
+
+__global__ void __launch_bounds__(256) copy_rect_kernel(CopyBatch batch)
+{
+    const CopyJob& j = batch.job[blockIdx.z];
+    const uint32_t u = blockIdx.x * 256u + threadIdx.x;
+    if (j.vec == 0u)
+    {
+        // different formats: convert_kernel's texel, from texel sx + u of the source row to texel dx + u of the destination row
+        if (u >= j.width) return;
+        for (uint32_t y = blockIdx.y; y < j.height; y += gridDim.y)
+        {
+            const Texel t = load_texel(j.src + uint64_t(y) * j.srcPitch, j.sx + u, j.srcFormat);
+            store_converted<false>(j.dst + uint64_t(y) * j.dstPitch, j.dx + u, j.dstFormat, apply_plan(t, j.plan), 0.0f, CONVERT_DITHER_NONE, 0u, 0u, 0u);
+        }
+        return;
+    }
+    if (u < j.width)
+    {
+        switch (j.vec)
+        {
+        case 16u: copy_rect_move<uint4, 4>(j, u); break;
+        case 8u: copy_rect_move<uint2, 4>(j, u); break;
+        case 4u: copy_rect_move<uint32_t, 4>(j, u); break;
+        case 2u: copy_rect_move<uint16_t, 4>(j, u); break;
+        default: copy_rect_move<uint8_t, 4>(j, u); break;
+        }
+    }
+    else if (u - j.width < j.tail)
+    {
+        // what a row holds after its whole accesses: byte by byte, by the lanes that follow them
+        const uint64_t at = uint64_t(j.width) * j.vec + (u - j.width);
+        for (uint32_t y = blockIdx.y; y < j.height; y += gridDim.y) j.dst[uint64_t(y) * j.dstPitch + at] = j.src[uint64_t(y) * j.srcPitch + at];
+    }
+}
+
+// ---- texassemble's merge (Texassemble/texassemble.cpp:2236-2268) --------------------------------------------------------------------
+// TransformImage over image 1 with a lambda that also reads image 2 (converted to R32G32B32A32_FLOAT by the caller, as texassemble does):
+// transform_kernel's shape with a second source. b's rows are read as float4 (16-byte aligned: the launcher checks).
+__global__ void __launch_bounds__(256) merge_kernel(ImgView a, ImgView b, ImgView dst, MergeArgs m)
+{
+    const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+    if (x >= a.width) return;
+    for (uint32_t y = blockIdx.y; y < a.height; y += gridDim.y)
+    {
+        const Texel t = load_texel(a.pixels + uint64_t(y) * a.rowPitch, x, a.format);
+        const float4 o = reinterpret_cast<const float4*>(b.pixels + uint64_t(y) * b.rowPitch)[x];
+        const float ca[4] = { t.r, t.g, t.b, t.a }, cb[4] = { o.x, o.y, o.z, o.w };
+        float c[4];
+        merge_texel(ca, cb, m, c);
+        store_texel(dst.pixels + uint64_t(y) * dst.rowPitch, x, dst.format, Texel{ c[0], c[1], c[2], c[3] });
     }
 }
 
@@ -1203,6 +1284,46 @@ hipError_t launch_transform(const ImgView& sv, const ImgView& dv, uint32_t op, c
     default: return hipErrorInvalidValue;
     }
 #undef DXTEX_XFORM
+    DXTEX_MARK(nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_copy_rects(const CopyJob* jobs, size_t count, hipStream_t stream, KernelMarks* marks)
+{
+    for (size_t first = 0; first < count; first += kCopyBatchMax)
+    {
+        CopyBatch batch;
+        batch.count = uint32_t(std::min<size_t>(kCopyBatchMax, count - first));
+        uint32_t units = 0, rows = 0;
+        for (uint32_t k = 0; k < batch.count; ++k)
+        {
+            const CopyJob& j = jobs[first + k];
+            batch.job[k] = j;
+            units = std::max(units, j.width + (j.vec ? j.tail : 0u));
+            rows = std::max(rows, j.vec ? (j.height + 3u) / 4u : j.height);
+        }
+        for (uint32_t k = batch.count; k < kCopyBatchMax; ++k) batch.job[k] = CopyJob{};
+        if (!units || !rows) continue;
+        // about 8192 workgroups over the batch, as convert_quad launches: a lane streams several row groups rather than one workgroup per row
+        const uint32_t gx = (units + 255u) / 256u;
+        const uint32_t gy = std::min<uint32_t>(grid_rows(rows), std::max<uint32_t>(1u, 8192u / (gx * batch.count)));
+        DXTEX_MARK("copy_rect");
+        hipLaunchKernelGGL(copy_rect_kernel, dim3(gx, gy, batch.count), dim3(256), 0, stream, batch);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    DXTEX_MARK(nullptr);
+    return hipSuccess;
+}
+
+hipError_t launch_merge(const ImgView& a, const ImgView& b, const ImgView& dst, const MergeArgs& args, hipStream_t stream, KernelMarks* marks)
+{
+    if (!a.width || !a.height) return hipSuccess;
+    if (b.format != FMT_R32G32B32A32_FLOAT || ((reinterpret_cast<uintptr_t>(b.pixels) | b.rowPitch) & 15u)) return hipErrorInvalidValue;
+    const uint32_t gx = (a.width + 255) / 256;
+    const dim3 grid(gx, std::min<uint32_t>(grid_rows(a.height), std::max<uint32_t>(1u, 8192u / gx)));
+    DXTEX_MARK("merge");
+    hipLaunchKernelGGL(merge_kernel, grid, dim3(256), 0, stream, a, b, dst, args);
     DXTEX_MARK(nullptr);
     return hipGetLastError();
 }

@@ -423,6 +423,47 @@ HRESULT CopyTopLevels(Device& device, const DeviceScratchImage& src, DeviceScrat
 // device-resident images of one format (e.g. the top levels of a chain).
 bool IsAlphaAllOpaque(Device& device, const DeviceScratchImage& image) noexcept;
 bool IsAlphaAllOpaque(Device& device, const Image* deviceImages, size_t nimages) noexcept;
+// ---- CopyRectangle and texassemble's steps (DirectXTexAMD_Assemble.cpp) -----------------------------------------------------------------
+struct Rect
+{
+    size_t x = 0, y = 0, w = 0, h = 0;
+    Rect() = default;
+    Rect(size_t _x, size_t _y, size_t _w, size_t _h) noexcept : x(_x), y(_y), w(_w), h(_h) {}
+};
+// CopyRectangle (DirectXTex.h:1018-1020, DirectXTexMisc.cpp:275-381) with the device in front: host images, only the rectangle's rows travel
+HRESULT CopyRectangle(Device& device, const Image& srcImage, const Rect& srcRect, const Image& dstImage, TEX_FILTER_FLAGS filter, size_t xOffset, size_t yOffset) noexcept;
+// the same between images resident on the device (src and dst must differ or not overlap): queued on the Device's stream
+HRESULT CopyRectangle(Device& device, const DeviceScratchImage& src, size_t srcMip, size_t srcItem, size_t srcSlice, const Rect& srcRect,
+                      const DeviceScratchImage& dst, size_t dstMip, size_t dstItem, size_t dstSlice, TEX_FILTER_FLAGS filter, size_t xOffset, size_t yOffset) noexcept;
+// texassemble's merge (Texassemble/texassemble.cpp:2236-2268): image 2 is converted to R32G32B32A32_FLOAT under `filter`, channel k of the
+// result is channel permute[k] of image 1 (0..3) or of image 2 (4..7), then 0 where zero[k], then 1 where one[k]; the result has image 1's format
+HRESULT MergeImages(Device& device, const Image& image1, const Image& image2, TEX_FILTER_FLAGS filter, const uint32_t permute[4], const bool zero[4],
+                    const bool one[4], ScratchImage& result) noexcept;
+
+// Where texassemble puts the six cube faces (+X -X +Y -Y +Z -Z) in a cross, tee or strip (texassemble.cpp:2040-2181): a grid of
+// cols x rows faces and each face's cell. The tables are data: tests/golden/assemble_layouts.json holds the same numbers.
+enum CROSS_KIND : uint32_t { CROSS_H_CROSS = 0, CROSS_V_CROSS, CROSS_H_TEE, CROSS_H_STRIP, CROSS_V_STRIP, CROSS_KIND_COUNT };
+struct CrossLayout { const char* name; size_t cols, rows; size_t x[6], y[6]; };
+const CrossLayout* GetCrossLayout(CROSS_KIND kind) noexcept;
+// The assemble steps on resident images; every one is ONE copy_rect launch per 32 rectangles. Mip 0 only, as in texassemble.
+// faces: at least six array items of one size -> a cols * w x rows * h image of their format, background zero
+HRESULT AssembleCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& faces, DeviceScratchImage& result) noexcept;
+// the reverse (cube-from-hc ...): an image whose size is a whole number of cells -> a cubemap of six faces
+HRESULT CubeFromCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& image, DeviceScratchImage& cube) noexcept;
+// array-strip: the array items of `items` stacked top to bottom in one image
+HRESULT AssembleStrip(Device& device, const DeviceScratchImage& items, DeviceScratchImage& result) noexcept;
+// whole images, pairwise, between device-resident images (src[i] into dst[i] at (0, 0); sizes of a pair must agree, formats may differ)
+HRESULT CopyImages(Device& device, const Image* srcDeviceImages, const Image* dstDeviceImages, size_t count, TEX_FILTER_FLAGS filter = TEX_FILTER_DEFAULT) noexcept;
+// cube / array / cubearray: `count` device-resident images of one size and format as the items of one array (asCube: a cubemap, count a
+// multiple of six); volume: as the slices of one volume
+HRESULT StackArray(Device& device, const Image* deviceImages, size_t count, bool asCube, DeviceScratchImage& result) noexcept;
+HRESULT StackVolume(Device& device, const Image* deviceImages, size_t count, DeviceScratchImage& result) noexcept;
+// merge on resident images (image 0 of each side); image 2 is converted on the device
+HRESULT MergeImages(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, TEX_FILTER_FLAGS filter, const uint32_t permute[4],
+                    const uint32_t zero[4], const uint32_t one[4], DeviceScratchImage& result) noexcept;
+// texassemble's ParseSwizzleMask (texassemble.cpp:662-790): 1 to 4 of rgbaxyzw (image 1), RGBAXYZW (image 2), 0, 1; the last repeats
+bool ParseMergeMask(const char* mask, uint32_t permute[4], uint32_t zero[4], uint32_t one[4]) noexcept;
+
 // bytes moved between host and device for this Device since the last reset (see dxtex_ctx_transfer_bytes)
 void GetTransferBytes(Device& device, uint64_t& hostToDevice, uint64_t& deviceToHost, bool reset = false) noexcept;
 } // namespace DirectXTexAMD

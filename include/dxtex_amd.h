@@ -25,6 +25,8 @@
  *     invert-Y and reconstruct-Z lambdas
  *   ComputeMSE_ with CMSE_FLAGS                DirectXTexMisc.cpp:27-176       dxtex_compute_mse_flags_device
  *   texdiag's Analyze / AnalyzeBC / Difference Texdiag/texdiag.cpp:698-1320    dxtex_analyze / dxtex_analyze_bc / dxtex_difference
+ *   CopyRectangle                              DirectXTexMisc.cpp:275-381      dxtex_copy_rectangle / dxtex_copy_rectangles_device
+ *   texassemble's merge lambda                 Texassemble/texassemble.cpp:2236-2268  dxtex_merge_image
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -331,6 +333,45 @@ dxtex_hresult dxtex_analyze_bc(dxtex_ctx* ctx, const dxtex_image* image, uint64_
  * DXTEX_E_NOT_SUPPORTED for compressed or unknown formats, b not R32G32B32A32_FLOAT, or dst->format != a->format. */
 dxtex_hresult dxtex_difference_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, uint32_t diffColor, float threshold);
 dxtex_hresult dxtex_difference(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, uint32_t diffColor, float threshold);
+
+/* ---- CopyRectangle and texassemble's merge ---------------------------------------------------------------------------------------- */
+
+/* Mirrors DirectX::Rect (DirectXTex.h). */
+typedef struct dxtex_rect { size_t x, y, w, h; } dxtex_rect;
+
+/* CopyRectangle (DirectXTexMisc.cpp:275-381): the w x h texels at (x, y) of src into dst at (xOffset, yOffset).
+ *   Same format: the rows' bytes are moved as the reference's memcpy moves them, a texel counting BitsPerPixel / 8 bytes - for the packed
+ *   two-texel formats (R8G8_B8G8, G8R8_G8B8, YUY2: 4; Y210, Y216: 8) that is an element of two texels, so a row of the rectangle runs
+ *   into the image's next row, there as here; where consecutive rows then write the same destination bytes, the later row's are the
+ *   ones that stay, as after the reference's row-by-row memcpy.
+ *   Different formats: LoadScanline -> ConvertScanline(filter) -> StoreScanline with its default threshold; never dithered (the dither
+ *   bits of `filter` are ignored). Stated deviation: the packed two-texel formats are refused on this route (DXTEX_E_NOT_SUPPORTED); the
+ *   reference pairs texels from the rectangle's left edge, whatever the parity of x.
+ * Bytes of dst outside the rectangle, row padding included, are not written.
+ * HRESULTs, in the reference's order (:283-311): E_POINTER for null pixels; DXTEX_E_NOT_SUPPORTED for compressed, planar and palettised
+ * formats; E_INVALIDARG for an empty rectangle, one outside src, or one that at its offset is outside dst, and for a value that names no
+ * format; DXTEX_E_NOT_SUPPORTED for R1_UNORM; E_FAIL where the rectangle's bytes run past rowPitch * height of either image (the
+ * reference tests the source's end and, between different formats, the destination's). Added here: DXTEX_E_NOT_SUPPORTED for formats the
+ * scanline layer does not load (typeless ones among them), E_INVALIDARG where the bytes read and the bytes written overlap.
+ * dxtex_copy_rectangle: host pointers; uploads the rectangle's rows only and downloads the rows it wrote only.
+ * dxtex_copy_rectangles_device: `count` independent rectangles on device memory, asynchronous on the context's stream, ONE kernel launch
+ * per 32 rectangles (the jobs travel in the kernel's argument block). All are checked before anything is queued. Rectangles of one
+ * call must not write bytes another one of the call reads or writes. */
+dxtex_hresult dxtex_copy_rectangle(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_rect* rect, const dxtex_image* dst, uint32_t filter,
+                                   size_t xOffset, size_t yOffset);
+dxtex_hresult dxtex_copy_rectangles_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_rect* rects, const dxtex_image* dsts,
+                                           const size_t* xOffsets, const size_t* yOffsets, size_t count, uint32_t filter);
+
+/* texassemble's merge (Texassemble/texassemble.cpp:2236-2268): per texel out[k] = (permute[k] < 4 ? a : b)[permute[k] & 3] (XMVectorPermute),
+ * then 0 where zero[k], then 1 where one[k]; a through LoadScanline, `b` R32G32B32A32_FLOAT (texassemble converts image 2 first; its
+ * rowPitch - and, for the device form, its pointer - a multiple of 16, else E_INVALIDARG); stored in a's format with StoreScanline's
+ * default threshold. Channels are moved, never computed. dst has a's format and size; its row padding is not written by either form.
+ * E_INVALIDARG for a permute index above 7 or overlapping pixels; E_FAIL for a size mismatch; DXTEX_E_NOT_SUPPORTED for compressed or
+ * unknown formats, b not R32G32B32A32_FLOAT, or dst->format != a->format. */
+dxtex_hresult dxtex_merge_image(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4],
+                                const uint32_t zero[4], const uint32_t one[4]);
+dxtex_hresult dxtex_merge_image_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4],
+                                       const uint32_t zero[4], const uint32_t one[4]);
 
 /* PremultiplyAlpha / its REVERSE (DirectXTex.h:864-884, DirectXTexPMAlpha.cpp:214-262): same size and format on both sides,
  * the format must carry alpha (else DXTEX_E_NOT_SUPPORTED). `flags` = TEX_PMALPHA_FLAGS. */
