@@ -1315,7 +1315,7 @@ dxtex_hresult check_no_overlap(dxtex_ctx* ctx, const dxtex_image& src, const dxt
 }
 
 // ComputeNormalMap's checks (DirectXTexNormalMaps.cpp:257-283, ComputeNMap :83-94), in its order; the destination's class decides the
-// encoding. Formats format_info() does not know (the ones GetConvertFlags has no entry for among them) are not supported here.
+// encoding. Formats format_info() does not know (GetConvertFlags has no entry for any of them) are not supported here.
 dxtex_hresult check_normal_map(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags, bool* unorm)
 {
     if (!ctx) return DXTEX_E_POINTER;
@@ -1364,7 +1364,7 @@ dxtex_hresult dxtex_compute_normal_map(dxtex_ctx* ctx, const dxtex_image* src, c
 namespace
 {
 // TransformImage's checks (DirectXTexMisc.cpp:606-700), in its order, over `count` source / destination pairs of one format; resolves what
-// the kernel needs of the descriptor. The four Xbox-only formats and everything else format_info() does not know are not supported.
+// the kernel needs of the descriptor. Formats format_info() does not know are not supported.
 dxtex_hresult check_transform(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, const dxtex_transform* t, XformArgs* args)
 {
     if (!ctx) return DXTEX_E_POINTER;

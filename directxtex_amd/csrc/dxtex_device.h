@@ -51,6 +51,8 @@ enum : int
     FMT_BC7_UNORM = 98, FMT_BC7_UNORM_SRGB = 99,
     FMT_AYUV = 100, FMT_Y410 = 101, FMT_Y416 = 102, FMT_YUY2 = 107, FMT_Y210 = 108, FMT_Y216 = 109,
     FMT_B4G4R4A4_UNORM = 115,
+    FMT_R10G10B10_7E3_A2_FLOAT = 116, FMT_R10G10B10_6E4_A2_FLOAT = 117,       // XBOX_DXGI_FORMAT_*: the console HDR formats
+    FMT_R10G10B10_SNORM_A2_UNORM = 189, FMT_R4G4_UNORM = 190,                 // XBOX_DXGI_FORMAT_*
     FMT_A4B4G4R4_UNORM = 191,
 };
 
@@ -116,6 +118,35 @@ __device__ __forceinline__ float load_float11(uint32_t bits, int MB)
         mant &= (1u << MB) - 1u;
     }
     return __uint_as_float(((expo + 112u) << 23) | (mant << (23 - MB)));
+}
+
+// FloatFrom7e3 / FloatFrom6e4 (DirectXTexConvert.cpp:54-86, :121-153): a 10-bit unsigned float with MB mantissa bits (7 or 6) and
+// 10 - MB exponent bits (bias 3 or 7) widened to fp32. Denormals are normalised, zero stays zero, and the top exponent is an ordinary
+// one: the formats have no infinity and no NaN. __host__ __device__ so that tests/cpp/xbox_check.cpp can sweep every code.
+__host__ __device__ inline float float_from_small10(uint32_t bits, int MB)
+{
+    uint32_t mant = bits & ((1u << MB) - 1u);
+    uint32_t expo = (bits & 0x3FFu) >> MB;
+    if (expo == 0)
+    {
+        if (mant == 0) return 0.0f;
+        const uint32_t n = uint32_t(MB) - (31u - uint32_t(__builtin_clz(mant)));       // the reference's normalising loop runs n times:
+        expo = 1u - n;                                                                  // Exponent-- and Mantissa <<= 1 until bit MB is set
+        mant = (mant << n) & ((1u << MB) - 1u);
+    }
+    union { uint32_t u; float f; } c;
+    c.u = ((expo + ((MB == 7) ? 124u : 120u)) << 23) | (mant << (23 - MB));
+    return c.f;
+}
+__host__ __device__ inline float float_from_7e3(uint32_t bits) { return float_from_small10(bits, 7); }
+__host__ __device__ inline float float_from_6e4(uint32_t bits) { return float_from_small10(bits, 6); }
+
+// One R10G10B10_7E3_A2_FLOAT / R10G10B10_6E4_A2_FLOAT texel (:1543-1589). Alpha is a true division (:1556, :1580), unlike XMLoadUDecN4's
+// multiply by float(1/3).
+__host__ __device__ inline void unpack_small10_a2(uint32_t v, int MB, float& r, float& g, float& b, float& a)
+{
+    r = float_from_small10(v & 0x3FFu, MB); g = float_from_small10((v >> 10) & 0x3FFu, MB); b = float_from_small10((v >> 20) & 0x3FFu, MB);
+    a = float(v >> 30) / 3.0f;
 }
 
 // XMLoadUInt4 / XMConvertVectorUIntToFloat, SSE2 path: cvtdq2ps of the low 31 bits, + 2^31 if the top bit was set
@@ -327,6 +358,24 @@ __device__ __forceinline__ Texel load_texel(const uint8_t* row, uint32_t x, int 
         // XMLoadUNibble4 * 1/15, swizzled <3, 2, 1, 0> (:1527-1541)
         const uint32_t v = reinterpret_cast<const uint16_t*>(row)[x];
         t.a = float(v & 0xFu) * (1.0f / 15.0f); t.b = float((v >> 4) & 0xFu) * (1.0f / 15.0f); t.g = float((v >> 8) & 0xFu) * (1.0f / 15.0f); t.r = float(v >> 12) * (1.0f / 15.0f);
+        break;
+    }
+    // ---- the Xbox formats (:1543-1612)
+    case FMT_R10G10B10_7E3_A2_FLOAT: unpack_small10_a2(reinterpret_cast<const uint32_t*>(row)[x], 7, t.r, t.g, t.b, t.a); break;
+    case FMT_R10G10B10_6E4_A2_FLOAT: unpack_small10_a2(reinterpret_cast<const uint32_t*>(row)[x], 6, t.r, t.g, t.b, t.a); break;
+    case FMT_R10G10B10_SNORM_A2_UNORM:
+    {
+        // XMLoadXDecN4 (:1591-1593): sign-extended fields * (1/511), then max with -1 (the -512 code); alpha * (1/3)
+        const uint32_t v = reinterpret_cast<const uint32_t*>(row)[x];
+        t.r = fmaxf(float(int32_t(v << 22) >> 22) * (1.0f / 511.0f), -1.0f); t.g = fmaxf(float(int32_t(v << 12) >> 22) * (1.0f / 511.0f), -1.0f);
+        t.b = fmaxf(float(int32_t(v << 2) >> 22) * (1.0f / 511.0f), -1.0f); t.a = float(v >> 30) * (1.0f / 3.0f);
+        break;
+    }
+    case FMT_R4G4_UNORM:
+    {
+        // XMLoadUNibble4 of the byte * (1/15, 1/15, 0, 0), z and w from g_XMIdentityR3 (:1595-1612)
+        const uint32_t v = row[x];
+        t.r = float(v & 0xFu) * (1.0f / 15.0f); t.g = float(v >> 4) * (1.0f / 15.0f); t.b = 0.0f; t.a = 1.0f;
         break;
     }
     // ---- integer formats: the VALUE as a float, not normalised. XMLoadUInt* (SSE2): the low 31 bits through cvtdq2ps (round to

@@ -68,7 +68,8 @@ __host__ __device__ inline void spec_pack(DitherSpec& s, int bytes, uint32_t lan
     s.shift[0] = s0; s.shift[1] = s1; s.shift[2] = s2; s.shift[3] = s3;
 }
 
-// The formats with a dithered store (the cases of :4127-4557 other than the two Xbox-only ones); valid = 0 for every other format.
+// The formats with a dithered store (every case of :4127-4557); valid = 0 for every other format (R10G10B10_7E3_A2_FLOAT and
+// R10G10B10_6E4_A2_FLOAT among them: :4558-4559 hands them to StoreScanline).
 __host__ __device__ inline DitherSpec dither_spec(int format)
 {
     DitherSpec s = {};
@@ -146,6 +147,15 @@ __host__ __device__ inline DitherSpec dither_spec(int format)
     case FMT_B4G4R4A4_UNORM: spec_macro(s, 15.0f, true, true); s.bgr = 1; spec_pack(s, 2, 15, 0xF, 0xF, 0xF, 0xF, 0, 4, 8, 12); break;
     case FMT_A4B4G4R4_UNORM:             // :4489-4533: Saturate, then XMVectorSwizzle<3, 2, 1, 0>
         spec_macro(s, 15.0f, true, true); s.rev = 1; spec_pack(s, 2, 15, 0xF, 0xF, 0xF, 0xF, 0, 4, 8, 12); break;
+    case FMT_R10G10B10_SNORM_A2_UNORM:   // STORE_SCANLINE(XMXDECN4, g_Scale9pc, false, true, ...) (:4509-4510): per-lane scale (511, 511, 511, 3);
+    {                                    // alpha is clamped to [-1, 1] like the colours, and its low two bits are what the bitfield keeps
+        const float s9[4] = { 511.0f, 511.0f, 511.0f, 3.0f }, one[4] = { 1.0f, 1.0f, 1.0f, 1.0f }, neg1[4] = { -1.0f, -1.0f, -1.0f, -1.0f };
+        const float lo[4] = { (0.0f - 511.0f) + 1.0f, (0.0f - 511.0f) + 1.0f, (0.0f - 511.0f) + 1.0f, (0.0f - 3.0f) + 1.0f };
+        spec_lanes(s, s9, neg1, one, lo, s9);
+        spec_pack(s, 4, 15, 0x3FF, 0x3FF, 0x3FF, 0x3, 0, 10, 20, 30); break;
+    }
+    case FMT_R4G4_UNORM:                 // :4512-4556: Saturate, g_Scale4pc, x and y into one byte
+        spec_macro(s, 15.0f, true, true); spec_pack(s, 1, 3, 0xF, 0xF, 0, 0, 0, 4, 0, 0); break;
     default:
         s.valid = 0;
         break;

@@ -9,7 +9,8 @@ enum FmtClass : uint32_t
 {
     FC_UNORM = 1, FC_SNORM = 2, FC_FLOAT = 4, FC_BC = 8,
     FC_R = 0x10, FC_G = 0x20, FC_B = 0x40, FC_A = 0x80, FC_SRGB = 0x100,
-    FC_POS_ONLY = 0x200,     // CONVF_POS_ONLY: unsigned float formats (R11G11B10_FLOAT, R9G9B9E5_SHAREDEXP)
+    FC_POS_ONLY = 0x200,     // CONVF_POS_ONLY: unsigned float formats (R11G11B10_FLOAT, R9G9B9E5_SHAREDEXP, R10G10B10_7E3_A2_FLOAT, R10G10B10_6E4_A2_FLOAT).
+                             // The last two have an alpha lane: the plan's range conversions (tcv1) act on all four lanes, as ConvertScanline's do
     FC_UINT = 0x400, FC_SINT = 0x800,      // CONVF_UINT / CONVF_SINT: the value itself travels through the float row
     FC_XR = 0x1000,          // CONVF_XR (R10G10B10_XR_BIAS_A2_UNORM)
     FC_YUV = 0x2000,         // CONVF_YUV: converted to / from RGB inside LoadScanline / StoreScanline
@@ -55,6 +56,11 @@ inline const FmtInfo* format_info(int format)
         { FMT_B5G5R5A1_UNORM, 16, FC_UNORM | FC_R | FC_G | FC_B | FC_A },
         { FMT_B4G4R4A4_UNORM, 16, FC_UNORM | FC_R | FC_G | FC_B | FC_A },
         { FMT_A4B4G4R4_UNORM, 16, FC_UNORM | FC_R | FC_G | FC_B | FC_A },        // WIN11_DXGI_FORMAT_A4B4G4R4_UNORM = 191 (:3046)
+        // the Xbox formats (:3042-3045): 10-bit unsigned floats (7e3 / 6e4) and 10-bit SNORM with a 2-bit UNORM alpha; two nibbles a byte
+        { FMT_R10G10B10_7E3_A2_FLOAT, 32, FC_FLOAT | FC_POS_ONLY | FC_R | FC_G | FC_B | FC_A },
+        { FMT_R10G10B10_6E4_A2_FLOAT, 32, FC_FLOAT | FC_POS_ONLY | FC_R | FC_G | FC_B | FC_A },
+        { FMT_R10G10B10_SNORM_A2_UNORM, 32, FC_SNORM | FC_R | FC_G | FC_B | FC_A },
+        { FMT_R4G4_UNORM, 8, FC_UNORM | FC_R | FC_G },
         // g_ConvertTable (DirectXTexConvert.cpp:2960-3047): integer, extended-range and 4:4:4 video formats
         { FMT_R32G32B32A32_UINT, 128, FC_UINT | FC_R | FC_G | FC_B | FC_A }, { FMT_R32G32B32A32_SINT, 128, FC_SINT | FC_R | FC_G | FC_B | FC_A },
         { FMT_R32G32B32_UINT, 96, FC_UINT | FC_R | FC_G | FC_B }, { FMT_R32G32B32_SINT, 96, FC_SINT | FC_R | FC_G | FC_B },

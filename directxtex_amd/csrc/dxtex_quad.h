@@ -16,7 +16,8 @@ namespace dxtex
     X(FMT_R16G16_UINT, 16) X(FMT_R16G16_SNORM, 16) X(FMT_R16G16_SINT, 16) X(FMT_R32_FLOAT, 16) X(FMT_R32_UINT, 16) \
     X(FMT_R32_SINT, 16) X(FMT_R9G9B9E5_SHAREDEXP, 16) X(FMT_B8G8R8A8_UNORM, 16) X(FMT_B8G8R8X8_UNORM, 16) X(FMT_R10G10B10_XR_BIAS_A2_UNORM, 16) \
     X(FMT_B8G8R8A8_UNORM_SRGB, 16) X(FMT_B8G8R8X8_UNORM_SRGB, 16) X(FMT_AYUV, 16) X(FMT_Y410, 16) X(FMT_D32_FLOAT_S8X24_UINT, 32) \
-    X(FMT_D32_FLOAT, 16) X(FMT_D24_UNORM_S8_UINT, 16)
+    X(FMT_D32_FLOAT, 16) X(FMT_D24_UNORM_S8_UINT, 16) X(FMT_R10G10B10_7E3_A2_FLOAT, 16) X(FMT_R10G10B10_6E4_A2_FLOAT, 16) \
+    X(FMT_R10G10B10_SNORM_A2_UNORM, 16)
 
 // the bytes of a quad of `format`, 0 for a format outside the list
 __host__ __device__ inline uint32_t quad_bytes(int format)

@@ -153,6 +153,46 @@ __device__ __forceinline__ uint32_t store_float11(float v, int MB)
     return ((I + ((1u << (shift - 1)) - 1u) + ((I >> shift) & 1u)) >> shift) & all;
 }
 
+// FloatTo7e3 / FloatTo6e4 (DirectXTexConvert.cpp:21-52, :88-119): fp32 -> 10-bit unsigned float with MB mantissa bits (7 or 6). A set
+// sign bit (-0 and negative NaNs included) gives 0, anything above the saturation threshold (+INF and positive NaNs included) 0x3FF;
+// below the smallest normal the mantissa is shifted into a denormal, the shift capped at 24; the 23 - MB dropped bits round to
+// nearest even, and a carry out of the mantissa moves into the exponent. __host__ __device__: tests/cpp/xbox_check.cpp sweeps it.
+__host__ __device__ inline uint32_t float_to_small10(float v, int MB)
+{
+    union { float f; uint32_t u; } c;
+    c.f = v;
+    uint32_t I = c.u;
+    if (I & 0x80000000u) return 0u;                                          // positive only
+    if (I > ((MB == 7) ? 0x41FF73FFu : 0x43FEFFFFu)) return 0x3FFu;          // too large: saturate
+    const int shift = 23 - MB;                                               // 16 or 17
+    if (I < ((MB == 7) ? 0x3E800000u : 0x3C800000u))
+    {
+        const uint32_t s = ((MB == 7) ? 125u : 121u) - (I >> 23);            // denormal in the small format
+        I = (0x800000u | (I & 0x7FFFFFu)) >> (s < 24u ? s : 24u);
+    }
+    else I += (MB == 7) ? 0xC2000000u : 0xC4000000u;                         // re-bias the exponent
+    return ((I + ((1u << (shift - 1)) - 1u) + ((I >> shift) & 1u)) >> shift) & 0x3FFu;
+}
+__host__ __device__ inline uint32_t float_to_7e3(float v) { return float_to_small10(v, 7); }
+__host__ __device__ inline uint32_t float_to_6e4(float v) { return float_to_small10(v, 6); }
+
+// XMVectorClamp(v, lo, hi) = minps(hi, maxps(lo, v)): v is the second operand of both, so a NaN stays a NaN (as in store_half and the
+// dithered stores' pre-step), where the packed stores' own maxps(v, lo) turns it into lo
+__host__ __device__ inline float clamp_xm(float v, float lo, float hi)
+{
+    const float s = (lo > v) ? lo : v;
+    return (hi < s) ? hi : s;
+}
+
+// R10G10B10_7E3_A2_FLOAT / R10G10B10_6E4_A2_FLOAT (:2439-2493): v * (1, 1, 1, 3), XMVectorClamp to [0, (hi, hi, hi, 3)] with hi = 31.875
+// (7e3) or 508 (6e4), the small-float pack per colour channel, alpha TRUNCATED (static_cast<uint32_t>) into its two bits
+__host__ __device__ inline uint32_t pack_small10_a2(float r, float g, float b, float a, int MB)
+{
+    const float hi = (MB == 7) ? 31.875f : 508.0f;
+    return float_to_small10(clamp_xm(r, 0.0f, hi), MB) | (float_to_small10(clamp_xm(g, 0.0f, hi), MB) << 10) |
+           (float_to_small10(clamp_xm(b, 0.0f, hi), MB) << 20) | ((uint32_t(clamp_xm(a * 3.0f, 0.0f, 3.0f)) & 3u) << 30);
+}
+
 // XMStoreFloat3SE (DirectXMath >= 3.10, which is what the reference calls: DirectXTexConvert.cpp:155-156). The mantissas are rounded
 // to nearest EVEN (DirectXMath's Internal::round_to_nearest); the reference's private copy for DirectXMath < 3.10 (:158-191) uses lroundf
 // (half away from zero) and is not compiled against a current DirectXMath.
@@ -400,6 +440,24 @@ __device__ __forceinline__ void store_texel(uint8_t* row, uint32_t x, int format
     case FMT_A4B4G4R4_UNORM:         // (a, b, g, r) * 15 through XMStoreUNibble4 (:2419-2437)
         reinterpret_cast<uint16_t*>(row)[x] = uint16_t((store_scaled_rne(t.a, 15.0f) & 0xFu) | ((store_scaled_rne(t.b, 15.0f) & 0xFu) << 4) |
                                                        ((store_scaled_rne(t.g, 15.0f) & 0xFu) << 8) | ((store_scaled_rne(t.r, 15.0f) & 0xFu) << 12));
+        break;
+    // ---- the Xbox formats (:2439-2520)
+    case FMT_R10G10B10_7E3_A2_FLOAT:
+        reinterpret_cast<uint32_t*>(row)[x] = pack_small10_a2(t.r, t.g, t.b, t.a, 7);
+        break;
+    case FMT_R10G10B10_6E4_A2_FLOAT:
+        reinterpret_cast<uint32_t*>(row)[x] = pack_small10_a2(t.r, t.g, t.b, t.a, 6);
+        break;
+    case FMT_R10G10B10_SNORM_A2_UNORM:
+    {
+        // XMStoreXDecN4 (:2495-2497): clamp to [-1, 1] ([0, 1] for w), * 511 (3), round to nearest even
+        const auto q = [](float v) { float s = (v > -1.0f) ? v : -1.0f; s = (s < 1.0f) ? s : 1.0f; return uint32_t(int32_t(rintf(s * 511.0f))) & 0x3FFu; };
+        float w = (t.a > 0.0f) ? t.a : 0.0f; w = (w < 1.0f) ? w : 1.0f;
+        reinterpret_cast<uint32_t*>(row)[x] = q(t.r) | (q(t.g) << 10) | (q(t.b) << 20) | ((uint32_t(int32_t(rintf(w * 3.0f))) & 3u) << 30);
+        break;
+    }
+    case FMT_R4G4_UNORM:             // (x, y) * 15 through XMStoreUNibble4, no bias on x64 (:2499-2520)
+        row[x] = uint8_t((store_scaled_rne(t.r, 15.0f) & 0xFu) | ((store_scaled_rne(t.g, 15.0f) & 0xFu) << 4));
         break;
     // ---- integer formats (see store_u32 / store_s32 / store_clamp_rne / store_clamp_trunc above)
     case FMT_R32G32B32A32_UINT: reinterpret_cast<uint4*>(row)[x] = make_uint4(store_u32(t.r), store_u32(t.g), store_u32(t.b), store_u32(t.a)); break;     // :1674-1675

@@ -70,8 +70,12 @@ enum DXGI_FORMAT : uint32_t
     DXGI_FORMAT_AYUV = 100, DXGI_FORMAT_Y410 = 101, DXGI_FORMAT_Y416 = 102, DXGI_FORMAT_NV12 = 103, DXGI_FORMAT_P010 = 104, DXGI_FORMAT_P016 = 105,
     DXGI_FORMAT_420_OPAQUE = 106, DXGI_FORMAT_YUY2 = 107, DXGI_FORMAT_Y210 = 108, DXGI_FORMAT_Y216 = 109, DXGI_FORMAT_NV11 = 110,
     DXGI_FORMAT_AI44 = 111, DXGI_FORMAT_IA44 = 112, DXGI_FORMAT_P8 = 113, DXGI_FORMAT_A8P8 = 114, DXGI_FORMAT_B4G4R4A4_UNORM = 115,
+    XBOX_DXGI_FORMAT_R10G10B10_7E3_A2_FLOAT = 116, XBOX_DXGI_FORMAT_R10G10B10_6E4_A2_FLOAT = 117,
     DXGI_FORMAT_P208 = 130, DXGI_FORMAT_V208 = 131, DXGI_FORMAT_V408 = 132,
     DXGI_FORMAT_SAMPLER_FEEDBACK_MIN_MIP_OPAQUE = 189, DXGI_FORMAT_SAMPLER_FEEDBACK_MIP_REGION_USED_OPAQUE = 190, DXGI_FORMAT_A4B4G4R4_UNORM = 191,
+    // the console formats share 189 and 190 with the sampler-feedback names above (DirectXTexP.h's XBOX_DXGI_FORMAT_* constants); every
+    // function of this library reads the two numbers as these
+    XBOX_DXGI_FORMAT_R10G10B10_SNORM_A2_UNORM = 189, XBOX_DXGI_FORMAT_R4G4_UNORM = 190,
 };
 
 enum TEX_DIMENSION : uint32_t { TEX_DIMENSION_TEXTURE1D = 2, TEX_DIMENSION_TEXTURE2D = 3, TEX_DIMENSION_TEXTURE3D = 4 };

@@ -43,7 +43,7 @@ const Name kFormats[] = {
     { "BC4_SNORM", 81 }, { "BC5_UNORM", 83 }, { "BC5_SNORM", 84 }, { "B5G6R5_UNORM", 85 }, { "B5G5R5A1_UNORM", 86 }, { "B8G8R8A8_UNORM", 87 }, { "B8G8R8X8_UNORM", 88 },
     { "R10G10B10_XR_BIAS_A2_UNORM", 89 }, { "B8G8R8A8_UNORM_SRGB", 91 }, { "B8G8R8X8_UNORM_SRGB", 93 }, { "BC6H_UF16", 95 }, { "BC6H_SF16", 96 }, { "BC7_UNORM", 98 },
     { "BC7_UNORM_SRGB", 99 }, { "AYUV", 100 }, { "Y410", 101 }, { "Y416", 102 }, { "YUY2", 107 }, { "Y210", 108 }, { "Y216", 109 }, { "B4G4R4A4_UNORM", 115 },
-    { "A4B4G4R4_UNORM", 191 },
+    { "R10G10B10_7E3_A2_FLOAT", 116 }, { "R10G10B10_6E4_A2_FLOAT", 117 }, { "R10G10B10_SNORM_A2_UNORM", 189 }, { "R4G4_UNORM", 190 }, { "A4B4G4R4_UNORM", 191 },
     // texdiag's aliases (:99-110)
     { "DXT1", 71 }, { "DXT2", 74 }, { "DXT3", 74 }, { "DXT4", 77 }, { "DXT5", 77 }, { "RGBA", 28 }, { "BGRA", 87 }, { "BGR", 88 }, { "FP16", 10 }, { "FP32", 2 },
 };
