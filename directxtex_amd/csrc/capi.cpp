@@ -382,15 +382,6 @@ dxtex_hresult launch_into(dxtex_ctx* ctx, const ImgView& dst, KernelMarks* marks
     return launched(ctx, e);
 }
 
-struct LevelPair { ImgView src, dst; };
-LevelPair pair_of(const dxtex_image& s, const dxtex_image& d) { return { view_of(s), view_of(d) }; }
-// the (level i - 1 -> level i) pairs of a mip chain
-std::vector<LevelPair> mip_pairs(const dxtex_image* levels, size_t nlevels)
-{
-    std::vector<LevelPair> pairs;
-    for (size_t i = 1; i < nlevels; ++i) pairs.push_back(pair_of(levels[i - 1], levels[i]));
-    return pairs;
-}
 // copies of n images whose pixels lie at the arena's offsets from `base` (a host variant's levels in the staging)
 std::vector<dxtex_image> in_arena(const dxtex_image* im, size_t n, uint8_t* base, const Arena& a)
 {
@@ -922,58 +913,57 @@ dxtex_hresult upload_tables(dxtex_ctx* ctx)
     return DXTEX_S_OK;
 }
 
-// Builds the triangle tables of every (src -> dst) pair into one device buffer, then launches the filter per pair.
-dxtex_hresult submit_resizes(dxtex_ctx* ctx, const std::vector<LevelPair>& pairs, uint32_t mode, uint32_t flags, bool mipAlias)
+// One level: src filtered into dst (through the float rows where dst's format is grouped).
+dxtex_hresult submit_level(dxtex_ctx* ctx, const ImgView& src, const ImgView& dst, uint32_t mode, uint32_t flags, bool mipAlias,
+                           const TriangleTables* tri, const ImgView* stale)
 {
     KernelMarks* marks = marks_of(ctx);
-    auto resize_one = [&](const LevelPair& p, const TriangleTables* t, const ImgView* stale)
+    return launch_into(ctx, dst, marks, [&](const ImgView& out) { return launch_resize(src, out, mode, flags, mipAlias, tri, ctx->stream, stale, marks); });
+}
+
+// The triangle tables of every lv[i - 1] -> lv[i] in one upload; (*tables)[i - 1] are that level's.
+dxtex_hresult upload_triangle_levels(dxtex_ctx* ctx, const ImgView* lv, size_t nlevels, uint32_t flags, std::vector<TriangleTables>* tables)
+{
+    ctx->triHost.clear();
+    std::vector<TriAxis> x, y;
+    for (size_t i = 1; i < nlevels; ++i)
     {
-        return launch_into(ctx, p.dst, marks, [&](const ImgView& out) { return launch_resize(p.src, out, mode, flags, mipAlias, t, ctx->stream, stale, marks); });
-    };
+        x.push_back(pack_triangle_axis(ctx->triHost, lv[i - 1].width, lv[i].width, (flags & DXTEX_FILTER_WRAP_U) != 0));
+        y.push_back(pack_triangle_axis(ctx->triHost, lv[i - 1].height, lv[i].height, (flags & DXTEX_FILTER_WRAP_V) != 0));
+    }
+    const dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
+    const uint8_t* d = ctx->triBuf.u8();
+    for (size_t i = 0; i < x.size(); ++i) tables->push_back({ tri_ofs(d, x[i]), d + x[i].ent, tri_ofs(d, y[i]), d + y[i].ent });
+    return DXTEX_S_OK;
+}
+
+// A mip chain on device-resident levels (lv[0] = the source): a launch per level until resize_tail_route() has a one-workgroup form for
+// the rest of the chain.
+dxtex_hresult submit_mips(dxtex_ctx* ctx, const std::vector<ImgView>& lv, uint32_t mode, uint32_t flags)
+{
+    std::vector<TriangleTables> tri;
     if (mode == DXTEX_FILTER_TRIANGLE)
     {
-        ctx->triHost.clear();
-        std::vector<TriAxis> x, y;
-        for (const LevelPair& p : pairs)
-        {
-            x.push_back(pack_triangle_axis(ctx->triHost, p.src.width, p.dst.width, (flags & DXTEX_FILTER_WRAP_U) != 0));
-            y.push_back(pack_triangle_axis(ctx->triHost, p.src.height, p.dst.height, (flags & DXTEX_FILTER_WRAP_V) != 0));
-        }
-        dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
-        const uint8_t* d = ctx->triBuf.u8();
-        for (size_t i = 0; i < pairs.size(); ++i)
-        {
-            const TriangleTables t = { tri_ofs(d, x[i]), d + x[i].ent, tri_ofs(d, y[i]), d + y[i].ent };
-            const dxtex_hresult hr1 = resize_one(pairs[i], &t, nullptr);
-            if (hr1 != DXTEX_S_OK) return hr1;
-        }
-        return DXTEX_S_OK;
+        const dxtex_hresult hr = upload_triangle_levels(ctx, lv.data(), lv.size(), flags, &tri); if (hr != DXTEX_S_OK) return hr;
     }
-    const ImgView* twoHigh = nullptr;      // box mips: the last source level that was 2 texels high (resize_box_kernel's stale tap)
-    for (size_t i = 0; i < pairs.size(); ++i)
+    StaleTap<ImgView> tap{};
+    for (size_t i = 1; i < lv.size(); ++i)
     {
-        const LevelPair& p = pairs[i];
-        // a mip chain's last levels (source at most 64 x 64, each level the next one's source) run in one workgroup
-        const bool cubicTail = mode == DXTEX_FILTER_CUBIC && p.src.width <= 64 && p.src.height <= 64;
-        if (mipAlias && !is_group_format(p.dst.format) && pairs.size() - i >= 2 && (cubicTail || resize_tail_applies(p.src.width, p.src.height, mode)))
-        {
-            bool chain = true;
-            for (size_t k = i + 1; k < pairs.size(); ++k) chain = chain && pairs[k].src.pixels == pairs[k - 1].dst.pixels && pairs[k].src.rowPitch == pairs[k - 1].dst.rowPitch;
-            std::vector<ImgView> lv;
-            if (chain)
-            {
-                lv.push_back(p.src);
-                for (size_t k = i; k < pairs.size(); ++k) lv.push_back(pairs[k].dst);
-                if (cubicTail) chain = resize_cubic_tail_applies(lv.data(), int(lv.size()), flags);
-            }
-            if (chain) return launched(ctx, launch_resize_tail(lv.data(), int(lv.size()), mode, flags, twoHigh, ctx->stream, marks));
-        }
-        if (mipAlias && p.src.height >= 2) twoHigh = &p.src;
-        const bool stale = mipAlias && mode == DXTEX_FILTER_BOX && p.src.height == 1 && p.src.width > 1 && twoHigh;
-        const dxtex_hresult hr1 = resize_one(p, nullptr, stale ? twoHigh : nullptr);
-        if (hr1 != DXTEX_S_OK) return hr1;
+        const ImgView* rest = &lv[i - 1];
+        const int nrest = int(lv.size() - (i - 1));
+        if (resize_tail_route(rest, nrest, mode, flags) != TailRoute::None)
+            return launched(ctx, launch_resize_tail(rest, nrest, mode, flags, tap.twoHigh.pixels ? &tap.twoHigh : nullptr, ctx->stream, marks_of(ctx)));
+        const bool stale = tap.step(lv[i - 1], mode == DXTEX_FILTER_BOX);
+        const dxtex_hresult hr = submit_level(ctx, lv[i - 1], lv[i], mode, flags, true, tri.empty() ? nullptr : &tri[i - 1], stale ? &tap.twoHigh : nullptr);
+        if (hr != DXTEX_S_OK) return hr;
     }
     return DXTEX_S_OK;
+}
+std::vector<ImgView> views_of(const dxtex_image* levels, size_t nlevels)
+{
+    std::vector<ImgView> lv(nlevels);
+    for (size_t i = 0; i < nlevels; ++i) lv[i] = view_of(levels[i]);
+    return lv;
 }
 
 // GenerateMipMaps' checks and filter choice (DirectXTexMipmaps.cpp:2828-3017, non-WIC path)
@@ -1010,7 +1000,7 @@ dxtex_hresult dxtex_generate_mips_device(dxtex_ctx* ctx, const dxtex_image* leve
     uint32_t mode = 0;
     dxtex_hresult hr = check_mips(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(levels, nlevels), mode, filter, true); });
+    return run_timed(ctx, [&] { return submit_mips(ctx, views_of(levels, nlevels), mode, filter); });
 }
 
 dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, size_t nlevels, uint32_t filter)
@@ -1026,7 +1016,7 @@ dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, siz
     hr = ctx->stageIn.grow(ctx, a.total); if (hr != DXTEX_S_OK) return hr;
     const std::vector<dxtex_image> d = in_arena(levels, nlevels, ctx->stageIn.u8(), a);
     HIP_TRY(ctx, counted_copy(ctx, d[0].pixels, levels[0].pixels, bytes[0], hipMemcpyHostToDevice, ctx->stream));
-    hr = run_timed(ctx, [&] { return submit_resizes(ctx, mip_pairs(d.data(), nlevels), mode, filter, true); });
+    hr = run_timed(ctx, [&] { return submit_mips(ctx, views_of(d.data(), nlevels), mode, filter); });
     if (hr != DXTEX_S_OK) return hr;
     for (size_t i = 1; i < nlevels; ++i)
         HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, d[i].pixels, bytes[i], hipMemcpyDeviceToHost, ctx->stream));
@@ -1046,7 +1036,7 @@ dxtex_hresult check_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nl
     if (!f || (f->cls & FC_GROUP)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "format is not supported by the MI355X path");
     size_t w = levels[0].width, h = levels[0].height, d = levels[0].depth;
     if (!w || !h || !d || d > 32767) return fail(ctx, DXTEX_E_INVALIDARG, "bad volume dimensions");           // depth > INT16_MAX, :3264
-    if (filter & 0x20000000u) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "TEX_FILTER_FORCE_WIC");
+    if (filter & TF_FORCE_WIC) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "TEX_FILTER_FORCE_WIC");
     for (size_t i = 0; i < nlevels; ++i)
     {
         if (!levels[i].pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
@@ -1065,12 +1055,6 @@ dxtex_hresult check_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, size_t nl
     return DXTEX_S_OK;
 }
 
-// slice z of a volume level as a 2-D surface
-ImgView slice_of(const VolumeView& v, uint32_t z)
-{
-    return ImgView{ const_cast<uint8_t*>(v.pixels) + uint64_t(z) * v.slicePitch, v.rowPitch, v.width, v.height, v.format };
-}
-
 // The level loop of Generate3DMips*Filter on device-resident levels: 3-D kernels while the source is more than one slice deep,
 // then the reference's 2-D branches (the kernels GenerateMipMaps uses) - except the triangle filter, which has no 2-D branch.
 dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, uint32_t mode, uint32_t flags)
@@ -1084,21 +1068,20 @@ dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, u
         {
             x[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].width, lv[i].width, (flags & DXTEX_FILTER_WRAP_U) != 0);
             y[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].height, lv[i].height, (flags & DXTEX_FILTER_WRAP_V) != 0);
-            z[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].depth, lv[i].depth, (flags & 0x4u) != 0);
+            z[i] = pack_triangle_axis(ctx->triHost, lv[i - 1].depth, lv[i].depth, (flags & TF_WRAP_W) != 0);
         }
         dxtex_hresult hr = upload_tables(ctx); if (hr != DXTEX_S_OK) return hr;
         tri = ctx->triBuf.u8();
     }
     KernelMarks* marks = marks_of(ctx);
-    const VolumeView* twoHigh = nullptr;     // box: the last SOURCE level that was 2 texels high (what urow1 / vrow1's old buffers hold)
+    StaleTap<VolumeView> tap{};
     for (size_t i = 1; i < lv.size(); ++i)
     {
         const VolumeView& s = lv[i - 1]; const VolumeView& d = lv[i];
-        if (s.height >= 2) twoHigh = &s;
+        const bool stale = tap.step(s, mode == DXTEX_FILTER_BOX);
         // row 1 of the last slice pair loaded into urow1 / vrow1 at that level: slices depth-2 and depth-1 (a one-slice level only has urow1)
-        const bool stale = mode == DXTEX_FILTER_BOX && s.height == 1 && s.width > 1 && twoHigh;
         ImgView staleU{}, staleV{};
-        if (stale) { staleU = slice_of(*twoHigh, twoHigh->depth >= 2 ? twoHigh->depth - 2 : 0); staleV = slice_of(*twoHigh, twoHigh->depth - 1); }
+        if (stale) { staleU = slice_of(tap.twoHigh, tap.twoHigh.depth >= 2 ? tap.twoHigh.depth - 2 : 0); staleV = slice_of(tap.twoHigh, tap.twoHigh.depth - 1); }
         hipError_t e;
         if (s.depth > 1 || mode == DXTEX_FILTER_TRIANGLE)
         {
@@ -1114,7 +1097,7 @@ dxtex_hresult submit_mips3d(dxtex_ctx* ctx, const std::vector<VolumeView>& lv, u
     return DXTEX_S_OK;
 }
 
-VolumeView view_of(const dxtex_volume& v, const uint8_t* pixels)
+VolumeView view_of(const dxtex_volume& v, uint8_t* pixels)
 {
     VolumeView o; o.pixels = pixels; o.rowPitch = v.rowPitch; o.slicePitch = v.slicePitch;
     o.width = uint32_t(v.width); o.height = uint32_t(v.height); o.depth = uint32_t(v.depth); o.format = v.format;
@@ -1178,9 +1161,16 @@ dxtex_hresult check_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_i
     return DXTEX_S_OK;
 }
 
+// Resize of one image: no mip aliasing, never the tail
 dxtex_hresult submit_resize(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t mode, uint32_t filter)
 {
-    return submit_resizes(ctx, { pair_of(src, dst) }, mode, filter, false);
+    const ImgView lv[2] = { view_of(src), view_of(dst) };
+    std::vector<TriangleTables> tri;
+    if (mode == DXTEX_FILTER_TRIANGLE)
+    {
+        const dxtex_hresult hr = upload_triangle_levels(ctx, lv, 2, filter, &tri); if (hr != DXTEX_S_OK) return hr;
+    }
+    return submit_level(ctx, lv[0], lv[1], mode, filter, false, tri.empty() ? nullptr : &tri[0], nullptr);
 }
 } // namespace
 
@@ -2330,7 +2320,7 @@ dxtex_hresult dxtex_generate_mips_multi(dxtex_ctx* const* ctxs, size_t nctx, con
                 dxtex_image s = levels[l - 1], d = levels[l];
                 s.pixels = arena + a.at[l - 1] + (s0 - E[l - 1].a) * levels[l - 1].rowPitch; s.height = 2 * (E[l].b - E[l].a);
                 d.pixels = arena + a.at[l]; d.height = E[l].b - E[l].a;
-                h = submit_resizes(ctx, { pair_of(s, d) }, mode, explicitFilter, false);
+                h = submit_resize(ctx, s, d, mode, explicitFilter);
                 if (h != DXTEX_S_OK) { time_end(ctx); return h; }
             }
             time_end(ctx);

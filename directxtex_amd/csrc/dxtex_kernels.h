@@ -96,8 +96,8 @@ hipError_t launch_merge(const ImgView& a, const ImgView& b, const ImgView& dst, 
 // Resize / one mip level: src is filtered (as src.format) into dst, whose rows are written in dst.format (R32G32B32A32_FLOAT rows for
 // launch_pack_group, src.format otherwise). filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row
-// ofs[i]..ofs[i+1] indexes (source index, fp32 weight bits) pairs, see triangle_filter.h. `stale` (box mips only): the last level of the
-// chain that was 2 texels high (its row 1 is what is read), see resize_box_kernel.
+// ofs[i]..ofs[i+1] indexes (source index, fp32 weight bits) pairs, see triangle_filter.h. `stale` (box mips only): StaleTap's level where
+// the tap applies (its row 1 is what is read, see resize_box_kernel), else nullptr.
 struct TriangleTables { const uint32_t* ofsX; const void* entX; const uint32_t* ofsY; const void* entY; };
 hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filterMode, uint32_t filterFlags, bool mipAlias,
                          const TriangleTables* tri, hipStream_t stream, const ImgView* stale = nullptr, KernelMarks* marks = nullptr);
@@ -106,18 +106,40 @@ hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filter
 // The size is dst's.
 hipError_t launch_pack_group(const ImgView& rows, const ImgView& dst, hipStream_t stream, KernelMarks* marks = nullptr);
 
-// The tail of a 2-D mip chain (levels[0] = the first source level, at most 64 x 64; levels[1..] = the levels generated from it, all of
-// levels[0]'s format) in one workgroup: point / linear / cubic / box, the arithmetic of launch_resize with mipAlias. twoHigh = the last
-// level of the chain before levels[0] that was at least 2 texels high (the box filter's stale tap, see resize_box_kernel), or nullptr.
-bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode);
-// cubic: only the tail of a power-of-two RGBA8 chain with clamp addressing (every level an exact halving) has a one-workgroup form;
-// levels[] as for launch_resize_tail
-bool resize_cubic_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags);
+// The box filter's fourth tap on a W x 1 source (Generate2DMipsBoxFilter, DirectXTexMipmaps.cpp:1017-1027; Generate3DMipsBoxFilter,
+// :1849-1869): the reference points urow3 (and vrow3) at row 1 of its second-row buffer once, before the level loop, and does not re-point
+// it when a 1-high source makes the second row alias the first. One tracker per chain; step() takes each level's source in chain order and
+// says whether the tap applies to that level: the filter is box and the source is 1 high and more than 1 wide. It then reads row 1 of
+// `twoHigh`, the most recent source level at least 2 high; with none (pixels == nullptr) it is off.
+template<class View>        // ImgView, VolumeView
+struct StaleTap
+{
+    View twoHigh;
+    __host__ __device__ bool step(const View& src, bool box)
+    {
+        if (src.height >= 2u) twoHigh = src;
+        return box && src.height == 1u && src.width > 1u && twoHigh.pixels != nullptr;
+    }
+};
+
+// The tail of a 2-D mip chain in one workgroup. levels[0] = the first source level, levels[1..] = the levels generated from it, each the
+// next one's source, all of levels[0]'s format. resize_tail_route() is the one place that decides whether the rest of a chain has such a
+// form: Generic (resize_tail_kernel: point / linear / box, the arithmetic of launch_resize with mipAlias) or HalvingLds (box / cubic on
+// RGBA8 with clamp addressing, every level an exact halving, staged in LDS), or None: this level takes a launch of its own.
+// launch_resize_tail asks it again and fails for None. twoHigh = the chain's StaleTap state before levels[0], or nullptr: the launcher
+// steps it on through the tail's levels and hands the kernel each level's stale view.
+enum class TailRoute { None, Generic, HalvingLds };
+TailRoute resize_tail_route(const ImgView* levels, int nlevels, uint32_t filterMode, uint32_t filterFlags);
 hipError_t launch_resize_tail(const ImgView* levels, int nlevels, uint32_t filterMode, uint32_t filterFlags,
                               const ImgView* twoHigh, hipStream_t stream, KernelMarks* marks = nullptr);
 
 // Volume mips (Generate3DMips*Filter): one level whose source is more than one slice deep. Slices of a level are `slicePitch` apart.
-struct VolumeView { const uint8_t* pixels; uint64_t rowPitch, slicePitch; uint32_t width, height, depth; int format; };
+struct VolumeView { uint8_t* pixels; uint64_t rowPitch, slicePitch; uint32_t width, height, depth; int format; };
+// slice z of a volume level as a 2-D surface
+__host__ __device__ inline ImgView slice_of(const VolumeView& v, uint32_t z)
+{
+    return ImgView{ v.pixels + uint64_t(z) * v.slicePitch, v.rowPitch, v.width, v.height, v.format };
+}
 struct TriangleTables3 { const uint32_t* ofsX; const void* entX; const uint32_t* ofsY; const void* entY; const uint32_t* ofsZ; const void* entZ; };
 // staleU / staleV (box only, both or neither): the slices whose row 1 the reference's never re-pointed urow3 / vrow3 still see, see resize3d_box_kernel.
 hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_t filterMode, uint32_t filterFlags, const TriangleTables3* tri,

@@ -2,6 +2,7 @@
 // library handles: which of the per-texel steps (sRGB decode, range conversion, channel shuffle, sRGB encode) a
 // given (input format, output format, TEX_FILTER flags) triple needs. The kernels then run apply_plan() per texel.
 #pragma once
+#include "../../include/dxtex_amd.h"
 #include "dxtex_formats.h"
 #include "dxtex_store.h"
 
@@ -11,6 +12,10 @@ enum : uint32_t
 {
     TF_FLOAT_X2BIAS = 0x200, TF_COPY_RED = 0x1000, TF_COPY_GREEN = 0x2000, TF_COPY_BLUE = 0x4000, TF_COPY_ALPHA = 0x8000,
     TF_SRGB_IN = 0x1000000, TF_SRGB_OUT = 0x2000000,
+    // TEX_FILTER bits the public header has no name for: the third axis' addressing, and the WIC request the GPU path refuses
+    TF_WRAP_W = 0x4, TF_MIRROR_W = 0x40, TF_FORCE_WIC = 0x20000000,
+    TF_SRGB_WRAP_MIRROR = TF_SRGB_IN | TF_SRGB_OUT | DXTEX_FILTER_WRAP_U | DXTEX_FILTER_WRAP_V | TF_WRAP_W |
+                          DXTEX_FILTER_MIRROR_U | DXTEX_FILTER_MIRROR_V | TF_MIRROR_W,        // any sRGB, wrap or mirror bit
 };
 
 // The depth branch of ConvertScanline (:3186-3434) as a TDP word (dxtex_device.h); in / out differ in FC_DEPTH

@@ -19,8 +19,10 @@
 // neighbourhoods of adjacent lanes overlap in L1/L2) and one coalesced write of the destination. The per-texel
 // fp32 expressions are evaluated in exactly the reference's order (compile with -ffp-contract=off), so results are
 // bit-identical for the non-sRGB formats; sRGB goes through powf and is within 1 ulp per step.
+#include "../../include/dxtex_amd.h"
 #include "dxtex_kernels.h"
 #include "dxtex_store.h"
+#include "dxtex_plan.h"
 #include "dxtex_quad.h"
 #include "dxtex_formats.h"
 #include "cubic_filter.h"
@@ -58,7 +60,10 @@ __device__ __forceinline__ void store_linear(const ImgView& v, uint32_t x, uint3
     store_texel(v.pixels + uint64_t(y) * v.rowPitch, x, v.format, t);
 }
 
-#define DXTEX_PER_CHANNEL(EXPR_R, EXPR_G, EXPR_B, EXPR_A) Texel{ (EXPR_R), (EXPR_G), (EXPR_B), (EXPR_A) }
+// XMLoadUByteN4 of one channel of a packed RGBA8 texel: byte * (1/255), as load_texel does. The RGBA8 fast paths below must unpack
+// with exactly this expression to keep the general kernels' bits.
+__device__ __forceinline__ float unorm8(uint32_t w, uint32_t shift) { return float((w >> shift) & 0xFFu) * (1.0f / 255.0f); }
+__device__ __forceinline__ Texel unpack_rgba8(uint32_t w) { Texel t; t.r = unorm8(w, 0); t.g = unorm8(w, 8); t.b = unorm8(w, 16); t.a = unorm8(w, 24); return t; }
 
 // ---- Convert -------------------------------------------------------------------------------------------------------------
 // Rows are the grid's y dimension, which HIP limits to 65535: taller images wrap (grid_rows() caps the launch, the kernels stride).
@@ -567,9 +572,22 @@ __global__ void __launch_bounds__(256) resize_box_kernel(ResizeArgs a)
     for (uint32_t y = blockIdx.y; y < a.dst.height; y += gridDim.y) resize_box_kernel_row(a, x, y);        // grid_rows(): HIP caps grid.y at 65535
 }
 
+// The box filter of four packed RGBA8 texels, resize_box_kernel's expression per channel: (((p0 + p1) + p2) + p3) * 0.25 with p0 / p1 the
+// left column's upper / lower texel and p2 / p3 the right column's.
+__device__ __forceinline__ uint32_t box_rgba8(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3)
+{
+    uint32_t packed = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+    {
+        const float p0 = unorm8(w0, 8 * c), p1 = unorm8(w1, 8 * c), p2 = unorm8(w2, 8 * c), p3 = unorm8(w3, 8 * c);
+        packed |= store_ubn_biased((((p0 + p1) + p2) + p3) * 0.25f) << (8 * c);
+    }
+    return packed;
+}
+
 // Box, exactly 2:1 on RGBA8 (the upper levels of a power-of-two mip chain, where the bytes are): one lane produces two adjacent
 // destination texels from one 16-byte load per source row - consecutive lanes read consecutive 16 bytes - and writes 8 bytes.
-// Same expression as resize_box_kernel: (((p00 + p01) + p10) + p11) * 0.25 with p0x the left column's two rows.
 __global__ void __launch_bounds__(256) resize_box_half_rgba8_kernel(ResizeArgs a)
 {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;              // pair of destination texels
@@ -581,18 +599,7 @@ __global__ void __launch_bounds__(256) resize_box_half_rgba8_kernel(ResizeArgs a
         const uint32_t top[4] = { t.x, t.y, t.z, t.w }, bot[4] = { b.x, b.y, b.z, b.w };
         uint32_t out[2];
 #pragma unroll
-        for (int k = 0; k < 2; ++k)
-        {
-            uint32_t packed = 0;
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-            {
-                const float p0 = float((top[2 * k] >> (8 * c)) & 0xFFu) * (1.0f / 255.0f), p1 = float((bot[2 * k] >> (8 * c)) & 0xFFu) * (1.0f / 255.0f);
-                const float p2 = float((top[2 * k + 1] >> (8 * c)) & 0xFFu) * (1.0f / 255.0f), p3 = float((bot[2 * k + 1] >> (8 * c)) & 0xFFu) * (1.0f / 255.0f);
-                packed |= store_ubn_biased((((p0 + p1) + p2) + p3) * 0.25f) << (8 * c);
-            }
-            out[k] = packed;
-        }
+        for (int k = 0; k < 2; ++k) out[k] = box_rgba8(top[2 * k], bot[2 * k], top[2 * k + 1], bot[2 * k + 1]);
         reinterpret_cast<uint2*>(a.dst.pixels + uint64_t(y) * a.dst.rowPitch)[q] = make_uint2(out[0], out[1]);
     }
 }
@@ -666,40 +673,51 @@ __device__ __forceinline__ Cub cubic_entry(uint32_t source, uint32_t dest, bool 
     return e;
 }
 
+// CUBIC_INTERPOLATE of four texels, channel by channel
+__device__ __forceinline__ Texel cubic4(float x, const Texel& p0, const Texel& p1, const Texel& p2, const Texel& p3)
+{
+    Texel o;
+    o.r = cubic1(x, p0.r, p1.r, p2.r, p3.r); o.g = cubic1(x, p0.g, p1.g, p2.g, p3.g);
+    o.b = cubic1(x, p0.b, p1.b, p2.b, p3.b); o.a = cubic1(x, p0.a, p1.a, p2.a, p3.a);
+    return o;
+}
+
+// The 2-D cubic of a surface at (tx, ty): four rows through tx (cubic_row), then the column through ty (filters.h:192-207). Here the rows
+// are written out, not looped over: the compiler leaves a loop over them rolled, with the array of rows indexed at run time in LDS. That
+// form is the faster one for resize3d_cubic_kernel, which keeps it (128^3 RGBA8 chain: 248 us against 314 us written out), and the
+// slower one for resize_cubic_kernel (1024^2 RGBA16F chain: 185 us against 123 us).
+__device__ __forceinline__ Texel cubic_row(const ImgView& s, const Cub& tx, uint32_t y, int srgbIn)
+{
+    return cubic4(tx.x, load_linear(s, tx.u0, y, srgbIn), load_linear(s, tx.u1, y, srgbIn), load_linear(s, tx.u2, y, srgbIn), load_linear(s, tx.u3, y, srgbIn));
+}
+__device__ __forceinline__ Texel cubic_surface(const ImgView& s, const Cub& tx, const Cub& ty, int srgbIn)
+{
+    const Texel c0 = cubic_row(s, tx, ty.u0, srgbIn), c1 = cubic_row(s, tx, ty.u1, srgbIn), c2 = cubic_row(s, tx, ty.u2, srgbIn), c3 = cubic_row(s, tx, ty.u3, srgbIn);
+    return cubic4(ty.x, c0, c1, c2, c3);
+}
+
 __device__ __forceinline__ void resize_cubic_kernel_row(ResizeArgs a, const uint32_t x, const uint32_t y)
 {
     if (x >= a.dst.width) return;
     const Cub tx = cubic_entry(a.src.width, a.dst.width, a.wrapU != 0, a.mirrorU != 0, x);
     const Cub ty = cubic_entry(a.src.height, a.dst.height, a.wrapV != 0, a.mirrorV != 0, y);
-    const uint32_t ys[4] = { ty.u0, ty.u1, ty.u2, ty.u3 };
-    Texel c[4];
     // RGBA8 away from the left / right border: the four taps of a row are adjacent texels, one 16-byte load instead of four
-    // format-dispatched 4-byte loads (XMLoadUByteN4: byte * (1/255), as load_texel does)
+    // format-dispatched 4-byte loads
     const bool rowLoad = a.src.format == FMT_R8G8B8A8_UNORM && !a.srgbIn && tx.u1 == tx.u0 + 1u && tx.u2 == tx.u0 + 2u && tx.u3 == tx.u0 + 3u;
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
+    Texel o;
+    if (rowLoad)
     {
-        Texel p0, p1, p2, p3;
-        if (rowLoad)
+        const uint32_t ys[4] = { ty.u0, ty.u1, ty.u2, ty.u3 };
+        Texel c[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
         {
             const uint32_t* q = reinterpret_cast<const uint32_t*>(a.src.pixels + uint64_t(ys[r]) * a.src.rowPitch) + tx.u0;
-            const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];        // 4-byte aligned: the compiler merges them into one dwordx4 load
-#define DXTEX_UNPACK(P, W) P.r = float(W & 0xFF) * (1.0f / 255.0f); P.g = float((W >> 8) & 0xFF) * (1.0f / 255.0f); \
-                           P.b = float((W >> 16) & 0xFF) * (1.0f / 255.0f); P.a = float(W >> 24) * (1.0f / 255.0f)
-            DXTEX_UNPACK(p0, w0); DXTEX_UNPACK(p1, w1); DXTEX_UNPACK(p2, w2); DXTEX_UNPACK(p3, w3);
-#undef DXTEX_UNPACK
+            c[r] = cubic4(tx.x, unpack_rgba8(q[0]), unpack_rgba8(q[1]), unpack_rgba8(q[2]), unpack_rgba8(q[3]));        // 4-byte aligned: the compiler merges them into one dwordx4 load
         }
-        else
-        {
-            p0 = load_linear(a.src, tx.u0, ys[r], a.srgbIn); p1 = load_linear(a.src, tx.u1, ys[r], a.srgbIn);
-            p2 = load_linear(a.src, tx.u2, ys[r], a.srgbIn); p3 = load_linear(a.src, tx.u3, ys[r], a.srgbIn);
-        }
-        c[r].r = cubic1(tx.x, p0.r, p1.r, p2.r, p3.r); c[r].g = cubic1(tx.x, p0.g, p1.g, p2.g, p3.g);
-        c[r].b = cubic1(tx.x, p0.b, p1.b, p2.b, p3.b); c[r].a = cubic1(tx.x, p0.a, p1.a, p2.a, p3.a);
+        o = cubic4(ty.x, c[0], c[1], c[2], c[3]);
     }
-    Texel o;
-    o.r = cubic1(ty.x, c[0].r, c[1].r, c[2].r, c[3].r); o.g = cubic1(ty.x, c[0].g, c[1].g, c[2].g, c[3].g);
-    o.b = cubic1(ty.x, c[0].b, c[1].b, c[2].b, c[3].b); o.a = cubic1(ty.x, c[0].a, c[1].a, c[2].a, c[3].a);
+    else o = cubic_surface(a.src, tx, ty, a.srgbIn);
     store_linear(a.dst, x, y, a.srgbOut, o);
 }
 __global__ void __launch_bounds__(256) resize_cubic_kernel(ResizeArgs a)
@@ -732,13 +750,11 @@ __global__ void __launch_bounds__(256) resize_cubic_half_rgba8_kernel(ResizeArgs
         uint32_t w0, w1, w2, w3;
         if (inside) { w0 = q[u0]; w1 = q[u0 + 1]; w2 = q[u0 + 2]; w3 = q[u0 + 3]; }
         else { w0 = q[i0]; w1 = q[i1]; w2 = q[i2]; w3 = q[i3]; }
-#define DXTEX_CH(W, S) (float(((W) >> (S)) & 0xFFu) * (1.0f / 255.0f))
         float4 c;
-        c.x = cubic_half1(DXTEX_CH(w0, 0), DXTEX_CH(w1, 0), DXTEX_CH(w2, 0), DXTEX_CH(w3, 0));
-        c.y = cubic_half1(DXTEX_CH(w0, 8), DXTEX_CH(w1, 8), DXTEX_CH(w2, 8), DXTEX_CH(w3, 8));
-        c.z = cubic_half1(DXTEX_CH(w0, 16), DXTEX_CH(w1, 16), DXTEX_CH(w2, 16), DXTEX_CH(w3, 16));
-        c.w = cubic_half1(DXTEX_CH(w0, 24), DXTEX_CH(w1, 24), DXTEX_CH(w2, 24), DXTEX_CH(w3, 24));
-#undef DXTEX_CH
+        c.x = cubic_half1(unorm8(w0, 0), unorm8(w1, 0), unorm8(w2, 0), unorm8(w3, 0));
+        c.y = cubic_half1(unorm8(w0, 8), unorm8(w1, 8), unorm8(w2, 8), unorm8(w3, 8));
+        c.z = cubic_half1(unorm8(w0, 16), unorm8(w1, 16), unorm8(w2, 16), unorm8(w3, 16));
+        c.w = cubic_half1(unorm8(w0, 24), unorm8(w1, 24), unorm8(w2, 24), unorm8(w3, 24));
         return c;
     };
     // the grid's y dimension is capped at 65535 strips (HIP's limit): a taller level is covered by striding over the strips
@@ -778,13 +794,11 @@ __global__ void __launch_bounds__(256) resize_cubic_half_rgba8_x2_kernel(ResizeA
         const uint8_t* row = a.src.pixels + uint64_t(sy) * a.src.rowPitch;
         const uint4 m = reinterpret_cast<const uint4*>(row)[k];
         const uint32_t wl = reinterpret_cast<const uint32_t*>(row)[iL], wr = reinterpret_cast<const uint32_t*>(row)[iR];
-#define DXTEX_CH(W, S) (float(((W) >> (S)) & 0xFFu) * (1.0f / 255.0f))
         Pair o;
-#define DXTEX_ONE(S, FL, FR) { const float t0 = DXTEX_CH(wl, S), t1 = DXTEX_CH(m.x, S), t2 = DXTEX_CH(m.y, S), t3 = DXTEX_CH(m.z, S), t4 = DXTEX_CH(m.w, S), t5 = DXTEX_CH(wr, S); \
+#define DXTEX_ONE(S, FL, FR) { const float t0 = unorm8(wl, S), t1 = unorm8(m.x, S), t2 = unorm8(m.y, S), t3 = unorm8(m.z, S), t4 = unorm8(m.w, S), t5 = unorm8(wr, S); \
                                FL = cubic_half1(t0, t1, t2, t3); FR = cubic_half1(t2, t3, t4, t5); }
         DXTEX_ONE(0, o.l.x, o.r.x) DXTEX_ONE(8, o.l.y, o.r.y) DXTEX_ONE(16, o.l.z, o.r.z) DXTEX_ONE(24, o.l.w, o.r.w)
 #undef DXTEX_ONE
-#undef DXTEX_CH
         return o;
     };
     for (uint64_t s0 = uint64_t(blockIdx.y) * stripRows; s0 < a.dst.height; s0 += uint64_t(gridDim.y) * stripRows)
@@ -856,17 +870,9 @@ __global__ void __launch_bounds__(256) resize_triangle_kernel(ResizeArgs a)
 // ---- volume mips: Generate3DMips{Point,Box,Linear,Cubic,Triangle}Filter (DirectXTexMipmaps.cpp:1666-2826) ----------------------------
 // One lane = one destination texel (x, y = blockIdx.y, z = blockIdx.z) of a level whose SOURCE has depth > 1; levels whose source
 // is one slice deep take the reference's 2-D branch, i.e. the kernels above.
-struct Vol
-{
-    uint8_t* pixels;                 // slice 0
-    uint64_t rowPitch, slicePitch;
-    uint32_t width, height, depth;
-    int format;
-};
-
 struct Resize3Args
 {
-    Vol src, dst;
+    VolumeView src, dst;
     int srgbIn, srgbOut;
     int wrapU, wrapV, wrapW, mirrorU, mirrorV, mirrorW;
     ImgView staleU, staleV;          // box: what the never re-pointed urow3 / vrow3 still see on W x 1 x D levels (see resize3d_box_kernel)
@@ -884,31 +890,28 @@ constexpr uint32_t kTailSide = 64;
 constexpr int kTailMaxLevels = 8;
 struct TailArgs
 {
-    ResizeArgs a;                       // flags; src = the first source level; stale as launch_resize sets it up
+    ResizeArgs a;                       // flags; src = the first source level
     ImgView level[kTailMaxLevels];      // the destination levels, in order
+    ImgView stale[kTailMaxLevels];      // per level what launch_resize takes as `stale`: the host steps the chain's StaleTap through the tail
     int nlevels;
-    uint32_t mode;                      // TEX_FILTER_POINT / LINEAR / CUBIC / BOX
-    ImgView twoHigh;                    // box: the last level of the whole chain that was 2 texels high BEFORE the tail (or null)
+    uint32_t mode;                      // DXTEX_FILTER_POINT / LINEAR / BOX (resize_tail_route sends no cubic chain here)
 };
 
 __global__ void __launch_bounds__(1024) resize_tail_kernel(TailArgs t)
 {
     ResizeArgs a = t.a;
-    ImgView twoHigh = t.twoHigh;
     for (int l = 0; l < t.nlevels; ++l)
     {
         a.dst = t.level[l];
-        if (a.mipAlias && a.src.height >= 2u) twoHigh = a.src;              // submit_resizes' bookkeeping of the stale tap
-        a.stale = (a.mipAlias && t.mode == 0x400000u && a.src.height == 1u && a.src.width > 1u && twoHigh.pixels) ? twoHigh : ImgView{ nullptr, 0, 0, 2, a.src.format };
+        a.stale = t.stale[l];
         const uint32_t n = a.dst.width * a.dst.height;
         for (uint32_t i = threadIdx.x; i < n; i += 1024u)
         {
             const uint32_t y = i / a.dst.width, x = i - y * a.dst.width;
             switch (t.mode)
             {
-            case 0x100000u: resize_point_kernel_row(a, x, y); break;
-            case 0x200000u: resize_linear_kernel_row(a, x, y); break;
-            case 0x300000u: resize_cubic_kernel_row(a, x, y); break;
+            case DXTEX_FILTER_POINT: resize_point_kernel_row(a, x, y); break;
+            case DXTEX_FILTER_LINEAR: resize_linear_kernel_row(a, x, y); break;
             default: resize_box_kernel_row(a, x, y); break;
             }
         }
@@ -948,16 +951,9 @@ __global__ void __launch_bounds__(1024) resize_half_tail_rgba8_kernel(CubicTailA
             const uint32_t y = i / dw, x = i - y * dw;
             if constexpr (!CUBIC)
             {
-                // the box filter of resize_box_half_rgba8_kernel: (((p0 + p1) + p2) + p3) * 0.25 over (2x, 2y), (2x, 2y + 1), (2x + 1, 2y), (2x + 1, 2y + 1)
+                // the box filter of resize_box_half_rgba8_kernel over (2x, 2y), (2x, 2y + 1), (2x + 1, 2y), (2x + 1, 2y + 1)
                 const uint32_t t0 = s[(2u * y) * w + 2u * x], t1 = s[(2u * y) * w + 2u * x + 1u], b0 = s[(2u * y + 1u) * w + 2u * x], b1 = s[(2u * y + 1u) * w + 2u * x + 1u];
-                uint32_t packed = 0;
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                {
-                    const float p0 = float((t0 >> (8 * c)) & 0xFFu) * (1.0f / 255.0f), p1 = float((b0 >> (8 * c)) & 0xFFu) * (1.0f / 255.0f);
-                    const float p2 = float((t1 >> (8 * c)) & 0xFFu) * (1.0f / 255.0f), p3 = float((b1 >> (8 * c)) & 0xFFu) * (1.0f / 255.0f);
-                    packed |= store_ubn_biased((((p0 + p1) + p2) + p3) * 0.25f) << (8 * c);
-                }
+                const uint32_t packed = box_rgba8(t0, b0, t1, b1);
                 d[i] = packed;
                 reinterpret_cast<uint32_t*>(t.dst[l] + uint64_t(y) * t.dstPitch[l])[x] = packed;
                 continue;
@@ -973,12 +969,10 @@ __global__ void __launch_bounds__(1024) resize_half_tail_rgba8_kernel(CubicTailA
                 const int32_t v = v0 + r;
                 const uint32_t* row = s + uint32_t(v < 0 ? 0 : (v > int32_t(h) - 1 ? int32_t(h) - 1 : v)) * w;
                 const uint32_t w0 = row[xi[0]], w1 = row[xi[1]], w2 = row[xi[2]], w3 = row[xi[3]];
-#define DXTEX_CH(W, S) (float(((W) >> (S)) & 0xFFu) * (1.0f / 255.0f))
-                c[r].x = cubic_half1(DXTEX_CH(w0, 0), DXTEX_CH(w1, 0), DXTEX_CH(w2, 0), DXTEX_CH(w3, 0));
-                c[r].y = cubic_half1(DXTEX_CH(w0, 8), DXTEX_CH(w1, 8), DXTEX_CH(w2, 8), DXTEX_CH(w3, 8));
-                c[r].z = cubic_half1(DXTEX_CH(w0, 16), DXTEX_CH(w1, 16), DXTEX_CH(w2, 16), DXTEX_CH(w3, 16));
-                c[r].w = cubic_half1(DXTEX_CH(w0, 24), DXTEX_CH(w1, 24), DXTEX_CH(w2, 24), DXTEX_CH(w3, 24));
-#undef DXTEX_CH
+                c[r].x = cubic_half1(unorm8(w0, 0), unorm8(w1, 0), unorm8(w2, 0), unorm8(w3, 0));
+                c[r].y = cubic_half1(unorm8(w0, 8), unorm8(w1, 8), unorm8(w2, 8), unorm8(w3, 8));
+                c[r].z = cubic_half1(unorm8(w0, 16), unorm8(w1, 16), unorm8(w2, 16), unorm8(w3, 16));
+                c[r].w = cubic_half1(unorm8(w0, 24), unorm8(w1, 24), unorm8(w2, 24), unorm8(w3, 24));
             }
             Texel o;
             o.r = cubic_half1(c[0].x, c[1].x, c[2].x, c[3].x); o.g = cubic_half1(c[0].y, c[1].y, c[2].y, c[3].y);
@@ -991,12 +985,6 @@ __global__ void __launch_bounds__(1024) resize_half_tail_rgba8_kernel(CubicTailA
         uint32_t* const tmp = s; s = d; d = tmp;          // the next level (a quarter of this one) fits where this level's source was
         w = dw; h = dh;
     }
-}
-
-__device__ __forceinline__ ImgView slice_of(const Vol& v, uint32_t z)
-{
-    ImgView s; s.pixels = v.pixels + uint64_t(z) * v.slicePitch; s.rowPitch = v.rowPitch; s.width = v.width; s.height = v.height; s.format = v.format;
-    return s;
 }
 
 // point (:1666-1813): source slice (z * zinc) >> 16, then the 2-D point filter inside it
@@ -1066,30 +1054,21 @@ __global__ void __launch_bounds__(256) resize3d_cubic_kernel(Resize3Args a)
     const Cub tx = cubic_entry(a.src.width, a.dst.width, a.wrapU != 0, a.mirrorU != 0, x);
     const Cub ty = cubic_entry(a.src.height, a.dst.height, a.wrapV != 0, a.mirrorV != 0, y);
     const Cub tz = cubic_entry(a.src.depth, a.dst.depth, a.wrapW != 0, a.mirrorW != 0, z);
-    const uint32_t ys[4] = { ty.u0, ty.u1, ty.u2, ty.u3 }, zs[4] = { tz.u0, tz.u1, tz.u2, tz.u3 };
+    const uint32_t zs[4] = { tz.u0, tz.u1, tz.u2, tz.u3 };
     Texel d[4];
 #pragma unroll 1
     for (int j = 0; j < 4; ++j)
     {
+        // the rows of cubic_surface as a loop, which stays rolled: see there
         const ImgView S = slice_of(a.src, zs[j]);
+        const uint32_t ys[4] = { ty.u0, ty.u1, ty.u2, ty.u3 };
         Texel c[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-        {
-            const Texel p0 = load_linear(S, tx.u0, ys[r], a.srgbIn), p1 = load_linear(S, tx.u1, ys[r], a.srgbIn);
-            const Texel p2 = load_linear(S, tx.u2, ys[r], a.srgbIn), p3 = load_linear(S, tx.u3, ys[r], a.srgbIn);
-            c[r].r = cubic1(tx.x, p0.r, p1.r, p2.r, p3.r); c[r].g = cubic1(tx.x, p0.g, p1.g, p2.g, p3.g);
-            c[r].b = cubic1(tx.x, p0.b, p1.b, p2.b, p3.b); c[r].a = cubic1(tx.x, p0.a, p1.a, p2.a, p3.a);
-        }
-        Texel o;
-        o.r = cubic1(ty.x, c[0].r, c[1].r, c[2].r, c[3].r); o.g = cubic1(ty.x, c[0].g, c[1].g, c[2].g, c[3].g);
-        o.b = cubic1(ty.x, c[0].b, c[1].b, c[2].b, c[3].b); o.a = cubic1(ty.x, c[0].a, c[1].a, c[2].a, c[3].a);
+        for (int r = 0; r < 4; ++r) c[r] = cubic_row(S, tx, ys[r], a.srgbIn);
+        const Texel o = cubic4(ty.x, c[0], c[1], c[2], c[3]);
         if (j == 0) d[0] = o; else if (j == 1) d[1] = o; else if (j == 2) d[2] = o; else d[3] = o;
     }
-    Texel o;
-    o.r = cubic1(tz.x, d[0].r, d[1].r, d[2].r, d[3].r); o.g = cubic1(tz.x, d[0].g, d[1].g, d[2].g, d[3].g);
-    o.b = cubic1(tz.x, d[0].b, d[1].b, d[2].b, d[3].b); o.a = cubic1(tz.x, d[0].a, d[1].a, d[2].a, d[3].a);
-    store_linear(slice_of(a.dst, z), x, y, a.srgbOut, o);
+    store_linear(slice_of(a.dst, z), x, y, a.srgbOut, cubic4(tz.x, d[0], d[1], d[2], d[3]));
 }
 
 // triangle (:2574-2826): acc = src * ((wz * wy) * wx) + acc, contributions ordered by (source slice, source row, source column,
@@ -1195,6 +1174,34 @@ bool can_srgb(int format)
     default:
         return srgb_linear_format(format);
     }
+}
+
+// (format, TEX_FILTER flags) -> what the filter kernels take: sRGB formats filter in linear space and TEX_FILTER_SRGB_IN / OUT force it
+// for the other colour formats (LoadScanlineLinear / StoreScanlineLinear, :2803-2945); wrap / mirror addressing per axis.
+struct FilterBits { int srgbIn, srgbOut, wrapU, wrapV, wrapW, mirrorU, mirrorV, mirrorW; };
+FilterBits decode_filter(int format, uint32_t flags)
+{
+    const bool linear = can_srgb(format);
+    FilterBits f;
+    f.srgbIn = (linear && (srgb_linear_format(format) || (flags & TF_SRGB_IN))) ? 1 : 0;
+    f.srgbOut = (linear && (srgb_linear_format(format) || (flags & TF_SRGB_OUT))) ? 1 : 0;
+    f.wrapU = (flags & DXTEX_FILTER_WRAP_U) != 0; f.wrapV = (flags & DXTEX_FILTER_WRAP_V) != 0; f.wrapW = (flags & TF_WRAP_W) != 0;
+    f.mirrorU = (flags & DXTEX_FILTER_MIRROR_U) != 0; f.mirrorV = (flags & DXTEX_FILTER_MIRROR_V) != 0; f.mirrorW = (flags & TF_MIRROR_W) != 0;
+    return f;
+}
+
+// The 2-D fields of a level's arguments that do not depend on the level
+ResizeArgs resize_args(int format, uint32_t filterFlags, bool mipAlias, const TriangleTables* tri)
+{
+    const FilterBits f = decode_filter(format, filterFlags);
+    ResizeArgs a;
+    a.srgbIn = f.srgbIn; a.srgbOut = f.srgbOut;
+    a.wrapU = f.wrapU; a.wrapV = f.wrapV; a.mirrorU = f.mirrorU; a.mirrorV = f.mirrorV;
+    a.mipAlias = mipAlias ? 1 : 0;
+    a.stale = no_stale(format);
+    a.triOfsX = tri ? tri->ofsX : nullptr; a.triX = tri ? reinterpret_cast<const uint2*>(tri->entX) : nullptr;
+    a.triOfsY = tri ? tri->ofsY : nullptr; a.triY = tri ? reinterpret_cast<const uint2*>(tri->entY) : nullptr;
+    return a;
 }
 } // namespace
 
@@ -1370,24 +1377,15 @@ hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filter
     const uint32_t srcW = src.width, srcH = src.height, dstW = dst.width, dstH = dst.height;
     const int format = src.format;
     if (!dstW || !dstH) return hipSuccess;
-    ResizeArgs a;
-    a.stale = stale ? *stale : no_stale(format);
+    ResizeArgs a = resize_args(format, filterFlags, mipAlias, tri);
+    if (stale) a.stale = *stale;
     a.src = src; a.dst = dst;
-    // sRGB formats filter in linear space; TEX_FILTER_SRGB forces it for the other colour formats (:2803-2945)
-    const bool wantIn = srgb_linear_format(format) || (filterFlags & 0x1000000u), wantOut = srgb_linear_format(format) || (filterFlags & 0x2000000u);
-    a.srgbIn = (can_srgb(format) && wantIn) ? 1 : 0;
-    a.srgbOut = (can_srgb(format) && wantOut) ? 1 : 0;
-    a.wrapU = (filterFlags & 0x1u) != 0; a.wrapV = (filterFlags & 0x2u) != 0;
-    a.mirrorU = (filterFlags & 0x10u) != 0; a.mirrorV = (filterFlags & 0x20u) != 0;
-    a.mipAlias = mipAlias ? 1 : 0;
-    a.triOfsX = tri ? tri->ofsX : nullptr; a.triX = tri ? reinterpret_cast<const uint2*>(tri->entX) : nullptr;
-    a.triOfsY = tri ? tri->ofsY : nullptr; a.triY = tri ? reinterpret_cast<const uint2*>(tri->entY) : nullptr;
     const dim3 grid((dstW + 255) / 256, grid_rows(dstH)), block(256);
     switch (filterMode)
     {
-    case 0x100000u: DXTEX_MARK("resize_point"); hipLaunchKernelGGL(resize_point_kernel, grid, block, 0, stream, a); break;
-    case 0x200000u: DXTEX_MARK("resize_linear"); hipLaunchKernelGGL(resize_linear_kernel, grid, block, 0, stream, a); break;
-    case 0x300000u:
+    case DXTEX_FILTER_POINT: DXTEX_MARK("resize_point"); hipLaunchKernelGGL(resize_point_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_LINEAR: DXTEX_MARK("resize_linear"); hipLaunchKernelGGL(resize_linear_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_CUBIC:
         // the 2:1 RGBA8 case of a power-of-two mip chain has a separable kernel (a column strip per lane); the small levels take it too (6 us a
         // launch against 10 - 30 us of the general kernel's sixteen dependent taps)
         if (format == FMT_R8G8B8A8_UNORM && !a.srgbIn && !a.srgbOut && srcW == 2 * dstW && srcH == 2 * dstH &&
@@ -1422,7 +1420,7 @@ hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filter
             hipLaunchKernelGGL(resize_cubic_kernel, grid, block, 0, stream, a);
         }
         break;
-    case 0x400000u:
+    case DXTEX_FILTER_BOX:
         if (format == FMT_R8G8B8A8_UNORM && !a.srgbIn && !a.srgbOut && srcW == 2 * dstW && srcH == 2 * dstH && (dstW % 2) == 0 && dstW >= 256 &&
             (src.rowPitch % 16) == 0 && (dst.rowPitch % 8) == 0 && (reinterpret_cast<uintptr_t>(src.pixels) % 16) == 0 && (reinterpret_cast<uintptr_t>(dst.pixels) % 8) == 0)
         {
@@ -1435,110 +1433,82 @@ hipError_t launch_resize(const ImgView& src, const ImgView& dst, uint32_t filter
             hipLaunchKernelGGL(resize_box_kernel, grid, block, 0, stream, a);
         }
         break;
-    case 0x500000u: DXTEX_MARK("resize_triangle"); hipLaunchKernelGGL(resize_triangle_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_TRIANGLE: DXTEX_MARK("resize_triangle"); hipLaunchKernelGGL(resize_triangle_kernel, grid, block, 0, stream, a); break;
     default: return hipErrorInvalidValue;
     }
     DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
 
-bool resize_half_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags);
+TailRoute resize_tail_route(const ImgView* levels, int nlevels, uint32_t filterMode, uint32_t filterFlags)
+{
+    // at least two levels to write (one is a plain launch), all of them in one argument block, from a source that 1024 lanes cover in a few trips
+    if (nlevels < 3 || nlevels - 1 > kTailMaxLevels || levels[0].width > kTailSide || levels[0].height > kTailSide) return TailRoute::None;
+    const FmtInfo* info = format_info(levels[0].format);
+    if (!info || (info->cls & FC_GROUP)) return TailRoute::None;           // grouped formats are stored from float rows, level by level
+    // the LDS tail of a power-of-two RGBA8 box / cubic chain: clamp addressing, no sRGB, dword access, every level halves both sides exactly
+    bool halving = (filterMode == DXTEX_FILTER_CUBIC || filterMode == DXTEX_FILTER_BOX) && levels[0].format == FMT_R8G8B8A8_UNORM && !(filterFlags & TF_SRGB_WRAP_MIRROR);
+    for (int k = 0; halving && k < nlevels; ++k)
+    {
+        halving = (levels[k].rowPitch % 4) == 0 && (reinterpret_cast<uintptr_t>(levels[k].pixels) % 4) == 0;
+        if (k) halving = halving && levels[k].width * 2u == levels[k - 1].width && levels[k].height * 2u == levels[k - 1].height;
+    }
+    if (halving) return TailRoute::HalvingLds;
+    // measured (8192^2 chain, rocprofv3): the box tail takes 15.8 us in one workgroup against 6 launches x 3.2 us; the cubic tail 84 us
+    // against 6 x 7 us (sixteen dependent-latency taps per texel and no other workgroup to hide them) - so cubic keeps its launches
+    const bool generic = filterMode == DXTEX_FILTER_POINT || filterMode == DXTEX_FILTER_LINEAR || filterMode == DXTEX_FILTER_BOX;
+    return generic ? TailRoute::Generic : TailRoute::None;
+}
+
 hipError_t launch_resize_tail(const ImgView* levels, int nlevels, uint32_t filterMode, uint32_t filterFlags,
                               const ImgView* twoHigh, hipStream_t stream, KernelMarks* marks)
 {
-    if (nlevels < 2) return hipSuccess;
     const int format = levels[0].format;
-    const bool halving = (filterMode == 0x300000u || filterMode == 0x400000u) && resize_half_tail_applies(levels, nlevels, filterFlags);
-    if (filterMode == 0x300000u && !halving)
+    switch (resize_tail_route(levels, nlevels, filterMode, filterFlags))
     {
-        // a cubic chain the one-workgroup form does not cover (not an exact-halving RGBA8 clamp chain): one launch per level, as GenerateMipMaps does above the tail
-        for (int k = 1; k < nlevels; ++k)
-        {
-            const hipError_t e = launch_resize(levels[k - 1], levels[k], filterMode, filterFlags, true, nullptr, stream, nullptr, marks);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    }
-    if (halving)
+    case TailRoute::HalvingLds:
     {
-        // the LDS tail: RGBA8, no sRGB, every level an exact halving (cubic: clamp addressing; admitted by the caller, checked again here)
         CubicTailArgs c;
         c.src = levels[0].pixels; c.srcPitch = levels[0].rowPitch; c.srcW = levels[0].width; c.srcH = levels[0].height; c.nlevels = nlevels - 1;
-        if (format != FMT_R8G8B8A8_UNORM || (filterFlags & 0x3000077u) || c.nlevels > kTailMaxLevels || c.srcW > kTailSide || c.srcH > kTailSide) return hipErrorInvalidValue;
-        for (int k = 1; k < nlevels; ++k)
-        {
-            if (levels[k].width * 2u != levels[k - 1].width || levels[k].height * 2u != levels[k - 1].height || (levels[k].rowPitch % 4) != 0 ||
-                (reinterpret_cast<uintptr_t>(levels[k].pixels) % 4) != 0) return hipErrorInvalidValue;
-            c.dst[k - 1] = levels[k].pixels; c.dstPitch[k - 1] = levels[k].rowPitch;
-        }
-        for (int k = nlevels - 1; k < kTailMaxLevels; ++k) { c.dst[k] = c.dst[0]; c.dstPitch[k] = c.dstPitch[0]; }
-        if (filterMode == 0x300000u) { DXTEX_MARK("resize_half_tail_rgba8<cubic>"); hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<true>, dim3(1), dim3(1024), 0, stream, c); }
+        for (int k = 0; k < kTailMaxLevels; ++k) { const ImgView& d = levels[k + 1 < nlevels ? k + 1 : 1]; c.dst[k] = d.pixels; c.dstPitch[k] = d.rowPitch; }
+        if (filterMode == DXTEX_FILTER_CUBIC) { DXTEX_MARK("resize_half_tail_rgba8<cubic>"); hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<true>, dim3(1), dim3(1024), 0, stream, c); }
         else { DXTEX_MARK("resize_half_tail_rgba8<box>"); hipLaunchKernelGGL(resize_half_tail_rgba8_kernel<false>, dim3(1), dim3(1024), 0, stream, c); }
-        DXTEX_MARK(nullptr);
-        return hipGetLastError();
+        break;
     }
-    TailArgs t;
-    ResizeArgs& a = t.a;
-    a.stale = no_stale(format);
-    a.src = levels[0];
-    a.dst = a.src;
-    const bool wantIn = srgb_linear_format(format) || (filterFlags & 0x1000000u), wantOut = srgb_linear_format(format) || (filterFlags & 0x2000000u);
-    a.srgbIn = (can_srgb(format) && wantIn) ? 1 : 0;
-    a.srgbOut = (can_srgb(format) && wantOut) ? 1 : 0;
-    a.wrapU = (filterFlags & 0x1u) != 0; a.wrapV = (filterFlags & 0x2u) != 0;
-    a.mirrorU = (filterFlags & 0x10u) != 0; a.mirrorV = (filterFlags & 0x20u) != 0;
-    a.mipAlias = 1;
-    a.triOfsX = nullptr; a.triX = nullptr; a.triOfsY = nullptr; a.triY = nullptr;
-    t.mode = filterMode;
-    t.twoHigh = twoHigh ? *twoHigh : no_stale(format);
-    for (int at = 1; at < nlevels; )
+    case TailRoute::Generic:
     {
-        t.nlevels = std::min(kTailMaxLevels, nlevels - at);
-        for (int k = 0; k < t.nlevels; ++k) t.level[k] = levels[at + k];
-        for (int k = t.nlevels; k < kTailMaxLevels; ++k) t.level[k] = t.level[0];
+        TailArgs t;
+        t.a = resize_args(format, filterFlags, true, nullptr);
+        t.a.src = levels[0];
+        t.a.dst = levels[0];
+        t.nlevels = nlevels - 1;
+        StaleTap<ImgView> tap{ twoHigh ? *twoHigh : no_stale(format) };
+        for (int k = 0; k < kTailMaxLevels; ++k)
+        {
+            const bool used = k + 1 < nlevels;                  // level k + 1 is filtered from level k; unused slots repeat the first level
+            t.level[k] = levels[used ? k + 1 : 1];
+            t.stale[k] = (used && tap.step(levels[k], filterMode == DXTEX_FILTER_BOX)) ? tap.twoHigh : no_stale(format);
+        }
+        t.mode = filterMode;
         DXTEX_MARK("resize_tail");
         hipLaunchKernelGGL(resize_tail_kernel, dim3(1), dim3(1024), 0, stream, t);
-        // a chain with more than kTailMaxLevels tail levels (cannot happen below 64 x 64, kept for safety) continues from the last one written
-        a.src = t.level[t.nlevels - 1];
-        at += t.nlevels;
+        break;
+    }
+    default: return hipErrorInvalidValue;
     }
     DXTEX_MARK(nullptr);
     return hipGetLastError();
-}
-
-bool resize_half_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags)
-{
-    // the LDS tail of a power-of-two RGBA8 chain (resize_cubic_tail_rgba8_kernel): every remaining level halves both sides exactly
-    if (nlevels < 2 || nlevels - 1 > kTailMaxLevels || levels[0].format != FMT_R8G8B8A8_UNORM || (filterFlags & 0x3000077u)) return false;       // sRGB, wrap, mirror bits
-    if (levels[0].width > kTailSide || levels[0].height > kTailSide || (levels[0].rowPitch % 4) != 0 || (reinterpret_cast<uintptr_t>(levels[0].pixels) % 4) != 0) return false;
-    for (int k = 1; k < nlevels; ++k)
-        if (levels[k].width * 2u != levels[k - 1].width || levels[k].height * 2u != levels[k - 1].height || (levels[k].rowPitch % 4) != 0 ||
-            (reinterpret_cast<uintptr_t>(levels[k].pixels) % 4) != 0) return false;
-    return true;
-}
-
-bool resize_cubic_tail_applies(const ImgView* levels, int nlevels, uint32_t filterFlags)
-{
-    return resize_half_tail_applies(levels, nlevels, filterFlags);
-}
-
-bool resize_tail_applies(uint32_t srcW, uint32_t srcH, uint32_t filterMode)
-{
-    // measured (8192^2 chain, rocprofv3): the box tail takes 15.8 us in one workgroup against 6 launches x 3.2 us; the cubic tail 84 us
-    // against 6 x 7 us (sixteen dependent-latency taps per texel and no other workgroup to hide them) - so cubic keeps its launches
-    return srcW <= kTailSide && srcH <= kTailSide && (filterMode == 0x100000u || filterMode == 0x200000u || filterMode == 0x400000u);
 }
 
 hipError_t launch_pmalpha(const ImgView& src, const ImgView& dst, uint32_t pmFlags, hipStream_t stream, KernelMarks* marks)
 {
     const int format = src.format;
     if (!src.width || !src.height) return hipSuccess;
-    // TEX_PMALPHA_IGNORE_SRGB (0x1): plain Load/StoreScanline; otherwise the *Linear wrappers with the SRGB_IN/OUT bits (:68-112)
-    const bool linear = !(pmFlags & 0x1u);
-    const bool wantIn = linear && (srgb_linear_format(format) || (pmFlags & 0x1000000u)), wantOut = linear && (srgb_linear_format(format) || (pmFlags & 0x2000000u));
+    // TEX_PMALPHA_IGNORE_SRGB: plain Load/StoreScanline; otherwise the *Linear wrappers with the SRGB_IN/OUT bits (:68-112), which are TEX_FILTER's
+    const FilterBits f = (pmFlags & DXTEX_PMALPHA_IGNORE_SRGB) ? FilterBits{} : decode_filter(format, pmFlags & (TF_SRGB_IN | TF_SRGB_OUT));
     DXTEX_MARK("pmalpha");
     hipLaunchKernelGGL(pmalpha_kernel, dim3((src.width + 255) / 256, grid_rows(src.height)), dim3(256), 0, stream, src, dst,
-                       (can_srgb(format) && wantIn) ? 1 : 0, (can_srgb(format) && wantOut) ? 1 : 0, (pmFlags & 0x2u) ? 1 : 0);
+                       f.srgbIn, f.srgbOut, (pmFlags & DXTEX_PMALPHA_REVERSE) ? 1 : 0);
     DXTEX_MARK(nullptr);
     return hipGetLastError();
 }
@@ -1579,15 +1549,11 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
 {
     if (!dst.width || !dst.height || !dst.depth) return hipSuccess;
     Resize3Args a;
-    auto vol = [](const VolumeView& v) { Vol o; o.pixels = const_cast<uint8_t*>(v.pixels); o.rowPitch = v.rowPitch; o.slicePitch = v.slicePitch;
-                                         o.width = v.width; o.height = v.height; o.depth = v.depth; o.format = v.format; return o; };
-    a.src = vol(src); a.dst = vol(dst);
+    a.src = src; a.dst = dst;
     const int format = src.format;
-    const bool wantIn = srgb_linear_format(format) || (filterFlags & 0x1000000u), wantOut = srgb_linear_format(format) || (filterFlags & 0x2000000u);
-    a.srgbIn = (can_srgb(format) && wantIn) ? 1 : 0;
-    a.srgbOut = (can_srgb(format) && wantOut) ? 1 : 0;
-    a.wrapU = (filterFlags & 0x1u) != 0; a.wrapV = (filterFlags & 0x2u) != 0; a.wrapW = (filterFlags & 0x4u) != 0;
-    a.mirrorU = (filterFlags & 0x10u) != 0; a.mirrorV = (filterFlags & 0x20u) != 0; a.mirrorW = (filterFlags & 0x40u) != 0;
+    const FilterBits f = decode_filter(format, filterFlags);
+    a.srgbIn = f.srgbIn; a.srgbOut = f.srgbOut;
+    a.wrapU = f.wrapU; a.wrapV = f.wrapV; a.wrapW = f.wrapW; a.mirrorU = f.mirrorU; a.mirrorV = f.mirrorV; a.mirrorW = f.mirrorW;
     a.staleU = staleU ? *staleU : no_stale(format);
     a.staleV = staleV ? *staleV : no_stale(format);
     a.triOfsX = tri ? tri->ofsX : nullptr; a.triX = tri ? reinterpret_cast<const uint2*>(tri->entX) : nullptr;
@@ -1596,11 +1562,11 @@ hipError_t launch_resize3d(const VolumeView& src, const VolumeView& dst, uint32_
     const dim3 grid((dst.width + 255) / 256, dst.height, dst.depth), block(256);
     switch (filterMode)
     {
-    case 0x100000u: DXTEX_MARK("resize3d_point"); hipLaunchKernelGGL(resize3d_point_kernel, grid, block, 0, stream, a); break;
-    case 0x200000u: DXTEX_MARK("resize3d_linear"); hipLaunchKernelGGL(resize3d_linear_kernel, grid, block, 0, stream, a); break;
-    case 0x300000u: DXTEX_MARK("resize3d_cubic"); hipLaunchKernelGGL(resize3d_cubic_kernel, grid, block, 0, stream, a); break;
-    case 0x400000u: DXTEX_MARK("resize3d_box"); hipLaunchKernelGGL(resize3d_box_kernel, grid, block, 0, stream, a); break;
-    case 0x500000u: DXTEX_MARK("resize3d_triangle"); hipLaunchKernelGGL(resize3d_triangle_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_POINT: DXTEX_MARK("resize3d_point"); hipLaunchKernelGGL(resize3d_point_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_LINEAR: DXTEX_MARK("resize3d_linear"); hipLaunchKernelGGL(resize3d_linear_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_CUBIC: DXTEX_MARK("resize3d_cubic"); hipLaunchKernelGGL(resize3d_cubic_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_BOX: DXTEX_MARK("resize3d_box"); hipLaunchKernelGGL(resize3d_box_kernel, grid, block, 0, stream, a); break;
+    case DXTEX_FILTER_TRIANGLE: DXTEX_MARK("resize3d_triangle"); hipLaunchKernelGGL(resize3d_triangle_kernel, grid, block, 0, stream, a); break;
     default: return hipErrorInvalidValue;
     }
     DXTEX_MARK(nullptr);

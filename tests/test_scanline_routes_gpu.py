@@ -5,11 +5,9 @@ The launchers pick a kernel from the shape, the formats and the alignment of the
 profile_end(), whose kernel names (the marks the launchers record) prove which route ran; the output is then compared with the oracle:
 byte-identical, or, where sRGB curves (powf) are involved, within one 8-bit step or one ulp of a float word on fewer than 1 % of words.
 
-Routes that the C ABI cannot reach (findings, kept here so that the table stays complete):
-- launch_resize_tail's per-level cubic branch (a cubic chain that is not an exact-halving RGBA8 clamp chain): submit_resizes only hands a
-  cubic chain to launch_resize_tail after resize_cubic_tail_applies() has accepted it, so that branch never runs; other cubic chains reach
-  resize_cubic / resize_cubic_half_rgba8[_x2] through launch_resize directly (the CUBIC rows below).
-- launch_resize_tail's loop over more than kTailMaxLevels (8) tail levels: a source of at most 64 x 64 has at most 7 levels below it.
+launch_resize_tail has two bodies, the generic tail and the LDS halving tail, and resize_tail_route() decides between them and the per-level
+kernels for the C ABI and the launcher alike: a cubic chain that is no exact-halving RGBA8 clamp chain stays on resize_cubic /
+resize_cubic_half_rgba8[_x2] (the CUBIC rows below), and a chain the predicate rejects is an error in launch_resize_tail.
 """
 import ctypes
 import os
@@ -227,6 +225,15 @@ ROUTES = [
     ("resize_half_tail_rgba8<box>", ("mips", RGBA8, (64, 64), BOX)),
     # launch_mse
     ("mse", ("mse", RGBA8, BGRA8, 64, 32)),
+    # launch_resize_tail, the box filter's stale tap on the W x 1 levels: the two-high level it reads is one the tail itself wrote (32 x 2),
+    # the tail's own first source (64 x 2), or a level before the tail that the host hands in (256 x 2, two per-level launches first).
+    # The W x 1 levels are no exact halvings, so RGBA8 takes the generic tail here too.
+    ("resize_tail", ("mips", RGBA16F, (64, 4), BOX)),
+    ("resize_tail", ("mips", RGBA8, (64, 4), BOX)),
+    ("resize_tail", ("mips", RGBA16F, (128, 4), BOX)),
+    ("resize_tail", ("mips", RGBA8, (128, 4), BOX)),
+    ("resize_tail", ("mips", RGBA16F, (256, 2), BOX)),
+    ("resize_tail", ("mips", RGBA8, (256, 2), BOX)),
 ]
 
 
@@ -242,6 +249,8 @@ def test_route(ctx, oracle, route, call):
     else:
         got, ref, names = _run_mse(ctx, oracle, *args)
     assert route in names, (route, sorted(names))
+    if route == "resize_tail":
+        assert "resize_half_tail_rgba8<box>" not in names, sorted(names)
     if kind == "mse":
         assert np.allclose(got, ref, rtol=1e-6, atol=0), (got, ref)
     else:
