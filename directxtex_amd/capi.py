@@ -152,6 +152,9 @@ _SIGS = {
     "dxtex_difference_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_copy_rectangle": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Rect), _P(Image), ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t]),
     "dxtex_copy_rectangles_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Rect), _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_uint32]),
+    "dxtex_planar_to_single": (ctypes.c_int32, [ctypes.c_int32]),
+    "dxtex_convert_to_single_plane": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image)]),
+    "dxtex_convert_to_single_plane_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t]),
     "dxtex_merge_image": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
     "dxtex_merge_image_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
     "dxtex_device_alloc": (ctypes.c_int32, [_ctx_p, ctypes.c_size_t, _P(ctypes.c_void_p)]),
@@ -203,6 +206,24 @@ def compute_pitch(fmt, width, height):
     return rp.value, sp.value
 
 
+def planar_to_single(fmt):
+    """PlanarToSingle: the single-plane format ConvertToSinglePlane gives a planar one (NV12, NV11 -> YUY2; P010 -> Y210; P016 -> Y216),
+    0 where there is none."""
+    return int(_lib.dxtex_planar_to_single(fmt))
+
+
+def _planar_pitches(fmt, width, height):
+    """ComputePitch (DirectXTexUtil.cpp:1054-1112) of the planar formats ConvertToSinglePlane takes: (rowPitch, slicePitch). Only the
+    default layout of Context.convert_to_single_plane; the C ABI takes both pitches from the caller."""
+    if fmt == 110:                      # NV11
+        row = ((width + 3) >> 2) * 4
+        return row, row * height * 2
+    if fmt not in (103, 104, 105):      # NV12, P010, P016
+        raise DxtexError(-2147024846, "no single-plane form")
+    row = ((width + 1) >> 1) * (2 if fmt == 103 else 4)
+    return row, row * (height + ((height + 1) >> 1))
+
+
 def is_compressed(fmt):
     return bool(_lib.dxtex_is_compressed(fmt))
 
@@ -222,11 +243,17 @@ def _host_image(arr, width, height, fmt, row_pitch=None):
     return Image(width, height, fmt, rp, sp, arr.ctypes.data)
 
 
-def device_image(ptr, width, height, fmt, row_pitch=None):
+def device_image(ptr, width, height, fmt, row_pitch=None, slice_pitch=None):
+    """A dxtex_image on device memory. The pitches default to compute_pitch's; a planar source (convert_to_single_plane_device), which
+    compute_pitch does not take, is described by both row_pitch and slice_pitch."""
+    if row_pitch is not None and slice_pitch is not None:
+        return Image(width, height, fmt, row_pitch, slice_pitch, ptr)
     rp, sp = compute_pitch(fmt, width, height)
     if row_pitch is not None:
         rows = sp // rp
         rp, sp = row_pitch, row_pitch * rows
+    if slice_pitch is not None:
+        sp = slice_pitch
     return Image(width, height, fmt, rp, sp, ptr)
 
 
@@ -542,6 +569,32 @@ class Context:
         r = (Rect * m)(*[Rect(*q) for q in rects])
         xs, ys = (ctypes.c_size_t * m)(*x_offsets), (ctypes.c_size_t * m)(*y_offsets)
         self._check(self._lib.dxtex_copy_rectangles_device(self._h, a, r, b, xs, ys, n, filter_flags), "copy_rectangles_device")
+
+    # -- ConvertToSinglePlane ---------------------------------------------------------------------------
+    def convert_to_single_plane(self, pixels, width, height, fmt, row_pitch=None, slice_pitch=None):
+        """dxtex_convert_to_single_plane: the planar host image `pixels` (NV12, P010, P016, NV11; ComputePitch's layout unless row_pitch /
+        slice_pitch say otherwise) -> its single-plane form (planar_to_single(fmt)) as bytes with tight pitch, zero where the reference's
+        end guard leaves elements unwritten (a slice_pitch below the layout's)."""
+        pixels = np.ascontiguousarray(pixels).view(np.uint8).reshape(-1)
+        nrp, nsp = _planar_pitches(fmt, width, height) if planar_to_single(fmt) else (0, 0)
+        rp = nrp if row_pitch is None else row_pitch
+        sp = slice_pitch if slice_pitch is not None else (nsp // nrp) * rp if nrp else 0
+        assert pixels.nbytes >= sp, (pixels.nbytes, sp)
+        dfmt = planar_to_single(fmt)
+        drp, dsp = compute_pitch(dfmt, width, height) if dfmt else (0, 0)
+        out = np.zeros(max(dsp, 1), np.uint8)
+        src = Image(width, height, fmt, rp, sp, pixels.ctypes.data)
+        dst = Image(width, height, dfmt, drp, dsp, out.ctypes.data)
+        self._check(self._lib.dxtex_convert_to_single_plane(self._h, ctypes.byref(src), ctypes.byref(dst)), "convert_to_single_plane")
+        return out[:dsp]
+
+    def convert_to_single_plane_device(self, srcs, dsts):
+        """dxtex_convert_to_single_plane_device: lists of device Images (device_image with row_pitch and slice_pitch for the planar
+        sources), one kernel launch per 32 of them; asynchronous on the context's stream."""
+        n = len(srcs)
+        m = max(n, 1)
+        a, b = (Image * m)(*srcs), (Image * m)(*dsts)
+        self._check(self._lib.dxtex_convert_to_single_plane_device(self._h, a, b, n), "convert_to_single_plane_device")
 
     @staticmethod
     def _merge_args(permute, zero, one):

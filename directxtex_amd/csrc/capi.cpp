@@ -9,6 +9,7 @@
 #include "dxtex_diag.h"
 #include "dxtex_plan.h"
 #include "dxtex_copyrect.h"
+#include "dxtex_plane.h"
 #include "triangle_filter.h"
 
 #include <hip/hip_runtime.h>
@@ -1992,6 +1993,85 @@ dxtex_hresult dxtex_copy_rectangle(dxtex_ctx* ctx, const dxtex_image* src, const
     if (hr != DXTEX_S_OK) return hr;
     ctx->d2hBytes += downRow * rect->h;
     HIP_TRY(ctx, rows_copy(dst->pixels + yOffset * dst->rowPitch + xOffset * dbpp, dst->rowPitch, d.pixels, downRow, downRow, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+// ---- ConvertToSinglePlane ------------------------------------------------------------------------------------------------------------------
+namespace
+{
+const char* plane_error(int32_t hr, const dxtex_image& src)
+{
+    if (hr == kPlanePointer) return "null pixels";
+    if (hr == kPlaneNotSupported) return "this planar format has no single-plane form";
+    if (hr == kPlaneFail) return "the destination's size differs from the source's";
+    if (!plane_is_planar(src.format)) return "the source format is not planar";
+    return "ConvertToSinglePlane: odd size (a width that is no multiple of four for NV11), or pitches, alignment, destination format or overlap";
+}
+
+// plane_check (dxtex_plane.h) on the caller's images: pitches are the caller's, nothing is computed from the format
+dxtex_hresult check_single_plane(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, PlaneJob* job)
+{
+    const PlaneImage s = { src.width, src.height, src.format, src.rowPitch, src.slicePitch, uint64_t(reinterpret_cast<uintptr_t>(src.pixels)) };
+    const PlaneImage d = { dst.width, dst.height, dst.format, dst.rowPitch, dst.slicePitch, uint64_t(reinterpret_cast<uintptr_t>(dst.pixels)) };
+    const int32_t hr = plane_check(s, d, job);
+    return hr == kPlaneOk ? DXTEX_S_OK : fail(ctx, hr, plane_error(hr, src));
+}
+} // namespace
+
+int32_t dxtex_planar_to_single(int32_t format) { return plane_to_single(format); }
+
+dxtex_hresult dxtex_convert_to_single_plane_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!srcs || !dsts || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
+    std::vector<PlaneJob> jobs(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_hresult hr = check_single_plane(ctx, srcs[i], dsts[i], &jobs[i]);
+        if (hr != DXTEX_S_OK) return hr;
+    }
+    return run_timed(ctx, [&] { return launched(ctx, launch_single_plane(jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_convert_to_single_plane(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    PlaneJob host, job;
+    dxtex_hresult hr = check_single_plane(ctx, *src, *dst, &host);
+    if (hr != DXTEX_S_OK) return hr;
+    if (!host.elems || !host.units) return DXTEX_S_OK;
+    // The source goes up as it is, slicePitch bytes with the caller's pitches; the destination in the staging has rows of the element bytes
+    // rounded up to 16 (so the wide route can run), and only the elements the kernel wrote come back into the caller's rows.
+    const size_t rowBytes = size_t(host.elems) * plane_elem_bytes(host), rows = src->height;
+    dxtex_image s = *src, d = *dst;
+    d.rowPitch = (rowBytes + 15u) & ~size_t(15);
+    d.slicePitch = d.rowPitch * rows;
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, s.slicePitch); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, d.slicePitch); if (hr != DXTEX_S_OK) return hr;
+    s.pixels = ctx->stageIn.u8(); d.pixels = ctx->stageOut.u8();
+    hr = check_single_plane(ctx, s, d, &job);
+    if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, s.pixels, src->pixels, s.slicePitch, hipMemcpyHostToDevice, ctx->stream));
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_single_plane(&job, 1, ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    // the end guard leaves whole rows first and then cut ones (plane_pairs does not grow with the unit): the whole rows in one copy
+    const size_t unitRows = job.nv11 ? 1 : 2;
+    uint32_t whole = 0;
+    while (whole < job.units && plane_written_elems(job, whole) == job.elems) ++whole;
+    if (whole)
+    {
+        ctx->d2hBytes += rowBytes * whole * unitRows;
+        HIP_TRY(ctx, hipMemcpy2DAsync(dst->pixels, dst->rowPitch, d.pixels, d.rowPitch, rowBytes, whole * unitRows, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    for (uint32_t unit = whole; unit < job.units; ++unit)
+    {
+        const size_t bytes = size_t(plane_written_elems(job, unit)) * plane_elem_bytes(job);
+        for (size_t y = unit * unitRows; bytes && y < (unit + 1) * unitRows; ++y)
+            HIP_TRY(ctx, counted_copy(ctx, dst->pixels + y * dst->rowPitch, d.pixels + y * d.rowPitch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }

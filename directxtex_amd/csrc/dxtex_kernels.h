@@ -93,6 +93,10 @@ struct MergeArgs;
 hipError_t launch_copy_rects(const CopyJob* jobs, size_t count, hipStream_t stream, KernelMarks* marks = nullptr);
 hipError_t launch_merge(const ImgView& a, const ImgView& b, const ImgView& dst, const MergeArgs& args, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// ConvertToSinglePlane: `count` resolved images (dxtex_plane.h; plane_check has checked every bound), kPlaneBatchMax of them per launch.
+struct PlaneJob;
+hipError_t launch_single_plane(const PlaneJob* jobs, size_t count, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // Resize / one mip level: src is filtered (as src.format) into dst, whose rows are written in dst.format (R32G32B32A32_FLOAT rows for
 // launch_pack_group, src.format otherwise). filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row

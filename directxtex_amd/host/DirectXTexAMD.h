@@ -427,6 +427,16 @@ HRESULT CopyTopLevels(Device& device, const DeviceScratchImage& src, DeviceScrat
 // device-resident images of one format (e.g. the top levels of a chain).
 bool IsAlphaAllOpaque(Device& device, const DeviceScratchImage& image) noexcept;
 bool IsAlphaAllOpaque(Device& device, const Image* deviceImages, size_t nimages) noexcept;
+// ---- ConvertToSinglePlane (DirectXTexAMD_Plane.cpp) --------------------------------------------------------------------------------------
+// ConvertToSinglePlane (DirectXTex.h:826-831, DirectXTexConvert.cpp:5411-5523) with the device in front: NV12 / NV11 -> YUY2, P010 -> Y210,
+// P016 -> Y216, the reference's validation, end guard and release-on-failure (see dxtex_convert_to_single_plane in dxtex_amd.h). The
+// planar formats stay outside IsSupportedOnDevice(): this is the one device entry point that takes them. A ScratchImage or
+// DeviceScratchImage holds a planar texture as the reference lays it out (ComputePitch's pitches, one blob).
+HRESULT ConvertToSinglePlane(Device& device, const Image& srcImage, ScratchImage& image) noexcept;
+// array items x mips: every source goes up as the caller describes it, ONE batched submission, one download
+HRESULT ConvertToSinglePlane(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, ScratchImage& result) noexcept;
+// resident: ONE batched submission on the Device's stream; the result can be handed to Convert, Resize, ... at once
+HRESULT ConvertToSinglePlane(Device& device, const DeviceScratchImage& src, DeviceScratchImage& result) noexcept;
 // ---- CopyRectangle and texassemble's steps (DirectXTexAMD_Assemble.cpp) -----------------------------------------------------------------
 struct Rect
 {

@@ -352,7 +352,6 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         else { std::printf(" FAILED: only .dds, .tga and .hdr can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
         std::fflush(stdout);
-        if (IsPlanar(in->info.format)) { std::printf("\nERROR: planar inputs are not supported\n"); return 1; }
         inputs.push_back(std::move(in));
     }
     // texassemble.cpp:1995-2035
@@ -392,6 +391,11 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         inputs[index]->image.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
+        if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
+        {
+            hr = ConvertToSinglePlane(dev, cur, next); if (FAILED(hr)) return Fail(" FAILED [converttosingleplane]", hr);
+            step();
+        }
         if (IsCompressed(info.format))
         {
             hr = Decompress(dev, cur, DXGI_FORMAT_UNKNOWN, next); if (FAILED(hr)) return Fail(" FAILED [decompress]", hr);

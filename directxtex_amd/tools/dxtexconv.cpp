@@ -331,7 +331,6 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     std::printf("reading %s (%zux%zu", inFile.c_str(), info.width, info.height);
     if (info.dimension == TEX_DIMENSION_TEXTURE3D) std::printf("x%zu", info.depth);
     std::printf(", %zu mips, %zu items, format %u)\n", info.mipLevels, info.arraySize, unsigned(info.format));
-    const DXGI_FORMAT tformat = o.format ? DXGI_FORMAT(o.format) : info.format;
     size_t tMips = (!o.mipLevels && info.mipLevels > 1) ? info.mipLevels : o.mipLevels;           // texconv.cpp:2270
 
     // --- the one upload
@@ -342,6 +341,15 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         const uint32_t misc2 = info.miscFlags2;
         image = std::move(t); info = image.GetMetadata(); info.miscFlags2 = misc2;
     };
+
+    // --- planar (texconv.cpp:2277-2312): NV12 / P010 / P016 / NV11 become their single-plane forms on the device, before anything else
+    if (IsPlanar(info.format))
+    {
+        DeviceScratchImage t;
+        check("converttosingleplane", ConvertToSinglePlane(dev, image, t));
+        keep(t);
+    }
+    const DXGI_FORMAT tformat = o.format ? DXGI_FORMAT(o.format) : info.format;
 
     // --- decompress (texconv.cpp:2325-2480). The compressed original is kept (on the host, where it already is, and on the device for the
     // alpha scan): if no step below changes the texels and the target is its format, it is written back as it is instead of being encoded again.

@@ -161,11 +161,19 @@ bool Parse(int argc, char** argv, Options& o)
     return true;
 }
 
-HRESULT Load(const Options& o, const std::string& file, TexMetadata& info, ScratchImage& image)
+// the loader of all three commands; a planar file becomes its single-plane form on the device, as texdiag's loader makes it (texdiag.cpp:3959-3972)
+HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata& info, ScratchImage& image)
 {
     if (hasExt(file, ".hdr")) return LoadFromHDRFile(file.c_str(), &info, image);
     if (hasExt(file, ".tga")) return LoadFromTGAFile(file.c_str(), TGA_FLAGS_NONE, &info, image);
-    return LoadFromDDSFile(file.c_str(), DDS_FLAGS(o.ddsRead), &info, image);
+    HRESULT hr = LoadFromDDSFile(file.c_str(), DDS_FLAGS(o.ddsRead), &info, image);
+    if (FAILED(hr) || !IsPlanar(info.format)) return hr;
+    ScratchImage single;
+    hr = ConvertToSinglePlane(dev, image.GetImages(), image.GetImageCount(), info, single);
+    if (FAILED(hr)) return hr;
+    info.format = single.GetMetadata().format;
+    image = std::move(single);
+    return S_OK;
 }
 
 void Print(const AnalyzeData& d)
@@ -219,7 +227,7 @@ int RunAnalyze(Device& dev, const Options& o)
     {
         TexMetadata info;
         ScratchImage image;
-        HRESULT hr = Load(o, file, info, image);
+        HRESULT hr = Load(dev, o, file, info, image);
         if (FAILED(hr)) return Fail((" FAILED loading " + file).c_str(), hr);
         std::printf("%s\n", file.c_str());
         // the whole file goes up once; every image is analysed on the device, the figures come back in one copy
@@ -275,9 +283,9 @@ int RunCompare(Device& dev, const Options& o)
 {
     TexMetadata info1, info2;
     ScratchImage image1, image2;
-    HRESULT hr = Load(o, o.files[0], info1, image1);
+    HRESULT hr = Load(dev, o, o.files[0], info1, image1);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[0]).c_str(), hr);
-    hr = Load(o, o.files[1], info2, image2);
+    hr = Load(dev, o, o.files[1], info2, image2);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[1]).c_str(), hr);
     if (info1.width != info2.width || info1.height != info2.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
     if ((info1.depth == 1 && info1.arraySize == 1 && info1.mipLevels == 1) || info1.depth != info2.depth || info1.arraySize != info2.arraySize ||
@@ -335,9 +343,9 @@ int RunDiff(Device& dev, const Options& o)
 {
     TexMetadata info1, info2;
     ScratchImage image1, image2, diff;
-    HRESULT hr = Load(o, o.files[0], info1, image1);
+    HRESULT hr = Load(dev, o, o.files[0], info1, image1);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[0]).c_str(), hr);
-    hr = Load(o, o.files[1], info2, image2);
+    hr = Load(dev, o, o.files[1], info2, image2);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[1]).c_str(), hr);
     if (info1.width != info2.width || info1.height != info2.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
     if (image1.GetImageCount() > 1 || image2.GetImageCount() > 1) std::printf("WARNING: ignoring all images but first one in each file\n");

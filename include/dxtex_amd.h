@@ -27,6 +27,7 @@
  *   texdiag's Analyze / AnalyzeBC / Difference Texdiag/texdiag.cpp:698-1320    dxtex_analyze / dxtex_analyze_bc / dxtex_difference
  *   CopyRectangle                              DirectXTexMisc.cpp:275-381      dxtex_copy_rectangle / dxtex_copy_rectangles_device
  *   texassemble's merge lambda                 Texassemble/texassemble.cpp:2236-2268  dxtex_merge_image
+ *   ConvertToSinglePlane                       DirectXTexConvert.cpp:4912-5077, :5411-5523  dxtex_convert_to_single_plane[_device]
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -372,6 +373,38 @@ dxtex_hresult dxtex_merge_image(dxtex_ctx* ctx, const dxtex_image* a, const dxte
                                 const uint32_t zero[4], const uint32_t one[4]);
 dxtex_hresult dxtex_merge_image_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4],
                                        const uint32_t zero[4], const uint32_t one[4]);
+
+/* ---- ConvertToSinglePlane (DirectXTexConvert.cpp:4912-5077, :5411-5523) ------------------------------------------------------------- */
+
+/* PlanarToSingle (:4916-4939): NV12 (103) and NV11 (110) -> YUY2 (107), P010 (104) -> Y210 (108), P016 (105) -> Y216 (109); 0 where a
+ * format has no single-plane form. A separate door: the planar formats stay unknown to every other entry point of this header
+ * (dxtex_bits_per_pixel is 0 for them, dxtex_compute_pitch does not take them). */
+int32_t       dxtex_planar_to_single(int32_t format);
+
+/* The planar image `src` interleaved into `dst`, which has the same size and the format dxtex_planar_to_single(src->format).
+ *   4:2:0 (NV12: 1-byte samples; P010 / P016: 2-byte samples): element k of destination rows 2c and 2c + 1 is
+ *     (Y[row][2k], U, Y[row][2k + 1], V) with U, V the samples 2k and 2k + 1 of chroma row c. The chroma plane starts at byte
+ *     height * rowPitch of the source, its rows are rowPitch apart.
+ *   NV11 (4:1:1): chroma pair j of row y, at byte height * rowPitch + y * (rowPitch >> 1) + 2j, feeds elements 2j and 2j + 1 of row y,
+ *     whose luma is samples 4j .. 4j + 3 of luma row y.
+ *   The reference's end guard is kept byte for byte (`if ((sPtrUV + 1) >= sourceE) break;` with sourceE = pixels + slicePitch): a chroma
+ *     pair whose second sample lies at or beyond slicePitch is not read, and neither it nor any later pair of that chroma row is written.
+ *     With ComputePitch's slicePitch that never happens; with a smaller slicePitch the tail of the last rows of dst stays as it was.
+ * Both pitches of both images are the caller's; nothing is derived from the format. No byte at or beyond src->pixels + src->slicePitch is
+ * read; only the written elements of dst are written, never its row padding.
+ * HRESULTs, in the reference's order (:5413-5424, :5005-5030): E_INVALIDARG for a source format that is not planar; E_POINTER for null
+ * pixels; DXTEX_E_NOT_SUPPORTED for a planar format without a single-plane form (420_OPAQUE, P208, V208, V408, the Xbox depth planes);
+ * E_INVALIDARG for an odd width or height (NV12, P010, P016) or a width that is no multiple of four (NV11). Added here, where the
+ * reference would read outside the image it was handed or has no destination of the caller's to get wrong, in this order: E_INVALIDARG
+ * for dst->format != dxtex_planar_to_single(src->format); E_FAIL for a destination of another size; E_INVALIDARG for a source rowPitch
+ * below the row's bytes, for slicePitch < height * rowPitch, for an odd pointer or pitch with the 16-bit formats, for a destination
+ * rowPitch below its row's bytes, and where the bytes read and the bytes written overlap.
+ * dxtex_convert_to_single_plane: host pointers, through the context's staging; uploads slicePitch bytes, downloads the elements it wrote.
+ * dxtex_convert_to_single_plane_device: `count` independent images on device memory, asynchronous on the context's stream, ONE kernel
+ * launch per 32 images (the jobs travel in the kernel's argument block). All are checked before anything is queued. Per image the
+ * 16-byte route runs when the row starts of luma and chroma are 8-byte aligned and those of dst 16-byte aligned, else element by element. */
+dxtex_hresult dxtex_convert_to_single_plane(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst);
+dxtex_hresult dxtex_convert_to_single_plane_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count);
 
 /* PremultiplyAlpha / its REVERSE (DirectXTex.h:864-884, DirectXTexPMAlpha.cpp:214-262): same size and format on both sides,
  * the format must carry alpha (else DXTEX_E_NOT_SUPPORTED). `flags` = TEX_PMALPHA_FLAGS. */
