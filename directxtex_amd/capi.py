@@ -134,6 +134,8 @@ _SIGS = {
     "dxtex_compute_normal_map_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_transform_image": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Transform)]),
     "dxtex_transform_images_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, _P(Transform)]),
+    "dxtex_rotate_color": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_rotate_color_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -699,6 +701,24 @@ class Context:
         n = len(srcs)
         a, b = (Image * max(n, 1))(*srcs), (Image * max(n, 1))(*dsts)
         self._check(self._lib.dxtex_transform_images_device(self._h, a, b, n, ctypes.byref(transform)), "transform_images_device")
+
+    # -- texconv's HDR colour rotation ----------------------------------------------------------------------------------------------
+    def rotate_color(self, pixels, width, height, fmt, rotate, paper_white_nits=200.0, row_pitch=None):
+        """dxtex_rotate_color: one image (host pixels) through rotate = ROTATE_* (formats.py). Returns the destination (tight pitch) as
+        a numpy uint8 buffer."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        rp, sp = compute_pitch(fmt, width, height)
+        out = np.zeros(sp, np.uint8)
+        dst = Image(width, height, fmt, rp, sp, out.ctypes.data)
+        self._check(self._lib.dxtex_rotate_color(self._h, ctypes.byref(src), ctypes.byref(dst), rotate, paper_white_nits), "rotate_color")
+        return out
+
+    def rotate_color_device(self, srcs, dsts, rotate, paper_white_nits=200.0):
+        """dxtex_rotate_color_device: lists of device Images (device_image) of one format, asynchronous on the context's stream."""
+        n = len(srcs)
+        a, b = (Image * max(n, 1))(*srcs), (Image * max(n, 1))(*dsts)
+        self._check(self._lib.dxtex_rotate_color_device(self._h, a, b, n, rotate, paper_white_nits), "rotate_color_device")
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

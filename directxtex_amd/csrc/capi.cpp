@@ -6,6 +6,7 @@
 #include "dxtex_kernels.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
+#include "dxtex_rotate.h"
 #include "dxtex_diag.h"
 #include "dxtex_plan.h"
 #include "dxtex_copyrect.h"
@@ -1432,6 +1433,65 @@ dxtex_hresult dxtex_transform_image(dxtex_ctx* ctx, const dxtex_image* src, cons
     dxtex_hresult hr = check_transform(ctx, src, dst, src && dst ? 1 : 0, t, &args);
     if (hr != DXTEX_S_OK) return hr;
     return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_transform(ctx, &s, &d, 1, t->op, args); });
+}
+
+namespace
+{
+// The colour rotation's checks over `count` source / destination pairs of one format: TransformImage's (check_transform), with texconv's
+// own rules for the operation and the paper-white level (texconv.cpp:1545-1553, :1891-1903); resolves the matrix and the curve.
+dxtex_hresult check_rotate_color(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t rotate, float nits,
+                                 RotateArgs* args, int* curve)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!srcs || !dsts || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
+    const int format = srcs[0].format;
+    const FmtInfo* f = format_info(format);
+    if (!f || (f->cls & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the colour rotation does not take planar, palettised, compressed or typeless formats");
+    if (!rotate_resolve(rotate, nits, *args, *curve)) return fail(ctx, DXTEX_E_INVALIDARG, "unknown colour rotation");
+    if (!rotate_nits_valid(nits)) return fail(ctx, DXTEX_E_INVALIDARG, "the paper-white level must be above 0 and at most 10000 nits");
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_image& s = srcs[i];
+        const dxtex_image& d = dsts[i];
+        if (s.width > 0xFFFFFFFFull || s.height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+        if (s.format != format || d.format != format) return fail(ctx, DXTEX_E_FAIL, "format mismatch");
+        if (s.width != d.width || s.height != d.height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
+        if (!s.pixels || !d.pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+        if (s.width && s.height) { const dxtex_hresult hr = check_no_overlap(ctx, s, d); if (hr != DXTEX_S_OK) return hr; }
+    }
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult submit_rotate_color(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, int curve, const RotateArgs& args)
+{
+    KernelMarks* marks = marks_of(ctx);
+    for (size_t i = 0; i < count; ++i)
+    {
+        if (!srcs[i].width || !srcs[i].height) continue;
+        const ImgView sv = view_of(srcs[i]);
+        const dxtex_hresult hr = launch_into(ctx, view_of(dsts[i]), marks, [&](const ImgView& out) { return launch_rotate_color(sv, out, curve, args, ctx->stream, marks); });
+        if (hr != DXTEX_S_OK) return hr;
+    }
+    return DXTEX_S_OK;
+}
+} // namespace
+
+dxtex_hresult dxtex_rotate_color_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t rotate, float paperWhiteNits)
+{
+    RotateArgs args;
+    int curve = 0;
+    const dxtex_hresult hr = check_rotate_color(ctx, srcs, dsts, count, rotate, paperWhiteNits, &args, &curve);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_rotate_color(ctx, srcs, dsts, count, curve, args); });
+}
+
+dxtex_hresult dxtex_rotate_color(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t rotate, float paperWhiteNits)
+{
+    RotateArgs args;
+    int curve = 0;
+    const dxtex_hresult hr = check_rotate_color(ctx, src, dst, src && dst ? 1 : 0, rotate, paperWhiteNits, &args, &curve);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rotate_color(ctx, &s, &d, 1, curve, args); });
 }
 
 namespace

@@ -85,6 +85,12 @@ hipError_t launch_transform(const ImgView& src, const ImgView& dst, uint32_t op,
                             KernelMarks* marks = nullptr);
 hipError_t launch_tonemap_max(const ImgView& src, uint32_t* maxBits, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// texconv's colour rotation of one image (the size is src's): LoadScanline -> the operation's matrix and curve (curve = ROTATE_CURVE_*,
+// args resolved by the caller with rotate_resolve, see dxtex_rotate.h) on r, g and b -> StoreScanline with threshold 0. dst's rows as for
+// launch_normal_map. A format of DXTEX_QUAD_FORMATS with 16-byte aligned rows on both sides takes four texels per lane (rotate_color.hip).
+struct RotateArgs;
+hipError_t launch_rotate_color(const ImgView& src, const ImgView& dst, int curve, const RotateArgs& args, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

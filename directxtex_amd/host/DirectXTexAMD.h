@@ -321,6 +321,21 @@ bool IsIdentitySwizzle(const TexTransform& transform) noexcept;       // texconv
 HRESULT TransformImage(Device& device, const Image& srcImage, const TexTransform& transform, ScratchImage& result) noexcept;
 HRESULT TransformImage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, const TexTransform& transform,
                        ScratchImage& result) noexcept;
+// texconv's HDR colour rotation (Texconv/texconv.cpp:2696-2964), the TransformImage lambdas it runs for -rotatecolor: r, g and b move
+// between the Rec.709, Rec.2020 and Display-P3 (D65) primaries, and into or out of HDR10 (Rec.2020 with the SMPTE ST.2084 curve;
+// paperWhiteNits, in (0, 10000], is the level of linear 1.0 and is read by the three HDR10 operations only). The values are texconv's
+// ROTATE_* (texconv.cpp:181-188). Checks and HRESULTs are TransformImage's, with E_INVALIDARG for a bad operation or paper-white level.
+// texconv converts to R16G16B16A16_FLOAT before HDR10_TO_709 and P3D65_TO_709 (:2699-2733): that step is the caller's (Convert). The
+// array form uploads the set once, rotates it on the device and downloads it once. The result has the source's metadata; on failure it
+// is released.
+enum TEX_ROTATE_COLOR : uint32_t
+{
+    TEX_ROTATE_709_TO_HDR10 = 1, TEX_ROTATE_HDR10_TO_709 = 2, TEX_ROTATE_709_TO_2020 = 3, TEX_ROTATE_2020_TO_709 = 4,
+    TEX_ROTATE_P3D65_TO_HDR10 = 5, TEX_ROTATE_P3D65_TO_2020 = 6, TEX_ROTATE_709_TO_P3D65 = 7, TEX_ROTATE_P3D65_TO_709 = 8,
+};
+HRESULT RotateColor(Device& device, const Image& srcImage, TEX_ROTATE_COLOR rotate, float paperWhiteNits, ScratchImage& result) noexcept;
+HRESULT RotateColor(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, TEX_ROTATE_COLOR rotate, float paperWhiteNits,
+                    ScratchImage& result) noexcept;
 // ScaleMipMapsAlphaForCoverage (DirectXTex.h:848-851): mipChain must already be initialised with the chain's layout
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, size_t item,
                                      float alphaReference, ScratchImage& mipChain) noexcept;
@@ -413,6 +428,7 @@ HRESULT Convert(Device& device, const DeviceScratchImage& src, DXGI_FORMAT forma
 HRESULT PremultiplyAlpha(Device& device, const DeviceScratchImage& src, TEX_PMALPHA_FLAGS flags, DeviceScratchImage& result) noexcept;
 HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, DeviceScratchImage& normalMaps) noexcept;
 HRESULT TransformImage(Device& device, const DeviceScratchImage& src, const TexTransform& transform, DeviceScratchImage& result) noexcept;
+HRESULT RotateColor(Device& device, const DeviceScratchImage& src, TEX_ROTATE_COLOR rotate, float paperWhiteNits, DeviceScratchImage& result) noexcept;
 // the diagnostics on resident images: image 0 of each side for ComputeMSE and Difference, every image (results[GetImageCount()]) for Analyze / AnalyzeBC
 HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, float& mse, float* mseV, CMSE_FLAGS flags) noexcept;
 HRESULT Analyze(Device& device, const DeviceScratchImage& images, AnalyzeData* results) noexcept;

@@ -1,10 +1,10 @@
 // dxtexconv - a texconv-style batch converter on top of the MI355X host layer (DirectXTexAMD.h): DDS in, DDS out, every
 // image-processing step on the GPU. The pipeline and its order are the reference tool's (Texconv/texconv.cpp): load (:2077-2090)
-// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> swizzle (:2645-2694) -> tone map
-// (:2966-3044) -> normal map (:3047-3098) or convert (:3100-3140) -> colour key (:3134-3191) -> invert Y (:3193-3240) -> reconstruct Z
+// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> swizzle (:2645-2694) -> colour
+// rotation (:2696-2964) -> tone map (:2966-3044) -> normal map (:3047-3098) or convert (:3100-3140) -> colour key (:3134-3191) -> invert Y (:3193-3240) -> reconstruct Z
 // (:3242-3301) -> mipmaps (:3302-3460) -> alpha-coverage preservation (:3462-3500) -> premultiply alpha (:3502-3545) -> compress
 // (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
-// rotations, HDR colour rotation, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
+// rotations, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
 //   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga>...        (-ft hdr | tga: Radiance / TGA output of level 0)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
@@ -19,6 +19,10 @@
 //     -swizzle <mask>      1-4 of rgbaxyzw01, the last repeated (e.g. bgr1, rrrg)    -tonemap   Reinhard tone map to LDR (maximum over all images)
 //     -c <hex-RGB>         colour key: texels near it become transparent (formats with alpha)    -inverty   g = 1 - g    -reconstructz   z from x, y
 //                          texconv's long names work too: --swizzle --tonemap --color-key --invert-y --reconstruct-z
+//     --rotate-color <op>  709toHDR10 HDR10to709 709to2020 2020to709 P3D65toHDR10 P3D65to2020 709toP3D65 P3D65to709 (either case): the HDR
+//                          colour rotation; HDR10to709 and P3D65to709 convert to R16G16B16A16_FLOAT first, as texconv does
+//     --paper-white-nits <n>   the level of linear 1.0 for the HDR10 operations, in (0, 10000], default 200
+//                          only under texconv's long names (with one or two dashes): its short -rotatecolor and -nits stay refused
 //     -dword -badtails -permissive -ignoremips -xlum            DDS reader tolerances (DDS_FLAGS)
 //     -dx10 -dx9           force the 'DX10' header (+ alpha mode) / a Direct3D 9 file        -tga20   TGA output with the 2.0 extension area
 //     -px <s> -sx <s> -l   output name prefix / suffix, lower case    -y   overwrite    -info (print what the files hold, no GPU)    -timing -nologo -gpu <n> | -gpus <a,b,...> (files dealt out over the GPUs)
@@ -73,6 +77,11 @@ const Name kFilters[] = {
 const Name kFeatureLevels[] = {         // largest 2D texture side (texconv.cpp:880-905)
     { "9.1", 2048 }, { "9.2", 2048 }, { "9.3", 4096 }, { "10.0", 8192 }, { "10.1", 8192 }, { "11.0", 16384 }, { "11.1", 16384 }, { "12.0", 16384 }, { "12.1", 16384 }, { "12.2", 16384 },
 };
+const Name kRotations[] = {           // g_pRotateColor (texconv.cpp:543-554)
+    { "709to2020", TEX_ROTATE_709_TO_2020 }, { "2020to709", TEX_ROTATE_2020_TO_709 }, { "709toHDR10", TEX_ROTATE_709_TO_HDR10 },
+    { "HDR10to709", TEX_ROTATE_HDR10_TO_709 }, { "P3D65to2020", TEX_ROTATE_P3D65_TO_2020 }, { "P3D65toHDR10", TEX_ROTATE_P3D65_TO_HDR10 },
+    { "709toP3D65", TEX_ROTATE_709_TO_P3D65 }, { "P3D65to709", TEX_ROTATE_P3D65_TO_709 },
+};
 constexpr uint32_t TEX_FILTER_SEPARATE_ALPHA = 0x100;
 
 bool lookup(const Name* t, size_t n, const char* s, uint32_t& out, bool numbers = true)
@@ -97,6 +106,8 @@ struct Options
     TexTransform swizzle;               // -swizzle: runs unless it is the identity
     bool tonemap = false, colorKey = false, invertY = false, reconstructZ = false;
     uint32_t colorKeyValue = 0;         // -c: 0x00RRGGBB
+    uint32_t rotateColor = 0;           // --rotate-color: TEX_ROTATE_COLOR, 0 = none
+    float paperWhiteNits = 200.f;       // --paper-white-nits
     std::vector<int> gpus;              // one worker (own Device, own host thread) per entry; input i goes to worker i mod n
     size_t overlap = 2;                 // workers per listed GPU: file k + 1 is read, decoded and uploaded while file k's kernels run
     std::string prefix, suffix, out;
@@ -146,6 +157,7 @@ int usage()
     std::fprintf(stderr, "usage: dxtexconv [-w W] [-h H] [-pow2] [-fl LEVEL] [-m N] [-f FORMAT] [-if FILTER] [-wrap] [-mirror] [-srgb|-srgbi|-srgbo]\n"
                          "                 [-pmalpha|-alpha] [-keepcoverage REF] [-at T] [-bc qxdu] [-x2bias] [-sepalpha] [-nmap <l|r|g|b|a>[m|u|v][i][o]] [-nmapamp W]\n"
                          "                 [-swizzle MASK] [-tonemap] [-c RRGGBB] [-inverty] [-reconstructz]\n"
+                         "                 [--rotate-color 709toHDR10|HDR10to709|709to2020|2020to709|P3D65toHDR10|P3D65to2020|709toP3D65|P3D65to709] [--paper-white-nits N]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N] -o <out.dds | dir> in.dds...\n");
     return 1;
@@ -227,6 +239,21 @@ bool Parse(int argc, char** argv, Options& o)
             unsigned int key = 0;
             if (missing || std::sscanf(v, "%x", &key) != 1) { std::fprintf(stderr, "Invalid value specified with -c (%s)\n", v); return false; }
             o.colorKey = true; o.colorKeyValue = key & 0xFFFFFFu;
+        }
+        else if (a == "-rotate-color")
+        {
+            // texconv.cpp:1545-1553 (LookupByName: either case); the short -rotatecolor is not accepted
+            const char* v = next();
+            if (missing) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return false; }
+            if (!lookup(kRotations, sizeof(kRotations) / sizeof(Name), v, o.rotateColor, false)) { std::fprintf(stderr, "Invalid value specified with -rotatecolor (%s)\n", v); return false; }
+        }
+        else if (a == "-paper-white-nits")
+        {
+            // texconv.cpp:1891-1903; the short -nits is not accepted
+            const char* v = next();
+            if (missing) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return false; }
+            if (std::sscanf(v, "%f", &o.paperWhiteNits) != 1) { std::fprintf(stderr, "Invalid value specified with -nits (%s)\n", v); return false; }
+            if (!(o.paperWhiteNits > 0.f && o.paperWhiteNits <= 10000.f)) { std::fprintf(stderr, "-nits (%s) parameter must be between 0 and 10000\n", v); return false; }
         }
         else if (a == "-tonemap") o.tonemap = true;
         else if (a == "-inverty" || a == "-invert-y") o.invertY = true;
@@ -423,6 +450,23 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     };
     auto simple = [](TEX_TRANSFORM_OP op, uint32_t key = 0) { TexTransform t; t.op = op; t.colorKey = key; return t; };
     if (!IsIdentitySwizzle(o.swizzle)) transform("swizzle", o.swizzle);
+
+    // --- colour rotation (texconv.cpp:2696-2964). HDR10to709 and P3D65to709 first convert to R16G16B16A16_FLOAT with the pipeline's flags
+    // and threshold (:2699-2733); `tformat` was fixed before (:2314), so without -f the convert step below returns to the input's format
+    if (o.rotateColor)
+    {
+        if (o.rotateColor == TEX_ROTATE_HDR10_TO_709 || o.rotateColor == TEX_ROTATE_P3D65_TO_709)
+        {
+            // (an input that already is R16G16B16A16_FLOAT fails here with E_INVALIDARG, as it does in texconv: Convert refuses the same format)
+            DeviceScratchImage t;
+            check("convert", Convert(dev, image, DXGI_FORMAT_R16G16B16A16_FLOAT, TEX_FILTER_FLAGS(filter | o.srgb | o.convert), o.alphaThreshold, t));
+            keep(t);
+        }
+        DeviceScratchImage r;
+        check("rotate color apply", RotateColor(dev, image, TEX_ROTATE_COLOR(o.rotateColor), o.paperWhiteNits, r));
+        keep(r);
+        haveOriginal = false;
+    }
     if (o.tonemap) transform("tonemap", simple(TEX_TRANSFORM_TONEMAP));
 
     // --- normal map (texconv.cpp:3047-3098), in place of the convert step; a compressed target gets texconv's intermediate format

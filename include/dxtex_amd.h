@@ -23,6 +23,8 @@
  *   TransformImage / EvaluateImage with        DirectXTexMisc.cpp:179-263      dxtex_transform_image
  *     texconv's swizzle, tone-map, colour-key,   texconv.cpp:2645-3301
  *     invert-Y and reconstruct-Z lambdas
+ *   TransformImage with texconv's colour       texconv.cpp:2696-2964           dxtex_rotate_color
+ *     rotation lambdas (HDR10, Rec.2020, P3)
  *   ComputeMSE_ with CMSE_FLAGS                DirectXTexMisc.cpp:27-176       dxtex_compute_mse_flags_device
  *   texdiag's Analyze / AnalyzeBC / Difference Texdiag/texdiag.cpp:698-1320    dxtex_analyze / dxtex_analyze_bc / dxtex_difference
  *   CopyRectangle                              DirectXTexMisc.cpp:275-381      dxtex_copy_rectangle / dxtex_copy_rectangles_device
@@ -264,6 +266,27 @@ typedef struct dxtex_transform
 dxtex_hresult dxtex_transform_image(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, const dxtex_transform* t);
 /* device pointers, `count` images of one format (a mip chain, an array, volume slices): asynchronous on the context's stream */
 dxtex_hresult dxtex_transform_images_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, const dxtex_transform* t);
+
+/* texconv's HDR colour rotation (Texconv/texconv.cpp:2696-2964): r, g and b move between the Rec.709, Rec.2020 and Display-P3 (D65)
+ * primaries, and into or out of HDR10 - Rec.2020 with the SMPTE ST.2084 curve, where paperWhiteNits is the level of linear 1.0.
+ * LoadScanline -> lambda -> StoreScanline (threshold 0); alpha keeps its bits; source and destination share format and size. The values
+ * are texconv's ROTATE_* (texconv.cpp:181-188). texconv converts to R16G16B16A16_FLOAT before HDR10_TO_709 and P3D65_TO_709; that is the
+ * caller's step here (dxtex_convert). powf is the correctly rounded one; a channel whose arithmetic gives a NaN is a NaN of any payload.
+ * HRESULTs: NOT_SUPPORTED for planar, palettised, compressed, typeless and unknown formats; E_INVALIDARG for a rotate outside 1..8, a
+ * paperWhiteNits outside (0, 10000] (a NaN included: texconv's rule for -nits), a width or height above UINT32_MAX and overlapping
+ * pixels; E_FAIL for a format or size mismatch between the images; E_POINTER for null pixels. */
+#define DXTEX_ROTATE_709_TO_HDR10     1u
+#define DXTEX_ROTATE_HDR10_TO_709     2u
+#define DXTEX_ROTATE_709_TO_2020      3u
+#define DXTEX_ROTATE_2020_TO_709      4u
+#define DXTEX_ROTATE_P3D65_TO_HDR10   5u
+#define DXTEX_ROTATE_P3D65_TO_2020    6u
+#define DXTEX_ROTATE_709_TO_P3D65     7u
+#define DXTEX_ROTATE_P3D65_TO_709     8u
+/* host pointers, one image, through the context's staging; returns when the destination has landed */
+dxtex_hresult dxtex_rotate_color(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t rotate, float paperWhiteNits);
+/* device pointers, `count` images of one format and any sizes (a mip chain, an array): asynchronous on the context's stream */
+dxtex_hresult dxtex_rotate_color_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t rotate, float paperWhiteNits);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
