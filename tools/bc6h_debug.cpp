@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE / DEVELOPMENT TOOL (not part of the product; built by oracle/Makefile into oracle/_ref/bc6h_core_check and
-// run by tests/test_bc7_core_cpu.py): runs the BC6H core of
+// run by tests/test_bc7_core_cpu.py and, in `file` mode, tests/test_bc6h_corpus_cpu.py): runs the BC6H core of
 // directxtex_amd/csrc/bc6h_core.h on the HOST, in the order the kernels of bc6h_encode.hip use it, next to the
 // reference's D3DX_BC6H::Encode compiled in place, and compares the emitted blocks.
 // Build + run:  tools/run_bc6h_debug.sh [ntiles] [seed]
@@ -105,6 +105,27 @@ static void print_bound_stats()
 }
 #endif
 
+#if defined(DXTEX_COUNT_EP16)
+// End states of the SF16 search of the 16-bit one-region mode (16:4): PerturbOne walks [0, 65536) whatever the signedness, so the search can end on
+// components above 32767, which the kernels' 16-bit task records cannot hold (bc6h_encode.hip: Ep16, ep16_mark). Classes: 0 = only A has such a
+// component, 1 = only B, 2 = both - taken BEFORE SwapIndices; then how many have A <= 32767 after the swap and how many of those pass EndPointsFit
+// (the kernels treat "A above 32767 before the swap" as never fitting: a tile counted in g_ep16Fit[0] or [2] is one where that would change bytes;
+// one in g_ep16Fit[1] is one where post's restored B decides). Every tile that fits is printed with its class.
+static unsigned long long g_ep16Searched, g_ep16[3], g_ep16AOk[3], g_ep16Fit[3], g_ep16FitWins;
+static int g_ep16Tile;
+static int ep16_class(const EndPts& e)
+{
+    const bool a = e.A[0] > 32767 || e.A[1] > 32767 || e.A[2] > 32767, b = e.B[0] > 32767 || e.B[1] > 32767 || e.B[2] > 32767;
+    return a ? (b ? 2 : 0) : (b ? 1 : -1);
+}
+static void print_ep16_stats(int tiles)
+{
+    printf("ep16: %d tiles, %llu searched in 16:4 | above 32767 before the swap: A only %llu, B only %llu, both %llu | A <= 32767 after the swap: %llu, %llu, %llu | "
+           "fit after the swap: %llu, %llu, %llu (%llu with a lower error than the unoptimised endpoints)\n", tiles, g_ep16Searched, g_ep16[0], g_ep16[1], g_ep16[2],
+           g_ep16AOk[0], g_ep16AOk[1], g_ep16AOk[2], g_ep16Fit[0], g_ep16Fit[1], g_ep16Fit[2], g_ep16FitWins);
+}
+#endif
+
 static uint32_t g_rng = 1;
 static uint32_t rnd() { g_rng = g_rng * 1664525u + 1013904223u; return g_rng >> 8; }
 static float frand() { return float(rnd() & 0xFFFF) / 65535.0f; }
@@ -147,6 +168,9 @@ static bool refine_host(const ModeRt& m, bool isSigned, uint32_t shape, const En
     const uint32_t m1 = m.regions2 ? kPart2Mask[shape] : 0u;
     const uint32_t masks[2] = { m.regions2 ? ((~m1) & 0xFFFFu) : 0xFFFFu, m1 };
     const uint32_t anchors[2] = { 0u, m.regions2 ? uint32_t(kAnchor2[shape]) : 0u };
+#if defined(DXTEX_COUNT_EP16)
+    int ep16Class = -1;
+#endif
     EndPts org[2], opt[2]; float orgErr[2] = { 0, 0 }, optErr[2] = { 0, 0 }; uint64_t orgIdx[2] = { 0, 0 }, optIdx[2] = { 0, 0 };
     Region6 rg[2], all; gather(ipx, 0xFFFF, all);
     for (int r = 0; r < nreg; ++r)
@@ -165,6 +189,9 @@ static bool refine_host(const ModeRt& m, bool isSigned, uint32_t shape, const En
     {
         const Region6& sr = (r == 0) ? all : rg[r];          // the reference's region-0 quirk
         if (g_noSearch) opt[r] = org[r]; else optimize_one6<N>(tex(sr), org[r], orgErr[r], m.prec, isSigned, opt[r]);
+#if defined(DXTEX_COUNT_EP16)
+        if (isSigned && m.prec == 16) { ++g_ep16Searched; ep16Class = ep16_class(opt[r]); }
+#endif
         optErr[r] = assign_indices6<N>(tex(rg[r]), rg[r].pos, opt[r], m.prec, isSigned, anchors[r], optIdx[r]);
     }
     float orgTot = 0.0f, optTot = 0.0f;
@@ -173,6 +200,18 @@ static bool refine_host(const ModeRt& m, bool isSigned, uint32_t shape, const En
     bool fitOpt = true; EndPts optT[2];
     for (int r = 0; r < nreg; ++r) { optT[r] = m.transformed ? transform_forward(opt[r], r, b0) : opt[r]; fitOpt = fitOpt && endpoints_fit(optT[r], r, m, isSigned); }
     const bool useOpt = fitOpt && optTot < orgTot;
+#if defined(DXTEX_COUNT_EP16)
+    if (ep16Class >= 0)
+    {
+        ++g_ep16[ep16Class];
+        if (opt[0].A[0] <= 32767 && opt[0].A[1] <= 32767 && opt[0].A[2] <= 32767) ++g_ep16AOk[ep16Class];
+        if (fitOpt)
+        {
+            ++g_ep16Fit[ep16Class]; g_ep16FitWins += useOpt;
+            printf("ep16 fit after swap: tile %d class %d useOpt %d\n", g_ep16Tile, ep16Class, int(useOpt));
+        }
+    }
+#endif
     const float err = useOpt ? optTot : orgTot;
     if (!(err < bestErr)) return true;
     bestErr = err;
@@ -387,9 +426,20 @@ int main(int argc, char** argv)
         if (argc > 4) g_onlyMode = atoi(argv[4]);
         if (argc > 5) g_noSearch = atoi(argv[5]) != 0;
         alignas(16) float px[64]; int t = 0;
-        while (fread(px, sizeof(px), 1, f) == 1) { uint64_t lo, hi; encode_host(px, sg, lo, hi); if (!getenv("DXTEX_BC6H_QUIET")) printf("%d %016llx %016llx\n", t, (unsigned long long)lo, (unsigned long long)hi); ++t; }
+        while (fread(px, sizeof(px), 1, f) == 1)
+        {
+#if defined(DXTEX_COUNT_EP16)
+            g_ep16Tile = t;
+#endif
+            uint64_t lo, hi; encode_host(px, sg, lo, hi);
+            if (!getenv("DXTEX_BC6H_QUIET")) printf("%d %016llx %016llx\n", t, (unsigned long long)lo, (unsigned long long)hi);
+            ++t;
+        }
 #if defined(DXTEX_COUNT_EVALS6)
         print_bound_stats();
+#endif
+#if defined(DXTEX_COUNT_EP16)
+        print_ep16_stats(t);
 #endif
         return 0;
     }
