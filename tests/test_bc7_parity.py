@@ -1,7 +1,12 @@
 """BC7: the HIP encoder reproduces the reference CPU search (D3DX_BC7::Encode, BC6HBC7.cpp:2783-2889)
 exactly, so the parity bar is byte equality per block; the north_star's one-sided MSE tolerance
 (MSE_gpu <= 1.02 * MSE_cpu + 1e-7) is asserted as well, measured by decoding both
-outputs with the reference decoder."""
+outputs with the reference decoder.
+
+What these images reach, read from the winning blocks of the reference encoder ("BC7 corpus", has the table): on the 64x64 seed 2
+images mode 3 wins with 32 of its 64 partitions, mode 1 with 56, mode 7 with 46; opaque mode 6 never wins; mode 5 wins with rotations 1 - 3 on
+zero to three blocks each. On the 48x32 seed 9 image with 3SUBSETS mode 0 wins with 7 of 16 partitions and mode 2 with 27 of 64. This file checks
+the drivers, flags, partial blocks, passes and knobs; the partitions, rotations and index selectors are covered by tests/test_bc7_corpus_gpu.py."""
 import numpy as np
 import pytest
 

@@ -317,8 +317,8 @@ int main(int argc, char** argv)
         uint64_t rlo, rhi; memcpy(&rlo, refBlk, 8); memcpy(&rhi, refBlk + 8, 8);
         if (rlo == best.lo && rhi == best.hi) continue;
         ++nbad;
-        if (nbad > 3) continue;
         int refMode = 0; while (refMode < 8 && !((refBlk[0] >> refMode) & 1)) ++refMode;
+        if (nbad > 3) { printf("tile %d MISMATCH: ref mode %d, ours mode %u (err %u)\n", t, refMode, best.ord / 128, best.err); continue; }      // every differing tile is named; the first three in detail
         printf("tile %d MISMATCH: ref mode %d, ours mode %u (err %u) spread %d opaque %d\n", t, refMode, best.ord / 128, best.err, spread, int(opaque));
 
         // stage-by-stage comparison against the reference's own member functions
