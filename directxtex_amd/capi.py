@@ -136,6 +136,10 @@ _SIGS = {
     "dxtex_transform_images_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, _P(Transform)]),
     "dxtex_rotate_color": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32, ctypes.c_float]),
     "dxtex_rotate_color_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float]),
+    "dxtex_rgbe_decode": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_float]),
+    "dxtex_rgbe_decode_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_float]),
+    "dxtex_rgbe_encode": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image)]),
+    "dxtex_rgbe_encode_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image)]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -719,6 +723,35 @@ class Context:
         n = len(srcs)
         a, b = (Image * max(n, 1))(*srcs), (Image * max(n, 1))(*dsts)
         self._check(self._lib.dxtex_rotate_color_device(self._h, a, b, n, rotate, paper_white_nits), "rotate_color_device")
+
+    # -- Radiance RGBE texels (the per-texel half of the .hdr codec) ---------------------------------------------------------------------
+    def rgbe_decode(self, rgbe_bytes, width, height, exposure=1.0, row_pitch=None):
+        """dxtex_rgbe_decode: rows of four-byte shared-exponent texels (host memory, row_pitch bytes apart, default width * 4) ->
+        R32G32B32A32_FLOAT with tight pitch, as a numpy uint8 buffer."""
+        rgbe_bytes = np.ascontiguousarray(rgbe_bytes)
+        src = _host_image(rgbe_bytes, width, height, F.DXGI_FORMAT_R8G8B8A8_UINT, row_pitch)
+        out = np.zeros(width * height * 16, np.uint8)
+        dst = Image(width, height, F.DXGI_FORMAT_R32G32B32A32_FLOAT, width * 16, width * height * 16, out.ctypes.data)
+        self._check(self._lib.dxtex_rgbe_decode(self._h, ctypes.byref(src), ctypes.byref(dst), exposure), "rgbe_decode")
+        return out
+
+    def rgbe_encode(self, pixels, width, height, fmt, row_pitch=None):
+        """dxtex_rgbe_encode: one R32G32B32A32_FLOAT, R32G32B32_FLOAT or R16G16B16A16_FLOAT image (host pixels) -> its RGBE texels, four
+        bytes each with tight pitch, as a numpy uint8 buffer."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        out = np.zeros(width * height * 4, np.uint8)
+        dst = Image(width, height, F.DXGI_FORMAT_R8G8B8A8_UINT, width * 4, width * height * 4, out.ctypes.data)
+        self._check(self._lib.dxtex_rgbe_encode(self._h, ctypes.byref(src), ctypes.byref(dst)), "rgbe_encode")
+        return out
+
+    def rgbe_decode_device(self, src, dst, exposure=1.0):
+        """dxtex_rgbe_decode_device on device Images (device_image): R8G8B8A8_UINT -> R32G32B32A32_FLOAT, asynchronous on the stream."""
+        self._check(self._lib.dxtex_rgbe_decode_device(self._h, ctypes.byref(src), ctypes.byref(dst), exposure), "rgbe_decode_device")
+
+    def rgbe_encode_device(self, src, dst):
+        """dxtex_rgbe_encode_device on device Images (device_image): a float format -> R8G8B8A8_UINT, asynchronous on the stream."""
+        self._check(self._lib.dxtex_rgbe_encode_device(self._h, ctypes.byref(src), ctypes.byref(dst)), "rgbe_encode_device")
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

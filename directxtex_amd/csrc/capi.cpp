@@ -1496,6 +1496,63 @@ dxtex_hresult dxtex_rotate_color(dxtex_ctx* ctx, const dxtex_image* src, const d
 
 namespace
 {
+// The checks of the RGBE pair, in the order include/dxtex_amd.h states. `rgbe` is the R8G8B8A8_UINT side, `flt` the float side.
+dxtex_hresult check_rgbe(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, bool decode, float exposure)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src || !dst) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!src->pixels || !dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    const dxtex_image& rgbe = decode ? *src : *dst;
+    const dxtex_image& flt = decode ? *dst : *src;
+    const bool floatOk = flt.format == FMT_R32G32B32A32_FLOAT || (!decode && (flt.format == FMT_R32G32B32_FLOAT || flt.format == FMT_R16G16B16A16_FLOAT));
+    if (rgbe.format != FMT_R8G8B8A8_UINT || !floatOk)
+        return fail(ctx, DXTEX_E_NOT_SUPPORTED, decode ? "RGBE decode is R8G8B8A8_UINT to R32G32B32A32_FLOAT" : "RGBE encode is R32G32B32A32_FLOAT, R32G32B32_FLOAT or R16G16B16A16_FLOAT to R8G8B8A8_UINT");
+    if (src->width != dst->width || src->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
+    if (src->width > 0xFFFFFFFFull || src->height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    const size_t floatBytes = flt.format == FMT_R32G32B32A32_FLOAT ? 16u : flt.format == FMT_R32G32B32_FLOAT ? 12u : 8u;
+    if (rgbe.rowPitch < rgbe.width * 4u || flt.rowPitch < flt.width * floatBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
+    if (src->width && src->height) { const dxtex_hresult hr = check_no_overlap(ctx, *src, *dst); if (hr != DXTEX_S_OK) return hr; }
+    if (decode && !(exposure > 0.0f && exposure <= 3.402823466e+38f)) return fail(ctx, DXTEX_E_INVALIDARG, "the exposure must be a finite positive number");
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult submit_rgbe(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, bool decode, float exposure)
+{
+    if (decode) return launched(ctx, launch_rgbe_decode(view_of(src), view_of(dst), 1.0f / exposure, ctx->stream, marks_of(ctx)));
+    return launched(ctx, launch_rgbe_encode(view_of(src), view_of(dst), ctx->stream, marks_of(ctx)));
+}
+} // namespace
+
+dxtex_hresult dxtex_rgbe_decode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure)
+{
+    const dxtex_hresult hr = check_rgbe(ctx, src, dst, true, exposure);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_rgbe(ctx, *src, *dst, true, exposure); });
+}
+
+dxtex_hresult dxtex_rgbe_decode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure)
+{
+    const dxtex_hresult hr = check_rgbe(ctx, src, dst, true, exposure);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rgbe(ctx, s, d, true, exposure); });
+}
+
+dxtex_hresult dxtex_rgbe_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
+{
+    const dxtex_hresult hr = check_rgbe(ctx, src, dst, false, 1.0f);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_rgbe(ctx, *src, *dst, false, 1.0f); });
+}
+
+dxtex_hresult dxtex_rgbe_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
+{
+    const dxtex_hresult hr = check_rgbe(ctx, src, dst, false, 1.0f);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rgbe(ctx, s, d, false, 1.0f); });
+}
+
+namespace
+{
 // PremultiplyAlpha's checks (DirectXTexPMAlpha.cpp:214-231)
 dxtex_hresult check_pmalpha(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
 {

@@ -91,6 +91,13 @@ hipError_t launch_tonemap_max(const ImgView& src, uint32_t* maxBits, hipStream_t
 struct RotateArgs;
 hipError_t launch_rotate_color(const ImgView& src, const ImgView& dst, int curve, const RotateArgs& args, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// Radiance RGBE texels (rgbe.hip; the arithmetic is in dxtex_rgbe.h), one image, the size is src's and dst matches it. Decode: R8G8B8A8_UINT
+// rows of shared-exponent texels -> R32G32B32A32_FLOAT rows, scale = 1 / exposure. Encode: R32G32B32A32_FLOAT, R32G32B32_FLOAT or
+// R16G16B16A16_FLOAT rows -> RGBE rows. A float side whose base and pitch are multiples of its texel (16 bytes; 8 for halves) takes one
+// access per texel (<wide>), every other one an access per channel (<narrow>). Source and destination must not overlap.
+hipError_t launch_rgbe_decode(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream, KernelMarks* marks = nullptr);
+hipError_t launch_rgbe_encode(const ImgView& src, const ImgView& dst, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

@@ -565,6 +565,19 @@ HRESULT LoadFromHDRMemory(const void* pSource, size_t size, TexMetadata* metadat
 HRESULT LoadFromHDRFile(const char* szFile, TexMetadata* metadata, ScratchImage& image) noexcept;
 HRESULT SaveToHDRMemory(const Image& image, Blob& blob) noexcept;
 HRESULT SaveToHDRFile(const Image& image, const char* szFile) noexcept;
+// The header and the run-length expansion only: tight width * 4-byte rows of shared-exponent texels, and the file's exposure. Needs no device.
+HRESULT LoadFromHDRMemoryRGBE(const void* pSource, size_t size, TexMetadata* metadata, float& exposure, Blob& rgbe) noexcept;
+HRESULT LoadFromHDRFileRGBE(const char* szFile, TexMetadata* metadata, float& exposure, Blob& rgbe) noexcept;
+// Resident forms: the texels cross PCIe as RGBE, 4 bytes each, and the float pass runs on the device (dxtex_rgbe_decode_device /
+// dxtex_rgbe_encode_device). HRESULTs, metadata, pixels and files are those of the host forms above. Load: one upload of width * height * 4
+// bytes, the result is released on failure. Save: deviceImage's pixels are a device pointer, as DeviceScratchImage::GetImage gives; one
+// download of width * height * 4 bytes. A channel of +Inf is saved as a zero texel (include/dxtex_amd.h, dxtex_rgbe_encode).
+HRESULT LoadFromHDRMemory(Device& device, const void* pSource, size_t size, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device (LoadFrom...RGBE gave all three arguments)
+HRESULT UploadHDRRows(Device& device, const TexMetadata& metadata, float exposure, const Blob& rgbe, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromHDRFile(Device& device, const char* szFile, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT SaveToHDRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept;
+HRESULT SaveToHDRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
 
 // ---- Truevision TGA, DirectXTexTGA.cpp: 8-bit grey -> R8, 16-bit -> B5G5R5A1, 24-bit -> RGBA8 (opaque), 32-bit -> RGBA8, colour-mapped
 // (24-bit palette) -> RGBA8; raw or run-length encoded; TGA 2.0 extension area for alpha mode and gamma ------------------------------

@@ -309,7 +309,8 @@ int Fail(const char* what, HRESULT hr)
     return 1;
 }
 
-struct Input { TexMetadata info; ScratchImage image; };
+// an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
+struct Input { TexMetadata info; ScratchImage image; bool hdr = false; float exposure = 1.f; Blob rgbe; };
 
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
 int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
@@ -348,7 +349,7 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
             }
         }
         else if (hasExt(file, ".tga")) { hr = LoadFromTGAFile(file.c_str(), TGA_FLAGS_NONE, &in->info, in->image); if (FAILED(hr)) return Fail(" FAILED", hr); }
-        else if (hasExt(file, ".hdr")) { hr = LoadFromHDRFile(file.c_str(), &in->info, in->image); if (FAILED(hr)) return Fail(" FAILED", hr); }
+        else if (hasExt(file, ".hdr")) { in->hdr = true; hr = LoadFromHDRFileRGBE(file.c_str(), &in->info, in->exposure, in->rgbe); if (FAILED(hr)) return Fail(" FAILED", hr); }
         else { std::printf(" FAILED: only .dds, .tga and .hdr can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
         std::fflush(stdout);
@@ -386,9 +387,10 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     for (size_t index = 0; index < inputs.size(); ++index)
     {
         DeviceScratchImage cur, next;
-        HRESULT hr = cur.Upload(dev, inputs[index]->image);
+        Input& in = *inputs[index];
+        HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : cur.Upload(dev, in.image);
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        inputs[index]->image.Release();
+        in.image.Release(); in.rgbe.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
@@ -506,16 +508,21 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     }
     if (FAILED(hr)) return Fail("FAILED building result image", hr);
 
+    // an .hdr output comes back as the RGBE rows the resident saver makes on the device; everything else as it is
+    const bool hdrOut = hasExt(o.output, ".hdr");
     ScratchImage out;
-    hr = result.Download(out);
-    if (FAILED(hr)) return Fail("FAILED building result image", hr);
+    if (!hdrOut)
+    {
+        hr = result.Download(out);
+        if (FAILED(hr)) return Fail("FAILED building result image", hr);
+    }
     std::printf("\nWriting %s ", o.output.c_str());
-    PrintInfo(out.GetMetadata());
+    PrintInfo(result.GetMetadata());
     std::printf("\n");
     std::fflush(stdout);
     struct stat st;
     if (!o.overwrite && stat(o.output.c_str(), &st) == 0) { std::printf("\nERROR: Output file already exists, use -y to overwrite\n"); return 1; }
-    if (hasExt(o.output, ".hdr")) hr = SaveToHDRFile(*out.GetImage(0, 0, 0), o.output.c_str());
+    if (hdrOut) hr = SaveToHDRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());
     else if (hasExt(o.output, ".tga")) hr = SaveToTGAFile(*out.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
     else hr = SaveToDDSFile(out.GetImages(), out.GetImageCount(), out.GetMetadata(),
                             o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());

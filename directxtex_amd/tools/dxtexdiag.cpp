@@ -227,14 +227,16 @@ int RunAnalyze(Device& dev, const Options& o)
     {
         TexMetadata info;
         ScratchImage image;
-        HRESULT hr = Load(dev, o, file, info, image);
+        // the whole file goes up once - an .hdr file as its RGBE rows, which the resident loader turns into floats on the device; every image
+        // is analysed there, the figures come back in one copy
+        DeviceScratchImage resident;
+        const bool hdr = hasExt(file, ".hdr");
+        HRESULT hr = hdr ? LoadFromHDRFile(dev, file.c_str(), &info, resident) : Load(dev, o, file, info, image);
         if (FAILED(hr)) return Fail((" FAILED loading " + file).c_str(), hr);
         std::printf("%s\n", file.c_str());
-        // the whole file goes up once; every image is analysed on the device, the figures come back in one copy
-        DeviceScratchImage resident;
-        hr = resident.Upload(dev, image);
+        if (!hdr) hr = resident.Upload(dev, image);
         if (FAILED(hr)) return Fail("ERROR: Failed uploading the images", hr);
-        const size_t n = image.GetImageCount();
+        const size_t n = resident.GetImageCount();
         std::vector<AnalyzeData> data(n);
         std::vector<AnalyzeBCData> bc(IsCompressed(info.format) ? n : 0);
         hr = Analyze(dev, resident, data.data());

@@ -30,6 +30,8 @@
  *   CopyRectangle                              DirectXTexMisc.cpp:275-381      dxtex_copy_rectangle / dxtex_copy_rectangles_device
  *   texassemble's merge lambda                 Texassemble/texassemble.cpp:2236-2268  dxtex_merge_image
  *   ConvertToSinglePlane                       DirectXTexConvert.cpp:4912-5077, :5411-5523  dxtex_convert_to_single_plane[_device]
+ *   LoadFromHDRMemory's float pass,            DirectXTexHDR.cpp:887-901, :328-407  dxtex_rgbe_decode / dxtex_rgbe_encode
+ *     FloatToRGBE / HalfToRGBE
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -287,6 +289,23 @@ dxtex_hresult dxtex_transform_images_device(dxtex_ctx* ctx, const dxtex_image* s
 dxtex_hresult dxtex_rotate_color(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t rotate, float paperWhiteNits);
 /* device pointers, `count` images of one format and any sizes (a mip chain, an array): asynchronous on the context's stream */
 dxtex_hresult dxtex_rotate_color_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t rotate, float paperWhiteNits);
+
+/* Radiance RGBE (.hdr) texels, the per-texel half of the codec (the run-length coder is byte-serial and stays with the caller). One image
+ * per call. The RGBE side is a dxtex_image of DXGI_FORMAT_R8G8B8A8_UINT: the four raw bytes of each shared-exponent texel.
+ *   decode   RGBE -> R32G32B32A32_FLOAT: channel = (1 / exposure) * ldexpf(byte + 0.5f, exponent byte - 136), alpha 1
+ *            (DirectXTexHDR.cpp:887-901). As there, a zero exponent byte is no special case: (0, 0, 0, 0) decodes to 2^-137, a denormal.
+ *   encode   R32G32B32A32_FLOAT, R32G32B32_FLOAT or R16G16B16A16_FLOAT -> RGBE: FloatToRGBE / HalfToRGBE (:328-407). A negative or NaN
+ *            channel counts as 0. The reference converts a NaN to a byte where a channel is +Inf, which is undefined; here a texel whose
+ *            largest channel is not finite becomes four zero bytes.
+ * HRESULTs, in this order: E_POINTER for a null image or null pixels; NOT_SUPPORTED for any other format on either side (SaveToHDRMemory's
+ * answer); E_FAIL for a size mismatch; E_INVALIDARG for a row pitch smaller than the row, a width or height above UINT32_MAX, overlapping
+ * pixels, or an exposure that is not a finite positive number. Pixels and pitches are aligned to the side's channel (1, 2 or 4 bytes). */
+/* host pointers, through the context's staging; returns when the destination has landed */
+dxtex_hresult dxtex_rgbe_decode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure);
+dxtex_hresult dxtex_rgbe_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst);
+/* device pointers: asynchronous on the context's stream */
+dxtex_hresult dxtex_rgbe_decode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure);
+dxtex_hresult dxtex_rgbe_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);

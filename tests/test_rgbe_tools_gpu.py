@@ -1,0 +1,105 @@
+"""The tools on .hdr files, end to end against the reference's reader, writer and Convert (oracle): dxtexconv sends an .hdr input up as its
+RGBE texels and brings an -ft hdr output down as RGBE texels (the -timing line counts the bytes), dxtexassemble builds a cube from .hdr faces."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import rgbe_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+LIB = os.path.join(ROOT, "directxtex_amd", "lib")
+W, H = 48, 20
+CUBE = 0x4          # TEX_MISC_TEXTURECUBE
+
+
+def _tool(name, args):
+    r = subprocess.run([os.path.join(LIB, name)] + [str(a) for a in args], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout + r.stderr
+
+
+def _image(seed, w=W, h=H):
+    """seeded noise over smooth ramps, with a flat band: runs and literals for the row coder"""
+    rng = np.random.default_rng(seed)
+    ramp = (np.arange(w, dtype=np.float32)[None, :, None] // 4 * np.float32(0.25) + np.arange(h, dtype=np.float32)[:, None, None] * np.float32(0.5))
+    img = np.broadcast_to(ramp, (h, w, 4)).copy()
+    img[:, w // 2:] *= rng.random((h, w - w // 2, 4), dtype=np.float32) * np.float32(2)
+    img[h // 2] = np.float32(0.75)
+    return img.astype(np.float32)
+
+
+def _moved(txt):
+    m = re.search(r"host -> device (\d+) bytes, device -> host (\d+) bytes", txt)
+    assert m, txt
+    return int(m.group(1)), int(m.group(2))
+
+
+def test_dxtexconv_uploads_an_hdr_file_as_rgbe(tmp_path, oracle):
+    src, out = tmp_path / "sky.hdr", tmp_path / "sky.dds"
+    data = oracle.ref_save_hdr(_image(1), W, H, R.RGBA32F, W * 16)[1]
+    data.tofile(src)
+    txt = _tool("dxtexconv", ["-timing", "-overlap", "1", "-m", "1", "-f", "R16G16B16A16_FLOAT", "-o", out, src])
+    hr, meta, floats = oracle.ref_load_hdr(data)
+    assert hr == 0
+    want = oracle.ref_convert(floats, W, H, R.RGBA32F, R.RGBA16F, 0, 0.5)
+    dmeta, px = oracle.ref_load_dds(np.fromfile(out, np.uint8))
+    assert (dmeta["width"], dmeta["height"], dmeta["format"], dmeta["mipLevels"]) == (W, H, R.RGBA16F, 1)
+    assert np.array_equal(np.asarray(px, np.uint8)[:want.size], np.asarray(want, np.uint8).reshape(-1)) and px.size == want.size
+    up, down = _moved(txt)
+    assert up == W * H * 4, txt
+    assert W * H * 8 <= down <= W * H * 8 + 8, txt            # the result, and the alpha scan's count
+
+
+@pytest.mark.parametrize("fmt", [R.RGBA32F, R.RGBA16F])
+def test_dxtexconv_downloads_an_hdr_output_as_rgbe(tmp_path, oracle, fmt):
+    src, out = tmp_path / "in.dds", tmp_path / "out.hdr"
+    px = R.as_format(_image(2), fmt)
+    oracle.ref_save_dds(px, W, H, fmt).tofile(src)
+    txt = _tool("dxtexconv", ["-timing", "-overlap", "1", "-m", "1", "-ft", "hdr", "-o", out, src])
+    rhr, ref = oracle.ref_save_hdr(px, W, H, fmt, W * R.BPT[fmt])
+    assert rhr == 0 and np.array_equal(np.fromfile(out, np.uint8), ref)
+    up, down = _moved(txt)
+    assert up == px.nbytes, txt
+    assert W * H * 4 <= down <= W * H * 4 + 8, txt            # the RGBE rows, and the alpha scan's count
+
+
+def test_dxtexassemble_cube_from_hdr_faces(tmp_path, oracle):
+    n = 24
+    paths, floats = [], []
+    for k in range(6):
+        data = oracle.ref_save_hdr(_image(10 + k, n, n), n, n, R.RGBA32F, n * 16)[1]
+        hr, meta, px = oracle.ref_load_hdr(data)
+        assert hr == 0
+        floats.append(px)
+        paths.append(tmp_path / f"face{k}.hdr")
+        data.tofile(paths[-1])
+    out = tmp_path / "cube.dds"
+    _tool("dxtexassemble", ["cube", "-nologo", "-y", "-o", out, *paths])
+    blob = np.concatenate(floats)
+    got = np.fromfile(out, np.uint8)
+    meta, px = oracle.ref_load_dds(got)
+    assert (meta["width"], meta["height"], meta["format"], meta["arraySize"], meta["mipLevels"], meta["miscFlags"] & CUBE) == (n, n, R.RGBA32F, 6, 1, CUBE)
+    assert np.array_equal(np.asarray(px, np.uint8)[:blob.size], blob) and px.size == blob.size
+    # the whole file: the reference's writer on the expected texture, with the alpha mode the file states
+    hr, want = oracle.ref_save_dds_ex(blob, n, n, 1, R.RGBA32F, 6, 1, meta["miscFlags"], meta["miscFlags2"], meta["dimension"], 0)
+    assert hr == 0 and np.array_equal(got, want)
+
+
+def test_dxtexdiag_analyze_of_an_hdr_file(tmp_path, oracle):
+    """analyze loads an .hdr file with the resident loader: its report is that of a float DDS holding the reference reader's floats."""
+    src, dds = tmp_path / "sky.hdr", tmp_path / "sky.dds"
+    data = oracle.ref_save_hdr(_image(3), W, H, R.RGBA32F, W * 16)[1]
+    data.tofile(src)
+    hr, meta, floats = oracle.ref_load_hdr(data)
+    assert hr == 0
+    oracle.ref_save_dds(floats, W, H, R.RGBA32F).tofile(dds)
+    a = _tool("dxtexdiag", ["analyze", "-nologo", src]).replace(str(src), "FILE")
+    b = _tool("dxtexdiag", ["analyze", "-nologo", dds]).replace(str(dds), "FILE")
+    assert "Minimum" in a or "min" in a.lower(), a
+    assert a == b
