@@ -140,6 +140,10 @@ _SIGS = {
     "dxtex_rgbe_decode_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_float]),
     "dxtex_rgbe_encode": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image)]),
     "dxtex_rgbe_encode_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image)]),
+    "dxtex_tga_unpack": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, _P(Image), _P(ctypes.c_uint32)]),
+    "dxtex_tga_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, _P(Image), ctypes.c_void_p]),
+    "dxtex_tga_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_tga_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -752,6 +756,48 @@ class Context:
     def rgbe_encode_device(self, src, dst):
         """dxtex_rgbe_encode_device on device Images (device_image): a float format -> R8G8B8A8_UINT, asynchronous on the stream."""
         self._check(self._lib.dxtex_rgbe_encode_device(self._h, ctypes.byref(src), ctypes.byref(dst)), "rgbe_encode_device")
+
+    # -- Truevision TGA texels (the per-texel half of the .tga codec) --------------------------------------------------------------------
+    @staticmethod
+    def _tga_palette(palette):
+        """256 host words for the palette argument, or None"""
+        if palette is None:
+            return None
+        palette = np.ascontiguousarray(palette, np.uint32)
+        assert palette.size == 256
+        return palette
+
+    def tga_unpack(self, texels, width, height, bytes_per_texel, fmt, flags=0, palette=None, row_pitch=None):
+        """dxtex_tga_unpack: the file-order texel stream (host bytes) -> (pixels of `fmt` as a numpy uint8 buffer with `row_pitch` bytes a
+        row, default tight; the alpha answer: 1 = opaque). flags = TGA_RIGHT_TO_LEFT | TGA_TOP_DOWN | TGA_ALLOW_ALL_ZERO_ALPHA."""
+        texels = np.ascontiguousarray(texels, np.uint8)
+        pal = self._tga_palette(palette)
+        pitch = compute_pitch(fmt, width, height)[0] if row_pitch is None else row_pitch
+        out = np.zeros(pitch * height, np.uint8)
+        dst = Image(width, height, fmt, pitch, pitch * height, out.ctypes.data)
+        opaque = ctypes.c_uint32(0xFFFFFFFF)
+        self._check(self._lib.dxtex_tga_unpack(self._h, texels.ctypes.data, texels.nbytes, bytes_per_texel, flags, None if pal is None else pal.ctypes.data,
+                                               ctypes.byref(dst), ctypes.byref(opaque)), "tga_unpack")
+        return out, int(opaque.value)
+
+    def tga_pack(self, pixels, width, height, fmt, bytes_per_texel, row_pitch=None):
+        """dxtex_tga_pack: one image (host pixels) -> the width * height * bytes_per_texel bytes of the file's rows, as a numpy uint8 buffer."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        out = np.zeros(width * height * bytes_per_texel, np.uint8)
+        self._check(self._lib.dxtex_tga_pack(self._h, ctypes.byref(src), bytes_per_texel, out.ctypes.data, out.nbytes), "tga_pack")
+        return out
+
+    def tga_unpack_device(self, texels_ptr, texel_bytes, bytes_per_texel, dst, flags=0, palette=None, opaque_ptr=None):
+        """dxtex_tga_unpack_device: the stream at a device pointer -> the device Image `dst` (device_image), asynchronous on the stream; the
+        answer goes to the device dword opaque_ptr if given. palette = 256 host words."""
+        pal = self._tga_palette(palette)
+        self._check(self._lib.dxtex_tga_unpack_device(self._h, texels_ptr, texel_bytes, bytes_per_texel, flags, None if pal is None else pal.ctypes.data,
+                                                      ctypes.byref(dst), opaque_ptr), "tga_unpack_device")
+
+    def tga_pack_device(self, src, bytes_per_texel, texels_ptr, texel_bytes):
+        """dxtex_tga_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
+        self._check(self._lib.dxtex_tga_pack_device(self._h, ctypes.byref(src), bytes_per_texel, texels_ptr, texel_bytes), "tga_pack_device")
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

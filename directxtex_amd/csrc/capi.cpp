@@ -4,6 +4,7 @@
 #include "../../include/dxtex_amd.h"
 #include "dxtex_formats.h"
 #include "dxtex_kernels.h"
+#include "dxtex_tga.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -332,9 +333,11 @@ dxtex_hresult run_timed(dxtex_ctx* ctx, Submit&& submit)
 
 // The staging of every single-image host-pointer entry point: inBytes from hostIn go up into ctx->stageIn, submit(stageIn, stageOut)
 // queues the kernels between the timing events (so dxtex_ctx_last_kernel_ms covers kernels only), outBytes of ctx->stageOut come back
-// to hostOut, and the call returns once they have landed. A failed submit returns at once: no download, no synchronisation.
+// to hostOut, and the call returns once they have landed. A failed submit returns at once: no download, no synchronisation. A call whose
+// kernels leave a second, small result in device memory of the context (devOut2, out2Bytes) gets it to hostOut2 in the same download.
 template<class Submit>
-dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, void* hostOut, size_t outBytes, Submit&& submit)
+dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, void* hostOut, size_t outBytes, Submit&& submit,
+                         void* hostOut2 = nullptr, const void* devOut2 = nullptr, size_t out2Bytes = 0)
 {
     ScopedDevice sd(ctx->device);
     dxtex_hresult hr = ctx->stageIn.grow(ctx, inBytes); if (hr != DXTEX_S_OK) return hr;
@@ -343,6 +346,7 @@ dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, voi
     hr = run_timed(ctx, [&] { return submit(ctx->stageIn.u8(), ctx->stageOut.u8()); });
     if (hr != DXTEX_S_OK) return hr;
     HIP_TRY(ctx, counted_copy(ctx, hostOut, ctx->stageOut.p, outBytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (out2Bytes) HIP_TRY(ctx, counted_copy(ctx, hostOut2, devOut2, out2Bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
@@ -1549,6 +1553,115 @@ dxtex_hresult dxtex_rgbe_encode(dxtex_ctx* ctx, const dxtex_image* src, const dx
     const dxtex_hresult hr = check_rgbe(ctx, src, dst, false, 1.0f);
     if (hr != DXTEX_S_OK) return hr;
     return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rgbe(ctx, s, d, false, 1.0f); });
+}
+
+namespace
+{
+static_assert(DXTEX_TGA_RIGHT_TO_LEFT == TGA_RIGHT_TO_LEFT && DXTEX_TGA_TOP_DOWN == TGA_TOP_DOWN && DXTEX_TGA_ALLOW_ALL_ZERO_ALPHA == TGA_ALLOW_ALL_ZERO_ALPHA,
+              "dxtex_tga.h's flags are the public ones");
+
+// the reader's table (include/dxtex_amd.h): which kind a (bytes per texel, destination format, palette or not) is; -1 for a pair outside it
+int tga_unpack_kind(int format, uint32_t bytesPerTexel, bool paletted)
+{
+    if (paletted) return (bytesPerTexel == 1 && (format == FMT_R8G8B8A8_UNORM || format == FMT_B8G8R8X8_UNORM)) ? TGA_PALETTE : -1;
+    switch (format)
+    {
+    case FMT_R8_UNORM: return bytesPerTexel == 1 ? TGA_GREY : -1;
+    case FMT_B5G5R5A1_UNORM: return bytesPerTexel == 2 ? TGA_5551 : -1;
+    case FMT_R8G8B8A8_UNORM: return bytesPerTexel == 3 ? TGA_RGB_RGBA : bytesPerTexel == 4 ? TGA_BGRA_RGBA : -1;
+    case FMT_B8G8R8X8_UNORM: return bytesPerTexel == 3 ? TGA_RGB_BGRX : -1;
+    case FMT_B8G8R8A8_UNORM: return bytesPerTexel == 4 ? TGA_BGRA_BGRA : -1;
+    default: return -1;
+    }
+}
+
+// the writer's table (SaveToTGAMemory): the row kind of a (format, bytes per texel); -1 for a pair outside it
+int tga_pack_row(int format, uint32_t bytesPerTexel)
+{
+    switch (format)
+    {
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return bytesPerTexel == 4 ? TGA_ROW_SWAP_RB : -1;
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: return bytesPerTexel == 4 ? TGA_ROW_COPY : -1;
+    case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return bytesPerTexel == 3 ? TGA_ROW_DROP_X : -1;
+    case FMT_R8_UNORM: case FMT_A8_UNORM: return bytesPerTexel == 1 ? TGA_ROW_COPY : -1;
+    case FMT_B5G5R5A1_UNORM: return bytesPerTexel == 2 ? TGA_ROW_COPY : -1;
+    default: return -1;
+    }
+}
+
+// The checks of the TGA four, in the order include/dxtex_amd.h states. `image` is the dxtex_image side, imageBytes a texel of it;
+// *kind = the reader's kind or the writer's row.
+dxtex_hresult check_tga(dxtex_ctx* ctx, const void* stream, size_t streamBytes, uint32_t bytesPerTexel, bool paletted, const dxtex_image* image, bool unpack, int* kind)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!stream) return fail(ctx, DXTEX_E_POINTER, "null texel stream");
+    if (!image) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!image->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    *kind = unpack ? tga_unpack_kind(image->format, bytesPerTexel, paletted) : tga_pack_row(image->format, bytesPerTexel);
+    if (*kind < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, unpack ? "no TGA reader case for this bytes per texel, format and palette" : "no TGA writer case for this format and bytes per texel");
+    if (!image->width || !image->height || image->width > 65535 || image->height > 65535) return fail(ctx, DXTEX_E_INVALIDARG, "a TGA image is 1 to 65535 texels wide and high");
+    const size_t imageBytes = unpack ? tga_image_bytes(*kind) : (*kind == TGA_ROW_DROP_X ? 4u : bytesPerTexel);
+    if (image->rowPitch < image->width * imageBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
+    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    const size_t need = image->width * image->height * bytesPerTexel;
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(stream), s1 = s0 + need;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + image->width * imageBytes;
+    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "texel stream and image pixels overlap");
+    if (streamBytes != need) return fail(ctx, DXTEX_E_FAIL, "the texel stream is not width * height * bytes per texel long");
+    return DXTEX_S_OK;
+}
+
+// The reader's kernels on device pointers. The two alpha ORs live in the context's result cell, the answer goes to `answer` (device memory;
+// null: behind the ORs). A kind without an alpha rule runs no alpha kernel: its answer is known (1 for 24 bits into R8G8B8A8, else 0).
+dxtex_hresult submit_tga_unpack(dxtex_ctx* ctx, const uint8_t* stream, int kind, uint32_t flags, const uint32_t* palette, const dxtex_image& dst, uint32_t* answer)
+{
+    const dxtex_hresult hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr;
+    uint32_t* cell = static_cast<uint32_t*>(ctx->resultCell.p);
+    if (!tga_has_alpha_rule(kind) && answer) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(answer), kind == TGA_RGB_RGBA ? 1 : 0, 1, ctx->stream));
+    return launched(ctx, launch_tga_unpack(stream, kind, flags, palette, view_of(dst), cell, answer ? answer : cell + 2, ctx->stream, marks_of(ctx)));
+}
+} // namespace
+
+dxtex_hresult dxtex_tga_unpack_device(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
+                                      const dxtex_image* dst, uint32_t* opaqueDevice)
+{
+    int kind;
+    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, palette != nullptr, dst, true, &kind);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_tga_unpack(ctx, static_cast<const uint8_t*>(texels), kind, flags, palette, *dst, opaqueDevice); });
+}
+
+dxtex_hresult dxtex_tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
+                               const dxtex_image* dst, uint32_t* opaque)
+{
+    if (ctx && !opaque) return fail(ctx, DXTEX_E_POINTER, "null alpha answer");
+    int kind;
+    dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, palette != nullptr, dst, true, &kind);
+    if (hr != DXTEX_S_OK) return hr;
+    *opaque = kind == TGA_RGB_RGBA ? 1u : 0u;
+    const bool rule = tga_has_alpha_rule(kind);
+    if (rule) { ScopedDevice sd(ctx->device); hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr; }
+    const uint32_t* answer = rule ? static_cast<const uint32_t*>(ctx->resultCell.p) + 2 : nullptr;
+    return run_staged(ctx, texels, texelBytes, dst->pixels, dst->rowPitch * dst->height,
+                      [&](uint8_t* in, uint8_t* out) { return submit_tga_unpack(ctx, in, kind, flags, palette, with_pixels(*dst, out), nullptr); },
+                      opaque, answer, rule ? sizeof(uint32_t) : 0);
+}
+
+dxtex_hresult dxtex_tga_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes)
+{
+    int row;
+    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, false, src, false, &row);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_tga_pack(view_of(*src), row, bytesPerTexel, static_cast<uint8_t*>(texels), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_tga_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes)
+{
+    int row;
+    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, false, src, false, &row);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + src->width * (row == TGA_ROW_DROP_X ? 4u : bytesPerTexel), texels, texelBytes,
+                      [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_tga_pack(view_of(with_pixels(*src, in)), row, bytesPerTexel, out, ctx->stream, marks_of(ctx))); });
 }
 
 namespace

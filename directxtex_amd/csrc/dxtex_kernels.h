@@ -98,6 +98,14 @@ hipError_t launch_rotate_color(const ImgView& src, const ImgView& dst, int curve
 hipError_t launch_rgbe_decode(const ImgView& src, const ImgView& dst, float scale, hipStream_t stream, KernelMarks* marks = nullptr);
 hipError_t launch_rgbe_encode(const ImgView& src, const ImgView& dst, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// Truevision TGA texels (tga.hip; the rules are in dxtex_tga.h). Unpack: `stream` = dst.width * dst.height texels in file order, kind = a
+// TgaKind that matches dst.format, flags = TgaFlags, palette = 256 host words for TGA_PALETTE (passed by value: free to go on return).
+// For a kind with an alpha rule alphaWord[0..1] (device) are cleared and receive the two ORs, and the opaque pass behind the unpack leaves
+// the answer in *answer (device); the other kinds touch neither. Pack: src's rows -> stream, row = a TgaRow. Wide / narrow: see tga.hip.
+hipError_t launch_tga_unpack(const uint8_t* stream, int kind, uint32_t flags, const uint32_t* palette, const ImgView& dst, uint32_t* alphaWord, uint32_t* answer,
+                             hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_tga_pack(const ImgView& src, int row, uint32_t bytesPerTexel, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

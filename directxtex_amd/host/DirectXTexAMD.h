@@ -536,6 +536,7 @@ public:
     HRESULT Initialize(size_t size) noexcept;
     HRESULT Trim(size_t size) noexcept;              // shortens the logical size, keeps the allocation
     void Release() noexcept;
+    void Swap(Blob& o) noexcept { uint8_t* b = m_buffer; m_buffer = o.m_buffer; o.m_buffer = b; const size_t n = m_size; m_size = o.m_size; o.m_size = n; }
     uint8_t* GetBufferPointer() const noexcept { return m_buffer; }
     size_t GetBufferSize() const noexcept { return m_size; }
 private:
@@ -595,4 +596,34 @@ HRESULT LoadFromTGAFile(const char* szFile, TGA_FLAGS flags, TexMetadata* metada
 // saves RGBA8 / BGRA8 (32-bit), BGRX8 (24-bit), R8 / A8 (grey), B5G5R5A1 (16-bit); metadata adds the TGA 2.0 extension area
 HRESULT SaveToTGAMemory(const Image& image, TGA_FLAGS flags, Blob& blob, const TexMetadata* metadata = nullptr) noexcept;
 HRESULT SaveToTGAFile(const Image& image, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata = nullptr) noexcept;
+// The reader's byte-serial half, which needs no device: header, palette, the extension area's alpha mode and gamma, the size check of a raw
+// file, the run-length packets undone. What comes back is the file's texels in the file's order, bytesPerTexel bytes each, and how to read
+// them; `metadata` is the loader's except for the alpha rule, which needs the texels (an opaque image gets TEX_ALPHA_MODE_OPAQUE).
+struct TGARawImage
+{
+    const uint8_t* texels = nullptr;             // width * height * bytesPerTexel bytes: inside the caller's buffer (a raw file: no copy) or in `storage`
+    size_t texelBytes = 0;
+    uint32_t bytesPerTexel = 0;                  // 1 (grey, or a palette index), 2, 3 or 4
+    DXGI_FORMAT format = DXGI_FORMAT_UNKNOWN;    // the image's, before gamma relabels it sRGB
+    bool paletted = false, rightToLeft = false, topDown = false;
+    uint32_t palette[256] = {};                  // colour-mapped files: the words an index stands for, zero outside the file's map
+    Blob storage;                                // a run-length file's texels; LoadFromTGAFileRaw: the file itself where `texels` points into it
+    void Release() noexcept;
+};
+HRESULT LoadFromTGAMemoryRaw(const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata* metadata, TGARawImage& raw) noexcept;
+HRESULT LoadFromTGAFileRaw(const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, TGARawImage& raw) noexcept;
+// Resident forms: the texels cross PCIe as the file has them, 1 to 4 bytes each, and the per-texel pass runs on the device
+// (dxtex_tga_unpack_device / dxtex_tga_pack_device). HRESULTs, metadata, pixels and files are those of the host forms above. Load: one upload
+// of width * height * bytesPerTexel bytes and, for 16- and 32-bit files, a 4-byte read-back of the alpha answer; the result is released on
+// failure. Save: deviceImage's pixels are a device pointer, as DeviceScratchImage::GetImage gives; one download of the file's rows.
+HRESULT LoadFromTGAMemory(Device& device, const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device (LoadFromTGA...Raw gave metadata and raw,
+// with the same flags); applies the alpha rule to `metadata`
+HRESULT UploadTGARaw(Device& device, TexMetadata& metadata, TGA_FLAGS flags, const TGARawImage& raw, DeviceScratchImage& image) noexcept;
+// the alpha rule's answer from the raw texels, on the host: one OR over their alpha bytes, for a caller that has to state the metadata
+// before it has a device (UploadTGARaw finds the same answer on the device, where it also sets the alphas that need it)
+void ApplyTGAAlphaRule(const TGARawImage& raw, TGA_FLAGS flags, TexMetadata& metadata) noexcept;
+HRESULT LoadFromTGAFile(Device& device, const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT SaveToTGAMemory(Device& device, const Image& deviceImage, TGA_FLAGS flags, Blob& blob, const TexMetadata* metadata = nullptr) noexcept;
+HRESULT SaveToTGAFile(Device& device, const Image& deviceImage, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata = nullptr) noexcept;
 } // namespace DirectXTexAMD

@@ -5,7 +5,13 @@
 // per format, 24-bit rows for B8G8R8X8, the extension area and footer (:1183-1380, :2249-2330). One routine handles every texel
 // size here where the reference has a copy per format; tests/test_hdr_tga_cpu.py checks files, pixels, metadata and HRESULTs
 // against the reference's own codec (oracle/_ref), including truncated and mutated files. Host code.
+// The reader is split in two. LoadFromTGAMemoryRaw does what is byte-serial - header, palette, extension area, undoing the run-length
+// packets - and hands back the texels as the file orders them, B bytes each. What happens to a texel after that is dxtex_tga.h's, which
+// the GPU kernels share: the host loader runs it here, the resident forms at the end of this file run it on the device, so that a file's
+// texels cross PCIe as the bytes they are. The writer is split the same way around its rows.
 #include "DirectXTexAMD.h"
+#include "../../include/dxtex_amd.h"
+#include "../csrc/dxtex_tga.h"
 
 #include <algorithm>
 #include <cmath>
@@ -112,103 +118,37 @@ namespace
         return S_OK;
     }
 
-    struct AlphaRange { uint32_t lo = 255, hi = 0; void see(uint32_t a) noexcept { lo = std::min(lo, a); hi = std::max(hi, a); } };
-
-    // One texel of the file (B bytes at s) as the image stores it, noting its alpha.
-    inline uint32_t Texel(const uint8_t* s, DXGI_FORMAT format, bool expand, const uint32_t* palette, AlphaRange& alpha) noexcept
+    // which of dxtex_tga.h's kinds a file is: its texel's bytes, the image's format before any sRGB relabel, colour-mapped or not
+    int KindOf(DXGI_FORMAT format, uint32_t bytesPerTexel, bool paletted) noexcept
     {
-        if (palette) return palette[s[0]];
+        if (paletted) return dxtex::TGA_PALETTE;
         switch (format)
         {
-        case DXGI_FORMAT_R8_UNORM: return s[0];
-        case DXGI_FORMAT_B5G5R5A1_UNORM: { const uint32_t t = rd16(s); alpha.see((t & 0x8000) ? 255 : 0); return t; }
-        case DXGI_FORMAT_R8G8B8A8_UNORM:          // the file is B, G, R (, A)
-            if (expand) { alpha.lo = alpha.hi = 255; return (uint32_t(s[0]) << 16) | (uint32_t(s[1]) << 8) | s[2] | 0xFF000000u; }
-            alpha.see(s[3]);
-            return (uint32_t(s[0]) << 16) | (uint32_t(s[1]) << 8) | s[2] | (uint32_t(s[3]) << 24);
-        case DXGI_FORMAT_B8G8R8A8_UNORM: alpha.see(s[3]); return rd32(s);
-        default: return uint32_t(s[0]) | (uint32_t(s[1]) << 8) | (uint32_t(s[2]) << 16);          // B8G8R8X8 from 24 bits: X stays 0
+        case DXGI_FORMAT_R8_UNORM: return dxtex::TGA_GREY;
+        case DXGI_FORMAT_B5G5R5A1_UNORM: return dxtex::TGA_5551;
+        case DXGI_FORMAT_R8G8B8A8_UNORM: return bytesPerTexel == 3 ? dxtex::TGA_RGB_RGBA : dxtex::TGA_BGRA_RGBA;
+        case DXGI_FORMAT_B8G8R8A8_UNORM: return dxtex::TGA_BGRA_BGRA;
+        default: return dxtex::TGA_RGB_BGRX;
         }
     }
 
-    // UncompressPixels / CopyPixels (:381-1180). S_FALSE: every alpha turned out opaque (or was made so).
-    HRESULT ReadPixels(const uint8_t* s, size_t size, uint32_t flags, const Image& image, uint32_t how, const uint32_t* palette) noexcept
+    // UncompressPixels' packets (:381-737) undone into file-order texels of B bytes. Packets do not cross rows; any truncation is E_FAIL.
+    HRESULT ExpandPackets(const uint8_t* s, size_t size, size_t width, size_t height, size_t B, uint8_t* d) noexcept
     {
-        if (!s || !image.pixels) return E_POINTER;
         const uint8_t* end = s + size;
-        const bool expand = (how & RD_EXPAND) != 0, flipX = (how & RD_INVERTX) != 0;
-        const DXGI_FORMAT format = image.format;
-        size_t B, D;              // bytes per texel in the file and in the image
-        switch (format)
-        {
-        case DXGI_FORMAT_R8_UNORM: B = D = 1; break;
-        case DXGI_FORMAT_B5G5R5A1_UNORM: B = D = 2; break;
-        case DXGI_FORMAT_R8G8B8A8_UNORM: B = expand ? 3 : 4; D = 4; break;
-        case DXGI_FORMAT_B8G8R8A8_UNORM: B = D = 4; break;
-        case DXGI_FORMAT_B8G8R8X8_UNORM: B = 3; D = 4; break;
-        default: return E_FAIL;
-        }
-        if (palette) B = 1;
-        AlphaRange alpha;
-        auto put = [&](uint8_t*& d, uint32_t t)
-        {
-            if (D == 1) *d = uint8_t(t); else if (D == 2) wr16(d, t); else std::memcpy(d, &t, 4);
-            if (flipX) d -= D; else d += D;
-        };
-        for (size_t y = 0; y < image.height; ++y)
-        {
-            // the file's first row is the image's bottom row unless the descriptor says top-down; right-to-left likewise
-            uint8_t* d = image.pixels + image.rowPitch * ((how & RD_INVERTY) ? y : (image.height - y - 1)) + (flipX ? (image.width - 1) * D : 0);
-            if (!(how & RD_RLE))
-            {
-                for (size_t x = 0; x < image.width; ++x, s += B)
-                {
-                    if (s + (B - 1) >= end) return E_FAIL;
-                    put(d, Texel(s, format, expand, palette, alpha));
-                }
-                continue;
-            }
-            for (size_t x = 0; x < image.width;)
+        for (size_t y = 0; y < height; ++y)
+            for (size_t x = 0; x < width;)
             {
                 if (s >= end) return E_FAIL;
-                size_t n = size_t(*s & 0x7F) + 1;
+                const size_t n = size_t(*s & 0x7F) + 1;
                 const bool run = (*s & 0x80) != 0;
                 ++s;
-                if (run)
-                {
-                    if (s + (B - 1) >= end) return E_FAIL;
-                    const uint32_t t = Texel(s, format, expand, nullptr, alpha);
-                    s += B;
-                    for (; n > 0; --n, ++x)
-                    {
-                        if (x >= image.width) return E_FAIL;           // packets do not cross rows
-                        put(d, t);
-                    }
-                }
-                else
-                {
-                    if (s + n * B > end) return E_FAIL;
-                    for (; n > 0; --n, ++x, s += B)
-                    {
-                        if (x >= image.width) return E_FAIL;
-                        put(d, Texel(s, format, expand, nullptr, alpha));
-                    }
-                }
+                if (size_t(end - s) < (run ? B : n * B) || n > width - x) return E_FAIL;
+                if (run) { for (size_t i = 0; i < n; ++i, d += B) std::memcpy(d, s, B); s += B; }
+                else { std::memcpy(d, s, n * B); s += n * B; d += n * B; }
+                x += n;
             }
-        }
-        if (palette || format == DXGI_FORMAT_R8_UNORM || format == DXGI_FORMAT_B8G8R8X8_UNORM) return S_OK;
-        if (alpha.hi == 0 && !(flags & TGA_FLAGS_ALLOW_ALL_ZERO_ALPHA))
-        {
-            // an alpha channel that is zero everywhere was not meant: make it opaque
-            for (size_t y = 0; y < image.height; ++y)
-            {
-                uint8_t* row = image.pixels + y * image.rowPitch;
-                if (D == 2) for (size_t x = 0; x < image.width; ++x) row[x * 2 + 1] |= 0x80;
-                else for (size_t x = 0; x < image.width; ++x) row[x * 4 + 3] = 0xFF;
-            }
-            return 1;         // S_FALSE
-        }
-        return (alpha.lo == 255) ? 1 : S_OK;
+        return S_OK;
     }
 
     // the extension area the footer points at, if the file has a TGA 2.0 footer and the area lies inside the file
@@ -253,7 +193,7 @@ namespace
         return format;
     }
 
-    HRESULT ReadAll(const char* szFile, std::vector<uint8_t>& buf, size_t minimum) noexcept
+    HRESULT ReadAll(const char* szFile, Blob& buf, size_t minimum) noexcept
     {
         FILE* f = std::fopen(szFile, "rb");
         if (!f) return E_FAIL;
@@ -261,10 +201,21 @@ namespace
         if (n < 0) { std::fclose(f); return E_FAIL; }
         if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
         if (size_t(n) < minimum) { std::fclose(f); return E_FAIL; }
-        try { buf.resize(size_t(n)); } catch (...) { std::fclose(f); return E_OUTOFMEMORY; }
-        const size_t got = buf.empty() ? 0 : std::fread(buf.data(), 1, buf.size(), f);
+        const HRESULT hr = buf.Initialize(size_t(n));
+        if (FAILED(hr)) { std::fclose(f); return hr; }
+        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
         std::fclose(f);
-        return got == buf.size() ? S_OK : E_FAIL;
+        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
+    }
+
+    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
+    {
+        FILE* f = std::fopen(szFile, "wb");
+        if (!f) return E_FAIL;
+        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
+        const bool closed = std::fclose(f) == 0;
+        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
+        return S_OK;
     }
 }
 
@@ -284,17 +235,18 @@ HRESULT GetMetadataFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS fla
 HRESULT GetMetadataFromTGAFile(const char* szFile, TGA_FLAGS flags, TexMetadata& metadata) noexcept
 {
     if (!szFile) return E_INVALIDARG;
-    std::vector<uint8_t> buf;
+    Blob buf;
     const HRESULT hr = ReadAll(szFile, buf, kHeaderLen);
     if (FAILED(hr)) return hr;
-    return GetMetadataFromTGAMemory(buf.data(), buf.size(), flags, metadata);
+    return GetMetadataFromTGAMemory(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata);
 }
 
-// LoadFromTGAMemory (DirectXTexTGA.cpp:1640-1745)
-HRESULT LoadFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
+// LoadFromTGAMemory's byte-serial half (DirectXTexTGA.cpp:1640-1745 around CopyPixels): header, palette, extension area, the size check of a
+// raw file, the packets of a run-length one
+HRESULT LoadFromTGAMemoryRaw(const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata* metadata, TGARawImage& raw) noexcept
 {
+    raw.Release();          // on any failure the result is empty
     if (!pSource || size == 0) return E_INVALIDARG;
-    image.Release();
     const uint8_t* p = static_cast<const uint8_t*>(pSource);
     size_t offset; uint32_t how = 0;
     TexMetadata mdata;
@@ -302,27 +254,98 @@ HRESULT LoadFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, Tex
     if (FAILED(hr)) return hr;
     if (offset > size) return HRESULT_E_INVALID_DATA;
     size_t mapBytes = 0;
-    uint32_t palette[256] = {};
     if (how & RD_PALETTED)
     {
         if (size - offset == 0) return E_FAIL;
-        hr = ReadPalette(ParseHeader(p), p + offset, size - offset, flags, palette, mapBytes);
-        if (FAILED(hr)) return hr;
+        hr = ReadPalette(ParseHeader(p), p + offset, size - offset, flags, raw.palette, mapBytes);
+        if (FAILED(hr)) { raw.Release(); return hr; }
     }
     const size_t remaining = size - offset - mapBytes;
-    if (remaining == 0) return HRESULT_E_HANDLE_EOF;
-    hr = image.Initialize2D(mdata.format, mdata.width, mdata.height, 1, 1);
-    if (FAILED(hr)) return hr;
-    hr = ReadPixels(p + offset + mapBytes, remaining, flags, *image.GetImage(0, 0, 0), how, (how & RD_PALETTED) ? palette : nullptr);
-    if (FAILED(hr)) { image.Release(); return hr; }
-    const uint8_t* ext = FindExtension(p, size);
-    if (!(flags & TGA_FLAGS_IGNORE_SRGB)) mdata.format = ApplyGamma(ext, mdata.format, flags, &image);
-    if (metadata)
+    if (remaining == 0) { raw.Release(); return HRESULT_E_HANDLE_EOF; }
+    const size_t B = (how & RD_PALETTED) ? 1 : ParseHeader(p).bitsPerPixel / 8, texels = mdata.width * mdata.height;
+    const uint8_t* s = p + offset + mapBytes;
+    if (!(how & RD_RLE))
     {
-        *metadata = mdata;
-        if (hr == 1) metadata->SetAlphaMode(TEX_ALPHA_MODE_OPAQUE);
-        else if (ext) metadata->SetAlphaMode(AlphaModeOf(ext));
+        if (remaining < texels * B) { raw.Release(); return E_FAIL; }
+        raw.texels = s;
     }
+    else
+    {
+        // a packet of 1 + B bytes or more holds 128 texels at the most: a file too short for its size fails before anything is allocated
+        if ((remaining / (1 + B) + 1) * 128 < texels) { raw.Release(); return E_FAIL; }
+        hr = raw.storage.Initialize(texels * B);
+        if (SUCCEEDED(hr)) hr = ExpandPackets(s, remaining, mdata.width, mdata.height, B, raw.storage.GetBufferPointer());
+        if (FAILED(hr)) { raw.Release(); return hr; }
+        raw.texels = raw.storage.GetBufferPointer();
+    }
+    raw.texelBytes = texels * B;
+    raw.bytesPerTexel = uint32_t(B);
+    raw.format = mdata.format;
+    raw.paletted = (how & RD_PALETTED) != 0;
+    raw.rightToLeft = (how & RD_INVERTX) != 0;
+    raw.topDown = (how & RD_INVERTY) != 0;
+    const uint8_t* ext = FindExtension(p, size);
+    if (!(flags & TGA_FLAGS_IGNORE_SRGB)) mdata.format = ApplyGamma(ext, mdata.format, flags, nullptr);
+    if (ext) mdata.SetAlphaMode(AlphaModeOf(ext));
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromTGAFileRaw(const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, TGARawImage& raw) noexcept
+{
+    raw.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    HRESULT hr = ReadAll(szFile, file, kHeaderLen);
+    if (FAILED(hr)) return hr;
+    hr = LoadFromTGAMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, raw);
+    if (SUCCEEDED(hr) && !raw.storage.GetBufferPointer()) raw.storage.Swap(file);          // a raw file: the texels lie inside it
+    return hr;
+}
+
+// LoadFromTGAMemory (DirectXTexTGA.cpp:1640-1745)
+HRESULT LoadFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
+{
+    if (!pSource || size == 0) return E_INVALIDARG;
+    image.Release();
+    TexMetadata mdata; TGARawImage raw;
+    HRESULT hr = LoadFromTGAMemoryRaw(pSource, size, flags, &mdata, raw);
+    if (FAILED(hr)) return hr;
+    hr = image.Initialize2D(raw.format, mdata.width, mdata.height, 1, 1);
+    if (FAILED(hr)) return hr;
+    const Image* img = image.GetImage(0, 0, 0);
+    if (!img) { image.Release(); return E_POINTER; }
+    // CopyPixels' texel half (:738-1180): the file's first row is the image's bottom row unless the descriptor says top-down; right-to-left likewise
+    const int kind = KindOf(raw.format, raw.bytesPerTexel, raw.paletted);
+    const size_t B = raw.bytesPerTexel, D = dxtex::tga_image_bytes(kind);
+    uint32_t orAlpha = 0, orNotAlpha = 0;
+    const uint8_t* s = raw.texels;
+    for (size_t y = 0; y < img->height; ++y)
+    {
+        uint8_t* row = img->pixels + img->rowPitch * (raw.topDown ? y : img->height - y - 1);
+        for (size_t x = 0; x < img->width; ++x, s += B)
+        {
+            uint32_t alpha;
+            const uint32_t t = dxtex::tga_unpack_texel(dxtex::tga_load(s, uint32_t(B)), kind, raw.palette, alpha);
+            dxtex::tga_store(row + (raw.rightToLeft ? img->width - 1 - x : x) * D, t, uint32_t(D));
+            orAlpha |= alpha; orNotAlpha |= alpha ^ 255u;
+        }
+    }
+    bool opaque = kind == dxtex::TGA_RGB_RGBA;
+    if (dxtex::tga_has_alpha_rule(kind))
+    {
+        bool makeOpaque;
+        opaque = dxtex::tga_alpha_answer(orAlpha, orNotAlpha, (flags & TGA_FLAGS_ALLOW_ALL_ZERO_ALPHA) != 0, makeOpaque) != 0;
+        if (makeOpaque)          // an alpha channel that is zero everywhere was not meant
+            for (size_t y = 0; y < img->height; ++y)
+            {
+                uint8_t* top = img->pixels + y * img->rowPitch + (D - 1);
+                for (size_t x = 0; x < img->width; ++x, top += D) *top = D == 2 ? uint8_t(*top | 0x80) : uint8_t(0xFF);
+            }
+    }
+    image.OverrideFormat(mdata.format);
+    if (opaque) mdata.SetAlphaMode(TEX_ALPHA_MODE_OPAQUE);
+    if (metadata) *metadata = mdata;
     return S_OK;
 }
 
@@ -330,77 +353,102 @@ HRESULT LoadFromTGAFile(const char* szFile, TGA_FLAGS flags, TexMetadata* metada
 {
     if (!szFile) return E_INVALIDARG;
     image.Release();
-    std::vector<uint8_t> buf;
+    Blob buf;
     const HRESULT hr = ReadAll(szFile, buf, kHeaderLen);
     if (FAILED(hr)) return hr;
-    return LoadFromTGAMemory(buf.data(), buf.size(), flags, metadata, image);
+    return LoadFromTGAMemory(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, image);
+}
+
+namespace
+{
+    // SaveToTGAMemory's checks and header choice per format (DirectXTexTGA.cpp:1183-1287, :2249-2275)
+    struct FileShape { uint8_t type, bits, descriptor; int row; };
+    HRESULT SaveChecks(const Image& image, TGA_FLAGS flags, const TexMetadata* metadata, FileShape& f) noexcept
+    {
+        if ((flags & (TGA_FLAGS_FORCE_LINEAR | TGA_FLAGS_FORCE_SRGB)) != 0 && !metadata) return E_INVALIDARG;
+        if (!image.pixels) return E_POINTER;
+        if (image.width > UINT16_MAX || image.height > UINT16_MAX) return HRESULT_E_NOT_SUPPORTED;
+        switch (image.format)
+        {
+        case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: f = { IMG_TRUECOLOR, 32, DESC_INVERTY | 8, dxtex::TGA_ROW_SWAP_RB }; break;
+        case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: f = { IMG_TRUECOLOR, 32, DESC_INVERTY | 8, dxtex::TGA_ROW_COPY }; break;
+        case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: f = { IMG_TRUECOLOR, 24, DESC_INVERTY, dxtex::TGA_ROW_DROP_X }; break;
+        case DXGI_FORMAT_R8_UNORM: case DXGI_FORMAT_A8_UNORM: f = { IMG_GREY, 8, DESC_INVERTY, dxtex::TGA_ROW_COPY }; break;
+        case DXGI_FORMAT_B5G5R5A1_UNORM: f = { IMG_TRUECOLOR, 16, DESC_INVERTY | 1, dxtex::TGA_ROW_COPY }; break;
+        default: return HRESULT_E_NOT_SUPPORTED;
+        }
+        return S_OK;
+    }
+
+    // The file around the texels: the 18-byte header, then rows(d) leaves width * height texels of bits / 8 bytes at d, top-down and
+    // tight; with metadata the TGA 2.0 extension area follows, and the footer.
+    template<class Rows>
+    HRESULT WriteFile(const Image& image, const FileShape& f, TGA_FLAGS flags, const TexMetadata* metadata, Blob& blob, Rows&& rows) noexcept
+    {
+        blob.Release();
+        const size_t slicePitch = image.width * (f.bits / 8) * image.height;
+        HRESULT hr = blob.Initialize(kHeaderLen + slicePitch + (metadata ? kExtensionLen : 0) + kFooterLen);
+        if (FAILED(hr)) return hr;
+        uint8_t* base = blob.GetBufferPointer();
+        std::memset(base, 0, kHeaderLen);
+        base[2] = f.type; wr16(base + 12, uint32_t(image.width)); wr16(base + 14, uint32_t(image.height)); base[16] = f.bits; base[17] = f.descriptor;
+        hr = rows(base + kHeaderLen);
+        if (FAILED(hr)) { blob.Release(); return hr; }
+        uint8_t* d = base + kHeaderLen + slicePitch;
+        uint32_t extOffset = 0;
+        if (metadata)
+        {
+            // SetExtension (:1322-1380): who wrote it, gamma, what the alpha channel means, when
+            std::memset(d, 0, kExtensionLen);
+            wr16(d, kExtensionLen);
+            std::memcpy(d + EXT_SOFTWARE, "DirectXTex", sizeof("DirectXTex"));
+            wr16(d + EXT_VERSION, 211); d[EXT_VERSION_LETTER] = ' ';          // DIRECTX_TEX_VERSION of the reference this mirrors (DirectXTex.h:50)
+            const bool srgb = !(flags & TGA_FLAGS_FORCE_LINEAR) && ((flags & TGA_FLAGS_FORCE_SRGB) || IsSRGB(metadata->format));
+            if (srgb) { wr16(d + EXT_GAMMA, 22); wr16(d + EXT_GAMMA + 2, 10); }
+            else if (flags & TGA_FLAGS_FORCE_LINEAR) { wr16(d + EXT_GAMMA, 1); wr16(d + EXT_GAMMA + 2, 1); }
+            switch (metadata->GetAlphaMode())
+            {
+            case TEX_ALPHA_MODE_STRAIGHT: d[EXT_ATTRIBUTES] = ATTR_ALPHA; break;
+            case TEX_ALPHA_MODE_PREMULTIPLIED: d[EXT_ATTRIBUTES] = ATTR_PREMULTIPLIED; break;
+            case TEX_ALPHA_MODE_OPAQUE: d[EXT_ATTRIBUTES] = ATTR_IGNORED; break;
+            case TEX_ALPHA_MODE_CUSTOM: d[EXT_ATTRIBUTES] = ATTR_UNDEFINED; break;
+            default: d[EXT_ATTRIBUTES] = HasAlpha(metadata->format) ? ATTR_UNDEFINED : ATTR_NONE; break;
+            }
+            std::time_t now = {};
+            std::time(&now);
+            if (const std::tm* t = std::gmtime(&now))
+            {
+                wr16(d + EXT_STAMP, uint32_t(t->tm_mon + 1)); wr16(d + EXT_STAMP + 2, uint32_t(t->tm_mday)); wr16(d + EXT_STAMP + 4, uint32_t(t->tm_year + 1900));
+                wr16(d + EXT_STAMP + 6, uint32_t(t->tm_hour)); wr16(d + EXT_STAMP + 8, uint32_t(t->tm_min)); wr16(d + EXT_STAMP + 10, uint32_t(t->tm_sec));
+            }
+            extOffset = uint32_t(d - base);
+            d += kExtensionLen;
+        }
+        std::memcpy(d, &extOffset, 4);
+        std::memset(d + 4, 0, 4);
+        std::memcpy(d + 8, kSignature, sizeof(kSignature));
+        return S_OK;
+    }
 }
 
 // SaveToTGAMemory (DirectXTexTGA.cpp:2249-2330): uncompressed, top-down; with metadata a TGA 2.0 extension area is added
 HRESULT SaveToTGAMemory(const Image& image, TGA_FLAGS flags, Blob& blob, const TexMetadata* metadata) noexcept
 {
-    if ((flags & (TGA_FLAGS_FORCE_LINEAR | TGA_FLAGS_FORCE_SRGB)) != 0 && !metadata) return E_INVALIDARG;
-    if (!image.pixels) return E_POINTER;
-    if (image.width > UINT16_MAX || image.height > UINT16_MAX) return HRESULT_E_NOT_SUPPORTED;
-    uint8_t type, bits, descriptor;
-    enum { ROW_COPY, ROW_SWAP_RB, ROW_DROP_X } row = ROW_COPY;
-    switch (image.format)
-    {
-    case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: type = IMG_TRUECOLOR; bits = 32; descriptor = DESC_INVERTY | 8; row = ROW_SWAP_RB; break;
-    case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: type = IMG_TRUECOLOR; bits = 32; descriptor = DESC_INVERTY | 8; break;
-    case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: type = IMG_TRUECOLOR; bits = 24; descriptor = DESC_INVERTY; row = ROW_DROP_X; break;
-    case DXGI_FORMAT_R8_UNORM: case DXGI_FORMAT_A8_UNORM: type = IMG_GREY; bits = 8; descriptor = DESC_INVERTY; break;
-    case DXGI_FORMAT_B5G5R5A1_UNORM: type = IMG_TRUECOLOR; bits = 16; descriptor = DESC_INVERTY | 1; break;
-    default: return HRESULT_E_NOT_SUPPORTED;
-    }
-    blob.Release();
-    const size_t rowPitch = image.width * (bits / 8), slicePitch = rowPitch * image.height;
-    HRESULT hr = blob.Initialize(kHeaderLen + slicePitch + (metadata ? kExtensionLen : 0) + kFooterLen);
+    FileShape f;
+    const HRESULT hr = SaveChecks(image, flags, metadata, f);
     if (FAILED(hr)) return hr;
-    uint8_t* base = blob.GetBufferPointer();
-    std::memset(base, 0, kHeaderLen);
-    base[2] = type; wr16(base + 12, uint32_t(image.width)); wr16(base + 14, uint32_t(image.height)); base[16] = bits; base[17] = descriptor;
-    uint8_t* d = base + kHeaderLen;
-    for (size_t y = 0; y < image.height; ++y, d += rowPitch)
+    const size_t B = f.bits / 8, D = f.row == dxtex::TGA_ROW_DROP_X ? 4 : B;
+    return WriteFile(image, f, flags, metadata, blob, [&](uint8_t* d)
     {
-        const uint8_t* s = image.pixels + y * image.rowPitch;
-        if (row == ROW_DROP_X) { for (size_t x = 0; x < image.width && x * 4 + 3 < image.rowPitch; ++x) { d[x * 3] = s[x * 4]; d[x * 3 + 1] = s[x * 4 + 1]; d[x * 3 + 2] = s[x * 4 + 2]; } }
-        else if (row == ROW_SWAP_RB) { for (size_t x = 0; x < image.width && x * 4 + 3 < image.rowPitch; ++x) { d[x * 4] = s[x * 4 + 2]; d[x * 4 + 1] = s[x * 4 + 1]; d[x * 4 + 2] = s[x * 4]; d[x * 4 + 3] = s[x * 4 + 3]; } }
-        else std::memcpy(d, s, std::min(rowPitch, image.rowPitch));
-    }
-    uint32_t extOffset = 0;
-    if (metadata)
-    {
-        // SetExtension (:1322-1380): who wrote it, gamma, what the alpha channel means, when
-        std::memset(d, 0, kExtensionLen);
-        wr16(d, kExtensionLen);
-        std::memcpy(d + EXT_SOFTWARE, "DirectXTex", sizeof("DirectXTex"));
-        wr16(d + EXT_VERSION, 211); d[EXT_VERSION_LETTER] = ' ';          // DIRECTX_TEX_VERSION of the reference this mirrors (DirectXTex.h:50)
-        const bool srgb = !(flags & TGA_FLAGS_FORCE_LINEAR) && ((flags & TGA_FLAGS_FORCE_SRGB) || IsSRGB(metadata->format));
-        if (srgb) { wr16(d + EXT_GAMMA, 22); wr16(d + EXT_GAMMA + 2, 10); }
-        else if (flags & TGA_FLAGS_FORCE_LINEAR) { wr16(d + EXT_GAMMA, 1); wr16(d + EXT_GAMMA + 2, 1); }
-        switch (metadata->GetAlphaMode())
+        for (size_t y = 0; y < image.height; ++y)
         {
-        case TEX_ALPHA_MODE_STRAIGHT: d[EXT_ATTRIBUTES] = ATTR_ALPHA; break;
-        case TEX_ALPHA_MODE_PREMULTIPLIED: d[EXT_ATTRIBUTES] = ATTR_PREMULTIPLIED; break;
-        case TEX_ALPHA_MODE_OPAQUE: d[EXT_ATTRIBUTES] = ATTR_IGNORED; break;
-        case TEX_ALPHA_MODE_CUSTOM: d[EXT_ATTRIBUTES] = ATTR_UNDEFINED; break;
-        default: d[EXT_ATTRIBUTES] = HasAlpha(metadata->format) ? ATTR_UNDEFINED : ATTR_NONE; break;
+            const uint8_t* s = image.pixels + y * image.rowPitch;
+            for (size_t x = 0; x < image.width && x * D + (D - 1) < image.rowPitch; ++x)          // a pitch below the row leaves the rest of it as allocated
+                dxtex::tga_store(d + x * B, dxtex::tga_pack_texel(dxtex::tga_load(s + x * D, uint32_t(D)), f.row), uint32_t(B));
+            d += image.width * B;
         }
-        std::time_t now = {};
-        std::time(&now);
-        if (const std::tm* t = std::gmtime(&now))
-        {
-            wr16(d + EXT_STAMP, uint32_t(t->tm_mon + 1)); wr16(d + EXT_STAMP + 2, uint32_t(t->tm_mday)); wr16(d + EXT_STAMP + 4, uint32_t(t->tm_year + 1900));
-            wr16(d + EXT_STAMP + 6, uint32_t(t->tm_hour)); wr16(d + EXT_STAMP + 8, uint32_t(t->tm_min)); wr16(d + EXT_STAMP + 10, uint32_t(t->tm_sec));
-        }
-        extOffset = uint32_t(d - base);
-        d += kExtensionLen;
-    }
-    std::memcpy(d, &extOffset, 4);
-    std::memset(d + 4, 0, 4);
-    std::memcpy(d + 8, kSignature, sizeof(kSignature));
-    return S_OK;
+        return S_OK;
+    });
 }
 
 HRESULT SaveToTGAFile(const Image& image, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata) noexcept
@@ -409,11 +457,140 @@ HRESULT SaveToTGAFile(const Image& image, TGA_FLAGS flags, const char* szFile, c
     Blob blob;
     const HRESULT hr = SaveToTGAMemory(image, flags, blob, metadata);
     if (FAILED(hr)) return hr;
-    FILE* f = std::fopen(szFile, "wb");
-    if (!f) return E_FAIL;
-    const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
-    const bool closed = std::fclose(f) == 0;
-    if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
+    return WriteBlob(blob, szFile);
+}
+
+// ---- resident forms: the texels travel as the file has them, the per-texel pass runs on the device (dxtex_tga_unpack_device / dxtex_tga_pack_device) ----
+namespace
+{
+    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
+    struct DeviceTemp
+    {
+        Device& device; void* p = nullptr;
+        explicit DeviceTemp(Device& d) noexcept : device(d) {}
+        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
+        DeviceTemp(const DeviceTemp&) = delete;
+        DeviceTemp& operator=(const DeviceTemp&) = delete;
+    };
+}
+
+void TGARawImage::Release() noexcept
+{
+    storage.Release();
+    std::memset(palette, 0, sizeof(palette));
+    texels = nullptr; texelBytes = 0; bytesPerTexel = 0; format = DXGI_FORMAT_UNKNOWN;
+    paletted = rightToLeft = topDown = false;
+}
+
+void ApplyTGAAlphaRule(const TGARawImage& raw, TGA_FLAGS flags, TexMetadata& metadata) noexcept
+{
+    const int kind = KindOf(raw.format, raw.bytesPerTexel, raw.paletted);
+    bool opaque = kind == dxtex::TGA_RGB_RGBA;
+    if (dxtex::tga_has_alpha_rule(kind) && raw.texels)
+    {
+        // the texel's top byte holds alpha (its top bit, for 5:5:5:1)
+        const uint32_t B = raw.bytesPerTexel, mask = B == 2 ? 0x80u : 0xFFu;
+        uint32_t orAlpha = 0, orNotAlpha = 0;
+        for (const uint8_t* top = raw.texels + (B - 1), *end = raw.texels + raw.texelBytes; top < end; top += B) { orAlpha |= *top & mask; orNotAlpha |= ~*top & mask; }
+        bool makeOpaque;
+        opaque = dxtex::tga_alpha_answer(orAlpha, orNotAlpha, (flags & TGA_FLAGS_ALLOW_ALL_ZERO_ALPHA) != 0, makeOpaque) != 0;
+    }
+    if (opaque) metadata.SetAlphaMode(TEX_ALPHA_MODE_OPAQUE);
+}
+
+HRESULT UploadTGARaw(Device& device, TexMetadata& metadata, TGA_FLAGS flags, const TGARawImage& raw, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!device) return E_POINTER;
+    if (!raw.texels || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1 ||
+        raw.texelBytes != metadata.width * metadata.height * raw.bytesPerTexel) return E_INVALIDARG;
+    TexMetadata plain = metadata;          // the image as ScratchImage::Initialize2D would describe it; the sRGB relabel follows the pixels
+    plain.format = raw.format; plain.miscFlags = 0; plain.miscFlags2 = 0;
+    HRESULT hr = image.Initialize(device, plain);
+    if (FAILED(hr)) return hr;
+    const Image* img = image.GetImage(0, 0, 0);
+    if (!img) { image.Release(); return E_POINTER; }
+    const int kind = KindOf(raw.format, raw.bytesPerTexel, raw.paletted);
+    const bool rule = dxtex::tga_has_alpha_rule(kind);
+    // the stream, and behind it (on a dword) the alpha answer
+    const size_t answerAt = (raw.texelBytes + 3) & ~size_t(3);
+    DeviceTemp temp(device);
+    hr = dxtex_device_alloc(device.Get(), answerAt + 4, &temp.p);
+    // with an alpha rule the read-back of the answer below is the one wait, and the stream's copy has happened by then; without one the
+    // synchronous copy is: the host texels are free to go when this returns
+    if (SUCCEEDED(hr)) hr = rule ? dxtex_memcpy_h2d_async(device.Get(), temp.p, raw.texels, raw.texelBytes) : dxtex_memcpy_h2d(device.Get(), temp.p, raw.texels, raw.texelBytes);
+    uint32_t opaque = kind == dxtex::TGA_RGB_RGBA ? 1u : 0u;
+    if (SUCCEEDED(hr))
+    {
+        const uint32_t how = (raw.rightToLeft ? DXTEX_TGA_RIGHT_TO_LEFT : 0u) | (raw.topDown ? DXTEX_TGA_TOP_DOWN : 0u) |
+                             ((flags & TGA_FLAGS_ALLOW_ALL_ZERO_ALPHA) ? DXTEX_TGA_ALLOW_ALL_ZERO_ALPHA : 0u);
+        const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
+        uint32_t* answer = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(temp.p) + answerAt);
+        hr = dxtex_tga_unpack_device(device.Get(), temp.p, raw.texelBytes, raw.bytesPerTexel, how, raw.paletted ? raw.palette : nullptr, &d, rule ? answer : nullptr);
+        if (rule)
+        {
+            // queued or not, the stream's copy reads the caller's texels: wait for it either way
+            const HRESULT waited = dxtex_memcpy_d2h(device.Get(), &opaque, answer, sizeof(opaque));
+            if (SUCCEEDED(hr)) hr = waited;
+        }
+    }
+    if (FAILED(hr)) { image.Release(); return hr; }
+    image.OverrideFormat(metadata.format);
+    if (opaque) metadata.SetAlphaMode(TEX_ALPHA_MODE_OPAQUE);
     return S_OK;
+}
+
+HRESULT LoadFromTGAMemory(Device& device, const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    image.Release();          // on any failure the result is empty
+    if (!pSource || size == 0) return E_INVALIDARG;
+    TexMetadata mdata; TGARawImage raw;
+    HRESULT hr = LoadFromTGAMemoryRaw(pSource, size, flags, &mdata, raw);
+    if (FAILED(hr)) return hr;
+    hr = UploadTGARaw(device, mdata, flags, raw, image);
+    if (FAILED(hr)) return hr;
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromTGAFile(Device& device, const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob buf;
+    const HRESULT hr = ReadAll(szFile, buf, kHeaderLen);
+    if (FAILED(hr)) return hr;
+    return LoadFromTGAMemory(device, buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, image);
+}
+
+HRESULT SaveToTGAMemory(Device& device, const Image& deviceImage, TGA_FLAGS flags, Blob& blob, const TexMetadata* metadata) noexcept
+{
+    FileShape f;
+    const HRESULT hr = SaveChecks(deviceImage, flags, metadata, f);
+    if (FAILED(hr)) return hr;
+    if (!device) return E_POINTER;
+    const uint32_t B = f.bits / 8;
+    const size_t bytes = deviceImage.width * deviceImage.height * B;
+    return WriteFile(deviceImage, f, flags, metadata, blob, [&](uint8_t* d)
+    {
+        DeviceTemp temp(device);
+        HRESULT hr2 = dxtex_device_alloc(device.Get(), bytes, &temp.p);
+        if (SUCCEEDED(hr2))
+        {
+            const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
+            hr2 = dxtex_tga_pack_device(device.Get(), &s, B, temp.p, bytes);
+        }
+        if (SUCCEEDED(hr2)) hr2 = dxtex_memcpy_d2h(device.Get(), d, temp.p, bytes);          // straight behind the header; returns when the rows have landed
+        return hr2;
+    });
+}
+
+HRESULT SaveToTGAFile(Device& device, const Image& deviceImage, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveToTGAMemory(device, deviceImage, flags, blob, metadata);
+    if (FAILED(hr)) return hr;
+    return WriteBlob(blob, szFile);
 }
 } // namespace DirectXTexAMD

@@ -310,7 +310,8 @@ int Fail(const char* what, HRESULT hr)
 }
 
 // an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
-struct Input { TexMetadata info; ScratchImage image; bool hdr = false; float exposure = 1.f; Blob rgbe; };
+// a .tga input likewise as the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
+struct Input { TexMetadata info; ScratchImage image; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; };
 
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
 int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
@@ -348,7 +349,13 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
                 return 1;
             }
         }
-        else if (hasExt(file, ".tga")) { hr = LoadFromTGAFile(file.c_str(), TGA_FLAGS_NONE, &in->info, in->image); if (FAILED(hr)) return Fail(" FAILED", hr); }
+        else if (hasExt(file, ".tga"))
+        {
+            in->tga = true;
+            hr = LoadFromTGAFileRaw(file.c_str(), TGA_FLAGS_NONE, &in->info, in->tgaRaw);
+            if (FAILED(hr)) return Fail(" FAILED", hr);
+            ApplyTGAAlphaRule(in->tgaRaw, TGA_FLAGS_NONE, in->info);          // the line below states the alpha mode
+        }
         else if (hasExt(file, ".hdr")) { in->hdr = true; hr = LoadFromHDRFileRGBE(file.c_str(), &in->info, in->exposure, in->rgbe); if (FAILED(hr)) return Fail(" FAILED", hr); }
         else { std::printf(" FAILED: only .dds, .tga and .hdr can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
@@ -388,9 +395,10 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     {
         DeviceScratchImage cur, next;
         Input& in = *inputs[index];
-        HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : cur.Upload(dev, in.image);
+        HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : in.tga ? UploadTGARaw(dev, in.info, TGA_FLAGS_NONE, in.tgaRaw, cur)
+                                                                                              : cur.Upload(dev, in.image);
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        in.image.Release(); in.rgbe.Release();
+        in.image.Release(); in.rgbe.Release(); in.tgaRaw.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
@@ -509,9 +517,9 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     if (FAILED(hr)) return Fail("FAILED building result image", hr);
 
     // an .hdr output comes back as the RGBE rows the resident saver makes on the device; everything else as it is
-    const bool hdrOut = hasExt(o.output, ".hdr");
+    const bool hdrOut = hasExt(o.output, ".hdr"), tgaOut = hasExt(o.output, ".tga");          // .tga: the file's rows, likewise
     ScratchImage out;
-    if (!hdrOut)
+    if (!hdrOut && !tgaOut)
     {
         hr = result.Download(out);
         if (FAILED(hr)) return Fail("FAILED building result image", hr);
@@ -523,7 +531,7 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     struct stat st;
     if (!o.overwrite && stat(o.output.c_str(), &st) == 0) { std::printf("\nERROR: Output file already exists, use -y to overwrite\n"); return 1; }
     if (hdrOut) hr = SaveToHDRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());
-    else if (hasExt(o.output, ".tga")) hr = SaveToTGAFile(*out.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
+    else if (tgaOut) hr = SaveToTGAFile(dev, *result.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
     else hr = SaveToDDSFile(out.GetImages(), out.GetImageCount(), out.GetMetadata(),
                             o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED", hr);

@@ -354,17 +354,18 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     auto hasExt = [](const std::string& f, const char* ext) { const size_t n = std::strlen(ext); return f.size() > n && !strcasecmp(f.c_str() + f.size() - n, ext); };
     // Radiance RGBE -> RGBA32F: the resident loader sends the file's texels up as the 4 bytes they are and makes the floats on the device
     DeviceScratchImage image;
-    const bool hdrIn = hasExt(inFile, ".hdr");
+    const bool hdrIn = hasExt(inFile, ".hdr"), tgaIn = hasExt(inFile, ".tga");
     if (hdrIn) check("load", LoadFromHDRFile(dev, inFile.c_str(), &info, image));
-    else if (hasExt(inFile, ".tga")) check("load", LoadFromTGAFile(inFile.c_str(), TGA_FLAGS_NONE, &info, loaded));
+    // TGA likewise: the file's 1 to 4 bytes a texel go up, the swizzle, the flips and the alpha rule run on the device
+    else if (tgaIn) check("load", LoadFromTGAFile(dev, inFile.c_str(), TGA_FLAGS_NONE, &info, image));
     else check("load", LoadFromDDSFile(inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, loaded));
     std::printf("reading %s (%zux%zu", inFile.c_str(), info.width, info.height);
     if (info.dimension == TEX_DIMENSION_TEXTURE3D) std::printf("x%zu", info.depth);
     std::printf(", %zu mips, %zu items, format %u)\n", info.mipLevels, info.arraySize, unsigned(info.format));
     size_t tMips = (!o.mipLevels && info.mipLevels > 1) ? info.mipLevels : o.mipLevels;           // texconv.cpp:2270
 
-    // --- the one upload (an .hdr file's has happened: its RGBE rows)
-    if (!hdrIn) check("upload", image.Upload(dev, loaded));
+    // --- the one upload (an .hdr or .tga file's has happened: its texels as the file has them)
+    if (!hdrIn && !tgaIn) check("upload", image.Upload(dev, loaded));
     auto keep = [&](DeviceScratchImage& t)         // a step produced t: it becomes the image, metadata keeps its alpha mode
     {
         const uint32_t misc2 = info.miscFlags2;
@@ -597,16 +598,18 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     }
     // --- the one download (blocks handed through are still on the host)
     // -ft hdr: level 0 of the first item, like texconv's non-DDS codecs, comes back as RGBE rows the resident saver made on the device
-    const bool hdrResident = o.hdrOut && !handThrough;
+    // -ft tga likewise: the file's rows (-tga20: and the TGA 2.0 extension area around them)
+    const bool hdrResident = o.hdrOut && !handThrough, tgaResident = o.tgaOut && !handThrough;
     ScratchImage result;
     if (handThrough) result = std::move(cimage);
     else if (hdrResident) check("save", SaveToHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
+    else if (tgaResident) check("save", SaveToTGAFile(dev, *image.GetImage(0, 0, 0), TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));
     else check("download", image.Download(result));
     image.Release();
     uint32_t ddsFlags = DDS_FLAGS_NONE;
     if (o.dx10) ddsFlags |= DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2;
     else if (o.dx9) ddsFlags |= DDS_FLAGS_FORCE_DX9_LEGACY;
-    if (hdrResident) { }
+    if (hdrResident || tgaResident) { }
     else if (o.hdrOut) check("save", SaveToHDRFile(result.GetImages()[0], outFile.c_str()));                // blocks handed through: the host codec's answer
     else if (o.tgaOut) check("save", SaveToTGAFile(result.GetImages()[0], TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));      // -tga20: with the TGA 2.0 extension area
     else check("save", SaveToDDSFile(result.GetImages(), result.GetImageCount(), info, DDS_FLAGS(ddsFlags), outFile.c_str()));

@@ -161,11 +161,10 @@ bool Parse(int argc, char** argv, Options& o)
     return true;
 }
 
-// the loader of all three commands; a planar file becomes its single-plane form on the device, as texdiag's loader makes it (texdiag.cpp:3959-3972)
+// the host loader of all three commands (.tga files go through the resident loader instead: Side, RunAnalyze); a planar file becomes its single-plane form on the device, as texdiag's loader makes it (texdiag.cpp:3959-3972)
 HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata& info, ScratchImage& image)
 {
     if (hasExt(file, ".hdr")) return LoadFromHDRFile(file.c_str(), &info, image);
-    if (hasExt(file, ".tga")) return LoadFromTGAFile(file.c_str(), TGA_FLAGS_NONE, &info, image);
     HRESULT hr = LoadFromDDSFile(file.c_str(), DDS_FLAGS(o.ddsRead), &info, image);
     if (FAILED(hr) || !IsPlanar(info.format)) return hr;
     ScratchImage single;
@@ -175,6 +174,35 @@ HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata
     image = std::move(single);
     return S_OK;
 }
+
+// One file of compare / diff. A .tga is loaded resident: its texels go up as the file has them and become the image on the device. Every
+// other file is loaded on the host, and its first image goes up when the command turns out to work on first images.
+struct Side
+{
+    TexMetadata info;
+    ScratchImage host;
+    DeviceScratchImage resident;
+    size_t count = 0;          // images in the file
+
+    HRESULT Open(Device& dev, const Options& o, const std::string& file)
+    {
+        if (hasExt(file, ".tga")) { count = 1; return LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident); }
+        const HRESULT hr = Load(dev, o, file, info, host);
+        count = host.GetImageCount();
+        return hr;
+    }
+    // the first image on the device: what the host forms of ComputeMSE and Difference upload
+    HRESULT First(Device& dev)
+    {
+        if (resident.GetImageCount()) return S_OK;
+        const Image* first = host.GetImage(0, 0, 0);
+        if (!first) return E_POINTER;
+        TexMetadata one;
+        one.width = first->width; one.height = first->height; one.depth = one.arraySize = one.mipLevels = 1;
+        one.format = first->format; one.dimension = TEX_DIMENSION_TEXTURE2D;
+        return resident.Upload(dev, first, 1, one);
+    }
+};
 
 void Print(const AnalyzeData& d)
 {
@@ -230,11 +258,12 @@ int RunAnalyze(Device& dev, const Options& o)
         // the whole file goes up once - an .hdr file as its RGBE rows, which the resident loader turns into floats on the device; every image
         // is analysed there, the figures come back in one copy
         DeviceScratchImage resident;
-        const bool hdr = hasExt(file, ".hdr");
-        HRESULT hr = hdr ? LoadFromHDRFile(dev, file.c_str(), &info, resident) : Load(dev, o, file, info, image);
+        const bool hdr = hasExt(file, ".hdr"), tga = hasExt(file, ".tga");          // .tga likewise: the file's own bytes a texel
+        HRESULT hr = hdr ? LoadFromHDRFile(dev, file.c_str(), &info, resident) : tga ? LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident)
+                                                                                   : Load(dev, o, file, info, image);
         if (FAILED(hr)) return Fail((" FAILED loading " + file).c_str(), hr);
         std::printf("%s\n", file.c_str());
-        if (!hdr) hr = resident.Upload(dev, image);
+        if (!hdr && !tga) hr = resident.Upload(dev, image);
         if (FAILED(hr)) return Fail("ERROR: Failed uploading the images", hr);
         const size_t n = resident.GetImageCount();
         std::vector<AnalyzeData> data(n);
@@ -283,19 +312,23 @@ double Psnr(const float* v) { return 10.0 * std::log10(3.0 / (double(v[0]) + dou
 
 int RunCompare(Device& dev, const Options& o)
 {
-    TexMetadata info1, info2;
-    ScratchImage image1, image2;
-    HRESULT hr = Load(dev, o, o.files[0], info1, image1);
+    Side side1, side2;
+    HRESULT hr = side1.Open(dev, o, o.files[0]);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[0]).c_str(), hr);
-    hr = Load(dev, o, o.files[1], info2, image2);
+    hr = side2.Open(dev, o, o.files[1]);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[1]).c_str(), hr);
+    const TexMetadata& info1 = side1.info; const TexMetadata& info2 = side2.info;
+    const ScratchImage& image1 = side1.host; const ScratchImage& image2 = side2.host;
     if (info1.width != info2.width || info1.height != info2.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
     if ((info1.depth == 1 && info1.arraySize == 1 && info1.mipLevels == 1) || info1.depth != info2.depth || info1.arraySize != info2.arraySize ||
-        info1.mipLevels != info2.mipLevels || image1.GetImageCount() != image2.GetImageCount())
+        info1.mipLevels != info2.mipLevels || side1.count != side2.count)
     {
-        if (image1.GetImageCount() > 1 || image2.GetImageCount() > 1) std::printf("WARNING: ignoring all images but first one in each file\n");
+        // first images (a .tga has no other, so this is where one ends up): on the device, where a .tga already is
+        if (side1.count > 1 || side2.count > 1) std::printf("WARNING: ignoring all images but first one in each file\n");
         float mse = 0, mseV[4] = {};
-        hr = ComputeMSE(dev, *image1.GetImage(0, 0, 0), *image2.GetImage(0, 0, 0), mse, mseV, CMSE_DEFAULT);
+        hr = side1.First(dev);
+        if (SUCCEEDED(hr)) hr = side2.First(dev);
+        if (SUCCEEDED(hr)) hr = ComputeMSE(dev, side1.resident, side2.resident, mse, mseV, CMSE_DEFAULT);
         if (FAILED(hr)) return Fail("Failed comparing images", hr);
         std::printf("Result: %f (%f %f %f %f) PSNR %f dB\n", mse, mseV[0], mseV[1], mseV[2], mseV[3], Psnr(mseV));
         return 0;
@@ -343,21 +376,35 @@ int RunCompare(Device& dev, const Options& o)
 
 int RunDiff(Device& dev, const Options& o)
 {
-    TexMetadata info1, info2;
-    ScratchImage image1, image2, diff;
-    HRESULT hr = Load(dev, o, o.files[0], info1, image1);
+    Side side1, side2;
+    HRESULT hr = side1.Open(dev, o, o.files[0]);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[0]).c_str(), hr);
-    hr = Load(dev, o, o.files[1], info2, image2);
+    hr = side2.Open(dev, o, o.files[1]);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[1]).c_str(), hr);
-    if (info1.width != info2.width || info1.height != info2.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
-    if (image1.GetImageCount() > 1 || image2.GetImageCount() > 1) std::printf("WARNING: ignoring all images but first one in each file\n");
-    hr = Difference(dev, *image1.GetImage(0, 0, 0), *image2.GetImage(0, 0, 0), TEX_FILTER_FLAGS(o.filter), DXGI_FORMAT(o.format), o.diffColor, o.threshold, diff);
+    if (side1.info.width != side2.info.width || side1.info.height != side2.info.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
+    if (side1.count > 1 || side2.count > 1) std::printf("WARNING: ignoring all images but first one in each file\n");
+    DeviceScratchImage map;
+    hr = side1.First(dev);
+    if (SUCCEEDED(hr)) hr = side2.First(dev);
+    if (SUCCEEDED(hr)) hr = Difference(dev, side1.resident, side2.resident, TEX_FILTER_FLAGS(o.filter), DXGI_FORMAT(o.format), o.diffColor, o.threshold, map);
     if (FAILED(hr)) return Fail("Failed diffing images", hr);
-    const Image* out = diff.GetImage(0, 0, 0);
-    if (!out) return Fail("Failed diffing images", E_POINTER);
-    if (hasExt(o.output, ".hdr")) hr = SaveToHDRFile(*out, o.output.c_str());
-    else if (hasExt(o.output, ".tga")) hr = SaveToTGAFile(*out, TGA_FLAGS_NONE, o.output.c_str());
-    else hr = SaveToDDSFile(*out, DDS_FLAGS_NONE, o.output.c_str());
+    // a .tga comes back as the file's rows the resident saver makes on the device; the other two as the image, for the host codecs
+    if (hasExt(o.output, ".tga"))
+    {
+        const Image* out = map.GetImage(0, 0, 0);
+        if (!out) return Fail("Failed diffing images", E_POINTER);
+        hr = SaveToTGAFile(dev, *out, TGA_FLAGS_NONE, o.output.c_str());
+    }
+    else
+    {
+        ScratchImage diff;
+        hr = map.Download(diff);
+        if (FAILED(hr)) return Fail("Failed diffing images", hr);
+        const Image* out = diff.GetImage(0, 0, 0);
+        if (!out) return Fail("Failed diffing images", E_POINTER);
+        if (hasExt(o.output, ".hdr")) hr = SaveToHDRFile(*out, o.output.c_str());
+        else hr = SaveToDDSFile(*out, DDS_FLAGS_NONE, o.output.c_str());
+    }
     if (FAILED(hr)) return Fail(" FAILED writing the difference", hr);
     std::printf("Difference %s\n", o.output.c_str());
     return 0;

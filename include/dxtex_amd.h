@@ -32,6 +32,9 @@
  *   ConvertToSinglePlane                       DirectXTexConvert.cpp:4912-5077, :5411-5523  dxtex_convert_to_single_plane[_device]
  *   LoadFromHDRMemory's float pass,            DirectXTexHDR.cpp:887-901, :328-407  dxtex_rgbe_decode / dxtex_rgbe_encode
  *     FloatToRGBE / HalfToRGBE
+ *   CopyPixels / UncompressPixels' texel half, DirectXTexTGA.cpp:396-1180;     dxtex_tga_unpack / dxtex_tga_pack
+ *     Copy24bppScanline / the swizzle of         :1288, :2249-2330
+ *     SaveToTGAMemory
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -306,6 +309,42 @@ dxtex_hresult dxtex_rgbe_encode(dxtex_ctx* ctx, const dxtex_image* src, const dx
 /* device pointers: asynchronous on the context's stream */
 dxtex_hresult dxtex_rgbe_decode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure);
 dxtex_hresult dxtex_rgbe_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst);
+
+/* Truevision TGA (.tga) texels, the per-texel half of the codec (header, palette bytes and run-length packets are byte-serial and stay
+ * with the caller). One image per call. The file side is the texel stream: `texelBytes` bytes, tight rows of width * bytesPerTexel, in
+ * the file's order - its first row is the image's bottom row unless DXTEX_TGA_TOP_DOWN, its first texel the rightmost one if
+ * DXTEX_TGA_RIGHT_TO_LEFT (bits 5 and 4 of the file's descriptor).
+ *   unpack   stream -> dst, through dst's pitch, both flips applied (CopyPixels, DirectXTexTGA.cpp:738-1180):
+ *              bytesPerTexel  dst->format       texel
+ *              1              R8_UNORM          the byte
+ *              2              B5G5R5A1_UNORM    the word; alpha counts as 0 or 255 by bit 15
+ *              3              R8G8B8A8_UNORM    B, G, R -> R, G, B, 255: opaque by construction
+ *              3              B8G8R8X8_UNORM    B, G, R, 0 (TGA_FLAGS_BGR); no alpha rule
+ *              4              R8G8B8A8_UNORM    B, G, R, A -> R, G, B, A
+ *              4              B8G8R8A8_UNORM    the word (TGA_FLAGS_BGR)
+ *              1, palette     R8G8B8A8_UNORM    palette[index]; `palette` = 256 words in host memory, read before the call returns
+ *                             or B8G8R8X8_UNORM (ReadPalette's table: zero words outside the file's colour map); no alpha rule
+ *            The alpha rule (2 and 4 bytes): where every alpha is zero and DXTEX_TGA_ALLOW_ALL_ZERO_ALPHA is not set, every alpha is made
+ *            opaque (255; bit 15). The answer is 1 if the image is opaque - made so, found so, or 24 bits into R8G8B8A8 - else 0: the
+ *            reference's S_FALSE / S_OK. It is independent of the order in which the device visits the texels.
+ *   pack     level 0 of src -> the stream the writer emits, top-down and left-to-right (SaveToTGAMemory, :2249-2330): R8G8B8A8_UNORM[_SRGB]
+ *            with R and B swapped (4 bytes), B8G8R8A8_UNORM[_SRGB] (4), B8G8R8X8_UNORM[_SRGB] without X (3), R8_UNORM / A8_UNORM (1),
+ *            B5G5R5A1_UNORM (2)
+ * HRESULTs, in this order: E_POINTER for a null stream, image, pixels or (host form of unpack) answer; NOT_SUPPORTED for a format /
+ * bytesPerTexel / palette combination outside the tables above; E_INVALIDARG for a width or height of zero or above 65535, a row pitch
+ * smaller than the row, or a stream that overlaps the pixels; E_FAIL for texelBytes != width * height * bytesPerTexel. */
+#define DXTEX_TGA_RIGHT_TO_LEFT          0x1u
+#define DXTEX_TGA_TOP_DOWN               0x2u
+#define DXTEX_TGA_ALLOW_ALL_ZERO_ALPHA   0x4u
+/* host pointers, through the context's staging; returns when the destination (and *opaque) has landed */
+dxtex_hresult dxtex_tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
+                               const dxtex_image* dst, uint32_t* opaque);
+dxtex_hresult dxtex_tga_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes);
+/* device pointers (the palette stays a host pointer): asynchronous on the context's stream. opaqueDevice: a dword of device memory that
+ * receives the answer in stream order, or NULL. The stream may start at any byte; one that starts on a multiple of 4 takes the wide route. */
+dxtex_hresult dxtex_tga_unpack_device(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
+                                      const dxtex_image* dst, uint32_t* opaqueDevice);
+dxtex_hresult dxtex_tga_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
