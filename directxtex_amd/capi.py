@@ -144,6 +144,10 @@ _SIGS = {
     "dxtex_tga_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, _P(Image), ctypes.c_void_p]),
     "dxtex_tga_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_tga_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_dds_unpack": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t]),
+    "dxtex_dds_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t]),
+    "dxtex_dds_pack24": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_dds_pack24_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -175,6 +179,7 @@ _SIGS = {
     "dxtex_copy_rows_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t]),
     "dxtex_memcpy_h2d_async": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_memcpy_d2h_async": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_memcpy_rows_d2h_async": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t]),
     "dxtex_host_alloc": (ctypes.c_int32, [_ctx_p, ctypes.c_size_t, _P(ctypes.c_void_p)]),
     "dxtex_host_free": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p]),
     "dxtex_alpha_all_opaque_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_size_t, _P(ctypes.c_int)]),
@@ -798,6 +803,51 @@ class Context:
     def tga_pack_device(self, src, bytes_per_texel, texels_ptr, texel_bytes):
         """dxtex_tga_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
         self._check(self._lib.dxtex_tga_pack_device(self._h, ctypes.byref(src), bytes_per_texel, texels_ptr, texel_bytes), "tga_pack_device")
+
+    # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
+    @staticmethod
+    def _dds_arrays(images, offsets, pitches):
+        n = len(images)
+        assert len(offsets) == n and len(pitches) == n
+        return (Image * max(n, 1))(*images), (ctypes.c_size_t * max(n, 1))(*offsets), (ctypes.c_size_t * max(n, 1))(*pitches), n
+
+    def dds_unpack(self, payload, op, images, offsets, pitches, opaque=False, palette=None):
+        """dxtex_dds_unpack: the file's payload (host bytes) -> one numpy uint8 buffer per image. images = [(width, height, fmt, row_pitch or
+        None)]; offsets / pitches = where each image's rows lie in the payload. op = DDS_ROW_*."""
+        payload = np.ascontiguousarray(payload, np.uint8)
+        pal = self._tga_palette(palette)
+        outs, ims = [], []
+        for (w, h, fmt, rp) in images:
+            mrp, msp = compute_pitch(fmt, w, h)
+            rows = msp // mrp if mrp else 0
+            rp = mrp if rp is None else rp
+            outs.append(np.zeros(rp * rows, np.uint8))
+            ims.append(Image(w, h, fmt, rp, rp * rows, outs[-1].ctypes.data))
+        arr, off, pit, n = self._dds_arrays(ims, offsets, pitches)
+        self._check(self._lib.dxtex_dds_unpack(self._h, payload.ctypes.data, payload.nbytes, op, int(bool(opaque)), None if pal is None else pal.ctypes.data,
+                                               arr, off, pit, n), "dds_unpack")
+        return outs
+
+    def dds_unpack_device(self, payload_ptr, payload_bytes, op, dsts, offsets, pitches, opaque=False, palette=None):
+        """dxtex_dds_unpack_device: the payload at a device pointer -> the device Images `dsts` (device_image), asynchronous on the stream."""
+        pal = self._tga_palette(palette)
+        arr, off, pit, n = self._dds_arrays(dsts, offsets, pitches)
+        self._check(self._lib.dxtex_dds_unpack_device(self._h, payload_ptr, payload_bytes, op, int(bool(opaque)), None if pal is None else pal.ctypes.data,
+                                                      arr, off, pit, n), "dds_unpack_device")
+
+    def dds_pack24(self, images, offsets, pitches, out_bytes):
+        """dxtex_dds_pack24: B8G8R8X8 images [(pixels, width, height, row_pitch or None)] -> out_bytes of 24-bit rows (zero where no row lies)."""
+        keep = [np.ascontiguousarray(px) for (px, _, _, _) in images]
+        ims = [_host_image(k, w, h, 88, rp) for k, (_, w, h, rp) in zip(keep, images)]
+        arr, off, pit, n = self._dds_arrays(ims, offsets, pitches)
+        out = np.zeros(out_bytes, np.uint8)
+        self._check(self._lib.dxtex_dds_pack24(self._h, arr, off, pit, n, out.ctypes.data, out.nbytes), "dds_pack24")
+        return out
+
+    def dds_pack24_device(self, srcs, offsets, pitches, out_ptr, out_bytes):
+        """dxtex_dds_pack24_device: the device Images `srcs` -> 24-bit rows at a device pointer, asynchronous on the stream."""
+        arr, off, pit, n = self._dds_arrays(srcs, offsets, pitches)
+        self._check(self._lib.dxtex_dds_pack24_device(self._h, arr, off, pit, n, out_ptr, out_bytes), "dds_pack24_device")
 
     def generate_mips3d(self, volume, width, height, depth, fmt, nlevels, filter_flags):
         """DirectX::GenerateMipMaps3D: `volume` = the base slices (tight, consecutive). Returns one uint8 buffer per level."""

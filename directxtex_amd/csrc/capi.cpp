@@ -5,6 +5,7 @@
 #include "dxtex_formats.h"
 #include "dxtex_kernels.h"
 #include "dxtex_tga.h"
+#include "dxtex_dds.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -1666,6 +1667,142 @@ dxtex_hresult dxtex_tga_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t by
 
 namespace
 {
+static_assert(DXTEX_DDS_ROW_COPY == ROW_COPY && DXTEX_DDS_ROW_888 == ROW_888 && DXTEX_DDS_ROW_P8 == ROW_P8 && DXTEX_DDS_ROW_WUV10 == ROW_WUV10 && DXTEX_DDS_ROW_OPS == ROW_OPS,
+              "dxtex_dds.h's ops are the public ones");
+
+// The checks of the DDS four, in the order include/dxtex_amd.h states; fills `jobs` with one descriptor per image. unpack: `images` are the
+// destinations, bytesPerTexel the op's file texel (1 for ROW_COPY, whose widths count bytes); pack24: the B8G8R8X8 sources, 3.
+dxtex_hresult check_dds(dxtex_ctx* ctx, const void* file, size_t fileBytes, bool unpack, uint32_t op, const uint32_t* palette, const dxtex_image* images,
+                        const size_t* offsets, const size_t* pitches, size_t count, std::vector<DdsImage>* jobs)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!file) return fail(ctx, DXTEX_E_POINTER, unpack ? "null payload" : "null output");
+    if (!images || !offsets || !pitches) return fail(ctx, DXTEX_E_POINTER, "null images, offsets or pitches");
+    for (size_t i = 0; i < count; ++i)
+        if (!images[i].pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
+    if (unpack && op >= uint32_t(ROW_OPS)) return fail(ctx, DXTEX_E_INVALIDARG, "unknown DDS row op");
+    if (unpack && dds_has_palette(int(op)) != (palette != nullptr)) return fail(ctx, DXTEX_E_INVALIDARG, palette ? "this DDS row op takes no palette" : "this DDS row op needs a palette");
+    const int format = images[0].format;
+    const int target = unpack ? dds_target(int(op), format) : DDS_TO_8888;
+    size_t probeRow = 0, probeSlice = 0;
+    if (unpack ? (target < 0 || (op == ROW_SWIZZLE && target == DDS_TO_BYTES) || (op == ROW_COPY && dxtex_compute_pitch(format, 1, 1, &probeRow, &probeSlice) != DXTEX_S_OK))
+               : format != FMT_B8G8R8X8_UNORM)
+        return fail(ctx, DXTEX_E_NOT_SUPPORTED, unpack ? "no DDS reader case for this row op and destination format" : "the 24-bit DDS rows are written from B8G8R8X8_UNORM");
+    const uint32_t fileTexel = !unpack ? 3u : op == ROW_COPY ? 1u : dds_file_bytes(int(op));
+    const size_t imageTexel = !unpack ? 4u : dds_image_bytes(target);
+    jobs->resize(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_image& im = images[i];
+        if (im.format != format) return fail(ctx, DXTEX_E_INVALIDARG, "the images of one call share a format");
+        // texels per row fit the kernels' 32-bit x with four to a lane; a copy works in bytes, and its own limit is on rowBytes below
+        if ((!(unpack && op == ROW_COPY) && im.width > 0x3FFFFFFFull) || im.height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+        const size_t words = (unpack && target == DDS_TO_YUY2) ? (im.width + 1) / 2 : im.width;          // a YUY2 word holds two texels
+        size_t rowBytes = words * imageTexel, rows = im.height;
+        if (unpack && op == ROW_COPY)
+        {
+            // in bytes: the format's own rows (block rows of a compressed image, every plane's rows of a planar one)
+            size_t slice = 0;
+            if (dxtex_compute_pitch(format, im.width, im.height, &rowBytes, &slice) != DXTEX_S_OK || rowBytes > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+            rows = (im.width && im.height && rowBytes) ? slice / rowBytes : 0;
+        }
+        if (!im.width || !im.height) { (*jobs)[i] = DdsImage{}; continue; }
+        if (rows > 0xFFFFFFFFull || im.rowPitch < rowBytes || im.rowPitch > (SIZE_MAX - rowBytes) / rows) return fail(ctx, DXTEX_E_INVALIDARG, "the image is too small for its rows: rowPitch is smaller than the row, or rowPitch x rows overflows");
+        DdsImage& j = (*jobs)[i];
+        j = DdsImage{ offsets[i], pitches[i], im.pixels, im.rowPitch, uint32_t(unpack && op == ROW_COPY ? rowBytes : words), uint32_t(rows) };
+        if (!dds_image_in_payload(j, fileTexel, fileBytes)) return fail(ctx, DXTEX_E_INVALIDARG, unpack ? "an image's rows reach past the payload" : "an image's rows reach past the output");
+        // the two sides apart: the kernels read one while they write the other
+        const uintptr_t f0 = reinterpret_cast<uintptr_t>(file) + j.fileOffset, f1 = f0 + (rows - 1) * j.filePitch + size_t(j.width) * fileTexel;
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(im.pixels), i1 = i0 + (rows - 1) * im.rowPitch + rowBytes;
+        if (f0 < i1 && i0 < f1) return fail(ctx, DXTEX_E_INVALIDARG, "payload and image pixels overlap");
+    }
+    return DXTEX_S_OK;
+}
+
+// bytes of an image's rows in memory, first to last
+size_t dds_span(const DdsImage& j, size_t rowBytes, bool fileSide) { return j.rows ? (j.rows - 1) * size_t(fileSide ? j.filePitch : j.pitch) + rowBytes : 0; }
+
+// rows of rowBytes between host and device through their own pitches, counted like every other transfer
+hipError_t counted_copy_rows(dxtex_ctx* ctx, void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t rowBytes, size_t rows, hipMemcpyKind kind)
+{
+    if (!rows || !rowBytes) return hipSuccess;
+    if (rows == 1 || (dstPitch == rowBytes && srcPitch == rowBytes)) return counted_copy(ctx, dst, src, rowBytes * rows, kind, ctx->stream);
+    if (kind == hipMemcpyHostToDevice) ctx->h2dBytes += rowBytes * rows; else ctx->d2hBytes += rowBytes * rows;
+    return hipMemcpy2DAsync(dst, dstPitch, src, srcPitch, rowBytes, rows, kind, ctx->stream);
+}
+} // namespace
+
+dxtex_hresult dxtex_dds_unpack_device(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
+                                      const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count)
+{
+    std::vector<DdsImage> jobs;
+    const dxtex_hresult hr = check_dds(ctx, payload, payloadBytes, true, op, palette, dsts, srcOffsets, srcRowPitches, count, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_dds_unpack(static_cast<const uint8_t*>(payload), payloadBytes, int(op), dsts[0].format, opaque != 0, palette,
+                                                                       jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_dds_unpack(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
+                               const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count)
+{
+    std::vector<DdsImage> jobs;
+    dxtex_hresult hr = check_dds(ctx, payload, payloadBytes, true, op, palette, dsts, srcOffsets, srcRowPitches, count, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    // the payload goes up as it is; each image gets its rows' span of the output staging and comes down through its own pitch
+    const size_t imageTexel = dds_image_bytes(dds_target(int(op), dsts[0].format));
+    std::vector<size_t> spans(count), rowBytes(count);
+    for (size_t i = 0; i < count; ++i) { rowBytes[i] = op == ROW_COPY ? jobs[i].width : jobs[i].width * imageTexel; spans[i] = dds_span(jobs[i], rowBytes[i], false); }
+    const Arena arena(spans.data(), count);
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, payloadBytes); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, arena.total); if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, payload, payloadBytes, hipMemcpyHostToDevice, ctx->stream));
+    for (size_t i = 0; i < count; ++i) jobs[i].pixels = ctx->stageOut.u8() + arena.at[i];
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_dds_unpack(ctx->stageIn.u8(), payloadBytes, int(op), dsts[0].format, opaque != 0, palette, jobs.data(), jobs.size(),
+                                                                     ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    for (size_t i = 0; i < count; ++i)
+        HIP_TRY(ctx, counted_copy_rows(ctx, dsts[i].pixels, dsts[i].rowPitch, jobs[i].pixels, jobs[i].pitch, rowBytes[i], jobs[i].rows, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_dds_pack24_device(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes)
+{
+    std::vector<DdsImage> jobs;
+    const dxtex_hresult hr = check_dds(ctx, out, outBytes, false, 0, nullptr, srcs, dstOffsets, dstRowPitches, count, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_dds_pack24(jobs.data(), jobs.size(), static_cast<uint8_t*>(out), outBytes, ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_dds_pack24(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes)
+{
+    std::vector<DdsImage> jobs;
+    dxtex_hresult hr = check_dds(ctx, out, outBytes, false, 0, nullptr, srcs, dstOffsets, dstRowPitches, count, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    std::vector<size_t> spans(count);
+    for (size_t i = 0; i < count; ++i) spans[i] = dds_span(jobs[i], size_t(jobs[i].width) * 4u, false);
+    const Arena arena(spans.data(), count);
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, arena.total); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, outBytes); if (hr != DXTEX_S_OK) return hr;
+    for (size_t i = 0; i < count; ++i)
+    {
+        HIP_TRY(ctx, counted_copy_rows(ctx, ctx->stageIn.u8() + arena.at[i], jobs[i].pitch, srcs[i].pixels, srcs[i].rowPitch, size_t(jobs[i].width) * 4u, jobs[i].rows, hipMemcpyHostToDevice));
+        jobs[i].pixels = ctx->stageIn.u8() + arena.at[i];
+    }
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_dds_pack24(jobs.data(), jobs.size(), ctx->stageOut.u8(), outBytes, ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    for (size_t i = 0; i < count; ++i)
+        HIP_TRY(ctx, counted_copy_rows(ctx, static_cast<uint8_t*>(out) + jobs[i].fileOffset, jobs[i].filePitch, ctx->stageOut.u8() + jobs[i].fileOffset, jobs[i].filePitch,
+                                       size_t(jobs[i].width) * 3u, jobs[i].rows, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+namespace
+{
 // PremultiplyAlpha's checks (DirectXTexPMAlpha.cpp:214-231)
 dxtex_hresult check_pmalpha(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
 {
@@ -2407,6 +2544,15 @@ dxtex_hresult dxtex_memcpy_d2h_async(dxtex_ctx* ctx, void* dst, const void* src,
     if (!ctx) return DXTEX_E_POINTER;
     ScopedDevice sd(ctx->device);
     HIP_TRY(ctx, counted_copy(ctx, dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return DXTEX_S_OK;
+}
+dxtex_hresult dxtex_memcpy_rows_d2h_async(dxtex_ctx* ctx, void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t rowBytes, size_t rows)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!dst || !src) return fail(ctx, DXTEX_E_POINTER, "null buffer");
+    if (rowBytes > dstPitch || rowBytes > srcPitch) return fail(ctx, DXTEX_E_INVALIDARG, "row is wider than a pitch");
+    ScopedDevice sd(ctx->device);
+    HIP_TRY(ctx, counted_copy_rows(ctx, dst, dstPitch, src, srcPitch, rowBytes, rows, hipMemcpyDeviceToHost));
     return DXTEX_S_OK;
 }
 dxtex_hresult dxtex_host_alloc(dxtex_ctx* ctx, size_t bytes, void** out)

@@ -1,0 +1,235 @@
+// DDS texels on the way into an image, per texel: shared by the GPU kernels (dds.hip), the host codec (host/DirectXTexAMD_DDS.cpp, a plain
+// C++ build) and the host check (tests/cpp/dds_check.cpp). Integer code: bytes move, nothing rounds.
+//
+// A legacy (Direct3D 9) file's rows reach the image through one of the row conversions of the reference's CopyImage
+// (DirectXTexDDS.cpp:1518-1808; ExpandScanline, SwizzleScanline and CopyScanline of DirectXTexConvert.cpp behind it). Which one is the
+// reader's choice from the header (PickRowOp in the host codec); what it does to one texel is here. A file texel is its 1, 2, 3 or 4 bytes
+// as a little-endian word.
+//   op            file bytes  result                      texel
+//   ROW_COPY      any         any                         the bytes; with the opaque flag the format's alpha is forced (dds_opaque_of)
+//   ROW_SWIZZLE   4           8888 family                 red and blue trade places
+//                             10:10:10:2 family           the two outer 10-bit fields trade places
+//                             YUY2                        UYVY -> YUY2: the bytes of each 16-bit half trade places
+//   ROW_565       2           R8G8B8A8_UNORM              sic: green's top two bits land in red's byte, green's low bits stay zero
+//   ROW_5551      2           R8G8B8A8_UNORM              bit 15 -> 0 or 255
+//   ROW_4444      2           R8G8B8A8_UNORM              B4G4R4A4: nibbles * 17
+//   ROW_ABGR4     2           R8G8B8A8_UNORM              A4B4G4R4
+//   ROW_888       3           R8G8B8A8_UNORM              B, G, R -> R, G, B, 255
+//   ROW_332       1           R8G8B8A8_UNORM, B5G6R5      bit patterns repeated
+//   ROW_8332      2           R8G8B8A8_UNORM              A8R3G3B2
+//   ROW_P8        1           R8G8B8A8_UNORM              palette[index]
+//   ROW_A8P8      2           R8G8B8A8_UNORM              palette[index] | alpha << 24 (OR-ed onto the entry's)
+//   ROW_44        1           R8G8B8A8_UNORM, B4G4R4A4    A4L4
+//   ROW_L8        1           R8G8B8A8_UNORM              L, L, L, 255
+//   ROW_L16       2           R16G16B16A16_UNORM          L, L, L, 65535
+//   ROW_A8L8      2           R8G8B8A8_UNORM              L, L, L, A
+//   ROW_L6V5U5    2           R8G8B8A8_UNORM              (L, U, V, 255): the signed fields rebased through flip()
+//   ROW_L8U8V8    4           R8G8B8A8_UNORM              X8L8V8U8 -> (L, U, V, 255)
+//   ROW_WUV10     4           R10G10B10A2_UNORM           A2W10V10U10: three signed fields rebased, alpha kept
+// Every other (op, result format) pair is refused (dds_target() < 0): the reader answers E_FAIL for it. The opaque flag (CV_NOALPHA) sets
+// the alpha of the ops that carry one; the others are opaque by construction.
+#pragma once
+#if defined(__HIPCC__) || defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define DXTEX_DDS_FN __host__ __device__ inline
+#else
+#define DXTEX_DDS_FN inline
+#endif
+#include <stdint.h>
+
+namespace dxtex
+{
+// stable values: DXTEX_DDS_ROW_* of include/dxtex_amd.h
+enum DdsRowOp : int { ROW_COPY = 0, ROW_SWIZZLE, ROW_565, ROW_5551, ROW_4444, ROW_ABGR4, ROW_888, ROW_332, ROW_8332, ROW_P8, ROW_A8P8, ROW_44, ROW_L8, ROW_L16,
+                      ROW_A8L8, ROW_L6V5U5, ROW_L8U8V8, ROW_WUV10, ROW_FAIL, ROW_OPS = ROW_FAIL };
+
+// what the result format makes of an op. DDS_TO_BYTES: the texel passes unchanged (ROW_COPY; ROW_SWIZZLE into a format without a swizzle).
+enum DdsTarget : int { DDS_TO_BYTES = 0, DDS_TO_8888, DDS_TO_1010102, DDS_TO_YUY2, DDS_TO_565, DDS_TO_4444, DDS_TO_16161616 };
+
+// DXGI_FORMAT values this header names (DirectXTex.h / dxgiformat.h; 116, 117, 189 and 191 are the console and 4:4:4:4 additions)
+enum : int
+{
+    DDS_F_R32G32B32A32_TYPELESS = 1, DDS_F_R32G32B32A32_FLOAT = 2, DDS_F_R32G32B32A32_UINT = 3, DDS_F_R32G32B32A32_SINT = 4,
+    DDS_F_R16G16B16A16_TYPELESS = 9, DDS_F_R16G16B16A16_FLOAT = 10, DDS_F_R16G16B16A16_UNORM = 11, DDS_F_R16G16B16A16_UINT = 12,
+    DDS_F_R16G16B16A16_SNORM = 13, DDS_F_R16G16B16A16_SINT = 14,
+    DDS_F_R10G10B10A2_TYPELESS = 23, DDS_F_R10G10B10A2_UNORM = 24, DDS_F_R10G10B10A2_UINT = 25,
+    DDS_F_R8G8B8A8_TYPELESS = 27, DDS_F_R8G8B8A8_UNORM = 28, DDS_F_R8G8B8A8_UNORM_SRGB = 29, DDS_F_R8G8B8A8_UINT = 30, DDS_F_R8G8B8A8_SNORM = 31,
+    DDS_F_R8G8B8A8_SINT = 32, DDS_F_A8_UNORM = 65, DDS_F_B5G6R5_UNORM = 85, DDS_F_B5G5R5A1_UNORM = 86, DDS_F_B8G8R8A8_UNORM = 87,
+    DDS_F_B8G8R8X8_UNORM = 88, DDS_F_R10G10B10_XR_BIAS_A2_UNORM = 89, DDS_F_B8G8R8A8_TYPELESS = 90, DDS_F_B8G8R8A8_UNORM_SRGB = 91,
+    DDS_F_B8G8R8X8_TYPELESS = 92, DDS_F_B8G8R8X8_UNORM_SRGB = 93, DDS_F_AYUV = 100, DDS_F_Y410 = 101, DDS_F_Y416 = 102, DDS_F_YUY2 = 107,
+    DDS_F_B4G4R4A4_UNORM = 115, DDS_F_R10G10B10_7E3_A2_FLOAT = 116, DDS_F_R10G10B10_6E4_A2_FLOAT = 117, DDS_F_R10G10B10_SNORM_A2_UNORM = 189,
+    DDS_F_A4B4G4R4_UNORM = 191,
+};
+
+// bytes of a file texel per op; 0 for ROW_COPY (which works in bytes) and anything that is no op
+DXTEX_DDS_FN constexpr uint32_t dds_file_bytes(int op)
+{
+    return (op == ROW_332 || op == ROW_P8 || op == ROW_44 || op == ROW_L8) ? 1u
+         : (op == ROW_565 || op == ROW_5551 || op == ROW_4444 || op == ROW_ABGR4 || op == ROW_8332 || op == ROW_A8P8 || op == ROW_L16 || op == ROW_A8L8 || op == ROW_L6V5U5) ? 2u
+         : op == ROW_888 ? 3u
+         : (op == ROW_SWIZZLE || op == ROW_L8U8V8 || op == ROW_WUV10) ? 4u : 0u;
+}
+// bytes of an image texel per target; 0 for DDS_TO_BYTES
+DXTEX_DDS_FN constexpr uint32_t dds_image_bytes(int target)
+{
+    return (target == DDS_TO_8888 || target == DDS_TO_1010102 || target == DDS_TO_YUY2) ? 4u : (target == DDS_TO_565 || target == DDS_TO_4444) ? 2u
+         : target == DDS_TO_16161616 ? 8u : 0u;
+}
+DXTEX_DDS_FN constexpr bool dds_has_palette(int op) { return op == ROW_P8 || op == ROW_A8P8; }
+
+DXTEX_DDS_FN constexpr bool dds_is_8888(int f)
+{
+    return f == DDS_F_R8G8B8A8_TYPELESS || f == DDS_F_R8G8B8A8_UNORM || f == DDS_F_R8G8B8A8_UNORM_SRGB || f == DDS_F_B8G8R8A8_UNORM || f == DDS_F_B8G8R8X8_UNORM
+        || f == DDS_F_B8G8R8A8_TYPELESS || f == DDS_F_B8G8R8A8_UNORM_SRGB || f == DDS_F_B8G8R8X8_TYPELESS || f == DDS_F_B8G8R8X8_UNORM_SRGB;
+}
+DXTEX_DDS_FN constexpr bool dds_is_1010102(int f)
+{
+    return f == DDS_F_R10G10B10A2_TYPELESS || f == DDS_F_R10G10B10A2_UNORM || f == DDS_F_R10G10B10A2_UINT || f == DDS_F_R10G10B10_XR_BIAS_A2_UNORM
+        || f == DDS_F_R10G10B10_SNORM_A2_UNORM;
+}
+
+// The refusal table: the target of (op, result format), or -1 where the reader answers E_FAIL (every expansion into anything but
+// R8G8B8A8_UNORM, except 332 into B5G6R5, 44 into B4G4R4A4, L16 into R16G16B16A16_UNORM and WUV10 into R10G10B10A2_UNORM; ROW_FAIL).
+DXTEX_DDS_FN constexpr int dds_target(int op, int format)
+{
+    return op == ROW_COPY ? DDS_TO_BYTES
+         : op == ROW_SWIZZLE ? (dds_is_1010102(format) ? DDS_TO_1010102 : dds_is_8888(format) ? DDS_TO_8888 : format == DDS_F_YUY2 ? DDS_TO_YUY2 : DDS_TO_BYTES)
+         : op == ROW_L16 ? (format == DDS_F_R16G16B16A16_UNORM ? DDS_TO_16161616 : -1)
+         : op == ROW_WUV10 ? (format == DDS_F_R10G10B10A2_UNORM ? DDS_TO_1010102 : -1)
+         : (op < 0 || op >= ROW_OPS) ? -1
+         : format == DDS_F_R8G8B8A8_UNORM ? DDS_TO_8888
+         : (op == ROW_332 && format == DDS_F_B5G6R5_UNORM) ? DDS_TO_565
+         : (op == ROW_44 && format == DDS_F_B4G4R4A4_UNORM) ? DDS_TO_4444 : -1;
+}
+
+// an n-bit channel widened to `to` bits by repeating its bit pattern (what all the legacy expansions do)
+DXTEX_DDS_FN constexpr uint32_t dds_widen(uint32_t v, unsigned n, unsigned to)
+{
+    uint32_t out = 0; unsigned have = 0;
+    while (have < to) { out = (out << n) | v; have += n; }
+    return out >> (have - to);
+}
+DXTEX_DDS_FN constexpr uint32_t dds_rgba8(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return r | (g << 8) | (b << 16) | (a << 24); }
+DXTEX_DDS_FN constexpr uint32_t dds_flip(uint32_t v, unsigned bits) { return v ^ (1u << (bits - 1)); }        // two's complement -> offset binary
+
+// One file texel `t` (its bytes as a word, the rest zero) as the image stores it: the low dds_image_bytes(target) bytes of the result.
+// target = dds_target(op, format) >= 0, never DDS_TO_BYTES; palette is read by ROW_P8 and ROW_A8P8 only.
+DXTEX_DDS_FN uint64_t dds_unpack_texel(uint32_t t, int op, int target, bool opaque, const uint32_t* palette)
+{
+    switch (op)
+    {
+    case ROW_SWIZZLE:           // SwizzleScanline with TEXP_SCANLINE_LEGACY (DirectXTexConvert.cpp:440-605)
+        if (target == DDS_TO_1010102) return ((t >> 20) & 0x3ffu) | ((t & 0x3ffu) << 20) | (t & 0x000ffc00u) | (opaque ? 0xC0000000u : (t & 0xC0000000u));
+        if (target == DDS_TO_8888) return ((t >> 16) & 0xffu) | ((t & 0xffu) << 16) | (t & 0x0000ff00u) | (opaque ? 0xff000000u : (t & 0xff000000u));
+        if (target == DDS_TO_YUY2) return ((t & 0x00ff00ffu) << 8) | ((t & 0xff00ff00u) >> 8);
+        return t;
+    case ROW_565:
+    {
+        // sic (ExpandScanline, DirectXTexConvert.cpp:643): the two bits that should fill green's low end are shifted into bits 4-5 of the
+        // word - the red byte - so green keeps zeros there and red picks them up
+        const uint32_t g6 = (t >> 5) & 0x3f;
+        return dds_rgba8(dds_widen((t >> 11) & 0x1f, 5, 8) | ((g6 >> 4) << 4), g6 << 2, dds_widen(t & 0x1f, 5, 8), 0xff);
+    }
+    case ROW_5551:
+        return dds_rgba8(dds_widen((t >> 10) & 0x1f, 5, 8), dds_widen((t >> 5) & 0x1f, 5, 8), dds_widen(t & 0x1f, 5, 8), (opaque || (t & 0x8000)) ? 0xff : 0);
+    case ROW_4444: case ROW_ABGR4:
+    {
+        // nibbles from the top: B4G4R4A4 = A R G B, A4B4G4R4 = R G B A
+        const uint32_t n3 = (t >> 12) & 0xf, n2 = (t >> 8) & 0xf, n1 = (t >> 4) & 0xf, n0 = t & 0xf;
+        return op == ROW_4444 ? dds_rgba8(n2 * 17, n1 * 17, n0 * 17, opaque ? 0xff : n3 * 17) : dds_rgba8(n3 * 17, n2 * 17, n1 * 17, opaque ? 0xff : n0 * 17);
+    }
+    case ROW_888:                // 24 bpp files are B, G, R in memory
+        return dds_rgba8((t >> 16) & 0xff, (t >> 8) & 0xff, t & 0xff, 0xff);
+    case ROW_332:
+        if (target == DDS_TO_565) return (dds_widen((t >> 5) & 7, 3, 5) << 11) | (dds_widen((t >> 2) & 7, 3, 6) << 5) | dds_widen(t & 3, 2, 5);
+        return dds_rgba8(dds_widen((t >> 5) & 7, 3, 8), dds_widen((t >> 2) & 7, 3, 8), dds_widen(t & 3, 2, 8), 0xff);
+    case ROW_8332:
+        return dds_rgba8(dds_widen((t >> 5) & 7, 3, 8), dds_widen((t >> 2) & 7, 3, 8), dds_widen(t & 3, 2, 8), opaque ? 0xff : ((t >> 8) & 0xff));
+    case ROW_P8:
+        return palette[t & 0xff];
+    case ROW_A8P8:               // the texel's alpha is OR-ed onto the palette entry's
+        return palette[t & 0xff] | (opaque ? 0xff000000u : (((t >> 8) & 0xffu) << 24));
+    case ROW_44:
+    {
+        const uint32_t l = t & 0xfu, a = (t >> 4) & 0xfu;
+        if (target == DDS_TO_4444) return l | (l << 4) | (l << 8) | (opaque ? 0xf000u : (a << 12));
+        return dds_rgba8(l * 17, l * 17, l * 17, opaque ? 0xff : a * 17u);
+    }
+    case ROW_L8:
+    {
+        const uint32_t l = t & 0xff;
+        return dds_rgba8(l, l, l, 0xff);
+    }
+    case ROW_L16:
+    {
+        const uint64_t l = t & 0xffffu;
+        return l | (l << 16) | (l << 32) | (uint64_t(0xffffu) << 48);
+    }
+    case ROW_A8L8:
+    {
+        const uint32_t l = t & 0xff;
+        return dds_rgba8(l, l, l, opaque ? 0xff : ((t >> 8) & 0xff));
+    }
+    case ROW_L6V5U5:             // unsigned 6-bit luminance, signed 5-bit v and u -> (L, U, V, 1) as unsigned bytes
+        return dds_rgba8(dds_widen((t >> 10) & 0x3f, 6, 8), dds_widen(dds_flip(t & 0x1f, 5), 5, 8), dds_widen(dds_flip((t >> 5) & 0x1f, 5), 5, 8), 0xff);
+    case ROW_L8U8V8:             // X8L8V8U8: (L, U, V, 1) with the signed bytes rebased to unsigned
+        return dds_rgba8((t >> 16) & 0xff, dds_flip(t & 0xff, 8), dds_flip((t >> 8) & 0xff, 8), 0xff);
+    case ROW_WUV10:              // A2W10V10U10: three signed 10-bit fields rebased to unsigned, alpha kept
+        return dds_flip(t & 0x3ff, 10) | (dds_flip((t >> 10) & 0x3ff, 10) << 10) | (dds_flip((t >> 20) & 0x3ff, 10) << 20) | (opaque ? 0xC0000000u : (t & 0xC0000000u));
+    default:
+        return t;
+    }
+}
+
+// CopyScanline with TEXP_SCANLINE_SETALPHA (DirectXTexConvert.cpp:207-430), the forced-opaque alpha of ROW_COPY: a texel of `texelBytes`
+// bytes whose LAST min(4, texelBytes) bytes, as a word v, become (v & keep) | set. texelBytes = 0: the format has no alpha the reader
+// forces, and its bytes pass unchanged.
+struct DdsOpaque { uint32_t texelBytes, keep, set; };
+DXTEX_DDS_FN constexpr DdsOpaque dds_opaque_of(int f)
+{
+    return (f == DDS_F_R32G32B32A32_TYPELESS || f == DDS_F_R32G32B32A32_FLOAT || f == DDS_F_R32G32B32A32_UINT || f == DDS_F_R32G32B32A32_SINT)
+             ? DdsOpaque{ 16u, 0u, f == DDS_F_R32G32B32A32_FLOAT ? 0x3f800000u : f == DDS_F_R32G32B32A32_SINT ? 0x7fffffffu : 0xffffffffu }
+         : (f == DDS_F_R16G16B16A16_TYPELESS || f == DDS_F_R16G16B16A16_FLOAT || f == DDS_F_R16G16B16A16_UNORM || f == DDS_F_R16G16B16A16_UINT
+            || f == DDS_F_R16G16B16A16_SNORM || f == DDS_F_R16G16B16A16_SINT || f == DDS_F_Y416)
+             ? DdsOpaque{ 8u, 0x0000ffffu, (f == DDS_F_R16G16B16A16_FLOAT ? 0x3c00u : (f == DDS_F_R16G16B16A16_SNORM || f == DDS_F_R16G16B16A16_SINT) ? 0x7fffu : 0xffffu) << 16 }
+         : (f == DDS_F_R10G10B10A2_TYPELESS || f == DDS_F_R10G10B10A2_UNORM || f == DDS_F_R10G10B10A2_UINT || f == DDS_F_R10G10B10_XR_BIAS_A2_UNORM
+            || f == DDS_F_Y410 || f == DDS_F_R10G10B10_7E3_A2_FLOAT || f == DDS_F_R10G10B10_6E4_A2_FLOAT || f == DDS_F_R10G10B10_SNORM_A2_UNORM)
+             ? DdsOpaque{ 4u, 0xffffffffu, 0xC0000000u }
+         : (f == DDS_F_R8G8B8A8_TYPELESS || f == DDS_F_R8G8B8A8_UNORM || f == DDS_F_R8G8B8A8_UNORM_SRGB || f == DDS_F_R8G8B8A8_UINT || f == DDS_F_R8G8B8A8_SNORM
+            || f == DDS_F_R8G8B8A8_SINT || f == DDS_F_B8G8R8A8_UNORM || f == DDS_F_B8G8R8A8_TYPELESS || f == DDS_F_B8G8R8A8_UNORM_SRGB || f == DDS_F_AYUV)
+             ? DdsOpaque{ 4u, 0x00ffffffu, (f == DDS_F_R8G8B8A8_SNORM || f == DDS_F_R8G8B8A8_SINT) ? 0x7f000000u : 0xff000000u }
+         : (f == DDS_F_B5G5R5A1_UNORM || f == DDS_F_B4G4R4A4_UNORM || f == DDS_F_A4B4G4R4_UNORM)
+             ? DdsOpaque{ 2u, 0xffffu, f == DDS_F_B4G4R4A4_UNORM ? 0xF000u : f == DDS_F_A4B4G4R4_UNORM ? 0x000Fu : 0x8000u }
+         : f == DDS_F_A8_UNORM ? DdsOpaque{ 1u, 0u, 0xffu }
+         : DdsOpaque{ 0u, 0xffffffffu, 0u };
+}
+// the last word of one texel, forced opaque
+DXTEX_DDS_FN constexpr uint32_t dds_opaque_word(uint32_t v, const DdsOpaque& o) { return (v & o.keep) | o.set; }
+
+// The same on 16 consecutive bytes of whole texels held as four dwords (16 is a multiple of every texelBytes): dword i changes if bit i of
+// `which` is set, to (v & keep) | set with the two masks below.
+struct DdsOpaque16 { uint32_t which, keep, set; };
+DXTEX_DDS_FN constexpr DdsOpaque16 dds_opaque16_of(const DdsOpaque& o)
+{
+    return o.texelBytes == 16u ? DdsOpaque16{ 0x8u, o.keep, o.set } : o.texelBytes == 8u ? DdsOpaque16{ 0xAu, o.keep, o.set }
+         : o.texelBytes == 4u ? DdsOpaque16{ 0xFu, o.keep, o.set } : o.texelBytes == 2u ? DdsOpaque16{ 0xFu, o.keep | (o.keep << 16), o.set | (o.set << 16) }
+         : o.texelBytes == 1u ? DdsOpaque16{ 0xFu, 0u, o.set * 0x01010101u } : DdsOpaque16{ 0u, 0xffffffffu, 0u };
+}
+
+// a file or image texel of 1 to 4 bytes at any address
+DXTEX_DDS_FN uint32_t dds_load(const uint8_t* s, uint32_t bytes)
+{
+    uint32_t t = s[0];
+    if (bytes > 1) t |= uint32_t(s[1]) << 8;
+    if (bytes > 2) t |= uint32_t(s[2]) << 16;
+    if (bytes > 3) t |= uint32_t(s[3]) << 24;
+    return t;
+}
+DXTEX_DDS_FN void dds_store(uint8_t* d, uint64_t t, uint32_t bytes)
+{
+    for (uint32_t i = 0; i < bytes; ++i) d[i] = uint8_t(t >> (8u * i));
+}
+
+// The writer's 24-bit rows (SaveToDDSMemory with DDS_FLAGS_FORCE_24BPP_RGB): a B8G8R8X8 texel loses its fourth byte
+DXTEX_DDS_FN constexpr uint32_t dds_pack24_texel(uint32_t t) { return t & 0x00ffffffu; }
+} // namespace dxtex

@@ -106,6 +106,27 @@ hipError_t launch_tga_unpack(const uint8_t* stream, int kind, uint32_t flags, co
                              hipStream_t stream_, KernelMarks* marks = nullptr);
 hipError_t launch_tga_pack(const ImgView& src, int row, uint32_t bytesPerTexel, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
 
+// DDS texels (dds.hip; the rules are in dxtex_dds.h). One DdsImage per image of the texture: where its rows lie in the file's payload
+// (fileOffset, filePitch) and in device memory (pixels, pitch); `width` texels a row (row BYTES for ROW_COPY, which also carries planar rows
+// and block rows), `rows` rows. kDdsBatchMax of them go into one launch, by value. Unpack: payload (device, as in the file) -> the images;
+// op = a DdsRowOp, format = the result format (dds_target(op, format) picks the variant), opaque = CV_NOALPHA, palette = 256 host words for
+// ROW_P8 / ROW_A8P8 (passed by value: free to go on return). Pack24: B8G8R8X8 images -> `out` at the file's pitches, 3 bytes a texel. Both
+// check every descriptor against the payload's size before they queue anything (hipErrorInvalidValue). Wide / narrow: see dds.hip.
+struct DdsImage { uint64_t fileOffset, filePitch; uint8_t* pixels; uint64_t pitch; uint32_t width, rows; };
+constexpr int kDdsBatchMax = 32;
+// the file side of `im`, rows of width * bytesPerTexel bytes, lies inside payloadBytes (and its rows do not run into each other)
+inline bool dds_image_in_payload(const DdsImage& im, uint32_t bytesPerTexel, size_t payloadBytes)
+{
+    if (!im.width || !im.rows) return true;
+    const uint64_t rowBytes = uint64_t(im.width) * bytesPerTexel;
+    if (im.rows > 1u && (im.filePitch < rowBytes || im.filePitch > (UINT64_MAX - rowBytes) / (im.rows - 1u))) return false;
+    const uint64_t span = uint64_t(im.rows - 1u) * im.filePitch + rowBytes;
+    return im.fileOffset <= payloadBytes && span <= payloadBytes - im.fileOffset;
+}
+hipError_t launch_dds_unpack(const uint8_t* payload, size_t payloadBytes, int op, int format, bool opaque, const uint32_t* palette, const DdsImage* images, size_t count,
+                             hipStream_t stream, KernelMarks* marks = nullptr);
+hipError_t launch_dds_pack24(const DdsImage* images, size_t count, uint8_t* out, size_t outBytes, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

@@ -483,6 +483,17 @@ HRESULT LayoutImages(const TexMetadata& mdata, CP_FLAGS flags, std::unique_ptr<I
 }
 }
 
+HRESULT LayoutScratchImage(const TexMetadata& mdata, CP_FLAGS flags, std::unique_ptr<Image[]>& images, size_t& nimages, size_t& pixelBytes, size_t& mipLevels) noexcept
+{
+    uint64_t total = 0;
+    bool accepted = false;
+    const HRESULT hr = LayoutImages(mdata, flags, images, nimages, total, mipLevels, accepted);
+    if (FAILED(hr)) return hr;
+    if (total > SIZE_MAX) return E_OUTOFMEMORY;
+    pixelBytes = size_t(total);
+    return S_OK;
+}
+
 HRESULT ScratchImage::Initialize(const TexMetadata& mdata, CP_FLAGS flags) noexcept
 {
     std::unique_ptr<Image[]> images;

@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <vector>
 
 struct dxtex_ctx;
 
@@ -417,6 +418,10 @@ private:
     uint8_t* m_memory = nullptr;
 };
 
+// The images ScratchImage::Initialize(mdata, flags) would make, without their memory: `pixels` of each holds its byte offset into the blob
+// of pixelBytes bytes. Same argument checks and HRESULTs; allocates the array only.
+HRESULT LayoutScratchImage(const TexMetadata& mdata, CP_FLAGS flags, std::unique_ptr<Image[]>& images, size_t& nimages, size_t& pixelBytes, size_t& mipLevels) noexcept;
+
 // The steps, resident: same argument meaning and HRESULTs as the (Image*, nimages, metadata) overloads above; all work is queued on the
 // Device's stream and the result may be handed to the next step at once. `src` and the result must belong to `device`.
 HRESULT Compress(Device& device, const DeviceScratchImage& src, DXGI_FORMAT format, TEX_COMPRESS_FLAGS compress, float threshold, DeviceScratchImage& cImages) noexcept;
@@ -431,6 +436,10 @@ HRESULT TransformImage(Device& device, const DeviceScratchImage& src, const TexT
 HRESULT RotateColor(Device& device, const DeviceScratchImage& src, TEX_ROTATE_COLOR rotate, float paperWhiteNits, DeviceScratchImage& result) noexcept;
 // the diagnostics on resident images: image 0 of each side for ComputeMSE and Difference, every image (results[GetImageCount()]) for Analyze / AnalyzeBC
 HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, float& mse, float* mseV, CMSE_FLAGS flags) noexcept;
+// image index1 of one texture against image index2 of the other (GetImages() order). A compressed texture is decompressed whole on every call:
+// a caller with many pairs hands over Decompress's result instead.
+HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, size_t index1, const DeviceScratchImage& image2, size_t index2, float& mse, float* mseV,
+                   CMSE_FLAGS flags) noexcept;
 HRESULT Analyze(Device& device, const DeviceScratchImage& images, AnalyzeData* results) noexcept;
 HRESULT AnalyzeBC(Device& device, const DeviceScratchImage& images, AnalyzeBCData* results) noexcept;
 HRESULT Difference(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, TEX_FILTER_FLAGS dwFilter, DXGI_FORMAT format,
@@ -558,6 +567,44 @@ HRESULT SaveToDDSMemory(const Image& image, DDS_FLAGS flags, Blob& blob) noexcep
 HRESULT SaveToDDSMemory(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, Blob& blob) noexcept;
 HRESULT SaveToDDSFile(const Image& image, DDS_FLAGS flags, const char* szFile) noexcept;
 HRESULT SaveToDDSFile(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept;
+
+// The byte-serial half of the reader, no device needed: the header, every refusal (the E_FAIL of a row conversion that does not exist for
+// the result format included), the permissive cube fix and the size checks. What is left is per texel: image i of the texture (ScratchImage
+// order) is `op` applied to the rows that start images[i].offset bytes into the payload, images[i].rowPitch apart - the file's pitch rule,
+// DDS_FLAGS_LEGACY_DWORD and DDS_FLAGS_BAD_DXTN_TAILS applied. On failure `raw` is released: no payload pointer is handed out.
+struct DDSRawImage
+{
+    struct Source { size_t offset, rowPitch, slicePitch; };
+    TexMetadata metadata;
+    uint32_t op = 0;                             // DXTEX_DDS_ROW_* (include/dxtex_amd.h)
+    bool opaque = false;                         // alpha is forced (CONV_FLAGS_NOALPHA)
+    bool paletted = false;
+    uint32_t palette[256] = {};
+    const uint8_t* payload = nullptr;            // into the caller's memory; LoadFromDDSFileRaw: into `storage`
+    size_t payloadBytes = 0;                     // what the images need of it: the sum of the file's slice pitches
+    std::vector<Source> images;
+    bool direct = false;                         // a plain copy and every file pitch is the image's: the payload IS the image memory
+    Blob storage;
+    void Release() noexcept;
+};
+HRESULT LoadFromDDSMemoryRaw(const void* pSource, size_t size, DDS_FLAGS flags, DDSMetaData* ddPixelFormat, DDSRawImage& raw) noexcept;
+HRESULT LoadFromDDSFileRaw(const char* szFile, DDS_FLAGS flags, DDSMetaData* ddPixelFormat, DDSRawImage& raw) noexcept;
+// Resident forms: the payload crosses PCIe at the size it has in the file and the per-texel half runs on the device (dxtex_dds_unpack_device
+// / dxtex_dds_pack24_device). HRESULTs, metadata, pixels and files are those of the host forms above. Load: raw.direct is ONE host -> device
+// copy straight into the image's memory and no kernel; anything else is one upload of raw.payloadBytes and the unpack launches. The result
+// is released on failure. Save: deviceImages' pixels are device pointers, as DeviceScratchImage::GetImages gives; images whose pitches are
+// the file's come down straight behind the header (one copy per run of contiguous images), DDS_FLAGS_FORCE_24BPP_RGB packs on the device
+// and comes down at 3 bytes a texel, anything else in one strided copy per image.
+HRESULT LoadFromDDSMemory(Device& device, const void* pSource, size_t size, DDS_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromDDSMemoryEx(Device& device, const void* pSource, size_t size, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromDDSFile(Device& device, const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromDDSFileEx(Device& device, const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device
+HRESULT UploadDDSRaw(Device& device, const DDSRawImage& raw, DeviceScratchImage& image) noexcept;
+HRESULT SaveToDDSMemory(Device& device, const Image& deviceImage, DDS_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToDDSMemory(Device& device, const Image* deviceImages, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToDDSFile(Device& device, const Image& deviceImage, DDS_FLAGS flags, const char* szFile) noexcept;
+HRESULT SaveToDDSFile(Device& device, const Image* deviceImages, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept;
 
 // ---- Radiance RGBE (.hdr), DirectXTexHDR.cpp: loads to R32G32B32A32_FLOAT; saves RGBA32F / RGB32F / RGBA16F images ---------------
 HRESULT GetMetadataFromHDRMemory(const void* pSource, size_t size, TexMetadata& metadata) noexcept;

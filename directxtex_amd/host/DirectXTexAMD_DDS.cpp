@@ -6,6 +6,8 @@
 // All of this is host code: it is the container either side of the GPU path, and tests/test_dds_cpu.py compares it with the
 // reference's own reader and writer (oracle/_ref) file by file.
 #include "DirectXTexAMD.h"
+#include "../../include/dxtex_amd.h"
+#include "../csrc/dxtex_dds.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -289,23 +291,12 @@ namespace
         return S_OK;
     }
 
-    // ---- row conversions ------------------------------------------------------------------------------------------------
-    inline uint32_t rd16(const uint8_t* p) noexcept { return uint32_t(p[0]) | (uint32_t(p[1]) << 8); }
-    inline uint32_t rd32(const uint8_t* p) noexcept { uint32_t v; std::memcpy(&v, p, 4); return v; }
-    inline void wr16(uint8_t* p, uint32_t v) noexcept { p[0] = uint8_t(v); p[1] = uint8_t(v >> 8); }
-    inline void wr32(uint8_t* p, uint32_t v) noexcept { std::memcpy(p, &v, 4); }
-    // an n-bit channel widened to `to` bits by repeating its bit pattern (what all the legacy expansions do)
-    inline uint32_t widen(uint32_t v, unsigned n, unsigned to) noexcept
-    {
-        uint32_t out = 0; unsigned have = 0;
-        while (have < to) { out = (out << n) | v; have += n; }
-        return out >> (have - to);
-    }
-    inline uint32_t rgba8(uint32_t r, uint32_t g, uint32_t b, uint32_t a) noexcept { return r | (g << 8) | (b << 16) | (a << 24); }
-    inline uint32_t flip(uint32_t v, unsigned bits) noexcept { return v ^ (1u << (bits - 1)); }        // two's complement -> offset binary
-
-    enum RowOp { ROW_COPY, ROW_SWIZZLE, ROW_565, ROW_5551, ROW_4444, ROW_ABGR4, ROW_888, ROW_332, ROW_8332, ROW_P8, ROW_A8P8, ROW_44, ROW_L8, ROW_L16,
-                 ROW_A8L8, ROW_L6V5U5, ROW_L8U8V8, ROW_WUV10, ROW_FAIL };
+    // ---- row conversions: the per-texel rules are csrc/dxtex_dds.h's, shared with the GPU kernels ------------------------------------
+    using dxtex::DdsRowOp;
+    using dxtex::ROW_COPY; using dxtex::ROW_SWIZZLE; using dxtex::ROW_565; using dxtex::ROW_5551; using dxtex::ROW_4444; using dxtex::ROW_ABGR4;
+    using dxtex::ROW_888; using dxtex::ROW_332; using dxtex::ROW_8332; using dxtex::ROW_P8; using dxtex::ROW_A8P8; using dxtex::ROW_44; using dxtex::ROW_L8;
+    using dxtex::ROW_L16; using dxtex::ROW_A8L8; using dxtex::ROW_L6V5U5; using dxtex::ROW_L8U8V8; using dxtex::ROW_WUV10; using dxtex::ROW_FAIL;
+    typedef DdsRowOp RowOp;
 
     // which conversion a row of this file gets (the dispatch of CopyImage, DirectXTexDDS.cpp:1644-1691)
     RowOp PickRowOp(uint32_t conv) noexcept
@@ -332,224 +323,46 @@ namespace
         return ROW_COPY;
     }
 
-    inline bool Is8888(DXGI_FORMAT f) noexcept
-    {
-        switch (f)
-        {
-        case DXGI_FORMAT_R8G8B8A8_TYPELESS: case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB:
-        case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8A8_TYPELESS: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB:
-        case DXGI_FORMAT_B8G8R8X8_TYPELESS: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB:
-            return true;
-        default: return false;
-        }
-    }
-    inline bool Is1010102(DXGI_FORMAT f) noexcept
-    {
-        return f == DXGI_FORMAT_R10G10B10A2_TYPELESS || f == DXGI_FORMAT_R10G10B10A2_UNORM || f == DXGI_FORMAT_R10G10B10A2_UINT
-            || f == DXGI_FORMAT_R10G10B10_XR_BIAS_A2_UNORM || uint32_t(f) == 189;
-    }
-
     // CopyScanline with TEXP_SCANLINE_SETALPHA (DirectXTexConvert.cpp:207-430): the formats whose alpha can be forced opaque
     void CopyOpaque(uint8_t* d, size_t dn, const uint8_t* s, size_t sn, DXGI_FORMAT f) noexcept
     {
         const size_t n = std::min(dn, sn);
-        switch (uint32_t(f))
+        const dxtex::DdsOpaque o = dxtex::dds_opaque_of(int(f));
+        if (!o.texelBytes) { std::memcpy(d, s, n); return; }
+        if (o.texelBytes == 1) { std::memset(d, int(o.set), dn); return; }           // A8: the whole destination row
+        // whole texels only: the bytes in front of a texel's last word pass, the word has its alpha set
+        const size_t T = o.texelBytes, W = std::min<size_t>(T, 4);
+        for (size_t i = 0; i + T <= n; i += T)
         {
-        case DXGI_FORMAT_R32G32B32A32_TYPELESS: case DXGI_FORMAT_R32G32B32A32_FLOAT: case DXGI_FORMAT_R32G32B32A32_UINT: case DXGI_FORMAT_R32G32B32A32_SINT:
-        {
-            const uint32_t a = (f == DXGI_FORMAT_R32G32B32A32_FLOAT) ? 0x3f800000u : (f == DXGI_FORMAT_R32G32B32A32_SINT) ? 0x7fffffffu : 0xffffffffu;
-            for (size_t i = 0; i + 16 <= n; i += 16) { std::memcpy(d + i, s + i, 12); wr32(d + i + 12, a); }
-            return;
-        }
-        case DXGI_FORMAT_R16G16B16A16_TYPELESS: case DXGI_FORMAT_R16G16B16A16_FLOAT: case DXGI_FORMAT_R16G16B16A16_UNORM: case DXGI_FORMAT_R16G16B16A16_UINT:
-        case DXGI_FORMAT_R16G16B16A16_SNORM: case DXGI_FORMAT_R16G16B16A16_SINT: case DXGI_FORMAT_Y416:
-        {
-            const uint32_t a = (f == DXGI_FORMAT_R16G16B16A16_FLOAT) ? 0x3c00u : (f == DXGI_FORMAT_R16G16B16A16_SNORM || f == DXGI_FORMAT_R16G16B16A16_SINT) ? 0x7fffu : 0xffffu;
-            for (size_t i = 0; i + 8 <= n; i += 8) { std::memcpy(d + i, s + i, 6); wr16(d + i + 6, a); }
-            return;
-        }
-        case DXGI_FORMAT_R10G10B10A2_TYPELESS: case DXGI_FORMAT_R10G10B10A2_UNORM: case DXGI_FORMAT_R10G10B10A2_UINT: case DXGI_FORMAT_R10G10B10_XR_BIAS_A2_UNORM:
-        case DXGI_FORMAT_Y410: case 116: case 117: case 189:
-            for (size_t i = 0; i + 4 <= n; i += 4) wr32(d + i, rd32(s + i) | 0xC0000000u);
-            return;
-        case DXGI_FORMAT_R8G8B8A8_TYPELESS: case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: case DXGI_FORMAT_R8G8B8A8_UINT:
-        case DXGI_FORMAT_R8G8B8A8_SNORM: case DXGI_FORMAT_R8G8B8A8_SINT: case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_TYPELESS:
-        case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: case DXGI_FORMAT_AYUV:
-        {
-            const uint32_t a = (f == DXGI_FORMAT_R8G8B8A8_SNORM || f == DXGI_FORMAT_R8G8B8A8_SINT) ? 0x7f000000u : 0xff000000u;
-            for (size_t i = 0; i + 4 <= n; i += 4) wr32(d + i, (rd32(s + i) & 0xFFFFFFu) | a);
-            return;
-        }
-        case DXGI_FORMAT_B5G5R5A1_UNORM: case DXGI_FORMAT_B4G4R4A4_UNORM: case DXGI_FORMAT_A4B4G4R4_UNORM:
-        {
-            const uint32_t a = (f == DXGI_FORMAT_B4G4R4A4_UNORM) ? 0xF000u : (f == DXGI_FORMAT_A4B4G4R4_UNORM) ? 0x000Fu : 0x8000u;
-            for (size_t i = 0; i + 2 <= n; i += 2) wr16(d + i, rd16(s + i) | a);
-            return;
-        }
-        case DXGI_FORMAT_A8_UNORM:
-            std::memset(d, 0xff, dn);
-            return;
-        default:
-            std::memcpy(d, s, n);
-            return;
+            std::memcpy(d + i, s + i, T - W);
+            dxtex::dds_store(d + i + T - W, dxtex::dds_opaque_word(dxtex::dds_load(s + i + T - W, uint32_t(W)), o), uint32_t(W));
         }
     }
 
     // One row. Returns false where the reference's expansion refuses the (source, result format) pair.
     bool ConvertRow(RowOp op, uint8_t* d, size_t dn, const uint8_t* s, size_t sn, DXGI_FORMAT outFormat, bool opaque, const uint32_t* pal8) noexcept
     {
-        const bool to8888 = outFormat == DXGI_FORMAT_R8G8B8A8_UNORM;
-        switch (op)
+        if (op == ROW_COPY)
         {
-        case ROW_COPY:
             if (opaque) CopyOpaque(d, dn, s, sn, outFormat);
             else std::memcpy(d, s, std::min(dn, sn));
             return true;
-        case ROW_SWIZZLE:           // SwizzleScanline with TEXP_SCANLINE_LEGACY (DirectXTexConvert.cpp:440-605)
-        {
-            const size_t n = std::min(dn, sn);
-            if (Is1010102(outFormat))
-                for (size_t i = 0; i + 4 <= n; i += 4)
-                {
-                    const uint32_t t = rd32(s + i);
-                    wr32(d + i, ((t >> 20) & 0x3ffu) | ((t & 0x3ffu) << 20) | (t & 0x000ffc00u) | (opaque ? 0xC0000000u : (t & 0xC0000000u)));
-                }
-            else if (Is8888(outFormat))
-                for (size_t i = 0; i + 4 <= n; i += 4)
-                {
-                    const uint32_t t = rd32(s + i);
-                    wr32(d + i, ((t >> 16) & 0xffu) | ((t & 0xffu) << 16) | (t & 0x0000ff00u) | (opaque ? 0xff000000u : (t & 0xff000000u)));
-                }
-            else if (outFormat == DXGI_FORMAT_YUY2)         // UYVY -> YUY2
-                for (size_t i = 0; i + 4 <= n; i += 4)
-                {
-                    const uint32_t t = rd32(s + i);
-                    wr32(d + i, ((t & 0x00ff00ffu) << 8) | ((t & 0xff00ff00u) >> 8));
-                }
-            else std::memcpy(d, s, n);
-            return true;
         }
-        case ROW_565:
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4)
-            {
-                const uint32_t t = rd16(s + i);
-                // sic (ExpandScanline, DirectXTexConvert.cpp:643): the two bits that should fill green's low end are shifted into
-                // bits 4-5 of the word - the red byte - so green keeps zeros there and red picks them up
-                const uint32_t g6 = (t >> 5) & 0x3f;
-                wr32(d + o, rgba8(widen(t >> 11, 5, 8) | ((g6 >> 4) << 4), g6 << 2, widen(t & 0x1f, 5, 8), 0xff));
-            }
-            return true;
-        case ROW_5551:
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4)
-            {
-                const uint32_t t = rd16(s + i);
-                wr32(d + o, rgba8(widen((t >> 10) & 0x1f, 5, 8), widen((t >> 5) & 0x1f, 5, 8), widen(t & 0x1f, 5, 8), (opaque || (t & 0x8000)) ? 0xff : 0));
-            }
-            return true;
-        case ROW_4444: case ROW_ABGR4:
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4)
-            {
-                const uint32_t t = rd16(s + i);
-                // nibbles from the top: B4G4R4A4 = A R G B, A4B4G4R4 = R G B A
-                const uint32_t n3 = t >> 12, n2 = (t >> 8) & 0xf, n1 = (t >> 4) & 0xf, n0 = t & 0xf;
-                if (op == ROW_4444) wr32(d + o, rgba8(n2 * 17, n1 * 17, n0 * 17, opaque ? 0xff : n3 * 17));
-                else wr32(d + o, rgba8(n3 * 17, n2 * 17, n1 * 17, opaque ? 0xff : n0 * 17));
-            }
-            return true;
-        case ROW_888:                // 24 bpp files are B, G, R in memory
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 3 <= sn && o + 4 <= dn; i += 3, o += 4) wr32(d + o, rgba8(s[i + 2], s[i + 1], s[i], 0xff));
-            return true;
-        case ROW_332:
-            if (to8888)
-                for (size_t i = 0, o = 0; i < sn && o + 4 <= dn; ++i, o += 4)
-                    wr32(d + o, rgba8(widen(s[i] >> 5, 3, 8), widen((s[i] >> 2) & 7, 3, 8), widen(s[i] & 3, 2, 8), 0xff));
-            else if (outFormat == DXGI_FORMAT_B5G6R5_UNORM)
-                for (size_t i = 0, o = 0; i < sn && o + 2 <= dn; ++i, o += 2)
-                    wr16(d + o, (widen(s[i] >> 5, 3, 5) << 11) | (widen((s[i] >> 2) & 7, 3, 6) << 5) | widen(s[i] & 3, 2, 5));
-            else return false;
-            return true;
-        case ROW_8332:
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4)
-            {
-                const uint32_t t = rd16(s + i);
-                wr32(d + o, rgba8(widen((t >> 5) & 7, 3, 8), widen((t >> 2) & 7, 3, 8), widen(t & 3, 2, 8), opaque ? 0xff : (t >> 8)));
-            }
-            return true;
-        case ROW_P8:
-            if (!to8888 || !pal8) return false;
-            for (size_t i = 0, o = 0; i < sn && o + 4 <= dn; ++i, o += 4) wr32(d + o, pal8[s[i]]);
-            return true;
-        case ROW_A8P8:               // the texel's alpha is OR-ed onto the palette entry's
-            if (!to8888 || !pal8) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4) wr32(d + o, pal8[s[i]] | (opaque ? 0xff000000u : (uint32_t(s[i + 1]) << 24)));
-            return true;
-        case ROW_44:
-            if (to8888)
-                for (size_t i = 0, o = 0; i < sn && o + 4 <= dn; ++i, o += 4)
-                {
-                    const uint32_t l = (s[i] & 0xfu) * 17;
-                    wr32(d + o, rgba8(l, l, l, opaque ? 0xff : (s[i] >> 4) * 17u));
-                }
-            else if (outFormat == DXGI_FORMAT_B4G4R4A4_UNORM)
-                for (size_t i = 0, o = 0; i < sn && o + 2 <= dn; ++i, o += 2)
-                {
-                    const uint32_t l = s[i] & 0xfu;
-                    wr16(d + o, l | (l << 4) | (l << 8) | (opaque ? 0xf000u : (uint32_t(s[i] >> 4) << 12)));
-                }
-            else return false;
-            return true;
-        case ROW_L8:
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i < sn && o + 4 <= dn; ++i, o += 4) wr32(d + o, rgba8(s[i], s[i], s[i], 0xff));
-            return true;
-        case ROW_L16:
-            if (outFormat != DXGI_FORMAT_R16G16B16A16_UNORM) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 8 <= dn; i += 2, o += 8)
-            {
-                const uint32_t l = rd16(s + i);
-                wr16(d + o, l); wr16(d + o + 2, l); wr16(d + o + 4, l); wr16(d + o + 6, 0xffff);
-            }
-            return true;
-        case ROW_A8L8:
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4) wr32(d + o, rgba8(s[i], s[i], s[i], opaque ? 0xff : s[i + 1]));
-            return true;
-        case ROW_L6V5U5:             // unsigned 6-bit luminance, signed 5-bit v and u -> (L, U, V, 1) as unsigned bytes
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 2 <= sn && o + 4 <= dn; i += 2, o += 4)
-            {
-                const uint32_t t = rd16(s + i);
-                wr32(d + o, rgba8(widen(t >> 10, 6, 8), widen(flip(t & 0x1f, 5), 5, 8), widen(flip((t >> 5) & 0x1f, 5), 5, 8), 0xff));
-            }
-            return true;
-        case ROW_L8U8V8:             // X8L8V8U8: (L, U, V, 1) with the signed bytes rebased to unsigned
-            if (!to8888) return false;
-            for (size_t i = 0, o = 0; i + 4 <= sn && o + 4 <= dn; i += 4, o += 4)
-            {
-                const uint32_t t = rd32(s + i);
-                wr32(d + o, rgba8((t >> 16) & 0xff, flip(t & 0xff, 8), flip((t >> 8) & 0xff, 8), 0xff));
-            }
-            return true;
-        case ROW_WUV10:              // A2W10V10U10: three signed 10-bit fields rebased to unsigned, alpha kept
-            if (outFormat != DXGI_FORMAT_R10G10B10A2_UNORM) return false;
-            for (size_t i = 0, o = 0; i + 4 <= sn && o + 4 <= dn; i += 4, o += 4)
-            {
-                const uint32_t t = rd32(s + i);
-                wr32(d + o, flip(t & 0x3ff, 10) | (flip((t >> 10) & 0x3ff, 10) << 10) | (flip((t >> 20) & 0x3ff, 10) << 20) | (opaque ? 0xC0000000u : (t & 0xC0000000u)));
-            }
-            return true;
-        default:
-            return false;
-        }
+        const int target = dxtex::dds_target(op, int(outFormat));
+        if (target < 0 || (dxtex::dds_has_palette(op) && !pal8)) return false;
+        if (target == dxtex::DDS_TO_BYTES) { std::memcpy(d, s, std::min(dn, sn)); return true; }          // a swizzle of a format that has none
+        const size_t B = dxtex::dds_file_bytes(op), D = dxtex::dds_image_bytes(target);
+        // SwizzleScanline stops at the shorter row; the expansions at whichever side runs out of whole texels first
+        const size_t texels = op == ROW_SWIZZLE ? std::min(dn, sn) / 4 : std::min(sn / B, dn / D);
+        for (size_t x = 0; x < texels; ++x)
+            dxtex::dds_store(d + x * D, dxtex::dds_unpack_texel(dxtex::dds_load(s + x * B, uint32_t(B)), op, target, opaque, pal8), uint32_t(D));
+        return true;
     }
 
-    // CopyImage (DirectXTexDDS.cpp:1518-1808): the payload, laid out by the FILE's pitch rule, into the ScratchImage
-    HRESULT CopyPayload(const uint8_t* pixels, size_t size, const TexMetadata& m, uint32_t cp, uint32_t conv, const uint32_t* pal8, const ScratchImage& image) noexcept
+    // CopyImage's bookkeeping (DirectXTexDDS.cpp:1518-1808): where each image of the ScratchImage layout `images` lies in the payload, laid
+    // out by the FILE's pitch rule, and every check CopyImage makes before and while it copies. No pixel is touched.
+    HRESULT LayoutPayload(size_t size, const TexMetadata& m, uint32_t cp, uint32_t conv, const Image* images, size_t nimages, std::vector<DDSRawImage::Source>& src,
+                          size_t& payloadBytes, bool& direct) noexcept
     {
         if (!size) return E_FAIL;
         if (conv & CV_EXPAND)
@@ -558,9 +371,7 @@ namespace
             else if (conv & (CV_565 | CV_5551 | CV_4444 | CV_8332 | CV_A8P8 | CV_L16 | CV_A8L8 | CV_L6V5U5)) cp |= CP_FLAGS_16BPP;
             else if (conv & (CV_44 | CV_332 | CV_PAL8 | CV_L8)) cp |= CP_FLAGS_8BPP;
         }
-        // where each image of the file starts, and its pitches
-        struct Src { size_t offset, rowPitch, slicePitch; };
-        std::vector<Src> src;
+        src.clear();
         const bool volume = m.dimension == TEX_DIMENSION_TEXTURE3D;
         uint64_t total = 0;
         for (size_t item = 0; item < (volume ? 1 : m.arraySize); ++item)
@@ -574,79 +385,134 @@ namespace
                 for (size_t slice = 0; slice < d; ++slice)
                 {
                     if (sp > UINT64_MAX - total) return HRESULT_E_HANDLE_EOF;          // no file holds that much
-                    src.push_back({ size_t(total), rp, sp }); total += sp;
+                    try { src.push_back({ size_t(total), rp, sp }); } catch (...) { return E_OUTOFMEMORY; }
+                    total += sp;
                 }
                 if (h > 1) h >>= 1;
                 if (w > 1) w >>= 1;
                 if (d > 1) d >>= 1;
             }
         }
-        if (src.empty() || src.size() != image.GetImageCount()) return E_FAIL;
+        if (src.empty() || src.size() != nimages) return E_FAIL;
         if (total > size) return HRESULT_E_HANDLE_EOF;
-        const Image* images = image.GetImages();
         if (!images) return E_FAIL;
         if (m.dimension != TEX_DIMENSION_TEXTURE1D && m.dimension != TEX_DIMENSION_TEXTURE2D && !volume) return E_FAIL;
-
-        const bool opaque = (conv & CV_NOALPHA) != 0;
-        const RowOp op = PickRowOp(conv);
         const bool compressed = IsCompressed(m.format), planar = IsPlanar(m.format);
         if (planar && volume) return HRESULT_E_NOT_SUPPORTED;
-        size_t index = 0;
-        const size_t chains = volume ? 1 : m.arraySize;
-        for (size_t item = 0; item < chains; ++item)
+        // what the first row of the first image would answer
+        const RowOp op = PickRowOp(conv);
+        if (!compressed)
         {
-            size_t lastgood = 0, d = volume ? m.depth : 1;          // sic: the reference restarts at image 0 for every array item
-            for (size_t level = 0; level < m.mipLevels; ++level)
+            if (planar) { if (!ComputeScanlines(m.format, images[0].height)) return E_FAIL; }
+            else if (dxtex::dds_target(op, int(m.format)) < 0) return E_FAIL;
+        }
+        payloadBytes = size_t(total);
+        direct = op == ROW_COPY && !(conv & CV_NOALPHA);
+        for (size_t i = 0; i < nimages && direct; ++i)
+            direct = src[i].offset == size_t(images[i].pixels - images[0].pixels) && src[i].rowPitch == images[i].rowPitch && src[i].slicePitch == images[i].slicePitch;
+        if (compressed && (cp & CP_FLAGS_BAD_DXTN_TAILS))
+        {
+            // levels smaller than a block were not stored: they take the bytes of the last level that was
+            const std::vector<DDSRawImage::Source> stored = src;
+            size_t index = 0;
+            for (size_t item = 0; item < (volume ? 1 : m.arraySize); ++item)
             {
-                for (size_t slice = 0; slice < d; ++slice, ++index)
+                size_t lastgood = 0, d = volume ? m.depth : 1;          // sic: the reference restarts at image 0 for every array item
+                for (size_t level = 0; level < m.mipLevels; ++level)
                 {
-                    const Image& dst = images[index];
-                    const Src& from = src[index];
-                    const uint8_t* sp = pixels + from.offset;
-                    if (compressed)
+                    for (size_t slice = 0; slice < d; ++slice, ++index)
                     {
-                        std::memcpy(dst.pixels, sp, std::min(dst.slicePitch, from.slicePitch));
-                        if (cp & CP_FLAGS_BAD_DXTN_TAILS)
-                        {
-                            // levels smaller than a block were not stored: take the bytes of the last level that was
-                            if (dst.width < 4 || dst.height < 4)
-                            {
-                                const Src& good = src[lastgood + (volume ? slice : 0)];
-                                std::memcpy(dst.pixels, pixels + good.offset, std::min(dst.slicePitch, good.slicePitch));
-                            }
-                            else if (!volume || slice == 0) lastgood = index;
-                        }
-                        continue;
+                        if (images[index].width < 4 || images[index].height < 4) { src[index] = stored[lastgood + (volume ? slice : 0)]; direct = false; }
+                        else if (!volume || slice == 0) lastgood = index;
                     }
-                    const size_t rows = planar ? ComputeScanlines(m.format, dst.height) : dst.height;
-                    if (planar && !rows) return E_FAIL;
-                    uint8_t* dp = dst.pixels;
-                    for (size_t y = 0; y < rows; ++y, sp += from.rowPitch, dp += dst.rowPitch)
-                    {
-                        if (planar) std::memcpy(dp, sp, std::min(dst.rowPitch, from.rowPitch));
-                        else if (!ConvertRow(op, dp, dst.rowPitch, sp, from.rowPitch, m.format, opaque, pal8)) return E_FAIL;
-                    }
+                    if (d > 1) d >>= 1;
                 }
-                if (d > 1) d >>= 1;
             }
         }
         return S_OK;
     }
 
-    HRESULT ReadWholeFile(const char* szFile, std::vector<uint8_t>& buf) noexcept
+    // One image's rows from the payload into `dst` (host memory): CopyImage's loop body
+    void CopyRows(const DDSRawImage& raw, size_t index, const Image& dst) noexcept
+    {
+        const DDSRawImage::Source& from = raw.images[index];
+        const DXGI_FORMAT format = raw.metadata.format;
+        const uint8_t* sp = raw.payload + from.offset;
+        if (IsCompressed(format)) { std::memcpy(dst.pixels, sp, std::min(dst.slicePitch, from.slicePitch)); return; }
+        const bool planar = IsPlanar(format);
+        const size_t rows = planar ? ComputeScanlines(format, dst.height) : dst.height;
+        uint8_t* dp = dst.pixels;
+        for (size_t y = 0; y < rows; ++y, sp += from.rowPitch, dp += dst.rowPitch)
+        {
+            if (planar) std::memcpy(dp, sp, std::min(dst.rowPitch, from.rowPitch));
+            else ConvertRow(RowOp(raw.op), dp, dst.rowPitch, sp, from.rowPitch, format, raw.opaque, raw.paletted ? raw.palette : nullptr);
+        }
+    }
+
+    // The reader up to the pixels: header, palette, the permissive cube fix, the payload's layout. `layout` = the images of
+    // ScratchImage::Initialize(raw.metadata), their pixels as offsets.
+    HRESULT ParseDDS(const void* pSource, size_t size, DDS_FLAGS flags, DDSMetaData* ddPixelFormat, DDSRawImage& raw, std::unique_ptr<Image[]>& layout, size_t& nimages) noexcept
+    {
+        uint32_t conv = 0;
+        TexMetadata m;
+        HRESULT hr = DecodeHeader(pSource, size, uint32_t(flags), m, ddPixelFormat, conv);
+        if (FAILED(hr)) return hr;
+        size_t offset = (conv & CV_DX10) ? kDX10Header : kMinHeader;
+        const uint8_t* bytes = static_cast<const uint8_t*>(pSource);
+        if (conv & CV_PAL8)
+        {
+            if (size < offset + 256 * sizeof(uint32_t)) return E_FAIL;
+            std::memcpy(raw.palette, bytes + offset, 256 * sizeof(uint32_t));
+            raw.paletted = true;
+            offset += 256 * sizeof(uint32_t);
+        }
+        const size_t remaining = size - offset;
+        if (remaining == 0) return E_FAIL;
+        size_t pixelBytes = 0, mipLevels = 0;
+        hr = LayoutScratchImage(m, CP_FLAGS_NONE, layout, nimages, pixelBytes, mipLevels);
+        if (FAILED(hr)) return hr;
+        if ((flags & DDS_FLAGS_PERMISSIVE) && (m.miscFlags & TEX_MISC_TEXTURECUBE) && (conv & CV_DX10) && pixelBytes > remaining && (m.arraySize % 6) == 0)
+        {
+            // a writer that stored 6 * cubes where the number of cubes belongs
+            m.arraySize /= 6;
+            hr = LayoutScratchImage(m, CP_FLAGS_NONE, layout, nimages, pixelBytes, mipLevels);
+            if (FAILED(hr)) return hr;
+            if (pixelBytes > remaining) return HRESULT_E_HANDLE_EOF;
+        }
+        m.mipLevels = mipLevels;
+        uint32_t cp = 0;
+        if (flags & DDS_FLAGS_LEGACY_DWORD) cp |= CP_FLAGS_LEGACY_DWORD;
+        if (flags & DDS_FLAGS_BAD_DXTN_TAILS) cp |= CP_FLAGS_BAD_DXTN_TAILS;
+        raw.metadata = m;
+        raw.op = uint32_t(PickRowOp(conv));
+        raw.opaque = (conv & CV_NOALPHA) != 0;
+        raw.payload = bytes + offset;
+        return LayoutPayload(remaining, m, cp, conv, layout.get(), nimages, raw.images, raw.payloadBytes, raw.direct);
+    }
+
+    HRESULT ReadWholeFile(const char* szFile, Blob& buf) noexcept
     {
         FILE* f = std::fopen(szFile, "rb");
         if (!f) return E_FAIL;
         std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
         if (n < 0) { std::fclose(f); return E_FAIL; }
         if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
-        try { buf.resize(size_t(n)); } catch (...) { std::fclose(f); return E_OUTOFMEMORY; }
-        const size_t got = buf.empty() ? 0 : std::fread(buf.data(), 1, buf.size(), f);
+        if (size_t(n) < kMinHeader) { std::fclose(f); return E_FAIL; }               // the file readers say E_FAIL here (DirectXTexDDS.cpp:1975-1978, :2178-2181)
+        if (FAILED(buf.Initialize(size_t(n)))) { std::fclose(f); return E_OUTOFMEMORY; }
+        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
         std::fclose(f);
-        if (got != buf.size()) return E_FAIL;
-        if (buf.size() < kMinHeader) return E_FAIL;               // the file readers say E_FAIL here (DirectXTexDDS.cpp:1975-1978, :2178-2181)
-        return S_OK;
+        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
     }
+
+    struct DeviceTemp
+    {
+        Device& device;
+        void* p = nullptr;
+        explicit DeviceTemp(Device& d) noexcept : device(d) {}
+        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }          // waits for the work that still uses it
+        DeviceTemp(const DeviceTemp&) = delete;
+        DeviceTemp& operator=(const DeviceTemp&) = delete;
+    };
 }
 
 HRESULT Blob::Initialize(size_t size) noexcept
@@ -691,43 +557,51 @@ HRESULT GetMetadataFromDDSFile(const char* szFile, DDS_FLAGS flags, TexMetadata&
     return GetMetadataFromDDSFileEx(szFile, flags, metadata, nullptr);
 }
 
+void DDSRawImage::Release() noexcept
+{
+    storage.Release();
+    images.clear();
+    std::memset(palette, 0, sizeof(palette));
+    metadata = TexMetadata();
+    op = 0; opaque = paletted = direct = false; payload = nullptr; payloadBytes = 0;
+}
+
+HRESULT LoadFromDDSMemoryRaw(const void* pSource, size_t size, DDS_FLAGS flags, DDSMetaData* ddPixelFormat, DDSRawImage& raw) noexcept
+{
+    raw.Release();
+    if (!pSource || size == 0) return E_INVALIDARG;
+    std::unique_ptr<Image[]> layout;
+    size_t nimages = 0;
+    const HRESULT hr = ParseDDS(pSource, size, flags, ddPixelFormat, raw, layout, nimages);
+    if (FAILED(hr)) raw.Release();
+    return hr;
+}
+
+HRESULT LoadFromDDSFileRaw(const char* szFile, DDS_FLAGS flags, DDSMetaData* ddPixelFormat, DDSRawImage& raw) noexcept
+{
+    raw.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    HRESULT hr = ReadWholeFile(szFile, file);
+    if (FAILED(hr)) return hr;
+    hr = LoadFromDDSMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, ddPixelFormat, raw);
+    if (SUCCEEDED(hr)) raw.storage.Swap(file);          // raw.payload points into it
+    return hr;
+}
+
 // LoadFromDDSMemoryEx (DirectXTexDDS.cpp:2019-2107)
 HRESULT LoadFromDDSMemoryEx(const void* pSource, size_t size, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, ScratchImage& image) noexcept
 {
     if (!pSource || size == 0) return E_INVALIDARG;
     image.Release();
-    uint32_t conv = 0;
-    TexMetadata m;
-    HRESULT hr = DecodeHeader(pSource, size, uint32_t(flags), m, ddPixelFormat, conv);
+    DDSRawImage raw;
+    HRESULT hr = LoadFromDDSMemoryRaw(pSource, size, flags, ddPixelFormat, raw);
     if (FAILED(hr)) return hr;
-    size_t offset = (conv & CV_DX10) ? kDX10Header : kMinHeader;
-    const uint8_t* bytes = static_cast<const uint8_t*>(pSource);
-    std::vector<uint32_t> pal8;
-    if (conv & CV_PAL8)
-    {
-        if (size < offset + 256 * sizeof(uint32_t)) return E_FAIL;
-        try { pal8.resize(256); } catch (...) { return E_OUTOFMEMORY; }
-        std::memcpy(pal8.data(), bytes + offset, 256 * sizeof(uint32_t));
-        offset += 256 * sizeof(uint32_t);
-    }
-    const size_t remaining = size - offset;
-    if (remaining == 0) return E_FAIL;
-    hr = image.Initialize(m);
+    hr = image.Initialize(raw.metadata);
     if (FAILED(hr)) return hr;
-    if ((flags & DDS_FLAGS_PERMISSIVE) && (m.miscFlags & TEX_MISC_TEXTURECUBE) && (conv & CV_DX10) && image.GetPixelsSize() > remaining && (m.arraySize % 6) == 0)
-    {
-        // a writer that stored 6 * cubes where the number of cubes belongs
-        m.arraySize /= 6;
-        hr = image.Initialize(m);
-        if (FAILED(hr)) return hr;
-        if (image.GetPixelsSize() > remaining) { image.Release(); return HRESULT_E_HANDLE_EOF; }
-    }
-    uint32_t cp = 0;
-    if (flags & DDS_FLAGS_LEGACY_DWORD) cp |= CP_FLAGS_LEGACY_DWORD;
-    if (flags & DDS_FLAGS_BAD_DXTN_TAILS) cp |= CP_FLAGS_BAD_DXTN_TAILS;
-    hr = CopyPayload(bytes + offset, remaining, m, cp, conv, pal8.empty() ? nullptr : pal8.data(), image);
-    if (FAILED(hr)) { image.Release(); return hr; }
-    if (metadata) *metadata = m;
+    if (image.GetImageCount() != raw.images.size()) { image.Release(); return E_FAIL; }
+    for (size_t i = 0; i < raw.images.size(); ++i) CopyRows(raw, i, image.GetImages()[i]);
+    if (metadata) *metadata = raw.metadata;
     return S_OK;
 }
 
@@ -740,15 +614,95 @@ HRESULT LoadFromDDSFileEx(const char* szFile, DDS_FLAGS flags, TexMetadata* meta
 {
     if (!szFile) return E_INVALIDARG;
     image.Release();
-    std::vector<uint8_t> buf;
+    Blob buf;
     const HRESULT hr = ReadWholeFile(szFile, buf);
     if (FAILED(hr)) return hr;
-    return LoadFromDDSMemoryEx(buf.data(), buf.size(), flags, metadata, ddPixelFormat, image);
+    return LoadFromDDSMemoryEx(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, ddPixelFormat, image);
 }
 
 HRESULT LoadFromDDSFile(const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
 {
     return LoadFromDDSFileEx(szFile, flags, metadata, nullptr, image);
+}
+
+// ---- reading, resident ----------------------------------------------------------------------------------------------------------------
+HRESULT UploadDDSRaw(Device& device, const DDSRawImage& raw, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!device) return E_POINTER;
+    if (!raw.payload || raw.images.empty()) return E_INVALIDARG;
+    HRESULT hr = image.Initialize(device, raw.metadata);
+    if (FAILED(hr)) return hr;
+    const size_t n = raw.images.size();
+    if (image.GetImageCount() != n) { image.Release(); return E_FAIL; }
+    if (raw.direct && raw.payloadBytes == image.GetPixelsSize())
+    {
+        // the file's pitches are the image's: the payload is the image memory, and no kernel runs
+        hr = dxtex_memcpy_h2d(device.Get(), image.GetPixels(), raw.payload, raw.payloadBytes);
+        if (FAILED(hr)) image.Release();
+        return hr;
+    }
+    const DXGI_FORMAT format = raw.metadata.format;
+    const bool compressed = IsCompressed(format), planar = IsPlanar(format), bytes = raw.op == DXTEX_DDS_ROW_COPY && !raw.opaque;
+    std::vector<dxtex_image> dsts;
+    std::vector<size_t> offsets, pitches;
+    try { dsts.resize(n); offsets.resize(n); pitches.resize(n); } catch (...) { image.Release(); return E_OUTOFMEMORY; }
+    for (size_t i = 0; i < n; ++i)
+    {
+        const Image& d = image.GetImages()[i];
+        const DDSRawImage::Source& from = raw.images[i];
+        dsts[i] = dxtex_image{ d.width, d.height, int32_t(d.format), d.rowPitch, d.slicePitch, d.pixels };
+        offsets[i] = from.offset; pitches[i] = from.rowPitch;
+        if (bytes)
+        {
+            // a plain copy is described in bytes, whatever the format: a compressed image is one row of the smaller slice pitch, a planar one
+            // every plane's rows (CopyImage's own three cases)
+            const size_t rows = compressed ? 1 : planar ? ComputeScanlines(format, d.height) : d.height;
+            const size_t rowBytes = compressed ? std::min(d.slicePitch, from.slicePitch) : std::min(d.rowPitch, from.rowPitch);
+            dsts[i] = dxtex_image{ rowBytes, rows, int32_t(DXGI_FORMAT_R8_UNORM), compressed ? rowBytes : d.rowPitch, d.slicePitch, d.pixels };
+            if (compressed) pitches[i] = rowBytes;
+        }
+    }
+    DeviceTemp temp(device);
+    hr = dxtex_device_alloc(device.Get(), raw.payloadBytes, &temp.p);
+    if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.payload, raw.payloadBytes);          // the caller's bytes are free to go on return
+    if (SUCCEEDED(hr)) hr = dxtex_dds_unpack_device(device.Get(), temp.p, raw.payloadBytes, raw.op, raw.opaque ? 1u : 0u, raw.paletted ? raw.palette : nullptr,
+                                                    dsts.data(), offsets.data(), pitches.data(), n);
+    if (FAILED(hr)) image.Release();
+    return hr;
+}
+
+HRESULT LoadFromDDSMemoryEx(Device& device, const void* pSource, size_t size, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, DeviceScratchImage& image) noexcept
+{
+    image.Release();          // on any failure the result is empty
+    if (!pSource || size == 0) return E_INVALIDARG;
+    DDSRawImage raw;
+    HRESULT hr = LoadFromDDSMemoryRaw(pSource, size, flags, ddPixelFormat, raw);
+    if (FAILED(hr)) return hr;
+    hr = UploadDDSRaw(device, raw, image);
+    if (FAILED(hr)) return hr;
+    if (metadata) *metadata = raw.metadata;
+    return S_OK;
+}
+
+HRESULT LoadFromDDSMemory(Device& device, const void* pSource, size_t size, DDS_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    return LoadFromDDSMemoryEx(device, pSource, size, flags, metadata, nullptr, image);
+}
+
+HRESULT LoadFromDDSFileEx(Device& device, const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob buf;
+    const HRESULT hr = ReadWholeFile(szFile, buf);
+    if (FAILED(hr)) return hr;
+    return LoadFromDDSMemoryEx(device, buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, ddPixelFormat, image);
+}
+
+HRESULT LoadFromDDSFile(Device& device, const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    return LoadFromDDSFileEx(device, szFile, flags, metadata, nullptr, image);
 }
 
 // ---- writing --------------------------------------------------------------------------------------------------------------
@@ -897,8 +851,12 @@ HRESULT EncodeDDSHeader(const TexMetadata& metadata, DDS_FLAGS ddsFlags, uint8_t
     return S_OK;
 }
 
-// SaveToDDSMemory (DirectXTexDDS.cpp:2403-2698)
-HRESULT SaveToDDSMemory(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, Blob& blob) noexcept
+namespace
+{
+// SaveToDDSMemory (DirectXTexDDS.cpp:2403-2698). device = nullptr: the images are host memory. Else their pixels are device pointers and the
+// payload comes down behind the header: 24-bit rows are packed on the device first, images at the file's pitches come down as they are
+// (one copy per run of images that lie back to back), any other one row by row.
+HRESULT SaveDDS(Device* device, const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, Blob& blob) noexcept
 {
     if (!images || !nimages) return E_INVALIDARG;
     size_t required = 0;
@@ -916,6 +874,7 @@ HRESULT SaveToDDSMemory(const Image* images, size_t nimages, const TexMetadata& 
         if (FAILED(hr)) return hr;
         required += sp[i];
     }
+    if (device && !*device) return E_POINTER;
     blob.Release();
     hr = blob.Initialize(required);
     if (FAILED(hr)) return hr;
@@ -942,21 +901,61 @@ HRESULT SaveToDDSMemory(const Image* images, size_t nimages, const TexMetadata& 
         return E_FAIL;
     }
     if (expected > nimages) { blob.Release(); return E_FAIL; }
+    if (device && use24bpp)
+    {
+        // every image's rows into one device buffer laid out like the file's payload, then one download at 3 bytes a texel
+        std::vector<dxtex_image> srcs;
+        std::vector<size_t> offsets;
+        try { srcs.resize(expected); offsets.resize(expected); } catch (...) { blob.Release(); return E_OUTOFMEMORY; }
+        size_t total = 0;
+        for (size_t i = 0; i < expected; ++i)
+        {
+            if (sp[i] > remaining - total) { blob.Release(); return E_FAIL; }
+            srcs[i] = dxtex_image{ images[i].width, images[i].height, int32_t(images[i].format), images[i].rowPitch, images[i].slicePitch, images[i].pixels };
+            offsets[i] = total; total += sp[i];
+        }
+        DeviceTemp temp(*device);
+        hr = dxtex_device_alloc(device->Get(), total, &temp.p);
+        if (SUCCEEDED(hr)) hr = dxtex_dds_pack24_device(device->Get(), srcs.data(), offsets.data(), rp.data(), expected, temp.p, total);
+        if (SUCCEEDED(hr)) hr = dxtex_memcpy_d2h(device->Get(), d, temp.p, total);          // returns when the rows have landed
+        if (FAILED(hr)) blob.Release();
+        return hr;
+    }
     for (size_t i = 0; i < expected; ++i)
     {
         const Image& im = images[i];
         if (sp[i] > remaining) { blob.Release(); return E_FAIL; }
-        if (use24bpp)
+        const bool same = im.rowPitch == rp[i] && im.slicePitch == sp[i];
+        if (device)
+        {
+            if (same)
+            {
+                // this image and those behind it that lie back to back on the device, in one copy
+                size_t run = sp[i], last = i;
+                while (last + 1 < expected && images[last + 1].rowPitch == rp[last + 1] && images[last + 1].slicePitch == sp[last + 1] &&
+                       images[last + 1].pixels == images[last].pixels + sp[last] && sp[last + 1] <= remaining - run) { ++last; run += sp[last]; }
+                hr = dxtex_memcpy_d2h_async(device->Get(), d, im.pixels, run);
+                d += run - sp[last]; remaining -= run - sp[last];
+                i = last;
+            }
+            else
+            {
+                const size_t lines = ComputeScanlines(metadata.format, im.height), n = std::min(im.rowPitch, rp[i]);
+                hr = dxtex_memcpy_rows_d2h_async(device->Get(), d, rp[i], im.pixels, im.rowPitch, n, lines);          // one strided copy
+            }
+            if (FAILED(hr)) { dxtex_ctx_synchronize(device->Get()); blob.Release(); return hr; }
+        }
+        else if (use24bpp)
         {
             // B8G8R8X8 rows lose their fourth byte
             for (size_t y = 0; y < im.height; ++y)
             {
                 const uint8_t* s = im.pixels + y * im.rowPitch;
                 uint8_t* o = d + y * rp[i];
-                for (size_t x = 0; x < im.width; ++x, s += 4, o += 3) { o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; }
+                for (size_t x = 0; x < im.width; ++x, s += 4, o += 3) dxtex::dds_store(o, dxtex::dds_pack24_texel(dxtex::dds_load(s, 4)), 3);
             }
         }
-        else if (im.rowPitch == rp[i] && im.slicePitch == sp[i]) std::memcpy(d, im.pixels, sp[i]);
+        else if (same) std::memcpy(d, im.pixels, sp[i]);
         else
         {
             const size_t lines = ComputeScanlines(metadata.format, im.height), n = std::min(im.rowPitch, rp[i]);
@@ -965,24 +964,16 @@ HRESULT SaveToDDSMemory(const Image* images, size_t nimages, const TexMetadata& 
         d += sp[i];
         remaining -= sp[i];
     }
+    if (device)
+    {
+        hr = dxtex_ctx_synchronize(device->Get());          // the blob is complete when this returns
+        if (FAILED(hr)) { blob.Release(); return hr; }
+    }
     return S_OK;
 }
 
-HRESULT SaveToDDSMemory(const Image& image, DDS_FLAGS flags, Blob& blob) noexcept
+HRESULT WriteBlobToFile(const Blob& blob, const char* szFile) noexcept
 {
-    // DirectXTex.inl:151-164
-    TexMetadata m;
-    m.width = image.width; m.height = image.height; m.depth = 1; m.arraySize = 1; m.mipLevels = 1;
-    m.format = image.format; m.dimension = TEX_DIMENSION_TEXTURE2D;
-    return SaveToDDSMemory(&image, 1, m, flags, blob);
-}
-
-HRESULT SaveToDDSFile(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept
-{
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToDDSMemory(images, nimages, metadata, flags, blob);
-    if (FAILED(hr)) return hr;
     FILE* f = std::fopen(szFile, "wb");
     if (!f) return E_FAIL;
     const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
@@ -991,11 +982,62 @@ HRESULT SaveToDDSFile(const Image* images, size_t nimages, const TexMetadata& me
     return S_OK;
 }
 
-HRESULT SaveToDDSFile(const Image& image, DDS_FLAGS flags, const char* szFile) noexcept
+TexMetadata MetadataOf(const Image& image) noexcept
 {
+    // DirectXTex.inl:151-164
     TexMetadata m;
     m.width = image.width; m.height = image.height; m.depth = 1; m.arraySize = 1; m.mipLevels = 1;
     m.format = image.format; m.dimension = TEX_DIMENSION_TEXTURE2D;
-    return SaveToDDSFile(&image, 1, m, flags, szFile);
+    return m;
+}
+}
+
+HRESULT SaveToDDSMemory(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, Blob& blob) noexcept
+{
+    return SaveDDS(nullptr, images, nimages, metadata, flags, blob);
+}
+
+HRESULT SaveToDDSMemory(const Image& image, DDS_FLAGS flags, Blob& blob) noexcept
+{
+    return SaveToDDSMemory(&image, 1, MetadataOf(image), flags, blob);
+}
+
+HRESULT SaveToDDSFile(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveToDDSMemory(images, nimages, metadata, flags, blob);
+    if (FAILED(hr)) return hr;
+    return WriteBlobToFile(blob, szFile);
+}
+
+HRESULT SaveToDDSFile(const Image& image, DDS_FLAGS flags, const char* szFile) noexcept
+{
+    return SaveToDDSFile(&image, 1, MetadataOf(image), flags, szFile);
+}
+
+// ---- writing, resident ----------------------------------------------------------------------------------------------------------------
+HRESULT SaveToDDSMemory(Device& device, const Image* deviceImages, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, Blob& blob) noexcept
+{
+    return SaveDDS(&device, deviceImages, nimages, metadata, flags, blob);
+}
+
+HRESULT SaveToDDSMemory(Device& device, const Image& deviceImage, DDS_FLAGS flags, Blob& blob) noexcept
+{
+    return SaveToDDSMemory(device, &deviceImage, 1, MetadataOf(deviceImage), flags, blob);
+}
+
+HRESULT SaveToDDSFile(Device& device, const Image* deviceImages, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveToDDSMemory(device, deviceImages, nimages, metadata, flags, blob);
+    if (FAILED(hr)) return hr;
+    return WriteBlobToFile(blob, szFile);
+}
+
+HRESULT SaveToDDSFile(Device& device, const Image& deviceImage, DDS_FLAGS flags, const char* szFile) noexcept
+{
+    return SaveToDDSFile(device, &deviceImage, 1, MetadataOf(deviceImage), flags, szFile);
 }
 } // namespace DirectXTexAMD

@@ -57,11 +57,17 @@ void Fill(AnalyzeData& r, const dxtex_image_stats& s) noexcept
 // ---- ComputeMSE -------------------------------------------------------------------------------------------------------------------------
 HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, float& mse, float* mseV, CMSE_FLAGS flags) noexcept
 {
+    return ComputeMSE(device, image1, 0, image2, 0, mse, mseV, flags);
+}
+
+HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, size_t index1, const DeviceScratchImage& image2, size_t index2, float& mse, float* mseV,
+                   CMSE_FLAGS flags) noexcept
+{
     if (!device) return E_POINTER;
     if (!Resident(device, image1) || !Resident(device, image2)) return E_INVALIDARG;
-    const Image* a = image1.GetImage(0, 0, 0);
-    const Image* b = image2.GetImage(0, 0, 0);
-    if (!a || !b) return E_POINTER;
+    if (index1 >= image1.GetImageCount() || index2 >= image2.GetImageCount()) return E_POINTER;
+    const Image* a = image1.GetImages() + index1;
+    const Image* b = image2.GetImages() + index2;
     if (a->width != b->width || a->height != b->height) return E_INVALIDARG;
     HRESULT hr = CheckFormat(a->format); if (FAILED(hr)) return hr;
     hr = CheckFormat(b->format); if (FAILED(hr)) return hr;
@@ -70,8 +76,8 @@ HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, const Devic
     const DeviceScratchImage* eb = nullptr;
     hr = Expanded(device, image1, t1, ea); if (FAILED(hr)) return hr;
     hr = Expanded(device, image2, t2, eb); if (FAILED(hr)) return hr;
-    a = ea->GetImage(0, 0, 0); b = eb->GetImage(0, 0, 0);
-    if (!a || !b) return E_POINTER;
+    if (index1 >= ea->GetImageCount() || index2 >= eb->GetImageCount()) return E_POINTER;
+    a = ea->GetImages() + index1; b = eb->GetImages() + index2;
     const dxtex_image va = View(*a), vb = View(*b);
     double v[4] = { 0, 0, 0, 0 };
     hr = dxtex_compute_mse_flags_device(device.Get(), &va, &vb, uint32_t(flags), v);

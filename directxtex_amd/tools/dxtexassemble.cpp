@@ -311,7 +311,8 @@ int Fail(const char* what, HRESULT hr)
 
 // an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
 // a .tga input likewise as the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
-struct Input { TexMetadata info; ScratchImage image; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; };
+// a .dds input as the file itself, parsed: its payload goes up as it is and the row conversions of a legacy file run on the device
+struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; };
 
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
 int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
@@ -328,8 +329,9 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         if (IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP)
         {
             if (!dds) { std::printf("\nERROR: Input must be a dds of a %s\n", o.command == CMD_ARRAY_STRIP ? "1D/2D array" : "cubemap"); return 1; }
-            hr = LoadFromDDSFile(file.c_str(), DDS_FLAGS_NONE, &in->info, in->image);
+            hr = LoadFromDDSFileRaw(file.c_str(), DDS_FLAGS_NONE, nullptr, in->dds);
             if (FAILED(hr)) return Fail(" FAILED", hr);
+            in->info = in->dds.metadata;
             if (o.command == CMD_ARRAY_STRIP)
             {
                 if (in->info.dimension == TEX_DIMENSION_TEXTURE3D || in->info.arraySize < 2 || in->info.IsCubemap()) { std::printf("\nERROR: Input must be a 1D/2D array\n"); return 1; }
@@ -339,8 +341,9 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         }
         else if (dds)
         {
-            hr = LoadFromDDSFile(file.c_str(), DDS_FLAGS_NONE, &in->info, in->image);
+            hr = LoadFromDDSFileRaw(file.c_str(), DDS_FLAGS_NONE, nullptr, in->dds);
             if (FAILED(hr)) return Fail(" FAILED", hr);
+            in->info = in->dds.metadata;
             if (in->info.IsVolumemap() || in->info.IsCubemap()) { std::printf("\nERROR: Can't assemble complex surfaces\n"); return 1; }
             if (in->info.mipLevels > 1 && !o.stripMips &&
                 (o.command == CMD_CUBE || o.command == CMD_VOLUME || o.command == CMD_ARRAY || o.command == CMD_CUBEARRAY || o.command == CMD_MERGE))
@@ -396,9 +399,9 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         DeviceScratchImage cur, next;
         Input& in = *inputs[index];
         HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : in.tga ? UploadTGARaw(dev, in.info, TGA_FLAGS_NONE, in.tgaRaw, cur)
-                                                                                              : cur.Upload(dev, in.image);
+                                                                                              : UploadDDSRaw(dev, in.dds, cur);
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        in.image.Release(); in.rgbe.Release(); in.tgaRaw.Release();
+        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
@@ -516,14 +519,8 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     }
     if (FAILED(hr)) return Fail("FAILED building result image", hr);
 
-    // an .hdr output comes back as the RGBE rows the resident saver makes on the device; everything else as it is
+    // an .hdr output comes back as the RGBE rows the resident saver makes on the device, a .dds as its payload straight behind the header
     const bool hdrOut = hasExt(o.output, ".hdr"), tgaOut = hasExt(o.output, ".tga");          // .tga: the file's rows, likewise
-    ScratchImage out;
-    if (!hdrOut && !tgaOut)
-    {
-        hr = result.Download(out);
-        if (FAILED(hr)) return Fail("FAILED building result image", hr);
-    }
     std::printf("\nWriting %s ", o.output.c_str());
     PrintInfo(result.GetMetadata());
     std::printf("\n");
@@ -532,7 +529,7 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     if (!o.overwrite && stat(o.output.c_str(), &st) == 0) { std::printf("\nERROR: Output file already exists, use -y to overwrite\n"); return 1; }
     if (hdrOut) hr = SaveToHDRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());
     else if (tgaOut) hr = SaveToTGAFile(dev, *result.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
-    else hr = SaveToDDSFile(out.GetImages(), out.GetImageCount(), out.GetMetadata(),
+    else hr = SaveToDDSFile(dev, result.GetImages(), result.GetImageCount(), result.GetMetadata(),
                             o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED", hr);
     return 0;

@@ -134,24 +134,6 @@ void FitPowerOf2(size_t origx, size_t origy, size_t& targetx, size_t& targety, s
     }
 }
 
-// mip level 0 of every array item / depth slice as a texture with one level (texconv.cpp:3324-3380), host images
-HRESULT TopLevels(const ScratchImage& in, ScratchImage& out)
-{
-    TexMetadata m = in.GetMetadata();
-    m.mipLevels = 1;
-    HRESULT hr = out.Initialize(m);
-    if (FAILED(hr)) return hr;
-    const bool volume = m.dimension == TEX_DIMENSION_TEXTURE3D;
-    for (size_t i = 0; i < (volume ? m.depth : m.arraySize); ++i)
-    {
-        const Image* s = volume ? in.GetImage(0, 0, i) : in.GetImage(0, i, 0);
-        const Image* d = volume ? out.GetImage(0, 0, i) : out.GetImage(0, i, 0);
-        if (!s || !d) return E_FAIL;
-        std::memcpy(d->pixels, s->pixels, d->slicePitch);
-    }
-    return S_OK;
-}
-
 int usage()
 {
     std::fprintf(stderr, "usage: dxtexconv [-w W] [-h H] [-pow2] [-fl LEVEL] [-m N] [-f FORMAT] [-if FILTER] [-wrap] [-mirror] [-srgb|-srgbi|-srgbo]\n"
@@ -350,7 +332,7 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     uint64_t up0 = 0, down0 = 0;
     GetTransferBytes(dev, up0, down0);
 
-    ScratchImage loaded; TexMetadata info;
+    TexMetadata info;
     auto hasExt = [](const std::string& f, const char* ext) { const size_t n = std::strlen(ext); return f.size() > n && !strcasecmp(f.c_str() + f.size() - n, ext); };
     // Radiance RGBE -> RGBA32F: the resident loader sends the file's texels up as the 4 bytes they are and makes the floats on the device
     DeviceScratchImage image;
@@ -358,14 +340,15 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     if (hdrIn) check("load", LoadFromHDRFile(dev, inFile.c_str(), &info, image));
     // TGA likewise: the file's 1 to 4 bytes a texel go up, the swizzle, the flips and the alpha rule run on the device
     else if (tgaIn) check("load", LoadFromTGAFile(dev, inFile.c_str(), TGA_FLAGS_NONE, &info, image));
-    else check("load", LoadFromDDSFile(inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, loaded));
+    // DDS likewise: the payload goes up at the size it has in the file - a native file straight into the image's memory, a legacy one through
+    // the row conversions on the device
+    else check("load", LoadFromDDSFile(dev, inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, image));
     std::printf("reading %s (%zux%zu", inFile.c_str(), info.width, info.height);
     if (info.dimension == TEX_DIMENSION_TEXTURE3D) std::printf("x%zu", info.depth);
     std::printf(", %zu mips, %zu items, format %u)\n", info.mipLevels, info.arraySize, unsigned(info.format));
     size_t tMips = (!o.mipLevels && info.mipLevels > 1) ? info.mipLevels : o.mipLevels;           // texconv.cpp:2270
 
-    // --- the one upload (an .hdr or .tga file's has happened: its texels as the file has them)
-    if (!hdrIn && !tgaIn) check("upload", image.Upload(dev, loaded));
+    // --- the one upload has happened: the file's texels as the file has them
     auto keep = [&](DeviceScratchImage& t)         // a step produced t: it becomes the image, metadata keeps its alpha mode
     {
         const uint32_t misc2 = info.miscFlags2;
@@ -381,9 +364,8 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     }
     const DXGI_FORMAT tformat = o.format ? DXGI_FORMAT(o.format) : info.format;
 
-    // --- decompress (texconv.cpp:2325-2480). The compressed original is kept (on the host, where it already is, and on the device for the
-    // alpha scan): if no step below changes the texels and the target is its format, it is written back as it is instead of being encoded again.
-    ScratchImage cimage;
+    // --- decompress (texconv.cpp:2325-2480). The compressed original is kept on the device: if no step below changes the texels and the
+    // target is its format, it is written back as it is instead of being encoded again.
     DeviceScratchImage dcimage;
     bool haveOriginal = false;
     if (IsCompressed(info.format))
@@ -403,10 +385,9 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         }
         DeviceScratchImage t;
         check("decompress", Decompress(dev, image, formatDecompress, t));
-        cimage = std::move(loaded); dcimage = std::move(image); haveOriginal = true;
+        dcimage = std::move(image); haveOriginal = true;
         keep(t);
     }
-    else loaded.Release();
 
     // --- undo premultiplied alpha
     if (o.demul && HasAlpha(info.format) && info.format != DXGI_FORMAT_A8_UNORM)
@@ -518,9 +499,6 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         if (haveOriginal && tMips == 1)
         {
             // only trimming mips off a compressed texture: its top level stays the encoder's original (:3378-3412)
-            ScratchImage c;
-            check("copy compressed to single level", TopLevels(cimage, c));
-            cimage = std::move(c);
             DeviceScratchImage dc;
             check("copy compressed to single level", CopyTopLevels(dev, dcimage, dc));
             dcimage = std::move(dc);
@@ -563,12 +541,12 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     bool handThrough = false;
     if (IsCompressed(tformat))
     {
-        if (haveOriginal && cimage.GetMetadata().format == tformat)
+        if (haveOriginal && dcimage.GetMetadata().format == tformat)
         {
             // nothing touched the texels and the input already has the target format: hand its blocks through (:3566-3574)
             handThrough = true;
             const uint32_t misc2 = info.miscFlags2;
-            info = cimage.GetMetadata(); info.miscFlags2 = misc2;
+            info = dcimage.GetMetadata(); info.miscFlags2 = misc2;
             image = std::move(dcimage);
         }
         else
@@ -596,23 +574,24 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         struct stat st;
         if (::stat(outFile.c_str(), &st) == 0) { std::printf("skipping %s: it exists (use -y to overwrite)\n", outFile.c_str()); return; }
     }
-    // --- the one download (blocks handed through are still on the host)
+    // --- the one download, by the resident writers: the payload comes down straight behind the file's header
     // -ft hdr: level 0 of the first item, like texconv's non-DDS codecs, comes back as RGBE rows the resident saver made on the device
     // -ft tga likewise: the file's rows (-tga20: and the TGA 2.0 extension area around them)
-    const bool hdrResident = o.hdrOut && !handThrough, tgaResident = o.tgaOut && !handThrough;
-    ScratchImage result;
-    if (handThrough) result = std::move(cimage);
-    else if (hdrResident) check("save", SaveToHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
-    else if (tgaResident) check("save", SaveToTGAFile(dev, *image.GetImage(0, 0, 0), TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));
-    else check("download", image.Download(result));
-    image.Release();
     uint32_t ddsFlags = DDS_FLAGS_NONE;
     if (o.dx10) ddsFlags |= DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2;
     else if (o.dx9) ddsFlags |= DDS_FLAGS_FORCE_DX9_LEGACY;
-    if (hdrResident || tgaResident) { }
-    else if (o.hdrOut) check("save", SaveToHDRFile(result.GetImages()[0], outFile.c_str()));                // blocks handed through: the host codec's answer
-    else if (o.tgaOut) check("save", SaveToTGAFile(result.GetImages()[0], TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));      // -tga20: with the TGA 2.0 extension area
-    else check("save", SaveToDDSFile(result.GetImages(), result.GetImageCount(), info, DDS_FLAGS(ddsFlags), outFile.c_str()));
+    if ((o.hdrOut || o.tgaOut) && handThrough)
+    {
+        // blocks handed through: the host codec's answer
+        ScratchImage result;
+        check("download", image.Download(result));
+        if (o.hdrOut) check("save", SaveToHDRFile(result.GetImages()[0], outFile.c_str()));
+        else check("save", SaveToTGAFile(result.GetImages()[0], TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));      // -tga20: with the TGA 2.0 extension area
+    }
+    else if (o.hdrOut) check("save", SaveToHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
+    else if (o.tgaOut) check("save", SaveToTGAFile(dev, *image.GetImage(0, 0, 0), TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));
+    else check("save", SaveToDDSFile(dev, image.GetImages(), image.GetImageCount(), info, DDS_FLAGS(ddsFlags), outFile.c_str()));
+    image.Release();
     std::printf("writing %s (%zux%zu", outFile.c_str(), info.width, info.height);
     if (info.dimension == TEX_DIMENSION_TEXTURE3D) std::printf("x%zu", info.depth);
     std::printf(", %zu mips, %zu items, format %u)\n", info.mipLevels, info.arraySize, unsigned(info.format));

@@ -10,6 +10,7 @@
 //   -t <float>    diff: threshold (default 0.25)                        -if <filter>  image filter for diff's conversions
 //   -o <file>     diff: output file, required (there is no BMP writer, texdiag's default)   -y  overwrite   -l  lower-case output name
 //   -dword -badtails -permissive -ignoremips -xlum   DDS reader flags    -nologo    -gpu <n>
+//   -timing       a last line with the bytes moved between host and device, as dxtexconv -timing counts them
 //   Not here: dumpbc (prints one block on the CPU) and dumpdds / info (dxtexconv -info).
 #include "../host/DirectXTexAMD.h"
 
@@ -71,7 +72,7 @@ struct Options
     std::vector<std::string> files;
     uint32_t format = DXGI_FORMAT_B8G8R8A8_UNORM, filter = TEX_FILTER_DEFAULT, ddsRead = DDS_FLAGS_NONE, diffColor = 0;
     float threshold = 0.25f;
-    bool overwrite = false, lower = false, nologo = false;
+    bool overwrite = false, lower = false, nologo = false, timing = false;
     int gpu = 0;
 };
 
@@ -80,7 +81,7 @@ int usage()
     std::fprintf(stderr, "usage: dxtexdiag analyze [options] <files>\n"
                          "       dxtexdiag compare [options] <file1> <file2>\n"
                          "       dxtexdiag diff [options] <file1> <file2> -o <out.dds | out.tga | out.hdr>\n"
-                         "options: -f <format> -if <filter> -c <hex colour> -t <threshold> -o <file> -y -l -nologo -gpu <n>\n"
+                         "options: -f <format> -if <filter> -c <hex colour> -t <threshold> -o <file> -y -l -nologo -timing -gpu <n>\n"
                          "         -dword -badtails -permissive -ignoremips -xlum\n");
     return 1;
 }
@@ -137,6 +138,7 @@ bool Parse(int argc, char** argv, Options& o)
         else if (a == "-y" || a == "--overwrite") o.overwrite = true;
         else if (a == "-l" || a == "--to-lowercase") o.lower = true;
         else if (a == "-nologo") o.nologo = true;
+        else if (a == "-timing") o.timing = true;
         else if (a == "-dword") o.ddsRead |= DDS_FLAGS_LEGACY_DWORD;
         else if (a == "-badtails") o.ddsRead |= DDS_FLAGS_BAD_DXTN_TAILS;
         else if (a == "-permissive") o.ddsRead |= DDS_FLAGS_PERMISSIVE;
@@ -161,46 +163,44 @@ bool Parse(int argc, char** argv, Options& o)
     return true;
 }
 
-// the host loader of all three commands (.tga files go through the resident loader instead: Side, RunAnalyze); a planar file becomes its single-plane form on the device, as texdiag's loader makes it (texdiag.cpp:3959-3972)
-HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata& info, ScratchImage& image)
+// Every file goes up once, at the bytes a texel it has on disk, and becomes the texture on the device: an .hdr file as its RGBE rows, a .tga
+// and a .dds as the file's own texels (the resident loaders). A planar file becomes its single-plane form there, as texdiag's loader makes
+// it (texdiag.cpp:3959-3972).
+HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata& info, DeviceScratchImage& resident)
 {
-    if (hasExt(file, ".hdr")) return LoadFromHDRFile(file.c_str(), &info, image);
-    HRESULT hr = LoadFromDDSFile(file.c_str(), DDS_FLAGS(o.ddsRead), &info, image);
+    HRESULT hr = hasExt(file, ".hdr") ? LoadFromHDRFile(dev, file.c_str(), &info, resident)
+               : hasExt(file, ".tga") ? LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident)
+                                      : LoadFromDDSFile(dev, file.c_str(), DDS_FLAGS(o.ddsRead), &info, resident);
     if (FAILED(hr) || !IsPlanar(info.format)) return hr;
-    ScratchImage single;
-    hr = ConvertToSinglePlane(dev, image.GetImages(), image.GetImageCount(), info, single);
+    DeviceScratchImage single;
+    hr = ConvertToSinglePlane(dev, resident, single);
     if (FAILED(hr)) return hr;
-    info.format = single.GetMetadata().format;
-    image = std::move(single);
+    resident = std::move(single);
+    info.format = resident.GetMetadata().format;
     return S_OK;
 }
 
-// One file of compare / diff. A .tga is loaded resident: its texels go up as the file has them and become the image on the device. Every
-// other file is loaded on the host, and its first image goes up when the command turns out to work on first images.
+// One file of compare / diff, resident. ComputeMSE and Difference take image 0 of it; compare's loop over every image takes the others.
 struct Side
 {
     TexMetadata info;
-    ScratchImage host;
     DeviceScratchImage resident;
     size_t count = 0;          // images in the file
 
     HRESULT Open(Device& dev, const Options& o, const std::string& file)
     {
-        if (hasExt(file, ".tga")) { count = 1; return LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident); }
-        const HRESULT hr = Load(dev, o, file, info, host);
-        count = host.GetImageCount();
+        const HRESULT hr = Load(dev, o, file, info, resident);
+        count = resident.GetImageCount();
         return hr;
     }
-    // the first image on the device: what the host forms of ComputeMSE and Difference upload
-    HRESULT First(Device& dev)
+    // for compare's loop: a block-compressed texture is decompressed once, not once per pair (ComputeMSE would, to the same floats)
+    HRESULT Expand(Device& dev)
     {
-        if (resident.GetImageCount()) return S_OK;
-        const Image* first = host.GetImage(0, 0, 0);
-        if (!first) return E_POINTER;
-        TexMetadata one;
-        one.width = first->width; one.height = first->height; one.depth = one.arraySize = one.mipLevels = 1;
-        one.format = first->format; one.dimension = TEX_DIMENSION_TEXTURE2D;
-        return resident.Upload(dev, first, 1, one);
+        if (!IsCompressed(resident.GetMetadata().format)) return S_OK;
+        DeviceScratchImage floats;
+        const HRESULT hr = Decompress(dev, resident, DXGI_FORMAT_R32G32B32A32_FLOAT, floats);
+        if (SUCCEEDED(hr)) resident = std::move(floats);
+        return hr;
     }
 };
 
@@ -254,17 +254,11 @@ int RunAnalyze(Device& dev, const Options& o)
     for (const std::string& file : o.files)
     {
         TexMetadata info;
-        ScratchImage image;
-        // the whole file goes up once - an .hdr file as its RGBE rows, which the resident loader turns into floats on the device; every image
-        // is analysed there, the figures come back in one copy
+        // the whole file goes up once; every image is analysed on the device, the figures come back in one copy
         DeviceScratchImage resident;
-        const bool hdr = hasExt(file, ".hdr"), tga = hasExt(file, ".tga");          // .tga likewise: the file's own bytes a texel
-        HRESULT hr = hdr ? LoadFromHDRFile(dev, file.c_str(), &info, resident) : tga ? LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident)
-                                                                                   : Load(dev, o, file, info, image);
+        HRESULT hr = Load(dev, o, file, info, resident);
         if (FAILED(hr)) return Fail((" FAILED loading " + file).c_str(), hr);
         std::printf("%s\n", file.c_str());
-        if (!hdr && !tga) hr = resident.Upload(dev, image);
-        if (FAILED(hr)) return Fail("ERROR: Failed uploading the images", hr);
         const size_t n = resident.GetImageCount();
         std::vector<AnalyzeData> data(n);
         std::vector<AnalyzeBCData> bc(IsCompressed(info.format) ? n : 0);
@@ -318,31 +312,29 @@ int RunCompare(Device& dev, const Options& o)
     hr = side2.Open(dev, o, o.files[1]);
     if (FAILED(hr)) return Fail((" FAILED loading " + o.files[1]).c_str(), hr);
     const TexMetadata& info1 = side1.info; const TexMetadata& info2 = side2.info;
-    const ScratchImage& image1 = side1.host; const ScratchImage& image2 = side2.host;
     if (info1.width != info2.width || info1.height != info2.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
     if ((info1.depth == 1 && info1.arraySize == 1 && info1.mipLevels == 1) || info1.depth != info2.depth || info1.arraySize != info2.arraySize ||
         info1.mipLevels != info2.mipLevels || side1.count != side2.count)
     {
-        // first images (a .tga has no other, so this is where one ends up): on the device, where a .tga already is
+        // first images (a .tga has no other, so this is where one ends up)
         if (side1.count > 1 || side2.count > 1) std::printf("WARNING: ignoring all images but first one in each file\n");
         float mse = 0, mseV[4] = {};
-        hr = side1.First(dev);
-        if (SUCCEEDED(hr)) hr = side2.First(dev);
-        if (SUCCEEDED(hr)) hr = ComputeMSE(dev, side1.resident, side2.resident, mse, mseV, CMSE_DEFAULT);
+        hr = ComputeMSE(dev, side1.resident, side2.resident, mse, mseV, CMSE_DEFAULT);
         if (FAILED(hr)) return Fail("Failed comparing images", hr);
         std::printf("Result: %f (%f %f %f %f) PSNR %f dB\n", mse, mseV[0], mseV[1], mseV[2], mseV[3], Psnr(mseV));
         return 0;
     }
+    hr = side1.Expand(dev);
+    if (SUCCEEDED(hr)) hr = side2.Expand(dev);
+    if (FAILED(hr)) return Fail("Failed comparing images", hr);
     float minMse = FLT_MAX, minV[4] = { FLT_MAX, FLT_MAX, FLT_MAX, FLT_MAX }, maxMse = -FLT_MAX, maxV[4] = { -FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX };
     double sumMse = 0, sumV[4] = { 0, 0, 0, 0 };
     size_t total = 0;
     const auto pair = [&](size_t a, size_t b, size_t mip, size_t item, size_t slice) -> bool
     {
-        const Image* i1 = image1.GetImage(mip, item, slice);
-        const Image* i2 = image2.GetImage(mip, item, slice);
-        if (!i1 || !i2) { std::printf("ERROR: Unexpected mismatch at [%3zu,%3zu]\n", a, b); return false; }
+        if (!side1.resident.GetImage(mip, item, slice) || !side2.resident.GetImage(mip, item, slice)) { std::printf("ERROR: Unexpected mismatch at [%3zu,%3zu]\n", a, b); return false; }
         float mse = 0, mseV[4] = {};
-        const HRESULT h = ComputeMSE(dev, *i1, *i2, mse, mseV, CMSE_DEFAULT);
+        const HRESULT h = ComputeMSE(dev, side1.resident, info1.ComputeIndex(mip, item, slice), side2.resident, info2.ComputeIndex(mip, item, slice), mse, mseV, CMSE_DEFAULT);
         if (FAILED(h)) { std::printf("Failed comparing images at [%3zu,%3zu] (%08X)\n", a, b, static_cast<unsigned int>(h)); return false; }
         minMse = std::min(minMse, mse); maxMse = std::max(maxMse, mse); sumMse += double(mse);
         for (int c = 0; c < 4; ++c) { minV[c] = std::min(minV[c], mseV[c]); maxV[c] = std::max(maxV[c], mseV[c]); sumV[c] += double(mseV[c]); }
@@ -384,16 +376,15 @@ int RunDiff(Device& dev, const Options& o)
     if (side1.info.width != side2.info.width || side1.info.height != side2.info.height) { std::printf("ERROR: Can only compare images of the same width & height\n"); return 1; }
     if (side1.count > 1 || side2.count > 1) std::printf("WARNING: ignoring all images but first one in each file\n");
     DeviceScratchImage map;
-    hr = side1.First(dev);
-    if (SUCCEEDED(hr)) hr = side2.First(dev);
-    if (SUCCEEDED(hr)) hr = Difference(dev, side1.resident, side2.resident, TEX_FILTER_FLAGS(o.filter), DXGI_FORMAT(o.format), o.diffColor, o.threshold, map);
+    hr = Difference(dev, side1.resident, side2.resident, TEX_FILTER_FLAGS(o.filter), DXGI_FORMAT(o.format), o.diffColor, o.threshold, map);
     if (FAILED(hr)) return Fail("Failed diffing images", hr);
-    // a .tga comes back as the file's rows the resident saver makes on the device; the other two as the image, for the host codecs
-    if (hasExt(o.output, ".tga"))
+    // a .tga comes back as the file's rows the resident saver makes on the device, a .dds straight behind its header; an .hdr as the image,
+    // for the host codec
+    if (!hasExt(o.output, ".hdr"))
     {
         const Image* out = map.GetImage(0, 0, 0);
         if (!out) return Fail("Failed diffing images", E_POINTER);
-        hr = SaveToTGAFile(dev, *out, TGA_FLAGS_NONE, o.output.c_str());
+        hr = hasExt(o.output, ".tga") ? SaveToTGAFile(dev, *out, TGA_FLAGS_NONE, o.output.c_str()) : SaveToDDSFile(dev, *out, DDS_FLAGS_NONE, o.output.c_str());
     }
     else
     {
@@ -402,8 +393,7 @@ int RunDiff(Device& dev, const Options& o)
         if (FAILED(hr)) return Fail("Failed diffing images", hr);
         const Image* out = diff.GetImage(0, 0, 0);
         if (!out) return Fail("Failed diffing images", E_POINTER);
-        if (hasExt(o.output, ".hdr")) hr = SaveToHDRFile(*out, o.output.c_str());
-        else hr = SaveToDDSFile(*out, DDS_FLAGS_NONE, o.output.c_str());
+        hr = SaveToHDRFile(*out, o.output.c_str());
     }
     if (FAILED(hr)) return Fail(" FAILED writing the difference", hr);
     std::printf("Difference %s\n", o.output.c_str());
@@ -419,7 +409,12 @@ int main(int argc, char** argv)
     Device dev;
     const HRESULT hr = dev.Create(o.gpu);
     if (FAILED(hr)) { std::fprintf(stderr, "no usable gfx950 device %d (%08X): this tool has no CPU path\n", o.gpu, static_cast<unsigned int>(hr)); return 1; }
-    if (o.command == "analyze") return RunAnalyze(dev, o);
-    if (o.command == "compare") return RunCompare(dev, o);
-    return RunDiff(dev, o);
+    const int rc = o.command == "analyze" ? RunAnalyze(dev, o) : o.command == "compare" ? RunCompare(dev, o) : RunDiff(dev, o);
+    if (o.timing)
+    {
+        uint64_t up = 0, down = 0;
+        GetTransferBytes(dev, up, down);
+        std::printf("  host -> device %llu bytes, device -> host %llu bytes\n", (unsigned long long)up, (unsigned long long)down);
+    }
+    return rc;
 }

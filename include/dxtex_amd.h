@@ -35,6 +35,8 @@
  *   CopyPixels / UncompressPixels' texel half, DirectXTexTGA.cpp:396-1180;     dxtex_tga_unpack / dxtex_tga_pack
  *     Copy24bppScanline / the swizzle of         :1288, :2249-2330
  *     SaveToTGAMemory
+ *   CopyImage's row conversions, the 24-bit    DirectXTexDDS.cpp:1518-1808     dxtex_dds_unpack / dxtex_dds_pack24
+ *     rows of SaveToDDSMemory
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -346,6 +348,67 @@ dxtex_hresult dxtex_tga_unpack_device(dxtex_ctx* ctx, const void* texels, size_t
                                       const dxtex_image* dst, uint32_t* opaqueDevice);
 dxtex_hresult dxtex_tga_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes);
 
+/* DDS (.dds) texels, the per-texel half of the codec (header, refusals and size checks are byte-serial and stay with the caller). One call
+ * takes every image of a texture - array items, mip levels, depth slices. The file side is the payload as it is in the file: image i's
+ * rows start srcOffsets[i] bytes into it and lie srcRowPitches[i] bytes apart (the file's pitch rule, DDS_FLAGS_LEGACY_DWORD and the
+ * 8 / 16 / 24 bpp rules included: they only change these numbers). DDS_FLAGS_BAD_DXTN_TAILS is an offset too: a level smaller than a block
+ * points at the last stored level's bytes.
+ *   unpack   payload -> dsts[i], each through its own pitch; all of one format (the conversions of CopyImage, DirectXTexDDS.cpp:1518-1808).
+ *            `opaque` forces alpha (the reader's CONV_FLAGS_NOALPHA) where the op carries one.
+ *              op                    file bytes  dsts' format                 texel
+ *              DXTEX_DDS_ROW_COPY    any         any the library sizes        the bytes, row by row (block rows of a compressed image, every
+ *                                                                             plane's rows of a planar one); opaque: the alpha of the 32:32:32:32,
+ *                                                                             16:16:16:16, 10:10:10:2, 8:8:8:8, 5:5:5:1 / 4:4:4:4 and A8 classes is set
+ *              DXTEX_DDS_ROW_SWIZZLE 4           R8G8B8A8 / B8G8R8A8 / B8G8R8X8 families   red and blue trade places
+ *                                                R10G10B10A2 family           the outer 10-bit fields trade places
+ *                                                YUY2                         UYVY -> YUY2
+ *              _565 _5551 _4444 _ABGR4 _8332 _A8L8 _L6V5U5   2   R8G8B8A8_UNORM   the legacy expansions (565 with the reference's green quirk)
+ *              _888                  3           R8G8B8A8_UNORM               B, G, R -> R, G, B, 255
+ *              _332                  1           R8G8B8A8_UNORM, B5G6R5_UNORM
+ *              _44                   1           R8G8B8A8_UNORM, B4G4R4A4_UNORM
+ *              _L8                   1           R8G8B8A8_UNORM
+ *              _P8                   1           R8G8B8A8_UNORM               palette[index]; `palette` = 256 words in host memory, read before
+ *              _A8P8                 2           R8G8B8A8_UNORM               the call returns; A8P8 ORs the texel's alpha onto the entry's
+ *              _L16                  2           R16G16B16A16_UNORM
+ *              _L8U8V8               4           R8G8B8A8_UNORM
+ *              _WUV10                4           R10G10B10A2_UNORM
+ *   pack24   B8G8R8X8_UNORM images -> the writer's 24-bit rows (DDS_FLAGS_FORCE_24BPP_RGB): image i's rows go dstOffsets[i] bytes into `out`,
+ *            dstRowPitches[i] apart, 3 bytes a texel. Bytes of `out` outside those rows are not written.
+ * HRESULTs, in this order: E_POINTER for a null payload / output, image array, offsets, pitches or pixels; E_INVALIDARG for zero images, an
+ * unknown op, a palette that is missing or unwanted; NOT_SUPPORTED for an (op, format) pair outside the table (pack24: any format but
+ * B8G8R8X8_UNORM); E_INVALIDARG for images of different formats, a destination too small for its rows (rowPitch below width x texel), a
+ * file pitch below the row, rows that reach past payloadBytes / outBytes, or a file side that overlaps the pixels. Nothing is written on
+ * any failure. An image of zero width or height is skipped. Row padding of an image is never written. */
+#define DXTEX_DDS_ROW_COPY     0u
+#define DXTEX_DDS_ROW_SWIZZLE  1u
+#define DXTEX_DDS_ROW_565      2u
+#define DXTEX_DDS_ROW_5551     3u
+#define DXTEX_DDS_ROW_4444     4u
+#define DXTEX_DDS_ROW_ABGR4    5u
+#define DXTEX_DDS_ROW_888      6u
+#define DXTEX_DDS_ROW_332      7u
+#define DXTEX_DDS_ROW_8332     8u
+#define DXTEX_DDS_ROW_P8       9u
+#define DXTEX_DDS_ROW_A8P8     10u
+#define DXTEX_DDS_ROW_44       11u
+#define DXTEX_DDS_ROW_L8       12u
+#define DXTEX_DDS_ROW_L16      13u
+#define DXTEX_DDS_ROW_A8L8     14u
+#define DXTEX_DDS_ROW_L6V5U5   15u
+#define DXTEX_DDS_ROW_L8U8V8   16u
+#define DXTEX_DDS_ROW_WUV10    17u
+#define DXTEX_DDS_ROW_OPS      18u
+/* host pointers, through the context's staging: the payload goes up as it is, each image's rows come down; returns when they have landed */
+dxtex_hresult dxtex_dds_unpack(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
+                               const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count);
+dxtex_hresult dxtex_dds_pack24(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes);
+/* device pointers (the palette and the three arrays stay host pointers): asynchronous on the context's stream, 32 images to a launch. The
+ * payload may start at any byte; an image whose rows are dword-aligned on the file side and 16-byte aligned on the image side (see
+ * csrc/dds.hip for the exact rule) takes the wide route. */
+dxtex_hresult dxtex_dds_unpack_device(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
+                                      const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count);
+dxtex_hresult dxtex_dds_pack24_device(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes);
+
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 
@@ -524,6 +587,9 @@ dxtex_hresult dxtex_copy_rows_device(dxtex_ctx* ctx, void* dst, size_t dstPitch,
  * buffer must stay valid until dxtex_ctx_synchronize. */
 dxtex_hresult dxtex_memcpy_h2d_async(dxtex_ctx* ctx, void* dst, const void* src, size_t bytes);
 dxtex_hresult dxtex_memcpy_d2h_async(dxtex_ctx* ctx, void* dst, const void* src, size_t bytes);
+/* `rows` rows of `rowBytes` bytes from a pitched device image into pitched host memory: ONE strided copy on the stream (a plain one where
+ * both pitches are the row), counted by dxtex_ctx_transfer_bytes as rowBytes * rows. E_INVALIDARG for a row wider than a pitch. */
+dxtex_hresult dxtex_memcpy_rows_d2h_async(dxtex_ctx* ctx, void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t rowBytes, size_t rows);
 /* Page-locked host memory for the two ends of the pipeline. */
 dxtex_hresult dxtex_host_alloc(dxtex_ctx* ctx, size_t bytes, void** out);
 dxtex_hresult dxtex_host_free(dxtex_ctx* ctx, void* p);

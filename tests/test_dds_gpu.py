@@ -1,0 +1,430 @@
+"""DDS texels on the GPU (dxtex_dds_unpack / dxtex_dds_pack24 and their _device forms) against the reference's .dds reader and writer
+(oracle): pixels and file rows byte for byte on both routes of each kernel, asserted by profile mark; batches of images; the broken
+DXTn tails; every HRESULT with nothing written. The files, and the op the reader picks for each, are test_dds_texel_cpu.py's CASES."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+
+import directxtex_amd as dx
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from test_dds_legacy_cpu import four, header  # noqa: E402
+from test_dds_texel_cpu import (A8, BAD_DXTN_TAILS, BGRX8, CASES, FILE_BYTES, IMAGE_BYTES, LEGACY_DWORD, R10A2, RGBA8, RGBA16, RGBA32F, ROW_A8P8,  # noqa: E402
+                                ROW_COPY, ROW_L8U8V8, ROW_P8, ROW_888, ROW_SWIZZLE, ROW_WUV10, YUY2, dds_file, forced_alpha, palette_words)
+
+pytestmark = pytest.mark.gpu
+
+E_FAIL, E_INVALIDARG, E_POINTER = 0x80004005 - (1 << 32), 0x80070057 - (1 << 32), 0x80004003 - (1 << 32)
+E_NOT_SUPPORTED = 0x80070032 - (1 << 32)
+FILL = 0xA5
+# where a group of four, a wave and a workgroup each have a tail, and where three-byte rows fall on and off a dword
+WIDTHS, HEIGHTS = (1, 3, 4, 5, 63, 64, 65, 257), (1, 2, 5)
+BASES, PITCH_PADS = (0, 1), (0, 4, 3)
+CP_LEGACY_DWORD, CP_BAD_DXTN_TAILS, CP_24BPP, CP_16BPP, CP_8BPP = 0x1, 0x1000, 0x10000, 0x20000, 0x40000
+OP_NAMES = ("copy", "swizzle", "565", "5551", "4444", "abgr4", "888", "332", "8332", "p8", "a8p8", "44", "l8", "l16", "a8l8", "l6v5u5", "l8u8v8", "wuv10")
+BATCH = 32          # images to a launch (csrc/dds.hip)
+SEEN = set()        # every profile mark the unpack tests met
+SEEN_OPAQUE = set() # (case, route) of every forced-alpha copy
+# ROW_COPY with the opaque flag on the alpha classes no .dds file reaches (the C ABI takes them): one format of each. name -> (op, opaque,
+# format); the expectation is the reference's rule as test_dds_texel_cpu.forced_alpha states it, the rows' pitches the reference's own.
+CLASSES = {"copy_32x4_opaque": (ROW_COPY, True, RGBA32F), "copy_16x4_opaque": (ROW_COPY, True, RGBA16), "copy_1010102_opaque": (ROW_COPY, True, R10A2),
+           "copy_a8_opaque": (ROW_COPY, True, A8)}
+
+
+def _geometry(name):
+    """(op, opaque, result format, bytes of a file texel, bytes of an image texel, the CP_FLAGS of the file's pitch rule)"""
+    op, opaque, fmt = CLASSES[name] if name in CLASSES else CASES[name][3:]
+    D = IMAGE_BYTES[fmt]
+    B = FILE_BYTES.get(op, D)
+    expands = op not in (ROW_COPY, ROW_SWIZZLE, ROW_L8U8V8, ROW_WUV10)
+    return op, opaque, fmt, B, D, ({1: CP_8BPP, 2: CP_16BPP, 3: CP_24BPP}[B] if expands else 0)
+
+
+def _words(fmt, w):
+    return (w + 1) // 2 if fmt == YUY2 else w          # a YUY2 word holds two texels
+
+
+def _layout(oracle, fmt, cp, w, h, depth=1, items=1, mips=1):
+    """The images of a texture in file order, as CopyImage lays them out: [(width, height, offset, row pitch)], total bytes."""
+    images, total = [], 0
+    for _ in range(items):
+        lw, lh, ld = w, h, depth
+        for _ in range(mips):
+            hr, rp, sp, _ = oracle.ref_compute_pitch(fmt, lw, lh, cp)
+            assert hr == 0
+            for _ in range(ld):
+                images.append((lw, lh, total, rp))
+                total += sp
+            lw, lh, ld = max(1, lw >> 1), max(1, lh >> 1), max(1, ld >> 1)
+    return images, total
+
+
+class Arena:
+    """Two device allocations reused by every case of a test: the payload's and the images'."""
+    def __init__(self, ctx, payload_bytes, image_bytes):
+        self.ctx, self.sn, self.dn = ctx, payload_bytes + 64, image_bytes + 64
+        self.s, self.d = ctx.device_alloc(self.sn), ctx.device_alloc(self.dn)
+
+    def close(self):
+        self.ctx.device_free(self.s)
+        self.ctx.device_free(self.d)
+
+
+@pytest.fixture
+def arena(ctx):
+    a = Arena(ctx, 1 << 15, 1 << 15)          # 257 x 5 texels of 16 bytes
+    yield a
+    a.close()
+
+
+def _expect_wide(op, B, D, row_words, rows, s_ptr, file_pitch, d_ptr, pitch):
+    """csrc/dds.hip's rule, restated"""
+    if op == ROW_COPY:
+        row_bytes = row_words * D
+        if file_pitch == row_bytes == pitch:          # rows back to back on both sides are one row
+            row_bytes *= rows
+        return row_bytes % 16 == 0 and all(v % 16 == 0 for v in (s_ptr, file_pitch, d_ptr, pitch))
+    fa, ia = (16 if B == 4 else 4), min(4 * D, 16)
+    return row_words % 4 == 0 and s_ptr % fa == 0 and file_pitch % fa == 0 and d_ptr % ia == 0 and pitch % ia == 0
+
+
+def _run_unpack(ctx, arena, name, images, payload, base, pad):
+    """Queues one dds_unpack_device over `images` [(w, h, offset, file pitch)] with the payload at arena.s + base and image i at its own
+    256-aligned place with `pad` bytes of row padding. -> ([rows of image i as (h, row bytes)], {mark: launches}, expected marks)."""
+    op, opaque, fmt, B, D, _ = _geometry(name)
+    src = np.full(arena.sn, FILL, np.uint8)
+    src[base:base + payload.size] = payload
+    ctx.upload(arena.s, src, sync=True)
+    ctx.upload(arena.d, np.full(arena.dn, FILL, np.uint8), sync=True)
+    dsts, places, at, expected = [], [], 0, {}
+    for (w, h, offset, file_pitch) in images:
+        row_bytes = _words(fmt, w) * D
+        pitch = row_bytes + pad
+        dsts.append(dx.device_image(arena.d + at, w, h, fmt, pitch, pitch * h))
+        places.append((at, pitch, row_bytes, h))
+        wide = _expect_wide(op, B, D, _words(fmt, w), h, arena.s + base + offset, file_pitch, arena.d + at, pitch)
+        mark = f"dds_unpack<{OP_NAMES[op]},{'wide' if wide else 'narrow'}>"
+        expected[mark] = expected.get(mark, 0) + 1
+        at = (at + pitch * h + 255) & ~255
+    assert at <= arena.dn and base + payload.size <= arena.sn
+    ctx.profile_begin()
+    ctx.dds_unpack_device(arena.s + base, payload.size, op, dsts, [i[2] for i in images], [i[3] for i in images], opaque,
+                          palette_words() if op in (ROW_P8, ROW_A8P8) else None)
+    prof = {k: v[1] for k, v in ctx.profile_end().items() if k.startswith("dds_")}
+    got, back = np.zeros(arena.dn, np.uint8), np.zeros(arena.sn, np.uint8)
+    ctx.download(got, arena.d, sync=True)
+    ctx.download(back, arena.s, sync=True)
+    assert np.array_equal(back, src), "the payload's allocation changed"
+    written = np.zeros(arena.dn, bool)
+    out = []
+    for (p, pitch, row_bytes, h) in places:
+        m = got[p:p + pitch * h].reshape(h, pitch)
+        out.append(m[:, :row_bytes])
+        written[p:p + pitch * h].reshape(h, pitch)[:, :row_bytes] = True
+    assert (got[~written] == FILL).all(), "bytes outside the rows were written"
+    SEEN.update(prof)
+    return out, prof, {k: (v + BATCH - 1) // BATCH for k, v in expected.items()}
+
+
+_reference = {}
+
+
+def _ref(oracle, name, w, h, legacy):
+    """(the file's payload, its row pitch, the reference loader's rows (h, row bytes)); computed once per case."""
+    key = (name, w, h, legacy)
+    if key not in _reference:
+        op, opaque, fmt, B, D, cp = _geometry(name)
+        (img,), total = _layout(oracle, fmt, cp | (CP_LEGACY_DWORD if legacy else 0), w, h)
+        payload = np.random.default_rng(w * 131 + h * 7 + B + len(name)).integers(0, 256, total, dtype=np.uint8)
+        if name in CLASSES:
+            _reference[key] = (payload, img[3], np.stack([forced_alpha(row[:w * D], fmt) for row in payload.reshape(h, img[3])]))
+            return _reference[key]
+        hr, meta, px = oracle.ref_load_dds_ex(np.frombuffer(dds_file(name, w, h, payload.tobytes()), np.uint8), CASES[name][2] | (LEGACY_DWORD if legacy else 0))
+        assert hr == 0 and (meta["width"], meta["height"], meta["format"]) == (w, h, fmt), (name, hex(hr), meta)
+        _reference[key] = (payload, img[3], px.reshape(h, -1))
+    return _reference[key]
+
+
+@pytest.mark.parametrize("name", list(CASES) + list(CLASSES))
+def test_unpack_matches_the_reference_reader(ctx, oracle, arena, name):
+    """Every size, with and without LEGACY_DWORD pitches, the payload at an aligned and an odd base, three destination paddings: pixels,
+    the bytes around them and the route's profile mark. The forced-alpha copies of CLASSES have no file: their rows are checked against
+    the reference's rule in numpy."""
+    for w in WIDTHS:
+        for h in HEIGHTS:
+            for legacy in (False, True):
+                payload, file_pitch, want = _ref(oracle, name, w, h, legacy)
+                for base in BASES:
+                    for pad in PITCH_PADS:
+                        (got,), prof, expected = _run_unpack(ctx, arena, name, [(w, h, 0, file_pitch)], payload, base, pad)
+                        where = (name, w, h, legacy, base, pad)
+                        assert np.array_equal(got, want), where
+                        assert prof == expected, (prof, expected, where)
+                        if _geometry(name)[:2] == (ROW_COPY, True):
+                            SEEN_OPAQUE.update((name, mark.split(",")[1][:-1]) for mark in prof)
+
+
+# ---- batches ----------------------------------------------------------------------------------------------------------------------------
+# (what, width, height, depth, items, levels, header flags, caps2, 'DX10'-only)
+TEXTURES = (("chain", 5, 3, 1, 1, 3, 0x1007 | 0x20000, 0, False), ("array", 8, 8, 1, 2, 4, 0x1007 | 0x20000, 0, True),
+            ("cube", 4, 4, 1, 6, 3, 0x1007 | 0x20000, 0x200 | 0xFC00, False), ("volume", 4, 4, 4, 1, 3, 0x1007 | 0x20000 | 0x800000, 0x200000, False),
+            ("one more than a batch", 4, 4, 1, BATCH + 1, 1, 0x1007, 0, True))
+
+
+@pytest.mark.parametrize("texture", TEXTURES, ids=[t[0] for t in TEXTURES])
+@pytest.mark.parametrize("name", ["888", "p8"])
+def test_a_texture_is_one_call(ctx, oracle, arena, name, texture):
+    """Chains, arrays, cubes and volumes in one call, and an array that needs a second launch. A legacy pixel format cannot say "array":
+    for those the expectation is the reference's load of each item's bytes as a file of its own."""
+    _, w, h, depth, items, mips, hflags, caps2, split = texture
+    op, opaque, fmt, B, D, cp = _geometry(name)
+    images, total = _layout(oracle, fmt, cp, w, h, depth, items, mips)
+    payload = np.random.default_rng(items * 17 + mips).integers(0, 256, total, dtype=np.uint8)
+    want = []
+    for part in (np.split(payload, items) if split else [payload]):
+        hr, meta, px = oracle.ref_load_dds_ex(np.frombuffer(dds_file(name, w, h, part.tobytes(), mips=mips, flags=hflags, depth=depth if depth > 1 else 0, caps2=caps2), np.uint8),
+                                              CASES[name][2])
+        assert hr == 0 and meta["mipLevels"] == mips and meta["arraySize"] == (1 if split else items), (hex(hr), meta)
+        want.append(px)
+    want = np.concatenate(want)
+    for base, pad in ((0, 0), (1, 3)):
+        got, prof, expected = _run_unpack(ctx, arena, name, images, payload, base, pad)
+        assert np.array_equal(np.concatenate([g.reshape(-1) for g in got]), want), (texture, base, pad)
+        assert prof == expected and sum(prof.values()) >= (2 if items > BATCH else 1), (prof, expected)
+
+
+BC1, BC3 = 71, 77
+TAILS = (("bc1 chain", BC1, 8, 8, 1, 1, 4), ("bc1 array", BC1, 8, 8, 1, 2, 4), ("bc3 volume", BC3, 8, 8, 4, 1, 3))
+
+
+@pytest.mark.parametrize("case", TAILS, ids=[t[0] for t in TAILS])
+def test_bad_dxtn_tails_are_descriptors(ctx, oracle, arena, case):
+    """DDS_FLAGS_BAD_DXTN_TAILS: a level smaller than a block was not stored, and its descriptor points at the last stored level's bytes -
+    image 0 again at the start of every array item, as in the reference. Against the reference's loader with the flag."""
+    _, fmt, w, h, depth, items, mips = case
+    volume = depth > 1
+    images, total = _layout(oracle, fmt, CP_BAD_DXTN_TAILS, w, h, depth, items, mips)
+    payload = np.random.default_rng(fmt).integers(0, 256, total, dtype=np.uint8)
+    dx10 = (fmt, 4 if volume else 3, 0, items, 0)
+    data = header(w, h, four("DX10"), flags=0x1007 | 0x20000 | (0x800000 if volume else 0), mips=mips, depth=depth if volume else 0, dx10=dx10) + payload.tobytes()
+    hr, meta, want = oracle.ref_load_dds_ex(np.frombuffer(data, np.uint8), BAD_DXTN_TAILS)
+    assert hr == 0 and meta["mipLevels"] == mips, (hex(hr), meta)
+    described, index = [], 0
+    for _ in range(items):
+        lastgood, d = 0, depth
+        for _ in range(mips):
+            for z in range(d):
+                lw, lh, offset, pitch = images[index]
+                if lw < 4 or lh < 4:
+                    _, _, offset, pitch = images[lastgood + (z if volume else 0)]
+                elif not volume or z == 0:
+                    lastgood = index
+                described.append((lw, lh, offset, pitch))
+                index += 1
+            d = max(1, d >> 1)
+    ctx.upload(arena.s, np.concatenate([payload, np.full(64, FILL, np.uint8)]), sync=True)
+    dsts, at, sizes = [], 0, []
+    for (lw, lh, _, _) in described:
+        rp, sp = dx.compute_pitch(fmt, lw, lh)
+        dsts.append(dx.device_image(arena.d + at, lw, lh, fmt, rp, sp))
+        sizes.append((at, sp))
+        at = (at + sp + 255) & ~255
+    ctx.upload(arena.d, np.full(at + 64, FILL, np.uint8), sync=True)
+    ctx.profile_begin()
+    ctx.dds_unpack_device(arena.s, payload.size, ROW_COPY, dsts, [i[2] for i in described], [i[3] for i in described])
+    prof = {k: v[1] for k, v in ctx.profile_end().items() if k.startswith("dds_")}
+    assert set(prof) <= {"dds_unpack<copy,wide>", "dds_unpack<copy,narrow>"} and sum(prof.values()) <= 2, prof
+    got = np.zeros(at + 64, np.uint8)
+    ctx.download(got, arena.d, sync=True)
+    assert np.array_equal(np.concatenate([got[p:p + n] for p, n in sizes]), want), case
+    mask = np.ones(got.size, bool)
+    for p, n in sizes:
+        mask[p:p + n] = False
+    assert (got[mask] == FILL).all()
+
+
+# ---- pack24 -----------------------------------------------------------------------------------------------------------------------------
+FORCE_24BPP_RGB = 0x100000
+_rows24 = {}
+
+
+def _ref_rows24(oracle, w, h, mips=1):
+    """(the B8G8R8X8 texture's tight pixels, the payload of the reference's 24-bit file); computed once per case."""
+    key = (w, h, mips)
+    if key not in _rows24:
+        images, total = _layout(oracle, BGRX8, 0, w, h, 1, 1, mips)
+        px = np.random.default_rng(w * 9 + h).integers(0, 256, total, dtype=np.uint8)
+        hr, ref = oracle.ref_save_dds_ex(px, w, h, 1, BGRX8, 1, mips, 0, 0, 3, FORCE_24BPP_RGB)
+        out_images, out_total = _layout(oracle, BGRX8, CP_24BPP, w, h, 1, 1, mips)
+        assert hr == 0 and ref.size == 128 + out_total and ref[88] == 24, (hex(hr), ref.size)          # a legacy header with a 24-bit pixel format
+        _rows24[key] = (px, images, ref[128:], out_images)
+    return _rows24[key]
+
+
+def _run_pack24(ctx, arena, px, images, out_images, out_total, pad, base):
+    srcs, at = [], 0
+    host = np.full(arena.dn, 0x5A, np.uint8)
+    for (w, h, offset, rp) in images:
+        pitch = rp + pad
+        rows = host[at:at + pitch * h].reshape(h, pitch)
+        rows[:, :rp] = px[offset:offset + rp * h].reshape(h, rp)
+        srcs.append(dx.device_image(arena.d + at, w, h, BGRX8, pitch, pitch * h))
+        at = (at + pitch * h + 255) & ~255
+    ctx.upload(arena.d, host, sync=True)
+    ctx.upload(arena.s, np.full(out_total + 64, FILL, np.uint8), sync=True)
+    expected = {}
+    for s, (w, h, offset, rp) in zip(srcs, out_images):
+        wide = w % 4 == 0 and (arena.s + base + offset) % 4 == 0 and rp % 4 == 0 and s.pixels % 16 == 0 and s.rowPitch % 16 == 0
+        mark = "dds_pack24<wide>" if wide else "dds_pack24<narrow>"
+        expected[mark] = expected.get(mark, 0) + 1
+    ctx.profile_begin()
+    ctx.dds_pack24_device(srcs, [i[2] for i in out_images], [i[3] for i in out_images], arena.s + base, out_total)
+    prof = {k: v[1] for k, v in ctx.profile_end().items() if k.startswith("dds_")}
+    got = np.zeros(out_total + 64, np.uint8)
+    ctx.download(got, arena.s, sync=True)
+    return got, prof, {k: (v + BATCH - 1) // BATCH for k, v in expected.items()}
+
+
+def test_pack24_matches_the_reference_writer(ctx, oracle, arena):
+    seen = set()
+    for w in WIDTHS:
+        for h in HEIGHTS:
+            px, images, want, out_images = _ref_rows24(oracle, w, h)
+            for pad in PITCH_PADS:
+                for base in BASES:
+                    got, prof, expected = _run_pack24(ctx, arena, px, images, out_images, want.size, pad, base)
+                    where = (w, h, pad, base)
+                    assert np.array_equal(got[base:base + want.size], want), where
+                    assert (got[:base] == FILL).all() and (got[base + want.size:] == FILL).all(), ("bytes outside the rows were written", where)
+                    assert prof == expected, (prof, expected, where)
+                    seen.update(prof)
+    assert seen == {"dds_pack24<wide>", "dds_pack24<narrow>"}
+
+
+def test_pack24_takes_a_chain(ctx, oracle, arena):
+    px, images, want, out_images = _ref_rows24(oracle, 5, 3, mips=3)
+    for pad, base in ((0, 0), (3, 1)):
+        got, prof, expected = _run_pack24(ctx, arena, px, images, out_images, want.size, pad, base)
+        assert np.array_equal(got[base:base + want.size], want) and (got[base + want.size:] == FILL).all() and prof == expected, (pad, base, prof)
+
+
+# ---- host forms and the stream ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["888", "p8", "l16", "copy_5551_opaque"])
+def test_host_forms_give_the_device_forms_bytes_and_move_the_files_bytes(ctx, oracle, name):
+    op, opaque, fmt, B, D, cp = _geometry(name)
+    for (w, h, pad) in ((4, 2, 0), (5, 5, 3), (257, 2, 4)):
+        payload, file_pitch, want = _ref(oracle, name, w, h, False)
+        ctx.transfer_bytes(reset=True)
+        (got,) = ctx.dds_unpack(payload, op, [(w, h, fmt, w * D + pad)], [0], [file_pitch], opaque, palette_words() if op == ROW_P8 else None)
+        assert ctx.transfer_bytes() == (payload.size, w * D * h), (name, w, h)          # up: the file's bytes; down: the rows
+        assert np.array_equal(got.reshape(h, -1)[:, :w * D], want), (name, w, h)
+    px, images, want, out_images = _ref_rows24(oracle, 5, 3, mips=3)
+    ctx.transfer_bytes(reset=True)
+    got = ctx.dds_pack24([(px[o:o + rp * h], w, h, None) for (w, h, o, rp) in images], [i[2] for i in out_images], [i[3] for i in out_images], want.size)
+    assert np.array_equal(got, want) and ctx.transfer_bytes() == (px.size, want.size)
+
+
+def test_two_files_queued_back_to_back(ctx, oracle):
+    """_device forms are asynchronous: two different files on the stream, one synchronise at the end, both right."""
+    jobs = []
+    for name, w, h in (("888", 64, 5), ("a8p8", 65, 2)):
+        op, opaque, fmt, B, D, cp = _geometry(name)
+        payload, file_pitch, want = _ref(oracle, name, w, h, False)
+        s, d = ctx.device_alloc(payload.size), ctx.device_alloc(w * D * h)
+        jobs.append((name, op, opaque, fmt, payload, file_pitch, want, s, d, w, h, D, np.zeros(w * D * h, np.uint8)))
+    try:
+        for (name, op, opaque, fmt, payload, file_pitch, want, s, d, w, h, D, out) in jobs:
+            ctx.upload(s, payload)
+            ctx.dds_unpack_device(s, payload.size, op, [dx.device_image(d, w, h, fmt)], [0], [file_pitch], opaque, palette_words() if name == "a8p8" else None)
+            ctx.download(out, d)
+        ctx.synchronize()
+        for job in jobs:
+            assert np.array_equal(job[-1].reshape(job[6].shape), job[6]), job[0]
+    finally:
+        for job in jobs:
+            ctx.device_free(job[7])
+            ctx.device_free(job[8])
+
+
+# ---- HRESULTs ---------------------------------------------------------------------------------------------------------------------------
+def test_hresults_and_nothing_written(ctx):
+    """Every failure of include/dxtex_amd.h's list, device and host forms; the destination and the output stay as they were."""
+    lib, h = ctx._lib, ctx._h
+    dev = ctx.device_alloc(8192)
+    fill = np.full(8192, FILL, np.uint8)
+    ctx.upload(dev, fill, sync=True)
+    pal = palette_words()
+    try:
+        def arrays(images, offsets, pitches):
+            n = max(len(images), 1)
+            return (dx.Image * n)(*images), (ctypes.c_size_t * n)(*offsets), (ctypes.c_size_t * n)(*pitches)
+
+        def unpack(payload, size, op, images, offsets, pitches, palette=None, host=False, count=None, opaque=0):
+            fn = lib.dxtex_dds_unpack if host else lib.dxtex_dds_unpack_device
+            a, o, p = arrays(images, offsets, pitches)
+            return fn(h, payload, size, op, opaque, None if palette is None else palette.ctypes.data, a, o, p, len(images) if count is None else count)
+
+        def pack(images, offsets, pitches, out, size, host=False, count=None):
+            fn = lib.dxtex_dds_pack24 if host else lib.dxtex_dds_pack24_device
+            a, o, p = arrays(images, offsets, pitches)
+            return fn(h, a, o, p, len(images) if count is None else count, out, size)
+
+        def image(w, hgt, fmt, pitch, ptr=dev + 4096):
+            return dx.device_image(ptr, w, hgt, fmt, pitch, pitch * max(hgt, 1))
+
+        good = image(4, 4, RGBA8, 16)
+        # E_POINTER
+        assert unpack(None, 48, ROW_888, [good], [0], [12]) == E_POINTER
+        assert unpack(dev, 48, ROW_888, [image(4, 4, RGBA8, 16, ptr=None)], [0], [12]) == E_POINTER
+        assert lib.dxtex_dds_unpack_device(h, dev, 48, ROW_888, 0, None, None, None, None, 1) == E_POINTER
+        assert pack([image(4, 4, BGRX8, 16)], [0], [12], None, 48) == E_POINTER and pack([image(4, 4, BGRX8, 16, ptr=None)], [0], [12], dev, 48) == E_POINTER
+        # E_INVALIDARG: zero images, an unknown op, a palette missing or unwanted
+        assert unpack(dev, 48, ROW_888, [good], [0], [12], count=0) == E_INVALIDARG and pack([image(4, 4, BGRX8, 16)], [0], [12], dev, 48, count=0) == E_INVALIDARG
+        assert unpack(dev, 48, 18, [good], [0], [12]) == E_INVALIDARG and unpack(dev, 48, 200, [good], [0], [12]) == E_INVALIDARG
+        assert unpack(dev, 16, ROW_P8, [good], [0], [4]) == E_INVALIDARG and unpack(dev, 48, ROW_888, [good], [0], [12], palette=pal) == E_INVALIDARG
+        # NOT_SUPPORTED: a pair outside the table
+        for op, fmt in ((ROW_888, 87), (ROW_888, 29), (2, 85), (7, 87), (13, RGBA8), (ROW_WUV10, RGBA8), (ROW_SWIZZLE, 61), (ROW_COPY, 0), (ROW_COPY, 500)):
+            assert unpack(dev, 4096, op, [image(4, 4, fmt, 64)], [0], [16]) == E_NOT_SUPPORTED, (op, fmt)
+        assert pack([image(4, 4, RGBA8, 16)], [0], [12], dev, 48) == E_NOT_SUPPORTED and pack([image(4, 4, 87, 16)], [0], [12], dev, 48) == E_NOT_SUPPORTED
+        # E_INVALIDARG: a descriptor past the payload, a destination too small, a file pitch below the row, mixed formats, overlap
+        assert unpack(dev, 47, ROW_888, [good], [0], [12]) == E_INVALIDARG and unpack(dev, 48, ROW_888, [good], [1], [12]) == E_INVALIDARG
+        assert unpack(dev, 4096, ROW_888, [good], [4090], [12]) == E_INVALIDARG and unpack(dev, 4096, ROW_888, [good], [1 << 62], [12]) == E_INVALIDARG
+        assert unpack(dev, 4096, ROW_888, [good], [0], [1 << 62]) == E_INVALIDARG
+        assert unpack(dev, 4096, ROW_888, [good, good], [0, 4000], [12, 100]) == E_INVALIDARG          # the second image of two
+        assert unpack(dev, 4096, ROW_888, [image(4, 4, RGBA8, 15)], [0], [12]) == E_INVALIDARG and unpack(dev, 4096, ROW_888, [good], [0], [11]) == E_INVALIDARG
+        assert unpack(dev, 4096, ROW_COPY, [good, image(4, 4, 87, 16)], [0, 64], [16, 16]) == E_INVALIDARG
+        assert unpack(dev, 8192, ROW_888, [good], [4096 + 60], [12]) == E_INVALIDARG          # the rows start inside the image's last row
+        assert pack([image(4, 4, BGRX8, 16)], [0], [12], dev, 47) == E_INVALIDARG and pack([image(4, 4, BGRX8, 15)], [0], [12], dev, 48) == E_INVALIDARG
+        assert pack([image(4, 4, BGRX8, 16)], [4096 - 4], [12], dev, 8192) == E_INVALIDARG          # the last row ends inside the image
+        ctx.synchronize()
+        back = np.zeros(8192, np.uint8)
+        ctx.download(back, dev, sync=True)
+        assert np.array_equal(back, fill), "a failed call wrote"
+        # the host forms check the same things
+        buf, px = np.full(64, FILL, np.uint8), np.full(64, FILL, np.uint8)
+        himg = dx.Image(4, 4, RGBA8, 16, 64, px.ctypes.data)
+        assert unpack(buf.ctypes.data, 47, ROW_888, [himg], [0], [12], host=True) == E_INVALIDARG
+        assert unpack(buf.ctypes.data, 48, ROW_888, [dx.Image(4, 4, 87, 16, 64, px.ctypes.data)], [0], [12], host=True) == E_NOT_SUPPORTED
+        assert unpack(buf.ctypes.data, 48, ROW_P8, [himg], [0], [12], host=True) == E_INVALIDARG and unpack(None, 48, ROW_888, [himg], [0], [12], host=True) == E_POINTER
+        assert pack([dx.Image(4, 4, BGRX8, 16, 64, px.ctypes.data)], [0], [12], buf.ctypes.data, 47, host=True) == E_INVALIDARG
+        assert pack([himg], [0], [12], buf.ctypes.data, 48, host=True) == E_NOT_SUPPORTED
+        assert (buf == FILL).all() and (px == FILL).all()
+        # and the calls these were derived from succeed
+        assert unpack(dev, 48, ROW_888, [good], [0], [12]) == 0 and pack([image(4, 4, BGRX8, 16)], [0], [12], dev, 48) == 0
+        ctx.synchronize()
+    finally:
+        ctx.device_free(dev)
+
+
+def test_zz_every_op_ran_on_both_routes():
+    """Runs last in the module: no op is barred from the wide route by its alignment rule, so each must have been seen on both, and so
+    must every forced-alpha copy, whose lane masks differ per class. This reads SEEN and SEEN_OPAQUE, which the tests above fill in the
+    same process: run alone, under a -k selection that drops them, or on a worker of a test distributor that did not get them, it fails
+    for that reason and says nothing about the code."""
+    assert SEEN >= {f"dds_unpack<{n},{r}>" for n in OP_NAMES for r in ("wide", "narrow")}, sorted(SEEN)
+    opaque_copies = [n for n in list(CASES) + list(CLASSES) if _geometry(n)[:2] == (ROW_COPY, True)]
+    assert len(opaque_copies) == 7 and SEEN_OPAQUE >= {(n, r) for n in opaque_copies for r in ("wide", "narrow")}, sorted(SEEN_OPAQUE)
