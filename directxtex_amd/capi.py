@@ -148,6 +148,10 @@ _SIGS = {
     "dxtex_dds_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t]),
     "dxtex_dds_pack24": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_dds_pack24_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_pnm_unpack": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P(Image)]),
+    "dxtex_pnm_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P(Image)]),
+    "dxtex_pnm_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_pnm_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -803,6 +807,38 @@ class Context:
     def tga_pack_device(self, src, bytes_per_texel, texels_ptr, texel_bytes):
         """dxtex_tga_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
         self._check(self._lib.dxtex_tga_pack_device(self._h, ctypes.byref(src), bytes_per_texel, texels_ptr, texel_bytes), "tga_pack_device")
+
+    # -- portable pixmap texels (the per-texel half of the .ppm / .pfm / .phm codec) -------------------------------------------------------
+    def pnm_unpack(self, samples, width, height, kind, fmt, maxval=255, flags=0, row_pitch=None, out=None):
+        """dxtex_pnm_unpack: the samples behind the header (host bytes) -> pixels of `fmt` as a numpy uint8 buffer with `row_pitch` bytes a
+        row, default tight. kind = PNM_*; flags = PNM_BIG_ENDIAN. out: the buffer to unpack into (so that a caller can see what is left
+        untouched), default a zeroed one."""
+        samples = np.ascontiguousarray(samples, np.uint8)
+        pitch = compute_pitch(fmt, width, height)[0] if row_pitch is None else row_pitch
+        if out is None:
+            out = np.zeros(pitch * height, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.nbytes >= pitch * height
+        dst = Image(width, height, fmt, pitch, pitch * height, out.ctypes.data)
+        self._check(self._lib.dxtex_pnm_unpack(self._h, samples.ctypes.data, samples.nbytes, kind, maxval, flags, ctypes.byref(dst)), "pnm_unpack")
+        return out
+
+    def pnm_pack(self, pixels, width, height, fmt, kind, row_pitch=None, out=None):
+        """dxtex_pnm_pack: one image (host pixels) -> the width * height * texel bytes of the file's rows, as a numpy uint8 buffer (or the
+        front of `out`)."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        if out is None:
+            out = np.zeros(width * height * F.PNM_FILE_BYTES[kind], np.uint8)
+        self._check(self._lib.dxtex_pnm_pack(self._h, ctypes.byref(src), kind, out.ctypes.data, out.nbytes), "pnm_pack")
+        return out
+
+    def pnm_unpack_device(self, samples_ptr, sample_bytes, kind, dst, maxval=255, flags=0):
+        """dxtex_pnm_unpack_device: the samples at a device pointer -> the device Image `dst` (device_image), asynchronous on the stream."""
+        self._check(self._lib.dxtex_pnm_unpack_device(self._h, samples_ptr, sample_bytes, kind, maxval, flags, ctypes.byref(dst)), "pnm_unpack_device")
+
+    def pnm_pack_device(self, src, kind, samples_ptr, sample_bytes):
+        """dxtex_pnm_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
+        self._check(self._lib.dxtex_pnm_pack_device(self._h, ctypes.byref(src), kind, samples_ptr, sample_bytes), "pnm_pack_device")
 
     # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
     @staticmethod

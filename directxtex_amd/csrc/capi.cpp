@@ -6,6 +6,7 @@
 #include "dxtex_kernels.h"
 #include "dxtex_tga.h"
 #include "dxtex_dds.h"
+#include "dxtex_pnm.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -1799,6 +1800,125 @@ dxtex_hresult dxtex_dds_pack24(dxtex_ctx* ctx, const dxtex_image* srcs, const si
                                        size_t(jobs[i].width) * 3u, jobs[i].rows, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
+}
+
+namespace
+{
+static_assert(DXTEX_PNM_P6 == PNM_P6 && DXTEX_PNM_PF == PNM_PF && DXTEX_PNM_Pf == PNM_Pf && DXTEX_PNM_PH == PNM_PH && DXTEX_PNM_Ph == PNM_Ph &&
+              DXTEX_PNM_BIG_ENDIAN == PNM_BIG_ENDIAN, "dxtex_pnm.h's kinds and flag are the public ones");
+
+// the reader's table (include/dxtex_amd.h): the one format a kind unpacks into
+int pnm_unpack_format(uint32_t kind)
+{
+    switch (kind)
+    {
+    case PNM_P6: return FMT_R8G8B8A8_UNORM;
+    case PNM_PF: return FMT_R32G32B32A32_FLOAT;
+    case PNM_Pf: return FMT_R32_FLOAT;
+    case PNM_PH: return FMT_R16G16B16A16_FLOAT;
+    default: return FMT_R16_FLOAT;
+    }
+}
+
+// the writer's table (SaveToPortablePixMap, SaveToPortablePixMapHDR): the PnmSource of a (kind, format); -1 for a pair outside it
+int pnm_pack_source(uint32_t kind, int format)
+{
+    switch (format)
+    {
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return kind == PNM_P6 ? PNM_SRC_RGBA8 : -1;
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return kind == PNM_P6 ? PNM_SRC_BGRA8 : -1;
+    case FMT_R32G32B32A32_FLOAT: return kind == PNM_PF ? PNM_SRC_RGBA32F : -1;
+    case FMT_R32G32B32_FLOAT: return kind == PNM_PF ? PNM_SRC_RGB32F : -1;
+    case FMT_R16G16B16A16_FLOAT: return kind == PNM_PF ? PNM_SRC_RGBA16F : -1;
+    case FMT_R32_FLOAT: return kind == PNM_Pf ? PNM_SRC_R32F : -1;
+    default: return -1;
+    }
+}
+
+// The checks of the PNM four, in the order include/dxtex_amd.h states. *source = the writer's PnmSource (pack); *rowBytes = a row of the
+// image side, *need = the samples the call moves.
+dxtex_hresult check_pnm(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* image, bool unpack,
+                        int* source, size_t* rowBytes, size_t* need)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!samples) return fail(ctx, DXTEX_E_POINTER, "null samples");
+    if (!image) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!image->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (kind >= PNM_KINDS) return fail(ctx, DXTEX_E_INVALIDARG, "unknown PNM kind");
+    if (unpack && kind == PNM_P6 && (maxval < 1 || maxval > 255)) return fail(ctx, DXTEX_E_INVALIDARG, "a P6 maxval is 1 to 255");
+    if (flags & ~uint32_t(PNM_BIG_ENDIAN)) return fail(ctx, DXTEX_E_INVALIDARG, "unknown PNM flag bits");
+    if (!image->width || !image->height || !sampleBytes) return fail(ctx, DXTEX_E_INVALIDARG, "empty image or no samples");
+    if (image->width > 0xFFFFFFFFull || image->height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    size_t imageTexel;
+    if (unpack)
+    {
+        if (image->format != pnm_unpack_format(kind)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this PNM kind does not unpack into this format");
+        imageTexel = pnm_image_bytes(int(kind));
+    }
+    else
+    {
+        *source = pnm_pack_source(kind, image->format);
+        if (*source < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "no PNM writer case for this kind and format");
+        imageTexel = pnm_source_bytes(*source);
+    }
+    const size_t fileTexel = pnm_file_bytes(int(kind));
+    if (image->width > SIZE_MAX / 16 / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    *need = image->width * image->height * fileTexel;
+    *rowBytes = image->width * imageTexel;
+    if (sampleBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer samples than width * height texels");
+    if (image->rowPitch < *rowBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
+    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(samples), s1 = s0 + *need;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + *rowBytes;
+    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "samples and image pixels overlap");
+    return DXTEX_S_OK;
+}
+} // namespace
+
+dxtex_hresult dxtex_pnm_unpack_device(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst)
+{
+    size_t rowBytes, need;
+    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_pnm_unpack(static_cast<const uint8_t*>(samples), int(kind), maxval, flags, view_of(*dst), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_pnm_unpack(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst)
+{
+    size_t rowBytes, need;
+    dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    // the samples go up as they are; the kernel writes tight rows (rounded up to 16 bytes, so that a width of four texels keeps the wide
+    // route) into the output staging, and only each row's texels come down, through the caller's pitch
+    const size_t pitch = (rowBytes + 15) & ~size_t(15);
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, need); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, pitch * dst->height); if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, samples, need, hipMemcpyHostToDevice, ctx->stream));
+    dxtex_image staged = with_pixels(*dst, ctx->stageOut.u8());
+    staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_pnm_unpack(ctx->stageIn.u8(), int(kind), maxval, flags, view_of(staged), ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy_rows(ctx, dst->pixels, dst->rowPitch, staged.pixels, pitch, rowBytes, dst->height, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_pnm_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes)
+{
+    int source; size_t rowBytes, need;
+    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, 255, 0, src, false, &source, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_pnm_pack(view_of(*src), source, static_cast<uint8_t*>(samples), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_pnm_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes)
+{
+    int source; size_t rowBytes, need;
+    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, 255, 0, src, false, &source, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, samples, need,
+                      [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_pnm_pack(view_of(with_pixels(*src, in)), source, out, ctx->stream, marks_of(ctx))); });
 }
 
 namespace

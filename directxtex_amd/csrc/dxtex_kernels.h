@@ -127,6 +127,12 @@ hipError_t launch_dds_unpack(const uint8_t* payload, size_t payloadBytes, int op
                              hipStream_t stream, KernelMarks* marks = nullptr);
 hipError_t launch_dds_pack24(const DdsImage* images, size_t count, uint8_t* out, size_t outBytes, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// Portable pixmap texels (pnm.hip; the rules are in dxtex_pnm.h). Unpack: `stream` = dst.width * dst.height texels in file order, kind = a
+// PnmKind that matches dst.format, maxval = 1..255 (read by PNM_P6 only), flags = PnmFlags. Pack: src's rows -> stream, source = the
+// PnmSource of src.format. Neither touches memory outside the stream's texels and each image row's `width` texels. Wide / narrow: see pnm.hip.
+hipError_t launch_pnm_unpack(const uint8_t* stream, int kind, uint32_t maxval, uint32_t flags, const ImgView& dst, hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_pnm_pack(const ImgView& src, int source, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

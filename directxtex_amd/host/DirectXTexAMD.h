@@ -28,6 +28,7 @@ constexpr HRESULT E_OUTOFMEMORY = HRESULT(0x8007000E);
 constexpr HRESULT E_POINTER = HRESULT(0x80004003);
 constexpr HRESULT E_NOTIMPL = HRESULT(0x80004001);
 constexpr HRESULT E_ABORT = HRESULT(0x80004004);
+constexpr HRESULT E_UNEXPECTED = HRESULT(0x8000FFFF);
 constexpr HRESULT HRESULT_E_NOT_SUPPORTED = HRESULT(0x80070032);
 constexpr HRESULT HRESULT_E_ARITHMETIC_OVERFLOW = HRESULT(0x80070216);
 inline bool FAILED(HRESULT hr) noexcept { return hr < 0; }
@@ -673,4 +674,48 @@ void ApplyTGAAlphaRule(const TGARawImage& raw, TGA_FLAGS flags, TexMetadata& met
 HRESULT LoadFromTGAFile(Device& device, const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
 HRESULT SaveToTGAMemory(Device& device, const Image& deviceImage, TGA_FLAGS flags, Blob& blob, const TexMetadata* metadata = nullptr) noexcept;
 HRESULT SaveToTGAFile(Device& device, const Image& deviceImage, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata = nullptr) noexcept;
+
+// ---- Portable pixmaps, Texconv/PortablePixMap.cpp: .ppm (P3 ASCII and P6 binary -> R8G8B8A8_UNORM), .pfm (PF -> R32G32B32A32_FLOAT, Pf ->
+// R32_FLOAT) and .phm (PH -> R16G16B16A16_FLOAT, Ph -> R16_FLOAT), either byte order. One loader takes all of them and tells them apart by
+// the second byte, as texconv does by extension. The reference has the File forms only; the Memory forms are this project's. -----------------
+HRESULT GetMetadataFromPortablePixMapMemory(const void* pSource, size_t size, TexMetadata& metadata) noexcept;
+HRESULT GetMetadataFromPortablePixMapFile(const char* szFile, TexMetadata& metadata) noexcept;
+HRESULT LoadFromPortablePixMapMemory(const void* pSource, size_t size, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT LoadFromPortablePixMapFile(const char* szFile, TexMetadata* metadata, ScratchImage& image) noexcept;
+// SaveToPortablePixMap: a P6 file from R8G8B8A8 / B8G8R8A8 / B8G8R8X8_UNORM[_SRGB]. SaveToPortablePixMapHDR: a little-endian PF file from
+// R32G32B32A32_FLOAT, R32G32B32_FLOAT or R16G16B16A16_FLOAT, a Pf file from R32_FLOAT. PH and Ph are never written, as in the reference.
+HRESULT SaveToPortablePixMapMemory(const Image& image, Blob& blob) noexcept;
+HRESULT SaveToPortablePixMapFile(const Image& image, const char* szFile) noexcept;
+HRESULT SaveToPortablePixMapHDRMemory(const Image& image, Blob& blob) noexcept;
+HRESULT SaveToPortablePixMapHDRFile(const Image& image, const char* szFile) noexcept;
+// The reader's byte-serial half, which needs no device: the text header and every refusal. What comes back is where the samples lie and how
+// to read them (dxtex_pnm_unpack's arguments). A P3 file's ASCII samples are byte-serial throughout: they are decoded here into
+// R8G8B8A8_UNORM words (`ascii`; the payload is then those words, in `storage`). On failure `raw` is released.
+struct PNMRawImage
+{
+    uint32_t kind = 0;                           // DXTEX_PNM_* (include/dxtex_amd.h)
+    uint32_t maxval = 255;                       // P6: 1..255
+    bool bigEndian = false;                      // float kinds: the scale line was >= 0
+    bool ascii = false;                          // a P3 file: the payload is the finished image, width * height words
+    const uint8_t* payload = nullptr;            // into the caller's memory; P3, and LoadFromPortablePixMapFileRaw: into `storage`
+    size_t payloadOffset = 0;                    // of the payload in the file (P3: 0)
+    size_t payloadBytes = 0;                     // width * height * bytes of a file texel
+    Blob storage;
+    void Release() noexcept;
+};
+HRESULT LoadFromPortablePixMapMemoryRaw(const void* pSource, size_t size, TexMetadata* metadata, PNMRawImage& raw) noexcept;
+HRESULT LoadFromPortablePixMapFileRaw(const char* szFile, TexMetadata* metadata, PNMRawImage& raw) noexcept;
+// Resident forms: the samples cross PCIe as the file has them - 3 bytes a texel for P6, 12 for PF, 6 for PH, 4 and 2 for the grey kinds - and
+// the per-texel pass runs on the device (dxtex_pnm_unpack_device / dxtex_pnm_pack_device). HRESULTs, metadata, pixels and files are those of
+// the host forms above. Load: one upload of payloadBytes (a P3 file: of the decoded words, straight into the image); the result is released
+// on failure. Save: deviceImage's pixels are a device pointer, as DeviceScratchImage::GetImage gives; one download of the file's rows,
+// straight behind the header.
+HRESULT LoadFromPortablePixMapMemory(Device& device, const void* pSource, size_t size, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromPortablePixMapFile(Device& device, const char* szFile, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device
+HRESULT UploadPortablePixMapRaw(Device& device, const TexMetadata& metadata, const PNMRawImage& raw, DeviceScratchImage& image) noexcept;
+HRESULT SaveToPortablePixMapMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept;
+HRESULT SaveToPortablePixMapFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
+HRESULT SaveToPortablePixMapHDRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept;
+HRESULT SaveToPortablePixMapHDRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
 } // namespace DirectXTexAMD

@@ -1,0 +1,516 @@
+// Portable pixmap reader / writer of the host layer: .ppm (P3 in, P6 in and out), .pfm (PF, Pf in and out) and .phm (PH, Ph in).
+// Behaviour follows Texconv/PortablePixMap.cpp, which reads and writes files only; the Memory forms are this project's. The reference's
+// codec is Win32 code (CreateFile2, sscanf_s) that the test oracle cannot compile, so the yardstick is tests/pnm_ref.py, a restatement of
+// the rules below with the same line numbers.
+// The reader is split in two. LoadFromPortablePixMapMemoryRaw does what is byte-serial - the text header, every refusal, and for a P3 file
+// the ASCII samples - and hands back where the samples lie and how to read them. What happens to a texel after that is dxtex_pnm.h's,
+// which the GPU kernels share: the host loader runs it here, the resident forms at the end of this file run it on the device, so that a
+// file's samples cross PCIe as the bytes they are. The writer is split the same way around its rows.
+#include "DirectXTexAMD.h"
+#include "../../include/dxtex_amd.h"
+#include "../csrc/dxtex_pnm.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+
+namespace DirectXTexAMD
+{
+namespace
+{
+    // isspace / isdigit of the "C" locale, which is what the reference's calls see
+    inline bool IsSpace(uint8_t c) noexcept { return c == ' ' || (c >= '\t' && c <= '\r'); }
+    inline bool IsDigit(uint8_t c) noexcept { return c >= '0' && c <= '9'; }
+
+    void SetMetadata(TexMetadata& m, size_t width, size_t height, DXGI_FORMAT format) noexcept
+    {
+        m = TexMetadata();
+        m.width = width; m.height = height; m.depth = m.arraySize = m.mipLevels = 1;
+        m.format = format; m.dimension = TEX_DIMENSION_TEXTURE2D;
+    }
+
+    // LoadFromPortablePixMap (:152-358). One loop over the bytes behind "P3" / "P6": white space (C isspace) separates tokens, a '#' runs to
+    // the end of its line, anything else is a decimal number accumulated in uint32_t with wrap-around (:252-263; a byte that is neither a
+    // digit nor white space: E_FAIL). The numbers are width, height, maxval and, for P3, the samples.
+    HRESULT ParsePPM(const uint8_t* data, size_t size, TexMetadata& metadata, PNMRawImage& raw) noexcept
+    {
+        const bool ascii = data[1] == '3';
+        enum { PPM_WIDTH, PPM_HEIGHT, PPM_MAX, PPM_DATA_R, PPM_DATA_G, PPM_DATA_B };
+        int mode = PPM_WIDTH;
+        const uint8_t* p = data + 2;          // the white space after the magic is the first separator (:178)
+        size_t left = size - 2;
+        size_t width = 0, height = 0;
+        uint32_t max = 255;
+        uint32_t* pixels = nullptr; uint32_t* pixelEnd = nullptr;
+        while (left > 0)
+        {
+            if (!ascii && mode == PPM_DATA_R)
+            {
+                // the samples of a P6 file (:188-226): maxval above 255 is E_UNEXPECTED; an optional '\r', then exactly '\n' - anything
+                // else, a blank included, is E_FAIL
+                if (max > 255) return E_UNEXPECTED;
+                if (left > 1 && *p == '\r') { ++p; --left; }
+                if (*p != '\n') return E_FAIL;
+                // a file that ends with that '\n' leaves the reader on it with one byte, which its loop takes for a partial texel (:203-214)
+                if (left == 1) return HRESULT_E_HANDLE_EOF;
+                ++p; --left;
+                // whole texels are taken while there are any; a trailing partial one is ERROR_HANDLE_EOF (:211-214), missing whole ones
+                // are E_FAIL (:225), surplus bytes are ignored
+                const uint64_t texels = uint64_t(width) * height;
+                if (left / 3 < texels) return (left % 3) ? HRESULT_E_HANDLE_EOF : E_FAIL;
+                raw.kind = DXTEX_PNM_P6; raw.maxval = max;
+                raw.payload = p; raw.payloadOffset = size_t(p - data); raw.payloadBytes = size_t(texels) * 3;
+                return S_OK;
+            }
+            if (IsSpace(*p)) { ++p; --left; }
+            else if (*p == '#')
+            {
+                while (left > 0 && *p != '\n') { ++p; --left; }
+                if (left > 0) { ++p; --left; }
+            }
+            else
+            {
+                uint32_t u = 0;
+                while (left > 0 && !IsSpace(*p))
+                {
+                    if (!IsDigit(*p)) return E_FAIL;
+                    u = u * 10 + uint32_t(*p - '0');
+                    ++p; --left;
+                }
+                switch (mode)
+                {
+                case PPM_WIDTH:          // :267-277
+                    if (u == 0) return E_FAIL;
+                    if (u > uint32_t(INT32_MAX)) return HRESULT_E_NOT_SUPPORTED;
+                    width = u;
+                    break;
+                case PPM_HEIGHT:          // :279-314
+                    if (u == 0) return E_FAIL;
+                    if (u > uint32_t(INT32_MAX)) return HRESULT_E_NOT_SUPPORTED;
+                    if (uint64_t(width) * uint64_t(u) * 4 > UINT32_MAX) return HRESULT_E_ARITHMETIC_OVERFLOW;
+                    height = u;
+                    SetMetadata(metadata, width, height, DXGI_FORMAT_R8G8B8A8_UNORM);
+                    if (ascii)
+                    {
+                        // The reference allocates the image here. Every failure from here on in a P3 file is E_FAIL, and a texel takes
+                        // at least five bytes of text, so a file too short for its size is refused before memory is asked for.
+                        if (uint64_t(left) + 1 < uint64_t(width) * height * 5) return E_FAIL;
+                        const HRESULT hr = raw.storage.Initialize(width * height * 4);
+                        if (FAILED(hr)) return hr;
+                        pixels = reinterpret_cast<uint32_t*>(raw.storage.GetBufferPointer());
+                        pixelEnd = pixels + width * height;
+                    }
+                    break;
+                case PPM_MAX:          // :316-321
+                    if (u == 0) return E_FAIL;
+                    max = u;
+                    break;
+                // P3 (:323-347): (u * 255) / max in uint32_t, red assigned with | 0xff000000, green and blue ORed in: no clamp
+                case PPM_DATA_R: *pixels = ((u * 255u) / max) | 0xff000000u; break;
+                case PPM_DATA_G: *pixels |= ((u * 255u) / max) << 8; break;
+                case PPM_DATA_B:
+                    *pixels |= ((u * 255u) / max) << 16;
+                    if (++pixels == pixelEnd)
+                    {
+                        raw.kind = DXTEX_PNM_P6; raw.maxval = 255; raw.ascii = true;
+                        raw.payload = raw.storage.GetBufferPointer(); raw.payloadOffset = 0; raw.payloadBytes = raw.storage.GetBufferSize();
+                        return S_OK;
+                    }
+                    mode = PPM_DATA_R - 1;
+                    break;
+                }
+                ++mode;
+            }
+        }
+        return E_FAIL;          // out of bytes (:357)
+    }
+
+    // FindEOL (:72-85): the position of the first '\n' within max bytes; 0 for none - or for one at position 0
+    inline size_t FindEOL(const uint8_t* p, size_t max) noexcept
+    {
+        for (size_t pos = 0; pos < max; ++pos) if (p[pos] == '\n') return pos;
+        return 0;
+    }
+
+    // The next header line that is no comment (:488-507, :537-556): `len` bytes at p, the '\n' behind them. Lines are looked for within
+    // the next min(256, left) bytes: none there, or an empty one, is E_FAIL.
+    HRESULT NextLine(const uint8_t*& p, size_t& left, size_t& len) noexcept
+    {
+        len = 0;
+        while (left > 0)
+        {
+            len = FindEOL(p, std::min<size_t>(256, left));
+            if (!len) return E_FAIL;
+            if (*p != '#') break;
+            p += len + 1;
+            if (left < len + 1) return HRESULT_E_HANDLE_EOF;
+            left -= len + 1;
+            if (!left) return E_FAIL;
+        }
+        return S_OK;
+    }
+
+    // strncpy_s(dataStr, pData, len + 1) into 256 bytes (:511, :558): the line and its '\n', cut at a NUL. A line of 255 characters does
+    // not fit with its terminator - the reference overruns there; here it is E_FAIL.
+    bool CopyLine(char (&dst)[256], const uint8_t* p, size_t len) noexcept
+    {
+        if (len + 1 >= sizeof(dst)) return false;
+        size_t n = 0;
+        while (n < len + 1 && p[n]) { dst[n] = char(p[n]); ++n; }
+        dst[n] = 0;
+        return true;
+    }
+
+    // behind a header line (:528-535, :566-573)
+    HRESULT SkipLine(const uint8_t*& p, size_t& left, size_t len) noexcept
+    {
+        p += len + 1;
+        if (left < len + 1) return HRESULT_E_HANDLE_EOF;
+        left -= len + 1;
+        return left ? S_OK : E_FAIL;
+    }
+
+    // LoadFromPortablePixMapHDR (:452-684) up to its texel loops
+    HRESULT ParsePFM(const uint8_t* data, size_t size, TexMetadata& metadata, PNMRawImage& raw) noexcept
+    {
+        DXGI_FORMAT format; uint32_t kind;
+        switch (data[1])          // :473-481
+        {
+        case 'f': format = DXGI_FORMAT_R32_FLOAT; kind = DXTEX_PNM_Pf; break;
+        case 'F': format = DXGI_FORMAT_R32G32B32A32_FLOAT; kind = DXTEX_PNM_PF; break;
+        case 'h': format = DXGI_FORMAT_R16_FLOAT; kind = DXTEX_PNM_Ph; break;
+        case 'H': format = DXGI_FORMAT_R16G16B16A16_FLOAT; kind = DXTEX_PNM_PH; break;
+        default: return E_FAIL;
+        }
+        const uint8_t* p = data + 3;
+        size_t left = size - 3;
+        if (!left) return E_FAIL;
+
+        size_t len;
+        HRESULT hr = NextLine(p, left, len);
+        if (FAILED(hr)) return hr;
+        char line[256], junk[256];
+        if (!CopyLine(line, p, len)) return E_FAIL;
+        // "%zu %zu%s" must convert exactly two (:514): a third token on the line is E_FAIL
+        size_t width = 0, height = 0;
+        if (std::sscanf(line, "%zu %zu%255s", &width, &height, junk) != 2) return E_FAIL;
+        if (width > size_t(INT32_MAX) || height > size_t(INT32_MAX)) return HRESULT_E_NOT_SUPPORTED;
+        if (uint64_t(width) * uint64_t(height) * dxtex::pnm_image_bytes(int(kind)) > UINT32_MAX) return HRESULT_E_ARITHMETIC_OVERFLOW;
+        hr = SkipLine(p, left, len);
+        if (FAILED(hr)) return hr;
+
+        hr = NextLine(p, left, len);
+        if (FAILED(hr)) return hr;
+        if (!CopyLine(line, p, len)) return E_FAIL;
+        float aspectRatio = 0.f;
+        if (std::sscanf(line, "%f%255s", &aspectRatio, junk) != 1) return E_FAIL;          // :561
+        const bool bigEndian = aspectRatio >= 0;          // :564; a NaN is little-endian
+        hr = SkipLine(p, left, len);
+        if (FAILED(hr)) return hr;
+
+        const uint64_t need = uint64_t(width) * dxtex::pnm_file_bytes(int(kind)) * uint64_t(height);
+        if (uint64_t(left) < need) return HRESULT_E_HANDLE_EOF;          // :575-577
+        SetMetadata(metadata, width, height, format);
+        // a zero dimension: what ScratchImage::Initialize2D answers (:589)
+        std::unique_ptr<Image[]> images; size_t nimages, pixelBytes, mips;
+        hr = LayoutScratchImage(metadata, CP_FLAGS_NONE, images, nimages, pixelBytes, mips);
+        if (FAILED(hr)) return hr;
+        raw.kind = kind; raw.maxval = 255; raw.bigEndian = bigEndian;
+        raw.payload = p; raw.payloadOffset = size_t(p - data); raw.payloadBytes = size_t(need);
+        return S_OK;
+    }
+
+    HRESULT ReadAll(const char* szFile, Blob& buf) noexcept          // ReadData (:87-143)
+    {
+        FILE* f = std::fopen(szFile, "rb");
+        if (!f) return E_FAIL;
+        std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
+        if (n < 0) { std::fclose(f); return E_FAIL; }
+        if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
+        if (n < 1) { std::fclose(f); return E_FAIL; }
+        const HRESULT hr = buf.Initialize(size_t(n));
+        if (FAILED(hr)) { std::fclose(f); return hr; }
+        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
+        std::fclose(f);
+        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
+    }
+
+    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
+    {
+        FILE* f = std::fopen(szFile, "wb");
+        if (!f) return E_FAIL;
+        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
+        const bool closed = std::fclose(f) == 0;
+        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
+        return S_OK;
+    }
+
+    // the writers' checks and header (SaveToPortablePixMap :361-390, SaveToPortablePixMapHDR :688-718): which kind a format is written as
+    struct FileShape { uint32_t kind; int source; char header[64]; size_t headerLen; };
+    HRESULT SaveChecks(const Image& image, bool hdr, FileShape& f) noexcept
+    {
+        if (!image.pixels) return E_POINTER;
+        f.kind = hdr ? DXTEX_PNM_PF : DXTEX_PNM_P6;
+        switch (image.format)
+        {
+        case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: f.source = hdr ? -1 : dxtex::PNM_SRC_RGBA8; break;
+        case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB:
+            f.source = hdr ? -1 : dxtex::PNM_SRC_BGRA8; break;
+        case DXGI_FORMAT_R32G32B32A32_FLOAT: f.source = hdr ? dxtex::PNM_SRC_RGBA32F : -1; break;
+        case DXGI_FORMAT_R32G32B32_FLOAT: f.source = hdr ? dxtex::PNM_SRC_RGB32F : -1; break;
+        case DXGI_FORMAT_R16G16B16A16_FLOAT: f.source = hdr ? dxtex::PNM_SRC_RGBA16F : -1; break;
+        case DXGI_FORMAT_R32_FLOAT: f.source = hdr ? dxtex::PNM_SRC_R32F : -1; if (hdr) f.kind = DXTEX_PNM_Pf; break;
+        default: f.source = -1; break;
+        }
+        if (f.source < 0) return HRESULT_E_NOT_SUPPORTED;
+        if (!image.width || !image.height) return E_INVALIDARG;
+        if (image.width > size_t(INT32_MAX) || image.height > size_t(INT32_MAX)) return HRESULT_E_NOT_SUPPORTED;
+        const int len = hdr ? std::snprintf(f.header, sizeof(f.header), "P%c\n%zu %zu\n-1.000000\n", f.kind == DXTEX_PNM_Pf ? 'f' : 'F', image.width, image.height)
+                            : std::snprintf(f.header, sizeof(f.header), "P6\n%zu %zu\n255\n", image.width, image.height);
+        if (len < 0 || size_t(len) >= sizeof(f.header)) return E_UNEXPECTED;
+        f.headerLen = size_t(len);
+        return S_OK;
+    }
+
+    // the file around the samples: the header, then rows(d, bytes) leaves the file's rows at d, tight
+    template<class Rows>
+    HRESULT WriteFile(const Image& image, const FileShape& f, Blob& blob, Rows&& rows) noexcept
+    {
+        blob.Release();
+        const size_t bytes = image.width * image.height * dxtex::pnm_file_bytes(int(f.kind));
+        HRESULT hr = blob.Initialize(f.headerLen + bytes);
+        if (FAILED(hr)) return hr;
+        std::memcpy(blob.GetBufferPointer(), f.header, f.headerLen);
+        hr = rows(blob.GetBufferPointer() + f.headerLen, bytes);
+        if (FAILED(hr)) blob.Release();
+        return hr;
+    }
+
+    HRESULT SaveHost(const Image& image, bool hdr, Blob& blob) noexcept
+    {
+        FileShape f;
+        const HRESULT hr = SaveChecks(image, hdr, f);
+        if (FAILED(hr)) return hr;
+        const size_t S = dxtex::pnm_source_bytes(f.source), B = dxtex::pnm_file_bytes(int(f.kind));
+        if (image.rowPitch < image.width * S) return E_INVALIDARG;
+        return WriteFile(image, f, blob, [&](uint8_t* d, size_t)
+        {
+            for (size_t y = 0; y < image.height; ++y)
+            {
+                const uint8_t* s = image.pixels + size_t(dxtex::pnm_image_row(int(f.kind), uint32_t(y), uint32_t(image.height))) * image.rowPitch;
+                for (size_t x = 0; x < image.width; ++x, s += S, d += B) dxtex::pnm_pack_texel(s, d, f.source);
+            }
+            return S_OK;
+        });
+    }
+
+    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
+    struct DeviceTemp
+    {
+        Device& device; void* p = nullptr;
+        explicit DeviceTemp(Device& d) noexcept : device(d) {}
+        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
+        DeviceTemp(const DeviceTemp&) = delete;
+        DeviceTemp& operator=(const DeviceTemp&) = delete;
+    };
+
+    HRESULT SaveResident(Device& device, const Image& deviceImage, bool hdr, Blob& blob) noexcept
+    {
+        FileShape f;
+        const HRESULT hr = SaveChecks(deviceImage, hdr, f);
+        if (FAILED(hr)) return hr;
+        if (!device) return E_POINTER;
+        return WriteFile(deviceImage, f, blob, [&](uint8_t* d, size_t bytes)
+        {
+            DeviceTemp temp(device);
+            HRESULT hr2 = dxtex_device_alloc(device.Get(), bytes, &temp.p);
+            if (SUCCEEDED(hr2))
+            {
+                const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
+                hr2 = dxtex_pnm_pack_device(device.Get(), &s, f.kind, temp.p, bytes);
+            }
+            if (SUCCEEDED(hr2)) hr2 = dxtex_memcpy_d2h(device.Get(), d, temp.p, bytes);          // straight behind the header; returns when the rows have landed
+            return hr2;
+        });
+    }
+}
+
+void PNMRawImage::Release() noexcept
+{
+    storage.Release();
+    kind = 0; maxval = 255; bigEndian = ascii = false;
+    payload = nullptr; payloadOffset = payloadBytes = 0;
+}
+
+HRESULT LoadFromPortablePixMapMemoryRaw(const void* pSource, size_t size, TexMetadata* metadata, PNMRawImage& raw) noexcept
+{
+    raw.Release();
+    if (!pSource) return E_INVALIDARG;
+    const uint8_t* data = static_cast<const uint8_t*>(pSource);
+    // :163-167, :463-467: 'P', the kind, a white-space byte
+    if (size < 3 || data[0] != 'P' || !IsSpace(data[2])) return E_FAIL;
+    TexMetadata mdata;
+    const HRESULT hr = (data[1] == '3' || data[1] == '6') ? ParsePPM(data, size, mdata, raw) : ParsePFM(data, size, mdata, raw);
+    if (FAILED(hr)) { raw.Release(); return hr; }
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromPortablePixMapFileRaw(const char* szFile, TexMetadata* metadata, PNMRawImage& raw) noexcept
+{
+    raw.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    hr = LoadFromPortablePixMapMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), metadata, raw);
+    if (SUCCEEDED(hr) && !raw.ascii) raw.storage.Swap(file);          // the payload points into the file: keep it
+    return hr;
+}
+
+HRESULT GetMetadataFromPortablePixMapMemory(const void* pSource, size_t size, TexMetadata& metadata) noexcept
+{
+    PNMRawImage raw;
+    return LoadFromPortablePixMapMemoryRaw(pSource, size, &metadata, raw);
+}
+
+HRESULT GetMetadataFromPortablePixMapFile(const char* szFile, TexMetadata& metadata) noexcept
+{
+    PNMRawImage raw;
+    return LoadFromPortablePixMapFileRaw(szFile, &metadata, raw);
+}
+
+HRESULT LoadFromPortablePixMapMemory(const void* pSource, size_t size, TexMetadata* metadata, ScratchImage& image) noexcept
+{
+    image.Release();          // on any failure the result is empty
+    TexMetadata mdata; PNMRawImage raw;
+    HRESULT hr = LoadFromPortablePixMapMemoryRaw(pSource, size, &mdata, raw);
+    if (FAILED(hr)) return hr;
+    hr = image.Initialize2D(mdata.format, mdata.width, mdata.height, 1, 1);
+    if (FAILED(hr)) return hr;
+    const Image* img = image.GetImage(0, 0, 0);
+    if (!img) { image.Release(); return E_POINTER; }
+    if (raw.ascii)
+        for (size_t y = 0; y < img->height; ++y) std::memcpy(img->pixels + y * img->rowPitch, raw.payload + y * img->width * 4, img->width * 4);
+    else
+    {
+        const int kind = int(raw.kind);
+        const size_t B = dxtex::pnm_file_bytes(kind), D = dxtex::pnm_image_bytes(kind);
+        uint32_t table[256];
+        const uint32_t* scale = nullptr;
+        if (kind == dxtex::PNM_P6 && raw.maxval != 255) { for (uint32_t i = 0; i < 256; ++i) table[i] = dxtex::pnm_scale(i, raw.maxval); scale = table; }
+        const uint8_t* s = raw.payload;
+        for (size_t y = 0; y < img->height; ++y)
+        {
+            uint8_t* d = img->pixels + size_t(dxtex::pnm_image_row(kind, uint32_t(y), uint32_t(img->height))) * img->rowPitch;
+            for (size_t x = 0; x < img->width; ++x, s += B, d += D) dxtex::pnm_unpack_texel(s, d, kind, raw.bigEndian, scale);
+        }
+    }
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromPortablePixMapFile(const char* szFile, TexMetadata* metadata, ScratchImage& image) noexcept
+{
+    image.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    const HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    return LoadFromPortablePixMapMemory(file.GetBufferPointer(), file.GetBufferSize(), metadata, image);
+}
+
+HRESULT SaveToPortablePixMapMemory(const Image& image, Blob& blob) noexcept { return SaveHost(image, false, blob); }
+HRESULT SaveToPortablePixMapHDRMemory(const Image& image, Blob& blob) noexcept { return SaveHost(image, true, blob); }
+
+HRESULT SaveToPortablePixMapFile(const Image& image, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveHost(image, false, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+
+HRESULT SaveToPortablePixMapHDRFile(const Image& image, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveHost(image, true, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+
+// ---- resident forms: the samples travel as the file has them, the per-texel pass runs on the device (dxtex_pnm_unpack_device / dxtex_pnm_pack_device) ----
+HRESULT UploadPortablePixMapRaw(Device& device, const TexMetadata& metadata, const PNMRawImage& raw, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!device) return E_POINTER;
+    if (!raw.payload || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1) return E_INVALIDARG;
+    HRESULT hr = image.Initialize(device, metadata);
+    if (FAILED(hr)) return hr;
+    const Image* img = image.GetImage(0, 0, 0);
+    if (!img) { image.Release(); return E_POINTER; }
+    if (raw.ascii)
+    {
+        // a P3 file's texels were decoded on the host, byte-serially, into the image's own words: tight rows into the image's pitch
+        if (raw.payloadBytes != img->width * img->height * 4) { image.Release(); return E_INVALIDARG; }
+        hr = img->rowPitch == img->width * 4 ? dxtex_memcpy_h2d(device.Get(), img->pixels, raw.payload, raw.payloadBytes) : E_UNEXPECTED;
+    }
+    else
+    {
+        // the payload goes to the start of an allocation of its own - whatever the header's length, the samples start aligned and a width
+        // that is a multiple of four takes the wide route
+        DeviceTemp temp(device);
+        hr = dxtex_device_alloc(device.Get(), raw.payloadBytes, &temp.p);
+        if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.payload, raw.payloadBytes);          // the caller's bytes are free to go on return
+        if (SUCCEEDED(hr))
+        {
+            const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
+            hr = dxtex_pnm_unpack_device(device.Get(), temp.p, raw.payloadBytes, raw.kind, raw.maxval, raw.bigEndian ? DXTEX_PNM_BIG_ENDIAN : 0u, &d);
+        }
+    }
+    if (FAILED(hr)) image.Release();
+    return hr;
+}
+
+HRESULT LoadFromPortablePixMapMemory(Device& device, const void* pSource, size_t size, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    image.Release();          // on any failure the result is empty
+    TexMetadata mdata; PNMRawImage raw;
+    HRESULT hr = LoadFromPortablePixMapMemoryRaw(pSource, size, &mdata, raw);
+    if (FAILED(hr)) return hr;
+    hr = UploadPortablePixMapRaw(device, mdata, raw, image);
+    if (FAILED(hr)) return hr;
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromPortablePixMapFile(Device& device, const char* szFile, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    const HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    return LoadFromPortablePixMapMemory(device, file.GetBufferPointer(), file.GetBufferSize(), metadata, image);
+}
+
+HRESULT SaveToPortablePixMapMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept { return SaveResident(device, deviceImage, false, blob); }
+HRESULT SaveToPortablePixMapHDRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept { return SaveResident(device, deviceImage, true, blob); }
+
+HRESULT SaveToPortablePixMapFile(Device& device, const Image& deviceImage, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveResident(device, deviceImage, false, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+
+HRESULT SaveToPortablePixMapHDRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveResident(device, deviceImage, true, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+} // namespace DirectXTexAMD

@@ -6,7 +6,8 @@
 // (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
 // rotations, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
-//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga>...        (-ft hdr | tga: Radiance / TGA output of level 0)
+//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm>...
+//                          (-ft hdr | tga | ppm | pfm: Radiance / TGA / portable pixmap output of level 0)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
 //     -m <n>               mip levels, 0 = full chain           -fl <9.1 .. 12.2> feature level: largest texture side allowed
 //     -f <format>          DXGI format name or number           -if <filter>      POINT LINEAR CUBIC FANT BOX TRIANGLE
@@ -97,7 +98,7 @@ struct Options
 {
     size_t width = 0, height = 0, mipLevels = 0, maxSize = 16384;          // mipLevels 0: keep a chain the input has, else build the full one
     bool pow2 = false, pmalpha = false, demul = false, dx10 = false, dx9 = false, sepalpha = false, lower = false, overwrite = false,
-         timing = false, nologo = false, hdrOut = false, tgaOut = false, tga20 = false, info = false;
+         timing = false, nologo = false, hdrOut = false, tgaOut = false, ppmOut = false, pfmOut = false, tga20 = false, info = false;
     uint32_t format = 0, filter = 0, filterOpts = 0, srgb = 0, convert = 0, compress = 0, ddsRead = DDS_FLAGS_ALLOW_LARGE_FILES;
     float alphaThreshold = TEX_THRESHOLD_DEFAULT, keepCoverage = 0.f;
     bool nmap = false;                  // -nmap: ComputeNormalMap replaces the convert step
@@ -141,7 +142,8 @@ int usage()
                          "                 [-swizzle MASK] [-tonemap] [-c RRGGBB] [-inverty] [-reconstructz]\n"
                          "                 [--rotate-color 709toHDR10|HDR10to709|709to2020|2020to709|P3D65toHDR10|P3D65to2020|709toP3D65|P3D65to709] [--paper-white-nits N]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
-                         "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N] -o <out.dds | dir> in.dds...\n");
+                         "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N]\n"
+                         "                 [-ft dds|hdr|tga|ppm|pfm] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm>...\n");
     return 1;
 }
 
@@ -284,7 +286,9 @@ bool Parse(int argc, char** argv, Options& o)
             const char* ft = next();
             if (!strcasecmp(ft, "hdr")) o.hdrOut = true;
             else if (!strcasecmp(ft, "tga")) o.tgaOut = true;
-            else if (strcasecmp(ft, "dds")) { std::fprintf(stderr, "output file types: dds, hdr, tga\n"); return false; }
+            else if (!strcasecmp(ft, "ppm")) o.ppmOut = true;
+            else if (!strcasecmp(ft, "pfm")) o.pfmOut = true;
+            else if (strcasecmp(ft, "dds")) { std::fprintf(stderr, "output file types: dds, hdr, tga, ppm, pfm\n"); return false; }
         }
         else if (a == "-r" || a == "-nogpu" || a == "-singleproc") { }            // nothing to switch here
         else if (a[0] == '-') { std::fprintf(stderr, "unknown or unsupported option %s\n", a.c_str()); return false; }
@@ -301,11 +305,12 @@ bool Parse(int argc, char** argv, Options& o)
 // <out> names a file when it ends in .dds and there is one input; otherwise a directory that receives <px><name><sx>.dds
 std::string OutputName(const Options& o, const std::string& input)
 {
-    auto endsDDS = [](const std::string& s) { return s.size() > 4 && (!strcasecmp(s.c_str() + s.size() - 4, ".dds") || !strcasecmp(s.c_str() + s.size() - 4, ".hdr") || !strcasecmp(s.c_str() + s.size() - 4, ".tga")); };
+    auto endsDDS = [](const std::string& s) { return s.size() > 4 && (!strcasecmp(s.c_str() + s.size() - 4, ".dds") || !strcasecmp(s.c_str() + s.size() - 4, ".hdr") || !strcasecmp(s.c_str() + s.size() - 4, ".tga") ||
+                                                                      !strcasecmp(s.c_str() + s.size() - 4, ".ppm") || !strcasecmp(s.c_str() + s.size() - 4, ".pfm")); };
     if (o.inputs.size() == 1 && endsDDS(o.out) && o.prefix.empty() && o.suffix.empty()) return o.out;
     std::string base = input.substr(input.find_last_of('/') == std::string::npos ? 0 : input.find_last_of('/') + 1);
     if (base.find_last_of('.') != std::string::npos) base.erase(base.find_last_of('.'));
-    std::string name = o.prefix + base + o.suffix + (o.hdrOut ? ".hdr" : o.tgaOut ? ".tga" : ".dds");
+    std::string name = o.prefix + base + o.suffix + (o.hdrOut ? ".hdr" : o.tgaOut ? ".tga" : o.ppmOut ? ".ppm" : o.pfmOut ? ".pfm" : ".dds");
     if (o.lower) std::transform(name.begin(), name.end(), name.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     return o.out + "/" + name;
 }
@@ -337,9 +342,13 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     // Radiance RGBE -> RGBA32F: the resident loader sends the file's texels up as the 4 bytes they are and makes the floats on the device
     DeviceScratchImage image;
     const bool hdrIn = hasExt(inFile, ".hdr"), tgaIn = hasExt(inFile, ".tga");
+    const bool pnmIn = hasExt(inFile, ".ppm") || hasExt(inFile, ".pfm") || hasExt(inFile, ".phm");
     if (hdrIn) check("load", LoadFromHDRFile(dev, inFile.c_str(), &info, image));
     // TGA likewise: the file's 1 to 4 bytes a texel go up, the swizzle, the flips and the alpha rule run on the device
     else if (tgaIn) check("load", LoadFromTGAFile(dev, inFile.c_str(), TGA_FLAGS_NONE, &info, image));
+    // portable pixmaps likewise: the samples behind the text header go up as they are, 3 bytes to 4 (or 3 elements to 4), the byte swap and
+    // the vertical flip run on the device
+    else if (pnmIn) check("load", LoadFromPortablePixMapFile(dev, inFile.c_str(), &info, image));
     // DDS likewise: the payload goes up at the size it has in the file - a native file straight into the image's memory, a legacy one through
     // the row conversions on the device
     else check("load", LoadFromDDSFile(dev, inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, image));
@@ -577,19 +586,24 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     // --- the one download, by the resident writers: the payload comes down straight behind the file's header
     // -ft hdr: level 0 of the first item, like texconv's non-DDS codecs, comes back as RGBE rows the resident saver made on the device
     // -ft tga likewise: the file's rows (-tga20: and the TGA 2.0 extension area around them)
+    // -ft ppm / pfm likewise: the file's samples, alpha dropped, halves widened and the rows of a .pfm flipped on the device
     uint32_t ddsFlags = DDS_FLAGS_NONE;
     if (o.dx10) ddsFlags |= DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2;
     else if (o.dx9) ddsFlags |= DDS_FLAGS_FORCE_DX9_LEGACY;
-    if ((o.hdrOut || o.tgaOut) && handThrough)
+    if ((o.hdrOut || o.tgaOut || o.ppmOut || o.pfmOut) && handThrough)
     {
         // blocks handed through: the host codec's answer
         ScratchImage result;
         check("download", image.Download(result));
         if (o.hdrOut) check("save", SaveToHDRFile(result.GetImages()[0], outFile.c_str()));
+        else if (o.ppmOut) check("save", SaveToPortablePixMapFile(result.GetImages()[0], outFile.c_str()));
+        else if (o.pfmOut) check("save", SaveToPortablePixMapHDRFile(result.GetImages()[0], outFile.c_str()));
         else check("save", SaveToTGAFile(result.GetImages()[0], TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));      // -tga20: with the TGA 2.0 extension area
     }
     else if (o.hdrOut) check("save", SaveToHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
     else if (o.tgaOut) check("save", SaveToTGAFile(dev, *image.GetImage(0, 0, 0), TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));
+    else if (o.ppmOut) check("save", SaveToPortablePixMapFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
+    else if (o.pfmOut) check("save", SaveToPortablePixMapHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
     else check("save", SaveToDDSFile(dev, image.GetImages(), image.GetImageCount(), info, DDS_FLAGS(ddsFlags), outFile.c_str()));
     image.Release();
     std::printf("writing %s (%zux%zu", outFile.c_str(), info.width, info.height);
@@ -614,6 +628,7 @@ int PrintInfo(const Options& o)
         auto hasExt = [&](const char* ext) { const size_t n = std::strlen(ext); return f.size() > n && !strcasecmp(f.c_str() + f.size() - n, ext); };
         TexMetadata m;
         const HRESULT hr = hasExt(".hdr") ? GetMetadataFromHDRFile(f.c_str(), m) : hasExt(".tga") ? GetMetadataFromTGAFile(f.c_str(), TGA_FLAGS_NONE, m)
+                           : (hasExt(".ppm") || hasExt(".pfm") || hasExt(".phm")) ? GetMetadataFromPortablePixMapFile(f.c_str(), m)
                                                                                                    : GetMetadataFromDDSFile(f.c_str(), DDS_FLAGS(o.ddsRead), m);
         if (FAILED(hr)) { std::printf("%s: FAILED (%08X)\n", f.c_str(), unsigned(hr)); ++failures; continue; }
         const char* name = "";

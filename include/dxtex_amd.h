@@ -37,6 +37,8 @@
  *     SaveToTGAMemory
  *   CopyImage's row conversions, the 24-bit    DirectXTexDDS.cpp:1518-1808     dxtex_dds_unpack / dxtex_dds_pack24
  *     rows of SaveToDDSMemory
+ *   LoadFromPortablePixMap[HDR]'s texel loops, Texconv/PortablePixMap.cpp      dxtex_pnm_unpack / dxtex_pnm_pack
+ *     the rows of SaveToPortablePixMap[HDR]      :209-223, :595-681, :392-422, :720-735
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -408,6 +410,42 @@ dxtex_hresult dxtex_dds_pack24(dxtex_ctx* ctx, const dxtex_image* srcs, const si
 dxtex_hresult dxtex_dds_unpack_device(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
                                       const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count);
 dxtex_hresult dxtex_dds_pack24_device(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes);
+
+/* Portable pixmap (.ppm, .pfm, .phm) texels, the per-texel half of the codec (the text header is byte-serial and stays with the caller,
+ * as do the ASCII samples of a P3 file). One image per call. The file side is the samples behind the header: tight rows of width * texel
+ * bytes; a .ppm is top-down, a .pfm / .phm stores the image's bottom row first. At least width * height * texel bytes; more are ignored.
+ *   unpack   samples -> dst, through dst's pitch (LoadFromPortablePixMap[HDR], Texconv/PortablePixMap.cpp:209-223, :595-681):
+ *              kind           file texel      dst->format           texel
+ *              DXTEX_PNM_P6   3 bytes R G B   R8G8B8A8_UNORM        c_i = 255 * byte_i / maxval (integer), c_0 | c_1 << 8 | c_2 << 16 | 0xff000000
+ *                                                                   in 32-bit unsigned arithmetic: no clamp, a sample above maxval spills upwards
+ *              DXTEX_PNM_PF   3 x f32         R32G32B32A32_FLOAT    the elements, alpha 1.0f
+ *              DXTEX_PNM_Pf   1 x f32         R32_FLOAT             the element
+ *              DXTEX_PNM_PH   3 x f16         R16G16B16A16_FLOAT    the elements, alpha 0x3c00
+ *              DXTEX_PNM_Ph   1 x f16         R16_FLOAT             the element
+ *            DXTEX_PNM_BIG_ENDIAN swaps the bytes of every 2- or 4-byte element; nothing else looks at a float's bits. maxval is read by
+ *            DXTEX_PNM_P6 only.
+ *   pack     level 0 of src -> the samples the writer emits (SaveToPortablePixMap[HDR], :361-443, :688-758):
+ *              DXTEX_PNM_P6   R8G8B8A8_UNORM[_SRGB], B8G8R8A8_UNORM[_SRGB], B8G8R8X8_UNORM[_SRGB] -> R, G, B, top-down
+ *              DXTEX_PNM_PF   R32G32B32A32_FLOAT, R32G32B32_FLOAT, R16G16B16A16_FLOAT (widened exactly) -> 3 little-endian floats, bottom row first
+ *              DXTEX_PNM_Pf   R32_FLOAT -> 1 little-endian float, bottom row first
+ *            DXTEX_PNM_PH and DXTEX_PNM_Ph are never written (NOT_SUPPORTED).
+ * HRESULTs, in this order: E_POINTER for null samples, image or pixels; E_INVALIDARG for an unknown kind, a maxval outside 1..255 with
+ * DXTEX_PNM_P6, unknown flag bits, a width, height or sampleBytes of zero; NOT_SUPPORTED for a kind and format that do not pair up per the
+ * tables; E_INVALIDARG for sampleBytes below width * height * texel bytes, a row pitch smaller than the row, or samples that overlap the
+ * pixels. Bytes of the image outside width * texel bytes of each row, and samples behind width * height * texel bytes, are not written. */
+#define DXTEX_PNM_P6          0u
+#define DXTEX_PNM_PF          1u
+#define DXTEX_PNM_Pf          2u
+#define DXTEX_PNM_PH          3u
+#define DXTEX_PNM_Ph          4u
+#define DXTEX_PNM_BIG_ENDIAN  0x1u
+/* host pointers, through the context's staging: the samples go up as they are, the rows come down through the image's pitch */
+dxtex_hresult dxtex_pnm_unpack(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst);
+dxtex_hresult dxtex_pnm_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes);
+/* device pointers: asynchronous on the context's stream. The samples may start at any byte; see csrc/pnm.hip for the alignment that takes
+ * the wide route (a width that is a multiple of 4, samples on a multiple of 4, 8 or 16 bytes by kind, image rows on 16). */
+dxtex_hresult dxtex_pnm_unpack_device(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst);
+dxtex_hresult dxtex_pnm_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
