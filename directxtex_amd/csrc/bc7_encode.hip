@@ -46,7 +46,7 @@ struct Bc7Args
     uint32_t* px;            // nblocks x 16 packed RGBA8 texels (D3DX_BC7::Encode's aLDRPixels, :2792-2799)
     struct TaskRec* recs;    // per-mode task records (reused by every mode)
     uint2* order;            // live tasks of the current mode, sorted by subset size: (task, tinfo)
-    uint32_t* tinfo;         // per task: texel mask | rotation << 16 | subset size << 24 (size 0 = no search needed)
+    uint32_t* tinfo;         // per task: texel mask | rotation << 16 | (leader's task + 1) << 18 for an alias | subset size << 24 (size 0 = no search needed)
     uint32_t* counters;      // 35 words, see bc7_bin_* kernels
     uint32_t* zeroOrd;       // per block: evaluation-order key of the first candidate (in Encode's order) known to reach error 0;
                              // Encode() returns there (:2803, :2835, :2845), so later candidates are never looked at
@@ -56,6 +56,8 @@ struct Bc7Args
                              // derives (:3526-3552) for the shapes Refine will look at (the fits of the other shapes are never read again)
     int* bestErr;            // per block: smallest error an already finished mode reached (subset_lower_bound prunes against it)
     int prune;               // 0 = search every candidate like the reference does (DXTEX_BC7_NO_PRUNE, for A/B runs)
+    int alias;               // 0 = search every one-colour subset of a block from scratch (DXTEX_BC7_NO_ALIAS, for A/B runs), see bc7_pre_kernel
+    uint32_t* aliased;       // development build only: per candidate slot, the tasks of the pass that pre made aliases (DXTEX_BC7_STATS)
     const uint32_t* flagged; // [0] = blocks of this pass flagged for an early mode 6, [1] = blocks with alpha (bc7_flag_count_kernel)
     uint32_t early6Min;      // the early phase of mode 6 only exists when at least this many blocks would be in it
     uint32_t earlyAlphaMin;  // ... and the early phases of modes 4 / 5 (blocks with alpha) when at least this many
@@ -468,10 +470,49 @@ __global__ void __launch_bounds__(256, (MODE == 4 || MODE == 5) ? DXTEX_PP45_WGS
         if (nb < a.nblocks && blk < uint32_t(BPW)) table = min(table, a.bestErr[nb]);
         if (candLb > table) npLive = 0;
     }
+    // One-colour subsets: search each of a block once. subset_lower_bound is <= 0 for them, so the pruning above never drops one,
+    // and in a flat block all 32 tasks of a two-subset mode are the same problem. Every decision of OptimizeOne (:3045-3110, PerturbOne
+    // :2926-2966, Exhaustive :2971-3042) is a strict comparison between MapColors sums or the test fOrgErr == 0; over n copies of one
+    // texel each such sum is n x its one-texel value (exact integers below 2^24), and MapColors' early-out hands back a partial sum that
+    // is already above its threshold. Two one-colour subsets of the same RGBA8 word that start from the same quantised endpoints
+    // therefore take the same decisions whatever their sizes and end on the same endpoints (tests/cpp/bc7_solid_check.cpp holds the
+    // reference to that). post recomputes all it emits from the endpoints over the task's own texels, so a live task whose key
+    // (word, A, B) an earlier live task of the block has already shown becomes that task's ALIAS: size 0 - the bin and the search kernels
+    // never see it - and the leader's r + 1 in tinfo's bits 18..23 (0 = none; the leader is earlier, so r + 1 <= 63), for post to fetch the
+    // leader's endpoints. Wave-uniform: one round per distinct key of the wavefront, none where no live task is of one colour.
+    uint32_t aliasTag = 0;
+    if constexpr (TM::NS >= 2) if (a.alias)
+    {
+        const uint32_t* pix = &sL[wave][blk * 16];
+        uint32_t word = 0;
+        bool pending = false;
+        if (active && npLive)
+        {
+            word = pix[__ffs(int(mask)) - 1];
+            uint32_t diff = 0;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) if ((mask >> i) & 1u) diff |= pix[i] ^ word;
+            pending = diff == 0;
+        }
+        for (unsigned long long todo = __ballot(pending); todo != 0; todo = __ballot(pending))
+        {
+            const int first = __ffsll(todo) - 1;       // the smallest pending r of the first block that has one: the leader of its key
+            const uint32_t w0 = uint32_t(__shfl(int(word), first)), a0 = uint32_t(__shfl(int(rec.A), first)), b0 = uint32_t(__shfl(int(rec.B), first));
+            if (pending && (lane / int(TM::TPB)) == (first / int(TM::TPB)) && word == w0 && rec.A == a0 && rec.B == b0)
+            {
+                pending = false;
+                if (lane != first) { aliasTag = uint32_t(first % int(TM::TPB)) + 1u; npLive = 0; }
+            }
+        }
+#if defined(DXTEX_DEV)
+        const unsigned long long tagged = __ballot(aliasTag != 0);
+        if (tagged && lane == 0) atomicAdd(&a.aliased[TM::SLOT], uint32_t(__popcll(tagged)));
+#endif
+    }
     if (nb < a.nblocks && blk < uint32_t(BPW))
     {
         a.recs[uint64_t(nb) * TM::TPB + r] = rec;
-        a.tinfo[uint64_t(nb) * TM::TPB + r] = (mask & 0xFFFFu) | (rot << 16) | (npLive << 24);
+        a.tinfo[uint64_t(nb) * TM::TPB + r] = (mask & 0xFFFFu) | (rot << 16) | (aliasTag << 18) | (npLive << 24);
     }
 }
 
@@ -1327,7 +1368,20 @@ __global__ void __launch_bounds__(256, (MODE == 4 || MODE == 5) ? DXTEX_PP45_WGS
         task_org<MODE, IM, false>(nullptr, &sL[wave][blk * 16], mask, anchor, rot, res, np, true, rg, b16,
                                   (TM::NS == 2) ? a.seeds + uint64_t(nb) * 64 + (TM::LIST ? 32 : 0) + r
                                                 : (TM::NS == 1) ? a.seeds1 + uint64_t(nb) * 2 : a.seeds3 + uint64_t(nb) * 192 + shape * 3 + (r % TM::G));
-        const TaskRec rec = a.recs[uint64_t(nb) * TM::TPB + r];
+        TaskRec rec = a.recs[uint64_t(nb) * TM::TPB + r];
+        if constexpr (TM::NS >= 2)
+        {
+            // an alias (bc7_pre_kernel) takes the endpoints its leader's search ended on; its unoptimised error is its own. The leader's
+            // record is read from memory, not from the leader's lane: task_geometry is evaluated again here and zeroOrd may have dropped
+            // since pre, but an alias never ranks before its leader in Encode's order, so a leader whose lane is inactive now leaves
+            // only aliases that are inactive too, and an active alias finds the finished record whatever its leader's lane does.
+            const uint32_t leader = (a.tinfo[uint64_t(nb) * TM::TPB + r] >> 18) & 63u;
+            if (leader)
+            {
+                const TaskRec lead = a.recs[uint64_t(nb) * TM::TPB + (leader - 1u)];
+                rec.A = lead.A; rec.B = lead.B;
+            }
+        }
         res.orgErr = rec.orgErr;
         if (TM::NS == 1) refine_post<MODE, IM>(b16, rec.A, rec.B, 0u, res);
         else refine_post<MODE, IM>(rg, rec.A, rec.B, anchor, res);
@@ -1613,7 +1667,9 @@ void launch_mode(const Bc7Args& a0, hipStream_t stream, KernelMarks* marks, cons
         uint32_t c[40] = {};
         (void)hipStreamSynchronize(stream);
         (void)hipMemcpy(c, a.counters, sizeof(c), hipMemcpyDeviceToHost);
-        std::fprintf(stderr, "bc7 stats %-22s phase %d: %9u task slots, %9u live; by size 16..1:", names[0], a.phase, ntasks, c[34]);
+        uint32_t aliased = 0;             // the slot's counter is zeroed per pass, and a mode that elects is launched once per pass
+        if (TM::NS >= 2) (void)hipMemcpy(&aliased, a.aliased + TM::SLOT, sizeof(aliased), hipMemcpyDeviceToHost);
+        std::fprintf(stderr, "bc7 stats %-22s phase %d: %9u task slots, %9u live, %9u aliased; by size 16..1:", names[0], a.phase, ntasks, c[34], aliased);
         for (int b = 16; b >= 1; --b) std::fprintf(stderr, " %u", c[b]);
         std::fprintf(stderr, "\n");
     }
@@ -1744,12 +1800,15 @@ hipError_t launch_bc7_encode_many(const BcImage* images, size_t count, uint32_t 
         a.seeds3 = reinterpret_cast<uint2*>(base + L.seeds3);
         static const bool noPrune = dev_env("DXTEX_BC7_NO_PRUNE") != nullptr;
         a.prune = noPrune ? 0 : 1;
+        static const bool noAlias = dev_env("DXTEX_BC7_NO_ALIAS") != nullptr;
+        a.alias = noAlias ? 0 : 1;
         static const int early6 = dev_env("DXTEX_BC7_EARLY6_PCT") ? atoi(dev_env("DXTEX_BC7_EARLY6_PCT")) : 100;
         a.early6Pct = early6;
         uint32_t slotMask = 0;
 
         uint32_t* flagCount = reinterpret_cast<uint32_t*>(base + L.flagcnt);
         a.flagged = flagCount;
+        a.aliased = flagCount + 48;      // [48 + slot]; zeroed with the flags below (BC7_QUICK has no mode that elects)
         // Mode 6's early phase costs its own search (5 ms for the 42 % of the benchmark image's blocks it takes) and buys pruning in modes 1 / 3; since
         // round 5's cheaper Exhaustive it only pays when at least half of the blocks are in it (131.8 -> 130.7 ms without it on the benchmark image)
         // (a small submission runs the early phase on a side stream of the plan below, next to modes 1 / 3: there it costs nothing and a quarter

@@ -62,6 +62,48 @@ static void seeds2(const HostBlock& b, uint32_t shape, int region, Region& rg, u
     anchor = region ? kAnchor2[shape] : 0;
 }
 
+// bc7_pre_kernel's election of one-colour subsets, per block and mode: a live task (unoptimised error != 0) whose texels are one
+// RGBA8 word takes the optimised endpoints of the first earlier live task with the same (word, unoptimised endpoints) instead of a
+// search of its own. g_elect = the leaders of the block and mode in hand; nullptr = every subset searched (the stage-by-stage
+// comparison after a mismatch, DXTEX_HOST_NO_ALIAS).
+struct SolidLeader { uint32_t word, orgA, orgB, optA, optB; };
+static std::vector<SolidLeader>* g_elect = nullptr;
+static long g_electTasks = 0, g_electAliased = 0, g_electRepeat = 0, g_electOtherStart = 0;
+
+template<int MODE>
+static void refine_subset_elect(const Region& rg, const HostBlock& b, uint32_t mask, uint32_t A, uint32_t B, uint32_t anchor, SubsetResult& out)
+{
+    if (!g_elect) { refine_subset<MODE, 0>(rg, A, B, anchor, out); return; }
+    refine_pre<MODE, 0>(rg, A, B, anchor, out);
+    ++g_electTasks;
+    const uint32_t word = b.ldr[__builtin_ctz(mask)];
+    bool solid = out.orgErr != 0;
+    for (int i = 0; i < 16; ++i) if (((mask >> i) & 1u) && b.ldr[i] != word) solid = false;
+    uint32_t oa = 0, ob = 0;
+    bool aliased = false;
+    if (solid)
+    {
+        bool repeat = false;
+        for (const SolidLeader& l : *g_elect)
+        {
+            if (l.word != word) continue;
+            repeat = true;
+            if (l.orgA == out.orgA && l.orgB == out.orgB) { oa = l.optA; ob = l.optB; aliased = true; break; }
+        }
+        g_electRepeat += repeat; g_electOtherStart += repeat && !aliased; g_electAliased += aliased;
+    }
+    if (!aliased)
+    {
+#if defined(DXTEX_BC7_USE_LOCKSTEP)
+        optimize_one_lockstep<MODE, 0>(rg, out.orgErr, out.orgA, out.orgB, oa, ob);
+#else
+        optimize_one<MODE, 0>(rg, out.orgErr, out.orgA, out.orgB, oa, ob);
+#endif
+        if (solid) g_elect->push_back({ word, out.orgA, out.orgB, oa, ob });
+    }
+    refine_post<MODE, 0>(rg, oa, ob, anchor, out);
+}
+
 template<int MODE>
 static Cand refine2_one(const HostBlock& b, uint32_t shape, int rank)
 {
@@ -70,11 +112,12 @@ static Cand refine2_one(const HostBlock& b, uint32_t shape, int rank)
     {
         Region rg; uint32_t A, B, anchor;
         seeds2(b, shape, region, rg, A, B, anchor);
+        const uint32_t regionMask = region ? uint32_t(kPart2Mask[shape]) : ((~uint32_t(kPart2Mask[shape])) & 0xFFFFu);
 #if defined(DXTEX_TABLE_STATS)
         { const uint32_t m1 = kPart2Mask[shape]; const uint32_t mo = region ? ((~m1) & 0xFFFF) : m1;      // the OTHER region
           g_statOther = subset_lower_bound(b.ldr, mo, 0u, (MODE >= 6) ? 4 : 3); }
 #endif
-        refine_subset<MODE, 0>(rg, A, B, anchor, r[region]);
+        refine_subset_elect<MODE>(rg, b, regionMask, A, B, anchor, r[region]);
     }
     const int orgTot = r[0].orgErr + r[1].orgErr, optTot = r[0].optErr + r[1].optErr;
     const bool useOpt = optTot < orgTot;
@@ -117,7 +160,7 @@ static Cand refine3_one(const HostBlock& b, uint32_t shape, int rank)
     {
         Region rg; uint32_t A, B;
         seeds3(b, shape, region, rg, A, B);
-        refine_subset<MODE, 0>(rg, A, B, anchor[region], r[region]);
+        refine_subset_elect<MODE>(rg, b, mask3(shape, region), A, B, anchor[region], r[region]);
         orgTot += r[region].orgErr; optTot += r[region].optErr;
     }
     const bool useOpt = optTot < orgTot;
@@ -248,6 +291,7 @@ int main(int argc, char** argv)
         fclose(f);
         if (got != tileFile.size()) { printf("%s: short read\n", argv[4]); return 2; }
     }
+    const bool noAlias = getenv("DXTEX_HOST_NO_ALIAS") != nullptr;
     int nbad = 0;
     for (int t = 0; t < ntiles; ++t)
     {
@@ -276,6 +320,9 @@ int main(int argc, char** argv)
         rough_lists(hb, e3, e2, l3, l2);
         Cand best; best.valid = false;
         Cand perMode[8]; for (auto& c : perMode) c.valid = false;
+        // the election starts afresh with every mode of every block, as every launch of bc7_pre_kernel does
+        std::vector<SolidLeader> leaders;
+        auto fresh = [&] { leaders.clear(); g_elect = noAlias ? nullptr : &leaders; };
         if (!quick)
         {
             if (use3)
@@ -283,13 +330,14 @@ int main(int argc, char** argv)
                 uint32_t m0[4], m2[16];
                 rough_list3<3>(hb, 16, 4, m0);            // mode 0: 16 shapes, 3-bit indices, the best max(1, 16 / 4)
                 rough_list3<2>(hb, 64, 16, m2);           // mode 2: 64 shapes, 2-bit indices, the best 16
-                for (int i = 0; i < 4; ++i) better(perMode[0], refine3_one<0>(hb, m0[i], i));
-                for (int i = 0; i < 16; ++i) better(perMode[2], refine3_one<2>(hb, m2[i], i));
+                fresh(); for (int i = 0; i < 4; ++i) better(perMode[0], refine3_one<0>(hb, m0[i], i));
+                fresh(); for (int i = 0; i < 16; ++i) better(perMode[2], refine3_one<2>(hb, m2[i], i));
             }
 #if defined(DXTEX_TABLE_STATS)
             {
                 // first pass without statistics: what the block ends up with (the optimistic table), and mode 6 / mode 1 alone (what is
                 // on the table when mode 1 / mode 3 start in the kernels' order)
+                g_elect = nullptr;            // the statistics are of every subset's own search
                 g_statTable = g_statTablePrev = 0x7FFFFFFF;
                 long sv[3][8]; memcpy(sv[0], g_tabWin, sizeof(g_tabWin)); memcpy(sv[1], g_tabWinOut, sizeof(g_tabWin)); memcpy(sv[2], g_tabWinOutPrev, sizeof(g_tabWin));
                 Cand b6 = refine1_one<6, 0>(hb, 0), b1; b1.valid = false; Cand b3; b3.valid = false;
@@ -304,14 +352,16 @@ int main(int argc, char** argv)
                 g_statTable = g_statTablePrev = 0x7FFFFFFF;
             }
 #else
-            for (int i = 0; i < 16; ++i) better(perMode[1], refine2_one<1>(hb, l3[i], i));
-            for (int i = 0; i < 16; ++i) better(perMode[3], refine2_one<3>(hb, l2[i], i));
+            fresh(); for (int i = 0; i < 16; ++i) better(perMode[1], refine2_one<1>(hb, l3[i], i));
+            fresh(); for (int i = 0; i < 16; ++i) better(perMode[3], refine2_one<3>(hb, l2[i], i));
 #endif
             for (uint32_t r = 0; r < 4; ++r) { better(perMode[4], refine1_one<4, 0>(hb, r)); better(perMode[4], refine1_one<4, 1>(hb, r)); }
             for (uint32_t r = 0; r < 4; ++r) better(perMode[5], refine1_one<5, 0>(hb, r));
         }
         better(perMode[6], refine1_one<6, 0>(hb, 0));
+        fresh();
         if (!quick && hb.hasAlpha) for (int i = 0; i < 16; ++i) better(perMode[7], refine2_one<7>(hb, l2[i], i));
+        g_elect = nullptr;
         for (int m = 0; m < 8; ++m) better(best, perMode[m]);
 
         uint64_t rlo, rhi; memcpy(&rlo, refBlk, 8); memcpy(&rhi, refBlk + 8, 8);
@@ -400,6 +450,10 @@ int main(int argc, char** argv)
             printf("\n");
         }
 #endif
+    if (g_electTasks)
+        printf("one-colour election: %ld of %ld subset tasks aliased (%.2f %%); of %ld live one-colour subsets that repeat an earlier one's colour, "
+               "%ld start from other endpoints (%.2f %%)\n", g_electAliased, g_electTasks, 100.0 * double(g_electAliased) / double(g_electTasks),
+               g_electRepeat, g_electOtherStart, g_electRepeat ? 100.0 * double(g_electOtherStart) / double(g_electRepeat) : 0.0);
     printf("%d of %d tiles differ\n", nbad, ntiles);
     return nbad ? 1 : 0;
 }
