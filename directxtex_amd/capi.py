@@ -152,6 +152,10 @@ _SIGS = {
     "dxtex_pnm_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _P(Image)]),
     "dxtex_pnm_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_pnm_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_png_unpack": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, _P(Image)]),
+    "dxtex_png_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, _P(Image)]),
+    "dxtex_png_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_png_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -839,6 +843,47 @@ class Context:
     def pnm_pack_device(self, src, kind, samples_ptr, sample_bytes):
         """dxtex_pnm_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
         self._check(self._lib.dxtex_pnm_pack_device(self._h, ctypes.byref(src), kind, samples_ptr, sample_bytes), "pnm_pack_device")
+
+    # -- PNG texels (the per-texel half of the .png codec) -------------------------------------------------------------------------------
+    @staticmethod
+    def _png_palette(palette):
+        """(pointer or None, count, the array to keep alive) of a palette given as R | G << 8 | B << 16 | A << 24 words"""
+        if palette is None:
+            return None, 0, None
+        words = np.ascontiguousarray(palette, np.uint32)
+        return words.ctypes.data, words.size, words
+
+    def png_unpack(self, rows, width, height, kind, fmt, flags=0, palette=None, row_pitch=None, out=None):
+        """dxtex_png_unpack: a file's unfiltered rows (host bytes, ceil(width * bits / 8) each) -> pixels of `fmt` as a numpy uint8 buffer
+        with `row_pitch` bytes a row, default tight. kind = PNG_*; flags = PNG_BGR; palette = up to 256 words for a palette kind. out: the
+        buffer to unpack into (so that a caller can see what is left untouched), default a zeroed one."""
+        rows = np.ascontiguousarray(rows, np.uint8)
+        pitch = compute_pitch(fmt, width, height)[0] if row_pitch is None else row_pitch
+        if out is None:
+            out = np.zeros(pitch * height, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.nbytes >= pitch * height
+        dst = Image(width, height, fmt, pitch, pitch * height, out.ctypes.data)
+        pal, count, _keep = self._png_palette(palette)
+        self._check(self._lib.dxtex_png_unpack(self._h, rows.ctypes.data, rows.nbytes, kind, flags, pal, count, ctypes.byref(dst)), "png_unpack")
+        return out
+
+    def png_pack(self, pixels, width, height, fmt, row_pitch=None, out=None):
+        """dxtex_png_pack: one image (host pixels) -> the file's rows, tight, as a numpy uint8 buffer (or the front of `out`)."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        if out is None:
+            out = np.zeros(width * height * 8, np.uint8)
+        self._check(self._lib.dxtex_png_pack(self._h, ctypes.byref(src), out.ctypes.data, out.nbytes), "png_pack")
+        return out
+
+    def png_unpack_device(self, rows_ptr, rows_bytes, kind, dst, flags=0, palette=None):
+        """dxtex_png_unpack_device: the rows at a device pointer -> the device Image `dst` (device_image), asynchronous on the stream."""
+        pal, count, _keep = self._png_palette(palette)
+        self._check(self._lib.dxtex_png_unpack_device(self._h, rows_ptr, rows_bytes, kind, flags, pal, count, ctypes.byref(dst)), "png_unpack_device")
+
+    def png_pack_device(self, src, rows_ptr, rows_bytes):
+        """dxtex_png_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
+        self._check(self._lib.dxtex_png_pack_device(self._h, ctypes.byref(src), rows_ptr, rows_bytes), "png_pack_device")
 
     # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
     @staticmethod

@@ -7,6 +7,7 @@
 #include "dxtex_tga.h"
 #include "dxtex_dds.h"
 #include "dxtex_pnm.h"
+#include "dxtex_png.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -1919,6 +1920,138 @@ dxtex_hresult dxtex_pnm_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t ki
     if (hr != DXTEX_S_OK) return hr;
     return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, samples, need,
                       [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_pnm_pack(view_of(with_pixels(*src, in)), source, out, ctx->stream, marks_of(ctx))); });
+}
+
+namespace
+{
+static_assert(DXTEX_PNG_G1 == PNG_G1 && DXTEX_PNG_G2 == PNG_G2 && DXTEX_PNG_G4 == PNG_G4 && DXTEX_PNG_G8 == PNG_G8 && DXTEX_PNG_G16 == PNG_G16 && DXTEX_PNG_GA8 == PNG_GA8 &&
+              DXTEX_PNG_GA16 == PNG_GA16 && DXTEX_PNG_RGB8 == PNG_RGB8 && DXTEX_PNG_RGB16 == PNG_RGB16 && DXTEX_PNG_RGBA8 == PNG_RGBA8 && DXTEX_PNG_RGBA16 == PNG_RGBA16 &&
+              DXTEX_PNG_P1 == PNG_P1 && DXTEX_PNG_P2 == PNG_P2 && DXTEX_PNG_P4 == PNG_P4 && DXTEX_PNG_P8 == PNG_P8 && DXTEX_PNG_BGR == PNG_BGR,
+              "dxtex_png.h's kinds and flag are the public ones");
+
+// the reader's table (include/dxtex_amd.h): whether a kind under these flags unpacks into this format
+bool png_unpack_pairs(uint32_t kind, uint32_t flags, int format)
+{
+    const bool bgr = (flags & PNG_BGR) != 0;
+    switch (kind)
+    {
+    case PNG_G1: case PNG_G2: case PNG_G4: case PNG_G8: return format == FMT_R8_UNORM;
+    case PNG_G16: return format == FMT_R16_UNORM;
+    case PNG_GA8: return format == (bgr ? FMT_B8G8R8A8_UNORM : FMT_R8G8B8A8_UNORM);          // g, g, g, a either way
+    case PNG_GA16: case PNG_RGB16: case PNG_RGBA16: return format == FMT_R16G16B16A16_UNORM;
+    case PNG_RGBA8: return bgr ? (format == FMT_B8G8R8A8_UNORM || format == FMT_B8G8R8A8_UNORM_SRGB) : (format == FMT_R8G8B8A8_UNORM || format == FMT_R8G8B8A8_UNORM_SRGB);
+    default: return bgr ? (format == FMT_B8G8R8X8_UNORM || format == FMT_B8G8R8X8_UNORM_SRGB) : (format == FMT_R8G8B8A8_UNORM || format == FMT_R8G8B8A8_UNORM_SRGB);          // RGB 8, palette
+    }
+}
+
+// the writer's table (WriteImage): the PngSource of a format; -1 for one outside it
+int png_pack_source(int format)
+{
+    switch (format)
+    {
+    case FMT_R8_UNORM: return PNG_SRC_R8;
+    case FMT_R16_UNORM: return PNG_SRC_R16;
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return PNG_SRC_RGBA8;
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: return PNG_SRC_BGRA8;
+    case FMT_R16G16B16A16_UNORM: return PNG_SRC_RGBA16;
+    case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return PNG_SRC_BGRX8;
+    default: return -1;
+    }
+}
+
+// The checks of the PNG four, in the order include/dxtex_amd.h states. *source = the writer's PngSource (pack); *rowBytes = a row of the
+// image side, *fileRow = a row of the file side, *need = the bytes the call moves on the file side. table: the palette kinds' 256 words.
+dxtex_hresult check_png(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
+                        const dxtex_image* image, bool unpack, int* source, size_t* rowBytes, size_t* fileRow, size_t* need, uint32_t (*table)[256])
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!rows) return fail(ctx, DXTEX_E_POINTER, "null rows");
+    if (!image) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!image->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (unpack)
+    {
+        if (kind >= PNG_KINDS) return fail(ctx, DXTEX_E_INVALIDARG, "unknown PNG kind");
+        if (flags & ~uint32_t(PNG_BGR)) return fail(ctx, DXTEX_E_INVALIDARG, "unknown PNG flag bits");
+        if (png_is_palette(int(kind)) != (palette != nullptr)) return fail(ctx, DXTEX_E_INVALIDARG, palette ? "this PNG kind takes no palette" : "this PNG kind needs a palette");
+        if (palette && (paletteCount < 1 || paletteCount > 256)) return fail(ctx, DXTEX_E_INVALIDARG, "a PNG palette has 1 to 256 entries");
+    }
+    if (!image->width || !image->height || !rowsBytes) return fail(ctx, DXTEX_E_INVALIDARG, "empty image or no rows");
+    // texels per row fit the kernels' 32-bit x with a group to a lane
+    if (image->width > 0x1FFFFFFFull || image->height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    size_t imageTexel;
+    if (unpack)
+    {
+        if (!png_unpack_pairs(kind, flags, image->format)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this PNG kind and flags do not unpack into this format");
+        imageTexel = png_image_bytes(int(kind));
+        *fileRow = size_t(png_row_bytes(int(kind), image->width));
+        for (uint32_t i = 0; palette && i < 256; ++i) (*table)[i] = i < paletteCount ? palette[i] : 0xFF000000u;
+    }
+    else
+    {
+        *source = png_pack_source(image->format);
+        if (*source < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "no PNG writer case for this format");
+        imageTexel = png_source_bytes(*source);
+        *fileRow = image->width * png_source_file_bytes(*source);
+    }
+    if (*fileRow > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    *need = *fileRow * image->height;
+    *rowBytes = image->width * imageTexel;
+    if (rowsBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer bytes than height rows");
+    if (image->rowPitch < *rowBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
+    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(rows), s1 = s0 + *need;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + *rowBytes;
+    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "rows and image pixels overlap");
+    return DXTEX_S_OK;
+}
+} // namespace
+
+dxtex_hresult dxtex_png_unpack_device(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
+                                      const dxtex_image* dst)
+{
+    size_t rowBytes, fileRow, need; uint32_t table[256];
+    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_png_unpack(static_cast<const uint8_t*>(rows), int(kind), flags, palette ? table : nullptr, view_of(*dst), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_png_unpack(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
+                               const dxtex_image* dst)
+{
+    size_t rowBytes, fileRow, need; uint32_t table[256];
+    dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
+    if (hr != DXTEX_S_OK) return hr;
+    // the rows go up as they are; the kernel writes tight rows (rounded up to 16 bytes, so that a width of whole groups keeps the wide
+    // route) into the output staging, and only each row's texels come down, through the caller's pitch
+    const size_t pitch = (rowBytes + 15) & ~size_t(15);
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, need); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, pitch * dst->height); if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, rows, need, hipMemcpyHostToDevice, ctx->stream));
+    dxtex_image staged = with_pixels(*dst, ctx->stageOut.u8());
+    staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
+    hr = run_timed(ctx, [&] { return launched(ctx, launch_png_unpack(ctx->stageIn.u8(), int(kind), flags, palette ? table : nullptr, view_of(staged), ctx->stream, marks_of(ctx))); });
+    if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy_rows(ctx, dst->pixels, dst->rowPitch, staged.pixels, pitch, rowBytes, dst->height, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes)
+{
+    int source; size_t rowBytes, fileRow, need;
+    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, 0, 0, nullptr, 0, src, false, &source, &rowBytes, &fileRow, &need, nullptr);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return launched(ctx, launch_png_pack(view_of(*src), source, static_cast<uint8_t*>(rows), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes)
+{
+    int source; size_t rowBytes, fileRow, need;
+    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, 0, 0, nullptr, 0, src, false, &source, &rowBytes, &fileRow, &need, nullptr);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, rows, need,
+                      [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_png_pack(view_of(with_pixels(*src, in)), source, out, ctx->stream, marks_of(ctx))); });
 }
 
 namespace

@@ -133,6 +133,13 @@ hipError_t launch_dds_pack24(const DdsImage* images, size_t count, uint8_t* out,
 hipError_t launch_pnm_unpack(const uint8_t* stream, int kind, uint32_t maxval, uint32_t flags, const ImgView& dst, hipStream_t stream_, KernelMarks* marks = nullptr);
 hipError_t launch_pnm_pack(const ImgView& src, int source, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
 
+// PNG texels (png.hip; the rules are in dxtex_png.h). Unpack: `stream` = dst.height unfiltered rows of png_row_bytes(kind, dst.width)
+// bytes, kind = a PngKind that matches dst.format, flags = PngFlags, palette = 256 host words (png_palette_table's) for a palette kind,
+// passed by value: free to go on return. Pack: src's rows -> stream, source = the PngSource of src.format. Neither touches memory outside
+// the stream's rows and each image row's `width` texels. Wide / narrow: see png.hip.
+hipError_t launch_png_unpack(const uint8_t* stream, int kind, uint32_t flags, const uint32_t* palette, const ImgView& dst, hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_png_pack(const ImgView& src, int source, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

@@ -718,4 +718,65 @@ HRESULT SaveToPortablePixMapMemory(Device& device, const Image& deviceImage, Blo
 HRESULT SaveToPortablePixMapFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
 HRESULT SaveToPortablePixMapHDRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept;
 HRESULT SaveToPortablePixMapHDRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
+
+// ---- PNG, Auxiliary/DirectXTexPNG.cpp (the reference's libpng codec): non-interlaced files of every colour type and depth in, grey 8 / 16,
+// RGB 8 and RGBA 8 / 16 out. No library is linked: chunks, CRC-32, inflate (stored, fixed and dynamic blocks, Adler-32) and the five row
+// filters are this file's own code. Formats, flags and metadata follow the reference (Update, GuessFormat, GetHeader, WriteImage); a missing
+// file is HRESULT_ERROR_FILE_NOT_FOUND, an interlaced one HRESULT_E_NOT_SUPPORTED, every other defect E_FAIL. Four departures:
+//   1. No alpha association and no gamma correction. The reference's png_set_alpha_mode(PNG_ALPHA_STANDARD, PNG_GAMMA_LINEAR) and, for a
+//      gAMA that is not 1, png_set_gamma(2.2, gamma) make libpng premultiply and re-encode samples, against its own comment ("keep RGB
+//      untouched"). Here every sample is the file's sample, as a WIC-built texconv delivers it; premultiplying and colour space are
+//      -pmalpha's and -srgb*'s.
+//   2. A grey file with a tRNS chunk is HRESULT_E_NOT_SUPPORTED (the reference expands it to two channels in a four-channel image).
+//   3. The writer emits the colour chunks its code asks for, in front of IDAT: gAMA 100000 under PNG_FLAGS_FORCE_LINEAR, else sRGB
+//      (intent 0) for an _SRGB format or under PNG_FLAGS_FORCE_SRGB; neither for grey. The reference sets them after png_write_info, where
+//      libpng most likely no longer writes them.
+//   4. The Memory forms are this project's; the reference has the File forms only.
+// The writer stores: filter 0 on every row and stored deflate blocks, as the reference's compression level 0 asks for. The file's bytes are
+// this project's own; its texels are the image's. ---------------------------------------------------------------------------------------------
+constexpr HRESULT HRESULT_ERROR_FILE_NOT_FOUND = HRESULT(0x80070002);
+enum PNG_FLAGS : uint32_t
+{
+    PNG_FLAGS_NONE = 0,
+    PNG_FLAGS_BGR = 0x1,                 // 24bpp files are returned as BGRX; 32bpp files as BGRA
+    PNG_FLAGS_IGNORE_SRGB = 0x2,         // ignores the sRGB chunk and gAMA: the format is the linear one
+    PNG_FLAGS_DEFAULT_LINEAR = 0x4,      // a file that names no colour space is linear
+    PNG_FLAGS_FORCE_SRGB = 0x20,         // the writer emits sRGB whatever the format
+    PNG_FLAGS_FORCE_LINEAR = 0x40,       // the writer emits gAMA 1.0 whatever the format
+};
+inline PNG_FLAGS operator|(PNG_FLAGS a, PNG_FLAGS b) noexcept { return PNG_FLAGS(uint32_t(a) | uint32_t(b)); }
+HRESULT GetMetadataFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata& metadata) noexcept;
+HRESULT GetMetadataFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata& metadata) noexcept;
+HRESULT LoadFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT LoadFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT SaveToPNGMemory(const Image& image, PNG_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToPNGFile(const Image& image, PNG_FLAGS flags, const char* szFile) noexcept;
+// The reader's byte-serial half, which needs no device: signature, chunks and their CRCs, inflate, the row filters, every refusal. What comes
+// back is the unfiltered rows - height rows of ceil(width * bits / 8) bytes, tight, no filter byte - and how to read them (dxtex_png_unpack's
+// arguments). GetMetadata* stop behind the last chunk in front of IDAT and inflate nothing. On failure `raw` is released.
+struct PNGRawImage
+{
+    uint32_t kind = 0;                           // DXTEX_PNG_* (include/dxtex_amd.h)
+    uint32_t flags = 0;                          // DXTEX_PNG_BGR where PNG_FLAGS_BGR changes this kind's format
+    uint32_t palette[256] = {};                  // palette kinds: R | G << 8 | B << 16 | A << 24, A from tRNS or 255
+    uint32_t paletteCount = 0;
+    size_t rowBytes = 0;                         // ceil(width * bits / 8)
+    const uint8_t* rows = nullptr;               // into `storage`
+    size_t rowsBytes = 0;                        // height * rowBytes
+    Blob storage;
+    void Release() noexcept;
+};
+HRESULT LoadFromPNGMemoryRaw(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, PNGRawImage& raw) noexcept;
+HRESULT LoadFromPNGFileRaw(const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, PNGRawImage& raw) noexcept;
+// Resident forms: the unfiltered rows cross PCIe as the file has them - 3 bytes a texel for RGB 8, one bit for grey 1 - and the per-texel
+// pass runs on the device (dxtex_png_unpack_device / dxtex_png_pack_device). HRESULTs, metadata, pixels and files are those of the host forms
+// above. Load: one upload of rowsBytes; a grey 8 or RGBA 8 file without PNG_FLAGS_BGR whose rows match the image's pitch goes straight into
+// the image and no kernel runs; the result is released on failure. Save: deviceImage's pixels are a device pointer, as
+// DeviceScratchImage::GetImage gives; one download of the file's rows.
+HRESULT LoadFromPNGMemory(Device& device, const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromPNGFile(Device& device, const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device
+HRESULT UploadPNGRaw(Device& device, const TexMetadata& metadata, const PNGRawImage& raw, DeviceScratchImage& image) noexcept;
+HRESULT SaveToPNGMemory(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToPNGFile(Device& device, const Image& deviceImage, PNG_FLAGS flags, const char* szFile) noexcept;
 } // namespace DirectXTexAMD

@@ -1,0 +1,784 @@
+// PNG reader / writer of the host layer. Behaviour follows Auxiliary/DirectXTexPNG.cpp, the reference's codec over libpng; DirectXTexAMD.h
+// states the four departures. No library is linked: the chunk walk, CRC-32, the inflater, Adler-32 and the row filters are below. libpng
+// is not there to run the reference against, so the yardstick is tests/png_ref.py, a restatement of the rules over Python's zlib.
+// The reader is split in two. LoadFromPNGMemoryRaw does what is byte-serial - signature, chunks, inflate, unfilter, every refusal - and
+// hands back the unfiltered rows and how to read them. What happens to a texel after that is dxtex_png.h's, which the GPU kernels share:
+// the host loader runs it here, the resident forms at the end of this file run it on the device, so that a file's rows cross PCIe as the
+// bytes they are. The writer is split the same way around its rows.
+// Unfiltering stays on the host: Average and Paeth chain every byte to its left neighbour and to the row above, which is one serial walk.
+#include "DirectXTexAMD.h"
+#include "../../include/dxtex_amd.h"
+#include "../csrc/dxtex_png.h"
+
+#include <algorithm>
+#include <cerrno>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+
+namespace DirectXTexAMD
+{
+namespace
+{
+    constexpr uint8_t kSignature[8] = { 0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n' };
+    constexpr uint32_t kSideLimit = 1000000;          // libpng's default png_set_user_limits
+    constexpr size_t kIdatMax = size_t(1) << 24;      // the writer's IDAT payloads: well below 2^31
+
+    inline uint32_t Be32(const uint8_t* p) noexcept { return (uint32_t(p[0]) << 24) | (uint32_t(p[1]) << 16) | (uint32_t(p[2]) << 8) | p[3]; }
+    inline void PutBe32(uint8_t* p, uint32_t v) noexcept { p[0] = uint8_t(v >> 24); p[1] = uint8_t(v >> 16); p[2] = uint8_t(v >> 8); p[3] = uint8_t(v); }
+    constexpr uint32_t Tag(char a, char b, char c, char d) noexcept { return (uint32_t(uint8_t(a)) << 24) | (uint32_t(uint8_t(b)) << 16) | (uint32_t(uint8_t(c)) << 8) | uint8_t(d); }
+
+    // CRC-32 (ISO 3309, the PNG specification's), eight bytes a step over eight tables
+    struct CrcTables
+    {
+        uint32_t t[8][256];
+        CrcTables() noexcept
+        {
+            for (uint32_t n = 0; n < 256; ++n)
+            {
+                uint32_t c = n;
+                for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+                t[0][n] = c;
+            }
+            for (uint32_t n = 0; n < 256; ++n)
+                for (int s = 1; s < 8; ++s) t[s][n] = (t[s - 1][n] >> 8) ^ t[0][t[s - 1][n] & 0xFFu];
+        }
+    };
+    const CrcTables& Crc() noexcept { static const CrcTables tables; return tables; }
+
+    uint32_t Crc32(uint32_t crc, const uint8_t* p, size_t n) noexcept          // crc: the running value, 0xffffffff to start, inverted at the end
+    {
+        const CrcTables& T = Crc();
+        while (n >= 8)
+        {
+            const uint32_t a = crc ^ (uint32_t(p[0]) | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24));
+            crc = T.t[7][a & 0xFFu] ^ T.t[6][(a >> 8) & 0xFFu] ^ T.t[5][(a >> 16) & 0xFFu] ^ T.t[4][a >> 24] ^ T.t[3][p[4]] ^ T.t[2][p[5]] ^ T.t[1][p[6]] ^ T.t[0][p[7]];
+            p += 8; n -= 8;
+        }
+        while (n--) crc = T.t[0][(crc ^ *p++) & 0xFFu] ^ (crc >> 8);
+        return crc;
+    }
+
+    uint32_t Adler32(const uint8_t* p, size_t n) noexcept
+    {
+        uint32_t a = 1, b = 0;
+        while (n)
+        {
+            const size_t k = std::min<size_t>(n, 5552);          // the most steps before b can pass 2^32
+            for (size_t i = 0; i < k; ++i) { a += p[i]; b += a; }
+            a %= 65521u; b %= 65521u;
+            p += k; n -= k;
+        }
+        return (b << 16) | a;
+    }
+
+    // ---- inflate (RFC 1950 / 1951): stored, fixed and dynamic blocks into one contiguous buffer, which is also the window -------------------
+    // A canonical Huffman code: codes of up to kFast bits through a table, longer ones counted down bit by bit. The rules for a set of
+    // lengths are zlib's: over-subscribed is an error, incomplete is an error unless the set is empty or its longest code is one bit.
+    constexpr int kFast = 10;
+    struct Huffman
+    {
+        uint16_t fast[1 << kFast];          // symbol << 4 | length; 0: not a code of up to kFast bits
+        uint16_t count[16];
+        uint16_t symbol[288];
+        bool Build(const uint8_t* lengths, int n, bool codeLengthCode) noexcept
+        {
+            std::memset(count, 0, sizeof(count));
+            std::memset(fast, 0, sizeof(fast));
+            for (int i = 0; i < n; ++i) ++count[lengths[i]];
+            count[0] = 0;
+            int left = 1, max = 0;
+            for (int len = 1; len <= 15; ++len)
+            {
+                left <<= 1; left -= count[len];
+                if (left < 0) return false;
+                if (count[len]) max = len;
+            }
+            if (max && left > 0 && (codeLengthCode || max != 1)) return false;
+            uint16_t offs[16]; offs[1] = 0;
+            for (int len = 1; len < 15; ++len) offs[len + 1] = uint16_t(offs[len] + count[len]);
+            for (int i = 0; i < n; ++i) if (lengths[i]) symbol[offs[lengths[i]]++] = uint16_t(i);
+            // the table: the code of every symbol of up to kFast bits, bit-reversed (the stream holds codes first bit first), at every index
+            // whose low bits are that code
+            uint32_t code = 0; int index = 0;
+            for (int len = 1; len <= kFast; ++len)
+            {
+                for (int k = 0; k < count[len]; ++k, ++code, ++index)
+                {
+                    uint32_t rev = 0;
+                    for (int b = 0; b < len; ++b) rev |= ((code >> b) & 1u) << (len - 1 - b);
+                    for (uint32_t j = rev; j < (1u << kFast); j += 1u << len) fast[j] = uint16_t((symbol[index] << 4) | len);
+                }
+                code <<= 1;
+            }
+            return true;
+        }
+    };
+
+    struct BitReader
+    {
+        const uint8_t* p; const uint8_t* end;
+        uint64_t buf = 0; int cnt = 0;
+        void Fill() noexcept { while (cnt <= 56 && p < end) { buf |= uint64_t(*p++) << cnt; cnt += 8; } }
+        // n <= 16 bits; false when the stream holds fewer
+        bool Bits(int n, uint32_t& v) noexcept
+        {
+            if (cnt < n) { Fill(); if (cnt < n) return false; }
+            v = uint32_t(buf & ((uint64_t(1) << n) - 1)); buf >>= n; cnt -= n;
+            return true;
+        }
+        // one symbol; -1 for a code that is not in the set or a stream that ends inside one
+        int Decode(const Huffman& h) noexcept
+        {
+            if (cnt < 15) Fill();
+            const uint16_t e = h.fast[buf & ((1u << kFast) - 1)];
+            if (e)
+            {
+                const int len = e & 15;
+                if (len > cnt) return -1;
+                buf >>= len; cnt -= len;
+                return e >> 4;
+            }
+            int code = 0, first = 0, index = 0;
+            for (int len = 1; len <= 15; ++len)
+            {
+                if (cnt < len) return -1;
+                code |= int((buf >> (len - 1)) & 1u);
+                const int c = h.count[len];
+                if (code - c < first) { buf >>= len; cnt -= len; return h.symbol[index + (code - first)]; }
+                index += c; first += c; first <<= 1; code <<= 1;
+            }
+            return -1;
+        }
+    };
+
+    constexpr uint16_t kLenBase[29] = { 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258 };
+    constexpr uint8_t kLenExtra[29] = { 0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0 };
+    constexpr uint16_t kDistBase[30] = { 1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577 };
+    constexpr uint8_t kDistExtra[30] = { 0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13 };
+
+    // The zlib stream at [z, z + zn) into out[0, cap). True when cap bytes came out: either the stream ended there and its Adler-32 holds,
+    // or it goes on - the surplus is not decoded. False for every defect, a stream that ends short of cap included.
+    bool Inflate(const uint8_t* z, size_t zn, uint8_t* out, size_t cap) noexcept
+    {
+        if (zn < 2) return false;
+        if ((z[0] & 0x0F) != 8 || (z[0] >> 4) > 7 || ((uint32_t(z[0]) << 8) | z[1]) % 31u != 0 || (z[1] & 0x20)) return false;          // deflate, a window of up to 32 KiB, no dictionary
+        BitReader br{ z + 2, z + zn };
+        size_t pos = 0;
+        std::unique_ptr<Huffman> lit(new (std::nothrow) Huffman), dist(new (std::nothrow) Huffman);
+        if (!lit || !dist) return false;
+        for (;;)
+        {
+            uint32_t last, type;
+            if (!br.Bits(1, last) || !br.Bits(2, type)) return false;
+            if (type == 0)
+            {
+                br.buf >>= br.cnt & 7; br.cnt &= ~7;          // to the next byte
+                uint32_t len, nlen;
+                if (!br.Bits(16, len) || !br.Bits(16, nlen)) return false;
+                if ((len ^ 0xFFFFu) != nlen) return false;
+                const bool surplus = len > cap - pos;
+                if (surplus) len = uint32_t(cap - pos);
+                // whole bytes: first what the bit buffer holds, then the rest from the stream
+                while (len && br.cnt) { out[pos++] = uint8_t(br.buf); br.buf >>= 8; br.cnt -= 8; --len; }
+                if (size_t(br.end - br.p) < len) return false;
+                if (len) std::memcpy(out + pos, br.p, len);
+                br.p += len; pos += len;
+                if (surplus) return true;
+            }
+            else if (type == 1 || type == 2)
+            {
+                uint8_t lengths[320];
+                if (type == 1)
+                {
+                    for (int i = 0; i < 288; ++i) lengths[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
+                    lit->Build(lengths, 288, false);
+                    for (int i = 0; i < 32; ++i) lengths[i] = 5;
+                    dist->Build(lengths, 32, false);          // symbols 30 and 31 complete the code; a stream that uses one is refused below
+                }
+                else
+                {
+                    uint32_t nlen, ndist, ncode;
+                    if (!br.Bits(5, nlen) || !br.Bits(5, ndist) || !br.Bits(4, ncode)) return false;
+                    nlen += 257; ndist += 1; ncode += 4;
+                    if (nlen > 286 || ndist > 30) return false;
+                    static constexpr uint8_t order[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
+                    uint8_t cl[19] = {};
+                    for (uint32_t i = 0; i < ncode; ++i) { uint32_t v; if (!br.Bits(3, v)) return false; cl[order[i]] = uint8_t(v); }
+                    if (!lit->Build(cl, 19, true)) return false;          // lit serves as the code length code first
+                    uint32_t i = 0;
+                    while (i < nlen + ndist)
+                    {
+                        const int sym = br.Decode(*lit);
+                        if (sym < 0) return false;
+                        if (sym < 16) { lengths[i++] = uint8_t(sym); continue; }
+                        uint32_t rep, prev = 0;
+                        if (sym == 16)
+                        {
+                            if (i == 0) return false;
+                            prev = lengths[i - 1];
+                            if (!br.Bits(2, rep)) return false;
+                            rep += 3;
+                        }
+                        else if (sym == 17) { if (!br.Bits(3, rep)) return false; rep += 3; }
+                        else { if (!br.Bits(7, rep)) return false; rep += 11; }
+                        if (i + rep > nlen + ndist) return false;
+                        while (rep--) lengths[i++] = uint8_t(prev);
+                    }
+                    if (lengths[256] == 0) return false;          // no end-of-block code
+                    if (!lit->Build(lengths, int(nlen), false) || !dist->Build(lengths + nlen, int(ndist), false)) return false;
+                }
+                for (;;)
+                {
+                    const int sym = br.Decode(*lit);
+                    if (sym < 0) return false;
+                    if (sym < 256)
+                    {
+                        if (pos == cap) return true;          // surplus
+                        out[pos++] = uint8_t(sym);
+                        continue;
+                    }
+                    if (sym == 256) break;
+                    if (sym > 285) return false;
+                    uint32_t extra;
+                    if (!br.Bits(kLenExtra[sym - 257], extra)) return false;
+                    size_t len = kLenBase[sym - 257] + extra;
+                    const int ds = br.Decode(*dist);
+                    if (ds < 0 || ds > 29) return false;
+                    if (!br.Bits(kDistExtra[ds], extra)) return false;
+                    const size_t d = kDistBase[ds] + extra;
+                    if (d > pos) return false;          // before the start
+                    const bool surplus = len > cap - pos;
+                    if (surplus) len = cap - pos;
+                    // byte by byte where the copy overlaps itself (a run), in one piece otherwise
+                    if (d >= len) std::memcpy(out + pos, out + pos - d, len);
+                    else for (size_t k = 0; k < len; ++k) out[pos + k] = out[pos + k - d];
+                    pos += len;
+                    if (surplus) return true;
+                }
+            }
+            else return false;
+            if (last) break;
+        }
+        if (pos != cap) return false;
+        // the check value sits behind the last block, from the next byte on
+        br.buf >>= br.cnt & 7; br.cnt &= ~7;
+        uint32_t hi, lo;
+        if (!br.Bits(16, hi) || !br.Bits(16, lo)) return false;
+        const uint32_t stored = (((hi & 0xFFu) << 8 | (hi >> 8)) << 16) | ((lo & 0xFFu) << 8 | (lo >> 8));
+        return stored == Adler32(out, cap);
+    }
+
+    // ---- the row filters ---------------------------------------------------------------------------------------------------------------
+    inline int Paeth(int a, int b, int c) noexcept
+    {
+        const int p = a + b - c, pa = p > a ? p - a : a - p, pb = p > b ? p - b : b - p, pc = p > c ? p - c : c - p;
+        return (pa <= pb && pa <= pc) ? a : (pb <= pc) ? b : c;
+    }
+
+    // `height` filtered rows of 1 + rowBytes at buf -> tight rows at the front of buf. bpp = max(1, bits per texel / 8); the row above the
+    // first reads as zeros. The write position never passes the read position.
+    bool Unfilter(uint8_t* buf, size_t height, size_t rowBytes, size_t bpp) noexcept
+    {
+        const uint8_t* prev = nullptr;
+        for (size_t y = 0; y < height; ++y)
+        {
+            const uint8_t* s = buf + y * (rowBytes + 1);
+            uint8_t* d = buf + y * rowBytes;
+            const uint8_t f = *s++;
+            const size_t head = std::min(bpp, rowBytes);
+            switch (f)
+            {
+            case 0: std::memmove(d, s, rowBytes); break;
+            case 1:
+                for (size_t i = 0; i < head; ++i) d[i] = s[i];
+                for (size_t i = head; i < rowBytes; ++i) d[i] = uint8_t(s[i] + d[i - bpp]);
+                break;
+            case 2:
+                if (!prev) std::memmove(d, s, rowBytes);
+                else for (size_t i = 0; i < rowBytes; ++i) d[i] = uint8_t(s[i] + prev[i]);
+                break;
+            case 3:
+                for (size_t i = 0; i < head; ++i) d[i] = uint8_t(s[i] + ((prev ? prev[i] : 0) >> 1));
+                for (size_t i = head; i < rowBytes; ++i) d[i] = uint8_t(s[i] + ((d[i - bpp] + (prev ? prev[i] : 0)) >> 1));
+                break;
+            case 4:
+                for (size_t i = 0; i < head; ++i) d[i] = uint8_t(s[i] + (prev ? prev[i] : 0));          // Paeth(0, b, 0) is b
+                for (size_t i = head; i < rowBytes; ++i) d[i] = uint8_t(s[i] + Paeth(d[i - bpp], prev ? prev[i] : 0, prev ? prev[i - bpp] : 0));
+                break;
+            default: return false;
+            }
+            prev = d;
+        }
+        return true;
+    }
+
+    // ---- the chunks ----------------------------------------------------------------------------------------------------------------------
+    struct Header
+    {
+        uint32_t width = 0, height = 0;
+        uint8_t depth = 0, colorType = 0;
+        bool hasPalette = false, hasSRGB = false, hasGamma = false, greyKey = false;
+        uint32_t gamma = 0;          // times 100000
+        uint8_t plte[768] = {}; uint32_t plteCount = 0;
+        uint8_t trns[256] = {}; uint32_t trnsCount = 0;
+    };
+
+    // a kind per colour type and depth; -1 for a pair the specification does not have
+    int KindOf(uint8_t colorType, uint8_t depth) noexcept
+    {
+        switch (colorType)
+        {
+        case 0: return depth == 1 ? DXTEX_PNG_G1 : depth == 2 ? DXTEX_PNG_G2 : depth == 4 ? DXTEX_PNG_G4 : depth == 8 ? DXTEX_PNG_G8 : depth == 16 ? int(DXTEX_PNG_G16) : -1;
+        case 2: return depth == 8 ? DXTEX_PNG_RGB8 : depth == 16 ? int(DXTEX_PNG_RGB16) : -1;
+        case 3: return depth == 1 ? DXTEX_PNG_P1 : depth == 2 ? DXTEX_PNG_P2 : depth == 4 ? DXTEX_PNG_P4 : depth == 8 ? int(DXTEX_PNG_P8) : -1;
+        case 4: return depth == 8 ? DXTEX_PNG_GA8 : depth == 16 ? int(DXTEX_PNG_GA16) : -1;
+        case 6: return depth == 8 ? DXTEX_PNG_RGBA8 : depth == 16 ? int(DXTEX_PNG_RGBA16) : -1;
+        default: return -1;
+        }
+    }
+
+    // Update's flag change, GuessFormat and GetHeader (:126-251) from what the chunks said
+    void FillMetadata(const Header& h, uint32_t flags, TexMetadata& m) noexcept
+    {
+        m = TexMetadata();
+        m.width = h.width; m.height = h.height; m.depth = m.arraySize = m.mipLevels = 1;
+        m.dimension = TEX_DIMENSION_TEXTURE2D;
+        if (h.colorType == 4) flags |= PNG_FLAGS_IGNORE_SRGB;          // :145
+        if (h.colorType == 0) m.format = h.depth == 16 ? DXGI_FORMAT_R16_UNORM : DXGI_FORMAT_R8_UNORM;
+        else if (h.depth == 16) m.format = DXGI_FORMAT_R16G16B16A16_UNORM;
+        else
+        {
+            const bool bgr = (flags & PNG_FLAGS_BGR) != 0;
+            const DXGI_FORMAT linear = bgr ? DXGI_FORMAT_B8G8R8A8_UNORM : DXGI_FORMAT_R8G8B8A8_UNORM;
+            const DXGI_FORMAT srgb = bgr ? DXGI_FORMAT_B8G8R8A8_UNORM_SRGB : DXGI_FORMAT_R8G8B8A8_UNORM_SRGB;
+            const int64_t off = int64_t(h.gamma) - 100000;          // |gamma - 1.0| <= 1e-6 in units of 1e-5: the value itself
+            if (flags & PNG_FLAGS_IGNORE_SRGB) m.format = linear;
+            else if (h.hasSRGB) m.format = srgb;
+            else if (h.hasGamma && off == 0) m.format = linear;
+            else m.format = (flags & PNG_FLAGS_DEFAULT_LINEAR) ? linear : srgb;
+        }
+        const bool haveAlpha = (h.colorType & 4) != 0;
+        if (!haveAlpha && m.format != DXGI_FORMAT_R8_UNORM && m.format != DXGI_FORMAT_R16_UNORM)
+        {
+            if (m.format == DXGI_FORMAT_B8G8R8A8_UNORM) m.format = DXGI_FORMAT_B8G8R8X8_UNORM;
+            else if (m.format == DXGI_FORMAT_B8G8R8A8_UNORM_SRGB) m.format = DXGI_FORMAT_B8G8R8X8_UNORM_SRGB;
+            else m.miscFlags2 |= TEX_ALPHA_MODE_OPAQUE;
+        }
+    }
+
+    // The file's chunks. With `idat` null the walk stops at the first IDAT (metadata only); otherwise every IDAT's bytes are appended to
+    // *idat and the file must end with IEND.
+    HRESULT WalkChunks(const uint8_t* data, size_t size, Header& h, Blob* idat, size_t& idatBytes) noexcept
+    {
+        if (size < 8 || std::memcmp(data, kSignature, 8) != 0) return E_FAIL;
+        size_t at = 8;
+        bool first = true, sawIdat = false;
+        // the IDAT bytes are no more than the file: one allocation
+        if (idat) { const HRESULT hr = idat->Initialize(size); if (FAILED(hr)) return hr; }
+        idatBytes = 0;
+        for (;;)
+        {
+            if (size - at < 12) return E_FAIL;
+            const uint32_t len = Be32(data + at), tag = Be32(data + at + 4);
+            if (len > 0x7FFFFFFFu || size - at - 12 < len) return E_FAIL;
+            const uint8_t* body = data + at + 8;
+            if ((Crc32(0xFFFFFFFFu, data + at + 4, size_t(len) + 4) ^ 0xFFFFFFFFu) != Be32(body + len)) return E_FAIL;
+            at += size_t(len) + 12;
+            if (first != (tag == Tag('I', 'H', 'D', 'R'))) return E_FAIL;          // IHDR comes first, and once
+            if (first)
+            {
+                first = false;
+                if (len != 13) return E_FAIL;
+                h.width = Be32(body); h.height = Be32(body + 4); h.depth = body[8]; h.colorType = body[9];
+                if (!h.width || !h.height || h.width > kSideLimit || h.height > kSideLimit) return E_FAIL;
+                if (KindOf(h.colorType, h.depth) < 0 || body[10] != 0 || body[11] != 0 || body[12] > 1) return E_FAIL;
+                if (body[12] == 1) return HRESULT_E_NOT_SUPPORTED;          // Adam7
+                continue;
+            }
+            if (tag == Tag('I', 'D', 'A', 'T'))
+            {
+                if (h.colorType == 3 && !h.hasPalette) return E_FAIL;
+                if (!idat) return S_OK;
+                sawIdat = true;
+                if (len) std::memcpy(idat->GetBufferPointer() + idatBytes, body, len);
+                idatBytes += len;
+            }
+            else if (tag == Tag('I', 'E', 'N', 'D')) return sawIdat ? S_OK : E_FAIL;
+            else if (tag == Tag('P', 'L', 'T', 'E'))
+            {
+                if (sawIdat || h.hasPalette || len == 0 || len % 3 != 0 || len > 768) return E_FAIL;
+                h.hasPalette = true; h.plteCount = len / 3;
+                std::memcpy(h.plte, body, len);
+            }
+            else if (!(tag & 0x20000000u)) return E_FAIL;          // a critical chunk this reader does not know
+            else if (sawIdat) continue;          // ancillary chunks behind the image data change nothing
+            else if (tag == Tag('t', 'R', 'N', 'S'))
+            {
+                // a chunk of the wrong length or in the wrong place is passed over, as libpng does with a warning
+                if (h.colorType == 3) { if (h.hasPalette && len >= 1 && len <= h.plteCount) { h.trnsCount = len; std::memcpy(h.trns, body, len); } }
+                else if (h.colorType == 0 && len == 2) h.greyKey = true;
+            }
+            else if (tag == Tag('g', 'A', 'M', 'A')) { if (len == 4 && Be32(body) != 0 && Be32(body) <= 0x7FFFFFFFu) { h.hasGamma = true; h.gamma = Be32(body); } }
+            else if (tag == Tag('s', 'R', 'G', 'B')) { if (len == 1) h.hasSRGB = true; }
+        }
+    }
+
+    HRESULT ReadAll(const char* szFile, Blob& buf) noexcept
+    {
+        FILE* f = std::fopen(szFile, "rb");
+        if (!f) return errno == ENOENT ? HRESULT_ERROR_FILE_NOT_FOUND : E_FAIL;
+        std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
+        if (n < 1) { std::fclose(f); return E_FAIL; }
+        const HRESULT hr = buf.Initialize(size_t(n));
+        if (FAILED(hr)) { std::fclose(f); return hr; }
+        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
+        std::fclose(f);
+        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
+    }
+
+    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
+    {
+        FILE* f = std::fopen(szFile, "wb");
+        if (!f) return E_FAIL;
+        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
+        const bool closed = std::fclose(f) == 0;
+        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
+        return S_OK;
+    }
+
+    HRESULT Metadata(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata& metadata, Header& h, Blob* idat, size_t& idatBytes) noexcept
+    {
+        if (!pSource) return E_INVALIDARG;
+        const HRESULT hr = WalkChunks(static_cast<const uint8_t*>(pSource), size, h, idat, idatBytes);
+        if (FAILED(hr)) return hr;
+        if (h.greyKey) return HRESULT_E_NOT_SUPPORTED;
+        FillMetadata(h, flags, metadata);
+        return S_OK;
+    }
+
+    // ---- the writer ----------------------------------------------------------------------------------------------------------------------
+    struct FileShape { int source; uint8_t depth, colorType; bool srgbFormat; };
+    HRESULT SaveChecks(const Image& image, FileShape& f) noexcept
+    {
+        if (!image.pixels) return E_POINTER;
+        f.srgbFormat = false; f.depth = 8;
+        switch (image.format)          // WriteImage :322-364
+        {
+        case DXGI_FORMAT_R8_UNORM: f.source = dxtex::PNG_SRC_R8; f.colorType = 0; break;
+        case DXGI_FORMAT_R16_UNORM: f.source = dxtex::PNG_SRC_R16; f.colorType = 0; f.depth = 16; break;
+        case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: f.srgbFormat = true; [[fallthrough]];
+        case DXGI_FORMAT_R8G8B8A8_UNORM: f.source = dxtex::PNG_SRC_RGBA8; f.colorType = 6; break;
+        case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: f.srgbFormat = true; [[fallthrough]];
+        case DXGI_FORMAT_B8G8R8A8_UNORM: f.source = dxtex::PNG_SRC_BGRA8; f.colorType = 6; break;
+        case DXGI_FORMAT_R16G16B16A16_UNORM: f.source = dxtex::PNG_SRC_RGBA16; f.colorType = 6; f.depth = 16; break;
+        case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: f.srgbFormat = true; [[fallthrough]];
+        case DXGI_FORMAT_B8G8R8X8_UNORM: f.source = dxtex::PNG_SRC_BGRX8; f.colorType = 2; break;
+        default: return HRESULT_E_NOT_SUPPORTED;
+        }
+        if (!image.width || !image.height || image.width > kSideLimit || image.height > kSideLimit) return E_INVALIDARG;
+        return S_OK;
+    }
+
+    uint8_t* PutChunk(uint8_t* p, uint32_t tag, const uint8_t* body, size_t len) noexcept
+    {
+        PutBe32(p, uint32_t(len)); PutBe32(p + 4, tag);
+        if (len && body != p + 8) std::memcpy(p + 8, body, len);
+        PutBe32(p + 8 + len, Crc32(0xFFFFFFFFu, p + 4, len + 4) ^ 0xFFFFFFFFu);
+        return p + 12 + len;
+    }
+
+    // The file around the rows: rows(d, bytes) leaves the file's rows at d, tight; they are then wrapped - a filter byte 0 in front of each
+    // row, the whole as stored deflate blocks in one zlib stream, that cut into IDAT chunks.
+    template<class Rows>
+    HRESULT WriteFile(const Image& image, PNG_FLAGS flags, const FileShape& f, Blob& blob, Rows&& rows) noexcept
+    {
+        blob.Release();
+        const size_t rowBytes = image.width * dxtex::png_source_file_bytes(f.source);
+        const size_t raw = image.height * (rowBytes + 1);
+        const size_t blocks = (raw + 65534) / 65535;
+        const size_t zbytes = 2 + blocks * 5 + raw + 4;
+        const size_t idats = (zbytes + kIdatMax - 1) / kIdatMax;
+        const bool gama = f.colorType != 0 && (flags & PNG_FLAGS_FORCE_LINEAR);
+        const bool srgb = f.colorType != 0 && !gama && (f.srgbFormat || (flags & PNG_FLAGS_FORCE_SRGB));
+        Blob tight, z;
+        HRESULT hr = tight.Initialize(rowBytes * image.height);
+        if (SUCCEEDED(hr)) hr = z.Initialize(zbytes);
+        if (SUCCEEDED(hr)) hr = blob.Initialize(8 + 25 + (gama ? 16 : 0) + (srgb ? 13 : 0) + zbytes + idats * 12 + 12);
+        if (SUCCEEDED(hr)) hr = rows(tight.GetBufferPointer(), tight.GetBufferSize());
+        if (FAILED(hr)) { blob.Release(); return hr; }
+        // the zlib stream: header, stored blocks that pay no heed to where rows end, the check value
+        uint8_t* zp = z.GetBufferPointer();
+        *zp++ = 0x78; *zp++ = 0x01;
+        uint32_t a = 1, b = 0;          // Adler-32 as the bytes pass
+        size_t inBlock = 0, left = raw;
+        auto put = [&](const uint8_t* s, size_t n)
+        {
+            while (n)
+            {
+                if (!inBlock)
+                {
+                    inBlock = std::min<size_t>(left, 65535);
+                    *zp++ = left <= 65535 ? 1 : 0;
+                    *zp++ = uint8_t(inBlock); *zp++ = uint8_t(inBlock >> 8); *zp++ = uint8_t(~inBlock); *zp++ = uint8_t(~inBlock >> 8);
+                }
+                const size_t k = std::min(n, inBlock);
+                std::memcpy(zp, s, k);
+                zp += k; s += k; n -= k; inBlock -= k; left -= k;
+            }
+        };
+        const uint8_t zero = 0;
+        for (size_t y = 0; y < image.height; ++y) { put(&zero, 1); put(tight.GetBufferPointer() + y * rowBytes, rowBytes); }
+        {
+            // over the blocks' payloads: the filter bytes and the rows
+            const uint8_t* t = tight.GetBufferPointer();
+            for (size_t y = 0; y < image.height; ++y, t += rowBytes)
+            {
+                b += a;          // the filter byte: a += 0
+                for (size_t i = 0; i < rowBytes; i += 5000)
+                {
+                    const size_t k = std::min<size_t>(5000, rowBytes - i);
+                    for (size_t j = 0; j < k; ++j) { a += t[i + j]; b += a; }
+                    a %= 65521u; b %= 65521u;
+                }
+                b %= 65521u;
+            }
+        }
+        PutBe32(zp, (b << 16) | a);
+        uint8_t* p = blob.GetBufferPointer();
+        std::memcpy(p, kSignature, 8); p += 8;
+        uint8_t ihdr[13];
+        PutBe32(ihdr, uint32_t(image.width)); PutBe32(ihdr + 4, uint32_t(image.height));
+        ihdr[8] = f.depth; ihdr[9] = f.colorType; ihdr[10] = ihdr[11] = ihdr[12] = 0;
+        p = PutChunk(p, Tag('I', 'H', 'D', 'R'), ihdr, 13);
+        if (gama) { uint8_t g[4]; PutBe32(g, 100000); p = PutChunk(p, Tag('g', 'A', 'M', 'A'), g, 4); }
+        if (srgb) { const uint8_t intent = 0; p = PutChunk(p, Tag('s', 'R', 'G', 'B'), &intent, 1); }
+        for (size_t at = 0; at < zbytes; at += kIdatMax) p = PutChunk(p, Tag('I', 'D', 'A', 'T'), z.GetBufferPointer() + at, std::min(kIdatMax, zbytes - at));
+        p = PutChunk(p, Tag('I', 'E', 'N', 'D'), nullptr, 0);
+        return size_t(p - blob.GetBufferPointer()) == blob.GetBufferSize() ? S_OK : E_UNEXPECTED;
+    }
+
+    HRESULT SaveHost(const Image& image, PNG_FLAGS flags, Blob& blob) noexcept
+    {
+        blob.Release();
+        FileShape f;
+        const HRESULT hr = SaveChecks(image, f);
+        if (FAILED(hr)) return hr;
+        const size_t S = dxtex::png_source_bytes(f.source), F = dxtex::png_source_file_bytes(f.source);
+        if (image.rowPitch < image.width * S) return E_INVALIDARG;
+        return WriteFile(image, flags, f, blob, [&](uint8_t* d, size_t)
+        {
+            for (size_t y = 0; y < image.height; ++y)
+            {
+                const uint8_t* s = image.pixels + y * image.rowPitch;
+                for (size_t x = 0; x < image.width; ++x, s += S, d += F) dxtex::png_pack_texel(s, d, f.source);
+            }
+            return S_OK;
+        });
+    }
+
+    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
+    struct DeviceTemp
+    {
+        Device& device; void* p = nullptr;
+        explicit DeviceTemp(Device& d) noexcept : device(d) {}
+        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
+        DeviceTemp(const DeviceTemp&) = delete;
+        DeviceTemp& operator=(const DeviceTemp&) = delete;
+    };
+
+    HRESULT SaveResident(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept
+    {
+        blob.Release();
+        FileShape f;
+        const HRESULT hr = SaveChecks(deviceImage, f);
+        if (FAILED(hr)) return hr;
+        if (!device) return E_POINTER;
+        return WriteFile(deviceImage, flags, f, blob, [&](uint8_t* d, size_t bytes)
+        {
+            DeviceTemp temp(device);
+            HRESULT hr2 = dxtex_device_alloc(device.Get(), bytes, &temp.p);
+            if (SUCCEEDED(hr2))
+            {
+                const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
+                hr2 = dxtex_png_pack_device(device.Get(), &s, temp.p, bytes);
+            }
+            if (SUCCEEDED(hr2)) hr2 = dxtex_memcpy_d2h(device.Get(), d, temp.p, bytes);          // returns when the rows have landed
+            return hr2;
+        });
+    }
+}
+
+void PNGRawImage::Release() noexcept
+{
+    storage.Release();
+    kind = flags = paletteCount = 0;
+    std::memset(palette, 0, sizeof(palette));
+    rowBytes = rowsBytes = 0;
+    rows = nullptr;
+}
+
+HRESULT LoadFromPNGMemoryRaw(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, PNGRawImage& raw) noexcept
+{
+    raw.Release();
+    Header h; TexMetadata mdata; Blob idat; size_t idatBytes = 0;
+    const HRESULT hr = Metadata(pSource, size, flags, mdata, h, &idat, idatBytes);
+    if (FAILED(hr)) return hr;
+    const int kind = KindOf(h.colorType, h.depth);
+    const size_t rowBytes = size_t(dxtex::png_row_bytes(kind, h.width));
+    const uint64_t need = uint64_t(h.height) * (rowBytes + 1);
+    // deflate gives at most 1032 bytes for one (a stored byte of 258-byte matches): a stream too short for the image is refused before
+    // memory is asked for
+    if (need / 1032u > idatBytes || need > SIZE_MAX / 2) return E_FAIL;
+    Blob out;
+    HRESULT hr2 = out.Initialize(size_t(need));
+    if (FAILED(hr2)) return hr2;
+    if (!Inflate(idat.GetBufferPointer(), idatBytes, out.GetBufferPointer(), size_t(need))) return E_FAIL;
+    idat.Release();
+    if (!Unfilter(out.GetBufferPointer(), h.height, rowBytes, std::max<size_t>(1, dxtex::png_file_bits(kind) / 8))) return E_FAIL;
+    hr2 = out.Trim(rowBytes * h.height);
+    if (FAILED(hr2)) return hr2;
+    raw.kind = uint32_t(kind);
+    raw.flags = ((flags & PNG_FLAGS_BGR) && h.colorType != 0 && h.depth <= 8) ? DXTEX_PNG_BGR : 0u;
+    if (h.colorType == 3)
+    {
+        dxtex::png_palette_table(h.plte, h.plteCount, h.trnsCount ? h.trns : nullptr, h.trnsCount, raw.palette);
+        raw.paletteCount = h.plteCount;
+    }
+    raw.rowBytes = rowBytes; raw.rowsBytes = rowBytes * h.height;
+    raw.storage.Swap(out);
+    raw.rows = raw.storage.GetBufferPointer();
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromPNGFileRaw(const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, PNGRawImage& raw) noexcept
+{
+    raw.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    const HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    return LoadFromPNGMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, raw);
+}
+
+HRESULT GetMetadataFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata& metadata) noexcept
+{
+    Header h; size_t idatBytes = 0;
+    return Metadata(pSource, size, flags, metadata, h, nullptr, idatBytes);
+}
+
+HRESULT GetMetadataFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata& metadata) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    const HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    return GetMetadataFromPNGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata);
+}
+
+HRESULT LoadFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
+{
+    image.Release();          // on any failure the result is empty
+    TexMetadata mdata; PNGRawImage raw;
+    HRESULT hr = LoadFromPNGMemoryRaw(pSource, size, flags, &mdata, raw);
+    if (FAILED(hr)) return hr;
+    hr = image.Initialize2D(mdata.format, mdata.width, mdata.height, 1, 1);
+    if (FAILED(hr)) return hr;
+    const Image* img = image.GetImage(0, 0, 0);
+    if (!img) { image.Release(); return E_POINTER; }
+    const int kind = int(raw.kind);
+    const size_t D = dxtex::png_image_bytes(kind);
+    const bool bgr = (raw.flags & DXTEX_PNG_BGR) != 0;
+    for (size_t y = 0; y < img->height; ++y)
+    {
+        const uint8_t* row = raw.rows + y * raw.rowBytes;
+        uint8_t* d = img->pixels + y * img->rowPitch;
+        for (size_t x = 0; x < img->width; ++x, d += D) dxtex::png_unpack_texel(row, x, d, kind, bgr, raw.palette);
+    }
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
+{
+    image.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    const HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    return LoadFromPNGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+}
+
+HRESULT SaveToPNGMemory(const Image& image, PNG_FLAGS flags, Blob& blob) noexcept { return SaveHost(image, flags, blob); }
+
+HRESULT SaveToPNGFile(const Image& image, PNG_FLAGS flags, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveHost(image, flags, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+
+// ---- resident forms: the rows travel as the file has them, the per-texel pass runs on the device (dxtex_png_unpack_device / dxtex_png_pack_device) ----
+HRESULT UploadPNGRaw(Device& device, const TexMetadata& metadata, const PNGRawImage& raw, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!device) return E_POINTER;
+    if (!raw.rows || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1) return E_INVALIDARG;
+    if (raw.rowsBytes != raw.rowBytes * metadata.height) return E_INVALIDARG;
+    HRESULT hr = image.Initialize(device, metadata);
+    if (FAILED(hr)) return hr;
+    const Image* img = image.GetImage(0, 0, 0);
+    if (!img) { image.Release(); return E_POINTER; }
+    const bool native = (raw.kind == DXTEX_PNG_G8 || raw.kind == DXTEX_PNG_RGBA8) && !(raw.flags & DXTEX_PNG_BGR);
+    if (native && img->rowPitch == raw.rowBytes)
+        hr = dxtex_memcpy_h2d(device.Get(), img->pixels, raw.rows, raw.rowsBytes);          // the rows are the image: one copy, no kernel
+    else
+    {
+        // the rows go to the start of an allocation of their own: aligned, so a width of whole groups takes the wide route
+        DeviceTemp temp(device);
+        hr = dxtex_device_alloc(device.Get(), raw.rowsBytes, &temp.p);
+        if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.rows, raw.rowsBytes);          // the caller's bytes are free to go on return
+        if (SUCCEEDED(hr))
+        {
+            const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
+            hr = dxtex_png_unpack_device(device.Get(), temp.p, raw.rowsBytes, raw.kind, raw.flags, raw.paletteCount ? raw.palette : nullptr, raw.paletteCount, &d);
+        }
+    }
+    if (FAILED(hr)) image.Release();
+    return hr;
+}
+
+HRESULT LoadFromPNGMemory(Device& device, const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    image.Release();          // on any failure the result is empty
+    TexMetadata mdata; PNGRawImage raw;
+    HRESULT hr = LoadFromPNGMemoryRaw(pSource, size, flags, &mdata, raw);
+    if (FAILED(hr)) return hr;
+    hr = UploadPNGRaw(device, mdata, raw, image);
+    if (FAILED(hr)) return hr;
+    if (metadata) *metadata = mdata;
+    return S_OK;
+}
+
+HRESULT LoadFromPNGFile(Device& device, const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
+{
+    image.Release();
+    if (!szFile) return E_INVALIDARG;
+    Blob file;
+    const HRESULT hr = ReadAll(szFile, file);
+    if (FAILED(hr)) return hr;
+    return LoadFromPNGMemory(device, file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+}
+
+HRESULT SaveToPNGMemory(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept { return SaveResident(device, deviceImage, flags, blob); }
+
+HRESULT SaveToPNGFile(Device& device, const Image& deviceImage, PNG_FLAGS flags, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveResident(device, deviceImage, flags, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+} // namespace DirectXTexAMD

@@ -1,4 +1,4 @@
-// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR and TGA in; DDS out (TGA / HDR
+// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA and PNG in; DDS out (TGA / HDR
 // too for the single-image results). Every input is loaded on the host, checked, uploaded ONCE, run through texassemble's per-input
 // pipeline on the device (decompress, -stripmips, -alpha, resize, -tonemap, convert), assembled there - every face, slice, item or mip a
 // rectangle of one batched copy_rect launch - and the result is downloaded once.
@@ -273,9 +273,9 @@ int Parse(int argc, char** argv, Options& o)
     }
     if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     const bool single = IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP || o.command == CMD_MERGE;
-    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr"))))
+    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr") || hasExt(o.output, ".png"))))
     {
-        std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga or .hdr" : "");
+        std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga, .hdr or .png" : "");
         return 1;
     }
     return 0;
@@ -312,7 +312,7 @@ int Fail(const char* what, HRESULT hr)
 // an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
 // a .tga input likewise as the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
 // a .dds input as the file itself, parsed: its payload goes up as it is and the row conversions of a legacy file run on the device
-struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; };
+struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; bool png = false; PNGRawImage pngRaw; };
 
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
 int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
@@ -359,8 +359,16 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
             if (FAILED(hr)) return Fail(" FAILED", hr);
             ApplyTGAAlphaRule(in->tgaRaw, TGA_FLAGS_NONE, in->info);          // the line below states the alpha mode
         }
+        else if (hasExt(file, ".png"))
+        {
+            // inflate and the row filters here, before there is a device; the unfiltered rows go up later (texassemble.cpp:1536-1544)
+            const bool bgr = o.format == DXGI_FORMAT_B8G8R8A8_UNORM || o.format == DXGI_FORMAT_B8G8R8X8_UNORM || o.format == DXGI_FORMAT_B8G8R8A8_UNORM_SRGB || o.format == DXGI_FORMAT_B8G8R8X8_UNORM_SRGB;
+            in->png = true;
+            hr = LoadFromPNGFileRaw(file.c_str(), bgr ? PNG_FLAGS_BGR : PNG_FLAGS_NONE, &in->info, in->pngRaw);
+            if (FAILED(hr)) return Fail(" FAILED", hr);
+        }
         else if (hasExt(file, ".hdr")) { in->hdr = true; hr = LoadFromHDRFileRGBE(file.c_str(), &in->info, in->exposure, in->rgbe); if (FAILED(hr)) return Fail(" FAILED", hr); }
-        else { std::printf(" FAILED: only .dds, .tga and .hdr can be read (the reference reads the rest through WIC)\n"); return 1; }
+        else { std::printf(" FAILED: only .dds, .tga, .hdr and .png can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
         std::fflush(stdout);
         inputs.push_back(std::move(in));
@@ -399,9 +407,10 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         DeviceScratchImage cur, next;
         Input& in = *inputs[index];
         HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : in.tga ? UploadTGARaw(dev, in.info, TGA_FLAGS_NONE, in.tgaRaw, cur)
+                                        : in.png ? UploadPNGRaw(dev, in.info, in.pngRaw, cur)
                                                                                               : UploadDDSRaw(dev, in.dds, cur);
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release();
+        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release(); in.pngRaw.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
@@ -529,6 +538,7 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     if (!o.overwrite && stat(o.output.c_str(), &st) == 0) { std::printf("\nERROR: Output file already exists, use -y to overwrite\n"); return 1; }
     if (hdrOut) hr = SaveToHDRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());
     else if (tgaOut) hr = SaveToTGAFile(dev, *result.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
+    else if (hasExt(o.output, ".png")) hr = SaveToPNGFile(dev, *result.GetImage(0, 0, 0), PNG_FLAGS_NONE, o.output.c_str());          // the file's rows, likewise
     else hr = SaveToDDSFile(dev, result.GetImages(), result.GetImageCount(), result.GetMetadata(),
                             o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED", hr);

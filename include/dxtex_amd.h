@@ -39,6 +39,8 @@
  *     rows of SaveToDDSMemory
  *   LoadFromPortablePixMap[HDR]'s texel loops, Texconv/PortablePixMap.cpp      dxtex_pnm_unpack / dxtex_pnm_pack
  *     the rows of SaveToPortablePixMap[HDR]      :209-223, :595-681, :392-422, :720-735
+ *   LoadFromPNGFile's / SaveToPNGFile's         Auxiliary/DirectXTexPNG.cpp     dxtex_png_unpack / dxtex_png_pack
+ *     per-texel transforms                       :126-225, :315-404
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -446,6 +448,56 @@ dxtex_hresult dxtex_pnm_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t ki
  * the wide route (a width that is a multiple of 4, samples on a multiple of 4, 8 or 16 bytes by kind, image rows on 16). */
 dxtex_hresult dxtex_pnm_unpack_device(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst);
 dxtex_hresult dxtex_pnm_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes);
+
+/* PNG (.png) texels, the per-texel half of the codec (chunks, CRCs, inflate and the row filters are byte-serial and stay with the caller).
+ * One image per call. The file side is the unfiltered image data: tight rows of ceil(width * bits / 8) bytes, no filter byte, top-down.
+ * At least height such rows; more bytes are ignored.
+ *   unpack   rows -> dst, through dst's pitch (Update and GuessFormat, Auxiliary/DirectXTexPNG.cpp:126-225):
+ *              kind                     bits a texel   dst->format                                   texel
+ *              DXTEX_PNG_G1 / G2 / G4   1, 2, 4        R8_UNORM                                      sample * 255, 85, 17; first texel in the high bits
+ *              DXTEX_PNG_G8 / G16       8, 16          R8_UNORM / R16_UNORM                          the sample, 16 bits swapped to little-endian
+ *              DXTEX_PNG_GA8 / GA16     16, 32         R8G8B8A8_UNORM / R16G16B16A16_UNORM           g, g, g, a
+ *              DXTEX_PNG_RGB8           24             R8G8B8A8_UNORM[_SRGB]; B8G8R8X8_UNORM[_SRGB] with DXTEX_PNG_BGR   r, g, b, 0xff
+ *              DXTEX_PNG_RGBA8          32             R8G8B8A8_UNORM[_SRGB]; B8G8R8A8_UNORM[_SRGB] with DXTEX_PNG_BGR   r, g, b, a
+ *              DXTEX_PNG_RGB16 / RGBA16 48, 64         R16G16B16A16_UNORM                            swapped; the filler is 0xffff
+ *              DXTEX_PNG_P1 .. P8       1, 2, 4, 8     as DXTEX_PNG_RGB8                             palette[index]
+ *            palette (the palette kinds only; NULL otherwise): paletteCount words R | G << 8 | B << 16 | A << 24 in host memory, read
+ *            before the call returns, 1 to 256 of them; an index at or past paletteCount gives opaque black (0xff000000). DXTEX_PNG_BGR
+ *            exchanges the first and third byte of the texel of DXTEX_PNG_RGB8, DXTEX_PNG_RGBA8 and the palette kinds, and with it the
+ *            format they pair with; the other kinds ignore it.
+ *   pack     level 0 of src -> the rows the writer emits (WriteImage, :315-404): R8_UNORM -> grey 8, R16_UNORM -> grey 16 (big-endian),
+ *            R8G8B8A8 / B8G8R8A8_UNORM[_SRGB] -> R, G, B, A, R16G16B16A16_UNORM -> RGBA 16 (big-endian), B8G8R8X8_UNORM[_SRGB] -> R, G, B.
+ *            width * height * (1, 2, 4, 4, 8, 3) bytes.
+ * No sample is premultiplied or gamma-corrected: see host/DirectXTexAMD.h on where this departs from the reference.
+ * HRESULTs, in this order: E_POINTER for null rows, image or pixels; E_INVALIDARG for an unknown kind, unknown flag bits, a palette that
+ * is missing, unasked for or of a count outside 1..256, a width, height or byte count of zero; NOT_SUPPORTED for a kind, flag and format
+ * that do not pair up per the tables; E_INVALIDARG for fewer bytes than the rows take, a row pitch smaller than the row, or rows that
+ * overlap the pixels. Bytes of the image outside each row's texels, and bytes behind the rows, are not written. */
+#define DXTEX_PNG_G1      0u
+#define DXTEX_PNG_G2      1u
+#define DXTEX_PNG_G4      2u
+#define DXTEX_PNG_G8      3u
+#define DXTEX_PNG_G16     4u
+#define DXTEX_PNG_GA8     5u
+#define DXTEX_PNG_GA16    6u
+#define DXTEX_PNG_RGB8    7u
+#define DXTEX_PNG_RGB16   8u
+#define DXTEX_PNG_RGBA8   9u
+#define DXTEX_PNG_RGBA16  10u
+#define DXTEX_PNG_P1      11u
+#define DXTEX_PNG_P2      12u
+#define DXTEX_PNG_P4      13u
+#define DXTEX_PNG_P8      14u
+#define DXTEX_PNG_BGR     0x1u
+/* host pointers, through the context's staging: the rows go up as they are, the image comes down through its pitch */
+dxtex_hresult dxtex_png_unpack(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
+                               const dxtex_image* dst);
+dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes);
+/* device pointers (the palette stays a host pointer): asynchronous on the context's stream. The rows may start at any byte; see
+ * csrc/png.hip for the alignment that takes the wide route. */
+dxtex_hresult dxtex_png_unpack_device(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
+                                      const dxtex_image* dst);
+dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
