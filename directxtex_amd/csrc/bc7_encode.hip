@@ -2,6 +2,9 @@
 // byte-identical to D3DXEncodeBC7, BC6HBC7.cpp:3654).
 //
 // Decomposition (SIMT-friendly restatement of D3DX_BC7::Encode's mode x rotation x index-mode x shape loops):
+//   dedupe  : lane = block. Encode is a pure function of a block's sixteen texels and the flags, so blocks of a pass with the same texels
+//             (flat areas, gutters, repeated tiles) are found through a hash table, verified texel by texel, and only the first of each
+//             group is encoded; every kernel below skips the others and pick copies the result (dxtex_bc7_dedupe.h).
 //   rough   : one wavefront per block, lane = partition shape. Each lane fits the float seed endpoints of
 //             its shape's subsets once, scores them with the 3-bit and the 2-bit palettes (modes 1 / 3,7
 //             share the seed), then the wavefront reproduces the reference's partial selection sort
@@ -12,10 +15,11 @@
 //             described further down. The per-mode winners travel through a 24 B slot per mode per block.
 //             pre drops the candidates that provably cannot win (subset_lower_bound, bc7_core.h); the modes run in
 //             an order chosen for that pruning (launch_bc7_encode_many), modes 4 / 5 / 6 possibly in two phases.
-//   pick    : lane = block; minimum over the per-mode winners in the reference's evaluation order.
+//   pick    : lane = block; minimum over the per-mode winners (a duplicate: its leader's) in the reference's evaluation order.
 #include "dxtex_kernels.h"
 #include "bc67_tables.h"
 #include "bc7_core.h"
+#include "dxtex_bc7_dedupe.h"
 #include "search_common.h"
 #include <algorithm>
 #include <cstdio>
@@ -67,7 +71,17 @@ struct Bc7Args
     uint32_t gateMin;        // when too few blocks are flagged - is skipped on the device: its kernels return at once when *gate < gateMin (nullptr: always run)
     uint32_t perturbWaveMax; // whole-block modes: lists of at most this many live tasks are searched by bc7_perturb_wave_kernel (0 = never)
     uint32_t exhWaveMax;     // ... and by bc7_exhaustive_wave_kernel
+    uint32_t* dupOf;         // per block: itself when the block is encoded, else its LEADER - an earlier block of the pass with the same sixteen
+                             // texels, whose candidate slots bc7_pick_kernel reads instead (bc7_dedupe_* kernels); between those two kernels: the
+                             // block's slot in the hash table
+    bc7dd::Slot* ddTable;    // the dedupe's hash table, ddSlots = 2 x nblocks slots, cleared per pass
+    uint32_t ddSlots;
+    uint32_t ddHashBits;     // 64; DXTEX_BC7_DEDUPE_HASH_BITS keeps fewer, so that unequal blocks share a hash
+    int dedupe;              // 0 = every block is encoded (DXTEX_BC7_NO_DEDUPE, for A/B runs)
+    uint32_t* ddCount;       // development build only: duplicates of the pass (DXTEX_BC7_STATS)
 };
+
+__device__ __forceinline__ bool is_duplicate(const Bc7Args& a, uint32_t nb) { return a.dupOf[nb] != nb; }      // nb < a.nblocks
 
 // Whole-block tasks (modes 4, 5, 6: one subset of 16 texels) on SHORT lists - a small image, the late phase of mode 6 - are searched by
 // groups of lanes instead of a lane each: with fewer tasks than lanes a kernel is as slow as its longest serial chain, and a chain of
@@ -103,6 +117,86 @@ __device__ __forceinline__ void load_block_texel(const SrcView& src, uint32_t nb
     }
 }
 
+// ---- dedupe: encode each distinct block of a pass once (dxtex_bc7_dedupe.h) -------------------------------------------
+// D3DX_BC7::Encode reads nothing but the sixteen texels load_block_texel hands out and the flags, which are uniform over a pass: two
+// blocks whose 64 float bit patterns are equal get the same sixteen bytes. insert puts every block into a hash table (lane = block;
+// lanes of a wavefront with the same hash - flat areas put thousands of equal keys side by side - send their first lane only, so a
+// wavefront issues one compare-and-swap and one minimum per distinct key); resolve compares every block's texels with those of its slot's
+// leader, the smallest block index the slot has seen, and makes it a duplicate only when all of them are equal. The kernels after them
+// skip duplicates (task_geometry), and pick copies the leader's result. Blocks of different images of a pass pair up under the same rule.
+// Neither kernel waits for another lane: the probe loop is bounded, and a block without a slot is simply encoded.
+__global__ void __launch_bounds__(256) bc7_dedupe_insert_kernel(Bc7Args a)
+{
+    const uint32_t nb = blockIdx.x * 256u + threadIdx.x;
+    const int lane = threadIdx.x & 63;
+    const bool valid = nb < a.nblocks;
+    uint64_t h = 0;
+    if (valid)
+    {
+        const BcSeg& sg = seg_of(a.seg, nb);
+#pragma unroll 4
+        for (uint32_t t = 0; t < 16; ++t)
+        {
+            float f4[4]; uint32_t ldr;
+            load_block_texel(sg.src, sg.nbw, sg.nb0 + (nb - sg.l0), t, f4, ldr);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) h = bc7dd::hash_word(h, __float_as_uint(f4[c]));
+        }
+    }
+    const unsigned long long key = bc7dd::hash_finish(h, a.ddHashBits);
+    // the first lane of the wavefront with this lane's hash (blocks ascend with the lanes, and the lanes past the pass's end come last)
+    int first = lane;
+    for (int j = 0; j < 63; ++j)
+    {
+        const unsigned long long kj = (unsigned long long)(uint32_t(__shfl(int(uint32_t(key)), j))) |
+                                      ((unsigned long long)(uint32_t(__shfl(int(uint32_t(key >> 32)), j))) << 32);
+        if (first == lane && j < lane && kj == key) first = j;
+    }
+    uint32_t slot = bc7dd::kNoSlot;
+    if (valid && first == lane)
+    {
+        bc7dd::Slot* table = a.ddTable;
+        slot = bc7dd::insert(key, nb, a.ddSlots,
+                             [table](uint32_t s, unsigned long long k) { return atomicCAS(&table[s].key, bc7dd::kEmptyKey, k); },
+                             [table](uint32_t s, uint32_t b) { atomicMin(&table[s].leader, b); });
+    }
+    slot = uint32_t(__shfl(int(slot), first));
+    if (valid) a.dupOf[nb] = slot;
+}
+
+__global__ void __launch_bounds__(256) bc7_dedupe_resolve_kernel(Bc7Args a)
+{
+    const uint32_t nb = blockIdx.x * 256u + threadIdx.x;
+    const bool valid = nb < a.nblocks;
+    uint32_t leader = nb;
+    if (valid && a.dedupe)
+    {
+        const uint32_t cand = bc7dd::candidate_leader(a.ddTable, a.dupOf[nb], nb);
+        if (cand != nb)
+        {
+            // always verified: the leader's texels are loaded from the source again, and a hash match alone makes no duplicate
+            const BcSeg& sg = seg_of(a.seg, nb);
+            const BcSeg& sl = seg_of(a.seg, cand);
+            uint32_t diff = 0;
+#pragma unroll 1
+            for (uint32_t t = 0; t < 16 && diff == 0; ++t)
+            {
+                float f[4], g[4]; uint32_t ldr;
+                load_block_texel(sg.src, sg.nbw, sg.nb0 + (nb - sg.l0), t, f, ldr);
+                load_block_texel(sl.src, sl.nbw, sl.nb0 + (cand - sl.l0), t, g, ldr);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) diff |= __float_as_uint(f[c]) ^ __float_as_uint(g[c]);
+            }
+            if (diff == 0) leader = cand;
+        }
+    }
+    if (valid) a.dupOf[nb] = leader;
+#if defined(DXTEX_DEV)
+    const unsigned long long dups = __ballot(valid && leader != nb);
+    if (dups && (threadIdx.x & 63u) == 0) atomicAdd(a.ddCount, uint32_t(__popcll(dups)));
+#endif
+}
+
 // Compiled for 8 wavefronts per SIMD: the kernel waits on LDS reads inside divergent Newton loops, and more waves hide that better
 // than the 168 bytes of spill per lane cost (14.9 -> 14.0 ms per 4096^2 image; 6 / 7 waves: 14.4 / 14.2 ms).
 #if !defined(DXTEX_ROUGH_WGS)
@@ -118,8 +212,11 @@ __global__ void __launch_bounds__(256, DXTEX_ROUGH_WGS) bc7_rough_kernel(Bc7Args
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t nb = blockIdx.x * 4 + wave;
     const bool inRange = nb < a.nblocks;
+    // A duplicate (bc7_dedupe_resolve_kernel) is not fitted: its wavefront loads nothing, still takes its share of the other blocks' dealt
+    // fits below - the barriers stay uniform over the workgroup - and leaves after them.
+    const bool dup = inRange && is_duplicate(a, nb);
 
-    if (inRange && lane < 16)
+    if (inRange && !dup && lane < 16)
     {
         uint32_t ldr;
         const BcSeg& sg = seg_of(a.seg, nb);
@@ -129,7 +226,7 @@ __global__ void __launch_bounds__(256, DXTEX_ROUGH_WGS) bc7_rough_kernel(Bc7Args
         if (lane == 0) { a.zeroOrd[nb] = 0xFFFFFFFFu; a.bestErr[nb] = 0x7FFFFFFF; }
     }
     {
-        const bool one = !inRange || lane >= 16 || sF[wave][(lane & 15) * 4 + 3] == 1.0f;       // own write, same lane
+        const bool one = !inRange || dup || lane >= 16 || sF[wave][(lane & 15) * 4 + 3] == 1.0f;       // own write, same lane
         const unsigned long long all = __ballot(one);
         if (lane == 0) sOpaque[wave] = (all == ~0ull) ? 1u : 0u;
     }
@@ -147,12 +244,13 @@ __global__ void __launch_bounds__(256, DXTEX_ROUGH_WGS) bc7_rough_kernel(Bc7Args
         const float* fpxk = sF[blk];
         const uint32_t* pixk = sL[blk];
         const bool opaque = sOpaque[blk] != 0u;
+        const bool fitted = nbk < a.nblocks && !is_duplicate(a, nbk);
 #pragma unroll 1
         for (int k = 0; k < 2; ++k)
         {
             const uint32_t group = k ? uint32_t(7 - wave) : uint32_t(wave);
             const uint32_t code = kFit2Order[group * 16 + ent];
-            if (nbk < a.nblocks)
+            if (fitted)
             {
                 const uint32_t m1 = kPart2Mask[code >> 1];
                 const uint32_t m = (code & 1u) ? m1 : ((~m1) & 0xFFFFu);
@@ -174,7 +272,7 @@ __global__ void __launch_bounds__(256, DXTEX_ROUGH_WGS) bc7_rough_kernel(Bc7Args
         }
     }
     __syncthreads();
-    if (!inRange) return;              // whole wave exits together
+    if (!inRange || dup) return;       // whole wave exits together
     const float* fpx = sF[wave];
     const uint32_t* pix = sL[wave];
 
@@ -314,7 +412,7 @@ __device__ __forceinline__ bool task_geometry(const Bc7Args& a, uint32_t nb, uin
 {
     typedef TaskMap<MODE, IM> TM;
     shape = 0; mask = 0xFFFFu; anchor = 0; rot = 0;
-    if (nb >= a.nblocks) return false;
+    if (nb >= a.nblocks || is_duplicate(a, nb)) return false;       // a duplicate has no tasks: pick takes its leader's result
     if (!phase_owns<MODE>(a, nb)) return false;
     const uint32_t rank = r / TM::G, region = r % TM::G;
     // fMSEBest == 0: the reference returns from Encode, i.e. skips every candidate that comes later in ITS order. The modes
@@ -1344,7 +1442,8 @@ __global__ void __launch_bounds__(256, (MODE == 4 || MODE == 5) ? DXTEX_PP45_WGS
     const uint32_t rank = r / TM::G, region = r % TM::G;
     uint32_t shape, mask, anchor, rot;
     const bool active = (blk < uint32_t(BPW)) && task_geometry<MODE, IM>(a, nb, r, shape, mask, anchor, rot);
-    const bool mine = blk < uint32_t(BPW) && nb < a.nblocks && phase_owns<MODE>(a, nb);
+    // (a duplicate is nobody's: its lists were never written and its candidate slots are never read)
+    const bool mine = blk < uint32_t(BPW) && nb < a.nblocks && !is_duplicate(a, nb) && phase_owns<MODE>(a, nb);
     if (!__any(active))
     {
         if (mine && r == 0)
@@ -1454,7 +1553,7 @@ template<bool RGBA>
 __global__ void __launch_bounds__(256) bc7_block_seeds_kernel(Bc7Args a)
 {
     const uint32_t nb = blockIdx.x * 256u + threadIdx.x;
-    if (nb >= a.nblocks) return;
+    if (nb >= a.nblocks || is_duplicate(a, nb)) return;
     const BcSeg& sg = seg_of(a.seg, nb);
     float f[64];
 #pragma unroll
@@ -1472,6 +1571,7 @@ __global__ void __launch_bounds__(256) bc7_flag_count_kernel(Bc7Args a, uint32_t
     uint32_t n = 0, m = 0;
     for (uint32_t nb = blockIdx.x * 256u + threadIdx.x; nb < a.nblocks; nb += gridDim.x * 256u)
     {
+        if (is_duplicate(a, nb)) continue;     // not encoded, not counted: the early-phase thresholds refer to blocks that are
         uint8_t* lst = a.lists + uint64_t(nb) * LIST_BYTES;
         const bool hasAlpha = lst[32] != 0;
         bool first = hasAlpha;
@@ -1497,7 +1597,7 @@ __global__ void __launch_bounds__(256) bc7_flag_count_kernel(Bc7Args a, uint32_t
 __global__ void __launch_bounds__(256) bc7_texels_kernel(Bc7Args a)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= a.nblocks * 16u) return;
+    if (i >= a.nblocks * 16u || is_duplicate(a, i >> 4)) return;
     float f4[4]; uint32_t ldr;
     const BcSeg& sg = seg_of(a.seg, i >> 4);
     load_block_texel(sg.src, sg.nbw, sg.nb0 + ((i >> 4) - sg.l0), i & 15u, f4, ldr);
@@ -1510,7 +1610,7 @@ __global__ void __launch_bounds__(256) bc7_pick_kernel(Bc7Args a, uint32_t slotM
 {
     const uint32_t nb = blockIdx.x * 256u + threadIdx.x;
     if (nb >= a.nblocks) return;
-    const Cand* c = a.cands + uint64_t(nb) * NUM_SLOTS;
+    const Cand* c = a.cands + uint64_t(a.dupOf[nb]) * NUM_SLOTS;      // a duplicate's bytes are its leader's; every slot is complete by now
     uint64_t bestKey = ~0ull;
     uint64_t lo = 0, hi = 0;
 #pragma unroll
@@ -1543,7 +1643,7 @@ constexpr int kMaxTasksPerBlock = 64;                 // mode 2: 16 candidates x
 const uint64_t kSmallPassBlocks = dev_env("DXTEX_BC7_SMALL_BLOCKS") ? strtoull(dev_env("DXTEX_BC7_SMALL_BLOCKS"), nullptr, 10) : 262144;     // up to a lone 2048^2 image (1448^2: 22.1 -> 20.4 ms, 2048^2: 39.2 -> 38.7; at 4096^2 the plan loses: 139.5 -> 143.7)
 struct ScratchLayout
 {
-    size_t lists, cands, px, recs, order, tinfo, counters, zeroOrd, bestErr, seeds, seeds1, seeds3, flagcnt, auxRecs, auxOrder, auxTinfo, auxCounters, total;
+    size_t lists, cands, px, recs, order, tinfo, counters, zeroOrd, bestErr, seeds, seeds1, seeds3, flagcnt, auxRecs, auxOrder, auxTinfo, auxCounters, dupOf, ddTable, total;
     size_t auxTpb, auxSlices;     // the extra pipelines' task arrays: slices of nb * auxTpb tasks
     explicit ScratchLayout(uint64_t nb, bool threeSubsets)
     {
@@ -1570,6 +1670,8 @@ struct ScratchLayout
         auxOrder = o; o = up(o + auxSlices * nb * auxTpb * sizeof(uint2));
         auxTinfo = o; o = up(o + auxSlices * nb * auxTpb * sizeof(uint32_t));
         auxCounters = o; o = up(o + size_t(kSideStreams) * 64 * sizeof(uint32_t));
+        dupOf = o; o = up(o + nb * sizeof(uint32_t));                                       // the dedupe: 36 bytes per block
+        ddTable = o; o = up(o + nb * bc7dd::kSlotsPerBlock * sizeof(bc7dd::Slot));
         total = o;
     }
 };
@@ -1819,11 +1921,37 @@ hipError_t launch_bc7_encode_many(const BcImage* images, size_t count, uint32_t 
                                    L.auxTpb >= 32 && perPass <= kSmallPassBlocks && dev_env("DXTEX_BC7_ORDER") == nullptr;
         a.early6Min = uint32_t(uint64_t(a.nblocks) * uint32_t(early6MinPct >= 0 ? early6MinPct : (smallPlanRuns ? 25 : 50)) / 100u);
         a.earlyAlphaMin = uint32_t(uint64_t(a.nblocks) * uint32_t(earlyAlphaMinPct) / 100u);
+        // Blocks of the pass with the same sixteen texels are encoded once (bc7_dedupe_* kernels): everything below skips the duplicates
+        static const bool noDedupe = dev_env("DXTEX_BC7_NO_DEDUPE") != nullptr;
+        static const int hashBits = dev_env("DXTEX_BC7_DEDUPE_HASH_BITS") ? atoi(dev_env("DXTEX_BC7_DEDUPE_HASH_BITS")) : 64;
+        a.dupOf = reinterpret_cast<uint32_t*>(base + L.dupOf);
+        a.ddTable = reinterpret_cast<bc7dd::Slot*>(base + L.ddTable);
+        a.ddSlots = a.nblocks * bc7dd::kSlotsPerBlock;
+        a.ddHashBits = uint32_t(std::min(64, std::max(0, hashBits)));
+        a.dedupe = noDedupe ? 0 : 1;
+        a.ddCount = flagCount + 60;
+        DXTEX_MARK("bc7_dedupe");
+        (void)hipMemsetAsync(flagCount, 0, 256, stream);
+        if (a.dedupe)
+        {
+            (void)hipMemsetAsync(a.ddTable, 0xFF, size_t(a.ddSlots) * sizeof(bc7dd::Slot), stream);
+            hipLaunchKernelGGL(bc7_dedupe_insert_kernel, dim3((a.nblocks + 255) / 256), dim3(256), 0, stream, a);
+        }
+        hipLaunchKernelGGL(bc7_dedupe_resolve_kernel, dim3((a.nblocks + 255) / 256), dim3(256), 0, stream, a);
+#if defined(DXTEX_DEV)
+        static const bool ddStats = dev_env("DXTEX_BC7_STATS") != nullptr;
+        if (ddStats)
+        {
+            uint32_t dups = 0;
+            (void)hipStreamSynchronize(stream);
+            (void)hipMemcpy(&dups, a.ddCount, sizeof(dups), hipMemcpyDeviceToHost);
+            std::fprintf(stderr, "bc7 stats dedupe: %u of %u blocks are duplicates\n", dups, a.nblocks);
+        }
+#endif
         if (!quick)
         {
             DXTEX_MARK("bc7_rough");
             hipLaunchKernelGGL(bc7_rough_kernel, dim3((a.nblocks + 3) / 4), dim3(256), 0, stream, a);
-            (void)hipMemsetAsync(flagCount, 0, 256, stream);
             hipLaunchKernelGGL(bc7_flag_count_kernel, dim3((a.nblocks + 255) / 256), dim3(256), 0, stream, a, flagCount);
         }
         else

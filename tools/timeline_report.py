@@ -6,7 +6,8 @@ import csv, sys
 
 path = sys.argv[1]; min_us = float(sys.argv[2]) if len(sys.argv) > 2 else 40.0
 rows = [r for r in csv.DictReader(open(path)) if 'bc7' in r['Kernel_Name'] or 'fillBuffer' in r['Kernel_Name']]
-first = [i for i, r in enumerate(rows) if 'bc7_rough' in r['Kernel_Name'] or 'bc7_texels' in r['Kernel_Name']][-1]
+# a pass starts with the dedupe kernels (resolve alone under DXTEX_BC7_NO_DEDUPE)
+first = ([i for i, r in enumerate(rows) if 'bc7_dedupe_insert' in r['Kernel_Name']] or [i for i, r in enumerate(rows) if 'bc7_dedupe_resolve' in r['Kernel_Name']])[-1]
 rows = sorted(rows[first:], key=lambda r: int(r['Start_Timestamp']))
 iv = [(int(r['Start_Timestamp']), int(r['End_Timestamp'])) for r in rows]
 t0 = iv[0][0]; tend = max(e for s, e in iv)
