@@ -147,6 +147,15 @@ inline hipError_t counted_copy(dxtex_ctx* ctx, void* dst, const void* src, size_
     return hipMemcpyAsync(dst, src, bytes, kind, stream);
 }
 
+// rows of rowBytes between host and device through their own pitches, counted like every other transfer
+hipError_t counted_copy_rows(dxtex_ctx* ctx, void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t rowBytes, size_t rows, hipMemcpyKind kind)
+{
+    if (!rows || !rowBytes) return hipSuccess;
+    if (rows == 1 || (dstPitch == rowBytes && srcPitch == rowBytes)) return counted_copy(ctx, dst, src, rowBytes * rows, kind, ctx->stream);
+    if (kind == hipMemcpyHostToDevice) ctx->h2dBytes += rowBytes * rows; else ctx->d2hBytes += rowBytes * rows;
+    return hipMemcpy2DAsync(dst, dstPitch, src, srcPitch, rowBytes, rows, kind, ctx->stream);
+}
+
 #define HIP_TRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ctx, (e_ == hipErrorOutOfMemory) ? DXTEX_E_OUTOFMEMORY : DXTEX_E_FAIL, #expr, e_); } while (0)
 
 template<bool Pinned>
@@ -350,6 +359,26 @@ dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, voi
     if (hr != DXTEX_S_OK) return hr;
     HIP_TRY(ctx, counted_copy(ctx, hostOut, ctx->stageOut.p, outBytes, hipMemcpyDeviceToHost, ctx->stream));
     if (out2Bytes) HIP_TRY(ctx, counted_copy(ctx, hostOut2, devOut2, out2Bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+// The staged-rows unpack of the PNM and PNG host forms: the `need` bytes of the file side go up as they are; the kernel writes tight rows
+// (rounded up to 16 bytes, so that a width of whole groups keeps the wide route) into the output staging, and only each row's texels come
+// down, through the caller's pitch. launch(stream, view) queues the kernel.
+template<class Launch>
+dxtex_hresult run_staged_rows(dxtex_ctx* ctx, const void* hostIn, size_t need, const dxtex_image* dst, size_t rowBytes, Launch&& launch)
+{
+    const size_t pitch = (rowBytes + 15) & ~size_t(15);
+    ScopedDevice sd(ctx->device);
+    dxtex_hresult hr = ctx->stageIn.grow(ctx, need); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, pitch * dst->height); if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, hostIn, need, hipMemcpyHostToDevice, ctx->stream));
+    dxtex_image staged = with_pixels(*dst, ctx->stageOut.u8());
+    staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
+    hr = run_timed(ctx, [&] { return launched(ctx, launch(ctx->stageIn.u8(), view_of(staged))); });
+    if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy_rows(ctx, dst->pixels, dst->rowPitch, staged.pixels, pitch, rowBytes, dst->height, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
@@ -1592,6 +1621,18 @@ int tga_pack_row(int format, uint32_t bytesPerTexel)
     }
 }
 
+// The tail the TGA, PNM and PNG checks share: the image's rows against its pitch, and the file side - `need` bytes at `stream`, named
+// `noun` in the message - apart from the rowBytes-wide rows of the image
+dxtex_hresult check_stream_image(dxtex_ctx* ctx, const char* noun, const void* stream, size_t need, const dxtex_image* image, size_t rowBytes)
+{
+    if (image->rowPitch < rowBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
+    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(stream), s1 = s0 + need;
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + rowBytes;
+    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, (std::string(noun) + " and image pixels overlap").c_str());
+    return DXTEX_S_OK;
+}
+
 // The checks of the TGA four, in the order include/dxtex_amd.h states. `image` is the dxtex_image side, imageBytes a texel of it;
 // *kind = the reader's kind or the writer's row.
 dxtex_hresult check_tga(dxtex_ctx* ctx, const void* stream, size_t streamBytes, uint32_t bytesPerTexel, bool paletted, const dxtex_image* image, bool unpack, int* kind)
@@ -1604,12 +1645,9 @@ dxtex_hresult check_tga(dxtex_ctx* ctx, const void* stream, size_t streamBytes, 
     if (*kind < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, unpack ? "no TGA reader case for this bytes per texel, format and palette" : "no TGA writer case for this format and bytes per texel");
     if (!image->width || !image->height || image->width > 65535 || image->height > 65535) return fail(ctx, DXTEX_E_INVALIDARG, "a TGA image is 1 to 65535 texels wide and high");
     const size_t imageBytes = unpack ? tga_image_bytes(*kind) : (*kind == TGA_ROW_DROP_X ? 4u : bytesPerTexel);
-    if (image->rowPitch < image->width * imageBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
-    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
     const size_t need = image->width * image->height * bytesPerTexel;
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(stream), s1 = s0 + need;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + image->width * imageBytes;
-    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "texel stream and image pixels overlap");
+    const dxtex_hresult hr = check_stream_image(ctx, "texel stream", stream, need, image, image->width * imageBytes);
+    if (hr != DXTEX_S_OK) return hr;
     if (streamBytes != need) return fail(ctx, DXTEX_E_FAIL, "the texel stream is not width * height * bytes per texel long");
     return DXTEX_S_OK;
 }
@@ -1724,15 +1762,6 @@ dxtex_hresult check_dds(dxtex_ctx* ctx, const void* file, size_t fileBytes, bool
 
 // bytes of an image's rows in memory, first to last
 size_t dds_span(const DdsImage& j, size_t rowBytes, bool fileSide) { return j.rows ? (j.rows - 1) * size_t(fileSide ? j.filePitch : j.pitch) + rowBytes : 0; }
-
-// rows of rowBytes between host and device through their own pitches, counted like every other transfer
-hipError_t counted_copy_rows(dxtex_ctx* ctx, void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t rowBytes, size_t rows, hipMemcpyKind kind)
-{
-    if (!rows || !rowBytes) return hipSuccess;
-    if (rows == 1 || (dstPitch == rowBytes && srcPitch == rowBytes)) return counted_copy(ctx, dst, src, rowBytes * rows, kind, ctx->stream);
-    if (kind == hipMemcpyHostToDevice) ctx->h2dBytes += rowBytes * rows; else ctx->d2hBytes += rowBytes * rows;
-    return hipMemcpy2DAsync(dst, dstPitch, src, srcPitch, rowBytes, rows, kind, ctx->stream);
-}
 } // namespace
 
 dxtex_hresult dxtex_dds_unpack_device(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
@@ -1867,12 +1896,7 @@ dxtex_hresult check_pnm(dxtex_ctx* ctx, const void* samples, size_t sampleBytes,
     *need = image->width * image->height * fileTexel;
     *rowBytes = image->width * imageTexel;
     if (sampleBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer samples than width * height texels");
-    if (image->rowPitch < *rowBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
-    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(samples), s1 = s0 + *need;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + *rowBytes;
-    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "samples and image pixels overlap");
-    return DXTEX_S_OK;
+    return check_stream_image(ctx, "samples", samples, *need, image, *rowBytes);
 }
 } // namespace
 
@@ -1887,22 +1911,10 @@ dxtex_hresult dxtex_pnm_unpack_device(dxtex_ctx* ctx, const void* samples, size_
 dxtex_hresult dxtex_pnm_unpack(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst)
 {
     size_t rowBytes, need;
-    dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
+    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
     if (hr != DXTEX_S_OK) return hr;
-    // the samples go up as they are; the kernel writes tight rows (rounded up to 16 bytes, so that a width of four texels keeps the wide
-    // route) into the output staging, and only each row's texels come down, through the caller's pitch
-    const size_t pitch = (rowBytes + 15) & ~size_t(15);
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, need); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, pitch * dst->height); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, samples, need, hipMemcpyHostToDevice, ctx->stream));
-    dxtex_image staged = with_pixels(*dst, ctx->stageOut.u8());
-    staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
-    hr = run_timed(ctx, [&] { return launched(ctx, launch_pnm_unpack(ctx->stageIn.u8(), int(kind), maxval, flags, view_of(staged), ctx->stream, marks_of(ctx))); });
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy_rows(ctx, dst->pixels, dst->rowPitch, staged.pixels, pitch, rowBytes, dst->height, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged_rows(ctx, samples, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
+                           { return launch_pnm_unpack(stream, int(kind), maxval, flags, view, ctx->stream, marks_of(ctx)); });
 }
 
 dxtex_hresult dxtex_pnm_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes)
@@ -1997,12 +2009,7 @@ dxtex_hresult check_png(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint
     *need = *fileRow * image->height;
     *rowBytes = image->width * imageTexel;
     if (rowsBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer bytes than height rows");
-    if (image->rowPitch < *rowBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
-    if (image->rowPitch > SIZE_MAX / image->height) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
-    const uintptr_t s0 = reinterpret_cast<uintptr_t>(rows), s1 = s0 + *need;
-    const uintptr_t i0 = reinterpret_cast<uintptr_t>(image->pixels), i1 = i0 + image->rowPitch * (image->height - 1) + *rowBytes;
-    if (s0 < i1 && i0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "rows and image pixels overlap");
-    return DXTEX_S_OK;
+    return check_stream_image(ctx, "rows", rows, *need, image, *rowBytes);
 }
 } // namespace
 
@@ -2019,22 +2026,10 @@ dxtex_hresult dxtex_png_unpack(dxtex_ctx* ctx, const void* rows, size_t rowsByte
                                const dxtex_image* dst)
 {
     size_t rowBytes, fileRow, need; uint32_t table[256];
-    dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
+    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
     if (hr != DXTEX_S_OK) return hr;
-    // the rows go up as they are; the kernel writes tight rows (rounded up to 16 bytes, so that a width of whole groups keeps the wide
-    // route) into the output staging, and only each row's texels come down, through the caller's pitch
-    const size_t pitch = (rowBytes + 15) & ~size_t(15);
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, need); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, pitch * dst->height); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, rows, need, hipMemcpyHostToDevice, ctx->stream));
-    dxtex_image staged = with_pixels(*dst, ctx->stageOut.u8());
-    staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
-    hr = run_timed(ctx, [&] { return launched(ctx, launch_png_unpack(ctx->stageIn.u8(), int(kind), flags, palette ? table : nullptr, view_of(staged), ctx->stream, marks_of(ctx))); });
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy_rows(ctx, dst->pixels, dst->rowPitch, staged.pixels, pitch, rowBytes, dst->height, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged_rows(ctx, rows, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
+                           { return launch_png_unpack(stream, int(kind), flags, palette ? table : nullptr, view, ctx->stream, marks_of(ctx)); });
 }
 
 dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes)

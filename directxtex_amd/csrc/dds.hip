@@ -31,26 +31,12 @@
 #include "dxtex_dds.h"
 #include <algorithm>
 #include <cstdio>
-#include <type_traits>
 
 namespace dxtex
 {
 namespace
 {
-struct DdsPalette { uint32_t word[256]; };
-struct DdsNoPalette {};
-template<int OP> using PaletteArg = std::conditional_t<dds_has_palette(OP), DdsPalette, DdsNoPalette>;
 struct DdsBatch { DdsImage image[kDdsBatchMax]; };
-
-// texel k of four consecutive B-byte texels held as B little-endian dwords
-template<uint32_t B>
-__device__ __forceinline__ uint32_t texel_of(const uint32_t (&w)[B], uint32_t k)
-{
-    const uint32_t bit = k * 8u * B, i = bit / 32u, shift = bit % 32u;
-    uint32_t t = w[i] >> shift;
-    if (shift + 8u * B > 32u) t |= w[i + 1] << (32u - shift);
-    return B == 4u ? t : t & ((1u << (8u * (B & 3u))) - 1u);
-}
 
 // four D-byte image texels as aligned accesses
 template<uint32_t D>
@@ -65,43 +51,18 @@ __device__ __forceinline__ void store4(uint8_t* d, const uint64_t (&t)[4])
     }
 }
 
-// one D-byte image texel: one access where the address is a multiple of D, bytes otherwise
-template<uint32_t D>
-__device__ __forceinline__ void store1(uint8_t* d, uint64_t t, bool aligned)
-{
-    if (!aligned) { dds_store(d, t, D); return; }
-    if constexpr (D == 2u) *reinterpret_cast<uint16_t*>(d) = uint16_t(t);
-    else if constexpr (D == 4u) *reinterpret_cast<uint32_t*>(d) = uint32_t(t);
-    else *reinterpret_cast<uint2*>(d) = make_uint2(uint32_t(t), uint32_t(t >> 32));
-}
-
-// one B-byte file texel
-template<uint32_t B>
-__device__ __forceinline__ uint32_t load1(const uint8_t* s, bool aligned)
-{
-    if (B == 1u || B == 3u || !aligned) return dds_load(s, B);
-    if constexpr (B == 2u) return *reinterpret_cast<const uint16_t*>(s);
-    else return *reinterpret_cast<const uint32_t*>(s);
-}
-
 // a plain narrow copy moves aligned dwords where the whole image allows it: both addresses, both pitches and the row's bytes multiples of 4
 __host__ __device__ __forceinline__ bool copy_words_ok(const uint8_t* src, const DdsImage& im)
 {
     return ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(im.pixels) | im.filePitch | im.pitch | im.width) & 3u) == 0;
 }
 
-__device__ __forceinline__ bool multiple_of_dev(const void* p, uint64_t pitch, uint32_t bytes) { return ((reinterpret_cast<uintptr_t>(p) | pitch) & (bytes - 1u)) == 0; }
-
 // `rule` is read by ROW_COPY only: its forced alpha (texelBytes 0: a plain copy). im.width counts bytes for ROW_COPY, texels otherwise.
 template<int OP, int TARGET, bool WIDE>
-__global__ void __launch_bounds__(256) dds_unpack_kernel(const uint8_t* payload, DdsBatch batch, uint32_t opaque, DdsOpaque rule, PaletteArg<OP> pal)
+__global__ void __launch_bounds__(256) dds_unpack_kernel(const uint8_t* payload, DdsBatch batch, uint32_t opaque, DdsOpaque rule, PaletteArg<dds_has_palette(OP)> pal)
 {
     __shared__ uint32_t table[dds_has_palette(OP) ? 256 : 1];
-    if constexpr (dds_has_palette(OP))
-    {
-        table[threadIdx.x] = pal.word[threadIdx.x];
-        __syncthreads();
-    }
+    if constexpr (dds_has_palette(OP)) palette_to_lds(table, pal);
     const DdsImage& im = batch.image[blockIdx.z];
     const uint8_t* src = payload + im.fileOffset;
     const uint32_t lane = blockIdx.x * 256u + threadIdx.x;
@@ -135,8 +96,8 @@ __global__ void __launch_bounds__(256) dds_unpack_kernel(const uint8_t* payload,
                 uint8_t* d = im.pixels + uint64_t(y) * im.pitch + x;
                 if (words) { *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s); continue; }
                 for (uint32_t i = 0; i + W < T; ++i) d[i] = s[i];
-                const uint32_t v = dds_load(s + (T - W), W);
-                dds_store(d + (T - W), rule.texelBytes ? dds_opaque_word(v, rule) : v, W);
+                const uint32_t v = le_load32(s + (T - W), W);
+                le_store64(d + (T - W), rule.texelBytes ? dds_opaque_word(v, rule) : v, W);
             }
         }
     }
@@ -145,7 +106,7 @@ __global__ void __launch_bounds__(256) dds_unpack_kernel(const uint8_t* payload,
         constexpr uint32_t B = dds_file_bytes(OP), D = dds_image_bytes(TARGET), G = WIDE ? 4u : 1u;
         const uint32_t x = lane * G;
         if (x >= im.width) return;
-        const bool srcAligned = multiple_of_dev(src, im.filePitch, B == 3u ? 1u : B), dstAligned = multiple_of_dev(im.pixels, im.pitch, D);
+        const bool srcAligned = multiple_of(src, im.filePitch, B == 3u ? 1u : B), dstAligned = multiple_of(im.pixels, im.pitch, D);
         for (uint32_t y = blockIdx.y; y < im.rows; y += gridDim.y)
         {
             const uint8_t* s = src + uint64_t(y) * im.filePitch + uint64_t(x) * B;
@@ -154,12 +115,7 @@ __global__ void __launch_bounds__(256) dds_unpack_kernel(const uint8_t* payload,
             {
                 uint32_t w[B];
                 uint64_t t[4];
-                if constexpr (B == 4u) { const uint4 v = *reinterpret_cast<const uint4*>(s); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-                else
-                {
-#pragma unroll
-                    for (uint32_t i = 0; i < B; ++i) w[i] = reinterpret_cast<const uint32_t*>(s)[i];
-                }
+                load_span<B, B == 4u ? 16u : 4u>(s, w);
 #pragma unroll
                 for (uint32_t k = 0; k < 4u; ++k) t[k] = dds_unpack_texel(texel_of<B>(w, k), OP, TARGET, opaque != 0, table);
                 store4<D>(d, t);
@@ -177,23 +133,23 @@ __global__ void __launch_bounds__(256) dds_pack24_kernel(uint8_t* out, DdsBatch 
     const uint32_t x = (blockIdx.x * 256u + threadIdx.x) * (WIDE ? 4u : 1u);
     if (x >= im.width) return;
     uint8_t* dst = out + im.fileOffset;
-    const bool srcAligned = multiple_of_dev(im.pixels, im.pitch, 4u);
+    const bool srcAligned = multiple_of(im.pixels, im.pitch, 4u);
     for (uint32_t y = blockIdx.y; y < im.rows; y += gridDim.y)
     {
         const uint8_t* s = im.pixels + uint64_t(y) * im.pitch + uint64_t(x) * 4u;
         uint8_t* d = dst + uint64_t(y) * im.filePitch + uint64_t(x) * 3u;
         if constexpr (WIDE)
         {
-            const uint4 v = *reinterpret_cast<const uint4*>(s);
-            const uint32_t t0 = dds_pack24_texel(v.x), t1 = dds_pack24_texel(v.y), t2 = dds_pack24_texel(v.z), t3 = dds_pack24_texel(v.w);
-            uint32_t* o = reinterpret_cast<uint32_t*>(d);
-            o[0] = t0 | (t1 << 24); o[1] = (t1 >> 8) | (t2 << 16); o[2] = (t2 >> 16) | (t3 << 8);
+            uint32_t t[4], o[3];
+            load_span<4u>(s, t);
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) t[k] = dds_pack24_texel(t[k]);
+            pack3x4(t, o);
+            store_span<3u>(d, o);
         }
-        else dds_store(d, dds_pack24_texel(load1<4u>(s, srcAligned)), 3u);
+        else le_store64(d, dds_pack24_texel(load1<4u>(s, srcAligned)), 3u);
     }
 }
-
-inline bool multiple_of(const void* p, uint64_t pitch, uint32_t bytes) { return ((reinterpret_cast<uintptr_t>(p) | pitch) & (bytes - 1u)) == 0; }
 
 // THE RULE of the wide route (see the top of the file)
 template<int OP, int TARGET>
@@ -222,11 +178,7 @@ struct Pending
         lanes = std::max(lanes, uint32_t((uint64_t(im.width) + unit - 1u) / unit));
         rows = std::max(rows, im.rows);
     }
-    dim3 grid() const
-    {
-        const uint32_t gx = (lanes + 255u) / 256u;
-        return dim3(gx, std::min<uint32_t>(std::min<uint32_t>(rows, 65535u), std::max<uint32_t>(1u, 8192u / gx)), count);
-    }
+    dim3 grid() const { return stream_grid(lanes, rows, 1u, count); }
     void clear() { for (uint32_t k = 0; k < count; ++k) batch.image[k] = DdsImage{}; count = lanes = rows = 0; }
 };
 
@@ -240,19 +192,17 @@ struct MarkNames
 const MarkNames kMarkNames;
 const char* mark_name(int op, bool wide) { return kMarkNames.name[op][wide ? 1 : 0]; }
 
-template<int OP, int TARGET>
-hipError_t unpack_op(const uint8_t* payload, bool opaque, const DdsOpaque& rule, const uint32_t* palette, const DdsImage* images, size_t count, hipStream_t hs, KernelMarks* marks)
+// The batch, flush and route loop of both launchers: sorts a texture's images into wide and narrow batches, queues each batch as it fills
+// and the two rests at the end, wide first. route(im, unit) decides one image's route and the texels (bytes) a lane takes of it, and may
+// reshape the image; launch(batch, isWide) marks and queues one kernel.
+template<class Route, class Launch>
+hipError_t launch_batches(const DdsImage* images, size_t count, KernelMarks* marks, Route&& route, Launch&& launch)
 {
-    PaletteArg<OP> pal;
-    if constexpr (dds_has_palette(OP)) std::copy(palette, palette + 256, pal.word);
-    const uint32_t narrowUnit = OP == ROW_COPY ? std::max(1u, rule.texelBytes) : 1u, wideUnit = OP == ROW_COPY ? 16u : 4u;
     Pending wide, narrow;
     const auto flush = [&](Pending& p, bool isWide) -> hipError_t
     {
         if (!p.count) return hipSuccess;
-        if (marks) marks->mark(mark_name(OP, isWide));
-        if (isWide) hipLaunchKernelGGL((dds_unpack_kernel<OP, TARGET, true>), p.grid(), dim3(256), 0, hs, payload, p.batch, opaque ? 1u : 0u, rule, pal);
-        else hipLaunchKernelGGL((dds_unpack_kernel<OP, TARGET, false>), p.grid(), dim3(256), 0, hs, payload, p.batch, opaque ? 1u : 0u, rule, pal);
+        launch(p, isWide);
         p.clear();
         return hipGetLastError();
     };
@@ -261,17 +211,39 @@ hipError_t unpack_op(const uint8_t* payload, bool opaque, const DdsOpaque& rule,
     {
         DdsImage im = images[i];
         if (!im.width || !im.rows) continue;
-        // a copy whose rows lie back to back on both sides is one long row
-        if (OP == ROW_COPY && im.filePitch == im.width && im.pitch == im.width && uint64_t(im.width) * im.rows <= 0xFFFFFFF0ull) { im.width *= im.rows; im.rows = 1; }
-        const bool isWide = wide_ok<OP, TARGET>(payload, im);
+        uint32_t unit;
+        const bool isWide = route(im, unit);
         Pending& p = isWide ? wide : narrow;
-        p.add(im, isWide ? wideUnit : (OP == ROW_COPY && !rule.texelBytes && copy_words_ok(payload + im.fileOffset, im)) ? 4u : narrowUnit);
+        p.add(im, unit);
         if (p.count == uint32_t(kDdsBatchMax)) e = flush(p, isWide);
     }
     if (e == hipSuccess) e = flush(wide, true);
     if (e == hipSuccess) e = flush(narrow, false);
-    if (marks) marks->mark(nullptr);
+    DXTEX_MARK(nullptr);
     return e;
+}
+
+template<int OP, int TARGET>
+hipError_t unpack_op(const uint8_t* payload, bool opaque, const DdsOpaque& rule, const uint32_t* palette, const DdsImage* images, size_t count, hipStream_t hs, KernelMarks* marks)
+{
+    PaletteArg<dds_has_palette(OP)> pal;
+    if constexpr (dds_has_palette(OP)) std::copy(palette, palette + 256, pal.word);
+    const uint32_t narrowUnit = OP == ROW_COPY ? std::max(1u, rule.texelBytes) : 1u, wideUnit = OP == ROW_COPY ? 16u : 4u;
+    return launch_batches(images, count, marks,
+        [&](DdsImage& im, uint32_t& unit)
+        {
+            // a copy whose rows lie back to back on both sides is one long row
+            if (OP == ROW_COPY && im.filePitch == im.width && im.pitch == im.width && uint64_t(im.width) * im.rows <= 0xFFFFFFF0ull) { im.width *= im.rows; im.rows = 1; }
+            const bool isWide = wide_ok<OP, TARGET>(payload, im);
+            unit = isWide ? wideUnit : (OP == ROW_COPY && !rule.texelBytes && copy_words_ok(payload + im.fileOffset, im)) ? 4u : narrowUnit;
+            return isWide;
+        },
+        [&](const Pending& p, bool isWide)
+        {
+            DXTEX_MARK(mark_name(OP, isWide));
+            if (isWide) hipLaunchKernelGGL((dds_unpack_kernel<OP, TARGET, true>), p.grid(), dim3(256), 0, hs, payload, p.batch, opaque ? 1u : 0u, rule, pal);
+            else hipLaunchKernelGGL((dds_unpack_kernel<OP, TARGET, false>), p.grid(), dim3(256), 0, hs, payload, p.batch, opaque ? 1u : 0u, rule, pal);
+        });
 }
 } // namespace
 
@@ -300,29 +272,18 @@ hipError_t launch_dds_pack24(const DdsImage* images, size_t count, uint8_t* out,
 {
     for (size_t i = 0; i < count; ++i)
         if (!dds_image_in_payload(images[i], 3u, outBytes)) return hipErrorInvalidValue;
-    Pending wide, narrow;
-    const auto flush = [&](Pending& p, bool isWide) -> hipError_t
-    {
-        if (!p.count) return hipSuccess;
-        if (marks) marks->mark(isWide ? "dds_pack24<wide>" : "dds_pack24<narrow>");
-        if (isWide) hipLaunchKernelGGL((dds_pack24_kernel<true>), p.grid(), dim3(256), 0, hs, out, p.batch);
-        else hipLaunchKernelGGL((dds_pack24_kernel<false>), p.grid(), dim3(256), 0, hs, out, p.batch);
-        p.clear();
-        return hipGetLastError();
-    };
-    hipError_t e = hipSuccess;
-    for (size_t i = 0; i < count && e == hipSuccess; ++i)
-    {
-        const DdsImage& im = images[i];
-        if (!im.width || !im.rows) continue;
-        const bool isWide = pack24_wide_ok(out, im);
-        Pending& p = isWide ? wide : narrow;
-        p.add(im, isWide ? 4u : 1u);
-        if (p.count == uint32_t(kDdsBatchMax)) e = flush(p, isWide);
-    }
-    if (e == hipSuccess) e = flush(wide, true);
-    if (e == hipSuccess) e = flush(narrow, false);
-    if (marks) marks->mark(nullptr);
-    return e;
+    return launch_batches(images, count, marks,
+        [&](DdsImage& im, uint32_t& unit)
+        {
+            const bool isWide = pack24_wide_ok(out, im);
+            unit = isWide ? 4u : 1u;
+            return isWide;
+        },
+        [&](const Pending& p, bool isWide)
+        {
+            DXTEX_MARK(isWide ? "dds_pack24<wide>" : "dds_pack24<narrow>");
+            if (isWide) hipLaunchKernelGGL((dds_pack24_kernel<true>), p.grid(), dim3(256), 0, hs, out, p.batch);
+            else hipLaunchKernelGGL((dds_pack24_kernel<false>), p.grid(), dim3(256), 0, hs, out, p.batch);
+        });
 }
 } // namespace dxtex

@@ -29,13 +29,7 @@
 // Every other (op, result format) pair is refused (dds_target() < 0): the reader answers E_FAIL for it. The opaque flag (CV_NOALPHA) sets
 // the alpha of the ops that carry one; the others are opaque by construction.
 #pragma once
-#if defined(__HIPCC__) || defined(__HIP__)
-#include <hip/hip_runtime.h>
-#define DXTEX_DDS_FN __host__ __device__ inline
-#else
-#define DXTEX_DDS_FN inline
-#endif
-#include <stdint.h>
+#include "dxtex_stream.h"
 
 namespace dxtex
 {
@@ -62,7 +56,7 @@ enum : int
 };
 
 // bytes of a file texel per op; 0 for ROW_COPY (which works in bytes) and anything that is no op
-DXTEX_DDS_FN constexpr uint32_t dds_file_bytes(int op)
+DXTEX_FN constexpr uint32_t dds_file_bytes(int op)
 {
     return (op == ROW_332 || op == ROW_P8 || op == ROW_44 || op == ROW_L8) ? 1u
          : (op == ROW_565 || op == ROW_5551 || op == ROW_4444 || op == ROW_ABGR4 || op == ROW_8332 || op == ROW_A8P8 || op == ROW_L16 || op == ROW_A8L8 || op == ROW_L6V5U5) ? 2u
@@ -70,19 +64,19 @@ DXTEX_DDS_FN constexpr uint32_t dds_file_bytes(int op)
          : (op == ROW_SWIZZLE || op == ROW_L8U8V8 || op == ROW_WUV10) ? 4u : 0u;
 }
 // bytes of an image texel per target; 0 for DDS_TO_BYTES
-DXTEX_DDS_FN constexpr uint32_t dds_image_bytes(int target)
+DXTEX_FN constexpr uint32_t dds_image_bytes(int target)
 {
     return (target == DDS_TO_8888 || target == DDS_TO_1010102 || target == DDS_TO_YUY2) ? 4u : (target == DDS_TO_565 || target == DDS_TO_4444) ? 2u
          : target == DDS_TO_16161616 ? 8u : 0u;
 }
-DXTEX_DDS_FN constexpr bool dds_has_palette(int op) { return op == ROW_P8 || op == ROW_A8P8; }
+DXTEX_FN constexpr bool dds_has_palette(int op) { return op == ROW_P8 || op == ROW_A8P8; }
 
-DXTEX_DDS_FN constexpr bool dds_is_8888(int f)
+DXTEX_FN constexpr bool dds_is_8888(int f)
 {
     return f == DDS_F_R8G8B8A8_TYPELESS || f == DDS_F_R8G8B8A8_UNORM || f == DDS_F_R8G8B8A8_UNORM_SRGB || f == DDS_F_B8G8R8A8_UNORM || f == DDS_F_B8G8R8X8_UNORM
         || f == DDS_F_B8G8R8A8_TYPELESS || f == DDS_F_B8G8R8A8_UNORM_SRGB || f == DDS_F_B8G8R8X8_TYPELESS || f == DDS_F_B8G8R8X8_UNORM_SRGB;
 }
-DXTEX_DDS_FN constexpr bool dds_is_1010102(int f)
+DXTEX_FN constexpr bool dds_is_1010102(int f)
 {
     return f == DDS_F_R10G10B10A2_TYPELESS || f == DDS_F_R10G10B10A2_UNORM || f == DDS_F_R10G10B10A2_UINT || f == DDS_F_R10G10B10_XR_BIAS_A2_UNORM
         || f == DDS_F_R10G10B10_SNORM_A2_UNORM;
@@ -90,7 +84,7 @@ DXTEX_DDS_FN constexpr bool dds_is_1010102(int f)
 
 // The refusal table: the target of (op, result format), or -1 where the reader answers E_FAIL (every expansion into anything but
 // R8G8B8A8_UNORM, except 332 into B5G6R5, 44 into B4G4R4A4, L16 into R16G16B16A16_UNORM and WUV10 into R10G10B10A2_UNORM; ROW_FAIL).
-DXTEX_DDS_FN constexpr int dds_target(int op, int format)
+DXTEX_FN constexpr int dds_target(int op, int format)
 {
     return op == ROW_COPY ? DDS_TO_BYTES
          : op == ROW_SWIZZLE ? (dds_is_1010102(format) ? DDS_TO_1010102 : dds_is_8888(format) ? DDS_TO_8888 : format == DDS_F_YUY2 ? DDS_TO_YUY2 : DDS_TO_BYTES)
@@ -103,18 +97,18 @@ DXTEX_DDS_FN constexpr int dds_target(int op, int format)
 }
 
 // an n-bit channel widened to `to` bits by repeating its bit pattern (what all the legacy expansions do)
-DXTEX_DDS_FN constexpr uint32_t dds_widen(uint32_t v, unsigned n, unsigned to)
+DXTEX_FN constexpr uint32_t dds_widen(uint32_t v, unsigned n, unsigned to)
 {
     uint32_t out = 0; unsigned have = 0;
     while (have < to) { out = (out << n) | v; have += n; }
     return out >> (have - to);
 }
-DXTEX_DDS_FN constexpr uint32_t dds_rgba8(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return r | (g << 8) | (b << 16) | (a << 24); }
-DXTEX_DDS_FN constexpr uint32_t dds_flip(uint32_t v, unsigned bits) { return v ^ (1u << (bits - 1)); }        // two's complement -> offset binary
+DXTEX_FN constexpr uint32_t dds_rgba8(uint32_t r, uint32_t g, uint32_t b, uint32_t a) { return r | (g << 8) | (b << 16) | (a << 24); }
+DXTEX_FN constexpr uint32_t dds_flip(uint32_t v, unsigned bits) { return v ^ (1u << (bits - 1)); }        // two's complement -> offset binary
 
 // One file texel `t` (its bytes as a word, the rest zero) as the image stores it: the low dds_image_bytes(target) bytes of the result.
 // target = dds_target(op, format) >= 0, never DDS_TO_BYTES; palette is read by ROW_P8 and ROW_A8P8 only.
-DXTEX_DDS_FN uint64_t dds_unpack_texel(uint32_t t, int op, int target, bool opaque, const uint32_t* palette)
+DXTEX_FN uint64_t dds_unpack_texel(uint32_t t, int op, int target, bool opaque, const uint32_t* palette)
 {
     switch (op)
     {
@@ -185,7 +179,7 @@ DXTEX_DDS_FN uint64_t dds_unpack_texel(uint32_t t, int op, int target, bool opaq
 // bytes whose LAST min(4, texelBytes) bytes, as a word v, become (v & keep) | set. texelBytes = 0: the format has no alpha the reader
 // forces, and its bytes pass unchanged.
 struct DdsOpaque { uint32_t texelBytes, keep, set; };
-DXTEX_DDS_FN constexpr DdsOpaque dds_opaque_of(int f)
+DXTEX_FN constexpr DdsOpaque dds_opaque_of(int f)
 {
     return (f == DDS_F_R32G32B32A32_TYPELESS || f == DDS_F_R32G32B32A32_FLOAT || f == DDS_F_R32G32B32A32_UINT || f == DDS_F_R32G32B32A32_SINT)
              ? DdsOpaque{ 16u, 0u, f == DDS_F_R32G32B32A32_FLOAT ? 0x3f800000u : f == DDS_F_R32G32B32A32_SINT ? 0x7fffffffu : 0xffffffffu }
@@ -204,32 +198,18 @@ DXTEX_DDS_FN constexpr DdsOpaque dds_opaque_of(int f)
          : DdsOpaque{ 0u, 0xffffffffu, 0u };
 }
 // the last word of one texel, forced opaque
-DXTEX_DDS_FN constexpr uint32_t dds_opaque_word(uint32_t v, const DdsOpaque& o) { return (v & o.keep) | o.set; }
+DXTEX_FN constexpr uint32_t dds_opaque_word(uint32_t v, const DdsOpaque& o) { return (v & o.keep) | o.set; }
 
 // The same on 16 consecutive bytes of whole texels held as four dwords (16 is a multiple of every texelBytes): dword i changes if bit i of
 // `which` is set, to (v & keep) | set with the two masks below.
 struct DdsOpaque16 { uint32_t which, keep, set; };
-DXTEX_DDS_FN constexpr DdsOpaque16 dds_opaque16_of(const DdsOpaque& o)
+DXTEX_FN constexpr DdsOpaque16 dds_opaque16_of(const DdsOpaque& o)
 {
     return o.texelBytes == 16u ? DdsOpaque16{ 0x8u, o.keep, o.set } : o.texelBytes == 8u ? DdsOpaque16{ 0xAu, o.keep, o.set }
          : o.texelBytes == 4u ? DdsOpaque16{ 0xFu, o.keep, o.set } : o.texelBytes == 2u ? DdsOpaque16{ 0xFu, o.keep | (o.keep << 16), o.set | (o.set << 16) }
          : o.texelBytes == 1u ? DdsOpaque16{ 0xFu, 0u, o.set * 0x01010101u } : DdsOpaque16{ 0u, 0xffffffffu, 0u };
 }
 
-// a file or image texel of 1 to 4 bytes at any address
-DXTEX_DDS_FN uint32_t dds_load(const uint8_t* s, uint32_t bytes)
-{
-    uint32_t t = s[0];
-    if (bytes > 1) t |= uint32_t(s[1]) << 8;
-    if (bytes > 2) t |= uint32_t(s[2]) << 16;
-    if (bytes > 3) t |= uint32_t(s[3]) << 24;
-    return t;
-}
-DXTEX_DDS_FN void dds_store(uint8_t* d, uint64_t t, uint32_t bytes)
-{
-    for (uint32_t i = 0; i < bytes; ++i) d[i] = uint8_t(t >> (8u * i));
-}
-
 // The writer's 24-bit rows (SaveToDDSMemory with DDS_FLAGS_FORCE_24BPP_RGB): a B8G8R8X8 texel loses its fourth byte
-DXTEX_DDS_FN constexpr uint32_t dds_pack24_texel(uint32_t t) { return t & 0x00ffffffu; }
+DXTEX_FN constexpr uint32_t dds_pack24_texel(uint32_t t) { return t & 0x00ffffffu; }
 } // namespace dxtex

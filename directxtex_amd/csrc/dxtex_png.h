@@ -24,13 +24,7 @@
 //   PNG_SRC_R8 -> grey 8, PNG_SRC_R16 -> grey 16, PNG_SRC_RGBA8 / PNG_SRC_BGRA8 -> RGBA 8 (B and R exchanged for the latter),
 //   PNG_SRC_RGBA16 -> RGBA 16, PNG_SRC_BGRX8 -> RGB 8 (exchanged, X dropped). 16-bit samples are written big-endian.
 #pragma once
-#if defined(__HIPCC__) || defined(__HIP__)
-#include <hip/hip_runtime.h>
-#define DXTEX_PNG_FN __host__ __device__ inline
-#else
-#define DXTEX_PNG_FN inline
-#endif
-#include <stdint.h>
+#include "dxtex_stream.h"
 
 namespace dxtex
 {
@@ -39,37 +33,31 @@ enum PngFlags : uint32_t { PNG_BGR = 0x1 };          // DXTEX_PNG_BGR of include
 enum PngSource : int { PNG_SRC_R8 = 0, PNG_SRC_R16, PNG_SRC_RGBA8, PNG_SRC_BGRA8, PNG_SRC_RGBA16, PNG_SRC_BGRX8, PNG_SOURCES };
 
 // bits of a file texel, bytes of an image texel, per reader kind
-DXTEX_PNG_FN constexpr uint32_t png_file_bits(int kind)
+DXTEX_FN constexpr uint32_t png_file_bits(int kind)
 {
     return (kind == PNG_G1 || kind == PNG_P1) ? 1u : (kind == PNG_G2 || kind == PNG_P2) ? 2u : (kind == PNG_G4 || kind == PNG_P4) ? 4u :
            (kind == PNG_G8 || kind == PNG_P8) ? 8u : (kind == PNG_G16 || kind == PNG_GA8) ? 16u : kind == PNG_RGB8 ? 24u :
            (kind == PNG_GA16 || kind == PNG_RGBA8) ? 32u : kind == PNG_RGB16 ? 48u : 64u;
 }
-DXTEX_PNG_FN constexpr uint32_t png_image_bytes(int kind)
+DXTEX_FN constexpr uint32_t png_image_bytes(int kind)
 {
     return kind <= PNG_G8 ? 1u : kind == PNG_G16 ? 2u : (kind == PNG_GA16 || kind == PNG_RGB16 || kind == PNG_RGBA16) ? 8u : 4u;
 }
-DXTEX_PNG_FN constexpr bool png_is_palette(int kind) { return kind >= PNG_P1 && kind <= PNG_P8; }
-DXTEX_PNG_FN constexpr bool png_is_sub_byte(int kind) { return png_file_bits(kind) < 8u; }
+DXTEX_FN constexpr bool png_is_palette(int kind) { return kind >= PNG_P1 && kind <= PNG_P8; }
+DXTEX_FN constexpr bool png_is_sub_byte(int kind) { return png_file_bits(kind) < 8u; }
 // the kinds PNG_BGR changes
-DXTEX_PNG_FN constexpr bool png_takes_bgr(int kind) { return kind == PNG_RGB8 || kind == PNG_RGBA8 || png_is_palette(kind); }
+DXTEX_FN constexpr bool png_takes_bgr(int kind) { return kind == PNG_RGB8 || kind == PNG_RGBA8 || png_is_palette(kind); }
 // bytes of one unfiltered row of the file
-DXTEX_PNG_FN constexpr uint64_t png_row_bytes(int kind, uint64_t width) { return (width * png_file_bits(kind) + 7u) / 8u; }
+DXTEX_FN constexpr uint64_t png_row_bytes(int kind, uint64_t width) { return (width * png_file_bits(kind) + 7u) / 8u; }
 // a sub-byte grey sample to 8 bits
-DXTEX_PNG_FN constexpr uint32_t png_grey_scale(uint32_t bits) { return bits == 1u ? 255u : bits == 2u ? 85u : 17u; }
+DXTEX_FN constexpr uint32_t png_grey_scale(uint32_t bits) { return bits == 1u ? 255u : bits == 2u ? 85u : 17u; }
 
 // the writer's side: bytes of an image texel and of a file texel per source
-DXTEX_PNG_FN constexpr uint32_t png_source_bytes(int src) { return src == PNG_SRC_R8 ? 1u : src == PNG_SRC_R16 ? 2u : src == PNG_SRC_RGBA16 ? 8u : 4u; }
-DXTEX_PNG_FN constexpr uint32_t png_source_file_bytes(int src) { return src == PNG_SRC_BGRX8 ? 3u : png_source_bytes(src); }
-
-DXTEX_PNG_FN constexpr uint64_t png_swap16(uint64_t e) { return ((e & 0xFFu) << 8) | ((e >> 8) & 0xFFu); }
-// each of four 16-bit samples of a word swapped
-DXTEX_PNG_FN constexpr uint64_t png_swap16x4(uint64_t t) { return ((t & 0x00FF00FF00FF00FFull) << 8) | ((t >> 8) & 0x00FF00FF00FF00FFull); }
-// bytes 0 and 2 of a word exchanged
-DXTEX_PNG_FN constexpr uint32_t png_exchange(uint32_t t) { return (t & 0xFF00FF00u) | ((t >> 16) & 0xFFu) | ((t & 0xFFu) << 16); }
+DXTEX_FN constexpr uint32_t png_source_bytes(int src) { return src == PNG_SRC_R8 ? 1u : src == PNG_SRC_R16 ? 2u : src == PNG_SRC_RGBA16 ? 8u : 4u; }
+DXTEX_FN constexpr uint32_t png_source_file_bytes(int src) { return src == PNG_SRC_BGRX8 ? 3u : png_source_bytes(src); }
 
 // The table a palette kind reads: 256 words. rgb = `count` entries of 3 bytes (PLTE), alpha = `alphaCount` bytes (tRNS) or null.
-DXTEX_PNG_FN void png_palette_table(const uint8_t* rgb, uint32_t count, const uint8_t* alpha, uint32_t alphaCount, uint32_t (&table)[256])
+DXTEX_FN void png_palette_table(const uint8_t* rgb, uint32_t count, const uint8_t* alpha, uint32_t alphaCount, uint32_t (&table)[256])
 {
     for (uint32_t i = 0; i < 256u; ++i)
     {
@@ -81,75 +69,63 @@ DXTEX_PNG_FN void png_palette_table(const uint8_t* rgb, uint32_t count, const ui
 
 // One file texel of a kind with whole bytes, its bytes as a little-endian word -> the image texel likewise. table = the palette's 256
 // words (PNG_P8), else unused.
-DXTEX_PNG_FN uint64_t png_texel(int kind, uint64_t t, bool bgr, const uint32_t* table)
+DXTEX_FN uint64_t png_texel(int kind, uint64_t t, bool bgr, const uint32_t* table)
 {
     switch (kind)
     {
     case PNG_G8: return t & 0xFFu;
-    case PNG_G16: return png_swap16(t);
+    case PNG_G16: return swap16(uint32_t(t));
     case PNG_GA8: { const uint64_t g = t & 0xFFu; return g | (g << 8) | (g << 16) | (((t >> 8) & 0xFFu) << 24); }
-    case PNG_GA16: { const uint64_t g = png_swap16(t), a = png_swap16(t >> 16); return g | (g << 16) | (g << 32) | (a << 48); }
-    case PNG_RGB8: { const uint32_t w = (uint32_t(t) & 0x00FFFFFFu) | 0xFF000000u; return bgr ? png_exchange(w) : w; }
-    case PNG_RGB16: return png_swap16x4(t & 0x0000FFFFFFFFFFFFull) | 0xFFFF000000000000ull;
-    case PNG_RGBA8: return bgr ? png_exchange(uint32_t(t)) : uint32_t(t);
-    case PNG_RGBA16: return png_swap16x4(t);
-    case PNG_P8: { const uint32_t w = table[t & 0xFFu]; return bgr ? png_exchange(w) : w; }
+    case PNG_GA16: { const uint64_t g = swap16(uint32_t(t)), a = swap16(uint32_t(t >> 16)); return g | (g << 16) | (g << 32) | (a << 48); }
+    case PNG_RGB8: { const uint32_t w = (uint32_t(t) & 0x00FFFFFFu) | 0xFF000000u; return bgr ? swap_rb(w) : w; }
+    case PNG_RGB16: return swap16x4(t & 0x0000FFFFFFFFFFFFull) | 0xFFFF000000000000ull;
+    case PNG_RGBA8: return bgr ? swap_rb(uint32_t(t)) : uint32_t(t);
+    case PNG_RGBA16: return swap16x4(t);
+    case PNG_P8: { const uint32_t w = table[t & 0xFFu]; return bgr ? swap_rb(w) : w; }
     default: return 0;
     }
 }
 
 // Texel j (0 .. 8 / bits - 1) of a byte of a sub-byte kind: the first one sits in the high bits
-DXTEX_PNG_FN constexpr uint32_t png_sample(uint32_t byte, uint32_t bits, uint32_t j) { return (byte >> (8u - bits * (j + 1u))) & ((1u << bits) - 1u); }
-DXTEX_PNG_FN uint32_t png_sub_byte_texel(int kind, uint32_t byte, uint32_t j, bool bgr, const uint32_t* table)
+DXTEX_FN constexpr uint32_t png_sample(uint32_t byte, uint32_t bits, uint32_t j) { return (byte >> (8u - bits * (j + 1u))) & ((1u << bits) - 1u); }
+DXTEX_FN uint32_t png_sub_byte_texel(int kind, uint32_t byte, uint32_t j, bool bgr, const uint32_t* table)
 {
     const uint32_t bits = png_file_bits(kind), s = png_sample(byte, bits, j);
     if (!png_is_palette(kind)) return s * png_grey_scale(bits);
-    return bgr ? png_exchange(table[s]) : table[s];
+    return bgr ? swap_rb(table[s]) : table[s];
 }
 
 // The writer's texel: an image texel as a little-endian word -> the file texel likewise (png_source_file_bytes(src) bytes of it count)
-DXTEX_PNG_FN uint64_t png_pack(int src, uint64_t t)
+DXTEX_FN uint64_t png_pack(int src, uint64_t t)
 {
     switch (src)
     {
     case PNG_SRC_R8: return t & 0xFFu;
-    case PNG_SRC_R16: return png_swap16(t);
+    case PNG_SRC_R16: return swap16(uint32_t(t));
     case PNG_SRC_RGBA8: return uint32_t(t);
-    case PNG_SRC_BGRA8: return png_exchange(uint32_t(t));
-    case PNG_SRC_RGBA16: return png_swap16x4(t);
-    case PNG_SRC_BGRX8: return png_exchange(uint32_t(t)) & 0x00FFFFFFu;
+    case PNG_SRC_BGRA8: return swap_rb(uint32_t(t));
+    case PNG_SRC_RGBA16: return swap16x4(t);
+    case PNG_SRC_BGRX8: return swap_rb(uint32_t(t)) & 0x00FFFFFFu;
     default: return 0;
     }
 }
 
-DXTEX_PNG_FN uint64_t png_load(const uint8_t* s, uint32_t bytes)
-{
-    uint64_t t = 0;
-    for (uint32_t b = 0; b < bytes; ++b) t |= uint64_t(s[b]) << (8u * b);
-    return t;
-}
-
-DXTEX_PNG_FN void png_store(uint8_t* d, uint64_t t, uint32_t bytes)
-{
-    for (uint32_t b = 0; b < bytes; ++b) d[b] = uint8_t(t >> (8u * b));
-}
-
 // Texel x of an unfiltered file row -> one image texel at d, byte by byte: the host codec's loop body and what the kernels' narrow route
 // does. Reads the byte(s) of texel x in `row`, writes png_image_bytes(kind).
-DXTEX_PNG_FN void png_unpack_texel(const uint8_t* row, uint64_t x, uint8_t* d, int kind, bool bgr, const uint32_t* table)
+DXTEX_FN void png_unpack_texel(const uint8_t* row, uint64_t x, uint8_t* d, int kind, bool bgr, const uint32_t* table)
 {
     const uint32_t bits = png_file_bits(kind), D = png_image_bytes(kind);
     if (bits < 8u)
     {
         const uint32_t per = 8u / bits;
-        png_store(d, png_sub_byte_texel(kind, row[x / per], uint32_t(x % per), bgr, table), D);
+        le_store64(d, png_sub_byte_texel(kind, row[x / per], uint32_t(x % per), bgr, table), D);
     }
-    else png_store(d, png_texel(kind, png_load(row + x * (bits / 8u), bits / 8u), bgr, table), D);
+    else le_store64(d, png_texel(kind, le_load64(row + x * (bits / 8u), bits / 8u), bgr, table), D);
 }
 
 // One image texel at s -> one file texel at d, byte by byte
-DXTEX_PNG_FN void png_pack_texel(const uint8_t* s, uint8_t* d, int src)
+DXTEX_FN void png_pack_texel(const uint8_t* s, uint8_t* d, int src)
 {
-    png_store(d, png_pack(src, png_load(s, png_source_bytes(src))), png_source_file_bytes(src));
+    le_store64(d, png_pack(src, le_load64(s, png_source_bytes(src))), png_source_file_bytes(src));
 }
 } // namespace dxtex

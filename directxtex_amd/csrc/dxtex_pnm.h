@@ -27,7 +27,6 @@
 // The reference's flip is FlipRotate's TEX_FR_FLIP_VERTICAL, of which only "row y becomes row height - 1 - y" is taken.
 #pragma once
 #include "dxtex_rgbe.h"
-#define DXTEX_PNM_FN DXTEX_RGBE_FN
 
 namespace dxtex
 {
@@ -36,45 +35,42 @@ enum PnmFlags : uint32_t { PNM_BIG_ENDIAN = 0x1 };          // DXTEX_PNM_BIG_END
 enum PnmSource : int { PNM_SRC_RGBA8 = 0, PNM_SRC_BGRA8, PNM_SRC_RGBA32F, PNM_SRC_RGB32F, PNM_SRC_RGBA16F, PNM_SRC_R32F, PNM_SOURCES };
 
 // bytes of one element (a sample), elements of a file texel and of an image texel, per reader kind
-DXTEX_PNM_FN constexpr uint32_t pnm_element_bytes(int kind) { return kind == PNM_P6 ? 1u : (kind == PNM_PF || kind == PNM_Pf) ? 4u : 2u; }
-DXTEX_PNM_FN constexpr uint32_t pnm_file_elements(int kind) { return (kind == PNM_Pf || kind == PNM_Ph) ? 1u : 3u; }
-DXTEX_PNM_FN constexpr uint32_t pnm_image_elements(int kind) { return (kind == PNM_Pf || kind == PNM_Ph) ? 1u : 4u; }
-DXTEX_PNM_FN constexpr uint32_t pnm_file_bytes(int kind) { return pnm_element_bytes(kind) * pnm_file_elements(kind); }
-DXTEX_PNM_FN constexpr uint32_t pnm_image_bytes(int kind) { return pnm_element_bytes(kind) * pnm_image_elements(kind); }
+DXTEX_FN constexpr uint32_t pnm_element_bytes(int kind) { return kind == PNM_P6 ? 1u : (kind == PNM_PF || kind == PNM_Pf) ? 4u : 2u; }
+DXTEX_FN constexpr uint32_t pnm_file_elements(int kind) { return (kind == PNM_Pf || kind == PNM_Ph) ? 1u : 3u; }
+DXTEX_FN constexpr uint32_t pnm_image_elements(int kind) { return (kind == PNM_Pf || kind == PNM_Ph) ? 1u : 4u; }
+DXTEX_FN constexpr uint32_t pnm_file_bytes(int kind) { return pnm_element_bytes(kind) * pnm_file_elements(kind); }
+DXTEX_FN constexpr uint32_t pnm_image_bytes(int kind) { return pnm_element_bytes(kind) * pnm_image_elements(kind); }
 // the element that stands for an alpha of one
-DXTEX_PNM_FN constexpr uint32_t pnm_one(int kind) { return kind == PNM_P6 ? 0xFFu : (kind == PNM_PF || kind == PNM_Pf) ? 0x3F800000u : 0x3C00u; }
+DXTEX_FN constexpr uint32_t pnm_one(int kind) { return kind == PNM_P6 ? 0xFFu : (kind == PNM_PF || kind == PNM_Pf) ? 0x3F800000u : 0x3C00u; }
 // file row y is image row pnm_image_row(kind, y, height)
-DXTEX_PNM_FN constexpr uint32_t pnm_image_row(int kind, uint32_t y, uint32_t height) { return kind == PNM_P6 ? y : height - 1u - y; }
+DXTEX_FN constexpr uint32_t pnm_image_row(int kind, uint32_t y, uint32_t height) { return kind == PNM_P6 ? y : height - 1u - y; }
 
 // the writer's side: bytes of an image texel per source, the kind it is written as, bytes of a file texel
-DXTEX_PNM_FN constexpr uint32_t pnm_source_bytes(int src) { return src == PNM_SRC_RGBA32F ? 16u : src == PNM_SRC_RGB32F ? 12u : src == PNM_SRC_RGBA16F ? 8u : 4u; }
-DXTEX_PNM_FN constexpr int pnm_source_kind(int src) { return (src == PNM_SRC_RGBA8 || src == PNM_SRC_BGRA8) ? PNM_P6 : src == PNM_SRC_R32F ? PNM_Pf : PNM_PF; }
-
-DXTEX_PNM_FN constexpr uint32_t pnm_swap16(uint32_t e) { return ((e & 0xFFu) << 8) | ((e >> 8) & 0xFFu); }
-DXTEX_PNM_FN constexpr uint32_t pnm_swap32(uint32_t e) { return (e << 24) | ((e & 0xFF00u) << 8) | ((e >> 8) & 0xFF00u) | (e >> 24); }
+DXTEX_FN constexpr uint32_t pnm_source_bytes(int src) { return src == PNM_SRC_RGBA32F ? 16u : src == PNM_SRC_RGB32F ? 12u : src == PNM_SRC_RGBA16F ? 8u : 4u; }
+DXTEX_FN constexpr int pnm_source_kind(int src) { return (src == PNM_SRC_RGBA8 || src == PNM_SRC_BGRA8) ? PNM_P6 : src == PNM_SRC_R32F ? PNM_Pf : PNM_PF; }
 
 // 255 * i / maxval in uint32_t; 1 <= maxval <= 255 and i <= 255, so nothing wraps here
-DXTEX_PNM_FN constexpr uint32_t pnm_scale(uint32_t i, uint32_t maxval) { return 255u * i / maxval; }
+DXTEX_FN constexpr uint32_t pnm_scale(uint32_t i, uint32_t maxval) { return 255u * i / maxval; }
 
 // One P6 texel, its three bytes as a little-endian word (the top byte is ignored). scale = the table of pnm_scale(i, maxval), or null for
 // maxval == 255.
-DXTEX_PNM_FN uint32_t pnm_p6_texel(uint32_t rgb, const uint32_t* scale)
+DXTEX_FN uint32_t pnm_p6_texel(uint32_t rgb, const uint32_t* scale)
 {
     if (!scale) return rgb | 0xFF000000u;
     return scale[rgb & 0xFFu] | (scale[(rgb >> 8) & 0xFFu] << 8) | (scale[(rgb >> 16) & 0xFFu] << 16) | 0xFF000000u;          // modulo 2^32
 }
 
 // One element of a float kind, its bytes as a little-endian word, as the image holds it
-DXTEX_PNM_FN constexpr uint32_t pnm_element(uint32_t e, uint32_t bytes, bool bigEndian) { return !bigEndian ? e : bytes == 2u ? pnm_swap16(e) : pnm_swap32(e); }
+DXTEX_FN constexpr uint32_t pnm_element(uint32_t e, uint32_t bytes, bool bigEndian) { return !bigEndian ? e : bytes == 2u ? swap16(e) : swap32(e); }
 
 // The writer's P6 texel: an image word -> R, G, B in the low three bytes
-DXTEX_PNM_FN constexpr uint32_t pnm_pack_p6(uint32_t t, bool bgr)
+DXTEX_FN constexpr uint32_t pnm_pack_p6(uint32_t t, bool bgr)
 {
-    return bgr ? (((t >> 16) & 0xFFu) | (t & 0xFF00u) | ((t & 0xFFu) << 16)) : (t & 0x00FFFFFFu);
+    return (bgr ? swap_rb(t) : t) & 0x00FFFFFFu;
 }
 
 // The writer's half -> float, as bits
-DXTEX_PNM_FN uint32_t pnm_half_to_float_bits(uint32_t h)
+DXTEX_FN uint32_t pnm_half_to_float_bits(uint32_t h)
 {
     const float f = rgbe_half_to_float(uint16_t(h));
     uint32_t bits;
@@ -82,42 +78,25 @@ DXTEX_PNM_FN uint32_t pnm_half_to_float_bits(uint32_t h)
     return bits;
 }
 
-DXTEX_PNM_FN uint32_t pnm_load(const uint8_t* s, uint32_t bytes)
-{
-    uint32_t t = s[0];
-    if (bytes > 1) t |= uint32_t(s[1]) << 8;
-    if (bytes > 2) t |= uint32_t(s[2]) << 16;
-    if (bytes > 3) t |= uint32_t(s[3]) << 24;
-    return t;
-}
-
-DXTEX_PNM_FN void pnm_store(uint8_t* d, uint32_t t, uint32_t bytes)
-{
-    d[0] = uint8_t(t);
-    if (bytes > 1) d[1] = uint8_t(t >> 8);
-    if (bytes > 2) d[2] = uint8_t(t >> 16);
-    if (bytes > 3) d[3] = uint8_t(t >> 24);
-}
-
 // One file texel at s -> one image texel at d, byte by byte: the host codec's loop body and what the kernels' narrow route does where
 // nothing is aligned. Reads pnm_file_bytes(kind) bytes, writes pnm_image_bytes(kind).
-DXTEX_PNM_FN void pnm_unpack_texel(const uint8_t* s, uint8_t* d, int kind, bool bigEndian, const uint32_t* scale)
+DXTEX_FN void pnm_unpack_texel(const uint8_t* s, uint8_t* d, int kind, bool bigEndian, const uint32_t* scale)
 {
-    if (kind == PNM_P6) { pnm_store(d, pnm_p6_texel(pnm_load(s, 3u), scale), 4u); return; }
+    if (kind == PNM_P6) { le_store32(d, pnm_p6_texel(le_load32(s, 3u), scale), 4u); return; }
     const uint32_t E = pnm_element_bytes(kind), n = pnm_file_elements(kind);
-    for (uint32_t c = 0; c < n; ++c) pnm_store(d + c * E, pnm_element(pnm_load(s + c * E, E), E, bigEndian), E);
-    if (n == 3u) pnm_store(d + 3u * E, pnm_one(kind), E);
+    for (uint32_t c = 0; c < n; ++c) le_store32(d + c * E, pnm_element(le_load32(s + c * E, E), E, bigEndian), E);
+    if (n == 3u) le_store32(d + 3u * E, pnm_one(kind), E);
 }
 
 // One image texel at s -> one file texel at d, byte by byte. Reads pnm_source_bytes(src) bytes, writes pnm_file_bytes(pnm_source_kind(src)).
-DXTEX_PNM_FN void pnm_pack_texel(const uint8_t* s, uint8_t* d, int src)
+DXTEX_FN void pnm_pack_texel(const uint8_t* s, uint8_t* d, int src)
 {
     switch (src)
     {
-    case PNM_SRC_RGBA8: case PNM_SRC_BGRA8: pnm_store(d, pnm_pack_p6(pnm_load(s, 4u), src == PNM_SRC_BGRA8), 3u); break;
-    case PNM_SRC_RGBA16F: for (uint32_t c = 0; c < 3u; ++c) pnm_store(d + 4u * c, pnm_half_to_float_bits(pnm_load(s + 2u * c, 2u)), 4u); break;
-    case PNM_SRC_R32F: pnm_store(d, pnm_load(s, 4u), 4u); break;
-    default: for (uint32_t c = 0; c < 3u; ++c) pnm_store(d + 4u * c, pnm_load(s + 4u * c, 4u), 4u); break;          // RGBA32F, RGB32F
+    case PNM_SRC_RGBA8: case PNM_SRC_BGRA8: le_store32(d, pnm_pack_p6(le_load32(s, 4u), src == PNM_SRC_BGRA8), 3u); break;
+    case PNM_SRC_RGBA16F: for (uint32_t c = 0; c < 3u; ++c) le_store32(d + 4u * c, pnm_half_to_float_bits(le_load32(s + 2u * c, 2u)), 4u); break;
+    case PNM_SRC_R32F: le_store32(d, le_load32(s, 4u), 4u); break;
+    default: for (uint32_t c = 0; c < 3u; ++c) le_store32(d + 4u * c, le_load32(s + 4u * c, 4u), 4u); break;          // RGBA32F, RGB32F
     }
 }
 } // namespace dxtex

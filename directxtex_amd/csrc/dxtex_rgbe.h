@@ -14,18 +14,12 @@
 // +Inf: the reference's top is then a NaN whose conversion to uint8_t is undefined. Here it is defined: a maximum that is not finite writes
 // four zero bytes.
 #pragma once
-#if defined(__HIPCC__) || defined(__HIP__)
-#include <hip/hip_runtime.h>
-#define DXTEX_RGBE_FN __host__ __device__ inline
-#else
-#define DXTEX_RGBE_FN inline
-#endif
+#include "dxtex_stream.h"
 #include <math.h>
-#include <stdint.h>
 
 namespace dxtex
 {
-DXTEX_RGBE_FN void rgbe_decode(const uint8_t in[4], float scale, float out[4])
+DXTEX_FN void rgbe_decode(const uint8_t in[4], float scale, float out[4])
 {
     const int e = int(in[3]) - (128 + 8);
     out[0] = scale * ldexpf(float(in[0]) + 0.5f, e);
@@ -34,7 +28,7 @@ DXTEX_RGBE_FN void rgbe_decode(const uint8_t in[4], float scale, float out[4])
     out[3] = 1.0f;
 }
 
-DXTEX_RGBE_FN void rgbe_encode(float r, float g, float b, uint8_t out[4])
+DXTEX_FN void rgbe_encode(float r, float g, float b, uint8_t out[4])
 {
     r = (r >= 0.f) ? r : 0.f; g = (g >= 0.f) ? g : 0.f; b = (b >= 0.f) ? b : 0.f;         // negatives (and NaN) count as 0
     const float rg = (r > g) ? r : g;
@@ -49,7 +43,7 @@ DXTEX_RGBE_FN void rgbe_encode(float r, float g, float b, uint8_t out[4])
 }
 
 // XMConvertHalfToFloat's value: exact for every half, denormals included
-DXTEX_RGBE_FN float rgbe_half_to_float(uint16_t h)
+DXTEX_FN float rgbe_half_to_float(uint16_t h)
 {
     const uint32_t sign = uint32_t(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
     if (e == 0)

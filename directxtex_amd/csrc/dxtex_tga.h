@@ -1,7 +1,7 @@
 // Truevision TGA texels, both directions, per texel: shared by the GPU kernels (tga.hip), the host codec (host/DirectXTexAMD_TGA.cpp, a
 // plain C++ build) and the host check (tests/cpp/tga_check.cpp). Integer code: bytes move, nothing rounds.
 //
-// A file texel is its B = 1, 2, 3 or 4 bytes as a little-endian word (tga_load); what the reader makes of it is one of seven kinds, the
+// A file texel is its B = 1, 2, 3 or 4 bytes as a little-endian word (le_load32); what the reader makes of it is one of seven kinds, the
 // cases of DecodeTGAHeader / CopyPixels (DirectXTexTGA.cpp:110-258, :738-1180):
 //   TGA_GREY       1 byte            -> R8_UNORM        the byte
 //   TGA_5551       2 bytes           -> B5G5R5A1_UNORM  the word; alpha counts as 255 with bit 15 set, else as 0
@@ -17,13 +17,7 @@
 // The writer's three row kinds (SaveToTGAMemory, :2249-2330; Copy24bppScanline, :1288): copy (B = 1, 2 or 4), swap R and B
 // (R8G8B8A8[_SRGB], B = 4), drop X (B8G8R8X8[_SRGB], B = 3).
 #pragma once
-#if defined(__HIPCC__) || defined(__HIP__)
-#include <hip/hip_runtime.h>
-#define DXTEX_TGA_FN __host__ __device__ inline
-#else
-#define DXTEX_TGA_FN inline
-#endif
-#include <stdint.h>
+#include "dxtex_stream.h"
 
 namespace dxtex
 {
@@ -33,39 +27,20 @@ enum TgaRow : int { TGA_ROW_COPY = 0, TGA_ROW_SWAP_RB, TGA_ROW_DROP_X };
 enum TgaFlags : uint32_t { TGA_RIGHT_TO_LEFT = 0x1, TGA_TOP_DOWN = 0x2, TGA_ALLOW_ALL_ZERO_ALPHA = 0x4 };
 
 // bytes of a file texel / of an image texel, per kind
-DXTEX_TGA_FN constexpr uint32_t tga_file_bytes(int kind) { return kind == TGA_GREY || kind == TGA_PALETTE ? 1u : kind == TGA_5551 ? 2u : (kind == TGA_RGB_RGBA || kind == TGA_RGB_BGRX) ? 3u : 4u; }
-DXTEX_TGA_FN constexpr uint32_t tga_image_bytes(int kind) { return kind == TGA_GREY ? 1u : kind == TGA_5551 ? 2u : 4u; }
-DXTEX_TGA_FN constexpr bool tga_has_alpha_rule(int kind) { return kind == TGA_5551 || kind == TGA_BGRA_RGBA || kind == TGA_BGRA_BGRA; }
-
-DXTEX_TGA_FN constexpr uint32_t tga_swap_rb(uint32_t t) { return (t & 0xFF00FF00u) | ((t & 0xFFu) << 16) | ((t >> 16) & 0xFFu); }
-
-DXTEX_TGA_FN uint32_t tga_load(const uint8_t* s, uint32_t bytes)
-{
-    uint32_t t = s[0];
-    if (bytes > 1) t |= uint32_t(s[1]) << 8;
-    if (bytes > 2) t |= uint32_t(s[2]) << 16;
-    if (bytes > 3) t |= uint32_t(s[3]) << 24;
-    return t;
-}
-
-DXTEX_TGA_FN void tga_store(uint8_t* d, uint32_t t, uint32_t bytes)
-{
-    d[0] = uint8_t(t);
-    if (bytes > 1) d[1] = uint8_t(t >> 8);
-    if (bytes > 2) d[2] = uint8_t(t >> 16);
-    if (bytes > 3) d[3] = uint8_t(t >> 24);
-}
+DXTEX_FN constexpr uint32_t tga_file_bytes(int kind) { return kind == TGA_GREY || kind == TGA_PALETTE ? 1u : kind == TGA_5551 ? 2u : (kind == TGA_RGB_RGBA || kind == TGA_RGB_BGRX) ? 3u : 4u; }
+DXTEX_FN constexpr uint32_t tga_image_bytes(int kind) { return kind == TGA_GREY ? 1u : kind == TGA_5551 ? 2u : 4u; }
+DXTEX_FN constexpr bool tga_has_alpha_rule(int kind) { return kind == TGA_5551 || kind == TGA_BGRA_RGBA || kind == TGA_BGRA_BGRA; }
 
 // One file texel (its bytes as a word, the rest zero) as the image stores it; alpha = what the alpha rule sees of it (255 where the kind
 // has no alpha). palette is read by TGA_PALETTE only.
-DXTEX_TGA_FN uint32_t tga_unpack_texel(uint32_t t, int kind, const uint32_t* palette, uint32_t& alpha)
+DXTEX_FN uint32_t tga_unpack_texel(uint32_t t, int kind, const uint32_t* palette, uint32_t& alpha)
 {
     alpha = 255u;
     switch (kind)
     {
     case TGA_5551: alpha = (t & 0x8000u) ? 255u : 0u; return t;
-    case TGA_RGB_RGBA: return tga_swap_rb(t) | 0xFF000000u;
-    case TGA_BGRA_RGBA: alpha = t >> 24; return tga_swap_rb(t);
+    case TGA_RGB_RGBA: return swap_rb(t) | 0xFF000000u;
+    case TGA_BGRA_RGBA: alpha = t >> 24; return swap_rb(t);
     case TGA_BGRA_BGRA: alpha = t >> 24; return t;
     case TGA_PALETTE: return palette[t & 0xFFu];
     default: return t;          // TGA_GREY, and TGA_RGB_BGRX: X stays 0
@@ -75,15 +50,15 @@ DXTEX_TGA_FN uint32_t tga_unpack_texel(uint32_t t, int kind, const uint32_t* pal
 // The loader's answer from the two ORs over an image with an alpha rule (CopyPixels' tail, :1150-1180). 1: opaque - every alpha is 255, or
 // every alpha is zero and the caller did not allow that, in which case makeOpaque tells it to set them (alpha 255; bit 15 of a 5:5:5:1
 // word). 0: alpha is in use.
-DXTEX_TGA_FN uint32_t tga_alpha_answer(uint32_t orOfAlpha, uint32_t orOfNotAlpha, bool allowAllZero, bool& makeOpaque)
+DXTEX_FN uint32_t tga_alpha_answer(uint32_t orOfAlpha, uint32_t orOfNotAlpha, bool allowAllZero, bool& makeOpaque)
 {
     makeOpaque = orOfAlpha == 0u && !allowAllZero;
     return (makeOpaque || orOfNotAlpha == 0u) ? 1u : 0u;
 }
 
 // One image texel (its bytes as a word) as the file stores it; the low 3 bytes count for TGA_ROW_DROP_X
-DXTEX_TGA_FN constexpr uint32_t tga_pack_texel(uint32_t t, int row)
+DXTEX_FN constexpr uint32_t tga_pack_texel(uint32_t t, int row)
 {
-    return row == TGA_ROW_SWAP_RB ? tga_swap_rb(t) : row == TGA_ROW_DROP_X ? (t & 0x00FFFFFFu) : t;
+    return row == TGA_ROW_SWAP_RB ? swap_rb(t) : row == TGA_ROW_DROP_X ? (t & 0x00FFFFFFu) : t;
 }
 } // namespace dxtex

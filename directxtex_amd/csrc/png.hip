@@ -6,9 +6,9 @@
 //   png_pack_kernel    level 0 of an image -> the file's rows, tight: B and R exchanged for a BGR source, X dropped, 16-bit samples
 //                      swapped to big-endian
 //
-// 256 lanes, x across, rows strided over gridDim.y (rgbe.hip's grid). Two routes:
+// 256 lanes, x across, rows strided over gridDim.y (dxtex_stream.h's grid). Two routes:
 //   wide    whole-byte kinds: a lane takes four texels, 4 * B bytes of the stream and 4 * D bytes of the image, each moved as the widest
-//           aligned accesses its dword count allows (span_align: a multiple of four dwords as dwordx4, of two as dwordx2, else single
+//           aligned accesses its dword count allows (dxtex_stream.h's span_align: a multiple of four dwords as dwordx4, of two as dwordx2, else single
 //           dwords). RGB 8: three dwords in, one dwordx4 out. RGBA 16: two dwordx4 in and out. Grey 8 and palette 8: one dword in.
 //           Sub-byte kinds: a lane takes one byte of the stream and writes its 8, 4 or 2 texels: 8 bytes of grey 1, a dwordx4 of palette 2,
 //           two of palette 1.
@@ -27,59 +27,11 @@
 #include "dxtex_kernels.h"
 #include "dxtex_png.h"
 #include <algorithm>
-#include <type_traits>
 
 namespace dxtex
 {
 namespace
 {
-struct PngPalette { uint32_t word[256]; };
-struct PngNoPalette {};
-template<int KIND> using PaletteArg = std::conditional_t<png_is_palette(KIND), PngPalette, PngNoPalette>;
-
-// the alignment N consecutive dwords are moved with
-template<uint32_t N> constexpr uint32_t span_align() { return N % 4u == 0 ? 16u : N % 2u == 0 ? 8u : 4u; }
-
-template<uint32_t N>
-__device__ __forceinline__ void load_span(const uint8_t* s, uint32_t (&w)[N])
-{
-    if constexpr (N % 4u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 4u; ++i) { const uint4 v = reinterpret_cast<const uint4*>(s)[i]; w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w; }
-    }
-    else if constexpr (N % 2u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 2u; ++i) { const uint2 v = reinterpret_cast<const uint2*>(s)[i]; w[2 * i] = v.x; w[2 * i + 1] = v.y; }
-    }
-    else
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N; ++i) w[i] = reinterpret_cast<const uint32_t*>(s)[i];
-    }
-}
-
-template<uint32_t N>
-__device__ __forceinline__ void store_span(uint8_t* d, const uint32_t (&w)[N])
-{
-    if constexpr (N % 4u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 4u; ++i) reinterpret_cast<uint4*>(d)[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    }
-    else if constexpr (N % 2u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 2u; ++i) reinterpret_cast<uint2*>(d)[i] = make_uint2(w[2 * i], w[2 * i + 1]);
-    }
-    else
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N; ++i) reinterpret_cast<uint32_t*>(d)[i] = w[i];
-    }
-}
-
 // BYTES bytes at byte OFF of consecutive little-endian dwords, as a little-endian word; every index is a constant once unrolled
 template<uint32_t OFF, uint32_t BYTES, uint32_t N>
 __device__ __forceinline__ uint64_t get_bytes(const uint32_t (&w)[N])
@@ -127,14 +79,14 @@ __device__ __forceinline__ void unpack_one(const uint32_t (&in)[png_file_bits(KI
 }
 
 template<int KIND, bool WIDE>
-__global__ void __launch_bounds__(256) png_unpack_kernel(const uint8_t* stream, bool bgr, ImgView dst, PaletteArg<KIND> pal)
+__global__ void __launch_bounds__(256) png_unpack_kernel(const uint8_t* stream, bool bgr, ImgView dst, PaletteArg<png_is_palette(KIND)> pal)
 {
     constexpr uint32_t BITS = png_file_bits(KIND), D = png_image_bytes(KIND), G = WIDE ? wide_group<KIND>() : 1u;
     __shared__ uint32_t lds[png_is_palette(KIND) ? 256 : 1];
     const uint32_t* table = nullptr;
     if constexpr (png_is_palette(KIND))
     {
-        lds[threadIdx.x] = bgr ? png_exchange(pal.word[threadIdx.x]) : pal.word[threadIdx.x];          // the whole workgroup reaches the barrier
+        lds[threadIdx.x] = bgr ? swap_rb(pal.word[threadIdx.x]) : pal.word[threadIdx.x];          // the whole workgroup reaches the barrier
         __syncthreads();
         table = lds;
         bgr = false;
@@ -205,33 +157,22 @@ __global__ void __launch_bounds__(256) png_pack_kernel(ImgView src, uint8_t* str
     }
 }
 
-inline bool multiple_of(const void* p, uint64_t pitch, uint32_t bytes) { return ((reinterpret_cast<uintptr_t>(p) | pitch) & (bytes - 1u)) == 0; }
-
-// rgbe.hip's grid, over lanes of `group` texels
-inline dim3 png_grid(uint32_t width, uint32_t height, uint32_t group)
-{
-    const uint32_t gx = ((width + group - 1u) / group + 255u) / 256u;
-    return dim3(gx, std::min<uint32_t>(std::min<uint32_t>(height, 65535u), std::max<uint32_t>(1u, 8192u / gx)));
-}
-
-#define DXTEX_MARK(NAME) do { if (marks) marks->mark(NAME); } while (0)
-
 template<int KIND>
 hipError_t unpack_kind(const uint8_t* stream, uint32_t flags, const uint32_t* palette, const ImgView& dv, hipStream_t hs, KernelMarks* marks)
 {
     const bool bgr = (flags & PNG_BGR) != 0 && png_takes_bgr(KIND);
-    PaletteArg<KIND> pal;
+    PaletteArg<png_is_palette(KIND)> pal;
     if constexpr (png_is_palette(KIND)) std::copy(palette, palette + 256, pal.word);
     constexpr uint32_t G = wide_group<KIND>();
     if (dv.width % G == 0 && multiple_of(stream, 0, wide_stream_align<KIND>()) && multiple_of(dv.pixels, dv.rowPitch, wide_image_align<KIND>()))
     {
         DXTEX_MARK("png_unpack<wide>");
-        hipLaunchKernelGGL((png_unpack_kernel<KIND, true>), png_grid(dv.width, dv.height, G), dim3(256), 0, hs, stream, bgr, dv, pal);
+        hipLaunchKernelGGL((png_unpack_kernel<KIND, true>), stream_grid(dv.width, dv.height, G), dim3(256), 0, hs, stream, bgr, dv, pal);
     }
     else
     {
         DXTEX_MARK("png_unpack<narrow>");
-        hipLaunchKernelGGL((png_unpack_kernel<KIND, false>), png_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, stream, bgr, dv, pal);
+        hipLaunchKernelGGL((png_unpack_kernel<KIND, false>), stream_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, stream, bgr, dv, pal);
     }
     DXTEX_MARK(nullptr);
     return hipGetLastError();
@@ -244,12 +185,12 @@ hipError_t pack_source(const ImgView& sv, uint8_t* stream, hipStream_t hs, Kerne
     if (sv.width % 4u == 0 && multiple_of(stream, 0, span_align<F>()) && multiple_of(sv.pixels, sv.rowPitch, span_align<S>()))
     {
         DXTEX_MARK("png_pack<wide>");
-        hipLaunchKernelGGL((png_pack_kernel<SRC, true>), png_grid(sv.width, sv.height, 4u), dim3(256), 0, hs, sv, stream);
+        hipLaunchKernelGGL((png_pack_kernel<SRC, true>), stream_grid(sv.width, sv.height, 4u), dim3(256), 0, hs, sv, stream);
     }
     else
     {
         DXTEX_MARK("png_pack<narrow>");
-        hipLaunchKernelGGL((png_pack_kernel<SRC, false>), png_grid(sv.width, sv.height, 1u), dim3(256), 0, hs, sv, stream);
+        hipLaunchKernelGGL((png_pack_kernel<SRC, false>), stream_grid(sv.width, sv.height, 1u), dim3(256), 0, hs, sv, stream);
     }
     DXTEX_MARK(nullptr);
     return hipGetLastError();

@@ -6,9 +6,9 @@
 //   pnm_pack_kernel    level 0 of an image -> the file's rows, tight: alpha dropped, B and R exchanged for a BGR source, halves widened, a
 //                      float kind's rows bottom first
 //
-// 256 lanes, x across, rows strided over gridDim.y (rgbe.hip's grid). Two routes:
+// 256 lanes, x across, rows strided over gridDim.y (dxtex_stream.h's grid). Two routes:
 //   wide    a lane takes four texels: 4 * B bytes of the stream and 4 * D bytes of the image, each moved as the widest aligned accesses
-//           its dword count allows (span_align: a multiple of four dwords as dwordx4, of two as dwordx2, else single dwords). P6: three
+//           its dword count allows (dxtex_stream.h's span_align: a multiple of four dwords as dwordx4, of two as dwordx2, else single dwords). P6: three
 //           dwords in, one dwordx4 out. PF: three dwordx4 in, four out. PH: three dwordx2 in, two dwordx4 out.
 //           THE RULE: width is a multiple of 4, and the stream's base, the image's base and the image's row pitch are multiples of their
 //           side's span_align (stream: 4 for P6, 16 for PF and Pf, 8 for PH and Ph; image: 16, and 8 for Ph). A row of the stream is
@@ -25,72 +25,11 @@
 #include <hip/hip_runtime.h>
 #include "dxtex_kernels.h"
 #include "dxtex_pnm.h"
-#include <algorithm>
 
 namespace dxtex
 {
 namespace
 {
-// the alignment N consecutive dwords are moved with
-template<uint32_t N> constexpr uint32_t span_align() { return N % 4u == 0 ? 16u : N % 2u == 0 ? 8u : 4u; }
-
-template<uint32_t N>
-__device__ __forceinline__ void load_span(const uint8_t* s, uint32_t (&w)[N])
-{
-    if constexpr (N % 4u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 4u; ++i) { const uint4 v = reinterpret_cast<const uint4*>(s)[i]; w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w; }
-    }
-    else if constexpr (N % 2u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 2u; ++i) { const uint2 v = reinterpret_cast<const uint2*>(s)[i]; w[2 * i] = v.x; w[2 * i + 1] = v.y; }
-    }
-    else
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N; ++i) w[i] = reinterpret_cast<const uint32_t*>(s)[i];
-    }
-}
-
-template<uint32_t N>
-__device__ __forceinline__ void store_span(uint8_t* d, const uint32_t (&w)[N])
-{
-    if constexpr (N % 4u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 4u; ++i) reinterpret_cast<uint4*>(d)[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    }
-    else if constexpr (N % 2u == 0)
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N / 2u; ++i) reinterpret_cast<uint2*>(d)[i] = make_uint2(w[2 * i], w[2 * i + 1]);
-    }
-    else
-    {
-#pragma unroll
-        for (uint32_t i = 0; i < N; ++i) reinterpret_cast<uint32_t*>(d)[i] = w[i];
-    }
-}
-
-// one E-byte element: one access where the address is a multiple of E, bytes otherwise
-template<uint32_t E>
-__device__ __forceinline__ uint32_t load_element(const uint8_t* s, bool aligned)
-{
-    if (E == 1u || E == 3u || !aligned) return pnm_load(s, E);
-    if constexpr (E == 2u) return *reinterpret_cast<const uint16_t*>(s);
-    else return *reinterpret_cast<const uint32_t*>(s);
-}
-
-template<uint32_t E>
-__device__ __forceinline__ void store_element(uint8_t* d, uint32_t e, bool aligned)
-{
-    if (E == 1u || E == 3u || !aligned) { pnm_store(d, e, E); return; }
-    if constexpr (E == 2u) *reinterpret_cast<uint16_t*>(d) = uint16_t(e);
-    else *reinterpret_cast<uint32_t*>(d) = e;
-}
-
 // 16-bit element j of consecutive ones held as little-endian dwords
 template<uint32_t N>
 __device__ __forceinline__ uint32_t half_of(const uint32_t (&w)[N], uint32_t j) { return (w[j / 2u] >> (16u * (j & 1u))) & 0xFFFFu; }
@@ -101,7 +40,9 @@ __device__ __forceinline__ void unpack4(const uint32_t (&in)[pnm_file_bytes(KIND
 {
     if constexpr (KIND == PNM_P6)
     {
-        // texel k's three bytes start at bit 24 * k of the 96
+        // texel k's three bytes start at bit 24 * k of the 96. This is texel_of<3> written out without its 24-bit mask, which
+        // pnm_p6_texel does not need (it ignores the top byte): with the mask the kernel came out two instructions longer and, in one of
+        // two measurements, 3 to 5 % slower (profiles/stream_layer.md)
         out[0] = pnm_p6_texel(in[0], scale);
         out[1] = pnm_p6_texel((in[0] >> 24) | (in[1] << 8), scale);
         out[2] = pnm_p6_texel((in[1] >> 16) | (in[2] << 16), scale);
@@ -167,13 +108,13 @@ __global__ void __launch_bounds__(256) pnm_unpack_kernel(const uint8_t* stream, 
             unpack4<KIND>(in, out, bigEndian, scale);
             store_span<D>(d, out);
         }
-        else if constexpr (KIND == PNM_P6) store_element<4u>(d, pnm_p6_texel(pnm_load(s, 3u), scale), imageAligned);
+        else if constexpr (KIND == PNM_P6) store1<4u>(d, pnm_p6_texel(le_load32(s, 3u), scale), imageAligned);
         else
         {
             constexpr uint32_t n = pnm_file_elements(KIND);
 #pragma unroll
-            for (uint32_t c = 0; c < n; ++c) store_element<E>(d + c * E, pnm_element(load_element<E>(s + c * E, streamAligned), E, bigEndian), imageAligned);
-            if constexpr (n == 3u) store_element<E>(d + 3u * E, pnm_one(KIND), imageAligned);
+            for (uint32_t c = 0; c < n; ++c) store1<E>(d + c * E, pnm_element(load1<E>(s + c * E, streamAligned), E, bigEndian), imageAligned);
+            if constexpr (n == 3u) store1<E>(d + 3u * E, pnm_one(KIND), imageAligned);
         }
     }
 }
@@ -187,7 +128,7 @@ __device__ __forceinline__ void pack4(const uint32_t (&in)[pnm_source_bytes(SRC)
         uint32_t t[4];
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) t[k] = pnm_pack_p6(in[k], SRC == PNM_SRC_BGRA8);
-        out[0] = t[0] | (t[1] << 24); out[1] = (t[1] >> 8) | (t[2] << 16); out[2] = (t[2] >> 16) | (t[3] << 8);
+        pack3x4(t, out);
     }
     else if constexpr (SRC == PNM_SRC_RGBA32F)
     {
@@ -228,30 +169,19 @@ __global__ void __launch_bounds__(256) pnm_pack_kernel(ImgView src, uint8_t* str
             pack4<SRC>(in, out);
             store_span<B>(d, out);
         }
-        else if constexpr (KIND == PNM_P6) pnm_store(d, pnm_pack_p6(load_element<4u>(s, imageAligned), SRC == PNM_SRC_BGRA8), 3u);
+        else if constexpr (KIND == PNM_P6) le_store32(d, pnm_pack_p6(load1<4u>(s, imageAligned), SRC == PNM_SRC_BGRA8), 3u);
         else if constexpr (SRC == PNM_SRC_RGBA16F)
         {
 #pragma unroll
-            for (uint32_t c = 0; c < 3u; ++c) store_element<4u>(d + 4u * c, pnm_half_to_float_bits(load_element<2u>(s + 2u * c, imageAligned)), streamAligned);
+            for (uint32_t c = 0; c < 3u; ++c) store1<4u>(d + 4u * c, pnm_half_to_float_bits(load1<2u>(s + 2u * c, imageAligned)), streamAligned);
         }
         else
         {
 #pragma unroll
-            for (uint32_t c = 0; c < B / 4u; ++c) store_element<4u>(d + 4u * c, load_element<4u>(s + 4u * c, imageAligned), streamAligned);
+            for (uint32_t c = 0; c < B / 4u; ++c) store1<4u>(d + 4u * c, load1<4u>(s + 4u * c, imageAligned), streamAligned);
         }
     }
 }
-
-inline bool multiple_of(const void* p, uint64_t pitch, uint32_t bytes) { return ((reinterpret_cast<uintptr_t>(p) | pitch) & (bytes - 1u)) == 0; }
-
-// rgbe.hip's grid, over lanes of `group` texels
-inline dim3 pnm_grid(uint32_t width, uint32_t height, uint32_t group)
-{
-    const uint32_t gx = ((width + group - 1u) / group + 255u) / 256u;
-    return dim3(gx, std::min<uint32_t>(std::min<uint32_t>(height, 65535u), std::max<uint32_t>(1u, 8192u / gx)));
-}
-
-#define DXTEX_MARK(NAME) do { if (marks) marks->mark(NAME); } while (0)
 
 template<int KIND>
 hipError_t unpack_kind(const uint8_t* stream, uint32_t maxval, uint32_t flags, const ImgView& dv, hipStream_t hs, KernelMarks* marks)
@@ -261,12 +191,12 @@ hipError_t unpack_kind(const uint8_t* stream, uint32_t maxval, uint32_t flags, c
     if (dv.width % 4u == 0 && multiple_of(stream, 0, span_align<B>()) && multiple_of(dv.pixels, dv.rowPitch, span_align<D>()))
     {
         DXTEX_MARK("pnm_unpack<wide>");
-        hipLaunchKernelGGL((pnm_unpack_kernel<KIND, true>), pnm_grid(dv.width, dv.height, 4u), dim3(256), 0, hs, stream, maxval, bigEndian, dv, true, true);
+        hipLaunchKernelGGL((pnm_unpack_kernel<KIND, true>), stream_grid(dv.width, dv.height, 4u), dim3(256), 0, hs, stream, maxval, bigEndian, dv, true, true);
     }
     else
     {
         DXTEX_MARK("pnm_unpack<narrow>");
-        hipLaunchKernelGGL((pnm_unpack_kernel<KIND, false>), pnm_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, stream, maxval, bigEndian, dv,
+        hipLaunchKernelGGL((pnm_unpack_kernel<KIND, false>), stream_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, stream, maxval, bigEndian, dv,
                            multiple_of(stream, 0, E), multiple_of(dv.pixels, dv.rowPitch, KIND == PNM_P6 ? 4u : E));
     }
     DXTEX_MARK(nullptr);
@@ -280,12 +210,12 @@ hipError_t pack_source(const ImgView& sv, uint8_t* stream, hipStream_t hs, Kerne
     if (sv.width % 4u == 0 && multiple_of(stream, 0, span_align<B>()) && multiple_of(sv.pixels, sv.rowPitch, span_align<S>()))
     {
         DXTEX_MARK("pnm_pack<wide>");
-        hipLaunchKernelGGL((pnm_pack_kernel<SRC, true>), pnm_grid(sv.width, sv.height, 4u), dim3(256), 0, hs, sv, stream, true, true);
+        hipLaunchKernelGGL((pnm_pack_kernel<SRC, true>), stream_grid(sv.width, sv.height, 4u), dim3(256), 0, hs, sv, stream, true, true);
     }
     else
     {
         DXTEX_MARK("pnm_pack<narrow>");
-        hipLaunchKernelGGL((pnm_pack_kernel<SRC, false>), pnm_grid(sv.width, sv.height, 1u), dim3(256), 0, hs, sv, stream,
+        hipLaunchKernelGGL((pnm_pack_kernel<SRC, false>), stream_grid(sv.width, sv.height, 1u), dim3(256), 0, hs, sv, stream,
                            multiple_of(sv.pixels, sv.rowPitch, SRC == PNM_SRC_RGBA16F ? 2u : 4u), multiple_of(stream, 0, 4u));
     }
     DXTEX_MARK(nullptr);

@@ -4,7 +4,7 @@
 //   rgbe_encode_kernel  R32G32B32A32_FLOAT, R32G32B32_FLOAT or R16G16B16A16_FLOAT rows -> RGBE rows
 //
 // Pure streaming: no LDS, no atomics, no cross-lane work. One texel per lane, x = blockIdx.x * 256 + threadIdx.x, rows strided over
-// gridDim.y (launch_rotate_color's grid). Two routes, by the alignment of the float side:
+// gridDim.y (dxtex_stream.h's grid). Two routes, by the alignment of the float side:
 //   wide    its base and row pitch are multiples of the texel (16 bytes; 8 for halves): one dwordx4 (dwordx2) access per texel, lane i at
 //           base + 16 * i, 1 KiB per wave instruction
 //   narrow  one access per channel (dwords; 16-bit loads for halves). R32G32B32_FLOAT always goes here. Alpha is not read.
@@ -15,24 +15,11 @@
 #include <hip/hip_runtime.h>
 #include "dxtex_kernels.h"
 #include "dxtex_rgbe.h"
-#include <algorithm>
 
 namespace dxtex
 {
 namespace
 {
-__device__ __forceinline__ uint32_t load_rgbe(const uint8_t* p, bool dwords)
-{
-    if (dwords) return *reinterpret_cast<const uint32_t*>(p);
-    return uint32_t(p[0]) | (uint32_t(p[1]) << 8) | (uint32_t(p[2]) << 16) | (uint32_t(p[3]) << 24);
-}
-
-__device__ __forceinline__ void store_rgbe(uint8_t* p, uint32_t v, bool dwords)
-{
-    if (dwords) { *reinterpret_cast<uint32_t*>(p) = v; return; }
-    p[0] = uint8_t(v); p[1] = uint8_t(v >> 8); p[2] = uint8_t(v >> 16); p[3] = uint8_t(v >> 24);
-}
-
 template<bool WIDE>
 __global__ void __launch_bounds__(256) rgbe_decode_kernel(ImgView src, ImgView dst, float scale, bool dwords)
 {
@@ -40,7 +27,7 @@ __global__ void __launch_bounds__(256) rgbe_decode_kernel(ImgView src, ImgView d
     if (x >= src.width) return;
     for (uint32_t y = blockIdx.y; y < src.height; y += gridDim.y)
     {
-        const uint32_t v = load_rgbe(src.pixels + uint64_t(y) * src.rowPitch + uint64_t(x) * 4u, dwords);
+        const uint32_t v = load1<4u>(src.pixels + uint64_t(y) * src.rowPitch + uint64_t(x) * 4u, dwords);
         const uint8_t in[4] = { uint8_t(v), uint8_t(v >> 8), uint8_t(v >> 16), uint8_t(v >> 24) };
         float out[4];
         rgbe_decode(in, scale, out);
@@ -87,30 +74,19 @@ __global__ void __launch_bounds__(256) rgbe_encode_kernel(ImgView src, ImgView d
         }
         uint8_t out[4];
         rgbe_encode(r, g, b, out);
-        store_rgbe(dst.pixels + uint64_t(y) * dst.rowPitch + uint64_t(x) * 4u,
+        store1<4u>(dst.pixels + uint64_t(y) * dst.rowPitch + uint64_t(x) * 4u,
                    uint32_t(out[0]) | (uint32_t(out[1]) << 8) | (uint32_t(out[2]) << 16) | (uint32_t(out[3]) << 24), dwords);
     }
 }
-
-inline bool aligned_to(const ImgView& v, uint32_t bytes) { return ((reinterpret_cast<uintptr_t>(v.pixels) | v.rowPitch) & (bytes - 1u)) == 0; }
-
-// launch_rotate_color's grid: about 8192 workgroups, enough to fill 256 CUs several times over, few enough that a lane streams several rows
-inline dim3 rgbe_grid(uint32_t width, uint32_t height)
-{
-    const uint32_t gx = (width + 255u) / 256u;
-    return dim3(gx, std::min<uint32_t>(std::min<uint32_t>(height, 65535u), std::max<uint32_t>(1u, 8192u / gx)));
-}
 } // namespace
-
-#define DXTEX_MARK(NAME) do { if (marks) marks->mark(NAME); } while (0)
 
 hipError_t launch_rgbe_decode(const ImgView& sv, const ImgView& dv, float scale, hipStream_t stream, KernelMarks* marks)
 {
     if (!sv.width || !sv.height) return hipSuccess;
     if (sv.format != FMT_R8G8B8A8_UINT || dv.format != FMT_R32G32B32A32_FLOAT || sv.width != dv.width || sv.height != dv.height) return hipErrorInvalidValue;
-    const dim3 grid = rgbe_grid(sv.width, sv.height);
-    const bool dwords = aligned_to(sv, 4u);
-    if (aligned_to(dv, 16u))
+    const dim3 grid = stream_grid(sv.width, sv.height, 1u);
+    const bool dwords = multiple_of(sv.pixels, sv.rowPitch, 4u);
+    if (multiple_of(dv.pixels, dv.rowPitch, 16u))
     {
         DXTEX_MARK("rgbe_decode<wide>");
         hipLaunchKernelGGL((rgbe_decode_kernel<true>), grid, dim3(256), 0, stream, sv, dv, scale, dwords);
@@ -128,14 +104,14 @@ hipError_t launch_rgbe_encode(const ImgView& sv, const ImgView& dv, hipStream_t 
 {
     if (!sv.width || !sv.height) return hipSuccess;
     if (dv.format != FMT_R8G8B8A8_UINT || sv.width != dv.width || sv.height != dv.height) return hipErrorInvalidValue;
-    const dim3 grid = rgbe_grid(sv.width, sv.height);
-    const bool dwords = aligned_to(dv, 4u);
+    const dim3 grid = stream_grid(sv.width, sv.height, 1u);
+    const bool dwords = multiple_of(dv.pixels, dv.rowPitch, 4u);
 #define DXTEX_RGBE_ENCODE(FORMAT, WIDE) do { DXTEX_MARK((WIDE) ? "rgbe_encode<wide>" : "rgbe_encode<narrow>"); \
         hipLaunchKernelGGL((rgbe_encode_kernel<FORMAT, WIDE>), grid, dim3(256), 0, stream, sv, dv, dwords); } while (0)
     switch (sv.format)
     {
-    case FMT_R32G32B32A32_FLOAT: if (aligned_to(sv, 16u)) DXTEX_RGBE_ENCODE(FMT_R32G32B32A32_FLOAT, true); else DXTEX_RGBE_ENCODE(FMT_R32G32B32A32_FLOAT, false); break;
-    case FMT_R16G16B16A16_FLOAT: if (aligned_to(sv, 8u)) DXTEX_RGBE_ENCODE(FMT_R16G16B16A16_FLOAT, true); else DXTEX_RGBE_ENCODE(FMT_R16G16B16A16_FLOAT, false); break;
+    case FMT_R32G32B32A32_FLOAT: if (multiple_of(sv.pixels, sv.rowPitch, 16u)) DXTEX_RGBE_ENCODE(FMT_R32G32B32A32_FLOAT, true); else DXTEX_RGBE_ENCODE(FMT_R32G32B32A32_FLOAT, false); break;
+    case FMT_R16G16B16A16_FLOAT: if (multiple_of(sv.pixels, sv.rowPitch, 8u)) DXTEX_RGBE_ENCODE(FMT_R16G16B16A16_FLOAT, true); else DXTEX_RGBE_ENCODE(FMT_R16G16B16A16_FLOAT, false); break;
     case FMT_R32G32B32_FLOAT: DXTEX_RGBE_ENCODE(FMT_R32G32B32_FLOAT, false); break;
     default: return hipErrorInvalidValue;
     }

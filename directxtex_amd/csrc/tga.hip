@@ -7,7 +7,7 @@
 //                      where every alpha is zero and that is not allowed, sets them. Every other wave returns after two scalar loads.
 //   tga_pack_kernel    level 0 of an image -> the file's rows: top-down, tight, B bytes a texel
 //
-// 256 lanes, x across, rows strided over gridDim.y (rgbe.hip's grid). Two routes:
+// 256 lanes, x across, rows strided over gridDim.y (dxtex_stream.h's grid). Two routes:
 //   wide    a lane takes four texels and every access is a naturally aligned dword or wider: 4 * B bytes of the stream as B dwords, 4 * D
 //           bytes of the image as one dword (D = 1), dwordx2 (D = 2) or dwordx4 (D = 4). Three-byte texels: three dwords in, one dwordx4
 //           out. Under TGA_RIGHT_TO_LEFT the four are reversed and the store address mirrored.
@@ -26,25 +26,11 @@
 #include "dxtex_kernels.h"
 #include "dxtex_tga.h"
 #include <algorithm>
-#include <type_traits>
 
 namespace dxtex
 {
 namespace
 {
-struct TgaPalette { uint32_t word[256]; };
-struct TgaNoPalette {};
-
-// texel k of four consecutive B-byte texels held as B little-endian dwords
-template<uint32_t B>
-__device__ __forceinline__ uint32_t texel_of(const uint32_t (&w)[B], uint32_t k)
-{
-    const uint32_t bit = k * 8u * B, i = bit / 32u, shift = bit % 32u;
-    uint32_t t = w[i] >> shift;
-    if (shift + 8u * B > 32u) t |= w[i + 1] << (32u - shift);
-    return B == 4u ? t : t & ((1u << (8u * (B & 3u))) - 1u);
-}
-
 // four D-byte words as one aligned access
 template<uint32_t D>
 __device__ __forceinline__ void store4(uint8_t* d, const uint32_t (&t)[4])
@@ -62,42 +48,19 @@ __device__ __forceinline__ void load4(const uint8_t* s, uint32_t (&t)[4])
     else { const uint4 v = *reinterpret_cast<const uint4*>(s); t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w; }
 }
 
-// one D-byte word: one access where the address is a multiple of D, bytes otherwise
-template<uint32_t D>
-__device__ __forceinline__ void store1(uint8_t* d, uint32_t t, bool aligned)
-{
-    if (D == 1u || !aligned) { tga_store(d, t, D); return; }
-    if constexpr (D == 2u) *reinterpret_cast<uint16_t*>(d) = uint16_t(t);
-    else *reinterpret_cast<uint32_t*>(d) = t;
-}
-
-template<uint32_t D>
-__device__ __forceinline__ uint32_t load1(const uint8_t* s, bool aligned)
-{
-    if (D == 1u || !aligned) return tga_load(s, D);
-    if constexpr (D == 2u) return *reinterpret_cast<const uint16_t*>(s);
-    else return *reinterpret_cast<const uint32_t*>(s);
-}
-
 __device__ __forceinline__ uint32_t wave_or(uint32_t v)          // gfx950: 64 lanes
 {
     for (int off = 32; off > 0; off >>= 1) v |= __shfl_xor(v, off);
     return v;
 }
 
-template<int KIND> using PaletteArg = std::conditional_t<KIND == TGA_PALETTE, TgaPalette, TgaNoPalette>;
-
 // dstAligned (narrow only): dst's base and pitch are multiples of its texel
 template<int KIND, bool WIDE>
-__global__ void __launch_bounds__(256) tga_unpack_kernel(const uint8_t* stream, uint32_t flags, ImgView dst, bool dstAligned, uint32_t* alphaWord, PaletteArg<KIND> pal)
+__global__ void __launch_bounds__(256) tga_unpack_kernel(const uint8_t* stream, uint32_t flags, ImgView dst, bool dstAligned, uint32_t* alphaWord, PaletteArg<KIND == TGA_PALETTE> pal)
 {
     constexpr uint32_t B = tga_file_bytes(KIND), D = tga_image_bytes(KIND), G = WIDE ? 4u : 1u;
     __shared__ uint32_t table[KIND == TGA_PALETTE ? 256 : 1];
-    if constexpr (KIND == TGA_PALETTE)
-    {
-        table[threadIdx.x] = pal.word[threadIdx.x];
-        __syncthreads();
-    }
+    if constexpr (KIND == TGA_PALETTE) palette_to_lds(table, pal);
     const uint32_t x = (blockIdx.x * 256u + threadIdx.x) * G;
     const bool rightToLeft = (flags & TGA_RIGHT_TO_LEFT) != 0, topDown = (flags & TGA_TOP_DOWN) != 0;
     uint32_t orAlpha = 0, orNotAlpha = 0;
@@ -112,8 +75,7 @@ __global__ void __launch_bounds__(256) tga_unpack_kernel(const uint8_t* stream, 
             if constexpr (WIDE)
             {
                 uint32_t w[B], t[4];
-#pragma unroll
-                for (uint32_t i = 0; i < B; ++i) w[i] = reinterpret_cast<const uint32_t*>(s)[i];
+                load_span<B, 4u>(s, w);
 #pragma unroll
                 for (uint32_t k = 0; k < 4u; ++k)
                 {
@@ -125,7 +87,7 @@ __global__ void __launch_bounds__(256) tga_unpack_kernel(const uint8_t* stream, 
             }
             else
             {
-                store1<D>(d, tga_unpack_texel(tga_load(s, B), KIND, table, alpha), dstAligned);
+                store1<D>(d, tga_unpack_texel(le_load32(s, B), KIND, table, alpha), dstAligned);
                 orAlpha |= alpha; orNotAlpha |= alpha ^ 255u;
             }
         }
@@ -185,38 +147,23 @@ __global__ void __launch_bounds__(256) tga_pack_kernel(ImgView src, uint8_t* str
             load4<D>(s, t);
 #pragma unroll
             for (uint32_t k = 0; k < 4u; ++k) t[k] = tga_pack_texel(t[k], ROW);
-            uint32_t* out = reinterpret_cast<uint32_t*>(d);
             if constexpr (B == 3u)
             {
-                out[0] = t[0] | (t[1] << 24); out[1] = (t[1] >> 8) | (t[2] << 16); out[2] = (t[2] >> 16) | (t[3] << 8);
+                uint32_t out[3];
+                pack3x4(t, out);
+                store_span<3u>(d, out);
             }
             else store4<B>(d, t);
         }
-        else
-        {
-            const uint32_t t = tga_pack_texel(load1<D>(s, srcAligned), ROW);
-            if constexpr (B == 3u) tga_store(d, t, 3u);
-            else store1<B>(d, t, dstAligned);
-        }
+        else store1<B>(d, tga_pack_texel(load1<D>(s, srcAligned), ROW), dstAligned);
     }
 }
-
-inline bool multiple_of(const void* p, uint64_t pitch, uint32_t bytes) { return ((reinterpret_cast<uintptr_t>(p) | pitch) & (bytes - 1u)) == 0; }
-
-// rgbe.hip's grid, over lanes of `group` texels
-inline dim3 tga_grid(uint32_t width, uint32_t height, uint32_t group)
-{
-    const uint32_t gx = ((width + group - 1u) / group + 255u) / 256u;
-    return dim3(gx, std::min<uint32_t>(std::min<uint32_t>(height, 65535u), std::max<uint32_t>(1u, 8192u / gx)));
-}
-
-#define DXTEX_MARK(NAME) do { if (marks) marks->mark(NAME); } while (0)
 
 template<int KIND>
 hipError_t unpack_kind(const uint8_t* stream, uint32_t flags, const uint32_t* palette, const ImgView& dv, uint32_t* alphaWord, uint32_t* answer, hipStream_t hs, KernelMarks* marks)
 {
     constexpr uint32_t D = tga_image_bytes(KIND);
-    PaletteArg<KIND> pal;
+    PaletteArg<KIND == TGA_PALETTE> pal;
     if constexpr (KIND == TGA_PALETTE) std::copy(palette, palette + 256, pal.word);
     if constexpr (tga_has_alpha_rule(KIND))
     {
@@ -227,17 +174,17 @@ hipError_t unpack_kind(const uint8_t* stream, uint32_t flags, const uint32_t* pa
     if (dv.width % 4u == 0 && multiple_of(stream, 0, 4u) && multiple_of(dv.pixels, dv.rowPitch, 4u * D))
     {
         DXTEX_MARK("tga_unpack<wide>");
-        hipLaunchKernelGGL((tga_unpack_kernel<KIND, true>), tga_grid(dv.width, dv.height, 4u), dim3(256), 0, hs, stream, orient, dv, true, alphaWord, pal);
+        hipLaunchKernelGGL((tga_unpack_kernel<KIND, true>), stream_grid(dv.width, dv.height, 4u), dim3(256), 0, hs, stream, orient, dv, true, alphaWord, pal);
     }
     else
     {
         DXTEX_MARK("tga_unpack<narrow>");
-        hipLaunchKernelGGL((tga_unpack_kernel<KIND, false>), tga_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, stream, orient, dv, multiple_of(dv.pixels, dv.rowPitch, D), alphaWord, pal);
+        hipLaunchKernelGGL((tga_unpack_kernel<KIND, false>), stream_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, stream, orient, dv, multiple_of(dv.pixels, dv.rowPitch, D), alphaWord, pal);
     }
     if constexpr (tga_has_alpha_rule(KIND))
     {
         DXTEX_MARK("tga_opaque");
-        hipLaunchKernelGGL((tga_opaque_kernel<D>), tga_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, dv, alphaWord, (flags & TGA_ALLOW_ALL_ZERO_ALPHA) != 0, answer);
+        hipLaunchKernelGGL((tga_opaque_kernel<D>), stream_grid(dv.width, dv.height, 1u), dim3(256), 0, hs, dv, alphaWord, (flags & TGA_ALLOW_ALL_ZERO_ALPHA) != 0, answer);
     }
     DXTEX_MARK(nullptr);
     return hipGetLastError();
@@ -250,12 +197,12 @@ hipError_t pack_row(const ImgView& sv, uint8_t* stream, hipStream_t hs, KernelMa
     if (sv.width % 4u == 0 && multiple_of(stream, 0, 4u) && multiple_of(sv.pixels, sv.rowPitch, 4u * D))
     {
         DXTEX_MARK("tga_pack<wide>");
-        hipLaunchKernelGGL((tga_pack_kernel<ROW, B, true>), tga_grid(sv.width, sv.height, 4u), dim3(256), 0, hs, sv, stream, true, true);
+        hipLaunchKernelGGL((tga_pack_kernel<ROW, B, true>), stream_grid(sv.width, sv.height, 4u), dim3(256), 0, hs, sv, stream, true, true);
     }
     else
     {
         DXTEX_MARK("tga_pack<narrow>");
-        hipLaunchKernelGGL((tga_pack_kernel<ROW, B, false>), tga_grid(sv.width, sv.height, 1u), dim3(256), 0, hs, sv, stream, multiple_of(sv.pixels, sv.rowPitch, D), multiple_of(stream, 0, B == 3u ? 1u : B));
+        hipLaunchKernelGGL((tga_pack_kernel<ROW, B, false>), stream_grid(sv.width, sv.height, 1u), dim3(256), 0, hs, sv, stream, multiple_of(sv.pixels, sv.rowPitch, D), multiple_of(stream, 0, B == 3u ? 1u : B));
     }
     DXTEX_MARK(nullptr);
     return hipGetLastError();

@@ -5,8 +5,7 @@
 // choice (:711-1033). The payload is the ScratchImage order (item-major, mips inside; volumes level by level).
 // All of this is host code: it is the container either side of the GPU path, and tests/test_dds_cpu.py compares it with the
 // reference's own reader and writer (oracle/_ref) file by file.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 #include "../csrc/dxtex_dds.h"
 
 #include <algorithm>
@@ -335,7 +334,7 @@ namespace
         for (size_t i = 0; i + T <= n; i += T)
         {
             std::memcpy(d + i, s + i, T - W);
-            dxtex::dds_store(d + i + T - W, dxtex::dds_opaque_word(dxtex::dds_load(s + i + T - W, uint32_t(W)), o), uint32_t(W));
+            dxtex::le_store64(d + i + T - W, dxtex::dds_opaque_word(dxtex::le_load32(s + i + T - W, uint32_t(W)), o), uint32_t(W));
         }
     }
 
@@ -355,7 +354,7 @@ namespace
         // SwizzleScanline stops at the shorter row; the expansions at whichever side runs out of whole texels first
         const size_t texels = op == ROW_SWIZZLE ? std::min(dn, sn) / 4 : std::min(sn / B, dn / D);
         for (size_t x = 0; x < texels; ++x)
-            dxtex::dds_store(d + x * D, dxtex::dds_unpack_texel(dxtex::dds_load(s + x * B, uint32_t(B)), op, target, opaque, pal8), uint32_t(D));
+            dxtex::le_store64(d + x * D, dxtex::dds_unpack_texel(dxtex::le_load32(s + x * B, uint32_t(B)), op, target, opaque, pal8), uint32_t(D));
         return true;
     }
 
@@ -489,30 +488,6 @@ namespace
         raw.payload = bytes + offset;
         return LayoutPayload(remaining, m, cp, conv, layout.get(), nimages, raw.images, raw.payloadBytes, raw.direct);
     }
-
-    HRESULT ReadWholeFile(const char* szFile, Blob& buf) noexcept
-    {
-        FILE* f = std::fopen(szFile, "rb");
-        if (!f) return E_FAIL;
-        std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-        if (n < 0) { std::fclose(f); return E_FAIL; }
-        if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
-        if (size_t(n) < kMinHeader) { std::fclose(f); return E_FAIL; }               // the file readers say E_FAIL here (DirectXTexDDS.cpp:1975-1978, :2178-2181)
-        if (FAILED(buf.Initialize(size_t(n)))) { std::fclose(f); return E_OUTOFMEMORY; }
-        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
-        std::fclose(f);
-        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
-    }
-
-    struct DeviceTemp
-    {
-        Device& device;
-        void* p = nullptr;
-        explicit DeviceTemp(Device& d) noexcept : device(d) {}
-        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }          // waits for the work that still uses it
-        DeviceTemp(const DeviceTemp&) = delete;
-        DeviceTemp& operator=(const DeviceTemp&) = delete;
-    };
 }
 
 HRESULT Blob::Initialize(size_t size) noexcept
@@ -582,7 +557,7 @@ HRESULT LoadFromDDSFileRaw(const char* szFile, DDS_FLAGS flags, DDSMetaData* ddP
     raw.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    HRESULT hr = ReadWholeFile(szFile, file);
+    HRESULT hr = ReadAll(szFile, file, kMinHeader);          // the file readers say E_FAIL for a shorter one (DirectXTexDDS.cpp:1975-1978, :2178-2181)
     if (FAILED(hr)) return hr;
     hr = LoadFromDDSMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, ddPixelFormat, raw);
     if (SUCCEEDED(hr)) raw.storage.Swap(file);          // raw.payload points into it
@@ -615,7 +590,7 @@ HRESULT LoadFromDDSFileEx(const char* szFile, DDS_FLAGS flags, TexMetadata* meta
     if (!szFile) return E_INVALIDARG;
     image.Release();
     Blob buf;
-    const HRESULT hr = ReadWholeFile(szFile, buf);
+    const HRESULT hr = ReadAll(szFile, buf, kMinHeader);
     if (FAILED(hr)) return hr;
     return LoadFromDDSMemoryEx(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, ddPixelFormat, image);
 }
@@ -695,7 +670,7 @@ HRESULT LoadFromDDSFileEx(Device& device, const char* szFile, DDS_FLAGS flags, T
     image.Release();
     if (!szFile) return E_INVALIDARG;
     Blob buf;
-    const HRESULT hr = ReadWholeFile(szFile, buf);
+    const HRESULT hr = ReadAll(szFile, buf, kMinHeader);
     if (FAILED(hr)) return hr;
     return LoadFromDDSMemoryEx(device, buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, ddPixelFormat, image);
 }
@@ -952,7 +927,7 @@ HRESULT SaveDDS(Device* device, const Image* images, size_t nimages, const TexMe
             {
                 const uint8_t* s = im.pixels + y * im.rowPitch;
                 uint8_t* o = d + y * rp[i];
-                for (size_t x = 0; x < im.width; ++x, s += 4, o += 3) dxtex::dds_store(o, dxtex::dds_pack24_texel(dxtex::dds_load(s, 4)), 3);
+                for (size_t x = 0; x < im.width; ++x, s += 4, o += 3) dxtex::le_store64(o, dxtex::dds_pack24_texel(dxtex::le_load32(s, 4)), 3);
             }
         }
         else if (same) std::memcpy(d, im.pixels, sp[i]);
@@ -969,16 +944,6 @@ HRESULT SaveDDS(Device* device, const Image* images, size_t nimages, const TexMe
         hr = dxtex_ctx_synchronize(device->Get());          // the blob is complete when this returns
         if (FAILED(hr)) { blob.Release(); return hr; }
     }
-    return S_OK;
-}
-
-HRESULT WriteBlobToFile(const Blob& blob, const char* szFile) noexcept
-{
-    FILE* f = std::fopen(szFile, "wb");
-    if (!f) return E_FAIL;
-    const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
-    const bool closed = std::fclose(f) == 0;
-    if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }         // no partial files left behind
     return S_OK;
 }
 
@@ -1008,7 +973,7 @@ HRESULT SaveToDDSFile(const Image* images, size_t nimages, const TexMetadata& me
     Blob blob;
     const HRESULT hr = SaveToDDSMemory(images, nimages, metadata, flags, blob);
     if (FAILED(hr)) return hr;
-    return WriteBlobToFile(blob, szFile);
+    return WriteBlob(blob, szFile);
 }
 
 HRESULT SaveToDDSFile(const Image& image, DDS_FLAGS flags, const char* szFile) noexcept
@@ -1033,7 +998,7 @@ HRESULT SaveToDDSFile(Device& device, const Image* deviceImages, size_t nimages,
     Blob blob;
     const HRESULT hr = SaveToDDSMemory(device, deviceImages, nimages, metadata, flags, blob);
     if (FAILED(hr)) return hr;
-    return WriteBlobToFile(blob, szFile);
+    return WriteBlob(blob, szFile);
 }
 
 HRESULT SaveToDDSFile(Device& device, const Image& deviceImage, DDS_FLAGS flags, const char* szFile) noexcept

@@ -6,8 +6,7 @@
 // either side of the GPU path. The per-texel arithmetic is dxtex_rgbe.h's, which the GPU kernels share: the host codec runs it here, the
 // resident forms at the end of this file run it on the device, so that a file's texels cross PCIe as the 4 bytes they are. Both forms
 // share the header parser and the run-length coders below.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 #include "../csrc/dxtex_rgbe.h"
 
 #include <algorithm>
@@ -17,7 +16,6 @@
 #include <cstring>
 #include <memory>
 #include <new>
-#include <vector>
 
 namespace DirectXTexAMD
 {
@@ -168,20 +166,6 @@ namespace
         }
         return used;
     }
-
-    HRESULT ReadAll(const char* szFile, std::vector<uint8_t>& buf, size_t minimum) noexcept
-    {
-        FILE* f = std::fopen(szFile, "rb");
-        if (!f) return E_FAIL;
-        std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-        if (n < 0) { std::fclose(f); return E_FAIL; }
-        if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
-        if (size_t(n) < minimum) { std::fclose(f); return E_FAIL; }
-        try { buf.resize(size_t(n)); } catch (...) { std::fclose(f); return E_OUTOFMEMORY; }
-        const size_t got = buf.empty() ? 0 : std::fread(buf.data(), 1, buf.size(), f);
-        std::fclose(f);
-        return got == buf.size() ? S_OK : E_FAIL;
-    }
 }
 
 HRESULT Blob::Trim(size_t size) noexcept
@@ -326,10 +310,10 @@ HRESULT LoadFromHDRFile(const char* szFile, TexMetadata* metadata, ScratchImage&
 {
     if (!szFile) return E_INVALIDARG;
     image.Release();
-    std::vector<uint8_t> buf;
+    Blob buf;
     const HRESULT hr = ReadAll(szFile, buf, sizeof(kSignature));
     if (FAILED(hr)) return hr;
-    return LoadFromHDRMemory(buf.data(), buf.size(), metadata, image);
+    return LoadFromHDRMemory(buf.GetBufferPointer(), buf.GetBufferSize(), metadata, image);
 }
 
 namespace
@@ -375,16 +359,6 @@ namespace
         if (FAILED(hr)) blob.Release();
         return hr;
     }
-
-    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
-    {
-        FILE* f = std::fopen(szFile, "wb");
-        if (!f) return E_FAIL;
-        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
-        const bool closed = std::fclose(f) == 0;
-        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
-        return S_OK;
-    }
 }
 
 // SaveToHDRMemory (DirectXTexHDR.cpp:1001-1110): RGBA32F, RGB32F or RGBA16F in, run-length encoded RGBE out
@@ -422,27 +396,14 @@ HRESULT SaveToHDRFile(const Image& image, const char* szFile) noexcept
 }
 
 // ---- resident forms: the texels travel as RGBE, the float pass runs on the device (dxtex_rgbe_decode_device / dxtex_rgbe_encode_device) ----
-namespace
-{
-    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
-    struct DeviceTemp
-    {
-        Device& device; void* p = nullptr;
-        explicit DeviceTemp(Device& d) noexcept : device(d) {}
-        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
-        DeviceTemp(const DeviceTemp&) = delete;
-        DeviceTemp& operator=(const DeviceTemp&) = delete;
-    };
-}
-
 HRESULT LoadFromHDRFileRGBE(const char* szFile, TexMetadata* metadata, float& exposure, Blob& rgbe) noexcept
 {
     if (!szFile) return E_INVALIDARG;
     rgbe.Release();
-    std::vector<uint8_t> buf;
+    Blob buf;
     const HRESULT hr = ReadAll(szFile, buf, sizeof(kSignature));
     if (FAILED(hr)) return hr;
-    return LoadFromHDRMemoryRGBE(buf.data(), buf.size(), metadata, exposure, rgbe);
+    return LoadFromHDRMemoryRGBE(buf.GetBufferPointer(), buf.GetBufferSize(), metadata, exposure, rgbe);
 }
 
 HRESULT UploadHDRRows(Device& device, const TexMetadata& metadata, float exposure, const Blob& rgbe, DeviceScratchImage& image) noexcept
@@ -486,10 +447,10 @@ HRESULT LoadFromHDRFile(Device& device, const char* szFile, TexMetadata* metadat
 {
     image.Release();
     if (!szFile) return E_INVALIDARG;
-    std::vector<uint8_t> buf;
+    Blob buf;
     const HRESULT hr = ReadAll(szFile, buf, sizeof(kSignature));
     if (FAILED(hr)) return hr;
-    return LoadFromHDRMemory(device, buf.data(), buf.size(), metadata, image);
+    return LoadFromHDRMemory(device, buf.GetBufferPointer(), buf.GetBufferSize(), metadata, image);
 }
 
 HRESULT SaveToHDRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept

@@ -6,8 +6,7 @@
 // the host loader runs it here, the resident forms at the end of this file run it on the device, so that a file's rows cross PCIe as the
 // bytes they are. The writer is split the same way around its rows.
 // Unfiltering stays on the host: Average and Paeth chain every byte to its left neighbour and to the row above, which is one serial walk.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 #include "../csrc/dxtex_png.h"
 
 #include <algorithm>
@@ -424,7 +423,8 @@ namespace
         }
     }
 
-    HRESULT ReadAll(const char* szFile, Blob& buf) noexcept
+    // this codec's own reader, not DirectXTexAMD_Internal.h's ReadAll: a missing file is ERROR_FILE_NOT_FOUND here and no size is too large
+    HRESULT ReadPNGFile(const char* szFile, Blob& buf) noexcept
     {
         FILE* f = std::fopen(szFile, "rb");
         if (!f) return errno == ENOENT ? HRESULT_ERROR_FILE_NOT_FOUND : E_FAIL;
@@ -435,16 +435,6 @@ namespace
         const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
         std::fclose(f);
         return got == buf.GetBufferSize() ? S_OK : E_FAIL;
-    }
-
-    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
-    {
-        FILE* f = std::fopen(szFile, "wb");
-        if (!f) return E_FAIL;
-        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
-        const bool closed = std::fclose(f) == 0;
-        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
-        return S_OK;
     }
 
     HRESULT Metadata(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata& metadata, Header& h, Blob* idat, size_t& idatBytes) noexcept
@@ -577,16 +567,6 @@ namespace
         });
     }
 
-    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
-    struct DeviceTemp
-    {
-        Device& device; void* p = nullptr;
-        explicit DeviceTemp(Device& d) noexcept : device(d) {}
-        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
-        DeviceTemp(const DeviceTemp&) = delete;
-        DeviceTemp& operator=(const DeviceTemp&) = delete;
-    };
-
     HRESULT SaveResident(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept
     {
         blob.Release();
@@ -657,7 +637,7 @@ HRESULT LoadFromPNGFileRaw(const char* szFile, PNG_FLAGS flags, TexMetadata* met
     raw.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    const HRESULT hr = ReadAll(szFile, file);
+    const HRESULT hr = ReadPNGFile(szFile, file);
     if (FAILED(hr)) return hr;
     return LoadFromPNGMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, raw);
 }
@@ -672,7 +652,7 @@ HRESULT GetMetadataFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata&
 {
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    const HRESULT hr = ReadAll(szFile, file);
+    const HRESULT hr = ReadPNGFile(szFile, file);
     if (FAILED(hr)) return hr;
     return GetMetadataFromPNGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata);
 }
@@ -705,7 +685,7 @@ HRESULT LoadFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata* metada
     image.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    const HRESULT hr = ReadAll(szFile, file);
+    const HRESULT hr = ReadPNGFile(szFile, file);
     if (FAILED(hr)) return hr;
     return LoadFromPNGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
 }
@@ -767,7 +747,7 @@ HRESULT LoadFromPNGFile(Device& device, const char* szFile, PNG_FLAGS flags, Tex
     image.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    const HRESULT hr = ReadAll(szFile, file);
+    const HRESULT hr = ReadPNGFile(szFile, file);
     if (FAILED(hr)) return hr;
     return LoadFromPNGMemory(device, file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
 }

@@ -6,8 +6,7 @@
 // the ASCII samples - and hands back where the samples lie and how to read them. What happens to a texel after that is dxtex_pnm.h's,
 // which the GPU kernels share: the host loader runs it here, the resident forms at the end of this file run it on the device, so that a
 // file's samples cross PCIe as the bytes they are. The writer is split the same way around its rows.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 #include "../csrc/dxtex_pnm.h"
 
 #include <algorithm>
@@ -221,31 +220,6 @@ namespace
         return S_OK;
     }
 
-    HRESULT ReadAll(const char* szFile, Blob& buf) noexcept          // ReadData (:87-143)
-    {
-        FILE* f = std::fopen(szFile, "rb");
-        if (!f) return E_FAIL;
-        std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-        if (n < 0) { std::fclose(f); return E_FAIL; }
-        if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
-        if (n < 1) { std::fclose(f); return E_FAIL; }
-        const HRESULT hr = buf.Initialize(size_t(n));
-        if (FAILED(hr)) { std::fclose(f); return hr; }
-        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
-        std::fclose(f);
-        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
-    }
-
-    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
-    {
-        FILE* f = std::fopen(szFile, "wb");
-        if (!f) return E_FAIL;
-        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
-        const bool closed = std::fclose(f) == 0;
-        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
-        return S_OK;
-    }
-
     // the writers' checks and header (SaveToPortablePixMap :361-390, SaveToPortablePixMapHDR :688-718): which kind a format is written as
     struct FileShape { uint32_t kind; int source; char header[64]; size_t headerLen; };
     HRESULT SaveChecks(const Image& image, bool hdr, FileShape& f) noexcept
@@ -305,16 +279,6 @@ namespace
         });
     }
 
-    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
-    struct DeviceTemp
-    {
-        Device& device; void* p = nullptr;
-        explicit DeviceTemp(Device& d) noexcept : device(d) {}
-        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
-        DeviceTemp(const DeviceTemp&) = delete;
-        DeviceTemp& operator=(const DeviceTemp&) = delete;
-    };
-
     HRESULT SaveResident(Device& device, const Image& deviceImage, bool hdr, Blob& blob) noexcept
     {
         FileShape f;
@@ -362,7 +326,7 @@ HRESULT LoadFromPortablePixMapFileRaw(const char* szFile, TexMetadata* metadata,
     raw.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    HRESULT hr = ReadAll(szFile, file);
+    HRESULT hr = ReadAll(szFile, file, 1);
     if (FAILED(hr)) return hr;
     hr = LoadFromPortablePixMapMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), metadata, raw);
     if (SUCCEEDED(hr) && !raw.ascii) raw.storage.Swap(file);          // the payload points into the file: keep it
@@ -416,7 +380,7 @@ HRESULT LoadFromPortablePixMapFile(const char* szFile, TexMetadata* metadata, Sc
     image.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    const HRESULT hr = ReadAll(szFile, file);
+    const HRESULT hr = ReadAll(szFile, file, 1);
     if (FAILED(hr)) return hr;
     return LoadFromPortablePixMapMemory(file.GetBufferPointer(), file.GetBufferSize(), metadata, image);
 }
@@ -490,7 +454,7 @@ HRESULT LoadFromPortablePixMapFile(Device& device, const char* szFile, TexMetada
     image.Release();
     if (!szFile) return E_INVALIDARG;
     Blob file;
-    const HRESULT hr = ReadAll(szFile, file);
+    const HRESULT hr = ReadAll(szFile, file, 1);
     if (FAILED(hr)) return hr;
     return LoadFromPortablePixMapMemory(device, file.GetBufferPointer(), file.GetBufferSize(), metadata, image);
 }

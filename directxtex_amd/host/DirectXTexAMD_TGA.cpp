@@ -9,8 +9,7 @@
 // packets - and hands back the texels as the file orders them, B bytes each. What happens to a texel after that is dxtex_tga.h's, which
 // the GPU kernels share: the host loader runs it here, the resident forms at the end of this file run it on the device, so that a file's
 // texels cross PCIe as the bytes they are. The writer is split the same way around its rows.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 #include "../csrc/dxtex_tga.h"
 
 #include <algorithm>
@@ -192,31 +191,6 @@ namespace
         }
         return format;
     }
-
-    HRESULT ReadAll(const char* szFile, Blob& buf, size_t minimum) noexcept
-    {
-        FILE* f = std::fopen(szFile, "rb");
-        if (!f) return E_FAIL;
-        std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-        if (n < 0) { std::fclose(f); return E_FAIL; }
-        if (uint64_t(n) > UINT32_MAX) { std::fclose(f); return HRESULT_E_FILE_TOO_LARGE; }
-        if (size_t(n) < minimum) { std::fclose(f); return E_FAIL; }
-        const HRESULT hr = buf.Initialize(size_t(n));
-        if (FAILED(hr)) { std::fclose(f); return hr; }
-        const size_t got = std::fread(buf.GetBufferPointer(), 1, buf.GetBufferSize(), f);
-        std::fclose(f);
-        return got == buf.GetBufferSize() ? S_OK : E_FAIL;
-    }
-
-    HRESULT WriteBlob(const Blob& blob, const char* szFile) noexcept
-    {
-        FILE* f = std::fopen(szFile, "wb");
-        if (!f) return E_FAIL;
-        const size_t n = std::fwrite(blob.GetBufferPointer(), 1, blob.GetBufferSize(), f);
-        const bool closed = std::fclose(f) == 0;
-        if (n != blob.GetBufferSize() || !closed) { std::remove(szFile); return E_FAIL; }
-        return S_OK;
-    }
 }
 
 HRESULT GetMetadataFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, TexMetadata& metadata) noexcept
@@ -326,8 +300,8 @@ HRESULT LoadFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, Tex
         for (size_t x = 0; x < img->width; ++x, s += B)
         {
             uint32_t alpha;
-            const uint32_t t = dxtex::tga_unpack_texel(dxtex::tga_load(s, uint32_t(B)), kind, raw.palette, alpha);
-            dxtex::tga_store(row + (raw.rightToLeft ? img->width - 1 - x : x) * D, t, uint32_t(D));
+            const uint32_t t = dxtex::tga_unpack_texel(dxtex::le_load32(s, uint32_t(B)), kind, raw.palette, alpha);
+            dxtex::le_store32(row + (raw.rightToLeft ? img->width - 1 - x : x) * D, t, uint32_t(D));
             orAlpha |= alpha; orNotAlpha |= alpha ^ 255u;
         }
     }
@@ -444,7 +418,7 @@ HRESULT SaveToTGAMemory(const Image& image, TGA_FLAGS flags, Blob& blob, const T
         {
             const uint8_t* s = image.pixels + y * image.rowPitch;
             for (size_t x = 0; x < image.width && x * D + (D - 1) < image.rowPitch; ++x)          // a pitch below the row leaves the rest of it as allocated
-                dxtex::tga_store(d + x * B, dxtex::tga_pack_texel(dxtex::tga_load(s + x * D, uint32_t(D)), f.row), uint32_t(B));
+                dxtex::le_store32(d + x * B, dxtex::tga_pack_texel(dxtex::le_load32(s + x * D, uint32_t(D)), f.row), uint32_t(B));
             d += image.width * B;
         }
         return S_OK;
@@ -461,19 +435,6 @@ HRESULT SaveToTGAFile(const Image& image, TGA_FLAGS flags, const char* szFile, c
 }
 
 // ---- resident forms: the texels travel as the file has them, the per-texel pass runs on the device (dxtex_tga_unpack_device / dxtex_tga_pack_device) ----
-namespace
-{
-    // device memory of the Device's context, freed on scope exit (the free waits for the work queued on it)
-    struct DeviceTemp
-    {
-        Device& device; void* p = nullptr;
-        explicit DeviceTemp(Device& d) noexcept : device(d) {}
-        ~DeviceTemp() { if (p) dxtex_device_free(device.Get(), p); }
-        DeviceTemp(const DeviceTemp&) = delete;
-        DeviceTemp& operator=(const DeviceTemp&) = delete;
-    };
-}
-
 void TGARawImage::Release() noexcept
 {
     storage.Release();

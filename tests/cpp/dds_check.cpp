@@ -60,14 +60,14 @@ static int rows(const char* list)
             {
                 const size_t T = o.texelBytes, W = T < 4 ? T : 4;
                 out.resize(texels.size() / T * T);
-                for (size_t i = 0; i + T <= out.size(); i += T) dds_store(out.data() + i + T - W, dds_opaque_word(dds_load(texels.data() + i + T - W, uint32_t(W)), o), uint32_t(W));
+                for (size_t i = 0; i + T <= out.size(); i += T) le_store64(out.data() + i + T - W, dds_opaque_word(le_load32(texels.data() + i + T - W, uint32_t(W)), o), uint32_t(W));
             }
         }
         else
         {
             const size_t B = dds_file_bytes(op), D = dds_image_bytes(target), n = texels.size() / B;
             out.resize(n * D);
-            for (size_t x = 0; x < n; ++x) dds_store(out.data() + x * D, dds_unpack_texel(dds_load(texels.data() + x * B, uint32_t(B)), op, target, opaque != 0, palette), uint32_t(D));
+            for (size_t x = 0; x < n; ++x) le_store64(out.data() + x * D, dds_unpack_texel(le_load32(texels.data() + x * B, uint32_t(B)), op, target, opaque != 0, palette), uint32_t(D));
         }
         if (!write_file(outPath, out)) return 4;
         std::printf("ok\n");

@@ -60,9 +60,9 @@ static int unpack_many(const char* list)
             for (size_t x = 0; x < width; ++x)
             {
                 uint32_t alpha;
-                const uint32_t t = tga_unpack_texel(tga_load(texels.data() + (y * width + x) * B, B), kind, palette, alpha);
+                const uint32_t t = tga_unpack_texel(le_load32(texels.data() + (y * width + x) * B, B), kind, palette, alpha);
                 const size_t dy = (flags & TGA_TOP_DOWN) ? y : height - 1 - y, dx = (flags & TGA_RIGHT_TO_LEFT) ? width - 1 - x : x;
-                tga_store(out.data() + dy * pitch + dx * D, t, D);
+                le_store32(out.data() + dy * pitch + dx * D, t, D);
                 orAlpha |= alpha; orNotAlpha |= alpha ^ 255u;
             }
         uint32_t answer = kind == TGA_RGB_RGBA ? 1u : 0u;
@@ -94,7 +94,7 @@ static int pack(char** a)
     std::vector<uint8_t> out(width * height * B);
     for (size_t y = 0; y < height; ++y)
         for (size_t x = 0; x < width; ++x)
-            tga_store(out.data() + (y * width + x) * B, tga_pack_texel(tga_load(px.data() + y * pitch + x * D, D), row), B);
+            le_store32(out.data() + (y * width + x) * B, tga_pack_texel(le_load32(px.data() + y * pitch + x * D, D), row), B);
     return write_file(a[6], out) ? 0 : 4;
 }
 

@@ -23,7 +23,7 @@ E_NOT_SUPPORTED = 0x80070032 - (1 << 32)
 FILL = 0xA5
 # where a group of four, a wave and a workgroup each have a tail, and where three-byte rows fall on and off a dword
 WIDTHS, HEIGHTS = (1, 3, 4, 5, 63, 64, 65, 257), (1, 2, 5)
-BASES, PITCH_PADS = (0, 1), (0, 4, 3)
+BASES, PITCH_PADS = (0, 1, 4), (0, 4, 3)
 CP_LEGACY_DWORD, CP_BAD_DXTN_TAILS, CP_24BPP, CP_16BPP, CP_8BPP = 0x1, 0x1000, 0x10000, 0x20000, 0x40000
 OP_NAMES = ("copy", "swizzle", "565", "5551", "4444", "abgr4", "888", "332", "8332", "p8", "a8p8", "44", "l8", "l16", "a8l8", "l6v5u5", "l8u8v8", "wuv10")
 BATCH = 32          # images to a launch (csrc/dds.hip)

@@ -37,7 +37,7 @@ KINDS = {
 ORIENTATIONS = (0, dx.TGA_RIGHT_TO_LEFT, dx.TGA_TOP_DOWN, dx.TGA_RIGHT_TO_LEFT | dx.TGA_TOP_DOWN)
 # where a group of four, a wave and a workgroup each have a tail, and where three-byte rows fall on and off dword alignment
 WIDTHS, HEIGHTS = (1, 3, 4, 5, 63, 64, 65, 257), (1, 2, 5)
-BASES = (0, 1, 18 + 5)          # the stream's offset into its allocation: aligned, odd, and behind a header with a five-byte ID field
+BASES = (0, 1, 4, 18 + 5)          # the stream's offset into its allocation: aligned, odd, a dword but no two, and behind a header with a five-byte ID field
 PITCH_PADS = (0, 4, 3)
 PALETTE_FIRST, PALETTE_LENGTH = 200, 56
 
