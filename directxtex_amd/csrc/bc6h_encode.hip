@@ -1308,6 +1308,9 @@ hipError_t launch_bc6h_encode_many(const BcImage* images, size_t count, bool isS
             hipLaunchKernelGGL(bc7_bin_count_kernel, dim3(binGroups), dim3(256), 0, stream, a.tinfo, ntasks, a.counters);
             hipLaunchKernelGGL(bc7_bin_scan_kernel, dim3(1), dim3(1), 0, stream, a.counters);
             hipLaunchKernelGGL(bc7_bin_scatter_kernel, dim3(binGroups), dim3(256), 0, stream, a.tinfo, ntasks, a.counters, a.order);
+#if defined(DXTEX_DEV)
+            reverse_bins_if_asked(a.counters, a.order, nullptr, 0, stream);      // DXTEX_TASK_ORDER_REVERSE: positions inside a bin are free
+#endif
         };
         a.taskBase = 0;
         for (int m = 0; m < 4; ++m) a.prec1[m] = kModes[10 + m].prec[0];

@@ -9,6 +9,10 @@
 #include <cstring>
 #include <vector>
 #include "dxtex_kernels.h"
+#if defined(DXTEX_DEV)
+#include <cstdio>
+#include "dxtex_dev.h"
+#endif
 
 namespace dxtex
 {
@@ -221,6 +225,44 @@ __global__ void __launch_bounds__(256) bc7_bin_scatter_kernel(const uint32_t* ti
         if (np) order[atomicAdd(&cursor[np], 1u)] = make_uint2(t, ti);
     }
 }
+
+#if defined(DXTEX_DEV)
+// Development build only (DXTEX_TASK_ORDER_REVERSE, dxtex_dev.h): after the scatter, every bin of `order` reversed in place - one workgroup
+// per bin b = 1..16, [end - count, end) with end = counters[17 + b], count = counters[b] - under the same gate as the scatter. The sort
+// promises sizes that do not rise along `order` and nothing about positions inside a bin (they come from atomics); the payloads must not
+// depend on them (tests/test_task_order_gpu.py).
+__global__ void __launch_bounds__(256) bc7_bin_reverse_kernel(const uint32_t* counters, uint2* order, const uint32_t* gate = nullptr, uint32_t gateMin = 0)
+{
+    if (gate && *gate < gateMin) return;
+    const uint32_t b = blockIdx.x + 1, n = counters[b], end = counters[17 + b];
+    if (n > end) return;
+    const uint32_t start = end - n;
+    for (uint32_t i = threadIdx.x; i < n / 2; i += 256)
+    {
+        const uint2 lo = order[start + i], hi = order[end - 1 - i];
+        order[start + i] = hi; order[end - 1 - i] = lo;
+    }
+}
+
+// Called by both launchers right after bc7_bin_scatter_kernel. Under DXTEX_BC7_STATS it reports how many bins held two tasks or more,
+// the ones whose order the reversal changed (none behind a closed gate: the counters stay zero there).
+inline void reverse_bins_if_asked(const uint32_t* counters, uint2* order, const uint32_t* gate, uint32_t gateMin, hipStream_t stream)
+{
+    static const bool reverse = dev_env("DXTEX_TASK_ORDER_REVERSE") != nullptr;
+    if (!reverse) return;
+    hipLaunchKernelGGL(bc7_bin_reverse_kernel, dim3(16), dim3(256), 0, stream, counters, order, gate, gateMin);
+    static const bool stats = dev_env("DXTEX_BC7_STATS") != nullptr;
+    if (stats)
+    {
+        uint32_t c[17] = {};
+        (void)hipStreamSynchronize(stream);
+        (void)hipMemcpy(c, counters, sizeof(c), hipMemcpyDeviceToHost);
+        unsigned bins = 0;
+        for (int b = 1; b <= 16; ++b) bins += c[b] >= 2 ? 1 : 0;
+        std::fprintf(stderr, "task order: reversed %u bins\n", bins);
+    }
+}
+#endif
 
 // Work distribution of the search kernels: a fixed number of persistent wavefronts pull task indices from
 // one global counter (counters[kQueueBase + loop]); a lane that finishes its task takes the next one, so lanes
