@@ -87,13 +87,54 @@ def _diff(got, ref):
     return np.nonzero(got.reshape(-1) != ref.reshape(-1))[0][:8]
 
 
+# The channels of the remaining formats, for _within_srgb_bar: whole-element channels by element type, and the bit fields (low bits first)
+# of the packed ones. Float channels are compared as their words (one step = one ulp); D32_FLOAT_S8X24_UINT is a float word and a
+# stencil word.
+CHANNEL_WORDS = {np.uint32: (3, 7, 17, 42, 20), np.int32: (4, 8, 18, 43), np.uint16: (11, 12, 35, 36, 55, 56, 57, 102, 54),
+                 np.int16: (13, 14, 37, 38, 58, 59), np.uint8: (30, 49, 50, 62, 65, 100), np.int8: (31, 32, 51, 52, 63, 64)}
+CHANNEL_FIELDS = {24: (np.uint32, (10, 10, 10, 2)), 25: (np.uint32, (10, 10, 10, 2)), 89: (np.uint32, (10, 10, 10, 2)),
+                  101: (np.uint32, (10, 10, 10, 2)), 26: (np.uint32, (11, 11, 10)), 45: (np.uint32, (24, 8)), 85: (np.uint16, (5, 6, 5)),
+                  86: (np.uint16, (5, 5, 5, 1)), 115: (np.uint16, (4, 4, 4, 4)), 191: (np.uint16, (4, 4, 4, 4))}
+
+
+def _channel_codes(raw, fmt):
+    """-> [(int64 codes of one channel of every texel, bits of that channel)]"""
+    raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+    for word, formats in CHANNEL_WORDS.items():
+        if fmt in formats:
+            return [(raw.view(word).astype(np.int64), np.dtype(word).itemsize * 8)]
+    word, fields = CHANNEL_FIELDS[fmt]
+    v = raw.view(word).astype(np.int64)
+    out, at = [], 0
+    for bits in fields:
+        out.append(((v >> at) & ((1 << bits) - 1), bits))
+        at += bits
+    return out
+
+
 def _within_srgb_bar(got, ref, fmt):
-    """sRGB curves go through powf on both sides: one 8-bit step for 8-bit UNORM, else at most one ulp of a float word on < 1 % of words."""
+    """sRGB curves go through powf on both sides: one 8-bit step for 8-bit UNORM, else at most one ulp of a float word on < 1 % of words.
+    Every other format by its channels: at most one quantisation step of the channel (one ulp of a float channel), and channels wider
+    than 8 bits differ on fewer than 1 % of their values."""
     if fmt in EIGHT_BIT or fmt == R8:
         return int(np.abs(got.astype(np.int32) - ref.astype(np.int32)).max(initial=0)) <= 1
-    word = np.uint32 if fmt in FLOAT32_WORDS else np.uint16
-    g = got.view(word).astype(np.int64); r = ref.view(word).astype(np.int64)
-    return int(np.abs(g - r).max(initial=0)) <= 1 and float((g != r).mean()) < 0.01
+    if fmt in FLOAT32_WORDS or fmt in FLOAT16_WORDS:
+        word = np.uint32 if fmt in FLOAT32_WORDS else np.uint16
+        g = got.view(word).astype(np.int64); r = ref.view(word).astype(np.int64)
+        return int(np.abs(g - r).max(initial=0)) <= 1 and float((g != r).mean()) < 0.01
+    if fmt == RGB9E5:
+        # mantissa * 2^exponent as integers: one step of the coarser of the two shared exponents
+        g = np.ascontiguousarray(got).view(np.uint32).astype(np.int64); r = np.ascontiguousarray(ref).view(np.uint32).astype(np.int64)
+        step = np.int64(1) << np.maximum(g >> 27, r >> 27)
+        near = all((np.abs((((g >> s) & 511) << (g >> 27)) - (((r >> s) & 511) << (r >> 27))) <= step).all() for s in (0, 9, 18))
+        return bool(near) and float((g != r).mean()) < 0.01
+    wide_diff, wide_n = 0, 0
+    for (g, bits), (r, _) in zip(_channel_codes(got, fmt), _channel_codes(ref, fmt)):
+        if int(np.abs(g - r).max(initial=0)) > 1:
+            return False
+        if bits > 8:
+            wide_diff += int((g != r).sum()); wide_n += g.size
+    return wide_n == 0 or wide_diff / wide_n < 0.01
 
 
 class Device:
