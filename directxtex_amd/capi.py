@@ -51,6 +51,44 @@ class Image(ctypes.Structure):
                 ("rowPitch", ctypes.c_size_t), ("slicePitch", ctypes.c_size_t), ("pixels", ctypes.c_void_p)]
 
 
+class JpegComponent(ctypes.Structure):
+    """dxtex_jpeg_component (include/dxtex_amd.h): one component of a JPEG frame."""
+    _fields_ = [("h", ctypes.c_uint32), ("v", ctypes.c_uint32), ("quant", ctypes.c_uint32), ("blocksPerRow", ctypes.c_uint32), ("blockRows", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("offset", ctypes.c_uint64)]
+
+
+class JpegFrame(ctypes.Structure):
+    """dxtex_jpeg_frame (include/dxtex_amd.h): a JPEG frame, its components and quantiser tables in natural order."""
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("components", ctypes.c_uint32), ("colour", ctypes.c_uint32),
+                ("component", JpegComponent * 3), ("quant", (ctypes.c_uint16 * 64) * 4)]
+
+
+def jpeg_frame(width, height, colour, sampling=(1, 1), quant=None, quant_of=(0, 1, 1)):
+    """The JpegFrame of an image whose luma is sampling = (h, v) over 1 x 1 chroma (grey: 1 x 1), laid out as dxtex_jpeg_decode takes the
+    coefficients: blocks padded to whole MCUs, one component after another. quant = up to four tables of 64 entries in natural order;
+    quant_of = the table of each component."""
+    f = JpegFrame()
+    f.width, f.height, f.colour = width, height, colour
+    f.components = 1 if colour == 0 else 3
+    hmax, vmax = sampling if f.components == 3 else (1, 1)
+    at = 0
+    for c in range(f.components):
+        h, v = (hmax, vmax) if c == 0 else (1, 1)
+        k = f.component[c]
+        k.h, k.v, k.quant = h, v, quant_of[c]
+        k.blocksPerRow, k.blockRows, k.offset = -(-width // (8 * hmax)) * h, -(-height // (8 * vmax)) * v, at
+        at += k.blocksPerRow * k.blockRows * 64
+    for t, table in enumerate(quant if quant is not None else ()):
+        for i, q in enumerate(table):
+            f.quant[t][i] = int(q)
+    return f
+
+
+def jpeg_coefficient_count(frame):
+    """the int16 coefficients a JpegFrame takes"""
+    return sum(frame.component[c].blocksPerRow * frame.component[c].blockRows * 64 for c in range(frame.components))
+
+
 class Rect(ctypes.Structure):
     """dxtex_rect / DirectX::Rect: a rectangle of texels."""
     _fields_ = [("x", ctypes.c_size_t), ("y", ctypes.c_size_t), ("w", ctypes.c_size_t), ("h", ctypes.c_size_t)]
@@ -156,6 +194,8 @@ _SIGS = {
     "dxtex_png_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, _P(Image)]),
     "dxtex_png_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_png_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_jpeg_decode": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, _P(JpegFrame), _P(Image)]),
+    "dxtex_jpeg_decode_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, _P(JpegFrame), _P(Image)]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -884,6 +924,24 @@ class Context:
     def png_pack_device(self, src, rows_ptr, rows_bytes):
         """dxtex_png_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
         self._check(self._lib.dxtex_png_pack_device(self._h, ctypes.byref(src), rows_ptr, rows_bytes), "png_pack_device")
+
+    # -- JPEG samples (everything behind the Huffman walk of the .jpg reader) ----------------------------------------------------------
+    def jpeg_decode(self, coefficients, frame, fmt, row_pitch=None, out=None):
+        """dxtex_jpeg_decode: a frame's quantised coefficients (host int16, laid out as jpeg_frame states) -> pixels of `fmt` as a numpy
+        uint8 buffer with `row_pitch` bytes a row, default tight. out: the buffer to decode into, default a zeroed one."""
+        coefficients = np.ascontiguousarray(coefficients, np.int16)
+        pitch = compute_pitch(fmt, frame.width, frame.height)[0] if row_pitch is None else row_pitch
+        if out is None:
+            out = np.zeros(pitch * frame.height, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.nbytes >= pitch * frame.height
+        dst = Image(frame.width, frame.height, fmt, pitch, pitch * frame.height, out.ctypes.data)
+        self._check(self._lib.dxtex_jpeg_decode(self._h, coefficients.ctypes.data, coefficients.nbytes, ctypes.byref(frame), ctypes.byref(dst)), "jpeg_decode")
+        return out
+
+    def jpeg_decode_device(self, coefficients_ptr, coefficient_bytes, frame, dst):
+        """dxtex_jpeg_decode_device: the coefficients at a device pointer -> the device Image `dst` (device_image), asynchronous on the
+        stream."""
+        self._check(self._lib.dxtex_jpeg_decode_device(self._h, coefficients_ptr, coefficient_bytes, ctypes.byref(frame), ctypes.byref(dst)), "jpeg_decode_device")
 
     # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
     @staticmethod

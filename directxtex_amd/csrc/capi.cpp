@@ -8,6 +8,7 @@
 #include "dxtex_dds.h"
 #include "dxtex_pnm.h"
 #include "dxtex_png.h"
+#include "dxtex_jpeg.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -86,6 +87,8 @@ struct dxtex_ctx
     DeviceBuf groupRows;
     // error-diffusion Convert: row buffers (launch_convert_diffuse) and the device counter of texels its merge re-ran
     DeviceBuf ditherRows, ditherRerun; uint64_t ditherTexels = 0;
+    // JPEG: a colour frame's block-padded sample planes between jpeg_idct and jpeg_colour (launch_jpeg_decode)
+    DeviceBuf jpegPlanes;
     // dxtex_compress_many (host pointers): double-buffered pinned + device staging, copy streams on either side of ctx->stream
     struct Lane
     {
@@ -2047,6 +2050,87 @@ dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows,
     if (hr != DXTEX_S_OK) return hr;
     return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, rows, need,
                       [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_png_pack(view_of(with_pixels(*src, in)), source, out, ctx->stream, marks_of(ctx))); });
+}
+
+namespace
+{
+static_assert(DXTEX_JPEG_GREY == JPEG_GREY && DXTEX_JPEG_YCBCR == JPEG_YCBCR && DXTEX_JPEG_RGB == JPEG_RGB, "dxtex_jpeg.h's colour kinds are the public ones");
+
+// The checks of the JPEG two, in the order include/dxtex_amd.h states. *f = the frame as the launcher takes it, *need = the bytes of its
+// coefficients, *rowBytes = a row of the image.
+dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst, JpegFrame* f, size_t* need,
+                         size_t* rowBytes)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!coefficients) return fail(ctx, DXTEX_E_POINTER, "null coefficients");
+    if (!frame) return fail(ctx, DXTEX_E_POINTER, "null frame");
+    if (!dst) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (frame->colour > DXTEX_JPEG_RGB) return fail(ctx, DXTEX_E_INVALIDARG, "unknown JPEG colour");
+    if (frame->components != (frame->colour == DXTEX_JPEG_GREY ? 1u : 3u)) return fail(ctx, DXTEX_E_INVALIDARG, "the component count does not match the colour");
+    if (!frame->width || !frame->height || frame->width > 65535u || frame->height > 65535u) return fail(ctx, DXTEX_E_INVALIDARG, "a JPEG frame is 1 to 65535 texels wide and high");
+    if (dst->width != frame->width || dst->height != frame->height) return fail(ctx, DXTEX_E_INVALIDARG, "the image is not the frame's size");
+    if (reinterpret_cast<uintptr_t>(coefficients) & 1u) return fail(ctx, DXTEX_E_INVALIDARG, "coefficients at an odd address");
+    for (uint32_t c = 0; c < frame->components; ++c)
+    {
+        const dxtex_jpeg_component& k = frame->component[c];
+        if (k.quant > 3u) return fail(ctx, DXTEX_E_INVALIDARG, "a quantiser index above 3");
+        if (k.h < 1u || k.h > 4u || k.v < 1u || k.v > 4u) return fail(ctx, DXTEX_E_INVALIDARG, "sampling factors are 1 to 4");
+    }
+    // sampling: luma 1x1, 2x1 or 2x2 over 1x1 chroma; grey 1x1
+    const uint32_t hmax = frame->component[0].h, vmax = frame->component[0].v;
+    bool sampling = (hmax == 1u && vmax == 1u) || (frame->components == 3u && hmax == 2u && vmax <= 2u);
+    for (uint32_t c = 1; c < frame->components; ++c) sampling = sampling && frame->component[c].h == 1u && frame->component[c].v == 1u;
+    if (!sampling) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "JPEG sampling other than 1x1, 2x1 or 2x2 luma over 1x1 chroma");
+    const bool grey = frame->colour == DXTEX_JPEG_GREY;
+    if (grey ? dst->format != FMT_R8_UNORM : (dst->format != FMT_R8G8B8A8_UNORM && dst->format != FMT_R8G8B8A8_UNORM_SRGB))
+        return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this JPEG colour does not decode into this format");
+    f->width = frame->width; f->height = frame->height; f->components = frame->components; f->colour = int(frame->colour);
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < frame->components; ++c)
+    {
+        const dxtex_jpeg_component& k = frame->component[c];
+        if (k.blocksPerRow != jpeg_padded_blocks(frame->width, k.h, hmax) || k.blockRows != jpeg_padded_blocks(frame->height, k.v, vmax) || k.offset != at)
+            return fail(ctx, DXTEX_E_INVALIDARG, "block counts or offsets that are not the frame's");
+        f->comp[c] = JpegComponent{ k.h, k.v, k.quant, k.blocksPerRow, k.blockRows, k.offset };
+        at += uint64_t(k.blocksPerRow) * k.blockRows * 64u;
+    }
+    std::memcpy(f->quant, frame->quant, sizeof(f->quant));
+    *need = size_t(at) * sizeof(int16_t);
+    *rowBytes = size_t(frame->width) * (grey ? 1u : 4u);
+    if (coefficientBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer bytes than the frame's coefficients");
+    return check_stream_image(ctx, "coefficients", coefficients, *need, dst, *rowBytes);
+}
+
+// both kernels on the context's stream, the planes in memory of the context
+dxtex_hresult submit_jpeg(dxtex_ctx* ctx, const uint8_t* coefficients, const JpegFrame& f, const ImgView& view)
+{
+    const dxtex_hresult hr = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+    if (hr != DXTEX_S_OK) return hr;
+    return launched(ctx, launch_jpeg_decode(reinterpret_cast<const int16_t*>(coefficients), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)));
+}
+} // namespace
+
+dxtex_hresult dxtex_jpeg_decode_device(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst)
+{
+    JpegFrame f; size_t need, rowBytes;
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, &f, &need, &rowBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_jpeg(ctx, static_cast<const uint8_t*>(coefficients), f, view_of(*dst)); });
+}
+
+dxtex_hresult dxtex_jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst)
+{
+    JpegFrame f; size_t need, rowBytes;
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, &f, &need, &rowBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    {
+        ScopedDevice sd(ctx->device);
+        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+        if (grown != DXTEX_S_OK) return grown;
+    }
+    return run_staged_rows(ctx, coefficients, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
+                           { return launch_jpeg_decode(reinterpret_cast<const int16_t*>(stream), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)); });
 }
 
 namespace

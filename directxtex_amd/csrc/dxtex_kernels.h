@@ -140,6 +140,15 @@ hipError_t launch_pnm_pack(const ImgView& src, int source, uint8_t* stream, hipS
 hipError_t launch_png_unpack(const uint8_t* stream, int kind, uint32_t flags, const uint32_t* palette, const ImgView& dst, hipStream_t stream_, KernelMarks* marks = nullptr);
 hipError_t launch_png_pack(const ImgView& src, int source, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
 
+// JPEG samples (jpeg.hip; the rules are in dxtex_jpeg.h). `frame` is what the entry points have checked (include/dxtex_amd.h's layout):
+// jpeg_idct dequantises and transforms every block of every component in one launch - a grey frame straight into dst, a colour frame into
+// block-padded planes at `planes`, jpeg_plane_bytes(frame) bytes of device memory (0 for grey) - and jpeg_colour upsamples, transforms and
+// stores each texel of dst. Nothing outside each row's `width` texels is written. Wide / narrow: see jpeg.hip.
+struct JpegComponent { uint32_t h, v, quant, blocksPerRow, blockRows; uint64_t offset; };
+struct JpegFrame { uint32_t width, height, components; int colour; JpegComponent comp[3]; uint16_t quant[4][64]; };
+size_t jpeg_plane_bytes(const JpegFrame& frame);
+hipError_t launch_jpeg_decode(const int16_t* coefficients, const JpegFrame& frame, const ImgView& dst, uint8_t* planes, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

@@ -779,4 +779,67 @@ HRESULT LoadFromPNGFile(Device& device, const char* szFile, PNG_FLAGS flags, Tex
 HRESULT UploadPNGRaw(Device& device, const TexMetadata& metadata, const PNGRawImage& raw, DeviceScratchImage& image) noexcept;
 HRESULT SaveToPNGMemory(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept;
 HRESULT SaveToPNGFile(Device& device, const Image& deviceImage, PNG_FLAGS flags, const char* szFile) noexcept;
+
+// ---- JPEG, Auxiliary/DirectXTexJPEG.cpp (the reference's libjpeg codec), the reader: baseline, extended and progressive Huffman files of one
+// or three 8-bit components in; the writer is not built yet. No library is linked: the marker walk, the Huffman decoder and the four
+// progressive passes are this project's own code and end in the file's quantised coefficients; dequantisation, the inverse DCT, chroma
+// upsampling and YCbCr -> RGB are csrc/dxtex_jpeg.h's, which follow libjpeg's defaults (JDCT_ISLOW, fancy upsampling) as the reference leaves
+// them. Formats and metadata follow TranslateColor / GetMetadata: grey is R8_UNORM; colour is R8G8B8A8_UNORM_SRGB, or R8G8B8A8_UNORM under
+// JPEG_FLAGS_DEFAULT_LINEAR, alpha 0xff, TEX_ALPHA_MODE_OPAQUE; 2-D, one item, one mip. The colour kind follows libjpeg's
+// default_decompress_parms: one component is grey; of three, a JFIF marker means YCbCr; without one, Adobe transform 0 is RGB and any other
+// YCbCr; with neither marker, component ids 'R', 'G', 'B' mean RGB and anything else YCbCr. Four components (CMYK, YCCK) are E_FAIL, as the
+// reference throws for them. Null arguments are E_INVALIDARG, a missing file HRESULT_ERROR_FILE_NOT_FOUND, every defect in the bytes E_FAIL.
+// Four departures:
+//   1. The Memory forms are this project's; the reference has the File forms only.
+//   2. HRESULT_E_NOT_SUPPORTED for: arithmetic coding (SOF9 to SOF15); lossless and hierarchical frames (SOF3, SOF5 to SOF7); 12-bit
+//      precision; a DNL-defined height (height 0 in SOF); sampling other than luma 1x1, 2x1 or 2x2 over 1x1 chroma (grey with any factors
+//      is 1x1); a progressive file whose scans end without bringing every coefficient of every component to Al = 0, whose blocks libjpeg
+//      would smooth.
+//   3. A truncated or corrupt entropy segment is E_FAIL, where libjpeg pads with zeros and warns: data that end before the last MCU, a bad
+//      code, a wrong RSTn, a run past coefficient 63 (or past the band of a progressive scan), a missing EOI.
+//   4. EXIF orientation, thumbnails and ICC profiles are ignored, as libjpeg ignores them.
+// Out of scope: the writer (SaveToJPEGFile), arithmetic coding, 12-bit samples, sampling other than 4:4:4 / 4:2:2 / 4:2:0, incomplete
+// progressive files. -------------------------------------------------------------------------------------------------------------------------
+enum JPEG_FLAGS : uint32_t
+{
+    JPEG_FLAGS_NONE = 0,
+    JPEG_FLAGS_DEFAULT_LINEAR = 0x1,     // a colour file is R8G8B8A8_UNORM, not R8G8B8A8_UNORM_SRGB
+};
+inline JPEG_FLAGS operator|(JPEG_FLAGS a, JPEG_FLAGS b) noexcept { return JPEG_FLAGS(uint32_t(a) | uint32_t(b)); }
+HRESULT GetMetadataFromJPEGMemory(const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata& metadata) noexcept;
+HRESULT GetMetadataFromJPEGFile(const char* szFile, JPEG_FLAGS flags, TexMetadata& metadata) noexcept;
+// without a device: the per-block and per-texel functions of csrc/dxtex_jpeg.h run serially
+HRESULT LoadFromJPEGMemory(const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT LoadFromJPEGFile(const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept;
+// The reader's byte-serial half, which needs no device: markers, tables, the Huffman walk of every scan, every refusal. What comes back is the
+// frame and its quantised coefficients (dxtex_jpeg_decode's arguments): int16, 64 a block in natural (row-major) order, blocks in raster
+// order per component, one component after another, each component padded to whole MCUs - ceil(width / (8 hmax)) * h by
+// ceil(height / (8 vmax)) * v blocks. GetMetadata* stop at the first scan. On failure `raw` is released.
+struct JPEGRawImage
+{
+    struct Component
+    {
+        uint32_t h = 0, v = 0;                   // sampling factors (grey: 1 x 1 whatever the file says)
+        uint32_t quant = 0;                      // which of `quant`
+        uint32_t blocksPerRow = 0, blockRows = 0;
+        size_t offset = 0;                       // of its first coefficient, in coefficients
+    };
+    uint32_t width = 0, height = 0, components = 0;
+    uint32_t colour = 0;                         // DXTEX_JPEG_GREY / _YCBCR / _RGB (include/dxtex_amd.h)
+    Component component[3];
+    uint16_t quant[4][64] = {};                  // natural order
+    const int16_t* coefficients = nullptr;       // into `storage`
+    size_t coefficientCount = 0;
+    Blob storage;
+    void Release() noexcept;
+};
+HRESULT LoadFromJPEGMemoryRaw(const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata* metadata, JPEGRawImage& raw) noexcept;
+HRESULT LoadFromJPEGFileRaw(const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, JPEGRawImage& raw) noexcept;
+// Resident forms: the coefficients cross PCIe as the file has them - 2 bytes a texel for grey, 3 for 4:2:0, 4 for 4:2:2, 6 for 4:4:4 - and the
+// inverse DCT, upsampling and colour run on the device (dxtex_jpeg_decode_device). HRESULTs, metadata and pixels are those of the host forms.
+// One upload of the coefficients, no download; the result is released on failure.
+HRESULT LoadFromJPEGMemory(Device& device, const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromJPEGFile(Device& device, const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device
+HRESULT UploadJPEGRaw(Device& device, const TexMetadata& metadata, const JPEGRawImage& raw, DeviceScratchImage& image) noexcept;
 } // namespace DirectXTexAMD

@@ -1,4 +1,4 @@
-// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA and PNG in; DDS out (TGA / HDR
+// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG and JPEG in; DDS out (TGA / HDR
 // too for the single-image results). Every input is loaded on the host, checked, uploaded ONCE, run through texassemble's per-input
 // pipeline on the device (decompress, -stripmips, -alpha, resize, -tonemap, convert), assembled there - every face, slice, item or mip a
 // rectangle of one batched copy_rect launch - and the result is downloaded once.
@@ -312,7 +312,7 @@ int Fail(const char* what, HRESULT hr)
 // an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
 // a .tga input likewise as the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
 // a .dds input as the file itself, parsed: its payload goes up as it is and the row conversions of a legacy file run on the device
-struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; bool png = false; PNGRawImage pngRaw; };
+struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; bool png = false; PNGRawImage pngRaw; bool jpeg = false; JPEGRawImage jpegRaw; };
 
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
 int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
@@ -367,8 +367,15 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
             hr = LoadFromPNGFileRaw(file.c_str(), bgr ? PNG_FLAGS_BGR : PNG_FLAGS_NONE, &in->info, in->pngRaw);
             if (FAILED(hr)) return Fail(" FAILED", hr);
         }
+        else if (hasExt(file, ".jpg") || hasExt(file, ".jpeg"))
+        {
+            // the Huffman walk here, before there is a device; the quantised coefficients go up later (texassemble.cpp:1526-1534)
+            in->jpeg = true;
+            hr = LoadFromJPEGFileRaw(file.c_str(), JPEG_FLAGS_NONE, &in->info, in->jpegRaw);
+            if (FAILED(hr)) return Fail(" FAILED", hr);
+        }
         else if (hasExt(file, ".hdr")) { in->hdr = true; hr = LoadFromHDRFileRGBE(file.c_str(), &in->info, in->exposure, in->rgbe); if (FAILED(hr)) return Fail(" FAILED", hr); }
-        else { std::printf(" FAILED: only .dds, .tga, .hdr and .png can be read (the reference reads the rest through WIC)\n"); return 1; }
+        else { std::printf(" FAILED: only .dds, .tga, .hdr, .png and .jpg can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
         std::fflush(stdout);
         inputs.push_back(std::move(in));
@@ -408,9 +415,10 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         Input& in = *inputs[index];
         HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : in.tga ? UploadTGARaw(dev, in.info, TGA_FLAGS_NONE, in.tgaRaw, cur)
                                         : in.png ? UploadPNGRaw(dev, in.info, in.pngRaw, cur)
+                                        : in.jpeg ? UploadJPEGRaw(dev, in.info, in.jpegRaw, cur)
                                                                                               : UploadDDSRaw(dev, in.dds, cur);
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release(); in.pngRaw.Release();
+        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release(); in.pngRaw.Release(); in.jpegRaw.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600

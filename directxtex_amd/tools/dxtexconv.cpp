@@ -6,7 +6,7 @@
 // (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
 // rotations, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
-//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png>...
+//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg>...
 //                          (-ft hdr | tga | ppm | pfm | png: Radiance / TGA / portable pixmap / PNG output of level 0)
 //                          (-ft png: <out> is a directory or a .png name)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
@@ -144,7 +144,7 @@ int usage()
                          "                 [--rotate-color 709toHDR10|HDR10to709|709to2020|2020to709|P3D65toHDR10|P3D65to2020|709toP3D65|P3D65to709] [--paper-white-nits N]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N]\n"
-                         "                 [-ft dds|hdr|tga|ppm|pfm|png] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png>...\n");
+                         "                 [-ft dds|hdr|tga|ppm|pfm|png] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg>...\n");
     return 1;
 }
 
@@ -255,7 +255,7 @@ bool Parse(int argc, char** argv, Options& o)
         else if (a == "-ignoremips") o.ddsRead |= DDS_FLAGS_IGNORE_MIPS;
         else if (a == "-xlum") o.ddsRead |= DDS_FLAGS_EXPAND_LUMINANCE;
         else if (a == "-tga20") o.tga20 = true;
-        else if (a == "-ignoresrgb") o.ignoreSrgb = true;          // texconv's OPT_IGNORE_SRGB_METADATA: a .png's sRGB chunk and gAMA do not choose the format
+        else if (a == "-ignoresrgb") o.ignoreSrgb = true;          // texconv's OPT_IGNORE_SRGB_METADATA: a .png's sRGB chunk and gAMA do not choose the format; a colour .jpg is linear
         else if (a == "-info") o.info = true;
         else if (a == "-dx10") o.dx10 = true;
         else if (a == "-dx9") o.dx9 = true;
@@ -291,6 +291,7 @@ bool Parse(int argc, char** argv, Options& o)
             else if (!strcasecmp(ft, "ppm")) o.ppmOut = true;
             else if (!strcasecmp(ft, "pfm")) o.pfmOut = true;
             else if (!strcasecmp(ft, "png")) o.pngOut = true;
+            else if (!strcasecmp(ft, "jpg") || !strcasecmp(ft, "jpeg")) { std::fprintf(stderr, "-ft %s: JPEG output is not written yet (the reader is; the writer is the next step)\n", ft); return false; }
             else if (strcasecmp(ft, "dds")) { std::fprintf(stderr, "output file types: dds, hdr, tga, ppm, pfm, png\n"); return false; }
         }
         else if (a == "-r" || a == "-nogpu" || a == "-singleproc") { }            // nothing to switch here
@@ -304,6 +305,8 @@ bool Parse(int argc, char** argv, Options& o)
     // reader that goes by the extension opens.
     for (const char* ext : { ".dds", ".hdr", ".tga", ".ppm", ".pfm" })
         if (o.pngOut && o.out.size() > 4 && !strcasecmp(o.out.c_str() + o.out.size() - 4, ext)) { std::fprintf(stderr, "-ft png writes a .png: -o %s names a %s file\n", o.out.c_str(), ext); return false; }
+    for (const char* ext : { ".jpg", ".jpeg" })
+        if (o.out.size() > std::strlen(ext) && !strcasecmp(o.out.c_str() + o.out.size() - std::strlen(ext), ext)) { std::fprintf(stderr, "-o %s: JPEG output is not written yet\n", o.out.c_str()); return false; }
     if (o.gpus.empty()) o.gpus.assign(1, 0);
     if (o.info) return !o.inputs.empty();
     return !o.inputs.empty() && !o.out.empty();
@@ -363,6 +366,10 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         const bool bgr = o.format == DXGI_FORMAT_B8G8R8A8_UNORM || o.format == DXGI_FORMAT_B8G8R8X8_UNORM || o.format == DXGI_FORMAT_B8G8R8A8_UNORM_SRGB || o.format == DXGI_FORMAT_B8G8R8X8_UNORM_SRGB;
         check("load", LoadFromPNGFile(dev, inFile.c_str(), PNG_FLAGS((bgr ? PNG_FLAGS_BGR : PNG_FLAGS_NONE) | (o.ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE)), &info, image));
     }
+    // JPEG: the Huffman walk is byte-serial and runs on the host, the quantised coefficients go up as the file has them, and dequantisation,
+    // the inverse DCT, upsampling and YCbCr -> RGB run on the device. The flag is texconv's (texconv.cpp:2192-2208)
+    else if (hasExt(inFile, ".jpg") || hasExt(inFile, ".jpeg"))
+        check("load", LoadFromJPEGFile(dev, inFile.c_str(), o.ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, &info, image));
     // DDS likewise: the payload goes up at the size it has in the file - a native file straight into the image's memory, a legacy one through
     // the row conversions on the device
     else check("load", LoadFromDDSFile(dev, inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, image));
@@ -647,6 +654,7 @@ int PrintInfo(const Options& o)
         const HRESULT hr = hasExt(".hdr") ? GetMetadataFromHDRFile(f.c_str(), m) : hasExt(".tga") ? GetMetadataFromTGAFile(f.c_str(), TGA_FLAGS_NONE, m)
                            : (hasExt(".ppm") || hasExt(".pfm") || hasExt(".phm")) ? GetMetadataFromPortablePixMapFile(f.c_str(), m)
                            : hasExt(".png") ? GetMetadataFromPNGFile(f.c_str(), o.ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE, m)
+                           : (hasExt(".jpg") || hasExt(".jpeg")) ? GetMetadataFromJPEGFile(f.c_str(), o.ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, m)
                                                                                                    : GetMetadataFromDDSFile(f.c_str(), DDS_FLAGS(o.ddsRead), m);
         if (FAILED(hr)) { std::printf("%s: FAILED (%08X)\n", f.c_str(), unsigned(hr)); ++failures; continue; }
         const char* name = "";

@@ -1,4 +1,4 @@
-// dxtexdiag: texdiag's analyze, compare and diff commands (Texdiag/texdiag.cpp) on the MI355X host layer. DDS, HDR, TGA and PNG in.
+// dxtexdiag: texdiag's analyze, compare and diff commands (Texdiag/texdiag.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG and JPEG in.
 //
 //   dxtexdiag analyze [options] <files>            per image: minimum, average, maximum, variance, std dev, luminance, FP specials; BC files
 //                                                  also get the block-mode histogram (texdiag's print layout, :681-695, :795-856)
@@ -171,6 +171,7 @@ HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata
     HRESULT hr = hasExt(file, ".hdr") ? LoadFromHDRFile(dev, file.c_str(), &info, resident)
                : hasExt(file, ".tga") ? LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident)
                : hasExt(file, ".png") ? LoadFromPNGFile(dev, file.c_str(), PNG_FLAGS_NONE, &info, resident)          // texdiag.cpp:605-608
+               : (hasExt(file, ".jpg") || hasExt(file, ".jpeg")) ? LoadFromJPEGFile(dev, file.c_str(), JPEG_FLAGS_NONE, &info, resident)          // texdiag.cpp:599-602
                                       : LoadFromDDSFile(dev, file.c_str(), DDS_FLAGS(o.ddsRead), &info, resident);
     if (FAILED(hr) || !IsPlanar(info.format)) return hr;
     DeviceScratchImage single;

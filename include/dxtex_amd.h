@@ -41,6 +41,8 @@
  *     the rows of SaveToPortablePixMap[HDR]      :209-223, :595-681, :392-422, :720-735
  *   LoadFromPNGFile's / SaveToPNGFile's         Auxiliary/DirectXTexPNG.cpp     dxtex_png_unpack / dxtex_png_pack
  *     per-texel transforms                       :126-225, :315-404
+ *   LoadFromJPEGFile behind the Huffman walk:   Auxiliary/DirectXTexJPEG.cpp    dxtex_jpeg_decode
+ *     libjpeg's jidctint.c, jdsample.c, jdcolor.c  :184-238
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -498,6 +500,47 @@ dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows,
 dxtex_hresult dxtex_png_unpack_device(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
                                       const dxtex_image* dst);
 dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes);
+
+/* JPEG (.jpg) samples: everything behind the Huffman walk, which is byte-serial and stays with the caller. One image per call. The file
+ * side is the frame and its quantised coefficients: int16, 64 a block in natural (row-major) order, blocks in raster order per component,
+ * one component after another from offset 0 with nothing between them, each component padded to whole MCUs:
+ * blocksPerRow = ceil(width / (8 hmax)) * h and blockRows = ceil(height / (8 vmax)) * v. The call dequantises, runs libjpeg's JDCT_ISLOW
+ * inverse DCT (jidctint.c), its fancy upsampling (jdsample.c) and its YCbCr -> RGB (jdcolor.c) and stores through dst's pitch:
+ *   colour             components   sampling (luma over 1x1 chroma)   dst->format              texel
+ *   DXTEX_JPEG_GREY    1            1x1                               R8_UNORM                 the sample
+ *   DXTEX_JPEG_YCBCR   3            1x1, 2x1, 2x2                     R8G8B8A8_UNORM[_SRGB]    r, g, b, 0xff after the transform
+ *   DXTEX_JPEG_RGB     3            1x1, 2x1, 2x2                     R8G8B8A8_UNORM[_SRGB]    the three samples, 0xff
+ * All arithmetic is 32-bit and wraps, so every input has one result, the one csrc/dxtex_jpeg.h gives on the host; it is libjpeg's wherever
+ * libjpeg's own arithmetic does not overflow. More coefficient bytes than the frame takes are ignored.
+ * HRESULTs, in this order: E_POINTER for null coefficients, frame, image or pixels; E_INVALIDARG for an unknown colour, a component count
+ * that does not match it, a width or height of 0 or above 65535, an image that is not the frame's size, coefficients at an odd address, a
+ * quantiser index above 3 or a sampling factor outside 1..4; NOT_SUPPORTED for sampling outside the table or a format that does not pair
+ * with the colour; E_INVALIDARG for block counts or offsets that are not the frame's, fewer bytes than the frame takes, a row pitch smaller
+ * than the row, or coefficients that overlap the pixels. Bytes of the image outside each row's texels are not written. */
+#define DXTEX_JPEG_GREY   0u
+#define DXTEX_JPEG_YCBCR  1u
+#define DXTEX_JPEG_RGB    2u
+typedef struct dxtex_jpeg_component
+{
+    uint32_t h, v;                 /* sampling factors */
+    uint32_t quant;                /* index into dxtex_jpeg_frame.quant */
+    uint32_t blocksPerRow, blockRows;
+    uint32_t reserved;             /* 0 */
+    uint64_t offset;               /* of the component's first coefficient, in coefficients (not bytes) */
+} dxtex_jpeg_component;
+typedef struct dxtex_jpeg_frame
+{
+    uint32_t width, height;
+    uint32_t components;           /* 1 or 3 */
+    uint32_t colour;               /* DXTEX_JPEG_* */
+    dxtex_jpeg_component component[3];
+    uint16_t quant[4][64];         /* natural order; entries a component does not name are ignored */
+} dxtex_jpeg_frame;
+/* host pointers, through the context's staging: the coefficients go up as they are, the image comes down through its pitch */
+dxtex_hresult dxtex_jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst);
+/* device pointers (the frame stays a host pointer, read before the call returns): asynchronous on the context's stream. The coefficients
+ * may start at any even byte; see csrc/jpeg.hip for the alignments that take 16-byte loads and the wide route of jpeg_colour. */
+dxtex_hresult dxtex_jpeg_decode_device(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
