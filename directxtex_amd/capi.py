@@ -196,6 +196,8 @@ _SIGS = {
     "dxtex_png_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_jpeg_decode": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, _P(JpegFrame), _P(Image)]),
     "dxtex_jpeg_decode_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, _P(JpegFrame), _P(Image)]),
+    "dxtex_jpeg_encode": (ctypes.c_int32, [_ctx_p, _P(Image), _P(JpegFrame), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_jpeg_encode_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(JpegFrame), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -925,7 +927,7 @@ class Context:
         """dxtex_png_pack_device: the device Image `src` -> the file's rows at a device pointer, asynchronous on the stream."""
         self._check(self._lib.dxtex_png_pack_device(self._h, ctypes.byref(src), rows_ptr, rows_bytes), "png_pack_device")
 
-    # -- JPEG samples (everything behind the Huffman walk of the .jpg reader) ----------------------------------------------------------
+    # -- JPEG samples (everything behind the Huffman walk of the .jpg reader, everything in front of the writer's Huffman coder) ----------
     def jpeg_decode(self, coefficients, frame, fmt, row_pitch=None, out=None):
         """dxtex_jpeg_decode: a frame's quantised coefficients (host int16, laid out as jpeg_frame states) -> pixels of `fmt` as a numpy
         uint8 buffer with `row_pitch` bytes a row, default tight. out: the buffer to decode into, default a zeroed one."""
@@ -942,6 +944,24 @@ class Context:
         """dxtex_jpeg_decode_device: the coefficients at a device pointer -> the device Image `dst` (device_image), asynchronous on the
         stream."""
         self._check(self._lib.dxtex_jpeg_decode_device(self._h, coefficients_ptr, coefficient_bytes, ctypes.byref(frame), ctypes.byref(dst)), "jpeg_decode_device")
+
+    def jpeg_encode(self, pixels, frame, fmt, row_pitch=None, out=None):
+        """dxtex_jpeg_encode: host pixels of `fmt` (a numpy uint8 buffer with `row_pitch` bytes a row, default tight) -> the frame's
+        quantised coefficients as a numpy int16 array, laid out as jpeg_frame states. out: the array to encode into, default a zeroed one
+        of the frame's size."""
+        pixels = np.ascontiguousarray(pixels, np.uint8)
+        pitch = compute_pitch(fmt, frame.width, frame.height)[0] if row_pitch is None else row_pitch
+        if out is None:
+            out = np.zeros(jpeg_coefficient_count(frame), np.int16)
+        assert out.dtype == np.int16 and out.flags["C_CONTIGUOUS"]
+        src = Image(frame.width, frame.height, fmt, pitch, pitch * frame.height, pixels.ctypes.data)
+        self._check(self._lib.dxtex_jpeg_encode(self._h, ctypes.byref(src), ctypes.byref(frame), out.ctypes.data, out.nbytes), "jpeg_encode")
+        return out
+
+    def jpeg_encode_device(self, src, frame, coefficients_ptr, coefficient_bytes):
+        """dxtex_jpeg_encode_device: the device Image `src` (device_image) -> the frame's coefficients at a device pointer, asynchronous on
+        the stream."""
+        self._check(self._lib.dxtex_jpeg_encode_device(self._h, ctypes.byref(src), ctypes.byref(frame), coefficients_ptr, coefficient_bytes), "jpeg_encode_device")
 
     # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
     @staticmethod

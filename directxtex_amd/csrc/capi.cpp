@@ -87,7 +87,7 @@ struct dxtex_ctx
     DeviceBuf groupRows;
     // error-diffusion Convert: row buffers (launch_convert_diffuse) and the device counter of texels its merge re-ran
     DeviceBuf ditherRows, ditherRerun; uint64_t ditherTexels = 0;
-    // JPEG: a colour frame's block-padded sample planes between jpeg_idct and jpeg_colour (launch_jpeg_decode)
+    // JPEG: a colour frame's block-padded sample planes between jpeg_idct and jpeg_colour (launch_jpeg_decode) or jpeg_samples and jpeg_fdct (launch_jpeg_encode)
     DeviceBuf jpegPlanes;
     // dxtex_compress_many (host pointers): double-buffered pinned + device staging, copy streams on either side of ctx->stream
     struct Lane
@@ -2056,20 +2056,20 @@ namespace
 {
 static_assert(DXTEX_JPEG_GREY == JPEG_GREY && DXTEX_JPEG_YCBCR == JPEG_YCBCR && DXTEX_JPEG_RGB == JPEG_RGB, "dxtex_jpeg.h's colour kinds are the public ones");
 
-// The checks of the JPEG two, in the order include/dxtex_amd.h states. *f = the frame as the launcher takes it, *need = the bytes of its
-// coefficients, *rowBytes = a row of the image.
-dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst, JpegFrame* f, size_t* need,
-                         size_t* rowBytes)
+// The checks of the JPEG four, in the order include/dxtex_amd.h states; `image` is dst of a decode and src of an encode. *f = the frame as
+// the launchers take it, *need = the bytes of its coefficients, *rowBytes = a row of the image, *bgr = an encode's source has B before R.
+dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* image, bool encode, JpegFrame* f,
+                         size_t* need, size_t* rowBytes, bool* bgr = nullptr)
 {
     if (!ctx) return DXTEX_E_POINTER;
     if (!coefficients) return fail(ctx, DXTEX_E_POINTER, "null coefficients");
     if (!frame) return fail(ctx, DXTEX_E_POINTER, "null frame");
-    if (!dst) return fail(ctx, DXTEX_E_POINTER, "null image");
-    if (!dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!image) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!image->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
     if (frame->colour > DXTEX_JPEG_RGB) return fail(ctx, DXTEX_E_INVALIDARG, "unknown JPEG colour");
     if (frame->components != (frame->colour == DXTEX_JPEG_GREY ? 1u : 3u)) return fail(ctx, DXTEX_E_INVALIDARG, "the component count does not match the colour");
     if (!frame->width || !frame->height || frame->width > 65535u || frame->height > 65535u) return fail(ctx, DXTEX_E_INVALIDARG, "a JPEG frame is 1 to 65535 texels wide and high");
-    if (dst->width != frame->width || dst->height != frame->height) return fail(ctx, DXTEX_E_INVALIDARG, "the image is not the frame's size");
+    if (image->width != frame->width || image->height != frame->height) return fail(ctx, DXTEX_E_INVALIDARG, "the image is not the frame's size");
     if (reinterpret_cast<uintptr_t>(coefficients) & 1u) return fail(ctx, DXTEX_E_INVALIDARG, "coefficients at an odd address");
     for (uint32_t c = 0; c < frame->components; ++c)
     {
@@ -2077,14 +2077,18 @@ dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coeffi
         if (k.quant > 3u) return fail(ctx, DXTEX_E_INVALIDARG, "a quantiser index above 3");
         if (k.h < 1u || k.h > 4u || k.v < 1u || k.v > 4u) return fail(ctx, DXTEX_E_INVALIDARG, "sampling factors are 1 to 4");
     }
+    if (encode && frame->colour == DXTEX_JPEG_RGB) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "RGB-coded JPEG frames are not written");
     // sampling: luma 1x1, 2x1 or 2x2 over 1x1 chroma; grey 1x1
     const uint32_t hmax = frame->component[0].h, vmax = frame->component[0].v;
     bool sampling = (hmax == 1u && vmax == 1u) || (frame->components == 3u && hmax == 2u && vmax <= 2u);
     for (uint32_t c = 1; c < frame->components; ++c) sampling = sampling && frame->component[c].h == 1u && frame->component[c].v == 1u;
     if (!sampling) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "JPEG sampling other than 1x1, 2x1 or 2x2 luma over 1x1 chroma");
     const bool grey = frame->colour == DXTEX_JPEG_GREY;
-    if (grey ? dst->format != FMT_R8_UNORM : (dst->format != FMT_R8G8B8A8_UNORM && dst->format != FMT_R8G8B8A8_UNORM_SRGB))
-        return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this JPEG colour does not decode into this format");
+    const bool rgba = image->format == FMT_R8G8B8A8_UNORM || image->format == FMT_R8G8B8A8_UNORM_SRGB;
+    const bool bgrx = image->format == FMT_B8G8R8A8_UNORM || image->format == FMT_B8G8R8A8_UNORM_SRGB || image->format == FMT_B8G8R8X8_UNORM || image->format == FMT_B8G8R8X8_UNORM_SRGB;
+    if (grey ? image->format != FMT_R8_UNORM : !(rgba || (encode && bgrx)))
+        return fail(ctx, DXTEX_E_NOT_SUPPORTED, encode ? "this format does not encode as this JPEG colour" : "this JPEG colour does not decode into this format");
+    if (bgr) *bgr = bgrx;
     f->width = frame->width; f->height = frame->height; f->components = frame->components; f->colour = int(frame->colour);
     uint64_t at = 0;
     for (uint32_t c = 0; c < frame->components; ++c)
@@ -2095,11 +2099,14 @@ dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coeffi
         f->comp[c] = JpegComponent{ k.h, k.v, k.quant, k.blocksPerRow, k.blockRows, k.offset };
         at += uint64_t(k.blocksPerRow) * k.blockRows * 64u;
     }
+    for (uint32_t c = 0; encode && c < frame->components; ++c)
+        for (uint32_t k = 0; k < 64; ++k)
+            if (!frame->quant[frame->component[c].quant][k]) return fail(ctx, DXTEX_E_INVALIDARG, "a quantiser entry of 0");
     std::memcpy(f->quant, frame->quant, sizeof(f->quant));
     *need = size_t(at) * sizeof(int16_t);
     *rowBytes = size_t(frame->width) * (grey ? 1u : 4u);
     if (coefficientBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer bytes than the frame's coefficients");
-    return check_stream_image(ctx, "coefficients", coefficients, *need, dst, *rowBytes);
+    return check_stream_image(ctx, "coefficients", coefficients, *need, image, *rowBytes);
 }
 
 // both kernels on the context's stream, the planes in memory of the context
@@ -2114,7 +2121,7 @@ dxtex_hresult submit_jpeg(dxtex_ctx* ctx, const uint8_t* coefficients, const Jpe
 dxtex_hresult dxtex_jpeg_decode_device(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst)
 {
     JpegFrame f; size_t need, rowBytes;
-    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, &f, &need, &rowBytes);
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, false, &f, &need, &rowBytes);
     if (hr != DXTEX_S_OK) return hr;
     return run_timed(ctx, [&] { return submit_jpeg(ctx, static_cast<const uint8_t*>(coefficients), f, view_of(*dst)); });
 }
@@ -2122,7 +2129,7 @@ dxtex_hresult dxtex_jpeg_decode_device(dxtex_ctx* ctx, const void* coefficients,
 dxtex_hresult dxtex_jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst)
 {
     JpegFrame f; size_t need, rowBytes;
-    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, &f, &need, &rowBytes);
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, false, &f, &need, &rowBytes);
     if (hr != DXTEX_S_OK) return hr;
     {
         ScopedDevice sd(ctx->device);
@@ -2131,6 +2138,33 @@ dxtex_hresult dxtex_jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t
     }
     return run_staged_rows(ctx, coefficients, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
                            { return launch_jpeg_decode(reinterpret_cast<const int16_t*>(stream), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)); });
+}
+
+dxtex_hresult dxtex_jpeg_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes)
+{
+    JpegFrame f; size_t need, rowBytes; bool bgr;
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, src, true, &f, &need, &rowBytes, &bgr);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&]
+    {
+        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+        if (grown != DXTEX_S_OK) return grown;
+        return launched(ctx, launch_jpeg_encode(view_of(*src), bgr, f, static_cast<int16_t*>(coefficients), ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)));
+    });
+}
+
+dxtex_hresult dxtex_jpeg_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes)
+{
+    JpegFrame f; size_t need, rowBytes; bool bgr;
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, src, true, &f, &need, &rowBytes, &bgr);
+    if (hr != DXTEX_S_OK) return hr;
+    {
+        ScopedDevice sd(ctx->device);
+        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+        if (grown != DXTEX_S_OK) return grown;
+    }
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, coefficients, need, [&](uint8_t* in, uint8_t* out)
+                      { return launched(ctx, launch_jpeg_encode(view_of(with_pixels(*src, in)), bgr, f, reinterpret_cast<int16_t*>(out), ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx))); });
 }
 
 namespace

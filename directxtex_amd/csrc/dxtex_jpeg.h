@@ -125,4 +125,120 @@ DXTEX_FN constexpr uint32_t jpeg_texel(int colour, uint32_t a, uint32_t b, uint3
 DXTEX_FN constexpr uint32_t jpeg_padded_blocks(uint32_t extent, uint32_t factor, uint32_t maxFactor) { return (extent + 8u * maxFactor - 1u) / (8u * maxFactor) * factor; }
 // the component's own samples along one axis
 DXTEX_FN constexpr uint32_t jpeg_downsampled(uint32_t extent, uint32_t factor, uint32_t maxFactor) { return (extent * factor + maxFactor - 1u) / maxFactor; }
+
+// ---- The writer's direction (jpeg_encode.hip holds the kernels): what libjpeg does to a texel before its Huffman coder, which is the only
+// byte-serial part - jccolor.c, jcprepct.c's edge padding, jcsample.c without smoothing, jfdctint.c (JDCT_ISLOW), jcdctmgr.c's quantiser and
+// jccoefct.c's dummy blocks - for the kernels, the host saver and a host check (tests/cpp/jpeg_write_check.cpp). The coefficients come out
+// in the layout the reader takes.
+
+// jccolor.c: an R8G8B8A8 texel word (B8G8R8x8 with `bgr`) -> Y | Cb << 8 | Cr << 16. Alpha or X is ignored. No term is negative.
+DXTEX_FN constexpr uint32_t jpeg_ycc(uint32_t texel, bool bgr)
+{
+    const uint32_t r = (bgr ? texel >> 16 : texel) & 0xFFu, g = (texel >> 8) & 0xFFu, b = (bgr ? texel : texel >> 16) & 0xFFu;
+    const uint32_t y = (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16;
+    const uint32_t cb = ((128u << 16) + 32767u + 32768u * b - 11059u * r - 21709u * g) >> 16;
+    const uint32_t cr = ((128u << 16) + 32767u + 32768u * r - 27439u * g - 5329u * b) >> 16;
+    return y | (cb << 8) | (cr << 16);
+}
+
+// jcsample.c's rounding: 2 x 2 adds 1 to an even output column and 2 to an odd one, 2 x 1 adds 0 and 1
+DXTEX_FN constexpr uint32_t jpeg_downsample_bias(uint32_t vs, uint32_t cx) { return (vs == 2u ? 1u : 0u) + (cx & 1u); }
+
+// The image a frame is made from: R8_UNORM (grey) or one of the 32-bit colour formats, read through its pitch, never past width x height
+struct JpegSource
+{
+    const uint8_t* pixels;
+    uint64_t pitch;
+    uint32_t width, height;
+    bool grey, bgr;
+};
+
+// component c (0 Y, 1 Cb, 2 Cr; grey: the sample) of the texel at (x, y), both clamped to the image: jcprepct.c's edge replication
+DXTEX_FN uint32_t jpeg_source_sample(const JpegSource& s, uint32_t c, uint32_t x, uint32_t y)
+{
+    x = x < s.width ? x : s.width - 1u; y = y < s.height ? y : s.height - 1u;
+    const uint8_t* p = s.pixels + uint64_t(y) * s.pitch + uint64_t(x) * (s.grey ? 1u : 4u);
+    return s.grey ? p[0] : (jpeg_ycc(le_load32(p, 4), s.bgr) >> (8u * c)) & 0xFFu;
+}
+
+// The sample at (cx, cy) of component c's block-padded plane; hs and vs are the luma factors over this component's (1 x 1, 2 x 1 or 2 x 2).
+// A full-size component replicates the image's last column and row. A downsampled one averages hs x vs texels whose columns and rows are
+// clamped to the image, and past its own ceil(height / vs) rows it repeats its last ROW, not the image's: h2v2 of an image of odd
+// height + 1 rows differs from that.
+DXTEX_FN uint32_t jpeg_plane_sample(const JpegSource& s, uint32_t c, uint32_t hs, uint32_t vs, uint32_t cx, uint32_t cy)
+{
+    if (hs == 1u) return jpeg_source_sample(s, c, cx, cy);
+    const uint32_t dh = (s.height + vs - 1u) / vs;
+    cy = cy < dh ? cy : dh - 1u;
+    uint32_t sum = jpeg_downsample_bias(vs, cx);
+    for (uint32_t j = 0; j < vs; ++j)
+        for (uint32_t i = 0; i < 2u; ++i) sum += jpeg_source_sample(s, c, 2u * cx + i, vs * cy + j);
+    return sum >> vs;
+}
+
+// One pass of jfdctint.c (CONST_BITS 13, PASS1_BITS 2) over in[0..7]. Along a row (`rows`): outputs 0 and 4 are scaled up by PASS1_BITS, the
+// rest descaled by CONST_BITS - PASS1_BITS. Down a column: 0 and 4 are descaled by PASS1_BITS, the rest by CONST_BITS + PASS1_BITS. The
+// results are 8 times the DCT's; the quantiser divides that out.
+DXTEX_FN void jpeg_fdct_pass(const int32_t (&in)[8], int32_t (&out)[8], bool rows)
+{
+    const int32_t t0 = jpeg_add(in[0], in[7]), t7 = jpeg_sub(in[0], in[7]), t1 = jpeg_add(in[1], in[6]), t6 = jpeg_sub(in[1], in[6]);
+    const int32_t t2 = jpeg_add(in[2], in[5]), t5 = jpeg_sub(in[2], in[5]), t3 = jpeg_add(in[3], in[4]), t4 = jpeg_sub(in[3], in[4]);
+    const int32_t t10 = jpeg_add(t0, t3), t13 = jpeg_sub(t0, t3), t11 = jpeg_add(t1, t2), t12 = jpeg_sub(t1, t2);
+    const uint32_t shift = rows ? 11u : 15u;
+    out[0] = rows ? jpeg_shl(jpeg_add(t10, t11), 2) : jpeg_descale(jpeg_add(t10, t11), 2);
+    out[4] = rows ? jpeg_shl(jpeg_sub(t10, t11), 2) : jpeg_descale(jpeg_sub(t10, t11), 2);
+    int32_t z1 = jpeg_mul(jpeg_add(t12, t13), 4433);
+    out[2] = jpeg_descale(jpeg_add(z1, jpeg_mul(t13, 6270)), shift);
+    out[6] = jpeg_descale(jpeg_sub(z1, jpeg_mul(t12, 15137)), shift);
+    z1 = jpeg_add(t4, t7);
+    int32_t z2 = jpeg_add(t5, t6), z3 = jpeg_add(t4, t6), z4 = jpeg_add(t5, t7);
+    const int32_t z5 = jpeg_mul(jpeg_add(z3, z4), 9633);
+    const int32_t o4 = jpeg_mul(t4, 2446), o5 = jpeg_mul(t5, 16819), o6 = jpeg_mul(t6, 25172), o7 = jpeg_mul(t7, 12299);
+    z1 = jpeg_mul(z1, -7373); z2 = jpeg_mul(z2, -20995);
+    z3 = jpeg_add(jpeg_mul(z3, -16069), z5); z4 = jpeg_add(jpeg_mul(z4, -3196), z5);
+    out[7] = jpeg_descale(jpeg_add(o4, jpeg_add(z1, z3)), shift); out[5] = jpeg_descale(jpeg_add(o5, jpeg_add(z2, z4)), shift);
+    out[3] = jpeg_descale(jpeg_add(o6, jpeg_add(z2, z3)), shift); out[1] = jpeg_descale(jpeg_add(o7, jpeg_add(z1, z4)), shift);
+}
+
+// jcdctmgr.c: the transform's output over 8 * quant, rounded half away from zero. quant is 1 to 65535; the entry points refuse 0.
+DXTEX_FN constexpr int16_t jpeg_quantise(int32_t c, uint32_t quant)
+{
+    const uint32_t d = 8u * quant, a = c < 0 ? 0u - uint32_t(c) : uint32_t(c), r = (a + (d >> 1)) / d;
+    return int16_t(uint16_t(c < 0 ? 0u - r : r));
+}
+
+// a whole block: 8 rows of 8 samples `pitch` bytes apart and the component's table in natural order -> 64 quantised coefficients, natural order
+DXTEX_FN void jpeg_fdct_block(const uint8_t* samples, uint64_t pitch, const uint16_t* quant, int16_t* coefficients)
+{
+    int32_t ws[64];
+    for (uint32_t r = 0; r < 8; ++r)
+    {
+        int32_t in[8], out[8];
+        for (uint32_t c = 0; c < 8; ++c) in[c] = int32_t(samples[r * pitch + c]) - 128;
+        jpeg_fdct_pass(in, out, true);
+        for (uint32_t c = 0; c < 8; ++c) ws[r * 8 + c] = out[c];
+    }
+    for (uint32_t c = 0; c < 8; ++c)
+    {
+        int32_t in[8], out[8];
+        for (uint32_t r = 0; r < 8; ++r) in[r] = ws[r * 8 + c];
+        jpeg_fdct_pass(in, out, false);
+        for (uint32_t r = 0; r < 8; ++r) coefficients[r * 8 + c] = jpeg_quantise(out[r], quant[r * 8 + c]);
+    }
+}
+
+// jccoefct.c's dummy blocks. A component's plane is padded to whole MCUs, of which rw x rh blocks hold its own samples; h is its horizontal
+// factor. A block outside them has all AC zero and the DC of the block coded before it in its MCU: in a real row, the row's last real block;
+// in a dummy row, the last block of the MCU's row above - itself the last real block where that one is a dummy. True for a dummy, with
+// the block whose DC it takes.
+DXTEX_FN constexpr bool jpeg_dummy_block(uint32_t bx, uint32_t by, uint32_t rw, uint32_t rh, uint32_t h, uint32_t& sx, uint32_t& sy)
+{
+    if (by < rh && bx < rw) return false;
+    const uint32_t last = (bx / h) * h + h - 1u;
+    sx = by < rh || last > rw - 1u ? rw - 1u : last;
+    sy = by < rh ? by : rh - 1u;
+    return true;
+}
+// the blocks that hold a component's own samples along one axis
+DXTEX_FN constexpr uint32_t jpeg_real_blocks(uint32_t extent, uint32_t factor, uint32_t maxFactor) { return (jpeg_downsampled(extent, factor, maxFactor) + 7u) / 8u; }
 } // namespace dxtex

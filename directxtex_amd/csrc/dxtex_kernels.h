@@ -148,6 +148,10 @@ struct JpegComponent { uint32_t h, v, quant, blocksPerRow, blockRows; uint64_t o
 struct JpegFrame { uint32_t width, height, components; int colour; JpegComponent comp[3]; uint16_t quant[4][64]; };
 size_t jpeg_plane_bytes(const JpegFrame& frame);
 hipError_t launch_jpeg_decode(const int16_t* coefficients, const JpegFrame& frame, const ImgView& dst, uint8_t* planes, hipStream_t stream, KernelMarks* marks = nullptr);
+// The other direction (jpeg_encode.hip): src is R8_UNORM for a grey frame or a 32-bit colour format, B before R with `bgr`, for a YCbCr one.
+// jpeg_samples transforms, downsamples and pads a colour frame into the same planes, jpeg_fdct transforms and quantises every block of
+// every component in one launch into the reader's coefficient layout at `coefficients` (any even address). src is not written.
+hipError_t launch_jpeg_encode(const ImgView& src, bool bgr, const JpegFrame& frame, int16_t* coefficients, uint8_t* planes, hipStream_t stream, KernelMarks* marks = nullptr);
 
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for

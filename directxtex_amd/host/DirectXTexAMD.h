@@ -780,8 +780,8 @@ HRESULT UploadPNGRaw(Device& device, const TexMetadata& metadata, const PNGRawIm
 HRESULT SaveToPNGMemory(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept;
 HRESULT SaveToPNGFile(Device& device, const Image& deviceImage, PNG_FLAGS flags, const char* szFile) noexcept;
 
-// ---- JPEG, Auxiliary/DirectXTexJPEG.cpp (the reference's libjpeg codec), the reader: baseline, extended and progressive Huffman files of one
-// or three 8-bit components in; the writer is not built yet. No library is linked: the marker walk, the Huffman decoder and the four
+// ---- JPEG, Auxiliary/DirectXTexJPEG.cpp (the reference's libjpeg codec): baseline, extended and progressive Huffman files of one or three
+// 8-bit components in, the reference's baseline files out (below). No library is linked: the marker walk, the Huffman decoder and the four
 // progressive passes are this project's own code and end in the file's quantised coefficients; dequantisation, the inverse DCT, chroma
 // upsampling and YCbCr -> RGB are csrc/dxtex_jpeg.h's, which follow libjpeg's defaults (JDCT_ISLOW, fancy upsampling) as the reference leaves
 // them. Formats and metadata follow TranslateColor / GetMetadata: grey is R8_UNORM; colour is R8G8B8A8_UNORM_SRGB, or R8G8B8A8_UNORM under
@@ -798,8 +798,8 @@ HRESULT SaveToPNGFile(Device& device, const Image& deviceImage, PNG_FLAGS flags,
 //   3. A truncated or corrupt entropy segment is E_FAIL, where libjpeg pads with zeros and warns: data that end before the last MCU, a bad
 //      code, a wrong RSTn, a run past coefficient 63 (or past the band of a progressive scan), a missing EOI.
 //   4. EXIF orientation, thumbnails and ICC profiles are ignored, as libjpeg ignores them.
-// Out of scope: the writer (SaveToJPEGFile), arithmetic coding, 12-bit samples, sampling other than 4:4:4 / 4:2:2 / 4:2:0, incomplete
-// progressive files. -------------------------------------------------------------------------------------------------------------------------
+// Out of scope: arithmetic coding, 12-bit samples, sampling other than 4:4:4 / 4:2:2 / 4:2:0, incomplete progressive files; in the writer,
+// any quality but 100, any sampling but 4:2:0, optimised Huffman tables, progressive and RGB-coded files. -------------------------------------------------------------------------------------------------------------------------
 enum JPEG_FLAGS : uint32_t
 {
     JPEG_FLAGS_NONE = 0,
@@ -842,4 +842,22 @@ HRESULT LoadFromJPEGMemory(Device& device, const void* pSource, size_t size, JPE
 HRESULT LoadFromJPEGFile(Device& device, const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
 // the second half of the resident load, for a caller that parsed the file before it had a device
 HRESULT UploadJPEGRaw(Device& device, const TexMetadata& metadata, const JPEGRawImage& raw, DeviceScratchImage& image) noexcept;
+// The writer, JPEGCompress::WriteImage: what libjpeg writes after jpeg_set_defaults and jpeg_set_quality(100), byte for byte. R8_UNORM gives a
+// grey file of one 1 x 1 component; R8G8B8A8_UNORM[_SRGB], B8G8R8A8_UNORM[_SRGB] and B8G8R8X8_UNORM[_SRGB] give YCbCr at 4:2:0 in one interleaved
+// scan, alpha or X ignored; every other format is HRESULT_E_NOT_SUPPORTED. JFIF 1.01, quantiser tables of ones, the standard Huffman tables,
+// no restart intervals. A null file name is E_INVALIDARG, an image above 65535 texels a side E_INVALIDARG. `flags` changes nothing: _SRGB
+// formats give the bytes of their plain twins. The Memory forms are this project's addition. On failure the blob is empty.
+HRESULT SaveToJPEGMemory(const Image& image, JPEG_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToJPEGFile(const Image& image, JPEG_FLAGS flags, const char* szFile) noexcept;
+// The writer's byte-serial half, which needs no device: the markers, the tables and factors the components name (DQT entries of 8 bits where
+// all are at most 255, else 16 bits and SOF1), then baseline Huffman coding with the standard tables in MCU order - luma with tables 0,
+// chroma with tables 1. Grey and YCbCr frames laid out as LoadFromJPEGMemoryRaw returns them; DXTEX_JPEG_RGB is HRESULT_E_NOT_SUPPORTED, a
+// frame whose block counts or offsets are not its own or a quantiser entry of 0 E_INVALIDARG. E_FAIL where a DC difference needs more than 11
+// bits or an AC coefficient more than 10 (libjpeg's JERR_BAD_DCT_COEF), which no 8-bit image reaches.
+HRESULT SaveJPEGRaw(const JPEGRawImage& raw, Blob& blob) noexcept;
+// Resident forms: colour transform, downsampling, forward DCT and quantisation run on the device (dxtex_jpeg_encode_device) and the image
+// comes down as its coefficients - 2 bytes a texel for grey, 3 for colour - in one download; nothing goes up. Bytes and HRESULTs are
+// those of the host forms.
+HRESULT SaveToJPEGMemory(Device& device, const Image& deviceImage, JPEG_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToJPEGFile(Device& device, const Image& deviceImage, JPEG_FLAGS flags, const char* szFile) noexcept;
 } // namespace DirectXTexAMD

@@ -1,4 +1,4 @@
-// JPEG reader of the host layer. Behaviour follows Auxiliary/DirectXTexJPEG.cpp, the reference's codec over libjpeg with its defaults
+// JPEG reader and writer of the host layer (the writer begins at SaveJPEGRaw). Behaviour follows Auxiliary/DirectXTexJPEG.cpp, the reference's codec over libjpeg with its defaults
 // (JDCT_ISLOW, fancy upsampling); DirectXTexAMD.h states the four departures. No library is linked: the marker walk, the Huffman decoder and
 // the four passes of a progressive file are below. The yardstick is tests/jpeg_ref.py, a numpy restatement that reproduces libjpeg-turbo's
 // decode byte for byte.
@@ -11,6 +11,7 @@
 
 #include <cerrno>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -719,5 +720,305 @@ HRESULT LoadFromJPEGFile(Device& device, const char* szFile, JPEG_FLAGS flags, T
     const HRESULT hr = ReadJPEGFile(szFile, file);
     if (FAILED(hr)) return hr;
     return LoadFromJPEGMemory(device, file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+}
+
+// ---- the writer. The same split run backwards: SaveJPEGRaw is the byte-serial half - markers, tables, baseline Huffman coding of a frame's
+// quantised coefficients - and what makes the coefficients is dxtex_jpeg.h's, run here serially by the host forms and on the device
+// (dxtex_jpeg_encode_device) by the resident ones. The files are the reference's, which leaves libjpeg at jpeg_set_defaults and quality 100:
+// JFIF 1.01, quantiser tables of ones, the standard Huffman tables of Annex K.3 to K.6, grey as one 1 x 1 component, colour as 4:2:0 YCbCr
+// in one interleaved scan; tests/golden/jpeg_write holds libjpeg-turbo's own bytes. ------------------------------------------------------------
+namespace
+{
+    // Annex K.3 - K.6: the codes of each length and the symbols in code order; [0] luminance, [1] chrominance
+    const uint8_t kDcCounts[2][16] = { { 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0 }, { 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0 } };
+    const uint8_t kDcSymbols[12] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11 };
+    const uint8_t kAcCounts[2][16] = { { 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125 }, { 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119 } };
+    const uint8_t kAcSymbols[2][162] = {
+        { 0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xA1, 0x08, 0x23, 0x42, 0xB1,
+          0xC1, 0x15, 0x52, 0xD1, 0xF0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0A, 0x16, 0x17, 0x18, 0x19, 0x1A, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x34, 0x35, 0x36, 0x37,
+          0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6A,
+          0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A, 0xA2, 0xA3,
+          0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xD2, 0xD3,
+          0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE1, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF1, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA },
+        { 0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xA1, 0xB1, 0xC1,
+          0x09, 0x23, 0x33, 0x52, 0xF0, 0x15, 0x62, 0x72, 0xD1, 0x0A, 0x16, 0x24, 0x34, 0xE1, 0x25, 0xF1, 0x17, 0x18, 0x19, 0x1A, 0x26, 0x27, 0x28, 0x29, 0x2A, 0x35, 0x36,
+          0x37, 0x38, 0x39, 0x3A, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4A, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5A, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+          0x6A, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7A, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8A, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9A,
+          0xA2, 0xA3, 0xA4, 0xA5, 0xA6, 0xA7, 0xA8, 0xA9, 0xAA, 0xB2, 0xB3, 0xB4, 0xB5, 0xB6, 0xB7, 0xB8, 0xB9, 0xBA, 0xC2, 0xC3, 0xC4, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA,
+          0xD2, 0xD3, 0xD4, 0xD5, 0xD6, 0xD7, 0xD8, 0xD9, 0xDA, 0xE2, 0xE3, 0xE4, 0xE5, 0xE6, 0xE7, 0xE8, 0xE9, 0xEA, 0xF2, 0xF3, 0xF4, 0xF5, 0xF6, 0xF7, 0xF8, 0xF9, 0xFA } };
+
+    // a table as the coder reads it: the code and its length of every symbol (length 0: the table has no such symbol)
+    struct CodeTable { uint16_t code[256]; uint8_t length[256]; };
+    void BuildCodes(const uint8_t* counts, const uint8_t* symbols, CodeTable& t) noexcept
+    {
+        std::memset(&t, 0, sizeof(t));
+        uint32_t code = 0, k = 0;
+        for (uint32_t len = 1; len <= 16; ++len, code <<= 1)
+            for (uint32_t i = 0; i < counts[len - 1]; ++i, ++code, ++k) { t.code[symbols[k]] = uint16_t(code); t.length[symbols[k]] = uint8_t(len); }
+    }
+
+    // The file as it grows: bytes on the heap, and the entropy coder's bits with their 0xFF stuffing. A failed allocation is remembered and
+    // everything after it dropped; the caller asks once at the end.
+    struct Writer
+    {
+        uint8_t* data = nullptr; size_t size = 0, capacity = 0; bool failed = false;
+        uint64_t acc = 0; uint32_t bits = 0;
+        ~Writer() { std::free(data); }
+        bool Reserve(size_t more) noexcept
+        {
+            if (failed) return false;
+            if (size + more <= capacity) return true;
+            const size_t want = (capacity * 2 > size + more ? capacity * 2 : size + more) + 4096;
+            uint8_t* grown = static_cast<uint8_t*>(std::realloc(data, want));
+            if (!grown) { failed = true; return false; }
+            data = grown; capacity = want;
+            return true;
+        }
+        void Byte(uint32_t b) noexcept { if (Reserve(1)) data[size++] = uint8_t(b); }
+        void Word(uint32_t w) noexcept { Byte(w >> 8); Byte(w & 0xFFu); }
+        void Bytes(const uint8_t* p, size_t n) noexcept { if (Reserve(n)) { std::memcpy(data + size, p, n); size += n; } }
+        void Marker(uint32_t m, size_t bodyBytes) noexcept { Byte(0xFF); Byte(m); Word(uint32_t(bodyBytes + 2)); }
+        // n <= 16 bits, the value's low n
+        void Put(uint32_t value, uint32_t n) noexcept
+        {
+            acc = (acc << n) | (value & ((1u << n) - 1u)); bits += n;
+            if (bits < 8) return;
+            if (!Reserve(2 * (bits / 8))) { bits &= 7u; return; }
+            while (bits >= 8)
+            {
+                const uint8_t b = uint8_t(acc >> (bits - 8));
+                data[size++] = b;
+                if (b == 0xFF) data[size++] = 0;
+                bits -= 8;
+            }
+        }
+        void Flush() noexcept { if (bits) Put(0x7Fu, 8u - bits); }          // the last byte is padded with 1-bits
+    };
+
+    inline uint32_t BitsOf(uint32_t magnitude) noexcept { uint32_t n = 0; while (magnitude) { ++n; magnitude >>= 1; } return n; }
+
+    // encode_one_block of jchuff.c: false where a DC difference needs more than 11 bits or an AC value more than 10 (JERR_BAD_DCT_COEF)
+    bool EncodeBlock(Writer& w, const int16_t* block, int32_t& predictor, const CodeTable& dc, const CodeTable& ac) noexcept
+    {
+        const int32_t diff = int32_t(block[0]) - predictor;
+        predictor = block[0];
+        uint32_t n = BitsOf(uint32_t(diff < 0 ? -diff : diff));
+        if (n > 11) return false;
+        w.Put(dc.code[n], dc.length[n]);
+        if (n) w.Put(uint32_t(diff < 0 ? diff - 1 : diff), n);
+        uint32_t run = 0;
+        for (uint32_t k = 1; k < 64; ++k)
+        {
+            const int32_t v = block[dxtex::kJpegNatural[k]];
+            if (!v) { ++run; continue; }
+            for (; run > 15; run -= 16) w.Put(ac.code[0xF0], ac.length[0xF0]);
+            n = BitsOf(uint32_t(v < 0 ? -v : v));
+            if (n > 10) return false;
+            w.Put(ac.code[(run << 4) | n], ac.length[(run << 4) | n]);
+            w.Put(uint32_t(v < 0 ? v - 1 : v), n);
+            run = 0;
+        }
+        if (run) w.Put(ac.code[0], ac.length[0]);
+        return true;
+    }
+
+    // the frame of an image as the reference writes it: quality 100, grey 1 x 1, colour 2 x 2 luma over 1 x 1 chroma
+    HRESULT FrameFor(const Image& image, dxtex_jpeg_frame& f) noexcept
+    {
+        if (!image.pixels) return E_POINTER;
+        bool grey = false;
+        switch (image.format)
+        {
+        case DXGI_FORMAT_R8_UNORM: grey = true; break;
+        case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB:
+        case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: break;
+        default: return HRESULT_E_NOT_SUPPORTED;
+        }
+        if (!image.width || !image.height || image.width > 65535 || image.height > 65535) return E_INVALIDARG;          // SOF0 holds 16 bits
+        f = dxtex_jpeg_frame();
+        f.width = uint32_t(image.width); f.height = uint32_t(image.height);
+        f.components = grey ? 1u : 3u; f.colour = grey ? DXTEX_JPEG_GREY : DXTEX_JPEG_YCBCR;
+        const uint32_t hmax = grey ? 1u : 2u, vmax = hmax;
+        uint64_t at = 0;
+        for (uint32_t c = 0; c < f.components; ++c)
+        {
+            dxtex_jpeg_component& k = f.component[c];
+            k.h = c ? 1u : hmax; k.v = c ? 1u : vmax; k.quant = c ? 1u : 0u;
+            k.blocksPerRow = dxtex::jpeg_padded_blocks(f.width, k.h, hmax); k.blockRows = dxtex::jpeg_padded_blocks(f.height, k.v, vmax);
+            k.offset = at;
+            at += uint64_t(k.blocksPerRow) * k.blockRows * 64u;
+        }
+        for (uint32_t t = 0; t < 2; ++t) for (uint32_t k = 0; k < 64; ++k) f.quant[t][k] = 1;
+        return S_OK;
+    }
+
+    // `raw` takes the frame and `coefficientCount` coefficients of storage of its own
+    HRESULT RawFor(const dxtex_jpeg_frame& f, JPEGRawImage& raw) noexcept
+    {
+        raw.Release();
+        size_t count = 0;
+        for (uint32_t c = 0; c < f.components; ++c) count += size_t(f.component[c].blocksPerRow) * f.component[c].blockRows * 64u;
+        const HRESULT hr = raw.storage.Initialize(count * sizeof(int16_t));
+        if (FAILED(hr)) return hr;
+        raw.width = f.width; raw.height = f.height; raw.components = f.components; raw.colour = f.colour;
+        for (uint32_t c = 0; c < f.components; ++c)
+        {
+            const dxtex_jpeg_component& k = f.component[c];
+            JPEGRawImage::Component& o = raw.component[c];
+            o.h = k.h; o.v = k.v; o.quant = k.quant; o.blocksPerRow = k.blocksPerRow; o.blockRows = k.blockRows; o.offset = size_t(k.offset);
+        }
+        std::memcpy(raw.quant, f.quant, sizeof(raw.quant));
+        raw.coefficients = reinterpret_cast<const int16_t*>(raw.storage.GetBufferPointer());
+        raw.coefficientCount = count;
+        return S_OK;
+    }
+}
+
+HRESULT SaveJPEGRaw(const JPEGRawImage& raw, Blob& blob) noexcept
+{
+    blob.Release();
+    if (!raw.coefficients || !raw.width || !raw.height || raw.width > 65535u || raw.height > 65535u) return E_INVALIDARG;
+    if (raw.components != (raw.colour == DXTEX_JPEG_GREY ? 1u : 3u) || raw.colour > DXTEX_JPEG_YCBCR) return raw.colour == DXTEX_JPEG_RGB ? HRESULT_E_NOT_SUPPORTED : E_INVALIDARG;
+    const uint32_t hmax = raw.component[0].h, vmax = raw.component[0].v;
+    size_t count = 0;
+    bool wide = false;          // a table with an entry above 255 is written with 16-bit entries, and the frame as SOF1: baseline has none
+    for (uint32_t c = 0; c < raw.components; ++c)
+    {
+        const JPEGRawImage::Component& k = raw.component[c];
+        if (k.quant > 3u || k.h < 1u || k.h > 4u || k.v < 1u || k.v > 4u || k.h > hmax || k.v > vmax || hmax % k.h || vmax % k.v) return E_INVALIDARG;
+        if (k.blocksPerRow != dxtex::jpeg_padded_blocks(raw.width, k.h, hmax) || k.blockRows != dxtex::jpeg_padded_blocks(raw.height, k.v, vmax) || k.offset != count) return E_INVALIDARG;
+        count += size_t(k.blocksPerRow) * k.blockRows * 64u;
+        for (uint32_t i = 0; i < 64; ++i) { if (!raw.quant[k.quant][i]) return E_INVALIDARG; wide = wide || raw.quant[k.quant][i] > 255u; }
+    }
+    if (raw.coefficientCount < count) return E_INVALIDARG;
+
+    Writer w;
+    w.Byte(0xFF); w.Byte(0xD8);
+    static const uint8_t jfif[14] = { 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0 };
+    w.Marker(0xE0, sizeof(jfif)); w.Bytes(jfif, sizeof(jfif));
+    bool sent[4] = {};
+    for (uint32_t c = 0; c < raw.components; ++c)
+    {
+        const uint32_t t = raw.component[c].quant;
+        if (sent[t]) continue;
+        sent[t] = true;
+        bool wideTable = false;
+        for (uint32_t i = 0; i < 64; ++i) wideTable = wideTable || raw.quant[t][i] > 255u;
+        w.Marker(0xDB, wideTable ? 129 : 65); w.Byte((wideTable ? 0x10u : 0u) | t);
+        for (uint32_t i = 0; i < 64; ++i) { const uint32_t q = raw.quant[t][dxtex::kJpegNatural[i]]; if (wideTable) w.Word(q); else w.Byte(q); }
+    }
+    w.Marker(wide ? 0xC1 : 0xC0, 6 + 3 * raw.components);
+    w.Byte(8); w.Word(raw.height); w.Word(raw.width); w.Byte(raw.components);
+    for (uint32_t c = 0; c < raw.components; ++c) { w.Byte(c + 1); w.Byte((raw.component[c].h << 4) | raw.component[c].v); w.Byte(raw.component[c].quant); }
+    // luma codes with tables 0, chroma with tables 1
+    std::unique_ptr<CodeTable[]> codes(new (std::nothrow) CodeTable[4]);
+    if (!codes) return E_OUTOFMEMORY;
+    for (uint32_t t = 0; t < (raw.components == 1 ? 1u : 2u); ++t)
+    {
+        w.Marker(0xC4, 17 + 12); w.Byte(t); w.Bytes(kDcCounts[t], 16); w.Bytes(kDcSymbols, 12);
+        w.Marker(0xC4, 17 + 162); w.Byte(0x10u | t); w.Bytes(kAcCounts[t], 16); w.Bytes(kAcSymbols[t], 162);
+        BuildCodes(kDcCounts[t], kDcSymbols, codes[2 * t]);
+        BuildCodes(kAcCounts[t], kAcSymbols[t], codes[2 * t + 1]);
+    }
+    w.Marker(0xDA, 4 + 2 * raw.components); w.Byte(raw.components);
+    for (uint32_t c = 0; c < raw.components; ++c) { w.Byte(c + 1); w.Byte(c ? 0x11 : 0x00); }
+    w.Byte(0); w.Byte(63); w.Byte(0);
+    // one scan: a grey frame's blocks in raster order, a colour frame's MCU by MCU, each component's h x v blocks in raster order
+    int32_t predictor[3] = {};
+    const uint32_t mcusAcross = raw.component[0].blocksPerRow / hmax, mcusDown = raw.component[0].blockRows / vmax;
+    for (uint32_t my = 0; my < mcusDown; ++my)
+        for (uint32_t mx = 0; mx < mcusAcross; ++mx)
+            for (uint32_t c = 0; c < raw.components; ++c)
+            {
+                const JPEGRawImage::Component& k = raw.component[c];
+                for (uint32_t v = 0; v < k.v; ++v)
+                    for (uint32_t h = 0; h < k.h; ++h)
+                    {
+                        const int16_t* block = raw.coefficients + k.offset + (size_t(my * k.v + v) * k.blocksPerRow + (mx * k.h + h)) * 64u;
+                        if (!EncodeBlock(w, block, predictor[c], codes[c ? 2 : 0], codes[c ? 3 : 1])) return E_FAIL;
+                    }
+            }
+    w.Flush();
+    w.Byte(0xFF); w.Byte(0xD9);
+    if (w.failed) return E_OUTOFMEMORY;
+    const HRESULT hr = blob.Initialize(w.size);
+    if (FAILED(hr)) return hr;
+    std::memcpy(blob.GetBufferPointer(), w.data, w.size);
+    return S_OK;
+}
+
+HRESULT SaveToJPEGMemory(const Image& image, JPEG_FLAGS, Blob& blob) noexcept
+{
+    blob.Release();          // on any failure the result is empty
+    dxtex_jpeg_frame f;
+    HRESULT hr = FrameFor(image, f);
+    if (FAILED(hr)) return hr;
+    const size_t texel = f.components == 1 ? 1u : 4u;
+    if (image.rowPitch < image.width * texel) return E_INVALIDARG;
+    JPEGRawImage raw;
+    hr = RawFor(f, raw);
+    if (FAILED(hr)) return hr;
+    const bool bgr = image.format != DXGI_FORMAT_R8G8B8A8_UNORM && image.format != DXGI_FORMAT_R8G8B8A8_UNORM_SRGB;
+    const dxtex::JpegSource source = { image.pixels, image.rowPitch, f.width, f.height, f.components == 1, bgr };
+    int16_t* coefficients = reinterpret_cast<int16_t*>(raw.storage.GetBufferPointer());
+    const uint32_t hmax = f.component[0].h, vmax = f.component[0].v;
+    for (uint32_t c = 0; c < f.components; ++c)
+    {
+        const dxtex_jpeg_component& k = f.component[c];
+        const uint32_t rw = dxtex::jpeg_real_blocks(f.width, k.h, hmax), rh = dxtex::jpeg_real_blocks(f.height, k.v, vmax);
+        for (uint32_t by = 0; by < k.blockRows; ++by)
+            for (uint32_t bx = 0; bx < k.blocksPerRow; ++bx)
+            {
+                uint32_t sx = bx, sy = by;
+                const bool dummy = dxtex::jpeg_dummy_block(bx, by, rw, rh, k.h, sx, sy);
+                uint8_t samples[64];
+                for (uint32_t y = 0; y < 8; ++y)
+                    for (uint32_t x = 0; x < 8; ++x) samples[y * 8 + x] = uint8_t(dxtex::jpeg_plane_sample(source, c, hmax / k.h, vmax / k.v, sx * 8 + x, sy * 8 + y));
+                int16_t* out = coefficients + k.offset + (size_t(by) * k.blocksPerRow + bx) * 64u;
+                dxtex::jpeg_fdct_block(samples, 8, f.quant[k.quant], out);
+                if (dummy) std::memset(out + 1, 0, 63 * sizeof(int16_t));
+            }
+    }
+    return SaveJPEGRaw(raw, blob);
+}
+
+HRESULT SaveToJPEGFile(const Image& image, JPEG_FLAGS flags, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveToJPEGMemory(image, flags, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+}
+
+// ---- resident forms: both kernels run on the device image, the coefficients come down once - 2 bytes a texel for grey, 3 for colour - and
+// nothing goes up ------------------------------------------------------------------------------------------------------------------------------
+HRESULT SaveToJPEGMemory(Device& device, const Image& deviceImage, JPEG_FLAGS, Blob& blob) noexcept
+{
+    blob.Release();
+    dxtex_jpeg_frame f;
+    HRESULT hr = FrameFor(deviceImage, f);
+    if (FAILED(hr)) return hr;
+    if (!device) return E_POINTER;
+    JPEGRawImage raw;
+    hr = RawFor(f, raw);
+    if (FAILED(hr)) return hr;
+    const size_t bytes = raw.coefficientCount * sizeof(int16_t);
+    DeviceTemp temp(device);
+    hr = dxtex_device_alloc(device.Get(), bytes, &temp.p);
+    if (SUCCEEDED(hr))
+    {
+        const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
+        hr = dxtex_jpeg_encode_device(device.Get(), &s, &f, temp.p, bytes);
+    }
+    if (SUCCEEDED(hr)) hr = dxtex_memcpy_d2h(device.Get(), raw.storage.GetBufferPointer(), temp.p, bytes);          // returns when the coefficients have landed
+    return FAILED(hr) ? hr : SaveJPEGRaw(raw, blob);
+}
+
+HRESULT SaveToJPEGFile(Device& device, const Image& deviceImage, JPEG_FLAGS flags, const char* szFile) noexcept
+{
+    if (!szFile) return E_INVALIDARG;
+    Blob blob;
+    const HRESULT hr = SaveToJPEGMemory(device, deviceImage, flags, blob);
+    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
 }
 } // namespace DirectXTexAMD

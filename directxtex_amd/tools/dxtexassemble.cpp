@@ -1,5 +1,5 @@
-// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG and JPEG in; DDS out (TGA / HDR
-// too for the single-image results). Every input is loaded on the host, checked, uploaded ONCE, run through texassemble's per-input
+// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG and JPEG in; DDS out (TGA / HDR /
+// PNG / JPEG too for the single-image results). Every input is loaded on the host, checked, uploaded ONCE, run through texassemble's per-input
 // pipeline on the device (decompress, -stripmips, -alpha, resize, -tonemap, convert), assembled there - every face, slice, item or mip a
 // rectangle of one batched copy_rect launch - and the result is downloaded once.
 //
@@ -273,9 +273,9 @@ int Parse(int argc, char** argv, Options& o)
     }
     if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     const bool single = IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP || o.command == CMD_MERGE;
-    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr") || hasExt(o.output, ".png"))))
+    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr") || hasExt(o.output, ".png") || hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg"))))
     {
-        std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga, .hdr or .png" : "");
+        std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga, .hdr, .png or .jpg" : "");
         return 1;
     }
     return 0;
@@ -547,6 +547,7 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     if (hdrOut) hr = SaveToHDRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());
     else if (tgaOut) hr = SaveToTGAFile(dev, *result.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
     else if (hasExt(o.output, ".png")) hr = SaveToPNGFile(dev, *result.GetImage(0, 0, 0), PNG_FLAGS_NONE, o.output.c_str());          // the file's rows, likewise
+    else if (hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg")) hr = SaveToJPEGFile(dev, *result.GetImage(0, 0, 0), JPEG_FLAGS_NONE, o.output.c_str());          // the coefficients
     else hr = SaveToDDSFile(dev, result.GetImages(), result.GetImageCount(), result.GetMetadata(),
                             o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED", hr);

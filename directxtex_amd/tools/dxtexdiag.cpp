@@ -4,7 +4,7 @@
 //                                                  also get the block-mode histogram (texdiag's print layout, :681-695, :795-856)
 //   dxtexdiag compare [options] <a> <b>            "Result: mse (r g b a) PSNR x dB" with 10 * log10(3 / (r + g + b)); when both files hold
 //                                                  the same number of mips, items and slices, every image and the minimum / average / maximum
-//   dxtexdiag diff [options] <a> <b> -o <out.dds|.tga|.hdr|.png>     the difference map of the first images
+//   dxtexdiag diff [options] <a> <b> -o <out.dds|.tga|.hdr|.png|.jpg>     the difference map of the first images
 //
 //   -f <format>   diff: format of the map (default B8G8R8A8_UNORM)     -c <hex>   diff: colour 0xRRGGBB for texels over the threshold (masked to 24 bits)
 //   -t <float>    diff: threshold (default 0.25)                        -if <filter>  image filter for diff's conversions
@@ -80,7 +80,7 @@ int usage()
 {
     std::fprintf(stderr, "usage: dxtexdiag analyze [options] <files>\n"
                          "       dxtexdiag compare [options] <file1> <file2>\n"
-                         "       dxtexdiag diff [options] <file1> <file2> -o <out.dds | out.tga | out.hdr | out.png>\n"
+                         "       dxtexdiag diff [options] <file1> <file2> -o <out.dds | out.tga | out.hdr | out.png | out.jpg>\n"
                          "options: -f <format> -if <filter> -c <hex colour> -t <threshold> -o <file> -y -l -nologo -timing -gpu <n>\n"
                          "         -dword -badtails -permissive -ignoremips -xlum\n");
     return 1;
@@ -150,11 +150,11 @@ bool Parse(int argc, char** argv, Options& o)
     if (o.command != "analyze" && o.files.size() != 2) { std::fprintf(stderr, "%s wants exactly two files\n", o.command.c_str()); return false; }
     if (o.command == "diff")
     {
-        if (o.output.empty()) { std::fprintf(stderr, "diff wants -o <out.dds | out.tga | out.hdr | out.png>\n"); return false; }
+        if (o.output.empty()) { std::fprintf(stderr, "diff wants -o <out.dds | out.tga | out.hdr | out.png | out.jpg>\n"); return false; }
         if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
-        if (!hasExt(o.output, ".dds") && !hasExt(o.output, ".tga") && !hasExt(o.output, ".hdr") && !hasExt(o.output, ".png"))
+        if (!hasExt(o.output, ".dds") && !hasExt(o.output, ".tga") && !hasExt(o.output, ".hdr") && !hasExt(o.output, ".png") && !hasExt(o.output, ".jpg") && !hasExt(o.output, ".jpeg"))
         {
-            std::fprintf(stderr, "the output file must be .dds, .tga or .hdr, or .png\n");
+            std::fprintf(stderr, "the output file must be .dds, .tga or .hdr, or .png or .jpg\n");
             return false;
         }
         struct stat st;
@@ -387,7 +387,8 @@ int RunDiff(Device& dev, const Options& o)
         const Image* out = map.GetImage(0, 0, 0);
         if (!out) return Fail("Failed diffing images", E_POINTER);
         hr = hasExt(o.output, ".tga") ? SaveToTGAFile(dev, *out, TGA_FLAGS_NONE, o.output.c_str())
-           : hasExt(o.output, ".png") ? SaveToPNGFile(dev, *out, PNG_FLAGS_NONE, o.output.c_str()) : SaveToDDSFile(dev, *out, DDS_FLAGS_NONE, o.output.c_str());
+           : hasExt(o.output, ".png") ? SaveToPNGFile(dev, *out, PNG_FLAGS_NONE, o.output.c_str())
+           : (hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg")) ? SaveToJPEGFile(dev, *out, JPEG_FLAGS_NONE, o.output.c_str()) : SaveToDDSFile(dev, *out, DDS_FLAGS_NONE, o.output.c_str());
     }
     else
     {

@@ -43,6 +43,8 @@
  *     per-texel transforms                       :126-225, :315-404
  *   LoadFromJPEGFile behind the Huffman walk:   Auxiliary/DirectXTexJPEG.cpp    dxtex_jpeg_decode
  *     libjpeg's jidctint.c, jdsample.c, jdcolor.c  :184-238
+ *   SaveToJPEGFile in front of the Huffman coder: Auxiliary/DirectXTexJPEG.cpp    dxtex_jpeg_encode
+ *     libjpeg's jccolor.c, jcsample.c, jfdctint.c  :240-300
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -541,6 +543,25 @@ dxtex_hresult dxtex_jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t
 /* device pointers (the frame stays a host pointer, read before the call returns): asynchronous on the context's stream. The coefficients
  * may start at any even byte; see csrc/jpeg.hip for the alignments that take 16-byte loads and the wide route of jpeg_colour. */
 dxtex_hresult dxtex_jpeg_decode_device(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst);
+/* The other direction: everything in front of the Huffman coder, which stays with the caller. The call runs libjpeg's RGB -> YCbCr
+ * (jccolor.c), its edge replication (jcprepct.c), its 2x1 / 2x2 chroma average without smoothing (jcsample.c), its JDCT_ISLOW forward DCT
+ * (jfdctint.c), its quantiser (jcdctmgr.c: the value over 8 * entry, rounded half away from zero) and its dummy blocks (jccoefct.c: all AC
+ * zero, the DC of the block coded before) and writes the frame's coefficients in the layout above:
+ *   colour             components   sampling (luma over 1x1 chroma)   src->format
+ *   DXTEX_JPEG_GREY    1            1x1                               R8_UNORM
+ *   DXTEX_JPEG_YCBCR   3            1x1, 2x1, 2x2                     R8G8B8A8_UNORM[_SRGB], B8G8R8A8_UNORM[_SRGB], B8G8R8X8_UNORM[_SRGB]
+ * Alpha or X is ignored. The quantiser entries are the frame's own, 1 to 65535. Arithmetic is 32-bit, that of csrc/dxtex_jpeg.h on the host.
+ * HRESULTs, in dxtex_jpeg_decode's order: E_POINTER for null coefficients, frame, image or pixels; E_INVALIDARG for an unknown colour, a
+ * component count that does not match it, a width or height of 0 or above 65535, an image that is not the frame's size, coefficients at an
+ * odd address, a quantiser index above 3 or a sampling factor outside 1..4; NOT_SUPPORTED for DXTEX_JPEG_RGB, sampling outside the table
+ * or a format that does not pair with the colour; E_INVALIDARG for block counts or offsets that are not the frame's, an entry of 0 in a
+ * quantiser table a component names, fewer coefficient bytes than the frame takes, a row pitch smaller than the row, or coefficients that
+ * overlap the pixels. Bytes behind the frame's coefficients are not written; the image is not written. */
+/* host pointers, through the context's staging: the image's rows go up, the coefficients come down */
+dxtex_hresult dxtex_jpeg_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes);
+/* device pointers (the frame stays a host pointer, read before the call returns): asynchronous on the context's stream. The coefficients
+ * may start at any even byte; see csrc/jpeg_encode.hip for the alignments that take 16-byte stores and the wide route of jpeg_samples. */
+dxtex_hresult dxtex_jpeg_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);

@@ -8,7 +8,12 @@ End to end, on the two files named (4096^2, quality 90; where Pillow is installe
 directory): `dxtexconv -nologo -timing -overlap 1 -y` to -f R8G8B8A8_UNORM -m 1 and to -f BC1_UNORM with the full chain, one unmeasured run
 and five measured ones each; the Huffman walk alone (jpeg_host_test time_raw); and the load through the API (jpeg_host_test time_load): the
 resident loader against this build's host loader plus Upload, alternating. The parent commit cannot read the files, so that host path is the
-only comparison there is."""
+only comparison there is.
+
+The writer (--skip-encode leaves it out): one 4096 x 4096 image of noise through dxtex_jpeg_encode_device as grey, 4:2:0 and 4:4:4, measured
+as the reader's kernels are, with quantiser tables of ones (the writer's) and of 8; then SaveToJPEGMemory on a resident 4096^2 image against
+Download plus this build's host saver, alternating, and SaveJPEGRaw alone on the same coefficients (jpeg_write_host_test time_save). The
+parent commit cannot write a .jpg, so that host path is again the only comparison."""
 import argparse, json, os, re, statistics, subprocess, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -57,6 +62,53 @@ def kernels():
     print(json.dumps({"case": "png_unpack<wide> RGB 8 -> R8G8B8A8, the same size", "png_unpack<wide> ms": round(ms / n, 4), "TBps": round(N * N * 7 / (ms / n * 1e-3) / 1e12, 3)}), flush=True)
     ctx.device_free(coef); ctx.device_free(image)
     ctx.close()
+
+
+def encode_kernels():
+    ctx = dx.Context(0)
+    coef = ctx.device_alloc(N * N * 6)
+    image = ctx.device_alloc(N * N * 4)
+    rng = np.random.default_rng(2)
+    chunk = rng.integers(0, 256, N * N // 2, dtype=np.uint8)
+    for at in range(0, N * N * 4, chunk.nbytes):
+        ctx.upload(image + at, chunk, sync=True)
+    img = dx.device_image
+    # bytes a texel: (samples reads + writes, fdct reads + writes)
+    cases = [("R8G8B8A8 -> 4:2:0", (2, 2), RGBA8, (4 + 1.5, 1.5 + 3)), ("R8G8B8A8 -> 4:4:4", (1, 1), RGBA8, (4 + 3, 3 + 6)), ("R8 -> grey", None, R8, (0, 1 + 2))]
+    for q in (1, 8):
+        quant = np.full((4, 64), q, np.uint16)
+        for what, sampling, fmt, moved in cases:
+            frame = dx.jpeg_frame(N, N, dx.JPEG_GREY if sampling is None else dx.JPEG_YCBCR, sampling or (1, 1), quant)
+            call = lambda: ctx.jpeg_encode_device(img(image, N, N, fmt), frame, coef, dx.jpeg_coefficient_count(frame) * 2)
+            for _ in range(3):
+                call()
+            ctx.synchronize()
+            ctx.profile_begin()
+            for _ in range(REPS):
+                call()
+            prof = ctx.profile_end()
+            row = {"case": what, "quantiser entries": q}
+            for k, (ms, n) in sorted(prof.items(), key=lambda kv: kv[0] == "jpeg_fdct"):
+                b = moved[k == "jpeg_fdct"]
+                row[k + " ms"] = round(ms / n, 4)
+                row[k + " TBps"] = round(N * N * b / (ms / n * 1e-3) / 1e12, 3)
+            print(json.dumps(row), flush=True)
+    ctx.device_free(coef); ctx.device_free(image)
+    ctx.close()
+
+
+def save_end_to_end():
+    exe = os.path.join(os.path.dirname(dx.library_path()), "jpeg_write_host_test")
+    for name, fmt in (("R8_UNORM -> grey", R8), ("R8G8B8A8_UNORM -> 4:2:0", RGBA8)):
+        r = subprocess.run([exe, "time_save", str(N), str(N), str(fmt), str(RUNS)], capture_output=True, text=True, check=True)
+        rows = re.findall(r"resident ([0-9.]+) ms up (\d+) down (\d+) host ([0-9.]+) ms up (\d+) down (\d+) file (\d+)", r.stdout)
+        raw = [float(v) for v in re.findall(r"raw ([0-9.]+) ms", r.stdout)]
+        assert len(rows) == RUNS and len(raw) == RUNS, r.stdout + r.stderr
+        res, host = [float(x[0]) for x in rows], [float(x[3]) for x in rows]
+        print(json.dumps({"case": name + ": SaveToJPEGMemory through the API", "file bytes": int(rows[0][6]), "resident ms": res, "resident median": statistics.median(res),
+                          "resident up/down": [int(rows[0][1]), int(rows[0][2])], "Download + host saver ms": host, "host path median": statistics.median(host),
+                          "host path up/down": [int(rows[0][4]), int(rows[0][5])], "SaveJPEGRaw alone ms": raw, "SaveJPEGRaw median": statistics.median(raw),
+                          "share of the resident save in the Huffman coder": round(statistics.median(raw) / statistics.median(res), 3)}), flush=True)
 
 
 def write_files(tmp):
@@ -108,11 +160,15 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-kernels", action="store_true")
     ap.add_argument("--skip-end-to-end", action="store_true")
+    ap.add_argument("--skip-encode", action="store_true")
     ap.add_argument("--c420")
     ap.add_argument("--c444")
     a = ap.parse_args()
     if not a.skip_kernels:
         kernels()
+    if not a.skip_encode:
+        encode_kernels()
+        save_end_to_end()
     if not a.skip_end_to_end:
         with tempfile.TemporaryDirectory() as tmp:
             end_to_end({"c420": a.c420, "c444": a.c444} if a.c420 and a.c444 else write_files(tmp), tmp)
