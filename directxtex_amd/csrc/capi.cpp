@@ -1543,12 +1543,11 @@ dxtex_hresult check_rgbe(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_ima
     if (!src->pixels || !dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
     const dxtex_image& rgbe = decode ? *src : *dst;
     const dxtex_image& flt = decode ? *dst : *src;
-    const bool floatOk = flt.format == FMT_R32G32B32A32_FLOAT || (!decode && (flt.format == FMT_R32G32B32_FLOAT || flt.format == FMT_R16G16B16A16_FLOAT));
-    if (rgbe.format != FMT_R8G8B8A8_UINT || !floatOk)
+    const size_t floatBytes = rgbe_source_bytes(flt.format);
+    if (rgbe.format != FMT_R8G8B8A8_UINT || !(decode ? flt.format == FMT_R32G32B32A32_FLOAT : floatBytes != 0))
         return fail(ctx, DXTEX_E_NOT_SUPPORTED, decode ? "RGBE decode is R8G8B8A8_UINT to R32G32B32A32_FLOAT" : "RGBE encode is R32G32B32A32_FLOAT, R32G32B32_FLOAT or R16G16B16A16_FLOAT to R8G8B8A8_UINT");
     if (src->width != dst->width || src->height != dst->height) return fail(ctx, DXTEX_E_FAIL, "size mismatch");
     if (src->width > 0xFFFFFFFFull || src->height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
-    const size_t floatBytes = flt.format == FMT_R32G32B32A32_FLOAT ? 16u : flt.format == FMT_R32G32B32_FLOAT ? 12u : 8u;
     if (rgbe.rowPitch < rgbe.width * 4u || flt.rowPitch < flt.width * floatBytes) return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch is smaller than the row");
     if (src->width && src->height) { const dxtex_hresult hr = check_no_overlap(ctx, *src, *dst); if (hr != DXTEX_S_OK) return hr; }
     if (decode && !(exposure > 0.0f && exposure <= 3.402823466e+38f)) return fail(ctx, DXTEX_E_INVALIDARG, "the exposure must be a finite positive number");
@@ -1560,69 +1559,26 @@ dxtex_hresult submit_rgbe(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_im
     if (decode) return launched(ctx, launch_rgbe_decode(view_of(src), view_of(dst), 1.0f / exposure, ctx->stream, marks_of(ctx)));
     return launched(ctx, launch_rgbe_encode(view_of(src), view_of(dst), ctx->stream, marks_of(ctx)));
 }
+
+// The RGBE pairs, one body: `device` runs the kernel on the caller's device images, else the host images go through the staging
+dxtex_hresult rgbe(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, bool decode, float exposure, bool device)
+{
+    const dxtex_hresult hr = check_rgbe(ctx, src, dst, decode, exposure);
+    if (hr != DXTEX_S_OK) return hr;
+    if (device) return run_timed(ctx, [&] { return submit_rgbe(ctx, *src, *dst, decode, exposure); });
+    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rgbe(ctx, s, d, decode, exposure); });
+}
 } // namespace
 
-dxtex_hresult dxtex_rgbe_decode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure)
-{
-    const dxtex_hresult hr = check_rgbe(ctx, src, dst, true, exposure);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return submit_rgbe(ctx, *src, *dst, true, exposure); });
-}
-
-dxtex_hresult dxtex_rgbe_decode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure)
-{
-    const dxtex_hresult hr = check_rgbe(ctx, src, dst, true, exposure);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rgbe(ctx, s, d, true, exposure); });
-}
-
-dxtex_hresult dxtex_rgbe_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
-{
-    const dxtex_hresult hr = check_rgbe(ctx, src, dst, false, 1.0f);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return submit_rgbe(ctx, *src, *dst, false, 1.0f); });
-}
-
-dxtex_hresult dxtex_rgbe_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst)
-{
-    const dxtex_hresult hr = check_rgbe(ctx, src, dst, false, 1.0f);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_host_twin(ctx, src, dst, [&](const dxtex_image& s, const dxtex_image& d) { return submit_rgbe(ctx, s, d, false, 1.0f); });
-}
+dxtex_hresult dxtex_rgbe_decode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure) { return rgbe(ctx, src, dst, true, exposure, true); }
+dxtex_hresult dxtex_rgbe_decode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, float exposure) { return rgbe(ctx, src, dst, true, exposure, false); }
+dxtex_hresult dxtex_rgbe_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst) { return rgbe(ctx, src, dst, false, 1.0f, true); }
+dxtex_hresult dxtex_rgbe_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst) { return rgbe(ctx, src, dst, false, 1.0f, false); }
 
 namespace
 {
 static_assert(DXTEX_TGA_RIGHT_TO_LEFT == TGA_RIGHT_TO_LEFT && DXTEX_TGA_TOP_DOWN == TGA_TOP_DOWN && DXTEX_TGA_ALLOW_ALL_ZERO_ALPHA == TGA_ALLOW_ALL_ZERO_ALPHA,
               "dxtex_tga.h's flags are the public ones");
-
-// the reader's table (include/dxtex_amd.h): which kind a (bytes per texel, destination format, palette or not) is; -1 for a pair outside it
-int tga_unpack_kind(int format, uint32_t bytesPerTexel, bool paletted)
-{
-    if (paletted) return (bytesPerTexel == 1 && (format == FMT_R8G8B8A8_UNORM || format == FMT_B8G8R8X8_UNORM)) ? TGA_PALETTE : -1;
-    switch (format)
-    {
-    case FMT_R8_UNORM: return bytesPerTexel == 1 ? TGA_GREY : -1;
-    case FMT_B5G5R5A1_UNORM: return bytesPerTexel == 2 ? TGA_5551 : -1;
-    case FMT_R8G8B8A8_UNORM: return bytesPerTexel == 3 ? TGA_RGB_RGBA : bytesPerTexel == 4 ? TGA_BGRA_RGBA : -1;
-    case FMT_B8G8R8X8_UNORM: return bytesPerTexel == 3 ? TGA_RGB_BGRX : -1;
-    case FMT_B8G8R8A8_UNORM: return bytesPerTexel == 4 ? TGA_BGRA_BGRA : -1;
-    default: return -1;
-    }
-}
-
-// the writer's table (SaveToTGAMemory): the row kind of a (format, bytes per texel); -1 for a pair outside it
-int tga_pack_row(int format, uint32_t bytesPerTexel)
-{
-    switch (format)
-    {
-    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return bytesPerTexel == 4 ? TGA_ROW_SWAP_RB : -1;
-    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: return bytesPerTexel == 4 ? TGA_ROW_COPY : -1;
-    case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return bytesPerTexel == 3 ? TGA_ROW_DROP_X : -1;
-    case FMT_R8_UNORM: case FMT_A8_UNORM: return bytesPerTexel == 1 ? TGA_ROW_COPY : -1;
-    case FMT_B5G5R5A1_UNORM: return bytesPerTexel == 2 ? TGA_ROW_COPY : -1;
-    default: return -1;
-    }
-}
 
 // The tail the TGA, PNM and PNG checks share: the image's rows against its pitch, and the file side - `need` bytes at `stream`, named
 // `noun` in the message - apart from the rowBytes-wide rows of the image
@@ -1636,20 +1592,22 @@ dxtex_hresult check_stream_image(dxtex_ctx* ctx, const char* noun, const void* s
     return DXTEX_S_OK;
 }
 
-// The checks of the TGA four, in the order include/dxtex_amd.h states. `image` is the dxtex_image side, imageBytes a texel of it;
-// *kind = the reader's kind or the writer's row.
-dxtex_hresult check_tga(dxtex_ctx* ctx, const void* stream, size_t streamBytes, uint32_t bytesPerTexel, bool paletted, const dxtex_image* image, bool unpack, int* kind)
+// The checks of the TGA four, in the order include/dxtex_amd.h states. `image` is the dxtex_image side, *rowBytes a row of its texels;
+// *kind = the reader's kind or the writer's row (dxtex_tga.h's tables).
+dxtex_hresult check_tga(dxtex_ctx* ctx, const void* stream, size_t streamBytes, uint32_t bytesPerTexel, bool paletted, const dxtex_image* image, bool unpack, int* kind,
+                        size_t* rowBytes)
 {
     if (!ctx) return DXTEX_E_POINTER;
     if (!stream) return fail(ctx, DXTEX_E_POINTER, "null texel stream");
     if (!image) return fail(ctx, DXTEX_E_POINTER, "null image");
     if (!image->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
-    *kind = unpack ? tga_unpack_kind(image->format, bytesPerTexel, paletted) : tga_pack_row(image->format, bytesPerTexel);
+    const TgaPackRow row = tga_pack_row(image->format);
+    *kind = unpack ? tga_unpack_kind(image->format, bytesPerTexel, paletted) : row.bytesPerTexel == bytesPerTexel ? row.row : -1;
     if (*kind < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, unpack ? "no TGA reader case for this bytes per texel, format and palette" : "no TGA writer case for this format and bytes per texel");
     if (!image->width || !image->height || image->width > 65535 || image->height > 65535) return fail(ctx, DXTEX_E_INVALIDARG, "a TGA image is 1 to 65535 texels wide and high");
-    const size_t imageBytes = unpack ? tga_image_bytes(*kind) : (*kind == TGA_ROW_DROP_X ? 4u : bytesPerTexel);
+    *rowBytes = image->width * (unpack ? tga_image_bytes(*kind) : tga_row_image_bytes(row));
     const size_t need = image->width * image->height * bytesPerTexel;
-    const dxtex_hresult hr = check_stream_image(ctx, "texel stream", stream, need, image, image->width * imageBytes);
+    const dxtex_hresult hr = check_stream_image(ctx, "texel stream", stream, need, image, *rowBytes);
     if (hr != DXTEX_S_OK) return hr;
     if (streamBytes != need) return fail(ctx, DXTEX_E_FAIL, "the texel stream is not width * height * bytes per texel long");
     return DXTEX_S_OK;
@@ -1664,24 +1622,17 @@ dxtex_hresult submit_tga_unpack(dxtex_ctx* ctx, const uint8_t* stream, int kind,
     if (!tga_has_alpha_rule(kind) && answer) HIP_TRY(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(answer), kind == TGA_RGB_RGBA ? 1 : 0, 1, ctx->stream));
     return launched(ctx, launch_tga_unpack(stream, kind, flags, palette, view_of(dst), cell, answer ? answer : cell + 2, ctx->stream, marks_of(ctx)));
 }
-} // namespace
 
-dxtex_hresult dxtex_tga_unpack_device(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
-                                      const dxtex_image* dst, uint32_t* opaqueDevice)
+// The TGA pairs, one body each: `device` runs the kernels on the caller's device pointers, else the host pointers go through the staging.
+// The host reader's answer comes down with the pixels.
+dxtex_hresult tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette, const dxtex_image* dst,
+                         uint32_t* opaque, bool device)
 {
-    int kind;
-    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, palette != nullptr, dst, true, &kind);
+    if (!device && ctx && !opaque) return fail(ctx, DXTEX_E_POINTER, "null alpha answer");
+    int kind; size_t rowBytes;
+    dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, palette != nullptr, dst, true, &kind, &rowBytes);
     if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return submit_tga_unpack(ctx, static_cast<const uint8_t*>(texels), kind, flags, palette, *dst, opaqueDevice); });
-}
-
-dxtex_hresult dxtex_tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
-                               const dxtex_image* dst, uint32_t* opaque)
-{
-    if (ctx && !opaque) return fail(ctx, DXTEX_E_POINTER, "null alpha answer");
-    int kind;
-    dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, palette != nullptr, dst, true, &kind);
-    if (hr != DXTEX_S_OK) return hr;
+    if (device) return run_timed(ctx, [&] { return submit_tga_unpack(ctx, static_cast<const uint8_t*>(texels), kind, flags, palette, *dst, opaque); });
     *opaque = kind == TGA_RGB_RGBA ? 1u : 0u;
     const bool rule = tga_has_alpha_rule(kind);
     if (rule) { ScopedDevice sd(ctx->device); hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr; }
@@ -1691,21 +1642,37 @@ dxtex_hresult dxtex_tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelB
                       opaque, answer, rule ? sizeof(uint32_t) : 0);
 }
 
+dxtex_hresult tga_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes, bool device)
+{
+    int row; size_t rowBytes;
+    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, false, src, false, &row, &rowBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    auto pack = [&](const dxtex_image& s, uint8_t* out) { return launched(ctx, launch_tga_pack(view_of(s), row, bytesPerTexel, out, ctx->stream, marks_of(ctx))); };
+    if (device) return run_timed(ctx, [&] { return pack(*src, static_cast<uint8_t*>(texels)); });
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, texels, texelBytes, [&](uint8_t* in, uint8_t* out) { return pack(with_pixels(*src, in), out); });
+}
+} // namespace
+
+dxtex_hresult dxtex_tga_unpack_device(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
+                                      const dxtex_image* dst, uint32_t* opaqueDevice)
+{
+    return tga_unpack(ctx, texels, texelBytes, bytesPerTexel, flags, palette, dst, opaqueDevice, true);
+}
+
+dxtex_hresult dxtex_tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelBytes, uint32_t bytesPerTexel, uint32_t flags, const uint32_t* palette,
+                               const dxtex_image* dst, uint32_t* opaque)
+{
+    return tga_unpack(ctx, texels, texelBytes, bytesPerTexel, flags, palette, dst, opaque, false);
+}
+
 dxtex_hresult dxtex_tga_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes)
 {
-    int row;
-    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, false, src, false, &row);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_tga_pack(view_of(*src), row, bytesPerTexel, static_cast<uint8_t*>(texels), ctx->stream, marks_of(ctx))); });
+    return tga_pack(ctx, src, bytesPerTexel, texels, texelBytes, true);
 }
 
 dxtex_hresult dxtex_tga_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes)
 {
-    int row;
-    const dxtex_hresult hr = check_tga(ctx, texels, texelBytes, bytesPerTexel, false, src, false, &row);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + src->width * (row == TGA_ROW_DROP_X ? 4u : bytesPerTexel), texels, texelBytes,
-                      [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_tga_pack(view_of(with_pixels(*src, in)), row, bytesPerTexel, out, ctx->stream, marks_of(ctx))); });
+    return tga_pack(ctx, src, bytesPerTexel, texels, texelBytes, false);
 }
 
 namespace
@@ -1840,34 +1807,6 @@ namespace
 static_assert(DXTEX_PNM_P6 == PNM_P6 && DXTEX_PNM_PF == PNM_PF && DXTEX_PNM_Pf == PNM_Pf && DXTEX_PNM_PH == PNM_PH && DXTEX_PNM_Ph == PNM_Ph &&
               DXTEX_PNM_BIG_ENDIAN == PNM_BIG_ENDIAN, "dxtex_pnm.h's kinds and flag are the public ones");
 
-// the reader's table (include/dxtex_amd.h): the one format a kind unpacks into
-int pnm_unpack_format(uint32_t kind)
-{
-    switch (kind)
-    {
-    case PNM_P6: return FMT_R8G8B8A8_UNORM;
-    case PNM_PF: return FMT_R32G32B32A32_FLOAT;
-    case PNM_Pf: return FMT_R32_FLOAT;
-    case PNM_PH: return FMT_R16G16B16A16_FLOAT;
-    default: return FMT_R16_FLOAT;
-    }
-}
-
-// the writer's table (SaveToPortablePixMap, SaveToPortablePixMapHDR): the PnmSource of a (kind, format); -1 for a pair outside it
-int pnm_pack_source(uint32_t kind, int format)
-{
-    switch (format)
-    {
-    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return kind == PNM_P6 ? PNM_SRC_RGBA8 : -1;
-    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return kind == PNM_P6 ? PNM_SRC_BGRA8 : -1;
-    case FMT_R32G32B32A32_FLOAT: return kind == PNM_PF ? PNM_SRC_RGBA32F : -1;
-    case FMT_R32G32B32_FLOAT: return kind == PNM_PF ? PNM_SRC_RGB32F : -1;
-    case FMT_R16G16B16A16_FLOAT: return kind == PNM_PF ? PNM_SRC_RGBA16F : -1;
-    case FMT_R32_FLOAT: return kind == PNM_Pf ? PNM_SRC_R32F : -1;
-    default: return -1;
-    }
-}
-
 // The checks of the PNM four, in the order include/dxtex_amd.h states. *source = the writer's PnmSource (pack); *rowBytes = a row of the
 // image side, *need = the samples the call moves.
 dxtex_hresult check_pnm(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* image, bool unpack,
@@ -1885,13 +1824,13 @@ dxtex_hresult check_pnm(dxtex_ctx* ctx, const void* samples, size_t sampleBytes,
     size_t imageTexel;
     if (unpack)
     {
-        if (image->format != pnm_unpack_format(kind)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this PNM kind does not unpack into this format");
+        if (image->format != pnm_unpack_format(int(kind))) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this PNM kind does not unpack into this format");
         imageTexel = pnm_image_bytes(int(kind));
     }
     else
     {
-        *source = pnm_pack_source(kind, image->format);
-        if (*source < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "no PNM writer case for this kind and format");
+        *source = pnm_pack_source(image->format);
+        if (*source < 0 || pnm_source_kind(*source) != int(kind)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "no PNM writer case for this kind and format");
         imageTexel = pnm_source_bytes(*source);
     }
     const size_t fileTexel = pnm_file_bytes(int(kind));
@@ -1901,40 +1840,47 @@ dxtex_hresult check_pnm(dxtex_ctx* ctx, const void* samples, size_t sampleBytes,
     if (sampleBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer samples than width * height texels");
     return check_stream_image(ctx, "samples", samples, *need, image, *rowBytes);
 }
+
+// The PNM pairs, one body each: `device` runs the kernel on the caller's device pointers, else the host pointers go through the staging
+dxtex_hresult pnm_unpack(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst, bool device)
+{
+    size_t rowBytes, need;
+    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    auto unpack = [&](const uint8_t* stream, const ImgView& view) { return launch_pnm_unpack(stream, int(kind), maxval, flags, view, ctx->stream, marks_of(ctx)); };
+    if (device) return run_timed(ctx, [&] { return launched(ctx, unpack(static_cast<const uint8_t*>(samples), view_of(*dst))); });
+    return run_staged_rows(ctx, samples, need, dst, rowBytes, unpack);
+}
+
+dxtex_hresult pnm_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes, bool device)
+{
+    int source; size_t rowBytes, need;
+    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, 255, 0, src, false, &source, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    auto pack = [&](const dxtex_image& s, uint8_t* out) { return launched(ctx, launch_pnm_pack(view_of(s), source, out, ctx->stream, marks_of(ctx))); };
+    if (device) return run_timed(ctx, [&] { return pack(*src, static_cast<uint8_t*>(samples)); });
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, samples, need, [&](uint8_t* in, uint8_t* out) { return pack(with_pixels(*src, in), out); });
+}
 } // namespace
 
 dxtex_hresult dxtex_pnm_unpack_device(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst)
 {
-    size_t rowBytes, need;
-    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_pnm_unpack(static_cast<const uint8_t*>(samples), int(kind), maxval, flags, view_of(*dst), ctx->stream, marks_of(ctx))); });
+    return pnm_unpack(ctx, samples, sampleBytes, kind, maxval, flags, dst, true);
 }
 
 dxtex_hresult dxtex_pnm_unpack(dxtex_ctx* ctx, const void* samples, size_t sampleBytes, uint32_t kind, uint32_t maxval, uint32_t flags, const dxtex_image* dst)
 {
-    size_t rowBytes, need;
-    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, maxval, flags, dst, true, nullptr, &rowBytes, &need);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_staged_rows(ctx, samples, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
-                           { return launch_pnm_unpack(stream, int(kind), maxval, flags, view, ctx->stream, marks_of(ctx)); });
+    return pnm_unpack(ctx, samples, sampleBytes, kind, maxval, flags, dst, false);
 }
 
 dxtex_hresult dxtex_pnm_pack_device(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes)
 {
-    int source; size_t rowBytes, need;
-    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, 255, 0, src, false, &source, &rowBytes, &need);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_pnm_pack(view_of(*src), source, static_cast<uint8_t*>(samples), ctx->stream, marks_of(ctx))); });
+    return pnm_pack(ctx, src, kind, samples, sampleBytes, true);
 }
 
 dxtex_hresult dxtex_pnm_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t kind, void* samples, size_t sampleBytes)
 {
-    int source; size_t rowBytes, need;
-    const dxtex_hresult hr = check_pnm(ctx, samples, sampleBytes, kind, 255, 0, src, false, &source, &rowBytes, &need);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, samples, need,
-                      [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_pnm_pack(view_of(with_pixels(*src, in)), source, out, ctx->stream, marks_of(ctx))); });
+    return pnm_pack(ctx, src, kind, samples, sampleBytes, false);
 }
 
 namespace
@@ -1943,36 +1889,6 @@ static_assert(DXTEX_PNG_G1 == PNG_G1 && DXTEX_PNG_G2 == PNG_G2 && DXTEX_PNG_G4 =
               DXTEX_PNG_GA16 == PNG_GA16 && DXTEX_PNG_RGB8 == PNG_RGB8 && DXTEX_PNG_RGB16 == PNG_RGB16 && DXTEX_PNG_RGBA8 == PNG_RGBA8 && DXTEX_PNG_RGBA16 == PNG_RGBA16 &&
               DXTEX_PNG_P1 == PNG_P1 && DXTEX_PNG_P2 == PNG_P2 && DXTEX_PNG_P4 == PNG_P4 && DXTEX_PNG_P8 == PNG_P8 && DXTEX_PNG_BGR == PNG_BGR,
               "dxtex_png.h's kinds and flag are the public ones");
-
-// the reader's table (include/dxtex_amd.h): whether a kind under these flags unpacks into this format
-bool png_unpack_pairs(uint32_t kind, uint32_t flags, int format)
-{
-    const bool bgr = (flags & PNG_BGR) != 0;
-    switch (kind)
-    {
-    case PNG_G1: case PNG_G2: case PNG_G4: case PNG_G8: return format == FMT_R8_UNORM;
-    case PNG_G16: return format == FMT_R16_UNORM;
-    case PNG_GA8: return format == (bgr ? FMT_B8G8R8A8_UNORM : FMT_R8G8B8A8_UNORM);          // g, g, g, a either way
-    case PNG_GA16: case PNG_RGB16: case PNG_RGBA16: return format == FMT_R16G16B16A16_UNORM;
-    case PNG_RGBA8: return bgr ? (format == FMT_B8G8R8A8_UNORM || format == FMT_B8G8R8A8_UNORM_SRGB) : (format == FMT_R8G8B8A8_UNORM || format == FMT_R8G8B8A8_UNORM_SRGB);
-    default: return bgr ? (format == FMT_B8G8R8X8_UNORM || format == FMT_B8G8R8X8_UNORM_SRGB) : (format == FMT_R8G8B8A8_UNORM || format == FMT_R8G8B8A8_UNORM_SRGB);          // RGB 8, palette
-    }
-}
-
-// the writer's table (WriteImage): the PngSource of a format; -1 for one outside it
-int png_pack_source(int format)
-{
-    switch (format)
-    {
-    case FMT_R8_UNORM: return PNG_SRC_R8;
-    case FMT_R16_UNORM: return PNG_SRC_R16;
-    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return PNG_SRC_RGBA8;
-    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: return PNG_SRC_BGRA8;
-    case FMT_R16G16B16A16_UNORM: return PNG_SRC_RGBA16;
-    case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return PNG_SRC_BGRX8;
-    default: return -1;
-    }
-}
 
 // The checks of the PNG four, in the order include/dxtex_amd.h states. *source = the writer's PngSource (pack); *rowBytes = a row of the
 // image side, *fileRow = a row of the file side, *need = the bytes the call moves on the file side. table: the palette kinds' 256 words.
@@ -1996,7 +1912,7 @@ dxtex_hresult check_png(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint
     size_t imageTexel;
     if (unpack)
     {
-        if (!png_unpack_pairs(kind, flags, image->format)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this PNG kind and flags do not unpack into this format");
+        if (!png_unpack_pairs(int(kind), flags, image->format)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this PNG kind and flags do not unpack into this format");
         imageTexel = png_image_bytes(int(kind));
         *fileRow = size_t(png_row_bytes(int(kind), image->width));
         for (uint32_t i = 0; palette && i < 256; ++i) (*table)[i] = i < paletteCount ? palette[i] : 0xFF000000u;
@@ -2014,43 +1930,44 @@ dxtex_hresult check_png(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint
     if (rowsBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer bytes than height rows");
     return check_stream_image(ctx, "rows", rows, *need, image, *rowBytes);
 }
+
+// The PNG pairs, one body each: `device` runs the kernel on the caller's device pointers, else the host pointers go through the staging
+dxtex_hresult png_unpack(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount, const dxtex_image* dst,
+                         bool device)
+{
+    size_t rowBytes, fileRow, need; uint32_t table[256];
+    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
+    if (hr != DXTEX_S_OK) return hr;
+    auto unpack = [&](const uint8_t* stream, const ImgView& view) { return launch_png_unpack(stream, int(kind), flags, palette ? table : nullptr, view, ctx->stream, marks_of(ctx)); };
+    if (device) return run_timed(ctx, [&] { return launched(ctx, unpack(static_cast<const uint8_t*>(rows), view_of(*dst))); });
+    return run_staged_rows(ctx, rows, need, dst, rowBytes, unpack);
+}
+
+dxtex_hresult png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes, bool device)
+{
+    int source; size_t rowBytes, fileRow, need;
+    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, 0, 0, nullptr, 0, src, false, &source, &rowBytes, &fileRow, &need, nullptr);
+    if (hr != DXTEX_S_OK) return hr;
+    auto pack = [&](const dxtex_image& s, uint8_t* out) { return launched(ctx, launch_png_pack(view_of(s), source, out, ctx->stream, marks_of(ctx))); };
+    if (device) return run_timed(ctx, [&] { return pack(*src, static_cast<uint8_t*>(rows)); });
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, rows, need, [&](uint8_t* in, uint8_t* out) { return pack(with_pixels(*src, in), out); });
+}
 } // namespace
 
 dxtex_hresult dxtex_png_unpack_device(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
                                       const dxtex_image* dst)
 {
-    size_t rowBytes, fileRow, need; uint32_t table[256];
-    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_png_unpack(static_cast<const uint8_t*>(rows), int(kind), flags, palette ? table : nullptr, view_of(*dst), ctx->stream, marks_of(ctx))); });
+    return png_unpack(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true);
 }
 
 dxtex_hresult dxtex_png_unpack(dxtex_ctx* ctx, const void* rows, size_t rowsBytes, uint32_t kind, uint32_t flags, const uint32_t* palette, uint32_t paletteCount,
                                const dxtex_image* dst)
 {
-    size_t rowBytes, fileRow, need; uint32_t table[256];
-    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, true, nullptr, &rowBytes, &fileRow, &need, &table);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_staged_rows(ctx, rows, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
-                           { return launch_png_unpack(stream, int(kind), flags, palette ? table : nullptr, view, ctx->stream, marks_of(ctx)); });
+    return png_unpack(ctx, rows, rowsBytes, kind, flags, palette, paletteCount, dst, false);
 }
 
-dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes)
-{
-    int source; size_t rowBytes, fileRow, need;
-    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, 0, 0, nullptr, 0, src, false, &source, &rowBytes, &fileRow, &need, nullptr);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_png_pack(view_of(*src), source, static_cast<uint8_t*>(rows), ctx->stream, marks_of(ctx))); });
-}
-
-dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes)
-{
-    int source; size_t rowBytes, fileRow, need;
-    const dxtex_hresult hr = check_png(ctx, rows, rowsBytes, 0, 0, nullptr, 0, src, false, &source, &rowBytes, &fileRow, &need, nullptr);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, rows, need,
-                      [&](uint8_t* in, uint8_t* out) { return launched(ctx, launch_png_pack(view_of(with_pixels(*src, in)), source, out, ctx->stream, marks_of(ctx))); });
-}
+dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes) { return png_pack(ctx, src, rows, rowsBytes, true); }
+dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes) { return png_pack(ctx, src, rows, rowsBytes, false); }
 
 namespace
 {
@@ -2084,11 +2001,10 @@ dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coeffi
     for (uint32_t c = 1; c < frame->components; ++c) sampling = sampling && frame->component[c].h == 1u && frame->component[c].v == 1u;
     if (!sampling) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "JPEG sampling other than 1x1, 2x1 or 2x2 luma over 1x1 chroma");
     const bool grey = frame->colour == DXTEX_JPEG_GREY;
-    const bool rgba = image->format == FMT_R8G8B8A8_UNORM || image->format == FMT_R8G8B8A8_UNORM_SRGB;
-    const bool bgrx = image->format == FMT_B8G8R8A8_UNORM || image->format == FMT_B8G8R8A8_UNORM_SRGB || image->format == FMT_B8G8R8X8_UNORM || image->format == FMT_B8G8R8X8_UNORM_SRGB;
-    if (grey ? image->format != FMT_R8_UNORM : !(rgba || (encode && bgrx)))
+    const int texel = jpeg_texel_of(image->format);
+    if (grey ? texel != JPEG_TEXEL_GREY : !(texel == JPEG_TEXEL_RGBA || (encode && texel == JPEG_TEXEL_BGRX)))
         return fail(ctx, DXTEX_E_NOT_SUPPORTED, encode ? "this format does not encode as this JPEG colour" : "this JPEG colour does not decode into this format");
-    if (bgr) *bgr = bgrx;
+    if (bgr) *bgr = texel == JPEG_TEXEL_BGRX;
     f->width = frame->width; f->height = frame->height; f->components = frame->components; f->colour = int(frame->colour);
     uint64_t at = 0;
     for (uint32_t c = 0; c < frame->components; ++c)
@@ -2109,62 +2025,69 @@ dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coeffi
     return check_stream_image(ctx, "coefficients", coefficients, *need, image, *rowBytes);
 }
 
-// both kernels on the context's stream, the planes in memory of the context
-dxtex_hresult submit_jpeg(dxtex_ctx* ctx, const uint8_t* coefficients, const JpegFrame& f, const ImgView& view)
+// The JPEG pairs, one body each: `device` runs the kernels on the caller's device pointers, else the host pointers go through the staging.
+// The planes between the two kernels live in memory of the context.
+dxtex_hresult jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst, bool device)
 {
-    const dxtex_hresult hr = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+    JpegFrame f; size_t need, rowBytes;
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, false, &f, &need, &rowBytes);
     if (hr != DXTEX_S_OK) return hr;
-    return launched(ctx, launch_jpeg_decode(reinterpret_cast<const int16_t*>(coefficients), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)));
+    auto decode = [&](const uint8_t* stream, const ImgView& view)
+    { return launch_jpeg_decode(reinterpret_cast<const int16_t*>(stream), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)); };
+    if (device)
+        return run_timed(ctx, [&]
+        {
+            const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+            return grown != DXTEX_S_OK ? grown : launched(ctx, decode(static_cast<const uint8_t*>(coefficients), view_of(*dst)));
+        });
+    {
+        ScopedDevice sd(ctx->device);
+        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+        if (grown != DXTEX_S_OK) return grown;
+    }
+    return run_staged_rows(ctx, coefficients, need, dst, rowBytes, decode);
+}
+
+dxtex_hresult jpeg_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes, bool device)
+{
+    JpegFrame f; size_t need, rowBytes; bool bgr;
+    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, src, true, &f, &need, &rowBytes, &bgr);
+    if (hr != DXTEX_S_OK) return hr;
+    auto encode = [&](const dxtex_image& s, void* out)
+    { return launched(ctx, launch_jpeg_encode(view_of(s), bgr, f, static_cast<int16_t*>(out), ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx))); };
+    if (device)
+        return run_timed(ctx, [&]
+        {
+            const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+            return grown != DXTEX_S_OK ? grown : encode(*src, coefficients);
+        });
+    {
+        ScopedDevice sd(ctx->device);
+        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+        if (grown != DXTEX_S_OK) return grown;
+    }
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, coefficients, need, [&](uint8_t* in, uint8_t* out) { return encode(with_pixels(*src, in), out); });
 }
 } // namespace
 
 dxtex_hresult dxtex_jpeg_decode_device(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst)
 {
-    JpegFrame f; size_t need, rowBytes;
-    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, false, &f, &need, &rowBytes);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return submit_jpeg(ctx, static_cast<const uint8_t*>(coefficients), f, view_of(*dst)); });
+    return jpeg_decode(ctx, coefficients, coefficientBytes, frame, dst, true);
 }
 
 dxtex_hresult dxtex_jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst)
 {
-    JpegFrame f; size_t need, rowBytes;
-    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, false, &f, &need, &rowBytes);
-    if (hr != DXTEX_S_OK) return hr;
-    {
-        ScopedDevice sd(ctx->device);
-        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-        if (grown != DXTEX_S_OK) return grown;
-    }
-    return run_staged_rows(ctx, coefficients, need, dst, rowBytes, [&](const uint8_t* stream, const ImgView& view)
-                           { return launch_jpeg_decode(reinterpret_cast<const int16_t*>(stream), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)); });
+    return jpeg_decode(ctx, coefficients, coefficientBytes, frame, dst, false);
 }
 
 dxtex_hresult dxtex_jpeg_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes)
 {
-    JpegFrame f; size_t need, rowBytes; bool bgr;
-    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, src, true, &f, &need, &rowBytes, &bgr);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&]
-    {
-        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-        if (grown != DXTEX_S_OK) return grown;
-        return launched(ctx, launch_jpeg_encode(view_of(*src), bgr, f, static_cast<int16_t*>(coefficients), ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)));
-    });
+    return jpeg_encode(ctx, src, frame, coefficients, coefficientBytes, true);
 }
 
 dxtex_hresult dxtex_jpeg_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes)
 {
-    JpegFrame f; size_t need, rowBytes; bool bgr;
-    const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, src, true, &f, &need, &rowBytes, &bgr);
-    if (hr != DXTEX_S_OK) return hr;
-    {
-        ScopedDevice sd(ctx->device);
-        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-        if (grown != DXTEX_S_OK) return grown;
-    }
-    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, coefficients, need, [&](uint8_t* in, uint8_t* out)
-                      { return launched(ctx, launch_jpeg_encode(view_of(with_pixels(*src, in)), bgr, f, reinterpret_cast<int16_t*>(out), ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx))); });
+    return jpeg_encode(ctx, src, frame, coefficients, coefficientBytes, false);
 }
 
 namespace

@@ -40,21 +40,6 @@ enum DdsRowOp : int { ROW_COPY = 0, ROW_SWIZZLE, ROW_565, ROW_5551, ROW_4444, RO
 // what the result format makes of an op. DDS_TO_BYTES: the texel passes unchanged (ROW_COPY; ROW_SWIZZLE into a format without a swizzle).
 enum DdsTarget : int { DDS_TO_BYTES = 0, DDS_TO_8888, DDS_TO_1010102, DDS_TO_YUY2, DDS_TO_565, DDS_TO_4444, DDS_TO_16161616 };
 
-// DXGI_FORMAT values this header names (DirectXTex.h / dxgiformat.h; 116, 117, 189 and 191 are the console and 4:4:4:4 additions)
-enum : int
-{
-    DDS_F_R32G32B32A32_TYPELESS = 1, DDS_F_R32G32B32A32_FLOAT = 2, DDS_F_R32G32B32A32_UINT = 3, DDS_F_R32G32B32A32_SINT = 4,
-    DDS_F_R16G16B16A16_TYPELESS = 9, DDS_F_R16G16B16A16_FLOAT = 10, DDS_F_R16G16B16A16_UNORM = 11, DDS_F_R16G16B16A16_UINT = 12,
-    DDS_F_R16G16B16A16_SNORM = 13, DDS_F_R16G16B16A16_SINT = 14,
-    DDS_F_R10G10B10A2_TYPELESS = 23, DDS_F_R10G10B10A2_UNORM = 24, DDS_F_R10G10B10A2_UINT = 25,
-    DDS_F_R8G8B8A8_TYPELESS = 27, DDS_F_R8G8B8A8_UNORM = 28, DDS_F_R8G8B8A8_UNORM_SRGB = 29, DDS_F_R8G8B8A8_UINT = 30, DDS_F_R8G8B8A8_SNORM = 31,
-    DDS_F_R8G8B8A8_SINT = 32, DDS_F_A8_UNORM = 65, DDS_F_B5G6R5_UNORM = 85, DDS_F_B5G5R5A1_UNORM = 86, DDS_F_B8G8R8A8_UNORM = 87,
-    DDS_F_B8G8R8X8_UNORM = 88, DDS_F_R10G10B10_XR_BIAS_A2_UNORM = 89, DDS_F_B8G8R8A8_TYPELESS = 90, DDS_F_B8G8R8A8_UNORM_SRGB = 91,
-    DDS_F_B8G8R8X8_TYPELESS = 92, DDS_F_B8G8R8X8_UNORM_SRGB = 93, DDS_F_AYUV = 100, DDS_F_Y410 = 101, DDS_F_Y416 = 102, DDS_F_YUY2 = 107,
-    DDS_F_B4G4R4A4_UNORM = 115, DDS_F_R10G10B10_7E3_A2_FLOAT = 116, DDS_F_R10G10B10_6E4_A2_FLOAT = 117, DDS_F_R10G10B10_SNORM_A2_UNORM = 189,
-    DDS_F_A4B4G4R4_UNORM = 191,
-};
-
 // bytes of a file texel per op; 0 for ROW_COPY (which works in bytes) and anything that is no op
 DXTEX_FN constexpr uint32_t dds_file_bytes(int op)
 {
@@ -73,13 +58,13 @@ DXTEX_FN constexpr bool dds_has_palette(int op) { return op == ROW_P8 || op == R
 
 DXTEX_FN constexpr bool dds_is_8888(int f)
 {
-    return f == DDS_F_R8G8B8A8_TYPELESS || f == DDS_F_R8G8B8A8_UNORM || f == DDS_F_R8G8B8A8_UNORM_SRGB || f == DDS_F_B8G8R8A8_UNORM || f == DDS_F_B8G8R8X8_UNORM
-        || f == DDS_F_B8G8R8A8_TYPELESS || f == DDS_F_B8G8R8A8_UNORM_SRGB || f == DDS_F_B8G8R8X8_TYPELESS || f == DDS_F_B8G8R8X8_UNORM_SRGB;
+    return f == FMT_R8G8B8A8_TYPELESS || f == FMT_R8G8B8A8_UNORM || f == FMT_R8G8B8A8_UNORM_SRGB || f == FMT_B8G8R8A8_UNORM || f == FMT_B8G8R8X8_UNORM
+        || f == FMT_B8G8R8A8_TYPELESS || f == FMT_B8G8R8A8_UNORM_SRGB || f == FMT_B8G8R8X8_TYPELESS || f == FMT_B8G8R8X8_UNORM_SRGB;
 }
 DXTEX_FN constexpr bool dds_is_1010102(int f)
 {
-    return f == DDS_F_R10G10B10A2_TYPELESS || f == DDS_F_R10G10B10A2_UNORM || f == DDS_F_R10G10B10A2_UINT || f == DDS_F_R10G10B10_XR_BIAS_A2_UNORM
-        || f == DDS_F_R10G10B10_SNORM_A2_UNORM;
+    return f == FMT_R10G10B10A2_TYPELESS || f == FMT_R10G10B10A2_UNORM || f == FMT_R10G10B10A2_UINT || f == FMT_R10G10B10_XR_BIAS_A2_UNORM
+        || f == FMT_R10G10B10_SNORM_A2_UNORM;
 }
 
 // The refusal table: the target of (op, result format), or -1 where the reader answers E_FAIL (every expansion into anything but
@@ -87,13 +72,13 @@ DXTEX_FN constexpr bool dds_is_1010102(int f)
 DXTEX_FN constexpr int dds_target(int op, int format)
 {
     return op == ROW_COPY ? DDS_TO_BYTES
-         : op == ROW_SWIZZLE ? (dds_is_1010102(format) ? DDS_TO_1010102 : dds_is_8888(format) ? DDS_TO_8888 : format == DDS_F_YUY2 ? DDS_TO_YUY2 : DDS_TO_BYTES)
-         : op == ROW_L16 ? (format == DDS_F_R16G16B16A16_UNORM ? DDS_TO_16161616 : -1)
-         : op == ROW_WUV10 ? (format == DDS_F_R10G10B10A2_UNORM ? DDS_TO_1010102 : -1)
+         : op == ROW_SWIZZLE ? (dds_is_1010102(format) ? DDS_TO_1010102 : dds_is_8888(format) ? DDS_TO_8888 : format == FMT_YUY2 ? DDS_TO_YUY2 : DDS_TO_BYTES)
+         : op == ROW_L16 ? (format == FMT_R16G16B16A16_UNORM ? DDS_TO_16161616 : -1)
+         : op == ROW_WUV10 ? (format == FMT_R10G10B10A2_UNORM ? DDS_TO_1010102 : -1)
          : (op < 0 || op >= ROW_OPS) ? -1
-         : format == DDS_F_R8G8B8A8_UNORM ? DDS_TO_8888
-         : (op == ROW_332 && format == DDS_F_B5G6R5_UNORM) ? DDS_TO_565
-         : (op == ROW_44 && format == DDS_F_B4G4R4A4_UNORM) ? DDS_TO_4444 : -1;
+         : format == FMT_R8G8B8A8_UNORM ? DDS_TO_8888
+         : (op == ROW_332 && format == FMT_B5G6R5_UNORM) ? DDS_TO_565
+         : (op == ROW_44 && format == FMT_B4G4R4A4_UNORM) ? DDS_TO_4444 : -1;
 }
 
 // an n-bit channel widened to `to` bits by repeating its bit pattern (what all the legacy expansions do)
@@ -181,20 +166,20 @@ DXTEX_FN uint64_t dds_unpack_texel(uint32_t t, int op, int target, bool opaque, 
 struct DdsOpaque { uint32_t texelBytes, keep, set; };
 DXTEX_FN constexpr DdsOpaque dds_opaque_of(int f)
 {
-    return (f == DDS_F_R32G32B32A32_TYPELESS || f == DDS_F_R32G32B32A32_FLOAT || f == DDS_F_R32G32B32A32_UINT || f == DDS_F_R32G32B32A32_SINT)
-             ? DdsOpaque{ 16u, 0u, f == DDS_F_R32G32B32A32_FLOAT ? 0x3f800000u : f == DDS_F_R32G32B32A32_SINT ? 0x7fffffffu : 0xffffffffu }
-         : (f == DDS_F_R16G16B16A16_TYPELESS || f == DDS_F_R16G16B16A16_FLOAT || f == DDS_F_R16G16B16A16_UNORM || f == DDS_F_R16G16B16A16_UINT
-            || f == DDS_F_R16G16B16A16_SNORM || f == DDS_F_R16G16B16A16_SINT || f == DDS_F_Y416)
-             ? DdsOpaque{ 8u, 0x0000ffffu, (f == DDS_F_R16G16B16A16_FLOAT ? 0x3c00u : (f == DDS_F_R16G16B16A16_SNORM || f == DDS_F_R16G16B16A16_SINT) ? 0x7fffu : 0xffffu) << 16 }
-         : (f == DDS_F_R10G10B10A2_TYPELESS || f == DDS_F_R10G10B10A2_UNORM || f == DDS_F_R10G10B10A2_UINT || f == DDS_F_R10G10B10_XR_BIAS_A2_UNORM
-            || f == DDS_F_Y410 || f == DDS_F_R10G10B10_7E3_A2_FLOAT || f == DDS_F_R10G10B10_6E4_A2_FLOAT || f == DDS_F_R10G10B10_SNORM_A2_UNORM)
+    return (f == FMT_R32G32B32A32_TYPELESS || f == FMT_R32G32B32A32_FLOAT || f == FMT_R32G32B32A32_UINT || f == FMT_R32G32B32A32_SINT)
+             ? DdsOpaque{ 16u, 0u, f == FMT_R32G32B32A32_FLOAT ? 0x3f800000u : f == FMT_R32G32B32A32_SINT ? 0x7fffffffu : 0xffffffffu }
+         : (f == FMT_R16G16B16A16_TYPELESS || f == FMT_R16G16B16A16_FLOAT || f == FMT_R16G16B16A16_UNORM || f == FMT_R16G16B16A16_UINT
+            || f == FMT_R16G16B16A16_SNORM || f == FMT_R16G16B16A16_SINT || f == FMT_Y416)
+             ? DdsOpaque{ 8u, 0x0000ffffu, (f == FMT_R16G16B16A16_FLOAT ? 0x3c00u : (f == FMT_R16G16B16A16_SNORM || f == FMT_R16G16B16A16_SINT) ? 0x7fffu : 0xffffu) << 16 }
+         : (f == FMT_R10G10B10A2_TYPELESS || f == FMT_R10G10B10A2_UNORM || f == FMT_R10G10B10A2_UINT || f == FMT_R10G10B10_XR_BIAS_A2_UNORM
+            || f == FMT_Y410 || f == FMT_R10G10B10_7E3_A2_FLOAT || f == FMT_R10G10B10_6E4_A2_FLOAT || f == FMT_R10G10B10_SNORM_A2_UNORM)
              ? DdsOpaque{ 4u, 0xffffffffu, 0xC0000000u }
-         : (f == DDS_F_R8G8B8A8_TYPELESS || f == DDS_F_R8G8B8A8_UNORM || f == DDS_F_R8G8B8A8_UNORM_SRGB || f == DDS_F_R8G8B8A8_UINT || f == DDS_F_R8G8B8A8_SNORM
-            || f == DDS_F_R8G8B8A8_SINT || f == DDS_F_B8G8R8A8_UNORM || f == DDS_F_B8G8R8A8_TYPELESS || f == DDS_F_B8G8R8A8_UNORM_SRGB || f == DDS_F_AYUV)
-             ? DdsOpaque{ 4u, 0x00ffffffu, (f == DDS_F_R8G8B8A8_SNORM || f == DDS_F_R8G8B8A8_SINT) ? 0x7f000000u : 0xff000000u }
-         : (f == DDS_F_B5G5R5A1_UNORM || f == DDS_F_B4G4R4A4_UNORM || f == DDS_F_A4B4G4R4_UNORM)
-             ? DdsOpaque{ 2u, 0xffffu, f == DDS_F_B4G4R4A4_UNORM ? 0xF000u : f == DDS_F_A4B4G4R4_UNORM ? 0x000Fu : 0x8000u }
-         : f == DDS_F_A8_UNORM ? DdsOpaque{ 1u, 0u, 0xffu }
+         : (f == FMT_R8G8B8A8_TYPELESS || f == FMT_R8G8B8A8_UNORM || f == FMT_R8G8B8A8_UNORM_SRGB || f == FMT_R8G8B8A8_UINT || f == FMT_R8G8B8A8_SNORM
+            || f == FMT_R8G8B8A8_SINT || f == FMT_B8G8R8A8_UNORM || f == FMT_B8G8R8A8_TYPELESS || f == FMT_B8G8R8A8_UNORM_SRGB || f == FMT_AYUV)
+             ? DdsOpaque{ 4u, 0x00ffffffu, (f == FMT_R8G8B8A8_SNORM || f == FMT_R8G8B8A8_SINT) ? 0x7f000000u : 0xff000000u }
+         : (f == FMT_B5G5R5A1_UNORM || f == FMT_B4G4R4A4_UNORM || f == FMT_A4B4G4R4_UNORM)
+             ? DdsOpaque{ 2u, 0xffffu, f == FMT_B4G4R4A4_UNORM ? 0xF000u : f == FMT_A4B4G4R4_UNORM ? 0x000Fu : 0x8000u }
+         : f == FMT_A8_UNORM ? DdsOpaque{ 1u, 0u, 0xffu }
          : DdsOpaque{ 0u, 0xffffffffu, 0u };
 }
 // the last word of one texel, forced opaque

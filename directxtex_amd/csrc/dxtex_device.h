@@ -1,4 +1,4 @@
-// Device-side helpers shared by the HIP kernels: DXGI format ids, HRESULT values, and the 4x4 tile
+// Device-side helpers shared by the HIP kernels: HRESULT values (the DXGI format ids are dxtex_stream.h's), and the 4x4 tile
 // loader that plays the role of the reference's LoadScanline + partial-block replication +
 // ConvertScanline (DirectXTexCompress.cpp:291-343, DirectXTexConvert.cpp:779-1619, :3080-3854).
 // gfx950 only. Compile with -ffp-contract=off: BC1-BC5 parity is bit-exact fp32.
@@ -6,56 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "dxtex_stream.h"
 
 namespace dxtex
 {
-// Public DXGI numbering (only the formats this library understands).
-enum : int
-{
-    FMT_UNKNOWN = 0,
-    FMT_R32G32B32A32_FLOAT = 2, FMT_R32G32B32A32_UINT = 3, FMT_R32G32B32A32_SINT = 4,
-    FMT_R32G32B32_FLOAT = 6, FMT_R32G32B32_UINT = 7, FMT_R32G32B32_SINT = 8,
-    FMT_R16G16B16A16_FLOAT = 10,
-    FMT_R16G16B16A16_UNORM = 11, FMT_R16G16B16A16_UINT = 12,
-    FMT_R16G16B16A16_SNORM = 13, FMT_R16G16B16A16_SINT = 14,
-    FMT_R32G32_FLOAT = 16, FMT_R32G32_UINT = 17, FMT_R32G32_SINT = 18,
-    FMT_D32_FLOAT_S8X24_UINT = 20,
-    FMT_R10G10B10A2_UNORM = 24, FMT_R10G10B10A2_UINT = 25,
-    FMT_R11G11B10_FLOAT = 26,
-    FMT_R8G8B8A8_UNORM = 28,
-    FMT_R8G8B8A8_UNORM_SRGB = 29, FMT_R8G8B8A8_UINT = 30,
-    FMT_R8G8B8A8_SNORM = 31, FMT_R8G8B8A8_SINT = 32,
-    FMT_R16G16_FLOAT = 34,
-    FMT_R16G16_UNORM = 35, FMT_R16G16_UINT = 36,
-    FMT_R16G16_SNORM = 37, FMT_R16G16_SINT = 38,
-    FMT_D32_FLOAT = 40, FMT_R32_FLOAT = 41, FMT_R32_UINT = 42, FMT_R32_SINT = 43,
-    FMT_D24_UNORM_S8_UINT = 45,
-    FMT_R8G8_UNORM = 49, FMT_R8G8_UINT = 50,
-    FMT_R8G8_SNORM = 51, FMT_R8G8_SINT = 52,
-    FMT_R16_FLOAT = 54, FMT_D16_UNORM = 55,
-    FMT_R16_UNORM = 56, FMT_R16_UINT = 57,
-    FMT_R16_SNORM = 58, FMT_R16_SINT = 59,
-    FMT_R8_UNORM = 61, FMT_R8_UINT = 62,
-    FMT_R8_SNORM = 63, FMT_R8_SINT = 64,
-    FMT_A8_UNORM = 65, FMT_R1_UNORM = 66,
-    FMT_R9G9B9E5_SHAREDEXP = 67, FMT_R8G8_B8G8_UNORM = 68, FMT_G8R8_G8B8_UNORM = 69,
-    FMT_BC1_UNORM = 71, FMT_BC1_UNORM_SRGB = 72,
-    FMT_BC2_UNORM = 74, FMT_BC2_UNORM_SRGB = 75,
-    FMT_BC3_UNORM = 77, FMT_BC3_UNORM_SRGB = 78,
-    FMT_BC4_UNORM = 80, FMT_BC4_SNORM = 81,
-    FMT_BC5_UNORM = 83, FMT_BC5_SNORM = 84,
-    FMT_B5G6R5_UNORM = 85, FMT_B5G5R5A1_UNORM = 86,
-    FMT_B8G8R8A8_UNORM = 87, FMT_B8G8R8X8_UNORM = 88, FMT_R10G10B10_XR_BIAS_A2_UNORM = 89,
-    FMT_B8G8R8A8_UNORM_SRGB = 91, FMT_B8G8R8X8_UNORM_SRGB = 93,
-    FMT_BC6H_UF16 = 95, FMT_BC6H_SF16 = 96,
-    FMT_BC7_UNORM = 98, FMT_BC7_UNORM_SRGB = 99,
-    FMT_AYUV = 100, FMT_Y410 = 101, FMT_Y416 = 102, FMT_YUY2 = 107, FMT_Y210 = 108, FMT_Y216 = 109,
-    FMT_B4G4R4A4_UNORM = 115,
-    FMT_R10G10B10_7E3_A2_FLOAT = 116, FMT_R10G10B10_6E4_A2_FLOAT = 117,       // XBOX_DXGI_FORMAT_*: the console HDR formats
-    FMT_R10G10B10_SNORM_A2_UNORM = 189, FMT_R4G4_UNORM = 190,                 // XBOX_DXGI_FORMAT_*
-    FMT_A4B4G4R4_UNORM = 191,
-};
-
 // BC_FLAGS == TEX_COMPRESS_FLAGS bit-for-bit (BC.h:30-48, DirectXTex.h:887-917).
 enum : uint32_t
 {

@@ -131,6 +131,21 @@ DXTEX_FN constexpr uint32_t jpeg_downsampled(uint32_t extent, uint32_t factor, u
 // jccoefct.c's dummy blocks - for the kernels, the host saver and a host check (tests/cpp/jpeg_write_check.cpp). The coefficients come out
 // in the layout the reader takes.
 
+// The format table, for the C ABI and the host codec alike: what an image format is to the coder, -1 for one that is neither read into
+// nor written. A grey frame is JPEG_TEXEL_GREY on both sides; a colour frame decodes into JPEG_TEXEL_RGBA only and encodes from
+// JPEG_TEXEL_RGBA or JPEG_TEXEL_BGRX (`bgr` below).
+enum JpegTexel : int { JPEG_TEXEL_GREY = 0, JPEG_TEXEL_RGBA, JPEG_TEXEL_BGRX };
+DXTEX_FN constexpr int jpeg_texel_of(int format)
+{
+    switch (format)
+    {
+    case FMT_R8_UNORM: return JPEG_TEXEL_GREY;
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return JPEG_TEXEL_RGBA;
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return JPEG_TEXEL_BGRX;
+    default: return -1;
+    }
+}
+
 // jccolor.c: an R8G8B8A8 texel word (B8G8R8x8 with `bgr`) -> Y | Cb << 8 | Cr << 16. Alpha or X is ignored. No term is negative.
 DXTEX_FN constexpr uint32_t jpeg_ycc(uint32_t texel, bool bgr)
 {

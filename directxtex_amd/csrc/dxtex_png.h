@@ -56,6 +56,36 @@ DXTEX_FN constexpr uint32_t png_grey_scale(uint32_t bits) { return bits == 1u ? 
 DXTEX_FN constexpr uint32_t png_source_bytes(int src) { return src == PNG_SRC_R8 ? 1u : src == PNG_SRC_R16 ? 2u : src == PNG_SRC_RGBA16 ? 8u : 4u; }
 DXTEX_FN constexpr uint32_t png_source_file_bytes(int src) { return src == PNG_SRC_BGRX8 ? 3u : png_source_bytes(src); }
 
+// The two format tables, for the C ABI and the host codec alike. The reader's: whether a kind under these flags unpacks into this format
+// (the host codec chooses one of them from the file's colour chunks and its PNG_FLAGS).
+DXTEX_FN constexpr bool png_unpack_pairs(int kind, uint32_t flags, int format)
+{
+    const bool bgr = (flags & PNG_BGR) != 0;
+    switch (kind)
+    {
+    case PNG_G1: case PNG_G2: case PNG_G4: case PNG_G8: return format == FMT_R8_UNORM;
+    case PNG_G16: return format == FMT_R16_UNORM;
+    case PNG_GA8: return format == (bgr ? FMT_B8G8R8A8_UNORM : FMT_R8G8B8A8_UNORM);          // g, g, g, a either way
+    case PNG_GA16: case PNG_RGB16: case PNG_RGBA16: return format == FMT_R16G16B16A16_UNORM;
+    case PNG_RGBA8: return bgr ? (format == FMT_B8G8R8A8_UNORM || format == FMT_B8G8R8A8_UNORM_SRGB) : (format == FMT_R8G8B8A8_UNORM || format == FMT_R8G8B8A8_UNORM_SRGB);
+    default: return bgr ? (format == FMT_B8G8R8X8_UNORM || format == FMT_B8G8R8X8_UNORM_SRGB) : (format == FMT_R8G8B8A8_UNORM || format == FMT_R8G8B8A8_UNORM_SRGB);          // RGB 8, palette
+    }
+}
+// The writer's (WriteImage): the PngSource of a format; -1 for one that is not written
+DXTEX_FN constexpr int png_pack_source(int format)
+{
+    switch (format)
+    {
+    case FMT_R8_UNORM: return PNG_SRC_R8;
+    case FMT_R16_UNORM: return PNG_SRC_R16;
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return PNG_SRC_RGBA8;
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: return PNG_SRC_BGRA8;
+    case FMT_R16G16B16A16_UNORM: return PNG_SRC_RGBA16;
+    case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return PNG_SRC_BGRX8;
+    default: return -1;
+    }
+}
+
 // The table a palette kind reads: 256 words. rgb = `count` entries of 3 bytes (PLTE), alpha = `alphaCount` bytes (tRNS) or null.
 DXTEX_FN void png_palette_table(const uint8_t* rgb, uint32_t count, const uint8_t* alpha, uint32_t alphaCount, uint32_t (&table)[256])
 {

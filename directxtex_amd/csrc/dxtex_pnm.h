@@ -49,6 +49,27 @@ DXTEX_FN constexpr uint32_t pnm_image_row(int kind, uint32_t y, uint32_t height)
 DXTEX_FN constexpr uint32_t pnm_source_bytes(int src) { return src == PNM_SRC_RGBA32F ? 16u : src == PNM_SRC_RGB32F ? 12u : src == PNM_SRC_RGBA16F ? 8u : 4u; }
 DXTEX_FN constexpr int pnm_source_kind(int src) { return (src == PNM_SRC_RGBA8 || src == PNM_SRC_BGRA8) ? PNM_P6 : src == PNM_SRC_R32F ? PNM_Pf : PNM_PF; }
 
+// The two format tables, for the C ABI and the host codec alike. The reader's: the one format a kind unpacks into.
+DXTEX_FN constexpr int pnm_unpack_format(int kind)
+{
+    return kind == PNM_P6 ? FMT_R8G8B8A8_UNORM : kind == PNM_PF ? FMT_R32G32B32A32_FLOAT : kind == PNM_Pf ? FMT_R32_FLOAT : kind == PNM_PH ? FMT_R16G16B16A16_FLOAT : FMT_R16_FLOAT;
+}
+// The writer's (SaveToPortablePixMap, SaveToPortablePixMapHDR): the PnmSource of a format, -1 for one that is not written;
+// pnm_source_kind() of it is the kind it is written as.
+DXTEX_FN constexpr int pnm_pack_source(int format)
+{
+    switch (format)
+    {
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return PNM_SRC_RGBA8;
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return PNM_SRC_BGRA8;
+    case FMT_R32G32B32A32_FLOAT: return PNM_SRC_RGBA32F;
+    case FMT_R32G32B32_FLOAT: return PNM_SRC_RGB32F;
+    case FMT_R16G16B16A16_FLOAT: return PNM_SRC_RGBA16F;
+    case FMT_R32_FLOAT: return PNM_SRC_R32F;
+    default: return -1;
+    }
+}
+
 // 255 * i / maxval in uint32_t; 1 <= maxval <= 255 and i <= 255, so nothing wraps here
 DXTEX_FN constexpr uint32_t pnm_scale(uint32_t i, uint32_t maxval) { return 255u * i / maxval; }
 

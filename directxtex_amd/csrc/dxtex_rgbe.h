@@ -19,6 +19,13 @@
 
 namespace dxtex
 {
+// The format table, for the C ABI and the host codec alike: the bytes of a texel of a format the encoder reads (the decoder writes
+// R32G32B32A32_FLOAT only); 0 for one it does not
+DXTEX_FN constexpr uint32_t rgbe_source_bytes(int format)
+{
+    return format == FMT_R32G32B32A32_FLOAT ? 16u : format == FMT_R32G32B32_FLOAT ? 12u : format == FMT_R16G16B16A16_FLOAT ? 8u : 0u;
+}
+
 DXTEX_FN void rgbe_decode(const uint8_t in[4], float scale, float out[4])
 {
     const int e = int(in[3]) - (128 + 8);

@@ -31,6 +31,39 @@ DXTEX_FN constexpr uint32_t tga_file_bytes(int kind) { return kind == TGA_GREY |
 DXTEX_FN constexpr uint32_t tga_image_bytes(int kind) { return kind == TGA_GREY ? 1u : kind == TGA_5551 ? 2u : 4u; }
 DXTEX_FN constexpr bool tga_has_alpha_rule(int kind) { return kind == TGA_5551 || kind == TGA_BGRA_RGBA || kind == TGA_BGRA_BGRA; }
 
+// The reader's table, for the C ABI and the host codec alike: which kind a (destination format before any sRGB relabel, bytes of a file
+// texel, colour-mapped or not) is; -1 for a triple outside it
+DXTEX_FN constexpr int tga_unpack_kind(int format, uint32_t bytesPerTexel, bool paletted)
+{
+    if (paletted) return (bytesPerTexel == 1 && (format == FMT_R8G8B8A8_UNORM || format == FMT_B8G8R8X8_UNORM)) ? TGA_PALETTE : -1;
+    switch (format)
+    {
+    case FMT_R8_UNORM: return bytesPerTexel == 1 ? TGA_GREY : -1;
+    case FMT_B5G5R5A1_UNORM: return bytesPerTexel == 2 ? TGA_5551 : -1;
+    case FMT_R8G8B8A8_UNORM: return bytesPerTexel == 3 ? TGA_RGB_RGBA : bytesPerTexel == 4 ? TGA_BGRA_RGBA : -1;
+    case FMT_B8G8R8X8_UNORM: return bytesPerTexel == 3 ? TGA_RGB_BGRX : -1;
+    case FMT_B8G8R8A8_UNORM: return bytesPerTexel == 4 ? TGA_BGRA_BGRA : -1;
+    default: return -1;
+    }
+}
+
+// The writer's table (SaveToTGAMemory) likewise: the bytes of a file texel and the row kind of a format; 0 bytes for a format that is
+// not written. An image texel has 4 bytes under TGA_ROW_DROP_X, else the file texel's.
+struct TgaPackRow { uint32_t bytesPerTexel; int row; };
+DXTEX_FN constexpr TgaPackRow tga_pack_row(int format)
+{
+    switch (format)
+    {
+    case FMT_R8G8B8A8_UNORM: case FMT_R8G8B8A8_UNORM_SRGB: return { 4u, TGA_ROW_SWAP_RB };
+    case FMT_B8G8R8A8_UNORM: case FMT_B8G8R8A8_UNORM_SRGB: return { 4u, TGA_ROW_COPY };
+    case FMT_B8G8R8X8_UNORM: case FMT_B8G8R8X8_UNORM_SRGB: return { 3u, TGA_ROW_DROP_X };
+    case FMT_R8_UNORM: case FMT_A8_UNORM: return { 1u, TGA_ROW_COPY };
+    case FMT_B5G5R5A1_UNORM: return { 2u, TGA_ROW_COPY };
+    default: return { 0u, -1 };
+    }
+}
+DXTEX_FN constexpr uint32_t tga_row_image_bytes(const TgaPackRow& r) { return r.row == TGA_ROW_DROP_X ? 4u : r.bytesPerTexel; }
+
 // One file texel (its bytes as a word, the rest zero) as the image stores it; alpha = what the alpha rule sees of it (255 where the kind
 // has no alpha). palette is read by TGA_PALETTE only.
 DXTEX_FN uint32_t tga_unpack_texel(uint32_t t, int kind, const uint32_t* palette, uint32_t& alpha)

@@ -1,8 +1,7 @@
 // CopyRectangle (DirectXTexMisc.cpp:275-381) and texassemble's steps (Texassemble/texassemble.cpp:2013-2400) on the host layer, over the C
 // ABI's dxtex_copy_rectangle, dxtex_copy_rectangles_device and dxtex_merge_image_device. The assemble steps work on DeviceScratchImages:
 // the inputs go up once, every face, slice or item is one rectangle of ONE batched launch, and the result comes down once.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 
 #include <new>
 #include <vector>
@@ -11,7 +10,6 @@ namespace DirectXTexAMD
 {
 namespace
 {
-dxtex_image View(const Image& i) noexcept { return dxtex_image{ i.width, i.height, int32_t(i.format), i.rowPitch, i.slicePitch, i.pixels }; }
 dxtex_rect View(const Rect& r) noexcept { return dxtex_rect{ r.x, r.y, r.w, r.h }; }
 
 inline bool Resident(const Device& device, const DeviceScratchImage& src) noexcept { return src.GetImages() && src.GetDevice() == &device; }
@@ -33,7 +31,7 @@ struct Batch
     std::vector<size_t> x, y;
     void Add(const Image& s, const Rect& r, const Image& d, size_t xo, size_t yo)
     {
-        src.push_back(View(s)); rect.push_back(View(r)); dst.push_back(View(d)); x.push_back(xo); y.push_back(yo);
+        src.push_back(ImageOf(s)); rect.push_back(View(r)); dst.push_back(ImageOf(d)); x.push_back(xo); y.push_back(yo);
     }
     HRESULT Run(Device& device) const noexcept
     {
@@ -55,7 +53,7 @@ const CrossLayout* GetCrossLayout(CROSS_KIND kind) noexcept { return kind < CROS
 HRESULT CopyRectangle(Device& device, const Image& srcImage, const Rect& srcRect, const Image& dstImage, TEX_FILTER_FLAGS filter, size_t xOffset, size_t yOffset) noexcept
 {
     if (!device) return E_POINTER;
-    const dxtex_image s = View(srcImage), d = View(dstImage);
+    const dxtex_image s = ImageOf(srcImage), d = ImageOf(dstImage);
     const dxtex_rect r = View(srcRect);
     return dxtex_copy_rectangle(device.Get(), &s, &r, &d, uint32_t(filter), xOffset, yOffset);
 }
@@ -68,7 +66,7 @@ HRESULT CopyRectangle(Device& device, const DeviceScratchImage& src, size_t srcM
     const Image* s = src.GetImage(srcMip, srcItem, srcSlice);
     const Image* d = dst.GetImage(dstMip, dstItem, dstSlice);
     if (!s || !d) return E_INVALIDARG;
-    const dxtex_image sv = View(*s), dv = View(*d);
+    const dxtex_image sv = ImageOf(*s), dv = ImageOf(*d);
     const dxtex_rect r = View(srcRect);
     return dxtex_copy_rectangles_device(device.Get(), &sv, &r, &dv, &xOffset, &yOffset, 1, uint32_t(filter));
 }
@@ -91,7 +89,7 @@ HRESULT MergeImages(Device& device, const DeviceScratchImage& image1, const Devi
         b = bFloat.GetImage(0, 0, 0);
     }
     hr = result.Initialize(device, Texture2D(a->format, a->width, a->height, 1)); if (FAILED(hr)) return hr;
-    const dxtex_image av = View(*a), bv = View(*b), dv = View(*result.GetImage(0, 0, 0));
+    const dxtex_image av = ImageOf(*a), bv = ImageOf(*b), dv = ImageOf(*result.GetImage(0, 0, 0));
     hr = dxtex_merge_image_device(device.Get(), &av, &bv, &dv, permute, zero, one);
     if (FAILED(hr)) result.Release();
     return hr;
@@ -208,7 +206,7 @@ HRESULT CopyImages(Device& device, const Image* srcDeviceImages, const Image* ds
         for (size_t i = 0; i < count; ++i)
         {
             if (srcDeviceImages[i].width != dstDeviceImages[i].width || srcDeviceImages[i].height != dstDeviceImages[i].height) return E_FAIL;
-            src[i] = View(srcDeviceImages[i]); dst[i] = View(dstDeviceImages[i]);
+            src[i] = ImageOf(srcDeviceImages[i]); dst[i] = ImageOf(dstDeviceImages[i]);
             rect[i] = dxtex_rect{ 0, 0, src[i].width, src[i].height };
         }
         return dxtex_copy_rectangles_device(device.Get(), src.data(), rect.data(), dst.data(), zero.data(), zero.data(), count, uint32_t(filter));

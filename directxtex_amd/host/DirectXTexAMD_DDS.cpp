@@ -555,13 +555,9 @@ HRESULT LoadFromDDSMemoryRaw(const void* pSource, size_t size, DDS_FLAGS flags, 
 HRESULT LoadFromDDSFileRaw(const char* szFile, DDS_FLAGS flags, DDSMetaData* ddPixelFormat, DDSRawImage& raw) noexcept
 {
     raw.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    HRESULT hr = ReadAll(szFile, file, kMinHeader);          // the file readers say E_FAIL for a shorter one (DirectXTexDDS.cpp:1975-1978, :2178-2181)
-    if (FAILED(hr)) return hr;
-    hr = LoadFromDDSMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, ddPixelFormat, raw);
-    if (SUCCEEDED(hr)) raw.storage.Swap(file);          // raw.payload points into it
-    return hr;
+    // the file readers say E_FAIL for a file below the smallest header (DirectXTexDDS.cpp:1975-1978, :2178-2181); raw.payload points into
+    // the file, and raw keeps it
+    return LoadFile(szFile, ReadAtLeast<kMinHeader>, [&](const uint8_t* p, size_t n) { return LoadFromDDSMemoryRaw(p, n, flags, ddPixelFormat, raw); }, &raw.storage);
 }
 
 // LoadFromDDSMemoryEx (DirectXTexDDS.cpp:2019-2107)
@@ -587,12 +583,8 @@ HRESULT LoadFromDDSMemory(const void* pSource, size_t size, DDS_FLAGS flags, Tex
 
 HRESULT LoadFromDDSFileEx(const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, ScratchImage& image) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    image.Release();
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, kMinHeader);
-    if (FAILED(hr)) return hr;
-    return LoadFromDDSMemoryEx(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, ddPixelFormat, image);
+    if (szFile) image.Release();
+    return LoadFile(szFile, ReadAtLeast<kMinHeader>, [&](const uint8_t* p, size_t n) { return LoadFromDDSMemoryEx(p, n, flags, metadata, ddPixelFormat, image); });
 }
 
 HRESULT LoadFromDDSFile(const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
@@ -626,7 +618,7 @@ HRESULT UploadDDSRaw(Device& device, const DDSRawImage& raw, DeviceScratchImage&
     {
         const Image& d = image.GetImages()[i];
         const DDSRawImage::Source& from = raw.images[i];
-        dsts[i] = dxtex_image{ d.width, d.height, int32_t(d.format), d.rowPitch, d.slicePitch, d.pixels };
+        dsts[i] = ImageOf(d);
         offsets[i] = from.offset; pitches[i] = from.rowPitch;
         if (bytes)
         {
@@ -634,15 +626,12 @@ HRESULT UploadDDSRaw(Device& device, const DDSRawImage& raw, DeviceScratchImage&
             // every plane's rows (CopyImage's own three cases)
             const size_t rows = compressed ? 1 : planar ? ComputeScanlines(format, d.height) : d.height;
             const size_t rowBytes = compressed ? std::min(d.slicePitch, from.slicePitch) : std::min(d.rowPitch, from.rowPitch);
-            dsts[i] = dxtex_image{ rowBytes, rows, int32_t(DXGI_FORMAT_R8_UNORM), compressed ? rowBytes : d.rowPitch, d.slicePitch, d.pixels };
+            dsts[i] = ImageOf(Image{ rowBytes, rows, DXGI_FORMAT_R8_UNORM, compressed ? rowBytes : d.rowPitch, d.slicePitch, d.pixels });
             if (compressed) pitches[i] = rowBytes;
         }
     }
-    DeviceTemp temp(device);
-    hr = dxtex_device_alloc(device.Get(), raw.payloadBytes, &temp.p);
-    if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.payload, raw.payloadBytes);          // the caller's bytes are free to go on return
-    if (SUCCEEDED(hr)) hr = dxtex_dds_unpack_device(device.Get(), temp.p, raw.payloadBytes, raw.op, raw.opaque ? 1u : 0u, raw.paletted ? raw.palette : nullptr,
-                                                    dsts.data(), offsets.data(), pitches.data(), n);
+    hr = UploadAndUnpack(device, raw.payload, raw.payloadBytes, [&](void* p)
+    { return dxtex_dds_unpack_device(device.Get(), p, raw.payloadBytes, raw.op, raw.opaque ? 1u : 0u, raw.paletted ? raw.palette : nullptr, dsts.data(), offsets.data(), pitches.data(), n); });
     if (FAILED(hr)) image.Release();
     return hr;
 }
@@ -668,11 +657,7 @@ HRESULT LoadFromDDSMemory(Device& device, const void* pSource, size_t size, DDS_
 HRESULT LoadFromDDSFileEx(Device& device, const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DDSMetaData* ddPixelFormat, DeviceScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, kMinHeader);
-    if (FAILED(hr)) return hr;
-    return LoadFromDDSMemoryEx(device, buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, ddPixelFormat, image);
+    return LoadFile(szFile, ReadAtLeast<kMinHeader>, [&](const uint8_t* p, size_t n) { return LoadFromDDSMemoryEx(device, p, n, flags, metadata, ddPixelFormat, image); });
 }
 
 HRESULT LoadFromDDSFile(Device& device, const char* szFile, DDS_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
@@ -886,13 +871,10 @@ HRESULT SaveDDS(Device* device, const Image* images, size_t nimages, const TexMe
         for (size_t i = 0; i < expected; ++i)
         {
             if (sp[i] > remaining - total) { blob.Release(); return E_FAIL; }
-            srcs[i] = dxtex_image{ images[i].width, images[i].height, int32_t(images[i].format), images[i].rowPitch, images[i].slicePitch, images[i].pixels };
+            srcs[i] = ImageOf(images[i]);
             offsets[i] = total; total += sp[i];
         }
-        DeviceTemp temp(*device);
-        hr = dxtex_device_alloc(device->Get(), total, &temp.p);
-        if (SUCCEEDED(hr)) hr = dxtex_dds_pack24_device(device->Get(), srcs.data(), offsets.data(), rp.data(), expected, temp.p, total);
-        if (SUCCEEDED(hr)) hr = dxtex_memcpy_d2h(device->Get(), d, temp.p, total);          // returns when the rows have landed
+        hr = PackAndDownload(*device, total, d, [&](void* p) { return dxtex_dds_pack24_device(device->Get(), srcs.data(), offsets.data(), rp.data(), expected, p, total); });
         if (FAILED(hr)) blob.Release();
         return hr;
     }
@@ -969,11 +951,7 @@ HRESULT SaveToDDSMemory(const Image& image, DDS_FLAGS flags, Blob& blob) noexcep
 
 HRESULT SaveToDDSFile(const Image* images, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToDDSMemory(images, nimages, metadata, flags, blob);
-    if (FAILED(hr)) return hr;
-    return WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToDDSMemory(images, nimages, metadata, flags, blob); });
 }
 
 HRESULT SaveToDDSFile(const Image& image, DDS_FLAGS flags, const char* szFile) noexcept
@@ -994,11 +972,7 @@ HRESULT SaveToDDSMemory(Device& device, const Image& deviceImage, DDS_FLAGS flag
 
 HRESULT SaveToDDSFile(Device& device, const Image* deviceImages, size_t nimages, const TexMetadata& metadata, DDS_FLAGS flags, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToDDSMemory(device, deviceImages, nimages, metadata, flags, blob);
-    if (FAILED(hr)) return hr;
-    return WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToDDSMemory(device, deviceImages, nimages, metadata, flags, blob); });
 }
 
 HRESULT SaveToDDSFile(Device& device, const Image& deviceImage, DDS_FLAGS flags, const char* szFile) noexcept

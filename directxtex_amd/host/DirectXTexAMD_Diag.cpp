@@ -2,8 +2,7 @@
 // (Texdiag/texdiag.cpp:698-787, :906-1226, :1229-1320) over the C ABI's dxtex_analyze_device, dxtex_analyze_bc_device,
 // dxtex_compute_mse_flags_device and dxtex_difference_device. Every overload works on DeviceScratchImages: a host image goes up once,
 // Decompress and Convert run on the device, and nothing but the figures (or Difference's finished map) comes back.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 
 #include <cmath>
 #include <new>
@@ -13,7 +12,6 @@ namespace DirectXTexAMD
 {
 namespace
 {
-dxtex_image View(const Image& i) noexcept { return dxtex_image{ i.width, i.height, int32_t(i.format), i.rowPitch, i.slicePitch, i.pixels }; }
 
 inline bool Resident(const Device& device, const DeviceScratchImage& src) noexcept { return src.GetImages() && src.GetDevice() == &device; }
 
@@ -78,7 +76,7 @@ HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, size_t inde
     hr = Expanded(device, image2, t2, eb); if (FAILED(hr)) return hr;
     if (index1 >= ea->GetImageCount() || index2 >= eb->GetImageCount()) return E_POINTER;
     a = ea->GetImages() + index1; b = eb->GetImages() + index2;
-    const dxtex_image va = View(*a), vb = View(*b);
+    const dxtex_image va = ImageOf(*a), vb = ImageOf(*b);
     double v[4] = { 0, 0, 0, 0 };
     hr = dxtex_compute_mse_flags_device(device.Get(), &va, &vb, uint32_t(flags), v);
     if (FAILED(hr)) return hr;
@@ -117,7 +115,7 @@ HRESULT Analyze(Device& device, const DeviceScratchImage& images, AnalyzeData* r
     {
         std::vector<dxtex_image> v(n);
         std::vector<dxtex_image_stats> s(n);
-        for (size_t i = 0; i < n; ++i) v[i] = View(e->GetImages()[i]);
+        for (size_t i = 0; i < n; ++i) v[i] = ImageOf(e->GetImages()[i]);
         hr = dxtex_analyze_device(device.Get(), v.data(), n, s.data());
         if (FAILED(hr)) return hr;
         for (size_t i = 0; i < n; ++i) Fill(results[i], s[i]);
@@ -150,7 +148,7 @@ HRESULT AnalyzeBC(Device& device, const DeviceScratchImage& images, AnalyzeBCDat
     if (!IsCompressed(images.GetMetadata().format)) return HRESULT_E_NOT_SUPPORTED;        // texdiag.cpp:933
     for (size_t i = 0; i < images.GetImageCount(); ++i)
     {
-        const dxtex_image v = View(images.GetImages()[i]);
+        const dxtex_image v = ImageOf(images.GetImages()[i]);
         const HRESULT hr = dxtex_analyze_bc_device(device.Get(), &v, results[i].blockHist, &results[i].blocks);
         if (FAILED(hr)) return hr;
     }
@@ -195,7 +193,7 @@ HRESULT Difference(Device& device, const DeviceScratchImage& image1, const Devic
     hr = diff.Initialize(device, SingleImage(*a)); if (FAILED(hr)) return hr;
     const Image* d = diff.GetImage(0, 0, 0);
     if (!d) return E_POINTER;
-    const dxtex_image va = View(*a), vb = View(*b), vd = View(*d);
+    const dxtex_image va = ImageOf(*a), vb = ImageOf(*b), vd = ImageOf(*d);
     hr = dxtex_difference_device(device.Get(), &va, &vb, &vd, diffColor, threshold);
     if (FAILED(hr)) return hr;
     if (format == a->format) { result = static_cast<DeviceScratchImage&&>(diff); return S_OK; }        // :1313-1317

@@ -308,12 +308,8 @@ HRESULT LoadFromHDRMemory(const void* pSource, size_t size, TexMetadata* metadat
 
 HRESULT LoadFromHDRFile(const char* szFile, TexMetadata* metadata, ScratchImage& image) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    image.Release();
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, sizeof(kSignature));
-    if (FAILED(hr)) return hr;
-    return LoadFromHDRMemory(buf.GetBufferPointer(), buf.GetBufferSize(), metadata, image);
+    if (szFile) image.Release();
+    return LoadFile(szFile, ReadAtLeast<sizeof(kSignature)>, [&](const uint8_t* p, size_t n) { return LoadFromHDRMemory(p, n, metadata, image); });
 }
 
 namespace
@@ -323,12 +319,9 @@ namespace
     {
         if (!image.pixels) return E_POINTER;
         if (image.width > INT16_MAX || image.height > INT16_MAX) return HRESULT_E_NOT_SUPPORTED;
-        switch (image.format)
-        {
-        case DXGI_FORMAT_R32G32B32A32_FLOAT: case DXGI_FORMAT_R16G16B16A16_FLOAT: channels = 4; return S_OK;
-        case DXGI_FORMAT_R32G32B32_FLOAT: channels = 3; return S_OK;
-        default: return HRESULT_E_NOT_SUPPORTED;
-        }
+        const uint32_t texel = dxtex::rgbe_source_bytes(int(image.format));          // the encoder's table
+        channels = texel == 12 ? 3 : 4;
+        return texel ? S_OK : HRESULT_E_NOT_SUPPORTED;
     }
 
     // The file around the texels: header, then every row run-length encoded where that fits, raw otherwise. row(y, rgbe) leaves the
@@ -388,22 +381,14 @@ HRESULT SaveToHDRMemory(const Image& image, Blob& blob) noexcept
 
 HRESULT SaveToHDRFile(const Image& image, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToHDRMemory(image, blob);
-    if (FAILED(hr)) return hr;
-    return WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToHDRMemory(image, blob); });
 }
 
 // ---- resident forms: the texels travel as RGBE, the float pass runs on the device (dxtex_rgbe_decode_device / dxtex_rgbe_encode_device) ----
 HRESULT LoadFromHDRFileRGBE(const char* szFile, TexMetadata* metadata, float& exposure, Blob& rgbe) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    rgbe.Release();
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, sizeof(kSignature));
-    if (FAILED(hr)) return hr;
-    return LoadFromHDRMemoryRGBE(buf.GetBufferPointer(), buf.GetBufferSize(), metadata, exposure, rgbe);
+    if (szFile) rgbe.Release();
+    return LoadFile(szFile, ReadAtLeast<sizeof(kSignature)>, [&](const uint8_t* p, size_t n) { return LoadFromHDRMemoryRGBE(p, n, metadata, exposure, rgbe); });
 }
 
 HRESULT UploadHDRRows(Device& device, const TexMetadata& metadata, float exposure, const Blob& rgbe, DeviceScratchImage& image) noexcept
@@ -412,22 +397,15 @@ HRESULT UploadHDRRows(Device& device, const TexMetadata& metadata, float exposur
     if (!device) return E_POINTER;
     if (!rgbe.GetBufferPointer() || metadata.format != DXGI_FORMAT_R32G32B32A32_FLOAT || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1 ||
         rgbe.GetBufferSize() != metadata.width * metadata.height * 4) return E_INVALIDARG;
-    HRESULT hr = image.Initialize(device, metadata);
-    if (FAILED(hr)) return hr;
-    const Image* img = image.GetImage(0, 0, 0);
-    if (!img) { image.Release(); return E_POINTER; }
-    DeviceTemp temp(device);
-    hr = dxtex_device_alloc(device.Get(), rgbe.GetBufferSize(), &temp.p);
-    // the synchronous copy: the host rows are free to go when it returns
-    if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, rgbe.GetBufferPointer(), rgbe.GetBufferSize());
-    if (SUCCEEDED(hr))
+    return InitializeAndFill(device, metadata, image, [&](const Image& img)
     {
-        const dxtex_image s = { metadata.width, metadata.height, int32_t(DXGI_FORMAT_R8G8B8A8_UINT), metadata.width * 4, rgbe.GetBufferSize(), static_cast<uint8_t*>(temp.p) };
-        const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
-        hr = dxtex_rgbe_decode_device(device.Get(), &s, &d, exposure);
-    }
-    if (FAILED(hr)) image.Release();
-    return hr;
+        return UploadAndUnpack(device, rgbe.GetBufferPointer(), rgbe.GetBufferSize(), [&](void* p)
+        {
+            const dxtex_image s = ImageOf(Image{ metadata.width, metadata.height, DXGI_FORMAT_R8G8B8A8_UINT, metadata.width * 4, rgbe.GetBufferSize(), static_cast<uint8_t*>(p) });
+            const dxtex_image d = ImageOf(img);
+            return dxtex_rgbe_decode_device(device.Get(), &s, &d, exposure);
+        });
+    });
 }
 
 HRESULT LoadFromHDRMemory(Device& device, const void* pSource, size_t size, TexMetadata* metadata, DeviceScratchImage& image) noexcept
@@ -446,11 +424,7 @@ HRESULT LoadFromHDRMemory(Device& device, const void* pSource, size_t size, TexM
 HRESULT LoadFromHDRFile(Device& device, const char* szFile, TexMetadata* metadata, DeviceScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, sizeof(kSignature));
-    if (FAILED(hr)) return hr;
-    return LoadFromHDRMemory(device, buf.GetBufferPointer(), buf.GetBufferSize(), metadata, image);
+    return LoadFile(szFile, ReadAtLeast<sizeof(kSignature)>, [&](const uint8_t* p, size_t n) { return LoadFromHDRMemory(device, p, n, metadata, image); });
 }
 
 HRESULT SaveToHDRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept
@@ -463,25 +437,18 @@ HRESULT SaveToHDRMemory(Device& device, const Image& deviceImage, Blob& blob) no
     Blob rgbe;
     hr = rgbe.Initialize(bytes);
     if (FAILED(hr)) return hr;
-    DeviceTemp temp(device);
-    hr = dxtex_device_alloc(device.Get(), bytes, &temp.p);
-    if (SUCCEEDED(hr))
+    hr = PackAndDownload(device, bytes, rgbe.GetBufferPointer(), [&](void* p)
     {
-        const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
-        const dxtex_image d = { deviceImage.width, deviceImage.height, int32_t(DXGI_FORMAT_R8G8B8A8_UINT), rowPitch, bytes, static_cast<uint8_t*>(temp.p) };
-        hr = dxtex_rgbe_encode_device(device.Get(), &s, &d);
-    }
-    if (SUCCEEDED(hr)) hr = dxtex_memcpy_d2h(device.Get(), rgbe.GetBufferPointer(), temp.p, bytes);          // returns when the rows have landed
+        const dxtex_image s = ImageOf(deviceImage);
+        const dxtex_image d = ImageOf(Image{ deviceImage.width, deviceImage.height, DXGI_FORMAT_R8G8B8A8_UINT, rowPitch, bytes, static_cast<uint8_t*>(p) });
+        return dxtex_rgbe_encode_device(device.Get(), &s, &d);
+    });
     if (FAILED(hr)) return hr;
     return WriteFile(deviceImage.width, deviceImage.height, blob, [&](size_t y, uint8_t*) -> const uint8_t* { return rgbe.GetBufferPointer() + y * rowPitch; });
 }
 
 HRESULT SaveToHDRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToHDRMemory(device, deviceImage, blob);
-    if (FAILED(hr)) return hr;
-    return WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToHDRMemory(device, deviceImage, blob); });
 }
 } // namespace DirectXTexAMD

@@ -592,11 +592,7 @@ HRESULT LoadFromJPEGMemoryRaw(const void* pSource, size_t size, JPEG_FLAGS flags
 HRESULT LoadFromJPEGFileRaw(const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, JPEGRawImage& raw) noexcept
 {
     raw.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadJPEGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return LoadFromJPEGMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, raw);
+    return LoadFile(szFile, ReadJPEGFile, [&](const uint8_t* p, size_t n) { return LoadFromJPEGMemoryRaw(p, n, flags, metadata, raw); });
 }
 
 HRESULT GetMetadataFromJPEGMemory(const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata& metadata) noexcept
@@ -612,11 +608,7 @@ HRESULT GetMetadataFromJPEGMemory(const void* pSource, size_t size, JPEG_FLAGS f
 
 HRESULT GetMetadataFromJPEGFile(const char* szFile, JPEG_FLAGS flags, TexMetadata& metadata) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadJPEGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return GetMetadataFromJPEGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata);
+    return LoadFile(szFile, ReadJPEGFile, [&](const uint8_t* p, size_t n) { return GetMetadataFromJPEGMemory(p, n, flags, metadata); });
 }
 
 HRESULT LoadFromJPEGMemory(const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
@@ -667,11 +659,7 @@ HRESULT LoadFromJPEGMemory(const void* pSource, size_t size, JPEG_FLAGS flags, T
 HRESULT LoadFromJPEGFile(const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadJPEGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return LoadFromJPEGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+    return LoadFile(szFile, ReadJPEGFile, [&](const uint8_t* p, size_t n) { return LoadFromJPEGMemory(p, n, flags, metadata, image); });
 }
 
 // ---- resident forms: the coefficients travel as the file has them, everything behind them runs on the device (dxtex_jpeg_decode_device) ----
@@ -681,23 +669,17 @@ HRESULT UploadJPEGRaw(Device& device, const TexMetadata& metadata, const JPEGRaw
     if (!device) return E_POINTER;
     if (!raw.coefficients || !raw.coefficientCount || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1) return E_INVALIDARG;
     if (metadata.width != raw.width || metadata.height != raw.height) return E_INVALIDARG;
-    HRESULT hr = image.Initialize(device, metadata);
-    if (FAILED(hr)) return hr;
-    const Image* img = image.GetImage(0, 0, 0);
-    if (!img) { image.Release(); return E_POINTER; }
-    // the coefficients go to the start of an allocation of their own: aligned, so every block is one 128-byte read
-    const size_t bytes = raw.coefficientCount * sizeof(int16_t);
-    DeviceTemp temp(device);
-    hr = dxtex_device_alloc(device.Get(), bytes, &temp.p);
-    if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.coefficients, bytes);          // the caller's coefficients are free to go on return
-    if (SUCCEEDED(hr))
+    return InitializeAndFill(device, metadata, image, [&](const Image& img)
     {
-        const dxtex_jpeg_frame f = FrameOf(raw);
-        const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
-        hr = dxtex_jpeg_decode_device(device.Get(), temp.p, bytes, &f, &d);
-    }
-    if (FAILED(hr)) image.Release();
-    return hr;
+        // the coefficients start an allocation of their own: every block is one aligned 128-byte read
+        const size_t bytes = raw.coefficientCount * sizeof(int16_t);
+        return UploadAndUnpack(device, raw.coefficients, bytes, [&](void* p)
+        {
+            const dxtex_jpeg_frame f = FrameOf(raw);
+            const dxtex_image d = ImageOf(img);
+            return dxtex_jpeg_decode_device(device.Get(), p, bytes, &f, &d);
+        });
+    });
 }
 
 HRESULT LoadFromJPEGMemory(Device& device, const void* pSource, size_t size, JPEG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
@@ -715,11 +697,7 @@ HRESULT LoadFromJPEGMemory(Device& device, const void* pSource, size_t size, JPE
 HRESULT LoadFromJPEGFile(Device& device, const char* szFile, JPEG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadJPEGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return LoadFromJPEGMemory(device, file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+    return LoadFile(szFile, ReadJPEGFile, [&](const uint8_t* p, size_t n) { return LoadFromJPEGMemory(device, p, n, flags, metadata, image); });
 }
 
 // ---- the writer. The same split run backwards: SaveJPEGRaw is the byte-serial half - markers, tables, baseline Huffman coding of a frame's
@@ -826,14 +804,9 @@ namespace
     HRESULT FrameFor(const Image& image, dxtex_jpeg_frame& f) noexcept
     {
         if (!image.pixels) return E_POINTER;
-        bool grey = false;
-        switch (image.format)
-        {
-        case DXGI_FORMAT_R8_UNORM: grey = true; break;
-        case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB:
-        case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: break;
-        default: return HRESULT_E_NOT_SUPPORTED;
-        }
+        const int texel = dxtex::jpeg_texel_of(int(image.format));          // the coder's table
+        if (texel < 0) return HRESULT_E_NOT_SUPPORTED;
+        const bool grey = texel == dxtex::JPEG_TEXEL_GREY;
         if (!image.width || !image.height || image.width > 65535 || image.height > 65535) return E_INVALIDARG;          // SOF0 holds 16 bits
         f = dxtex_jpeg_frame();
         f.width = uint32_t(image.width); f.height = uint32_t(image.height);
@@ -958,7 +931,7 @@ HRESULT SaveToJPEGMemory(const Image& image, JPEG_FLAGS, Blob& blob) noexcept
     JPEGRawImage raw;
     hr = RawFor(f, raw);
     if (FAILED(hr)) return hr;
-    const bool bgr = image.format != DXGI_FORMAT_R8G8B8A8_UNORM && image.format != DXGI_FORMAT_R8G8B8A8_UNORM_SRGB;
+    const bool bgr = dxtex::jpeg_texel_of(int(image.format)) == dxtex::JPEG_TEXEL_BGRX;
     const dxtex::JpegSource source = { image.pixels, image.rowPitch, f.width, f.height, f.components == 1, bgr };
     int16_t* coefficients = reinterpret_cast<int16_t*>(raw.storage.GetBufferPointer());
     const uint32_t hmax = f.component[0].h, vmax = f.component[0].v;
@@ -984,10 +957,7 @@ HRESULT SaveToJPEGMemory(const Image& image, JPEG_FLAGS, Blob& blob) noexcept
 
 HRESULT SaveToJPEGFile(const Image& image, JPEG_FLAGS flags, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToJPEGMemory(image, flags, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToJPEGMemory(image, flags, blob); });
 }
 
 // ---- resident forms: both kernels run on the device image, the coefficients come down once - 2 bytes a texel for grey, 3 for colour - and
@@ -1003,22 +973,13 @@ HRESULT SaveToJPEGMemory(Device& device, const Image& deviceImage, JPEG_FLAGS, B
     hr = RawFor(f, raw);
     if (FAILED(hr)) return hr;
     const size_t bytes = raw.coefficientCount * sizeof(int16_t);
-    DeviceTemp temp(device);
-    hr = dxtex_device_alloc(device.Get(), bytes, &temp.p);
-    if (SUCCEEDED(hr))
-    {
-        const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
-        hr = dxtex_jpeg_encode_device(device.Get(), &s, &f, temp.p, bytes);
-    }
-    if (SUCCEEDED(hr)) hr = dxtex_memcpy_d2h(device.Get(), raw.storage.GetBufferPointer(), temp.p, bytes);          // returns when the coefficients have landed
+    const dxtex_image s = ImageOf(deviceImage);
+    hr = PackAndDownload(device, bytes, raw.storage.GetBufferPointer(), [&](void* p) { return dxtex_jpeg_encode_device(device.Get(), &s, &f, p, bytes); });
     return FAILED(hr) ? hr : SaveJPEGRaw(raw, blob);
 }
 
 HRESULT SaveToJPEGFile(Device& device, const Image& deviceImage, JPEG_FLAGS flags, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToJPEGMemory(device, deviceImage, flags, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToJPEGMemory(device, deviceImage, flags, blob); });
 }
 } // namespace DirectXTexAMD

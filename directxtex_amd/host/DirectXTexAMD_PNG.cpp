@@ -452,20 +452,12 @@ namespace
     HRESULT SaveChecks(const Image& image, FileShape& f) noexcept
     {
         if (!image.pixels) return E_POINTER;
-        f.srgbFormat = false; f.depth = 8;
-        switch (image.format)          // WriteImage :322-364
-        {
-        case DXGI_FORMAT_R8_UNORM: f.source = dxtex::PNG_SRC_R8; f.colorType = 0; break;
-        case DXGI_FORMAT_R16_UNORM: f.source = dxtex::PNG_SRC_R16; f.colorType = 0; f.depth = 16; break;
-        case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: f.srgbFormat = true; [[fallthrough]];
-        case DXGI_FORMAT_R8G8B8A8_UNORM: f.source = dxtex::PNG_SRC_RGBA8; f.colorType = 6; break;
-        case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: f.srgbFormat = true; [[fallthrough]];
-        case DXGI_FORMAT_B8G8R8A8_UNORM: f.source = dxtex::PNG_SRC_BGRA8; f.colorType = 6; break;
-        case DXGI_FORMAT_R16G16B16A16_UNORM: f.source = dxtex::PNG_SRC_RGBA16; f.colorType = 6; f.depth = 16; break;
-        case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: f.srgbFormat = true; [[fallthrough]];
-        case DXGI_FORMAT_B8G8R8X8_UNORM: f.source = dxtex::PNG_SRC_BGRX8; f.colorType = 2; break;
-        default: return HRESULT_E_NOT_SUPPORTED;
-        }
+        // the writer's table (WriteImage :322-364): one channel is grey, B8G8R8X8 colour without alpha, the rest colour with it
+        f.source = dxtex::png_pack_source(int(image.format));
+        if (f.source < 0) return HRESULT_E_NOT_SUPPORTED;
+        f.srgbFormat = IsSRGB(image.format);
+        f.depth = (f.source == dxtex::PNG_SRC_R16 || f.source == dxtex::PNG_SRC_RGBA16) ? 16 : 8;
+        f.colorType = (f.source == dxtex::PNG_SRC_R8 || f.source == dxtex::PNG_SRC_R16) ? 0 : f.source == dxtex::PNG_SRC_BGRX8 ? 2 : 6;
         if (!image.width || !image.height || image.width > kSideLimit || image.height > kSideLimit) return E_INVALIDARG;
         return S_OK;
     }
@@ -574,18 +566,9 @@ namespace
         const HRESULT hr = SaveChecks(deviceImage, f);
         if (FAILED(hr)) return hr;
         if (!device) return E_POINTER;
+        const dxtex_image s = ImageOf(deviceImage);
         return WriteFile(deviceImage, flags, f, blob, [&](uint8_t* d, size_t bytes)
-        {
-            DeviceTemp temp(device);
-            HRESULT hr2 = dxtex_device_alloc(device.Get(), bytes, &temp.p);
-            if (SUCCEEDED(hr2))
-            {
-                const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
-                hr2 = dxtex_png_pack_device(device.Get(), &s, temp.p, bytes);
-            }
-            if (SUCCEEDED(hr2)) hr2 = dxtex_memcpy_d2h(device.Get(), d, temp.p, bytes);          // returns when the rows have landed
-            return hr2;
-        });
+        { return PackAndDownload(device, bytes, d, [&](void* p) { return dxtex_png_pack_device(device.Get(), &s, p, bytes); }); });
     }
 }
 
@@ -635,11 +618,8 @@ HRESULT LoadFromPNGMemoryRaw(const void* pSource, size_t size, PNG_FLAGS flags, 
 HRESULT LoadFromPNGFileRaw(const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, PNGRawImage& raw) noexcept
 {
     raw.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadPNGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return LoadFromPNGMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, raw);
+    // the rows are always inflated into storage of their own: the file is not kept
+    return LoadFile(szFile, ReadPNGFile, [&](const uint8_t* p, size_t n) { return LoadFromPNGMemoryRaw(p, n, flags, metadata, raw); });
 }
 
 HRESULT GetMetadataFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata& metadata) noexcept
@@ -650,11 +630,7 @@ HRESULT GetMetadataFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS fla
 
 HRESULT GetMetadataFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata& metadata) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadPNGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return GetMetadataFromPNGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata);
+    return LoadFile(szFile, ReadPNGFile, [&](const uint8_t* p, size_t n) { return GetMetadataFromPNGMemory(p, n, flags, metadata); });
 }
 
 HRESULT LoadFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
@@ -683,21 +659,14 @@ HRESULT LoadFromPNGMemory(const void* pSource, size_t size, PNG_FLAGS flags, Tex
 HRESULT LoadFromPNGFile(const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadPNGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return LoadFromPNGMemory(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+    return LoadFile(szFile, ReadPNGFile, [&](const uint8_t* p, size_t n) { return LoadFromPNGMemory(p, n, flags, metadata, image); });
 }
 
 HRESULT SaveToPNGMemory(const Image& image, PNG_FLAGS flags, Blob& blob) noexcept { return SaveHost(image, flags, blob); }
 
 HRESULT SaveToPNGFile(const Image& image, PNG_FLAGS flags, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveHost(image, flags, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveHost(image, flags, blob); });
 }
 
 // ---- resident forms: the rows travel as the file has them, the per-texel pass runs on the device (dxtex_png_unpack_device / dxtex_png_pack_device) ----
@@ -707,27 +676,15 @@ HRESULT UploadPNGRaw(Device& device, const TexMetadata& metadata, const PNGRawIm
     if (!device) return E_POINTER;
     if (!raw.rows || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1) return E_INVALIDARG;
     if (raw.rowsBytes != raw.rowBytes * metadata.height) return E_INVALIDARG;
-    HRESULT hr = image.Initialize(device, metadata);
-    if (FAILED(hr)) return hr;
-    const Image* img = image.GetImage(0, 0, 0);
-    if (!img) { image.Release(); return E_POINTER; }
-    const bool native = (raw.kind == DXTEX_PNG_G8 || raw.kind == DXTEX_PNG_RGBA8) && !(raw.flags & DXTEX_PNG_BGR);
-    if (native && img->rowPitch == raw.rowBytes)
-        hr = dxtex_memcpy_h2d(device.Get(), img->pixels, raw.rows, raw.rowsBytes);          // the rows are the image: one copy, no kernel
-    else
+    return InitializeAndFill(device, metadata, image, [&](const Image& img) -> HRESULT
     {
-        // the rows go to the start of an allocation of their own: aligned, so a width of whole groups takes the wide route
-        DeviceTemp temp(device);
-        hr = dxtex_device_alloc(device.Get(), raw.rowsBytes, &temp.p);
-        if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.rows, raw.rowsBytes);          // the caller's bytes are free to go on return
-        if (SUCCEEDED(hr))
-        {
-            const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
-            hr = dxtex_png_unpack_device(device.Get(), temp.p, raw.rowsBytes, raw.kind, raw.flags, raw.paletteCount ? raw.palette : nullptr, raw.paletteCount, &d);
-        }
-    }
-    if (FAILED(hr)) image.Release();
-    return hr;
+        const bool native = (raw.kind == DXTEX_PNG_G8 || raw.kind == DXTEX_PNG_RGBA8) && !(raw.flags & DXTEX_PNG_BGR);
+        if (native && img.rowPitch == raw.rowBytes) return dxtex_memcpy_h2d(device.Get(), img.pixels, raw.rows, raw.rowsBytes);          // the rows are the image: one copy, no kernel
+        // the rows start an allocation of their own: a width of whole groups takes the wide route
+        const dxtex_image d = ImageOf(img);
+        return UploadAndUnpack(device, raw.rows, raw.rowsBytes, [&](void* p)
+        { return dxtex_png_unpack_device(device.Get(), p, raw.rowsBytes, raw.kind, raw.flags, raw.paletteCount ? raw.palette : nullptr, raw.paletteCount, &d); });
+    });
 }
 
 HRESULT LoadFromPNGMemory(Device& device, const void* pSource, size_t size, PNG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
@@ -745,20 +702,13 @@ HRESULT LoadFromPNGMemory(Device& device, const void* pSource, size_t size, PNG_
 HRESULT LoadFromPNGFile(Device& device, const char* szFile, PNG_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadPNGFile(szFile, file);
-    if (FAILED(hr)) return hr;
-    return LoadFromPNGMemory(device, file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, image);
+    return LoadFile(szFile, ReadPNGFile, [&](const uint8_t* p, size_t n) { return LoadFromPNGMemory(device, p, n, flags, metadata, image); });
 }
 
 HRESULT SaveToPNGMemory(Device& device, const Image& deviceImage, PNG_FLAGS flags, Blob& blob) noexcept { return SaveResident(device, deviceImage, flags, blob); }
 
 HRESULT SaveToPNGFile(Device& device, const Image& deviceImage, PNG_FLAGS flags, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveResident(device, deviceImage, flags, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveResident(device, deviceImage, flags, blob); });
 }
 } // namespace DirectXTexAMD

@@ -89,7 +89,7 @@ namespace
                     if (u > uint32_t(INT32_MAX)) return HRESULT_E_NOT_SUPPORTED;
                     if (uint64_t(width) * uint64_t(u) * 4 > UINT32_MAX) return HRESULT_E_ARITHMETIC_OVERFLOW;
                     height = u;
-                    SetMetadata(metadata, width, height, DXGI_FORMAT_R8G8B8A8_UNORM);
+                    SetMetadata(metadata, width, height, DXGI_FORMAT(dxtex::pnm_unpack_format(dxtex::PNM_P6)));
                     if (ascii)
                     {
                         // The reference allocates the image here. Every failure from here on in a P3 file is E_FAIL, and a texel takes
@@ -173,13 +173,13 @@ namespace
     // LoadFromPortablePixMapHDR (:452-684) up to its texel loops
     HRESULT ParsePFM(const uint8_t* data, size_t size, TexMetadata& metadata, PNMRawImage& raw) noexcept
     {
-        DXGI_FORMAT format; uint32_t kind;
+        uint32_t kind;
         switch (data[1])          // :473-481
         {
-        case 'f': format = DXGI_FORMAT_R32_FLOAT; kind = DXTEX_PNM_Pf; break;
-        case 'F': format = DXGI_FORMAT_R32G32B32A32_FLOAT; kind = DXTEX_PNM_PF; break;
-        case 'h': format = DXGI_FORMAT_R16_FLOAT; kind = DXTEX_PNM_Ph; break;
-        case 'H': format = DXGI_FORMAT_R16G16B16A16_FLOAT; kind = DXTEX_PNM_PH; break;
+        case 'f': kind = DXTEX_PNM_Pf; break;
+        case 'F': kind = DXTEX_PNM_PF; break;
+        case 'h': kind = DXTEX_PNM_Ph; break;
+        case 'H': kind = DXTEX_PNM_PH; break;
         default: return E_FAIL;
         }
         const uint8_t* p = data + 3;
@@ -210,7 +210,7 @@ namespace
 
         const uint64_t need = uint64_t(width) * dxtex::pnm_file_bytes(int(kind)) * uint64_t(height);
         if (uint64_t(left) < need) return HRESULT_E_HANDLE_EOF;          // :575-577
-        SetMetadata(metadata, width, height, format);
+        SetMetadata(metadata, width, height, DXGI_FORMAT(dxtex::pnm_unpack_format(int(kind))));
         // a zero dimension: what ScratchImage::Initialize2D answers (:589)
         std::unique_ptr<Image[]> images; size_t nimages, pixelBytes, mips;
         hr = LayoutScratchImage(metadata, CP_FLAGS_NONE, images, nimages, pixelBytes, mips);
@@ -225,19 +225,11 @@ namespace
     HRESULT SaveChecks(const Image& image, bool hdr, FileShape& f) noexcept
     {
         if (!image.pixels) return E_POINTER;
-        f.kind = hdr ? DXTEX_PNM_PF : DXTEX_PNM_P6;
-        switch (image.format)
-        {
-        case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: f.source = hdr ? -1 : dxtex::PNM_SRC_RGBA8; break;
-        case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB:
-            f.source = hdr ? -1 : dxtex::PNM_SRC_BGRA8; break;
-        case DXGI_FORMAT_R32G32B32A32_FLOAT: f.source = hdr ? dxtex::PNM_SRC_RGBA32F : -1; break;
-        case DXGI_FORMAT_R32G32B32_FLOAT: f.source = hdr ? dxtex::PNM_SRC_RGB32F : -1; break;
-        case DXGI_FORMAT_R16G16B16A16_FLOAT: f.source = hdr ? dxtex::PNM_SRC_RGBA16F : -1; break;
-        case DXGI_FORMAT_R32_FLOAT: f.source = hdr ? dxtex::PNM_SRC_R32F : -1; if (hdr) f.kind = DXTEX_PNM_Pf; break;
-        default: f.source = -1; break;
-        }
+        // the writer's table: a format's source, written as a .ppm by the plain saver and as a .pfm by the HDR one
+        f.source = dxtex::pnm_pack_source(int(image.format));
         if (f.source < 0) return HRESULT_E_NOT_SUPPORTED;
+        f.kind = uint32_t(dxtex::pnm_source_kind(f.source));
+        if ((f.kind != DXTEX_PNM_P6) != hdr) return HRESULT_E_NOT_SUPPORTED;
         if (!image.width || !image.height) return E_INVALIDARG;
         if (image.width > size_t(INT32_MAX) || image.height > size_t(INT32_MAX)) return HRESULT_E_NOT_SUPPORTED;
         const int len = hdr ? std::snprintf(f.header, sizeof(f.header), "P%c\n%zu %zu\n-1.000000\n", f.kind == DXTEX_PNM_Pf ? 'f' : 'F', image.width, image.height)
@@ -285,18 +277,9 @@ namespace
         const HRESULT hr = SaveChecks(deviceImage, hdr, f);
         if (FAILED(hr)) return hr;
         if (!device) return E_POINTER;
-        return WriteFile(deviceImage, f, blob, [&](uint8_t* d, size_t bytes)
-        {
-            DeviceTemp temp(device);
-            HRESULT hr2 = dxtex_device_alloc(device.Get(), bytes, &temp.p);
-            if (SUCCEEDED(hr2))
-            {
-                const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
-                hr2 = dxtex_pnm_pack_device(device.Get(), &s, f.kind, temp.p, bytes);
-            }
-            if (SUCCEEDED(hr2)) hr2 = dxtex_memcpy_d2h(device.Get(), d, temp.p, bytes);          // straight behind the header; returns when the rows have landed
-            return hr2;
-        });
+        const dxtex_image s = ImageOf(deviceImage);
+        return WriteFile(deviceImage, f, blob, [&](uint8_t* d, size_t bytes)          // the rows land straight behind the header
+        { return PackAndDownload(device, bytes, d, [&](void* p) { return dxtex_pnm_pack_device(device.Get(), &s, f.kind, p, bytes); }); });
     }
 }
 
@@ -324,13 +307,8 @@ HRESULT LoadFromPortablePixMapMemoryRaw(const void* pSource, size_t size, TexMet
 HRESULT LoadFromPortablePixMapFileRaw(const char* szFile, TexMetadata* metadata, PNMRawImage& raw) noexcept
 {
     raw.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    HRESULT hr = ReadAll(szFile, file, 1);
-    if (FAILED(hr)) return hr;
-    hr = LoadFromPortablePixMapMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), metadata, raw);
-    if (SUCCEEDED(hr) && !raw.ascii) raw.storage.Swap(file);          // the payload points into the file: keep it
-    return hr;
+    // anything but a P3 file: the payload points into the file, and raw keeps it
+    return LoadFile(szFile, ReadAtLeast<1>, [&](const uint8_t* p, size_t n) { return LoadFromPortablePixMapMemoryRaw(p, n, metadata, raw); }, &raw.storage);
 }
 
 HRESULT GetMetadataFromPortablePixMapMemory(const void* pSource, size_t size, TexMetadata& metadata) noexcept
@@ -378,11 +356,7 @@ HRESULT LoadFromPortablePixMapMemory(const void* pSource, size_t size, TexMetada
 HRESULT LoadFromPortablePixMapFile(const char* szFile, TexMetadata* metadata, ScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadAll(szFile, file, 1);
-    if (FAILED(hr)) return hr;
-    return LoadFromPortablePixMapMemory(file.GetBufferPointer(), file.GetBufferSize(), metadata, image);
+    return LoadFile(szFile, ReadAtLeast<1>, [&](const uint8_t* p, size_t n) { return LoadFromPortablePixMapMemory(p, n, metadata, image); });
 }
 
 HRESULT SaveToPortablePixMapMemory(const Image& image, Blob& blob) noexcept { return SaveHost(image, false, blob); }
@@ -390,18 +364,12 @@ HRESULT SaveToPortablePixMapHDRMemory(const Image& image, Blob& blob) noexcept {
 
 HRESULT SaveToPortablePixMapFile(const Image& image, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveHost(image, false, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveHost(image, false, blob); });
 }
 
 HRESULT SaveToPortablePixMapHDRFile(const Image& image, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveHost(image, true, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveHost(image, true, blob); });
 }
 
 // ---- resident forms: the samples travel as the file has them, the per-texel pass runs on the device (dxtex_pnm_unpack_device / dxtex_pnm_pack_device) ----
@@ -410,31 +378,19 @@ HRESULT UploadPortablePixMapRaw(Device& device, const TexMetadata& metadata, con
     image.Release();
     if (!device) return E_POINTER;
     if (!raw.payload || metadata.arraySize != 1 || metadata.mipLevels != 1 || metadata.depth != 1) return E_INVALIDARG;
-    HRESULT hr = image.Initialize(device, metadata);
-    if (FAILED(hr)) return hr;
-    const Image* img = image.GetImage(0, 0, 0);
-    if (!img) { image.Release(); return E_POINTER; }
-    if (raw.ascii)
+    return InitializeAndFill(device, metadata, image, [&](const Image& img) -> HRESULT
     {
-        // a P3 file's texels were decoded on the host, byte-serially, into the image's own words: tight rows into the image's pitch
-        if (raw.payloadBytes != img->width * img->height * 4) { image.Release(); return E_INVALIDARG; }
-        hr = img->rowPitch == img->width * 4 ? dxtex_memcpy_h2d(device.Get(), img->pixels, raw.payload, raw.payloadBytes) : E_UNEXPECTED;
-    }
-    else
-    {
-        // the payload goes to the start of an allocation of its own - whatever the header's length, the samples start aligned and a width
-        // that is a multiple of four takes the wide route
-        DeviceTemp temp(device);
-        hr = dxtex_device_alloc(device.Get(), raw.payloadBytes, &temp.p);
-        if (SUCCEEDED(hr)) hr = dxtex_memcpy_h2d(device.Get(), temp.p, raw.payload, raw.payloadBytes);          // the caller's bytes are free to go on return
-        if (SUCCEEDED(hr))
+        if (raw.ascii)
         {
-            const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
-            hr = dxtex_pnm_unpack_device(device.Get(), temp.p, raw.payloadBytes, raw.kind, raw.maxval, raw.bigEndian ? DXTEX_PNM_BIG_ENDIAN : 0u, &d);
+            // a P3 file's texels were decoded on the host, byte-serially, into the image's own words: tight rows into the image's pitch
+            if (raw.payloadBytes != img.width * img.height * 4) return E_INVALIDARG;
+            return img.rowPitch == img.width * 4 ? dxtex_memcpy_h2d(device.Get(), img.pixels, raw.payload, raw.payloadBytes) : E_UNEXPECTED;
         }
-    }
-    if (FAILED(hr)) image.Release();
-    return hr;
+        // the payload starts an allocation of its own: a width that is a multiple of four takes the wide route
+        const dxtex_image d = ImageOf(img);
+        return UploadAndUnpack(device, raw.payload, raw.payloadBytes, [&](void* p)
+        { return dxtex_pnm_unpack_device(device.Get(), p, raw.payloadBytes, raw.kind, raw.maxval, raw.bigEndian ? DXTEX_PNM_BIG_ENDIAN : 0u, &d); });
+    });
 }
 
 HRESULT LoadFromPortablePixMapMemory(Device& device, const void* pSource, size_t size, TexMetadata* metadata, DeviceScratchImage& image) noexcept
@@ -452,11 +408,7 @@ HRESULT LoadFromPortablePixMapMemory(Device& device, const void* pSource, size_t
 HRESULT LoadFromPortablePixMapFile(Device& device, const char* szFile, TexMetadata* metadata, DeviceScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    const HRESULT hr = ReadAll(szFile, file, 1);
-    if (FAILED(hr)) return hr;
-    return LoadFromPortablePixMapMemory(device, file.GetBufferPointer(), file.GetBufferSize(), metadata, image);
+    return LoadFile(szFile, ReadAtLeast<1>, [&](const uint8_t* p, size_t n) { return LoadFromPortablePixMapMemory(device, p, n, metadata, image); });
 }
 
 HRESULT SaveToPortablePixMapMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept { return SaveResident(device, deviceImage, false, blob); }
@@ -464,17 +416,11 @@ HRESULT SaveToPortablePixMapHDRMemory(Device& device, const Image& deviceImage, 
 
 HRESULT SaveToPortablePixMapFile(Device& device, const Image& deviceImage, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveResident(device, deviceImage, false, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveResident(device, deviceImage, false, blob); });
 }
 
 HRESULT SaveToPortablePixMapHDRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveResident(device, deviceImage, true, blob);
-    return FAILED(hr) ? hr : WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveResident(device, deviceImage, true, blob); });
 }
 } // namespace DirectXTexAMD

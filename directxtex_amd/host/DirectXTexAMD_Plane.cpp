@@ -1,7 +1,6 @@
 // ConvertToSinglePlane (DirectXTexConvert.cpp:5411-5523) on the host layer, over the C ABI's dxtex_convert_to_single_plane and
 // dxtex_convert_to_single_plane_device. The array and resident forms issue ONE batched submission for all images (array items x mips).
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 
 #include <new>
 #include <vector>
@@ -10,7 +9,6 @@ namespace DirectXTexAMD
 {
 namespace
 {
-dxtex_image View(const Image& i) noexcept { return dxtex_image{ i.width, i.height, int32_t(i.format), i.rowPitch, i.slicePitch, i.pixels }; }
 
 // the checks both array forms share, in the reference's order (:5458-5472); `format` receives PlanarToSingle(metadata.format)
 HRESULT CheckPlanarSet(const Image* srcImages, size_t nimages, const TexMetadata& metadata, DXGI_FORMAT& format) noexcept
@@ -56,7 +54,7 @@ struct DeviceBlock
 HRESULT SubmitPlanes(Device& device, const dxtex_image* srcs, const Image* dest, size_t nimages)          // may throw bad_alloc: the callers catch
 {
     std::vector<dxtex_image> d(nimages);
-    for (size_t i = 0; i < nimages; ++i) d[i] = View(dest[i]);
+    for (size_t i = 0; i < nimages; ++i) d[i] = ImageOf(dest[i]);
     return dxtex_convert_to_single_plane_device(device.Get(), srcs, d.data(), nimages);
 }
 }
@@ -73,7 +71,7 @@ HRESULT ConvertToSinglePlane(Device& device, const Image& srcImage, ScratchImage
     if (FAILED(hr)) return hr;
     const Image* rimage = image.GetImage(0, 0, 0);
     if (!rimage) { image.Release(); return E_POINTER; }
-    const dxtex_image s = View(srcImage), d = View(*rimage);
+    const dxtex_image s = ImageOf(srcImage), d = ImageOf(*rimage);
     hr = dxtex_convert_to_single_plane(device.Get(), &s, &d);
     if (FAILED(hr)) image.Release();
     return hr;
@@ -99,7 +97,7 @@ HRESULT ConvertToSinglePlane(Device& device, const Image* srcImages, size_t nima
         size_t total = 0;
         for (size_t i = 0; i < nimages; ++i)
         {
-            srcs[i] = View(srcImages[i]);
+            srcs[i] = ImageOf(srcImages[i]);
             srcs[i].pixels = reinterpret_cast<uint8_t*>(total);
             total += (srcImages[i].slicePitch + 15) & ~size_t(15);
         }
@@ -138,7 +136,7 @@ HRESULT ConvertToSinglePlane(Device& device, const DeviceScratchImage& src, Devi
         if (SUCCEEDED(hr))
         {
             std::vector<dxtex_image> srcs(nimages);
-            for (size_t i = 0; i < nimages; ++i) srcs[i] = View(src.GetImages()[i]);
+            for (size_t i = 0; i < nimages; ++i) srcs[i] = ImageOf(src.GetImages()[i]);
             hr = SubmitPlanes(device, srcs.data(), result.GetImages(), nimages);
         }
         if (FAILED(hr)) result.Release();

@@ -1,8 +1,7 @@
 // RotateColor: texconv's HDR colour rotation (Texconv/texconv.cpp:2696-2964) on the host layer, over the C ABI's dxtex_rotate_color and
 // dxtex_rotate_color_device. The checks are TransformImage's (DirectXTexMisc.cpp:606-700), which the reference runs the lambdas through,
 // plus texconv's own for the operation and the paper-white level. The array and resident forms issue ONE batched call for all images.
-#include "DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
+#include "DirectXTexAMD_Internal.h"
 
 #include <vector>
 
@@ -10,7 +9,6 @@ namespace DirectXTexAMD
 {
 namespace
 {
-dxtex_image View(const Image& i) noexcept { return dxtex_image{ i.width, i.height, int32_t(i.format), i.rowPitch, i.slicePitch, i.pixels }; }
 
 bool RotateUnsupported(DXGI_FORMAT f) noexcept { return IsPlanar(f) || IsPalettized(f) || IsCompressed(f) || IsTypeless(f); }
 
@@ -46,7 +44,7 @@ HRESULT RotateColor(Device& device, const Image& srcImage, TEX_ROTATE_COLOR rota
     if (FAILED(hr)) return hr;
     const Image* img = result.GetImage(0, 0, 0);
     if (!img) { result.Release(); return E_POINTER; }
-    const dxtex_image s = View(srcImage), d = View(*img);
+    const dxtex_image s = ImageOf(srcImage), d = ImageOf(*img);
     hr = dxtex_rotate_color(device.Get(), &s, &d, uint32_t(rotate), paperWhiteNits);
     if (FAILED(hr)) result.Release();
     return hr;
@@ -82,7 +80,7 @@ HRESULT RotateColor(Device& device, const DeviceScratchImage& src, TEX_ROTATE_CO
     {
         const size_t n = src.GetImageCount();
         std::vector<dxtex_image> s(n), d(n);
-        for (size_t i = 0; i < n; ++i) { s[i] = View(src.GetImages()[i]); d[i] = View(result.GetImages()[i]); }
+        for (size_t i = 0; i < n; ++i) { s[i] = ImageOf(src.GetImages()[i]); d[i] = ImageOf(result.GetImages()[i]); }
         hr = dxtex_rotate_color_device(device.Get(), s.data(), d.data(), n, uint32_t(rotate), paperWhiteNits);
     }
     catch (...) { hr = E_OUTOFMEMORY; }

@@ -117,19 +117,8 @@ namespace
         return S_OK;
     }
 
-    // which of dxtex_tga.h's kinds a file is: its texel's bytes, the image's format before any sRGB relabel, colour-mapped or not
-    int KindOf(DXGI_FORMAT format, uint32_t bytesPerTexel, bool paletted) noexcept
-    {
-        if (paletted) return dxtex::TGA_PALETTE;
-        switch (format)
-        {
-        case DXGI_FORMAT_R8_UNORM: return dxtex::TGA_GREY;
-        case DXGI_FORMAT_B5G5R5A1_UNORM: return dxtex::TGA_5551;
-        case DXGI_FORMAT_R8G8B8A8_UNORM: return bytesPerTexel == 3 ? dxtex::TGA_RGB_RGBA : dxtex::TGA_BGRA_RGBA;
-        case DXGI_FORMAT_B8G8R8A8_UNORM: return dxtex::TGA_BGRA_BGRA;
-        default: return dxtex::TGA_RGB_BGRX;
-        }
-    }
+    // which of dxtex_tga.h's kinds a file is (its reader's table): every (format, bytes, colour-mapped) DecodeHeader gives is in it
+    int KindOf(const TGARawImage& raw) noexcept { return dxtex::tga_unpack_kind(int(raw.format), raw.bytesPerTexel, raw.paletted); }
 
     // UncompressPixels' packets (:381-737) undone into file-order texels of B bytes. Packets do not cross rows; any truncation is E_FAIL.
     HRESULT ExpandPackets(const uint8_t* s, size_t size, size_t width, size_t height, size_t B, uint8_t* d) noexcept
@@ -208,11 +197,7 @@ HRESULT GetMetadataFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS fla
 
 HRESULT GetMetadataFromTGAFile(const char* szFile, TGA_FLAGS flags, TexMetadata& metadata) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, kHeaderLen);
-    if (FAILED(hr)) return hr;
-    return GetMetadataFromTGAMemory(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata);
+    return LoadFile(szFile, ReadAtLeast<kHeaderLen>, [&](const uint8_t* p, size_t n) { return GetMetadataFromTGAMemory(p, n, flags, metadata); });
 }
 
 // LoadFromTGAMemory's byte-serial half (DirectXTexTGA.cpp:1640-1745 around CopyPixels): header, palette, extension area, the size check of a
@@ -268,13 +253,8 @@ HRESULT LoadFromTGAMemoryRaw(const void* pSource, size_t size, TGA_FLAGS flags, 
 HRESULT LoadFromTGAFileRaw(const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, TGARawImage& raw) noexcept
 {
     raw.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob file;
-    HRESULT hr = ReadAll(szFile, file, kHeaderLen);
-    if (FAILED(hr)) return hr;
-    hr = LoadFromTGAMemoryRaw(file.GetBufferPointer(), file.GetBufferSize(), flags, metadata, raw);
-    if (SUCCEEDED(hr) && !raw.storage.GetBufferPointer()) raw.storage.Swap(file);          // a raw file: the texels lie inside it
-    return hr;
+    // a file without packets: the texels lie inside it, and raw keeps it
+    return LoadFile(szFile, ReadAtLeast<kHeaderLen>, [&](const uint8_t* p, size_t n) { return LoadFromTGAMemoryRaw(p, n, flags, metadata, raw); }, &raw.storage);
 }
 
 // LoadFromTGAMemory (DirectXTexTGA.cpp:1640-1745)
@@ -290,7 +270,7 @@ HRESULT LoadFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, Tex
     const Image* img = image.GetImage(0, 0, 0);
     if (!img) { image.Release(); return E_POINTER; }
     // CopyPixels' texel half (:738-1180): the file's first row is the image's bottom row unless the descriptor says top-down; right-to-left likewise
-    const int kind = KindOf(raw.format, raw.bytesPerTexel, raw.paletted);
+    const int kind = KindOf(raw);
     const size_t B = raw.bytesPerTexel, D = dxtex::tga_image_bytes(kind);
     uint32_t orAlpha = 0, orNotAlpha = 0;
     const uint8_t* s = raw.texels;
@@ -325,12 +305,8 @@ HRESULT LoadFromTGAMemory(const void* pSource, size_t size, TGA_FLAGS flags, Tex
 
 HRESULT LoadFromTGAFile(const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    image.Release();
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, kHeaderLen);
-    if (FAILED(hr)) return hr;
-    return LoadFromTGAMemory(buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, image);
+    if (szFile) image.Release();
+    return LoadFile(szFile, ReadAtLeast<kHeaderLen>, [&](const uint8_t* p, size_t n) { return LoadFromTGAMemory(p, n, flags, metadata, image); });
 }
 
 namespace
@@ -342,15 +318,11 @@ namespace
         if ((flags & (TGA_FLAGS_FORCE_LINEAR | TGA_FLAGS_FORCE_SRGB)) != 0 && !metadata) return E_INVALIDARG;
         if (!image.pixels) return E_POINTER;
         if (image.width > UINT16_MAX || image.height > UINT16_MAX) return HRESULT_E_NOT_SUPPORTED;
-        switch (image.format)
-        {
-        case DXGI_FORMAT_R8G8B8A8_UNORM: case DXGI_FORMAT_R8G8B8A8_UNORM_SRGB: f = { IMG_TRUECOLOR, 32, DESC_INVERTY | 8, dxtex::TGA_ROW_SWAP_RB }; break;
-        case DXGI_FORMAT_B8G8R8A8_UNORM: case DXGI_FORMAT_B8G8R8A8_UNORM_SRGB: f = { IMG_TRUECOLOR, 32, DESC_INVERTY | 8, dxtex::TGA_ROW_COPY }; break;
-        case DXGI_FORMAT_B8G8R8X8_UNORM: case DXGI_FORMAT_B8G8R8X8_UNORM_SRGB: f = { IMG_TRUECOLOR, 24, DESC_INVERTY, dxtex::TGA_ROW_DROP_X }; break;
-        case DXGI_FORMAT_R8_UNORM: case DXGI_FORMAT_A8_UNORM: f = { IMG_GREY, 8, DESC_INVERTY, dxtex::TGA_ROW_COPY }; break;
-        case DXGI_FORMAT_B5G5R5A1_UNORM: f = { IMG_TRUECOLOR, 16, DESC_INVERTY | 1, dxtex::TGA_ROW_COPY }; break;
-        default: return HRESULT_E_NOT_SUPPORTED;
-        }
+        // the writer's table: a byte is grey, anything wider true colour; the descriptor's low bits count the alpha bits - 8 of 32, 1 of 16
+        const dxtex::TgaPackRow r = dxtex::tga_pack_row(int(image.format));
+        const uint32_t B = r.bytesPerTexel;
+        if (!B) return HRESULT_E_NOT_SUPPORTED;
+        f = { uint8_t(B == 1 ? IMG_GREY : IMG_TRUECOLOR), uint8_t(B * 8), uint8_t(DESC_INVERTY | (B == 4 ? 8 : B == 2 ? 1 : 0)), r.row };
         return S_OK;
     }
 
@@ -427,11 +399,7 @@ HRESULT SaveToTGAMemory(const Image& image, TGA_FLAGS flags, Blob& blob, const T
 
 HRESULT SaveToTGAFile(const Image& image, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToTGAMemory(image, flags, blob, metadata);
-    if (FAILED(hr)) return hr;
-    return WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToTGAMemory(image, flags, blob, metadata); });
 }
 
 // ---- resident forms: the texels travel as the file has them, the per-texel pass runs on the device (dxtex_tga_unpack_device / dxtex_tga_pack_device) ----
@@ -445,7 +413,7 @@ void TGARawImage::Release() noexcept
 
 void ApplyTGAAlphaRule(const TGARawImage& raw, TGA_FLAGS flags, TexMetadata& metadata) noexcept
 {
-    const int kind = KindOf(raw.format, raw.bytesPerTexel, raw.paletted);
+    const int kind = KindOf(raw);
     bool opaque = kind == dxtex::TGA_RGB_RGBA;
     if (dxtex::tga_has_alpha_rule(kind) && raw.texels)
     {
@@ -467,35 +435,33 @@ HRESULT UploadTGARaw(Device& device, TexMetadata& metadata, TGA_FLAGS flags, con
         raw.texelBytes != metadata.width * metadata.height * raw.bytesPerTexel) return E_INVALIDARG;
     TexMetadata plain = metadata;          // the image as ScratchImage::Initialize2D would describe it; the sRGB relabel follows the pixels
     plain.format = raw.format; plain.miscFlags = 0; plain.miscFlags2 = 0;
-    HRESULT hr = image.Initialize(device, plain);
-    if (FAILED(hr)) return hr;
-    const Image* img = image.GetImage(0, 0, 0);
-    if (!img) { image.Release(); return E_POINTER; }
-    const int kind = KindOf(raw.format, raw.bytesPerTexel, raw.paletted);
+    const int kind = KindOf(raw);
     const bool rule = dxtex::tga_has_alpha_rule(kind);
-    // the stream, and behind it (on a dword) the alpha answer
-    const size_t answerAt = (raw.texelBytes + 3) & ~size_t(3);
-    DeviceTemp temp(device);
-    hr = dxtex_device_alloc(device.Get(), answerAt + 4, &temp.p);
-    // with an alpha rule the read-back of the answer below is the one wait, and the stream's copy has happened by then; without one the
-    // synchronous copy is: the host texels are free to go when this returns
-    if (SUCCEEDED(hr)) hr = rule ? dxtex_memcpy_h2d_async(device.Get(), temp.p, raw.texels, raw.texelBytes) : dxtex_memcpy_h2d(device.Get(), temp.p, raw.texels, raw.texelBytes);
     uint32_t opaque = kind == dxtex::TGA_RGB_RGBA ? 1u : 0u;
-    if (SUCCEEDED(hr))
+    const HRESULT hr = InitializeAndFill(device, plain, image, [&](const Image& img)
     {
+        // the stream, and behind it (on a dword) the alpha answer
+        const size_t answerAt = (raw.texelBytes + 3) & ~size_t(3);
+        DeviceTemp temp(device);
+        HRESULT hr2 = dxtex_device_alloc(device.Get(), answerAt + 4, &temp.p);
+        // with an alpha rule the read-back of the answer below is the one wait, and the stream's copy has happened by then; without one the
+        // synchronous copy is: the host texels are free to go when this returns
+        if (SUCCEEDED(hr2)) hr2 = rule ? dxtex_memcpy_h2d_async(device.Get(), temp.p, raw.texels, raw.texelBytes) : dxtex_memcpy_h2d(device.Get(), temp.p, raw.texels, raw.texelBytes);
+        if (FAILED(hr2)) return hr2;
         const uint32_t how = (raw.rightToLeft ? DXTEX_TGA_RIGHT_TO_LEFT : 0u) | (raw.topDown ? DXTEX_TGA_TOP_DOWN : 0u) |
                              ((flags & TGA_FLAGS_ALLOW_ALL_ZERO_ALPHA) ? DXTEX_TGA_ALLOW_ALL_ZERO_ALPHA : 0u);
-        const dxtex_image d = { img->width, img->height, int32_t(img->format), img->rowPitch, img->slicePitch, img->pixels };
+        const dxtex_image d = ImageOf(img);
         uint32_t* answer = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(temp.p) + answerAt);
-        hr = dxtex_tga_unpack_device(device.Get(), temp.p, raw.texelBytes, raw.bytesPerTexel, how, raw.paletted ? raw.palette : nullptr, &d, rule ? answer : nullptr);
+        hr2 = dxtex_tga_unpack_device(device.Get(), temp.p, raw.texelBytes, raw.bytesPerTexel, how, raw.paletted ? raw.palette : nullptr, &d, rule ? answer : nullptr);
         if (rule)
         {
             // queued or not, the stream's copy reads the caller's texels: wait for it either way
             const HRESULT waited = dxtex_memcpy_d2h(device.Get(), &opaque, answer, sizeof(opaque));
-            if (SUCCEEDED(hr)) hr = waited;
+            if (SUCCEEDED(hr2)) hr2 = waited;
         }
-    }
-    if (FAILED(hr)) { image.Release(); return hr; }
+        return hr2;
+    });
+    if (FAILED(hr)) return hr;
     image.OverrideFormat(metadata.format);
     if (opaque) metadata.SetAlphaMode(TEX_ALPHA_MODE_OPAQUE);
     return S_OK;
@@ -517,11 +483,7 @@ HRESULT LoadFromTGAMemory(Device& device, const void* pSource, size_t size, TGA_
 HRESULT LoadFromTGAFile(Device& device, const char* szFile, TGA_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept
 {
     image.Release();
-    if (!szFile) return E_INVALIDARG;
-    Blob buf;
-    const HRESULT hr = ReadAll(szFile, buf, kHeaderLen);
-    if (FAILED(hr)) return hr;
-    return LoadFromTGAMemory(device, buf.GetBufferPointer(), buf.GetBufferSize(), flags, metadata, image);
+    return LoadFile(szFile, ReadAtLeast<kHeaderLen>, [&](const uint8_t* p, size_t n) { return LoadFromTGAMemory(device, p, n, flags, metadata, image); });
 }
 
 HRESULT SaveToTGAMemory(Device& device, const Image& deviceImage, TGA_FLAGS flags, Blob& blob, const TexMetadata* metadata) noexcept
@@ -532,26 +494,13 @@ HRESULT SaveToTGAMemory(Device& device, const Image& deviceImage, TGA_FLAGS flag
     if (!device) return E_POINTER;
     const uint32_t B = f.bits / 8;
     const size_t bytes = deviceImage.width * deviceImage.height * B;
-    return WriteFile(deviceImage, f, flags, metadata, blob, [&](uint8_t* d)
-    {
-        DeviceTemp temp(device);
-        HRESULT hr2 = dxtex_device_alloc(device.Get(), bytes, &temp.p);
-        if (SUCCEEDED(hr2))
-        {
-            const dxtex_image s = { deviceImage.width, deviceImage.height, int32_t(deviceImage.format), deviceImage.rowPitch, deviceImage.slicePitch, deviceImage.pixels };
-            hr2 = dxtex_tga_pack_device(device.Get(), &s, B, temp.p, bytes);
-        }
-        if (SUCCEEDED(hr2)) hr2 = dxtex_memcpy_d2h(device.Get(), d, temp.p, bytes);          // straight behind the header; returns when the rows have landed
-        return hr2;
-    });
+    const dxtex_image s = ImageOf(deviceImage);
+    return WriteFile(deviceImage, f, flags, metadata, blob, [&](uint8_t* d)          // the rows land straight behind the header
+    { return PackAndDownload(device, bytes, d, [&](void* p) { return dxtex_tga_pack_device(device.Get(), &s, B, p, bytes); }); });
 }
 
 HRESULT SaveToTGAFile(Device& device, const Image& deviceImage, TGA_FLAGS flags, const char* szFile, const TexMetadata* metadata) noexcept
 {
-    if (!szFile) return E_INVALIDARG;
-    Blob blob;
-    const HRESULT hr = SaveToTGAMemory(device, deviceImage, flags, blob, metadata);
-    if (FAILED(hr)) return hr;
-    return WriteBlob(blob, szFile);
+    return SaveFile(szFile, [&](Blob& blob) { return SaveToTGAMemory(device, deviceImage, flags, blob, metadata); });
 }
 } // namespace DirectXTexAMD

@@ -5,6 +5,8 @@
 //   jpeg_write_check coefficients <width> <height> <format> <pitch> <h> <v> <quant: 4 * 64 uint16> <pixels> <out>
 //       the frame whose luma is h x v over 1 x 1 chroma (format 61, R8_UNORM: grey, 1 x 1), component c with table c, from rows of `pitch`
 //       bytes of format 28 / 29 (R8G8B8A8), 87 / 91 (B8G8R8A8) or 88 / 93 (B8G8R8X8): the coefficients as include/dxtex_amd.h lays them out
+//   jpeg_write_check formats
+//       the format table over its whole domain: "texel <format> <JpegTexel, -1 for a format the coder does not take>" for every format 0..191
 #include "dxtex_jpeg.h"
 
 #include <cstdio>
@@ -29,7 +31,7 @@ static int coefficients(char** a)
 {
     const uint32_t width = uint32_t(std::atoi(a[0])), height = uint32_t(std::atoi(a[1])), pitch = uint32_t(std::atoi(a[3]));
     const int format = std::atoi(a[2]);
-    const bool grey = format == 61, bgr = format == 87 || format == 88 || format == 91 || format == 93;
+    const bool grey = jpeg_texel_of(format) == JPEG_TEXEL_GREY, bgr = jpeg_texel_of(format) == JPEG_TEXEL_BGRX;
     const uint32_t hmax = grey ? 1u : uint32_t(std::atoi(a[4])), vmax = grey ? 1u : uint32_t(std::atoi(a[5])), ncomp = grey ? 1u : 3u;
     std::vector<uint8_t> q, px;
     if (!read_file(a[6], q) || !read_file(a[7], px) || q.size() != 512 || !width || !height) return 1;
@@ -62,9 +64,16 @@ static int coefficients(char** a)
     return (std::fclose(f) == 0 && ok) ? 0 : 1;
 }
 
+static int formats()
+{
+    for (int f = 0; f < 192; ++f) std::printf("texel %d %d\n", f, jpeg_texel_of(f));
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 2 && !std::strcmp(argv[1], "formats")) return formats();
     if (argc == 11 && !std::strcmp(argv[1], "coefficients")) return coefficients(argv + 2);
-    std::fprintf(stderr, "usage: jpeg_write_check coefficients <width> <height> <format> <pitch> <h> <v> <quant> <pixels> <out>\n");
+    std::fprintf(stderr, "usage: jpeg_write_check coefficients <width> <height> <format> <pitch> <h> <v> <quant> <pixels> <out> | formats\n");
     return 2;
 }

@@ -8,6 +8,9 @@
 //       tight image rows through png_pack_texel -> the file's rows
 //   png_check table <plte> <trns | -> <out>
 //       png_palette_table of a PLTE chunk's and a tRNS chunk's bytes: 256 little-endian words
+//   png_check formats
+//       the two format tables over their whole domain: "pack <format> <source>" for every format 0..191, and "unpack <kind> <flags> <format>"
+//       for every (kind, PNG_BGR or not, format 0..191) that png_unpack_pairs accepts
 #include "dxtex_png.h"
 
 #include <cstdio>
@@ -81,11 +84,22 @@ static int table(char** a)
     return write_file(a[2], words, sizeof(words)) ? 0 : 1;
 }
 
+static int formats()
+{
+    for (int f = 0; f < 192; ++f) std::printf("pack %d %d\n", f, png_pack_source(f));
+    for (int kind = 0; kind < PNG_KINDS; ++kind)
+        for (uint32_t flags = 0; flags < 2; ++flags)
+            for (int f = 0; f < 192; ++f)
+                if (png_unpack_pairs(kind, flags, f)) std::printf("unpack %d %u %d\n", kind, flags, f);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 2 && !std::strcmp(argv[1], "formats")) return formats();
     if (argc == 9 && !std::strcmp(argv[1], "unpack")) return unpack(argv + 2);
     if (argc == 7 && !std::strcmp(argv[1], "pack")) return pack(argv + 2);
     if (argc == 5 && !std::strcmp(argv[1], "table")) return table(argv + 2);
-    std::fprintf(stderr, "usage: png_check unpack <kind> <bgr> <w> <h> <rows> <palette|-> <out> | pack <source> <w> <h> <in> <out> | table <plte> <trns|-> <out>\n");
+    std::fprintf(stderr, "usage: png_check unpack <kind> <bgr> <w> <h> <rows> <palette|-> <out> | pack <source> <w> <h> <in> <out> | table <plte> <trns|-> <out> | formats\n");
     return 2;
 }

@@ -12,6 +12,9 @@
 //       tight image rows through pnm_pack_texel and pnm_image_row -> the file's samples
 //   pnm_check half <out>
 //       pnm_half_to_float_bits of every half 0..65535, little-endian uint32 each
+//   pnm_check formats
+//       the two format tables over their whole domain: "pack <format> <source> <kind it is written as, -1 without a source>" for every
+//       format 0..191, and "unpack <kind> <format>" for every kind
 #include "dxtex_pnm.h"
 
 #include <cstdio>
@@ -103,12 +106,20 @@ static int half(const char* out)
     return write_file(out, bits.data(), bits.size() * 4) ? 0 : 1;
 }
 
+static int formats()
+{
+    for (int f = 0; f < 192; ++f) { const int src = pnm_pack_source(f); std::printf("pack %d %d %d\n", f, src, src < 0 ? -1 : pnm_source_kind(src)); }
+    for (int kind = 0; kind < PNM_KINDS; ++kind) std::printf("unpack %d %d\n", kind, pnm_unpack_format(kind));
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 2 && !std::strcmp(argv[1], "formats")) return formats();
     if (argc == 3 && !std::strcmp(argv[1], "p6")) return p6(argv[2]);
     if (argc == 9 && !std::strcmp(argv[1], "unpack")) return unpack(argv + 2);
     if (argc == 7 && !std::strcmp(argv[1], "pack")) return pack(argv + 2);
     if (argc == 3 && !std::strcmp(argv[1], "half")) return half(argv[2]);
-    std::fprintf(stderr, "usage: pnm_check p6 <out> | unpack <kind> <big endian> <maxval> <w> <h> <in> <out> | pack <source> <w> <h> <in> <out> | half <out>\n");
+    std::fprintf(stderr, "usage: pnm_check p6 <out> | unpack <kind> <big endian> <maxval> <w> <h> <in> <out> | pack <source> <w> <h> <in> <out> | half <out> | formats\n");
     return 2;
 }

@@ -7,6 +7,9 @@
 //       texel lands) and prints the alpha answer, one line per image.
 //   tga_check pack <row> <bytesPerTexel> <width> <height> <rowPitch> <pixels file> <out file>
 //       row = a TgaRow; writes the width * height * bytesPerTexel bytes of the file's rows
+//   tga_check formats
+//       the two format tables over their whole domain: "pack <format> <bytes per texel> <row>" for every format 0..191, and "unpack <format>
+//       <bytes per texel> <paletted> <kind>" for every format, bytes per texel 0..5 and both palette states
 #include "dxtex_tga.h"
 
 #include <cstdio>
@@ -98,10 +101,20 @@ static int pack(char** a)
     return write_file(a[6], out) ? 0 : 4;
 }
 
+static int formats()
+{
+    for (int f = 0; f < 192; ++f) { const TgaPackRow r = tga_pack_row(f); std::printf("pack %d %u %d\n", f, r.bytesPerTexel, r.row); }
+    for (int f = 0; f < 192; ++f)
+        for (uint32_t B = 0; B <= 5; ++B)
+            for (int paletted = 0; paletted < 2; ++paletted) std::printf("unpack %d %u %d %d\n", f, B, paletted, tga_unpack_kind(f, B, paletted != 0));
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
+    if (argc == 2 && !std::strcmp(argv[1], "formats")) return formats();
     if (argc == 3 && !std::strcmp(argv[1], "unpack_many")) return unpack_many(argv[2]);
     if (argc == 9 && !std::strcmp(argv[1], "pack")) return pack(argv + 2);
-    std::fprintf(stderr, "usage: tga_check unpack_many <list> | pack <row> <bytesPerTexel> <width> <height> <rowPitch> <pixels> <out>\n");
+    std::fprintf(stderr, "usage: tga_check unpack_many <list> | pack <row> <bytesPerTexel> <width> <height> <rowPitch> <pixels> <out> | formats\n");
     return 2;
 }

@@ -232,3 +232,12 @@ def test_pillow_writes_the_savers_files_and_decodes_them_to_the_readers_pixels(t
         decoded = np.asarray(Image.open(io.BytesIO(data)))
         mine = R.pixels(R.decode(data)).reshape(px.shape[0], px.shape[1], -1)
         assert np.array_equal(decoded.reshape(px.shape[0], px.shape[1], -1), mine[..., :3]), (fmt, px.shape)
+
+
+def test_format_table_over_the_whole_domain():
+    """The table the C ABI and the host saver share (csrc/dxtex_jpeg.h, jpeg_texel_of) for every format 0..191: R8_UNORM is grey, R8G8B8A8
+    [_SRGB] colour, B8G8R8A8 / B8G8R8X8 [_SRGB] colour with B before R, everything else refused."""
+    r = subprocess.run([CHECK, "formats"], capture_output=True, text=True, check=True, timeout=60)
+    table = {int(p[1]): int(p[2]) for p in (line.split() for line in r.stdout.splitlines()) if p[0] == "texel"}
+    written = {R.R8: 0, R.RGBA8: 1, R.RGBA8_SRGB: 1, W.B8G8R8A8: 2, W.B8G8R8A8_SRGB: 2, W.B8G8R8X8: 2, W.B8G8R8X8_SRGB: 2}
+    assert table == {f: written.get(f, -1) for f in range(192)}

@@ -560,3 +560,55 @@ def test_dxtexconv_ft_png_wants_a_directory_or_a_png_name():
         assert "usage: dxtexconv" not in r.stderr, (out, r.stderr)
     r = subprocess.run([conv], capture_output=True, text=True)
     assert "-ft dds|hdr|tga|ppm|pfm|png" in r.stderr and "-ignoresrgb" in r.stderr and "in.png" in r.stderr, r.stderr
+
+
+# csrc/dxtex_png.h's reader table, written out: {(kind, PNG_BGR or not): the formats the kind unpacks into}
+_RGBA = {0: (R.RGBA8, R.RGBA8_SRGB), 1: (R.BGRA8, R.BGRA8_SRGB)}
+_RGBX = {0: (R.RGBA8, R.RGBA8_SRGB), 1: (R.BGRX8, R.BGRX8_SRGB)}
+UNPACK_PAIRS = {(k, b): (R.R8,) for k in (R.G1, R.G2, R.G4, R.G8) for b in (0, 1)}
+UNPACK_PAIRS.update({(R.G16, b): (R.R16,) for b in (0, 1)})
+UNPACK_PAIRS.update({(R.GA8, 0): (R.RGBA8,), (R.GA8, 1): (R.BGRA8,)})
+UNPACK_PAIRS.update({(k, b): (R.RGBA16,) for k in (R.GA16, R.RGB16, R.RGBA16K) for b in (0, 1)})
+UNPACK_PAIRS.update({(R.RGBA8K, b): _RGBA[b] for b in (0, 1)})
+UNPACK_PAIRS.update({(k, b): _RGBX[b] for k in (R.RGB8, R.P1, R.P2, R.P4, R.P8) for b in (0, 1)})
+
+
+def format_tables():
+    """(pack, unpack) of `png_check formats`: {format: source} and the set of (kind, flags, format) png_unpack_pairs accepts"""
+    pack, unpack = {}, set()
+    for line in subprocess.run([CHECK, "formats"], capture_output=True, text=True, check=True, timeout=60).stdout.splitlines():
+        p = line.split()
+        if p[0] == "pack":
+            pack[int(p[1])] = int(p[2])
+        else:
+            unpack.add(tuple(int(x) for x in p[1:]))
+    return pack, unpack
+
+
+def test_format_tables_over_the_whole_domain():
+    """The tables the C ABI and the host codec share answer the written-out tables for every format 0..191: the writer's source - everything
+    outside SOURCE refused - and, for every kind with and without PNG_BGR, the formats it unpacks into."""
+    pack, unpack = format_tables()
+    assert pack == {f: SOURCE.get(f, -1) for f in range(192)}
+    assert unpack == {(k, b, f) for (k, b), fmts in UNPACK_PAIRS.items() for f in fmts}
+
+
+def test_every_format_the_reader_chooses_is_in_the_reader_table(tmp_path):
+    """Every colour type and depth x PNG_FLAGS_BGR or not, under the flags and the chunk that move the choice between linear and sRGB: the
+    (kind, raw flags, format) the loader hands on is one png_unpack_pairs accepts."""
+    _, unpack = format_tables()
+    rng = np.random.default_rng(11)
+    files = []
+    for kind in KINDS:
+        ct, depth = R.TYPE_OF[kind]
+        rows = case_rows(kind, 3, 2, rng)
+        plte, trns = case_palette(kind, rng, trns=0)
+        for flags in (0, R.FLAGS_IGNORE_SRGB, R.FLAGS_DEFAULT_LINEAR):
+            for srgb in (None, 0):
+                files += [(flags | bgr, R.encode(3, 2, ct, depth, rows, plte=plte, trns=trns, srgb=srgb)) for bgr in (0, R.FLAGS_BGR)]
+    chosen = set()
+    for (raw_hr, hr, meta_hr, d), (flags, _) in zip(load_many(HOST, str(tmp_path), files), files):
+        assert (raw_hr, hr, meta_hr) == (0, 0, 0), (flags, hex(raw_hr), hex(hr), hex(meta_hr))
+        assert (d["kind"], d["flags"], d["format"]) in unpack, (flags, d)
+        chosen.add(d["format"])
+    assert chosen == set(SOURCE)          # every format of the table is chosen by some file

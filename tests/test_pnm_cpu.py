@@ -329,3 +329,18 @@ def test_every_half_widens_like_the_oracle(tmp_path, oracle):
     halves = np.arange(65536, dtype=np.uint16).reshape(256, 256)
     rgb = np.stack([halves, halves[::-1], halves.T], axis=2)
     assert np.array_equal(got[rgb], widen(rgb))
+
+
+def test_format_tables_over_the_whole_domain():
+    """The tables the C ABI and the host codec share (csrc/dxtex_pnm.h): the writer's source and the kind it is written as for every format
+    0..191 - everything outside SOURCE refused - and the reader's one format per kind."""
+    pack, unpack = {}, {}
+    for line in subprocess.run([CHECK, "formats"], capture_output=True, text=True, check=True, timeout=60).stdout.splitlines():
+        p = line.split()
+        if p[0] == "pack":
+            pack[int(p[1])] = (int(p[2]), int(p[3]))
+        else:
+            unpack[int(p[1])] = int(p[2])
+    kind_of_source = {0: R.P6, 1: R.P6, 2: R.PF, 3: R.PF, 4: R.PF, 5: R.Pf}
+    assert pack == {f: (SOURCE[f], kind_of_source[SOURCE[f]]) if f in SOURCE else (-1, -1) for f in range(192)}
+    assert unpack == R.KIND_FORMAT

@@ -175,3 +175,57 @@ def test_pack_rows_are_the_reference_writers(tmp_path, fmt, B, D, row):
         subprocess.run([CHECK, "pack", str(row), str(B), str(w), str(h), str(pitch), src, out], check=True, timeout=60)
         assert np.array_equal(np.fromfile(out, np.uint8), ref[18:18 + w * h * B]), (fmt, w, h)
         assert ref[16] == 8 * B
+
+
+# csrc/dxtex_tga.h's two format tables, written out; every other point of the domain is refused
+PACK_TABLE = {fmt: (B, row) for fmt, B, _, row in WRITER}
+UNPACK_TABLE = {(R8, 1, 0): GREY, (B5G5R5A1, 2, 0): K5551, (RGBA8, 3, 0): RGB_RGBA, (RGBA8, 4, 0): BGRA_RGBA, (BGRX8, 3, 0): RGB_BGRX, (BGRA8, 4, 0): BGRA_BGRA,
+                (RGBA8, 1, 1): PALETTE, (BGRX8, 1, 1): PALETTE}
+
+
+def format_tables():
+    """(pack, unpack) of `tga_check formats`: {format: (bytes per texel, row)} and {(format, bytes per texel, paletted): kind}"""
+    pack, unpack = {}, {}
+    for line in subprocess.run([CHECK, "formats"], capture_output=True, text=True, check=True, timeout=60).stdout.splitlines():
+        p = line.split()
+        v = [int(x) for x in p[1:]]
+        if p[0] == "pack":
+            pack[v[0]] = (v[1], v[2])
+        else:
+            unpack[tuple(v[:3])] = v[3]
+    return pack, unpack
+
+
+def test_format_tables_over_the_whole_domain():
+    """The tables the C ABI and the host codec share answer the written-out table for every format 0..191 (reader: every bytes per texel
+    0..5 and both palette states), and refuse everything else."""
+    pack, unpack = format_tables()
+    assert pack == {f: PACK_TABLE.get(f, (0, -1)) for f in range(192)}
+    assert unpack == {(f, B, p): UNPACK_TABLE.get((f, B, p), -1) for f in range(192) for B in range(6) for p in (0, 1)}
+
+
+def test_every_header_the_reader_accepts_is_in_the_reader_table(tmp_path):
+    """Every image type x bits x colour map or not x TGA_FLAGS: where LoadFromTGAMemoryRaw accepts the file, the (format before gamma, bytes
+    per texel, colour-mapped) it reports is a triple the strict table knows, with the kind the loader's own restatement gives."""
+    _, unpack = format_tables()
+    entries, headers = [], []
+    w, h = 3, 2
+    for image_type in (1, 2, 3, 9, 10, 11):
+        for bits in (8, 15, 16, 24, 32):
+            for mapped in (0, 1):
+                B = (bits + 7) // 8
+                head = bytes([0, mapped, image_type, 0, 0, 2 * mapped, 0, 24 * mapped, 0, 0, 0, 0, w, 0, h, 0, bits, 0])
+                rows = [bytes((7 * (y * w + x) + c) & 0xFF for x in range(w) for c in range(B)) for y in range(h)]
+                body = b"".join((bytes([w - 1]) + r) if image_type >= 9 else r for r in rows)          # one raw packet a row
+                for flags in FLAGS:
+                    entries.append((head + bytes(6 * mapped) + body + bytes(8), flags))
+                    headers.append((image_type, bits, mapped))
+    accepted = set()
+    for (hr, d), header, (_, flags) in zip(raw_load_many(HOST, str(tmp_path), entries), headers, entries):
+        if hr != 0:
+            continue
+        accepted.add(header)
+        triple = (d["plainFormat"], d["bytesPerTexel"], d["paletted"])
+        assert unpack[triple] >= 0 and unpack[triple] == kind_of(*triple), (header, flags, triple)
+    # what DecodeTGAHeader takes: 8-bit colour-mapped, 16 / 24 / 32-bit true colour, 8-bit grey; the latter two raw or run-length encoded
+    assert accepted == {(1, 8, 1)} | {(t, b, 0) for t in (2, 10) for b in (16, 24, 32)} | {(3, 8, 0), (11, 8, 0)}
