@@ -63,6 +63,24 @@ class JpegFrame(ctypes.Structure):
                 ("component", JpegComponent * 3), ("quant", (ctypes.c_uint16 * 64) * 4)]
 
 
+class ExrChunk(ctypes.Structure):
+    """dxtex_exr_chunk (include/dxtex_amd.h): one chunk of an .exr file's expanded stream."""
+    _fields_ = [("offset", ctypes.c_uint64), ("bytes", ctypes.c_uint32), ("firstRow", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("coded", ctypes.c_uint32)]
+
+
+class ExrChannel(ctypes.Structure):
+    """dxtex_exr_channel (include/dxtex_amd.h): where one of R, G, B, A lies in a scanline, and its type."""
+    _fields_ = [("offset", ctypes.c_uint32), ("type", ctypes.c_uint32)]
+
+
+def _exr_tables(chunks, channels):
+    """(ExrChunk array or None, count, ExrChannel[4] or None) from chunks = [(offset, bytes, first row, rows, coded)] and channels =
+    [(offset, type)] * 4 for R, G, B, A; None stays a null pointer."""
+    ch = None if chunks is None else (ExrChunk * max(1, len(chunks)))(*[ExrChunk(*c) for c in chunks])
+    tab = None if channels is None else (ExrChannel * 4)(*[ExrChannel(*c) for c in channels])
+    return ch, (0 if chunks is None else len(chunks)), tab
+
+
 def jpeg_frame(width, height, colour, sampling=(1, 1), quant=None, quant_of=(0, 1, 1)):
     """The JpegFrame of an image whose luma is sampling = (h, v) over 1 x 1 chroma (grey: 1 x 1), laid out as dxtex_jpeg_decode takes the
     coefficients: blocks padded to whole MCUs, one component after another. quant = up to four tables of 64 entries in natural order;
@@ -198,6 +216,10 @@ _SIGS = {
     "dxtex_jpeg_decode_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, _P(JpegFrame), _P(Image)]),
     "dxtex_jpeg_encode": (ctypes.c_int32, [_ctx_p, _P(Image), _P(JpegFrame), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_jpeg_encode_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(JpegFrame), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_exr_unpack": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_exr_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_exr_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_exr_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -962,6 +984,42 @@ class Context:
         """dxtex_jpeg_encode_device: the device Image `src` (device_image) -> the frame's coefficients at a device pointer, asynchronous on
         the stream."""
         self._check(self._lib.dxtex_jpeg_encode_device(self._h, ctypes.byref(src), ctypes.byref(frame), coefficients_ptr, coefficient_bytes), "jpeg_encode_device")
+
+    # -- OpenEXR chunks (everything behind the inflater of the .exr reader, the writer's scanlines) -------------------------------------------
+    def exr_unpack(self, stream, chunks, channels, scanline_bytes, width, height, items=1, row_pitch=None, out=None):
+        """dxtex_exr_unpack: the expanded stream (host bytes), its chunks [(offset, bytes, first row, rows, coded)] and the channel table
+        [(offset, type)] for R, G, B, A -> `items` R16G16B16A16_FLOAT images of width x height, one behind another in a numpy uint8 buffer
+        with `row_pitch` bytes a row, default tight. out: the buffer to unpack into, default a zeroed one."""
+        stream = np.ascontiguousarray(stream, np.uint8)
+        pitch = width * 8 if row_pitch is None else row_pitch
+        if out is None:
+            out = np.zeros(pitch * height * items, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.nbytes >= pitch * height * items
+        imgs = (Image * items)(*[Image(width, height, F.DXGI_FORMAT_R16G16B16A16_FLOAT, pitch, pitch * height, out.ctypes.data + i * pitch * height) for i in range(items)])
+        ch, count, tab = _exr_tables(chunks, channels)
+        self._check(self._lib.dxtex_exr_unpack(self._h, stream.ctypes.data, stream.nbytes, ch, count, tab, scanline_bytes, imgs, items), "exr_unpack")
+        return out
+
+    def exr_unpack_device(self, stream_ptr, stream_bytes, chunks, channels, scanline_bytes, items):
+        """dxtex_exr_unpack_device: the stream at a device pointer (its coded chunks are undone in place) -> the device Images `items`
+        (a list of device_image), asynchronous on the stream."""
+        imgs = None if items is None else (Image * max(1, len(items)))(*items)
+        ch, count, tab = _exr_tables(chunks, channels)
+        self._check(self._lib.dxtex_exr_unpack_device(self._h, stream_ptr, stream_bytes, ch, count, tab, scanline_bytes, imgs, 0 if items is None else len(items)), "exr_unpack_device")
+
+    def exr_pack(self, pixels, width, height, fmt, row_pitch=None, out=None):
+        """dxtex_exr_pack: one image (host pixels) -> the writer's scanlines (per row the A, B, G, R half planes), width * height * 8 bytes
+        as a numpy uint8 buffer (or the front of `out`)."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        if out is None:
+            out = np.zeros(width * height * 8, np.uint8)
+        self._check(self._lib.dxtex_exr_pack(self._h, ctypes.byref(src), out.ctypes.data, out.nbytes), "exr_pack")
+        return out
+
+    def exr_pack_device(self, src, scanlines_ptr, scanline_bytes):
+        """dxtex_exr_pack_device: the device Image `src` -> the writer's scanlines at a device pointer, asynchronous on the stream."""
+        self._check(self._lib.dxtex_exr_pack_device(self._h, ctypes.byref(src), scanlines_ptr, scanline_bytes), "exr_pack_device")
 
     # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
     @staticmethod

@@ -9,6 +9,7 @@
 #include "dxtex_pnm.h"
 #include "dxtex_png.h"
 #include "dxtex_jpeg.h"
+#include "dxtex_exr.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -89,6 +90,8 @@ struct dxtex_ctx
     DeviceBuf ditherRows, ditherRerun; uint64_t ditherTexels = 0;
     // JPEG: a colour frame's block-padded sample planes between jpeg_idct and jpeg_colour (launch_jpeg_decode) or jpeg_samples and jpeg_fdct (launch_jpeg_encode)
     DeviceBuf jpegPlanes;
+    // OpenEXR: the tiles' byte sums between exr_undo_sums and exr_undo (launch_exr_undo)
+    DeviceBuf exrSums;
     // dxtex_compress_many (host pointers): double-buffered pinned + device staging, copy streams on either side of ctx->stream
     struct Lane
     {
@@ -1968,6 +1971,135 @@ dxtex_hresult dxtex_png_unpack(dxtex_ctx* ctx, const void* rows, size_t rowsByte
 
 dxtex_hresult dxtex_png_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes) { return png_pack(ctx, src, rows, rowsBytes, true); }
 dxtex_hresult dxtex_png_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes) { return png_pack(ctx, src, rows, rowsBytes, false); }
+
+namespace
+{
+static_assert(DXTEX_EXR_UINT == EXR_UINT && DXTEX_EXR_HALF == EXR_HALF && DXTEX_EXR_FLOAT == EXR_FLOAT && DXTEX_EXR_ABSENT == EXR_ABSENT, "dxtex_exr.h's channel types are the public ones");
+static_assert(sizeof(dxtex_exr_chunk) == sizeof(ExrChunk) && sizeof(dxtex_exr_channel) == sizeof(ExrChannel), "dxtex_exr.h's descriptors are the public ones");
+
+// The checks of dxtex_exr_unpack[_device], in the order include/dxtex_amd.h states. *layout and *list = what the launchers take.
+dxtex_hresult check_exr_unpack(dxtex_ctx* ctx, const void* stream, size_t streamBytes, const dxtex_exr_chunk* chunks, size_t chunkCount, const dxtex_exr_channel* channels,
+                               uint32_t scanlineBytes, const dxtex_image* items, size_t itemCount, ExrLayout* layout, std::vector<ExrChunk>* list)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!stream) return fail(ctx, DXTEX_E_POINTER, "null stream");
+    if (!chunks) return fail(ctx, DXTEX_E_POINTER, "null chunk descriptors");
+    if (!channels) return fail(ctx, DXTEX_E_POINTER, "null channel table");
+    if (!items) return fail(ctx, DXTEX_E_POINTER, "null items");
+    for (size_t i = 0; i < itemCount && i < kExrItemsMax; ++i) if (!items[i].pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!chunkCount) return fail(ctx, DXTEX_E_INVALIDARG, "no chunks");
+    if (!itemCount || itemCount > kExrItemsMax) return fail(ctx, DXTEX_E_INVALIDARG, "1 to 6 items");
+    const size_t width = items[0].width, height = items[0].height;
+    if (!width || !height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    if (width > 0x0FFFFFFFull || height > 0x0FFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    for (uint32_t c = 0; c < 4; ++c) if (channels[c].type > EXR_ABSENT) return fail(ctx, DXTEX_E_INVALIDARG, "unknown channel type");
+    if (!scanlineBytes) return fail(ctx, DXTEX_E_INVALIDARG, "a scanline of no bytes");
+    for (size_t i = 0; i < itemCount; ++i) if (items[i].format != FMT_R16G16B16A16_FLOAT) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "EXR chunks unpack into R16G16B16A16_FLOAT");
+    for (size_t i = 1; i < itemCount; ++i) if (items[i].width != width || items[i].height != height) return fail(ctx, DXTEX_E_INVALIDARG, "items of different sizes");
+    for (uint32_t c = 0; c < 4; ++c)
+        if (channels[c].type != EXR_ABSENT && (channels[c].offset > scanlineBytes || uint64_t(width) * exr_type_bytes(channels[c].type) > scanlineBytes - channels[c].offset))
+            return fail(ctx, DXTEX_E_INVALIDARG, "a channel's samples leave the scanline");
+    const uint64_t rows = uint64_t(height) * itemCount;
+    uint64_t end = 0;
+    list->resize(chunkCount);
+    for (size_t i = 0; i < chunkCount; ++i)
+    {
+        const dxtex_exr_chunk& c = chunks[i];
+        if (c.coded > 1u || !c.rows || c.offset > streamBytes || c.bytes > streamBytes - c.offset) return fail(ctx, DXTEX_E_INVALIDARG, "a chunk descriptor leaves the stream");
+        if (uint64_t(c.rows) * scanlineBytes != c.bytes) return fail(ctx, DXTEX_E_INVALIDARG, "a chunk is not rows * scanlineBytes long");
+        if (c.firstRow >= rows || c.rows > rows - c.firstRow) return fail(ctx, DXTEX_E_INVALIDARG, "a chunk names rows outside the window");
+        if (c.offset < end) return fail(ctx, DXTEX_E_INVALIDARG, "chunk descriptors overlap or are not in stream order");
+        end = c.offset + c.bytes;
+        (*list)[i] = ExrChunk{ c.offset, c.bytes, c.firstRow, c.rows, c.coded };
+    }
+    const size_t rowBytes = width * 8;
+    for (size_t i = 0; i < itemCount; ++i)
+    {
+        const dxtex_hresult hr = check_stream_image(ctx, "stream", stream, streamBytes, &items[i], rowBytes);
+        if (hr != DXTEX_S_OK) return hr;
+    }
+    *layout = ExrLayout{ uint32_t(width), uint32_t(rows), uint32_t(height), scanlineBytes,
+                         { { channels[0].offset, channels[0].type }, { channels[1].offset, channels[1].type }, { channels[2].offset, channels[2].type }, { channels[3].offset, channels[3].type } } };
+    return DXTEX_S_OK;
+}
+
+// exr_undo in place, then exr_texels: what both forms queue
+dxtex_hresult submit_exr_unpack(dxtex_ctx* ctx, uint8_t* stream, const std::vector<ExrChunk>& list, const ExrLayout& layout, const dxtex_image* items, size_t itemCount)
+{
+    const dxtex_hresult hr = ctx->exrSums.grow(ctx, std::max<size_t>(1, exr_undo_sums_count(list.data(), list.size())) * sizeof(uint32_t), 1u << 16);
+    if (hr != DXTEX_S_OK) return hr;
+    ImgView views[kExrItemsMax];
+    for (size_t i = 0; i < itemCount; ++i) views[i] = view_of(items[i]);
+    hipError_t e = launch_exr_undo(stream, list.data(), list.size(), static_cast<uint32_t*>(ctx->exrSums.p), ctx->stream, marks_of(ctx));
+    if (e == hipSuccess) e = launch_exr_texels(stream, list.data(), list.size(), layout, views, itemCount, ctx->stream, marks_of(ctx));
+    return launched(ctx, e);
+}
+
+dxtex_hresult check_exr_pack(dxtex_ctx* ctx, const dxtex_image* src, const void* scanlines, size_t scanlineBytes, int* source, size_t* rowBytes, size_t* need)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!src->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!scanlines) return fail(ctx, DXTEX_E_POINTER, "null scanlines");
+    if (!src->width || !src->height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    if (src->width > 0x0FFFFFFFull || src->height > 0x0FFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    *source = exr_pack_source(src->format);
+    if (*source < 0) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "no EXR writer case for this format");
+    *need = src->width * src->height * kExrFileTexelBytes;
+    *rowBytes = src->width * exr_source_bytes(*source);
+    if (scanlineBytes < *need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer than width * height * 8 bytes of scanlines");
+    return check_stream_image(ctx, "scanlines", scanlines, *need, src, *rowBytes);
+}
+
+dxtex_hresult exr_pack(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes, bool device)
+{
+    int source; size_t rowBytes, need;
+    const dxtex_hresult hr = check_exr_pack(ctx, src, scanlines, scanlineBytes, &source, &rowBytes, &need);
+    if (hr != DXTEX_S_OK) return hr;
+    auto pack = [&](const dxtex_image& s, uint8_t* out) { return launched(ctx, launch_exr_pack(view_of(s), source, out, ctx->stream, marks_of(ctx))); };
+    if (device) return run_timed(ctx, [&] { return pack(*src, static_cast<uint8_t*>(scanlines)); });
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, scanlines, need, [&](uint8_t* in, uint8_t* out) { return pack(with_pixels(*src, in), out); });
+}
+} // namespace
+
+dxtex_hresult dxtex_exr_unpack_device(dxtex_ctx* ctx, void* stream, size_t streamBytes, const dxtex_exr_chunk* chunks, size_t chunkCount,
+                                      const dxtex_exr_channel* channels, uint32_t scanlineBytes, const dxtex_image* items, size_t itemCount)
+{
+    ExrLayout layout; std::vector<ExrChunk> list;
+    const dxtex_hresult hr = check_exr_unpack(ctx, stream, streamBytes, chunks, chunkCount, channels, scanlineBytes, items, itemCount, &layout, &list);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_exr_unpack(ctx, static_cast<uint8_t*>(stream), list, layout, items, itemCount); });
+}
+
+dxtex_hresult dxtex_exr_unpack(dxtex_ctx* ctx, const void* stream, size_t streamBytes, const dxtex_exr_chunk* chunks, size_t chunkCount,
+                               const dxtex_exr_channel* channels, uint32_t scanlineBytes, const dxtex_image* items, size_t itemCount)
+{
+    ExrLayout layout; std::vector<ExrChunk> list;
+    dxtex_hresult hr = check_exr_unpack(ctx, stream, streamBytes, chunks, chunkCount, channels, scanlineBytes, items, itemCount, &layout, &list);
+    if (hr != DXTEX_S_OK) return hr;
+    // the stream goes up as it is; the items' rows are written tight (rounded up to 16 bytes) into the output staging, one item behind
+    // another, and only each row's texels come down, through the caller's pitches
+    const size_t rowBytes = size_t(layout.width) * 8, pitch = (rowBytes + 15) & ~size_t(15), itemBytes = pitch * layout.itemRows;
+    ScopedDevice sd(ctx->device);
+    hr = ctx->stageIn.grow(ctx, streamBytes); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, itemBytes * itemCount); if (hr != DXTEX_S_OK) return hr;
+    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, stream, streamBytes, hipMemcpyHostToDevice, ctx->stream));
+    dxtex_image staged[kExrItemsMax];
+    for (size_t i = 0; i < itemCount; ++i)
+    {
+        staged[i] = with_pixels(items[i], ctx->stageOut.u8() + i * itemBytes);
+        staged[i].rowPitch = pitch; staged[i].slicePitch = itemBytes;
+    }
+    hr = run_timed(ctx, [&] { return submit_exr_unpack(ctx, ctx->stageIn.u8(), list, layout, staged, itemCount); });
+    if (hr != DXTEX_S_OK) return hr;
+    for (size_t i = 0; i < itemCount; ++i)
+        HIP_TRY(ctx, counted_copy_rows(ctx, items[i].pixels, items[i].rowPitch, staged[i].pixels, pitch, rowBytes, layout.itemRows, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DXTEX_S_OK;
+}
+
+dxtex_hresult dxtex_exr_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes) { return exr_pack(ctx, src, scanlines, scanlineBytes, true); }
+dxtex_hresult dxtex_exr_pack(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes) { return exr_pack(ctx, src, scanlines, scanlineBytes, false); }
 
 namespace
 {

@@ -153,6 +153,19 @@ hipError_t launch_jpeg_decode(const int16_t* coefficients, const JpegFrame& fram
 // every component in one launch into the reader's coefficient layout at `coefficients` (any even address). src is not written.
 hipError_t launch_jpeg_encode(const ImgView& src, bool bgr, const JpegFrame& frame, int16_t* coefficients, uint8_t* planes, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// OpenEXR scanline chunks (exr.hip; the rules are in dxtex_exr.h). The caller has checked every descriptor against the stream and the
+// layout. launch_exr_undo runs the byte-wise prefix sum of every coded chunk in place (`sums`: exr_undo_sums_count(chunks, count) words of
+// device memory, read and written only where a coded chunk is longer than kExrUndoTile); launch_exr_texels then writes the rows of every
+// chunk into the R16G16B16A16_FLOAT items, row y of the window at row y % itemRows of item y / itemRows. launch_exr_pack: the writer's
+// rows, 8 * width bytes each (the A, B, G, R half planes), from level 0 of an image of one of dxtex_exr.h's sources.
+struct ExrChunk;
+struct ExrLayout;
+size_t exr_undo_sums_count(const ExrChunk* chunks, size_t count);
+hipError_t launch_exr_undo(uint8_t* stream, const ExrChunk* chunks, size_t count, uint32_t* sums, hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_exr_texels(const uint8_t* stream, const ExrChunk* chunks, size_t count, const ExrLayout& layout, const ImgView* items, size_t itemCount,
+                             hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_exr_pack(const ImgView& src, int source, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

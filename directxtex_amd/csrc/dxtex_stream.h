@@ -1,4 +1,4 @@
-// The texel-stream layer under the five file codecs (rgbe.hip, tga.hip, dds.hip, pnm.hip, png.hip and their dxtex_*.h): what moving a
+// The texel-stream layer under the file codecs (rgbe.hip, tga.hip, dds.hip, pnm.hip, png.hip, exr.hip and their dxtex_*.h): what moving a
 // file's texels at their own bytes a texel needs whatever the format, once. The per-format headers hold only their enums, tables and
 // texel rules and call these directly.
 //

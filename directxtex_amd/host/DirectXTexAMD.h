@@ -860,4 +860,64 @@ HRESULT SaveJPEGRaw(const JPEGRawImage& raw, Blob& blob) noexcept;
 // those of the host forms.
 HRESULT SaveToJPEGMemory(Device& device, const Image& deviceImage, JPEG_FLAGS flags, Blob& blob) noexcept;
 HRESULT SaveToJPEGFile(Device& device, const Image& deviceImage, JPEG_FLAGS flags, const char* szFile) noexcept;
+
+// ---- OpenEXR, Auxiliary/DirectXTexEXR.cpp (the reference's codec over the OpenEXR library's RgbaInputFile / RgbaOutputFile): single-part
+// scanline files of compression NONE, RLE, ZIPS and ZIP in, NONE out. No library is linked: the header walk, the offset table, the RLE
+// packets and - through DirectXTexAMD_Inflate.h - inflate are this project's own code; what happens to a chunk's bytes after that is
+// csrc/dxtex_exr.h's. Metadata follow LoadFromEXRCommon / GetMetadataFromEXR*: R16G16B16A16_FLOAT, 2-D, one mip, the image is the data
+// window; with an `envmap` attribute and width == height / 6 the height becomes the width and there are six array items. Channels follow
+// RgbaInputFile: absent R, G, B read 0 and absent A 1.0; a file with Y and none of R, G, B reads R = G = B = Y; channels of other names,
+// layer-prefixed ones included, are skipped; FLOAT and UINT samples become halves by the library's floatToHalf / uintToHalf (csrc/dxtex_exr.h).
+// Null arguments are E_INVALIDARG, a missing file HRESULT_ERROR_FILE_NOT_FOUND, and E_FAIL is: bad magic, truncation, a malformed header
+// or channel list, a missing needed attribute (channels, compression, dataWindow, displayWindow, lineOrder, pixelAspectRatio,
+// screenWindowCenter, screenWindowWidth), an empty or overflowing window, an offset of zero or outside the file, a chunk whose y is not
+// its table slot's, an expansion that does not give exactly the plain size. Departures:
+//   1. HRESULT_E_NOT_SUPPORTED where the library would go on: tiled, deep and multipart files; PIZ, PXR24, B44, B44A, DWAA and DWAB;
+//      RY / BY chroma channels; a channel among R, G, B, A, Y that is used and whose sampling is not 1.
+//   2. Chunks are read through the offset table alone, so the line order needs no handling and an incomplete table is not reconstructed.
+//   3. The writer stores compression NONE, one scanline a chunk, where the reference writes ZIP through zlib; the texels are the same:
+//      channels A, B, G, R, all HALF, increasing Y, data window = display window = 0, 0, w-1, h-1, the eight needed attributes in name
+//      order. R16G16B16A16_FLOAT moves as bits; R32G32B32A32_FLOAT and R32G32B32_FLOAT (alpha 1.0) become halves by XMConvertFloatToHalf,
+//      as the reference's XMStoreHalf4 does; every other format is HRESULT_E_NOT_SUPPORTED.
+//   4. The preview image and every attribute beyond those named are ignored.
+// Out of scope: PIZ and the lossy codecs, tiled, deep and multipart files, luminance-chroma files, a deflating writer. -------------------------
+HRESULT GetMetadataFromEXRMemory(const void* pSource, size_t size, TexMetadata& metadata) noexcept;
+HRESULT GetMetadataFromEXRFile(const char* szFile, TexMetadata& metadata) noexcept;
+HRESULT LoadFromEXRMemory(const void* pSource, size_t size, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT LoadFromEXRFile(const char* szFile, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT SaveToEXRMemory(const Image& image, Blob& blob) noexcept;
+HRESULT SaveToEXRFile(const Image& image, const char* szFile) noexcept;
+// The reader's byte-serial half, which needs no device: the header walk, every refusal, the offset table, inflate and the RLE packets. What
+// comes back is ONE STREAM of the chunks' expanded bytes, coded or plain (csrc/dxtex_exr.h), and dxtex_exr_unpack's other arguments: a
+// descriptor per chunk - consecutive plain chunks that follow one another in the stream and in the window share one - and where R, G, B
+// and A lie in a scanline. A coded chunk starts on a multiple of 16 bytes of the stream. GetMetadata* stop behind the header. On failure
+// `raw` is released.
+struct EXRRawImage
+{
+    struct Chunk { uint64_t offset; uint32_t bytes, firstRow, rows, coded; };          // dxtex_exr_chunk's layout
+    struct Channel { uint32_t offset, type; };                                          // dxtex_exr_channel's; type DXTEX_EXR_*
+    uint32_t compression = 0;                    // the file's code: 0 NONE, 1 RLE, 2 ZIPS, 3 ZIP
+    uint32_t scanlineBytes = 0;                  // of every channel of the file, skipped ones included
+    Channel channel[4] = {};                     // R, G, B, A
+    std::unique_ptr<Chunk[]> chunks;
+    size_t chunkCount = 0;
+    size_t deflatedBytes = 0;                    // of the file's chunks as stored
+    const uint8_t* stream = nullptr;             // into `storage`
+    size_t streamBytes = 0;
+    Blob storage;
+    void Release() noexcept;
+};
+HRESULT LoadFromEXRMemoryRaw(const void* pSource, size_t size, TexMetadata* metadata, EXRRawImage& raw) noexcept;
+HRESULT LoadFromEXRFileRaw(const char* szFile, TexMetadata* metadata, EXRRawImage& raw) noexcept;
+// Resident forms: the stream crosses PCIe as it leaves the inflater - 6 bytes a texel for RGB half - and the delta undo (a byte-wise prefix
+// sum), the plane gather, the sample conversion and the channel fill run on the device (dxtex_exr_unpack_device). HRESULTs, metadata and
+// pixels are those of the host forms. Load: one upload of streamBytes, no download; the result is released on failure. Save: deviceImage's
+// pixels are a device pointer, as DeviceScratchImage::GetImage gives; the scanlines come down at 8 bytes a texel, straight behind the
+// header and offset table and between the chunk headers the host wrote.
+HRESULT LoadFromEXRMemory(Device& device, const void* pSource, size_t size, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromEXRFile(Device& device, const char* szFile, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device
+HRESULT UploadEXRRaw(Device& device, const TexMetadata& metadata, const EXRRawImage& raw, DeviceScratchImage& image) noexcept;
+HRESULT SaveToEXRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept;
+HRESULT SaveToEXRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
 } // namespace DirectXTexAMD

@@ -1,4 +1,4 @@
-// What the file codecs of the host layer share (DirectXTexAMD_DDS / _HDR / _TGA / _PNM / _PNG / _JPEG.cpp): a whole file into a Blob, a
+// What the file codecs of the host layer share (DirectXTexAMD_DDS / _HDR / _TGA / _PNM / _PNG / _JPEG / _EXR.cpp): a whole file into a Blob, a
 // Blob into a file, the file twins of the Memory forms, an Image as the C ABI takes it, device memory that lives as long as a scope, and
 // the frame of a resident load and a resident save. Not part of the public interface. Header-only, and every definition has internal
 // linkage: a translation unit compiled on its own, as the sanitised test programs compile one codec each, calls its own copy.

@@ -1,5 +1,5 @@
-// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG and JPEG in; DDS out (TGA / HDR /
-// PNG / JPEG too for the single-image results). Every input is loaded on the host, checked, uploaded ONCE, run through texassemble's per-input
+// dxtexassemble: texassemble's commands (Texassemble/texassemble.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG, JPEG and OpenEXR in; DDS out (TGA / HDR /
+// PNG / JPEG / OpenEXR too for the single-image results). Every input is loaded on the host, checked, uploaded ONCE, run through texassemble's per-input
 // pipeline on the device (decompress, -stripmips, -alpha, resize, -tonemap, convert), assembled there - every face, slice, item or mip a
 // rectangle of one batched copy_rect launch - and the result is downloaded once.
 //
@@ -273,7 +273,7 @@ int Parse(int argc, char** argv, Options& o)
     }
     if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     const bool single = IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP || o.command == CMD_MERGE;
-    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr") || hasExt(o.output, ".png") || hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg"))))
+    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr") || hasExt(o.output, ".png") || hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg") || hasExt(o.output, ".exr"))))
     {
         std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga, .hdr, .png or .jpg" : "");
         return 1;
@@ -312,7 +312,7 @@ int Fail(const char* what, HRESULT hr)
 // an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
 // a .tga input likewise as the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
 // a .dds input as the file itself, parsed: its payload goes up as it is and the row conversions of a legacy file run on the device
-struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; bool png = false; PNGRawImage pngRaw; bool jpeg = false; JPEGRawImage jpegRaw; };
+struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; bool png = false; PNGRawImage pngRaw; bool jpeg = false; JPEGRawImage jpegRaw; bool exr = false; EXRRawImage exrRaw; };
 
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
 int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
@@ -374,6 +374,13 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
             hr = LoadFromJPEGFileRaw(file.c_str(), JPEG_FLAGS_NONE, &in->info, in->jpegRaw);
             if (FAILED(hr)) return Fail(" FAILED", hr);
         }
+        else if (hasExt(file, ".exr"))
+        {
+            // the header walk, inflate and the RLE packets here, before there is a device; the expanded chunks go up later
+            in->exr = true;
+            hr = LoadFromEXRFileRaw(file.c_str(), &in->info, in->exrRaw);
+            if (FAILED(hr)) return Fail(" FAILED", hr);
+        }
         else if (hasExt(file, ".hdr")) { in->hdr = true; hr = LoadFromHDRFileRGBE(file.c_str(), &in->info, in->exposure, in->rgbe); if (FAILED(hr)) return Fail(" FAILED", hr); }
         else { std::printf(" FAILED: only .dds, .tga, .hdr, .png and .jpg can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
@@ -416,9 +423,10 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : in.tga ? UploadTGARaw(dev, in.info, TGA_FLAGS_NONE, in.tgaRaw, cur)
                                         : in.png ? UploadPNGRaw(dev, in.info, in.pngRaw, cur)
                                         : in.jpeg ? UploadJPEGRaw(dev, in.info, in.jpegRaw, cur)
+                                        : in.exr ? UploadEXRRaw(dev, in.info, in.exrRaw, cur)
                                                                                               : UploadDDSRaw(dev, in.dds, cur);
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release(); in.pngRaw.Release(); in.jpegRaw.Release();
+        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release(); in.pngRaw.Release(); in.jpegRaw.Release(); in.exrRaw.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
@@ -548,6 +556,7 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     else if (tgaOut) hr = SaveToTGAFile(dev, *result.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
     else if (hasExt(o.output, ".png")) hr = SaveToPNGFile(dev, *result.GetImage(0, 0, 0), PNG_FLAGS_NONE, o.output.c_str());          // the file's rows, likewise
     else if (hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg")) hr = SaveToJPEGFile(dev, *result.GetImage(0, 0, 0), JPEG_FLAGS_NONE, o.output.c_str());          // the coefficients
+    else if (hasExt(o.output, ".exr")) hr = SaveToEXRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());          // the scanlines' half planes
     else hr = SaveToDDSFile(dev, result.GetImages(), result.GetImageCount(), result.GetMetadata(),
                             o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED", hr);

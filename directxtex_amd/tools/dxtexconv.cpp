@@ -6,9 +6,9 @@
 // (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
 // rotations, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
-//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg>...
-//                          (-ft hdr | tga | ppm | pfm | png: Radiance / TGA / portable pixmap / PNG output of level 0)
-//                          (-ft png: <out> is a directory or a .png name)
+//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr>...
+//                          (-ft hdr | tga | ppm | pfm | png | exr: Radiance / TGA / portable pixmap / PNG / OpenEXR output of level 0)
+//                          (-ft png, -ft exr: <out> is a directory or a .png / .exr name)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
 //     -m <n>               mip levels, 0 = full chain           -fl <9.1 .. 12.2> feature level: largest texture side allowed
 //     -f <format>          DXGI format name or number           -if <filter>      POINT LINEAR CUBIC FANT BOX TRIANGLE
@@ -99,7 +99,7 @@ struct Options
 {
     size_t width = 0, height = 0, mipLevels = 0, maxSize = 16384;          // mipLevels 0: keep a chain the input has, else build the full one
     bool pow2 = false, pmalpha = false, demul = false, dx10 = false, dx9 = false, sepalpha = false, lower = false, overwrite = false,
-         timing = false, nologo = false, hdrOut = false, tgaOut = false, ppmOut = false, pfmOut = false, pngOut = false, ignoreSrgb = false, tga20 = false, info = false;
+         timing = false, nologo = false, hdrOut = false, tgaOut = false, ppmOut = false, pfmOut = false, pngOut = false, exrOut = false, ignoreSrgb = false, tga20 = false, info = false;
     uint32_t format = 0, filter = 0, filterOpts = 0, srgb = 0, convert = 0, compress = 0, ddsRead = DDS_FLAGS_ALLOW_LARGE_FILES;
     float alphaThreshold = TEX_THRESHOLD_DEFAULT, keepCoverage = 0.f;
     bool nmap = false;                  // -nmap: ComputeNormalMap replaces the convert step
@@ -144,7 +144,7 @@ int usage()
                          "                 [--rotate-color 709toHDR10|HDR10to709|709to2020|2020to709|P3D65toHDR10|P3D65to2020|709toP3D65|P3D65to709] [--paper-white-nits N]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N]\n"
-                         "                 [-ft dds|hdr|tga|ppm|pfm|png] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg>...\n");
+                         "                 [-ft dds|hdr|tga|ppm|pfm|png|exr] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr>...\n");
     return 1;
 }
 
@@ -291,6 +291,7 @@ bool Parse(int argc, char** argv, Options& o)
             else if (!strcasecmp(ft, "ppm")) o.ppmOut = true;
             else if (!strcasecmp(ft, "pfm")) o.pfmOut = true;
             else if (!strcasecmp(ft, "png")) o.pngOut = true;
+            else if (!strcasecmp(ft, "exr")) o.exrOut = true;
             else if (!strcasecmp(ft, "jpg") || !strcasecmp(ft, "jpeg")) { std::fprintf(stderr, "-ft %s: JPEG output is not written yet (the reader is; the writer is the next step)\n", ft); return false; }
             else if (strcasecmp(ft, "dds")) { std::fprintf(stderr, "output file types: dds, hdr, tga, ppm, pfm, png\n"); return false; }
         }
@@ -303,8 +304,11 @@ bool Parse(int argc, char** argv, Options& o)
     if (o.dx10 && o.dx9) { std::fprintf(stderr, "-dx10 and -dx9 exclude each other\n"); return false; }
     // -ft png: -o names a directory or a .png file. A name that ends in another type's extension would receive a PNG under that name, which no
     // reader that goes by the extension opens.
-    for (const char* ext : { ".dds", ".hdr", ".tga", ".ppm", ".pfm" })
+    for (const char* ext : { ".dds", ".hdr", ".tga", ".ppm", ".pfm", ".exr" })
         if (o.pngOut && o.out.size() > 4 && !strcasecmp(o.out.c_str() + o.out.size() - 4, ext)) { std::fprintf(stderr, "-ft png writes a .png: -o %s names a %s file\n", o.out.c_str(), ext); return false; }
+    // -ft exr likewise
+    for (const char* ext : { ".dds", ".hdr", ".tga", ".ppm", ".pfm", ".png" })
+        if (o.exrOut && o.out.size() > 4 && !strcasecmp(o.out.c_str() + o.out.size() - 4, ext)) { std::fprintf(stderr, "-ft exr writes a .exr: -o %s names a %s file\n", o.out.c_str(), ext); return false; }
     for (const char* ext : { ".jpg", ".jpeg" })
         if (o.out.size() > std::strlen(ext) && !strcasecmp(o.out.c_str() + o.out.size() - std::strlen(ext), ext)) { std::fprintf(stderr, "-o %s: JPEG output is not written yet\n", o.out.c_str()); return false; }
     if (o.gpus.empty()) o.gpus.assign(1, 0);
@@ -316,11 +320,11 @@ bool Parse(int argc, char** argv, Options& o)
 std::string OutputName(const Options& o, const std::string& input)
 {
     auto endsDDS = [](const std::string& s) { return s.size() > 4 && (!strcasecmp(s.c_str() + s.size() - 4, ".dds") || !strcasecmp(s.c_str() + s.size() - 4, ".hdr") || !strcasecmp(s.c_str() + s.size() - 4, ".tga") ||
-                                                                      !strcasecmp(s.c_str() + s.size() - 4, ".ppm") || !strcasecmp(s.c_str() + s.size() - 4, ".pfm") || !strcasecmp(s.c_str() + s.size() - 4, ".png")); };
+                                                                      !strcasecmp(s.c_str() + s.size() - 4, ".ppm") || !strcasecmp(s.c_str() + s.size() - 4, ".pfm") || !strcasecmp(s.c_str() + s.size() - 4, ".png") || !strcasecmp(s.c_str() + s.size() - 4, ".exr")); };
     if (o.inputs.size() == 1 && endsDDS(o.out) && o.prefix.empty() && o.suffix.empty()) return o.out;
     std::string base = input.substr(input.find_last_of('/') == std::string::npos ? 0 : input.find_last_of('/') + 1);
     if (base.find_last_of('.') != std::string::npos) base.erase(base.find_last_of('.'));
-    std::string name = o.prefix + base + o.suffix + (o.hdrOut ? ".hdr" : o.tgaOut ? ".tga" : o.ppmOut ? ".ppm" : o.pfmOut ? ".pfm" : o.pngOut ? ".png" : ".dds");
+    std::string name = o.prefix + base + o.suffix + (o.hdrOut ? ".hdr" : o.tgaOut ? ".tga" : o.ppmOut ? ".ppm" : o.pfmOut ? ".pfm" : o.pngOut ? ".png" : o.exrOut ? ".exr" : ".dds");
     if (o.lower) std::transform(name.begin(), name.end(), name.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     return o.out + "/" + name;
 }
@@ -370,6 +374,9 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     // the inverse DCT, upsampling and YCbCr -> RGB run on the device. The flag is texconv's (texconv.cpp:2192-2208)
     else if (hasExt(inFile, ".jpg") || hasExt(inFile, ".jpeg"))
         check("load", LoadFromJPEGFile(dev, inFile.c_str(), o.ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, &info, image));
+    // OpenEXR: the header walk, inflate and the RLE packets are byte-serial and run on the host, the chunks go up as they leave the inflater -
+    // 6 bytes a texel for RGB half - and the delta undo, the plane gather, the conversion to half and the channel fill run on the device
+    else if (hasExt(inFile, ".exr")) check("load", LoadFromEXRFile(dev, inFile.c_str(), &info, image));
     // DDS likewise: the payload goes up at the size it has in the file - a native file straight into the image's memory, a legacy one through
     // the row conversions on the device
     else check("load", LoadFromDDSFile(dev, inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, image));
@@ -609,10 +616,11 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     // -ft tga likewise: the file's rows (-tga20: and the TGA 2.0 extension area around them)
     // -ft ppm / pfm likewise: the file's samples, alpha dropped, halves widened and the rows of a .pfm flipped on the device
     // -ft png likewise: the file's rows, B and R exchanged, X dropped and 16-bit samples swapped on the device; the host wraps them (PNG_FLAGS_NONE)
+    // -ft exr likewise: the scanlines' A, B, G, R half planes, floats made halves on the device; they land between the chunk headers the host wrote
     uint32_t ddsFlags = DDS_FLAGS_NONE;
     if (o.dx10) ddsFlags |= DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2;
     else if (o.dx9) ddsFlags |= DDS_FLAGS_FORCE_DX9_LEGACY;
-    if ((o.hdrOut || o.tgaOut || o.ppmOut || o.pfmOut || o.pngOut) && handThrough)
+    if ((o.hdrOut || o.tgaOut || o.ppmOut || o.pfmOut || o.pngOut || o.exrOut) && handThrough)
     {
         // blocks handed through: the host codec's answer
         ScratchImage result;
@@ -621,6 +629,7 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         else if (o.ppmOut) check("save", SaveToPortablePixMapFile(result.GetImages()[0], outFile.c_str()));
         else if (o.pfmOut) check("save", SaveToPortablePixMapHDRFile(result.GetImages()[0], outFile.c_str()));
         else if (o.pngOut) check("save", SaveToPNGFile(result.GetImages()[0], PNG_FLAGS_NONE, outFile.c_str()));
+        else if (o.exrOut) check("save", SaveToEXRFile(result.GetImages()[0], outFile.c_str()));
         else check("save", SaveToTGAFile(result.GetImages()[0], TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));      // -tga20: with the TGA 2.0 extension area
     }
     else if (o.hdrOut) check("save", SaveToHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
@@ -628,6 +637,7 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     else if (o.ppmOut) check("save", SaveToPortablePixMapFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
     else if (o.pfmOut) check("save", SaveToPortablePixMapHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
     else if (o.pngOut) check("save", SaveToPNGFile(dev, *image.GetImage(0, 0, 0), PNG_FLAGS_NONE, outFile.c_str()));
+    else if (o.exrOut) check("save", SaveToEXRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
     else check("save", SaveToDDSFile(dev, image.GetImages(), image.GetImageCount(), info, DDS_FLAGS(ddsFlags), outFile.c_str()));
     image.Release();
     std::printf("writing %s (%zux%zu", outFile.c_str(), info.width, info.height);
@@ -654,6 +664,7 @@ int PrintInfo(const Options& o)
         const HRESULT hr = hasExt(".hdr") ? GetMetadataFromHDRFile(f.c_str(), m) : hasExt(".tga") ? GetMetadataFromTGAFile(f.c_str(), TGA_FLAGS_NONE, m)
                            : (hasExt(".ppm") || hasExt(".pfm") || hasExt(".phm")) ? GetMetadataFromPortablePixMapFile(f.c_str(), m)
                            : hasExt(".png") ? GetMetadataFromPNGFile(f.c_str(), o.ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE, m)
+                           : hasExt(".exr") ? GetMetadataFromEXRFile(f.c_str(), m)
                            : (hasExt(".jpg") || hasExt(".jpeg")) ? GetMetadataFromJPEGFile(f.c_str(), o.ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, m)
                                                                                                    : GetMetadataFromDDSFile(f.c_str(), DDS_FLAGS(o.ddsRead), m);
         if (FAILED(hr)) { std::printf("%s: FAILED (%08X)\n", f.c_str(), unsigned(hr)); ++failures; continue; }

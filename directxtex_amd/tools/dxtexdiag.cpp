@@ -1,10 +1,10 @@
-// dxtexdiag: texdiag's analyze, compare and diff commands (Texdiag/texdiag.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG and JPEG in.
+// dxtexdiag: texdiag's analyze, compare and diff commands (Texdiag/texdiag.cpp) on the MI355X host layer. DDS, HDR, TGA, PNG, JPEG and OpenEXR in.
 //
 //   dxtexdiag analyze [options] <files>            per image: minimum, average, maximum, variance, std dev, luminance, FP specials; BC files
 //                                                  also get the block-mode histogram (texdiag's print layout, :681-695, :795-856)
 //   dxtexdiag compare [options] <a> <b>            "Result: mse (r g b a) PSNR x dB" with 10 * log10(3 / (r + g + b)); when both files hold
 //                                                  the same number of mips, items and slices, every image and the minimum / average / maximum
-//   dxtexdiag diff [options] <a> <b> -o <out.dds|.tga|.hdr|.png|.jpg>     the difference map of the first images
+//   dxtexdiag diff [options] <a> <b> -o <out.dds|.tga|.hdr|.png|.jpg|.exr>     the difference map of the first images
 //
 //   -f <format>   diff: format of the map (default B8G8R8A8_UNORM)     -c <hex>   diff: colour 0xRRGGBB for texels over the threshold (masked to 24 bits)
 //   -t <float>    diff: threshold (default 0.25)                        -if <filter>  image filter for diff's conversions
@@ -152,7 +152,7 @@ bool Parse(int argc, char** argv, Options& o)
     {
         if (o.output.empty()) { std::fprintf(stderr, "diff wants -o <out.dds | out.tga | out.hdr | out.png | out.jpg>\n"); return false; }
         if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
-        if (!hasExt(o.output, ".dds") && !hasExt(o.output, ".tga") && !hasExt(o.output, ".hdr") && !hasExt(o.output, ".png") && !hasExt(o.output, ".jpg") && !hasExt(o.output, ".jpeg"))
+        if (!hasExt(o.output, ".dds") && !hasExt(o.output, ".tga") && !hasExt(o.output, ".hdr") && !hasExt(o.output, ".png") && !hasExt(o.output, ".jpg") && !hasExt(o.output, ".jpeg") && !hasExt(o.output, ".exr"))
         {
             std::fprintf(stderr, "the output file must be .dds, .tga or .hdr, or .png or .jpg\n");
             return false;
@@ -171,6 +171,7 @@ HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata
     HRESULT hr = hasExt(file, ".hdr") ? LoadFromHDRFile(dev, file.c_str(), &info, resident)
                : hasExt(file, ".tga") ? LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident)
                : hasExt(file, ".png") ? LoadFromPNGFile(dev, file.c_str(), PNG_FLAGS_NONE, &info, resident)          // texdiag.cpp:605-608
+               : hasExt(file, ".exr") ? LoadFromEXRFile(dev, file.c_str(), &info, resident)          // texdiag.cpp's USE_OPENEXR branch
                : (hasExt(file, ".jpg") || hasExt(file, ".jpeg")) ? LoadFromJPEGFile(dev, file.c_str(), JPEG_FLAGS_NONE, &info, resident)          // texdiag.cpp:599-602
                                       : LoadFromDDSFile(dev, file.c_str(), DDS_FLAGS(o.ddsRead), &info, resident);
     if (FAILED(hr) || !IsPlanar(info.format)) return hr;
@@ -388,6 +389,7 @@ int RunDiff(Device& dev, const Options& o)
         if (!out) return Fail("Failed diffing images", E_POINTER);
         hr = hasExt(o.output, ".tga") ? SaveToTGAFile(dev, *out, TGA_FLAGS_NONE, o.output.c_str())
            : hasExt(o.output, ".png") ? SaveToPNGFile(dev, *out, PNG_FLAGS_NONE, o.output.c_str())
+           : hasExt(o.output, ".exr") ? SaveToEXRFile(dev, *out, o.output.c_str())
            : (hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg")) ? SaveToJPEGFile(dev, *out, JPEG_FLAGS_NONE, o.output.c_str()) : SaveToDDSFile(dev, *out, DDS_FLAGS_NONE, o.output.c_str());
     }
     else

@@ -45,6 +45,10 @@
  *     libjpeg's jidctint.c, jdsample.c, jdcolor.c  :184-238
  *   SaveToJPEGFile in front of the Huffman coder: Auxiliary/DirectXTexJPEG.cpp    dxtex_jpeg_encode
  *     libjpeg's jccolor.c, jcsample.c, jfdctint.c  :240-300
+ *   LoadFromEXRFile behind the inflater (the    Auxiliary/DirectXTexEXR.cpp     dxtex_exr_unpack / dxtex_exr_pack
+ *     library's delta undo, plane interleave,    :286-321, :529-650
+ *     RgbaInputFile's fill and conversion), the
+ *     half planes of SaveToEXRFile
  *
  * Threading: a context is bound to one GPU and one HIP stream; use one context per GPU (or per host
  * thread). Contexts share nothing. No function retains caller pointers past its return, except the
@@ -562,6 +566,51 @@ dxtex_hresult dxtex_jpeg_encode(dxtex_ctx* ctx, const dxtex_image* src, const dx
 /* device pointers (the frame stays a host pointer, read before the call returns): asynchronous on the context's stream. The coefficients
  * may start at any even byte; see csrc/jpeg_encode.hip for the alignments that take 16-byte stores and the wide route of jpeg_samples. */
 dxtex_hresult dxtex_jpeg_encode_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jpeg_frame* frame, void* coefficients, size_t coefficientBytes);
+
+/* OpenEXR (.exr) scanline chunks: everything behind the header walk, the offset table, the inflater and the RLE packets, which are
+ * byte-serial and stay with the caller (Auxiliary/DirectXTexEXR.cpp reads through the OpenEXR library; csrc/dxtex_exr.h states the rules).
+ * The file side is ONE STREAM of the chunks' expanded bytes and a descriptor per chunk. A chunk holds `rows` scanlines of scanlineBytes
+ * each: for each scanline, for each channel of the file in name order, `width` samples. It is plain, or coded - what a ZIP, ZIPS or RLE
+ * chunk expands to: delta-coded bytes in two planes.
+ *   unpack   undoes every coded chunk (the byte-wise prefix sum, exr_undo; the planes are addressed, not moved), then writes every
+ *            chunk's rows (exr_texels): R, G, B and A are gathered through `channels` (entry 0 R .. 3 A: the byte offset of the channel's
+ *            samples within a scanline and DXTEX_EXR_UINT / _HALF / _FLOAT, or DXTEX_EXR_ABSENT), converted to half - HALF as bits; FLOAT
+ *            rounded to nearest even, but a finite value beyond +-65504 becomes the infinity and a NaN keeps its top mantissa bits; UINT
+ *            likewise, above 65504 +Inf - and an absent R, G or B reads 0, an absent A 1.0. Row y of the window lands at row
+ *            y % items[0].height of items[y / items[0].height]: one item, or the six faces of an environment map.
+ *   pack     level 0 of src -> the writer's scanlines, tight: for each row `width` halves of A, then of B, of G, of R (8 bytes a texel).
+ *            R16G16B16A16_FLOAT moves as bits; R32G32B32A32_FLOAT and R32G32B32_FLOAT (alpha 1.0) convert by XMConvertFloatToHalf.
+ * HRESULTs of unpack, in this order: E_POINTER for a null stream, chunks, channels, items or pixels; E_INVALIDARG for no chunks, no items
+ * or more than six, a width or height of zero, an unknown channel type or a scanlineBytes of zero; NOT_SUPPORTED for items that are not
+ * R16G16B16A16_FLOAT; E_INVALIDARG for items of different sizes, an offset in the channel table that leaves a scanline, a descriptor that
+ * leaves the stream, is not rows * scanlineBytes long, names rows outside the window or overlaps the one before it (descriptors are in
+ * ascending stream order), a row pitch smaller than the row, or a stream that overlaps an item's pixels.
+ * HRESULTs of pack: E_POINTER for a null image, pixels or scanlines; E_INVALIDARG for a width or height of zero; NOT_SUPPORTED for any
+ * other format; E_INVALIDARG for fewer than width * height * 8 bytes, a row pitch smaller than the row, or scanlines that overlap the
+ * pixels. Bytes of the items outside each row's texels, and rows no chunk names, are not written. */
+#define DXTEX_EXR_UINT    0u
+#define DXTEX_EXR_HALF    1u
+#define DXTEX_EXR_FLOAT   2u
+#define DXTEX_EXR_ABSENT  3u
+typedef struct dxtex_exr_chunk
+{
+    uint64_t offset;               /* of the chunk's first byte in the stream */
+    uint32_t bytes;                /* rows * scanlineBytes */
+    uint32_t firstRow, rows;       /* of the window, from its top */
+    uint32_t coded;                /* 0 plain, 1 coded */
+} dxtex_exr_chunk;
+typedef struct dxtex_exr_channel { uint32_t offset, type; } dxtex_exr_channel;
+/* host pointers, through the context's staging: the stream goes up as it is (and is not written), the rows come down through the items'
+ * pitches */
+dxtex_hresult dxtex_exr_unpack(dxtex_ctx* ctx, const void* stream, size_t streamBytes, const dxtex_exr_chunk* chunks, size_t chunkCount,
+                               const dxtex_exr_channel* channels, uint32_t scanlineBytes, const dxtex_image* items, size_t itemCount);
+dxtex_hresult dxtex_exr_pack(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes);
+/* device pointers (the descriptors and the channel table stay host pointers, read before the call returns): asynchronous on the
+ * context's stream. THE STREAM IS WRITTEN: its coded chunks are left undone in place. It may start at any byte; see csrc/exr.hip for the
+ * alignments that take the wide routes (stream and coded chunks on multiples of 16). */
+dxtex_hresult dxtex_exr_unpack_device(dxtex_ctx* ctx, void* stream, size_t streamBytes, const dxtex_exr_chunk* chunks, size_t chunkCount,
+                                      const dxtex_exr_channel* channels, uint32_t scanlineBytes, const dxtex_image* items, size_t itemCount);
+dxtex_hresult dxtex_exr_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes);
 
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
