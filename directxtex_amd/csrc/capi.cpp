@@ -17,6 +17,7 @@
 #include "dxtex_plan.h"
 #include "dxtex_copyrect.h"
 #include "dxtex_plane.h"
+#include "dxtex_staging.h"
 #include "triangle_filter.h"
 
 #include <hip/hip_runtime.h>
@@ -153,11 +154,19 @@ inline hipError_t counted_copy(dxtex_ctx* ctx, void* dst, const void* src, size_
     return hipMemcpyAsync(dst, src, bytes, kind, stream);
 }
 
-// rows of rowBytes between host and device through their own pitches, counted like every other transfer
+// rows of rowBytes between host and device through their own pitches, counted like every other transfer. A row of the packed formats can
+// be longer than a pitch (see check_copy_rect): such rows travel one by one, in order, so that the later row wins as in the reference.
 hipError_t counted_copy_rows(dxtex_ctx* ctx, void* dst, size_t dstPitch, const void* src, size_t srcPitch, size_t rowBytes, size_t rows, hipMemcpyKind kind)
 {
     if (!rows || !rowBytes) return hipSuccess;
     if (rows == 1 || (dstPitch == rowBytes && srcPitch == rowBytes)) return counted_copy(ctx, dst, src, rowBytes * rows, kind, ctx->stream);
+    if (rowBytes > dstPitch || rowBytes > srcPitch)
+    {
+        hipError_t e = hipSuccess;
+        for (size_t y = 0; y < rows && e == hipSuccess; ++y)
+            e = counted_copy(ctx, static_cast<uint8_t*>(dst) + y * dstPitch, static_cast<const uint8_t*>(src) + y * srcPitch, rowBytes, kind, ctx->stream);
+        return e;
+    }
     if (kind == hipMemcpyHostToDevice) ctx->h2dBytes += rowBytes * rows; else ctx->d2hBytes += rowBytes * rows;
     return hipMemcpy2DAsync(dst, dstPitch, src, srcPitch, rowBytes, rows, kind, ctx->stream);
 }
@@ -349,47 +358,58 @@ dxtex_hresult run_timed(dxtex_ctx* ctx, Submit&& submit)
     return hr;
 }
 
-// The staging of every single-image host-pointer entry point: inBytes from hostIn go up into ctx->stageIn, submit(stageIn, stageOut)
-// queues the kernels between the timing events (so dxtex_ctx_last_kernel_ms covers kernels only), outBytes of ctx->stageOut come back
-// to hostOut, and the call returns once they have landed. A failed submit returns at once: no download, no synchronisation. A call whose
-// kernels leave a second, small result in device memory of the context (devOut2, out2Bytes) gets it to hostOut2 in the same download.
+// Every host-pointer entry point, after its checks: the plan's two buffers grown, its uploads issued, submit(stageIn, stageOut) - which
+// queues the kernels on the staged bytes - between the timing events (so dxtex_ctx_last_kernel_ms covers kernels only), the plan's downloads,
+// and the call returns once they have landed. A failed submit returns at once: no download, no synchronisation. A submit that times itself
+// (or runs untimed) says so with timed = false. The bases are only valid inside submit: the buffers may move when they grow.
 template<class Submit>
-dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, void* hostOut, size_t outBytes, Submit&& submit,
-                         void* hostOut2 = nullptr, const void* devOut2 = nullptr, size_t out2Bytes = 0)
+dxtex_hresult run_plan(dxtex_ctx* ctx, const StagingPlan& plan, Submit&& submit, bool timed = true)
 {
+    if (!plan.ok()) return fail(ctx, DXTEX_E_INVALIDARG, "the bytes to stage overflow");
     ScopedDevice sd(ctx->device);
-    dxtex_hresult hr = ctx->stageIn.grow(ctx, inBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, outBytes); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, hostIn, inBytes, hipMemcpyHostToDevice, ctx->stream));
-    hr = run_timed(ctx, [&] { return submit(ctx->stageIn.u8(), ctx->stageOut.u8()); });
+    dxtex_hresult hr = ctx->stageIn.grow(ctx, plan.need(STAGE_IN)); if (hr != DXTEX_S_OK) return hr;
+    hr = ctx->stageOut.grow(ctx, plan.need(STAGE_OUT)); if (hr != DXTEX_S_OK) return hr;
+    uint8_t* const base[2] = { ctx->stageIn.u8(), ctx->stageOut.u8() };
+    for (const StageCopy& c : plan.uploads())
+        HIP_TRY(ctx, counted_copy_rows(ctx, base[STAGE_IN] + c.at(), c.devPitch, c.host, c.hostPitch, c.rowBytes, c.rows, hipMemcpyHostToDevice));
+    hr = timed ? run_timed(ctx, [&] { return submit(base[STAGE_IN], base[STAGE_OUT]); }) : submit(base[STAGE_IN], base[STAGE_OUT]);
     if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, hostOut, ctx->stageOut.p, outBytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (out2Bytes) HIP_TRY(ctx, counted_copy(ctx, hostOut2, devOut2, out2Bytes, hipMemcpyDeviceToHost, ctx->stream));
+    for (const StageCopy& c : plan.downloads())
+        HIP_TRY(ctx, counted_copy_rows(ctx, c.host, c.hostPitch, base[c.part.buf] + c.at(), c.devPitch, c.rowBytes, c.rows, hipMemcpyDeviceToHost));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DXTEX_S_OK;
 }
 
-// The staged-rows unpack of the PNM and PNG host forms: the `need` bytes of the file side go up as they are; the kernel writes tight rows
-// (rounded up to 16 bytes, so that a width of whole groups keeps the wide route) into the output staging, and only each row's texels come
-// down, through the caller's pitch. launch(stream, view) queues the kernel.
+// One flat run of bytes up and one down: the single-image entry points and the codecs' pack side
+template<class Submit>
+dxtex_hresult run_staged(dxtex_ctx* ctx, const void* hostIn, size_t inBytes, void* hostOut, size_t outBytes, Submit&& submit)
+{
+    StagingPlan plan;
+    plan.upload(hostIn, plan.in(inBytes), inBytes);
+    plan.download(hostOut, plan.out(outBytes), outBytes);
+    return run_plan(ctx, plan, submit);
+}
+
+// The staged-rows unpack of the PNM, PNG and JPEG host forms: the `need` bytes of the file side go up as they are; the kernel writes tight
+// rows (rounded up to 16 bytes, so that a width of whole groups keeps the wide route) into the output staging, and only each row's texels
+// come down, through the caller's pitch. launch(stream, view) queues the kernel.
 template<class Launch>
 dxtex_hresult run_staged_rows(dxtex_ctx* ctx, const void* hostIn, size_t need, const dxtex_image* dst, size_t rowBytes, Launch&& launch)
 {
     const size_t pitch = (rowBytes + 15) & ~size_t(15);
-    ScopedDevice sd(ctx->device);
-    dxtex_hresult hr = ctx->stageIn.grow(ctx, need); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, pitch * dst->height); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, hostIn, need, hipMemcpyHostToDevice, ctx->stream));
-    dxtex_image staged = with_pixels(*dst, ctx->stageOut.u8());
-    staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
-    hr = run_timed(ctx, [&] { return launched(ctx, launch(ctx->stageIn.u8(), view_of(staged))); });
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy_rows(ctx, dst->pixels, dst->rowPitch, staged.pixels, pitch, rowBytes, dst->height, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    StagingPlan plan;
+    plan.upload(hostIn, plan.in(need), need);
+    plan.download(dst->pixels, dst->rowPitch, plan.out(pitch, dst->height), 0, pitch, rowBytes, dst->height);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
+    {
+        dxtex_image staged = with_pixels(*dst, out);
+        staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
+        return launched(ctx, launch(in, view_of(staged)));
+    });
 }
 
-// run_staged for a source and a destination image: submit(src, dst) receives the two images with their pixels in the staging
+// The host-pointer twin of a single-image entry point, after its check_*: srcBytes of src and dstBytes of dst travel, and submit(src, dst)
+// - what the _device twin runs on the caller's images - runs on the staged ones
 template<class Submit>
 dxtex_hresult run_staged_images(dxtex_ctx* ctx, const dxtex_image* src, size_t srcBytes, const dxtex_image* dst, size_t dstBytes, Submit&& submit)
 {
@@ -397,8 +417,7 @@ dxtex_hresult run_staged_images(dxtex_ctx* ctx, const dxtex_image* src, size_t s
                       [&](uint8_t* in, uint8_t* out) { return submit(with_pixels(*src, in), with_pixels(*dst, out)); });
 }
 
-// The host-pointer twin of a single-image entry point, after its check_*: the pitch checks (so the staging holds every byte the kernels
-// touch), then submit(src, dst) - what the _device twin runs on the caller's images - on the staged ones.
+// run_staged_images with the bytes the pitch checks give (so the staging holds every byte the kernels touch)
 template<class Submit>
 dxtex_hresult run_host_twin(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, Submit&& submit)
 {
@@ -406,6 +425,32 @@ dxtex_hresult run_host_twin(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_
     const dxtex_hresult hr = check_host_pitches(ctx, src, dst, &srcBytes, &dstBytes);
     if (hr != DXTEX_S_OK) return hr;
     return run_staged_images(ctx, src, srcBytes, dst, dstBytes, submit);
+}
+
+// the bytes of a host image that the kernels touch (check_host_pitches for one image)
+dxtex_hresult host_image_bytes(dxtex_ctx* ctx, const dxtex_image& im, size_t* bytes)
+{
+    size_t other = 0;
+    return check_host_pitches(ctx, &im, &im, bytes, &other);
+}
+
+// Difference and merge on host pointers: a and b go up whole, into a part of the input staging each; submit(a, b, dst) runs on the staged
+// images, dst with the caller's pitch; only dst's texel rows come down, so the caller's row padding stays as it was, as with the device form
+template<class Submit>
+dxtex_hresult run_staged_pair(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, Submit&& submit)
+{
+    size_t dstBytes = 0, aBytes = 0, bBytes = 0, rowBytes = 0, sliceBytes = 0;
+    dxtex_hresult hr = host_image_bytes(ctx, *dst, &dstBytes);
+    if (hr == DXTEX_S_OK) hr = host_image_bytes(ctx, *a, &aBytes);
+    if (hr == DXTEX_S_OK) hr = host_image_bytes(ctx, *b, &bBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    (void)dxtex_compute_pitch(dst->format, dst->width, dst->height, &rowBytes, &sliceBytes);      // (host_image_bytes has asked the same)
+    StagingPlan plan;
+    const StagePart pa = plan.in(aBytes), pb = plan.in(bBytes), pd = plan.out(dstBytes);
+    plan.upload(a->pixels, pa, aBytes);
+    plan.upload(b->pixels, pb, bBytes);
+    plan.download(dst->pixels, dst->rowPitch, pd, 0, dst->rowPitch, rowBytes, rowBytes ? sliceBytes / rowBytes : 0);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out) { return submit(with_pixels(*a, in + pa.at), with_pixels(*b, in + pb.at), with_pixels(*dst, out)); });
 }
 
 // A destination whose element holds several texels (FC_GROUP) is written in two steps: the operation leaves R32G32B32A32_FLOAT rows in
@@ -424,14 +469,6 @@ dxtex_hresult launch_into(dxtex_ctx* ctx, const ImgView& dst, KernelMarks* marks
     hipError_t e = launch(rows);
     if (e == hipSuccess) e = launch_pack_group(rows, dst, ctx->stream, marks);
     return launched(ctx, e);
-}
-
-// copies of n images whose pixels lie at the arena's offsets from `base` (a host variant's levels in the staging)
-std::vector<dxtex_image> in_arena(const dxtex_image* im, size_t n, uint8_t* base, const Arena& a)
-{
-    std::vector<dxtex_image> o(n);
-    for (size_t i = 0; i < n; ++i) o[i] = with_pixels(im[i], base + a.at[i]);
-    return o;
 }
 } // namespace
 
@@ -1052,20 +1089,18 @@ dxtex_hresult dxtex_generate_mips(dxtex_ctx* ctx, const dxtex_image* levels, siz
     uint32_t mode = 0;
     dxtex_hresult hr = check_mips(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    // one device allocation holding the whole chain
-    std::vector<size_t> bytes(nlevels);
-    for (size_t i = 0; i < nlevels; ++i) bytes[i] = levels[i].rowPitch * levels[i].height;
-    const Arena a(bytes.data(), nlevels);
-    hr = ctx->stageIn.grow(ctx, a.total); if (hr != DXTEX_S_OK) return hr;
-    const std::vector<dxtex_image> d = in_arena(levels, nlevels, ctx->stageIn.u8(), a);
-    HIP_TRY(ctx, counted_copy(ctx, d[0].pixels, levels[0].pixels, bytes[0], hipMemcpyHostToDevice, ctx->stream));
-    hr = run_timed(ctx, [&] { return submit_mips(ctx, views_of(d.data(), nlevels), mode, filter); });
-    if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 1; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, d[i].pixels, bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    // the whole chain in the input staging: level 0 goes up, the levels the kernels fill come down
+    StagingPlan plan;
+    std::vector<StagePart> part(nlevels);
+    for (size_t i = 0; i < nlevels; ++i) part[i] = plan.in(levels[i].rowPitch, levels[i].height);
+    plan.upload(levels[0].pixels, part[0], part[0].bytes);
+    for (size_t i = 1; i < nlevels; ++i) plan.download(levels[i].pixels, part[i], part[i].bytes);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t*)
+    {
+        std::vector<ImgView> lv = views_of(levels, nlevels);
+        for (size_t i = 0; i < nlevels; ++i) lv[i].pixels = in + part[i].at;
+        return submit_mips(ctx, lv, mode, filter);
+    });
 }
 
 namespace
@@ -1164,20 +1199,17 @@ dxtex_hresult dxtex_generate_mips3d(dxtex_ctx* ctx, const dxtex_volume* levels, 
     uint32_t mode = 0;
     dxtex_hresult hr = check_mips3d(ctx, levels, nlevels, filter, &mode);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    std::vector<size_t> bytes(nlevels);
-    for (size_t i = 0; i < nlevels; ++i) bytes[i] = levels[i].slicePitch * levels[i].depth;
-    const Arena a(bytes.data(), nlevels);
-    hr = ctx->stageIn.grow(ctx, a.total); if (hr != DXTEX_S_OK) return hr;
-    std::vector<VolumeView> lv(nlevels);
-    for (size_t i = 0; i < nlevels; ++i) lv[i] = view_of(levels[i], ctx->stageIn.u8() + a.at[i]);
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, levels[0].pixels, bytes[0], hipMemcpyHostToDevice, ctx->stream));
-    hr = run_timed(ctx, [&] { return submit_mips3d(ctx, lv, mode, filter); });
-    if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 1; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, levels[i].pixels, lv[i].pixels, bytes[i], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    StagingPlan plan;       // as dxtex_generate_mips
+    std::vector<StagePart> part(nlevels);
+    for (size_t i = 0; i < nlevels; ++i) part[i] = plan.in(levels[i].slicePitch, levels[i].depth);
+    plan.upload(levels[0].pixels, part[0], part[0].bytes);
+    for (size_t i = 1; i < nlevels; ++i) plan.download(levels[i].pixels, part[i], part[i].bytes);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t*)
+    {
+        std::vector<VolumeView> lv(nlevels);
+        for (size_t i = 0; i < nlevels; ++i) lv[i] = view_of(levels[i], in + part[i].at);
+        return submit_mips3d(ctx, lv, mode, filter);
+    });
 }
 
 namespace
@@ -1637,12 +1669,16 @@ dxtex_hresult tga_unpack(dxtex_ctx* ctx, const void* texels, size_t texelBytes, 
     if (hr != DXTEX_S_OK) return hr;
     if (device) return run_timed(ctx, [&] { return submit_tga_unpack(ctx, static_cast<const uint8_t*>(texels), kind, flags, palette, *dst, opaque); });
     *opaque = kind == TGA_RGB_RGBA ? 1u : 0u;
-    const bool rule = tga_has_alpha_rule(kind);
-    if (rule) { ScopedDevice sd(ctx->device); hr = ctx->resultCell.grow(ctx, 4 * sizeof(double)); if (hr != DXTEX_S_OK) return hr; }
-    const uint32_t* answer = rule ? static_cast<const uint32_t*>(ctx->resultCell.p) + 2 : nullptr;
-    return run_staged(ctx, texels, texelBytes, dst->pixels, dst->rowPitch * dst->height,
-                      [&](uint8_t* in, uint8_t* out) { return submit_tga_unpack(ctx, in, kind, flags, palette, with_pixels(*dst, out), nullptr); },
-                      opaque, answer, rule ? sizeof(uint32_t) : 0);
+    // a kind with an alpha rule leaves its answer in a second part of the output staging, and it comes down behind the pixels
+    StagingPlan plan;
+    plan.upload(texels, plan.in(texelBytes), texelBytes);
+    const StagePart pixels = plan.out(dst->rowPitch, dst->height), answer = plan.out(tga_has_alpha_rule(kind) ? sizeof(uint32_t) : 0);
+    plan.download(dst->pixels, pixels, pixels.bytes);
+    plan.download(opaque, answer, answer.bytes);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
+    {
+        return submit_tga_unpack(ctx, in, kind, flags, palette, with_pixels(*dst, out), answer.bytes ? reinterpret_cast<uint32_t*>(out + answer.at) : nullptr);
+    });
 }
 
 dxtex_hresult tga_pack(dxtex_ctx* ctx, const dxtex_image* src, uint32_t bytesPerTexel, void* texels, size_t texelBytes, bool device)
@@ -1733,77 +1769,75 @@ dxtex_hresult check_dds(dxtex_ctx* ctx, const void* file, size_t fileBytes, bool
     return DXTEX_S_OK;
 }
 
-// bytes of an image's rows in memory, first to last
-size_t dds_span(const DdsImage& j, size_t rowBytes, bool fileSide) { return j.rows ? (j.rows - 1) * size_t(fileSide ? j.filePitch : j.pitch) + rowBytes : 0; }
+// The DDS pairs, one body each: `device` runs the kernel on the caller's device pointers, else the host pointers go through the staging -
+// the file side flat, each image's rows as a part of their own at the caller's pitch, and only the rows' texels travel on the image side
+dxtex_hresult dds_unpack(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette, const dxtex_image* dsts,
+                         const size_t* srcOffsets, const size_t* srcRowPitches, size_t count, bool device)
+{
+    std::vector<DdsImage> jobs;
+    const dxtex_hresult hr = check_dds(ctx, payload, payloadBytes, true, op, palette, dsts, srcOffsets, srcRowPitches, count, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    auto unpack = [&](const uint8_t* file)
+    { return launched(ctx, launch_dds_unpack(file, payloadBytes, int(op), dsts[0].format, opaque != 0, palette, jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); };
+    if (device) return run_timed(ctx, [&] { return unpack(static_cast<const uint8_t*>(payload)); });
+    const size_t imageTexel = op == ROW_COPY ? 1u : dds_image_bytes(dds_target(int(op), dsts[0].format));
+    StagingPlan plan;
+    plan.upload(payload, plan.in(payloadBytes), payloadBytes);
+    std::vector<StagePart> part(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const size_t rowBytes = jobs[i].width * imageTexel;
+        part[i] = plan.out(jobs[i].rows ? (jobs[i].rows - 1) * size_t(jobs[i].pitch) + rowBytes : 0);      // (check_dds has bounded the span)
+        plan.download(dsts[i].pixels, dsts[i].rowPitch, part[i], 0, jobs[i].pitch, rowBytes, jobs[i].rows);
+    }
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
+    {
+        for (size_t i = 0; i < count; ++i) jobs[i].pixels = out + part[i].at;
+        return unpack(in);
+    });
+}
+
+dxtex_hresult dds_pack24(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes, bool device)
+{
+    std::vector<DdsImage> jobs;
+    const dxtex_hresult hr = check_dds(ctx, out, outBytes, false, 0, nullptr, srcs, dstOffsets, dstRowPitches, count, &jobs);
+    if (hr != DXTEX_S_OK) return hr;
+    auto pack = [&](uint8_t* file) { return launched(ctx, launch_dds_pack24(jobs.data(), jobs.size(), file, outBytes, ctx->stream, marks_of(ctx))); };
+    if (device) return run_timed(ctx, [&] { return pack(static_cast<uint8_t*>(out)); });
+    StagingPlan plan;
+    const StagePart file = plan.out(outBytes);
+    std::vector<StagePart> part(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const size_t width = jobs[i].width;
+        part[i] = plan.in(jobs[i].rows ? (jobs[i].rows - 1) * size_t(jobs[i].pitch) + width * 4u : 0);
+        plan.upload(srcs[i].pixels, srcs[i].rowPitch, part[i], 0, jobs[i].pitch, width * 4u, jobs[i].rows);
+        plan.download(static_cast<uint8_t*>(out) + jobs[i].fileOffset, jobs[i].filePitch, file, jobs[i].fileOffset, jobs[i].filePitch, width * 3u, jobs[i].rows);
+    }
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* staged)
+    {
+        for (size_t i = 0; i < count; ++i) jobs[i].pixels = in + part[i].at;
+        return pack(staged);
+    });
+}
 } // namespace
 
 dxtex_hresult dxtex_dds_unpack_device(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
                                       const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count)
 {
-    std::vector<DdsImage> jobs;
-    const dxtex_hresult hr = check_dds(ctx, payload, payloadBytes, true, op, palette, dsts, srcOffsets, srcRowPitches, count, &jobs);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_dds_unpack(static_cast<const uint8_t*>(payload), payloadBytes, int(op), dsts[0].format, opaque != 0, palette,
-                                                                       jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
+    return dds_unpack(ctx, payload, payloadBytes, op, opaque, palette, dsts, srcOffsets, srcRowPitches, count, true);
 }
 
 dxtex_hresult dxtex_dds_unpack(dxtex_ctx* ctx, const void* payload, size_t payloadBytes, uint32_t op, uint32_t opaque, const uint32_t* palette,
                                const dxtex_image* dsts, const size_t* srcOffsets, const size_t* srcRowPitches, size_t count)
 {
-    std::vector<DdsImage> jobs;
-    dxtex_hresult hr = check_dds(ctx, payload, payloadBytes, true, op, palette, dsts, srcOffsets, srcRowPitches, count, &jobs);
-    if (hr != DXTEX_S_OK) return hr;
-    // the payload goes up as it is; each image gets its rows' span of the output staging and comes down through its own pitch
-    const size_t imageTexel = dds_image_bytes(dds_target(int(op), dsts[0].format));
-    std::vector<size_t> spans(count), rowBytes(count);
-    for (size_t i = 0; i < count; ++i) { rowBytes[i] = op == ROW_COPY ? jobs[i].width : jobs[i].width * imageTexel; spans[i] = dds_span(jobs[i], rowBytes[i], false); }
-    const Arena arena(spans.data(), count);
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, payloadBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, arena.total); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, payload, payloadBytes, hipMemcpyHostToDevice, ctx->stream));
-    for (size_t i = 0; i < count; ++i) jobs[i].pixels = ctx->stageOut.u8() + arena.at[i];
-    hr = run_timed(ctx, [&] { return launched(ctx, launch_dds_unpack(ctx->stageIn.u8(), payloadBytes, int(op), dsts[0].format, opaque != 0, palette, jobs.data(), jobs.size(),
-                                                                     ctx->stream, marks_of(ctx))); });
-    if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 0; i < count; ++i)
-        HIP_TRY(ctx, counted_copy_rows(ctx, dsts[i].pixels, dsts[i].rowPitch, jobs[i].pixels, jobs[i].pitch, rowBytes[i], jobs[i].rows, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return dds_unpack(ctx, payload, payloadBytes, op, opaque, palette, dsts, srcOffsets, srcRowPitches, count, false);
 }
 
 dxtex_hresult dxtex_dds_pack24_device(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes)
-{
-    std::vector<DdsImage> jobs;
-    const dxtex_hresult hr = check_dds(ctx, out, outBytes, false, 0, nullptr, srcs, dstOffsets, dstRowPitches, count, &jobs);
-    if (hr != DXTEX_S_OK) return hr;
-    return run_timed(ctx, [&] { return launched(ctx, launch_dds_pack24(jobs.data(), jobs.size(), static_cast<uint8_t*>(out), outBytes, ctx->stream, marks_of(ctx))); });
-}
-
+{ return dds_pack24(ctx, srcs, dstOffsets, dstRowPitches, count, out, outBytes, true); }
 dxtex_hresult dxtex_dds_pack24(dxtex_ctx* ctx, const dxtex_image* srcs, const size_t* dstOffsets, const size_t* dstRowPitches, size_t count, void* out, size_t outBytes)
-{
-    std::vector<DdsImage> jobs;
-    dxtex_hresult hr = check_dds(ctx, out, outBytes, false, 0, nullptr, srcs, dstOffsets, dstRowPitches, count, &jobs);
-    if (hr != DXTEX_S_OK) return hr;
-    std::vector<size_t> spans(count);
-    for (size_t i = 0; i < count; ++i) spans[i] = dds_span(jobs[i], size_t(jobs[i].width) * 4u, false);
-    const Arena arena(spans.data(), count);
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, arena.total); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, outBytes); if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 0; i < count; ++i)
-    {
-        HIP_TRY(ctx, counted_copy_rows(ctx, ctx->stageIn.u8() + arena.at[i], jobs[i].pitch, srcs[i].pixels, srcs[i].rowPitch, size_t(jobs[i].width) * 4u, jobs[i].rows, hipMemcpyHostToDevice));
-        jobs[i].pixels = ctx->stageIn.u8() + arena.at[i];
-    }
-    hr = run_timed(ctx, [&] { return launched(ctx, launch_dds_pack24(jobs.data(), jobs.size(), ctx->stageOut.u8(), outBytes, ctx->stream, marks_of(ctx))); });
-    if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 0; i < count; ++i)
-        HIP_TRY(ctx, counted_copy_rows(ctx, static_cast<uint8_t*>(out) + jobs[i].fileOffset, jobs[i].filePitch, ctx->stageOut.u8() + jobs[i].fileOffset, jobs[i].filePitch,
-                                       size_t(jobs[i].width) * 3u, jobs[i].rows, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
-}
+{ return dds_pack24(ctx, srcs, dstOffsets, dstRowPitches, count, out, outBytes, false); }
 
 namespace
 {
@@ -2080,22 +2114,20 @@ dxtex_hresult dxtex_exr_unpack(dxtex_ctx* ctx, const void* stream, size_t stream
     // the stream goes up as it is; the items' rows are written tight (rounded up to 16 bytes) into the output staging, one item behind
     // another, and only each row's texels come down, through the caller's pitches
     const size_t rowBytes = size_t(layout.width) * 8, pitch = (rowBytes + 15) & ~size_t(15), itemBytes = pitch * layout.itemRows;
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, streamBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, itemBytes * itemCount); if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, ctx->stageIn.p, stream, streamBytes, hipMemcpyHostToDevice, ctx->stream));
-    dxtex_image staged[kExrItemsMax];
-    for (size_t i = 0; i < itemCount; ++i)
+    StagingPlan plan;
+    plan.upload(stream, plan.in(streamBytes), streamBytes);
+    const StagePart rows = plan.out(itemBytes, itemCount);
+    for (size_t i = 0; i < itemCount; ++i) plan.download(items[i].pixels, items[i].rowPitch, rows, i * itemBytes, pitch, rowBytes, layout.itemRows);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
     {
-        staged[i] = with_pixels(items[i], ctx->stageOut.u8() + i * itemBytes);
-        staged[i].rowPitch = pitch; staged[i].slicePitch = itemBytes;
-    }
-    hr = run_timed(ctx, [&] { return submit_exr_unpack(ctx, ctx->stageIn.u8(), list, layout, staged, itemCount); });
-    if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 0; i < itemCount; ++i)
-        HIP_TRY(ctx, counted_copy_rows(ctx, items[i].pixels, items[i].rowPitch, staged[i].pixels, pitch, rowBytes, layout.itemRows, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+        dxtex_image staged[kExrItemsMax];
+        for (size_t i = 0; i < itemCount; ++i)
+        {
+            staged[i] = with_pixels(items[i], out + i * itemBytes);
+            staged[i].rowPitch = pitch; staged[i].slicePitch = itemBytes;
+        }
+        return submit_exr_unpack(ctx, in, list, layout, staged, itemCount);
+    });
 }
 
 dxtex_hresult dxtex_exr_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes) { return exr_pack(ctx, src, scanlines, scanlineBytes, true); }
@@ -2157,6 +2189,13 @@ dxtex_hresult check_jpeg(dxtex_ctx* ctx, const void* coefficients, size_t coeffi
     return check_stream_image(ctx, "coefficients", coefficients, *need, image, *rowBytes);
 }
 
+// the planes of frame f between a JPEG pair's two kernels, in memory of the context
+dxtex_hresult grow_jpeg_planes(dxtex_ctx* ctx, const JpegFrame& f)
+{
+    ScopedDevice sd(ctx->device);
+    return ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
+}
+
 // The JPEG pairs, one body each: `device` runs the kernels on the caller's device pointers, else the host pointers go through the staging.
 // The planes between the two kernels live in memory of the context.
 dxtex_hresult jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coefficientBytes, const dxtex_jpeg_frame* frame, const dxtex_image* dst, bool device)
@@ -2164,19 +2203,11 @@ dxtex_hresult jpeg_decode(dxtex_ctx* ctx, const void* coefficients, size_t coeff
     JpegFrame f; size_t need, rowBytes;
     const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, dst, false, &f, &need, &rowBytes);
     if (hr != DXTEX_S_OK) return hr;
+    const dxtex_hresult grown = grow_jpeg_planes(ctx, f);
+    if (grown != DXTEX_S_OK) return grown;
     auto decode = [&](const uint8_t* stream, const ImgView& view)
     { return launch_jpeg_decode(reinterpret_cast<const int16_t*>(stream), f, view, ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx)); };
-    if (device)
-        return run_timed(ctx, [&]
-        {
-            const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-            return grown != DXTEX_S_OK ? grown : launched(ctx, decode(static_cast<const uint8_t*>(coefficients), view_of(*dst)));
-        });
-    {
-        ScopedDevice sd(ctx->device);
-        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-        if (grown != DXTEX_S_OK) return grown;
-    }
+    if (device) return run_timed(ctx, [&] { return launched(ctx, decode(static_cast<const uint8_t*>(coefficients), view_of(*dst))); });
     return run_staged_rows(ctx, coefficients, need, dst, rowBytes, decode);
 }
 
@@ -2185,19 +2216,11 @@ dxtex_hresult jpeg_encode(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_jp
     JpegFrame f; size_t need, rowBytes; bool bgr;
     const dxtex_hresult hr = check_jpeg(ctx, coefficients, coefficientBytes, frame, src, true, &f, &need, &rowBytes, &bgr);
     if (hr != DXTEX_S_OK) return hr;
+    const dxtex_hresult grown = grow_jpeg_planes(ctx, f);
+    if (grown != DXTEX_S_OK) return grown;
     auto encode = [&](const dxtex_image& s, void* out)
     { return launched(ctx, launch_jpeg_encode(view_of(s), bgr, f, static_cast<int16_t*>(out), ctx->jpegPlanes.u8(), ctx->stream, marks_of(ctx))); };
-    if (device)
-        return run_timed(ctx, [&]
-        {
-            const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-            return grown != DXTEX_S_OK ? grown : encode(*src, coefficients);
-        });
-    {
-        ScopedDevice sd(ctx->device);
-        const dxtex_hresult grown = ctx->jpegPlanes.grow(ctx, jpeg_plane_bytes(f));
-        if (grown != DXTEX_S_OK) return grown;
-    }
+    if (device) return run_timed(ctx, [&] { return encode(*src, coefficients); });
     return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, coefficients, need, [&](uint8_t* in, uint8_t* out) { return encode(with_pixels(*src, in), out); });
 }
 } // namespace
@@ -2329,22 +2352,22 @@ dxtex_hresult dxtex_scale_mips_alpha_for_coverage(dxtex_ctx* ctx, const dxtex_im
 {
     dxtex_hresult hr = check_coverage_chain(ctx, src, dst, nlevels);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    std::vector<size_t> srcBytes(nlevels), dstBytes(nlevels);
-    for (size_t i = 0; i < nlevels; ++i) { srcBytes[i] = src[i].rowPitch * src[i].height; dstBytes[i] = dst[i].rowPitch * dst[i].height; }
-    const Arena as(srcBytes.data(), nlevels), ad(dstBytes.data(), nlevels);
-    hr = ctx->stageIn.grow(ctx, as.total); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, ad.total); if (hr != DXTEX_S_OK) return hr;
-    const std::vector<dxtex_image> s = in_arena(src, nlevels, ctx->stageIn.u8(), as), d = in_arena(dst, nlevels, ctx->stageOut.u8(), ad);
+    StagingPlan plan;
+    std::vector<StagePart> ps(nlevels), pd(nlevels);
     for (size_t i = 0; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, s[i].pixels, src[i].pixels, srcBytes[i], hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->stageOut.p, 0, ad.total, ctx->stream));
-    hr = submit_coverage_chain(ctx, s.data(), d.data(), nlevels, alphaReference);
-    if (hr != DXTEX_S_OK) return hr;
-    for (size_t i = 0; i < nlevels; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, dst[i].pixels, d[i].pixels, dstBytes[i], hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    {
+        ps[i] = plan.in(src[i].rowPitch, src[i].height); pd[i] = plan.out(dst[i].rowPitch, dst[i].height);
+        plan.upload(src[i].pixels, ps[i], ps[i].bytes);
+        plan.download(dst[i].pixels, pd[i], pd[i].bytes);
+    }
+    // (the chain reads its counts back as it goes: untimed, as the device form is)
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
+    {
+        std::vector<dxtex_image> s(nlevels), d(nlevels);
+        for (size_t i = 0; i < nlevels; ++i) { s[i] = with_pixels(src[i], in + ps[i].at); d[i] = with_pixels(dst[i], out + pd[i].at); }
+        HIP_TRY(ctx, hipMemsetAsync(out, 0, plan.need(STAGE_OUT), ctx->stream));
+        return submit_coverage_chain(ctx, s.data(), d.data(), nlevels, alphaReference);
+    }, false);
 }
 
 dxtex_hresult dxtex_compute_mse_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, double mse[4])
@@ -2377,26 +2400,6 @@ dxtex_hresult check_diag_image(dxtex_ctx* ctx, const dxtex_image& im)
     const FmtInfo* f = format_info(im.format);
     if (!f || (f->cls & FC_BC)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "the diagnostics take uncompressed images of a loadable format (decompress first)");
     if (im.width > 0xFFFFFFFFull || im.height > 0xFFFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
-    return DXTEX_S_OK;
-}
-
-// the bytes of a host image that the kernels touch (check_host_pitches for one image)
-dxtex_hresult host_image_bytes(dxtex_ctx* ctx, const dxtex_image& im, size_t* bytes)
-{
-    size_t other = 0;
-    return check_host_pitches(ctx, &im, &im, bytes, &other);
-}
-
-// `n` host images into consecutive 256-byte aligned parts of ctx->stageIn: their device twins
-dxtex_hresult stage_inputs(dxtex_ctx* ctx, const dxtex_image* images, size_t n, std::vector<dxtex_image>* staged)
-{
-    std::vector<size_t> bytes(n);
-    for (size_t i = 0; i < n; ++i) { const dxtex_hresult hr = host_image_bytes(ctx, images[i], &bytes[i]); if (hr != DXTEX_S_OK) return hr; }
-    const Arena arena(bytes.data(), n);
-    const dxtex_hresult hr = ctx->stageIn.grow(ctx, arena.total); if (hr != DXTEX_S_OK) return hr;
-    *staged = in_arena(images, n, ctx->stageIn.u8(), arena);
-    for (size_t i = 0; i < n; ++i)
-        HIP_TRY(ctx, counted_copy(ctx, (*staged)[i].pixels, images[i].pixels, bytes[i], hipMemcpyHostToDevice, ctx->stream));
     return DXTEX_S_OK;
 }
 
@@ -2524,11 +2527,22 @@ dxtex_hresult dxtex_analyze(dxtex_ctx* ctx, const dxtex_image* images, size_t co
 {
     dxtex_hresult hr = check_analyze(ctx, images, count, stats_out);
     if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    std::vector<dxtex_image> staged;
-    hr = stage_inputs(ctx, images, count, &staged);
-    if (hr != DXTEX_S_OK) return hr;
-    return submit_analyze(ctx, staged.data(), count, stats_out);
+    // every image a part of the input staging; nothing comes down through it (submit_analyze times itself and brings its figures back)
+    StagingPlan plan;
+    std::vector<StagePart> part(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        size_t bytes = 0;
+        hr = host_image_bytes(ctx, images[i], &bytes); if (hr != DXTEX_S_OK) return hr;
+        part[i] = plan.in(bytes);
+        plan.upload(images[i].pixels, part[i], bytes);
+    }
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t*)
+    {
+        std::vector<dxtex_image> staged(count);
+        for (size_t i = 0; i < count; ++i) staged[i] = with_pixels(images[i], in + part[i].at);
+        return submit_analyze(ctx, staged.data(), count, stats_out);
+    }, false);
 }
 
 dxtex_hresult dxtex_analyze_bc_device(dxtex_ctx* ctx, const dxtex_image* image, uint64_t hist[15], uint64_t* blocks)
@@ -2571,28 +2585,7 @@ dxtex_hresult dxtex_difference(dxtex_ctx* ctx, const dxtex_image* a, const dxtex
 {
     dxtex_hresult hr = check_difference(ctx, a, b, dst);
     if (hr != DXTEX_S_OK) return hr;
-    size_t dstBytes = 0;
-    hr = host_image_bytes(ctx, *dst, &dstBytes);
-    if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    const dxtex_image in[2] = { *a, *b };
-    std::vector<dxtex_image> staged;
-    hr = stage_inputs(ctx, in, 2, &staged);
-    if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = run_timed(ctx, [&] { return submit_difference(ctx, staged[0], staged[1], with_pixels(*dst, ctx->stageOut.u8()), diffColor, threshold); });
-    if (hr != DXTEX_S_OK) return hr;
-    // only the texels come back: the caller's row padding stays as it was, as with the device form
-    size_t rowBytes = 0, sliceBytes = 0;
-    if (dxtex_compute_pitch(dst->format, dst->width, dst->height, &rowBytes, &sliceBytes) != DXTEX_S_OK) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
-    if (rowBytes && sliceBytes)
-    {
-        const size_t rows = sliceBytes / rowBytes;
-        ctx->d2hBytes += rowBytes * rows;
-        HIP_TRY(ctx, hipMemcpy2DAsync(dst->pixels, dst->rowPitch, ctx->stageOut.p, dst->rowPitch, rowBytes, rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged_pair(ctx, a, b, dst, [&](const dxtex_image& sa, const dxtex_image& sb, const dxtex_image& sd) { return submit_difference(ctx, sa, sb, sd, diffColor, threshold); });
 }
 
 // ---- CopyRectangle and texassemble's merge ----------------------------------------------------------------------------------------------
@@ -2744,45 +2737,25 @@ dxtex_hresult dxtex_copy_rectangle(dxtex_ctx* ctx, const dxtex_image* src, const
     if (!ctx) return DXTEX_E_POINTER;
     if (!src || !rect || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image or rectangle");
     std::vector<CopyJob> host, jobs;
-    dxtex_hresult hr = check_copy_rect(ctx, *src, *rect, *dst, filter, xOffset, yOffset, &host);
+    const dxtex_hresult hr = check_copy_rect(ctx, *src, *rect, *dst, filter, xOffset, yOffset, &host);
     if (hr != DXTEX_S_OK) return hr;
     // Only the rectangle travels: its rows go up into a tight image in the staging, the same rectangle of a tight destination comes back
     // into the caller's rows. (Nothing else of the caller's destination is read or written, so its other bytes stay as they were.)
-    const FmtInfo* in = format_info(src->format);
-    const FmtInfo* out = format_info(dst->format);
-    const size_t sbpp = copy_texel_bytes(*in), dbpp = copy_texel_bytes(*out);
+    const size_t sbpp = copy_texel_bytes(*format_info(src->format)), dbpp = copy_texel_bytes(*format_info(dst->format));
     const size_t upRow = rect->w * sbpp, downRow = rect->w * dbpp;
-    dxtex_image s = *src, d = *dst;
-    s.width = d.width = rect->w; s.height = d.height = rect->h;
-    s.rowPitch = upRow; d.rowPitch = downRow;
-    s.slicePitch = upRow * rect->h; d.slicePitch = downRow * rect->h;
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, s.slicePitch); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, d.slicePitch); if (hr != DXTEX_S_OK) return hr;
-    s.pixels = ctx->stageIn.u8(); d.pixels = ctx->stageOut.u8();
-    const dxtex_rect whole = { 0, 0, rect->w, rect->h };
-    hr = check_copy_rect(ctx, s, whole, d, filter, 0, 0, &jobs);
-    if (hr != DXTEX_S_OK) return hr;
-    // rows of `width` bytes between a host image and its tight copy in the staging. A row of the packed formats can be longer than the
-    // host image's pitch (see check_copy_rect): those rows travel one by one, in order, so that the later row wins as in the reference.
-    const auto rows_copy = [&](uint8_t* to, size_t toPitch, const uint8_t* from, size_t fromPitch, size_t width, hipMemcpyKind kind) -> hipError_t
+    StagingPlan plan;
+    plan.upload(src->pixels + rect->y * src->rowPitch + rect->x * sbpp, src->rowPitch, plan.in(upRow, rect->h), 0, upRow, upRow, rect->h);
+    plan.download(dst->pixels + yOffset * dst->rowPitch + xOffset * dbpp, dst->rowPitch, plan.out(downRow, rect->h), 0, downRow, downRow, rect->h);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
     {
-        if (width <= toPitch && width <= fromPitch) return hipMemcpy2DAsync(to, toPitch, from, fromPitch, width, rect->h, kind, ctx->stream);
-        for (size_t y = 0; y < rect->h; ++y)
-        {
-            const hipError_t e = hipMemcpyAsync(to + y * toPitch, from + y * fromPitch, width, kind, ctx->stream);
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
-    };
-    ctx->h2dBytes += upRow * rect->h;
-    HIP_TRY(ctx, rows_copy(s.pixels, upRow, src->pixels + rect->y * src->rowPitch + rect->x * sbpp, src->rowPitch, upRow, hipMemcpyHostToDevice));
-    hr = run_timed(ctx, [&] { return launched(ctx, launch_copy_rects(jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
-    if (hr != DXTEX_S_OK) return hr;
-    ctx->d2hBytes += downRow * rect->h;
-    HIP_TRY(ctx, rows_copy(dst->pixels + yOffset * dst->rowPitch + xOffset * dbpp, dst->rowPitch, d.pixels, downRow, downRow, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+        dxtex_image s = *src, d = *dst;
+        s.width = d.width = rect->w; s.height = d.height = rect->h;
+        s.rowPitch = upRow; d.rowPitch = downRow;
+        s.slicePitch = upRow * rect->h; d.slicePitch = downRow * rect->h;
+        s.pixels = in; d.pixels = out;
+        const dxtex_hresult staged = check_copy_rect(ctx, s, { 0, 0, rect->w, rect->h }, d, filter, 0, 0, &jobs);
+        return staged != DXTEX_S_OK ? staged : launched(ctx, launch_copy_rects(jobs.data(), jobs.size(), ctx->stream, marks_of(ctx)));
+    });
 }
 
 // ---- ConvertToSinglePlane ------------------------------------------------------------------------------------------------------------------
@@ -2827,41 +2800,30 @@ dxtex_hresult dxtex_convert_to_single_plane(dxtex_ctx* ctx, const dxtex_image* s
     if (!ctx) return DXTEX_E_POINTER;
     if (!src || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
     PlaneJob host, job;
-    dxtex_hresult hr = check_single_plane(ctx, *src, *dst, &host);
+    const dxtex_hresult hr = check_single_plane(ctx, *src, *dst, &host);
     if (hr != DXTEX_S_OK) return hr;
     if (!host.elems || !host.units) return DXTEX_S_OK;
     // The source goes up as it is, slicePitch bytes with the caller's pitches; the destination in the staging has rows of the element bytes
-    // rounded up to 16 (so the wide route can run), and only the elements the kernel wrote come back into the caller's rows.
-    const size_t rowBytes = size_t(host.elems) * plane_elem_bytes(host), rows = src->height;
-    dxtex_image s = *src, d = *dst;
-    d.rowPitch = (rowBytes + 15u) & ~size_t(15);
-    d.slicePitch = d.rowPitch * rows;
-    ScopedDevice sd(ctx->device);
-    hr = ctx->stageIn.grow(ctx, s.slicePitch); if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, d.slicePitch); if (hr != DXTEX_S_OK) return hr;
-    s.pixels = ctx->stageIn.u8(); d.pixels = ctx->stageOut.u8();
-    hr = check_single_plane(ctx, s, d, &job);
-    if (hr != DXTEX_S_OK) return hr;
-    HIP_TRY(ctx, counted_copy(ctx, s.pixels, src->pixels, s.slicePitch, hipMemcpyHostToDevice, ctx->stream));
-    hr = run_timed(ctx, [&] { return launched(ctx, launch_single_plane(&job, 1, ctx->stream, marks_of(ctx))); });
-    if (hr != DXTEX_S_OK) return hr;
-    // the end guard leaves whole rows first and then cut ones (plane_pairs does not grow with the unit): the whole rows in one copy
-    const size_t unitRows = job.nv11 ? 1 : 2;
+    // rounded up to 16 (so the wide route can run), and only the elements the kernel writes come back into the caller's rows: the end guard
+    // leaves whole rows first and then cut ones (plane_pairs does not grow with the unit), the whole rows in one copy.
+    const size_t rowBytes = size_t(host.elems) * plane_elem_bytes(host), rows = src->height, pitch = (rowBytes + 15u) & ~size_t(15);
+    const size_t unitRows = host.nv11 ? 1 : 2;
+    StagingPlan plan;
+    plan.upload(src->pixels, plan.in(src->slicePitch), src->slicePitch);
+    const StagePart staged = plan.out(pitch, rows);
     uint32_t whole = 0;
-    while (whole < job.units && plane_written_elems(job, whole) == job.elems) ++whole;
-    if (whole)
+    while (whole < host.units && plane_written_elems(host, whole) == host.elems) ++whole;
+    plan.download(dst->pixels, dst->rowPitch, staged, 0, pitch, rowBytes, whole * unitRows);
+    for (uint32_t unit = whole; unit < host.units; ++unit)
+        for (size_t y = unit * unitRows; y < (unit + 1) * unitRows; ++y)
+            plan.download(dst->pixels + y * dst->rowPitch, dst->rowPitch, staged, y * pitch, pitch, size_t(plane_written_elems(host, unit)) * plane_elem_bytes(host), 1);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
     {
-        ctx->d2hBytes += rowBytes * whole * unitRows;
-        HIP_TRY(ctx, hipMemcpy2DAsync(dst->pixels, dst->rowPitch, d.pixels, d.rowPitch, rowBytes, whole * unitRows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    for (uint32_t unit = whole; unit < job.units; ++unit)
-    {
-        const size_t bytes = size_t(plane_written_elems(job, unit)) * plane_elem_bytes(job);
-        for (size_t y = unit * unitRows; bytes && y < (unit + 1) * unitRows; ++y)
-            HIP_TRY(ctx, counted_copy(ctx, dst->pixels + y * dst->rowPitch, d.pixels + y * d.rowPitch, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+        dxtex_image s = with_pixels(*src, in), d = with_pixels(*dst, out);
+        d.rowPitch = pitch; d.slicePitch = pitch * rows;
+        const dxtex_hresult again = check_single_plane(ctx, s, d, &job);
+        return again != DXTEX_S_OK ? again : launched(ctx, launch_single_plane(&job, 1, ctx->stream, marks_of(ctx)));
+    });
 }
 
 dxtex_hresult dxtex_merge_image_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4],
@@ -2880,28 +2842,7 @@ dxtex_hresult dxtex_merge_image(dxtex_ctx* ctx, const dxtex_image* a, const dxte
     MergeArgs args;
     dxtex_hresult hr = check_merge(ctx, a, b, dst, permute, zero, one, &args);
     if (hr != DXTEX_S_OK) return hr;
-    size_t dstBytes = 0;
-    hr = host_image_bytes(ctx, *dst, &dstBytes);
-    if (hr != DXTEX_S_OK) return hr;
-    ScopedDevice sd(ctx->device);
-    const dxtex_image in[2] = { *a, *b };
-    std::vector<dxtex_image> staged;
-    hr = stage_inputs(ctx, in, 2, &staged);
-    if (hr != DXTEX_S_OK) return hr;
-    hr = ctx->stageOut.grow(ctx, dstBytes); if (hr != DXTEX_S_OK) return hr;
-    hr = run_timed(ctx, [&] { return submit_merge(ctx, staged[0], staged[1], with_pixels(*dst, ctx->stageOut.u8()), args); });
-    if (hr != DXTEX_S_OK) return hr;
-    // only the texels come back, as with dxtex_difference: the caller's row padding stays as it was
-    size_t rowBytes = 0, sliceBytes = 0;
-    if (dxtex_compute_pitch(dst->format, dst->width, dst->height, &rowBytes, &sliceBytes) != DXTEX_S_OK) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
-    if (rowBytes && sliceBytes)
-    {
-        const size_t rows = sliceBytes / rowBytes;
-        ctx->d2hBytes += rowBytes * rows;
-        HIP_TRY(ctx, hipMemcpy2DAsync(dst->pixels, dst->rowPitch, ctx->stageOut.p, dst->rowPitch, rowBytes, rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return DXTEX_S_OK;
+    return run_staged_pair(ctx, a, b, dst, [&](const dxtex_image& sa, const dxtex_image& sb, const dxtex_image& sd) { return submit_merge(ctx, sa, sb, sd, args); });
 }
 
 dxtex_hresult dxtex_device_alloc(dxtex_ctx* ctx, size_t bytes, void** out)

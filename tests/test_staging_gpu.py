@@ -219,3 +219,127 @@ def test_coverage_staging(ctx, img):
     dst = [host_image(b, w, h, RGBA8) for b, (w, h) in zip(outs, dims)]
     dst[2].width += 1                                 # a destination level of another size
     assert refused(ctx, "dxtex_scale_mips_alpha_for_coverage", (dx.Image * n)(*src), (dx.Image * n)(*dst), n, ctypes.c_float(0.5)) == (E_FAIL, (0, 0))
+
+
+# ---- the entry points that move several images, or less than whole images: the same runner, one plan each ------------------------------------
+PAD = 12
+
+
+def texels(buf, w, h, row_pitch, slices=1, slice_pitch=None):
+    """The texel columns of `slices` RGBA8 slices of h rows in a padded buffer."""
+    sp = slice_pitch or row_pitch * h
+    return np.stack([buf[z * sp:z * sp + row_pitch * h].reshape(h, row_pitch)[:, :w * 4] for z in range(slices)])
+
+
+def padded_level0(img, row_pitch, slices=1, slice_pitch=None):
+    sp = slice_pitch or row_pitch * H
+    buf = np.zeros(sp * slices, np.uint8)
+    for z in range(slices):
+        buf[z * sp:z * sp + row_pitch * H].reshape(H, row_pitch)[:, :W * 4] = img.reshape(H, W * 4)
+    return buf
+
+
+def test_generate_mips_padded_pitches(ctx, img):
+    n = 3
+    dims = chain(W, H, n)
+    rps = [w * 4 + PAD for w, _ in dims]
+    sizes = [rp * h for rp, (_, h) in zip(rps, dims)]
+    host = [padded_level0(img, rps[0])] + [np.zeros(s, np.uint8) for s in sizes[1:]]
+    levels = (dx.Image * n)(*[dx.Image(w, h, RGBA8, rp, s, b.ctypes.data) for b, (w, h), rp, s in zip(host, dims, rps, sizes)])
+    assert moved(ctx, lambda: ctx._check(ctx._lib.dxtex_generate_mips(ctx._h, levels, n, LINEAR), "generate_mips")) == (sizes[0], sum(sizes[1:]))
+    with Device(ctx) as d:
+        ptrs = [d.put(host[0])] + [d.empty(s) for s in sizes[1:]]
+        ctx.generate_mips_device([dx.device_image(p, w, h, RGBA8, row_pitch=rp) for p, (w, h), rp in zip(ptrs, dims, rps)], LINEAR)
+        for p, s, got, (w, h), rp in list(zip(ptrs, sizes, host, dims, rps))[1:]:
+            assert np.array_equal(texels(d.get(p, s), w, h, rp), texels(got, w, h, rp)), (w, h)
+
+
+def test_generate_mips3d_padded_pitches(ctx, img):
+    n, depth = 3, 3
+    dims = [(w, h, max(1, depth >> i)) for i, (w, h) in enumerate(chain(W, H, n))]
+    rps = [w * 4 + PAD for w, _, _ in dims]
+    sps = [rp * h + 24 for rp, (_, h, _) in zip(rps, dims)]
+    sizes = [sp * dd for sp, (_, _, dd) in zip(sps, dims)]
+    host = [padded_level0(img, rps[0], depth, sps[0])] + [np.zeros(s, np.uint8) for s in sizes[1:]]
+    Volume = dx.capi.Volume
+    vols = (Volume * n)(*[Volume(w, h, dd, RGBA8, rp, sp, b.ctypes.data) for b, (w, h, dd), rp, sp in zip(host, dims, rps, sps)])
+    assert moved(ctx, lambda: ctx._check(ctx._lib.dxtex_generate_mips3d(ctx._h, vols, n, LINEAR), "generate_mips3d")) == (sizes[0], sum(sizes[1:]))
+    with Device(ctx) as d:
+        ptrs = [d.put(host[0])] + [d.empty(s) for s in sizes[1:]]
+        dvols = (Volume * n)(*[Volume(w, h, dd, RGBA8, rp, sp, p) for p, (w, h, dd), rp, sp in zip(ptrs, dims, rps, sps)])
+        ctx._check(ctx._lib.dxtex_generate_mips3d_device(ctx._h, dvols, n, LINEAR), "generate_mips3d_device")
+        for p, s, got, (w, h, dd), rp, sp in list(zip(ptrs, sizes, host, dims, rps, sps))[1:]:
+            assert np.array_equal(texels(d.get(p, s), w, h, rp, dd, sp), texels(got, w, h, rp, dd, sp)), (w, h, dd)
+
+
+def merge_inputs(img):
+    b = np.random.default_rng(11).random((H, W, 4), dtype=np.float32)
+    return np.ascontiguousarray(img), b, (ctypes.c_uint32 * 4)(0, 5, 2, 7), (ctypes.c_uint32 * 4)(0, 0, 1, 0), (ctypes.c_uint32 * 4)(0, 0, 0, 0)
+
+
+def test_merge_keeps_row_padding(ctx, img):
+    a, b, permute, zero, one = merge_inputs(img)
+    rp = W * 4 + 8
+    out = np.full(rp * H, 0xA5, np.uint8)
+    ia, ib, idst = host_image(a, W, H, RGBA8), host_image(b, W, H, dx.DXGI_FORMAT_R32G32B32A32_FLOAT), dx.Image(W, H, RGBA8, rp, rp * H, out.ctypes.data)
+    up, down = moved(ctx, lambda: ctx._check(ctx._lib.dxtex_merge_image(ctx._h, ctypes.byref(ia), ctypes.byref(ib), ctypes.byref(idst), permute, zero, one), "merge_image"))
+    assert (up, down) == (W * 4 * H + W * 16 * H, W * 4 * H)
+    got = out.reshape(H, rp)
+    assert (got[:, W * 4:] == 0xA5).all()
+    with Device(ctx) as d:
+        pa, pb, pd = d.put(a), d.put(b), d.empty(rp * H)
+        ctx.merge_image_device(dx.device_image(pa, W, H, RGBA8), dx.device_image(pb, W, H, dx.DXGI_FORMAT_R32G32B32A32_FLOAT),
+                               dx.device_image(pd, W, H, RGBA8, row_pitch=rp), (0, 5, 2, 7), (0, 0, 1, 0))
+        assert np.array_equal(d.get(pd, rp * H).reshape(H, rp)[:, :W * 4], got[:, :W * 4])
+
+
+def last_error(ctx):
+    return ctx._lib.dxtex_ctx_last_error(ctx._h).decode()
+
+
+def test_refusals_of_the_planned_calls_move_nothing(ctx, img):
+    capi = dx.capi
+    sizes = (ctypes.c_size_t * 1)
+    # dxtex_dds_unpack: a 4 x 4 image of 3-byte texels needs 48 bytes of payload (check_dds)
+    payload, px = np.zeros(64, np.uint8), np.zeros(64, np.uint8)
+    dst = (dx.Image * 1)(dx.Image(4, 4, RGBA8, 16, 64, px.ctypes.data))
+    assert refused(ctx, "dxtex_dds_unpack", payload.ctypes.data, 47, dx.DDS_ROW_888, 0, None, dst, sizes(0), sizes(12), 1) == (E_INVALIDARG, (0, 0))
+    assert last_error(ctx) == "an image's rows reach past the payload"
+    # dxtex_exr_unpack: no chunks (check_exr_unpack)
+    stream, half = np.zeros(128, np.uint8), np.zeros(4 * 4 * 8, np.uint8)
+    items = (dx.Image * 1)(dx.Image(4, 4, RGBA16F, 32, 128, half.ctypes.data))
+    table = (capi.ExrChannel * 4)(*[capi.ExrChannel(8 * c, dx.EXR_HALF) for c in range(4)])
+    assert refused(ctx, "dxtex_exr_unpack", stream.ctypes.data, 128, (capi.ExrChunk * 1)(), 0, table, 32, items, 1) == (E_INVALIDARG, (0, 0))
+    assert last_error(ctx) == "no chunks"
+    # dxtex_merge_image: a permute index of 8 (check_merge)
+    a, b, _, zero, one = merge_inputs(img)
+    out = np.zeros(W * 4 * H, np.uint8)
+    ia, ib, idst = host_image(a, W, H, RGBA8), host_image(b, W, H, dx.DXGI_FORMAT_R32G32B32A32_FLOAT), host_image(out, W, H, RGBA8)
+    assert refused(ctx, "dxtex_merge_image", ctypes.byref(ia), ctypes.byref(ib), ctypes.byref(idst), (ctypes.c_uint32 * 4)(0, 1, 2, 8), zero, one) == (E_INVALIDARG, (0, 0))
+    assert last_error(ctx) == "permute index above 7"
+    # dxtex_analyze: no images (check_analyze)
+    assert refused(ctx, "dxtex_analyze", ctypes.byref(ia), 0, (capi.ImageStats * 1)()) == (E_INVALIDARG, (0, 0))
+    assert last_error(ctx) == "no images"
+
+
+def test_staging_is_reused_across_needs(ctx, img):
+    """A large plan, a small one, the large one again: each result is its device form's (a wrong total, or a base taken before the buffers
+    grew, would show in the second or third)."""
+    n = 3
+    dims = chain(W, H, n)
+    sizes = [pitch(RGBA8, w, h)[1] for w, h in dims]
+    rect, at = (5, 7, 3, 2), (11, 4)
+    with Device(ctx) as d:
+        ptrs = [d.put(img)] + [d.empty(s) for s in sizes[1:]]
+        ctx.generate_mips_device([dx.device_image(p, w, h, RGBA8) for p, (w, h) in zip(ptrs, dims)], 0)
+        want_mips = [d.get(p, s) for p, s in zip(ptrs[1:], sizes[1:])]
+        pdst = d.empty(sizes[0])
+        ctx.copy_rectangles_device([dx.device_image(ptrs[0], W, H, RGBA8)], [rect], [dx.device_image(pdst, W, H, RGBA8)], [at[0]], [at[1]])
+        want_rect = d.get(pdst, sizes[0])
+    first = ctx.generate_mips(img, W, H, RGBA8, n, 0)
+    small = np.zeros(sizes[0], np.uint8)
+    assert moved(ctx, lambda: ctx.copy_rectangle(host_image(img, W, H, RGBA8), rect, host_image(small, W, H, RGBA8), 0, *at)) == (3 * 4 * 2, 3 * 4 * 2)
+    again = ctx.generate_mips(img, W, H, RGBA8, n, 0)
+    assert np.array_equal(small, want_rect)
+    for got in (first, again):
+        assert all(np.array_equal(g, w) for g, w in zip(got[1:], want_mips))
