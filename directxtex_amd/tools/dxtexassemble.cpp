@@ -14,7 +14,7 @@
 //   -w <n> -h <n> -m <n> -f <format> -if <filter> -srgb -srgbi -srgbo -wrap -mirror -sepalpha -alpha -tonemap -stripmips -swizzle <mask>
 //   -o <file> -y -l -dx10 -fl <level> -nologo -gpu <n> -timing -help
 //   The cross / strip commands default to a .bmp output in texassemble; there is no BMP writer here, so they want -o.
-#include "../host/DirectXTexAMD.h"
+#include "tool_files.h"
 
 #include <algorithm>
 #include <cctype>
@@ -24,50 +24,19 @@
 #include <cstring>
 #include <memory>
 #include <string>
-#include <strings.h>
 #include <sys/stat.h>
 #include <vector>
 
-using namespace DirectXTexAMD;
+using namespace tool;
 
 namespace
 {
-struct Name { const char* name; uint32_t value; };
-const Name kFormats[] = {
-    { "R32G32B32A32_FLOAT", 2 }, { "R32G32B32A32_UINT", 3 }, { "R32G32B32A32_SINT", 4 }, { "R32G32B32_FLOAT", 6 }, { "R32G32B32_UINT", 7 }, { "R32G32B32_SINT", 8 },
-    { "R16G16B16A16_FLOAT", 10 }, { "R16G16B16A16_UNORM", 11 }, { "R16G16B16A16_UINT", 12 }, { "R16G16B16A16_SNORM", 13 }, { "R16G16B16A16_SINT", 14 },
-    { "R32G32_FLOAT", 16 }, { "R32G32_UINT", 17 }, { "R32G32_SINT", 18 }, { "D32_FLOAT_S8X24_UINT", 20 }, { "R10G10B10A2_UNORM", 24 }, { "R10G10B10A2_UINT", 25 },
-    { "R11G11B10_FLOAT", 26 }, { "R8G8B8A8_UNORM", 28 }, { "R8G8B8A8_UNORM_SRGB", 29 }, { "R8G8B8A8_UINT", 30 }, { "R8G8B8A8_SNORM", 31 }, { "R8G8B8A8_SINT", 32 },
-    { "R16G16_FLOAT", 34 }, { "R16G16_UNORM", 35 }, { "R16G16_UINT", 36 }, { "R16G16_SNORM", 37 }, { "R16G16_SINT", 38 }, { "D32_FLOAT", 40 }, { "R32_FLOAT", 41 },
-    { "R32_UINT", 42 }, { "R32_SINT", 43 }, { "D24_UNORM_S8_UINT", 45 }, { "R8G8_UNORM", 49 }, { "R8G8_UINT", 50 }, { "R8G8_SNORM", 51 }, { "R8G8_SINT", 52 },
-    { "R16_FLOAT", 54 }, { "D16_UNORM", 55 }, { "R16_UNORM", 56 }, { "R16_UINT", 57 }, { "R16_SNORM", 58 }, { "R16_SINT", 59 }, { "R8_UNORM", 61 }, { "R8_UINT", 62 },
-    { "R8_SNORM", 63 }, { "R8_SINT", 64 }, { "A8_UNORM", 65 }, { "R1_UNORM", 66 }, { "R9G9B9E5_SHAREDEXP", 67 }, { "R8G8_B8G8_UNORM", 68 }, { "G8R8_G8B8_UNORM", 69 },
-    { "BC1_UNORM", 71 }, { "BC1_UNORM_SRGB", 72 }, { "BC2_UNORM", 74 }, { "BC2_UNORM_SRGB", 75 }, { "BC3_UNORM", 77 }, { "BC3_UNORM_SRGB", 78 }, { "BC4_UNORM", 80 },
-    { "BC4_SNORM", 81 }, { "BC5_UNORM", 83 }, { "BC5_SNORM", 84 }, { "B5G6R5_UNORM", 85 }, { "B5G5R5A1_UNORM", 86 }, { "B8G8R8A8_UNORM", 87 }, { "B8G8R8X8_UNORM", 88 },
-    { "R10G10B10_XR_BIAS_A2_UNORM", 89 }, { "B8G8R8A8_UNORM_SRGB", 91 }, { "B8G8R8X8_UNORM_SRGB", 93 }, { "BC6H_UF16", 95 }, { "BC6H_SF16", 96 }, { "BC7_UNORM", 98 },
-    { "BC7_UNORM_SRGB", 99 }, { "AYUV", 100 }, { "Y410", 101 }, { "Y416", 102 }, { "YUY2", 107 }, { "Y210", 108 }, { "Y216", 109 }, { "B4G4R4A4_UNORM", 115 },
-    { "R10G10B10_7E3_A2_FLOAT", 116 }, { "R10G10B10_6E4_A2_FLOAT", 117 }, { "R10G10B10_SNORM_A2_UNORM", 189 }, { "R4G4_UNORM", 190 }, { "A4B4G4R4_UNORM", 191 },
-    // texassemble's aliases
-    { "DXT1", 71 }, { "DXT2", 74 }, { "DXT3", 74 }, { "DXT4", 77 }, { "DXT5", 77 }, { "RGBA", 28 }, { "BGRA", 87 }, { "BGR", 88 }, { "FP16", 10 }, { "FP32", 2 },
-};
 const Name kFilters[] = {
     { "POINT", TEX_FILTER_POINT }, { "LINEAR", TEX_FILTER_LINEAR }, { "CUBIC", TEX_FILTER_CUBIC }, { "FANT", TEX_FILTER_FANT }, { "BOX", TEX_FILTER_BOX },
     { "TRIANGLE", TEX_FILTER_TRIANGLE }, { "POINT_DITHER", TEX_FILTER_POINT | TEX_FILTER_DITHER }, { "LINEAR_DITHER", TEX_FILTER_LINEAR | TEX_FILTER_DITHER },
     { "CUBIC_DITHER", TEX_FILTER_CUBIC | TEX_FILTER_DITHER }, { "TRIANGLE_DITHER", TEX_FILTER_TRIANGLE | TEX_FILTER_DITHER },
     { "POINT_DITHER_DIFFUSION", TEX_FILTER_POINT | TEX_FILTER_DITHER_DIFFUSION }, { "LINEAR_DITHER_DIFFUSION", TEX_FILTER_LINEAR | TEX_FILTER_DITHER_DIFFUSION },
 };
-
-bool lookup(const Name* t, size_t n, const char* s, uint32_t& out)
-{
-    for (size_t i = 0; i < n; ++i) if (!strcasecmp(t[i].name, s)) { out = t[i].value; return true; }
-    return false;
-}
-const char* FormatName(DXGI_FORMAT f)
-{
-    for (const Name& n : kFormats) if (n.value == uint32_t(f)) return n.name;
-    return "*UNKNOWN*";
-}
-
 
 constexpr uint32_t TEX_FILTER_SEPARATE_ALPHA = 0x100;      // DirectXTex.h: resize the alpha channel separately (as in dxtexconv)
 
@@ -136,12 +105,6 @@ void PrintUsage()
                 "   -stripmips          Use only base image from input dds files\n   -gpu <n>            HIP device\n   -timing             Display elapsed processing time\n");
 }
 
-bool hasExt(const std::string& s, const char* ext)
-{
-    const size_t n = std::strlen(ext);
-    return s.size() >= n && !strcasecmp(s.c_str() + s.size() - n, ext);
-}
-
 bool ParseSize(const char* v, size_t& out)
 {
     char* end = nullptr;
@@ -156,7 +119,7 @@ int Parse(int argc, char** argv, Options& o)
 {
     if (argc < 2) { PrintUsage(); return 2; }
     if (!std::strcmp(argv[1], "-help") || !std::strcmp(argv[1], "--help") || !std::strcmp(argv[1], "-?")) { PrintUsage(); return 2; }
-    if (!lookup(kCommands, sizeof(kCommands) / sizeof(kCommands[0]), argv[1], o.command))
+    if (!lookup(kCommands, argv[1], o.command))
     {
         std::printf("Must use one of: cube, volume, array, cubearray, h-cross, v-cross, h-tee, h-strip, v-strip, array-strip,\n"
                     "   merge, cube-from-hc, cube-from-vc, cube-from-ht, cube-from-hs, cube-from-vs, from-mips, cube-from-mips\n\n");
@@ -186,12 +149,12 @@ int Parse(int argc, char** argv, Options& o)
         else if (a == "-f" || a == "--format")
         {
             if (!value(v)) return 1;
-            if (!lookup(kFormats, sizeof(kFormats) / sizeof(kFormats[0]), v, o.format)) { std::printf("Invalid value specified with -f (%s)\n", v); return 1; }
+            if (!lookup(kFormats, v, o.format)) { std::printf("Invalid value specified with -f (%s)\n", v); return 1; }
         }
         else if (a == "-if" || a == "--image-filter")
         {
             if (!value(v)) return 1;
-            if (!lookup(kFilters, sizeof(kFilters) / sizeof(kFilters[0]), v, o.filter)) { std::printf("Invalid value specified with -if (%s)\n", v); return 1; }
+            if (!lookup(kFilters, v, o.filter)) { std::printf("Invalid value specified with -if (%s)\n", v); return 1; }
         }
         else if (a == "-srgbi" || a == "--srgb-in") o.srgb |= TEX_FILTER_SRGB_IN;
         else if (a == "-srgbo" || a == "--srgb-out") o.srgb |= TEX_FILTER_SRGB_OUT;
@@ -264,7 +227,7 @@ int Parse(int argc, char** argv, Options& o)
     if (o.output.empty())
     {
         if (IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP) { std::printf("ERROR: Need to specify output file via -o (there is no .bmp writer)\n"); return 1; }
-        if (hasExt(o.files[0], ".dds")) { std::printf("ERROR: Need to specify output file via -o\n"); return 1; }
+        if (FileTypeOf(o.files[0]) == FileType::DDS) { std::printf("ERROR: Need to specify output file via -o\n"); return 1; }
         std::string stem = o.files[0];
         const size_t slash = stem.find_last_of('/');
         if (slash != std::string::npos) stem = stem.substr(slash + 1);
@@ -273,7 +236,8 @@ int Parse(int argc, char** argv, Options& o)
     }
     if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     const bool single = IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP || o.command == CMD_MERGE;
-    if (!hasExt(o.output, ".dds") && !(single && (hasExt(o.output, ".tga") || hasExt(o.output, ".hdr") || hasExt(o.output, ".png") || hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg") || hasExt(o.output, ".exr"))))
+    const FileType outType = FileTypeOf(o.output);
+    if (outType != FileType::DDS && !(single && (outType == FileType::TGA || outType == FileType::HDR || outType == FileType::PNG || outType == FileType::JPEG || outType == FileType::EXR)))
     {
         std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga, .hdr, .png or .jpg" : "");
         return 1;
@@ -303,19 +267,8 @@ void PrintInfo(const TexMetadata& info)
     std::printf(")");
 }
 
-int Fail(const char* what, HRESULT hr)
-{
-    std::printf("%s (%08X)\n", what, static_cast<unsigned int>(hr));
-    return 1;
-}
-
-// an .hdr input is held as the file's RGBE rows (4 bytes a texel) and its exposure: the floats are made on the device after the upload
-// a .tga input likewise as the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
-// a .dds input as the file itself, parsed: its payload goes up as it is and the row conversions of a legacy file run on the device
-struct Input { TexMetadata info; DDSRawImage dds; bool hdr = false; float exposure = 1.f; Blob rgbe; bool tga = false; TGARawImage tgaRaw; bool png = false; PNGRawImage pngRaw; bool jpeg = false; JPEGRawImage jpegRaw; bool exr = false; EXRRawImage exrRaw; };
-
 // texassemble.cpp:1360-1581: the files, read and checked on the host - no device yet
-int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
+int LoadInputs(const Options& o, std::vector<std::unique_ptr<SourceFile>>& inputs)
 {
     for (size_t i = 0; i < o.files.size(); ++i)
     {
@@ -323,15 +276,20 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
         if (i) std::printf("\n");
         std::printf("reading %s", file.c_str());
         std::fflush(stdout);
-        std::unique_ptr<Input> in(new Input);
-        HRESULT hr;
-        const bool dds = hasExt(file, ".dds");
-        if (IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP)
+        const FileType type = FileTypeOf(file);
+        const bool fromDds = IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP;
+        if (fromDds && type != FileType::DDS) { std::printf("\nERROR: Input must be a dds of a %s\n", o.command == CMD_ARRAY_STRIP ? "1D/2D array" : "cubemap"); return 1; }
+        // this tool takes no portable pixmaps
+        if (type == FileType::UNKNOWN || type == FileType::PPM || type == FileType::PFM || type == FileType::PHM) { std::printf(" FAILED: only .dds, .tga, .hdr, .png and .jpg can be read (the reference reads the rest through WIC)\n"); return 1; }
+        // the byte-serial half of every codec here, before there is a device; a .png headed for a BGR format is decoded as one
+        // (texassemble.cpp:1526-1544). For a .tga this states the alpha mode the line below prints
+        std::unique_ptr<SourceFile> in(new SourceFile);
+        LoadFlags flags;
+        flags.png = PngBgrFor(o.format);
+        const HRESULT hr = in->Parse(file.c_str(), type, flags);
+        if (FAILED(hr)) return Fail(" FAILED", hr);
+        if (fromDds)
         {
-            if (!dds) { std::printf("\nERROR: Input must be a dds of a %s\n", o.command == CMD_ARRAY_STRIP ? "1D/2D array" : "cubemap"); return 1; }
-            hr = LoadFromDDSFileRaw(file.c_str(), DDS_FLAGS_NONE, nullptr, in->dds);
-            if (FAILED(hr)) return Fail(" FAILED", hr);
-            in->info = in->dds.metadata;
             if (o.command == CMD_ARRAY_STRIP)
             {
                 if (in->info.dimension == TEX_DIMENSION_TEXTURE3D || in->info.arraySize < 2 || in->info.IsCubemap()) { std::printf("\nERROR: Input must be a 1D/2D array\n"); return 1; }
@@ -339,11 +297,8 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
             else if (!in->info.IsCubemap()) { std::printf("\nERROR: Input must be a cubemap\n"); return 1; }
             else if (in->info.arraySize != 6) std::printf("\nWARNING: Only the first cubemap in an array is written out as a cross/strip\n");
         }
-        else if (dds)
+        else if (type == FileType::DDS)
         {
-            hr = LoadFromDDSFileRaw(file.c_str(), DDS_FLAGS_NONE, nullptr, in->dds);
-            if (FAILED(hr)) return Fail(" FAILED", hr);
-            in->info = in->dds.metadata;
             if (in->info.IsVolumemap() || in->info.IsCubemap()) { std::printf("\nERROR: Can't assemble complex surfaces\n"); return 1; }
             if (in->info.mipLevels > 1 && !o.stripMips &&
                 (o.command == CMD_CUBE || o.command == CMD_VOLUME || o.command == CMD_ARRAY || o.command == CMD_CUBEARRAY || o.command == CMD_MERGE))
@@ -352,37 +307,6 @@ int LoadInputs(const Options& o, std::vector<std::unique_ptr<Input>>& inputs)
                 return 1;
             }
         }
-        else if (hasExt(file, ".tga"))
-        {
-            in->tga = true;
-            hr = LoadFromTGAFileRaw(file.c_str(), TGA_FLAGS_NONE, &in->info, in->tgaRaw);
-            if (FAILED(hr)) return Fail(" FAILED", hr);
-            ApplyTGAAlphaRule(in->tgaRaw, TGA_FLAGS_NONE, in->info);          // the line below states the alpha mode
-        }
-        else if (hasExt(file, ".png"))
-        {
-            // inflate and the row filters here, before there is a device; the unfiltered rows go up later (texassemble.cpp:1536-1544)
-            const bool bgr = o.format == DXGI_FORMAT_B8G8R8A8_UNORM || o.format == DXGI_FORMAT_B8G8R8X8_UNORM || o.format == DXGI_FORMAT_B8G8R8A8_UNORM_SRGB || o.format == DXGI_FORMAT_B8G8R8X8_UNORM_SRGB;
-            in->png = true;
-            hr = LoadFromPNGFileRaw(file.c_str(), bgr ? PNG_FLAGS_BGR : PNG_FLAGS_NONE, &in->info, in->pngRaw);
-            if (FAILED(hr)) return Fail(" FAILED", hr);
-        }
-        else if (hasExt(file, ".jpg") || hasExt(file, ".jpeg"))
-        {
-            // the Huffman walk here, before there is a device; the quantised coefficients go up later (texassemble.cpp:1526-1534)
-            in->jpeg = true;
-            hr = LoadFromJPEGFileRaw(file.c_str(), JPEG_FLAGS_NONE, &in->info, in->jpegRaw);
-            if (FAILED(hr)) return Fail(" FAILED", hr);
-        }
-        else if (hasExt(file, ".exr"))
-        {
-            // the header walk, inflate and the RLE packets here, before there is a device; the expanded chunks go up later
-            in->exr = true;
-            hr = LoadFromEXRFileRaw(file.c_str(), &in->info, in->exrRaw);
-            if (FAILED(hr)) return Fail(" FAILED", hr);
-        }
-        else if (hasExt(file, ".hdr")) { in->hdr = true; hr = LoadFromHDRFileRGBE(file.c_str(), &in->info, in->exposure, in->rgbe); if (FAILED(hr)) return Fail(" FAILED", hr); }
-        else { std::printf(" FAILED: only .dds, .tga, .hdr, .png and .jpg can be read (the reference reads the rest through WIC)\n"); return 1; }
         PrintInfo(in->info);
         std::fflush(stdout);
         inputs.push_back(std::move(in));
@@ -410,7 +334,7 @@ bool CalculateMipLevels(size_t width, size_t height, size_t& mipLevels)
     return true;
 }
 
-int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
+int Run(Device& dev, Options& o, std::vector<std::unique_ptr<SourceFile>>& inputs)
 {
     std::vector<DeviceScratchImage> resident(inputs.size());
     size_t width = o.width, height = o.height, mipLevels = o.mipLevels;
@@ -419,14 +343,9 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     for (size_t index = 0; index < inputs.size(); ++index)
     {
         DeviceScratchImage cur, next;
-        Input& in = *inputs[index];
-        HRESULT hr = in.hdr ? UploadHDRRows(dev, in.info, in.exposure, in.rgbe, cur) : in.tga ? UploadTGARaw(dev, in.info, TGA_FLAGS_NONE, in.tgaRaw, cur)
-                                        : in.png ? UploadPNGRaw(dev, in.info, in.pngRaw, cur)
-                                        : in.jpeg ? UploadJPEGRaw(dev, in.info, in.jpegRaw, cur)
-                                        : in.exr ? UploadEXRRaw(dev, in.info, in.exrRaw, cur)
-                                                                                              : UploadDDSRaw(dev, in.dds, cur);
+        SourceFile& in = *inputs[index];
+        HRESULT hr = in.Upload(dev, cur);          // the file's own bytes go up; the host copy is let go
         if (FAILED(hr)) return Fail(" FAILED [upload]", hr);
-        in.dds.Release(); in.rgbe.Release(); in.tgaRaw.Release(); in.pngRaw.Release(); in.jpegRaw.Release(); in.exrRaw.Release();
         TexMetadata info = cur.GetMetadata();
         const auto step = [&]() { cur = std::move(next); next = DeviceScratchImage(); info = cur.GetMetadata(); };
         if (IsPlanar(info.format))          // texassemble.cpp:1587-1600
@@ -544,21 +463,15 @@ int Run(Device& dev, Options& o, std::vector<std::unique_ptr<Input>>& inputs)
     }
     if (FAILED(hr)) return Fail("FAILED building result image", hr);
 
-    // an .hdr output comes back as the RGBE rows the resident saver makes on the device, a .dds as its payload straight behind the header
-    const bool hdrOut = hasExt(o.output, ".hdr"), tgaOut = hasExt(o.output, ".tga");          // .tga: the file's rows, likewise
     std::printf("\nWriting %s ", o.output.c_str());
     PrintInfo(result.GetMetadata());
     std::printf("\n");
     std::fflush(stdout);
     struct stat st;
     if (!o.overwrite && stat(o.output.c_str(), &st) == 0) { std::printf("\nERROR: Output file already exists, use -y to overwrite\n"); return 1; }
-    if (hdrOut) hr = SaveToHDRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());
-    else if (tgaOut) hr = SaveToTGAFile(dev, *result.GetImage(0, 0, 0), TGA_FLAGS_NONE, o.output.c_str());
-    else if (hasExt(o.output, ".png")) hr = SaveToPNGFile(dev, *result.GetImage(0, 0, 0), PNG_FLAGS_NONE, o.output.c_str());          // the file's rows, likewise
-    else if (hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg")) hr = SaveToJPEGFile(dev, *result.GetImage(0, 0, 0), JPEG_FLAGS_NONE, o.output.c_str());          // the coefficients
-    else if (hasExt(o.output, ".exr")) hr = SaveToEXRFile(dev, *result.GetImage(0, 0, 0), o.output.c_str());          // the scanlines' half planes
-    else hr = SaveToDDSFile(dev, result.GetImages(), result.GetImageCount(), result.GetMetadata(),
-                            o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE, o.output.c_str());
+    // the one download, by the resident writers (tool_files.h: Save)
+    hr = Save(dev, FileTypeOf(o.output), result, result.GetMetadata(), o.dx10 ? DDS_FLAGS(DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2) : DDS_FLAGS_NONE,
+              nullptr, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED", hr);
     return 0;
 }
@@ -570,7 +483,7 @@ int main(int argc, char** argv)
     const int parsed = Parse(argc, argv, o);
     if (parsed) return parsed == 2 ? 0 : 1;
     if (!o.nologo) std::printf("dxtexassemble: DirectXTex texture assembler on MI355X (gfx950)\n\n");
-    std::vector<std::unique_ptr<Input>> inputs;
+    std::vector<std::unique_ptr<SourceFile>> inputs;
     if (LoadInputs(o, inputs)) return 1;
     Device dev;
     const HRESULT hr = dev.Create(o.gpu);

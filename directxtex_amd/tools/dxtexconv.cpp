@@ -29,7 +29,7 @@
 //     -dx10 -dx9           force the 'DX10' header (+ alpha mode) / a Direct3D 9 file        -tga20   TGA output with the 2.0 extension area
 //     -px <s> -sx <s> -l   output name prefix / suffix, lower case    -y   overwrite    -info (print what the files hold, no GPU)    -timing -nologo -gpu <n> | -gpus <a,b,...> (files dealt out over the GPUs)
 //     -overlap <n>         workers (contexts) per GPU, default 2: the transfers and file codecs of one file overlap the kernels of another
-#include "../host/DirectXTexAMD.h"
+#include "tool_files.h"
 
 #include <algorithm>
 #include <cctype>
@@ -44,32 +44,12 @@
 #include <thread>
 #include <vector>
 
-using namespace DirectXTexAMD;
+using namespace tool;
 
 namespace
 {
-struct Name { const char* name; uint32_t value; };
-const Name kFormats[] = {
-    { "R32G32B32A32_FLOAT", 2 }, { "R16G16B16A16_FLOAT", 10 }, { "R16G16B16A16_UNORM", 11 }, { "R32G32_FLOAT", 16 }, { "R8G8B8A8_UNORM", 28 },
-    { "R8G8B8A8_UNORM_SRGB", 29 }, { "R8G8B8A8_SNORM", 31 }, { "R16G16_FLOAT", 34 }, { "R16G16_UNORM", 35 }, { "R32_FLOAT", 41 }, { "R8G8_UNORM", 49 },
-    { "R8G8_SNORM", 51 }, { "R16_FLOAT", 54 }, { "R16_UNORM", 56 }, { "R8_UNORM", 61 }, { "R8_SNORM", 63 }, { "A8_UNORM", 65 },
-    { "BC1_UNORM", 71 }, { "BC1_UNORM_SRGB", 72 }, { "BC2_UNORM", 74 }, { "BC2_UNORM_SRGB", 75 }, { "BC3_UNORM", 77 }, { "BC3_UNORM_SRGB", 78 },
-    { "BC4_UNORM", 80 }, { "BC4_SNORM", 81 }, { "BC5_UNORM", 83 }, { "BC5_SNORM", 84 }, { "B8G8R8A8_UNORM", 87 }, { "B8G8R8X8_UNORM", 88 },
-    { "B8G8R8A8_UNORM_SRGB", 91 }, { "B8G8R8X8_UNORM_SRGB", 93 }, { "BC6H_UF16", 95 }, { "BC6H_SF16", 96 }, { "BC7_UNORM", 98 }, { "BC7_UNORM_SRGB", 99 },
-    { "R32G32B32_FLOAT", 6 }, { "R16G16B16A16_SNORM", 13 }, { "R10G10B10A2_UNORM", 24 }, { "R11G11B10_FLOAT", 26 }, { "R16G16_SNORM", 37 }, { "R16_SNORM", 58 },
-    { "R9G9B9E5_SHAREDEXP", 67 }, { "B5G6R5_UNORM", 85 }, { "B5G5R5A1_UNORM", 86 }, { "B4G4R4A4_UNORM", 115 },
-    { "R32G32B32A32_UINT", 3 }, { "R32G32B32A32_SINT", 4 }, { "R32G32B32_UINT", 7 }, { "R32G32B32_SINT", 8 }, { "R16G16B16A16_UINT", 12 }, { "R16G16B16A16_SINT", 14 },
-    { "R32G32_UINT", 17 }, { "R32G32_SINT", 18 }, { "R10G10B10A2_UINT", 25 }, { "R8G8B8A8_UINT", 30 }, { "R8G8B8A8_SINT", 32 }, { "R16G16_UINT", 36 }, { "R16G16_SINT", 38 },
-    { "R32_UINT", 42 }, { "R32_SINT", 43 }, { "R8G8_UINT", 50 }, { "R8G8_SINT", 52 }, { "R16_UINT", 57 }, { "R16_SINT", 59 }, { "R8_UINT", 62 }, { "R8_SINT", 64 },
-    { "R10G10B10_XR_BIAS_A2_UNORM", 89 }, { "AYUV", 100 }, { "Y410", 101 }, { "Y416", 102 },
-    { "D32_FLOAT_S8X24_UINT", 20 }, { "D32_FLOAT", 40 }, { "D24_UNORM_S8_UINT", 45 }, { "D16_UNORM", 55 },
-    { "R1_UNORM", 66 }, { "R8G8_B8G8_UNORM", 68 }, { "G8R8_G8B8_UNORM", 69 }, { "YUY2", 107 }, { "Y210", 108 }, { "Y216", 109 }, { "A4B4G4R4_UNORM", 191 },
-    // the console formats, under texconv's names (texconv.cpp:422-425)
-    { "R10G10B10_7E3_A2_FLOAT", 116 }, { "R10G10B10_6E4_A2_FLOAT", 117 }, { "R10G10B10_SNORM_A2_UNORM", 189 }, { "R4G4_UNORM", 190 },
-    // texconv's aliases (texconv.cpp:420-440)
-    { "DXT1", 71 }, { "DXT2", 74 }, { "DXT3", 74 }, { "DXT4", 77 }, { "DXT5", 77 }, { "RGBA", 28 }, { "BGRA", 87 }, { "BGR", 88 }, { "FP16", 10 }, { "FP32", 2 },
-    { "BC4", 80 }, { "BC5", 83 }, { "BC6H", 95 }, { "BC7", 98 },
-};
+// texconv's short names for the block formats it has one for (texconv.cpp:420-440); the other tools refuse them
+const Name kBlockAliases[] = { { "BC4", 80 }, { "BC5", 83 }, { "BC6H", 95 }, { "BC7", 98 } };
 const Name kFilters[] = {
     { "POINT", TEX_FILTER_POINT }, { "LINEAR", TEX_FILTER_LINEAR }, { "CUBIC", TEX_FILTER_CUBIC }, { "BOX", TEX_FILTER_BOX }, { "FANT", TEX_FILTER_BOX },
     { "TRIANGLE", TEX_FILTER_TRIANGLE },
@@ -86,20 +66,12 @@ const Name kRotations[] = {           // g_pRotateColor (texconv.cpp:543-554)
 };
 constexpr uint32_t TEX_FILTER_SEPARATE_ALPHA = 0x100;
 
-bool lookup(const Name* t, size_t n, const char* s, uint32_t& out, bool numbers = true)
-{
-    for (size_t i = 0; i < n; ++i) if (!strcasecmp(t[i].name, s)) { out = t[i].value; return true; }
-    if (!numbers) return false;
-    char* end = nullptr; const unsigned long v = std::strtoul(s, &end, 0);
-    if (end && *end == 0 && end != s) { out = uint32_t(v); return true; }
-    return false;
-}
-
 struct Options
 {
     size_t width = 0, height = 0, mipLevels = 0, maxSize = 16384;          // mipLevels 0: keep a chain the input has, else build the full one
     bool pow2 = false, pmalpha = false, demul = false, dx10 = false, dx9 = false, sepalpha = false, lower = false, overwrite = false,
-         timing = false, nologo = false, hdrOut = false, tgaOut = false, ppmOut = false, pfmOut = false, pngOut = false, exrOut = false, ignoreSrgb = false, tga20 = false, info = false;
+         timing = false, nologo = false, ignoreSrgb = false, tga20 = false, info = false;
+    FileType outType = FileType::DDS;   // -ft
     uint32_t format = 0, filter = 0, filterOpts = 0, srgb = 0, convert = 0, compress = 0, ddsRead = DDS_FLAGS_ALLOW_LARGE_FILES;
     float alphaThreshold = TEX_THRESHOLD_DEFAULT, keepCoverage = 0.f;
     bool nmap = false;                  // -nmap: ComputeNormalMap replaces the convert step
@@ -114,7 +86,20 @@ struct Options
     size_t overlap = 2;                 // workers per listed GPU: file k + 1 is read, decoded and uploaded while file k's kernels run
     std::string prefix, suffix, out;
     std::vector<std::string> inputs;
+
+    // the readers' flags are texconv's (texconv.cpp:2192-2217): -ignoresrgb keeps a .png's sRGB chunk and gAMA from choosing the format and
+    // makes a colour .jpg linear; a .png headed for a BGR format is decoded as one (the load only: -info reports the file)
+    LoadFlags ReadFlags(bool load) const
+    {
+        return { DDS_FLAGS(ddsRead), TGA_FLAGS_NONE, PNG_FLAGS((load ? PngBgrFor(format) : PNG_FLAGS_NONE) | (ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE)),
+                 ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE };
+    }
 };
+
+// the types this tool writes: every one with a -ft name but JPEG
+bool Writes(FileType t) { return t != FileType::UNKNOWN && t != FileType::PHM && t != FileType::JPEG; }
+// an extension this tool does not know is read as a .dds
+FileType InputType(const std::string& file) { const FileType t = FileTypeOf(file); return t == FileType::UNKNOWN ? FileType::DDS : t; }
 
 bool ispow2(size_t x) { return x && !(x & (x - 1)); }
 
@@ -159,9 +144,9 @@ bool Parse(int argc, char** argv, Options& o)
         if (a == "-w") o.width = std::strtoull(next(), nullptr, 10);
         else if (a == "-h") o.height = std::strtoull(next(), nullptr, 10);
         else if (a == "-m") o.mipLevels = std::strtoull(next(), nullptr, 10);
-        else if (a == "-f") { if (!lookup(kFormats, sizeof(kFormats) / sizeof(Name), next(), o.format)) { std::fprintf(stderr, "unknown format\n"); return false; } }
-        else if (a == "-if") { if (!lookup(kFilters, sizeof(kFilters) / sizeof(Name), next(), o.filter)) { std::fprintf(stderr, "unknown filter (dithered filters have no GPU path)\n"); return false; } }
-        else if (a == "-fl") { uint32_t v; if (!lookup(kFeatureLevels, sizeof(kFeatureLevels) / sizeof(Name), next(), v, false)) { std::fprintf(stderr, "unknown feature level\n"); return false; } o.maxSize = v; }
+        else if (a == "-f") { const char* v = next(); if (!lookup(kFormats, v, o.format, true) && !lookup(kBlockAliases, v, o.format)) { std::fprintf(stderr, "unknown format\n"); return false; } }
+        else if (a == "-if") { if (!lookup(kFilters, next(), o.filter, true)) { std::fprintf(stderr, "unknown filter (dithered filters have no GPU path)\n"); return false; } }
+        else if (a == "-fl") { uint32_t v; if (!lookup(kFeatureLevels, next(), v)) { std::fprintf(stderr, "unknown feature level\n"); return false; } o.maxSize = v; }
         else if (a == "-bc")
         {
             for (const char* p = next(); *p; ++p)
@@ -230,7 +215,7 @@ bool Parse(int argc, char** argv, Options& o)
             // texconv.cpp:1545-1553 (LookupByName: either case); the short -rotatecolor is not accepted
             const char* v = next();
             if (missing) { std::fprintf(stderr, "option %s needs a value\n", a.c_str()); return false; }
-            if (!lookup(kRotations, sizeof(kRotations) / sizeof(Name), v, o.rotateColor, false)) { std::fprintf(stderr, "Invalid value specified with -rotatecolor (%s)\n", v); return false; }
+            if (!lookup(kRotations, v, o.rotateColor)) { std::fprintf(stderr, "Invalid value specified with -rotatecolor (%s)\n", v); return false; }
         }
         else if (a == "-paper-white-nits")
         {
@@ -286,14 +271,9 @@ bool Parse(int argc, char** argv, Options& o)
         else if (a == "-ft")
         {
             const char* ft = next();
-            if (!strcasecmp(ft, "hdr")) o.hdrOut = true;
-            else if (!strcasecmp(ft, "tga")) o.tgaOut = true;
-            else if (!strcasecmp(ft, "ppm")) o.ppmOut = true;
-            else if (!strcasecmp(ft, "pfm")) o.pfmOut = true;
-            else if (!strcasecmp(ft, "png")) o.pngOut = true;
-            else if (!strcasecmp(ft, "exr")) o.exrOut = true;
-            else if (!strcasecmp(ft, "jpg") || !strcasecmp(ft, "jpeg")) { std::fprintf(stderr, "-ft %s: JPEG output is not written yet (the reader is; the writer is the next step)\n", ft); return false; }
-            else if (strcasecmp(ft, "dds")) { std::fprintf(stderr, "output file types: dds, hdr, tga, ppm, pfm, png\n"); return false; }
+            o.outType = FileTypeOfFt(ft);
+            if (o.outType == FileType::JPEG) { std::fprintf(stderr, "-ft %s: JPEG output is not written yet (the reader is; the writer is the next step)\n", ft); return false; }
+            if (o.outType == FileType::UNKNOWN) { std::fprintf(stderr, "output file types: dds, hdr, tga, ppm, pfm, png\n"); return false; }
         }
         else if (a == "-r" || a == "-nogpu" || a == "-singleproc") { }            // nothing to switch here
         else if (a[0] == '-') { std::fprintf(stderr, "unknown or unsupported option %s\n", a.c_str()); return false; }
@@ -303,28 +283,23 @@ bool Parse(int argc, char** argv, Options& o)
     if (o.pmalpha && o.demul) { std::fprintf(stderr, "-pmalpha and -alpha exclude each other\n"); return false; }
     if (o.dx10 && o.dx9) { std::fprintf(stderr, "-dx10 and -dx9 exclude each other\n"); return false; }
     // -ft png: -o names a directory or a .png file. A name that ends in another type's extension would receive a PNG under that name, which no
-    // reader that goes by the extension opens.
-    for (const char* ext : { ".dds", ".hdr", ".tga", ".ppm", ".pfm", ".exr" })
-        if (o.pngOut && o.out.size() > 4 && !strcasecmp(o.out.c_str() + o.out.size() - 4, ext)) { std::fprintf(stderr, "-ft png writes a .png: -o %s names a %s file\n", o.out.c_str(), ext); return false; }
-    // -ft exr likewise
-    for (const char* ext : { ".dds", ".hdr", ".tga", ".ppm", ".pfm", ".png" })
-        if (o.exrOut && o.out.size() > 4 && !strcasecmp(o.out.c_str() + o.out.size() - 4, ext)) { std::fprintf(stderr, "-ft exr writes a .exr: -o %s names a %s file\n", o.out.c_str(), ext); return false; }
-    for (const char* ext : { ".jpg", ".jpeg" })
-        if (o.out.size() > std::strlen(ext) && !strcasecmp(o.out.c_str() + o.out.size() - std::strlen(ext), ext)) { std::fprintf(stderr, "-o %s: JPEG output is not written yet\n", o.out.c_str()); return false; }
+    // reader that goes by the extension opens. -ft exr likewise; the other types are not checked.
+    const FileType named = FileTypeOf(o.out);
+    if ((o.outType == FileType::PNG || o.outType == FileType::EXR) && Writes(named) && named != o.outType) { std::fprintf(stderr, "-ft %s writes a %s: -o %s names a %s file\n", ExtensionOf(o.outType) + 1, ExtensionOf(o.outType), o.out.c_str(), ExtensionOf(named)); return false; }
+    if (named == FileType::JPEG) { std::fprintf(stderr, "-o %s: JPEG output is not written yet\n", o.out.c_str()); return false; }
     if (o.gpus.empty()) o.gpus.assign(1, 0);
     if (o.info) return !o.inputs.empty();
     return !o.inputs.empty() && !o.out.empty();
 }
 
-// <out> names a file when it ends in .dds and there is one input; otherwise a directory that receives <px><name><sx>.dds
+// <out> names a file when it ends in the extension of a type this tool writes and there is one input; otherwise a directory that receives
+// <px><name><sx> and the output type's extension
 std::string OutputName(const Options& o, const std::string& input)
 {
-    auto endsDDS = [](const std::string& s) { return s.size() > 4 && (!strcasecmp(s.c_str() + s.size() - 4, ".dds") || !strcasecmp(s.c_str() + s.size() - 4, ".hdr") || !strcasecmp(s.c_str() + s.size() - 4, ".tga") ||
-                                                                      !strcasecmp(s.c_str() + s.size() - 4, ".ppm") || !strcasecmp(s.c_str() + s.size() - 4, ".pfm") || !strcasecmp(s.c_str() + s.size() - 4, ".png") || !strcasecmp(s.c_str() + s.size() - 4, ".exr")); };
-    if (o.inputs.size() == 1 && endsDDS(o.out) && o.prefix.empty() && o.suffix.empty()) return o.out;
+    if (o.inputs.size() == 1 && Writes(FileTypeOf(o.out)) && o.prefix.empty() && o.suffix.empty()) return o.out;
     std::string base = input.substr(input.find_last_of('/') == std::string::npos ? 0 : input.find_last_of('/') + 1);
     if (base.find_last_of('.') != std::string::npos) base.erase(base.find_last_of('.'));
-    std::string name = o.prefix + base + o.suffix + (o.hdrOut ? ".hdr" : o.tgaOut ? ".tga" : o.ppmOut ? ".ppm" : o.pfmOut ? ".pfm" : o.pngOut ? ".png" : o.exrOut ? ".exr" : ".dds");
+    std::string name = o.prefix + base + o.suffix + ExtensionOf(o.outType);
     if (o.lower) std::transform(name.begin(), name.end(), name.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     return o.out + "/" + name;
 }
@@ -352,34 +327,9 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
     GetTransferBytes(dev, up0, down0);
 
     TexMetadata info;
-    auto hasExt = [](const std::string& f, const char* ext) { const size_t n = std::strlen(ext); return f.size() > n && !strcasecmp(f.c_str() + f.size() - n, ext); };
-    // Radiance RGBE -> RGBA32F: the resident loader sends the file's texels up as the 4 bytes they are and makes the floats on the device
+    // the file goes up at the bytes a texel it has on disk and becomes the image's texels on the device (tool_files.h: SourceFile)
     DeviceScratchImage image;
-    const bool hdrIn = hasExt(inFile, ".hdr"), tgaIn = hasExt(inFile, ".tga");
-    const bool pnmIn = hasExt(inFile, ".ppm") || hasExt(inFile, ".pfm") || hasExt(inFile, ".phm");
-    if (hdrIn) check("load", LoadFromHDRFile(dev, inFile.c_str(), &info, image));
-    // TGA likewise: the file's 1 to 4 bytes a texel go up, the swizzle, the flips and the alpha rule run on the device
-    else if (tgaIn) check("load", LoadFromTGAFile(dev, inFile.c_str(), TGA_FLAGS_NONE, &info, image));
-    // portable pixmaps likewise: the samples behind the text header go up as they are, 3 bytes to 4 (or 3 elements to 4), the byte swap and
-    // the vertical flip run on the device
-    else if (pnmIn) check("load", LoadFromPortablePixMapFile(dev, inFile.c_str(), &info, image));
-    // PNG likewise: inflate and the row filters are byte-serial and run on the host, the unfiltered rows go up as the 1/8 to 8 bytes a texel
-    // they are, and the expansion to the image's texels runs on the device. The flags are texconv's (texconv.cpp:2213-2217)
-    else if (hasExt(inFile, ".png"))
-    {
-        const bool bgr = o.format == DXGI_FORMAT_B8G8R8A8_UNORM || o.format == DXGI_FORMAT_B8G8R8X8_UNORM || o.format == DXGI_FORMAT_B8G8R8A8_UNORM_SRGB || o.format == DXGI_FORMAT_B8G8R8X8_UNORM_SRGB;
-        check("load", LoadFromPNGFile(dev, inFile.c_str(), PNG_FLAGS((bgr ? PNG_FLAGS_BGR : PNG_FLAGS_NONE) | (o.ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE)), &info, image));
-    }
-    // JPEG: the Huffman walk is byte-serial and runs on the host, the quantised coefficients go up as the file has them, and dequantisation,
-    // the inverse DCT, upsampling and YCbCr -> RGB run on the device. The flag is texconv's (texconv.cpp:2192-2208)
-    else if (hasExt(inFile, ".jpg") || hasExt(inFile, ".jpeg"))
-        check("load", LoadFromJPEGFile(dev, inFile.c_str(), o.ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, &info, image));
-    // OpenEXR: the header walk, inflate and the RLE packets are byte-serial and run on the host, the chunks go up as they leave the inflater -
-    // 6 bytes a texel for RGB half - and the delta undo, the plane gather, the conversion to half and the channel fill run on the device
-    else if (hasExt(inFile, ".exr")) check("load", LoadFromEXRFile(dev, inFile.c_str(), &info, image));
-    // DDS likewise: the payload goes up at the size it has in the file - a native file straight into the image's memory, a legacy one through
-    // the row conversions on the device
-    else check("load", LoadFromDDSFile(dev, inFile.c_str(), DDS_FLAGS(o.ddsRead), &info, image));
+    check("load", Load(dev, inFile.c_str(), InputType(inFile), o.ReadFlags(true), info, image));
     std::printf("reading %s (%zux%zu", inFile.c_str(), info.width, info.height);
     if (info.dimension == TEX_DIMENSION_TEXTURE3D) std::printf("x%zu", info.depth);
     std::printf(", %zu mips, %zu items, format %u)\n", info.mipLevels, info.arraySize, unsigned(info.format));
@@ -611,34 +561,30 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         struct stat st;
         if (::stat(outFile.c_str(), &st) == 0) { std::printf("skipping %s: it exists (use -y to overwrite)\n", outFile.c_str()); return; }
     }
-    // --- the one download, by the resident writers: the payload comes down straight behind the file's header
-    // -ft hdr: level 0 of the first item, like texconv's non-DDS codecs, comes back as RGBE rows the resident saver made on the device
-    // -ft tga likewise: the file's rows (-tga20: and the TGA 2.0 extension area around them)
-    // -ft ppm / pfm likewise: the file's samples, alpha dropped, halves widened and the rows of a .pfm flipped on the device
-    // -ft png likewise: the file's rows, B and R exchanged, X dropped and 16-bit samples swapped on the device; the host wraps them (PNG_FLAGS_NONE)
-    // -ft exr likewise: the scanlines' A, B, G, R half planes, floats made halves on the device; they land between the chunk headers the host wrote
+    // --- the one download, by the resident writers (tool_files.h: Save). A .dds takes every image; the other types take level 0 of the first
+    // item, like texconv's non-DDS codecs. -tga20: with the TGA 2.0 extension area
     uint32_t ddsFlags = DDS_FLAGS_NONE;
     if (o.dx10) ddsFlags |= DDS_FLAGS_FORCE_DX10_EXT | DDS_FLAGS_FORCE_DX10_EXT_MISC2;
     else if (o.dx9) ddsFlags |= DDS_FLAGS_FORCE_DX9_LEGACY;
-    if ((o.hdrOut || o.tgaOut || o.ppmOut || o.pfmOut || o.pngOut || o.exrOut) && handThrough)
+    const TexMetadata* tga20 = o.tga20 ? &info : nullptr;
+    if (o.outType != FileType::DDS && handThrough)
     {
         // blocks handed through: the host codec's answer
         ScratchImage result;
         check("download", image.Download(result));
-        if (o.hdrOut) check("save", SaveToHDRFile(result.GetImages()[0], outFile.c_str()));
-        else if (o.ppmOut) check("save", SaveToPortablePixMapFile(result.GetImages()[0], outFile.c_str()));
-        else if (o.pfmOut) check("save", SaveToPortablePixMapHDRFile(result.GetImages()[0], outFile.c_str()));
-        else if (o.pngOut) check("save", SaveToPNGFile(result.GetImages()[0], PNG_FLAGS_NONE, outFile.c_str()));
-        else if (o.exrOut) check("save", SaveToEXRFile(result.GetImages()[0], outFile.c_str()));
-        else check("save", SaveToTGAFile(result.GetImages()[0], TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));      // -tga20: with the TGA 2.0 extension area
+        const Image& first = result.GetImages()[0];
+        switch (o.outType)
+        {
+        case FileType::HDR: check("save", SaveToHDRFile(first, outFile.c_str())); break;
+        case FileType::TGA: check("save", SaveToTGAFile(first, TGA_FLAGS_NONE, outFile.c_str(), tga20)); break;
+        case FileType::PPM: check("save", SaveToPortablePixMapFile(first, outFile.c_str())); break;
+        case FileType::PFM: check("save", SaveToPortablePixMapHDRFile(first, outFile.c_str())); break;
+        case FileType::PNG: check("save", SaveToPNGFile(first, PNG_FLAGS_NONE, outFile.c_str())); break;
+        case FileType::EXR: check("save", SaveToEXRFile(first, outFile.c_str())); break;
+        default: check("save", HRESULT_E_NOT_SUPPORTED);          // -ft takes no other type
+        }
     }
-    else if (o.hdrOut) check("save", SaveToHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
-    else if (o.tgaOut) check("save", SaveToTGAFile(dev, *image.GetImage(0, 0, 0), TGA_FLAGS_NONE, outFile.c_str(), o.tga20 ? &info : nullptr));
-    else if (o.ppmOut) check("save", SaveToPortablePixMapFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
-    else if (o.pfmOut) check("save", SaveToPortablePixMapHDRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
-    else if (o.pngOut) check("save", SaveToPNGFile(dev, *image.GetImage(0, 0, 0), PNG_FLAGS_NONE, outFile.c_str()));
-    else if (o.exrOut) check("save", SaveToEXRFile(dev, *image.GetImage(0, 0, 0), outFile.c_str()));
-    else check("save", SaveToDDSFile(dev, image.GetImages(), image.GetImageCount(), info, DDS_FLAGS(ddsFlags), outFile.c_str()));
+    else check("save", Save(dev, o.outType, image, info, DDS_FLAGS(ddsFlags), tga20, outFile.c_str()));
     image.Release();
     std::printf("writing %s (%zux%zu", outFile.c_str(), info.width, info.height);
     if (info.dimension == TEX_DIMENSION_TEXTURE3D) std::printf("x%zu", info.depth);
@@ -659,17 +605,10 @@ int PrintInfo(const Options& o)
     int failures = 0;
     for (const std::string& f : o.inputs)
     {
-        auto hasExt = [&](const char* ext) { const size_t n = std::strlen(ext); return f.size() > n && !strcasecmp(f.c_str() + f.size() - n, ext); };
         TexMetadata m;
-        const HRESULT hr = hasExt(".hdr") ? GetMetadataFromHDRFile(f.c_str(), m) : hasExt(".tga") ? GetMetadataFromTGAFile(f.c_str(), TGA_FLAGS_NONE, m)
-                           : (hasExt(".ppm") || hasExt(".pfm") || hasExt(".phm")) ? GetMetadataFromPortablePixMapFile(f.c_str(), m)
-                           : hasExt(".png") ? GetMetadataFromPNGFile(f.c_str(), o.ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE, m)
-                           : hasExt(".exr") ? GetMetadataFromEXRFile(f.c_str(), m)
-                           : (hasExt(".jpg") || hasExt(".jpeg")) ? GetMetadataFromJPEGFile(f.c_str(), o.ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, m)
-                                                                                                   : GetMetadataFromDDSFile(f.c_str(), DDS_FLAGS(o.ddsRead), m);
+        const HRESULT hr = GetMetadata(f.c_str(), InputType(f), o.ReadFlags(false), m);
         if (FAILED(hr)) { std::printf("%s: FAILED (%08X)\n", f.c_str(), unsigned(hr)); ++failures; continue; }
-        const char* name = "";
-        for (const Name& n : kFormats) if (n.value == uint32_t(m.format)) { name = n.name; break; }
+        const char* name = FormatName(m.format, "");
         static const char* const alpha[] = { "unknown", "straight", "premultiplied", "opaque", "custom" };
         size_t images = 0, bytes = 0;
         for (size_t level = 0, w = m.width, h = m.height, d = m.depth; level < m.mipLevels; ++level)

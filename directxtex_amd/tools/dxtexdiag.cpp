@@ -12,7 +12,7 @@
 //   -dword -badtails -permissive -ignoremips -xlum   DDS reader flags    -nologo    -gpu <n>
 //   -timing       a last line with the bytes moved between host and device, as dxtexconv -timing counts them
 //   Not here: dumpbc (prints one block on the CPU) and dumpdds / info (dxtexconv -info).
-#include "../host/DirectXTexAMD.h"
+#include "tool_files.h"
 
 #include <algorithm>
 #include <cctype>
@@ -22,49 +22,19 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <strings.h>
 #include <sys/stat.h>
 #include <vector>
 
-using namespace DirectXTexAMD;
+using namespace tool;
 
 namespace
 {
-struct Name { const char* name; uint32_t value; };
-const Name kFormats[] = {
-    { "R32G32B32A32_FLOAT", 2 }, { "R32G32B32A32_UINT", 3 }, { "R32G32B32A32_SINT", 4 }, { "R32G32B32_FLOAT", 6 }, { "R32G32B32_UINT", 7 }, { "R32G32B32_SINT", 8 },
-    { "R16G16B16A16_FLOAT", 10 }, { "R16G16B16A16_UNORM", 11 }, { "R16G16B16A16_UINT", 12 }, { "R16G16B16A16_SNORM", 13 }, { "R16G16B16A16_SINT", 14 },
-    { "R32G32_FLOAT", 16 }, { "R32G32_UINT", 17 }, { "R32G32_SINT", 18 }, { "D32_FLOAT_S8X24_UINT", 20 }, { "R10G10B10A2_UNORM", 24 }, { "R10G10B10A2_UINT", 25 },
-    { "R11G11B10_FLOAT", 26 }, { "R8G8B8A8_UNORM", 28 }, { "R8G8B8A8_UNORM_SRGB", 29 }, { "R8G8B8A8_UINT", 30 }, { "R8G8B8A8_SNORM", 31 }, { "R8G8B8A8_SINT", 32 },
-    { "R16G16_FLOAT", 34 }, { "R16G16_UNORM", 35 }, { "R16G16_UINT", 36 }, { "R16G16_SNORM", 37 }, { "R16G16_SINT", 38 }, { "D32_FLOAT", 40 }, { "R32_FLOAT", 41 },
-    { "R32_UINT", 42 }, { "R32_SINT", 43 }, { "D24_UNORM_S8_UINT", 45 }, { "R8G8_UNORM", 49 }, { "R8G8_UINT", 50 }, { "R8G8_SNORM", 51 }, { "R8G8_SINT", 52 },
-    { "R16_FLOAT", 54 }, { "D16_UNORM", 55 }, { "R16_UNORM", 56 }, { "R16_UINT", 57 }, { "R16_SNORM", 58 }, { "R16_SINT", 59 }, { "R8_UNORM", 61 }, { "R8_UINT", 62 },
-    { "R8_SNORM", 63 }, { "R8_SINT", 64 }, { "A8_UNORM", 65 }, { "R1_UNORM", 66 }, { "R9G9B9E5_SHAREDEXP", 67 }, { "R8G8_B8G8_UNORM", 68 }, { "G8R8_G8B8_UNORM", 69 },
-    { "BC1_UNORM", 71 }, { "BC1_UNORM_SRGB", 72 }, { "BC2_UNORM", 74 }, { "BC2_UNORM_SRGB", 75 }, { "BC3_UNORM", 77 }, { "BC3_UNORM_SRGB", 78 }, { "BC4_UNORM", 80 },
-    { "BC4_SNORM", 81 }, { "BC5_UNORM", 83 }, { "BC5_SNORM", 84 }, { "B5G6R5_UNORM", 85 }, { "B5G5R5A1_UNORM", 86 }, { "B8G8R8A8_UNORM", 87 }, { "B8G8R8X8_UNORM", 88 },
-    { "R10G10B10_XR_BIAS_A2_UNORM", 89 }, { "B8G8R8A8_UNORM_SRGB", 91 }, { "B8G8R8X8_UNORM_SRGB", 93 }, { "BC6H_UF16", 95 }, { "BC6H_SF16", 96 }, { "BC7_UNORM", 98 },
-    { "BC7_UNORM_SRGB", 99 }, { "AYUV", 100 }, { "Y410", 101 }, { "Y416", 102 }, { "YUY2", 107 }, { "Y210", 108 }, { "Y216", 109 }, { "B4G4R4A4_UNORM", 115 },
-    { "R10G10B10_7E3_A2_FLOAT", 116 }, { "R10G10B10_6E4_A2_FLOAT", 117 }, { "R10G10B10_SNORM_A2_UNORM", 189 }, { "R4G4_UNORM", 190 }, { "A4B4G4R4_UNORM", 191 },
-    // texdiag's aliases (:99-110)
-    { "DXT1", 71 }, { "DXT2", 74 }, { "DXT3", 74 }, { "DXT4", 77 }, { "DXT5", 77 }, { "RGBA", 28 }, { "BGRA", 87 }, { "BGR", 88 }, { "FP16", 10 }, { "FP32", 2 },
-};
 const Name kFilters[] = {
     { "POINT", TEX_FILTER_POINT }, { "LINEAR", TEX_FILTER_LINEAR }, { "CUBIC", TEX_FILTER_CUBIC }, { "FANT", TEX_FILTER_FANT }, { "BOX", TEX_FILTER_BOX },
     { "TRIANGLE", TEX_FILTER_TRIANGLE }, { "POINT_DITHER", TEX_FILTER_POINT | TEX_FILTER_DITHER }, { "LINEAR_DITHER", TEX_FILTER_LINEAR | TEX_FILTER_DITHER },
     { "CUBIC_DITHER", TEX_FILTER_CUBIC | TEX_FILTER_DITHER }, { "TRIANGLE_DITHER", TEX_FILTER_TRIANGLE | TEX_FILTER_DITHER },
     { "POINT_DITHER_DIFFUSION", TEX_FILTER_POINT | TEX_FILTER_DITHER_DIFFUSION }, { "LINEAR_DITHER_DIFFUSION", TEX_FILTER_LINEAR | TEX_FILTER_DITHER_DIFFUSION },
 };
-
-bool lookup(const Name* t, size_t n, const char* s, uint32_t& out)
-{
-    for (size_t i = 0; i < n; ++i) if (!strcasecmp(t[i].name, s)) { out = t[i].value; return true; }
-    return false;
-}
-const char* FormatName(DXGI_FORMAT f)
-{
-    for (const Name& n : kFormats) if (n.value == uint32_t(f)) return n.name;
-    return "*UNKNOWN*";
-}
 
 struct Options
 {
@@ -76,6 +46,10 @@ struct Options
     int gpu = 0;
 };
 
+// the types this tool reads, and diff writes: all but the portable pixmaps. Any other input is read as a .dds.
+bool Takes(FileType t) { return t != FileType::UNKNOWN && t != FileType::PPM && t != FileType::PFM && t != FileType::PHM; }
+FileType InputType(const std::string& file) { const FileType t = FileTypeOf(file); return Takes(t) ? t : FileType::DDS; }
+
 int usage()
 {
     std::fprintf(stderr, "usage: dxtexdiag analyze [options] <files>\n"
@@ -84,12 +58,6 @@ int usage()
                          "options: -f <format> -if <filter> -c <hex colour> -t <threshold> -o <file> -y -l -nologo -timing -gpu <n>\n"
                          "         -dword -badtails -permissive -ignoremips -xlum\n");
     return 1;
-}
-
-bool hasExt(const std::string& s, const char* ext)
-{
-    const size_t n = std::strlen(ext);
-    return s.size() >= n && !strcasecmp(s.c_str() + s.size() - n, ext);
 }
 
 bool Parse(int argc, char** argv, Options& o)
@@ -111,12 +79,12 @@ bool Parse(int argc, char** argv, Options& o)
         if (a == "-f" || a == "--format")
         {
             if (!value(v)) return false;
-            if (!lookup(kFormats, sizeof(kFormats) / sizeof(kFormats[0]), v, o.format)) { std::fprintf(stderr, "invalid value specified with -f (%s)\n", v); return false; }
+            if (!lookup(kFormats, v, o.format)) { std::fprintf(stderr, "invalid value specified with -f (%s)\n", v); return false; }
         }
         else if (a == "-if" || a == "--image-filter")
         {
             if (!value(v)) return false;
-            if (!lookup(kFilters, sizeof(kFilters) / sizeof(kFilters[0]), v, o.filter)) { std::fprintf(stderr, "invalid value specified with -if (%s)\n", v); return false; }
+            if (!lookup(kFilters, v, o.filter)) { std::fprintf(stderr, "invalid value specified with -if (%s)\n", v); return false; }
         }
         else if (a == "-c" || a == "--diff-color")
         {
@@ -152,7 +120,7 @@ bool Parse(int argc, char** argv, Options& o)
     {
         if (o.output.empty()) { std::fprintf(stderr, "diff wants -o <out.dds | out.tga | out.hdr | out.png | out.jpg>\n"); return false; }
         if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
-        if (!hasExt(o.output, ".dds") && !hasExt(o.output, ".tga") && !hasExt(o.output, ".hdr") && !hasExt(o.output, ".png") && !hasExt(o.output, ".jpg") && !hasExt(o.output, ".jpeg") && !hasExt(o.output, ".exr"))
+        if (!Takes(FileTypeOf(o.output)))
         {
             std::fprintf(stderr, "the output file must be .dds, .tga or .hdr, or .png or .jpg\n");
             return false;
@@ -163,17 +131,14 @@ bool Parse(int argc, char** argv, Options& o)
     return true;
 }
 
-// Every file goes up once, at the bytes a texel it has on disk, and becomes the texture on the device: an .hdr file as its RGBE rows, a .tga
-// and a .dds as the file's own texels (the resident loaders). A planar file becomes its single-plane form there, as texdiag's loader makes
-// it (texdiag.cpp:3959-3972).
+// Every file goes up once, at the bytes a texel it has on disk, and becomes the texture on the device (tool_files.h: SourceFile); the readers'
+// flags are texdiag's (texdiag.cpp:599-608). A planar file becomes its single-plane form there, as texdiag's loader makes it
+// (texdiag.cpp:3959-3972).
 HRESULT Load(Device& dev, const Options& o, const std::string& file, TexMetadata& info, DeviceScratchImage& resident)
 {
-    HRESULT hr = hasExt(file, ".hdr") ? LoadFromHDRFile(dev, file.c_str(), &info, resident)
-               : hasExt(file, ".tga") ? LoadFromTGAFile(dev, file.c_str(), TGA_FLAGS_NONE, &info, resident)
-               : hasExt(file, ".png") ? LoadFromPNGFile(dev, file.c_str(), PNG_FLAGS_NONE, &info, resident)          // texdiag.cpp:605-608
-               : hasExt(file, ".exr") ? LoadFromEXRFile(dev, file.c_str(), &info, resident)          // texdiag.cpp's USE_OPENEXR branch
-               : (hasExt(file, ".jpg") || hasExt(file, ".jpeg")) ? LoadFromJPEGFile(dev, file.c_str(), JPEG_FLAGS_NONE, &info, resident)          // texdiag.cpp:599-602
-                                      : LoadFromDDSFile(dev, file.c_str(), DDS_FLAGS(o.ddsRead), &info, resident);
+    LoadFlags flags;
+    flags.dds = DDS_FLAGS(o.ddsRead);
+    HRESULT hr = tool::Load(dev, file.c_str(), InputType(file), flags, info, resident);
     if (FAILED(hr) || !IsPlanar(info.format)) return hr;
     DeviceScratchImage single;
     hr = ConvertToSinglePlane(dev, resident, single);
@@ -244,12 +209,6 @@ void Print(const AnalyzeBCData& d, DXGI_FORMAT fmt)
         break;
     default: break;
     }
-}
-
-int Fail(const char* what, HRESULT hr)
-{
-    std::printf("%s (%08X)\n", what, static_cast<unsigned int>(hr));
-    return 1;
 }
 
 int RunAnalyze(Device& dev, const Options& o)
@@ -381,26 +340,8 @@ int RunDiff(Device& dev, const Options& o)
     DeviceScratchImage map;
     hr = Difference(dev, side1.resident, side2.resident, TEX_FILTER_FLAGS(o.filter), DXGI_FORMAT(o.format), o.diffColor, o.threshold, map);
     if (FAILED(hr)) return Fail("Failed diffing images", hr);
-    // a .tga comes back as the file's rows the resident saver makes on the device, a .dds straight behind its header; an .hdr as the image,
-    // for the host codec
-    if (!hasExt(o.output, ".hdr"))
-    {
-        const Image* out = map.GetImage(0, 0, 0);
-        if (!out) return Fail("Failed diffing images", E_POINTER);
-        hr = hasExt(o.output, ".tga") ? SaveToTGAFile(dev, *out, TGA_FLAGS_NONE, o.output.c_str())
-           : hasExt(o.output, ".png") ? SaveToPNGFile(dev, *out, PNG_FLAGS_NONE, o.output.c_str())
-           : hasExt(o.output, ".exr") ? SaveToEXRFile(dev, *out, o.output.c_str())
-           : (hasExt(o.output, ".jpg") || hasExt(o.output, ".jpeg")) ? SaveToJPEGFile(dev, *out, JPEG_FLAGS_NONE, o.output.c_str()) : SaveToDDSFile(dev, *out, DDS_FLAGS_NONE, o.output.c_str());
-    }
-    else
-    {
-        ScratchImage diff;
-        hr = map.Download(diff);
-        if (FAILED(hr)) return Fail("Failed diffing images", hr);
-        const Image* out = diff.GetImage(0, 0, 0);
-        if (!out) return Fail("Failed diffing images", E_POINTER);
-        hr = SaveToHDRFile(*out, o.output.c_str());
-    }
+    // the map comes back as the file's rows the resident saver makes on the device, a .dds straight behind its header (tool_files.h: Save)
+    hr = Save(dev, FileTypeOf(o.output), map, map.GetMetadata(), DDS_FLAGS_NONE, nullptr, o.output.c_str());
     if (FAILED(hr)) return Fail(" FAILED writing the difference", hr);
     std::printf("Difference %s\n", o.output.c_str());
     return 0;

@@ -1,0 +1,197 @@
+// tool_files.h - what dxtexconv, dxtexdiag and dxtexassemble share about files: the file-type table, the format-name table, and one load /
+// metadata / save path over the host layer's codecs (DirectXTexAMD.h). Every codec's resident loader is "parse on the host, then upload", so
+// a file is a SourceFile in two phases: Parse opens no device (dxtexassemble reads every input before it creates one), Upload sends the
+// file's own bytes up and lets the host copy go. What a tool does with an extension it does not take is the tool's policy and stays there.
+#pragma once
+#include "../host/DirectXTexAMD.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <strings.h>
+
+namespace tool
+{
+using namespace DirectXTexAMD;
+
+// ---- file types: one row per extension; `ft` is the name dxtexconv's -ft takes for it (none: read only) ---------------------------------------
+enum class FileType { DDS, HDR, TGA, PPM, PFM, PHM, PNG, JPEG, EXR, UNKNOWN };
+struct FileTypeRow { FileType type; const char* ext; const char* ft; };
+const FileTypeRow kFileTypes[] = {
+    { FileType::DDS, ".dds", "dds" }, { FileType::HDR, ".hdr", "hdr" }, { FileType::TGA, ".tga", "tga" }, { FileType::PPM, ".ppm", "ppm" },
+    { FileType::PFM, ".pfm", "pfm" }, { FileType::PHM, ".phm", nullptr }, { FileType::PNG, ".png", "png" }, { FileType::JPEG, ".jpg", "jpg" },
+    { FileType::JPEG, ".jpeg", "jpeg" }, { FileType::EXR, ".exr", "exr" },
+};
+
+inline bool hasExt(const std::string& s, const char* ext)
+{
+    const size_t n = std::strlen(ext);
+    return s.size() >= n && !strcasecmp(s.c_str() + s.size() - n, ext);
+}
+inline FileType FileTypeOf(const std::string& name)
+{
+    for (const FileTypeRow& r : kFileTypes) if (hasExt(name, r.ext)) return r.type;
+    return FileType::UNKNOWN;
+}
+inline FileType FileTypeOfFt(const char* ft)
+{
+    for (const FileTypeRow& r : kFileTypes) if (r.ft && !strcasecmp(r.ft, ft)) return r.type;
+    return FileType::UNKNOWN;
+}
+inline const char* ExtensionOf(FileType type)
+{
+    for (const FileTypeRow& r : kFileTypes) if (r.type == type) return r.ext;
+    return "";
+}
+
+// ---- name tables --------------------------------------------------------------------------------------------------------------------------------
+struct Name { const char* name; uint32_t value; };
+template <size_t N> bool lookup(const Name (&t)[N], const char* s, uint32_t& out, bool numbers = false)
+{
+    for (const Name& n : t) if (!strcasecmp(n.name, s)) { out = n.value; return true; }
+    if (!numbers) return false;
+    char* end = nullptr; const unsigned long v = std::strtoul(s, &end, 0);
+    if (end && *end == 0 && end != s) { out = uint32_t(v); return true; }
+    return false;
+}
+
+// DXGI formats: the canonical names first (FormatName answers with the first row of a value), then the aliases texconv, texdiag and
+// texassemble share (texconv.cpp:420-440)
+const Name kFormats[] = {
+    { "R32G32B32A32_FLOAT", 2 }, { "R32G32B32A32_UINT", 3 }, { "R32G32B32A32_SINT", 4 }, { "R32G32B32_FLOAT", 6 }, { "R32G32B32_UINT", 7 }, { "R32G32B32_SINT", 8 },
+    { "R16G16B16A16_FLOAT", 10 }, { "R16G16B16A16_UNORM", 11 }, { "R16G16B16A16_UINT", 12 }, { "R16G16B16A16_SNORM", 13 }, { "R16G16B16A16_SINT", 14 },
+    { "R32G32_FLOAT", 16 }, { "R32G32_UINT", 17 }, { "R32G32_SINT", 18 }, { "D32_FLOAT_S8X24_UINT", 20 }, { "R10G10B10A2_UNORM", 24 }, { "R10G10B10A2_UINT", 25 },
+    { "R11G11B10_FLOAT", 26 }, { "R8G8B8A8_UNORM", 28 }, { "R8G8B8A8_UNORM_SRGB", 29 }, { "R8G8B8A8_UINT", 30 }, { "R8G8B8A8_SNORM", 31 }, { "R8G8B8A8_SINT", 32 },
+    { "R16G16_FLOAT", 34 }, { "R16G16_UNORM", 35 }, { "R16G16_UINT", 36 }, { "R16G16_SNORM", 37 }, { "R16G16_SINT", 38 }, { "D32_FLOAT", 40 }, { "R32_FLOAT", 41 },
+    { "R32_UINT", 42 }, { "R32_SINT", 43 }, { "D24_UNORM_S8_UINT", 45 }, { "R8G8_UNORM", 49 }, { "R8G8_UINT", 50 }, { "R8G8_SNORM", 51 }, { "R8G8_SINT", 52 },
+    { "R16_FLOAT", 54 }, { "D16_UNORM", 55 }, { "R16_UNORM", 56 }, { "R16_UINT", 57 }, { "R16_SNORM", 58 }, { "R16_SINT", 59 }, { "R8_UNORM", 61 }, { "R8_UINT", 62 },
+    { "R8_SNORM", 63 }, { "R8_SINT", 64 }, { "A8_UNORM", 65 }, { "R1_UNORM", 66 }, { "R9G9B9E5_SHAREDEXP", 67 }, { "R8G8_B8G8_UNORM", 68 }, { "G8R8_G8B8_UNORM", 69 },
+    { "BC1_UNORM", 71 }, { "BC1_UNORM_SRGB", 72 }, { "BC2_UNORM", 74 }, { "BC2_UNORM_SRGB", 75 }, { "BC3_UNORM", 77 }, { "BC3_UNORM_SRGB", 78 }, { "BC4_UNORM", 80 },
+    { "BC4_SNORM", 81 }, { "BC5_UNORM", 83 }, { "BC5_SNORM", 84 }, { "B5G6R5_UNORM", 85 }, { "B5G5R5A1_UNORM", 86 }, { "B8G8R8A8_UNORM", 87 }, { "B8G8R8X8_UNORM", 88 },
+    { "R10G10B10_XR_BIAS_A2_UNORM", 89 }, { "B8G8R8A8_UNORM_SRGB", 91 }, { "B8G8R8X8_UNORM_SRGB", 93 }, { "BC6H_UF16", 95 }, { "BC6H_SF16", 96 }, { "BC7_UNORM", 98 },
+    { "BC7_UNORM_SRGB", 99 }, { "AYUV", 100 }, { "Y410", 101 }, { "Y416", 102 }, { "YUY2", 107 }, { "Y210", 108 }, { "Y216", 109 }, { "B4G4R4A4_UNORM", 115 },
+    // the console formats, under texconv's names (texconv.cpp:422-425)
+    { "R10G10B10_7E3_A2_FLOAT", 116 }, { "R10G10B10_6E4_A2_FLOAT", 117 }, { "R10G10B10_SNORM_A2_UNORM", 189 }, { "R4G4_UNORM", 190 }, { "A4B4G4R4_UNORM", 191 },
+    { "DXT1", 71 }, { "DXT2", 74 }, { "DXT3", 74 }, { "DXT4", 77 }, { "DXT5", 77 }, { "RGBA", 28 }, { "BGRA", 87 }, { "BGR", 88 }, { "FP16", 10 }, { "FP32", 2 },
+};
+inline const char* FormatName(DXGI_FORMAT f, const char* fallback = "*UNKNOWN*")
+{
+    for (const Name& n : kFormats) if (n.value == uint32_t(f)) return n.name;
+    return fallback;
+}
+
+inline int Fail(const char* what, HRESULT hr) { std::printf("%s (%08X)\n", what, static_cast<unsigned int>(hr)); return 1; }
+
+// ---- reader flags, one per codec that takes any ---------------------------------------------------------------------------------------------------
+struct LoadFlags { DDS_FLAGS dds = DDS_FLAGS_NONE; TGA_FLAGS tga = TGA_FLAGS_NONE; PNG_FLAGS png = PNG_FLAGS_NONE; JPEG_FLAGS jpeg = JPEG_FLAGS_NONE; };
+// a .png headed for a BGR format is decoded as BGR (texconv.cpp:2213-2217, texassemble.cpp:1536-1544)
+inline PNG_FLAGS PngBgrFor(uint32_t f)
+{
+    return (f == DXGI_FORMAT_B8G8R8A8_UNORM || f == DXGI_FORMAT_B8G8R8X8_UNORM || f == DXGI_FORMAT_B8G8R8A8_UNORM_SRGB || f == DXGI_FORMAT_B8G8R8X8_UNORM_SRGB) ? PNG_FLAGS_BGR : PNG_FLAGS_NONE;
+}
+
+// ---- one input file, as the host half of its codec's resident loader leaves it: the bytes that go up are the file's own -----------------------
+//   .dds  the file itself, parsed: its payload goes up as it is and the row conversions of a legacy file run on the device
+//   .hdr  the RGBE rows (4 bytes a texel) and the exposure: the floats are made on the device
+//   .tga  the file's texels in the file's order (1 to 4 bytes each): swizzle, flips and the alpha rule run on the device
+//   .ppm .pfm .phm  the samples behind the text header: 3 to 4, the byte swap and the vertical flip run on the device
+//   .png  inflate and the row filters are byte-serial and run here; the unfiltered rows go up, the expansion to texels runs on the device
+//   .jpg  the Huffman walk runs here; the quantised coefficients go up, dequantisation, IDCT, upsampling and colour run on the device
+//   .exr  the header walk, inflate and the RLE packets run here; the chunks go up, the undo, the gather and the conversion run on the device
+struct SourceFile
+{
+    FileType type = FileType::UNKNOWN;
+    TexMetadata info;
+    DDSRawImage dds; float exposure = 1.f; Blob rgbe; TGA_FLAGS tgaFlags = TGA_FLAGS_NONE; TGARawImage tga;
+    PNMRawImage pnm; PNGRawImage png; JPEGRawImage jpeg; EXRRawImage exr;
+
+    // host only: no device is opened
+    HRESULT Parse(const char* file, FileType fileType, const LoadFlags& flags)
+    {
+        type = fileType;
+        HRESULT hr;
+        switch (type)
+        {
+        case FileType::DDS: hr = LoadFromDDSFileRaw(file, flags.dds, nullptr, dds); if (SUCCEEDED(hr)) info = dds.metadata; return hr;
+        case FileType::HDR: return LoadFromHDRFileRGBE(file, &info, exposure, rgbe);
+        case FileType::TGA:
+            tgaFlags = flags.tga;
+            hr = LoadFromTGAFileRaw(file, flags.tga, &info, tga);
+            if (SUCCEEDED(hr)) ApplyTGAAlphaRule(tga, flags.tga, info);          // a caller that prints `info` before the upload states the alpha mode
+            return hr;
+        case FileType::PPM: case FileType::PFM: case FileType::PHM: return LoadFromPortablePixMapFileRaw(file, &info, pnm);
+        case FileType::PNG: return LoadFromPNGFileRaw(file, flags.png, &info, png);
+        case FileType::JPEG: return LoadFromJPEGFileRaw(file, flags.jpeg, &info, jpeg);
+        case FileType::EXR: return LoadFromEXRFileRaw(file, &info, exr);
+        default: return HRESULT_E_NOT_SUPPORTED;
+        }
+    }
+    // the one transfer; the host copy is released whatever the outcome
+    HRESULT Upload(Device& dev, DeviceScratchImage& image)
+    {
+        HRESULT hr;
+        switch (type)
+        {
+        case FileType::DDS: hr = UploadDDSRaw(dev, dds, image); break;
+        case FileType::HDR: hr = UploadHDRRows(dev, info, exposure, rgbe, image); break;
+        case FileType::TGA: hr = UploadTGARaw(dev, info, tgaFlags, tga, image); break;
+        case FileType::PPM: case FileType::PFM: case FileType::PHM: hr = UploadPortablePixMapRaw(dev, info, pnm, image); break;
+        case FileType::PNG: hr = UploadPNGRaw(dev, info, png, image); break;
+        case FileType::JPEG: hr = UploadJPEGRaw(dev, info, jpeg, image); break;
+        case FileType::EXR: hr = UploadEXRRaw(dev, info, exr, image); break;
+        default: hr = HRESULT_E_NOT_SUPPORTED; break;
+        }
+        Release();
+        return hr;
+    }
+    void Release() { dds.Release(); rgbe.Release(); tga.Release(); pnm.Release(); png.Release(); jpeg.Release(); exr.Release(); }
+};
+
+// what LoadFrom*File(Device&, ...) does for every codec: parse, upload, and `info` only on success
+inline HRESULT Load(Device& dev, const char* file, FileType type, const LoadFlags& flags, TexMetadata& info, DeviceScratchImage& image)
+{
+    SourceFile source;
+    HRESULT hr = source.Parse(file, type, flags);
+    if (SUCCEEDED(hr)) hr = source.Upload(dev, image);
+    if (SUCCEEDED(hr)) info = source.info;
+    return hr;
+}
+
+// the header only
+inline HRESULT GetMetadata(const char* file, FileType type, const LoadFlags& flags, TexMetadata& info)
+{
+    switch (type)
+    {
+    case FileType::DDS: return GetMetadataFromDDSFile(file, flags.dds, info);
+    case FileType::HDR: return GetMetadataFromHDRFile(file, info);
+    case FileType::TGA: return GetMetadataFromTGAFile(file, flags.tga, info);
+    case FileType::PPM: case FileType::PFM: case FileType::PHM: return GetMetadataFromPortablePixMapFile(file, info);
+    case FileType::PNG: return GetMetadataFromPNGFile(file, flags.png, info);
+    case FileType::JPEG: return GetMetadataFromJPEGFile(file, flags.jpeg, info);
+    case FileType::EXR: return GetMetadataFromEXRFile(file, info);
+    default: return HRESULT_E_NOT_SUPPORTED;
+    }
+}
+
+// The one download, by the resident writers: what comes down is the file's own rows (RGBE, TGA texels, PNM samples, PNG rows, JPEG
+// coefficients, EXR half planes), made on the device, or a .dds payload straight behind its header. A .dds takes every image with `info`
+// and `ddsFlags`; every other type takes image (0, 0, 0). tga20: write the TGA 2.0 extension area from this metadata.
+inline HRESULT Save(Device& dev, FileType type, const DeviceScratchImage& image, const TexMetadata& info, DDS_FLAGS ddsFlags, const TexMetadata* tga20, const char* file)
+{
+    if (type == FileType::DDS) return SaveToDDSFile(dev, image.GetImages(), image.GetImageCount(), info, ddsFlags, file);
+    const Image* first = image.GetImage(0, 0, 0);
+    if (!first) return E_POINTER;
+    switch (type)
+    {
+    case FileType::HDR: return SaveToHDRFile(dev, *first, file);
+    case FileType::TGA: return SaveToTGAFile(dev, *first, TGA_FLAGS_NONE, file, tga20);
+    case FileType::PPM: return SaveToPortablePixMapFile(dev, *first, file);
+    case FileType::PFM: return SaveToPortablePixMapHDRFile(dev, *first, file);
+    case FileType::PNG: return SaveToPNGFile(dev, *first, PNG_FLAGS_NONE, file);
+    case FileType::JPEG: return SaveToJPEGFile(dev, *first, JPEG_FLAGS_NONE, file);
+    case FileType::EXR: return SaveToEXRFile(dev, *first, file);
+    default: return HRESULT_E_NOT_SUPPORTED;          // .phm: there is no writer
+    }
+}
+} // namespace tool

@@ -91,6 +91,34 @@ def test_dxtexassemble_cube_from_hdr_faces(tmp_path, oracle):
     assert hr == 0 and np.array_equal(got, want)
 
 
+@pytest.mark.parametrize("w,h", [(20, 12), (7, 3)])            # run-length rows, and flat ones (narrower than 8)
+def test_dxtexdiag_diff_writes_an_hdr_map_as_rgbe(tmp_path, oracle, w, h):
+    """diff -o d.hdr saves the resident map like every other output: the file is what dxtexconv -ft hdr (and the reference's writer) makes of
+    the same map saved as .dds, and 4 bytes a texel come down. A map in a format the .hdr writer refuses fails as the host writer did."""
+    a, b = tmp_path / "a.dds", tmp_path / "b.dds"
+    oracle.ref_save_dds(_image(20, w, h), w, h, R.RGBA32F).tofile(a)
+    oracle.ref_save_dds(_image(21, w, h), w, h, R.RGBA32F).tofile(b)
+    hdr, dds, conv = tmp_path / "d.hdr", tmp_path / "d.dds", tmp_path / "conv.hdr"
+    txt = _tool("dxtexdiag", ["diff", "-nologo", "-timing", "-f", "R32G32B32A32_FLOAT", a, b, "-o", hdr])
+    _tool("dxtexdiag", ["diff", "-nologo", "-f", "R32G32B32A32_FLOAT", a, b, "-o", dds])
+    _tool("dxtexconv", ["-nologo", "-m", "1", "-ft", "hdr", "-o", conv, dds])
+    got = np.fromfile(hdr, np.uint8)
+    assert np.array_equal(got, np.fromfile(conv, np.uint8))
+    meta, px = oracle.ref_load_dds(np.fromfile(dds, np.uint8))
+    assert (meta["width"], meta["height"], meta["format"]) == (w, h, R.RGBA32F)
+    rhr, ref = oracle.ref_save_hdr(np.asarray(px, np.uint8)[:w * h * 16], w, h, R.RGBA32F, w * 16)
+    assert rhr == 0 and np.array_equal(got, ref)
+    up, down = _moved(txt)
+    print(f"{w}x{h}: host -> device {up} bytes, device -> host {down} bytes")
+    assert up == 2 * w * h * 16, txt
+    assert w * h * 4 <= down <= w * h * 4 + 8, txt            # the RGBE rows, not the map's 16 bytes a texel
+    # the default map format, B8G8R8A8_UNORM: the .hdr writer's refusal, and no file
+    refused = tmp_path / "refused.hdr"
+    r = subprocess.run([os.path.join(LIB, "dxtexdiag"), "diff", "-nologo", str(a), str(b), "-o", str(refused)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 1 and "80070032" in r.stdout + r.stderr, r.stdout + r.stderr
+    assert not refused.exists()
+
+
 def test_dxtexdiag_analyze_of_an_hdr_file(tmp_path, oracle):
     """analyze loads an .hdr file with the resident loader: its report is that of a float DDS holding the reference reader's floats."""
     src, dds = tmp_path / "sky.hdr", tmp_path / "sky.dds"
