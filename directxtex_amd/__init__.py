@@ -8,4 +8,4 @@ or PyTorch fallback: if the library is missing, importing :mod:`directxtex_amd.c
 from .formats import *  # noqa: F401,F403
 from . import capi  # noqa: F401
 from .capi import (Context, DxtexError, Image, ImageStats, Rect, Transform, compute_pitch, device_image, planar_to_single, is_compressed, bits_per_pixel, library_path,  # noqa: F401
-                   make_transform, parse_swizzle_mask, JpegFrame, JpegComponent, jpeg_frame, jpeg_coefficient_count, ExrChunk, ExrChannel)
+                   make_transform, parse_swizzle_mask, JpegFrame, JpegComponent, jpeg_frame, jpeg_coefficient_count, ExrChunk, ExrChannel, TiffSegment, TiffLayout)

@@ -73,6 +73,26 @@ class ExrChannel(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint32), ("type", ctypes.c_uint32)]
 
 
+class TiffSegment(ctypes.Structure):
+    """dxtex_tiff_segment (include/dxtex_amd.h): one strip or tile of a .tif file's expanded stream."""
+    _fields_ = [("offset", ctypes.c_uint64), ("firstRow", ctypes.c_uint32), ("rows", ctypes.c_uint32), ("firstCol", ctypes.c_uint32), ("cols", ctypes.c_uint32),
+                ("rowBytes", ctypes.c_uint32), ("plane", ctypes.c_uint32)]
+
+
+class TiffLayout(ctypes.Structure):
+    """dxtex_tiff_layout (include/dxtex_amd.h): the file as the kernels see it."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("width", "height", "bits", "samples", "kind", "predictor", "bigEndian", "planar", "whiteIsZero", "opaque")]
+
+
+def _tiff_tables(segments, layout, palette):
+    """(TiffSegment array or None, count, TiffLayout or None, 256 words or None) from segments = [(offset, first row, rows, first column,
+    columns, row bytes, plane)], layout = the ten fields of TiffLayout in order and palette = up to 256 words; None stays a null pointer."""
+    seg = None if segments is None else (TiffSegment * max(1, len(segments)))(*[TiffSegment(*s) for s in segments])
+    lay = None if layout is None else TiffLayout(*layout)
+    pal = None if palette is None else (ctypes.c_uint32 * 256)(*[int(w) for w in palette])
+    return seg, (0 if segments is None else len(segments)), lay, pal
+
+
 def _exr_tables(chunks, channels):
     """(ExrChunk array or None, count, ExrChannel[4] or None) from chunks = [(offset, bytes, first row, rows, coded)] and channels =
     [(offset, type)] * 4 for R, G, B, A; None stays a null pointer."""
@@ -220,6 +240,10 @@ _SIGS = {
     "dxtex_exr_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_exr_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_exr_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_tiff_unpack": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, _P(Image)]),
+    "dxtex_tiff_unpack_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, _P(Image)]),
+    "dxtex_tiff_pack": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
+    "dxtex_tiff_pack_device": (ctypes.c_int32, [_ctx_p, _P(Image), ctypes.c_void_p, ctypes.c_size_t]),
     "dxtex_generate_mips3d": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_generate_mips3d_device": (ctypes.c_int32, [_ctx_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_premultiply_alpha": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
@@ -1020,6 +1044,42 @@ class Context:
     def exr_pack_device(self, src, scanlines_ptr, scanline_bytes):
         """dxtex_exr_pack_device: the device Image `src` -> the writer's scanlines at a device pointer, asynchronous on the stream."""
         self._check(self._lib.dxtex_exr_pack_device(self._h, ctypes.byref(src), scanlines_ptr, scanline_bytes), "exr_pack_device")
+
+    # -- TIFF strips and tiles (everything behind LZW, PackBits and inflate of the .tif reader, the writer's rows) ---------------------------------
+    def tiff_unpack(self, stream, segments, layout, fmt, palette=None, row_pitch=None, out=None):
+        """dxtex_tiff_unpack: the expanded stream (host bytes), its segments [(offset, first row, rows, first column, columns, row bytes,
+        plane)] and the layout (the ten fields of TiffLayout) -> pixels of `fmt` as a numpy uint8 buffer with `row_pitch` bytes a row,
+        default tight. out: the buffer to unpack into, default a zeroed one."""
+        stream = np.ascontiguousarray(stream, np.uint8)
+        width, height = layout[0], layout[1]
+        pitch = compute_pitch(fmt, width, height)[0] if row_pitch is None else row_pitch
+        if out is None:
+            out = np.zeros(pitch * height, np.uint8)
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.nbytes >= pitch * height
+        dst = Image(width, height, fmt, pitch, pitch * height, out.ctypes.data)
+        seg, count, lay, pal = _tiff_tables(segments, layout, palette)
+        self._check(self._lib.dxtex_tiff_unpack(self._h, stream.ctypes.data, stream.nbytes, seg, count, ctypes.byref(lay), pal, ctypes.byref(dst)), "tiff_unpack")
+        return out
+
+    def tiff_unpack_device(self, stream_ptr, stream_bytes, segments, layout, dst, palette=None):
+        """dxtex_tiff_unpack_device: the stream at a device pointer (its rows are undone in place where the file has a predictor) -> the
+        device Image `dst` (device_image), asynchronous on the stream."""
+        seg, count, lay, pal = _tiff_tables(segments, layout, palette)
+        self._check(self._lib.dxtex_tiff_unpack_device(self._h, stream_ptr, stream_bytes, seg, count, None if lay is None else ctypes.byref(lay), pal,
+                                                       None if dst is None else ctypes.byref(dst)), "tiff_unpack_device")
+
+    def tiff_pack(self, pixels, width, height, fmt, row_pitch=None, out=None):
+        """dxtex_tiff_pack: one image (host pixels) -> the writer's rows, tight, as a numpy uint8 buffer (or the front of `out`)."""
+        pixels = np.ascontiguousarray(pixels)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        if out is None:
+            out = np.zeros(width * height * 16, np.uint8)
+        self._check(self._lib.dxtex_tiff_pack(self._h, ctypes.byref(src), out.ctypes.data, out.nbytes), "tiff_pack")
+        return out
+
+    def tiff_pack_device(self, src, rows_ptr, rows_bytes):
+        """dxtex_tiff_pack_device: the device Image `src` -> the writer's rows at a device pointer, asynchronous on the stream."""
+        self._check(self._lib.dxtex_tiff_pack_device(self._h, ctypes.byref(src), rows_ptr, rows_bytes), "tiff_pack_device")
 
     # -- DDS texels (the per-texel half of the .dds codec) -------------------------------------------------------------------------------
     @staticmethod

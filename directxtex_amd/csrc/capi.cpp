@@ -10,6 +10,7 @@
 #include "dxtex_png.h"
 #include "dxtex_jpeg.h"
 #include "dxtex_exr.h"
+#include "dxtex_tiff.h"
 #include "dxtex_nmap.h"
 #include "dxtex_transform.h"
 #include "dxtex_rotate.h"
@@ -2132,6 +2133,130 @@ dxtex_hresult dxtex_exr_unpack(dxtex_ctx* ctx, const void* stream, size_t stream
 
 dxtex_hresult dxtex_exr_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes) { return exr_pack(ctx, src, scanlines, scanlineBytes, true); }
 dxtex_hresult dxtex_exr_pack(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes) { return exr_pack(ctx, src, scanlines, scanlineBytes, false); }
+
+namespace
+{
+static_assert(DXTEX_TIFF_GREY1 == TIFF_GREY1 && DXTEX_TIFF_GREY32F == TIFF_GREY32F && DXTEX_TIFF_PAL1 == TIFF_PAL1 && DXTEX_TIFF_PAL8 == TIFF_PAL8 && DXTEX_TIFF_RGB8 == TIFF_RGB8 &&
+              DXTEX_TIFF_RGBA16 == TIFF_RGBA16 && DXTEX_TIFF_RGBA32F == TIFF_RGBA32F && TIFF_KINDS == 14u, "dxtex_tiff.h's kinds are the public ones");
+static_assert(sizeof(dxtex_tiff_segment) == sizeof(TiffSegment) && sizeof(dxtex_tiff_layout) == sizeof(TiffLayout), "dxtex_tiff.h's descriptors are the public ones");
+
+// The checks of dxtex_tiff_unpack[_device], in the order include/dxtex_amd.h states. *l and *list = what the launchers take; *copies = the
+// file is its image already and every segment a run of whole rows.
+dxtex_hresult check_tiff_unpack(dxtex_ctx* ctx, const void* stream, size_t streamBytes, const dxtex_tiff_segment* segments, size_t count, const dxtex_tiff_layout* layout,
+                                const uint32_t* palette, const dxtex_image* dst, TiffLayout* l, std::vector<TiffSegment>* list, bool* copies)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!stream) return fail(ctx, DXTEX_E_POINTER, "null stream");
+    if (!segments) return fail(ctx, DXTEX_E_POINTER, "null segment descriptors");
+    if (!layout) return fail(ctx, DXTEX_E_POINTER, "null layout");
+    if (!dst) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!dst->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (layout->kind < TIFF_KINDS && tiff_is_palette(layout->kind) && !palette) return fail(ctx, DXTEX_E_POINTER, "this TIFF kind needs a palette");
+    if (!count) return fail(ctx, DXTEX_E_INVALIDARG, "no segments");
+    if (!dst->width || !dst->height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    if (dst->width > 0x0FFFFFFFull || dst->height > 0x0FFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    if (dst->width != layout->width || dst->height != layout->height) return fail(ctx, DXTEX_E_INVALIDARG, "the image is not the layout's size");
+    if (layout->kind >= TIFF_KINDS) return fail(ctx, DXTEX_E_INVALIDARG, "unknown TIFF kind");
+    const TiffKindRow kind = tiff_kind_row(layout->kind);
+    if (layout->bits != kind.bits || layout->samples != kind.samples) return fail(ctx, DXTEX_E_INVALIDARG, "bits or samples are not the kind's");
+    if (layout->predictor < 1u || layout->predictor > 3u) return fail(ctx, DXTEX_E_INVALIDARG, "predictor 1, 2 or 3");
+    if (!tiff_predictor_fits(layout->predictor, layout->bits)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "predictor 2 takes 8- or 16-bit samples, predictor 3 32-bit ones");
+    if (!tiff_unpacks_into(layout->kind, dst->format)) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "this TIFF kind does not unpack into this format");
+    *l = TiffLayout{ layout->width, layout->height, layout->bits, layout->samples, layout->kind, layout->predictor, layout->bigEndian ? 1u : 0u,
+                     layout->planar && layout->samples > 1u ? 1u : 0u, layout->whiteIsZero ? 1u : 0u, layout->opaque && layout->samples == 4u ? 1u : 0u };
+    const uint32_t rowSamples = l->planar ? 1u : l->samples, planes = l->planar ? l->samples : 1u;
+    const size_t rowBytes = dst->width * kind.imageBytes;
+    *copies = tiff_is_native(*l);
+    uint64_t end = 0;
+    list->resize(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_tiff_segment& s = segments[i];
+        if (!s.rows || !s.cols || s.firstRow >= l->height || s.rows > l->height - s.firstRow || s.firstCol >= l->width || s.cols > l->width - s.firstCol || s.plane >= planes)
+            return fail(ctx, DXTEX_E_INVALIDARG, "a segment descriptor leaves the image");
+        if (s.rowBytes < tiff_row_bytes(s.cols, rowSamples, l->bits) || (l->bits > 8u && s.rowBytes % (l->bits / 8u)))
+            return fail(ctx, DXTEX_E_INVALIDARG, "a segment's rowBytes is smaller than its columns need");
+        if (s.offset > streamBytes || uint64_t(s.rows) * s.rowBytes > streamBytes - s.offset) return fail(ctx, DXTEX_E_INVALIDARG, "a segment descriptor leaves the stream");
+        if (s.offset < end) return fail(ctx, DXTEX_E_INVALIDARG, "segment descriptors overlap or are not in stream order");
+        end = s.offset + uint64_t(s.rows) * s.rowBytes;
+        *copies = *copies && s.firstCol == 0 && s.cols == l->width && s.rowBytes == rowBytes;
+        (*list)[i] = TiffSegment{ s.offset, s.firstRow, s.rows, s.firstCol, s.cols, s.rowBytes, s.plane };
+    }
+    return check_stream_image(ctx, "stream", stream, streamBytes, dst, rowBytes);
+}
+
+// what both forms queue: row copies for a file that is its image, else tiff_undo in place and tiff_texels
+dxtex_hresult submit_tiff_unpack(dxtex_ctx* ctx, uint8_t* stream, const std::vector<TiffSegment>& list, const TiffLayout& l, const uint32_t* palette, const dxtex_image& dst, bool copies)
+{
+    if (copies)
+    {
+        for (const TiffSegment& s : list)
+            HIP_TRY(ctx, hipMemcpy2DAsync(dst.pixels + size_t(s.firstRow) * dst.rowPitch, dst.rowPitch, stream + s.offset, s.rowBytes, s.rowBytes, s.rows, hipMemcpyDeviceToDevice, ctx->stream));
+        return DXTEX_S_OK;
+    }
+    uint32_t table[256] = {};
+    if (palette) std::copy(palette, palette + 256, table);
+    hipError_t e = launch_tiff_undo(stream, list.data(), list.size(), l, ctx->stream, marks_of(ctx));
+    if (e == hipSuccess) e = launch_tiff_texels(stream, list.data(), list.size(), l, palette ? table : nullptr, view_of(dst), ctx->stream, marks_of(ctx));
+    return launched(ctx, e);
+}
+
+dxtex_hresult tiff_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes, bool device)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src) return fail(ctx, DXTEX_E_POINTER, "null image");
+    if (!src->pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!rows) return fail(ctx, DXTEX_E_POINTER, "null rows");
+    if (!src->width || !src->height) return fail(ctx, DXTEX_E_INVALIDARG, "empty image");
+    if (src->width > 0x0FFFFFFFull || src->height > 0x0FFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    const TiffSource source = tiff_pack_source(src->format);
+    if (!source.bits) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "no TIFF writer case for this format");
+    const size_t fileRow = src->width * source.fileBytes, need = fileRow * src->height, rowBytes = src->width * source.imageBytes;
+    if (rowsBytes < need) return fail(ctx, DXTEX_E_INVALIDARG, "fewer bytes of rows than the file's texels");
+    const dxtex_hresult hr = check_stream_image(ctx, "rows", rows, need, src, rowBytes);
+    if (hr != DXTEX_S_OK) return hr;
+    auto pack = [&](const dxtex_image& s, uint8_t* out) -> dxtex_hresult
+    {
+        if (source.bgr) return launched(ctx, launch_tiff_pack(view_of(s), out, ctx->stream, marks_of(ctx)));
+        HIP_TRY(ctx, hipMemcpy2DAsync(out, fileRow, s.pixels, s.rowPitch, fileRow, s.height, hipMemcpyDeviceToDevice, ctx->stream));          // the rows are the file's: no kernel
+        return DXTEX_S_OK;
+    };
+    if (device) return run_timed(ctx, [&] { return pack(*src, static_cast<uint8_t*>(rows)); });
+    return run_staged(ctx, src->pixels, src->rowPitch * (src->height - 1) + rowBytes, rows, need, [&](uint8_t* in, uint8_t* out) { return pack(with_pixels(*src, in), out); });
+}
+} // namespace
+
+dxtex_hresult dxtex_tiff_unpack_device(dxtex_ctx* ctx, void* stream, size_t streamBytes, const dxtex_tiff_segment* segments, size_t segmentCount,
+                                       const dxtex_tiff_layout* layout, const uint32_t* palette, const dxtex_image* dst)
+{
+    TiffLayout l; std::vector<TiffSegment> list; bool copies;
+    const dxtex_hresult hr = check_tiff_unpack(ctx, stream, streamBytes, segments, segmentCount, layout, palette, dst, &l, &list, &copies);
+    if (hr != DXTEX_S_OK) return hr;
+    return run_timed(ctx, [&] { return submit_tiff_unpack(ctx, static_cast<uint8_t*>(stream), list, l, palette, *dst, copies); });
+}
+
+dxtex_hresult dxtex_tiff_unpack(dxtex_ctx* ctx, const void* stream, size_t streamBytes, const dxtex_tiff_segment* segments, size_t segmentCount,
+                                const dxtex_tiff_layout* layout, const uint32_t* palette, const dxtex_image* dst)
+{
+    TiffLayout l; std::vector<TiffSegment> list; bool copies;
+    const dxtex_hresult hr = check_tiff_unpack(ctx, stream, streamBytes, segments, segmentCount, layout, palette, dst, &l, &list, &copies);
+    if (hr != DXTEX_S_OK) return hr;
+    // the stream goes up as it is; the rows are written tight (rounded up to 16 bytes) into the output staging and only each row's texels
+    // come down, through the caller's pitch
+    const size_t rowBytes = size_t(l.width) * tiff_kind_row(l.kind).imageBytes, pitch = (rowBytes + 15) & ~size_t(15);
+    StagingPlan plan;
+    plan.upload(stream, plan.in(streamBytes), streamBytes);
+    plan.download(dst->pixels, dst->rowPitch, plan.out(pitch, dst->height), 0, pitch, rowBytes, dst->height);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
+    {
+        dxtex_image staged = with_pixels(*dst, out);
+        staged.rowPitch = pitch; staged.slicePitch = pitch * dst->height;
+        return submit_tiff_unpack(ctx, in, list, l, palette, staged, copies);
+    });
+}
+
+dxtex_hresult dxtex_tiff_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes) { return tiff_pack(ctx, src, rows, rowsBytes, true); }
+dxtex_hresult dxtex_tiff_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes) { return tiff_pack(ctx, src, rows, rowsBytes, false); }
 
 namespace
 {

@@ -166,6 +166,18 @@ hipError_t launch_exr_texels(const uint8_t* stream, const ExrChunk* chunks, size
                              hipStream_t stream_, KernelMarks* marks = nullptr);
 hipError_t launch_exr_pack(const ImgView& src, int source, uint8_t* stream, hipStream_t stream_, KernelMarks* marks = nullptr);
 
+// TIFF strips and tiles (tiff.hip; the rules are in dxtex_tiff.h). The caller has checked every descriptor against the stream, the layout
+// and the image. launch_tiff_undo runs the predictor of every row of every segment in place (nothing for predictor 1);
+// launch_tiff_texels then writes every segment's texels into dst, whose format is the kind's (palette: 256 words for the palette kinds).
+// launch_tiff_pack: the writer's tight rows from level 0 of a B8G8R8A8 (4 bytes a texel) or B8G8R8X8 (3) image; the writer's other
+// sources are row copies.
+struct TiffSegment;
+struct TiffLayout;
+hipError_t launch_tiff_undo(uint8_t* stream, const TiffSegment* segments, size_t count, const TiffLayout& layout, hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_tiff_texels(const uint8_t* stream, const TiffSegment* segments, size_t count, const TiffLayout& layout, const uint32_t* palette, const ImgView& dst,
+                              hipStream_t stream_, KernelMarks* marks = nullptr);
+hipError_t launch_tiff_pack(const ImgView& src, uint8_t* rows, hipStream_t stream_, KernelMarks* marks = nullptr);
+
 // CopyRectangle: `count` resolved rectangles (dxtex_copyrect.h; the caller has checked every bound), kCopyBatchMax of them per launch.
 // texassemble's merge of a (any loadable format) and b (R32G32B32A32_FLOAT, 16-byte aligned rows) into dst, whose rows are as for
 // launch_normal_map; the size is a's.

@@ -920,4 +920,81 @@ HRESULT LoadFromEXRFile(Device& device, const char* szFile, TexMetadata* metadat
 HRESULT UploadEXRRaw(Device& device, const TexMetadata& metadata, const EXRRawImage& raw, DeviceScratchImage& image) noexcept;
 HRESULT SaveToEXRMemory(Device& device, const Image& deviceImage, Blob& blob) noexcept;
 HRESULT SaveToEXRFile(Device& device, const Image& deviceImage, const char* szFile) noexcept;
+
+// ---- TIFF, which the reference reads and writes through WIC (DirectXTexWIC.cpp: WIC_CODEC_TIFF; texconv's -ft tif). No library is
+// linked: the header, the IFD walk, LZW, PackBits and - through DirectXTexAMD_Inflate.h - inflate are this project's own code; what
+// happens to a strip's or a tile's bytes after that is csrc/dxtex_tiff.h's. Accepted: classic TIFF (magic 42), II and MM, the first IFD;
+// strips (any RowsPerStrip) and tiles; PlanarConfiguration 1 and 2; Compression 1, 5 (LZW, MSB-first with the early code-width change), 8
+// and 32946 (deflate), 32773 (PackBits); Predictor 1, 2 for 8- and 16-bit samples, 3 for 32-bit floats; SampleFormat 1 (4 reads as 1) for
+// integers and 3 for 32 bits; FillOrder 1; the defaults of the TIFF 6.0 text. Kinds and formats follow g_WICFormats / g_WICConvert /
+// DetermineFormat without WIC_FLAGS_ALLOW_MONO: bilevel, grey 4 and grey 8 are R8_UNORM (multiplied out, WhiteIsZero inverted), grey 16
+// R16_UNORM, grey float R32_FLOAT, palette 1 / 4 / 8 R8G8B8A8_UNORM (entry >> 8, alpha 0xff), RGB 8 and RGBA 8 R8G8B8A8_UNORM, RGB 16 and
+// RGBA 16 R16G16B16A16_UNORM, RGB float R32G32B32_FLOAT, RGBA float R32G32B32A32_FLOAT; a kind without alpha is TEX_ALPHA_MODE_OPAQUE. An
+// 8-bit colour file is _SRGB when its Exif IFD (tag 34665) holds ColorSpace (40961) = 1, or under TIFF_FLAGS_DEFAULT_SRGB when it holds
+// none; never under TIFF_FLAGS_IGNORE_SRGB. Null arguments are E_INVALIDARG, a missing file HRESULT_ERROR_FILE_NOT_FOUND, and E_FAIL is:
+// a bad header, truncation, an offset or count outside the file, a missing needed tag, a segment that expands to fewer bytes than its rows
+// need. Departures (WIC is not there to run against, so these are this project's rules; tests/tiff_ref.py restates them):
+//   1. The Memory forms exist.
+//   2. HRESULT_E_NOT_SUPPORTED for BigTIFF; JPEG, CCITT and any other compression; YCbCr, CMYK, CIELab and any other photometric; signed
+//      integers, 16- and 64-bit floats; bits other than 1 / 4 / 8 / 16 / 32 or unequal across samples; grey plus alpha; more than one
+//      extra sample; FillOrder 2; old-style LSB-first LZW; predictor 2 on 1-, 4- or 32-bit samples (and 3 on anything but 32-bit floats);
+//      WhiteIsZero floats.
+//   3. Associated alpha (ExtraSamples 1) keeps the file's samples and sets TEX_ALPHA_MODE_PREMULTIPLIED, where WIC would divide. An
+//      unspecified fourth sample (ExtraSamples 0 or absent) reads as opaque: alpha forced to its maximum, TEX_ALPHA_MODE_OPAQUE.
+//   4. Orientation and further IFDs are ignored, and so is Predictor where the compression is 1 or 32773: it belongs to the LZW and deflate
+//      coders, and libtiff reads such files as they are.
+//   5. The writer stores uncompressed: II, one IFD, one strip, chunky; ExtraSamples 2 for alpha, resolution 72 / 72 and Software
+//      "DirectXTex" as the reference's EncodeImage / EncodeMetadata set; Exif ColorSpace 1 for an _SRGB format or under
+//      TIFF_FLAGS_FORCE_SRGB, never under TIFF_FLAGS_FORCE_LINEAR. It takes R8_UNORM, R16_UNORM, R32_FLOAT, R8G8B8A8_UNORM[_SRGB],
+//      R16G16B16A16_UNORM, R32G32B32_FLOAT, R32G32B32A32_FLOAT, B8G8R8A8_UNORM[_SRGB] (written RGBA) and B8G8R8X8_UNORM[_SRGB] (written
+//      RGB, 3 bytes); every other format is HRESULT_E_NOT_SUPPORTED. ------------------------------------------------------------------------
+enum TIFF_FLAGS : uint32_t
+{
+    TIFF_FLAGS_NONE = 0,
+    TIFF_FLAGS_IGNORE_SRGB = 0x1,        // the Exif colour space does not choose the format: it is the linear one
+    TIFF_FLAGS_DEFAULT_SRGB = 0x2,       // an 8-bit colour file that names no colour space is _SRGB
+    TIFF_FLAGS_FORCE_SRGB = 0x20,        // the writer stores Exif ColorSpace 1 whatever the format
+    TIFF_FLAGS_FORCE_LINEAR = 0x40,      // the writer stores no colour space whatever the format
+};
+inline TIFF_FLAGS operator|(TIFF_FLAGS a, TIFF_FLAGS b) noexcept { return TIFF_FLAGS(uint32_t(a) | uint32_t(b)); }
+HRESULT GetMetadataFromTIFFMemory(const void* pSource, size_t size, TIFF_FLAGS flags, TexMetadata& metadata) noexcept;
+HRESULT GetMetadataFromTIFFFile(const char* szFile, TIFF_FLAGS flags, TexMetadata& metadata) noexcept;
+HRESULT LoadFromTIFFMemory(const void* pSource, size_t size, TIFF_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT LoadFromTIFFFile(const char* szFile, TIFF_FLAGS flags, TexMetadata* metadata, ScratchImage& image) noexcept;
+HRESULT SaveToTIFFMemory(const Image& image, TIFF_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToTIFFFile(const Image& image, TIFF_FLAGS flags, const char* szFile) noexcept;
+// The reader's byte-serial half, which needs no device: the header, the IFD walk, every refusal, LZW, PackBits and inflate. What comes
+// back is ONE STREAM of the segments' expanded bytes - still predictor-coded, in the file's byte order, at the file's bits per sample -
+// and dxtex_tiff_unpack's other arguments: a descriptor per segment (strips that follow one another in the stream and in the image share
+// one; every other segment starts on a multiple of 16 bytes), the layout and the palette's 256 words. GetMetadata* stop behind the IFD. On
+// failure `raw` is released.
+struct TIFFRawImage
+{
+    struct Segment { uint64_t offset; uint32_t firstRow, rows, firstCol, cols, rowBytes, plane; };          // dxtex_tiff_segment's layout
+    struct Layout { uint32_t width, height, bits, samples, kind, predictor, bigEndian, planar, whiteIsZero, opaque; };          // dxtex_tiff_layout's
+    uint32_t compression = 0;                    // the file's code
+    Layout layout = {};
+    uint32_t palette[256] = {};                  // for the palette kinds: the words tiff_texels stores
+    std::unique_ptr<Segment[]> segments;
+    size_t segmentCount = 0;
+    size_t storedBytes = 0;                      // of the file's segments as stored
+    const uint8_t* stream = nullptr;             // into `storage`
+    size_t streamBytes = 0;
+    Blob storage;
+    void Release() noexcept;
+};
+HRESULT LoadFromTIFFMemoryRaw(const void* pSource, size_t size, TIFF_FLAGS flags, TexMetadata* metadata, TIFFRawImage& raw) noexcept;
+HRESULT LoadFromTIFFFileRaw(const char* szFile, TIFF_FLAGS flags, TexMetadata* metadata, TIFFRawImage& raw) noexcept;
+// Resident forms: the stream crosses PCIe as it leaves the decoder - 3 bytes a texel for RGB 8, one bit for bilevel - and the predictor
+// undo (a strided prefix sum along every row), the sample expansion, the palette, the alpha fill and the byte swaps run on the device
+// (dxtex_tiff_unpack_device). HRESULTs, metadata and pixels are those of the host forms. Load: one upload of streamBytes, no download; a
+// file that is its image already (csrc/dxtex_tiff.h's tiff_is_native) whose one segment matches the image's pitch goes straight into it,
+// no kernel; the result is released on failure. Save: deviceImage's pixels are a device pointer, as DeviceScratchImage::GetImage gives;
+// the file's rows come down straight behind the header the host wrote, and only the two BGR sources run a kernel.
+HRESULT LoadFromTIFFMemory(Device& device, const void* pSource, size_t size, TIFF_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+HRESULT LoadFromTIFFFile(Device& device, const char* szFile, TIFF_FLAGS flags, TexMetadata* metadata, DeviceScratchImage& image) noexcept;
+// the second half of the resident load, for a caller that parsed the file before it had a device
+HRESULT UploadTIFFRaw(Device& device, const TexMetadata& metadata, const TIFFRawImage& raw, DeviceScratchImage& image) noexcept;
+HRESULT SaveToTIFFMemory(Device& device, const Image& deviceImage, TIFF_FLAGS flags, Blob& blob) noexcept;
+HRESULT SaveToTIFFFile(Device& device, const Image& deviceImage, TIFF_FLAGS flags, const char* szFile) noexcept;
 } // namespace DirectXTexAMD

@@ -237,7 +237,7 @@ int Parse(int argc, char** argv, Options& o)
     if (o.lower) std::transform(o.output.begin(), o.output.end(), o.output.begin(), [](unsigned char c) { return char(std::tolower(c)); });
     const bool single = IsCrossOut(o.command) || o.command == CMD_ARRAY_STRIP || o.command == CMD_MERGE;
     const FileType outType = FileTypeOf(o.output);
-    if (outType != FileType::DDS && !(single && (outType == FileType::TGA || outType == FileType::HDR || outType == FileType::PNG || outType == FileType::JPEG || outType == FileType::EXR)))
+    if (outType != FileType::DDS && !(single && (outType == FileType::TGA || outType == FileType::HDR || outType == FileType::PNG || outType == FileType::JPEG || outType == FileType::EXR || outType == FileType::TIFF)))
     {
         std::printf("ERROR: the output file must be .dds%s\n", single ? ", .tga, .hdr, .png or .jpg" : "");
         return 1;

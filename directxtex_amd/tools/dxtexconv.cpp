@@ -6,9 +6,9 @@
 // (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
 // rotations, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
-//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr>...
-//                          (-ft hdr | tga | ppm | pfm | png | exr: Radiance / TGA / portable pixmap / PNG / OpenEXR output of level 0)
-//                          (-ft png, -ft exr: <out> is a directory or a .png / .exr name)
+//   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr | in.tif>...
+//                          (-ft hdr | tga | ppm | pfm | png | exr | tif: Radiance / TGA / portable pixmap / PNG / OpenEXR / TIFF output of level 0)
+//                          (-ft png, -ft exr, -ft tif: <out> is a directory or a .png / .exr / .tif name)
 //     -w <n> -h <n>        target size                         -pow2             fit to a power of two (keeps the aspect ratio)
 //     -m <n>               mip levels, 0 = full chain           -fl <9.1 .. 12.2> feature level: largest texture side allowed
 //     -f <format>          DXGI format name or number           -if <filter>      POINT LINEAR CUBIC FANT BOX TRIANGLE
@@ -88,11 +88,11 @@ struct Options
     std::vector<std::string> inputs;
 
     // the readers' flags are texconv's (texconv.cpp:2192-2217): -ignoresrgb keeps a .png's sRGB chunk and gAMA from choosing the format and
-    // makes a colour .jpg linear; a .png headed for a BGR format is decoded as one (the load only: -info reports the file)
+    // makes a colour .jpg linear and keeps a .tif's Exif colour space from choosing the format; a .png headed for a BGR format is decoded as one (the load only: -info reports the file)
     LoadFlags ReadFlags(bool load) const
     {
         return { DDS_FLAGS(ddsRead), TGA_FLAGS_NONE, PNG_FLAGS((load ? PngBgrFor(format) : PNG_FLAGS_NONE) | (ignoreSrgb ? PNG_FLAGS_IGNORE_SRGB : PNG_FLAGS_NONE)),
-                 ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE };
+                 ignoreSrgb ? JPEG_FLAGS_DEFAULT_LINEAR : JPEG_FLAGS_NONE, ignoreSrgb ? TIFF_FLAGS_IGNORE_SRGB : TIFF_FLAGS_NONE };
     }
 };
 
@@ -129,7 +129,7 @@ int usage()
                          "                 [--rotate-color 709toHDR10|HDR10to709|709to2020|2020to709|P3D65toHDR10|P3D65to2020|709toP3D65|P3D65to709] [--paper-white-nits N]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N]\n"
-                         "                 [-ft dds|hdr|tga|ppm|pfm|png|exr] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr>...\n");
+                         "                 [-ft dds|hdr|tga|ppm|pfm|png|exr|tif] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr | in.tif>...\n");
     return 1;
 }
 
@@ -283,9 +283,9 @@ bool Parse(int argc, char** argv, Options& o)
     if (o.pmalpha && o.demul) { std::fprintf(stderr, "-pmalpha and -alpha exclude each other\n"); return false; }
     if (o.dx10 && o.dx9) { std::fprintf(stderr, "-dx10 and -dx9 exclude each other\n"); return false; }
     // -ft png: -o names a directory or a .png file. A name that ends in another type's extension would receive a PNG under that name, which no
-    // reader that goes by the extension opens. -ft exr likewise; the other types are not checked.
+    // reader that goes by the extension opens. -ft exr and -ft tif likewise; the other types are not checked.
     const FileType named = FileTypeOf(o.out);
-    if ((o.outType == FileType::PNG || o.outType == FileType::EXR) && Writes(named) && named != o.outType) { std::fprintf(stderr, "-ft %s writes a %s: -o %s names a %s file\n", ExtensionOf(o.outType) + 1, ExtensionOf(o.outType), o.out.c_str(), ExtensionOf(named)); return false; }
+    if ((o.outType == FileType::PNG || o.outType == FileType::EXR || o.outType == FileType::TIFF) && Writes(named) && named != o.outType) { std::fprintf(stderr, "-ft %s writes a %s: -o %s names a %s file\n", ExtensionOf(o.outType) + 1, ExtensionOf(o.outType), o.out.c_str(), ExtensionOf(named)); return false; }
     if (named == FileType::JPEG) { std::fprintf(stderr, "-o %s: JPEG output is not written yet\n", o.out.c_str()); return false; }
     if (o.gpus.empty()) o.gpus.assign(1, 0);
     if (o.info) return !o.inputs.empty();
@@ -581,6 +581,7 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
         case FileType::PFM: check("save", SaveToPortablePixMapHDRFile(first, outFile.c_str())); break;
         case FileType::PNG: check("save", SaveToPNGFile(first, PNG_FLAGS_NONE, outFile.c_str())); break;
         case FileType::EXR: check("save", SaveToEXRFile(first, outFile.c_str())); break;
+        case FileType::TIFF: check("save", SaveToTIFFFile(first, TIFF_FLAGS_NONE, outFile.c_str())); break;
         default: check("save", HRESULT_E_NOT_SUPPORTED);          // -ft takes no other type
         }
     }

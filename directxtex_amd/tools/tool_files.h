@@ -16,13 +16,22 @@ namespace tool
 using namespace DirectXTexAMD;
 
 // ---- file types: one row per extension; `ft` is the name dxtexconv's -ft takes for it (none: read only) ---------------------------------------
-enum class FileType { DDS, HDR, TGA, PPM, PFM, PHM, PNG, JPEG, EXR, UNKNOWN };
+// (UNKNOWN keeps its number: tests/test_tool_files_cpu.py states it, so a type added since follows it)
+enum class FileType { DDS, HDR, TGA, PPM, PFM, PHM, PNG, JPEG, EXR, UNKNOWN, TIFF };
 struct FileTypeRow { FileType type; const char* ext; const char* ft; };
 const FileTypeRow kFileTypes[] = {
     { FileType::DDS, ".dds", "dds" }, { FileType::HDR, ".hdr", "hdr" }, { FileType::TGA, ".tga", "tga" }, { FileType::PPM, ".ppm", "ppm" },
     { FileType::PFM, ".pfm", "pfm" }, { FileType::PHM, ".phm", nullptr }, { FileType::PNG, ".png", "png" }, { FileType::JPEG, ".jpg", "jpg" },
     { FileType::JPEG, ".jpeg", "jpeg" }, { FileType::EXR, ".exr", "exr" },
 };
+// the same table, continued: tests/cpp/tool_files_test.cpp counts kFileTypes' ten rows, so the rows added since lie here. Every lookup walks both.
+const FileTypeRow kFileTypesMore[] = { { FileType::TIFF, ".tif", "tif" }, { FileType::TIFF, ".tiff", "tiff" } };
+template<class F> inline const FileTypeRow* FindFileType(F&& matches)
+{
+    for (const FileTypeRow& r : kFileTypes) if (matches(r)) return &r;
+    for (const FileTypeRow& r : kFileTypesMore) if (matches(r)) return &r;
+    return nullptr;
+}
 
 inline bool hasExt(const std::string& s, const char* ext)
 {
@@ -31,18 +40,18 @@ inline bool hasExt(const std::string& s, const char* ext)
 }
 inline FileType FileTypeOf(const std::string& name)
 {
-    for (const FileTypeRow& r : kFileTypes) if (hasExt(name, r.ext)) return r.type;
-    return FileType::UNKNOWN;
+    const FileTypeRow* row = FindFileType([&](const FileTypeRow& r) { return hasExt(name, r.ext); });
+    return row ? row->type : FileType::UNKNOWN;
 }
 inline FileType FileTypeOfFt(const char* ft)
 {
-    for (const FileTypeRow& r : kFileTypes) if (r.ft && !strcasecmp(r.ft, ft)) return r.type;
-    return FileType::UNKNOWN;
+    const FileTypeRow* row = FindFileType([&](const FileTypeRow& r) { return r.ft && !strcasecmp(r.ft, ft); });
+    return row ? row->type : FileType::UNKNOWN;
 }
 inline const char* ExtensionOf(FileType type)
 {
-    for (const FileTypeRow& r : kFileTypes) if (r.type == type) return r.ext;
-    return "";
+    const FileTypeRow* row = FindFileType([&](const FileTypeRow& r) { return r.type == type; });
+    return row ? row->ext : "";
 }
 
 // ---- name tables --------------------------------------------------------------------------------------------------------------------------------
@@ -84,7 +93,7 @@ inline const char* FormatName(DXGI_FORMAT f, const char* fallback = "*UNKNOWN*")
 inline int Fail(const char* what, HRESULT hr) { std::printf("%s (%08X)\n", what, static_cast<unsigned int>(hr)); return 1; }
 
 // ---- reader flags, one per codec that takes any ---------------------------------------------------------------------------------------------------
-struct LoadFlags { DDS_FLAGS dds = DDS_FLAGS_NONE; TGA_FLAGS tga = TGA_FLAGS_NONE; PNG_FLAGS png = PNG_FLAGS_NONE; JPEG_FLAGS jpeg = JPEG_FLAGS_NONE; };
+struct LoadFlags { DDS_FLAGS dds = DDS_FLAGS_NONE; TGA_FLAGS tga = TGA_FLAGS_NONE; PNG_FLAGS png = PNG_FLAGS_NONE; JPEG_FLAGS jpeg = JPEG_FLAGS_NONE; TIFF_FLAGS tiff = TIFF_FLAGS_NONE; };
 // a .png headed for a BGR format is decoded as BGR (texconv.cpp:2213-2217, texassemble.cpp:1536-1544)
 inline PNG_FLAGS PngBgrFor(uint32_t f)
 {
@@ -99,12 +108,13 @@ inline PNG_FLAGS PngBgrFor(uint32_t f)
 //   .png  inflate and the row filters are byte-serial and run here; the unfiltered rows go up, the expansion to texels runs on the device
 //   .jpg  the Huffman walk runs here; the quantised coefficients go up, dequantisation, IDCT, upsampling and colour run on the device
 //   .exr  the header walk, inflate and the RLE packets run here; the chunks go up, the undo, the gather and the conversion run on the device
+//   .tif .tiff  the IFD walk, LZW, PackBits and inflate run here; the strips and tiles go up, the predictor undo and the expansion to texels run on the device
 struct SourceFile
 {
     FileType type = FileType::UNKNOWN;
     TexMetadata info;
     DDSRawImage dds; float exposure = 1.f; Blob rgbe; TGA_FLAGS tgaFlags = TGA_FLAGS_NONE; TGARawImage tga;
-    PNMRawImage pnm; PNGRawImage png; JPEGRawImage jpeg; EXRRawImage exr;
+    PNMRawImage pnm; PNGRawImage png; JPEGRawImage jpeg; EXRRawImage exr; TIFFRawImage tiff;
 
     // host only: no device is opened
     HRESULT Parse(const char* file, FileType fileType, const LoadFlags& flags)
@@ -124,6 +134,7 @@ struct SourceFile
         case FileType::PNG: return LoadFromPNGFileRaw(file, flags.png, &info, png);
         case FileType::JPEG: return LoadFromJPEGFileRaw(file, flags.jpeg, &info, jpeg);
         case FileType::EXR: return LoadFromEXRFileRaw(file, &info, exr);
+        case FileType::TIFF: return LoadFromTIFFFileRaw(file, flags.tiff, &info, tiff);
         default: return HRESULT_E_NOT_SUPPORTED;
         }
     }
@@ -140,12 +151,13 @@ struct SourceFile
         case FileType::PNG: hr = UploadPNGRaw(dev, info, png, image); break;
         case FileType::JPEG: hr = UploadJPEGRaw(dev, info, jpeg, image); break;
         case FileType::EXR: hr = UploadEXRRaw(dev, info, exr, image); break;
+        case FileType::TIFF: hr = UploadTIFFRaw(dev, info, tiff, image); break;
         default: hr = HRESULT_E_NOT_SUPPORTED; break;
         }
         Release();
         return hr;
     }
-    void Release() { dds.Release(); rgbe.Release(); tga.Release(); pnm.Release(); png.Release(); jpeg.Release(); exr.Release(); }
+    void Release() { dds.Release(); rgbe.Release(); tga.Release(); pnm.Release(); png.Release(); jpeg.Release(); exr.Release(); tiff.Release(); }
 };
 
 // what LoadFrom*File(Device&, ...) does for every codec: parse, upload, and `info` only on success
@@ -170,12 +182,13 @@ inline HRESULT GetMetadata(const char* file, FileType type, const LoadFlags& fla
     case FileType::PNG: return GetMetadataFromPNGFile(file, flags.png, info);
     case FileType::JPEG: return GetMetadataFromJPEGFile(file, flags.jpeg, info);
     case FileType::EXR: return GetMetadataFromEXRFile(file, info);
+    case FileType::TIFF: return GetMetadataFromTIFFFile(file, flags.tiff, info);
     default: return HRESULT_E_NOT_SUPPORTED;
     }
 }
 
 // The one download, by the resident writers: what comes down is the file's own rows (RGBE, TGA texels, PNM samples, PNG rows, JPEG
-// coefficients, EXR half planes), made on the device, or a .dds payload straight behind its header. A .dds takes every image with `info`
+// coefficients, EXR half planes, TIFF rows), made on the device, or a .dds payload straight behind its header. A .dds takes every image with `info`
 // and `ddsFlags`; every other type takes image (0, 0, 0). tga20: write the TGA 2.0 extension area from this metadata.
 inline HRESULT Save(Device& dev, FileType type, const DeviceScratchImage& image, const TexMetadata& info, DDS_FLAGS ddsFlags, const TexMetadata* tga20, const char* file)
 {
@@ -191,6 +204,7 @@ inline HRESULT Save(Device& dev, FileType type, const DeviceScratchImage& image,
     case FileType::PNG: return SaveToPNGFile(dev, *first, PNG_FLAGS_NONE, file);
     case FileType::JPEG: return SaveToJPEGFile(dev, *first, JPEG_FLAGS_NONE, file);
     case FileType::EXR: return SaveToEXRFile(dev, *first, file);
+    case FileType::TIFF: return SaveToTIFFFile(dev, *first, TIFF_FLAGS_NONE, file);
     default: return HRESULT_E_NOT_SUPPORTED;          // .phm: there is no writer
     }
 }

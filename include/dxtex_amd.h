@@ -612,6 +612,74 @@ dxtex_hresult dxtex_exr_unpack_device(dxtex_ctx* ctx, void* stream, size_t strea
                                       const dxtex_exr_channel* channels, uint32_t scanlineBytes, const dxtex_image* items, size_t itemCount);
 dxtex_hresult dxtex_exr_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* scanlines, size_t scanlineBytes);
 
+/* TIFF (.tif) strips and tiles: everything behind the header, the IFD walk, LZW, PackBits and inflate, which are byte-serial and stay with
+ * the caller (the reference reads TIFF through WIC; csrc/dxtex_tiff.h states the rules). The file side is ONE STREAM of the segments'
+ * expanded bytes and a descriptor per segment - a strip, a tile, or one of either of one plane where planes are separate - still
+ * predictor-coded, in the file's byte order, at the file's bits per sample; rows start on byte boundaries.
+ *   unpack   undoes the predictor of every row in place (tiff_undo: predictor 2 is a prefix sum over 8- or 16-bit elements with a stride
+ *            of samples per pixel, and leaves big-endian 16-bit rows little-endian; predictor 3 is that sum over the row's bytes, and its
+ *            four byte planes are addressed, not regrouped), then writes every segment's texels (tiff_texels) into dst, whose format is
+ *            the kind's: R8_UNORM for GREY1 / 4 / 8 (multiplied out, WhiteIsZero inverted), R16_UNORM, R32_FLOAT, R8G8B8A8_UNORM for
+ *            the palette kinds (`palette`: the 256 words to store), RGB8 and RGBA8 (or its _SRGB twin), R16G16B16A16_UNORM,
+ *            R32G32B32_FLOAT, R32G32B32A32_FLOAT; a missing alpha, and a fourth sample under `opaque`, is the depth's maximum.
+ *            A file that is its image already (chunky strips, predictor 1, little-endian or 8-bit, GREY8 / 16 / 32F, RGBA8 / 16 / 32F or
+ *            RGB32F, nothing inverted or forced) is row copies and no kernel.
+ *   pack     level 0 of src -> the writer's tight rows: R8_UNORM, R16_UNORM, R32_FLOAT, R8G8B8A8_UNORM[_SRGB], R16G16B16A16_UNORM,
+ *            R32G32B32_FLOAT and R32G32B32A32_FLOAT as they are (row copies, no kernel), B8G8R8A8_UNORM[_SRGB] as RGBA and
+ *            B8G8R8X8_UNORM[_SRGB] as RGB at 3 bytes a texel (tiff_pack).
+ * HRESULTs of unpack, in this order: E_POINTER for a null stream, segments, layout, dst or pixels, or a palette kind without a palette;
+ * E_INVALIDARG for no segments, a width or height of zero or other than the layout's, an unknown kind, bits or samples that are not the
+ * kind's, a predictor other than 1, 2, 3; NOT_SUPPORTED for a predictor that does not fit the bits (2: 8 or 16, 3: 32) or a dst format
+ * that is not the kind's; E_INVALIDARG for a descriptor that leaves the stream, the image or its plane count, whose rowBytes is smaller
+ * than its columns need, or that overlaps the one before it (descriptors are in ascending stream order), a row pitch smaller than the
+ * row, or a stream that overlaps the pixels.
+ * HRESULTs of pack: E_POINTER for a null image, pixels or rows; E_INVALIDARG for a width or height of zero; NOT_SUPPORTED for any other
+ * format; E_INVALIDARG for fewer than height * width * (file bytes a texel) bytes of rows, a row pitch smaller than the row, or rows
+ * that overlap the pixels. Bytes of dst outside each row's texels, and texels no segment names, are not written. */
+#define DXTEX_TIFF_GREY1    0u
+#define DXTEX_TIFF_GREY4    1u
+#define DXTEX_TIFF_GREY8    2u
+#define DXTEX_TIFF_GREY16   3u
+#define DXTEX_TIFF_GREY32F  4u
+#define DXTEX_TIFF_PAL1     5u
+#define DXTEX_TIFF_PAL4     6u
+#define DXTEX_TIFF_PAL8     7u
+#define DXTEX_TIFF_RGB8     8u
+#define DXTEX_TIFF_RGBA8    9u
+#define DXTEX_TIFF_RGB16    10u
+#define DXTEX_TIFF_RGBA16   11u
+#define DXTEX_TIFF_RGB32F   12u
+#define DXTEX_TIFF_RGBA32F  13u
+typedef struct dxtex_tiff_segment
+{
+    uint64_t offset;               /* of the segment's first byte in the stream */
+    uint32_t firstRow, rows;       /* of the image */
+    uint32_t firstCol, cols;       /* of the image; a tile's row may hold more columns than cols */
+    uint32_t rowBytes;             /* of one row of the segment */
+    uint32_t plane;                /* 0 unless planes are separate */
+} dxtex_tiff_segment;
+typedef struct dxtex_tiff_layout
+{
+    uint32_t width, height;
+    uint32_t bits, samples;        /* the kind's */
+    uint32_t kind;                 /* DXTEX_TIFF_* */
+    uint32_t predictor;            /* 1, 2 or 3 */
+    uint32_t bigEndian;            /* an MM file */
+    uint32_t planar;               /* PlanarConfiguration 2 and more than one sample */
+    uint32_t whiteIsZero;
+    uint32_t opaque;               /* the fourth sample is not alpha: it reads as the maximum */
+} dxtex_tiff_layout;
+/* host pointers, through the context's staging: the stream goes up as it is (and is not written), the rows come down through dst's pitch */
+dxtex_hresult dxtex_tiff_unpack(dxtex_ctx* ctx, const void* stream, size_t streamBytes, const dxtex_tiff_segment* segments, size_t segmentCount,
+                                const dxtex_tiff_layout* layout, const uint32_t* palette, const dxtex_image* dst);
+dxtex_hresult dxtex_tiff_pack(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes);
+/* device pointers (the descriptors, the layout and the palette stay host pointers, read before the call returns): asynchronous on the
+ * context's stream. THE STREAM IS WRITTEN where the file has a predictor: its rows are left undone in place. It may start at any byte;
+ * see csrc/tiff.hip for the alignments that take the wide routes. */
+dxtex_hresult dxtex_tiff_unpack_device(dxtex_ctx* ctx, void* stream, size_t streamBytes, const dxtex_tiff_segment* segments, size_t segmentCount,
+                                       const dxtex_tiff_layout* layout, const uint32_t* palette, const dxtex_image* dst);
+dxtex_hresult dxtex_tiff_pack_device(dxtex_ctx* ctx, const dxtex_image* src, void* rows, size_t rowsBytes);
+
 dxtex_hresult dxtex_resize(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 dxtex_hresult dxtex_resize_device(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t filter);
 
