@@ -13,69 +13,18 @@
 //   dds_device_test host_save <in.dds> <DDS_FLAGS of the load> <DDS_FLAGS of the save> <out.dds>   load + save, host forms
 //   dds_device_test time_save24 <in.dds> <out.dds> <runs>   for profiles/dds.md: a B8G8R8X8 file to a 24-bit file, file to file, the resident
 //       loader and writer against the host loader + Upload + Download + host writer; prints the milliseconds of each run, alternating
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-    buf.resize(size_t(n > 0 ? n : 0));
-    const bool ok = buf.empty() || std::fread(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
-
-static bool write_file(const std::string& path, const void* p, size_t n)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = !n || std::fwrite(p, 1, n, f) == n;
-    return (std::fclose(f) == 0) && ok;
-}
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
-}
+#include "codec_host_test.h"
 
 static bool same_pixels(const ScratchImage& a, const ScratchImage& b)
 {
     return a.GetPixelsSize() == b.GetPixelsSize() && a.GetPixels() && b.GetPixels() && !std::memcmp(a.GetPixels(), b.GetPixels(), a.GetPixelsSize());
 }
 
-// launches of kernels whose mark starts with "dds_" since profile_begin
-static unsigned dds_launches(Device& dev)
-{
-    char names[4096] = {};
-    float ms[64]; uint32_t launches[64]; size_t count = 0;
-    if (dxtex_ctx_profile_end(dev.Get(), names, sizeof(names), ms, launches, 64, &count) != DXTEX_S_OK) return 999;
-    unsigned total = 0;
-    std::istringstream ss(names);
-    std::string name;
-    for (size_t i = 0; i < count && std::getline(ss, name); ++i)
-        if (name.rfind("dds_", 0) == 0) total += launches[i];
-    return total;
-}
-
 struct Line { std::string path; unsigned long a = 0, b = 0; };
 static std::vector<Line> read_list(const char* list)
 {
     std::vector<Line> lines;
-    std::ifstream in(list);
-    for (std::string text; std::getline(in, text);)
+    for (const std::string& text : read_lines(list))
     {
         std::istringstream ss(text);
         Line l;
@@ -97,24 +46,16 @@ static int load_many(const char* list)
         const DDS_FLAGS flags = DDS_FLAGS(files[i].a);
         TexMetadata hostMd; ScratchImage host;
         const HRESULT hostHr = LoadFromDDSMemory(data.data(), data.size(), flags, &hostMd, host);
-        uint64_t up = 0, down = 0;
-        GetTransferBytes(dev, up, down, true);
-        dxtex_ctx_profile_begin(dev.Get());
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromDDSMemory(dev, data.data(), data.size(), flags, &md, image);
-        const unsigned launches = dds_launches(dev);
-        GetTransferBytes(dev, up, down);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %08x fail %s\n", i, unsigned(hr), unsigned(hostHr), released ? "released" : "held");
-            continue;
-        }
+        const unsigned launches = window.end({ "dds_" })[0].launches;
+        if (FAILED(hr)) { std::printf("%zu %08x %08x fail %s\n", i, unsigned(hr), unsigned(hostHr), released(image) ? "released" : "held"); continue; }
         ScratchImage back;
         if (FAILED(image.Download(back))) { std::fprintf(stderr, "%s: download failed\n", files[i].path.c_str()); return 1; }
         const bool metaEqual = SUCCEEDED(hostHr) && same_metadata(md, hostMd) && same_metadata(image.GetMetadata(), host.GetMetadata());
         std::printf("%zu %08x %08x ok %d %d %llu %llu %u\n", i, unsigned(hr), unsigned(hostHr), int(metaEqual), int(SUCCEEDED(hostHr) && same_pixels(back, host)),
-                    (unsigned long long)up, (unsigned long long)down, launches);
+                    (unsigned long long)window.up, (unsigned long long)window.down, launches);
     }
     return 0;
 }
@@ -133,10 +74,9 @@ static int save_many(const char* list)
         const HRESULT hostHr = SaveToDDSMemory(host.GetImages(), host.GetImageCount(), md, flags, hostBlob);
         DeviceScratchImage image;
         if (FAILED(image.Upload(dev, host))) { std::fprintf(stderr, "%s: upload failed\n", files[i].path.c_str()); return 1; }
-        uint64_t up = 0, down = 0;
-        GetTransferBytes(dev, up, down, true);
+        Window window(dev);
         const HRESULT hr = SaveToDDSMemory(dev, image.GetImages(), image.GetImageCount(), md, flags, blob);
-        GetTransferBytes(dev, up, down);
+        window.end();
         const bool equal = SUCCEEDED(hr) && SUCCEEDED(hostHr) && blob.GetBufferSize() == hostBlob.GetBufferSize() &&
                            !std::memcmp(blob.GetBufferPointer(), hostBlob.GetBufferPointer(), blob.GetBufferSize());
         bool roundTrip = false;
@@ -146,7 +86,7 @@ static int save_many(const char* list)
             roundTrip = SUCCEEDED(LoadFromDDSMemory(dev, blob.GetBufferPointer(), blob.GetBufferSize(), DDS_FLAGS(files[i].a), &md2, again)) && SUCCEEDED(again.Download(back)) &&
                         same_pixels(back, host) && md2.format == md.format;
         }
-        std::printf("%zu %08x %08x %d %llu %llu %d %zu\n", i, unsigned(hr), unsigned(hostHr), int(equal), (unsigned long long)up, (unsigned long long)down, int(roundTrip), blob.GetBufferSize());
+        std::printf("%zu %08x %08x %d %llu %llu %d %zu\n", i, unsigned(hr), unsigned(hostHr), int(equal), (unsigned long long)window.up, (unsigned long long)window.down, int(roundTrip), blob.GetBufferSize());
     }
     return 0;
 }

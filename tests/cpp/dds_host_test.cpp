@@ -7,33 +7,7 @@
 //        <direct> <payload's offset in the file> <payloadBytes> <same 0/1> <offset:rowPitch:slicePitch of every image>";
 //       same = Raw's metadata is Ex's, Ex's image count is Raw's, and Raw's palette is the file's. One DDSRawImage serves every file: a
 //       failure must leave it empty whatever it held before.
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    std::fseek(f, 0, SEEK_END); const long n = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-    buf.resize(size_t(n > 0 ? n : 0));
-    const bool ok = buf.empty() || std::fread(buf.data(), 1, buf.size(), f) == buf.size();
-    std::fclose(f);
-    return ok;
-}
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
-}
+#include "codec_host_test.h"
 
 static int raw_many(const char* list)
 {
@@ -47,11 +21,11 @@ static int raw_many(const char* list)
         if (!(ss >> path >> flags)) return 2;
         std::vector<uint8_t> data;
         if (!read_file(path, data)) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-        std::vector<uint8_t> exact(data.begin(), data.end());          // a read past the file's last byte is a read past an allocation
-        const uint8_t* p = exact.empty() ? nullptr : exact.data();
-        const HRESULT hr = LoadFromDDSMemoryRaw(p, exact.size(), DDS_FLAGS(flags), nullptr, raw);
+        const Exact exact(data.data(), data.size());
+        const uint8_t* p = exact.n ? exact.p : nullptr;
+        const HRESULT hr = LoadFromDDSMemoryRaw(p, exact.n, DDS_FLAGS(flags), nullptr, raw);
         TexMetadata md; ScratchImage image;
-        const HRESULT hrEx = LoadFromDDSMemoryEx(p, exact.size(), DDS_FLAGS(flags), &md, nullptr, image);
+        const HRESULT hrEx = LoadFromDDSMemoryEx(p, exact.n, DDS_FLAGS(flags), &md, nullptr, image);
         if (FAILED(hr))
         {
             const bool released = !raw.payload && !raw.payloadBytes && raw.images.empty() && !raw.storage.GetBufferPointer();
@@ -60,7 +34,7 @@ static int raw_many(const char* list)
         }
         const TexMetadata& m = raw.metadata;
         const size_t at = size_t(raw.payload - p);
-        bool same = SUCCEEDED(hrEx) && same_metadata(m, md) && image.GetImageCount() == raw.images.size() && raw.payload >= p && at + raw.payloadBytes <= exact.size();
+        bool same = SUCCEEDED(hrEx) && same_metadata(m, md) && image.GetImageCount() == raw.images.size() && raw.payload >= p && at + raw.payloadBytes <= exact.n;
         if (same && raw.paletted) same = at >= sizeof(raw.palette) && !std::memcmp(raw.palette, raw.payload - sizeof(raw.palette), sizeof(raw.palette));
         std::printf("%zu %08x %08x ok %zu %zu %zu %u %zu %zu %u %u %u %u %d %d %d %zu %zu %d", index, unsigned(hr), unsigned(hrEx), m.width, m.height, m.depth, unsigned(m.format),
                     m.arraySize, m.mipLevels, unsigned(m.miscFlags), unsigned(m.miscFlags2), unsigned(m.dimension), raw.op, int(raw.opaque), int(raw.paletted), int(raw.direct),

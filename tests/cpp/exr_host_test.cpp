@@ -24,61 +24,7 @@
 //   exr_host_test time_load <file> <runs> | time_save <file> <runs>
 //       for tools/exr_bench.py: wall time and bytes moved of the resident path beside the same build's host path, one line per run; time_load
 //       also prints the Raw loader's time alone ("raw") and the host's serial undo of the same stream ("undo")
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
-
-static bool write_file(const std::string& path, const void* p, size_t bytes)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = bytes == 0 || std::fwrite(p, 1, bytes, f) == bytes;
-    return (std::fclose(f) == 0) && ok;
-}
-
-static std::vector<std::string> read_list(const char* path)
-{
-    std::vector<std::string> files;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);) if (!line.empty()) files.push_back(line);
-    return files;
-}
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
-}
-
-// an exact-size copy on the heap: a read past the file's last byte is a read past an allocation
-struct Exact
-{
-    uint8_t* p = nullptr; size_t n = 0;
-    Exact(const uint8_t* s, size_t bytes) : n(bytes) { p = static_cast<uint8_t*>(std::malloc(n ? n : 1)); if (n) std::memcpy(p, s, n); }
-    ~Exact() { std::free(p); }
-};
+#include "codec_host_test.h"
 
 // both loaders on one buffer; what a failure must leave behind is checked here
 static bool load_both(const uint8_t* p, size_t n, EXRRawImage& raw, ScratchImage& image, TexMetadata& rawMd, TexMetadata& md, HRESULT& rawHr, HRESULT& hr, const char* what)
@@ -93,7 +39,7 @@ static bool load_both(const uint8_t* p, size_t n, EXRRawImage& raw, ScratchImage
 
 static int load_many(const char* list)
 {
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     EXRRawImage raw; ScratchImage image;          // one object each for every file: a failure must leave it empty whatever it held before
     for (size_t i = 0; i < files.size(); ++i)
@@ -129,32 +75,12 @@ static int load_many(const char* list)
 
 static int damaged(const char* file, bool truncations, uint64_t seed, size_t cases)
 {
-    std::vector<uint8_t> data;
-    if (!read_file(file, data) || data.empty()) return 1;
     EXRRawImage raw; ScratchImage image;
-    size_t loaded = 0, refused = 0;
-    uint64_t s = seed * 6364136223846793005ull + 1442695040888963407ull;
-    auto next = [&] { s = s * 6364136223846793005ull + 1442695040888963407ull; return uint32_t(s >> 33); };
-    if (truncations) cases = data.size();
-    for (size_t i = 0; i < cases; ++i)
+    return damaged_copies(file, truncations, seed, cases, [&](const uint8_t* p, size_t n, HRESULT& hr)
     {
-        std::vector<uint8_t> copy(data.begin(), truncations ? data.begin() + i : data.end());
-        if (!truncations)
-            for (uint32_t k = 1 + next() % 4; k; --k)
-            {
-                const size_t at = next() % copy.size();
-                const uint32_t how = next() % 3;
-                copy[at] = how == 0 ? uint8_t(next()) : how == 1 ? uint8_t(copy[at] ^ (1u << (next() % 8))) : (next() & 1 ? 0xFF : 0x00);
-            }
-        const Exact exact(copy.data(), copy.size());
-        TexMetadata rawMd, md;
-        HRESULT rawHr, hr;
-        if (!load_both(exact.p, exact.n, raw, image, rawMd, md, rawHr, hr, "a damaged copy")) return 1;
-        if (truncations && SUCCEEDED(hr)) { std::fprintf(stderr, "a prefix of %zu bytes loaded\n", i); return 1; }
-        if (SUCCEEDED(hr)) ++loaded; else ++refused;
-    }
-    std::printf("%s %zu %zu\n", truncations ? "truncations" : "fuzz", loaded, refused);
-    return 0;
+        TexMetadata rawMd, md; HRESULT rawHr;
+        return load_both(p, n, raw, image, rawMd, md, rawHr, hr, "a damaged copy");
+    });
 }
 
 static int files(const char* file)
@@ -173,14 +99,6 @@ static int files(const char* file)
     return 0;
 }
 
-static bool image_arg(char** a, std::vector<uint8_t>& px, Image& src)
-{
-    if (!read_file(a[0], px)) return false;
-    src.width = size_t(std::atoll(a[1])); src.height = size_t(std::atoll(a[2])); src.format = DXGI_FORMAT(std::atoi(a[3]));
-    src.rowPitch = size_t(std::atoll(a[4])); src.slicePitch = src.rowPitch * src.height; src.pixels = px.data();
-    return px.size() >= src.slicePitch;
-}
-
 static int save(char** a)
 {
     std::vector<uint8_t> px; Image src;
@@ -193,25 +111,11 @@ static int save(char** a)
     return 0;
 }
 
-// launches of kernels whose mark starts with `prefix` since profile_begin
-static void exr_launches(Device& dev, unsigned (&total)[3])
-{
-    static const char* const prefix[3] = { "exr_undo", "exr_texels", "exr_pack" };
-    char names[4096] = {};
-    float ms[64]; uint32_t launches[64]; size_t count = 0;
-    total[0] = total[1] = total[2] = 0;
-    if (dxtex_ctx_profile_end(dev.Get(), names, sizeof(names), ms, launches, 64, &count) != DXTEX_S_OK) { total[0] = total[1] = total[2] = 999; return; }
-    std::istringstream ss(names);
-    std::string name;
-    for (size_t i = 0; i < count && std::getline(ss, name); ++i)
-        for (int k = 0; k < 3; ++k) if (name.rfind(prefix[k], 0) == 0) total[k] += launches[i];
-}
-
 static int device_load_many(const char* list)
 {
     Device dev;
     if (FAILED(dev.Create(0))) { std::fprintf(stderr, "no device\n"); return 1; }
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     DeviceScratchImage image;
     for (size_t i = 0; i < files.size(); ++i)
@@ -222,26 +126,17 @@ static int device_load_many(const char* list)
         const uint8_t* source = data.empty() ? &none : data.data();          // an empty file is a size of zero, not a null pointer
         const HRESULT hostHr = LoadFromEXRMemory(source, data.size(), &hostMd, host);
         (void)LoadFromEXRMemoryRaw(source, data.size(), &rawMd, raw);
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
-        dxtex_ctx_profile_begin(dev.Get());
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromEXRMemory(dev, source, data.size(), &md, image);
-        unsigned launches[3];
-        exr_launches(dev, launches);
-        GetTransferBytes(dev, up1, down1);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released ? "released" : "held");
-            continue;
-        }
+        const std::vector<Window::Mark> marks = window.end({ "exr_undo", "exr_texels" });
+        if (FAILED(hr)) { std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released(image) ? "released" : "held"); continue; }
         ScratchImage back;
         if (FAILED(image.Download(back))) { std::fprintf(stderr, "%s: download failed\n", files[i].c_str()); return 1; }
         const bool metaEqual = SUCCEEDED(hostHr) && same_metadata(md, hostMd) && same_metadata(image.GetMetadata(), host.GetMetadata());
         const bool pixelsEqual = SUCCEEDED(hostHr) && back.GetPixelsSize() == host.GetPixelsSize() && !std::memcmp(back.GetPixels(), host.GetPixels(), host.GetPixelsSize());
         std::printf("%zu %08x %08x ok %zu %zu %zu %zu %llu %llu %d %d %u %u\n", i, unsigned(hr), unsigned(hostHr), md.width, md.height, md.arraySize, raw.streamBytes,
-                    (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), int(metaEqual), int(pixelsEqual), launches[0], launches[1]);
+                    (unsigned long long)window.up, (unsigned long long)window.down, int(metaEqual), int(pixelsEqual), marks[0].launches, marks[1].launches);
     }
     return 0;
 }
@@ -257,29 +152,17 @@ static int device_save(char** a)
     DeviceScratchImage image;
     HRESULT hr = image.Upload(dev, &src, 1, md);
     if (FAILED(hr)) { std::printf("upload %08x\n", unsigned(hr)); return 1; }
-    uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-    GetTransferBytes(dev, up0, down0);
-    dxtex_ctx_profile_begin(dev.Get());
+    Window window(dev);
     hr = SaveToEXRFile(dev, *image.GetImage(0, 0, 0), a[5]);
-    unsigned launches[3];
-    exr_launches(dev, launches);
-    GetTransferBytes(dev, up1, down1);
+    const std::vector<Window::Mark> marks = window.end({ "exr_pack" });
     const std::string hostOut = std::string(a[5]) + ".host";
     const HRESULT hostHr = SaveToEXRFile(src, hostOut.c_str());
-    std::printf("hr %08x %08x %llu %llu %u\n", unsigned(hr), unsigned(hostHr), (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), launches[2]);
+    std::printf("hr %08x %08x %llu %llu %u\n", unsigned(hr), unsigned(hostHr), (unsigned long long)window.up, (unsigned long long)window.down, marks[0].launches);
     return 0;
 }
 
 // tools/exr_bench.py: a file through the resident loader and through the host loader plus Upload, alternating, `runs` times each after one
 // unmeasured run each; a resident image through the resident saver and through Download plus the host saver likewise
-template<class F>
-static double timed_ms(F&& f)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    f();
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 static int time_paths(const char* file, int runs, bool save)
 {
     Device dev;
@@ -290,40 +173,35 @@ static int time_paths(const char* file, int runs, bool save)
     TexMetadata md;
     if (FAILED(LoadFromEXRMemory(dev, data.data(), data.size(), &md, resident))) return 1;
     bool ok = true;
-    for (int i = -1; i < runs; ++i)
+    if (save)
     {
-        uint64_t up0, down0, up1, down1, up2, down2;
-        double a, b, rawMs = 0, undoMs = 0;
-        GetTransferBytes(dev, up0, down0);
-        if (!save)
+        const Image& img = *resident.GetImage(0, 0, 0);
+        return time_runs(dev, runs,
+            [&] { return timed_ms([&] { Blob blob; ok = ok && SUCCEEDED(SaveToEXRMemory(dev, img, blob)); }); },
+            [&] { return timed_ms([&] { Blob blob; ScratchImage host; ok = ok && SUCCEEDED(resident.Download(host)) && SUCCEEDED(SaveToEXRMemory(*host.GetImage(0, 0, 0), blob)); }); },
+            [&](std::string& extra) { extra = " raw 0.000 ms undo 0.000 ms"; return ok; });
+    }
+    return time_runs(dev, runs,
+        [&] { return timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromEXRMemory(dev, data.data(), data.size(), nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&] { return timed_ms([&] { ScratchImage host; DeviceScratchImage image;
+                                    ok = ok && SUCCEEDED(LoadFromEXRMemory(data.data(), data.size(), nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&](std::string& extra)
         {
-            a = timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromEXRMemory(dev, data.data(), data.size(), nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-            GetTransferBytes(dev, up1, down1);
-            b = timed_ms([&] { ScratchImage host; DeviceScratchImage image;
-                               ok = ok && SUCCEEDED(LoadFromEXRMemory(data.data(), data.size(), nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
             EXRRawImage raw;
-            rawMs = timed_ms([&] { ok = ok && SUCCEEDED(LoadFromEXRMemoryRaw(data.data(), data.size(), nullptr, raw)); });
+            const double rawMs = timed_ms([&] { ok = ok && SUCCEEDED(LoadFromEXRMemoryRaw(data.data(), data.size(), nullptr, raw)); });
+            if (!ok) return false;
             // the host's serial undo of the same stream: the delta of every coded chunk, one byte after another
-            if (ok) undoMs = timed_ms([&]
+            const double undoMs = timed_ms([&]
             {
                 uint8_t* s = raw.storage.GetBufferPointer();
                 for (size_t c = 0; c < raw.chunkCount; ++c)
                     if (raw.chunks[c].coded) { uint8_t* t = s + raw.chunks[c].offset; for (size_t k = 1; k < raw.chunks[c].bytes; ++k) t[k] = uint8_t(t[k - 1] + t[k] - 128); }
             });
-        }
-        else
-        {
-            const Image& img = *resident.GetImage(0, 0, 0);
-            a = timed_ms([&] { Blob blob; ok = ok && SUCCEEDED(SaveToEXRMemory(dev, img, blob)); });
-            GetTransferBytes(dev, up1, down1);
-            b = timed_ms([&] { Blob blob; ScratchImage host; ok = ok && SUCCEEDED(resident.Download(host)) && SUCCEEDED(SaveToEXRMemory(*host.GetImage(0, 0, 0), blob)); });
-        }
-        GetTransferBytes(dev, up2, down2);
-        if (!ok) { std::fprintf(stderr, "a step failed\n"); return 1; }
-        if (i >= 0) std::printf("run %d resident %.3f ms up %llu down %llu host %.3f ms up %llu down %llu raw %.3f ms undo %.3f ms\n", i, a, (unsigned long long)(up1 - up0),
-                                (unsigned long long)(down1 - down0), b, (unsigned long long)(up2 - up1), (unsigned long long)(down2 - down1), rawMs, undoMs);
-    }
-    return 0;
+            char text[64];
+            std::snprintf(text, sizeof(text), " raw %.3f ms undo %.3f ms", rawMs, undoMs);
+            extra = text;
+            return true;
+        });
 }
 
 int main(int argc, char** argv)

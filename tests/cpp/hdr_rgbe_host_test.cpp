@@ -12,56 +12,18 @@
 //   hdr_rgbe_host_test device_save <in.bin> <width> <height> <format> <rowPitch> <out.hdr>
 //       the image goes up, the resident SaveToHDRFile writes it; prints "hr <hresult hex> <bytes host -> device> <bytes device -> host>"
 //       counted around the save alone
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
-
-static bool write_file(const std::string& path, const void* p, size_t bytes)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = bytes == 0 || std::fwrite(p, 1, bytes, f) == bytes;
-    return (std::fclose(f) == 0) && ok;
-}
-
-static std::vector<std::string> read_list(const char* path)
-{
-    std::vector<std::string> files;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);) if (!line.empty()) files.push_back(line);
-    return files;
-}
+#include "codec_host_test.h"
 
 static int rgbe_load_many(const char* list)
 {
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     for (size_t i = 0; i < files.size(); ++i)
     {
         if (!read_file(files[i], data)) { std::fprintf(stderr, "cannot read %s\n", files[i].c_str()); return 1; }
-        // an exact-size copy on the heap: a read past the file's last byte is a read past an allocation
-        std::vector<uint8_t> exact(data.begin(), data.end());
+        const Exact exact(data.data(), data.size());
         TexMetadata md; float exposure = 0.f; Blob rgbe;
-        const HRESULT hr = LoadFromHDRMemoryRGBE(exact.empty() ? nullptr : exact.data(), exact.size(), &md, exposure, rgbe);
+        const HRESULT hr = LoadFromHDRMemoryRGBE(exact.n ? exact.p : nullptr, exact.n, &md, exposure, rgbe);
         if (FAILED(hr))
         {
             if (rgbe.GetBufferPointer()) { std::fprintf(stderr, "%s: the rows were not released\n", files[i].c_str()); return 1; }
@@ -80,30 +42,24 @@ static int device_load_many(const char* list)
 {
     Device dev;
     if (FAILED(dev.Create(0))) { std::fprintf(stderr, "no device\n"); return 1; }
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     DeviceScratchImage image;          // one object for every file: a failure must leave it empty whatever it held before
     for (size_t i = 0; i < files.size(); ++i)
     {
         if (!read_file(files[i], data)) { std::fprintf(stderr, "cannot read %s\n", files[i].c_str()); return 1; }
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromHDRMemory(dev, data.empty() ? nullptr : data.data(), data.size(), &md, image);
-        GetTransferBytes(dev, up1, down1);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %s\n", i, unsigned(hr), released ? "released" : "held");
-            continue;
-        }
+        window.end();
+        if (FAILED(hr)) { std::printf("%zu %08x %s\n", i, unsigned(hr), released(image) ? "released" : "held"); continue; }
         ScratchImage host;
         if (FAILED(image.Download(host))) { std::fprintf(stderr, "%s: download failed\n", files[i].c_str()); return 1; }
         const TexMetadata& im = image.GetMetadata();
         if (im.width != md.width || im.height != md.height || im.format != md.format || im.miscFlags2 != md.miscFlags2) { std::fprintf(stderr, "%s: metadata differs\n", files[i].c_str()); return 1; }
         if (!write_file(files[i] + ".out", host.GetPixels(), host.GetPixelsSize())) return 1;
         std::printf("%zu %08x ok %zu %zu %u %u %llu %llu\n", i, unsigned(hr), md.width, md.height, unsigned(md.format), unsigned(md.miscFlags2),
-                    (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0));
+                    (unsigned long long)window.up, (unsigned long long)window.down);
     }
     return 0;
 }
@@ -112,22 +68,17 @@ static int device_save(char** a)
 {
     Device dev;
     if (FAILED(dev.Create(0))) { std::fprintf(stderr, "no device\n"); return 1; }
-    std::vector<uint8_t> px;
-    if (!read_file(a[0], px)) return 1;
-    Image src;
-    src.width = size_t(std::atoll(a[1])); src.height = size_t(std::atoll(a[2])); src.format = DXGI_FORMAT(std::atoi(a[3]));
-    src.rowPitch = size_t(std::atoll(a[4])); src.slicePitch = src.rowPitch * src.height; src.pixels = px.data();
-    if (px.size() < src.slicePitch) return 1;
+    std::vector<uint8_t> px; Image src;
+    if (!image_arg(a, px, src)) return 1;
     TexMetadata md;
     md.width = src.width; md.height = src.height; md.depth = md.arraySize = md.mipLevels = 1; md.format = src.format; md.dimension = TEX_DIMENSION_TEXTURE2D;
     DeviceScratchImage image;
     HRESULT hr = image.Upload(dev, &src, 1, md);
     if (FAILED(hr)) { std::printf("upload %08x\n", unsigned(hr)); return 1; }
-    uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-    GetTransferBytes(dev, up0, down0);
+    Window window(dev);
     hr = SaveToHDRFile(dev, *image.GetImage(0, 0, 0), a[5]);
-    GetTransferBytes(dev, up1, down1);
-    std::printf("hr %08x %llu %llu\n", unsigned(hr), (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0));
+    window.end();
+    std::printf("hr %08x %llu %llu\n", unsigned(hr), (unsigned long long)window.up, (unsigned long long)window.down);
     return 0;
 }
 

@@ -16,60 +16,19 @@
 //   jpeg_host_test time_raw <file> <runs> | time_load <file> <runs>
 //       for tools/jpeg_bench.py: the byte-serial half alone (no device); wall time and bytes moved of the resident path beside the same
 //       build's host path plus Upload, one line per run
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
+#include "codec_host_test.h"
 
 struct Line { JPEG_FLAGS flags; std::string path; };
 static std::vector<Line> read_list(const char* path)
 {
     std::vector<Line> lines;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);)
+    for (const std::string& line : read_lines(path))
     {
-        if (line.empty()) continue;
         const size_t sp = line.find(' ');
-        if (sp == std::string::npos) continue;
-        lines.push_back({ JPEG_FLAGS(std::strtoul(line.substr(0, sp).c_str(), nullptr, 0)), line.substr(sp + 1) });
+        if (sp != std::string::npos) lines.push_back({ JPEG_FLAGS(std::strtoul(line.substr(0, sp).c_str(), nullptr, 0)), line.substr(sp + 1) });
     }
     return lines;
 }
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
-}
-
-// an exact-size copy on the heap: a read past the file's last byte is a read past an allocation
-struct Exact
-{
-    uint8_t* p = nullptr; size_t n = 0;
-    explicit Exact(const std::vector<uint8_t>& v) : n(v.size()) { p = static_cast<uint8_t*>(std::malloc(n ? n : 1)); if (n) std::memcpy(p, v.data(), n); }
-    ~Exact() { std::free(p); }
-};
 
 static int load_many(const char* list)
 {
@@ -83,7 +42,7 @@ static int load_many(const char* list)
     {
         const std::string& path = files[i].path;
         if (!read_file(path, data)) { std::fprintf(stderr, "cannot read %s\n", path.c_str()); return 1; }
-        const Exact exact(data);
+        const Exact exact(data.data(), data.size());
         TexMetadata rawMd, md, only;
         const HRESULT rawHr = LoadFromJPEGMemoryRaw(exact.p, exact.n, files[i].flags, &rawMd, raw);
         const HRESULT hr = LoadFromJPEGMemory(exact.p, exact.n, files[i].flags, &md, image);
@@ -129,20 +88,6 @@ static int errors(const char* file)
     return 0;
 }
 
-// launches of kernels whose mark starts with "jpeg_" since profile_begin
-static unsigned jpeg_launches(Device& dev)
-{
-    char names[4096] = {};
-    float ms[64]; uint32_t launches[64]; size_t count = 0;
-    if (dxtex_ctx_profile_end(dev.Get(), names, sizeof(names), ms, launches, 64, &count) != DXTEX_S_OK) return 999;
-    unsigned total = 0;
-    std::istringstream ss(names);
-    std::string name;
-    for (size_t i = 0; i < count && std::getline(ss, name); ++i)
-        if (name.rfind("jpeg_", 0) == 0) total += launches[i];
-    return total;
-}
-
 static int device_load_many(const char* list)
 {
     Device dev;
@@ -158,35 +103,19 @@ static int device_load_many(const char* list)
         const uint8_t* source = data.empty() ? &none : data.data();          // an empty file is a size of zero, not a null pointer
         const HRESULT hostHr = LoadFromJPEGMemory(source, data.size(), files[i].flags, &hostMd, host);
         (void)LoadFromJPEGMemoryRaw(source, data.size(), files[i].flags, &rawMd, raw);
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
-        dxtex_ctx_profile_begin(dev.Get());
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromJPEGMemory(dev, source, data.size(), files[i].flags, &md, image);
-        const unsigned launches = jpeg_launches(dev);
-        GetTransferBytes(dev, up1, down1);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released ? "released" : "held");
-            continue;
-        }
+        const unsigned launches = window.end({ "jpeg_" })[0].launches;
+        if (FAILED(hr)) { std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released(image) ? "released" : "held"); continue; }
         ScratchImage back;
         if (FAILED(image.Download(back))) { std::fprintf(stderr, "%s: download failed\n", files[i].path.c_str()); return 1; }
         const bool metaEqual = SUCCEEDED(hostHr) && same_metadata(md, hostMd);
         const bool pixelsEqual = SUCCEEDED(hostHr) && back.GetPixelsSize() == host.GetPixelsSize() && !std::memcmp(back.GetPixels(), host.GetPixels(), host.GetPixelsSize());
         std::printf("%zu %08x %08x ok %zu %zu %u %zu %llu %llu %d %d %u\n", i, unsigned(hr), unsigned(hostHr), md.width, md.height, unsigned(md.format), raw.coefficientCount * 2,
-                    (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), int(metaEqual), int(pixelsEqual), launches);
+                    (unsigned long long)window.up, (unsigned long long)window.down, int(metaEqual), int(pixelsEqual), launches);
     }
     return 0;
-}
-
-template<class F>
-static double timed_ms(F&& f)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    f();
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 static int time_raw(const char* file, int runs)
@@ -211,20 +140,11 @@ static int time_load(const char* file, int runs)
     std::vector<uint8_t> data;
     if (!read_file(file, data)) return 1;
     bool ok = true;
-    for (int i = -1; i < runs; ++i)
-    {
-        uint64_t up0, down0, up1, down1, up2, down2;
-        GetTransferBytes(dev, up0, down0);
-        const double a = timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromJPEGMemory(dev, data.data(), data.size(), JPEG_FLAGS_NONE, nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-        GetTransferBytes(dev, up1, down1);
-        const double b = timed_ms([&] { ScratchImage host; DeviceScratchImage image;
-                                        ok = ok && SUCCEEDED(LoadFromJPEGMemory(data.data(), data.size(), JPEG_FLAGS_NONE, nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-        GetTransferBytes(dev, up2, down2);
-        if (!ok) { std::fprintf(stderr, "a step failed\n"); return 1; }
-        if (i >= 0) std::printf("run %d resident %.3f ms up %llu down %llu host %.3f ms up %llu down %llu\n", i, a, (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0),
-                                b, (unsigned long long)(up2 - up1), (unsigned long long)(down2 - down1));
-    }
-    return 0;
+    return time_runs(dev, runs,
+        [&] { return timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromJPEGMemory(dev, data.data(), data.size(), JPEG_FLAGS_NONE, nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&] { return timed_ms([&] { ScratchImage host; DeviceScratchImage image;
+                                    ok = ok && SUCCEEDED(LoadFromJPEGMemory(data.data(), data.size(), JPEG_FLAGS_NONE, nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&](std::string&) { return ok; });
 }
 
 int main(int argc, char** argv)

@@ -19,46 +19,13 @@
 //   jpeg_write_host_test time_save <width> <height> <format> <runs>
 //       for tools/jpeg_bench.py: wall time and bytes moved of the resident saver beside Download plus the same build's host saver, and the
 //       byte-serial half alone, one line per run
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
-
-static bool write_file(const std::string& path, const uint8_t* p, size_t n)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = std::fwrite(p, 1, n, f) == n;
-    return (std::fclose(f) == 0) && ok;
-}
+#include "codec_host_test.h"
 
 struct Line { unsigned format; size_t width, height, pitch; std::string path; };
 static std::vector<Line> read_list(const char* path)
 {
     std::vector<Line> lines;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);)
+    for (const std::string& line : read_lines(path))
     {
         std::istringstream ss(line);
         Line l;
@@ -68,14 +35,6 @@ static std::vector<Line> read_list(const char* path)
     }
     return lines;
 }
-
-// an exact-size copy on the heap: a read past the image's last texel is a read past an allocation
-struct Exact
-{
-    uint8_t* p = nullptr; size_t n = 0;
-    explicit Exact(const std::vector<uint8_t>& v) : n(v.size()) { p = static_cast<uint8_t*>(std::malloc(n ? n : 1)); if (n) std::memcpy(p, v.data(), n); }
-    ~Exact() { std::free(p); }
-};
 
 static Image image_of(const Line& l, uint8_t* pixels) { return Image{ l.width, l.height, DXGI_FORMAT(l.format), l.pitch, l.pitch * l.height, pixels }; }
 
@@ -89,7 +48,7 @@ static int save_many(const char* list)
     for (size_t i = 0; i < lines.size(); ++i)
     {
         if (!read_file(lines[i].path, data)) { std::fprintf(stderr, "cannot read %s\n", lines[i].path.c_str()); return 1; }
-        const Exact exact(data);
+        const Exact exact(data.data(), data.size());
         const HRESULT hr = SaveToJPEGMemory(image_of(lines[i], exact.p), JPEG_FLAGS_NONE, blob);
         if (FAILED(hr) && (blob.GetBufferPointer() || blob.GetBufferSize())) { std::fprintf(stderr, "%zu: the blob was not released\n", i); return 1; }
         if (SUCCEEDED(hr) && !write_file(numbered(list, i), blob.GetBufferPointer(), blob.GetBufferSize())) return 1;
@@ -100,15 +59,13 @@ static int save_many(const char* list)
 
 static int resave_many(const char* list)
 {
-    std::vector<std::string> files;
-    std::ifstream in(list);
-    for (std::string line; std::getline(in, line);) if (!line.empty()) files.push_back(line);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     Blob blob; JPEGRawImage raw;
     for (size_t i = 0; i < files.size(); ++i)
     {
         if (!read_file(files[i], data)) { std::fprintf(stderr, "cannot read %s\n", files[i].c_str()); return 1; }
-        const Exact exact(data);
+        const Exact exact(data.data(), data.size());
         const HRESULT loadHr = LoadFromJPEGMemoryRaw(exact.p, exact.n, JPEG_FLAGS_NONE, nullptr, raw);
         const HRESULT hr = SUCCEEDED(loadHr) ? SaveJPEGRaw(raw, blob) : loadHr;
         if (SUCCEEDED(hr) && !write_file(numbered(list, i), blob.GetBufferPointer(), blob.GetBufferSize())) return 1;
@@ -210,10 +167,10 @@ static int sweep()
                 const size_t pitch = w * k.texel + k.pad;
                 std::vector<uint8_t> px(pitch * (h - 1) + w * k.texel);          // the last row ends with its last texel
                 for (uint8_t& b : px) b = uint8_t(lcg(seed));
-                const Exact exact(px);
+                const Exact exact(px.data(), px.size());
                 HRESULT hr = SaveToJPEGMemory(Image{ w, h, k.format, pitch, pitch * h, exact.p }, JPEG_FLAGS_NONE, blob);
                 if (FAILED(hr)) { std::fprintf(stderr, "%zux%zu format %u: save %08x\n", w, h, unsigned(k.format), unsigned(hr)); return 1; }
-                const Exact file(std::vector<uint8_t>(blob.GetBufferPointer(), blob.GetBufferPointer() + blob.GetBufferSize()));
+                const Exact file(blob.GetBufferPointer(), blob.GetBufferSize());
                 TexMetadata md;
                 hr = LoadFromJPEGMemory(file.p, file.n, JPEG_FLAGS_NONE, &md, loaded);
                 if (FAILED(hr) || md.width != w || md.height != h || md.format != k.loads) { std::fprintf(stderr, "%zux%zu format %u: load %08x\n", w, h, unsigned(k.format), unsigned(hr)); return 1; }
@@ -226,20 +183,6 @@ static int sweep()
         }
     std::printf("sweep ok %zu\n", files);
     return 0;
-}
-
-// launches of kernels whose mark starts with "jpeg_" since profile_begin
-static unsigned jpeg_launches(Device& dev)
-{
-    char names[4096] = {};
-    float ms[64]; uint32_t launches[64]; size_t count = 0;
-    if (dxtex_ctx_profile_end(dev.Get(), names, sizeof(names), ms, launches, 64, &count) != DXTEX_S_OK) return 999;
-    unsigned total = 0;
-    std::istringstream ss(names);
-    std::string name;
-    for (size_t i = 0; i < count && std::getline(ss, name); ++i)
-        if (name.rfind("jpeg_", 0) == 0) total += launches[i];
-    return total;
 }
 
 // the image of a line on the device, through a ScratchImage of its format
@@ -273,12 +216,9 @@ static int device_save_many(const char* list)
         const Image* img = resident.GetImage(0, 0, 0);
         if (!img) return 1;
         blob.Initialize(16);          // a failure must leave it empty whatever it held before
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
-        dxtex_ctx_profile_begin(dev.Get());
+        Window window(dev);
         const HRESULT hr = SaveToJPEGMemory(dev, *img, JPEG_FLAGS_NONE, blob);
-        const unsigned launches = jpeg_launches(dev);
-        GetTransferBytes(dev, up1, down1);
+        const unsigned launches = window.end({ "jpeg_" })[0].launches;
         if (FAILED(hr))
         {
             std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), (blob.GetBufferPointer() || blob.GetBufferSize()) ? "held" : "empty");
@@ -288,18 +228,10 @@ static int device_save_many(const char* list)
         if (FAILED(LoadFromJPEGMemoryRaw(blob.GetBufferPointer(), blob.GetBufferSize(), JPEG_FLAGS_NONE, nullptr, raw))) { std::fprintf(stderr, "%zu: the file does not load\n", i); return 1; }
         if (!write_file(numbered(list, i), blob.GetBufferPointer(), blob.GetBufferSize())) return 1;
         const bool equal = SUCCEEDED(hostHr) && blob.GetBufferSize() == host.GetBufferSize() && !std::memcmp(blob.GetBufferPointer(), host.GetBufferPointer(), host.GetBufferSize());
-        std::printf("%zu %08x %08x ok %zu %llu %llu %d %u\n", i, unsigned(hr), unsigned(hostHr), raw.coefficientCount * 2, (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0),
+        std::printf("%zu %08x %08x ok %zu %llu %llu %d %u\n", i, unsigned(hr), unsigned(hostHr), raw.coefficientCount * 2, (unsigned long long)window.up, (unsigned long long)window.down,
                     int(equal), launches);
     }
     return 0;
-}
-
-template<class F>
-static double timed_ms(F&& f)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    f();
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // a gradient with noise through the resident saver and through Download plus the host saver, alternating, `runs` times each after one
@@ -318,21 +250,18 @@ static int time_save(size_t width, size_t height, unsigned format, int runs)
     DeviceScratchImage resident;
     if (FAILED(resident.Upload(dev, host))) return 1;
     const Image* dimg = resident.GetImage(0, 0, 0);
-    bool ok = dimg != nullptr;
+    if (!dimg) { std::fprintf(stderr, "a step failed\n"); return 1; }
+    bool ok = true;
     Blob a, b;
-    for (int i = -1; i < runs && ok; ++i)
-    {
-        uint64_t up0, down0, up1, down1, up2, down2;
-        GetTransferBytes(dev, up0, down0);
-        const double ta = timed_ms([&] { ok = ok && SUCCEEDED(SaveToJPEGMemory(dev, *dimg, JPEG_FLAGS_NONE, a)); });
-        GetTransferBytes(dev, up1, down1);
-        const double tb = timed_ms([&] { ScratchImage back; ok = ok && SUCCEEDED(resident.Download(back)) && SUCCEEDED(SaveToJPEGMemory(*back.GetImage(0, 0, 0), JPEG_FLAGS_NONE, b)); });
-        GetTransferBytes(dev, up2, down2);
-        ok = ok && a.GetBufferSize() == b.GetBufferSize() && !std::memcmp(a.GetBufferPointer(), b.GetBufferPointer(), a.GetBufferSize());
-        if (i >= 0) std::printf("run %d resident %.3f ms up %llu down %llu host %.3f ms up %llu down %llu file %zu\n", i, ta, (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0),
-                                tb, (unsigned long long)(up2 - up1), (unsigned long long)(down2 - down1), a.GetBufferSize());
-    }
-    if (!ok) { std::fprintf(stderr, "a step failed\n"); return 1; }
+    const int failed = time_runs(dev, runs,
+        [&] { return timed_ms([&] { ok = ok && SUCCEEDED(SaveToJPEGMemory(dev, *dimg, JPEG_FLAGS_NONE, a)); }); },
+        [&] { return timed_ms([&] { ScratchImage back; ok = ok && SUCCEEDED(resident.Download(back)) && SUCCEEDED(SaveToJPEGMemory(*back.GetImage(0, 0, 0), JPEG_FLAGS_NONE, b)); }); },
+        [&](std::string& extra)
+        {
+            extra = " file " + std::to_string(a.GetBufferSize());
+            return ok && a.GetBufferSize() == b.GetBufferSize() && !std::memcmp(a.GetBufferPointer(), b.GetBufferPointer(), a.GetBufferSize());
+        });
+    if (failed) return failed;
     JPEGRawImage raw;
     if (FAILED(LoadFromJPEGMemoryRaw(a.GetBufferPointer(), a.GetBufferSize(), JPEG_FLAGS_NONE, nullptr, raw))) return 1;
     for (int i = -1; i < runs; ++i)

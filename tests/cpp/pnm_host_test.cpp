@@ -17,70 +17,17 @@
 //       hex> <host hresult hex> <bytes host -> device> <bytes device -> host>" counted around the resident save alone
 //   pnm_host_test time_load <file> <runs> | time_save <file> <runs> <hdr 0|1>
 //       for tools/pnm_bench.py: wall time and bytes moved of the resident path beside the same build's host path, one line per run
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-#include "../../include/dxtex_amd.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
-
-static bool write_file(const std::string& path, const void* p, size_t bytes)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = bytes == 0 || std::fwrite(p, 1, bytes, f) == bytes;
-    return (std::fclose(f) == 0) && ok;
-}
-
-static std::vector<std::string> read_list(const char* path)
-{
-    std::vector<std::string> files;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);) if (!line.empty()) files.push_back(line);
-    return files;
-}
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
-}
-
-// an exact-size copy on the heap: a read past the file's last byte is a read past an allocation
-struct Exact
-{
-    uint8_t* p = nullptr; size_t n = 0;
-    explicit Exact(const std::vector<uint8_t>& v) : n(v.size()) { p = static_cast<uint8_t*>(std::malloc(n ? n : 1)); if (n) std::memcpy(p, v.data(), n); }
-    ~Exact() { std::free(p); }
-};
+#include "codec_host_test.h"
 
 static int load_many(const char* list)
 {
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     PNMRawImage raw; ScratchImage image;          // one object each for every file: a failure must leave it empty whatever it held before
     for (size_t i = 0; i < files.size(); ++i)
     {
         if (!read_file(files[i], data)) { std::fprintf(stderr, "cannot read %s\n", files[i].c_str()); return 1; }
-        const Exact exact(data);
+        const Exact exact(data.data(), data.size());
         TexMetadata rawMd, md;
         const HRESULT rawHr = LoadFromPortablePixMapMemoryRaw(exact.p, exact.n, &rawMd, raw);
         const HRESULT hr = LoadFromPortablePixMapMemory(exact.p, exact.n, &md, image);
@@ -103,14 +50,6 @@ static int load_many(const char* list)
     return 0;
 }
 
-static bool image_arg(char** a, std::vector<uint8_t>& px, Image& src)
-{
-    if (!read_file(a[0], px)) return false;
-    src.width = size_t(std::atoll(a[1])); src.height = size_t(std::atoll(a[2])); src.format = DXGI_FORMAT(std::atoi(a[3]));
-    src.rowPitch = size_t(std::atoll(a[4])); src.slicePitch = src.rowPitch * src.height; src.pixels = px.data();
-    return px.size() >= src.slicePitch;
-}
-
 static int save(char** a)
 {
     std::vector<uint8_t> px; Image src;
@@ -127,7 +66,7 @@ static int device_load_many(const char* list)
 {
     Device dev;
     if (FAILED(dev.Create(0))) { std::fprintf(stderr, "no device\n"); return 1; }
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     DeviceScratchImage image;
     for (size_t i = 0; i < files.size(); ++i)
@@ -138,23 +77,17 @@ static int device_load_many(const char* list)
         const uint8_t* source = data.empty() ? &none : data.data();          // an empty file is a size of zero, not a null pointer
         const HRESULT hostHr = LoadFromPortablePixMapMemory(source, data.size(), &hostMd, host);
         (void)LoadFromPortablePixMapMemoryRaw(source, data.size(), &rawMd, raw);
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromPortablePixMapMemory(dev, source, data.size(), &md, image);
-        GetTransferBytes(dev, up1, down1);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released ? "released" : "held");
-            continue;
-        }
+        window.end();
+        if (FAILED(hr)) { std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released(image) ? "released" : "held"); continue; }
         ScratchImage back;
         if (FAILED(image.Download(back))) { std::fprintf(stderr, "%s: download failed\n", files[i].c_str()); return 1; }
         const bool metaEqual = SUCCEEDED(hostHr) && same_metadata(md, hostMd) && same_metadata(image.GetMetadata(), host.GetMetadata());
         const bool pixelsEqual = SUCCEEDED(hostHr) && back.GetPixelsSize() == host.GetPixelsSize() && !std::memcmp(back.GetPixels(), host.GetPixels(), host.GetPixelsSize());
         std::printf("%zu %08x %08x ok %zu %zu %u %zu %d %llu %llu %d %d\n", i, unsigned(hr), unsigned(hostHr), md.width, md.height, unsigned(md.format), raw.payloadBytes, int(raw.ascii),
-                    (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), int(metaEqual), int(pixelsEqual));
+                    (unsigned long long)window.up, (unsigned long long)window.down, int(metaEqual), int(pixelsEqual));
     }
     return 0;
 }
@@ -171,26 +104,17 @@ static int device_save(char** a)
     DeviceScratchImage image;
     HRESULT hr = image.Upload(dev, &src, 1, md);
     if (FAILED(hr)) { std::printf("upload %08x\n", unsigned(hr)); return 1; }
-    uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-    GetTransferBytes(dev, up0, down0);
+    Window window(dev);
     hr = hdr ? SaveToPortablePixMapHDRFile(dev, *image.GetImage(0, 0, 0), a[6]) : SaveToPortablePixMapFile(dev, *image.GetImage(0, 0, 0), a[6]);
-    GetTransferBytes(dev, up1, down1);
+    window.end();
     const std::string hostOut = std::string(a[6]) + ".host";
     const HRESULT hostHr = hdr ? SaveToPortablePixMapHDRFile(src, hostOut.c_str()) : SaveToPortablePixMapFile(src, hostOut.c_str());
-    std::printf("hr %08x %08x %llu %llu\n", unsigned(hr), unsigned(hostHr), (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0));
+    std::printf("hr %08x %08x %llu %llu\n", unsigned(hr), unsigned(hostHr), (unsigned long long)window.up, (unsigned long long)window.down);
     return 0;
 }
 
 // tools/pnm_bench.py: a file through the resident loader and through the host loader plus Upload, alternating, `runs` times each after one
 // unmeasured run each; a resident image through the resident saver and through Download plus the host saver likewise
-template<class F>
-static double timed_ms(F&& f)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    f();
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 static int time_paths(const char* file, int runs, bool saveHdr, bool save)
 {
     Device dev;
@@ -201,32 +125,20 @@ static int time_paths(const char* file, int runs, bool saveHdr, bool save)
     TexMetadata md;
     if (FAILED(LoadFromPortablePixMapMemory(dev, data.data(), data.size(), &md, resident))) return 1;
     bool ok = true;
-    for (int i = -1; i < runs; ++i)
+    if (save)
     {
-        uint64_t up0, down0, up1, down1, up2, down2;
-        double a, b;
-        GetTransferBytes(dev, up0, down0);
-        if (!save)
-        {
-            a = timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromPortablePixMapMemory(dev, data.data(), data.size(), nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-            GetTransferBytes(dev, up1, down1);
-            b = timed_ms([&] { ScratchImage host; DeviceScratchImage image;
-                               ok = ok && SUCCEEDED(LoadFromPortablePixMapMemory(data.data(), data.size(), nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-        }
-        else
-        {
-            const Image& img = *resident.GetImage(0, 0, 0);
-            a = timed_ms([&] { Blob blob; ok = ok && SUCCEEDED(saveHdr ? SaveToPortablePixMapHDRMemory(dev, img, blob) : SaveToPortablePixMapMemory(dev, img, blob)); });
-            GetTransferBytes(dev, up1, down1);
-            b = timed_ms([&] { Blob blob; ScratchImage host;
-                               ok = ok && SUCCEEDED(resident.Download(host)) && SUCCEEDED(saveHdr ? SaveToPortablePixMapHDRMemory(*host.GetImage(0, 0, 0), blob) : SaveToPortablePixMapMemory(*host.GetImage(0, 0, 0), blob)); });
-        }
-        GetTransferBytes(dev, up2, down2);
-        if (!ok) { std::fprintf(stderr, "a step failed\n"); return 1; }
-        if (i >= 0) std::printf("run %d resident %.3f ms up %llu down %llu host %.3f ms up %llu down %llu\n", i, a, (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0),
-                                b, (unsigned long long)(up2 - up1), (unsigned long long)(down2 - down1));
+        const Image& img = *resident.GetImage(0, 0, 0);
+        return time_runs(dev, runs,
+            [&] { return timed_ms([&] { Blob blob; ok = ok && SUCCEEDED(saveHdr ? SaveToPortablePixMapHDRMemory(dev, img, blob) : SaveToPortablePixMapMemory(dev, img, blob)); }); },
+            [&] { return timed_ms([&] { Blob blob; ScratchImage host;
+                                        ok = ok && SUCCEEDED(resident.Download(host)) && SUCCEEDED(saveHdr ? SaveToPortablePixMapHDRMemory(*host.GetImage(0, 0, 0), blob) : SaveToPortablePixMapMemory(*host.GetImage(0, 0, 0), blob)); }); },
+            [&](std::string&) { return ok; });
     }
-    return 0;
+    return time_runs(dev, runs,
+        [&] { return timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromPortablePixMapMemory(dev, data.data(), data.size(), nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&] { return timed_ms([&] { ScratchImage host; DeviceScratchImage image;
+                                    ok = ok && SUCCEEDED(LoadFromPortablePixMapMemory(data.data(), data.size(), nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&](std::string&) { return ok; });
 }
 
 int main(int argc, char** argv)

@@ -16,44 +16,13 @@
 //       the image goes up, the resident SaveToTGAFile writes <out.tga> and the host one <out.tga>.host from the same pixels (alpha mode >= 0:
 //       with metadata, so with the extension area); prints "hr <resident hresult hex> <host hresult hex> <bytes host -> device>
 //       <bytes device -> host>" counted around the resident save alone
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
-
-static bool write_file(const std::string& path, const void* p, size_t bytes)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = bytes == 0 || std::fwrite(p, 1, bytes, f) == bytes;
-    return (std::fclose(f) == 0) && ok;
-}
+#include "codec_host_test.h"
 
 struct Entry { std::string path; TGA_FLAGS flags; };
 static std::vector<Entry> read_list(const char* path)
 {
     std::vector<Entry> files;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);)
+    for (const std::string& line : read_lines(path))
     {
         std::istringstream ss(line);
         Entry e; unsigned long flags;
@@ -70,10 +39,9 @@ static int raw_load_many(const char* list)
     for (size_t i = 0; i < files.size(); ++i)
     {
         if (!read_file(files[i].path, data)) { std::fprintf(stderr, "cannot read %s\n", files[i].path.c_str()); return 1; }
-        // an exact-size copy on the heap: a read past the file's last byte is a read past an allocation
-        std::vector<uint8_t> exact(data.begin(), data.end());
+        const Exact exact(data.data(), data.size());
         TexMetadata md;
-        const HRESULT hr = LoadFromTGAMemoryRaw(exact.empty() ? nullptr : exact.data(), exact.size(), files[i].flags, &md, raw);
+        const HRESULT hr = LoadFromTGAMemoryRaw(exact.n ? exact.p : nullptr, exact.n, files[i].flags, &md, raw);
         if (FAILED(hr))
         {
             if (raw.texels || raw.storage.GetBufferPointer()) { std::fprintf(stderr, "%s: the texels were not released\n", files[i].path.c_str()); return 1; }
@@ -81,7 +49,7 @@ static int raw_load_many(const char* list)
             continue;
         }
         if (raw.texelBytes != md.width * md.height * raw.bytesPerTexel) { std::fprintf(stderr, "%s: %zu bytes of texels\n", files[i].path.c_str(), raw.texelBytes); return 1; }
-        const bool inside = raw.texels >= exact.data() && raw.texels + raw.texelBytes <= exact.data() + exact.size();
+        const bool inside = raw.texels >= exact.p && raw.texels + raw.texelBytes <= exact.p + exact.n;
         if (inside == (raw.storage.GetBufferPointer() != nullptr)) { std::fprintf(stderr, "%s: texels neither in the file nor in the blob\n", files[i].path.c_str()); return 1; }
         if (!write_file(files[i].path + ".texels", raw.texels, raw.texelBytes) || !write_file(files[i].path + ".palette", raw.palette, sizeof(raw.palette))) return 1;
         TexMetadata ruled = md;
@@ -90,12 +58,6 @@ static int raw_load_many(const char* list)
                     unsigned(raw.format), raw.bytesPerTexel, int(raw.rightToLeft), int(raw.topDown), int(raw.paletted), int(inside));
     }
     return 0;
-}
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
 }
 
 static int device_load_many(const char* list)
@@ -110,24 +72,18 @@ static int device_load_many(const char* list)
         if (!read_file(files[i].path, data)) { std::fprintf(stderr, "cannot read %s\n", files[i].path.c_str()); return 1; }
         TexMetadata hostMd; ScratchImage host;
         const HRESULT hostHr = LoadFromTGAMemory(data.empty() ? nullptr : data.data(), data.size(), files[i].flags, &hostMd, host);
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromTGAMemory(dev, data.empty() ? nullptr : data.data(), data.size(), files[i].flags, &md, image);
-        GetTransferBytes(dev, up1, down1);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released ? "released" : "held");
-            continue;
-        }
+        window.end();
+        if (FAILED(hr)) { std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released(image) ? "released" : "held"); continue; }
         ScratchImage back;
         if (FAILED(image.Download(back))) { std::fprintf(stderr, "%s: download failed\n", files[i].path.c_str()); return 1; }
         const bool metaEqual = SUCCEEDED(hostHr) && same_metadata(md, hostMd) && same_metadata(image.GetMetadata(), host.GetMetadata());
         const bool pixelsEqual = SUCCEEDED(hostHr) && back.GetPixelsSize() == host.GetPixelsSize() && !std::memcmp(back.GetPixels(), host.GetPixels(), host.GetPixelsSize());
         if (!write_file(files[i].path + ".out", back.GetPixels(), back.GetPixelsSize())) return 1;
         std::printf("%zu %08x %08x ok %zu %zu %u %u %u %llu %llu %d %d\n", i, unsigned(hr), unsigned(hostHr), md.width, md.height, unsigned(md.format), unsigned(md.miscFlags2),
-                    unsigned(image.GetMetadata().format), (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), int(metaEqual), int(pixelsEqual));
+                    unsigned(image.GetMetadata().format), (unsigned long long)window.up, (unsigned long long)window.down, int(metaEqual), int(pixelsEqual));
     }
     return 0;
 }
@@ -136,12 +92,8 @@ static int device_save(char** a)
 {
     Device dev;
     if (FAILED(dev.Create(0))) { std::fprintf(stderr, "no device\n"); return 1; }
-    std::vector<uint8_t> px;
-    if (!read_file(a[0], px)) return 1;
-    Image src;
-    src.width = size_t(std::atoll(a[1])); src.height = size_t(std::atoll(a[2])); src.format = DXGI_FORMAT(std::atoi(a[3]));
-    src.rowPitch = size_t(std::atoll(a[4])); src.slicePitch = src.rowPitch * src.height; src.pixels = px.data();
-    if (px.size() < src.slicePitch) return 1;
+    std::vector<uint8_t> px; Image src;
+    if (!image_arg(a, px, src)) return 1;
     const TGA_FLAGS flags = TGA_FLAGS(std::strtoul(a[5], nullptr, 0));
     const int alphaMode = std::atoi(a[7]);
     TexMetadata md;
@@ -151,12 +103,11 @@ static int device_save(char** a)
     if (FAILED(hr)) { std::printf("upload %08x\n", unsigned(hr)); return 1; }
     if (alphaMode >= 0) md.SetAlphaMode(TEX_ALPHA_MODE(alphaMode));
     const TexMetadata* with = alphaMode >= 0 ? &md : nullptr;
-    uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-    GetTransferBytes(dev, up0, down0);
+    Window window(dev);
     hr = SaveToTGAFile(dev, *image.GetImage(0, 0, 0), flags, a[6], with);
-    GetTransferBytes(dev, up1, down1);
+    window.end();
     const HRESULT hostHr = SaveToTGAFile(src, flags, (std::string(a[6]) + ".host").c_str(), with);
-    std::printf("hr %08x %08x %llu %llu\n", unsigned(hr), unsigned(hostHr), (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0));
+    std::printf("hr %08x %08x %llu %llu\n", unsigned(hr), unsigned(hostHr), (unsigned long long)window.up, (unsigned long long)window.down);
     return 0;
 }
 

@@ -24,62 +24,8 @@
 //       for tools/tiff_bench.py: wall time and bytes moved of the resident load beside the same build's host load plus Upload, one line per
 //       run, with the Raw loader's time alone ("raw"), the host's serial undo of the same stream ("undo") and the device's kernels ("undo_gpu",
 //       "texels_gpu", from the context's profile)
-#include "../../directxtex_amd/host/DirectXTexAMD.h"
+#include "codec_host_test.h"
 #include "../../directxtex_amd/csrc/dxtex_tiff.h"
-#include "../../include/dxtex_amd.h"
-
-#include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
-
-using namespace DirectXTexAMD;
-
-static bool read_file(const std::string& path, std::vector<uint8_t>& buf)
-{
-    FILE* f = std::fopen(path.c_str(), "rb");
-    if (!f) return false;
-    buf.clear();
-    uint8_t chunk[65536];
-    size_t n;
-    while ((n = std::fread(chunk, 1, sizeof(chunk), f)) > 0) buf.insert(buf.end(), chunk, chunk + n);
-    std::fclose(f);
-    return true;
-}
-
-static bool write_file(const std::string& path, const void* p, size_t bytes)
-{
-    FILE* f = std::fopen(path.c_str(), "wb");
-    if (!f) return false;
-    const bool ok = bytes == 0 || std::fwrite(p, 1, bytes, f) == bytes;
-    return (std::fclose(f) == 0) && ok;
-}
-
-static std::vector<std::string> read_list(const char* path)
-{
-    std::vector<std::string> files;
-    std::ifstream in(path);
-    for (std::string line; std::getline(in, line);) if (!line.empty()) files.push_back(line);
-    return files;
-}
-
-static bool same_metadata(const TexMetadata& a, const TexMetadata& b)
-{
-    return a.width == b.width && a.height == b.height && a.depth == b.depth && a.arraySize == b.arraySize && a.mipLevels == b.mipLevels &&
-           a.miscFlags == b.miscFlags && a.miscFlags2 == b.miscFlags2 && a.format == b.format && a.dimension == b.dimension;
-}
-
-// an exact-size copy on the heap: a read past the file's last byte is a read past an allocation
-struct Exact
-{
-    uint8_t* p = nullptr; size_t n = 0;
-    Exact(const uint8_t* s, size_t bytes) : n(bytes) { p = static_cast<uint8_t*>(std::malloc(n ? n : 1)); if (n) std::memcpy(p, s, n); }
-    ~Exact() { std::free(p); }
-};
 
 // both loaders on one buffer; what a failure must leave behind is checked here
 static bool load_both(const uint8_t* p, size_t n, TIFF_FLAGS flags, TIFFRawImage& raw, ScratchImage& image, TexMetadata& rawMd, TexMetadata& md, HRESULT& rawHr, HRESULT& hr, const char* what)
@@ -94,7 +40,7 @@ static bool load_both(const uint8_t* p, size_t n, TIFF_FLAGS flags, TIFFRawImage
 
 static int load_many(const char* list, TIFF_FLAGS flags)
 {
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     TIFFRawImage raw; ScratchImage image;          // one object each for every file: a failure must leave it empty whatever it held before
     for (size_t i = 0; i < files.size(); ++i)
@@ -123,32 +69,12 @@ static int load_many(const char* list, TIFF_FLAGS flags)
 
 static int damaged(const char* file, bool truncations, uint64_t seed, size_t cases)
 {
-    std::vector<uint8_t> data;
-    if (!read_file(file, data) || data.empty()) return 1;
     TIFFRawImage raw; ScratchImage image;
-    size_t loaded = 0, refused = 0;
-    uint64_t s = seed * 6364136223846793005ull + 1442695040888963407ull;
-    auto next = [&] { s = s * 6364136223846793005ull + 1442695040888963407ull; return uint32_t(s >> 33); };
-    if (truncations) cases = data.size();
-    for (size_t i = 0; i < cases; ++i)
+    return damaged_copies(file, truncations, seed, cases, [&](const uint8_t* p, size_t n, HRESULT& hr)
     {
-        std::vector<uint8_t> copy(data.begin(), truncations ? data.begin() + i : data.end());
-        if (!truncations)
-            for (uint32_t k = 1 + next() % 4; k; --k)
-            {
-                const size_t at = next() % copy.size();
-                const uint32_t how = next() % 3;
-                copy[at] = how == 0 ? uint8_t(next()) : how == 1 ? uint8_t(copy[at] ^ (1u << (next() % 8))) : (next() & 1 ? 0xFF : 0x00);
-            }
-        const Exact exact(copy.data(), copy.size());
-        TexMetadata rawMd, md;
-        HRESULT rawHr, hr;
-        if (!load_both(exact.p, exact.n, TIFF_FLAGS_NONE, raw, image, rawMd, md, rawHr, hr, "a damaged copy")) return 1;
-        if (truncations && SUCCEEDED(hr)) { std::fprintf(stderr, "a prefix of %zu bytes loaded\n", i); return 1; }
-        if (SUCCEEDED(hr)) ++loaded; else ++refused;
-    }
-    std::printf("%s %zu %zu\n", truncations ? "truncations" : "fuzz", loaded, refused);
-    return 0;
+        TexMetadata rawMd, md; HRESULT rawHr;
+        return load_both(p, n, TIFF_FLAGS_NONE, raw, image, rawMd, md, rawHr, hr, "a damaged copy");
+    });
 }
 
 static int files(const char* file)
@@ -167,14 +93,6 @@ static int files(const char* file)
     return 0;
 }
 
-static bool image_arg(char** a, std::vector<uint8_t>& px, Image& src)
-{
-    if (!read_file(a[0], px)) return false;
-    src.width = size_t(std::atoll(a[1])); src.height = size_t(std::atoll(a[2])); src.format = DXGI_FORMAT(std::atoi(a[3]));
-    src.rowPitch = size_t(std::atoll(a[4])); src.slicePitch = src.rowPitch * src.height; src.pixels = px.data();
-    return px.size() >= src.slicePitch;
-}
-
 static int save(char** a)
 {
     std::vector<uint8_t> px; Image src;
@@ -187,25 +105,11 @@ static int save(char** a)
     return 0;
 }
 
-// launches and milliseconds of the kernels whose mark starts with each prefix, since profile_begin
-static void tiff_launches(Device& dev, unsigned (&total)[3], float (&time)[3])
-{
-    static const char* const prefix[3] = { "tiff_undo", "tiff_texels", "tiff_pack" };
-    char names[4096] = {};
-    float ms[64]; uint32_t launches[64]; size_t count = 0;
-    for (int k = 0; k < 3; ++k) { total[k] = 0; time[k] = 0; }
-    if (dxtex_ctx_profile_end(dev.Get(), names, sizeof(names), ms, launches, 64, &count) != DXTEX_S_OK) { total[0] = total[1] = total[2] = 999; return; }
-    std::istringstream ss(names);
-    std::string name;
-    for (size_t i = 0; i < count && std::getline(ss, name); ++i)
-        for (int k = 0; k < 3; ++k) if (name.rfind(prefix[k], 0) == 0) { total[k] += launches[i]; time[k] += ms[i]; }
-}
-
 static int device_load_many(const char* list, TIFF_FLAGS flags)
 {
     Device dev;
     if (FAILED(dev.Create(0))) { std::fprintf(stderr, "no device\n"); return 1; }
-    const std::vector<std::string> files = read_list(list);
+    const std::vector<std::string> files = read_lines(list);
     std::vector<uint8_t> data;
     DeviceScratchImage image;
     for (size_t i = 0; i < files.size(); ++i)
@@ -216,34 +120,17 @@ static int device_load_many(const char* list, TIFF_FLAGS flags)
         const uint8_t* source = data.empty() ? &none : data.data();          // an empty file is a size of zero, not a null pointer
         const HRESULT hostHr = LoadFromTIFFMemory(source, data.size(), flags, &hostMd, host);
         (void)LoadFromTIFFMemoryRaw(source, data.size(), flags, &rawMd, raw);
-        uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-        GetTransferBytes(dev, up0, down0);
-        dxtex_ctx_profile_begin(dev.Get());
+        Window window(dev);
         TexMetadata md;
         const HRESULT hr = LoadFromTIFFMemory(dev, source, data.size(), flags, &md, image);
-        unsigned launches[3]; float ms[3];
-        tiff_launches(dev, launches, ms);
-        GetTransferBytes(dev, up1, down1);
-        if (FAILED(hr))
-        {
-            const bool released = image.GetImageCount() == 0 && image.GetPixels() == nullptr && image.GetImages() == nullptr;
-            std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released ? "released" : "held");
-            continue;
-        }
+        const std::vector<Window::Mark> marks = window.end({ "tiff_undo", "tiff_texels" });
+        if (FAILED(hr)) { std::printf("%zu %08x %08x %s\n", i, unsigned(hr), unsigned(hostHr), released(image) ? "released" : "held"); continue; }
         ScratchImage back;
         if (FAILED(image.Download(back))) { std::fprintf(stderr, "%s: download failed\n", files[i].c_str()); return 1; }
         const bool metaEqual = SUCCEEDED(hostHr) && same_metadata(md, hostMd) && same_metadata(image.GetMetadata(), host.GetMetadata());
-        bool pixelsEqual = SUCCEEDED(hostHr) && back.GetImageCount() == 1 && host.GetImageCount() == 1;
-        if (pixelsEqual)
-        {
-            // the rows' texels: the pitches of the two images may differ
-            const Image& a = *back.GetImage(0, 0, 0); const Image& b = *host.GetImage(0, 0, 0);
-            size_t rp = 0, sp = 0;
-            pixelsEqual = SUCCEEDED(ComputePitch(md.format, md.width, md.height, rp, sp));
-            for (size_t y = 0; pixelsEqual && y < md.height; ++y) pixelsEqual = !std::memcmp(a.pixels + y * a.rowPitch, b.pixels + y * b.rowPitch, rp);
-        }
+        const bool pixelsEqual = SUCCEEDED(hostHr) && back.GetImageCount() == 1 && host.GetImageCount() == 1 && same_texels(*back.GetImage(0, 0, 0), *host.GetImage(0, 0, 0));
         std::printf("%zu %08x %08x ok %zu %zu %zu %llu %llu %d %d %u %u\n", i, unsigned(hr), unsigned(hostHr), md.width, md.height, raw.streamBytes,
-                    (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), int(metaEqual), int(pixelsEqual), launches[0], launches[1]);
+                    (unsigned long long)window.up, (unsigned long long)window.down, int(metaEqual), int(pixelsEqual), marks[0].launches, marks[1].launches);
     }
     return 0;
 }
@@ -260,25 +147,13 @@ static int device_save(char** a)
     DeviceScratchImage image;
     HRESULT hr = image.Upload(dev, &src, 1, md);
     if (FAILED(hr)) { std::printf("upload %08x\n", unsigned(hr)); return 1; }
-    uint64_t up0 = 0, down0 = 0, up1 = 0, down1 = 0;
-    GetTransferBytes(dev, up0, down0);
-    dxtex_ctx_profile_begin(dev.Get());
+    Window window(dev);
     hr = SaveToTIFFFile(dev, *image.GetImage(0, 0, 0), flags, a[6]);
-    unsigned launches[3]; float ms[3];
-    tiff_launches(dev, launches, ms);
-    GetTransferBytes(dev, up1, down1);
+    const std::vector<Window::Mark> marks = window.end({ "tiff_pack" });
     const std::string hostOut = std::string(a[6]) + ".host";
     const HRESULT hostHr = SaveToTIFFFile(src, flags, hostOut.c_str());
-    std::printf("hr %08x %08x %llu %llu %u\n", unsigned(hr), unsigned(hostHr), (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), launches[2]);
+    std::printf("hr %08x %08x %llu %llu %u\n", unsigned(hr), unsigned(hostHr), (unsigned long long)window.up, (unsigned long long)window.down, marks[0].launches);
     return 0;
-}
-
-template<class F>
-static double timed_ms(F&& f)
-{
-    const auto t0 = std::chrono::steady_clock::now();
-    f();
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 static int time_load(const char* file, int runs)
@@ -288,37 +163,38 @@ static int time_load(const char* file, int runs)
     std::vector<uint8_t> data;
     if (!read_file(file, data)) return 1;
     bool ok = true;
-    for (int i = -1; i < runs; ++i)
-    {
-        uint64_t up0, down0, up1, down1, up2, down2;
-        double rawMs = 0, undoMs = 0;
-        GetTransferBytes(dev, up0, down0);
-        dxtex_ctx_profile_begin(dev.Get());
-        const double a = timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromTIFFMemory(dev, data.data(), data.size(), TIFF_FLAGS_NONE, nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-        unsigned launches[3]; float ms[3];
-        tiff_launches(dev, launches, ms);
-        GetTransferBytes(dev, up1, down1);
-        const double b = timed_ms([&] { ScratchImage host; DeviceScratchImage image;
-                                        ok = ok && SUCCEEDED(LoadFromTIFFMemory(data.data(), data.size(), TIFF_FLAGS_NONE, nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
-        TIFFRawImage raw;
-        rawMs = timed_ms([&] { ok = ok && SUCCEEDED(LoadFromTIFFMemoryRaw(data.data(), data.size(), TIFF_FLAGS_NONE, nullptr, raw)); });
-        // the host's serial undo of the same stream
-        if (ok) undoMs = timed_ms([&]
+    std::vector<Window::Mark> marks;
+    return time_runs(dev, runs,
+        [&]
         {
-            const dxtex::TiffLayout l{ raw.layout.width, raw.layout.height, raw.layout.bits, raw.layout.samples, raw.layout.kind, raw.layout.predictor, raw.layout.bigEndian, raw.layout.planar,
-                                       raw.layout.whiteIsZero, raw.layout.opaque };
-            for (size_t c = 0; c < raw.segmentCount; ++c)
+            Window window(dev);          // the kernels' own milliseconds, read outside the timed call
+            const double ms = timed_ms([&] { DeviceScratchImage image; ok = ok && SUCCEEDED(LoadFromTIFFMemory(dev, data.data(), data.size(), TIFF_FLAGS_NONE, nullptr, image)) && dxtex_ctx_synchronize(dev.Get()) == 0; });
+            marks = window.end({ "tiff_undo", "tiff_texels" });
+            return ms;
+        },
+        [&] { return timed_ms([&] { ScratchImage host; DeviceScratchImage image;
+                                    ok = ok && SUCCEEDED(LoadFromTIFFMemory(data.data(), data.size(), TIFF_FLAGS_NONE, nullptr, host)) && SUCCEEDED(image.Upload(dev, host)) && dxtex_ctx_synchronize(dev.Get()) == 0; }); },
+        [&](std::string& extra)
+        {
+            TIFFRawImage raw;
+            const double rawMs = timed_ms([&] { ok = ok && SUCCEEDED(LoadFromTIFFMemoryRaw(data.data(), data.size(), TIFF_FLAGS_NONE, nullptr, raw)); });
+            if (!ok) return false;
+            // the host's serial undo of the same stream
+            const double undoMs = timed_ms([&]
             {
-                const TIFFRawImage::Segment& s = raw.segments[c];
-                dxtex::tiff_undo_segment_serial(raw.storage.GetBufferPointer(), dxtex::TiffSegment{ s.offset, s.firstRow, s.rows, s.firstCol, s.cols, s.rowBytes, s.plane }, l);
-            }
+                const dxtex::TiffLayout l{ raw.layout.width, raw.layout.height, raw.layout.bits, raw.layout.samples, raw.layout.kind, raw.layout.predictor, raw.layout.bigEndian, raw.layout.planar,
+                                           raw.layout.whiteIsZero, raw.layout.opaque };
+                for (size_t c = 0; c < raw.segmentCount; ++c)
+                {
+                    const TIFFRawImage::Segment& s = raw.segments[c];
+                    dxtex::tiff_undo_segment_serial(raw.storage.GetBufferPointer(), dxtex::TiffSegment{ s.offset, s.firstRow, s.rows, s.firstCol, s.cols, s.rowBytes, s.plane }, l);
+                }
+            });
+            char text[128];
+            std::snprintf(text, sizeof(text), " raw %.3f ms undo %.3f ms undo_gpu %.4f ms texels_gpu %.4f ms", rawMs, undoMs, marks[0].ms, marks[1].ms);
+            extra = text;
+            return true;
         });
-        GetTransferBytes(dev, up2, down2);
-        if (!ok) { std::fprintf(stderr, "a step failed\n"); return 1; }
-        if (i >= 0) std::printf("run %d resident %.3f ms up %llu down %llu host %.3f ms up %llu down %llu raw %.3f ms undo %.3f ms undo_gpu %.4f ms texels_gpu %.4f ms\n", i, a,
-                                (unsigned long long)(up1 - up0), (unsigned long long)(down1 - down0), b, (unsigned long long)(up2 - up1), (unsigned long long)(down2 - down1), rawMs, undoMs, ms[0], ms[1]);
-    }
-    return 0;
 }
 
 int main(int argc, char** argv)

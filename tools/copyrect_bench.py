@@ -1,34 +1,18 @@
 """Measures the four rows of profiles/copyrect.md on one MI355X (run from the repository root: python tools/copyrect_bench.py).
 Median of 20 after 5 warm-up calls; '_ms' = dxtex_ctx_last_kernel_ms (the library's event pair around its kernels), '_wall' = 20 queued
 calls + one synchronize, per call - the only clock that covers dxtex_copy_rows_device, which queues a runtime copy and no kernel of ours."""
-import json, os, sys, time
+import json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directxtex_amd as dx
 from directxtex_amd import capi
+import codec_bench
 
 ctx = dx.Context(0)
+med_ms = lambda fn: codec_bench.med_ms(ctx, fn)
+wall_ms = lambda fn: codec_bench.wall_ms(ctx, fn)
 RGBA8, RGBA16F = 28, 10
 N = 8192
-
-def med_ms(fn, reps=20, warm=5):
-    for _ in range(warm): fn()
-    ctx.synchronize()
-    v = []
-    for _ in range(reps):
-        fn(); ctx.synchronize(); v.append(ctx.last_kernel_ms())
-    return float(np.median(v))
-
-def wall_ms(fn, reps=20, warm=5):
-    for _ in range(warm): fn()
-    ctx.synchronize()
-    t = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        for _ in range(reps): fn()
-        ctx.synchronize()
-        t.append((time.perf_counter() - t0) * 1e3 / reps)
-    return float(np.median(t))
 
 src = ctx.device_alloc(N * N * 4); dst = ctx.device_alloc(N * N * 4); dst16 = ctx.device_alloc(N * N * 8)
 host = np.random.default_rng(0).integers(0, 256, N * N * 4, dtype=np.uint8)

@@ -11,10 +11,11 @@ End to end: `dxtexconv -nologo -timing -overlap 1 -y` on files this script write
 - five runs of this build (directxtex_amd/lib/dxtexconv) and, with --parent DIR, five of the dxtexconv in DIR (a build of the parent
 commit), alternating. Prints each run's -timing line figures, the medians, the parent's spread (max - min of its five) and whether the two
 builds' outputs are byte-identical. dxtexconv has no switch for DDS_FLAGS_FORCE_24BPP_RGB, so the 24-bit writer is measured as a kernel only."""
-import argparse, json, os, re, statistics, struct, subprocess, sys, tempfile
+import argparse, json, os, struct, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directxtex_amd as dx
+from codec_bench import measure_conv
 
 N, REPS, RUNS = 4096, 20, 5
 RGBA8, BGRX8, RGBA16 = dx.DXGI_FORMAT_R8G8B8A8_UNORM, dx.DXGI_FORMAT_B8G8R8X8_UNORM, 11          # 11: R16G16B16A16_UNORM
@@ -79,47 +80,18 @@ def write_inputs(tmp):
     return files
 
 
-def run(conv, args, out):
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([conv, "-nologo", "-timing", "-overlap", "1", "-y"] + args, capture_output=True, text=True, check=True)
-    m = re.search(r": ([0-9.]+) ms, host -> device (\d+) bytes, device -> host (\d+) bytes", r.stdout)
-    assert m, r.stdout
-    with open(out, "rb") as f:
-        data = f.read()
-    return float(m.group(1)), int(m.group(2)), int(m.group(3)), data
-
-
 def end_to_end(parent):
     ours = os.path.join(os.path.dirname(dx.library_path()), "dxtexconv")
     builds = [("this build", ours)] + ([("parent", os.path.join(parent, "dxtexconv"))] if parent else [])
-    rows = []
     with tempfile.TemporaryDirectory() as tmp:
         files = write_inputs(tmp)
         out = os.path.join(tmp, "out.dds")
-        cases = [("24-bit R8G8B8 DDS -> -f R8G8B8A8_UNORM -m 1", ["-m", "1", "-f", "R8G8B8A8_UNORM", "-o", out, files["r8g8b8"]]),
-                 ("24-bit R8G8B8 DDS -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, files["r8g8b8"]]),
-                 ("L8 DDS -> -f BC4_UNORM -m 1", ["-m", "1", "-f", "BC4_UNORM", "-o", out, files["l8"]]),
-                 ("R8G8B8A8_UNORM DDS -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, files["rgba8"]]),
-                 ("BC7_UNORM DDS handed through", ["-m", "1", "-f", "BC7_UNORM", "-o", out, files["bc7"]])]
-        for title, args in cases:
-            times = {name: [] for name, _ in builds}
-            moved, outputs = {}, {}
-            for name, conv in builds:          # one unmeasured run each: the first touch of a file and of the device
-                run(conv, args, out)
-            for _ in range(RUNS):
-                for name, conv in builds:
-                    ms, up, down, data = run(conv, args, out)
-                    times[name].append(ms); moved[name] = (up, down); outputs[name] = data
-            for name, _ in builds:
-                t = times[name]
-                rows.append({"case": title, "build": name, "ms": t, "median": statistics.median(t), "spread": round(max(t) - min(t), 1),
-                             "host -> device": moved[name][0], "device -> host": moved[name][1]})
-                print(json.dumps(rows[-1]), flush=True)
-            if parent:
-                print(json.dumps({"case": title, "outputs byte-identical": outputs["this build"] == outputs["parent"],
-                                  "slower than the parent by more than its spread": rows[-2]["median"] > rows[-1]["median"] + rows[-1]["spread"]}), flush=True)
-    return rows
+        cases = [("24-bit R8G8B8 DDS -> -f R8G8B8A8_UNORM -m 1", ["-m", "1", "-f", "R8G8B8A8_UNORM", "-o", out, files["r8g8b8"]], out),
+                 ("24-bit R8G8B8 DDS -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, files["r8g8b8"]], out),
+                 ("L8 DDS -> -f BC4_UNORM -m 1", ["-m", "1", "-f", "BC4_UNORM", "-o", out, files["l8"]], out),
+                 ("R8G8B8A8_UNORM DDS -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, files["rgba8"]], out),
+                 ("BC7_UNORM DDS handed through", ["-m", "1", "-f", "BC7_UNORM", "-o", out, files["bc7"]], out)]
+        return measure_conv(cases, builds, RUNS)
 
 
 if __name__ == "__main__":

@@ -14,13 +14,14 @@ is set beside the same build's host path through the API (tests/cpp/exr_host_tes
 the host loader plus Upload, the resident saver against Download plus the host saver, alternating, five runs after one unmeasured; time_load
 also times the Raw loader alone (header, table, inflate: the byte-serial share of the resident load) and the host's serial undo of the same
 stream, which is what exr_undo replaces."""
-import argparse, json, os, re, statistics, subprocess, sys, tempfile
+import argparse, json, os, statistics, subprocess, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import directxtex_amd as dx
 import exr_ref as R
+from codec_bench import measure_conv, profile_cases, run_rows, summary
 
 W, H, REPS, RUNS = 4096, 2048, 20, 5
 RGBA32F, RGBA16F = dx.DXGI_FORMAT_R32G32B32A32_FLOAT, dx.DXGI_FORMAT_R16G16B16A16_FLOAT
@@ -63,21 +64,7 @@ def kernels():
              ("pnm_unpack<wide>", "PH -> R16G16B16A16_FLOAT, the same image size", 14, lambda: ctx.pnm_unpack_device(stream, W * H * 6, dx.PNM_PH, img(image, W, H, RGBA16F))),
              ("exr_pack<wide>", "R32G32B32A32_FLOAT -> the writer's half planes", 24, lambda: ctx.exr_pack_device(img(image, W, H, RGBA32F), stream, W * H * 8)),
              ("exr_pack<wide>", "R16G16B16A16_FLOAT -> the writer's half planes", 16, lambda: ctx.exr_pack_device(img(image, W, H, RGBA16F), stream, W * H * 8))]
-    rows = []
-    for mark, what, bytes_a_texel, call in cases:
-        for _ in range(3):
-            call()
-        ctx.synchronize()
-        ctx.profile_begin()
-        for _ in range(REPS):
-            call()
-        prof = ctx.profile_end()
-        row = {"kernel": mark, "case": what}
-        for k, (ms, n) in sorted(prof.items()):
-            row[k + " ms"] = round(ms / REPS, 4)
-        row["TBps"] = round(W * H * bytes_a_texel / (prof[mark][0] / REPS * 1e-3) / 1e12, 3)
-        rows.append(row)
-        print(json.dumps(row), flush=True)
+    rows = profile_cases(ctx, cases, W * H, REPS)          # one call launches exr_undo_sums and exr_undo: milliseconds a call, not a launch
     ctx.device_free(stream); ctx.device_free(image)
     ctx.close()
     return rows
@@ -93,26 +80,13 @@ def write_inputs(tmp, conv):
     return exr, rgba32f
 
 
-def run(conv, args, out):
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([conv, "-nologo", "-timing", "-overlap", "1", "-y"] + args, capture_output=True, text=True, check=True)
-    m = re.search(r": ([0-9.]+) ms, host -> device (\d+) bytes, device -> host (\d+) bytes", r.stdout)
-    assert m, r.stdout
-    return float(m.group(1)), int(m.group(2)), int(m.group(3))
-
-
 def api_paths(exe, command, file):
-    r = subprocess.run([exe, command, file, str(RUNS)], capture_output=True, text=True, check=True)
-    rows = re.findall(r"resident ([0-9.]+) ms up (\d+) down (\d+) host ([0-9.]+) ms up (\d+) down (\d+) raw ([0-9.]+) ms undo ([0-9.]+) ms", r.stdout)
-    assert len(rows) == RUNS, r.stdout + r.stderr
-    res, host = [float(x[0]) for x in rows], [float(x[3]) for x in rows]
-    out = {"resident ms": res, "resident median": statistics.median(res), "resident up/down": [int(rows[0][1]), int(rows[0][2])],
-           "host path ms": host, "host path median": statistics.median(host), "host path spread": round(max(host) - min(host), 1),
-           "host path up/down": [int(rows[0][4]), int(rows[0][5])]}
+    rows = run_rows([exe, command, file, str(RUNS)])
+    assert len(rows) == RUNS, rows
+    out = summary(rows)
     if command == "time_load":
-        out["raw loader median ms"] = statistics.median(float(x[6]) for x in rows)
-        out["host serial undo median ms"] = statistics.median(float(x[7]) for x in rows)
+        out["raw loader median ms"] = statistics.median(x["raw"] for x in rows)
+        out["host serial undo median ms"] = statistics.median(x["undo"] for x in rows)
     return out
 
 
@@ -126,11 +100,7 @@ def end_to_end():
         cases = [(".exr -> -f R16G16B16A16_FLOAT -m 1", ["-m", "1", "-f", "R16G16B16A16_FLOAT", "-o", out, exr], out),
                  (".exr -> -f BC6H_UF16, full chain", ["-f", "BC6H_UF16", "-o", out, exr], out),
                  ("R32G32B32A32_FLOAT DDS -> -ft exr", ["-m", "1", "-ft", "exr", "-o", tmp, rgba32f], os.path.join(tmp, "rgba32f.exr"))]
-        for title, args, result in cases:
-            run(conv, args, result)          # one unmeasured run: the first touch of a file and of the device
-            t = [run(conv, args, result) for _ in range(RUNS)]
-            ms = [x[0] for x in t]
-            print(json.dumps({"case": title, "ms": ms, "median": statistics.median(ms), "spread": round(max(ms) - min(ms), 1), "host -> device": t[0][1], "device -> host": t[0][2]}), flush=True)
+        measure_conv(cases, [(None, conv)], RUNS)
         print(json.dumps({"case": "load .exr through the API", **api_paths(exe, "time_load", exr)}), flush=True)
         print(json.dumps({"case": "save .exr through the API (from R16G16B16A16_FLOAT)", **api_paths(exe, "time_save", exr)}), flush=True)
 

@@ -14,11 +14,12 @@ The writer (--skip-encode leaves it out): one 4096 x 4096 image of noise through
 as the reader's kernels are, with quantiser tables of ones (the writer's) and of 8; then SaveToJPEGMemory on a resident 4096^2 image against
 Download plus this build's host saver, alternating, and SaveJPEGRaw alone on the same coefficients (jpeg_write_host_test time_save). The
 parent commit cannot write a .jpg, so that host path is again the only comparison."""
-import argparse, json, os, re, statistics, subprocess, sys, tempfile
+import argparse, json, os, statistics, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import directxtex_amd as dx
+from codec_bench import measure_conv, run_rows, summary
 
 N, REPS, RUNS = 4096, 20, 5
 RGBA8, R8 = dx.DXGI_FORMAT_R8G8B8A8_UNORM, dx.DXGI_FORMAT_R8_UNORM
@@ -100,15 +101,14 @@ def encode_kernels():
 def save_end_to_end():
     exe = os.path.join(os.path.dirname(dx.library_path()), "jpeg_write_host_test")
     for name, fmt in (("R8_UNORM -> grey", R8), ("R8G8B8A8_UNORM -> 4:2:0", RGBA8)):
-        r = subprocess.run([exe, "time_save", str(N), str(N), str(fmt), str(RUNS)], capture_output=True, text=True, check=True)
-        rows = re.findall(r"resident ([0-9.]+) ms up (\d+) down (\d+) host ([0-9.]+) ms up (\d+) down (\d+) file (\d+)", r.stdout)
-        raw = [float(v) for v in re.findall(r"raw ([0-9.]+) ms", r.stdout)]
-        assert len(rows) == RUNS and len(raw) == RUNS, r.stdout + r.stderr
-        res, host = [float(x[0]) for x in rows], [float(x[3]) for x in rows]
-        print(json.dumps({"case": name + ": SaveToJPEGMemory through the API", "file bytes": int(rows[0][6]), "resident ms": res, "resident median": statistics.median(res),
-                          "resident up/down": [int(rows[0][1]), int(rows[0][2])], "Download + host saver ms": host, "host path median": statistics.median(host),
-                          "host path up/down": [int(rows[0][4]), int(rows[0][5])], "SaveJPEGRaw alone ms": raw, "SaveJPEGRaw median": statistics.median(raw),
-                          "share of the resident save in the Huffman coder": round(statistics.median(raw) / statistics.median(res), 3)}), flush=True)
+        lines = run_rows([exe, "time_save", str(N), str(N), str(fmt), str(RUNS)])
+        rows, raw = [x for x in lines if "resident" in x], [x["raw"] for x in lines if "resident" not in x]
+        assert len(rows) == RUNS and len(raw) == RUNS, lines
+        s = summary(rows)
+        print(json.dumps({"case": name + ": SaveToJPEGMemory through the API", "file bytes": rows[0]["file"], "resident ms": s["resident ms"], "resident median": s["resident median"],
+                          "resident up/down": s["resident up/down"], "Download + host saver ms": s["host path ms"], "host path median": s["host path median"],
+                          "host path up/down": s["host path up/down"], "SaveJPEGRaw alone ms": raw, "SaveJPEGRaw median": statistics.median(raw),
+                          "share of the resident save in the Huffman coder": round(statistics.median(raw) / s["resident median"], 3)}), flush=True)
 
 
 def write_files(tmp):
@@ -123,37 +123,24 @@ def write_files(tmp):
     return paths
 
 
-def run(conv, args, out):
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([conv, "-nologo", "-timing", "-overlap", "1", "-y"] + args, capture_output=True, text=True, check=True)
-    m = re.search(r": ([0-9.]+) ms, host -> device (\d+) bytes, device -> host (\d+) bytes", r.stdout)
-    assert m, r.stdout
-    return float(m.group(1)), int(m.group(2)), int(m.group(3))
-
-
 def end_to_end(paths, tmp):
     lib = os.path.dirname(dx.library_path())
     conv, exe = os.path.join(lib, "dxtexconv"), os.path.join(lib, "jpeg_host_test")
     out = os.path.join(tmp, "out.dds")
     for name, path in paths.items():
         print(json.dumps({"file": name, "bytes": os.path.getsize(path)}), flush=True)
-        r = subprocess.run([exe, "time_raw", path, str(RUNS)], capture_output=True, text=True, check=True)
-        raw = [float(v) for v in re.findall(r"raw ([0-9.]+) ms", r.stdout)]
+        lines = run_rows([exe, "time_raw", path, str(RUNS)])
+        raw = [x["raw"] for x in lines]
         print(json.dumps({"case": name + ": LoadFromJPEGMemoryRaw (markers and the Huffman walk, no device)", "ms": raw, "median": statistics.median(raw),
-                          "coefficient bytes": int(re.search(r"coefficients (\d+)", r.stdout).group(1))}), flush=True)
-        for title, args in ((" -> -f R8G8B8A8_UNORM -m 1", ["-m", "1", "-f", "R8G8B8A8_UNORM", "-o", out, path]), (" -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, path])):
-            run(conv, args, out)          # one unmeasured run: the first touch of a file and of the device
-            t = [run(conv, args, out) for _ in range(RUNS)]
-            ms = [x[0] for x in t]
-            print(json.dumps({"case": name + title, "ms": ms, "median": statistics.median(ms), "spread": round(max(ms) - min(ms), 1), "host -> device": t[0][1], "device -> host": t[0][2]}), flush=True)
-        r = subprocess.run([exe, "time_load", path, str(RUNS)], capture_output=True, text=True, check=True)
-        rows = re.findall(r"resident ([0-9.]+) ms up (\d+) down (\d+) host ([0-9.]+) ms up (\d+) down (\d+)", r.stdout)
-        assert len(rows) == RUNS, r.stdout + r.stderr
-        res, host = [float(x[0]) for x in rows], [float(x[3]) for x in rows]
-        print(json.dumps({"case": name + ": load through the API", "resident ms": res, "resident median": statistics.median(res), "resident up/down": [int(rows[0][1]), int(rows[0][2])],
-                          "host path ms": host, "host path median": statistics.median(host), "host path up/down": [int(rows[0][4]), int(rows[0][5])],
-                          "share of the resident load in the Huffman walk": round(statistics.median(raw) / statistics.median(res), 3)}), flush=True)
+                          "coefficient bytes": lines[0]["coefficients"]}), flush=True)
+        measure_conv([(name + " -> -f R8G8B8A8_UNORM -m 1", ["-m", "1", "-f", "R8G8B8A8_UNORM", "-o", out, path], out),
+                      (name + " -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, path], out)], [(None, conv)], RUNS)
+        rows = run_rows([exe, "time_load", path, str(RUNS)])
+        assert len(rows) == RUNS, rows
+        s = summary(rows)
+        del s["host path spread"]
+        print(json.dumps({"case": name + ": load through the API", **s,
+                          "share of the resident load in the Huffman walk": round(statistics.median(raw) / s["resident median"], 3)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -15,13 +15,14 @@ adaptively, the filter of least absolute sum per row - and zlib deflates them at
 - one unmeasured run and five measured ones each; the medians and the bytes moved. The parent commit cannot read these files, so the load
 and the save are set beside the same build's host path through the API (png_host_test time_load / time_save): the resident loader against
 the host loader plus Upload, the resident saver against Download plus the host saver, alternating, five runs after one unmeasured."""
-import argparse, json, os, re, statistics, subprocess, sys, tempfile, time, zlib
+import argparse, json, os, statistics, subprocess, sys, tempfile, time, zlib
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import directxtex_amd as dx
 import png_ref as R
+from codec_bench import api_paths, measure_conv, parse_runs, profile_cases
 
 N, REPS, RUNS = 4096, 20, 5
 RGBA8, R8 = dx.DXGI_FORMAT_R8G8B8A8_UNORM, dx.DXGI_FORMAT_R8_UNORM
@@ -42,23 +43,11 @@ def kernels():
              ("tga_unpack<wide>", "8-bit TGA indices -> R8G8B8A8, the same bytes", 5, lambda: ctx.tga_unpack_device(stream, N * N, 1, img(image, N, N, RGBA8), palette=pal)),
              ("png_unpack<wide>", "grey 1 -> R8 (a byte of the stream a lane)", 1.125, lambda: ctx.png_unpack_device(stream, N * N // 8, dx.PNG_G1, img(image, N, N, R8))),
              ("png_unpack<narrow>", "RGB 8 -> R8G8B8A8, rows one byte off", 7, lambda: ctx.png_unpack_device(stream + 1, N * N * 3, dx.PNG_RGB8, img(image, N, N, RGBA8)))]
-    for mark, what, bytes_a_texel, call in cases:
+    for case in cases:
         try:
-            for _ in range(3):
-                call()
+            profile_cases(ctx, [case], N * N, REPS)
         except TypeError as e:          # a binding without this form: say so and go on
-            print(json.dumps({"kernel": mark, "case": what, "skipped": str(e)}), flush=True)
-            continue
-        ctx.synchronize()
-        ctx.profile_begin()
-        for _ in range(REPS):
-            call()
-        prof = ctx.profile_end()
-        row = {"kernel": mark, "case": what}
-        for k, (ms, n) in sorted(prof.items()):
-            row[k + " ms"] = round(ms / n, 4)
-        row["TBps"] = round(N * N * bytes_a_texel / (prof[mark][0] / REPS * 1e-3) / 1e12, 3)
-        print(json.dumps(row), flush=True)
+            print(json.dumps({"kernel": case[0], "case": case[1], "skipped": str(e)}), flush=True)
     ctx.device_free(stream); ctx.device_free(image)
     ctx.close()
 
@@ -94,25 +83,6 @@ def picture(w, h, channels, rng):
     return np.stack(planes, axis=2).reshape(h, w * channels)
 
 
-def run(conv, args, out):
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([conv, "-nologo", "-timing", "-overlap", "1", "-y"] + args, capture_output=True, text=True, check=True)
-    m = re.search(r": ([0-9.]+) ms, host -> device (\d+) bytes, device -> host (\d+) bytes", r.stdout)
-    assert m, r.stdout
-    return float(m.group(1)), int(m.group(2)), int(m.group(3))
-
-
-def api_paths(exe, command, file):
-    r = subprocess.run([exe, command, file, str(RUNS)], capture_output=True, text=True, check=True)
-    rows = re.findall(r"resident ([0-9.]+) ms up (\d+) down (\d+) host ([0-9.]+) ms up (\d+) down (\d+)", r.stdout)
-    assert len(rows) == RUNS, r.stdout + r.stderr
-    res, host = [float(x[0]) for x in rows], [float(x[3]) for x in rows]
-    return {"resident ms": res, "resident median": statistics.median(res), "resident up/down": [int(rows[0][1]), int(rows[0][2])],
-            "host path ms": host, "host path median": statistics.median(host), "host path spread": round(max(host) - min(host), 1),
-            "host path up/down": [int(rows[0][4]), int(rows[0][5])]}
-
-
 def end_to_end():
     lib = os.path.dirname(dx.library_path())
     conv, exe = os.path.join(lib, "dxtexconv"), os.path.join(lib, "png_host_test")
@@ -125,7 +95,7 @@ def end_to_end():
         print(json.dumps({"file": "2048^2 RGBA 16", "bytes": os.path.getsize(rgba16), "inflated": raw16, "rows by filter": filters16}), flush=True)
         # the inflater beside zlib, on the same stream
         r = subprocess.run([exe, "time_raw", rgb, str(RUNS)], capture_output=True, text=True, check=True)
-        ours = [float(v) for v in re.findall(r"raw ([0-9.]+) ms", r.stdout)]
+        ours = [x["raw"] for x in parse_runs(r.stdout)]
         theirs = []
         for _ in range(RUNS):
             t0 = time.perf_counter(); zlib.decompress(z); theirs.append((time.perf_counter() - t0) * 1e3)
@@ -139,13 +109,9 @@ def end_to_end():
                  (".png RGB 8 -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, rgb], out),
                  (".png RGBA 16 (2048^2) -> -f BC7_UNORM, full chain", ["-f", "BC7_UNORM", "-o", out, rgba16], out),
                  ("R32G32B32A32_FLOAT DDS (4096 x 2048) -> -f R16G16B16A16_UNORM -ft png", ["-m", "1", "-f", "R16G16B16A16_UNORM", "-ft", "png", "-o", tmp, f32], os.path.join(tmp, "f32.png"))]
-        for title, args, result in cases:
-            run(conv, args, result)          # one unmeasured run: the first touch of a file and of the device
-            t = [run(conv, args, result) for _ in range(RUNS)]
-            ms = [x[0] for x in t]
-            print(json.dumps({"case": title, "ms": ms, "median": statistics.median(ms), "spread": round(max(ms) - min(ms), 1), "host -> device": t[0][1], "device -> host": t[0][2]}), flush=True)
-        print(json.dumps({"case": "load the RGB 8 .png through the API", **api_paths(exe, "time_load", rgb)}), flush=True)
-        print(json.dumps({"case": "save the RGB 8 image as .png through the API (R8G8B8A8_UNORM_SRGB -> RGBA 8)", **api_paths(exe, "time_save", rgb)}), flush=True)
+        measure_conv(cases, [(None, conv)], RUNS)
+        print(json.dumps({"case": "load the RGB 8 .png through the API", **api_paths(exe, "time_load", rgb, RUNS)}), flush=True)
+        print(json.dumps({"case": "save the RGB 8 image as .png through the API (R8G8B8A8_UNORM_SRGB -> RGBA 8)", **api_paths(exe, "time_save", rgb, RUNS)}), flush=True)
 
 
 if __name__ == "__main__":

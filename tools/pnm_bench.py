@@ -11,10 +11,11 @@ End to end: `dxtexconv -nologo -timing -overlap 1 -y` on files this script write
 - one unmeasured run and five measured ones each; the medians and the bytes moved. The parent commit cannot read these files, so each case
 is set beside the same build's host path through the API (tests/cpp/pnm_host_test.cpp time_load / time_save): the resident loader against
 the host loader plus Upload, the resident saver against Download plus the host saver, alternating, five runs after one unmeasured."""
-import argparse, json, os, re, statistics, subprocess, sys, tempfile
+import argparse, json, os, subprocess, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directxtex_amd as dx
+from codec_bench import api_paths, measure_conv, profile_cases
 
 N, REPS, RUNS = 4096, 20, 5
 RGBA8, BGRX8, RGBA32F, RGBA16F = dx.DXGI_FORMAT_R8G8B8A8_UNORM, dx.DXGI_FORMAT_B8G8R8X8_UNORM, dx.DXGI_FORMAT_R32G32B32A32_FLOAT, dx.DXGI_FORMAT_R16G16B16A16_FLOAT
@@ -42,22 +43,7 @@ def kernels():
              ("pnm_pack<wide>", "R32G32B32A32_FLOAT -> PF", 28, lambda: ctx.pnm_pack_device(img(image, N, N, RGBA32F), dx.PNM_PF, stream, N * N * 12)),
              ("pnm_pack<wide>", "R16G16B16A16_FLOAT -> PF", 20, lambda: ctx.pnm_pack_device(img(image, N, N, RGBA16F), dx.PNM_PF, stream, N * N * 12)),
              ("pnm_pack<narrow>", "R16G16B16A16_FLOAT -> PF, samples one byte off", 20, lambda: ctx.pnm_pack_device(img(image, N, N, RGBA16F), dx.PNM_PF, stream + 1, N * N * 12))]
-    rows = []
-    for mark, what, bytes_a_texel, call in cases:
-        for _ in range(3):
-            call()
-        ctx.synchronize()
-        ctx.profile_begin()
-        for _ in range(REPS):
-            call()
-        prof = ctx.profile_end()
-        row = {"kernel": mark, "case": what}
-        for k, (ms, n) in sorted(prof.items()):
-            assert n == REPS, prof
-            row[k + " ms"] = round(ms / n, 4)
-        row["TBps"] = round(N * N * bytes_a_texel / (prof[mark][0] / REPS * 1e-3) / 1e12, 3)
-        rows.append(row)
-        print(json.dumps(row), flush=True)
+    rows = profile_cases(ctx, cases, N * N, REPS)
     ctx.device_free(stream); ctx.device_free(image)
     ctx.close()
     return rows
@@ -78,25 +64,6 @@ def write_inputs(tmp, conv):
     return ppm, pfm, rgba32f
 
 
-def run(conv, args, out):
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([conv, "-nologo", "-timing", "-overlap", "1", "-y"] + args, capture_output=True, text=True, check=True)
-    m = re.search(r": ([0-9.]+) ms, host -> device (\d+) bytes, device -> host (\d+) bytes", r.stdout)
-    assert m, r.stdout
-    return float(m.group(1)), int(m.group(2)), int(m.group(3))
-
-
-def api_paths(exe, command, file, extra=()):
-    r = subprocess.run([exe, command, file, str(RUNS), *extra], capture_output=True, text=True, check=True)
-    rows = re.findall(r"resident ([0-9.]+) ms up (\d+) down (\d+) host ([0-9.]+) ms up (\d+) down (\d+)", r.stdout)
-    assert len(rows) == RUNS, r.stdout + r.stderr
-    res, host = [float(x[0]) for x in rows], [float(x[3]) for x in rows]
-    return {"resident ms": res, "resident median": statistics.median(res), "resident up/down": [int(rows[0][1]), int(rows[0][2])],
-            "host path ms": host, "host path median": statistics.median(host), "host path spread": round(max(host) - min(host), 1),
-            "host path up/down": [int(rows[0][4]), int(rows[0][5])]}
-
-
 def end_to_end():
     lib = os.path.dirname(dx.library_path())
     conv, exe = os.path.join(lib, "dxtexconv"), os.path.join(lib, "pnm_host_test")
@@ -107,15 +74,11 @@ def end_to_end():
                  (".ppm -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, ppm], out),
                  (".pfm -> -f BC6H_UF16, full chain", ["-f", "BC6H_UF16", "-o", out, pfm], out),
                  ("R32G32B32A32_FLOAT DDS -> -ft pfm", ["-m", "1", "-ft", "pfm", "-o", tmp, rgba32f], os.path.join(tmp, "rgba32f.pfm"))]
-        for title, args, result in cases:
-            run(conv, args, result)          # one unmeasured run: the first touch of a file and of the device
-            t = [run(conv, args, result) for _ in range(RUNS)]
-            ms = [x[0] for x in t]
-            print(json.dumps({"case": title, "ms": ms, "median": statistics.median(ms), "spread": round(max(ms) - min(ms), 1), "host -> device": t[0][1], "device -> host": t[0][2]}), flush=True)
-        print(json.dumps({"case": "load .ppm through the API", **api_paths(exe, "time_load", ppm)}), flush=True)
-        print(json.dumps({"case": "load .pfm through the API", **api_paths(exe, "time_load", pfm)}), flush=True)
-        print(json.dumps({"case": "save .pfm through the API (from R32G32B32A32_FLOAT)", **api_paths(exe, "time_save", pfm, ("1",))}), flush=True)
-        print(json.dumps({"case": "save .ppm through the API (from R8G8B8A8_UNORM)", **api_paths(exe, "time_save", ppm, ("0",))}), flush=True)
+        measure_conv(cases, [(None, conv)], RUNS)
+        print(json.dumps({"case": "load .ppm through the API", **api_paths(exe, "time_load", ppm, RUNS)}), flush=True)
+        print(json.dumps({"case": "load .pfm through the API", **api_paths(exe, "time_load", pfm, RUNS)}), flush=True)
+        print(json.dumps({"case": "save .pfm through the API (from R32G32B32A32_FLOAT)", **api_paths(exe, "time_save", pfm, RUNS, ("1",))}), flush=True)
+        print(json.dumps({"case": "save .ppm through the API (from R8G8B8A8_UNORM)", **api_paths(exe, "time_save", ppm, RUNS, ("0",))}), flush=True)
 
 
 if __name__ == "__main__":

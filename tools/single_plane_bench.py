@@ -2,35 +2,19 @@
 Median of 20 after 5 warm-up calls; '_ms' = dxtex_ctx_last_kernel_ms (the library's event pair around its kernels), '_wall' = 20 queued
 calls + one synchronize, per call. The same-format mover (dxtex_copy_rectangles_device on a whole 8192 x 8192 YUY2 image, 128 MiB each
 way) is timed in the same run, once before each conversion, as the yardstick: time per byte moved (read + written)."""
-import json, os, sys, time
+import json, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directxtex_amd as dx
 from directxtex_amd import capi
+import codec_bench
 
 ctx = dx.Context(0)
+med_ms = lambda fn: codec_bench.med_ms(ctx, fn)
+wall_ms = lambda fn: codec_bench.wall_ms(ctx, fn)
 NV12, P010, YUY2, Y210 = 103, 104, 107, 108
 N, F = 8192, 2048
 MiB = float(1 << 20)
-
-def med_ms(fn, reps=20, warm=5):
-    for _ in range(warm): fn()
-    ctx.synchronize()
-    v = []
-    for _ in range(reps):
-        fn(); ctx.synchronize(); v.append(ctx.last_kernel_ms())
-    return float(np.median(v))
-
-def wall_ms(fn, reps=20, warm=5):
-    for _ in range(warm): fn()
-    ctx.synchronize()
-    t = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        for _ in range(reps): fn()
-        ctx.synchronize()
-        t.append((time.perf_counter() - t0) * 1e3 / reps)
-    return float(np.median(t))
 
 def planar_pitches(fmt, w, h):
     """ComputePitch of NV12 / P010: rows of w samples, a half-height chroma plane after the luma plane"""

@@ -10,10 +10,11 @@ End to end: `dxtexconv -nologo -timing -overlap 1 -y` on files this script write
 - five runs of this build (directxtex_amd/lib/dxtexconv) and, with --parent DIR, five of the dxtexconv in DIR (a build of the parent
 commit), alternating. Prints each run's -timing line figures, the medians, the parent's spread (max - min of its five) and whether the two
 builds' outputs are byte-identical."""
-import argparse, json, os, re, statistics, struct, subprocess, sys, tempfile
+import argparse, os, struct, subprocess, sys, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import directxtex_amd as dx
+from codec_bench import measure_conv, profile_cases
 
 N, REPS, RUNS = 4096, 20, 5
 RGBA8, BGRX8, BGRA8, R8 = dx.DXGI_FORMAT_R8G8B8A8_UNORM, dx.DXGI_FORMAT_B8G8R8X8_UNORM, dx.DXGI_FORMAT_B8G8R8A8_UNORM, dx.DXGI_FORMAT_R8_UNORM
@@ -34,22 +35,7 @@ def kernels():
              ("tga_pack<wide>", "B8G8R8X8 -> 24 bits", 7, lambda: ctx.tga_pack_device(img(image, N, N, BGRX8), 3, stream, N * N * 3)),
              ("tga_pack<narrow>", "B8G8R8X8 -> 24 bits, stream one byte off", 7, lambda: ctx.tga_pack_device(img(image, N, N, BGRX8), 3, stream + 1, N * N * 3)),
              ("tga_pack<wide>", "R8G8B8A8 -> 32 bits", 8, lambda: ctx.tga_pack_device(img(image, N, N, RGBA8), 4, stream, N * N * 4))]
-    rows = []
-    for mark, what, bytes_a_texel, call in cases:
-        for _ in range(3):
-            call()
-        ctx.synchronize()
-        ctx.profile_begin()
-        for _ in range(REPS):
-            call()
-        prof = ctx.profile_end()
-        row = {"kernel": mark, "case": what}
-        for k, (ms, n) in sorted(prof.items()):
-            assert n == REPS, prof
-            row[k + " ms"] = round(ms / n, 4)
-        row["TBps"] = round(N * N * bytes_a_texel / (prof[mark][0] / REPS * 1e-3) / 1e12, 3)
-        rows.append(row)
-        print(json.dumps(row))
+    rows = profile_cases(ctx, cases, N * N, REPS)
     ctx.device_free(stream); ctx.device_free(image)
     ctx.close()
     return rows
@@ -80,21 +66,9 @@ def write_inputs(tmp, conv):
     return raw24, rle32, bgrx
 
 
-def run(conv, args, out):
-    if os.path.exists(out):
-        os.remove(out)
-    r = subprocess.run([conv, "-nologo", "-timing", "-overlap", "1", "-y"] + args, capture_output=True, text=True, check=True)
-    m = re.search(r": ([0-9.]+) ms, host -> device (\d+) bytes, device -> host (\d+) bytes", r.stdout)
-    assert m, r.stdout
-    with open(out, "rb") as f:
-        data = f.read()
-    return float(m.group(1)), int(m.group(2)), int(m.group(3)), data
-
-
 def end_to_end(parent):
     ours = os.path.join(os.path.dirname(dx.library_path()), "dxtexconv")
     builds = [("this build", ours)] + ([("parent", os.path.join(parent, "dxtexconv"))] if parent else [])
-    rows = []
     with tempfile.TemporaryDirectory() as tmp:
         raw24, rle32, bgrx = write_inputs(tmp, ours)
         out = os.path.join(tmp, "out.dds")
@@ -103,24 +77,7 @@ def end_to_end(parent):
                  ("32-bit run-length .tga -> -f R8G8B8A8_UNORM -m 1", ["-m", "1", "-f", "R8G8B8A8_UNORM", "-o", out, rle32], out),
                  ("32-bit run-length .tga -> -f BC1_UNORM, full chain", ["-f", "BC1_UNORM", "-o", out, rle32], out),
                  ("B8G8R8X8 DDS -> -ft tga", ["-m", "1", "-ft", "tga", "-o", tmp, bgrx], os.path.join(tmp, "bgrx.tga"))]
-        for title, args, result in cases:
-            times = {name: [] for name, _ in builds}
-            moved, files = {}, {}
-            for name, conv in builds:          # one unmeasured run each: the first touch of a file and of the device
-                run(conv, args, result)
-            for _ in range(RUNS):
-                for name, conv in builds:
-                    ms, up, down, data = run(conv, args, result)
-                    times[name].append(ms); moved[name] = (up, down); files[name] = data
-            for name, _ in builds:
-                t = times[name]
-                rows.append({"case": title, "build": name, "ms": t, "median": statistics.median(t), "spread": round(max(t) - min(t), 1),
-                             "host -> device": moved[name][0], "device -> host": moved[name][1]})
-                print(json.dumps(rows[-1]))
-            if parent:
-                print(json.dumps({"case": title, "outputs byte-identical": files["this build"] == files["parent"],
-                                  "slower than the parent by more than its spread": rows[-2]["median"] > rows[-1]["median"] + rows[-1]["spread"]}))
-    return rows
+        return measure_conv(cases, builds, RUNS)
 
 
 if __name__ == "__main__":

@@ -15,6 +15,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tiff_ref as T  # noqa: E402
+from codec_bench import parse_runs  # noqa: E402
 
 EXE = os.path.join(ROOT, "directxtex_amd", "lib", "tiff_host_test")
 
@@ -45,10 +46,9 @@ def main():
                 print(name, "failed:", r.stderr.strip())
                 continue
             cols = {}
-            for line in r.stdout.splitlines():
-                f = line.split()
-                for key, at in (("resident", 3), ("up", 6), ("host", 10), ("raw", 17), ("undo", 20), ("undo_gpu", 23), ("texels_gpu", 26)):
-                    cols.setdefault(key, []).append(float(f[at]))
+            for row in parse_runs(r.stdout):
+                for key in ("resident", "up", "host", "raw", "undo", "undo_gpu", "texels_gpu"):
+                    cols.setdefault(key, []).append(float(row["resident up" if key == "up" else key]))
             print(name, os.path.getsize(path), "bytes:", ", ".join(f"{k} {statistics.median(v):.3f}" for k, v in cols.items()))
 
 
