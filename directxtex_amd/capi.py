@@ -263,6 +263,8 @@ _SIGS = {
     "dxtex_copy_rectangle": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Rect), _P(Image), ctypes.c_uint32, ctypes.c_size_t, ctypes.c_size_t]),
     "dxtex_copy_rectangles_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Rect), _P(Image), _P(ctypes.c_size_t), _P(ctypes.c_size_t), ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_planar_to_single": (ctypes.c_int32, [ctypes.c_int32]),
+    "dxtex_flip_rotate": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_uint32]),
+    "dxtex_flip_rotate_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t, ctypes.c_uint32]),
     "dxtex_convert_to_single_plane": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image)]),
     "dxtex_convert_to_single_plane_device": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), ctypes.c_size_t]),
     "dxtex_merge_image": (ctypes.c_int32, [_ctx_p, _P(Image), _P(Image), _P(Image), _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
@@ -680,6 +682,27 @@ class Context:
         r = (Rect * m)(*[Rect(*q) for q in rects])
         xs, ys = (ctypes.c_size_t * m)(*x_offsets), (ctypes.c_size_t * m)(*y_offsets)
         self._check(self._lib.dxtex_copy_rectangles_device(self._h, a, r, b, xs, ys, n, filter_flags), "copy_rectangles_device")
+
+    # -- FlipRotate ---------------------------------------------------------------------------------------
+    def flip_rotate(self, pixels, width, height, fmt, flags, row_pitch=None):
+        """dxtex_flip_rotate: the host image `pixels` turned clockwise by the angle of `flags` (TEX_FR_*), then flipped -> the result's
+        bytes with tight pitch (height x width texels for ROTATE90 / ROTATE270). Texels move as bytes."""
+        pixels = np.ascontiguousarray(pixels).view(np.uint8).reshape(-1)
+        src = _host_image(pixels, width, height, fmt, row_pitch)
+        ow, oh = (height, width) if flags & 1 else (width, height)
+        rp, sp = compute_pitch(fmt, ow, oh)
+        out = np.zeros(max(sp, 1), np.uint8)
+        dst = Image(ow, oh, fmt, rp, sp, out.ctypes.data)
+        self._check(self._lib.dxtex_flip_rotate(self._h, ctypes.byref(src), ctypes.byref(dst), flags), "flip_rotate")
+        return out[:sp]
+
+    def flip_rotate_device(self, srcs, dsts, flags):
+        """dxtex_flip_rotate_device: lists of device Images (a destination may be a cell of a larger image: a pointer into it and its
+        pitch), one kernel launch per route per 32 of them; asynchronous on the context's stream."""
+        n = len(srcs)
+        m = max(n, 1)
+        a, b = (Image * m)(*srcs), (Image * m)(*dsts)
+        self._check(self._lib.dxtex_flip_rotate_device(self._h, a, b, n, flags), "flip_rotate_device")
 
     # -- ConvertToSinglePlane ---------------------------------------------------------------------------
     def convert_to_single_plane(self, pixels, width, height, fmt, row_pitch=None, slice_pitch=None):

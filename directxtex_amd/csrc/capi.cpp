@@ -18,6 +18,7 @@
 #include "dxtex_plan.h"
 #include "dxtex_copyrect.h"
 #include "dxtex_plane.h"
+#include "dxtex_fliprotate.h"
 #include "dxtex_staging.h"
 #include "triangle_filter.h"
 
@@ -2948,6 +2949,91 @@ dxtex_hresult dxtex_convert_to_single_plane(dxtex_ctx* ctx, const dxtex_image* s
         d.rowPitch = pitch; d.slicePitch = pitch * rows;
         const dxtex_hresult again = check_single_plane(ctx, s, d, &job);
         return again != DXTEX_S_OK ? again : launched(ctx, launch_single_plane(&job, 1, ctx->stream, marks_of(ctx)));
+    });
+}
+
+// ---- FlipRotate ------------------------------------------------------------------------------------------------------------------------
+namespace
+{
+// bytes of a texel FlipRotate moves, 0 where it refuses the format: compressed and two-texel packed formats and R1_UNORM; planar, palettised
+// and typeless formats and values that name no format are not in the table at all
+uint32_t flip_texel_bytes(int format)
+{
+    const FmtInfo* f = format_info(format);
+    if (!f || (f->cls & (FC_BC | FC_GROUP)) || (f->bpp % 8u)) return 0;
+    return fr_texel_bytes_ok(f->bpp / 8u) ? f->bpp / 8u : 0;
+}
+
+// The checks in the order include/dxtex_amd.h gives, and the resolved job.
+dxtex_hresult check_flip_rotate(dxtex_ctx* ctx, const dxtex_image& src, const dxtex_image& dst, uint32_t flags, FlipJob* job)
+{
+    if (!src.pixels || !dst.pixels) return fail(ctx, DXTEX_E_POINTER, "null pixels");
+    if (!fr_flags_legal(flags)) return fail(ctx, DXTEX_E_INVALIDARG, "flags are not TEX_FR_FLAGS that name an operation");
+    const uint32_t texel = flip_texel_bytes(src.format);
+    if (!texel) return fail(ctx, DXTEX_E_NOT_SUPPORTED, "FlipRotate takes formats of one texel of 1, 2, 4, 8, 12 or 16 bytes an element");
+    const FlipOp op = fr_resolve(flags);
+    if (dst.format != src.format) return fail(ctx, DXTEX_E_FAIL, "the destination's format differs from the source's");
+    if (dst.width != (op.transpose ? src.height : src.width) || dst.height != (op.transpose ? src.width : src.height))
+        return fail(ctx, DXTEX_E_FAIL, "the destination's size is not the turned source's");
+    if (src.width > 0x7FFFFFFFull || src.height > 0x7FFFFFFFull) return fail(ctx, DXTEX_E_INVALIDARG, "image too large");
+    const uint64_t srcRow = src.width * texel, dstRow = dst.width * texel;
+    if (src.rowPitch < srcRow || dst.rowPitch < dstRow) return fail(ctx, DXTEX_E_INVALIDARG, "a rowPitch is below its row's bytes");
+    if ((src.height && src.rowPitch > UINT64_MAX / src.height) || (dst.height && dst.rowPitch > UINT64_MAX / dst.height))
+        return fail(ctx, DXTEX_E_INVALIDARG, "rowPitch x rows overflows");
+    FlipJob j = {};
+    j.src = src.pixels; j.dst = dst.pixels;
+    j.srcPitch = src.rowPitch; j.dstPitch = dst.rowPitch;
+    j.width = uint32_t(dst.width); j.height = uint32_t(dst.height);
+    j.texel = texel;
+    j.mirrorX = op.mirrorX; j.mirrorY = op.mirrorY;
+    if (src.width && src.height)
+    {
+        // the bytes read and the bytes written: from the first row to the end of the last row's texels
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src.pixels), s1 = s0 + (src.height - 1) * src.rowPitch + srcRow;
+        const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst.pixels), d1 = d0 + (dst.height - 1) * dst.rowPitch + dstRow;
+        if (s0 < d1 && d0 < s1) return fail(ctx, DXTEX_E_INVALIDARG, "source and destination pixels overlap");
+    }
+    fr_choose_route(&j, op.transpose != 0);
+    *job = j;
+    return DXTEX_S_OK;
+}
+} // namespace
+
+dxtex_hresult dxtex_flip_rotate_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t flags)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!srcs || !dsts || !count) return fail(ctx, DXTEX_E_INVALIDARG, "no images");
+    std::vector<FlipJob> jobs(count);
+    for (size_t i = 0; i < count; ++i)
+    {
+        const dxtex_hresult hr = check_flip_rotate(ctx, srcs[i], dsts[i], flags, &jobs[i]);
+        if (hr != DXTEX_S_OK) return hr;
+    }
+    return run_timed(ctx, [&] { return launched(ctx, launch_flip_rotate(jobs.data(), jobs.size(), ctx->stream, marks_of(ctx))); });
+}
+
+dxtex_hresult dxtex_flip_rotate(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags)
+{
+    if (!ctx) return DXTEX_E_POINTER;
+    if (!src || !dst) return fail(ctx, DXTEX_E_INVALIDARG, "null image");
+    FlipJob host, job;
+    const dxtex_hresult hr = check_flip_rotate(ctx, *src, *dst, flags, &host);
+    if (hr != DXTEX_S_OK) return hr;
+    if (!host.width || !host.height) return DXTEX_S_OK;
+    // Only the rows' texels travel: the source goes up into rows of its bytes rounded up to 16 (so that the wide form can run), the
+    // destination's texels come back from such rows into the caller's. Nothing else of the caller's destination is read or written.
+    const size_t upRow = size_t(src->width) * host.texel, downRow = size_t(dst->width) * host.texel;
+    const size_t upPitch = (upRow + 15u) & ~size_t(15), downPitch = (downRow + 15u) & ~size_t(15);
+    StagingPlan plan;
+    plan.upload(src->pixels, src->rowPitch, plan.in(upPitch, src->height), 0, upPitch, upRow, src->height);
+    plan.download(dst->pixels, dst->rowPitch, plan.out(downPitch, dst->height), 0, downPitch, downRow, dst->height);
+    return run_plan(ctx, plan, [&](uint8_t* in, uint8_t* out)
+    {
+        dxtex_image s = with_pixels(*src, in), d = with_pixels(*dst, out);
+        s.rowPitch = upPitch; s.slicePitch = upPitch * src->height;
+        d.rowPitch = downPitch; d.slicePitch = downPitch * dst->height;
+        const dxtex_hresult staged = check_flip_rotate(ctx, s, d, flags, &job);
+        return staged != DXTEX_S_OK ? staged : launched(ctx, launch_flip_rotate(&job, 1, ctx->stream, marks_of(ctx)));
     });
 }
 

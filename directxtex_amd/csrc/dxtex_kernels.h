@@ -190,6 +190,11 @@ hipError_t launch_merge(const ImgView& a, const ImgView& b, const ImgView& dst, 
 struct PlaneJob;
 hipError_t launch_single_plane(const PlaneJob* jobs, size_t count, hipStream_t stream, KernelMarks* marks = nullptr);
 
+// FlipRotate: `count` resolved images (dxtex_fliprotate.h; the caller has checked every bound). One launch per route - rows, tiles - per
+// kFlipBatchMax jobs of it.
+struct FlipJob;
+hipError_t launch_flip_rotate(const FlipJob* jobs, size_t count, hipStream_t stream, KernelMarks* marks = nullptr);
+
 // Resize / one mip level: src is filtered (as src.format) into dst, whose rows are written in dst.format (R32G32B32A32_FLOAT rows for
 // launch_pack_group, src.format otherwise). filterMode = TEX_FILTER_POINT..TRIANGLE (already resolved, never 0); filterFlags carries the
 // wrap / mirror / sRGB bits. `tri` (device pointers) is required for TEX_FILTER_TRIANGLE: per destination column / row

@@ -338,6 +338,24 @@ enum TEX_ROTATE_COLOR : uint32_t
 HRESULT RotateColor(Device& device, const Image& srcImage, TEX_ROTATE_COLOR rotate, float paperWhiteNits, ScratchImage& result) noexcept;
 HRESULT RotateColor(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, TEX_ROTATE_COLOR rotate, float paperWhiteNits,
                     ScratchImage& result) noexcept;
+// FlipRotate (DirectXTex.h:723-737, DirectXTexFlipRotate.cpp:185-381) with the device in front. The flags are the reference's values; the
+// result is the source turned CLOCKWISE by the angle, then mirrored left-right if FLIP_HORIZONTAL is set, then mirrored top-bottom if
+// FLIP_VERTICAL is set (include/dxtex_amd.h states the rule per texel; DirectXTexAMD_FlipRotate.cpp is the one place that reads it).
+// STATED DEPARTURES: the reference hands the flag word to WIC, whose documentation does not say whether a flip combined with a rotation
+// is applied before or after it, and its tools never combine them - the order above is this project's and nothing can check it. Texels
+// move as bytes: where the reference sends a format WIC lacks through float and back (not the identity for R32_UINT above 2^24), bits
+// are kept here; the two-texel packed formats, which the reference would convert, are refused with the compressed ones
+// (HRESULT_E_NOT_SUPPORTED), as are planar, palettised and typeless formats and R1_UNORM.
+// Checks and their order are the reference's (:191-203, :290-297, :335-381). The metadata are the source's with width and height
+// exchanged for 90 / 270: mip levels, array size, depth, dimension, the cube flag and the alpha mode are kept, and whatever Initialize
+// refuses is refused. Every item, mip and depth slice goes into ONE batched call. On failure the result is released.
+enum TEX_FR_FLAGS : uint32_t
+{
+    TEX_FR_ROTATE0 = 0x0, TEX_FR_ROTATE90 = 0x1, TEX_FR_ROTATE180 = 0x2, TEX_FR_ROTATE270 = 0x3, TEX_FR_FLIP_HORIZONTAL = 0x08, TEX_FR_FLIP_VERTICAL = 0x10,
+};
+inline TEX_FR_FLAGS operator|(TEX_FR_FLAGS a, TEX_FR_FLAGS b) noexcept { return TEX_FR_FLAGS(uint32_t(a) | uint32_t(b)); }
+HRESULT FlipRotate(Device& device, const Image& srcImage, TEX_FR_FLAGS flags, ScratchImage& image) noexcept;
+HRESULT FlipRotate(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, TEX_FR_FLAGS flags, ScratchImage& result) noexcept;
 // ScaleMipMapsAlphaForCoverage (DirectXTex.h:848-851): mipChain must already be initialised with the chain's layout
 HRESULT ScaleMipMapsAlphaForCoverage(Device& device, const Image* srcImages, size_t nimages, const TexMetadata& metadata, size_t item,
                                      float alphaReference, ScratchImage& mipChain) noexcept;
@@ -435,6 +453,8 @@ HRESULT PremultiplyAlpha(Device& device, const DeviceScratchImage& src, TEX_PMAL
 HRESULT ComputeNormalMap(Device& device, const DeviceScratchImage& src, CNMAP_FLAGS flags, float amplitude, DXGI_FORMAT format, DeviceScratchImage& normalMaps) noexcept;
 HRESULT TransformImage(Device& device, const DeviceScratchImage& src, const TexTransform& transform, DeviceScratchImage& result) noexcept;
 HRESULT RotateColor(Device& device, const DeviceScratchImage& src, TEX_ROTATE_COLOR rotate, float paperWhiteNits, DeviceScratchImage& result) noexcept;
+// resident: ONE batched call on the Device's stream, no byte crosses PCIe
+HRESULT FlipRotate(Device& device, const DeviceScratchImage& src, TEX_FR_FLAGS flags, DeviceScratchImage& result) noexcept;
 // the diagnostics on resident images: image 0 of each side for ComputeMSE and Difference, every image (results[GetImageCount()]) for Analyze / AnalyzeBC
 HRESULT ComputeMSE(Device& device, const DeviceScratchImage& image1, const DeviceScratchImage& image2, float& mse, float* mseV, CMSE_FLAGS flags) noexcept;
 // image index1 of one texture against image index2 of the other (GetImages() order). A compressed texture is decompressed whole on every call:
@@ -490,6 +510,12 @@ const CrossLayout* GetCrossLayout(CROSS_KIND kind) noexcept;
 HRESULT AssembleCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& faces, DeviceScratchImage& result) noexcept;
 // the reverse (cube-from-hc ...): an image whose size is a whole number of cells -> a cubemap of six faces
 HRESULT CubeFromCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& image, DeviceScratchImage& cube) noexcept;
+// The cross with a turned -Z face: what texassemble's v-cross-fnz and cube-from-vc-fnz do with TEX_FR_ROTATE180
+// (texassemble.cpp:2134-2151, :2469-2487, :2532-2540). The five other faces stay the one copy_rect launch they are; the -Z face is one
+// FlipRotate written straight into - or read straight out of - its cell of the cross through an image view on it: no temporary image, no
+// second copy. negZ must be legal and must not exchange the face's width and height (E_INVALIDARG).
+HRESULT AssembleCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& faces, TEX_FR_FLAGS negZ, DeviceScratchImage& result) noexcept;
+HRESULT CubeFromCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& image, TEX_FR_FLAGS negZ, DeviceScratchImage& cube) noexcept;
 // array-strip: the array items of `items` stacked top to bottom in one image
 HRESULT AssembleStrip(Device& device, const DeviceScratchImage& items, DeviceScratchImage& result) noexcept;
 // whole images, pairwise, between device-resident images (src[i] into dst[i] at (0, 0); sizes of a pair must agree, formats may differ)

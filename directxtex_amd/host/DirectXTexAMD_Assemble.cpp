@@ -175,6 +175,78 @@ HRESULT CubeFromCross(Device& device, CROSS_KIND kind, const DeviceScratchImage&
     return hr;
 }
 
+namespace
+{
+// a legal flag word that keeps the face's width and height
+bool TurnKeepsSize(TEX_FR_FLAGS f) noexcept { return f != 0 && (uint32_t(f) & ~0x1Bu) == 0 && (uint32_t(f) & 1u) == 0; }
+
+// the w x h cell at (x, y) of `image` as an image of its own: a pointer into it and its pitch
+Image CellOf(const Image& image, size_t x, size_t y, size_t w, size_t h) noexcept
+{
+    Image cell = image;
+    cell.pixels = image.pixels + y * image.rowPitch + x * (BitsPerPixel(image.format) / 8);
+    cell.width = w; cell.height = h;
+    cell.slicePitch = image.rowPitch * h;
+    return cell;
+}
+}
+
+HRESULT AssembleCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& faces, TEX_FR_FLAGS negZ, DeviceScratchImage& result) noexcept
+{
+    const CrossLayout* layout = GetCrossLayout(kind);
+    if (!device) return E_POINTER;
+    if (!layout || !Resident(device, faces) || faces.GetMetadata().arraySize < 6 || faces.GetMetadata().IsVolumemap() || !TurnKeepsSize(negZ)) return E_INVALIDARG;
+    const TexMetadata& f = faces.GetMetadata();
+    HRESULT hr = result.Initialize(device, Texture2D(f.format, f.width * layout->cols, f.height * layout->rows, 1));       // zero-filled: the background
+    if (FAILED(hr)) return hr;
+    try
+    {
+        Batch batch;
+        for (size_t i = 0; i < 5; ++i)
+            batch.Add(*faces.GetImage(0, i, 0), Rect(0, 0, f.width, f.height), *result.GetImage(0, 0, 0), layout->x[i] * f.width, layout->y[i] * f.height);
+        hr = batch.Run(device);
+        if (SUCCEEDED(hr))
+        {
+            const dxtex_image s = ImageOf(*faces.GetImage(0, 5, 0));
+            const dxtex_image d = ImageOf(CellOf(*result.GetImage(0, 0, 0), layout->x[5] * f.width, layout->y[5] * f.height, f.width, f.height));
+            hr = dxtex_flip_rotate_device(device.Get(), &s, &d, 1, uint32_t(negZ));
+        }
+    }
+    catch (const std::bad_alloc&) { hr = E_OUTOFMEMORY; }
+    if (FAILED(hr)) result.Release();
+    return hr;
+}
+
+HRESULT CubeFromCross(Device& device, CROSS_KIND kind, const DeviceScratchImage& image, TEX_FR_FLAGS negZ, DeviceScratchImage& cube) noexcept
+{
+    const CrossLayout* layout = GetCrossLayout(kind);
+    if (!device) return E_POINTER;
+    if (!layout || !Resident(device, image) || image.GetMetadata().IsVolumemap() || !TurnKeepsSize(negZ)) return E_INVALIDARG;
+    const TexMetadata& c = image.GetMetadata();
+    if (!c.width || !c.height || c.width % layout->cols || c.height % layout->rows) return E_INVALIDARG;
+    const size_t w = c.width / layout->cols, h = c.height / layout->rows;
+    TexMetadata m = Texture2D(c.format, w, h, 6);
+    m.miscFlags |= TEX_MISC_TEXTURECUBE;
+    HRESULT hr = cube.Initialize(device, m);
+    if (FAILED(hr)) return hr;
+    try
+    {
+        Batch batch;
+        for (size_t i = 0; i < 5; ++i)
+            batch.Add(*image.GetImage(0, 0, 0), Rect(layout->x[i] * w, layout->y[i] * h, w, h), *cube.GetImage(0, i, 0), 0, 0);
+        hr = batch.Run(device);
+        if (SUCCEEDED(hr))
+        {
+            const dxtex_image s = ImageOf(CellOf(*image.GetImage(0, 0, 0), layout->x[5] * w, layout->y[5] * h, w, h));
+            const dxtex_image d = ImageOf(*cube.GetImage(0, 5, 0));
+            hr = dxtex_flip_rotate_device(device.Get(), &s, &d, 1, uint32_t(negZ));
+        }
+    }
+    catch (const std::bad_alloc&) { hr = E_OUTOFMEMORY; }
+    if (FAILED(hr)) cube.Release();
+    return hr;
+}
+
 HRESULT AssembleStrip(Device& device, const DeviceScratchImage& items, DeviceScratchImage& result) noexcept
 {
     if (!device) return E_POINTER;

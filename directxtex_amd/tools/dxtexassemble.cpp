@@ -9,7 +9,8 @@
 //   cube-from-hc -vc -ht -hs -vs         the reverse: one image cut into the six faces of a cubemap
 //   merge                                rgb of image 1 and a channel of image 2 (-swizzle, default rgbB)
 //   from-mips cube-from-mips             one input per mip level (per face: all levels of +X, then of -X, ...)
-//   Not here: gif (WIC), v-cross-fnz and cube-from-vc-fnz (they need FlipRotate, which is WIC-only in the reference).
+//   Not here: gif (WIC); v-cross-fnz and cube-from-vc-fnz, which still print their refusal: the host layer does them (AssembleCross /
+//   CubeFromCross with TEX_FR_ROTATE180 for the -Z face), the commands are not turned on.
 //
 //   -w <n> -h <n> -m <n> -f <format> -if <filter> -srgb -srgbi -srgbo -wrap -mirror -sepalpha -alpha -tonemap -stripmips -swizzle <mask>
 //   -o <file> -y -l -dx10 -fl <level> -nologo -gpu <n> -timing -help
@@ -129,7 +130,7 @@ int Parse(int argc, char** argv, Options& o)
     if (o.command == CMD_GIF) { std::printf("ERROR: gif is not supported (the reference reads animated GIFs through WIC)\n"); return 1; }
     if (o.command == CMD_V_CROSS_FNZ || o.command == CMD_CUBE_FROM_VC_FNZ)
     {
-        std::printf("ERROR: %s is not supported (it needs FlipRotate, which is WIC-only in the reference)\n", argv[1]);
+        std::printf("ERROR: %s is not supported (the host layer's AssembleCross / CubeFromCross with TEX_FR_ROTATE180 do it; the command is not turned on)\n", argv[1]);
         return 1;
     }
     for (int i = 2; i < argc; ++i)

@@ -1,10 +1,10 @@
 // dxtexconv - a texconv-style batch converter on top of the MI355X host layer (DirectXTexAMD.h): DDS in, DDS out, every
 // image-processing step on the GPU. The pipeline and its order are the reference tool's (Texconv/texconv.cpp): load (:2077-2090)
-// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> resize (:2577-2640) -> swizzle (:2645-2694) -> colour
+// -> decompress (:2325-2480) -> undo premultiplied alpha (:2482-2530) -> flip (:2533-2574) -> resize (:2577-2640) -> swizzle (:2645-2694) -> colour
 // rotation (:2696-2964) -> tone map (:2966-3044) -> normal map (:3047-3098) or convert (:3100-3140) -> colour key (:3134-3191) -> invert Y (:3193-3240) -> reconstruct Z
 // (:3242-3301) -> mipmaps (:3302-3460) -> alpha-coverage preservation (:3462-3500) -> premultiply alpha (:3502-3545) -> compress
-// (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (flips and
-// rotations, -dxt5nm / -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
+// (:3547-3735) -> alpha mode (:3738-3766) -> save (:3858-3878). Option names are texconv's; what has no GPU implementation here (-dxt5nm /
+// -dxt5rxgb, WIC codecs, dithered conversion) is refused, not approximated.
 //
 //   dxtexconv [options] -o <out.dds | output directory> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr | in.tif>...
 //                          (-ft hdr | tga | ppm | pfm | png | exr | tif: Radiance / TGA / portable pixmap / PNG / OpenEXR / TIFF output of level 0)
@@ -25,6 +25,8 @@
 //                          colour rotation; HDR10to709 and P3D65to709 convert to R16G16B16A16_FLOAT first, as texconv does
 //     --paper-white-nits <n>   the level of linear 1.0 for the HDR10 operations, in (0, 10000], default 200
 //                          only under texconv's long names (with one or two dashes): its short -rotatecolor and -nits stay refused
+//     --horizontal-flip --vertical-flip   mirror the whole texture (every item, mip and slice) left-right / top-bottom, after the
+//                          un-premultiply and before the resize; under the long names only: the short -hflip and -vflip stay refused
 //     -dword -badtails -permissive -ignoremips -xlum            DDS reader tolerances (DDS_FLAGS)
 //     -dx10 -dx9           force the 'DX10' header (+ alpha mode) / a Direct3D 9 file        -tga20   TGA output with the 2.0 extension area
 //     -px <s> -sx <s> -l   output name prefix / suffix, lower case    -y   overwrite    -info (print what the files hold, no GPU)    -timing -nologo -gpu <n> | -gpus <a,b,...> (files dealt out over the GPUs)
@@ -82,6 +84,7 @@ struct Options
     uint32_t colorKeyValue = 0;         // -c: 0x00RRGGBB
     uint32_t rotateColor = 0;           // --rotate-color: TEX_ROTATE_COLOR, 0 = none
     float paperWhiteNits = 200.f;       // --paper-white-nits
+    bool hflip = false, vflip = false;  // --horizontal-flip, --vertical-flip
     std::vector<int> gpus;              // one worker (own Device, own host thread) per entry; input i goes to worker i mod n
     size_t overlap = 2;                 // workers per listed GPU: file k + 1 is read, decoded and uploaded while file k's kernels run
     std::string prefix, suffix, out;
@@ -127,6 +130,7 @@ int usage()
                          "                 [-pmalpha|-alpha] [-keepcoverage REF] [-at T] [-bc qxdu] [-x2bias] [-sepalpha] [-nmap <l|r|g|b|a>[m|u|v][i][o]] [-nmapamp W]\n"
                          "                 [-swizzle MASK] [-tonemap] [-c RRGGBB] [-inverty] [-reconstructz]\n"
                          "                 [--rotate-color 709toHDR10|HDR10to709|709to2020|2020to709|P3D65toHDR10|P3D65to2020|709toP3D65|P3D65to709] [--paper-white-nits N]\n"
+                         "                 [--horizontal-flip] [--vertical-flip]\n"
                          "                 [-dword] [-badtails] [-permissive]\n"
                          "                 [-ignoremips] [-xlum] [-dx10|-dx9] [-px S] [-sx S] [-l] [-y] [-timing] [-nologo] [-gpu N | -gpus A,B,...] [-overlap N]\n"
                          "                 [-ft dds|hdr|tga|ppm|pfm|png|exr|tif] [-ignoresrgb] -o <out | dir> <in.dds | in.hdr | in.tga | in.ppm | in.pfm | in.phm | in.png | in.jpg | in.exr | in.tif>...\n");
@@ -225,6 +229,8 @@ bool Parse(int argc, char** argv, Options& o)
             if (std::sscanf(v, "%f", &o.paperWhiteNits) != 1) { std::fprintf(stderr, "Invalid value specified with -nits (%s)\n", v); return false; }
             if (!(o.paperWhiteNits > 0.f && o.paperWhiteNits <= 10000.f)) { std::fprintf(stderr, "-nits (%s) parameter must be between 0 and 10000\n", v); return false; }
         }
+        else if (a == "-horizontal-flip") o.hflip = true;           // texconv.cpp:289, :318; the short -hflip and -vflip are not accepted
+        else if (a == "-vertical-flip") o.vflip = true;
         else if (a == "-tonemap") o.tonemap = true;
         else if (a == "-inverty" || a == "-invert-y") o.invertY = true;
         else if (a == "-reconstructz" || a == "-reconstruct-z") o.reconstructZ = true;
@@ -390,6 +396,15 @@ void ConvertOne(Device& dev, const Options& o, const std::string& inFile, const 
             image = std::move(t);
             haveOriginal = false;
         }
+    }
+
+    // --- flip (texconv.cpp:2533-2574): every item, mip and slice of the texture; ends any hand-through of the blocks, as cimage.reset() there
+    if (o.hflip || o.vflip)
+    {
+        DeviceScratchImage t;
+        check("fliprotate", FlipRotate(dev, image, TEX_FR_FLAGS((o.hflip ? TEX_FR_FLIP_HORIZONTAL : 0u) | (o.vflip ? TEX_FR_FLIP_VERTICAL : 0u)), t));
+        keep(t);
+        haveOriginal = false;
     }
 
     // --- resize: level 0 of every item / slice; the result has one level (DirectXTexResize.cpp:942-1103)

@@ -29,6 +29,7 @@
  *   texdiag's Analyze / AnalyzeBC / Difference Texdiag/texdiag.cpp:698-1320    dxtex_analyze / dxtex_analyze_bc / dxtex_difference
  *   CopyRectangle                              DirectXTexMisc.cpp:275-381      dxtex_copy_rectangle / dxtex_copy_rectangles_device
  *   texassemble's merge lambda                 Texassemble/texassemble.cpp:2236-2268  dxtex_merge_image
+ *   FlipRotate                                 DirectXTexFlipRotate.cpp:185-381 dxtex_flip_rotate / dxtex_flip_rotate_device
  *   ConvertToSinglePlane                       DirectXTexConvert.cpp:4912-5077, :5411-5523  dxtex_convert_to_single_plane[_device]
  *   LoadFromHDRMemory's float pass,            DirectXTexHDR.cpp:887-901, :328-407  dxtex_rgbe_decode / dxtex_rgbe_encode
  *     FloatToRGBE / HalfToRGBE
@@ -788,6 +789,42 @@ dxtex_hresult dxtex_merge_image(dxtex_ctx* ctx, const dxtex_image* a, const dxte
                                 const uint32_t zero[4], const uint32_t one[4]);
 dxtex_hresult dxtex_merge_image_device(dxtex_ctx* ctx, const dxtex_image* a, const dxtex_image* b, const dxtex_image* dst, const uint32_t permute[4],
                                        const uint32_t zero[4], const uint32_t one[4]);
+
+/* ---- FlipRotate (DirectXTex.h:723-737, DirectXTexFlipRotate.cpp) ----------------------------------------------------------------------- */
+
+/* TEX_FR_FLAGS with the reference's values. Legal: flags != 0 && (flags & ~0x1B) == 0, fifteen values; anything else is E_INVALIDARG. */
+#define DXTEX_FR_ROTATE0          0x0u
+#define DXTEX_FR_ROTATE90         0x1u
+#define DXTEX_FR_ROTATE180        0x2u
+#define DXTEX_FR_ROTATE270        0x3u
+#define DXTEX_FR_FLIP_HORIZONTAL  0x08u
+#define DXTEX_FR_FLIP_VERTICAL    0x10u
+
+/* `src` turned CLOCKWISE by the angle, then mirrored left-right if FLIP_HORIZONTAL is set, then mirrored top-bottom if FLIP_VERTICAL is
+ * set, into `dst`. With src as [h][w] texels:  out = rot90(src, k = -(flags & 3));  H: out = out[:, ::-1];  V: out = out[::-1].
+ * Per texel (xd, yd) of the W x H result (W, H = h, w for 90 / 270, else w, h): x1 = H-flag ? W - 1 - xd : xd, y1 = V-flag ? H - 1 - yd : yd;
+ * the source texel is (x1, y1) for 0, (y1, h - 1 - x1) for 90, (w - 1 - x1, h - 1 - y1) for 180, (w - 1 - y1, x1) for 270. The fifteen flag
+ * words are the eight symmetries of the rectangle: {2, 24} {1, 27} {3, 25} {8, 18} {16, 10} {9, 19} {11, 17} and {26}, the identity.
+ * dst has src's format; its size is src's, or the swapped one for 90 / 270. Its rowPitch may be any value at least as large as the row; its
+ * row padding and everything outside it are not written, so a destination may be a cell of a larger image (a pointer into it and its pitch).
+ * Formats: texels move as bytes and are never loaded or stored through a float row. Every format this library knows whose element is one
+ * texel of 1, 2, 4, 8, 12 or 16 bytes is taken, depth and integer formats included. DXTEX_E_NOT_SUPPORTED for compressed formats (as the
+ * reference), planar, palettised and typeless formats, the two-texel packed formats and R1_UNORM, and a value that names no format.
+ * DEPARTURES from the reference, stated: (1) it hands the flag word to WIC, whose documentation does not say whether a flip combined with a
+ * rotation is applied before or after it; its tools never combine them, so the order above is this library's and nothing can check it.
+ * (2) It sends formats WIC lacks through R32G32B32A32_FLOAT (or half) and back, which is not the identity (R32_UINT above 2^24); here bits
+ * are kept. (3) It would convert the packed formats; here they are refused.
+ * HRESULTs, in this order: E_POINTER for null pixels; E_INVALIDARG for illegal flags; DXTEX_E_NOT_SUPPORTED for the formats above; E_FAIL
+ * for a format or size mismatch between a pair (the reference's :354-381); E_INVALIDARG for a rowPitch below its row's bytes or a side
+ * above 2^31 - 1, and where the bytes read and the bytes written overlap.
+ * dxtex_flip_rotate: host pointers, through the context's staging; uploads the source rows' texels and downloads the result rows' texels only.
+ * dxtex_flip_rotate_device: `count` independent pairs on device memory, asynchronous on the context's stream; all are checked before
+ * anything is queued. ONE kernel launch per route per 32 images (the jobs travel in the kernel's argument block): the four symmetries
+ * that keep width and height are row moves, 16 bytes a lane where both first-row addresses, both pitches and the row's byte count are
+ * multiples of 16 (and the texel is not 12 bytes), a texel a lane otherwise; the four that exchange them go through a padded LDS tile with
+ * both global sides coalesced. Pairs of one call must not write bytes another one of the call reads or writes. */
+dxtex_hresult dxtex_flip_rotate(dxtex_ctx* ctx, const dxtex_image* src, const dxtex_image* dst, uint32_t flags);
+dxtex_hresult dxtex_flip_rotate_device(dxtex_ctx* ctx, const dxtex_image* srcs, const dxtex_image* dsts, size_t count, uint32_t flags);
 
 /* ---- ConvertToSinglePlane (DirectXTexConvert.cpp:4912-5077, :5411-5523) ------------------------------------------------------------- */
 
